@@ -14,12 +14,22 @@ Inference has no exchange step, so N ranks are N replicas on disjoint batches (w
 data-parallel TRAINING step (B=32/GPU, RCCL all-reduce of the flat head gradient) is timed as well and reported under
 "train_dp" in the same JSON line.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the --steps inference steps and prints ONE JSON line (rank 0) with the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...); everything else is measured only under --full, where the same
+line also carries
   roofline      dominant kernel (the fused ConvFFN, convffn32_kernel): algorithmic FLOPs / HIP-event time per launch, against
                 the 2.5 PFLOP/s dense bf16 peak
+  power         board power of rank 0's GPU inside the timed region
   cpu_baseline  the fp32 CPU oracle (oracle/, "port") timed on this box's host cores on a bounded sample
   surface       the same step through the reference's plugin surface (lerobot_fastvla.FastVLAPolicy.select_action / forward,
                 task strings through the tokenizer), beside the engine-level number
+  train_dp, train_unfrozen, train_unfrozen_tower, other_parity_mode, splice_prefix_cache, cpu_baseline_c1, dist.fv_comm
+                the training legs, the other decoder parity mode, the image-prefix cache (--splice), the C1 protocol and the N > 1
+                live check of the library's own communicator
+Fields of legs that did not run are null.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (the actions, (batch, 14) float32) as
+DIR/actions.npy.  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -103,7 +113,15 @@ def parse():
     ap.add_argument("--profile-steps", type=int, default=2)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL over xGMI; gloo only to "
                                                       "rehearse the multi-process path on a one-GPU box)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: per-kernel profile pass and roofline, board power, training legs, plugin surface, "
+                         "other parity mode, prefix cache (--splice), CPU baselines, N > 1 communicator check (the --no-* options still select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's actions to DIR/actions.npy (float32; rank 0)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -299,7 +317,7 @@ def main():
             return {"board_w_mean": round(sum(sm) / len(sm), 1), "board_w_median": round(sm[len(sm) // 2], 1), "board_w_max": round(sm[-1], 1),
                     "cap_w": self.cap, "samples": len(sm), "source": "amdgpu hwmon power1_input of rank 0's GPU, sampled every 20 ms inside the timed region"}
 
-    power = PowerSampler() if rank == 0 else None
+    power = PowerSampler() if rank == 0 and args.full else None
 
     def timed(fn, steps, warmup, sampler=None):
         for _ in range(warmup):
@@ -323,89 +341,102 @@ def main():
             el = float(tt)
         return el
 
-    el = timed(step_infer, args.steps, args.warmup, power)
+    last = {}
+
+    def step_infer_timed():
+        last["actions"] = step_infer()
+
+    el = timed(step_infer_timed, args.steps, args.warmup, power)
     power_info = power.last if power else None
     ms_per_step = 1e3 * el / args.steps
     value = world * args.steps / el
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "actions.npy"), last["actions"].detach().to(torch.float32).cpu().numpy())
+    del last
 
-    # ---- per-kernel-family HIP-event pass (same work, right after the timed region, on the same stream)
-    # kernels are timed one at a time here: the decoder/tower stream overlap of the timed region would make concurrent
-    # kernels share the chip and inflate each other's durations (the committed rocprofv3 stats use FASTVLA_OVERLAP=0 too)
-    overlap = eng.overlap_streams
-    eng.overlap_streams = False
-    eng.profile(True)
-    for _ in range(args.profile_steps):
-        step_infer()
-    torch.cuda.synchronize()
-    fams, shapes = eng.profile_read()
-    eng.profile(False)
-    eng.overlap_streams = overlap
-    ps = args.profile_steps
-    gem = fams["gemm"]
-    gemm_tflops = gem["flops"] / (gem["ms"] * 1e-3) / 1e12 if gem["ms"] > 0 else 0.0
-    total_flops = sum(f["flops"] for f in fams.values()) / ps
-    # the MFMA family is two kernels: the fused ConvFFN (epi 6: 4*M*C*4C flop) and the plain GEMM (2*M*N*|K|)
-    def _fl(r):
-        return (4.0 if r["epi"] == 6 else 2.0) * r["m"] * r["n"] * abs(r["k"]) * r["launches"]
-    ffn_name = "convffn32_kernel (fused fc1+GELU+fc2, bf16 MFMA 32x32x16)"
-    # `roofline` is ONE kernel as rocprofv3 lists it: the fused ConvFFN is a template with one instance per channel width, each its own
-    # row of the --stats table, so the dominant kernel is the instance with the most time (C = 384 at the 0.5B tower), not the three
-    # pooled; the pooled, launch-weighted figure of rounds 1-2 stays beside it as "family"
-    ffn_rows = [r for r in shapes if r["epi"] == 6]
-    groups = {f"{ffn_name.split(' ')[0]}<C={c}> {ffn_name.split(' ', 1)[1]}": [r for r in ffn_rows if r["n"] == c] for c in sorted({r["n"] for r in ffn_rows})}
-    groups["gemm_kernel (bf16 MFMA 16x16x32, fp32 acc)"] = [r for r in shapes if r["epi"] != 6]
-    gstat = {k: dict(ms=sum(r["ms"] for r in v), flops=sum(_fl(r) for r in v), n=sum(r["launches"] for r in v))
-             for k, v in groups.items() if v}
-    dom = max((k for k in gstat if not k.startswith("gemm_kernel")), key=lambda k: gstat[k]["ms"], default=None)
-    if dom is None or gstat["gemm_kernel (bf16 MFMA 16x16x32, fp32 acc)"]["ms"] > sum(v["ms"] for k, v in gstat.items() if not k.startswith("gemm_kernel")):
-        dom = "gemm_kernel (bf16 MFMA 16x16x32, fp32 acc)"
-    dg = gstat[dom]
-    dom_tflops = dg["flops"] / (dg["ms"] * 1e-3) / 1e12
-    fam = dict(ms=sum(r["ms"] for r in ffn_rows), flops=sum(_fl(r) for r in ffn_rows), n=sum(r["launches"] for r in ffn_rows)) if ffn_rows else None
-    traffic = None
-    traffic_src = None
-    pmc = ROOT / "profiles" / "pmc_traffic.json"  # HBM bytes per launch from rocprofv3 --pmc passes (collected offline)
-    if pmc.is_file():
-        try:
-            traffic = json.loads(pmc.read_text()).get(dom.split(" ")[0].replace("<C=", "<"))   # per template instance (tools/pmc_traffic.py)
-            traffic_src = "profiles/pmc_traffic.json: rocprofv3 --pmc passes of an EARLIER run of this command (tools/pmc_traffic.py), not a quantity of this run"
-        except Exception:
-            traffic = None
-    roofline = {
-        "bound": "mfma", "kernel": dom,
-        "achieved": round(dom_tflops, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-        "frac": round(dom_tflops / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
-        # both readings at the TOP level so rounds stay comparable: `frac_instance` = this line's `frac` (the dominant template instance as
-        # rocprofv3 lists it; rounds 3+), `frac_family` = the fused ConvFFN over all channel widths, launch-weighted (what rounds 1-2 called frac)
-        "frac_instance": round(dom_tflops / MFMA_PEAK_TFLOPS, 4),
-        "frac_family": None if not fam else round(fam["flops"] / (fam["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-        "practical": {"peak": 1860.0 if "32x32x16" in dom else 2050.0, "frac": round(dom_tflops / (1860.0 if "32x32x16" in dom else 2050.0), 4), "unit": "TFLOP/s",
-                      "source": "tools/mfma_ceiling.hip measured on this chip in round 2: the bare MFMA loop of this kernel's shape on random bf16 operands held in registers, "
-                                "i.e. what the board's 1.4 kW cap buys with nothing else switching (DESIGN.md 5.0, 5.5); a constant of the repo, not a quantity of this run"},
-        "launches_per_step": dg["n"] // ps, "kernel_ms_per_step": round(dg["ms"] / ps, 3),
-        "kernel_flops_per_launch": dg["flops"] / dg["n"], "kernel_avg_launch_ms": round(dg["ms"] / dg["n"], 4),
-        "family": None if not fam else {"kernels": ffn_name + ", all channel widths, launch-weighted (the figure rounds 1-2 reported as roofline)",
-                                        "achieved": round(fam["flops"] / (fam["ms"] * 1e-3) / 1e12, 2),
-                                        "frac": round(fam["flops"] / (fam["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                                        "launches_per_step": fam["n"] // ps, "ms_per_step": round(fam["ms"] / ps, 3),
-                                        "avg_launch_ms": round(fam["ms"] / fam["n"], 4),
-                                        "per_width": {k.split(" ")[0]: {"frac": round(v["flops"] / (v["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                                                                        "ms_per_step": round(v["ms"] / ps, 3), "avg_launch_ms": round(v["ms"] / v["n"], 4)}
-                                                      for k, v in gstat.items() if not k.startswith("gemm_kernel")}},
-        "all_mfma_kernels": {"achieved": round(gemm_tflops, 2), "frac": round(gemm_tflops / MFMA_PEAK_TFLOPS, 4),
-                             "ms_per_step": round(gem["ms"] / ps, 3), "flops_per_step": gem["flops"] / ps},
-        "step_achieved": round(total_flops / (ms_per_step * 1e-3) / 1e12, 2),
-        "step_frac": round(total_flops / (ms_per_step * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-        "source": f"hipEvents around every launch over {ps} steps after the timed region (stream overlap off); algorithmic flops "
-                  "(2MNK per GEMM, 4*M*C*4C per fused ConvFFN; split-bf16 passes not double-counted)",
-    }
-    families = {k: {"ms_per_step": round(v["ms"] / ps, 3), "launches": v["launches"] // ps,
-                    "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2),
-                    "gbs": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)} for k, v in fams.items() if v["launches"]}
-    top = sorted(shapes, key=lambda r: -r["ms"])[:30]
-    gemm_shapes = [{"mnk": [r["m"], r["n"], r["k"]], "epi": r["epi"], "ms_per_step": round(r["ms"] / ps, 3),
-                    "n": r["launches"] // ps,
-                    "tflops": round(_fl(r) / max(r["ms"], 1e-9) / 1e9, 1)} for r in top]
+    # ---- --full only: per-kernel-family HIP-event pass (same work, right after the timed region, on the same stream)
+    roofline = families = gemm_shapes = None
+    total_flops = 0.0
+    if args.full:
+        # kernels are timed one at a time here: the decoder/tower stream overlap of the timed region would make concurrent
+        # kernels share the chip and inflate each other's durations (the committed rocprofv3 stats use FASTVLA_OVERLAP=0 too)
+        overlap = eng.overlap_streams
+        eng.overlap_streams = False
+        eng.profile(True)
+        for _ in range(args.profile_steps):
+            step_infer()
+        torch.cuda.synchronize()
+        fams, shapes = eng.profile_read()
+        eng.profile(False)
+        eng.overlap_streams = overlap
+        ps = args.profile_steps
+        gem = fams["gemm"]
+        gemm_tflops = gem["flops"] / (gem["ms"] * 1e-3) / 1e12 if gem["ms"] > 0 else 0.0
+        total_flops = sum(f["flops"] for f in fams.values()) / ps
+        # the MFMA family is two kernels: the fused ConvFFN (epi 6: 4*M*C*4C flop) and the plain GEMM (2*M*N*|K|)
+        def _fl(r):
+            return (4.0 if r["epi"] == 6 else 2.0) * r["m"] * r["n"] * abs(r["k"]) * r["launches"]
+        ffn_name = "convffn32_kernel (fused fc1+GELU+fc2, bf16 MFMA 32x32x16)"
+        # `roofline` is ONE kernel as rocprofv3 lists it: the fused ConvFFN is a template with one instance per channel width, each its own
+        # row of the --stats table, so the dominant kernel is the instance with the most time (C = 384 at the 0.5B tower), not the three
+        # pooled; the pooled, launch-weighted figure of rounds 1-2 stays beside it as "family"
+        ffn_rows = [r for r in shapes if r["epi"] == 6]
+        groups = {f"{ffn_name.split(' ')[0]}<C={c}> {ffn_name.split(' ', 1)[1]}": [r for r in ffn_rows if r["n"] == c] for c in sorted({r["n"] for r in ffn_rows})}
+        groups["gemm_kernel (bf16 MFMA 16x16x32, fp32 acc)"] = [r for r in shapes if r["epi"] != 6]
+        gstat = {k: dict(ms=sum(r["ms"] for r in v), flops=sum(_fl(r) for r in v), n=sum(r["launches"] for r in v))
+                 for k, v in groups.items() if v}
+        dom = max((k for k in gstat if not k.startswith("gemm_kernel")), key=lambda k: gstat[k]["ms"], default=None)
+        if dom is None or gstat["gemm_kernel (bf16 MFMA 16x16x32, fp32 acc)"]["ms"] > sum(v["ms"] for k, v in gstat.items() if not k.startswith("gemm_kernel")):
+            dom = "gemm_kernel (bf16 MFMA 16x16x32, fp32 acc)"
+        dg = gstat[dom]
+        dom_tflops = dg["flops"] / (dg["ms"] * 1e-3) / 1e12
+        fam = dict(ms=sum(r["ms"] for r in ffn_rows), flops=sum(_fl(r) for r in ffn_rows), n=sum(r["launches"] for r in ffn_rows)) if ffn_rows else None
+        traffic = None
+        traffic_src = None
+        pmc = ROOT / "profiles" / "pmc_traffic.json"  # HBM bytes per launch from rocprofv3 --pmc passes (collected offline)
+        if pmc.is_file():
+            try:
+                traffic = json.loads(pmc.read_text()).get(dom.split(" ")[0].replace("<C=", "<"))   # per template instance (tools/pmc_traffic.py)
+                traffic_src = "profiles/pmc_traffic.json: rocprofv3 --pmc passes of an EARLIER run of this command (tools/pmc_traffic.py), not a quantity of this run"
+            except Exception:
+                traffic = None
+        roofline = {
+            "bound": "mfma", "kernel": dom,
+            "achieved": round(dom_tflops, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(dom_tflops / MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
+            # both readings at the TOP level so rounds stay comparable: `frac_instance` = this line's `frac` (the dominant template instance as
+            # rocprofv3 lists it; rounds 3+), `frac_family` = the fused ConvFFN over all channel widths, launch-weighted (what rounds 1-2 called frac)
+            "frac_instance": round(dom_tflops / MFMA_PEAK_TFLOPS, 4),
+            "frac_family": None if not fam else round(fam["flops"] / (fam["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+            "practical": {"peak": 1860.0 if "32x32x16" in dom else 2050.0, "frac": round(dom_tflops / (1860.0 if "32x32x16" in dom else 2050.0), 4), "unit": "TFLOP/s",
+                          "source": "tools/mfma_ceiling.hip measured on this chip in round 2: the bare MFMA loop of this kernel's shape on random bf16 operands held in registers, "
+                                    "i.e. what the board's 1.4 kW cap buys with nothing else switching (DESIGN.md 5.0, 5.5); a constant of the repo, not a quantity of this run"},
+            "launches_per_step": dg["n"] // ps, "kernel_ms_per_step": round(dg["ms"] / ps, 3),
+            "kernel_flops_per_launch": dg["flops"] / dg["n"], "kernel_avg_launch_ms": round(dg["ms"] / dg["n"], 4),
+            "family": None if not fam else {"kernels": ffn_name + ", all channel widths, launch-weighted (the figure rounds 1-2 reported as roofline)",
+                                            "achieved": round(fam["flops"] / (fam["ms"] * 1e-3) / 1e12, 2),
+                                            "frac": round(fam["flops"] / (fam["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                                            "launches_per_step": fam["n"] // ps, "ms_per_step": round(fam["ms"] / ps, 3),
+                                            "avg_launch_ms": round(fam["ms"] / fam["n"], 4),
+                                            "per_width": {k.split(" ")[0]: {"frac": round(v["flops"] / (v["ms"] * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                                                                            "ms_per_step": round(v["ms"] / ps, 3), "avg_launch_ms": round(v["ms"] / v["n"], 4)}
+                                                          for k, v in gstat.items() if not k.startswith("gemm_kernel")}},
+            "all_mfma_kernels": {"achieved": round(gemm_tflops, 2), "frac": round(gemm_tflops / MFMA_PEAK_TFLOPS, 4),
+                                 "ms_per_step": round(gem["ms"] / ps, 3), "flops_per_step": gem["flops"] / ps},
+            "step_achieved": round(total_flops / (ms_per_step * 1e-3) / 1e12, 2),
+            "step_frac": round(total_flops / (ms_per_step * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+            "source": f"hipEvents around every launch over {ps} steps after the timed region (stream overlap off); algorithmic flops "
+                      "(2MNK per GEMM, 4*M*C*4C per fused ConvFFN; split-bf16 passes not double-counted)",
+        }
+        families = {k: {"ms_per_step": round(v["ms"] / ps, 3), "launches": v["launches"] // ps,
+                        "tflops": round(v["flops"] / max(v["ms"], 1e-9) / 1e9, 2),
+                        "gbs": round(v["bytes"] / max(v["ms"], 1e-9) / 1e6, 1)} for k, v in fams.items() if v["launches"]}
+        top = sorted(shapes, key=lambda r: -r["ms"])[:30]
+        gemm_shapes = [{"mnk": [r["m"], r["n"], r["k"]], "epi": r["epi"], "ms_per_step": round(r["ms"] / ps, 3),
+                        "n": r["launches"] // ps,
+                        "tflops": round(_fl(r) / max(r["ms"], 1e-9) / 1e9, 1)} for r in top]
 
     # ---- the line, as a closure over everything measured so far: the legs below fill their own fields in.  At N > 1 a watchdog bounds them -- whatever a
     # secondary leg does on hardware nobody has run it on yet (a stalled collective, one rank failing alone), the headline of a scaling run still gets printed.
@@ -441,7 +472,7 @@ def main():
         print(json.dumps(out), flush=True)
 
     watchdog = None
-    if world > 1:
+    if world > 1 and args.full:
         def on_deadline():
             dist_info["deadline_hit"] = True
             dist_info["deadline_s"] = args.secondary_deadline
@@ -464,7 +495,7 @@ def main():
     # Pipelined as vla_fastvlm.training.Trainer runs it: the frozen backbone forward of batch k+1 is enqueued between the
     # START of batch k's gradient all-reduce (side stream, RCCL over xGMI) and the optimiser kernel that needs its result,
     # so the collective runs underneath ~30 ms of tower kernels.  One timed step = one backbone forward + one head step.
-    if not args.no_train:
+    if args.full and not args.no_train:
         from vla_fastvlm.training.dp import GradExchange
         Bt = args.train_batch
         m_buf, v_buf = torch.zeros_like(flat), torch.zeros_like(flat)
@@ -533,7 +564,7 @@ def main():
     # kept + MSE + backward over 494 M parameters (dgrad / wgrad on the forward's GEMM kernels, split-bf16 gradient operands) + clip + AdamW +
     # bf16 operand refresh.  Under N > 1 the gradient travels per bucket (one decoder layer = 60 MB) on a side stream while the backward
     # pass is still running.  Its own roofline fraction: algorithmic flops (tower + 3 x (projector + decoder GEMMs) + attention fwd/bwd).
-    if not args.no_train_unfrozen and (world == 1 or not args.no_train_unfrozen_dp) and args.llm_precision == 1 and model.llm.head_dim >= 64 and not big:
+    if args.full and not args.no_train_unfrozen and (world == 1 or not args.no_train_unfrozen_dp) and args.llm_precision == 1 and model.llm.head_dim >= 64 and not big:
         from vla_fastvlm.training.dp import BucketedGradExchange
         Bu = min(args.unfrozen_batch, B)
         try:
@@ -618,7 +649,7 @@ def main():
     # backward kernels) + clip + AdamW over 494 M + 125 M parameters + refresh of every packed operand image.  Algorithmic flops: 3 x (tower + projector + decoder
     # GEMMs) + attention fwd/bwd (the recomputed fc1 of every ConvFFN is executed, not counted).
     run_tower_leg = train_unfrozen is not None and "error" not in train_unfrozen and not args.no_train_tower
-    if world > 1 and not args.no_train_unfrozen and not args.no_train_unfrozen_dp:
+    if world > 1 and args.full and not args.no_train_unfrozen and not args.no_train_unfrozen_dp:
         run_tower_leg = ranks_agree(run_tower_leg)      # the previous leg may have failed on one rank only
     if run_tower_leg:
         try:
@@ -692,7 +723,7 @@ def main():
     # Python glue, tokenisation, the action deque and forward()'s `.item()` are inside these numbers.  The policy drives the SAME
     # engine (frozen weights are not loaded twice); its head parameters are its own nn.Parameters.
     surface = None
-    if not args.no_surface and not args.splice and world == 1:
+    if args.full and not args.no_surface and not args.splice and world == 1:
         from vla_fastvlm.lerobot_fastvla import FastVLAConfig as LRConfig, FastVLAPolicy as LRPolicy
         from vla_fastvlm.lerobot_fastvla._lerobot_compat import FeatureType, PolicyFeature
         feats = {"observation.images.top": PolicyFeature(FeatureType.VISUAL, (3, args.image, args.image)),
@@ -772,7 +803,7 @@ def main():
     # ---- the other decoder parity mode on a second engine (same weights, inputs, head): the opt-in policy 2 trades the decoder's 1e-5
     # for ~5e-4 (batch rel-L2) on the actions; both numbers belong in one line
     alt = None
-    if rank == 0 and world == 1 and not args.no_alt and w is not None and args.llm_precision in (1, 2, 5) and not args.splice:
+    if args.full and rank == 0 and world == 1 and not args.no_alt and w is not None and args.llm_precision in (1, 2, 5) and not args.splice:
         ap_ = {1: 5, 5: 1, 2: 1}[args.llm_precision]
         eng2 = FastVLAEngine(model, state_dim=14, action_dim=14, hidden_dim=1024, fusion_dim=1024, device=dev, max_batch=B, max_text_tokens=T,
                              tower_microbatch=args.microbatch, llm_precision=ap_)
@@ -794,7 +825,7 @@ def main():
     # positions (the timed step above); new frames = tower + prefix pass (image positions, K / V kept) + suffix pass (text
     # positions); cached frames = the suffix pass alone (a repeated frame, or another prompt on the same frame)
     prefix = None
-    if args.splice and args.llm_precision >= 1 and model.llm.head_dim >= 64:
+    if args.full and args.splice and args.llm_precision >= 1 and model.llm.head_dim >= 64:
         holder = {}
 
         def step_new_frames():
@@ -817,7 +848,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N=1 only): the fp32 oracle on a bounded sample of the same workload
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and w is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and w is not None:
         from oracle import fastvit_hd, head as ohead, policy, qwen2
         n = args.cpu_sample
         lc = qwen2.Qwen2Cfg(hidden=model.llm.hidden, layers=model.llm.layers, heads=model.llm.heads, kv_heads=model.llm.kv_heads,
@@ -848,7 +879,7 @@ def main():
     # the result needs, "as_shipped" adds what the reference also computes and drops (full-vocabulary lm_head logits for every
     # token, 25 retained hidden-state tensors, a KV cache).  The GPU path's own C1 step is timed beside it.
     c1 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_c1 and w is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_c1 and w is not None:
         from oracle import fastvit_hd, head as ohead, policy, qwen2
         import statistics
         Bc, Tc = 4, 32
@@ -930,7 +961,7 @@ def main():
     # through fv_allreduce_grads.  Last thing of the run, on a helper thread with a time limit: a failure is recorded, a stall is recorded and the process
     # leaves without joining it; neither costs the line.
     stalled = False
-    if world > 1 and dist_info is not None and not args.no_fv_comm_check:
+    if world > 1 and args.full and dist_info is not None and not args.no_fv_comm_check:
         if args.backend != "nccl" or ndev < world:
             dist_info["fv_comm"] = {"ok": None, "skipped": f"backend {args.backend}, {ndev} device(s) for {world} ranks: RCCL needs one GPU per rank"}
         else:

@@ -376,7 +376,7 @@ def test_bench_gpus2_spawns_two_ranks_and_fills_train_dp():
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--model", "tiny", "--batch", "4",
-                        "--train-batch", "4", "--tokens", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"],
+                        "--train-batch", "4", "--tokens", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -398,7 +398,7 @@ def test_bench_gpus2_unfrozen_legs_exchange_their_buckets():
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--model", "small", "--batch", "4", "--train-batch", "4",
-                        "--unfrozen-batch", "2", "--tokens", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-surface", "--train-unfrozen-dp"],
+                        "--unfrozen-batch", "2", "--tokens", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-surface", "--train-unfrozen-dp", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -426,7 +426,7 @@ def test_bench_gpus2_deadline_prints_the_headline_and_leaves():
     root = Path(__file__).resolve().parent.parent
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--model", "tiny", "--batch", "4", "--train-batch", "4",
-                        "--tokens", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--secondary-deadline", "0.02"],
+                        "--tokens", "16", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--secondary-deadline", "0.02", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -434,6 +434,34 @@ def test_bench_gpus2_deadline_prints_the_headline_and_leaves():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["roofline"] is not None
     assert line["dist"]["deadline_hit"] is True and line["dist"]["world_size"] == 2
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_actions(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline fields only (every secondary leg null), the timed step
+    count as asked, and the last timed step's actions as DIR/actions.npy (float32, (batch, 14))."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    import numpy as np
+    root = Path(__file__).resolve().parent.parent
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--model", "tiny", "--batch", "4", "--tokens", "16", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert abs(line["ms_per_step"] - 1e3 / line["value"]) <= 1e-2 * line["ms_per_step"] + 1e-3
+    assert line["unit"] == "steps/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    for leg in ("roofline", "power", "cpu_baseline", "cpu_baseline_c1", "train_dp", "train_unfrozen", "train_unfrozen_tower", "surface",
+                "other_parity_mode", "families", "gemm_shapes"):
+        assert line[leg] is None, leg
+    a = np.load(out / "actions.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 14) and np.isfinite(a).all() and np.abs(a).max() > 0
 
 
 def test_image_prefix_cache_in_the_backbone():

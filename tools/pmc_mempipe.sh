@@ -12,7 +12,7 @@ i=0
 # hardware"), and a refused configuration leaves rocprofv3 hanging after its abort -- hence the timeout on every pass
 for group in "TA_TA_BUSY_sum" "TA_ADDR_STALLED_BY_TC_CYCLES_sum" "TCP_PENDING_STALL_CYCLES_sum" "TCC_MISS" "TCC_HIT"; do
   i=$((i+1))
-  timeout -k 5 150 rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OUT/g$i" -- python3 "$ROOT/bench.py" --steps 2 --warmup 1 --profile-steps 1 --no-train --no-cpu-baseline > /dev/null 2> "$OUT/g$i.err" || echo "group $i failed"
+  timeout -k 5 150 rocprofv3 --pmc $group --kernel-trace --output-format csv -d "$OUT/g$i" -- python3 "$ROOT/bench.py" --full --steps 2 --warmup 1 --profile-steps 1 --no-train --no-cpu-baseline > /dev/null 2> "$OUT/g$i.err" || echo "group $i failed"
   python3 - "$OUT/g$i" "$OUT/g$i.csv" <<'PY'
 import csv, glob, sys, collections
 src, dst = sys.argv[1], sys.argv[2]
