@@ -337,6 +337,38 @@ int fv_train_tower_read_unit(fv_handle* h, int unit, int B, const void* tws, siz
 int fv_train_tower_unit(fv_handle* h, int unit, const void* x_in, const float* g_out, float gscale, int B, void* tws, size_t tws_bytes, void* y_out, float* g_in,
                         float* flat_grads, fv_stream s);
 
+/* ---- LoRA mode of the slice above (csrc/lora_path.inc, csrc/lora_kernels.hip).  The reference has no adapter mode: this extends its one knob
+ * (fastvla/configuration_fastvla.py:23 `freeze_backbone`) and its step body (training/trainer.py:60-66,171-182: clip_grad_norm_ + AdamW over the parameters
+ * with requires_grad) to the usual way a VLM of this size is fine-tuned: the decoder's matrices stay FROZEN in the fp32 master and every target matrix runs as
+ *     W' = W0 + s * B @ A        s = alpha / rank,  A (rank x in),  B (out x rank)                   (PEFT's merged LoRA, no dropout)
+ * while the action expert and the mm_projector train in full.  The TRAINABLE parameters live in a flat fp32 buffer of their own (gradients and Adam's m / v
+ * mirror THAT buffer; the full-size m / v are never needed):
+ *     [ action expert | projector | layer 0 adapters .. layer L-1 adapters ]
+ * head and projector at the offsets fv_train_layout gives them (the two buffers share their front), adapters per LOGICAL matrix in PEFT's names
+ * ("model.layers.{l}.self_attn.q_proj.lora_A.weight" (rank x in), "...lora_B.weight" (out x rank), "...mlp.gate_proj...", ...), plain row-major.
+ * One step:  fv_train_forward_backward (unchanged: the full dW' into the full gradient buffer)  ->  fv_train_lora_project  ->  all-reduce + ONE
+ * fv_adamw_clip_step over the trainable buffer (its clip norm is over exactly the trainable tensors)  ->  fv_train_lora_commit.
+ * All four calls below that take a stream are asynchronous on it and allocate nothing. */
+enum fv_lora_target { FV_LORA_Q = 1, FV_LORA_K = 2, FV_LORA_V = 4, FV_LORA_O = 8, FV_LORA_GATE = 16, FV_LORA_UP = 32, FV_LORA_DOWN = 64, FV_LORA_ALL = 127 };
+/* after fv_train_begin.  rank 1 .. 64, alpha > 0, target_mask a non-empty set of fv_lora_target bits (FV_ERR_ARG otherwise); FV_ERR_UNSUPPORTED after
+ * fv_train_tower_begin (tower adapters do not exist; fv_train_tower_begin refuses after this call in turn).  Allocates the descriptor tables and the
+ * projection's scratch once; a second call with the same arguments is a no-op, with others FV_ERR_STATE. */
+int fv_train_lora_begin(fv_handle* h, int rank, float alpha, int target_mask);
+/* the trainable buffer's tensors (packing 0 throughout; bucket 0 head, 1 projector, 3 + l the adapters of layer l).  out may be NULL (sizes only). */
+int fv_train_lora_layout(fv_handle* h, fv_train_tensor* out, int max_tensors, int* n_tensors, int64_t* total_numel);
+/* lora_grads (trainable layout) <- the full gradient buffer fv_train_forward_backward filled: head and projector gradients copied, and for every adapted matrix
+ *     dA = s * B^T @ dW'        dB = s * dW' @ A^T
+ * from ONE read of dW' (ranks above 32: two), in fp32 on the f32-input matrix core, summed in a fixed order (bit-reproducible).  The loss scale dW' carries
+ * passes straight through (fv_adamw_clip_step's grad_scale removes it as in the full mode). */
+int fv_train_lora_project(fv_handle* h, const float* flat_grads_full, const float* lora_params, float* lora_grads, fv_stream s);
+/* fv_train_commit in LoRA mode: the operand images of every adapted matrix from W0 + s * B @ A (evaluated in fp32, then rounded as fv_train_commit rounds W0),
+ * every other tensor as fv_train_commit.  Head and projector are taken from lora_params: the master's head | projector FRONT is overwritten with theirs (that is
+ * where fv_train_forward_backward reads the head); nothing else of the master is written -- W0 stays as it is. */
+int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream s);
+/* W0 += s * B @ A into the master, for every adapted matrix (and its front <- lora_params' front): bit for bit the fp32 values fv_train_lora_commit rounds, so
+ * fv_train_commit on the merged master builds the same operand images.  For exporting a plain checkpoint; the adapters are not reset. */
+int fv_train_lora_merge(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream s);
+
 /* ---- optional per-kernel-family HIP-event timing (bench.py roofline numbers) ------------------------------------- */
 enum fv_family { FV_FAM_GEMM = 0, FV_FAM_DWCONV, FV_FAM_STEM, FV_FAM_ATTN, FV_FAM_NORM, FV_FAM_ELT, FV_FAM_HEAD, FV_FAM_COUNT };
 typedef struct fv_profile_entry { double ms, flops, bytes; int64_t launches; } fv_profile_entry;

@@ -1,0 +1,178 @@
+"""Full fine-tuning step against the LoRA step of the unfrozen decoder, same process, same inputs, alternating windows -- and the LoRA kernels alone:
+    python tools/lora_bench.py [--model fastvlm-0.5b] [--batch 32] [--tokens 64] [--rank 16] [--steps 6] [--rounds 3] [--out FILE.json]
+full step = fv_train_forward_backward + fv_adamw_clip_step over the whole master + fv_train_commit               (tools/train_unfrozen_bench.py --no-tower)
+LoRA step = fv_train_forward_backward + fv_train_lora_project + fv_adamw_clip_step over the trainable buffer + fv_train_lora_commit
+The frozen tower runs once, outside the windows (it is the same work in both modes).  Times: host clock around windows that end in a device synchronise;
+kernels alone: device events around repeated launches.  GB/s = the bytes the algorithm needs (computed from the shapes below) over that time.
+Memory: the torch allocator's peak while a mode's buffers are the only ones alive (the library's own allocations -- weights, operand copies -- are the same
+in both modes and not in that figure)."""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (str(ROOT), str(ROOT / "vla-from-fastvlm_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+from fastvla_hip import FastVLAEngine, arch, lora, weights  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="fastvlm-0.5b")
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--tokens", type=int, default=64)
+    ap.add_argument("--rank", type=int, default=16)
+    ap.add_argument("--targets", default="all")
+    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/lora_bench.py measures on the GPU: no HIP device visible")
+    dev = torch.device("cuda", 0)
+    model = arch.preset(args.model)
+    B, T = args.batch, args.tokens
+    eng = FastVLAEngine(model, max_batch=B, max_text_tokens=T, llm_precision=1)
+    eng.load_weights(weights.init_backbone(model, seed=1234))
+    eng.train_begin()
+    eng.train_lora_begin(args.rank, None, args.targets)
+    _, total, _ = eng.train_layout()
+    lt, ltotal = eng.train_lora_layout()
+    front = next(t["offset"] for t in lt if ".lora_" in t["name"])
+    g = torch.Generator().manual_seed(1)
+    images = torch.rand(B, 3, 336, 336, generator=g).to(dev)
+    ids = torch.randint(0, 151643, (B, T), generator=g)
+    lens = torch.full((B,), T)
+    states, targets = torch.randn(B, 14, generator=g).to(dev), torch.randn(B, 14, generator=g).to(dev)
+    _, tower_out = eng.vision_forward(eng.preprocess(images), return_tower_out=True)
+    tower_out = tower_out.clone()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base_mem = torch.cuda.memory_allocated()
+
+    flat = torch.zeros(total, device=dev)
+    eng.train_export_params(flat)
+    for k, v in eng.head_views(flat[: eng.head_numel()]).items():
+        v.copy_(torch.randn(v.shape, generator=g) * 0.02 + (1.0 if k in ("state_projection.0.weight", "fusion.1.weight") else 0.0))
+    master0 = flat.clone().cpu()
+    grads = torch.zeros_like(flat)
+    ws = eng.train_workspace(B, T)
+    lflat = torch.zeros(ltotal, device=dev)
+    lflat[:front].copy_(flat[:front])
+    lora.init_adapters(lflat, lt, seed=0)
+    for name, v in lora.adapter_views(lflat, lt).items():      # B != 0: the projection and the commit do real work
+        if name.endswith(".lora_B.weight"):
+            v.copy_((torch.randn(v.shape, generator=g) * 0.01).to(dev))
+    lflat0 = lflat.clone()
+    lg, lm, lv = torch.zeros_like(lflat), torch.zeros_like(lflat), torch.zeros_like(lflat)
+    n = {"full": 0, "lora": 0}
+    hp = dict(lr=1e-5, weight_decay=1e-4, max_grad_norm=1.0, grad_scale=1.0 / eng.train_loss_scale())
+
+    def fb(off):
+        return eng.train_forward_backward(flat, tower_out, ids, lens, states, targets, ws, training=True, dropout_p=0.1, seed=7, offset=off, flat_grads=grads)[1]
+
+    def lora_step():
+        n["lora"] += 1
+        loss = fb(n["lora"])
+        eng.train_lora_project(grads, lflat, lg)
+        eng.adamw_step(lflat, lg, lm, lv, n["lora"], **hp)
+        eng.train_lora_commit(flat, lflat)
+        return loss
+
+    def window(step, k):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(k):
+            loss = step()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / k, float(loss)
+
+    # ---- LoRA mode alone in memory: its peak, then its warm-up
+    window(lora_step, args.warmup)
+    mem_lora = torch.cuda.max_memory_allocated() - base_mem
+    # ---- full mode: Adam's moments over the whole master join
+    torch.cuda.reset_peak_memory_stats()
+    before_full = torch.cuda.memory_allocated()
+    m, v = torch.zeros_like(flat), torch.zeros_like(flat)
+
+    def full_step():
+        n["full"] += 1
+        loss = fb(n["full"])
+        eng.adamw_step(flat, grads, m, v, n["full"], **hp)
+        eng.train_commit(flat)
+        return loss
+
+    def to_full():       # the same starting point for every window of a mode
+        flat.copy_(master0.to(dev)); eng.train_commit(flat)
+
+    def to_lora():
+        flat.copy_(master0.to(dev)); lflat.copy_(lflat0); eng.train_lora_commit(flat, lflat)
+
+    to_full()
+    window(full_step, args.warmup)
+    mem_full = torch.cuda.max_memory_allocated() - base_mem - (lflat.numel() * 4 * 5)     # (the LoRA mode's five small buffers are alive too: taken out)
+    rounds = []
+    for _ in range(args.rounds):       # alternating windows: other work shares the host
+        to_full()
+        f_ms, f_loss = window(full_step, args.steps)
+        to_lora()
+        l_ms, l_loss = window(lora_step, args.steps)
+        rounds.append({"full_ms": round(f_ms, 2), "lora_ms": round(l_ms, 2), "full_loss": f_loss, "lora_loss": l_loss})
+    to_lora()
+
+    # ---- the kernels alone
+    def timed(fn, reps):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    fb(1)
+    shp = lora.logical_shapes(model)
+    names = lora.parse_targets(args.targets)
+    L, r = model.llm.layers, args.rank
+    adapted = L * sum(shp[t][0] * shp[t][1] for t in names)                   # elements of dW' / W0 under adapters
+    adapters = sum(t["numel"] for t in lt if ".lora_" in t["name"])
+    passes = (r + 31) // 32
+    partial = L * sum(((shp[t][0] + 127) // 128) * r * shp[t][1] for t in names)      # dA partial sums: written once, read once
+    proj_bytes = 4.0 * (adapted * passes + 2 * partial + 3 * adapters) + 8.0 * front
+    mats = sum(t["numel"] for t in eng.train_layout()[0] if t["rows"] > 1 and t["bucket"] > 0)
+    vecs = sum(t["numel"] for t in eng.train_layout()[0] if t["rows"] == 1 and t["bucket"] > 0)
+    embed = model.llm.vocab * model.llm.hidden
+    commit_bytes = 4.0 * mats + 2.0 * mats + 2.0 * (mats - embed - model.llm.hidden * model.tower.out_dim) + 8.0 * vecs   # fp32 in, bf16 rows out, one transposed copy out
+    t_proj = timed(lambda: eng.train_lora_project(grads, lflat, lg), args.kernel_reps)
+    t_lcommit = timed(lambda: eng.train_lora_commit(flat, lflat), args.kernel_reps)
+    t_commit = timed(lambda: eng.train_commit(flat), args.kernel_reps)
+    t_merge = timed(lambda: eng.train_lora_merge(grads, lflat), args.kernel_reps)     # (into the gradient buffer: a scratch target of the master's size)
+    t_adam_full = timed(lambda: eng.adamw_step(flat, grads, m, v, 1, **hp), max(3, args.kernel_reps // 4))
+    t_adam_lora = timed(lambda: eng.adamw_step(lflat, lg, lm, lv, 1, **hp), args.kernel_reps)
+    med = lambda xs: sorted(xs)[len(xs) // 2]   # noqa: E731
+    res = {"model": args.model, "batch": B, "tokens": model.tower.num_tokens + T, "rank": r, "targets": list(names), "steps_per_window": args.steps, "rounds": rounds,
+           "full_ms_per_step": med([x["full_ms"] for x in rounds]), "lora_ms_per_step": med([x["lora_ms"] for x in rounds]),
+           "full_numel": total, "trainable_numel": ltotal, "adapter_numel": adapters, "exchange_mb": {"full": round(total * 4 / 1e6, 1), "lora": round(ltotal * 4 / 1e6, 1)},
+           "torch_peak_gb": {"lora": round(mem_lora / 1e9, 2), "full": round(mem_full / 1e9, 2)},
+           "kernels_ms": {"lora_project": round(t_proj, 3), "lora_commit": round(t_lcommit, 3), "commit": round(t_commit, 3), "lora_merge": round(t_merge, 3),
+                          "adamw_full": round(t_adam_full, 3), "adamw_lora": round(t_adam_lora, 3)},
+           "hbm_gb_s": {"lora_project": round(proj_bytes / t_proj / 1e6, 1), "lora_commit": round(commit_bytes / t_lcommit / 1e6, 1), "commit": round(commit_bytes / t_commit / 1e6, 1)},
+           "bytes_gb": {"lora_project": round(proj_bytes / 1e9, 3), "commit": round(commit_bytes / 1e9, 3)}}
+    print(json.dumps(res))
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -87,7 +87,17 @@ struct TowerTrainUnit {   // the backward's own operand images of one tower unit
   bf16_t* stem0_w32 = nullptr;                  // (stem) the first conv as fp16 [C0][32]: taps (bf16-rounded, as the forward's MFMA image holds them) in columns 0 .. 26, zeros behind
   bf16_t *mixF16 = nullptr, *dwF16 = nullptr;   // ... and fp16 Toeplitz tables of the FLIPPED depthwise taps (3x3 mixer / RepCPE 7x7 in mixF16, the ConvFFN's 7x7 in dwF16): dgrad on the marching MFMA kernel
 };
+struct LoraGroup { int m0 = 0, m1 = 0, strip_begin = 0, nstrips = 0, max_in = 0; };   // matrices [m0, m1) of one projection launch (their dA partials share the scratch)
+struct LoraState {   // fv_train_lora_* (lora_path.inc): adapters on the decoder's matrices, the master frozen
+  bool on = false; int rank = 0, mask = 0; float alpha = 0.f, scale = 0.f;
+  fv::LoraMat* mats = nullptr; int nmats = 0;                                // device: every adapted logical matrix
+  fv::LoraCommitDesc* cdesc = nullptr; int cn = 0, ctiles = 0;               // device: the packed tensors that hold them (adapted commit / merge)
+  fv::CommitDesc* rest = nullptr; int rest_n = 0, rest_tiles = 0;            // device: every other tensor (plain commit)
+  float* scratch = nullptr; size_t scratch_floats = 0; std::vector<LoraGroup> groups;
+  int64_t front = 0, total = 0;                                              // head + projector floats in front of the adapters; the trainable buffer's size
+};
 struct TrainState {
+  LoraState lora;
   bool ready = false; std::vector<TrainLayerT> layers; bf16_t *pj2T = nullptr, *pj2T16 = nullptr;
   bool fwd_f16 = false;   // fv_train_set_forward_f16: the TRAINING forward's projections in ONE fp16 pass (half the MFMA work of the split-bf16 form)
   // the tower half (tower_train.inc): its tensors join the flat master when `tower` is set
@@ -1450,4 +1460,5 @@ int fv_allreduce_grads(fv_handle* h, void* comm, float* flat_grads, int64_t n, f
 }  // extern "C"
 
 #include "train_path.inc"
+#include "lora_path.inc"
 #include "tower_train.inc"

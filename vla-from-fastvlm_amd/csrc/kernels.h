@@ -182,6 +182,31 @@ struct CommitDesc {
 };
 int launch_commit(const CommitDesc* desc_dev, int ndesc, int ntiles, const float* flat, int f16_transposes, unsigned* sat, hipStream_t s);
 
+// ---- LoRA mode of backbone training (lora_kernels.hip; fv_train_lora_*) ------------------------------------------------------------------
+// one adapted LOGICAL matrix (q, k, v, o, gate, up or down of one layer): W' = W0 + s . B . A, A [rank][in], B [out][rank] in the trainable flat buffer
+constexpr int LORA_STRIP_ROWS = 128;   // rows of dW' one block of the projection takes (dA leaves it as one partial sum per strip)
+struct LoraMat {
+  long long w_off;       // the PACKED tensor this matrix lives in: offset in the full flat buffer (master / gradient), floats; its row stride is `in`
+  long long a_off, b_off;   // lora_A / lora_B in the trainable flat buffer (parameters and gradients alike), floats
+  int out, in;           // logical rows x columns (multiples of 32)
+  int row0, blk;         // logical row i = packed row row0 + (i >> 3) * blk + (i & 7)  (blk 8: plain or a q|k|v row range; 16: gate / up interleaved by 8)
+  int strip0;            // first strip of this matrix in the projection's strip numbering
+  long long part_off;    // its per-strip dA partial sums in the scratch, floats, relative to its launch group
+};
+struct LoraCommitDesc {
+  CommitDesc c;          // the packed tensor, as fv_train_commit sees it (tile0 in the LoRA launch's own numbering)
+  int kind;              // 0 plain (mat[0]), 1 q|k|v row ranges (mat[0..2], qd / kd rows), 2 gate / up interleaved (mat[0] gate, mat[1] up)
+  int qd, kd;
+  int mat[3];            // index into the LoraMat table, -1 = that part has no adapter
+};
+// dA, dB of matrices [m0, m1) (their strips: strip_begin .. strip_begin + nstrips) from ONE read of the full gradient; scratch holds the group's dA partials
+int launch_lora_project(const LoraMat* mats_dev, int m0, int m1, int strip_begin, int nstrips, int max_in, const float* grads_full, const float* lora,
+                        float* lora_grads, float* scratch, int rank, float scale, hipStream_t s);
+int launch_lora_commit(const LoraCommitDesc* desc_dev, int ndesc, int ntiles, const LoraMat* mats_dev, const float* flat, const float* lora, int rank, float scale,
+                       int f16_transposes, unsigned* sat, hipStream_t s);
+int launch_lora_merge(const LoraCommitDesc* desc_dev, int ndesc, int ntiles, const LoraMat* mats_dev, float* flat, const float* lora, int rank, float scale,
+                      hipStream_t s);
+
 // ---- tower backward (tower_bwd_kernels.hip; SURVEY.md 8f-4, second slice) ---------------------------------------------------------
 // gradients NHWC fp16 (loss-scaled), activations NHWC bf16, weight gradients fp32 by fixed-order partial sums (no atomics)
 size_t dw_bwd_scratch_floats(int B, int Ho, int Wo, int Co, int k);

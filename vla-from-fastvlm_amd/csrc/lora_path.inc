@@ -1,0 +1,244 @@
+// lora_path.inc -- host side of the LoRA mode of backbone training (fv_train_lora_*), included by engine.hip behind train_path.inc.
+//
+// The reference has no adapter mode: its one knob is fastvla/configuration_fastvla.py:23 `freeze_backbone` and its step body training/trainer.py:60-66,
+// 171-182 (clip_grad_norm_ + AdamW over the parameters with requires_grad).  Here the decoder's matrices stay frozen in the fp32 master and every TARGET
+// matrix (q, k, v, o, gate, up, down of every layer) runs as W0 + s . B . A, s = alpha / rank -- PEFT's merged LoRA without dropout.  The TRAINABLE
+// parameters live in a flat buffer of their own,
+//     [ action expert | projector | layer 0 adapters .. layer L-1 adapters ]        (fv_train_lora_layout)
+// whose front (head + projector) has the master's own offsets; gradients and Adam's m / v mirror THAT buffer.  One step:
+//     fv_train_forward_backward (unchanged: full dW' into the full gradient buffer)  ->  fv_train_lora_project (dA, dB; head / projector gradients copied)
+//     ->  all-reduce + fv_adamw_clip_step over the trainable buffer  ->  fv_train_lora_commit (operand images from W0 + s . B . A).
+// Kernels: lora_kernels.hip.
+
+namespace {
+
+const char* const LORA_TARGET_NAMES[7] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"};
+
+struct LoraLogical { int out, in, row0, blk; const char* packed; int kind, part; };   // one target of a layer: where it sits inside its packed tensor
+
+void lora_logicals(const fv_model_desc& d, LoraLogical out[7]) {
+  const int H = d.llm_hidden, I = d.llm_inter, D = d.llm_head_dim, qd = d.llm_heads * D, kd = d.llm_kv_heads * D;
+  out[0] = {qd, H, 0, 8, "self_attn.qkv_proj.weight", 1, 0};
+  out[1] = {kd, H, qd, 8, "self_attn.qkv_proj.weight", 1, 1};
+  out[2] = {kd, H, qd + kd, 8, "self_attn.qkv_proj.weight", 1, 2};
+  out[3] = {H, qd, 0, 8, "self_attn.o_proj.weight", 0, 0};
+  out[4] = {I, H, 0, 16, "mlp.gate_up_proj.weight", 2, 0};
+  out[5] = {I, H, 8, 16, "mlp.gate_up_proj.weight", 2, 1};
+  out[6] = {H, I, 0, 8, "mlp.down_proj.weight", 0, 0};
+}
+
+// the trainable buffer: head and projector exactly as train_tensors lists them (same offsets), then lora_A (rank x in) / lora_B (out x rank) per layer and target
+std::vector<TrainTensor> lora_tensors(fv_handle* h, int rank, int mask, int64_t* total, int64_t* front) {
+  std::vector<TrainTensor> out;
+  int64_t off = 0;
+  for (const TrainTensor& t : train_tensors(h, nullptr)) {
+    if (t.bucket > TB_PROJ) { off = t.off; break; }
+    TrainTensor c = t;
+    c.lib = nullptr; c.tcopy = c.tcopy16 = c.row16 = nullptr;
+    out.push_back(c);
+  }
+  if (front) *front = off;
+  LoraLogical lg[7];
+  lora_logicals(h->d, lg);
+  for (int l = 0; l < h->d.llm_layers; ++l)
+    for (int k = 0; k < 7; ++k) {
+      if (!(mask >> k & 1)) continue;
+      const std::string pre = "model.layers." + std::to_string(l) + "." + LORA_TARGET_NAMES[k];
+      for (int ab = 0; ab < 2; ++ab) {
+        TrainTensor t;
+        t.name = pre + (ab ? ".lora_B.weight" : ".lora_A.weight");
+        t.rows = ab ? lg[k].out : rank; t.cols = ab ? rank : lg[k].in; t.numel = (int64_t)t.rows * t.cols;
+        t.off = off; t.bucket = TB_LAYER0 + l; t.is_mat = true;
+        off += (t.numel + 3) / 4 * 4;
+        out.push_back(t);
+      }
+    }
+  if (total) *total = off;
+  return out;
+}
+
+// every table the LoRA entry points read: the adapted matrices, the commit descriptors of the packed tensors that hold them, the plain commit table of the rest
+int build_lora_tables(fv_handle* h) {
+  LoraState& ls = h->train.lora;
+  const int rank = ls.rank;
+  LoraLogical lg[7];
+  lora_logicals(h->d, lg);
+  int64_t total = 0, front = 0;
+  const std::vector<TrainTensor> lt = lora_tensors(h, rank, ls.mask, &total, &front);
+  std::map<std::string, int64_t> loff;
+  for (const TrainTensor& t : lt) loff[t.name] = t.off;
+  std::vector<fv::LoraMat> mats;
+  std::vector<fv::LoraCommitDesc> cds;
+  std::vector<fv::CommitDesc> rest;
+  int ctiles = 0, rtiles = 0, strips = 0;
+  for (const TrainTensor& t : train_tensors(h, nullptr)) {
+    if (!t.lib) continue;
+    fv::CommitDesc c{};
+    c.src_off = t.off; c.dst = t.lib; c.is_mat = t.is_mat ? 1 : 0;
+    int ntile;
+    if (t.is_mat) {
+      c.rows = t.rows; c.cols = t.cols;
+      c.dstT16 = t.tcopy16 ? *t.tcopy16 : nullptr; c.dstTb = t.tcopy ? *t.tcopy : nullptr;
+      c.dst16 = (h->train.fwd_f16 && t.row16) ? *t.row16 : nullptr; c.scale16 = t.scale16;
+      ntile = ((t.rows + 63) / 64) * ((t.cols + 63) / 64);
+    } else {
+      c.rows = 1; c.cols = (int)t.numel;
+      ntile = (int)((t.numel + 4095) / 4096);
+    }
+    fv::LoraCommitDesc lc{};
+    lc.c = c; lc.mat[0] = lc.mat[1] = lc.mat[2] = -1;
+    bool adapted = false;
+    const size_t lpos = t.name.find("model.layers.");
+    if (t.is_mat && lpos == 0 && t.bucket >= TB_LAYER0) {
+      const std::string pre = t.name.substr(0, t.name.find('.', 13) + 1);   // "model.layers.<l>."
+      for (int k = 0; k < 7; ++k) {
+        if (!(ls.mask >> k & 1) || t.name != pre + lg[k].packed) continue;
+        fv::LoraMat m{};
+        m.w_off = t.off; m.out = lg[k].out; m.in = lg[k].in; m.row0 = lg[k].row0; m.blk = lg[k].blk;
+        m.a_off = loff.at(pre + LORA_TARGET_NAMES[k] + ".lora_A.weight");
+        m.b_off = loff.at(pre + LORA_TARGET_NAMES[k] + ".lora_B.weight");
+        if (m.in != t.cols || m.out % 32 || m.in % 32)
+          return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_begin: %s%s is %d x %d (adapted matrices need dimensions that are multiples of 32)", pre.c_str(),
+                         LORA_TARGET_NAMES[k], m.out, m.in);
+        m.strip0 = strips;
+        strips += (m.out + fv::LORA_STRIP_ROWS - 1) / fv::LORA_STRIP_ROWS;
+        lc.kind = lg[k].kind; lc.mat[lg[k].part] = (int)mats.size();
+        mats.push_back(m);
+        adapted = true;
+      }
+    }
+    if (adapted) {
+      lc.qd = h->d.llm_heads * h->d.llm_head_dim; lc.kd = h->d.llm_kv_heads * h->d.llm_head_dim;
+      lc.c.tile0 = ctiles; ctiles += ntile;
+      cds.push_back(lc);
+    } else {
+      c.tile0 = rtiles; rtiles += ntile;
+      rest.push_back(c);
+    }
+  }
+  if (mats.empty()) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: no target matrix selected");
+  // projection groups: consecutive matrices whose per-strip dA partial sums (strips x rank x in floats) fit the scratch together
+  const size_t cap = (size_t)32 << 20;   // floats (128 MB); one matrix alone may exceed it
+  ls.groups.clear();
+  size_t scratch = 0;
+  LoraGroup g{};
+  size_t used = 0;
+  for (size_t i = 0; i < mats.size(); ++i) {
+    const int ns = (mats[i].out + fv::LORA_STRIP_ROWS - 1) / fv::LORA_STRIP_ROWS;
+    const size_t need = (size_t)ns * rank * mats[i].in;
+    if (g.m1 > g.m0 && used + need > cap) { ls.groups.push_back(g); g = LoraGroup{}; g.m0 = g.m1 = (int)i; g.strip_begin = mats[i].strip0; used = 0; }
+    if (g.m1 == g.m0) { g.m0 = (int)i; g.strip_begin = mats[i].strip0; }
+    mats[i].part_off = (long long)used;
+    used += need; g.m1 = (int)i + 1; g.nstrips += ns; g.max_in = std::max(g.max_in, mats[i].in);
+    scratch = std::max(scratch, used);
+  }
+  ls.groups.push_back(g);
+  void* p = nullptr;
+  FV_TRY(dev_alloc(h, mats.size() * sizeof(fv::LoraMat), &p));
+  FV_HIP_CHECK(hipMemcpy(p, mats.data(), mats.size() * sizeof(fv::LoraMat), hipMemcpyHostToDevice));
+  ls.mats = static_cast<fv::LoraMat*>(p); ls.nmats = (int)mats.size();
+  FV_TRY(dev_alloc(h, cds.size() * sizeof(fv::LoraCommitDesc), &p));
+  FV_HIP_CHECK(hipMemcpy(p, cds.data(), cds.size() * sizeof(fv::LoraCommitDesc), hipMemcpyHostToDevice));
+  ls.cdesc = static_cast<fv::LoraCommitDesc*>(p); ls.cn = (int)cds.size(); ls.ctiles = ctiles;
+  FV_TRY(dev_alloc(h, rest.size() * sizeof(fv::CommitDesc), &p));
+  FV_HIP_CHECK(hipMemcpy(p, rest.data(), rest.size() * sizeof(fv::CommitDesc), hipMemcpyHostToDevice));
+  ls.rest = static_cast<fv::CommitDesc*>(p); ls.rest_n = (int)rest.size(); ls.rest_tiles = rtiles;
+  if (scratch > ls.scratch_floats) {
+    FV_TRY(dev_alloc(h, scratch * 4, &p));
+    ls.scratch = static_cast<float*>(p); ls.scratch_floats = scratch;
+  }
+  ls.front = front; ls.total = total;
+  return FV_OK;
+}
+
+int lora_check(fv_handle* h) {
+  FV_TRY(train_check(h));
+  if (!h->train.lora.on) return fv_fail(FV_ERR_STATE, "LoRA training not initialised: call fv_train_lora_begin first");
+  return FV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fv_train_lora_begin(fv_handle* h, int rank, float alpha, int target_mask) {
+  HandleScope _hs(h);
+  FV_TRY(train_check(h));
+  if (rank < 1 || rank > 64) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: rank %d (1 .. 64)", rank);
+  if (!(alpha > 0.f) || !std::isfinite(alpha)) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: alpha must be positive and finite");
+  if (target_mask <= 0 || target_mask >= 128) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: target_mask 0x%x (bits 0 .. 6: q, k, v, o, gate, up, down; at least one)", target_mask);
+  if (h->train.tower) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_begin: the tower is being trained (fv_train_tower_begin): adapters go with a frozen tower");
+  LoraState& ls = h->train.lora;
+  if (ls.on) {
+    if (ls.rank == rank && ls.alpha == alpha && ls.mask == target_mask) return FV_OK;
+    return fv_fail(FV_ERR_STATE, "fv_train_lora_begin: already begun with rank %d, alpha %g, targets 0x%x", ls.rank, (double)ls.alpha, ls.mask);
+  }
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  ls.rank = rank; ls.alpha = alpha; ls.scale = alpha / (float)rank; ls.mask = target_mask;
+  FV_TRY(build_lora_tables(h));
+  ls.on = true;
+  return FV_OK;
+}
+
+int fv_train_lora_layout(fv_handle* h, fv_train_tensor* out, int max_tensors, int* n_tensors, int64_t* total_numel) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (!h->train.lora.on) return fv_fail(FV_ERR_STATE, "LoRA training not initialised: call fv_train_lora_begin first");
+  int64_t total = 0;
+  const std::vector<TrainTensor> tt = lora_tensors(h, h->train.lora.rank, h->train.lora.mask, &total, nullptr);
+  if (n_tensors) *n_tensors = (int)tt.size();
+  if (total_numel) *total_numel = total;
+  if (out) {
+    if (max_tensors < (int)tt.size()) return fv_fail(FV_ERR_ARG, "fv_train_lora_layout: room for %d tensors, %zu needed", max_tensors, tt.size());
+    for (size_t i = 0; i < tt.size(); ++i) {
+      memset(&out[i], 0, sizeof(out[i]));
+      snprintf(out[i].name, sizeof(out[i].name), "%s", tt[i].name.c_str());
+      out[i].offset = tt[i].off; out[i].numel = tt[i].numel; out[i].rows = tt[i].rows; out[i].cols = tt[i].cols;
+      out[i].bucket = tt[i].bucket; out[i].packing = 0;
+    }
+  }
+  return FV_OK;
+}
+
+int fv_train_lora_project(fv_handle* h, const float* flat_grads_full, const float* lora_params, float* lora_grads, fv_stream st) {
+  HandleScope _hs(h);
+  FV_TRY(lora_check(h));
+  if (!flat_grads_full || !lora_params || !lora_grads) return fv_fail(FV_ERR_ARG, "fv_train_lora_project: null buffer");
+  if (((uintptr_t)flat_grads_full | (uintptr_t)lora_params | (uintptr_t)lora_grads) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_project: buffers must be 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(st);
+  const LoraState& ls = h->train.lora;
+  // head and projector train in full: their gradients move over as they are (same offsets in both buffers)
+  FV_HIP_CHECK(hipMemcpyAsync(lora_grads, flat_grads_full, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
+  for (const LoraGroup& g : ls.groups)
+    FV_TRY(fv::launch_lora_project(ls.mats, g.m0, g.m1, g.strip_begin, g.nstrips, g.max_in, flat_grads_full, lora_params, lora_grads, ls.scratch, ls.rank, ls.scale, s));
+  return FV_OK;
+}
+
+int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream st) {
+  HandleScope _hs(h);
+  FV_TRY(lora_check(h));
+  if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_commit: null buffer");
+  if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_commit: buffers must be 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(st);
+  const LoraState& ls = h->train.lora;
+  // the master's head | projector front mirrors the trainable buffer's (fv_train_forward_backward reads the head there); nothing else of it is written
+  FV_HIP_CHECK(hipMemcpyAsync(flat_params_master, lora_params, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
+  const int f16t = h->train.grad_split == 2 ? 1 : 0;
+  FV_TRY(fv::launch_commit(ls.rest, ls.rest_n, ls.rest_tiles, flat_params_master, f16t, h->f16_flags, s));
+  FV_TRY(fv::launch_lora_commit(ls.cdesc, ls.cn, ls.ctiles, ls.mats, flat_params_master, lora_params, ls.rank, ls.scale, f16t, h->f16_flags, s));
+  return FV_OK;
+}
+
+int fv_train_lora_merge(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream st) {
+  HandleScope _hs(h);
+  FV_TRY(lora_check(h));
+  if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_merge: null buffer");
+  if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_merge: buffers must be 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(st);
+  const LoraState& ls = h->train.lora;
+  FV_HIP_CHECK(hipMemcpyAsync(flat_params_master, lora_params, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
+  FV_TRY(fv::launch_lora_merge(ls.cdesc, ls.cn, ls.ctiles, ls.mats, flat_params_master, lora_params, ls.rank, ls.scale, s));
+  return FV_OK;
+}
+
+}  // extern "C"

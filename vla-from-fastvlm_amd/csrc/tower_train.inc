@@ -637,6 +637,7 @@ int fv_train_tower_begin(fv_handle* h) {
   HandleScope _hs(h);
   FV_TRY(train_check(h));
   if (h->train.tower) return FV_OK;
+  if (h->train.lora.on) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_tower_begin: LoRA mode is on (fv_train_lora_begin): adapters go with a frozen tower");
   const fv_model_desc& d = h->d;
   for (int i = 0; i < d.tower_stages; ++i)
     if (d.tower_dims[i] % 8 || (d.tower_is_attn[i] && d.tower_head_dim != 32))

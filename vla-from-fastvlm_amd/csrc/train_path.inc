@@ -43,6 +43,8 @@ enum { TB_HEAD = 0, TB_PROJ = 1, TB_EMBED = 2, TB_LAYER0 = 3 };
 void append_tower_tensors(fv_handle* h, std::vector<TrainTensor>& out, int64_t& off);
 int tower_export(fv_handle* h, float* flat, hipStream_t s);
 int tower_bucket_count(const fv_handle* h);
+// lora_path.inc (the LoRA mode): its commit tables name the same operand copies as fv_train_commit's and are rebuilt with it
+int build_lora_tables(fv_handle* h);
 
 std::vector<TrainTensor> train_tensors(fv_handle* h, int64_t* total) {
   const fv_model_desc& d = h->d;
@@ -258,6 +260,7 @@ int build_commit_table(fv_handle* h) {
   FV_TRY(dev_alloc(h, cd.size() * sizeof(fv::CommitDesc), &dp));
   FV_HIP_CHECK(hipMemcpy(dp, cd.data(), cd.size() * sizeof(fv::CommitDesc), hipMemcpyHostToDevice));
   h->train.commit_desc = static_cast<fv::CommitDesc*>(dp); h->train.commit_n = (int)cd.size(); h->train.commit_tiles = tiles;
+  if (h->train.lora.on) FV_TRY(build_lora_tables(h));
   return FV_OK;
 }
 

@@ -620,6 +620,38 @@ class FastVLAEngine:
         _lib.check(rc, "fv_train_forward_backward", self.h)
         return actions, loss, flat_grads
 
+    # ---------------------------------------------------------------- LoRA mode of the slice (fv_train_lora_*; csrc/lora_path.inc)
+    def train_lora_begin(self, rank: int, alpha: Optional[float] = None, targets=None) -> None:
+        """After train_begin(): adapters W0 + (alpha / rank) B A on the target matrices of every decoder layer (default: alpha = rank, all seven targets);
+        the master stays frozen.  Not together with train_tower_begin()."""
+        from . import lora
+        cfg = lora.check_config(rank, alpha, targets)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fv_train_lora_begin(self.h, cfg["rank"], cfg["alpha"], lora.target_mask(cfg["targets"])), "fv_train_lora_begin", self.h)
+        self.lora_config = cfg
+
+    def train_lora_layout(self):
+        """-> (tensors, total_numel) of the TRAINABLE flat buffer [head | projector | layer adapters] (fv_train_lora_layout), dicts as train_layout()'s."""
+        n, total = C.c_int(), C.c_int64()
+        _lib.check(self.lib.fv_train_lora_layout(self.h, None, 0, C.byref(n), C.byref(total)), "fv_train_lora_layout", self.h)
+        arr = (_lib.TrainTensor * n.value)()
+        _lib.check(self.lib.fv_train_lora_layout(self.h, arr, n.value, C.byref(n), C.byref(total)), "fv_train_lora_layout", self.h)
+        tensors = [dict(name=t.name.decode(), offset=t.offset, numel=t.numel, rows=t.rows, cols=t.cols, bucket=t.bucket, packing=t.packing) for t in arr]
+        return tensors, int(total.value)
+
+    def train_lora_project(self, flat_grads_full: torch.Tensor, lora_params: torch.Tensor, lora_grads: torch.Tensor) -> None:
+        """lora_grads <- head / projector gradients copied, dA = s B^T dW', dB = s dW' A^T of every adapted matrix (fv_train_lora_project)"""
+        _lib.check(self.lib.fv_train_lora_project(self.h, flat_grads_full.data_ptr(), lora_params.data_ptr(), lora_grads.data_ptr(), _stream()),
+                   "fv_train_lora_project", self.h)
+
+    def train_lora_commit(self, flat_master: torch.Tensor, lora_params: torch.Tensor) -> None:
+        """operand images <- W0 + s B A (adapted matrices) / the master (the rest); the master's head | projector front <- lora_params' (fv_train_lora_commit)"""
+        _lib.check(self.lib.fv_train_lora_commit(self.h, flat_master.data_ptr(), lora_params.data_ptr(), _stream()), "fv_train_lora_commit", self.h)
+
+    def train_lora_merge(self, flat_master: torch.Tensor, lora_params: torch.Tensor) -> None:
+        """flat_master's adapted matrices += s B A, the very fp32 values train_lora_commit rounds (fv_train_lora_merge)"""
+        _lib.check(self.lib.fv_train_lora_merge(self.h, flat_master.data_ptr(), lora_params.data_ptr(), _stream()), "fv_train_lora_merge", self.h)
+
     # ---------------------------------------------------------------- the tower half of the slice (fv_train_tower_*; csrc/tower_train.inc)
     def train_tower_begin(self) -> None:
         """After train_begin(): the FastViT-HD tower's tensors (inference form) join the flat master -- train_layout() then lists them behind

@@ -27,19 +27,42 @@ class FastVLAPolicy(nn.Module):
         self._opt_state = None
         self._unfrozen = None   # training/unfrozen.py UnfrozenState once enable_backbone_training() ran
 
-    def enable_backbone_training(self, bucket_min_numel: int = 1 << 22, tower: Optional[bool] = None):
+    def enable_backbone_training(self, bucket_min_numel: int = 1 << 22, tower: Optional[bool] = None, lora_rank: Optional[int] = None,
+                                 lora_alpha: Optional[float] = None, lora_targets=None, lora_seed: int = 0):
         """Extension of this build: fine-tune the Qwen2 decoder + mm_projector together with the action expert
         (image tokens spliced); tower=True (or FASTVLA_TRAIN_TOWER=1) trains the FastViT-HD tower too, in its inference form, otherwise it stays
         frozen.  Explicit on purpose: the reference's `freeze_backbone=False` trains nothing but the head either (model/fastvlm_adapter.py:501),
-        so the config flag alone must not change what a step computes."""
+        so the config flag alone must not change what a step computes.
+
+        lora_rank=r (1 .. 64; or FASTVLA_LORA_RANK, with FASTVLA_LORA_ALPHA / FASTVLA_LORA_TARGETS): LoRA mode -- the decoder's matrices stay frozen and the
+        target matrices (default all seven: q, k, v, o, gate, up, down) run as W0 + (lora_alpha / r) B A (default alpha = r), action expert and mm_projector
+        train in full; gradients, Adam's moments and the data-parallel exchange cover the trainable tensors only.  Not together with tower=True."""
+        from fastvla_hip import lora as _lora
         if tower is None:
             tower = os.environ.get("FASTVLA_TRAIN_TOWER", "0") == "1"
+        if lora_rank is None and lora_alpha is None and lora_targets is None:
+            lcfg = _lora.config_from_env()       # the environment twins, in the style of FASTVLA_TRAIN_TOWER
+            if lcfg is not None and tower:
+                raise ValueError("FASTVLA_LORA_RANK and a trained tower (tower=True / FASTVLA_TRAIN_TOWER=1) cannot be combined: LoRA adapters go with a frozen vision tower")
+        else:
+            if lora_rank is None:
+                raise ValueError("lora_alpha / lora_targets need lora_rank")
+            lcfg = _lora.check_config(lora_rank, lora_alpha, lora_targets, tower=bool(tower))
         if self._unfrozen is not None and bool(tower) and not self._unfrozen.train_tower:
             raise RuntimeError("backbone training is already running with the tower frozen: ask for tower=True on the first call")
+        if self._unfrozen is not None and lcfg is not None and self._unfrozen.lora != lcfg:
+            raise RuntimeError(f"backbone training is already running with lora={self._unfrozen.lora}: ask for LoRA on the first call")
         if self._unfrozen is None:
             from ..training.unfrozen import UnfrozenState
-            self._unfrozen = UnfrozenState(self, bucket_min_numel=bucket_min_numel, train_tower=bool(tower))
+            self._unfrozen = UnfrozenState(self, bucket_min_numel=bucket_min_numel, train_tower=bool(tower), lora=lcfg, lora_seed=lora_seed)
         return self._unfrozen
+
+    def merge_lora(self) -> None:
+        """LoRA mode: fold the adapters into the fp32 master (W0 += s B A, lora_B = 0).  The model computes what it computed before; the backbone export
+        (save_policy_checkpoint(include_backbone=True), FASTVLA_SAVE_BACKBONE) then writes a plain checkpoint under the reference's keys."""
+        if self._unfrozen is None or self._unfrozen.lora is None:
+            raise RuntimeError("merge_lora(): this policy has no LoRA adapters (enable_backbone_training(lora_rank=...))")
+        self._unfrozen.merge_lora()
 
     def forward(self, images: torch.Tensor, states: torch.Tensor, tasks: List[str] | str,
                 device: torch.device | None = None) -> torch.Tensor:
@@ -108,15 +131,18 @@ class FastVLAPolicy(nn.Module):
         return st
 
     def load_optimizer_state(self, m: torch.Tensor, v: torch.Tensor, step: int, flat: Optional[torch.Tensor] = None,
-                             train_tower: Optional[bool] = None) -> None:
+                             train_tower: Optional[bool] = None, lora: Optional[Dict] = None) -> None:
         """Restore AdamW moments and the bias-correction step (Trainer._load_checkpoint; reference trainer.py:257-262
         restores them through accelerator.load_state).  train_tower: what optimizer.pt recorded about the run being resumed (None: a round-5 file, which
         did not record it -- FASTVLA_TRAIN_TOWER decides then, as before)."""
         head_numel = sum(p.numel() for p in self.model.head_parameters())
-        if self._unfrozen is None and (train_tower is not None or m.numel() > 2 * head_numel):
+        if self._unfrozen is None and (train_tower is not None or lora is not None or m.numel() > 2 * head_numel):
             # moments of a whole-backbone run (training/unfrozen.py writes one flat m / v over every trainable tensor): the run resumes unfrozen,
-            # training what the checkpointed run trained
-            self.enable_backbone_training(tower=train_tower)
+            # training what the checkpointed run trained (lora: optimizer.pt's record of a LoRA run -- its m / v / flat cover the trainable buffer)
+            if lora is not None:
+                self.enable_backbone_training(lora_rank=lora["rank"], lora_alpha=lora["alpha"], lora_targets=lora["targets"])
+            else:
+                self.enable_backbone_training(tower=train_tower)
         if self._unfrozen is not None:
             u = self._unfrozen
             if m.numel() != u.m.numel():
@@ -126,13 +152,10 @@ class FastVLAPolicy(nn.Module):
             u.step_count = int(step)
             self._opt_state["step"] = int(step)
             if flat is not None:      # the fp32 master of the run being resumed (Trainer._save_checkpoint): parameters continue bit for bit
-                if flat.numel() != u.flat.numel():
-                    raise ValueError(f"checkpointed master has {flat.numel()} elements, this run's {u.flat.numel()}")
-                u.flat.copy_(flat.to(u.flat.device))
-                u.eng.train_commit(u.flat)
-                bb = self.model.backbone
-                bb.clear_prefix_cache()
-                bb.clear_prompt_cache()
+                if flat.numel() != u.trainable.numel():       # (LoRA mode: the trainable buffer -- head, projector, adapters)
+                    raise ValueError(f"checkpointed master has {flat.numel()} elements, this run's {u.trainable.numel()}")
+                u.trainable.copy_(flat.to(u.trainable.device))
+                u.commit()
             return
         flat = self.model._flat
         if flat is None:

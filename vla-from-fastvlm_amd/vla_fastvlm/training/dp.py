@@ -33,10 +33,12 @@ class GradExchange:
         self.stream = torch.cuda.Stream(device=device) if device is not None and torch.device(device).type == "cuda" else None
         self._pending = False
         self._ev = None  # (start, end) events of the last collective on the side stream: bench.py's allreduce_ms
+        self.last_numel: Optional[int] = None   # payload of the last start(), in elements (a LoRA run exchanges its trainable buffer only)
 
     def start(self, flat_grads: torch.Tensor, timed: bool = False) -> float:
         """Launch SUM(flat_grads) across ranks (in place); returns the scale (1/world) the optimiser must apply."""
         world = world_size(self.group)
+        self.last_numel = int(flat_grads.numel())
         if world == 1:
             return 1.0
         if flat_grads.is_cuda and self.stream is not None:

@@ -129,11 +129,13 @@ class Trainer:
         flat = core.materialize(self.device)
         if self._resume_opt is not None and hasattr(self.model, "load_optimizer_state"):
             self.model.load_optimizer_state(self._resume_opt["m"], self._resume_opt["v"], int(self._resume_opt["step"]), flat=self._resume_opt.get("flat"),
-                                            train_tower=self._resume_opt.get("train_tower"))
+                                            train_tower=self._resume_opt.get("train_tower"), **({"lora": self._resume_opt["lora"]} if self._resume_opt.get("lora") else {}))
             self._resume_opt = None
         un = getattr(self.model, "_unfrozen", None)
         if un is not None:
-            flat = un.flat        # an unfrozen run: the replicas share the WHOLE master (head + projector + decoder [+ tower]), not the head alone
+            # an unfrozen run: the replicas share the WHOLE master (head + projector + decoder [+ tower]), not the head alone; a LoRA run its trainable
+            # buffer (head + projector + adapters: the frozen master is the same checkpoint on every rank)
+            flat = un.trainable
         if self.world > 1:
             broadcast_flat(flat)
             st = getattr(self.model, "_opt_state", None)
@@ -203,6 +205,12 @@ class Trainer:
     # its own strict loader accepts the file; False (default, or FASTVLA_SAVE_BACKBONE unset) keeps checkpoints at the head's 12 MB.
     save_backbone_weights: bool = os.environ.get("FASTVLA_SAVE_BACKBONE", "0") == "1"
 
+    def _backbone_must_travel(self) -> bool:
+        """an unfrozen run's checkpoint without the VLM would lose what was trained -- unless it is a LoRA run, whose adapters travel in their own small file
+        (after merge_lora() the master itself changed: it travels again)"""
+        un = getattr(self.model, "_unfrozen", None)
+        return un is not None and (un.lora is None or un.lora_merged)
+
     def _save_checkpoint(self, suffix: str) -> None:
         """Same files as reference trainer.py:246-255: policy_config.json + policy_state_dict.pt (head tensors under the
         reference's `model.*` keys; the frozen backbone lives in the library and is not duplicated)."""
@@ -211,7 +219,7 @@ class Trainer:
         from ..utils.checkpoint import save_policy_checkpoint
         # an unfrozen run's checkpoint without the VLM would lose what was trained: the backbone always travels then
         d = save_policy_checkpoint(self.model, Path(self.config.output_dir) / "checkpoints" / suffix,
-                                   include_backbone=self.save_backbone_weights or getattr(self.model, "_unfrozen", None) is not None)
+                                   include_backbone=self.save_backbone_weights or self._backbone_must_travel())
         st = getattr(self.model, "_opt_state", None)
         if st is not None:
             rec = {"m": st["m"].cpu(), "v": st["v"].cpu(), "step": st["step"], "global_step": self.global_step, "update_step": self.update_step}
@@ -219,8 +227,10 @@ class Trainer:
             if un is not None:
                 # the fp32 MASTER of an unfrozen run: the VLM tensors of policy_state_dict.pt come back through the engine's bf16 operand copies, and a master
                 # rebuilt from those has lost the low bits every later update (~1e-3 of a bf16 ulp) lives in
-                rec["flat"] = un.flat.cpu()
+                rec["flat"] = un.trainable.cpu()     # (a LoRA run: head + projector + adapters; its frozen master is the base checkpoint)
                 rec["train_backbone"], rec["train_tower"] = True, bool(un.train_tower)   # what the run trains comes back from the checkpoint, not from the environment
+                if un.lora is not None:
+                    rec["lora"] = dict(un.lora)
             torch.save(rec, d / "optimizer.pt")
 
     def _load_checkpoint(self, path: str) -> None:
@@ -237,7 +247,8 @@ class Trainer:
             self.model._unfrozen = None
             self.model.model.backbone.load_backbone_state(vlm)
             if un is not None:
-                self.model.enable_backbone_training(tower=un.train_tower)
+                self.model.enable_backbone_training(tower=un.train_tower, **({"lora_rank": un.lora["rank"], "lora_alpha": un.lora["alpha"], "lora_targets": un.lora["targets"]}
+                                                                               if un.lora is not None else {}))
         own = self.model.state_dict()
         # `.io_norm.` / splice-mode keys exist in state_dict() only while they are on, so a freshly built model does not list them -- let them
         # through (FastVLMBackbone._load_from_state_dict re-applies them)
@@ -246,6 +257,9 @@ class Trainer:
         ex = read_extras(p)
         if "splice_image_tokens" in ex:
             self.model.model.backbone.splice_image_tokens = bool(ex["splice_image_tokens"])
+        if ex.get("lora"):
+            from ..utils.checkpoint import load_lora_adapters
+            load_lora_adapters(self.model, p, ex["lora"])
         if (p / "optimizer.pt").is_file():
             self._resume_opt = torch.load(p / "optimizer.pt", map_location="cpu")  # applied by _sync_replicas()
             self.global_step = int(self._resume_opt.get("global_step", 0))

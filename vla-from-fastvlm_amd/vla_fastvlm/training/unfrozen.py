@@ -11,6 +11,12 @@ schedule -- with every kernel in libfastvla_hip.so (fv_train_forward_backward, f
 All trainable tensors live in ONE flat fp32 buffer (fv_train_layout: [head | projector | embedding | layers | final norm], matrices in the
 library's packed layout); gradients, Adam's m and v mirror it.  Under torch.distributed the gradient is exchanged per BUCKET while the
 backward pass is still running (training/dp.py BucketedGradExchange, driven by the library's fv_bucket_cb).
+
+LoRA mode (`lora={"rank", "alpha", "targets"}`; fv_train_lora_*): the decoder's matrices stay FROZEN in that master and every target matrix runs as
+W0 + (alpha / rank) B A; action expert and mm_projector still train in full.  The trainable tensors then live in a second, small flat buffer
+(fv_train_lora_layout: [head | projector | layer adapters]) and the gradient that is exchanged, Adam's m / v and the optimiser step cover THAT buffer only:
+forward/backward (unchanged, full dW') -> fv_train_lora_project -> ONE all-reduce -> clip + AdamW -> fv_train_lora_commit.  The full-size m / v are never
+allocated; the full master and the full gradient buffer remain.
 """
 from __future__ import annotations
 
@@ -24,7 +30,7 @@ from .dp import BucketedGradExchange, GradExchange
 
 
 class UnfrozenState:
-    def __init__(self, policy, bucket_min_numel: int = 1 << 22, train_tower: bool = False):
+    def __init__(self, policy, bucket_min_numel: int = 1 << 22, train_tower: bool = False, lora: Optional[Dict] = None, lora_seed: int = 0):
         m = policy.model
         bb = m.backbone
         self.policy = policy
@@ -32,8 +38,13 @@ class UnfrozenState:
         if eng.llm_precision != 1:
             raise RuntimeError("backbone training needs the split-bf16 decoder policy (llm_precision=1): its bf16 weight copies are refreshed "
                                f"from the fp32 master after every step; this engine runs llm_precision={eng.llm_precision}")
+        if lora is not None and train_tower:
+            raise ValueError("LoRA adapters go with a frozen vision tower: lora and train_tower cannot be combined")
         eng.train_begin()
         self.train_tower = bool(train_tower)
+        self.lora = dict(lora) if lora is not None else None      # {"rank", "alpha", "targets"}: the decoder's matrices frozen, adapters trained
+        if self.lora is not None:
+            eng.train_lora_begin(self.lora["rank"], self.lora["alpha"], self.lora["targets"])
         if self.train_tower:
             eng.train_tower_begin()        # the FastViT-HD tower's inference-form tensors join the flat master (fv_train_tower_*)
         self._tws: Dict[int, torch.Tensor] = {}
@@ -48,14 +59,26 @@ class UnfrozenState:
         old = m.materialize(dev)
         hn = eng.head_numel()
         self.flat[:hn].copy_(old)
-        views = eng.head_views(self.flat[:hn])
+        self.lflat: Optional[torch.Tensor] = None
+        self.lora_merged, self.lora_adapters_zero = False, False
+        if self.lora is not None:
+            # the trainable buffer: its head | projector front starts as the master's (the two share their offsets), lora_A as PEFT initialises it, lora_B = 0
+            from fastvla_hip import lora as _lora
+            self.lora_tensors, self.lora_total = eng.train_lora_layout()
+            self.front = next(t["offset"] for t in self.lora_tensors if ".lora_" in t["name"])
+            self.lflat = torch.zeros(self.lora_total, dtype=torch.float32, device=dev)
+            self.lflat[: self.front].copy_(self.flat[: self.front])
+            _lora.init_adapters(self.lflat, self.lora_tensors, seed=lora_seed)
+            self.lg = torch.zeros_like(self.lflat)
+        self.trainable = self.lflat if self.lora is not None else self.flat     # what the optimiser steps over
+        views = eng.head_views(self.trainable[:hn])
         with torch.no_grad():
             for p, k in zip(m.head_parameters(), HEAD_KEYS):
                 p.data = views[k]
-        m._flat = self.flat[:hn]
+        m._flat = self.trainable[:hn]
         self.g = torch.zeros_like(self.flat)
         self.acc: Optional[torch.Tensor] = None
-        self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self.m, self.v = torch.zeros_like(self.trainable), torch.zeros_like(self.trainable)
         self.step_count, self.micro = 0, 0
         self.norm = torch.zeros(1, device=dev)
         self.loss_scale_log2 = 12
@@ -66,7 +89,7 @@ class UnfrozenState:
         bb.splice_image_tokens = True          # the model being trained IS the spliced one: inference must run the same graph
         bb._trained_tensors = self.named_backbone_tensors   # checkpoint export reads the master, not the original weight source
         pending = policy._opt_state if isinstance(policy._opt_state, dict) and "resume" in policy._opt_state else None
-        policy._opt_state = {"m": self.m, "v": self.v, "step": 0, "flat": self.flat, "norm": self.norm}
+        policy._opt_state = {"m": self.m, "v": self.v, "step": 0, "flat": self.trainable, "norm": self.norm}
         if pending is not None and pending["resume"]["m"].numel() == self.m.numel():   # load_optimizer_state() ran before this state existed
             r = pending["resume"]
             self.m.copy_(r["m"].to(dev))
@@ -91,6 +114,61 @@ class UnfrozenState:
             out[pre + "bn.running_mean"] = torch.zeros(c, device=w.device)
             out[pre + "bn.running_var"] = torch.full((c,), 1.0 - bn_eps, device=w.device)
         return out
+
+    # ------------------------------------------------------------------ LoRA: adapters in and out, merge
+    def lora_state(self) -> Dict:
+        """what an adapter checkpoint holds: {"config": {rank, alpha, targets}, "tensors": {PEFT name -> lora_A / lora_B, and the mm_projector's four tensors,
+        which train in full beside them}} (CPU copies)"""
+        assert self.lora is not None
+        out = {}
+        for t in self.lora_tensors:
+            if t["bucket"] == 0:
+                continue
+            v = self.lflat[t["offset"]: t["offset"] + t["numel"]]
+            out[t["name"]] = (v.view(t["rows"], t["cols"]) if t["rows"] > 1 else v).detach().cpu().clone()
+        return {"config": dict(self.lora), "tensors": out}
+
+    def load_lora_state(self, state: Dict) -> None:
+        """the inverse: every adapter (and projector tensor) of this layout must be in `state["tensors"]` with its shape -- a missing one raises"""
+        assert self.lora is not None
+        cfg = state.get("config", {})
+        if int(cfg.get("rank", -1)) != self.lora["rank"] or list(cfg.get("targets", [])) != list(self.lora["targets"]) or float(cfg.get("alpha", -1)) != float(self.lora["alpha"]):
+            raise ValueError(f"adapter file was written with {cfg}, this run uses {self.lora}")
+        tensors = state.get("tensors", {})
+        want = [t for t in self.lora_tensors if t["bucket"] != 0]
+        missing = [t["name"] for t in want if t["name"] not in tensors]
+        if missing:
+            raise KeyError(f"adapter file lacks {len(missing)} tensors, e.g. {missing[:3]}")
+        for t in want:
+            src = tensors[t["name"]]
+            if src.numel() != t["numel"]:
+                raise ValueError(f"{t['name']}: {tuple(src.shape)} in the file, {t['rows']} x {t['cols']} expected")
+            self.lflat[t["offset"]: t["offset"] + t["numel"]].copy_(src.reshape(-1).to(self.lflat.device, torch.float32))
+        self.lora_adapters_zero = False
+        self.commit()
+
+    def commit(self) -> None:
+        """operand images <- the current parameters (fv_train_commit / fv_train_lora_commit), and every cache computed with the old ones dropped"""
+        if self.lora is not None:
+            self.eng.train_lora_commit(self.flat, self.lflat)
+        else:
+            self.eng.train_commit(self.flat)
+        bb = self.policy.model.backbone
+        bb.clear_prefix_cache()
+        bb.clear_prompt_cache()
+
+    def merge_lora(self) -> None:
+        """W0 += s B A into the master (fv_train_lora_merge: the very fp32 values the adapted commit rounds), then lora_B = 0: the model is unchanged, the master
+        is now a plain fine-tuned decoder that named_backbone_tensors() / the backbone export write under the reference's keys."""
+        assert self.lora is not None
+        self.eng.train_lora_merge(self.flat, self.lflat)
+        for t in self.lora_tensors:
+            if t["name"].endswith(".lora_B.weight"):
+                self.lflat[t["offset"]: t["offset"] + t["numel"]].zero_()
+                self.m[t["offset"]: t["offset"] + t["numel"]].zero_()
+                self.v[t["offset"]: t["offset"] + t["numel"]].zero_()
+        self.lora_merged, self.lora_adapters_zero = True, True
+        self.commit()
 
     def _workspace(self, B: int, T: int) -> torch.Tensor:
         key = (B, T)
@@ -138,7 +216,9 @@ class UnfrozenState:
         p = float(pol.config.dropout) if pol.training else 0.0
         m = pol.model
         m._drop_calls += 1
-        overlap = k == 1 and sync              # per-bucket all-reduce under the backward pass; with accumulation the sum is exchanged once
+        # per-bucket all-reduce under the backward pass; with accumulation the sum is exchanged once -- and in LoRA mode what is exchanged does not exist
+        # before the projection has run: one all-reduce of the (small) trainable buffer
+        overlap = k == 1 and sync and self.lora is None
         if overlap:
             self.bucketed.group = process_group
             self.bucketed.begin(self.g)
@@ -158,13 +238,16 @@ class UnfrozenState:
         if self.train_tower:
             eng.train_tower_backward(prep["pix"], dto, tws, self.g, bucket_cb=self.bucketed.bucket_ready if overlap else None)
         total = self.g
+        if self.lora is not None:
+            eng.train_lora_project(self.g, self.lflat, self.lg)    # dA, dB of every adapted matrix; head / projector gradients copied
+            total = self.lg
         if k > 1:
             if self.acc is None:
-                self.acc = torch.zeros_like(self.flat)
+                self.acc = torch.zeros_like(self.trainable)
             if self.micro == 1:
-                self.acc.copy_(self.g)
+                self.acc.copy_(total)
             else:
-                eng.grad_accumulate(self.acc, self.g)
+                eng.grad_accumulate(self.acc, total)
             total = self.acc
         out = {"loss": loss[0], "mse": loss[0].detach(), "actions": actions, "synced": sync, "next": None}
         if sync:
@@ -177,12 +260,12 @@ class UnfrozenState:
             self.step_count += 1
             self.micro = 0
             scale /= eng.train_loss_scale()      # every gradient of fv_train_forward_backward carries the loss scale (2^12 by default)
-            eng.adamw_step(self.flat, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+            eng.adamw_step(self.trainable, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                            max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm)
-            eng.train_commit(self.flat)       # bf16 operand copies (and their transposes) follow the master
-            bb = pol.model.backbone
-            bb.clear_prefix_cache()           # per-image decoder prefixes / per-prompt features computed with the OLD weights must not serve an eval between steps
-            bb.clear_prompt_cache()
+            self.lora_adapters_zero = False
+            # bf16 operand copies (and their transposes) follow the master (LoRA: W0 + s B A); per-image decoder prefixes / per-prompt features computed with
+            # the OLD weights must not serve an eval between steps
+            self.commit()
             pol._opt_state["step"] = self.step_count
             if self.step_count % self.saturation_check_every == 0:
                 # the backward's fp16 operands carry the gradient x 2^loss_scale: a clamp means the scale is too large for this model / loss

@@ -26,6 +26,9 @@ BACKBONE_PREFIX = "model.backbone.model."
 # reference's strict `load_state_dict` / `FastVLAConfig(**payload)` accept a checkpoint of an unfrozen run as it is.  Keys: "splice_image_tokens"
 # (the decoder was trained on [image tokens | text]: inference must run the same graph), "train_backbone", "train_tower".
 EXTRAS_FILE = "hip_extras.json"
+# a LoRA run (enable_backbone_training(lora_rank=...)): the adapters, the mm_projector that trains beside them and {rank, alpha, targets} in a file of their
+# own; EXTRAS_FILE names it under "lora" = {"rank", "alpha", "targets", "file"}, and a directory whose extras name adapters that are not there does not load
+LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
 
@@ -59,8 +62,20 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
     ex = read_extras(root)
     if "splice_image_tokens" in ex:
         policy.model.backbone.splice_image_tokens = bool(ex["splice_image_tokens"])
+    if ex.get("lora"):
+        load_lora_adapters(policy, root, ex["lora"])
     policy.eval()
     return policy
+
+
+def load_lora_adapters(policy: FastVLAPolicy, checkpoint_dir, lora_extras: dict) -> None:
+    """Put the policy into LoRA mode as hip_extras.json records it and load the adapter file it names.  Raises when the file (or a tensor in it) is missing:
+    running the base model in place of the fine-tuned one silently is the one thing this must not do."""
+    f = Path(checkpoint_dir) / lora_extras.get("file", LORA_FILE)
+    if not f.is_file():
+        raise FileNotFoundError(f"{Path(checkpoint_dir) / EXTRAS_FILE} records LoRA adapters (rank {lora_extras.get('rank')}) in '{f.name}', which is not there")
+    un = policy.enable_backbone_training(lora_rank=int(lora_extras["rank"]), lora_alpha=float(lora_extras["alpha"]), lora_targets=list(lora_extras["targets"]))
+    un.load_lora_state(torch.load(f, map_location="cpu"))
 
 
 def save_policy_checkpoint(policy: FastVLAPolicy, checkpoint_dir: str, include_backbone: bool = False) -> Path:
@@ -75,6 +90,15 @@ def save_policy_checkpoint(policy: FastVLAPolicy, checkpoint_dir: str, include_b
     un = getattr(policy, "_unfrozen", None)
     extras = {"splice_image_tokens": bool(policy.model.backbone.splice_image_tokens), "train_backbone": un is not None,
               "train_tower": bool(un is not None and un.train_tower)}
+    lora_cfg = getattr(un, "lora", None)
+    if lora_cfg is not None:
+        if un.lora_merged and not include_backbone:
+            raise ValueError("merge_lora() changed the decoder master: save with include_backbone=True (adapters alone no longer describe the model)")
+        if not un.lora_adapters_zero:      # (right after merge_lora() the adapters are zero and the master holds everything: a plain checkpoint)
+            torch.save(un.lora_state(), d / LORA_FILE)
+            extras["lora"] = {**lora_cfg, "file": LORA_FILE}
+        elif (d / LORA_FILE).is_file():
+            (d / LORA_FILE).unlink()
     if any(extras.values()):
         (d / EXTRAS_FILE).write_text(json.dumps(extras, indent=2))
     if include_backbone:
