@@ -368,6 +368,19 @@ int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* l
 /* W0 += s * B @ A into the master, for every adapted matrix (and its front <- lora_params' front): bit for bit the fp32 values fv_train_lora_commit rounds, so
  * fv_train_commit on the merged master builds the same operand images.  For exporting a plain checkpoint; the adapters are not reset. */
 int fv_train_lora_merge(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream s);
+/* The DIRECT LoRA step: fv_train_forward_backward's forward and input-gradient chain, with the weight gradients of the decoder replaced by
+ *     P = dY @ B,  Q = X @ A^T,  dA = s * P^T @ X,  dB = s * dY^T @ Q        (csrc/lora_direct_kernels.hip: fp32 throughout, fixed summation order)
+ * per adapted matrix, straight from the gradient's fp16 rows and the kept activations: dW' is never formed and NO full-size gradient buffer exists.  lora_grads
+ * (trainable layout, overwritten, TIMES the loss scale) receives the head and projector gradients in its front and dA / dB of every adapter; the embedding, norm and
+ * qkv-bias gradients and dW' of every decoder matrix are not computed, nor are the transposed operand copies that only a weight-gradient GEMM reads.  flat_params is the
+ * master (its head | projector front as fv_train_lora_commit left it), lora_params the trainable buffer (B and A are read from it).  fv_train_lora_project is not
+ * called in this mode; the rest of the step (all-reduce, fv_adamw_clip_step, fv_train_lora_commit) is unchanged, and so is the workspace (fv_train_workspace_bytes).
+ * Needs fv_train_lora_begin (FV_ERR_STATE otherwise) and refuses with FV_ERR_UNSUPPORTED, before anything is enqueued: backward options other than the default
+ * fv_train_set_options(2, 1, k), fv_train_set_forward_f16.  (A trained tower never gets here: fv_train_lora_begin and fv_train_tower_begin exclude each other.)
+ * The first call allocates the kernels' scratch (sized for max_batch). */
+int fv_train_lora_forward_backward(fv_handle* h, const float* flat_params, const float* lora_params, const void* tower_out, const int32_t* ids, const int32_t* lens,
+                                   const float* states, const float* targets, int B, int T, int training, float dropout_p, uint64_t seed, uint64_t offset, void* ws,
+                                   size_t ws_bytes, float* actions, float* loss, float* lora_grads, fv_stream s);
 
 /* ---- optional per-kernel-family HIP-event timing (bench.py roofline numbers) ------------------------------------- */
 enum fv_family { FV_FAM_GEMM = 0, FV_FAM_DWCONV, FV_FAM_STEM, FV_FAM_ATTN, FV_FAM_NORM, FV_FAM_ELT, FV_FAM_HEAD, FV_FAM_COUNT };

@@ -149,6 +149,14 @@ int fv_op_dw_wgrad(const void* x, const void* dy, float* dw, float* db, float* s
 int fv_op_convffn32_split(const void* x, const void* wq, const float* b1, const float* b2, const float* ls, const void* res, void* out,
                           int M, int C, float* part, size_t part_bytes, fv_stream s);
 
+/* the direct LoRA backward's kernels alone (csrc/lora_direct_kernels.hip), ONE packed tensor with the adapters inside it: kind 0 plain, 1 q|k|v (qd / kd wide column
+ * ranges of dY), 2 gate / up interleaved by 8; part_mask bit p = part p (q / gate / the matrix, k / up, v) has an adapter; a_off / b_off[3] per PART: lora_A (rank x K) /
+ * lora_B (out x rank) as float offsets into lora (parameters) and lora_grads (outputs: scale * dA, scale * dB).  dY fp16 rows [R][Np]; X [R] rows of K columns, row stride
+ * ldx: xkind 2 = split bf16 (value = X[c] + X[lo_off + c]), 3 = fp16.  scratch: the float count fv_op_lora_direct_scratch_floats(R, rank, max(Np, K)) returns. */
+int fv_op_lora_direct_scratch_floats(int R, int rank, int max_cols, size_t* out_floats);
+int fv_op_lora_direct(int kind, int part_mask, int rank, int Np, int K, int qd, int kd, const int64_t* a_off, const int64_t* b_off, const void* dY, const void* X,
+                      int xkind, int ldx, int lo_off, int R, const float* lora, float* lora_grads, float scale, float* scratch, size_t scratch_floats, fv_stream s);
+
 #ifdef __cplusplus
 }
 #endif

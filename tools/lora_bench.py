@@ -1,12 +1,14 @@
-"""Full fine-tuning step against the LoRA step of the unfrozen decoder, same process, same inputs, alternating windows -- and the LoRA kernels alone:
+"""Full fine-tuning step against the two LoRA steps (projected, direct) of the unfrozen decoder, same process, same inputs, alternating windows -- and the LoRA kernels alone:
     python tools/lora_bench.py [--model fastvlm-0.5b] [--batch 32] [--tokens 64] [--rank 16] [--steps 6] [--rounds 3] [--out FILE.json]
 full step = fv_train_forward_backward + fv_adamw_clip_step over the whole master + fv_train_commit               (tools/train_unfrozen_bench.py --no-tower)
 LoRA step = fv_train_forward_backward + fv_train_lora_project + fv_adamw_clip_step over the trainable buffer + fv_train_lora_commit
+direct    = fv_train_lora_forward_backward (dA, dB straight from activations and output gradients; no full gradient buffer) + the same AdamW + commit
 The frozen tower runs once, outside the windows (it is the same work in both modes).  Times: host clock around windows that end in a device synchronise;
 kernels alone: device events around repeated launches.  GB/s = the bytes the algorithm needs (computed from the shapes below) over that time.
 Memory: the torch allocator's peak while a mode's buffers are the only ones alive (the library's own allocations -- weights, operand copies -- are the same
 in both modes and not in that figure)."""
 import argparse
+import ctypes as C
 import json
 import sys
 import time
@@ -18,7 +20,7 @@ ROOT = Path(__file__).resolve().parent.parent
 for p in (str(ROOT), str(ROOT / "vla-from-fastvlm_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
-from fastvla_hip import FastVLAEngine, arch, lora, weights  # noqa: E402
+from fastvla_hip import FastVLAEngine, _lib, arch, lora, weights  # noqa: E402
 
 
 def main():
@@ -62,7 +64,6 @@ def main():
     for k, v in eng.head_views(flat[: eng.head_numel()]).items():
         v.copy_(torch.randn(v.shape, generator=g) * 0.02 + (1.0 if k in ("state_projection.0.weight", "fusion.1.weight") else 0.0))
     master0 = flat.clone().cpu()
-    grads = torch.zeros_like(flat)
     ws = eng.train_workspace(B, T)
     lflat = torch.zeros(ltotal, device=dev)
     lflat[:front].copy_(flat[:front])
@@ -72,8 +73,16 @@ def main():
             v.copy_((torch.randn(v.shape, generator=g) * 0.01).to(dev))
     lflat0 = lflat.clone()
     lg, lm, lv = torch.zeros_like(lflat), torch.zeros_like(lflat), torch.zeros_like(lflat)
-    n = {"full": 0, "lora": 0}
+    n = {"full": 0, "lora": 0, "direct": 0}
     hp = dict(lr=1e-5, weight_decay=1e-4, max_grad_norm=1.0, grad_scale=1.0 / eng.train_loss_scale())
+
+    def direct_step():
+        n["direct"] += 1
+        loss = eng.train_lora_forward_backward(flat, lflat, tower_out, ids, lens, states, targets, ws, training=True, dropout_p=0.1, seed=7, offset=n["direct"],
+                                               lora_grads=lg)[1]
+        eng.adamw_step(lflat, lg, lm, lv, n["direct"], **hp)
+        eng.train_lora_commit(flat, lflat)
+        return loss
 
     def fb(off):
         return eng.train_forward_backward(flat, tower_out, ids, lens, states, targets, ws, training=True, dropout_p=0.1, seed=7, offset=off, flat_grads=grads)[1]
@@ -94,7 +103,13 @@ def main():
         torch.cuda.synchronize()
         return 1e3 * (time.perf_counter() - t0) / k, float(loss)
 
-    # ---- LoRA mode alone in memory: its peak, then its warm-up
+    # ---- direct LoRA mode alone in memory (the full-size gradient buffer does not exist yet): its peak, then its warm-up
+    window(direct_step, args.warmup)
+    mem_direct = torch.cuda.max_memory_allocated() - base_mem
+    # ---- projected LoRA mode: the full gradient buffer joins
+    torch.cuda.reset_peak_memory_stats()
+    grads = torch.zeros_like(flat)
+    lflat.copy_(lflat0); lm.zero_(); lv.zero_(); eng.train_lora_commit(flat, lflat)
     window(lora_step, args.warmup)
     mem_lora = torch.cuda.max_memory_allocated() - base_mem
     # ---- full mode: Adam's moments over the whole master join
@@ -124,7 +139,10 @@ def main():
         f_ms, f_loss = window(full_step, args.steps)
         to_lora()
         l_ms, l_loss = window(lora_step, args.steps)
-        rounds.append({"full_ms": round(f_ms, 2), "lora_ms": round(l_ms, 2), "full_loss": f_loss, "lora_loss": l_loss})
+        to_lora()
+        d_ms, d_loss = window(direct_step, args.steps)
+        rounds.append({"full_ms": round(f_ms, 2), "lora_ms": round(l_ms, 2), "lora_direct_ms": round(d_ms, 2), "full_loss": f_loss, "lora_loss": l_loss,
+                       "lora_direct_loss": d_loss})
     to_lora()
 
     # ---- the kernels alone
@@ -158,12 +176,51 @@ def main():
     t_merge = timed(lambda: eng.train_lora_merge(grads, lflat), args.kernel_reps)     # (into the gradient buffer: a scratch target of the master's size)
     t_adam_full = timed(lambda: eng.adamw_step(flat, grads, m, v, 1, **hp), max(3, args.kernel_reps // 4))
     t_adam_lora = timed(lambda: eng.adamw_step(lflat, lg, lm, lv, 1, **hp), args.kernel_reps)
+    # the direct backward's kernels alone (csrc/lora_direct_kernels.hip), through the test-only op library: the four packed tensors of ONE layer at this step's
+    # row count, on random operands, times the layer count
+    t_direct = None
+    try:
+        ops = _lib.load_testops()
+        l_ = model.llm
+        H, I, qd, kd = l_.hidden, l_.inter, l_.heads * l_.head_dim, l_.kv_heads * l_.head_dim
+        R = B * (model.tower.num_tokens + T)
+        tmask = lora.target_mask(args.targets)
+        packs = [(1, tmask & 7, (qd, kd, kd), qd + 2 * kd, H, 2), (0, tmask >> 3 & 1, (H, 0, 0), H, qd, 2), (2, tmask >> 4 & 3, (I, I, 0), 2 * I, H, 2),
+                 (0, tmask >> 6 & 1, (H, 0, 0), H, I, 3)]
+        nfl = C.c_size_t()
+        _lib.check(ops.fv_op_lora_direct_scratch_floats(R, r, max(2 * I, qd + 2 * kd, H), C.byref(nfl)), "fv_op_lora_direct_scratch_floats")
+        scratch = torch.empty(nfl.value, device=dev)
+        calls = []
+        for kind, pm, outs, Np, K, xk in packs:
+            if not pm:
+                continue
+            dY = (torch.randn(R, Np, device=dev) * 0.1).to(torch.float16)
+            X = torch.randn(R, 2 * K if xk == 2 else K, device=dev).to(torch.bfloat16 if xk == 2 else torch.float16)
+            ao, bo, off = [0, 0, 0], [0, 0, 0], 0
+            for p_ in range(3):
+                if outs[p_] and pm >> p_ & 1:
+                    ao[p_] = off; off += r * K
+                    bo[p_] = off; off += outs[p_] * r
+            par, out = torch.randn(off, device=dev) * 0.01, torch.zeros(off, device=dev)
+            calls.append((kind, pm, Np, K, (C.c_int64 * 3)(*ao), (C.c_int64 * 3)(*bo), dY, X, xk, 2 * K if xk == 2 else K, K if xk == 2 else 0, par, out))
+
+        def direct_kernels():
+            st_ = torch.cuda.current_stream().cuda_stream
+            for kind, pm, Np, K, ao, bo, dY, X, xk, ldx, lo_off, par, out in calls:
+                _lib.check(ops.fv_op_lora_direct(kind, pm, r, Np, K, qd, kd, ao, bo, dY.data_ptr(), X.data_ptr(), xk, ldx, lo_off, R, par.data_ptr(), out.data_ptr(), 1.0,
+                                                 scratch.data_ptr(), scratch.numel(), st_), "fv_op_lora_direct")
+
+        t_direct = L * timed(direct_kernels, max(3, args.kernel_reps // 4))
+        del calls, scratch
+    except (OSError, AttributeError) as exc:      # (the op library is test infrastructure: a tree without it still measures the steps)
+        print(f"[lora_bench] direct kernels alone not measured: {exc}", file=sys.stderr)
     med = lambda xs: sorted(xs)[len(xs) // 2]   # noqa: E731
     res = {"model": args.model, "batch": B, "tokens": model.tower.num_tokens + T, "rank": r, "targets": list(names), "steps_per_window": args.steps, "rounds": rounds,
            "full_ms_per_step": med([x["full_ms"] for x in rounds]), "lora_ms_per_step": med([x["lora_ms"] for x in rounds]),
+           "lora_direct_ms_per_step": med([x["lora_direct_ms"] for x in rounds]),
            "full_numel": total, "trainable_numel": ltotal, "adapter_numel": adapters, "exchange_mb": {"full": round(total * 4 / 1e6, 1), "lora": round(ltotal * 4 / 1e6, 1)},
-           "torch_peak_gb": {"lora": round(mem_lora / 1e9, 2), "full": round(mem_full / 1e9, 2)},
-           "kernels_ms": {"lora_project": round(t_proj, 3), "lora_commit": round(t_lcommit, 3), "commit": round(t_commit, 3), "lora_merge": round(t_merge, 3),
+           "torch_peak_gb": {"lora_direct": round(mem_direct / 1e9, 2), "lora": round(mem_lora / 1e9, 2), "full": round(mem_full / 1e9, 2)},
+           "kernels_ms": {"lora_direct_all_layers": None if t_direct is None else round(t_direct, 3), "lora_project": round(t_proj, 3), "lora_commit": round(t_lcommit, 3), "commit": round(t_commit, 3), "lora_merge": round(t_merge, 3),
                           "adamw_full": round(t_adam_full, 3), "adamw_lora": round(t_adam_lora, 3)},
            "hbm_gb_s": {"lora_project": round(proj_bytes / t_proj / 1e6, 1), "lora_commit": round(commit_bytes / t_lcommit / 1e6, 1), "commit": round(commit_bytes / t_commit / 1e6, 1)},
            "bytes_gb": {"lora_project": round(proj_bytes / 1e9, 3), "commit": round(commit_bytes / 1e9, 3)}}

@@ -1,7 +1,8 @@
 """One rank of a data-parallel LoRA training step (fv_train_lora_*; vla_fastvlm/training/unfrozen.py) -- the worker tests/test_gpu_lora.py starts once alone and
 twice as two gloo ranks on one GPU (under RCCL on a multi-GPU node: torchrun --nproc-per-node N tools/lora_dp_worker.py --out DIR).  Every rank builds the same
 `small` policy in LoRA mode with the same non-zero adapters, takes its slice of ONE fixed batch, runs FastVLAPolicy.fused_train_step -- forward/backward,
-projection onto the adapters, ONE all-reduce of the trainable buffer, clip + AdamW, adapted commit -- and writes its reduced gradient and updated buffers to --out."""
+projection onto the adapters (--direct: adapter gradients straight from the backward instead), ONE all-reduce of the trainable buffer, clip + AdamW, adapted
+commit -- and writes its reduced gradient and updated buffers to --out."""
 import argparse
 import os
 import sys
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--backend", default="gloo")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--rank-dim", type=int, default=8)
+    ap.add_argument("--direct", action="store_true", help="the direct LoRA backward (fv_train_lora_forward_backward): no full-size gradient buffer, no projection")
     args = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -41,7 +43,8 @@ def main():
     torch.manual_seed(5)
     pol = FastVLAPolicy(FastVLAConfig(vlm_model_name="synthetic:small:41", hidden_dim=64, fusion_dim=64, dropout=0.0, freeze_backbone=False)).to(dev)
     pol.train()
-    st = pol.enable_backbone_training(lora_rank=args.rank_dim)
+    st = pol.enable_backbone_training(lora_rank=args.rank_dim, lora_direct=args.direct)
+    assert (st.g is None) == bool(args.direct)
     # lora_B != 0, the same on every rank: with PEFT's B = 0 start every dA would be exactly zero
     g = torch.Generator().manual_seed(17)
     for name, v in lora.adapter_views(st.lflat, st.lora_tensors).items():

@@ -95,6 +95,8 @@ struct LoraState {   // fv_train_lora_* (lora_path.inc): adapters on the decoder
   fv::CommitDesc* rest = nullptr; int rest_n = 0, rest_tiles = 0;            // device: every other tensor (plain commit)
   float* scratch = nullptr; size_t scratch_floats = 0; std::vector<LoraGroup> groups;
   int64_t front = 0, total = 0;                                              // head + projector floats in front of the adapters; the trainable buffer's size
+  std::vector<fv::LoraDirectPack> packs;                                     // host: [layer][q|k|v, o, gate/up, down] -- the direct backward's calls (nm = 0: no adapter inside)
+  float* dscratch = nullptr; size_t dscratch_floats = 0;                     // device: the direct backward's P | Q | partial sums (allocated by its first step)
 };
 struct TrainState {
   LoraState lora;

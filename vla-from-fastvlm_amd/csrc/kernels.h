@@ -207,6 +207,21 @@ int launch_lora_commit(const LoraCommitDesc* desc_dev, int ndesc, int ntiles, co
 int launch_lora_merge(const LoraCommitDesc* desc_dev, int ndesc, int ntiles, const LoraMat* mats_dev, float* flat, const float* lora, int rank, float scale,
                       hipStream_t s);
 
+// ---- the direct LoRA backward (lora_direct_kernels.hip; fv_train_lora_forward_backward): dA, dB straight from dY and X, dW' never formed --------------------
+// ONE packed tensor of one layer and the adapters inside it ("slots", in part order: q, k, v / gate, up / the matrix itself)
+struct LoraDirectPack {
+  int kind;              // 0 plain, 1 q|k|v column ranges of dY (qd / kd wide), 2 gate / up interleaved by 8 (as LoraCommitDesc::kind)
+  int nm, r, NCp;        // adapters in this call (1 .. 3), rank, nm * r rounded up to 32 (the width of the P / Q arrays)
+  int Np, K;             // columns of dY (the packed tensor's rows) and of X (its columns); multiples of 32
+  int qd, kd;
+  int slot_of_part[3];   // part (0 q / gate / plain, 1 k / up, 2 v) -> slot, -1 = that part is not a target
+  long long a_off[3], b_off[3];   // per slot: lora_A / lora_B in the trainable flat buffer (parameters and gradients alike), floats
+};
+size_t lora_direct_scratch_floats(long R, int rank, int max_cols);   // P | Q | partial sums for R rows; max_cols = the widest of any call's Np and K
+// dY: fp16 rows [R][Np].  X: xkind 2 = split bf16 rows (value = X[c] + X[lo_off + c]), 3 = fp16 rows; row stride ldx.  lgrads receives s . dA, s . dB of every slot
+int launch_lora_direct(const LoraDirectPack& pk, const bf16_t* dY, const bf16_t* X, int xkind, int ldx, int lo_off, int R, const float* lora, float* lgrads,
+                       float scale, float* scratch, size_t scratch_floats, hipStream_t s);
+
 // ---- tower backward (tower_bwd_kernels.hip; SURVEY.md 8f-4, second slice) ---------------------------------------------------------
 // gradients NHWC fp16 (loss-scaled), activations NHWC bf16, weight gradients fp32 by fixed-order partial sums (no atomics)
 size_t dw_bwd_scratch_floats(int B, int Ho, int Wo, int Co, int k);

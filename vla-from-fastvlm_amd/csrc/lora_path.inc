@@ -8,7 +8,9 @@
 // whose front (head + projector) has the master's own offsets; gradients and Adam's m / v mirror THAT buffer.  One step:
 //     fv_train_forward_backward (unchanged: full dW' into the full gradient buffer)  ->  fv_train_lora_project (dA, dB; head / projector gradients copied)
 //     ->  all-reduce + fv_adamw_clip_step over the trainable buffer  ->  fv_train_lora_commit (operand images from W0 + s . B . A).
-// Kernels: lora_kernels.hip.
+// The DIRECT mode replaces the first two by fv_train_lora_forward_backward: the same forward and dgrad chain (train_path.inc, ONE body), dA / dB of every adapter
+// straight from the gradient's fp16 rows and the kept activations (lora_direct_kernels.hip) into the trainable-layout gradient buffer; no full gradient buffer.
+// Kernels: lora_kernels.hip, lora_direct_kernels.hip.
 
 namespace {
 
@@ -148,6 +150,60 @@ int build_lora_tables(fv_handle* h) {
     ls.scratch = static_cast<float*>(p); ls.scratch_floats = scratch;
   }
   ls.front = front; ls.total = total;
+  // the direct backward's calls: one per packed tensor and layer, the adapters inside it as slots in part order
+  {
+    const fv_model_desc& d = h->d;
+    const int qd = d.llm_heads * d.llm_head_dim, kd = d.llm_kv_heads * d.llm_head_dim;
+    ls.packs.assign((size_t)d.llm_layers * 4, fv::LoraDirectPack{});
+    for (int l = 0; l < d.llm_layers; ++l)
+      for (int k = 0; k < 7; ++k) {
+        if (!(ls.mask >> k & 1)) continue;
+        const int which = k < 3 ? 0 : (k == 3 ? 1 : (k < 6 ? 2 : 3));
+        fv::LoraDirectPack& pk = ls.packs[(size_t)l * 4 + which];
+        if (pk.nm == 0) {
+          pk.kind = lg[k].kind; pk.r = rank; pk.qd = qd; pk.kd = kd; pk.K = lg[k].in;
+          pk.Np = which == 0 ? qd + 2 * kd : (which == 2 ? 2 * d.llm_inter : lg[k].out);
+          pk.slot_of_part[0] = pk.slot_of_part[1] = pk.slot_of_part[2] = -1;
+        }
+        const std::string pre = "model.layers." + std::to_string(l) + "." + LORA_TARGET_NAMES[k];
+        pk.slot_of_part[lg[k].part] = pk.nm;
+        pk.a_off[pk.nm] = loff.at(pre + ".lora_A.weight");
+        pk.b_off[pk.nm] = loff.at(pre + ".lora_B.weight");
+        ++pk.nm;
+        pk.NCp = (pk.nm * rank + 31) / 32 * 32;
+      }
+  }
+  return FV_OK;
+}
+
+// the direct backward's scratch: allocated once, for the largest step the handle admits (max_batch x (image tokens + max_text_tokens) rows)
+int lora_direct_scratch(fv_handle* h, float** scratch, size_t* floats) {
+  LoraState& ls = h->train.lora;
+  const fv_model_desc& d = h->d;
+  const int side = d.image_size >> (d.tower_stages + 1);
+  const long rmax = (long)d.max_batch * (side * side + d.max_text_tokens);
+  const int qkvw = (d.llm_heads + 2 * d.llm_kv_heads) * d.llm_head_dim;
+  const int wmax = std::max(std::max(2 * d.llm_inter, qkvw), std::max(d.llm_hidden, d.llm_heads * d.llm_head_dim));
+  const size_t need = fv::lora_direct_scratch_floats(rmax, ls.rank, wmax);
+  if (need > ls.dscratch_floats) {
+    void* p = nullptr;
+    FV_HIP_CHECK(hipSetDevice(h->device));
+    FV_TRY(dev_alloc(h, need * 4, &p));
+    ls.dscratch = static_cast<float*>(p); ls.dscratch_floats = need;
+  }
+  *scratch = ls.dscratch; *floats = ls.dscratch_floats;
+  return FV_OK;
+}
+
+// dA, dB of the adapters inside packed tensor `which` (0 q|k|v, 1 o, 2 gate/up, 3 down) of layer l; nothing at all when none of its matrices is a target
+int lora_direct_call(fv_handle* h, int l, int which, const bf16_t* dY16, const bf16_t* X, int xkind, int ldx, int lo_off, int R, const float* lora_params,
+                     float* lora_grads, hipStream_t s) {
+  const LoraState& ls = h->train.lora;
+  const fv::LoraDirectPack& pk = ls.packs[(size_t)l * 4 + which];
+  if (pk.nm == 0) return FV_OK;
+  // flop: the four skinny products; bytes: dY and X twice each
+  FV_P(FV_FAM_GEMM, 4.0 * R * pk.NCp * ((double)pk.Np + pk.K), 2.0 * R * (2.0 * pk.Np + (xkind == 2 ? 4.0 : 2.0) * pk.K),
+       fv::launch_lora_direct(pk, dY16, X, xkind, ldx, lo_off, R, lora_params, lora_grads, ls.scale, ls.dscratch, ls.dscratch_floats, s));
   return FV_OK;
 }
 
@@ -212,6 +268,25 @@ int fv_train_lora_project(fv_handle* h, const float* flat_grads_full, const floa
   for (const LoraGroup& g : ls.groups)
     FV_TRY(fv::launch_lora_project(ls.mats, g.m0, g.m1, g.strip_begin, g.nstrips, g.max_in, flat_grads_full, lora_params, lora_grads, ls.scratch, ls.rank, ls.scale, s));
   return FV_OK;
+}
+
+int fv_train_lora_forward_backward(fv_handle* h, const float* flat_params, const float* lora_params, const void* tower_out, const int32_t* ids, const int32_t* lens,
+                                   const float* states, const float* targets, int B, int T, int training, float dropout_p, uint64_t seed, uint64_t offset, void* ws,
+                                   size_t ws_bytes, float* actions, float* loss, float* lora_grads, fv_stream st) {
+  HandleScope _hs(h);
+  FV_TRY(lora_check(h));
+  if (!lora_params || !lora_grads) return fv_fail(FV_ERR_ARG, "fv_train_lora_forward_backward: null pointer");
+  if (((uintptr_t)lora_params | (uintptr_t)lora_grads) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_forward_backward: buffers must be 16-byte aligned");
+  // refused HERE, before anything is enqueued
+  if (!fp16_backward(h))
+    return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_forward_backward: the direct LoRA backward runs on the default one-pass fp16 backward (fv_train_set_options 2, 1, k)");
+  if (h->train.fwd_f16) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_forward_backward: not together with the fp16 training forward (fv_train_set_forward_f16)");
+  // (a trained tower cannot reach this point: fv_train_lora_begin refuses after fv_train_tower_begin and the other way round, so lora_check has answered already)
+  float* scr = nullptr;
+  size_t scr_floats = 0;
+  FV_TRY(lora_direct_scratch(h, &scr, &scr_floats));
+  return train_forward_backward_impl(h, flat_params, tower_out, ids, lens, states, targets, B, T, training, dropout_p, seed, offset, ws, ws_bytes, actions, loss, nullptr,
+                                     nullptr, nullptr, st, lora_params, lora_grads);
 }
 
 int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream st) {

@@ -208,4 +208,27 @@ int fv_op_convffn32_split(const void* x, const void* wq, const float* b1, const 
                               static_cast<bf16_t*>(out), M, C, 4 * C, static_cast<hipStream_t>(s), part, part_bytes);
 }
 
+// the direct LoRA backward's kernels alone (lora_direct_kernels.hip): ONE packed tensor (kind 0 plain, 1 q|k|v, 2 gate/up) with adapters on the parts in
+// part_mask (bit p: part p); a_off / b_off per PART (floats into lora / lora_grads).  dY fp16 rows [R][Np]; X split bf16 (xkind 2) or fp16 (xkind 3) rows
+int fv_op_lora_direct_scratch_floats(int R, int rank, int max_cols, size_t* out_floats) {
+  if (!out_floats || R <= 0 || rank < 1 || rank > 64 || max_cols <= 0) return fv_fail(FV_ERR_ARG, "fv_op_lora_direct_scratch_floats: bad arguments");
+  *out_floats = fv::lora_direct_scratch_floats(R, rank, max_cols);
+  return FV_OK;
+}
+int fv_op_lora_direct(int kind, int part_mask, int rank, int Np, int K, int qd, int kd, const int64_t* a_off, const int64_t* b_off, const void* dY, const void* X,
+                      int xkind, int ldx, int lo_off, int R, const float* lora, float* lora_grads, float scale, float* scratch, size_t scratch_floats, fv_stream s) {
+  if (!a_off || !b_off) return fv_fail(FV_ERR_ARG, "fv_op_lora_direct: null offsets");
+  const int nparts = kind == 1 ? 3 : (kind == 2 ? 2 : 1);
+  if (kind < 0 || kind > 2 || part_mask <= 0 || part_mask >= (1 << nparts)) return fv_fail(FV_ERR_ARG, "fv_op_lora_direct: kind %d, part mask 0x%x", kind, part_mask);
+  fv::LoraDirectPack pk{};
+  pk.kind = kind; pk.r = rank; pk.Np = Np; pk.K = K; pk.qd = qd; pk.kd = kd;
+  for (int p = 0; p < 3; ++p) {
+    pk.slot_of_part[p] = -1;
+    if (p < nparts && (part_mask >> p & 1)) { pk.slot_of_part[p] = pk.nm; pk.a_off[pk.nm] = a_off[p]; pk.b_off[pk.nm] = b_off[p]; ++pk.nm; }
+  }
+  pk.NCp = (pk.nm * rank + 31) / 32 * 32;
+  return fv::launch_lora_direct(pk, static_cast<const bf16_t*>(dY), static_cast<const bf16_t*>(X), xkind, ldx, lo_off, R, lora, lora_grads, scale, scratch,
+                                scratch_floats, static_cast<hipStream_t>(s));
+}
+
 }  // extern "C"

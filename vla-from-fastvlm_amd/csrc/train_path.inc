@@ -45,6 +45,8 @@ int tower_export(fv_handle* h, float* flat, hipStream_t s);
 int tower_bucket_count(const fv_handle* h);
 // lora_path.inc (the LoRA mode): its commit tables name the same operand copies as fv_train_commit's and are rebuilt with it
 int build_lora_tables(fv_handle* h);
+int lora_direct_call(fv_handle* h, int l, int which, const bf16_t* dY16, const bf16_t* X, int xkind, int ldx, int lo_off, int R, const float* lora_params,
+                     float* lora_grads, hipStream_t s);
 
 std::vector<TrainTensor> train_tensors(fv_handle* h, int64_t* total) {
   const fv_model_desc& d = h->d;
@@ -108,6 +110,7 @@ struct TrainPlan {
   size_t pre0, hsplit, tok;                                   // projector stash
   size_t act_s, dx, dtmp, dsplit, AT, XT, dqkv, attn_scr, delta, scr, pooled, dpooled, xg, dxg, head_saved, head_scr, splitk;
   size_t splitk_bytes, total;
+  size_t wmax;   // the widest gradient operand (columns): the dsplit scratch holds rows x 3 wmax 16-bit values
 };
 
 TrainPlan plan_train(const fv_handle* h, int B, int T) {
@@ -132,6 +135,7 @@ TrainPlan plan_train(const fv_handle* h, int B, int T) {
   p.act_s = 0;
   p.dx = take(rows * H * 4);
   p.dtmp = take(std::max(rows * std::max(std::max(I, H), qd), (size_t)p.RI * CO) * 4);   // (also dL/d(tower_out) in fp32 on its way to the tower's backward)
+  p.wmax = wmax;
   p.dsplit = take(rows * 3 * wmax * 2);   // the split-bf16 rows of the widest gradient operand, and room for its fp16 rows behind them
   p.AT = take(wmax * 2 * rmax * 2);
   p.XT = take(xmax * rmax * 2);
@@ -423,22 +427,32 @@ int fv_train_workspace_bytes(fv_handle* h, int B, int T, size_t* out_bytes) {
   return FV_OK;
 }
 
-int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void* tower_out_v, const int32_t* ids, const int32_t* lens,
-                              const float* states, const float* targets, int B, int T, int training, float dropout_p, uint64_t seed,
-                              uint64_t offset, void* ws_v, size_t ws_bytes, float* actions, float* loss, float* flat_grads, fv_bucket_cb cb,
-                              void* user, fv_stream st) {
+// ONE body for fv_train_forward_backward and fv_train_lora_forward_backward (lora_path.inc).  lora_grads != null selects the DIRECT LoRA backward: the same forward
+// and dgrad chain; the head and projector gradients go to lora_grads (same offsets); every decoder weight gradient is replaced by lora_direct_call (dA, dB straight
+// from the gradient's fp16 rows and the kept activation) or dropped (embedding, norms, qkv bias, matrices without an adapter), the fp16 COLUMN copies of gradient and
+// activation are not made, and flat_grads does not exist.
+static int train_forward_backward_impl(fv_handle* h, const float* flat_params, const void* tower_out_v, const int32_t* ids, const int32_t* lens,
+                                       const float* states, const float* targets, int B, int T, int training, float dropout_p, uint64_t seed,
+                                       uint64_t offset, void* ws_v, size_t ws_bytes, float* actions, float* loss, float* flat_grads, fv_bucket_cb cb,
+                                       void* user, fv_stream st, const float* lora_params, float* lora_grads) {
   HandleScope _hs(h);
   TrainScope _ts(h);
   FV_TRY(train_check(h));
-  if (!flat_params || !tower_out_v || !ids || !lens || !states || !targets || !ws_v || !actions || !loss || !flat_grads)
-    return fv_fail(FV_ERR_ARG, "fv_train_forward_backward: null pointer");
+  const bool direct = lora_grads != nullptr;
+  const char* who = direct ? "fv_train_lora_forward_backward" : "fv_train_forward_backward";
+  float* gbuf = direct ? lora_grads : flat_grads;    // where the head's and the projector's gradients go (the two layouts share their front)
+  if (!flat_params || !tower_out_v || !ids || !lens || !states || !targets || !ws_v || !actions || !loss || !gbuf)
+    return fv_fail(FV_ERR_ARG, "%s: null pointer", who);
   const fv_model_desc& d = h->d;
-  if (B <= 0 || B > d.max_batch || T <= 0 || T % 8 || T > d.max_text_tokens) return fv_fail(FV_ERR_ARG, "fv_train_forward_backward: bad B / T (T must be a multiple of 8)");
-  // refused HERE, before anything is enqueued or any bucket's all-reduce is launched (launch_embed_bwd runs at the very end of the backward)
+  if (B <= 0 || B > d.max_batch || T <= 0 || T % 8 || T > d.max_text_tokens) return fv_fail(FV_ERR_ARG, "%s: bad B / T (T must be a multiple of 8)", who);
+  // refused HERE, before anything is enqueued or any bucket's all-reduce is launched (launch_embed_bwd runs at the very end of the backward).  The direct LoRA
+  // backward computes no embedding gradient, but fv_train_workspace_bytes sizes the workspace for both entry points and admits no larger step: same limit, its own words
+  if (direct && (long)B * T > 16384)
+    return fv_fail(FV_ERR_UNSUPPORTED, "%s: %ld text positions per step (fv_train_workspace_bytes admits B * T <= 16384)", who, (long)B * T);
   if ((long)B * T > 16384) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_forward_backward: %ld text positions per step (the embedding gradient keeps the batch's ids in 64 KB of LDS: B * T <= 16384)", (long)B * T);
   const TrainPlan tp = plan_train(h, B, T);
   if (tp.total > ws_bytes) return fv_fail(FV_ERR_STATE, "training workspace too small (%zu > %zu)", tp.total, ws_bytes);
-  if (((uintptr_t)ws_v | (uintptr_t)flat_grads | (uintptr_t)flat_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_forward_backward: buffers must be 16-byte aligned");
+  if (((uintptr_t)ws_v | (uintptr_t)gbuf | (uintptr_t)flat_params) & 15) return fv_fail(FV_ERR_ARG, "%s: buffers must be 16-byte aligned", who);
   if (tp.Tt > h->rope_rows) return fv_fail(FV_ERR_ARG, "sequence of %d tokens exceeds the RoPE table (%d)", tp.Tt, h->rope_rows);
   hipStream_t s = static_cast<hipStream_t>(st);
   char* ws = static_cast<char*>(ws_v);
@@ -450,7 +464,7 @@ int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void
   int64_t total = 0;
   const std::vector<TrainTensor> tt = train_tensors(h, &total);
   auto G = [&](const std::string& name) -> float* {
-    for (const TrainTensor& t : tt) if (t.name == name) return flat_grads + t.off;
+    for (const TrainTensor& t : tt) if (t.name == name) return (direct && t.bucket > TB_PROJ) ? nullptr : gbuf + t.off;   // direct: no gradient behind the projector
     return nullptr;
   };
   auto bucket_done = [&](int bucket) {
@@ -565,7 +579,7 @@ int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void
                                                      head_saved, s, io));
 
   // ------------------------------------------------------------------------------------------------ backward
-  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p, head_saved, loss, flat_grads, head_scr, s, dpooled,
+  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p, head_saved, loss, gbuf, head_scr, s, dpooled,
                                                       std::ldexp(1.0f, h->train.loss_scale_log2)));
   bucket_done(TB_HEAD);
   // final norm on the pooled rows; the residual-gradient stream starts as zero everywhere else
@@ -579,7 +593,18 @@ int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void
     const TrainLayerT& Tw = h->train.layers[l];
     const std::string pre = "model.layers." + std::to_string(l) + ".";
     // down projection: x_out = x_mid + act . Wd^T
-    if (fp16_backward(h)) {
+    if (direct) {
+      // gradient ROWS only (no column copies: nothing here runs a weight-gradient GEMM).  dx's fp16 rows go into the last third of the dsplit scratch, so that they
+      // outlive the SwiGLU backward, which writes d gate/up's rows at its start and silu(gate) * up as fp16 rows (the down adapters' activation) into the XT scratch
+      bf16_t* dx16 = dsplit + (size_t)rows * 2 * tp.wmax;
+      bf16_t* act16 = reinterpret_cast<bf16_t*>(ws + tp.XT);
+      FV_P(FV_FAM_ELT, 0.0, (double)rows * H * 6, fv::launch_rows_to_f16(dx, 0, H, 0, dx16, H, rows, H, h->f16_flags, s));
+      FV_TRY(dgrad(h, tp, ws, nullptr, 0, H, Tw.downT, I, rows, dtmp, s, nullptr, Tw.downT16, dx16));  // d act [rows][I]
+      FV_P(FV_FAM_ELT, 18.0 * rows * I, 16.0 * rows * I, fv::launch_swiglu_bwd_rows(GU(l), 1, dtmp, rows, rows, I, dsplit, act16, h->f16_flags, s));
+      FV_TRY(lora_direct_call(h, l, 3, dx16, act16, 3, I, 0, rows, lora_params, lora_grads, s));
+      FV_TRY(dgrad(h, tp, ws, nullptr, 0, I2, Tw.guT, H, rows, dtmp, s, nullptr, Tw.guT16, dsplit)); // d xn2 [rows][H]
+      FV_TRY(lora_direct_call(h, l, 2, dsplit, XN2(l), 2, 2 * H, H, rows, lora_params, lora_grads, s));
+    } else if (fp16_backward(h)) {
       // dx -> fp16 rows + columns in one pass; d act; then the SwiGLU backward writes d gate/up straight into the two fp16 operands its consumers
       // read (rows for the dgrad, columns for the wgrad) AND act^T for the down projection's wgrad, which therefore runs after it
       bf16_t* at0 = reinterpret_cast<bf16_t*>(ws + tp.AT);
@@ -603,7 +628,11 @@ int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void
     FV_P(FV_FAM_NORM, 12.0 * rows * H, 20.0 * rows * H,
          fv::launch_rmsnorm_bwd(X_mid(l), Lw.ln2, dtmp, dx, dx, G(pre + "post_attention_layernorm.weight"), scr, rows, H, d.rms_eps, s));
     // o projection: x_mid = x_in + att . Wo^T
-    if (fp16_backward(h)) {
+    if (direct) {
+      FV_P(FV_FAM_ELT, 0.0, (double)rows * H * 6, fv::launch_rows_to_f16(dx, 0, H, 0, dsplit, H, rows, H, h->f16_flags, s));
+      FV_TRY(dgrad(h, tp, ws, nullptr, 0, H, Tw.oT, qd, rows, dtmp, s, nullptr, Tw.oT16, dsplit));   // d att [rows][qd]
+      FV_TRY(lora_direct_call(h, l, 1, dsplit, ATT(l), 2, 2 * qd, qd, rows, lora_params, lora_grads, s));
+    } else if (fp16_backward(h)) {
       FV_TRY(grad_operands(h, tp, ws, dx, H, H, rows, reinterpret_cast<bf16_t*>(ws + tp.AT), s));
       FV_TRY(dgrad(h, tp, ws, nullptr, 0, H, Tw.oT, qd, rows, dtmp, s, nullptr, Tw.oT16, dsplit));   // d att [rows][qd]
       FV_TRY(wgrad(h, tp, ws, nullptr, 0, H, ATT(l), 2 * qd, qd, rows, G(pre + "self_attn.o_proj.weight"), s, nullptr, true));
@@ -614,8 +643,12 @@ int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void
     FV_P(FV_FAM_ATTN, 8.0 * B * (double)Tt * Tt * qd, 4.0 * rows * (2 * qkvw + 2 * qd),
          fv::launch_attention_bwd(QKV(l), qkvw, ATT(l), ATT(l) + qd, 2 * qd, dtmp, qd, LSE(l), delta, dqkv, B, Tt, d.llm_heads, d.llm_kv_heads, D, lens, Ni,
                                   att_scale, h->rope, s, apart, ws + tp.attn_scr));
-    FV_TRY(fv::launch_colsum(dqkv, qkvw, rows, qkvw, G(pre + "self_attn.qkv_proj.bias"), colscr, s));
-    if (fp16_backward(h)) {
+    if (!direct) FV_TRY(fv::launch_colsum(dqkv, qkvw, rows, qkvw, G(pre + "self_attn.qkv_proj.bias"), colscr, s));
+    if (direct) {
+      FV_P(FV_FAM_ELT, 0.0, (double)rows * qkvw * 6, fv::launch_rows_to_f16(dqkv, 0, qkvw, 0, dsplit, qkvw, rows, qkvw, h->f16_flags, s));
+      FV_TRY(dgrad(h, tp, ws, nullptr, 0, qkvw, Tw.qkvT, H, rows, dtmp, s, nullptr, Tw.qkvT16, dsplit));   // d xn1 [rows][H]
+      FV_TRY(lora_direct_call(h, l, 0, dsplit, XN1(l), 2, 2 * H, H, rows, lora_params, lora_grads, s));
+    } else if (fp16_backward(h)) {
       FV_TRY(grad_operands(h, tp, ws, dqkv, qkvw, qkvw, rows, reinterpret_cast<bf16_t*>(ws + tp.AT), s));
       FV_TRY(dgrad(h, tp, ws, nullptr, 0, qkvw, Tw.qkvT, H, rows, dtmp, s, nullptr, Tw.qkvT16, dsplit));   // d xn1 [rows][H]
       FV_TRY(wgrad(h, tp, ws, nullptr, 0, qkvw, XN1(l), f16fwd ? H : 2 * H, H, rows, G(pre + "self_attn.qkv_proj.weight"), s, nullptr, true, nullptr, false, f16fwd ? 3 : -1));
@@ -627,8 +660,8 @@ int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void
          fv::launch_rmsnorm_bwd(X_in(l), Lw.ln1, dtmp, dx, dx, G(pre + "input_layernorm.weight"), scr, rows, H, d.rms_eps, s));
     bucket_done(TB_LAYER0 + l);
   }
-  // embedding rows of the text positions
-  {
+  // embedding rows of the text positions (direct LoRA: the embedding is frozen and its gradient -- memset and scatter -- is not computed)
+  if (!direct) {
     float* gE = G("model.embed_tokens.weight");
     FV_HIP_CHECK(hipMemsetAsync(gE, 0, (size_t)d.llm_vocab * H * 4, s));
     FV_TRY(fv::launch_embed_bwd(ids, lens, dx, gE, B, T, Ni, H, d.llm_vocab, s));
@@ -660,6 +693,18 @@ int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void
     }
   }
   return FV_OK;
+}
+
+int fv_train_forward_backward(fv_handle* h, const float* flat_params, const void* tower_out, const int32_t* ids, const int32_t* lens,
+                              const float* states, const float* targets, int B, int T, int training, float dropout_p, uint64_t seed,
+                              uint64_t offset, void* ws, size_t ws_bytes, float* actions, float* loss, float* flat_grads, fv_bucket_cb cb,
+                              void* user, fv_stream st) {
+  if (h && h->train.ready && !flat_grads) {   // (null flat_grads is the impl's switch to the direct LoRA backward: not through this entry point)
+    HandleScope _hs(h);
+    return fv_fail(FV_ERR_ARG, "fv_train_forward_backward: null pointer");
+  }
+  return train_forward_backward_impl(h, flat_params, tower_out, ids, lens, states, targets, B, T, training, dropout_p, seed, offset, ws, ws_bytes, actions, loss,
+                                     flat_grads, cb, user, st, nullptr, nullptr);
 }
 
 }  // extern "C"

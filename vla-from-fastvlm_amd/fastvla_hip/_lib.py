@@ -124,6 +124,7 @@ SIGNATURES = {
     "fv_train_lora_project": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "fv_train_lora_commit": (_i, [_vp, _vp, _vp, _vp]),
     "fv_train_lora_merge": (_i, [_vp, _vp, _vp, _vp]),
+    "fv_train_lora_forward_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _vp, C.c_size_t, _vp, _vp, _vp, _vp]),
     "fv_train_tower_begin": (_i, [_vp]),
     "fv_train_tower_workspace_bytes": (_i, [_vp, _i, C.POINTER(C.c_size_t)]),
     "fv_train_tower_forward": (_i, [_vp, _vp, _i, _vp, C.c_size_t, _vp, _vp]),
@@ -163,6 +164,8 @@ OPS_SIGNATURES = {
     "fv_op_gemm_f16_gelup": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "fv_op_dw_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fv_op_convffn32_split": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_size_t, _vp]),
+    "fv_op_lora_direct_scratch_floats": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
+    "fv_op_lora_direct": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, C.c_size_t, _vp]),
     "fv_op_attention_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "fv_op_rmsnorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

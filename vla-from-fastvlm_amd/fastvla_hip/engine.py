@@ -582,12 +582,8 @@ class FastVLAEngine:
                 out[name] = v.clone()
         return out
 
-    def train_forward_backward(self, flat_params: torch.Tensor, tower_out: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor, states: torch.Tensor,
-                               targets: torch.Tensor, ws: torch.Tensor, *, training: bool = True, dropout_p: float = 0.0, seed: int = 0, offset: int = 0,
-                               flat_grads: Optional[torch.Tensor] = None, bucket_cb=None):
-        """One step's forward + MSE + backward over every trainable tensor (fv_train_forward_backward).  tower_out: (B, Ni, tower_out_dim)
-        bf16 from vision_forward(..., return_tower_out=True).  bucket_cb(bucket, offset, numel) is called when a bucket's gradient has
-        been enqueued completely.  -> (actions (B, A) in normalised space, loss (1,), flat_grads TIMES train_loss_scale())."""
+    def _train_step_inputs(self, tower_out, ids, lens, states, targets, ws):
+        """what train_forward_backward and train_lora_forward_backward share: the inputs on the device in the library's types, the outputs, the aligned workspace"""
         B, T = ids.shape
         ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
         lens = lens.to(device=self.device, dtype=torch.int32).contiguous()
@@ -596,10 +592,20 @@ class FastVLAEngine:
         tower_out = tower_out.contiguous()
         if tower_out.dtype != torch.bfloat16 or tower_out.shape != (B, self.model.tower.num_tokens, self.model.tower.out_dim):
             raise ValueError(f"tower_out must be (B, {self.model.tower.num_tokens}, {self.model.tower.out_dim}) bf16, got {tuple(tower_out.shape)} {tower_out.dtype}")
-        if flat_grads is None:
-            flat_grads = torch.empty_like(flat_params)
         actions = torch.empty(B, self.head_dims["da"], dtype=torch.float32, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
+        pad = (-ws.data_ptr()) % 256
+        return B, T, tower_out, ids, lens, states, targets, actions, loss, ws.data_ptr() + pad, ws.numel() - pad
+
+    def train_forward_backward(self, flat_params: torch.Tensor, tower_out: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor, states: torch.Tensor,
+                               targets: torch.Tensor, ws: torch.Tensor, *, training: bool = True, dropout_p: float = 0.0, seed: int = 0, offset: int = 0,
+                               flat_grads: Optional[torch.Tensor] = None, bucket_cb=None):
+        """One step's forward + MSE + backward over every trainable tensor (fv_train_forward_backward).  tower_out: (B, Ni, tower_out_dim)
+        bf16 from vision_forward(..., return_tower_out=True).  bucket_cb(bucket, offset, numel) is called when a bucket's gradient has
+        been enqueued completely.  -> (actions (B, A) in normalised space, loss (1,), flat_grads TIMES train_loss_scale())."""
+        B, T, tower_out, ids, lens, states, targets, actions, loss, ws_ptr, ws_bytes = self._train_step_inputs(tower_out, ids, lens, states, targets, ws)
+        if flat_grads is None:
+            flat_grads = torch.empty_like(flat_params)
         err = {}
 
         def _cb(_user, bucket, off, numel):
@@ -610,10 +616,8 @@ class FastVLAEngine:
                     err.setdefault("exc", exc)
 
         fn = _lib.BUCKET_CB(_cb)
-        base = ws.data_ptr()
-        pad = (-base) % 256
         rc = self.lib.fv_train_forward_backward(self.h, flat_params.data_ptr(), tower_out.data_ptr(), ids.data_ptr(), lens.data_ptr(), states.data_ptr(),
-                                                targets.data_ptr(), B, T, int(training), float(dropout_p), seed, offset, base + pad, ws.numel() - pad,
+                                                targets.data_ptr(), B, T, int(training), float(dropout_p), seed, offset, ws_ptr, ws_bytes,
                                                 actions.data_ptr(), loss.data_ptr(), flat_grads.data_ptr(), fn, None, _stream())
         if "exc" in err:
             raise err["exc"]
@@ -643,6 +647,22 @@ class FastVLAEngine:
         """lora_grads <- head / projector gradients copied, dA = s B^T dW', dB = s dW' A^T of every adapted matrix (fv_train_lora_project)"""
         _lib.check(self.lib.fv_train_lora_project(self.h, flat_grads_full.data_ptr(), lora_params.data_ptr(), lora_grads.data_ptr(), _stream()),
                    "fv_train_lora_project", self.h)
+
+    def train_lora_forward_backward(self, flat_params: torch.Tensor, lora_params: torch.Tensor, tower_out: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor,
+                                    states: torch.Tensor, targets: torch.Tensor, ws: torch.Tensor, *, training: bool = True, dropout_p: float = 0.0, seed: int = 0,
+                                    offset: int = 0, lora_grads: Optional[torch.Tensor] = None):
+        """The DIRECT LoRA step (fv_train_lora_forward_backward): train_forward_backward's forward and input-gradient chain, dA / dB of every adapter straight from
+        the gradient rows and the kept activations -- no full-size gradient buffer, no train_lora_project.  flat_params: the master; lora_params: the trainable
+        buffer.  -> (actions, loss (1,), lora_grads in the trainable layout TIMES train_loss_scale()).  Needs train_lora_begin() and the default backward options."""
+        B, T, tower_out, ids, lens, states, targets, actions, loss, ws_ptr, ws_bytes = self._train_step_inputs(tower_out, ids, lens, states, targets, ws)
+        if lora_grads is None:
+            lora_grads = torch.empty_like(lora_params)
+        with torch.cuda.device(self.device):     # (the first call allocates the kernels' scratch)
+            rc = self.lib.fv_train_lora_forward_backward(self.h, flat_params.data_ptr(), lora_params.data_ptr(), tower_out.data_ptr(), ids.data_ptr(), lens.data_ptr(),
+                                                         states.data_ptr(), targets.data_ptr(), B, T, int(training), float(dropout_p), seed, offset, ws_ptr,
+                                                         ws_bytes, actions.data_ptr(), loss.data_ptr(), lora_grads.data_ptr(), _stream())
+        _lib.check(rc, "fv_train_lora_forward_backward", self.h)
+        return actions, loss, lora_grads
 
     def train_lora_commit(self, flat_master: torch.Tensor, lora_params: torch.Tensor) -> None:
         """operand images <- W0 + s B A (adapted matrices) / the master (the rest); the master's head | projector front <- lora_params' (fv_train_lora_commit)"""

@@ -74,6 +74,18 @@ def config_from_env(environ=None) -> Optional[Dict]:
     return check_config(rank, float(alpha) if alpha else None, env.get("FASTVLA_LORA_TARGETS") or None)
 
 
+def direct_from_env(environ=None) -> bool:
+    """FASTVLA_LORA_DIRECT: "1" -> the direct LoRA backward (fv_train_lora_forward_backward); unset / empty / "0" -> the projected one; anything else raises.
+    A property of the run, not of the adapters: it is no part of config_from_env's dict."""
+    env = os.environ if environ is None else environ
+    raw = (env.get("FASTVLA_LORA_DIRECT") or "").strip()
+    if raw in ("", "0"):
+        return False
+    if raw == "1":
+        return True
+    raise ValueError(f"FASTVLA_LORA_DIRECT must be 0 or 1, got '{raw}'")
+
+
 def _pad4(n: int) -> int:
     return (n + 3) // 4 * 4
 

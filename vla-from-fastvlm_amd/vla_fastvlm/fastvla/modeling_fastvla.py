@@ -28,7 +28,7 @@ class FastVLAPolicy(nn.Module):
         self._unfrozen = None   # training/unfrozen.py UnfrozenState once enable_backbone_training() ran
 
     def enable_backbone_training(self, bucket_min_numel: int = 1 << 22, tower: Optional[bool] = None, lora_rank: Optional[int] = None,
-                                 lora_alpha: Optional[float] = None, lora_targets=None, lora_seed: int = 0):
+                                 lora_alpha: Optional[float] = None, lora_targets=None, lora_seed: int = 0, lora_direct: Optional[bool] = None):
         """Extension of this build: fine-tune the Qwen2 decoder + mm_projector together with the action expert
         (image tokens spliced); tower=True (or FASTVLA_TRAIN_TOWER=1) trains the FastViT-HD tower too, in its inference form, otherwise it stays
         frozen.  Explicit on purpose: the reference's `freeze_backbone=False` trains nothing but the head either (model/fastvlm_adapter.py:501),
@@ -36,25 +36,35 @@ class FastVLAPolicy(nn.Module):
 
         lora_rank=r (1 .. 64; or FASTVLA_LORA_RANK, with FASTVLA_LORA_ALPHA / FASTVLA_LORA_TARGETS): LoRA mode -- the decoder's matrices stay frozen and the
         target matrices (default all seven: q, k, v, o, gate, up, down) run as W0 + (lora_alpha / r) B A (default alpha = r), action expert and mm_projector
-        train in full; gradients, Adam's moments and the data-parallel exchange cover the trainable tensors only.  Not together with tower=True."""
+        train in full; gradients, Adam's moments and the data-parallel exchange cover the trainable tensors only.  Not together with tower=True.
+
+        lora_direct=True (with lora_rank; or FASTVLA_LORA_DIRECT=1): the DIRECT LoRA backward -- dA / dB straight from activations and output gradients
+        (fv_train_lora_forward_backward); the full-size gradient buffer is never allocated.  A property of the run, not of the adapters: adapter and optimiser
+        files written in one mode load in the other; a state that is already running keeps the mode it was started in (lora_direct=None), and asking it
+        for the other mode explicitly raises RuntimeError."""
         from fastvla_hip import lora as _lora
         if tower is None:
             tower = os.environ.get("FASTVLA_TRAIN_TOWER", "0") == "1"
         if lora_rank is None and lora_alpha is None and lora_targets is None:
             lcfg = _lora.config_from_env()       # the environment twins, in the style of FASTVLA_TRAIN_TOWER
+            if lcfg is None and (lora_direct or (lora_direct is None and _lora.direct_from_env())):
+                raise ValueError("lora_direct / FASTVLA_LORA_DIRECT need a rank (lora_rank or FASTVLA_LORA_RANK)")
             if lcfg is not None and tower:
                 raise ValueError("FASTVLA_LORA_RANK and a trained tower (tower=True / FASTVLA_TRAIN_TOWER=1) cannot be combined: LoRA adapters go with a frozen vision tower")
         else:
             if lora_rank is None:
-                raise ValueError("lora_alpha / lora_targets need lora_rank")
+                raise ValueError("lora_alpha / lora_targets / lora_direct need lora_rank")
             lcfg = _lora.check_config(lora_rank, lora_alpha, lora_targets, tower=bool(tower))
         if self._unfrozen is not None and bool(tower) and not self._unfrozen.train_tower:
             raise RuntimeError("backbone training is already running with the tower frozen: ask for tower=True on the first call")
         if self._unfrozen is not None and lcfg is not None and self._unfrozen.lora != lcfg:
             raise RuntimeError(f"backbone training is already running with lora={self._unfrozen.lora}: ask for LoRA on the first call")
+        if self._unfrozen is not None and lcfg is not None and lora_direct is not None and bool(lora_direct) != self._unfrozen.lora_direct:
+            raise RuntimeError(f"backbone training is already running with lora_direct={self._unfrozen.lora_direct}: ask for the backward mode on the first call")
         if self._unfrozen is None:
             from ..training.unfrozen import UnfrozenState
-            self._unfrozen = UnfrozenState(self, bucket_min_numel=bucket_min_numel, train_tower=bool(tower), lora=lcfg, lora_seed=lora_seed)
+            direct = lcfg is not None and (_lora.direct_from_env() if lora_direct is None else bool(lora_direct))
+            self._unfrozen = UnfrozenState(self, bucket_min_numel=bucket_min_numel, train_tower=bool(tower), lora=lcfg, lora_seed=lora_seed, lora_direct=direct)
         return self._unfrozen
 
     def merge_lora(self) -> None:

@@ -17,6 +17,10 @@ W0 + (alpha / rank) B A; action expert and mm_projector still train in full.  Th
 (fv_train_lora_layout: [head | projector | layer adapters]) and the gradient that is exchanged, Adam's m / v and the optimiser step cover THAT buffer only:
 forward/backward (unchanged, full dW') -> fv_train_lora_project -> ONE all-reduce -> clip + AdamW -> fv_train_lora_commit.  The full-size m / v are never
 allocated; the full master and the full gradient buffer remain.
+
+Direct LoRA mode (`lora_direct=True`; fv_train_lora_forward_backward): the backward writes head, projector and adapter gradients straight into the
+trainable-layout gradient buffer (dA = s (dY B)^T X, dB = s dY^T (X A^T) from the gradient rows and the kept activations) -- the full weight gradient is never
+formed, the full-size gradient buffer is never allocated (`self.g is None`) and fv_train_lora_project is not called; everything behind the backward is the same.
 """
 from __future__ import annotations
 
@@ -30,7 +34,8 @@ from .dp import BucketedGradExchange, GradExchange
 
 
 class UnfrozenState:
-    def __init__(self, policy, bucket_min_numel: int = 1 << 22, train_tower: bool = False, lora: Optional[Dict] = None, lora_seed: int = 0):
+    def __init__(self, policy, bucket_min_numel: int = 1 << 22, train_tower: bool = False, lora: Optional[Dict] = None, lora_seed: int = 0,
+                 lora_direct: bool = False):
         m = policy.model
         bb = m.backbone
         self.policy = policy
@@ -40,9 +45,12 @@ class UnfrozenState:
                                f"from the fp32 master after every step; this engine runs llm_precision={eng.llm_precision}")
         if lora is not None and train_tower:
             raise ValueError("LoRA adapters go with a frozen vision tower: lora and train_tower cannot be combined")
+        if lora_direct and lora is None:
+            raise ValueError("lora_direct needs a LoRA configuration (lora_rank)")
         eng.train_begin()
         self.train_tower = bool(train_tower)
         self.lora = dict(lora) if lora is not None else None      # {"rank", "alpha", "targets"}: the decoder's matrices frozen, adapters trained
+        self.lora_direct = bool(lora_direct)                      # the run's backward mode: NOT part of self.lora (what adapter / optimiser files compare)
         if self.lora is not None:
             eng.train_lora_begin(self.lora["rank"], self.lora["alpha"], self.lora["targets"])
         if self.train_tower:
@@ -76,7 +84,7 @@ class UnfrozenState:
             for p, k in zip(m.head_parameters(), HEAD_KEYS):
                 p.data = views[k]
         m._flat = self.trainable[:hn]
-        self.g = torch.zeros_like(self.flat)
+        self.g = None if self.lora_direct else torch.zeros_like(self.flat)      # direct LoRA: the full-size gradient buffer does not exist
         self.acc: Optional[torch.Tensor] = None
         self.m, self.v = torch.zeros_like(self.trainable), torch.zeros_like(self.trainable)
         self.step_count, self.micro = 0, 0
@@ -232,14 +240,19 @@ class UnfrozenState:
             tws, dto = self._tws[B], self._dto[B]
             eng.train_set_tower_grad(dto)
             tower_out = eng.train_tower_forward(prep["pix"], tws)
-        actions, loss, _ = eng.train_forward_backward(self.flat, tower_out, prep["ids"], prep["lens"], prep["states"], prep["targets"], ws,
-                                                      training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, flat_grads=self.g,
-                                                      bucket_cb=self.bucketed.bucket_ready if overlap else None)
+        if self.lora_direct:
+            actions, loss, _ = eng.train_lora_forward_backward(self.flat, self.lflat, tower_out, prep["ids"], prep["lens"], prep["states"], prep["targets"], ws,
+                                                               training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, lora_grads=self.lg)
+        else:
+            actions, loss, _ = eng.train_forward_backward(self.flat, tower_out, prep["ids"], prep["lens"], prep["states"], prep["targets"], ws,
+                                                          training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, flat_grads=self.g,
+                                                          bucket_cb=self.bucketed.bucket_ready if overlap else None)
         if self.train_tower:
             eng.train_tower_backward(prep["pix"], dto, tws, self.g, bucket_cb=self.bucketed.bucket_ready if overlap else None)
         total = self.g
         if self.lora is not None:
-            eng.train_lora_project(self.g, self.lflat, self.lg)    # dA, dB of every adapted matrix; head / projector gradients copied
+            if not self.lora_direct:
+                eng.train_lora_project(self.g, self.lflat, self.lg)    # dA, dB of every adapted matrix; head / projector gradients copied
             total = self.lg
         if k > 1:
             if self.acc is None:

@@ -27,7 +27,8 @@ BACKBONE_PREFIX = "model.backbone.model."
 # (the decoder was trained on [image tokens | text]: inference must run the same graph), "train_backbone", "train_tower".
 EXTRAS_FILE = "hip_extras.json"
 # a LoRA run (enable_backbone_training(lora_rank=...)): the adapters, the mm_projector that trains beside them and {rank, alpha, targets} in a file of their
-# own; EXTRAS_FILE names it under "lora" = {"rank", "alpha", "targets", "file"}, and a directory whose extras name adapters that are not there does not load
+# own; EXTRAS_FILE names it under "lora" = {"rank", "alpha", "targets", "file", "direct"}, and a directory whose extras name adapters that are not there does not
+# load.  "direct" records the run's backward mode (the direct LoRA backward; absent = projected): the default when loading has to switch LoRA mode on itself
 LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
@@ -74,7 +75,9 @@ def load_lora_adapters(policy: FastVLAPolicy, checkpoint_dir, lora_extras: dict)
     f = Path(checkpoint_dir) / lora_extras.get("file", LORA_FILE)
     if not f.is_file():
         raise FileNotFoundError(f"{Path(checkpoint_dir) / EXTRAS_FILE} records LoRA adapters (rank {lora_extras.get('rank')}) in '{f.name}', which is not there")
-    un = policy.enable_backbone_training(lora_rank=int(lora_extras["rank"]), lora_alpha=float(lora_extras["alpha"]), lora_targets=list(lora_extras["targets"]))
+    # (a policy that is already in LoRA mode keeps the backward mode it was started in and just receives the adapters)
+    mode = {} if getattr(policy, "_unfrozen", None) is not None else {"lora_direct": bool(lora_extras.get("direct", False))}
+    un = policy.enable_backbone_training(lora_rank=int(lora_extras["rank"]), lora_alpha=float(lora_extras["alpha"]), lora_targets=list(lora_extras["targets"]), **mode)
     un.load_lora_state(torch.load(f, map_location="cpu"))
 
 
@@ -97,6 +100,8 @@ def save_policy_checkpoint(policy: FastVLAPolicy, checkpoint_dir: str, include_b
         if not un.lora_adapters_zero:      # (right after merge_lora() the adapters are zero and the master holds everything: a plain checkpoint)
             torch.save(un.lora_state(), d / LORA_FILE)
             extras["lora"] = {**lora_cfg, "file": LORA_FILE}
+            if getattr(un, "lora_direct", False):      # (written only when on: a missing key means the projected backward, and a projected run's file is what it was)
+                extras["lora"]["direct"] = True
         elif (d / LORA_FILE).is_file():
             (d / LORA_FILE).unlink()
     if any(extras.values()):
