@@ -354,6 +354,21 @@ enum fv_lora_target { FV_LORA_Q = 1, FV_LORA_K = 2, FV_LORA_V = 4, FV_LORA_O = 8
  * fv_train_tower_begin (tower adapters do not exist; fv_train_tower_begin refuses after this call in turn).  Allocates the descriptor tables and the
  * projection's scratch once; a second call with the same arguments is a no-op, with others FV_ERR_STATE. */
 int fv_train_lora_begin(fv_handle* h, int rank, float alpha, int target_mask);
+/* fv_train_lora_begin with variants (fv_train_lora_begin == flags 0; anything but these two bits FV_ERR_ARG; beginning again with other flags FV_ERR_STATE):
+ *   FV_LORA_RSLORA  rank-stabilised scaling: s = alpha / sqrt(rank).  Nothing else changes; both backward modes work.
+ *   FV_LORA_DORA    weight-decomposed LoRA (PEFT's use_dora):  W' = diag(m / n) @ V,  V = W0 + s * B @ A,  n_i = ||V_i,:||_2,  m a TRAINED magnitude per output
+ *                   row.  The layout lists "....lora_magnitude_vector.weight" (1 x out) behind each target's lora_B; head and projector keep their offsets.
+ *                   The norm is a constant in the backward (PEFT, the DoRA paper section 4.3): with G = dW', c = m / n
+ *                       dm_i = (sum_j G_ij V_ij) / n_i        dA = s * B^T @ diag(c) @ G        dB = s * diag(c) @ G @ A^T
+ *                   fv_train_lora_commit refreshes n into a buffer the handle owns and remembers the master it read; fv_train_lora_project uses both, so it
+ *                   MUST FOLLOW A COMMIT OF THE SAME PARAMETERS (FV_ERR_STATE when no commit has run; a stale one goes unnoticed).  fv_train_lora_merge
+ *                   writes diag(c) @ V.  fv_train_lora_forward_backward answers FV_ERR_UNSUPPORTED (dm from activations needs the pre-bias GEMM outputs). */
+enum fv_lora_flags { FV_LORA_DORA = 1, FV_LORA_RSLORA = 2 };
+int fv_train_lora_begin_ex(fv_handle* h, int rank, float alpha, int target_mask, int flags);
+/* DoRA only (FV_ERR_STATE otherwise): every magnitude in lora_params <- the row norm of W0 + s * B @ A for the A, B it holds, by the kernel and summation order
+ * the commit uses -- so m / n is exactly 1.0f and the commit that follows builds the operand images a commit without the magnitude would (with lora_B = 0:
+ * fv_train_commit's own; m = ||W0|| per row, PEFT's initialisation).  Also after fv_train_lora_merge, with lora_B zeroed, on the merged master. */
+int fv_train_lora_init_magnitude(fv_handle* h, const float* flat_params_master, float* lora_params, fv_stream s);
 /* the trainable buffer's tensors (packing 0 throughout; bucket 0 head, 1 projector, 3 + l the adapters of layer l).  out may be NULL (sizes only). */
 int fv_train_lora_layout(fv_handle* h, fv_train_tensor* out, int max_tensors, int* n_tensors, int64_t* total_numel);
 /* lora_grads (trainable layout) <- the full gradient buffer fv_train_forward_backward filled: head and projector gradients copied, and for every adapted matrix
@@ -363,7 +378,9 @@ int fv_train_lora_layout(fv_handle* h, fv_train_tensor* out, int max_tensors, in
 int fv_train_lora_project(fv_handle* h, const float* flat_grads_full, const float* lora_params, float* lora_grads, fv_stream s);
 /* fv_train_commit in LoRA mode: the operand images of every adapted matrix from W0 + s * B @ A (evaluated in fp32, then rounded as fv_train_commit rounds W0),
  * every other tensor as fv_train_commit.  Head and projector are taken from lora_params: the master's head | projector FRONT is overwritten with theirs (that is
- * where fv_train_forward_backward reads the head); nothing else of the master is written -- W0 stays as it is. */
+ * where fv_train_forward_backward reads the head); nothing else of the master is written -- W0 stays as it is.
+ * With FV_LORA_DORA the commit also refreshes the row norms and KEEPS the pointer flat_params_master: the next fv_train_lora_project reads W0 through it, so that
+ * buffer must stay allocated, in place and unchanged behind its front until that projection has run (a freed, moved or re-filled master goes unnoticed). */
 int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream s);
 /* W0 += s * B @ A into the master, for every adapted matrix (and its front <- lora_params' front): bit for bit the fp32 values fv_train_lora_commit rounds, so
  * fv_train_commit on the merged master builds the same operand images.  For exporting a plain checkpoint; the adapters are not reset. */

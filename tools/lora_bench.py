@@ -6,7 +6,10 @@ direct    = fv_train_lora_forward_backward (dA, dB straight from activations and
 The frozen tower runs once, outside the windows (it is the same work in both modes).  Times: host clock around windows that end in a device synchronise;
 kernels alone: device events around repeated launches.  GB/s = the bytes the algorithm needs (computed from the shapes below) over that time.
 Memory: the torch allocator's peak while a mode's buffers are the only ones alive (the library's own allocations -- weights, operand copies -- are the same
-in both modes and not in that figure)."""
+in both modes and not in that figure).
+--rslora: every LoRA mode runs with s = alpha / sqrt(rank).  --dora: a DoRA step (fv_train_lora_begin_ex FV_LORA_DORA: the projected LoRA step with the row-norm
+pass in its commit and the magnitude gradient in its projection) joins the alternating windows, on a second engine over the same weights (a handle holds one
+adapter mode), and its projection / commit / row-norm times join kernels_ms; every other figure is measured as without it."""
 import argparse
 import ctypes as C
 import json
@@ -34,6 +37,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kernel-reps", type=int, default=20)
+    ap.add_argument("--dora", action="store_true", help="also measure the DoRA step (a second engine in the same process)")
+    ap.add_argument("--rslora", action="store_true", help="s = alpha / sqrt(rank) in every LoRA mode")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -44,7 +49,7 @@ def main():
     eng = FastVLAEngine(model, max_batch=B, max_text_tokens=T, llm_precision=1)
     eng.load_weights(weights.init_backbone(model, seed=1234))
     eng.train_begin()
-    eng.train_lora_begin(args.rank, None, args.targets)
+    eng.train_lora_begin(args.rank, None, args.targets, rslora=args.rslora)
     _, total, _ = eng.train_layout()
     lt, ltotal = eng.train_lora_layout()
     front = next(t["offset"] for t in lt if ".lora_" in t["name"])
@@ -133,6 +138,47 @@ def main():
     to_full()
     window(full_step, args.warmup)
     mem_full = torch.cuda.max_memory_allocated() - base_mem - (lflat.numel() * 4 * 5)     # (the LoRA mode's five small buffers are alive too: taken out)
+    # ---- DoRA (--dora): its own engine over the same weights, master and inputs; magnitudes start as the row norms of W0, so with lora_B != 0 they differ from
+    # the norms of W0 + s B A and every kernel does its real work
+    eng_d = None
+    if args.dora:
+        eng_d = FastVLAEngine(model, max_batch=B, max_text_tokens=T, llm_precision=1)
+        eng_d.load_weights(weights.init_backbone(model, seed=1234))
+        eng_d.train_begin()
+        eng_d.train_lora_begin(args.rank, None, args.targets, dora=True, rslora=args.rslora)
+        dt, dtotal = eng_d.train_lora_layout()
+        dflat = torch.zeros(dtotal, device=dev)
+        dflat[:front].copy_(flat[:front])
+        dnamed = lora.adapter_views(dflat, dt)
+        for name, view in lora.adapter_views(lflat0, lt).items():
+            dnamed[name].copy_(view)
+        zeroB = dflat.clone()
+        for name, view in lora.adapter_views(zeroB, dt).items():
+            if name.endswith(".lora_B.weight"):
+                view.zero_()
+        eng_d.train_lora_init_magnitude(flat, zeroB)
+        for name, view in lora.adapter_views(zeroB, dt).items():
+            if name.endswith(".lora_magnitude_vector.weight"):
+                dnamed[name].copy_(view)
+        del zeroB
+        dflat0 = dflat.clone()
+        dg, dm_, dv_ = torch.zeros_like(dflat), torch.zeros_like(dflat), torch.zeros_like(dflat)
+        ws_d = eng_d.train_workspace(B, T)
+        n["dora"] = 0
+
+        def dora_step():
+            n["dora"] += 1
+            loss = eng_d.train_forward_backward(flat, tower_out, ids, lens, states, targets, ws_d, training=True, dropout_p=0.1, seed=7, offset=n["dora"], flat_grads=grads)[1]
+            eng_d.train_lora_project(grads, dflat, dg)
+            eng_d.adamw_step(dflat, dg, dm_, dv_, n["dora"], **hp)
+            eng_d.train_lora_commit(flat, dflat)
+            return loss
+
+        def to_dora():
+            flat.copy_(master0.to(dev)); dflat.copy_(dflat0); eng_d.train_lora_commit(flat, dflat)
+
+        to_dora()
+        window(dora_step, args.warmup)
     rounds = []
     for _ in range(args.rounds):       # alternating windows: other work shares the host
         to_full()
@@ -143,6 +189,10 @@ def main():
         d_ms, d_loss = window(direct_step, args.steps)
         rounds.append({"full_ms": round(f_ms, 2), "lora_ms": round(l_ms, 2), "lora_direct_ms": round(d_ms, 2), "full_loss": f_loss, "lora_loss": l_loss,
                        "lora_direct_loss": d_loss})
+        if eng_d is not None:
+            to_dora()
+            o_ms, o_loss = window(dora_step, args.steps)
+            rounds[-1].update({"dora_ms": round(o_ms, 2), "dora_loss": o_loss})
     to_lora()
 
     # ---- the kernels alone
@@ -224,6 +274,22 @@ def main():
                           "adamw_full": round(t_adam_full, 3), "adamw_lora": round(t_adam_lora, 3)},
            "hbm_gb_s": {"lora_project": round(proj_bytes / t_proj / 1e6, 1), "lora_commit": round(commit_bytes / t_lcommit / 1e6, 1), "commit": round(commit_bytes / t_commit / 1e6, 1)},
            "bytes_gb": {"lora_project": round(proj_bytes / 1e9, 3), "commit": round(commit_bytes / 1e9, 3)}}
+    if args.rslora:
+        res["rslora"] = True
+    if eng_d is not None:
+        to_dora()
+        eng_d.train_forward_backward(flat, tower_out, ids, lens, states, targets, ws_d, training=True, dropout_p=0.1, seed=7, offset=1, flat_grads=grads)
+        t_dproj = timed(lambda: eng_d.train_lora_project(grads, dflat, dg), args.kernel_reps)
+        t_dcommit = timed(lambda: eng_d.train_lora_commit(flat, dflat), args.kernel_reps)
+        scratch_m = dflat.clone()
+        t_norm = timed(lambda: eng_d.train_lora_init_magnitude(flat, scratch_m), args.kernel_reps)
+        res["dora_ms_per_step"] = med([x["dora_ms"] for x in rounds])
+        res["dora_trainable_numel"] = dtotal
+        res["kernels_ms"].update({"dora_project": round(t_dproj, 3), "dora_commit": round(t_dcommit, 3), "dora_row_norms": round(t_norm, 3)})
+        # DoRA's projection reads the adapted master rows once more (dm), its commit once more (the row-norm pass)
+        res["hbm_gb_s"].update({"dora_project": round((proj_bytes + 4.0 * adapted) / t_dproj / 1e6, 1), "dora_commit": round((commit_bytes + 4.0 * adapted) / t_dcommit / 1e6, 1),
+                                "dora_row_norms": round(4.0 * adapted / t_norm / 1e6, 1)})
+        eng_d.close()
     print(json.dumps(res))
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)

@@ -2,7 +2,8 @@
 twice as two gloo ranks on one GPU (under RCCL on a multi-GPU node: torchrun --nproc-per-node N tools/lora_dp_worker.py --out DIR).  Every rank builds the same
 `small` policy in LoRA mode with the same non-zero adapters, takes its slice of ONE fixed batch, runs FastVLAPolicy.fused_train_step -- forward/backward,
 projection onto the adapters (--direct: adapter gradients straight from the backward instead), ONE all-reduce of the trainable buffer, clip + AdamW, adapted
-commit -- and writes its reduced gradient and updated buffers to --out."""
+commit -- and writes its reduced gradient and updated buffers to --out.  --dora / --rslora: the adapters' variants (with lora_B != 0 the magnitudes, which
+start as the row norms of W0, differ from the norms of W0 + s B A: every magnitude has a gradient)."""
 import argparse
 import os
 import sys
@@ -30,6 +31,8 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--rank-dim", type=int, default=8)
     ap.add_argument("--direct", action="store_true", help="the direct LoRA backward (fv_train_lora_forward_backward): no full-size gradient buffer, no projection")
+    ap.add_argument("--dora", action="store_true", help="weight-decomposed LoRA: a trained magnitude per output row (projected backward only)")
+    ap.add_argument("--rslora", action="store_true", help="rank-stabilised scaling: s = alpha / sqrt(rank)")
     args = ap.parse_args()
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -43,7 +46,8 @@ def main():
     torch.manual_seed(5)
     pol = FastVLAPolicy(FastVLAConfig(vlm_model_name="synthetic:small:41", hidden_dim=64, fusion_dim=64, dropout=0.0, freeze_backbone=False)).to(dev)
     pol.train()
-    st = pol.enable_backbone_training(lora_rank=args.rank_dim, lora_direct=args.direct)
+    st = pol.enable_backbone_training(lora_rank=args.rank_dim, lora_direct=args.direct, **({"lora_dora": True} if args.dora else {}),
+                                      **({"lora_rslora": True} if args.rslora else {}))
     assert (st.g is None) == bool(args.direct)
     # lora_B != 0, the same on every rank: with PEFT's B = 0 start every dA would be exactly zero
     g = torch.Generator().manual_seed(17)

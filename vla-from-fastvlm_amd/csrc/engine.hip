@@ -97,6 +97,9 @@ struct LoraState {   // fv_train_lora_* (lora_path.inc): adapters on the decoder
   int64_t front = 0, total = 0;                                              // head + projector floats in front of the adapters; the trainable buffer's size
   std::vector<fv::LoraDirectPack> packs;                                     // host: [layer][q|k|v, o, gate/up, down] -- the direct backward's calls (nm = 0: no adapter inside)
   float* dscratch = nullptr; size_t dscratch_floats = 0;                     // device: the direct backward's P | Q | partial sums (allocated by its first step)
+  int flags = 0;                                                             // fv_lora_flags (FV_LORA_DORA | FV_LORA_RSLORA)
+  float* norms = nullptr; size_t norm_floats = 0; int nbands = 0;            // DoRA, device: the row norms of every adapted matrix (LoraMat::n_off), refreshed by the commit
+  const float* master = nullptr;                                             // DoRA: the master the last commit read (the projection's W0 stream)
 };
 struct TrainState {
   LoraState lora;

@@ -192,20 +192,27 @@ struct LoraMat {
   int row0, blk;         // logical row i = packed row row0 + (i >> 3) * blk + (i & 7)  (blk 8: plain or a q|k|v row range; 16: gate / up interleaved by 8)
   int strip0;            // first strip of this matrix in the projection's strip numbering
   long long part_off;    // its per-strip dA partial sums in the scratch, floats, relative to its launch group
+  long long m_off, n_off;   // DoRA only: its magnitude vector (`out` floats) in the trainable flat buffer; its row norms in the handle's norm buffer
 };
 struct LoraCommitDesc {
   CommitDesc c;          // the packed tensor, as fv_train_commit sees it (tile0 in the LoRA launch's own numbering)
   int kind;              // 0 plain (mat[0]), 1 q|k|v row ranges (mat[0..2], qd / kd rows), 2 gate / up interleaved (mat[0] gate, mat[1] up)
   int qd, kd;
   int mat[3];            // index into the LoraMat table, -1 = that part has no adapter
+  int band0;             // first 64-row band of this tensor in the row-norm launch's numbering (DoRA)
 };
 // dA, dB of matrices [m0, m1) (their strips: strip_begin .. strip_begin + nstrips) from ONE read of the full gradient; scratch holds the group's dA partials
+// DoRA (W' = diag(m / n) (W0 + s . B . A), n the row norms of W0 + s . B . A, held constant in the backward): `norms` non-null selects it everywhere below.
+// The projection then also needs the master (dm's row dot with W0) and leaves dm = (sum_j dW'_ij V_ij) / n_i beside dA = s B^T diag(c) dW', dB = s diag(c) dW' A^T.
 int launch_lora_project(const LoraMat* mats_dev, int m0, int m1, int strip_begin, int nstrips, int max_in, const float* grads_full, const float* lora,
-                        float* lora_grads, float* scratch, int rank, float scale, hipStream_t s);
+                        float* lora_grads, float* scratch, int rank, float scale, hipStream_t s, const float* master = nullptr, const float* norms = nullptr);
 int launch_lora_commit(const LoraCommitDesc* desc_dev, int ndesc, int ntiles, const LoraMat* mats_dev, const float* flat, const float* lora, int rank, float scale,
-                       int f16_transposes, unsigned* sat, hipStream_t s);
+                       int f16_transposes, unsigned* sat, hipStream_t s, const float* norms = nullptr);
 int launch_lora_merge(const LoraCommitDesc* desc_dev, int ndesc, int ntiles, const LoraMat* mats_dev, float* flat, const float* lora, int rank, float scale,
-                      hipStream_t s);
+                      hipStream_t s, const float* norms = nullptr);
+// norms[n_off + i] = ||(W0 + s . B . A)_i,:||_2 of every adapted row (nbands = the tensors' 64-row bands); mag non-null: the magnitudes in that trainable buffer too
+int launch_lora_norms(const LoraCommitDesc* desc_dev, int ndesc, int nbands, const LoraMat* mats_dev, const float* flat, const float* lora, int rank, float scale,
+                      float* norms, float* mag, hipStream_t s);
 
 // ---- the direct LoRA backward (lora_direct_kernels.hip; fv_train_lora_forward_backward): dA, dB straight from dY and X, dW' never formed --------------------
 // ONE packed tensor of one layer and the adapters inside it ("slots", in part order: q, k, v / gate, up / the matrix itself)

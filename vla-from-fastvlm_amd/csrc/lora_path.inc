@@ -10,6 +10,10 @@
 //     ->  all-reduce + fv_adamw_clip_step over the trainable buffer  ->  fv_train_lora_commit (operand images from W0 + s . B . A).
 // The DIRECT mode replaces the first two by fv_train_lora_forward_backward: the same forward and dgrad chain (train_path.inc, ONE body), dA / dB of every adapter
 // straight from the gradient's fp16 rows and the kept activations (lora_direct_kernels.hip) into the trainable-layout gradient buffer; no full gradient buffer.
+// Two variants ride on fv_train_lora_begin_ex's flags.  FV_LORA_RSLORA: s = alpha / sqrt(rank) -- ls.scale, nothing else.  FV_LORA_DORA (PEFT's use_dora): every
+// target also owns a magnitude vector m (`out` floats, "...lora_magnitude_vector.weight", behind its lora_B in the trainable buffer) and runs as
+// diag(m / n) (W0 + s . B . A), n the row norms, which the commit refreshes into a buffer the handle owns and the projection reads (norm held constant in the
+// backward, as PEFT does); the direct backward refuses it.
 // Kernels: lora_kernels.hip, lora_direct_kernels.hip.
 
 namespace {
@@ -30,7 +34,7 @@ void lora_logicals(const fv_model_desc& d, LoraLogical out[7]) {
 }
 
 // the trainable buffer: head and projector exactly as train_tensors lists them (same offsets), then lora_A (rank x in) / lora_B (out x rank) per layer and target
-std::vector<TrainTensor> lora_tensors(fv_handle* h, int rank, int mask, int64_t* total, int64_t* front) {
+std::vector<TrainTensor> lora_tensors(fv_handle* h, int rank, int mask, int64_t* total, int64_t* front, bool dora = false) {
   std::vector<TrainTensor> out;
   int64_t off = 0;
   for (const TrainTensor& t : train_tensors(h, nullptr)) {
@@ -54,6 +58,14 @@ std::vector<TrainTensor> lora_tensors(fv_handle* h, int rank, int mask, int64_t*
         off += (t.numel + 3) / 4 * 4;
         out.push_back(t);
       }
+      if (dora) {     // DoRA's magnitude, one float per output row
+        TrainTensor t;
+        t.name = pre + ".lora_magnitude_vector.weight";
+        t.rows = 1; t.cols = lg[k].out; t.numel = lg[k].out;
+        t.off = off; t.bucket = TB_LAYER0 + l; t.is_mat = false;
+        off += (t.numel + 3) / 4 * 4;
+        out.push_back(t);
+      }
     }
   if (total) *total = off;
   return out;
@@ -66,13 +78,15 @@ int build_lora_tables(fv_handle* h) {
   LoraLogical lg[7];
   lora_logicals(h->d, lg);
   int64_t total = 0, front = 0;
-  const std::vector<TrainTensor> lt = lora_tensors(h, rank, ls.mask, &total, &front);
+  const bool dora = (ls.flags & FV_LORA_DORA) != 0;
+  const std::vector<TrainTensor> lt = lora_tensors(h, rank, ls.mask, &total, &front, dora);
   std::map<std::string, int64_t> loff;
   for (const TrainTensor& t : lt) loff[t.name] = t.off;
   std::vector<fv::LoraMat> mats;
   std::vector<fv::LoraCommitDesc> cds;
   std::vector<fv::CommitDesc> rest;
-  int ctiles = 0, rtiles = 0, strips = 0;
+  int ctiles = 0, rtiles = 0, strips = 0, bands = 0;
+  long long nrows = 0;
   for (const TrainTensor& t : train_tensors(h, nullptr)) {
     if (!t.lib) continue;
     fv::CommitDesc c{};
@@ -102,6 +116,8 @@ int build_lora_tables(fv_handle* h) {
         if (m.in != t.cols || m.out % 32 || m.in % 32)
           return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_begin: %s%s is %d x %d (adapted matrices need dimensions that are multiples of 32)", pre.c_str(),
                          LORA_TARGET_NAMES[k], m.out, m.in);
+        m.m_off = dora ? loff.at(pre + LORA_TARGET_NAMES[k] + ".lora_magnitude_vector.weight") : -1;
+        m.n_off = nrows; nrows += m.out;
         m.strip0 = strips;
         strips += (m.out + fv::LORA_STRIP_ROWS - 1) / fv::LORA_STRIP_ROWS;
         lc.kind = lg[k].kind; lc.mat[lg[k].part] = (int)mats.size();
@@ -112,6 +128,7 @@ int build_lora_tables(fv_handle* h) {
     if (adapted) {
       lc.qd = h->d.llm_heads * h->d.llm_head_dim; lc.kd = h->d.llm_kv_heads * h->d.llm_head_dim;
       lc.c.tile0 = ctiles; ctiles += ntile;
+      lc.band0 = bands; bands += (t.rows + 63) / 64;
       cds.push_back(lc);
     } else {
       c.tile0 = rtiles; rtiles += ntile;
@@ -148,6 +165,11 @@ int build_lora_tables(fv_handle* h) {
   if (scratch > ls.scratch_floats) {
     FV_TRY(dev_alloc(h, scratch * 4, &p));
     ls.scratch = static_cast<float*>(p); ls.scratch_floats = scratch;
+  }
+  ls.nbands = bands;
+  if (dora && (size_t)nrows > ls.norm_floats) {
+    FV_TRY(dev_alloc(h, (size_t)nrows * 4, &p));
+    ls.norms = static_cast<float*>(p); ls.norm_floats = (size_t)nrows;
   }
   ls.front = front; ls.total = total;
   // the direct backward's calls: one per packed tensor and layer, the adapters inside it as slots in part order
@@ -213,25 +235,41 @@ int lora_check(fv_handle* h) {
   return FV_OK;
 }
 
+bool lora_dora(const fv_handle* h) { return (h->train.lora.flags & FV_LORA_DORA) != 0; }
+
+// DoRA: the row norms of W0 + s . B . A for these parameters into the handle's buffer (mag non-null: the magnitudes of that trainable buffer too)
+int lora_refresh_norms(fv_handle* h, const float* master, const float* lora_params, float* mag, hipStream_t s) {
+  LoraState& ls = h->train.lora;
+  FV_TRY(fv::launch_lora_norms(ls.cdesc, ls.cn, ls.nbands, ls.mats, master, lora_params, ls.rank, ls.scale, ls.norms, mag, s));
+  return FV_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
-int fv_train_lora_begin(fv_handle* h, int rank, float alpha, int target_mask) {
+int fv_train_lora_begin(fv_handle* h, int rank, float alpha, int target_mask) { return fv_train_lora_begin_ex(h, rank, alpha, target_mask, 0); }
+
+int fv_train_lora_begin_ex(fv_handle* h, int rank, float alpha, int target_mask, int flags) {
   HandleScope _hs(h);
   FV_TRY(train_check(h));
+  if (flags & ~(FV_LORA_DORA | FV_LORA_RSLORA)) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin_ex: flags 0x%x (FV_LORA_DORA = 1, FV_LORA_RSLORA = 2)", flags);
   if (rank < 1 || rank > 64) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: rank %d (1 .. 64)", rank);
   if (!(alpha > 0.f) || !std::isfinite(alpha)) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: alpha must be positive and finite");
   if (target_mask <= 0 || target_mask >= 128) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: target_mask 0x%x (bits 0 .. 6: q, k, v, o, gate, up, down; at least one)", target_mask);
   if (h->train.tower) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_begin: the tower is being trained (fv_train_tower_begin): adapters go with a frozen tower");
   LoraState& ls = h->train.lora;
   if (ls.on) {
-    if (ls.rank == rank && ls.alpha == alpha && ls.mask == target_mask) return FV_OK;
-    return fv_fail(FV_ERR_STATE, "fv_train_lora_begin: already begun with rank %d, alpha %g, targets 0x%x", ls.rank, (double)ls.alpha, ls.mask);
+    if (ls.rank == rank && ls.alpha == alpha && ls.mask == target_mask && ls.flags == flags) return FV_OK;
+    if (ls.flags == 0 && flags == 0)
+      return fv_fail(FV_ERR_STATE, "fv_train_lora_begin: already begun with rank %d, alpha %g, targets 0x%x", ls.rank, (double)ls.alpha, ls.mask);
+    return fv_fail(FV_ERR_STATE, "fv_train_lora_begin: already begun with rank %d, alpha %g, targets 0x%x, flags 0x%x", ls.rank, (double)ls.alpha, ls.mask, ls.flags);
   }
   FV_HIP_CHECK(hipSetDevice(h->device));
-  ls.rank = rank; ls.alpha = alpha; ls.scale = alpha / (float)rank; ls.mask = target_mask;
-  FV_TRY(build_lora_tables(h));
+  ls.rank = rank; ls.alpha = alpha; ls.mask = target_mask; ls.flags = flags;
+  ls.scale = (flags & FV_LORA_RSLORA) ? alpha / sqrtf((float)rank) : alpha / (float)rank;
+  const int rc = build_lora_tables(h);
+  if (rc != FV_OK) { ls.flags = 0; return rc; }
   ls.on = true;
   return FV_OK;
 }
@@ -241,7 +279,7 @@ int fv_train_lora_layout(fv_handle* h, fv_train_tensor* out, int max_tensors, in
   if (!h) return fv_fail(FV_ERR_ARG, "null handle");
   if (!h->train.lora.on) return fv_fail(FV_ERR_STATE, "LoRA training not initialised: call fv_train_lora_begin first");
   int64_t total = 0;
-  const std::vector<TrainTensor> tt = lora_tensors(h, h->train.lora.rank, h->train.lora.mask, &total, nullptr);
+  const std::vector<TrainTensor> tt = lora_tensors(h, h->train.lora.rank, h->train.lora.mask, &total, nullptr, lora_dora(h));
   if (n_tensors) *n_tensors = (int)tt.size();
   if (total_numel) *total_numel = total;
   if (out) {
@@ -264,9 +302,12 @@ int fv_train_lora_project(fv_handle* h, const float* flat_grads_full, const floa
   hipStream_t s = static_cast<hipStream_t>(st);
   const LoraState& ls = h->train.lora;
   // head and projector train in full: their gradients move over as they are (same offsets in both buffers)
+  const bool dora = lora_dora(h);
+  if (dora && !ls.master) return fv_fail(FV_ERR_STATE, "fv_train_lora_project: DoRA reads the row norms and the master of the last fv_train_lora_commit: commit these parameters first");
   FV_HIP_CHECK(hipMemcpyAsync(lora_grads, flat_grads_full, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
   for (const LoraGroup& g : ls.groups)
-    FV_TRY(fv::launch_lora_project(ls.mats, g.m0, g.m1, g.strip_begin, g.nstrips, g.max_in, flat_grads_full, lora_params, lora_grads, ls.scratch, ls.rank, ls.scale, s));
+    FV_TRY(fv::launch_lora_project(ls.mats, g.m0, g.m1, g.strip_begin, g.nstrips, g.max_in, flat_grads_full, lora_params, lora_grads, ls.scratch, ls.rank, ls.scale, s,
+                                   dora ? ls.master : nullptr, dora ? ls.norms : nullptr));
   return FV_OK;
 }
 
@@ -278,6 +319,9 @@ int fv_train_lora_forward_backward(fv_handle* h, const float* flat_params, const
   if (!lora_params || !lora_grads) return fv_fail(FV_ERR_ARG, "fv_train_lora_forward_backward: null pointer");
   if (((uintptr_t)lora_params | (uintptr_t)lora_grads) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_forward_backward: buffers must be 16-byte aligned");
   // refused HERE, before anything is enqueued
+  if (lora_dora(h))
+    return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_forward_backward: not with DoRA (the magnitude's gradient needs the pre-bias GEMM outputs, which o / down do not keep): "
+                                       "use fv_train_forward_backward + fv_train_lora_project");
   if (!fp16_backward(h))
     return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_forward_backward: the direct LoRA backward runs on the default one-pass fp16 backward (fv_train_set_options 2, 1, k)");
   if (h->train.fwd_f16) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_forward_backward: not together with the fp16 training forward (fv_train_set_forward_f16)");
@@ -295,12 +339,17 @@ int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* l
   if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_commit: null buffer");
   if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_commit: buffers must be 16-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(st);
-  const LoraState& ls = h->train.lora;
+  LoraState& ls = h->train.lora;
   // the master's head | projector front mirrors the trainable buffer's (fv_train_forward_backward reads the head there); nothing else of it is written
   FV_HIP_CHECK(hipMemcpyAsync(flat_params_master, lora_params, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
   const int f16t = h->train.grad_split == 2 ? 1 : 0;
   FV_TRY(fv::launch_commit(ls.rest, ls.rest_n, ls.rest_tiles, flat_params_master, f16t, h->f16_flags, s));
-  FV_TRY(fv::launch_lora_commit(ls.cdesc, ls.cn, ls.ctiles, ls.mats, flat_params_master, lora_params, ls.rank, ls.scale, f16t, h->f16_flags, s));
+  const bool dora = lora_dora(h);
+  if (dora) {
+    FV_TRY(lora_refresh_norms(h, flat_params_master, lora_params, nullptr, s));
+    ls.master = flat_params_master;
+  }
+  FV_TRY(fv::launch_lora_commit(ls.cdesc, ls.cn, ls.ctiles, ls.mats, flat_params_master, lora_params, ls.rank, ls.scale, f16t, h->f16_flags, s, dora ? ls.norms : nullptr));
   return FV_OK;
 }
 
@@ -310,10 +359,25 @@ int fv_train_lora_merge(fv_handle* h, float* flat_params_master, const float* lo
   if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_merge: null buffer");
   if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_merge: buffers must be 16-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(st);
-  const LoraState& ls = h->train.lora;
+  LoraState& ls = h->train.lora;
   FV_HIP_CHECK(hipMemcpyAsync(flat_params_master, lora_params, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
-  FV_TRY(fv::launch_lora_merge(ls.cdesc, ls.cn, ls.ctiles, ls.mats, flat_params_master, lora_params, ls.rank, ls.scale, s));
+  const bool dora = lora_dora(h);
+  if (dora) {     // the norms of the master BEFORE it is overwritten; they describe neither buffer afterwards: the next commit refreshes them
+    FV_TRY(lora_refresh_norms(h, flat_params_master, lora_params, nullptr, s));
+    ls.master = nullptr;
+  }
+  FV_TRY(fv::launch_lora_merge(ls.cdesc, ls.cn, ls.ctiles, ls.mats, flat_params_master, lora_params, ls.rank, ls.scale, s, dora ? ls.norms : nullptr));
   return FV_OK;
+}
+
+int fv_train_lora_init_magnitude(fv_handle* h, const float* flat_params_master, float* lora_params, fv_stream st) {
+  HandleScope _hs(h);
+  FV_TRY(lora_check(h));
+  if (!lora_dora(h)) return fv_fail(FV_ERR_STATE, "fv_train_lora_init_magnitude: LoRA mode was begun without FV_LORA_DORA");
+  if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_init_magnitude: null buffer");
+  if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_init_magnitude: buffers must be 16-byte aligned");
+  h->train.lora.master = nullptr;     // (the norm buffer now describes these buffers, but no commit of them has run)
+  return lora_refresh_norms(h, flat_params_master, lora_params, lora_params, static_cast<hipStream_t>(st));
 }
 
 }  // extern "C"

@@ -120,6 +120,8 @@ SIGNATURES = {
     "fv_train_workspace_bytes": (_i, [_vp, _i, _i, C.POINTER(C.c_size_t)]),
     "fv_train_forward_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _vp, C.c_size_t, _vp, _vp, _vp, BUCKET_CB, _vp, _vp]),
     "fv_train_lora_begin": (_i, [_vp, _i, _f, _i]),
+    "fv_train_lora_begin_ex": (_i, [_vp, _i, _f, _i, _i]),
+    "fv_train_lora_init_magnitude": (_i, [_vp, _vp, _vp, _vp]),
     "fv_train_lora_layout": (_i, [_vp, C.POINTER(TrainTensor), _i, C.POINTER(_i), C.POINTER(_i64)]),
     "fv_train_lora_project": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "fv_train_lora_commit": (_i, [_vp, _vp, _vp, _vp]),

@@ -625,14 +625,24 @@ class FastVLAEngine:
         return actions, loss, flat_grads
 
     # ---------------------------------------------------------------- LoRA mode of the slice (fv_train_lora_*; csrc/lora_path.inc)
-    def train_lora_begin(self, rank: int, alpha: Optional[float] = None, targets=None) -> None:
+    def train_lora_begin(self, rank: int, alpha: Optional[float] = None, targets=None, dora: bool = False, rslora: bool = False) -> None:
         """After train_begin(): adapters W0 + (alpha / rank) B A on the target matrices of every decoder layer (default: alpha = rank, all seven targets);
-        the master stays frozen.  Not together with train_tower_begin()."""
+        the master stays frozen.  Not together with train_tower_begin().  rslora: s = alpha / sqrt(rank).  dora: a trained magnitude per output row over the
+        direction W0 + s B A (fv_train_lora_begin_ex; initialise it with train_lora_init_magnitude)."""
         from . import lora
-        cfg = lora.check_config(rank, alpha, targets)
+        cfg = lora.check_config(rank, alpha, targets, dora=dora, rslora=rslora)
+        flags = lora.flags_of(cfg)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.fv_train_lora_begin(self.h, cfg["rank"], cfg["alpha"], lora.target_mask(cfg["targets"])), "fv_train_lora_begin", self.h)
+            if flags:
+                _lib.check(self.lib.fv_train_lora_begin_ex(self.h, cfg["rank"], cfg["alpha"], lora.target_mask(cfg["targets"]), flags), "fv_train_lora_begin_ex", self.h)
+            else:
+                _lib.check(self.lib.fv_train_lora_begin(self.h, cfg["rank"], cfg["alpha"], lora.target_mask(cfg["targets"])), "fv_train_lora_begin", self.h)
         self.lora_config = cfg
+
+    def train_lora_init_magnitude(self, flat_master: torch.Tensor, lora_params: torch.Tensor) -> None:
+        """DoRA: every lora_magnitude_vector in lora_params <- the row norms of W0 + s B A for the A, B it holds (fv_train_lora_init_magnitude), so that
+        m / n == 1 exactly and the next train_lora_commit builds what a commit without the magnitude would."""
+        _lib.check(self.lib.fv_train_lora_init_magnitude(self.h, flat_master.data_ptr(), lora_params.data_ptr(), _stream()), "fv_train_lora_init_magnitude", self.h)
 
     def train_lora_layout(self):
         """-> (tensors, total_numel) of the TRAINABLE flat buffer [head | projector | layer adapters] (fv_train_lora_layout), dicts as train_layout()'s."""
@@ -665,7 +675,8 @@ class FastVLAEngine:
         return actions, loss, lora_grads
 
     def train_lora_commit(self, flat_master: torch.Tensor, lora_params: torch.Tensor) -> None:
-        """operand images <- W0 + s B A (adapted matrices) / the master (the rest); the master's head | projector front <- lora_params' (fv_train_lora_commit)"""
+        """operand images <- W0 + s B A (adapted matrices; DoRA: diag(m / n) (W0 + s B A), the row norms n refreshed) / the master (the rest); the master's
+        head | projector front <- lora_params' (fv_train_lora_commit).  DoRA: flat_master must stay alive and in place until train_lora_project has run."""
         _lib.check(self.lib.fv_train_lora_commit(self.h, flat_master.data_ptr(), lora_params.data_ptr(), _stream()), "fv_train_lora_commit", self.h)
 
     def train_lora_merge(self, flat_master: torch.Tensor, lora_params: torch.Tensor) -> None:

@@ -1,6 +1,10 @@
 """LoRA mode of backbone training, the parts that need no device: target names and their bit mask (include/fastvla_hip.h fv_lora_target), argument checks,
 the environment twins, a host-side mirror of fv_train_lora_layout (so a layout can be inspected, and the C side checked, without a handle) and PEFT's
-initialisation of the adapters."""
+initialisation of the adapters.
+
+Two variants (fv_train_lora_begin_ex's flags): `rslora` -- rank-stabilised scaling, s = alpha / sqrt(rank) -- and `dora` -- weight-decomposed LoRA, PEFT's
+use_dora: W' = diag(m / ||V||_row) V over V = W0 + s B A with a trained magnitude m per output row ("...lora_magnitude_vector.weight", 1 x out, behind each
+target's lora_B).  Both keys appear in a configuration ONLY when true, so a plain run's configuration, adapter file and hip_extras.json are what they were."""
 from __future__ import annotations
 
 import math
@@ -45,8 +49,21 @@ def targets_of_mask(mask: int) -> Tuple[str, ...]:
     return tuple(t for i, t in enumerate(TARGETS) if mask >> i & 1)
 
 
-def check_config(rank, alpha=None, targets=None, tower: bool = False) -> Dict:
-    """-> {"rank", "alpha", "targets"} with the defaults filled in (alpha = rank, all seven targets); raises ValueError on anything the library would refuse."""
+FLAG_DORA, FLAG_RSLORA = 1, 2      # include/fastvla_hip.h fv_lora_flags
+VARIANT_KEYS = ("dora", "rslora")
+
+
+def _flag(name: str, v) -> bool:
+    if isinstance(v, bool) or v is None:
+        return bool(v)
+    if isinstance(v, int) and v in (0, 1):
+        return bool(v)
+    raise ValueError(f"{name} must be a bool, got {v!r}")
+
+
+def check_config(rank, alpha=None, targets=None, tower: bool = False, dora=False, rslora=False) -> Dict:
+    """-> {"rank", "alpha", "targets"} with the defaults filled in (alpha = rank, all seven targets), plus "dora": True / "rslora": True ONLY when asked for
+    (a plain configuration keeps exactly its three keys); raises ValueError on anything the library would refuse."""
     if isinstance(rank, bool) or int(rank) != rank:
         raise ValueError(f"lora_rank must be an integer, got {rank!r}")
     rank = int(rank)
@@ -57,21 +74,64 @@ def check_config(rank, alpha=None, targets=None, tower: bool = False) -> Dict:
         raise ValueError(f"lora_alpha must be positive and finite, got {alpha}")
     if tower:
         raise ValueError("LoRA adapters go with a frozen vision tower: lora_rank and tower=True cannot be combined")
-    return {"rank": rank, "alpha": alpha, "targets": list(parse_targets(targets))}
+    cfg = {"rank": rank, "alpha": alpha, "targets": list(parse_targets(targets))}
+    if _flag("lora_dora", dora):
+        cfg["dora"] = True
+    if _flag("lora_rslora", rslora):
+        cfg["rslora"] = True
+    return cfg
+
+
+def variants_of(cfg: Optional[Dict]) -> Dict:
+    """the variant keys of a configuration (or of a record that may predate them) as keyword arguments: {} for plain LoRA"""
+    return {k: True for k in VARIANT_KEYS if cfg and cfg.get(k)}
+
+
+def flags_of(cfg: Dict) -> int:
+    return (FLAG_DORA if cfg.get("dora") else 0) | (FLAG_RSLORA if cfg.get("rslora") else 0)
+
+
+def scale_of(cfg: Dict) -> float:
+    """s of W0 + s B A: alpha / rank, or alpha / sqrt(rank) under rsLoRA"""
+    return cfg["alpha"] / math.sqrt(cfg["rank"]) if cfg.get("rslora") else cfg["alpha"] / cfg["rank"]
+
+
+def _env_flag(env, name: str) -> bool:
+    raw = (env.get(name) or "").strip()
+    if raw in ("", "0"):
+        return False
+    if raw == "1":
+        return True
+    raise ValueError(f"{name} must be 0 or 1, got '{raw}'")
+
+
+def variants_from_env(environ=None) -> Dict:
+    """FASTVLA_LORA_DORA / FASTVLA_LORA_RSLORA ("1" on; unset / empty / "0" off; anything else raises) -> {"dora": True} / {"rslora": True} / both / {}"""
+    env = os.environ if environ is None else environ
+    out = {}
+    if _env_flag(env, "FASTVLA_LORA_DORA"):
+        out["dora"] = True
+    if _env_flag(env, "FASTVLA_LORA_RSLORA"):
+        out["rslora"] = True
+    return out
 
 
 def config_from_env(environ=None) -> Optional[Dict]:
-    """FASTVLA_LORA_RANK (unset / empty / 0: no LoRA), FASTVLA_LORA_ALPHA, FASTVLA_LORA_TARGETS (comma-separated) -> check_config's dict or None."""
+    """FASTVLA_LORA_RANK (unset / empty / 0: no LoRA), FASTVLA_LORA_ALPHA, FASTVLA_LORA_TARGETS (comma-separated), FASTVLA_LORA_DORA / FASTVLA_LORA_RSLORA
+    (0 / 1) -> check_config's dict or None.  A variant without a rank raises."""
     env = os.environ if environ is None else environ
     raw = (env.get("FASTVLA_LORA_RANK") or "").strip()
+    var = variants_from_env(env)
     if raw in ("", "0"):
+        if var:
+            raise ValueError("FASTVLA_LORA_DORA / FASTVLA_LORA_RSLORA need a rank (FASTVLA_LORA_RANK)")
         return None
     try:
         rank = int(raw)
     except ValueError:
         raise ValueError(f"FASTVLA_LORA_RANK must be an integer, got '{raw}'") from None
     alpha = (env.get("FASTVLA_LORA_ALPHA") or "").strip()
-    return check_config(rank, float(alpha) if alpha else None, env.get("FASTVLA_LORA_TARGETS") or None)
+    return check_config(rank, float(alpha) if alpha else None, env.get("FASTVLA_LORA_TARGETS") or None, **var)
 
 
 def direct_from_env(environ=None) -> bool:
@@ -98,9 +158,11 @@ def logical_shapes(model: ModelConfig) -> Dict[str, Tuple[int, int]]:
             "gate_proj": (l.inter, l.hidden), "up_proj": (l.inter, l.hidden), "down_proj": (l.hidden, l.inter)}
 
 
-def lora_layout(model: ModelConfig, rank: int, targets=None, *, state_dim: int = 14, action_dim: int = 14, hidden_dim: int = 1024, fusion_dim: int = 1024):
+def lora_layout(model: ModelConfig, rank: int, targets=None, *, state_dim: int = 14, action_dim: int = 14, hidden_dim: int = 1024, fusion_dim: int = 1024,
+                dora: bool = False):
     """The trainable flat buffer of LoRA mode, as fv_train_lora_layout reports it: -> (tensors, total_numel), tensors = dicts with name, offset, numel, rows,
-    cols, bucket, packing (always 0).  [ head | projector | layer 0 adapters .. ]: every tensor starts on a multiple of 4 floats."""
+    cols, bucket, packing (always 0).  [ head | projector | layer 0 adapters .. ]: every tensor starts on a multiple of 4 floats.  dora: each target's
+    lora_magnitude_vector (1 x out) behind its lora_B."""
     names = parse_targets(targets)
     H, CO = model.llm.hidden, model.tower.out_dim
     ds, da, hid, fus = state_dim, action_dim, hidden_dim, fusion_dim
@@ -126,12 +188,15 @@ def lora_layout(model: ModelConfig, rank: int, targets=None, *, state_dim: int =
             pre = f"model.layers.{l}.{_MODULE[t]}.{t}"
             add(pre + ".lora_A.weight", rank, i, 3 + l)
             add(pre + ".lora_B.weight", o, rank, 3 + l)
+            if dora:
+                add(pre + ".lora_magnitude_vector.weight", 1, o, 3 + l)
     return out, off
 
 
 def init_adapters(flat: torch.Tensor, tensors: Sequence[Dict], seed: int = 0) -> None:
     """PEFT's initialisation into the trainable buffer: lora_A Kaiming-uniform with a = sqrt(5) (U(-1/sqrt(in), 1/sqrt(in))) from a seeded CPU generator, in
-    layout order, lora_B = 0 -- so the adapted model starts as the base model."""
+    layout order, lora_B = 0 -- so the adapted model starts as the base model.  (DoRA's magnitudes are not touched: FastVLAEngine.train_lora_init_magnitude
+    computes them on the device from the master.)"""
     g = torch.Generator(device="cpu").manual_seed(int(seed))
     for t in tensors:
         v = flat[t["offset"]: t["offset"] + t["numel"]]

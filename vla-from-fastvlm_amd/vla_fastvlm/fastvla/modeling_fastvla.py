@@ -28,7 +28,8 @@ class FastVLAPolicy(nn.Module):
         self._unfrozen = None   # training/unfrozen.py UnfrozenState once enable_backbone_training() ran
 
     def enable_backbone_training(self, bucket_min_numel: int = 1 << 22, tower: Optional[bool] = None, lora_rank: Optional[int] = None,
-                                 lora_alpha: Optional[float] = None, lora_targets=None, lora_seed: int = 0, lora_direct: Optional[bool] = None):
+                                 lora_alpha: Optional[float] = None, lora_targets=None, lora_seed: int = 0, lora_direct: Optional[bool] = None,
+                                 lora_dora: Optional[bool] = None, lora_rslora: Optional[bool] = None):
         """Extension of this build: fine-tune the Qwen2 decoder + mm_projector together with the action expert
         (image tokens spliced); tower=True (or FASTVLA_TRAIN_TOWER=1) trains the FastViT-HD tower too, in its inference form, otherwise it stays
         frozen.  Explicit on purpose: the reference's `freeze_backbone=False` trains nothing but the head either (model/fastvlm_adapter.py:501),
@@ -41,12 +42,25 @@ class FastVLAPolicy(nn.Module):
         lora_direct=True (with lora_rank; or FASTVLA_LORA_DIRECT=1): the DIRECT LoRA backward -- dA / dB straight from activations and output gradients
         (fv_train_lora_forward_backward); the full-size gradient buffer is never allocated.  A property of the run, not of the adapters: adapter and optimiser
         files written in one mode load in the other; a state that is already running keeps the mode it was started in (lora_direct=None), and asking it
-        for the other mode explicitly raises RuntimeError."""
+        for the other mode explicitly raises RuntimeError.
+
+        lora_rslora=True (or FASTVLA_LORA_RSLORA=1): rank-stabilised scaling, W0 + (lora_alpha / sqrt(r)) B A.  lora_dora=True (or FASTVLA_LORA_DORA=1):
+        weight-decomposed LoRA (PEFT's use_dora) -- a trained magnitude per output row over the direction W0 + s B A, initialised to the row norms so the
+        adapted model starts as the base model.  Both ARE properties of the adapters: they are recorded with {rank, alpha, targets} wherever those travel.
+        DoRA runs on the projected backward only: lora_dora=True with lora_direct=True raises ValueError."""
         from fastvla_hip import lora as _lora
         if tower is None:
             tower = os.environ.get("FASTVLA_TRAIN_TOWER", "0") == "1"
         if lora_rank is None and lora_alpha is None and lora_targets is None:
+            if (lora_dora or lora_rslora) and (os.environ.get("FASTVLA_LORA_RANK") or "").strip() in ("", "0"):
+                raise ValueError("lora_dora / lora_rslora need a rank (lora_rank or FASTVLA_LORA_RANK)")
             lcfg = _lora.config_from_env()       # the environment twins, in the style of FASTVLA_TRAIN_TOWER
+            if lcfg is not None:                 # (an explicit argument beats its environment twin)
+                for key, arg in (("dora", lora_dora), ("rslora", lora_rslora)):
+                    if arg is not None:
+                        lcfg.pop(key, None)
+                        if arg:
+                            lcfg[key] = True
             if lcfg is None and (lora_direct or (lora_direct is None and _lora.direct_from_env())):
                 raise ValueError("lora_direct / FASTVLA_LORA_DIRECT need a rank (lora_rank or FASTVLA_LORA_RANK)")
             if lcfg is not None and tower:
@@ -54,7 +68,11 @@ class FastVLAPolicy(nn.Module):
         else:
             if lora_rank is None:
                 raise ValueError("lora_alpha / lora_targets / lora_direct need lora_rank")
-            lcfg = _lora.check_config(lora_rank, lora_alpha, lora_targets, tower=bool(tower))
+            var = _lora.variants_from_env()
+            lcfg = _lora.check_config(lora_rank, lora_alpha, lora_targets, tower=bool(tower), dora=var.get("dora", False) if lora_dora is None else lora_dora,
+                                      rslora=var.get("rslora", False) if lora_rslora is None else lora_rslora)
+        if lcfg is not None and lcfg.get("dora") and (lora_direct or (lora_direct is None and self._unfrozen is None and _lora.direct_from_env())):
+            raise ValueError("lora_dora and lora_direct cannot be combined: DoRA's magnitude gradient needs the full weight gradient (the projected backward)")
         if self._unfrozen is not None and bool(tower) and not self._unfrozen.train_tower:
             raise RuntimeError("backbone training is already running with the tower frozen: ask for tower=True on the first call")
         if self._unfrozen is not None and lcfg is not None and self._unfrozen.lora != lcfg:
@@ -150,7 +168,8 @@ class FastVLAPolicy(nn.Module):
             # moments of a whole-backbone run (training/unfrozen.py writes one flat m / v over every trainable tensor): the run resumes unfrozen,
             # training what the checkpointed run trained (lora: optimizer.pt's record of a LoRA run -- its m / v / flat cover the trainable buffer)
             if lora is not None:
-                self.enable_backbone_training(lora_rank=lora["rank"], lora_alpha=lora["alpha"], lora_targets=lora["targets"])
+                self.enable_backbone_training(lora_rank=lora["rank"], lora_alpha=lora["alpha"], lora_targets=lora["targets"],
+                                              lora_dora=bool(lora.get("dora")), lora_rslora=bool(lora.get("rslora")))
             else:
                 self.enable_backbone_training(tower=train_tower)
         if self._unfrozen is not None:

@@ -248,7 +248,8 @@ class Trainer:
             self.model.model.backbone.load_backbone_state(vlm)
             if un is not None:
                 self.model.enable_backbone_training(tower=un.train_tower, **({"lora_rank": un.lora["rank"], "lora_alpha": un.lora["alpha"], "lora_targets": un.lora["targets"],
-                                                                                "lora_direct": un.lora_direct}
+                                                                                "lora_direct": un.lora_direct, "lora_dora": bool(un.lora.get("dora")),
+                                                                                "lora_rslora": bool(un.lora.get("rslora"))}
                                                                                if un.lora is not None else {}))
         own = self.model.state_dict()
         # `.io_norm.` / splice-mode keys exist in state_dict() only while they are on, so a freshly built model does not list them -- let them

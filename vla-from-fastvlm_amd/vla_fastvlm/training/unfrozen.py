@@ -21,6 +21,10 @@ allocated; the full master and the full gradient buffer remain.
 Direct LoRA mode (`lora_direct=True`; fv_train_lora_forward_backward): the backward writes head, projector and adapter gradients straight into the
 trainable-layout gradient buffer (dA = s (dY B)^T X, dB = s dY^T (X A^T) from the gradient rows and the kept activations) -- the full weight gradient is never
 formed, the full-size gradient buffer is never allocated (`self.g is None`) and fv_train_lora_project is not called; everything behind the backward is the same.
+
+Variants (keys of `lora`, present only when true): "rslora" -- s = alpha / sqrt(rank); "dora" -- every target also trains a magnitude per output row,
+W' = diag(m / ||V||_row) V over V = W0 + s B A (the norm a constant in the backward, as in PEFT).  m starts as the row norms (fv_train_lora_init_magnitude), so
+the adapted model starts as the base model bit for bit; the step is the projected one (the commit refreshes the norms the projection reads); not with lora_direct.
 """
 from __future__ import annotations
 
@@ -47,12 +51,14 @@ class UnfrozenState:
             raise ValueError("LoRA adapters go with a frozen vision tower: lora and train_tower cannot be combined")
         if lora_direct and lora is None:
             raise ValueError("lora_direct needs a LoRA configuration (lora_rank)")
+        if lora_direct and lora.get("dora"):
+            raise ValueError("lora_dora and lora_direct cannot be combined: DoRA's magnitude gradient needs the full weight gradient (the projected backward)")
         eng.train_begin()
         self.train_tower = bool(train_tower)
         self.lora = dict(lora) if lora is not None else None      # {"rank", "alpha", "targets"}: the decoder's matrices frozen, adapters trained
         self.lora_direct = bool(lora_direct)                      # the run's backward mode: NOT part of self.lora (what adapter / optimiser files compare)
         if self.lora is not None:
-            eng.train_lora_begin(self.lora["rank"], self.lora["alpha"], self.lora["targets"])
+            eng.train_lora_begin(self.lora["rank"], self.lora["alpha"], self.lora["targets"], dora=bool(self.lora.get("dora")), rslora=bool(self.lora.get("rslora")))
         if self.train_tower:
             eng.train_tower_begin()        # the FastViT-HD tower's inference-form tensors join the flat master (fv_train_tower_*)
         self._tws: Dict[int, torch.Tensor] = {}
@@ -77,6 +83,9 @@ class UnfrozenState:
             self.lflat = torch.zeros(self.lora_total, dtype=torch.float32, device=dev)
             self.lflat[: self.front].copy_(self.flat[: self.front])
             _lora.init_adapters(self.lflat, self.lora_tensors, seed=lora_seed)
+            if self.lora.get("dora"):
+                eng.train_lora_init_magnitude(self.flat, self.lflat)      # m = ||W0|| per row (lora_B = 0): m / n == 1 exactly
+                eng.train_lora_commit(self.flat, self.lflat)              # the projection reads the norms and the master of a commit: the same operand images, bit for bit
             self.lg = torch.zeros_like(self.lflat)
         self.trainable = self.lflat if self.lora is not None else self.flat     # what the optimiser steps over
         views = eng.head_views(self.trainable[:hn])
@@ -125,8 +134,8 @@ class UnfrozenState:
 
     # ------------------------------------------------------------------ LoRA: adapters in and out, merge
     def lora_state(self) -> Dict:
-        """what an adapter checkpoint holds: {"config": {rank, alpha, targets}, "tensors": {PEFT name -> lora_A / lora_B, and the mm_projector's four tensors,
-        which train in full beside them}} (CPU copies)"""
+        """what an adapter checkpoint holds: {"config": {rank, alpha, targets[, dora][, rslora]}, "tensors": {PEFT name -> lora_A / lora_B (DoRA:
+        lora_magnitude_vector too), and the mm_projector's four tensors, which train in full beside them}} (CPU copies)"""
         assert self.lora is not None
         out = {}
         for t in self.lora_tensors:
@@ -142,6 +151,8 @@ class UnfrozenState:
         cfg = state.get("config", {})
         if int(cfg.get("rank", -1)) != self.lora["rank"] or list(cfg.get("targets", [])) != list(self.lora["targets"]) or float(cfg.get("alpha", -1)) != float(self.lora["alpha"]):
             raise ValueError(f"adapter file was written with {cfg}, this run uses {self.lora}")
+        if any(bool(cfg.get(k)) != bool(self.lora.get(k)) for k in ("dora", "rslora")):     # (a file that predates the keys is plain LoRA)
+            raise ValueError(f"adapter file was written with {cfg}, this run uses {self.lora} (DoRA / rsLoRA adapters and plain LoRA adapters are not interchangeable)")
         tensors = state.get("tensors", {})
         want = [t for t in self.lora_tensors if t["bucket"] != 0]
         missing = [t["name"] for t in want if t["name"] not in tensors]
@@ -167,14 +178,19 @@ class UnfrozenState:
 
     def merge_lora(self) -> None:
         """W0 += s B A into the master (fv_train_lora_merge: the very fp32 values the adapted commit rounds), then lora_B = 0: the model is unchanged, the master
-        is now a plain fine-tuned decoder that named_backbone_tensors() / the backbone export write under the reference's keys."""
+        is now a plain fine-tuned decoder that named_backbone_tensors() / the backbone export write under the reference's keys.  DoRA: the master receives
+        diag(m / n) (W0 + s B A), and the magnitudes are re-initialised from it (m = its row norms, m / n == 1 exactly), so the adapted commit of the merged
+        master is the plain one."""
         assert self.lora is not None
         self.eng.train_lora_merge(self.flat, self.lflat)
+        dora = bool(self.lora.get("dora"))
         for t in self.lora_tensors:
-            if t["name"].endswith(".lora_B.weight"):
+            if t["name"].endswith(".lora_B.weight") or (dora and t["name"].endswith(".lora_magnitude_vector.weight")):
                 self.lflat[t["offset"]: t["offset"] + t["numel"]].zero_()
                 self.m[t["offset"]: t["offset"] + t["numel"]].zero_()
                 self.v[t["offset"]: t["offset"] + t["numel"]].zero_()
+        if dora:
+            self.eng.train_lora_init_magnitude(self.flat, self.lflat)
         self.lora_merged, self.lora_adapters_zero = True, True
         self.commit()
 

@@ -28,7 +28,8 @@ BACKBONE_PREFIX = "model.backbone.model."
 EXTRAS_FILE = "hip_extras.json"
 # a LoRA run (enable_backbone_training(lora_rank=...)): the adapters, the mm_projector that trains beside them and {rank, alpha, targets} in a file of their
 # own; EXTRAS_FILE names it under "lora" = {"rank", "alpha", "targets", "file", "direct"}, and a directory whose extras name adapters that are not there does not
-# load.  "direct" records the run's backward mode (the direct LoRA backward; absent = projected): the default when loading has to switch LoRA mode on itself
+# load.  "dora" / "rslora" (the adapters' variants) are there only when true: a plain run's record is what it always was, and a record without them is plain LoRA.
+# "direct" records the run's backward mode (the direct LoRA backward; absent = projected): the default when loading has to switch LoRA mode on itself
 LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
@@ -77,7 +78,8 @@ def load_lora_adapters(policy: FastVLAPolicy, checkpoint_dir, lora_extras: dict)
         raise FileNotFoundError(f"{Path(checkpoint_dir) / EXTRAS_FILE} records LoRA adapters (rank {lora_extras.get('rank')}) in '{f.name}', which is not there")
     # (a policy that is already in LoRA mode keeps the backward mode it was started in and just receives the adapters)
     mode = {} if getattr(policy, "_unfrozen", None) is not None else {"lora_direct": bool(lora_extras.get("direct", False))}
-    un = policy.enable_backbone_training(lora_rank=int(lora_extras["rank"]), lora_alpha=float(lora_extras["alpha"]), lora_targets=list(lora_extras["targets"]), **mode)
+    un = policy.enable_backbone_training(lora_rank=int(lora_extras["rank"]), lora_alpha=float(lora_extras["alpha"]), lora_targets=list(lora_extras["targets"]),
+                                         lora_dora=bool(lora_extras.get("dora")), lora_rslora=bool(lora_extras.get("rslora")), **mode)
     un.load_lora_state(torch.load(f, map_location="cpu"))
 
 
