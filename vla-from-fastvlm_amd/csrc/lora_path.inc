@@ -14,125 +14,125 @@
 // target also owns a magnitude vector m (`out` floats, "...lora_magnitude_vector.weight", behind its lora_B in the trainable buffer) and runs as
 // diag(m / n) (W0 + s . B . A), n the row norms, which the commit refreshes into a buffer the handle owns and the projection reads (norm held constant in the
 // backward, as PEFT does); the direct backward refuses it.
+// Structure.  lora_tensors lays the trainable buffer out and keeps every adapter's offsets by (layer, target, A | B | m).  build_lora_tables makes every device table
+// and the direct backward's packs in ONE pass over train_tensors, finding a layer's adapted tensors by TrainTensor::layer / role and building each descriptor with
+// train_path.inc's commit_desc_of (so does fv_train_commit's table); the entry points share check_buffers, write_layout and upload.
 // Kernels: lora_kernels.hip, lora_direct_kernels.hip.
 
 namespace {
 
 const char* const LORA_TARGET_NAMES[7] = {"self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"};
 
-struct LoraLogical { int out, in, row0, blk; const char* packed; int kind, part; };   // one target of a layer: where it sits inside its packed tensor
+// one target of a layer: where it sits inside its packed tensor (that tensor's DR_* role, `which` of lora_direct_call's four, row layout `kind`, `part` within it)
+struct LoraLogical { int out, in, row0, blk, role, which, kind, part; };
 
 void lora_logicals(const fv_model_desc& d, LoraLogical out[7]) {
   const int H = d.llm_hidden, I = d.llm_inter, D = d.llm_head_dim, qd = d.llm_heads * D, kd = d.llm_kv_heads * D;
-  out[0] = {qd, H, 0, 8, "self_attn.qkv_proj.weight", 1, 0};
-  out[1] = {kd, H, qd, 8, "self_attn.qkv_proj.weight", 1, 1};
-  out[2] = {kd, H, qd + kd, 8, "self_attn.qkv_proj.weight", 1, 2};
-  out[3] = {H, qd, 0, 8, "self_attn.o_proj.weight", 0, 0};
-  out[4] = {I, H, 0, 16, "mlp.gate_up_proj.weight", 2, 0};
-  out[5] = {I, H, 8, 16, "mlp.gate_up_proj.weight", 2, 1};
-  out[6] = {H, I, 0, 8, "mlp.down_proj.weight", 0, 0};
+  out[0] = {qd, H, 0, 8, DR_QKV_W, 0, 1, 0};
+  out[1] = {kd, H, qd, 8, DR_QKV_W, 0, 1, 1};
+  out[2] = {kd, H, qd + kd, 8, DR_QKV_W, 0, 1, 2};
+  out[3] = {H, qd, 0, 8, DR_O_W, 1, 0, 0};
+  out[4] = {I, H, 0, 16, DR_GU_W, 2, 2, 0};
+  out[5] = {I, H, 8, 16, DR_GU_W, 2, 2, 1};
+  out[6] = {H, I, 0, 8, DR_DOWN_W, 3, 0, 0};
 }
 
-// the trainable buffer: head and projector exactly as train_tensors lists them (same offsets), then lora_A (rank x in) / lora_B (out x rank) per layer and target
-std::vector<TrainTensor> lora_tensors(fv_handle* h, int rank, int mask, int64_t* total, int64_t* front, bool dora = false) {
-  std::vector<TrainTensor> out;
+// the trainable buffer: head and projector exactly as train_tensors lists them (same offsets), then lora_A (rank x in) / lora_B (out x rank) [/ DoRA's magnitude,
+// one float per output row] per layer and target
+struct LoraLayout {
+  std::vector<TrainTensor> tensors;
+  int64_t total = 0, front = 0;      // floats in all; floats of the head + projector front
+  std::vector<int64_t> offs;         // [layer][target][A, B, m]: offset in the trainable buffer, -1 = not there
+  int64_t off(int l, int k, int abm) const { return offs[((size_t)l * 7 + k) * 3 + abm]; }
+};
+LoraLayout lora_tensors(fv_handle* h, int rank, int mask, bool dora) {
+  LoraLayout lay;
   int64_t off = 0;
   for (const TrainTensor& t : train_tensors(h, nullptr)) {
     if (t.bucket > TB_PROJ) { off = t.off; break; }
     TrainTensor c = t;
     c.lib = nullptr; c.tcopy = c.tcopy16 = c.row16 = nullptr;
-    out.push_back(c);
+    lay.tensors.push_back(c);
   }
-  if (front) *front = off;
+  lay.front = off;
+  lay.offs.assign((size_t)h->d.llm_layers * 7 * 3, -1);
   LoraLogical lg[7];
   lora_logicals(h->d, lg);
+  static const char* const suffix[3] = {".lora_A.weight", ".lora_B.weight", ".lora_magnitude_vector.weight"};
   for (int l = 0; l < h->d.llm_layers; ++l)
     for (int k = 0; k < 7; ++k) {
       if (!(mask >> k & 1)) continue;
       const std::string pre = "model.layers." + std::to_string(l) + "." + LORA_TARGET_NAMES[k];
-      for (int ab = 0; ab < 2; ++ab) {
+      for (int abm = 0; abm < (dora ? 3 : 2); ++abm) {
         TrainTensor t;
-        t.name = pre + (ab ? ".lora_B.weight" : ".lora_A.weight");
-        t.rows = ab ? lg[k].out : rank; t.cols = ab ? rank : lg[k].in; t.numel = (int64_t)t.rows * t.cols;
-        t.off = off; t.bucket = TB_LAYER0 + l; t.is_mat = true;
+        t.name = pre + suffix[abm];
+        t.rows = abm == 0 ? rank : (abm == 1 ? lg[k].out : 1); t.cols = abm == 0 ? lg[k].in : (abm == 1 ? rank : lg[k].out); t.numel = (int64_t)t.rows * t.cols;
+        t.off = off; t.bucket = TB_LAYER0 + l; t.is_mat = abm < 2;
+        lay.offs[((size_t)l * 7 + k) * 3 + abm] = off;
         off += (t.numel + 3) / 4 * 4;
-        out.push_back(t);
-      }
-      if (dora) {     // DoRA's magnitude, one float per output row
-        TrainTensor t;
-        t.name = pre + ".lora_magnitude_vector.weight";
-        t.rows = 1; t.cols = lg[k].out; t.numel = lg[k].out;
-        t.off = off; t.bucket = TB_LAYER0 + l; t.is_mat = false;
-        off += (t.numel + 3) / 4 * 4;
-        out.push_back(t);
+        lay.tensors.push_back(t);
       }
     }
-  if (total) *total = off;
-  return out;
+  lay.total = off;
+  return lay;
 }
 
-// every table the LoRA entry points read: the adapted matrices, the commit descriptors of the packed tensors that hold them, the plain commit table of the rest
+// every table the LoRA entry points read, from ONE pass over train_tensors: the adapted matrices, the commit descriptors of the packed tensors that hold them, the
+// plain commit table of the rest, and the direct backward's calls (one per packed tensor and layer, the adapters inside it as slots in part order)
 int build_lora_tables(fv_handle* h) {
   LoraState& ls = h->train.lora;
-  const int rank = ls.rank;
+  const fv_model_desc& d = h->d;
+  const int rank = ls.rank, qd = d.llm_heads * d.llm_head_dim, kd = d.llm_kv_heads * d.llm_head_dim;
   LoraLogical lg[7];
-  lora_logicals(h->d, lg);
-  int64_t total = 0, front = 0;
+  lora_logicals(d, lg);
   const bool dora = (ls.flags & FV_LORA_DORA) != 0;
-  const std::vector<TrainTensor> lt = lora_tensors(h, rank, ls.mask, &total, &front, dora);
-  std::map<std::string, int64_t> loff;
-  for (const TrainTensor& t : lt) loff[t.name] = t.off;
+  const LoraLayout lay = lora_tensors(h, rank, ls.mask, dora);
   std::vector<fv::LoraMat> mats;
   std::vector<fv::LoraCommitDesc> cds;
   std::vector<fv::CommitDesc> rest;
+  std::vector<fv::LoraDirectPack> packs((size_t)d.llm_layers * 4, fv::LoraDirectPack{});
   int ctiles = 0, rtiles = 0, strips = 0, bands = 0;
   long long nrows = 0;
   for (const TrainTensor& t : train_tensors(h, nullptr)) {
     if (!t.lib) continue;
-    fv::CommitDesc c{};
-    c.src_off = t.off; c.dst = t.lib; c.is_mat = t.is_mat ? 1 : 0;
-    int ntile;
-    if (t.is_mat) {
-      c.rows = t.rows; c.cols = t.cols;
-      c.dstT16 = t.tcopy16 ? *t.tcopy16 : nullptr; c.dstTb = t.tcopy ? *t.tcopy : nullptr;
-      c.dst16 = (h->train.fwd_f16 && t.row16) ? *t.row16 : nullptr; c.scale16 = t.scale16;
-      ntile = ((t.rows + 63) / 64) * ((t.cols + 63) / 64);
-    } else {
-      c.rows = 1; c.cols = (int)t.numel;
-      ntile = (int)((t.numel + 4095) / 4096);
-    }
     fv::LoraCommitDesc lc{};
-    lc.c = c; lc.mat[0] = lc.mat[1] = lc.mat[2] = -1;
+    int ntile = 0;
+    FV_TRY(commit_desc_of(h, t, lc.c, ntile));
+    lc.mat[0] = lc.mat[1] = lc.mat[2] = -1;
     bool adapted = false;
-    const size_t lpos = t.name.find("model.layers.");
-    if (t.is_mat && lpos == 0 && t.bucket >= TB_LAYER0) {
-      const std::string pre = t.name.substr(0, t.name.find('.', 13) + 1);   // "model.layers.<l>."
-      for (int k = 0; k < 7; ++k) {
-        if (!(ls.mask >> k & 1) || t.name != pre + lg[k].packed) continue;
-        fv::LoraMat m{};
-        m.w_off = t.off; m.out = lg[k].out; m.in = lg[k].in; m.row0 = lg[k].row0; m.blk = lg[k].blk;
-        m.a_off = loff.at(pre + LORA_TARGET_NAMES[k] + ".lora_A.weight");
-        m.b_off = loff.at(pre + LORA_TARGET_NAMES[k] + ".lora_B.weight");
-        if (m.in != t.cols || m.out % 32 || m.in % 32)
-          return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_begin: %s%s is %d x %d (adapted matrices need dimensions that are multiples of 32)", pre.c_str(),
-                         LORA_TARGET_NAMES[k], m.out, m.in);
-        m.m_off = dora ? loff.at(pre + LORA_TARGET_NAMES[k] + ".lora_magnitude_vector.weight") : -1;
-        m.n_off = nrows; nrows += m.out;
-        m.strip0 = strips;
-        strips += (m.out + fv::LORA_STRIP_ROWS - 1) / fv::LORA_STRIP_ROWS;
-        lc.kind = lg[k].kind; lc.mat[lg[k].part] = (int)mats.size();
-        mats.push_back(m);
-        adapted = true;
+    for (int k = 0; k < 7 && t.layer >= 0; ++k) {
+      if (!(ls.mask >> k & 1) || t.role != lg[k].role) continue;
+      const int l = t.layer;
+      fv::LoraMat m{};
+      m.w_off = t.off; m.out = lg[k].out; m.in = lg[k].in; m.row0 = lg[k].row0; m.blk = lg[k].blk;
+      m.a_off = lay.off(l, k, 0); m.b_off = lay.off(l, k, 1); m.m_off = lay.off(l, k, 2);
+      if (m.in != t.cols || m.out % 32 || m.in % 32)
+        return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_begin: model.layers.%d.%s is %d x %d (adapted matrices need dimensions that are multiples of 32)", l,
+                       LORA_TARGET_NAMES[k], m.out, m.in);
+      m.n_off = nrows; nrows += m.out;
+      m.strip0 = strips;
+      strips += (m.out + fv::LORA_STRIP_ROWS - 1) / fv::LORA_STRIP_ROWS;
+      lc.kind = lg[k].kind; lc.mat[lg[k].part] = (int)mats.size();
+      mats.push_back(m);
+      adapted = true;
+      fv::LoraDirectPack& pk = packs[(size_t)l * 4 + lg[k].which];
+      if (pk.nm == 0) {
+        pk.kind = lg[k].kind; pk.r = rank; pk.qd = qd; pk.kd = kd; pk.K = t.cols; pk.Np = t.rows;
+        pk.slot_of_part[0] = pk.slot_of_part[1] = pk.slot_of_part[2] = -1;
       }
+      pk.slot_of_part[lg[k].part] = pk.nm;
+      pk.a_off[pk.nm] = m.a_off; pk.b_off[pk.nm] = m.b_off;
+      ++pk.nm;
+      pk.NCp = (pk.nm * rank + 31) / 32 * 32;
     }
     if (adapted) {
-      lc.qd = h->d.llm_heads * h->d.llm_head_dim; lc.kd = h->d.llm_kv_heads * h->d.llm_head_dim;
+      lc.qd = qd; lc.kd = kd;
       lc.c.tile0 = ctiles; ctiles += ntile;
       lc.band0 = bands; bands += (t.rows + 63) / 64;
       cds.push_back(lc);
     } else {
-      c.tile0 = rtiles; rtiles += ntile;
-      rest.push_back(c);
+      lc.c.tile0 = rtiles; rtiles += ntile;
+      rest.push_back(lc.c);
     }
   }
   if (mats.empty()) return fv_fail(FV_ERR_ARG, "fv_train_lora_begin: no target matrix selected");
@@ -152,16 +152,10 @@ int build_lora_tables(fv_handle* h) {
     scratch = std::max(scratch, used);
   }
   ls.groups.push_back(g);
+  FV_TRY(upload(h, mats, &ls.mats)); ls.nmats = (int)mats.size();
+  FV_TRY(upload(h, cds, &ls.cdesc)); ls.cn = (int)cds.size(); ls.ctiles = ctiles;
+  FV_TRY(upload(h, rest, &ls.rest)); ls.rest_n = (int)rest.size(); ls.rest_tiles = rtiles;
   void* p = nullptr;
-  FV_TRY(dev_alloc(h, mats.size() * sizeof(fv::LoraMat), &p));
-  FV_HIP_CHECK(hipMemcpy(p, mats.data(), mats.size() * sizeof(fv::LoraMat), hipMemcpyHostToDevice));
-  ls.mats = static_cast<fv::LoraMat*>(p); ls.nmats = (int)mats.size();
-  FV_TRY(dev_alloc(h, cds.size() * sizeof(fv::LoraCommitDesc), &p));
-  FV_HIP_CHECK(hipMemcpy(p, cds.data(), cds.size() * sizeof(fv::LoraCommitDesc), hipMemcpyHostToDevice));
-  ls.cdesc = static_cast<fv::LoraCommitDesc*>(p); ls.cn = (int)cds.size(); ls.ctiles = ctiles;
-  FV_TRY(dev_alloc(h, rest.size() * sizeof(fv::CommitDesc), &p));
-  FV_HIP_CHECK(hipMemcpy(p, rest.data(), rest.size() * sizeof(fv::CommitDesc), hipMemcpyHostToDevice));
-  ls.rest = static_cast<fv::CommitDesc*>(p); ls.rest_n = (int)rest.size(); ls.rest_tiles = rtiles;
   if (scratch > ls.scratch_floats) {
     FV_TRY(dev_alloc(h, scratch * 4, &p));
     ls.scratch = static_cast<float*>(p); ls.scratch_floats = scratch;
@@ -171,30 +165,8 @@ int build_lora_tables(fv_handle* h) {
     FV_TRY(dev_alloc(h, (size_t)nrows * 4, &p));
     ls.norms = static_cast<float*>(p); ls.norm_floats = (size_t)nrows;
   }
-  ls.front = front; ls.total = total;
-  // the direct backward's calls: one per packed tensor and layer, the adapters inside it as slots in part order
-  {
-    const fv_model_desc& d = h->d;
-    const int qd = d.llm_heads * d.llm_head_dim, kd = d.llm_kv_heads * d.llm_head_dim;
-    ls.packs.assign((size_t)d.llm_layers * 4, fv::LoraDirectPack{});
-    for (int l = 0; l < d.llm_layers; ++l)
-      for (int k = 0; k < 7; ++k) {
-        if (!(ls.mask >> k & 1)) continue;
-        const int which = k < 3 ? 0 : (k == 3 ? 1 : (k < 6 ? 2 : 3));
-        fv::LoraDirectPack& pk = ls.packs[(size_t)l * 4 + which];
-        if (pk.nm == 0) {
-          pk.kind = lg[k].kind; pk.r = rank; pk.qd = qd; pk.kd = kd; pk.K = lg[k].in;
-          pk.Np = which == 0 ? qd + 2 * kd : (which == 2 ? 2 * d.llm_inter : lg[k].out);
-          pk.slot_of_part[0] = pk.slot_of_part[1] = pk.slot_of_part[2] = -1;
-        }
-        const std::string pre = "model.layers." + std::to_string(l) + "." + LORA_TARGET_NAMES[k];
-        pk.slot_of_part[lg[k].part] = pk.nm;
-        pk.a_off[pk.nm] = loff.at(pre + ".lora_A.weight");
-        pk.b_off[pk.nm] = loff.at(pre + ".lora_B.weight");
-        ++pk.nm;
-        pk.NCp = (pk.nm * rank + 31) / 32 * 32;
-      }
-  }
+  ls.front = lay.front; ls.total = lay.total;
+  ls.packs = packs;
   return FV_OK;
 }
 
@@ -218,14 +190,15 @@ int lora_direct_scratch(fv_handle* h, float** scratch, size_t* floats) {
 }
 
 // dA, dB of the adapters inside packed tensor `which` (0 q|k|v, 1 o, 2 gate/up, 3 down) of layer l; nothing at all when none of its matrices is a target
-int lora_direct_call(fv_handle* h, int l, int which, const bf16_t* dY16, const bf16_t* X, int xkind, int ldx, int lo_off, int R, const float* lora_params,
-                     float* lora_grads, hipStream_t s) {
+// from the gradient's fp16 rows dY16 [R][Np] and the kept activation X (split bf16 or fp16 rows)
+int lora_direct_call(const DecCtx& c, int l, int which, const bf16_t* dY16, const ActOp& X, int R) {
+  fv_handle* h = c.h; hipStream_t s = c.s;
   const LoraState& ls = h->train.lora;
   const fv::LoraDirectPack& pk = ls.packs[(size_t)l * 4 + which];
   if (pk.nm == 0) return FV_OK;
   // flop: the four skinny products; bytes: dY and X twice each
-  FV_P(FV_FAM_GEMM, 4.0 * R * pk.NCp * ((double)pk.Np + pk.K), 2.0 * R * (2.0 * pk.Np + (xkind == 2 ? 4.0 : 2.0) * pk.K),
-       fv::launch_lora_direct(pk, dY16, X, xkind, ldx, lo_off, R, lora_params, lora_grads, ls.scale, ls.dscratch, ls.dscratch_floats, s));
+  FV_P(FV_FAM_GEMM, 4.0 * R * pk.NCp * ((double)pk.Np + pk.K), 2.0 * R * (2.0 * pk.Np + (X.kind == ActOp::SPLIT ? 4.0 : 2.0) * pk.K),
+       fv::launch_lora_direct(pk, dY16, X.p, X.kind, X.ld, X.kind == ActOp::SPLIT ? pk.K : 0, R, c.lora_params, c.lora_grads, ls.scale, ls.dscratch, ls.dscratch_floats, s));
   return FV_OK;
 }
 
@@ -236,6 +209,17 @@ int lora_check(fv_handle* h) {
 }
 
 bool lora_dora(const fv_handle* h) { return (h->train.lora.flags & FV_LORA_DORA) != 0; }
+
+// the caller's device buffers of one entry point: none null (`what`: the word its message has always used), all 16-byte aligned
+int check_buffers(const char* who, const char* what, std::initializer_list<const void*> bufs) {
+  uintptr_t bits = 0;
+  for (const void* b : bufs) {
+    if (!b) return fv_fail(FV_ERR_ARG, "%s: null %s", who, what);
+    bits |= (uintptr_t)b;
+  }
+  if (bits & 15) return fv_fail(FV_ERR_ARG, "%s: buffers must be 16-byte aligned", who);
+  return FV_OK;
+}
 
 // DoRA: the row norms of W0 + s . B . A for these parameters into the handle's buffer (mag non-null: the magnitudes of that trainable buffer too)
 int lora_refresh_norms(fv_handle* h, const float* master, const float* lora_params, float* mag, hipStream_t s) {
@@ -278,27 +262,16 @@ int fv_train_lora_layout(fv_handle* h, fv_train_tensor* out, int max_tensors, in
   HandleScope _hs(h);
   if (!h) return fv_fail(FV_ERR_ARG, "null handle");
   if (!h->train.lora.on) return fv_fail(FV_ERR_STATE, "LoRA training not initialised: call fv_train_lora_begin first");
-  int64_t total = 0;
-  const std::vector<TrainTensor> tt = lora_tensors(h, h->train.lora.rank, h->train.lora.mask, &total, nullptr, lora_dora(h));
-  if (n_tensors) *n_tensors = (int)tt.size();
-  if (total_numel) *total_numel = total;
-  if (out) {
-    if (max_tensors < (int)tt.size()) return fv_fail(FV_ERR_ARG, "fv_train_lora_layout: room for %d tensors, %zu needed", max_tensors, tt.size());
-    for (size_t i = 0; i < tt.size(); ++i) {
-      memset(&out[i], 0, sizeof(out[i]));
-      snprintf(out[i].name, sizeof(out[i].name), "%s", tt[i].name.c_str());
-      out[i].offset = tt[i].off; out[i].numel = tt[i].numel; out[i].rows = tt[i].rows; out[i].cols = tt[i].cols;
-      out[i].bucket = tt[i].bucket; out[i].packing = 0;
-    }
-  }
-  return FV_OK;
+  const LoraLayout lay = lora_tensors(h, h->train.lora.rank, h->train.lora.mask, lora_dora(h));
+  if (n_tensors) *n_tensors = (int)lay.tensors.size();
+  if (total_numel) *total_numel = lay.total;
+  return write_layout("fv_train_lora_layout", lay.tensors, out, max_tensors);
 }
 
 int fv_train_lora_project(fv_handle* h, const float* flat_grads_full, const float* lora_params, float* lora_grads, fv_stream st) {
   HandleScope _hs(h);
   FV_TRY(lora_check(h));
-  if (!flat_grads_full || !lora_params || !lora_grads) return fv_fail(FV_ERR_ARG, "fv_train_lora_project: null buffer");
-  if (((uintptr_t)flat_grads_full | (uintptr_t)lora_params | (uintptr_t)lora_grads) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_project: buffers must be 16-byte aligned");
+  FV_TRY(check_buffers("fv_train_lora_project", "buffer", {flat_grads_full, lora_params, lora_grads}));
   hipStream_t s = static_cast<hipStream_t>(st);
   const LoraState& ls = h->train.lora;
   // head and projector train in full: their gradients move over as they are (same offsets in both buffers)
@@ -316,8 +289,7 @@ int fv_train_lora_forward_backward(fv_handle* h, const float* flat_params, const
                                    size_t ws_bytes, float* actions, float* loss, float* lora_grads, fv_stream st) {
   HandleScope _hs(h);
   FV_TRY(lora_check(h));
-  if (!lora_params || !lora_grads) return fv_fail(FV_ERR_ARG, "fv_train_lora_forward_backward: null pointer");
-  if (((uintptr_t)lora_params | (uintptr_t)lora_grads) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_forward_backward: buffers must be 16-byte aligned");
+  FV_TRY(check_buffers("fv_train_lora_forward_backward", "pointer", {lora_params, lora_grads}));
   // refused HERE, before anything is enqueued
   if (lora_dora(h))
     return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_lora_forward_backward: not with DoRA (the magnitude's gradient needs the pre-bias GEMM outputs, which o / down do not keep): "
@@ -336,8 +308,7 @@ int fv_train_lora_forward_backward(fv_handle* h, const float* flat_params, const
 int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream st) {
   HandleScope _hs(h);
   FV_TRY(lora_check(h));
-  if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_commit: null buffer");
-  if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_commit: buffers must be 16-byte aligned");
+  FV_TRY(check_buffers("fv_train_lora_commit", "buffer", {flat_params_master, lora_params}));
   hipStream_t s = static_cast<hipStream_t>(st);
   LoraState& ls = h->train.lora;
   // the master's head | projector front mirrors the trainable buffer's (fv_train_forward_backward reads the head there); nothing else of it is written
@@ -356,8 +327,7 @@ int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* l
 int fv_train_lora_merge(fv_handle* h, float* flat_params_master, const float* lora_params, fv_stream st) {
   HandleScope _hs(h);
   FV_TRY(lora_check(h));
-  if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_merge: null buffer");
-  if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_merge: buffers must be 16-byte aligned");
+  FV_TRY(check_buffers("fv_train_lora_merge", "buffer", {flat_params_master, lora_params}));
   hipStream_t s = static_cast<hipStream_t>(st);
   LoraState& ls = h->train.lora;
   FV_HIP_CHECK(hipMemcpyAsync(flat_params_master, lora_params, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
@@ -374,8 +344,7 @@ int fv_train_lora_init_magnitude(fv_handle* h, const float* flat_params_master, 
   HandleScope _hs(h);
   FV_TRY(lora_check(h));
   if (!lora_dora(h)) return fv_fail(FV_ERR_STATE, "fv_train_lora_init_magnitude: LoRA mode was begun without FV_LORA_DORA");
-  if (!flat_params_master || !lora_params) return fv_fail(FV_ERR_ARG, "fv_train_lora_init_magnitude: null buffer");
-  if (((uintptr_t)flat_params_master | (uintptr_t)lora_params) & 15) return fv_fail(FV_ERR_ARG, "fv_train_lora_init_magnitude: buffers must be 16-byte aligned");
+  FV_TRY(check_buffers("fv_train_lora_init_magnitude", "buffer", {flat_params_master, lora_params}));
   h->train.lora.master = nullptr;     // (the norm buffer now describes these buffers, but no commit of them has run)
   return lora_refresh_norms(h, flat_params_master, lora_params, lora_params, static_cast<hipStream_t>(st));
 }

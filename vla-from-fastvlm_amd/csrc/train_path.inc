@@ -22,13 +22,23 @@
 // exact fp16 copies of the bf16 weights; the activations' columns), one pass each -- half the MFMA work of the split form this path
 // started with and more exact than it (8.4e-4 against 1.8e-3 worst per-tensor gradient); the other options keep the split-bf16 /
 // plain-bf16 forms for comparison.  Everything else fp32 (train_kernels.hip); no atomics on any gradient.
+//
+// Structure.  train_tensors is the one list of what trains (offset, bucket and, for the decoder's own tensors, layer and role: nothing downstream reads a name).
+// The step (train_forward_backward_impl) builds ONE DecCtx -- plan, workspace, stream, the backward's mode decided once, every gradient pointer and bucket range
+// from one pass over that list -- and runs fwd_gemm (a forward projection in the form f16fwd selects), mlp_backward and proj_backward (the only places that
+// switch on the mode) over it.  dgrad / wgrad take the gradient as a GradOp and the activation as an ActOp: values that NAME the form the operand exists in.
 
 namespace {
+
+// what a tensor of the decoder / projector is (TrainTensor::role): the seven of a layer, then the named ones outside the layers
+enum { DR_LN1, DR_QKV_W, DR_QKV_B, DR_O_W, DR_LN2, DR_GU_W, DR_DOWN_W, DR_LAYER_ROLES,
+       DR_PJ0_W = DR_LAYER_ROLES, DR_PJ0_B, DR_PJ2_W, DR_PJ2_B, DR_EMBED, DR_NORM, DR_ROLES };
 
 struct TrainTensor {
   std::string name;
   int64_t off = 0, numel = 0;
   int rows = 1, cols = 0, bucket = 0, packing = 0;
+  int layer = -1, role = -1;   // decoder layer and DR_* role; -1: outside the layers / none (head, tower, adapters)
   void* lib = nullptr;      // the library's own copy (bf16 matrix or fp32 vector); null for the head (caller-owned only)
   bool is_mat = false;
   bf16_t** tcopy = nullptr; // where the transposed bf16 copy lives (dgrad operand), matrices of the decoder / projector.2 only
@@ -45,16 +55,15 @@ int tower_export(fv_handle* h, float* flat, hipStream_t s);
 int tower_bucket_count(const fv_handle* h);
 // lora_path.inc (the LoRA mode): its commit tables name the same operand copies as fv_train_commit's and are rebuilt with it
 int build_lora_tables(fv_handle* h);
-int lora_direct_call(fv_handle* h, int l, int which, const bf16_t* dY16, const bf16_t* X, int xkind, int ldx, int lo_off, int R, const float* lora_params,
-                     float* lora_grads, hipStream_t s);
 
 std::vector<TrainTensor> train_tensors(fv_handle* h, int64_t* total) {
   const fv_model_desc& d = h->d;
   std::vector<TrainTensor> out;
   int64_t off = 0;
-  auto add = [&](const std::string& n, int rows, int cols, int bucket, void* lib, bool mat, int packing = 0, bf16_t** tc = nullptr, bf16_t** tc16 = nullptr) {
+  int layer = -1;
+  auto add = [&](int role, const std::string& n, int rows, int cols, int bucket, void* lib, bool mat, int packing = 0, bf16_t** tc = nullptr, bf16_t** tc16 = nullptr) {
     TrainTensor t;
-    t.name = n; t.off = off; t.rows = rows; t.cols = cols; t.numel = (int64_t)rows * cols; t.bucket = bucket; t.lib = lib; t.is_mat = mat;
+    t.name = n; t.layer = layer; t.role = role; t.off = off; t.rows = rows; t.cols = cols; t.numel = (int64_t)rows * cols; t.bucket = bucket; t.lib = lib; t.is_mat = mat;
     t.packing = packing; t.tcopy = tc; t.tcopy16 = tc16;
     off += (t.numel + 3) / 4 * 4;
     out.push_back(t);
@@ -75,29 +84,31 @@ std::vector<TrainTensor> train_tensors(fv_handle* h, int64_t* total) {
   const int H = d.llm_hidden, CO = d.tower_out_dim, I = d.llm_inter, D = d.llm_head_dim;
   const int qd = d.llm_heads * D, kd = d.llm_kv_heads * D, qkvw = qd + 2 * kd;
   Tower& tw = h->tw;
-  add("model.mm_projector.0.weight", H, CO, TB_PROJ, tw.pj0_w, true, 0, h->train.tower ? &h->train.pj0T : nullptr, h->train.tower ? &h->train.pj0T16 : nullptr);
-  add("model.mm_projector.0.bias", 1, H, TB_PROJ, tw.pj0_b, false);
-  add("model.mm_projector.2.weight", H, H, TB_PROJ, tw.pj2_w, true, 0, &h->train.pj2T, &h->train.pj2T16);
-  add("model.mm_projector.2.bias", 1, H, TB_PROJ, tw.pj2_b, false);
-  add("model.embed_tokens.weight", d.llm_vocab, H, TB_EMBED, h->dec.embed, true);
+  add(DR_PJ0_W, "model.mm_projector.0.weight", H, CO, TB_PROJ, tw.pj0_w, true, 0, h->train.tower ? &h->train.pj0T : nullptr, h->train.tower ? &h->train.pj0T16 : nullptr);
+  add(DR_PJ0_B, "model.mm_projector.0.bias", 1, H, TB_PROJ, tw.pj0_b, false);
+  add(DR_PJ2_W, "model.mm_projector.2.weight", H, H, TB_PROJ, tw.pj2_w, true, 0, &h->train.pj2T, &h->train.pj2T16);
+  add(DR_PJ2_B, "model.mm_projector.2.bias", 1, H, TB_PROJ, tw.pj2_b, false);
+  add(DR_EMBED, "model.embed_tokens.weight", d.llm_vocab, H, TB_EMBED, h->dec.embed, true);
   for (size_t l = 0; l < h->dec.layers.size(); ++l) {
     DecLayer& L = h->dec.layers[l];
     const std::string pre = "model.layers." + std::to_string(l) + ".";
     const int b = TB_LAYER0 + (int)l;
+    layer = (int)l;
     TrainLayerT* T = h->train.layers.size() > l ? &h->train.layers[l] : nullptr;
-    add(pre + "input_layernorm.weight", 1, H, b, L.ln1, false);
-    add(pre + "self_attn.qkv_proj.weight", qkvw, H, b, L.qkv_w, true, 1, T ? &T->qkvT : nullptr, T ? &T->qkvT16 : nullptr);   // rows: q | k | v
+    add(DR_LN1, pre + "input_layernorm.weight", 1, H, b, L.ln1, false);
+    add(DR_QKV_W, pre + "self_attn.qkv_proj.weight", qkvw, H, b, L.qkv_w, true, 1, T ? &T->qkvT : nullptr, T ? &T->qkvT16 : nullptr);   // rows: q | k | v
     if (T) out.back().row16 = &T->qkv16;
-    add(pre + "self_attn.qkv_proj.bias", 1, qkvw, b, L.qkv_b, false, 1);
-    add(pre + "self_attn.o_proj.weight", H, qd, b, L.o_w, true, 0, T ? &T->oT : nullptr, T ? &T->oT16 : nullptr);
+    add(DR_QKV_B, pre + "self_attn.qkv_proj.bias", 1, qkvw, b, L.qkv_b, false, 1);
+    add(DR_O_W, pre + "self_attn.o_proj.weight", H, qd, b, L.o_w, true, 0, T ? &T->oT : nullptr, T ? &T->oT16 : nullptr);
     if (T) out.back().row16 = &T->o16;
-    add(pre + "post_attention_layernorm.weight", 1, H, b, L.ln2, false);
-    add(pre + "mlp.gate_up_proj.weight", 2 * I, H, b, L.gu_w, true, 2, T ? &T->guT : nullptr, T ? &T->guT16 : nullptr);      // rows: [8 gate | 8 up] blocks
+    add(DR_LN2, pre + "post_attention_layernorm.weight", 1, H, b, L.ln2, false);
+    add(DR_GU_W, pre + "mlp.gate_up_proj.weight", 2 * I, H, b, L.gu_w, true, 2, T ? &T->guT : nullptr, T ? &T->guT16 : nullptr);      // rows: [8 gate | 8 up] blocks
     if (T) out.back().row16 = &T->gu16;
-    add(pre + "mlp.down_proj.weight", H, I, b, L.down_w, true, 0, T ? &T->downT : nullptr, T ? &T->downT16 : nullptr);
+    add(DR_DOWN_W, pre + "mlp.down_proj.weight", H, I, b, L.down_w, true, 0, T ? &T->downT : nullptr, T ? &T->downT16 : nullptr);
     if (T) { out.back().row16 = &T->down16; out.back().scale16 = 16.0f; }
   }
-  add("model.norm.weight", 1, H, TB_LAYER0 + (int)h->dec.layers.size(), h->dec.norm, false);
+  layer = -1;
+  add(DR_NORM, "model.norm.weight", 1, H, TB_LAYER0 + (int)h->dec.layers.size(), h->dec.norm, false);
   if (h->train.tower) append_tower_tensors(h, out, off);
   if (total) *total = off;
   return out;
@@ -154,89 +165,163 @@ TrainPlan plan_train(const fv_handle* h, int B, int T) {
   return p;
 }
 
-#define TR_GEMM(...)                       \
-  do {                                     \
-    fv::GemmArgs _g{__VA_ARGS__};          \
-    FV_TRY(gemm_p(h, _g, s));              \
-  } while (0)
+// one-pass fp16 arithmetic on both sides of the backward (the default options)
+bool fp16_backward(const fv_handle* h) { return h->train.grad_split == 2 && h->train.wgrad_f16; }
 
-// dW[N][K] (fp32, into the flat gradient) = dY^T . X over `R` rows: dY fp32 [R][ldy] (N columns), X bf16 [R][ldx] (K columns, the hi
-// half of a split operand) or bf16-exact; both transposed into the scratch operands first
-// (dYs != null: the gradient already as split bf16 [R][2N] = [hi | lo] -- its two halves are transposed on their own)
-// (at_ready: the fp16 transposed gradient already sits in the AT scratch -- launch_swiglu_bwd_f16 wrote it)
-// at_ptr: where that transposed gradient sits (default: the start of the AT scratch); xt_ready: the transposed fp16 activation is in the XT scratch already
-int wgrad(fv_handle* h, const TrainPlan& tp, char* ws, const float* dY, int ldy, int N, const bf16_t* X, int ldx, int K, int R, float* dW, hipStream_t s,
-          const bf16_t* dYs = nullptr, bool at_ready = false, bf16_t* at_ptr = nullptr, bool xt_ready = false, int xkind = -1) {   // xkind 3: X holds fp16 rows
+// how the backward's contractions get their operands.  SPLIT: every dgrad / wgrad makes its own from the fp32 gradient, in the form fv_train_set_options names (the
+// split-bf16 forms and every mixed setting); FP16 (the default options): a gradient's fp16 rows and columns from ONE read, shared by its dgrad and its wgrad;
+// DIRECT: the direct LoRA backward on top of FP16's options -- fp16 rows only, lora_direct_call in place of every weight-gradient GEMM of the decoder
+enum BwdMode { BWD_SPLIT, BWD_FP16, BWD_DIRECT };
+
+struct DecCtx {   // everything one forward / backward step of the decoder needs (after tower_train.inc's TowerCtx); built once per call, never kept
+  fv_handle* h; TrainPlan tp; char* ws; hipStream_t s;
+  BwdMode mode; bool f16fwd;
+  const float* lora_params; float* lora_grads;   // DIRECT: the trainable buffer and its gradient
+  fv_bucket_cb cb; void* user;
+  std::vector<float*> lgrad;     // [layer][DR_LAYER_ROLES]: where each gradient goes; DIRECT: null behind the projector (no gradient is formed there)
+  float* ngrad[DR_ROLES];        // ... and the named tensors outside the layers
+  struct Span { int64_t lo = INT64_MAX, hi = 0; };
+  std::vector<Span> span;        // [bucket]: its floats [lo, hi) in the gradient buffer
+  template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+  // layer l's kept tensors: the residual stream into the layer and between its halves, the normed rows, qkv / lse / attention output, gate/up accumulators, act
+  float* X_in(int l) const { return at<float>(tp.x_in + tp.s_x * l); }      float* X_mid(int l) const { return at<float>(tp.x_mid + tp.s_x * l); }
+  bf16_t* XN1(int l) const { return at<bf16_t>(tp.xn1 + tp.s_xn * l); }     bf16_t* XN2(int l) const { return at<bf16_t>(tp.xn2 + tp.s_xn * l); }
+  float* QKV(int l) const { return at<float>(tp.qkvf + tp.s_qkvf * l); }    float* LSE(int l) const { return at<float>(tp.lse + tp.s_lse * l); }
+  bf16_t* ATT(int l) const { return at<bf16_t>(tp.att + tp.s_att * l); }    bf16_t* ACT(int l) const { return at<bf16_t>(tp.act + tp.s_act * l); }
+  float* GU(int l) const { return at<float>(tp.gu + tp.s_gu * l); }
+  // the backward's scratch: the residual-gradient stream, every dgrad's output, a gradient's 16-bit rows / its columns, an activation's columns
+  float* dx() const { return at<float>(tp.dx); }                            float* dtmp() const { return at<float>(tp.dtmp); }
+  bf16_t* dsplit() const { return at<bf16_t>(tp.dsplit); }                  bf16_t* AT() const { return at<bf16_t>(tp.AT); }
+  bf16_t* XT() const { return at<bf16_t>(tp.XT); }                          float* scr() const { return at<float>(tp.scr); }
+  float* colscr() const { return scr() + fv::rmsnorm_bwd_scratch_floats(tp.rows, h->d.llm_hidden); }
+  float* G(int l, int role) const { return lgrad[(size_t)l * DR_LAYER_ROLES + role]; }
+  float* G(int role) const { return ngrad[role]; }
+  void bucket_done(int b) const { if (cb) cb(user, b, span[b].lo, span[b].hi - span[b].lo); }
+};
+
+// gbuf: where the head's and the projector's gradients go (and, outside DIRECT, everything else): the full and the trainable layout share that front
+DecCtx dec_ctx(fv_handle* h, const TrainPlan& tp, void* ws, hipStream_t s, float* gbuf, const float* lora_params, float* lora_grads, fv_bucket_cb cb, void* user) {
+  DecCtx c{h, tp, static_cast<char*>(ws), s, lora_grads ? BWD_DIRECT : (fp16_backward(h) ? BWD_FP16 : BWD_SPLIT), h->train.fwd_f16, lora_params, lora_grads, cb, user};
+  c.lgrad.assign(h->dec.layers.size() * DR_LAYER_ROLES, nullptr);
+  for (const TrainTensor& t : train_tensors(h, nullptr)) {
+    float* g = (c.mode == BWD_DIRECT && t.bucket > TB_PROJ) ? nullptr : gbuf + t.off;
+    if (t.layer >= 0) c.lgrad[(size_t)t.layer * DR_LAYER_ROLES + t.role] = g;
+    else if (t.role >= 0) c.ngrad[t.role] = g;
+    if (c.span.size() <= (size_t)t.bucket) c.span.resize(t.bucket + 1);
+    DecCtx::Span& sp = c.span[t.bucket];
+    sp.lo = std::min(sp.lo, t.off); sp.hi = std::max(sp.hi, t.off + (t.numel + 3) / 4 * 4);
+  }
+  c.span[TB_HEAD] = {0, (fv::head_offsets(h->hd).o[12] + 3) / 4 * 4};   // the head's own layout (and its padding)
+  return c;
+}
+
+// ---- the operand forms: what a dgrad / wgrad is handed says which copy of its operand EXISTS; the helper makes the one its arithmetic reads ----------------
+struct GradOp {   // the gradient dY [R][N]
+  enum Form { ROWS_F32, ROWS_SPLIT, ROWS_F16, COLS_F16 } form;
+  const float* f32; const bf16_t* p16; int ld;
+  static GradOp rows_f32(const float* p, int ld) { return {ROWS_F32, p, nullptr, ld}; }
+  static GradOp rows_split(const bf16_t* p) { return {ROWS_SPLIT, nullptr, p, 0}; }   // split bf16 [R][2N] = [hi | lo]
+  static GradOp rows_f16(const bf16_t* p) { return {ROWS_F16, nullptr, p, 0}; }       // fp16 rows [R][N], already made (dgrad)
+  static GradOp cols_f16(const bf16_t* at) { return {COLS_F16, nullptr, at, 0}; }     // fp16 columns [N][Rp], already in the AT scratch at `at` (wgrad)
+};
+struct ActOp {    // the activation X [R][K] a weight gradient contracts with
+  enum Kind { BF16 = 1, SPLIT = 2, F16 = 3, IN_XT = 4 } kind;   // 1 .. 3: launch_transpose_to_f16's in_kind
+  const bf16_t* p; int ld;
+  static ActOp bf16(const bf16_t* p, int ld) { return {BF16, p, ld}; }
+  static ActOp split(const bf16_t* p, int ld) { return {SPLIT, p, ld}; }   // [hi | lo], the lo half K columns in (the bf16 forms contract with the hi half alone)
+  static ActOp f16(const bf16_t* p, int ld) { return {F16, p, ld}; }       // fp16 rows
+  static ActOp in_xt() { return {IN_XT, nullptr, 0}; }                     // its fp16 columns sit in the XT scratch already
+};
+int lora_direct_call(const DecCtx& c, int l, int which, const bf16_t* dY16, const ActOp& X, int R);   // lora_path.inc
+int bad_operand(const char* who) { return fv_fail(FV_ERR_STATE, "%s: operand form not available under these backward options (internal)", who); }
+
+int gemm_sk(const DecCtx& c, fv::GemmArgs g) {   // with the split-K scratch attached (few output tiles over a long contraction: launch_gemm cuts along K)
+  g.splitk_ws = c.tp.splitk_bytes ? c.at<float>(c.tp.splitk) : nullptr;
+  g.splitk_bytes = c.tp.splitk_bytes;
+  return gemm_p(c.h, g, c.s);
+}
+
+// dW[N][K] (fp32, into the flat gradient) = dY^T . X over `R` rows; both operands transposed into the AT / XT scratch first, unless they are there already
+int wgrad(const DecCtx& c, const GradOp& dY, int N, const ActOp& X, int K, int R, float* dW) {
+  fv_handle* h = c.h; hipStream_t s = c.s;
   const int Rp = (R + 63) / 64 * 64;
   const int sp = h->train.grad_split;   // 0: the gradient's bf16 hi half alone (one pass)
-  bf16_t* AT = at_ptr ? at_ptr : reinterpret_cast<bf16_t*>(ws + tp.AT);
-  bf16_t* XT = reinterpret_cast<bf16_t*>(ws + tp.XT);
+  bf16_t* AT = dY.form == GradOp::COLS_F16 ? const_cast<bf16_t*>(dY.p16) : c.AT();
+  bf16_t* XT = c.XT();
   if (h->train.wgrad_f16) {
     // ONE fp16 pass: the (loss-scaled) gradient and the activation both rounded ONCE to 11 significant bits -- 2e-4 per tensor where the
     // split-bf16 gradient against the bf16 (8-bit) activation gave 1.8e-3, at half the MFMA work.  X: the split operand's halves summed first.
-    if (at_ready) {}
-    else if (dYs) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_transpose_to_f16(dYs, 2, 2 * N, N, AT, Rp, R, Rp, N, h->f16_flags, s));
-    else FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_transpose_to_f16(dY, 0, ldy, 0, AT, Rp, R, Rp, N, h->f16_flags, s));
-    if (!xt_ready) FV_P(FV_FAM_ELT, 0.0, (double)R * K * 6, fv::launch_transpose_to_f16(X, xkind >= 0 ? xkind : (ldx >= 2 * K ? 2 : 1), ldx, K, XT, Rp, R, Rp, K, h->f16_flags, s));
+    if (dY.form == GradOp::ROWS_SPLIT) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_transpose_to_f16(dY.p16, 2, 2 * N, N, AT, Rp, R, Rp, N, h->f16_flags, s));
+    else if (dY.form == GradOp::ROWS_F32) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_transpose_to_f16(dY.f32, 0, dY.ld, 0, AT, Rp, R, Rp, N, h->f16_flags, s));
+    else if (dY.form != GradOp::COLS_F16) return bad_operand("wgrad");
+    if (X.kind != ActOp::IN_XT) FV_P(FV_FAM_ELT, 0.0, (double)R * K * 6, fv::launch_transpose_to_f16(X.p, X.kind, X.ld, K, XT, Rp, R, Rp, K, h->f16_flags, s));
     fv::GemmArgs g16{AT, Rp, XT, N, K, Rp, nullptr, nullptr, nullptr, 0, dW, K, FV_EPI_F32, 0};
     g16.f16 = 1;
-    g16.splitk_ws = tp.splitk_bytes ? reinterpret_cast<float*>(ws + tp.splitk) : nullptr;
-    g16.splitk_bytes = tp.splitk_bytes;
-    FV_TRY(gemm_p(h, g16, s));
-    return FV_OK;
+    return gemm_sk(c, g16);
   }
-  if (dYs) {
-    FV_P(FV_FAM_ELT, 0.0, (double)R * N * 4, fv::launch_transpose_to_bf16(dYs, 1, 2 * N, AT, 2 * Rp, 0, R, Rp, N, s));
-    if (sp) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 4, fv::launch_transpose_to_bf16(dYs + N, 1, 2 * N, AT + Rp, 2 * Rp, 0, R, Rp, N, s));
-  } else
-  FV_P(FV_FAM_ELT, 0.0, (double)R * N * 8, fv::launch_transpose_to_bf16(dY, 0, ldy, AT, 2 * Rp, sp ? Rp : 0, R, Rp, N, s));
-  FV_P(FV_FAM_ELT, 0.0, (double)R * K * 4, fv::launch_transpose_to_bf16(X, 1, ldx, XT, Rp, 0, R, Rp, K, s));
-  fv::GemmArgs g{AT, 2 * Rp, XT, N, K, Rp, nullptr, nullptr, nullptr, 0, dW, K, FV_EPI_F32, sp};
+  if (X.kind != ActOp::BF16 && X.kind != ActOp::SPLIT) return bad_operand("wgrad");
+  if (dY.form != GradOp::ROWS_SPLIT && dY.form != GradOp::ROWS_F32) return bad_operand("wgrad");
+  if (dY.form == GradOp::ROWS_SPLIT) {   // its two halves are transposed on their own
+    FV_P(FV_FAM_ELT, 0.0, (double)R * N * 4, fv::launch_transpose_to_bf16(dY.p16, 1, 2 * N, AT, 2 * Rp, 0, R, Rp, N, s));
+    if (sp) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 4, fv::launch_transpose_to_bf16(dY.p16 + N, 1, 2 * N, AT + Rp, 2 * Rp, 0, R, Rp, N, s));
+  } else FV_P(FV_FAM_ELT, 0.0, (double)R * N * 8, fv::launch_transpose_to_bf16(dY.f32, 0, dY.ld, AT, 2 * Rp, sp ? Rp : 0, R, Rp, N, s));
+  FV_P(FV_FAM_ELT, 0.0, (double)R * K * 4, fv::launch_transpose_to_bf16(X.p, 1, X.ld, XT, Rp, 0, R, Rp, K, s));
   // few output tiles over a contraction as long as the batch (o_proj: 4 x 4 tiles, K = 2 x 10240): cut along K, one unit per CU
-  g.splitk_ws = tp.splitk_bytes ? reinterpret_cast<float*>(ws + tp.splitk) : nullptr;
-  g.splitk_bytes = tp.splitk_bytes;
-  FV_TRY(gemm_p(h, g, s));
-  return FV_OK;
+  return gemm_sk(c, fv::GemmArgs{AT, 2 * Rp, XT, N, K, Rp, nullptr, nullptr, nullptr, 0, dW, K, FV_EPI_F32, sp});
 }
 
-// dX[R][K] (fp32) = dY[R][N] . W[N][K] through the transposed weight copy WT [K][N]
-// (dY16: the gradient's fp16 rows [R][N], already made)
-int dgrad(fv_handle* h, const TrainPlan& tp, char* ws, const float* dY, int ldy, int N, const bf16_t* WT, int K, int R, float* dX, hipStream_t s,
-          const bf16_t* dYs = nullptr, const bf16_t* WT16 = nullptr, const bf16_t* dY16 = nullptr) {
-  const bf16_t* ds = dYs;
+// dX[R][K] (fp32) = dY[R][N] . W[N][K] through the transposed weight copy: WT [K][N] bf16, WT16 its fp16 twin
+int dgrad(const DecCtx& c, const GradOp& dY, int N, const bf16_t* WT, const bf16_t* WT16, int K, int R, float* dX) {
+  fv_handle* h = c.h; hipStream_t s = c.s;
   const int sp = h->train.grad_split;
   if (sp == 2) {   // ONE fp16 pass: the (loss-scaled) gradient rounded once to 11 bits against the fp16 copy of the transposed weight (exact: bf16 widens into fp16)
-    bf16_t* d16 = reinterpret_cast<bf16_t*>(ws + tp.dsplit);
-    bf16_t* dst = dYs ? d16 + (size_t)R * 2 * N : d16;   // (a pre-split operand lives in the same scratch: the fp16 rows go behind it)
-    if (dY16) dst = const_cast<bf16_t*>(dY16);
-    else if (dYs) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_rows_to_f16(dYs, 2, 2 * N, N, dst, N, R, N, h->f16_flags, s));
-    else FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_rows_to_f16(dY, 0, ldy, 0, dst, N, R, N, h->f16_flags, s));
-    fv::GemmArgs g16{dst, N, WT16, R, K, N, nullptr, nullptr, nullptr, 0, dX, K, FV_EPI_F32, 0};
+    bf16_t* dst = c.dsplit() + (dY.form == GradOp::ROWS_SPLIT ? (size_t)R * 2 * N : 0);   // (a pre-split operand lives in the same scratch: the fp16 rows go behind it)
+    if (dY.form == GradOp::ROWS_SPLIT) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_rows_to_f16(dY.p16, 2, 2 * N, N, dst, N, R, N, h->f16_flags, s));
+    else if (dY.form == GradOp::ROWS_F32) FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_rows_to_f16(dY.f32, 0, dY.ld, 0, dst, N, R, N, h->f16_flags, s));
+    else if (dY.form != GradOp::ROWS_F16) return bad_operand("dgrad");
+    fv::GemmArgs g16{dY.form == GradOp::ROWS_F16 ? dY.p16 : dst, N, WT16, R, K, N, nullptr, nullptr, nullptr, 0, dX, K, FV_EPI_F32, 0};
     g16.f16 = 1;
-    g16.splitk_ws = tp.splitk_bytes ? reinterpret_cast<float*>(ws + tp.splitk) : nullptr;
-    g16.splitk_bytes = tp.splitk_bytes;
-    FV_TRY(gemm_p(h, g16, s));
-    return FV_OK;
+    return gemm_sk(c, g16);
   }
-  if (!ds) {
-    bf16_t* dsw = reinterpret_cast<bf16_t*>(ws + tp.dsplit);
-    FV_P(FV_FAM_ELT, 0.0, (double)R * N * 8, fv::launch_split_rows(dY, ldy, dsw, 2 * N, sp ? N : 0, R, N, s));
-    ds = dsw;
-  }
-  fv::GemmArgs g{ds, 2 * N, WT, R, K, N, nullptr, nullptr, nullptr, 0, dX, K, FV_EPI_F32, sp};
-  g.splitk_ws = tp.splitk_bytes ? reinterpret_cast<float*>(ws + tp.splitk) : nullptr;
-  g.splitk_bytes = tp.splitk_bytes;
-  FV_TRY(gemm_p(h, g, s));
+  const bf16_t* ds = dY.p16;
+  if (dY.form == GradOp::ROWS_F32) {
+    FV_P(FV_FAM_ELT, 0.0, (double)R * N * 8, fv::launch_split_rows(dY.f32, dY.ld, c.dsplit(), 2 * N, sp ? N : 0, R, N, s));
+    ds = c.dsplit();
+  } else if (dY.form != GradOp::ROWS_SPLIT) return bad_operand("dgrad");
+  return gemm_sk(c, fv::GemmArgs{ds, 2 * N, WT, R, K, N, nullptr, nullptr, nullptr, 0, dX, K, FV_EPI_F32, sp});
+}
+
+// FP16: an fp32 gradient's dgrad operand (fp16 rows, in the dsplit scratch) and wgrad operand (fp16 columns, at `at`) from ONE read of it
+int grad_operands(const DecCtx& c, const float* dY, int N, int R, bf16_t* at) {
+  fv_handle* h = c.h; hipStream_t s = c.s;
+  const int Rp = (R + 63) / 64 * 64;
+  FV_P(FV_FAM_ELT, 0.0, (double)R * N * 8, fv::launch_transpose_to_f16(dY, 0, N, 0, at, Rp, R, Rp, N, h->f16_flags, s, c.dsplit(), N));
   return FV_OK;
 }
 
-// one-pass fp16 arithmetic on both sides (the defaults): an fp32 gradient's dgrad operand (fp16 rows, in the dsplit scratch) and wgrad operand (fp16
-// columns, at `at`) from ONE read of it
-bool fp16_backward(const fv_handle* h) { return h->train.grad_split == 2 && h->train.wgrad_f16; }
-int grad_operands(fv_handle* h, const TrainPlan& tp, char* ws, const float* dY, int ldy, int N, int R, bf16_t* at, hipStream_t s) {
-  const int Rp = (R + 63) / 64 * 64;
-  FV_P(FV_FAM_ELT, 0.0, (double)R * N * 8,
-       fv::launch_transpose_to_f16(dY, 0, ldy, 0, at, Rp, R, Rp, N, h->f16_flags, s, reinterpret_cast<bf16_t*>(ws + tp.dsplit), N));
+// host table -> device (the handle owns the allocation)
+template <typename T> int upload(fv_handle* h, const std::vector<T>& v, T** dev) {
+  void* p = nullptr;
+  FV_TRY(dev_alloc(h, v.size() * sizeof(T), &p));
+  FV_HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  *dev = static_cast<T*>(p);
+  return FV_OK;
+}
+
+// what one commit launch writes for tensor t (every operand copy the library keeps of it) and how many tiles that takes; tile0 is the table builder's to number
+int commit_desc_of(fv_handle* h, const TrainTensor& t, fv::CommitDesc& c, int& ntiles) {
+  c = fv::CommitDesc{};
+  c.src_off = t.off; c.dst = t.lib; c.is_mat = t.is_mat ? 1 : 0;
+  if (t.is_mat) {
+    if (t.cols % 8 || t.rows % 8) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_begin: %s is %d x %d (dimensions must be multiples of 8)", t.name.c_str(), t.rows, t.cols);
+    c.rows = t.rows; c.cols = t.cols;
+    c.dstT16 = t.tcopy16 ? *t.tcopy16 : nullptr; c.dstTb = t.tcopy ? *t.tcopy : nullptr;
+    c.dst16 = (h->train.fwd_f16 && t.row16) ? *t.row16 : nullptr; c.scale16 = t.scale16;
+    ntiles = ((t.rows + 63) / 64) * ((t.cols + 63) / 64);
+  } else {
+    c.rows = 1; c.cols = (int)t.numel;
+    ntiles = (int)((t.numel + 4095) / 4096);
+  }
   return FV_OK;
 }
 
@@ -246,25 +331,113 @@ int build_commit_table(fv_handle* h) {
   int tiles = 0;
   for (const TrainTensor& t : train_tensors(h, nullptr)) {
     if (!t.lib) continue;
-    fv::CommitDesc c{};
-    c.src_off = t.off; c.dst = t.lib; c.is_mat = t.is_mat ? 1 : 0; c.tile0 = tiles;
-    if (t.is_mat) {
-      if (t.cols % 8 || t.rows % 8) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_begin: %s is %d x %d (dimensions must be multiples of 8)", t.name.c_str(), t.rows, t.cols);
-      c.rows = t.rows; c.cols = t.cols;
-      c.dstT16 = t.tcopy16 ? *t.tcopy16 : nullptr; c.dstTb = t.tcopy ? *t.tcopy : nullptr;
-      c.dst16 = (h->train.fwd_f16 && t.row16) ? *t.row16 : nullptr; c.scale16 = t.scale16;
-      tiles += ((t.rows + 63) / 64) * ((t.cols + 63) / 64);
-    } else {
-      c.rows = 1; c.cols = (int)t.numel;
-      tiles += (int)((t.numel + 4095) / 4096);
-    }
+    fv::CommitDesc c;
+    int n = 0;
+    FV_TRY(commit_desc_of(h, t, c, n));
+    c.tile0 = tiles; tiles += n;
     cd.push_back(c);
   }
-  void* dp = nullptr;
-  FV_TRY(dev_alloc(h, cd.size() * sizeof(fv::CommitDesc), &dp));
-  FV_HIP_CHECK(hipMemcpy(dp, cd.data(), cd.size() * sizeof(fv::CommitDesc), hipMemcpyHostToDevice));
-  h->train.commit_desc = static_cast<fv::CommitDesc*>(dp); h->train.commit_n = (int)cd.size(); h->train.commit_tiles = tiles;
+  FV_TRY(upload(h, cd, &h->train.commit_desc));
+  h->train.commit_n = (int)cd.size(); h->train.commit_tiles = tiles;
   if (h->train.lora.on) FV_TRY(build_lora_tables(h));
+  return FV_OK;
+}
+
+// fv_train_layout / fv_train_lora_layout: the tensor list as the ABI's records
+int write_layout(const char* who, const std::vector<TrainTensor>& tt, fv_train_tensor* out, int max_tensors) {
+  if (!out) return FV_OK;
+  if (max_tensors < (int)tt.size()) return fv_fail(FV_ERR_ARG, "%s: room for %d tensors, %zu needed", who, max_tensors, tt.size());
+  for (size_t i = 0; i < tt.size(); ++i) {
+    memset(&out[i], 0, sizeof(out[i]));
+    snprintf(out[i].name, sizeof(out[i].name), "%s", tt[i].name.c_str());
+    out[i].offset = tt[i].off; out[i].numel = tt[i].numel; out[i].rows = tt[i].rows; out[i].cols = tt[i].cols;
+    out[i].bucket = tt[i].bucket; out[i].packing = tt[i].packing;
+  }
+  return FV_OK;
+}
+
+// ---- the step's per-projection pieces --------------------------------------------------------------------------------------------------------
+// The training forward's projections come in two forms.  Default: split-bf16 rows [hi | lo] against the bf16 weight (two passes).  f16fwd (fv_train_set_forward_f16):
+// ONE fp16 pass -- the normed rows leave the RMSNorm as fp16, the attention output is rounded once from its split form, the SwiGLU output leaves the gate/up epilogue
+// as fp16 (x 2^-4, the down copy carries the 2^4); weights = exact fp16 copies of the bf16 weights.  The accumulators the backward differentiates (qkv fp32, gate/up
+// stash, lse) and the fp32 residual stream are kept exactly the same in both.
+int fwd_norm(const DecCtx& c, const float* x, const float* w, bf16_t* y) {
+  fv_handle* h = c.h; hipStream_t s = c.s;
+  const int H = h->d.llm_hidden, rows = c.tp.rows, f = c.f16fwd ? 1 : 0;
+  FV_P(FV_FAM_NORM, 4.0 * rows * H, (f ? 6.0 : 8.0) * rows * H,
+       fv::launch_rmsnorm(x, w, y, f ? nullptr : y + H, f ? H : 2 * H, rows, H, h->d.rms_eps, s, f, f ? h->f16_flags : nullptr));
+  return FV_OK;
+}
+// y [rows][N] = x . W^T over K columns (+ res, an fp32 residual [rows][H]): operand, leading dimension and weight copy as f16fwd says
+fv::GemmArgs fwd_gemm(const DecCtx& c, const bf16_t* X, const bf16_t* W, const bf16_t* W16, int N, int K, const float* bias, const float* res, void* out, int ldo, int epi) {
+  fv::GemmArgs g{X, c.f16fwd ? K : 2 * K, c.f16fwd ? W16 : W, c.tp.rows, N, K, bias, nullptr, res, res ? c.h->d.llm_hidden : 0, out, ldo, epi, c.f16fwd ? 0 : 1};
+  g.f16 = c.f16fwd ? 1 : 0;
+  return g;
+}
+
+// backward of one projection y = x . W^T of layer l (`which`: 0 q|k|v, 1 o -- lora_direct_call's numbering): gradient operands, dX = dY . W, then dW = dY^T . X or,
+// DIRECT, dA / dB of the adapters inside W.  THE place the mode is switched on for these two (the MLP pair has its own, below)
+int proj_backward(const DecCtx& c, int l, int which, const float* dY, int N, const ActOp& X, int K, const bf16_t* WT, const bf16_t* WT16, float* dX, float* dW) {
+  fv_handle* h = c.h; hipStream_t s = c.s;
+  const int R = c.tp.rows;
+  switch (c.mode) {
+    case BWD_DIRECT:   // gradient ROWS only (no column copies: nothing here runs a weight-gradient GEMM)
+      FV_P(FV_FAM_ELT, 0.0, (double)R * N * 6, fv::launch_rows_to_f16(dY, 0, N, 0, c.dsplit(), N, R, N, h->f16_flags, s));
+      FV_TRY(dgrad(c, GradOp::rows_f16(c.dsplit()), N, WT, WT16, K, R, dX));
+      return lora_direct_call(c, l, which, c.dsplit(), X, R);
+    case BWD_FP16:
+      FV_TRY(grad_operands(c, dY, N, R, c.AT()));
+      FV_TRY(dgrad(c, GradOp::rows_f16(c.dsplit()), N, WT, WT16, K, R, dX));
+      return wgrad(c, GradOp::cols_f16(c.AT()), N, X, K, R, dW);
+    case BWD_SPLIT:
+      FV_TRY(dgrad(c, GradOp::rows_f32(dY, N), N, WT, WT16, K, R, dX));
+      return wgrad(c, GradOp::rows_f32(dY, N), N, X, K, R, dW);
+  }
+  return FV_OK;
+}
+
+// backward of layer l's MLP, x_out = x_mid + act . Wd^T with act = silu(gate) * up, gate/up = xn2 . Wgu^T: dx -> d xn2 in dtmp, dWd, dWgu.  The two projections are
+// entangled through the SwiGLU backward, which writes d gate/up (and, FP16 / DIRECT, act) straight into the operand forms its consumers read: once per mode
+int mlp_backward(const DecCtx& c, int l) {
+  fv_handle* h = c.h; hipStream_t s = c.s;
+  const TrainLayerT& Tw = h->train.layers[l];
+  const int H = h->d.llm_hidden, I = h->d.llm_inter, I2 = 2 * I, rows = c.tp.rows;
+  float *dx = c.dx(), *dtmp = c.dtmp();
+  bf16_t* dsplit = c.dsplit();
+  const ActOp xn2 = c.f16fwd ? ActOp::f16(c.XN2(l), H) : ActOp::split(c.XN2(l), 2 * H);
+  switch (c.mode) {
+    case BWD_DIRECT: {
+      // gradient ROWS only (no column copies: nothing here runs a weight-gradient GEMM).  dx's fp16 rows go into the last third of the dsplit scratch, so that they
+      // outlive the SwiGLU backward, which writes d gate/up's rows at its start and silu(gate) * up as fp16 rows (the down adapters' activation) into the XT scratch
+      bf16_t* dx16 = dsplit + (size_t)rows * 2 * c.tp.wmax;
+      bf16_t* act16 = c.XT();
+      FV_P(FV_FAM_ELT, 0.0, (double)rows * H * 6, fv::launch_rows_to_f16(dx, 0, H, 0, dx16, H, rows, H, h->f16_flags, s));
+      FV_TRY(dgrad(c, GradOp::rows_f16(dx16), H, Tw.downT, Tw.downT16, I, rows, dtmp));  // d act [rows][I]
+      FV_P(FV_FAM_ELT, 18.0 * rows * I, 16.0 * rows * I, fv::launch_swiglu_bwd_rows(c.GU(l), 1, dtmp, rows, rows, I, dsplit, act16, h->f16_flags, s));
+      FV_TRY(lora_direct_call(c, l, 3, dx16, ActOp::f16(act16, I), rows));
+      FV_TRY(dgrad(c, GradOp::rows_f16(dsplit), I2, Tw.guT, Tw.guT16, H, rows, dtmp)); // d xn2 [rows][H]
+      return lora_direct_call(c, l, 2, dsplit, xn2, rows);
+    }
+    case BWD_FP16: {
+      // dx -> fp16 rows + columns in one pass; d act; then the SwiGLU backward writes d gate/up straight into the two fp16 operands its consumers
+      // read (rows for the dgrad, columns for the wgrad) AND act^T for the down projection's wgrad, which therefore runs after it
+      bf16_t* at0 = c.AT();
+      bf16_t* at1 = at0 + (size_t)I2 * c.tp.Rp;   // behind the widest gradient's columns
+      FV_TRY(grad_operands(c, dx, H, rows, at1));
+      FV_TRY(dgrad(c, GradOp::rows_f16(dsplit), H, Tw.downT, Tw.downT16, I, rows, dtmp));  // d act [rows][I]
+      FV_P(FV_FAM_ELT, 18.0 * rows * I, 22.0 * rows * I, fv::launch_swiglu_bwd_f16(c.GU(l), 1, dtmp, rows, c.tp.Rp, I, dsplit, at0, h->f16_flags, s, c.XT()));
+      FV_TRY(wgrad(c, GradOp::cols_f16(at1), H, ActOp::in_xt(), I, rows, c.G(l, DR_DOWN_W)));
+      FV_TRY(dgrad(c, GradOp::rows_f16(dsplit), I2, Tw.guT, Tw.guT16, H, rows, dtmp)); // d xn2 [rows][H]
+      return wgrad(c, GradOp::cols_f16(at0), I2, xn2, H, rows, c.G(l, DR_GU_W));
+    }
+    case BWD_SPLIT:
+      FV_TRY(dgrad(c, GradOp::rows_f32(dx, H), H, Tw.downT, Tw.downT16, I, rows, dtmp));  // d act [rows][I]
+      FV_TRY(wgrad(c, GradOp::rows_f32(dx, H), H, ActOp::split(c.ACT(l), I2), I, rows, c.G(l, DR_DOWN_W)));   // the kept activation's hi half is the operand
+      // d gate/up straight into the split-bf16 form both of its consumers read (no fp32 copy, no separate split pass)
+      FV_P(FV_FAM_ELT, 16.0 * rows * I, 20.0 * rows * I, fv::launch_swiglu_bwd(c.GU(l), dtmp, rows, I, s, dsplit));
+      FV_TRY(dgrad(c, GradOp::rows_split(dsplit), I2, Tw.guT, Tw.guT16, H, rows, dtmp)); // d xn2 [rows][H]
+      return wgrad(c, GradOp::rows_split(dsplit), I2, xn2, H, rows, c.G(l, DR_GU_W));
+  }
   return FV_OK;
 }
 
@@ -286,16 +459,7 @@ int fv_train_layout(fv_handle* h, fv_train_tensor* out, int max_tensors, int* n_
   if (n_tensors) *n_tensors = (int)tt.size();
   if (total_numel) *total_numel = total;
   if (n_buckets) *n_buckets = TB_LAYER0 + h->d.llm_layers + 1 + (h->train.tower ? tower_bucket_count(h) : 0);
-  if (out) {
-    if (max_tensors < (int)tt.size()) return fv_fail(FV_ERR_ARG, "fv_train_layout: room for %d tensors, %zu needed", max_tensors, tt.size());
-    for (size_t i = 0; i < tt.size(); ++i) {
-      memset(&out[i], 0, sizeof(out[i]));
-      snprintf(out[i].name, sizeof(out[i].name), "%s", tt[i].name.c_str());
-      out[i].offset = tt[i].off; out[i].numel = tt[i].numel; out[i].rows = tt[i].rows; out[i].cols = tt[i].cols;
-      out[i].bucket = tt[i].bucket; out[i].packing = tt[i].packing;
-    }
-  }
-  return FV_OK;
+  return write_layout("fv_train_layout", tt, out, max_tensors);
 }
 
 int fv_train_begin(fv_handle* h) {
@@ -308,27 +472,16 @@ int fv_train_begin(fv_handle* h) {
     return fv_fail(FV_ERR_UNSUPPORTED, "unfrozen training: hidden (<= 4096), 2 * inter and the packed qkv width must be multiples of 64");
   if (h->train.ready) return FV_OK;
   FV_HIP_CHECK(hipSetDevice(h->device));
-  const size_t H = d.llm_hidden, I = d.llm_inter, D = d.llm_head_dim, qd = d.llm_heads * D, qkvw = qd + 2 * d.llm_kv_heads * D;
   h->train.layers.resize(h->dec.layers.size());
-  void* p = nullptr;
-  for (TrainLayerT& T : h->train.layers) {
-    FV_TRY(dev_alloc(h, qkvw * H * 2, &p)); T.qkvT = static_cast<bf16_t*>(p);
-    FV_TRY(dev_alloc(h, H * qd * 2, &p)); T.oT = static_cast<bf16_t*>(p);
-    FV_TRY(dev_alloc(h, 2 * I * H * 2, &p)); T.guT = static_cast<bf16_t*>(p);
-    FV_TRY(dev_alloc(h, H * I * 2, &p)); T.downT = static_cast<bf16_t*>(p);
-    FV_TRY(dev_alloc(h, qkvw * H * 2, &p)); T.qkvT16 = static_cast<bf16_t*>(p);
-    FV_TRY(dev_alloc(h, H * qd * 2, &p)); T.oT16 = static_cast<bf16_t*>(p);
-    FV_TRY(dev_alloc(h, 2 * I * H * 2, &p)); T.guT16 = static_cast<bf16_t*>(p);
-    FV_TRY(dev_alloc(h, H * I * 2, &p)); T.downT16 = static_cast<bf16_t*>(p);
-  }
-  FV_TRY(dev_alloc(h, H * H * 2, &p)); h->train.pj2T = static_cast<bf16_t*>(p);
-  FV_TRY(dev_alloc(h, H * H * 2, &p)); h->train.pj2T16 = static_cast<bf16_t*>(p);
   // transposed copies of the weights as loaded: bf16 (split / plain dgrad) and fp16 (one-pass dgrad; bf16 widens into fp16 exactly)
-  for (const TrainTensor& t : train_tensors(h, nullptr))
-    if (t.tcopy) {
-      FV_TRY(fv::launch_transpose_to_bf16(t.lib, 1, t.cols, *t.tcopy, t.rows, 0, t.rows, t.rows, t.cols, nullptr));
-      FV_TRY(fv::launch_transpose_to_f16(t.lib, 1, t.cols, 0, *t.tcopy16, t.rows, t.rows, t.rows, t.cols, h->f16_flags, nullptr));
-    }
+  for (const TrainTensor& t : train_tensors(h, nullptr)) {
+    if (!t.tcopy) continue;
+    void* p = nullptr;
+    FV_TRY(dev_alloc(h, (size_t)t.numel * 2, &p)); *t.tcopy = static_cast<bf16_t*>(p);
+    FV_TRY(dev_alloc(h, (size_t)t.numel * 2, &p)); *t.tcopy16 = static_cast<bf16_t*>(p);
+    FV_TRY(fv::launch_transpose_to_bf16(t.lib, 1, t.cols, *t.tcopy, t.rows, 0, t.rows, t.rows, t.cols, nullptr));
+    FV_TRY(fv::launch_transpose_to_f16(t.lib, 1, t.cols, 0, *t.tcopy16, t.rows, t.rows, t.rows, t.cols, h->f16_flags, nullptr));
+  }
   FV_TRY(build_commit_table(h));
   FV_HIP_CHECK(hipDeviceSynchronize());
   h->train.ready = true;
@@ -447,240 +600,110 @@ static int train_forward_backward_impl(fv_handle* h, const float* flat_params, c
   if (B <= 0 || B > d.max_batch || T <= 0 || T % 8 || T > d.max_text_tokens) return fv_fail(FV_ERR_ARG, "%s: bad B / T (T must be a multiple of 8)", who);
   // refused HERE, before anything is enqueued or any bucket's all-reduce is launched (launch_embed_bwd runs at the very end of the backward).  The direct LoRA
   // backward computes no embedding gradient, but fv_train_workspace_bytes sizes the workspace for both entry points and admits no larger step: same limit, its own words
-  if (direct && (long)B * T > 16384)
-    return fv_fail(FV_ERR_UNSUPPORTED, "%s: %ld text positions per step (fv_train_workspace_bytes admits B * T <= 16384)", who, (long)B * T);
-  if ((long)B * T > 16384) return fv_fail(FV_ERR_UNSUPPORTED, "fv_train_forward_backward: %ld text positions per step (the embedding gradient keeps the batch's ids in 64 KB of LDS: B * T <= 16384)", (long)B * T);
+  if ((long)B * T > 16384)
+    return direct ? fv_fail(FV_ERR_UNSUPPORTED, "%s: %ld text positions per step (fv_train_workspace_bytes admits B * T <= 16384)", who, (long)B * T)
+                  : fv_fail(FV_ERR_UNSUPPORTED, "fv_train_forward_backward: %ld text positions per step (the embedding gradient keeps the batch's ids in 64 KB of LDS: B * T <= 16384)", (long)B * T);
   const TrainPlan tp = plan_train(h, B, T);
   if (tp.total > ws_bytes) return fv_fail(FV_ERR_STATE, "training workspace too small (%zu > %zu)", tp.total, ws_bytes);
   if (((uintptr_t)ws_v | (uintptr_t)gbuf | (uintptr_t)flat_params) & 15) return fv_fail(FV_ERR_ARG, "%s: buffers must be 16-byte aligned", who);
   if (tp.Tt > h->rope_rows) return fv_fail(FV_ERR_ARG, "sequence of %d tokens exceeds the RoPE table (%d)", tp.Tt, h->rope_rows);
   hipStream_t s = static_cast<hipStream_t>(st);
-  char* ws = static_cast<char*>(ws_v);
+  const DecCtx c = dec_ctx(h, tp, ws_v, s, gbuf, lora_params, lora_grads, cb, user);
   const bf16_t* tower_out = static_cast<const bf16_t*>(tower_out_v);
   const int H = d.llm_hidden, I = d.llm_inter, I2 = 2 * I, D = d.llm_head_dim, CO = d.tower_out_dim;
   const int qd = d.llm_heads * D, kd = d.llm_kv_heads * D, qkvw = qd + 2 * kd;
   const int rows = tp.rows, RI = tp.RI, Ni = tp.Ni, Tt = tp.Tt, L = (int)h->dec.layers.size();
   const float att_scale = 1.0f / std::sqrt((float)D);
-  int64_t total = 0;
-  const std::vector<TrainTensor> tt = train_tensors(h, &total);
-  auto G = [&](const std::string& name) -> float* {
-    for (const TrainTensor& t : tt) if (t.name == name) return (direct && t.bucket > TB_PROJ) ? nullptr : gbuf + t.off;   // direct: no gradient behind the projector
-    return nullptr;
-  };
-  auto bucket_done = [&](int bucket) {
-    if (!cb) return;
-    int64_t lo = INT64_MAX, hi = 0;
-    for (const TrainTensor& t : tt) if (t.bucket == bucket) { lo = std::min(lo, t.off); hi = std::max(hi, t.off + (t.numel + 3) / 4 * 4); }
-    if (bucket == TB_HEAD) { lo = 0; hi = (fv::head_offsets(h->hd).o[12] + 3) / 4 * 4; }   // the head's own layout (and its padding)
-    cb(user, bucket, lo, hi - lo);
-  };
-  auto X_in = [&](int l) { return reinterpret_cast<float*>(ws + tp.x_in + tp.s_x * l); };
-  auto X_mid = [&](int l) { return reinterpret_cast<float*>(ws + tp.x_mid + tp.s_x * l); };
-  auto XN1 = [&](int l) { return reinterpret_cast<bf16_t*>(ws + tp.xn1 + tp.s_xn * l); };
-  auto XN2 = [&](int l) { return reinterpret_cast<bf16_t*>(ws + tp.xn2 + tp.s_xn * l); };
-  auto QKV = [&](int l) { return reinterpret_cast<float*>(ws + tp.qkvf + tp.s_qkvf * l); };
-  auto ATT = [&](int l) { return reinterpret_cast<bf16_t*>(ws + tp.att + tp.s_att * l); };
-  auto LSE = [&](int l) { return reinterpret_cast<float*>(ws + tp.lse + tp.s_lse * l); };
-  auto GU = [&](int l) { return reinterpret_cast<float*>(ws + tp.gu + tp.s_gu * l); };
-  auto ACT = [&](int l) { return reinterpret_cast<bf16_t*>(ws + tp.act + tp.s_act * l); };
-  float* apart = reinterpret_cast<float*>(ws + tp.apart);
-  bf16_t* dsplit = reinterpret_cast<bf16_t*>(ws + tp.dsplit);
-  float* pre0 = reinterpret_cast<float*>(ws + tp.pre0);
-  bf16_t* hsplit = reinterpret_cast<bf16_t*>(ws + tp.hsplit);
-  float* tok = reinterpret_cast<float*>(ws + tp.tok);
-  float* dx = reinterpret_cast<float*>(ws + tp.dx);
-  float* dtmp = reinterpret_cast<float*>(ws + tp.dtmp);
-  float* dqkv = reinterpret_cast<float*>(ws + tp.dqkv);
-  float* delta = reinterpret_cast<float*>(ws + tp.delta);
-  float* scr = reinterpret_cast<float*>(ws + tp.scr);
-  float* pooled = reinterpret_cast<float*>(ws + tp.pooled);
-  float* dpooled = reinterpret_cast<float*>(ws + tp.dpooled);
-  float* xg = reinterpret_cast<float*>(ws + tp.xg);
-  float* dxg = reinterpret_cast<float*>(ws + tp.dxg);
-  float* head_saved = reinterpret_cast<float*>(ws + tp.head_saved);
-  float* head_scr = reinterpret_cast<float*>(ws + tp.head_scr);
-  float* splitk = tp.splitk_bytes ? reinterpret_cast<float*>(ws + tp.splitk) : nullptr;
-  float* colscr = scr + fv::rmsnorm_bwd_scratch_floats(rows, H);
+  float *pre0 = c.at<float>(tp.pre0), *tok = c.at<float>(tp.tok), *pooled = c.at<float>(tp.pooled), *head_saved = c.at<float>(tp.head_saved);
+  bf16_t *hsplit = c.at<bf16_t>(tp.hsplit), *dsplit = c.dsplit();
+  float *dx = c.dx(), *dtmp = c.dtmp(), *dqkv = c.at<float>(tp.dqkv), *scr = c.scr(), *colscr = c.colscr();
+  void* attn_scr = c.at<char>(tp.attn_scr);
   Tower& tw = h->tw;
 
   // ------------------------------------------------------------------------------------------------ forward (everything kept)
-  TR_GEMM(tower_out, CO, tw.pj0_w, RI, H, CO, tw.pj0_b, nullptr, nullptr, 0, pre0, H, FV_EPI_F32, 0);
+  FV_TRY(gemm_p(h, fv::GemmArgs{tower_out, CO, tw.pj0_w, RI, H, CO, tw.pj0_b, nullptr, nullptr, 0, pre0, H, FV_EPI_F32, 0}, s));
   FV_P(FV_FAM_ELT, 20.0 * RI * H, 8.0 * RI * H, fv::launch_gelu_fwd(pre0, hsplit, 2 * H, H, RI, H, s));
-  TR_GEMM(hsplit, 2 * H, tw.pj2_w, RI, H, H, tw.pj2_b, nullptr, nullptr, 0, tok, H, FV_EPI_F32, 1);
-  FV_P(FV_FAM_ELT, 0.0, 6.0 * rows * H, fv::launch_embed_gather(ids, h->dec.embed, tok, X_in(0), B, T, Ni, H, d.llm_vocab, s));
-  const bool f16fwd = h->train.fwd_f16;
-  if (f16fwd && !fp16_backward(h)) return fv_fail(FV_ERR_UNSUPPORTED, "the fp16 training forward goes with the default one-pass fp16 backward (fv_train_set_options 2, 1, k)");
-  for (int l = 0; l < L && f16fwd; ++l) {
-    // ONE fp16 pass per projection (fv_train_set_forward_f16): the normed rows leave the RMSNorm as fp16, the attention output is rounded once from its split form,
-    // the SwiGLU output leaves the gate/up epilogue as fp16 (x 2^-4, the down copy carries the 2^4); weights = exact fp16 copies of the bf16 weights.  The
-    // accumulators the backward differentiates (qkv fp32, gate/up stash, lse) and the fp32 residual stream are kept exactly as in the split-bf16 form.
+  FV_TRY(gemm_p(h, fv::GemmArgs{hsplit, 2 * H, tw.pj2_w, RI, H, H, tw.pj2_b, nullptr, nullptr, 0, tok, H, FV_EPI_F32, 1}, s));
+  FV_P(FV_FAM_ELT, 0.0, 6.0 * rows * H, fv::launch_embed_gather(ids, h->dec.embed, tok, c.X_in(0), B, T, Ni, H, d.llm_vocab, s));
+  if (c.f16fwd && c.mode == BWD_SPLIT) return fv_fail(FV_ERR_UNSUPPORTED, "the fp16 training forward goes with the default one-pass fp16 backward (fv_train_set_options 2, 1, k)");
+  for (int l = 0; l < L; ++l) {
     const DecLayer& Lw = h->dec.layers[l];
     const TrainLayerT& Tw = h->train.layers[l];
-    FV_P(FV_FAM_NORM, 4.0 * rows * H, 6.0 * rows * H, fv::launch_rmsnorm(X_in(l), Lw.ln1, XN1(l), nullptr, H, rows, H, d.rms_eps, s, 1, h->f16_flags));
-    {
-      fv::GemmArgs q1{XN1(l), H, Tw.qkv16, rows, qkvw, H, Lw.qkv_b, nullptr, nullptr, 0, QKV(l), qkvw, FV_EPI_F32, 0};
-      q1.f16 = 1; q1.splitk_ws = splitk; q1.splitk_bytes = tp.splitk_bytes;
-      FV_TRY(gemm_p(h, q1, s));
-    }
+    FV_TRY(fwd_norm(c, c.X_in(l), Lw.ln1, c.XN1(l)));
+    FV_TRY(gemm_sk(c, fwd_gemm(c, c.XN1(l), Lw.qkv_w, Tw.qkv16, qkvw, H, Lw.qkv_b, nullptr, c.QKV(l), qkvw, FV_EPI_F32)));
     FV_P(FV_FAM_ATTN, 2.0 * B * (double)Tt * Tt * qd, 4.0 * rows * (qkvw + qd),
-         fv::launch_attention_f32(QKV(l), qkvw, ATT(l), ATT(l) + qd, 2 * qd, B, Tt, d.llm_heads, d.llm_kv_heads, D, lens, Ni, att_scale, s, h->rope, nullptr, 0, 0, LSE(l), 0, ws + tp.attn_scr));
-    FV_P(FV_FAM_ELT, 0.0, (double)rows * qd * 6, fv::launch_rows_to_f16(ATT(l), 2, 2 * qd, qd, dsplit, qd, rows, qd, h->f16_flags, s));
-    {
-      fv::GemmArgs o1{dsplit, qd, Tw.o16, rows, H, qd, nullptr, nullptr, X_in(l), H, X_mid(l), H, FV_EPI_RES_F32, 0};
-      o1.f16 = 1; o1.splitk_ws = splitk; o1.splitk_bytes = tp.splitk_bytes;
-      FV_TRY(gemm_p(h, o1, s));
+         fv::launch_attention_f32(c.QKV(l), qkvw, c.ATT(l), c.ATT(l) + qd, 2 * qd, B, Tt, d.llm_heads, d.llm_kv_heads, D, lens, Ni, att_scale, s, h->rope, nullptr, 0, 0, c.LSE(l), 0, attn_scr));
+    const bf16_t* att = c.ATT(l);   // kept split for the backward; the fp16 forward reads it rounded once to fp16 rows
+    if (c.f16fwd) {
+      FV_P(FV_FAM_ELT, 0.0, (double)rows * qd * 6, fv::launch_rows_to_f16(c.ATT(l), 2, 2 * qd, qd, dsplit, qd, rows, qd, h->f16_flags, s));
+      att = dsplit;
     }
-    FV_P(FV_FAM_NORM, 4.0 * rows * H, 6.0 * rows * H, fv::launch_rmsnorm(X_mid(l), Lw.ln2, XN2(l), nullptr, H, rows, H, d.rms_eps, s, 1, h->f16_flags));
-    {
-      fv::GemmArgs g1{XN2(l), H, Tw.gu16, rows, I2, H, nullptr, nullptr, nullptr, 0, ACT(l), I, FV_EPI_SWIGLU_F16, 0};
-      g1.f16 = 1; g1.stash = GU(l); g1.stash_f16 = 1; g1.sat = h->f16_flags;
-      FV_TRY(gemm_p(h, g1, s));
-    }
-    {
-      fv::GemmArgs d1{ACT(l), I, Tw.down16, rows, H, I, nullptr, nullptr, X_mid(l), H, X_in(l + 1), H, FV_EPI_RES_F32, 0};
-      d1.f16 = 1; d1.splitk_ws = splitk; d1.splitk_bytes = tp.splitk_bytes;
-      FV_TRY(gemm_p(h, d1, s));
-    }
-  }
-  for (int l = 0; l < L && !f16fwd; ++l) {
-    const DecLayer& Lw = h->dec.layers[l];
-    FV_P(FV_FAM_NORM, 4.0 * rows * H, 8.0 * rows * H, fv::launch_rmsnorm(X_in(l), Lw.ln1, XN1(l), XN1(l) + H, 2 * H, rows, H, d.rms_eps, s));
-    {
-      fv::GemmArgs q1{XN1(l), 2 * H, Lw.qkv_w, rows, qkvw, H, Lw.qkv_b, nullptr, nullptr, 0, QKV(l), qkvw, FV_EPI_F32, 1};
-      q1.splitk_ws = splitk; q1.splitk_bytes = tp.splitk_bytes;
-      FV_TRY(gemm_p(h, q1, s));
-    }
-    FV_P(FV_FAM_ATTN, 2.0 * B * (double)Tt * Tt * qd, 4.0 * rows * (qkvw + qd),
-         fv::launch_attention_f32(QKV(l), qkvw, ATT(l), ATT(l) + qd, 2 * qd, B, Tt, d.llm_heads, d.llm_kv_heads, D, lens, Ni, att_scale, s, h->rope, nullptr, 0, 0, LSE(l), 0, ws + tp.attn_scr));
-    {
-      fv::GemmArgs o1{ATT(l), 2 * qd, Lw.o_w, rows, H, qd, nullptr, nullptr, X_in(l), H, X_mid(l), H, FV_EPI_RES_F32, 1};
-      o1.splitk_ws = splitk; o1.splitk_bytes = tp.splitk_bytes;
-      FV_TRY(gemm_p(h, o1, s));
-    }
-    FV_P(FV_FAM_NORM, 4.0 * rows * H, 8.0 * rows * H, fv::launch_rmsnorm(X_mid(l), Lw.ln2, XN2(l), XN2(l) + H, 2 * H, rows, H, d.rms_eps, s));
-    {   // gate/up with the SwiGLU in its epilogue (act leaves as the down projection's split operand) AND the raw accumulators kept for the backward
-      fv::GemmArgs g1{XN2(l), 2 * H, Lw.gu_w, rows, I2, H, nullptr, nullptr, nullptr, 0, ACT(l), I2, FV_EPI_SWIGLU_SPLIT, 1};
-      g1.stash = GU(l);
+    FV_TRY(gemm_sk(c, fwd_gemm(c, att, Lw.o_w, Tw.o16, H, qd, nullptr, c.X_in(l), c.X_mid(l), H, FV_EPI_RES_F32)));
+    FV_TRY(fwd_norm(c, c.X_mid(l), Lw.ln2, c.XN2(l)));
+    {   // gate/up with the SwiGLU in its epilogue (act leaves as the down projection's operand) AND the raw accumulators kept for the backward
+      fv::GemmArgs g1 = fwd_gemm(c, c.XN2(l), Lw.gu_w, Tw.gu16, I2, H, nullptr, nullptr, c.ACT(l), c.f16fwd ? I : I2, c.f16fwd ? FV_EPI_SWIGLU_F16 : FV_EPI_SWIGLU_SPLIT);
+      g1.stash = c.GU(l);
       // the one-pass fp16 backward rounds d gate/up and act to fp16 operands anyway: it keeps the accumulators as fp16 too (the epilogue of this
       // launch is write-bound: 600 -> 400 MB; the SwiGLU backward reads 200 MB less)
-      g1.stash_f16 = fp16_backward(h) ? 1 : 0; g1.sat = h->f16_flags;
+      g1.stash_f16 = c.mode != BWD_SPLIT ? 1 : 0; g1.sat = h->f16_flags;
       FV_TRY(gemm_p(h, g1, s));
     }
-    {
-      fv::GemmArgs d1{ACT(l), I2, Lw.down_w, rows, H, I, nullptr, nullptr, X_mid(l), H, X_in(l + 1), H, FV_EPI_RES_F32, 1};
-      d1.splitk_ws = splitk; d1.splitk_bytes = tp.splitk_bytes;
-      FV_TRY(gemm_p(h, d1, s));
-    }
+    FV_TRY(gemm_sk(c, fwd_gemm(c, c.ACT(l), Lw.down_w, Tw.down16, H, I, nullptr, c.X_mid(l), c.X_in(l + 1), H, FV_EPI_RES_F32)));
   }
-  FV_P(FV_FAM_ELT, 4.0 * B * H, 8.0 * B * H, fv::launch_pool_norm(X_in(L), lens, h->dec.norm, pooled, B, Tt, Ni, H, d.rms_eps, 0, s));
+  FV_P(FV_FAM_ELT, 4.0 * B * H, 8.0 * B * H, fv::launch_pool_norm(c.X_in(L), lens, h->dec.norm, pooled, B, Tt, Ni, H, d.rms_eps, 0, s));
   const fv::HeadIoNorm* io = h->has_io ? &h->io : nullptr;
   // training != 0: the loss lives in normalised action space (fv_head_forward's convention)
   FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_forward(h->hd, flat_params, pooled, states, B, training ? (dropout_p > 0.f ? 1 : 2) : 2, dropout_p, seed, offset, actions,
                                                      head_saved, s, io));
 
   // ------------------------------------------------------------------------------------------------ backward
-  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p, head_saved, loss, gbuf, head_scr, s, dpooled,
+  float *dpooled = c.at<float>(tp.dpooled), *xg = c.at<float>(tp.xg), *dxg = c.at<float>(tp.dxg);
+  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p, head_saved, loss, gbuf, c.at<float>(tp.head_scr), s, dpooled,
                                                       std::ldexp(1.0f, h->train.loss_scale_log2)));
-  bucket_done(TB_HEAD);
+  c.bucket_done(TB_HEAD);
   // final norm on the pooled rows; the residual-gradient stream starts as zero everywhere else
-  FV_TRY(fv::launch_pool_rows(X_in(L), xg, lens, B, Tt, Ni, H, 0, s));
-  FV_TRY(fv::launch_rmsnorm_bwd(xg, h->dec.norm, dpooled, nullptr, dxg, G("model.norm.weight"), scr, B, H, d.rms_eps, s));
+  FV_TRY(fv::launch_pool_rows(c.X_in(L), xg, lens, B, Tt, Ni, H, 0, s));
+  FV_TRY(fv::launch_rmsnorm_bwd(xg, h->dec.norm, dpooled, nullptr, dxg, c.G(DR_NORM), scr, B, H, d.rms_eps, s));
   FV_HIP_CHECK(hipMemsetAsync(dx, 0, (size_t)rows * H * 4, s));
   FV_TRY(fv::launch_pool_rows(dx, dxg, lens, B, Tt, Ni, H, 1, s));
-  bucket_done(TB_LAYER0 + L);
+  c.bucket_done(TB_LAYER0 + L);
   for (int l = L - 1; l >= 0; --l) {
     const DecLayer& Lw = h->dec.layers[l];
     const TrainLayerT& Tw = h->train.layers[l];
-    const std::string pre = "model.layers." + std::to_string(l) + ".";
-    // down projection: x_out = x_mid + act . Wd^T
-    if (direct) {
-      // gradient ROWS only (no column copies: nothing here runs a weight-gradient GEMM).  dx's fp16 rows go into the last third of the dsplit scratch, so that they
-      // outlive the SwiGLU backward, which writes d gate/up's rows at its start and silu(gate) * up as fp16 rows (the down adapters' activation) into the XT scratch
-      bf16_t* dx16 = dsplit + (size_t)rows * 2 * tp.wmax;
-      bf16_t* act16 = reinterpret_cast<bf16_t*>(ws + tp.XT);
-      FV_P(FV_FAM_ELT, 0.0, (double)rows * H * 6, fv::launch_rows_to_f16(dx, 0, H, 0, dx16, H, rows, H, h->f16_flags, s));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, H, Tw.downT, I, rows, dtmp, s, nullptr, Tw.downT16, dx16));  // d act [rows][I]
-      FV_P(FV_FAM_ELT, 18.0 * rows * I, 16.0 * rows * I, fv::launch_swiglu_bwd_rows(GU(l), 1, dtmp, rows, rows, I, dsplit, act16, h->f16_flags, s));
-      FV_TRY(lora_direct_call(h, l, 3, dx16, act16, 3, I, 0, rows, lora_params, lora_grads, s));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, I2, Tw.guT, H, rows, dtmp, s, nullptr, Tw.guT16, dsplit)); // d xn2 [rows][H]
-      FV_TRY(lora_direct_call(h, l, 2, dsplit, XN2(l), 2, 2 * H, H, rows, lora_params, lora_grads, s));
-    } else if (fp16_backward(h)) {
-      // dx -> fp16 rows + columns in one pass; d act; then the SwiGLU backward writes d gate/up straight into the two fp16 operands its consumers
-      // read (rows for the dgrad, columns for the wgrad) AND act^T for the down projection's wgrad, which therefore runs after it
-      bf16_t* at0 = reinterpret_cast<bf16_t*>(ws + tp.AT);
-      bf16_t* at1 = at0 + (size_t)I2 * tp.Rp;   // behind the widest gradient's columns
-      FV_TRY(grad_operands(h, tp, ws, dx, H, H, rows, at1, s));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, H, Tw.downT, I, rows, dtmp, s, nullptr, Tw.downT16, dsplit));  // d act [rows][I]
-      FV_P(FV_FAM_ELT, 18.0 * rows * I, 22.0 * rows * I,
-           fv::launch_swiglu_bwd_f16(GU(l), 1, dtmp, rows, tp.Rp, I, dsplit, at0, h->f16_flags, s, reinterpret_cast<bf16_t*>(ws + tp.XT)));
-      FV_TRY(wgrad(h, tp, ws, nullptr, 0, H, nullptr, 0, I, rows, G(pre + "mlp.down_proj.weight"), s, nullptr, true, at1, true));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, I2, Tw.guT, H, rows, dtmp, s, nullptr, Tw.guT16, dsplit)); // d xn2 [rows][H]
-      FV_TRY(wgrad(h, tp, ws, nullptr, 0, I2, XN2(l), f16fwd ? H : 2 * H, H, rows, G(pre + "mlp.gate_up_proj.weight"), s, nullptr, true, nullptr, false, f16fwd ? 3 : -1));
-    } else {
-      FV_TRY(dgrad(h, tp, ws, dx, H, H, Tw.downT, I, rows, dtmp, s, nullptr, Tw.downT16));  // d act [rows][I]
-      FV_TRY(wgrad(h, tp, ws, dx, H, H, ACT(l), I2, I, rows, G(pre + "mlp.down_proj.weight"), s));   // the kept activation's hi half is the operand
-      // d gate/up straight into the split-bf16 form both of its consumers read (no fp32 copy, no separate split pass)
-      FV_P(FV_FAM_ELT, 16.0 * rows * I, 20.0 * rows * I, fv::launch_swiglu_bwd(GU(l), dtmp, rows, I, s, dsplit));
-      // gate/up: gu = xn2 . Wgu^T
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, I2, Tw.guT, H, rows, dtmp, s, dsplit, Tw.guT16)); // d xn2 [rows][H]
-      FV_TRY(wgrad(h, tp, ws, nullptr, 0, I2, XN2(l), 2 * H, H, rows, G(pre + "mlp.gate_up_proj.weight"), s, dsplit));
-    }
-    FV_P(FV_FAM_NORM, 12.0 * rows * H, 20.0 * rows * H,
-         fv::launch_rmsnorm_bwd(X_mid(l), Lw.ln2, dtmp, dx, dx, G(pre + "post_attention_layernorm.weight"), scr, rows, H, d.rms_eps, s));
-    // o projection: x_mid = x_in + att . Wo^T
-    if (direct) {
-      FV_P(FV_FAM_ELT, 0.0, (double)rows * H * 6, fv::launch_rows_to_f16(dx, 0, H, 0, dsplit, H, rows, H, h->f16_flags, s));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, H, Tw.oT, qd, rows, dtmp, s, nullptr, Tw.oT16, dsplit));   // d att [rows][qd]
-      FV_TRY(lora_direct_call(h, l, 1, dsplit, ATT(l), 2, 2 * qd, qd, rows, lora_params, lora_grads, s));
-    } else if (fp16_backward(h)) {
-      FV_TRY(grad_operands(h, tp, ws, dx, H, H, rows, reinterpret_cast<bf16_t*>(ws + tp.AT), s));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, H, Tw.oT, qd, rows, dtmp, s, nullptr, Tw.oT16, dsplit));   // d att [rows][qd]
-      FV_TRY(wgrad(h, tp, ws, nullptr, 0, H, ATT(l), 2 * qd, qd, rows, G(pre + "self_attn.o_proj.weight"), s, nullptr, true));
-    } else {
-      FV_TRY(dgrad(h, tp, ws, dx, H, H, Tw.oT, qd, rows, dtmp, s, nullptr, Tw.oT16));       // d att [rows][qd]
-      FV_TRY(wgrad(h, tp, ws, dx, H, H, ATT(l), 2 * qd, qd, rows, G(pre + "self_attn.o_proj.weight"), s));
-    }
+    FV_TRY(mlp_backward(c, l));   // down, SwiGLU, gate/up: dx -> d xn2 in dtmp
+    FV_P(FV_FAM_NORM, 12.0 * rows * H, 20.0 * rows * H, fv::launch_rmsnorm_bwd(c.X_mid(l), Lw.ln2, dtmp, dx, dx, c.G(l, DR_LN2), scr, rows, H, d.rms_eps, s));
+    // o projection: x_mid = x_in + att . Wo^T; d att [rows][qd] into dtmp
+    FV_TRY(proj_backward(c, l, 1, dx, H, ActOp::split(c.ATT(l), 2 * qd), qd, Tw.oT, Tw.oT16, dtmp, c.G(l, DR_O_W)));
     FV_P(FV_FAM_ATTN, 8.0 * B * (double)Tt * Tt * qd, 4.0 * rows * (2 * qkvw + 2 * qd),
-         fv::launch_attention_bwd(QKV(l), qkvw, ATT(l), ATT(l) + qd, 2 * qd, dtmp, qd, LSE(l), delta, dqkv, B, Tt, d.llm_heads, d.llm_kv_heads, D, lens, Ni,
-                                  att_scale, h->rope, s, apart, ws + tp.attn_scr));
-    if (!direct) FV_TRY(fv::launch_colsum(dqkv, qkvw, rows, qkvw, G(pre + "self_attn.qkv_proj.bias"), colscr, s));
-    if (direct) {
-      FV_P(FV_FAM_ELT, 0.0, (double)rows * qkvw * 6, fv::launch_rows_to_f16(dqkv, 0, qkvw, 0, dsplit, qkvw, rows, qkvw, h->f16_flags, s));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, qkvw, Tw.qkvT, H, rows, dtmp, s, nullptr, Tw.qkvT16, dsplit));   // d xn1 [rows][H]
-      FV_TRY(lora_direct_call(h, l, 0, dsplit, XN1(l), 2, 2 * H, H, rows, lora_params, lora_grads, s));
-    } else if (fp16_backward(h)) {
-      FV_TRY(grad_operands(h, tp, ws, dqkv, qkvw, qkvw, rows, reinterpret_cast<bf16_t*>(ws + tp.AT), s));
-      FV_TRY(dgrad(h, tp, ws, nullptr, 0, qkvw, Tw.qkvT, H, rows, dtmp, s, nullptr, Tw.qkvT16, dsplit));   // d xn1 [rows][H]
-      FV_TRY(wgrad(h, tp, ws, nullptr, 0, qkvw, XN1(l), f16fwd ? H : 2 * H, H, rows, G(pre + "self_attn.qkv_proj.weight"), s, nullptr, true, nullptr, false, f16fwd ? 3 : -1));
-    } else {
-      FV_TRY(dgrad(h, tp, ws, dqkv, qkvw, qkvw, Tw.qkvT, H, rows, dtmp, s, nullptr, Tw.qkvT16));   // d xn1 [rows][H]
-      FV_TRY(wgrad(h, tp, ws, dqkv, qkvw, qkvw, XN1(l), 2 * H, H, rows, G(pre + "self_attn.qkv_proj.weight"), s));
-    }
-    FV_P(FV_FAM_NORM, 12.0 * rows * H, 20.0 * rows * H,
-         fv::launch_rmsnorm_bwd(X_in(l), Lw.ln1, dtmp, dx, dx, G(pre + "input_layernorm.weight"), scr, rows, H, d.rms_eps, s));
-    bucket_done(TB_LAYER0 + l);
+         fv::launch_attention_bwd(c.QKV(l), qkvw, c.ATT(l), c.ATT(l) + qd, 2 * qd, dtmp, qd, c.LSE(l), c.at<float>(tp.delta), dqkv, B, Tt, d.llm_heads, d.llm_kv_heads, D, lens, Ni,
+                                  att_scale, h->rope, s, c.at<float>(tp.apart), attn_scr));
+    if (c.mode != BWD_DIRECT) FV_TRY(fv::launch_colsum(dqkv, qkvw, rows, qkvw, c.G(l, DR_QKV_B), colscr, s));
+    // qkv projection: qkv = xn1 . Wqkv^T + b; d xn1 [rows][H] into dtmp
+    FV_TRY(proj_backward(c, l, 0, dqkv, qkvw, c.f16fwd ? ActOp::f16(c.XN1(l), H) : ActOp::split(c.XN1(l), 2 * H), H, Tw.qkvT, Tw.qkvT16, dtmp, c.G(l, DR_QKV_W)));
+    FV_P(FV_FAM_NORM, 12.0 * rows * H, 20.0 * rows * H, fv::launch_rmsnorm_bwd(c.X_in(l), Lw.ln1, dtmp, dx, dx, c.G(l, DR_LN1), scr, rows, H, d.rms_eps, s));
+    c.bucket_done(TB_LAYER0 + l);
   }
   // embedding rows of the text positions (direct LoRA: the embedding is frozen and its gradient -- memset and scatter -- is not computed)
-  if (!direct) {
-    float* gE = G("model.embed_tokens.weight");
+  if (c.mode != BWD_DIRECT) {
+    float* gE = c.G(DR_EMBED);
     FV_HIP_CHECK(hipMemsetAsync(gE, 0, (size_t)d.llm_vocab * H * 4, s));
     FV_TRY(fv::launch_embed_bwd(ids, lens, dx, gE, B, T, Ni, H, d.llm_vocab, s));
-    bucket_done(TB_EMBED);
+    c.bucket_done(TB_EMBED);
   }
-  // projector: tok = gelu(tower_out . W0^T + b0) . W2^T + b2 at the image positions
+  // projector: tok = gelu(tower_out . W0^T + b0) . W2^T + b2 at the image positions (every mode: each helper makes the operand form the options name)
   {
     float* dtok = dqkv;   // [RI][H] fp32 (the attention scratch is free now)
     FV_TRY(fv::launch_image_rows(dx, dtok, B, Tt, Ni, H, s));
-    FV_TRY(fv::launch_colsum(dtok, H, RI, H, G("model.mm_projector.2.bias"), colscr, s));
-    FV_TRY(dgrad(h, tp, ws, dtok, H, H, h->train.pj2T, H, RI, dtmp, s, nullptr, h->train.pj2T16));   // d h [RI][H]
-    FV_TRY(wgrad(h, tp, ws, dtok, H, H, hsplit, 2 * H, H, RI, G("model.mm_projector.2.weight"), s));
+    FV_TRY(fv::launch_colsum(dtok, H, RI, H, c.G(DR_PJ2_B), colscr, s));
+    FV_TRY(dgrad(c, GradOp::rows_f32(dtok, H), H, h->train.pj2T, h->train.pj2T16, H, RI, dtmp));   // d h [RI][H]
+    FV_TRY(wgrad(c, GradOp::rows_f32(dtok, H), H, ActOp::split(hsplit, 2 * H), H, RI, c.G(DR_PJ2_W)));
     FV_TRY(fv::launch_gelu_bwd(dtmp, pre0, (size_t)RI * H, s));
-    FV_TRY(fv::launch_colsum(dtmp, H, RI, H, G("model.mm_projector.0.bias"), colscr, s));
-    FV_TRY(wgrad(h, tp, ws, dtmp, H, H, tower_out, CO, CO, RI, G("model.mm_projector.0.weight"), s));
-    bucket_done(TB_PROJ);
+    FV_TRY(fv::launch_colsum(dtmp, H, RI, H, c.G(DR_PJ0_B), colscr, s));
+    FV_TRY(wgrad(c, GradOp::rows_f32(dtmp, H), H, ActOp::bf16(tower_out, CO), CO, RI, c.G(DR_PJ0_W)));
+    c.bucket_done(TB_PROJ);
     if (h->train.d_tower_out) {
       // dL/d(tower_out) = d pre0 . W0, straight out as the fp16 rows the tower's backward continues from (fv_train_tower_backward)
-      if (!fp16_backward(h)) return fv_fail(FV_ERR_UNSUPPORTED, "tower training runs on the default one-pass fp16 backward (fv_train_set_options 2, 1, k)");
+      if (c.mode == BWD_SPLIT) return fv_fail(FV_ERR_UNSUPPORTED, "tower training runs on the default one-pass fp16 backward (fv_train_set_options 2, 1, k)");
       FV_P(FV_FAM_ELT, 0.0, (double)RI * H * 6, fv::launch_rows_to_f16(dtmp, 0, H, 0, dsplit, H, RI, H, h->f16_flags, s));
       // (fp32 first: the stream gets its own power-of-two scale on the way to fp16 -- tower_bwd_kernels.hip launch_rescale_to_f16; d pre0 in dtmp has been consumed.
       // Its target, twice the loss scale -- 2^13 by default --, follows fv_train_set_options: a caller that lowers the loss scale after fp16 saturations lowers
