@@ -25,7 +25,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from gpu_util import DEV, rel_l2  # noqa: E402
-from test_gpu_lora import LLM_05B, LLM_7B, _random_adapters, _trainable_named  # noqa: E402
+from test_gpu_lora import LLM_05B, LLM_7B, RAGGED_LLM, RAGGED_PROJECTED_RANKS, _random_adapters, _slice_stats, _trainable_named  # noqa: E402
 from test_gpu_train_unfrozen import GRAD_TOL, _inputs, _rig  # noqa: E402
 from fastvla_hip import FastVLAEngine, FastVLAHipError, _lib, arch, lora, weights  # noqa: E402
 from oracle import fastvit_hd, head, qwen2, train_unfrozen  # noqa: E402
@@ -61,15 +61,10 @@ def _random_magnitudes(eng, flat, lflat, lt, seed):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. norms and projection, op level
-@pytest.mark.parametrize("shape", ["0.5b", "7b"])
-@pytest.mark.parametrize("rank", [4, 16, 64])
-def test_norms_and_projection_match_float64(shape, rank):
-    """rel-L2 <= 1e-5 for n, dA, dB and dm of every adapted matrix: the project's derived bar for fp32 sums (an fp32 sum of K terms in any order errs by about
-    sqrt(K) 2^-24: 8e-6 at K = 18944; lane-partial sums, which both new reductions use, sit near 5e-7).  Two calls are bit-identical; head and projector
-    gradients are copied.  Measured on the MI355X, worst over the six cases: n 5.6e-8, dA 2.5e-7, dB 2.5e-6, dm 1.8e-6
-    (dB and dm carry the K-long fmaf chain of the dW' . A^T accumulator: both worst cases are down_proj at the 7B shape, K = 18944)."""
-    dims = LLM_05B if shape == "0.5b" else LLM_7B
-    model = arch.ModelConfig("dora-" + shape, arch.LLMConfig(layers=1, vocab=512, **dims), arch.preset("tiny").tower)
+def _dora_op_case(shape, model, rank, merge=False):
+    """row norms, dA, dB and dm of every adapted matrix of this model against float64 (1e-5 each), two calls bit-identical, head and projector gradients copied.
+    merge: every rank index of dA (a row) and of dB (a column) is held to the same 1e-5 against the RMS slice norm, and fv_train_lora_merge into a copy of the
+    master is compared with float64 diag(m / n) (W0 + s B A): 1e-5 per matrix and row by row.  -> the worst figures"""
     w = weights.init_backbone(model, seed=3)
     eng = FastVLAEngine(model, state_dim=14, action_dim=14, hidden_dim=64, fusion_dim=64, max_batch=2, max_text_tokens=8, llm_precision=1)
     eng.load_weights(w)
@@ -129,8 +124,67 @@ def test_norms_and_projection_match_float64(shape, rank):
             print(f"[dora op {shape} r={rank}] {pre} {what}: rel_l2 {e:.2e}")
             worst[what] = max(worst[what], e)
             assert e <= 1e-5, (pre, what, e)
+            if merge and what in ("dA", "dB"):
+                es, fl = _slice_stats(have, ref, 1 if what == "dA" else 0)
+                worst["slice"], worst["floor"] = max(worst.get("slice", 0.0), es), min(worst.get("floor", 1e30), fl)
+                assert fl >= 0.1, (pre, what, fl)      # no rank index is judged against a norm it does not have
+                assert es <= 1e-5, (pre, what, es)
     print(f"[dora op {shape} r={rank}] worst: " + " ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    if merge:
+        merged = flat.clone()
+        eng.train_lora_merge(merged, lflat)
+        torch.cuda.synchronize()
+        named1 = eng.train_named_tensors(merged)
+        for pre in pres:
+            k = pre + ".weight"
+            V = w0[k].double().cpu() + s * (par[pre + ".lora_B.weight"].double().cpu() @ par[pre + ".lora_A.weight"].double().cpu())
+            ref = (par[pre + MAG].double().cpu().reshape(-1) / V.norm(dim=1))[:, None] * V
+            e = rel_l2(named1[k].cpu(), ref)
+            rows = float(((named1[k].double().cpu() - ref).norm(dim=1) / ref.norm(dim=1)).max())     # row by row, each against its own norm ...
+            er, fl = _slice_stats(named1[k].cpu(), ref, 1)                                             # ... and against the RMS row norm
+            print(f"[dora merge {shape} r={rank}] {k}: rel_l2 {e:.2e}, worst row {max(rows, er):.2e}")
+            worst["merge"], worst["merge_row"] = max(worst.get("merge", 0.0), e), max(worst.get("merge_row", 0.0), rows, er)
+            worst["floor"] = min(worst["floor"], fl)
+            assert fl >= 0.1, (k, fl)
+            assert e <= 1e-5 and rows <= 1e-5 and er <= 1e-5, (k, e, rows, er)
+        for k in w0:
+            if k not in {pre + ".weight" for pre in pres}:
+                assert torch.equal(w0[k], named1[k]), k
+        # the adapted commit's bf16 rows (lora_commit_kernel<0, 1>, partial tile of columns included), read back: the merged master rounded to bf16, bit for bit
+        eng.train_lora_commit(flat, lflat)
+        back = torch.zeros(total, device=DEV)
+        eng.train_export_params(back)
+        torch.cuda.synchronize()
+        named_b = eng.train_named_tensors(back)
+        for pre in pres:
+            assert torch.equal(named_b[pre + ".weight"], named1[pre + ".weight"].to(torch.bfloat16).float()), pre
+        print(f"[dora op {shape} r={rank}] worst slice {worst['slice']:.2e}; merged master {worst['merge']:.2e}, row {worst['merge_row']:.2e}; "
+              f"smallest reference slice / RMS {worst['floor']:.2f}")
     eng.close()
+    return worst
+
+
+@pytest.mark.parametrize("shape", ["0.5b", "7b"])
+@pytest.mark.parametrize("rank", [4, 16, 64])
+def test_norms_and_projection_match_float64(shape, rank):
+    """rel-L2 <= 1e-5 for n, dA, dB and dm of every adapted matrix: the project's derived bar for fp32 sums (an fp32 sum of K terms in any order errs by about
+    sqrt(K) 2^-24: 8e-6 at K = 18944; lane-partial sums, which both new reductions use, sit near 5e-7).  Two calls are bit-identical; head and projector
+    gradients are copied.  Measured on the MI355X, worst over the six cases: n 5.6e-8, dA 2.5e-7, dB 2.5e-6, dm 1.8e-6
+    (dB and dm carry the K-long fmaf chain of the dW' . A^T accumulator: both worst cases are down_proj at the 7B shape, K = 18944)."""
+    dims = LLM_05B if shape == "0.5b" else LLM_7B
+    _dora_op_case(shape, arch.ModelConfig("dora-" + shape, arch.LLMConfig(layers=1, vocab=512, **dims), arch.preset("tiny").tower), rank)
+
+
+@pytest.mark.parametrize("rank", RAGGED_PROJECTED_RANKS)
+def test_norms_projection_and_merge_at_the_ragged_shape(rank):
+    """_dora_op_case at the ragged layer (RAGGED_LLM in test_gpu_lora.py: partial strips, a partial commit tile of columns) and at the ranks of
+    RAGGED_PROJECTED_RANKS: at 33 and 63 dm is assembled by two launches of the projection, at 1, 33 and 63 a k-pair of lora_norm_kernel's B . A is half empty.
+    The bars are those of test_norms_and_projection_match_float64 (1e-5 for n, dA, dB, dm; the contractions here are at most 352 long) and of
+    test_commit_at_initialisation_is_the_plain_commit_and_merge_equals_commit (1e-5 for the merged master, row by row); every rank index of dA and dB is held to
+    1e-5 against the RMS slice norm of the reference, none of which is below a tenth of that RMS (asserted; the smallest is 0.29, a merged row
+    whose magnitude drew the factor 0.5).
+    Measured on the MI355X, worst over the four ranks: n 4.0e-8, dA 1.5e-7, dB 3.5e-7, dm 3.8e-7, slice 4.4e-7, merged master 1.5e-7, merged row 3.6e-7."""
+    _dora_op_case("ragged", arch.ModelConfig("dora-ragged", arch.LLMConfig(layers=1, vocab=512, **RAGGED_LLM), arch.preset("tiny").tower), rank, merge=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2. commit / merge
@@ -334,6 +388,8 @@ def _step_case(name, llm, B, T, hd, rank, targets, dora, rslora, direct=False):
     ("small", None, 3, 16, 64, 4, ("q_proj", "v_proj")),
     ("0.5b-width-4-layers", arch.LLMConfig(hidden=896, layers=4, heads=14, kv_heads=2, head_dim=64, inter=4864, vocab=8192), 4, 32, 128, 16, None),
     ("7b-width-2-layers", arch.LLMConfig(hidden=3584, layers=2, heads=28, kv_heads=4, head_dim=128, inter=18944, vocab=4096), 2, 16, 128, 16, None),
+    # two ragged layers at rank 33: the magnitude's gradient assembled by two projection launches on partial strips; control: the unfrozen step's ragged case
+    ("ragged-2-layers", arch.LLMConfig(layers=2, vocab=512, **RAGGED_LLM), 3, 16, 64, 33, None),
 ])
 def test_dora_step_matches_autograd(name, llm, B, T, hd, rank, targets):
     """The four cases and the bars of test_lora_step_matches_autograd: actions and loss <= 1e-3, every gradient <= GRAD_TOL (2e-3), lora_magnitude_vector included;

@@ -793,6 +793,28 @@ def test_gemm_glds_128_tile_fp32_epilogues():
     check_close(out.cpu(), ref, rel=2e-5, amax=2e-5, what="glds128 ksplit res_f32")
 
 
+@pytest.mark.parametrize("M,ws_on", [(195, False), (195, True), (32800, False)])
+def test_gemm_ksplit_with_a_k_that_is_no_multiple_of_64(M, ws_on):
+    """A decoder whose inter is 32 mod 64 (fv_train_begin admits it) contracts its down projection over K = 352 = 5.5 K-tiles: the split-bf16 form then runs on
+    the register-staged kernel, whose last tile of EACH half is half zeros.  In place on the fp32 residual stream, as the decoder calls it: the 64-row instance
+    alone, cut into K ranges (scratch supplied: 12 tiles over 3 ranges, the seam of the halves inside a range) and the 128-row instance (>= 512 blocks).  The bars
+    of test_gemm_glds_128_tile_fp32_epilogues' split form."""
+    torch.manual_seed(M)
+    N, K = 192, 352
+    A = torch.randn(M, K)
+    Ah = bf(A)
+    Al = bf(A - Ah)
+    W, res = bf(torch.randn(N, K) * 0.05), torch.randn(M, N)
+    a = torch.cat([dev_bf16(Ah), dev_bf16(Al)], dim=1).contiguous()
+    w, x = dev_bf16(W), dev_f32(res)
+    ws = torch.empty(8 * M * 256, dtype=torch.float32, device=DEV) if ws_on else None
+    call(lib().fv_op_gemm_splitk(a.data_ptr(), 2 * K, w.data_ptr(), M, N, K, None, x.data_ptr(), N, x.data_ptr(), N, _lib.EPI_RES_F32, 1,
+                                 ws.data_ptr() if ws_on else None, ws.numel() * 4 if ws_on else 0, stream()), "fv_op_gemm_splitk")
+    torch.cuda.synchronize()
+    ref = (res.double() + (Ah + Al).double() @ W.double().t()).float()
+    check_close(x.cpu(), ref, rel=2e-5, amax=2e-5, what=f"ksplit res_f32 {M}x{N}x{K}")
+
+
 def test_gemm_splitk_down_projection_shape():
     """M = 4096, N = 896: 64 output tiles of 256 x 256 (the last column tile padded) cut into K ranges, one unit per CU, summed
     by the reduce kernel -- plain and split-bf16 operands, against the same GEMM without the scratch buffer."""

@@ -138,6 +138,13 @@ def _inputs(model, B, T, seed):
     return tower_out, ids, mask, states, targets
 
 
+def _adam_first_update_bound(pmax, lr=1e-3, weight_decay=1e-2):
+    """the largest |new - old| of a tensor's first clip + AdamW step: |Adam's first update| <= lr, decoupled weight decay lr . wd . |p|, and the difference of two
+    stored fp32 parameters carries the spacing of fp32 at |p| (the term of test_gpu_dora.py's _check_adamw; never below the 1e-7 these tests allowed before it: one
+    ulp of the action expert's LayerNorm weight 1.22 is 1.2e-7, and the ragged-2-layers case lands on it)"""
+    return lr + max(1e-7, 2.0 ** -22 * pmax) + weight_decay * lr * pmax
+
+
 def _check_grads(eng, grads_flat, ref, tol=GRAD_TOL):
     got = eng.train_named_tensors(grads_flat / eng.train_loss_scale())    # every gradient carries the loss scale (a power of two: the division is exact)
     assert set(got) == set(ref["grads"]), sorted(set(got) ^ set(ref["grads"]))[:8]
@@ -163,6 +170,8 @@ def _check_grads(eng, grads_flat, ref, tol=GRAD_TOL):
     ("0.5b-full-depth", arch.preset("fastvlm-0.5b").llm, "full", 2, 8, 256),
     # FastVLM-7B's decoder geometry at full width (C5's model): head_dim 128 through the attention backward, GQA group 7, K = 18944 contractions
     ("7b-width-2-layers", arch.LLMConfig(hidden=3584, layers=2, heads=28, kv_heads=4, head_dim=128, inter=18944, vocab=4096), "tiny", 2, 16, 128),
+    # no dimension a multiple of 128, GQA group 3 on ONE kv head, inter 352 = 5.5 K-tiles of the split-bf16 down projection: the control of the LoRA tests' ragged cases
+    ("ragged-2-layers", arch.LLMConfig(hidden=192, layers=2, heads=3, kv_heads=1, head_dim=64, inter=352, vocab=512), "tiny", 3, 16, 64),
 ])
 def test_unfrozen_step_matches_autograd(name, llm, tower, B, T, hd):
     if not torch.cuda.is_available():
@@ -242,7 +251,7 @@ def test_unfrozen_step_matches_autograd(name, llm, tower, B, T, hd):
         # clipped gradient is within 100 eps of zero (a key bias under a nearly position-independent score, unused embedding rows) move by
         # lr * noise / (|noise| + eps) and are compared by |update| <= lr only
         big = (ref["grads"][k].reshape(du.shape) * coef).abs() > 1e-6
-        assert float(du.abs().max()) <= 1.0001e-3 + 1e-2 * 1e-3 * float(params[k].abs().max()), k
+        assert float(du.abs().max()) <= _adam_first_update_bound(float(params[k].abs().max())), k
         if big.any():
             bad = float(((du - dr).abs()[big] > 0.05 * 1e-3 + 1e-2 * dr.abs()[big]).float().mean())
             assert bad <= 5e-3, (k, bad)

@@ -1211,7 +1211,9 @@ static int launch_gemm_core(const GemmArgs& a, hipStream_t s) {
   if (a.ksplit == 2) {
     if (!a.W8 || a.K % 128 || a.lda * 2 < 3 * a.K || ((uintptr_t)a.W8 & 15)) return fv_fail(FV_ERR_ARG, "gemm: the hi + lo8 form needs W8, K %% 128 == 0 and lda >= 1.5 K");
     if (a.f16) return fv_fail(FV_ERR_ARG, "gemm: hi + lo8 goes with bf16 hi operands");
-  } else if (a.ksplit && (a.K % BK || a.lda < 2 * a.K)) return fv_fail(FV_ERR_ARG, "gemm: ksplit needs K %% 64 == 0 and lda >= 2K");
+  } else if (a.ksplit && a.lda < 2 * a.K) return fv_fail(FV_ERR_ARG, "gemm: ksplit needs lda >= 2K");
+  // (ksplit with a K that is no multiple of 64 -- a decoder whose inter is 32 mod 64 -- goes to the register-staged kernel: every form on whole 64-element
+  // K tiles below asks for K % 64 == 0 itself, gemm_kernel walks ceil(K / 64) tiles per half and zero-fills the last one's columns past K on both operands)
   static int cus = 0;
   if (!cus) {
     int dev = 0;
