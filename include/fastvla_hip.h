@@ -230,6 +230,32 @@ int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_a
 int fv_adamw_clip_step(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, int64_t n,
                        const fv_adamw_hparams* hp, int64_t step, float* grad_norm_out, fv_stream s);
 
+/* ---- parameter groups for the step above (torch.optim.AdamW's param_groups; the reference's trainer, training/trainer.py:60-66, has ONE group
+ * because it only trains the head).  A table of groups tiles the flat buffer [0, n): each group scales the learning rate (lr_g = hp.lr * lr_scale),
+ * carries its own weight decay and may be frozen.  `frozen` is what freezes a group: its elements are neither read into the clip norm nor written
+ * (p, m, v keep their bits); lr_scale = 0 alone is a plain group: its gradient counts in the norm and its m / v move (p stays, the decoupled decay being lr_g * weight_decay).
+ * The library cuts every group into segments of at most FV_ADAMW_SEGMENT floats, one thread block each (csrc/optim_kernels.hip). */
+#define FV_ADAMW_SEGMENT 8192
+typedef struct fv_adamw_group {
+  int64_t begin, end;              /* [begin, end) in floats, both multiples of 4 */
+  float lr_scale, weight_decay;    /* finite, >= 0 */
+  int32_t frozen, reserved;        /* reserved must be 0 */
+} fv_adamw_group;                  /* 32 bytes */
+typedef struct fv_adamw_groups fv_adamw_groups;   /* opaque: device segment table + its partial-sum scratch */
+/* A configuration call: allocates, uploads and synchronises.  FV_ERR_ARG, with a message naming the offending group, for: n <= 0 or n % 4 != 0; n_groups
+ * outside 1 .. 65536; a group that is empty, unsorted, overlapping or leaves a gap; a boundary that is not a multiple of 4; the last end != n; a negative or
+ * non-finite lr_scale / weight_decay; reserved != 0.  Destroy the table before the handle. */
+int fv_adamw_groups_create(fv_handle* h, const fv_adamw_group* host_groups, int n_groups, int64_t n, fv_adamw_groups** out);
+int fv_adamw_groups_destroy(fv_handle* h, fv_adamw_groups* groups);
+/* fv_adamw_clip_step over the table: ONE global clip norm over the non-frozen elements (coefficient as fv_adamw_clip_step's), then per element the same
+ * expression with lr_g and the group's weight decay -- hp->weight_decay is IGNORED by this entry.  A table whose groups all carry lr_scale 1 and one decay
+ * gives fv_adamw_clip_step's p, m, v bit for bit when no clipping applies (the norm itself is summed in another fixed order).
+ * grad_norm_out (1 f32, may be NULL): the pre-clip global norm; group_norms_out (n_groups f32, device, may be NULL): sqrt(group's sum of squares) * grad_scale,
+ * 0 for a frozen group.  No float atomics: two runs give the same bits.  FV_ERR_ARG when n differs from the table's or a buffer is not 16-byte aligned.
+ * Asynchronous on s, allocates nothing.  The table owns the partial sums, so ONE step may be in flight per table. */
+int fv_adamw_clip_step_groups(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, int64_t n, const fv_adamw_hparams* hp,
+                              const fv_adamw_groups* groups, int64_t step, float* grad_norm_out, float* group_norms_out, fv_stream s);
+
 /* gradient accumulation (training/trainer.py:96,171: accelerate sums micro-batch gradients before the optimiser step):
  * acc += grads over n floats; both 16-byte aligned flat head buffers. */
 int fv_grad_accumulate(fv_handle* h, float* acc, const float* grads, int64_t n, fv_stream s);

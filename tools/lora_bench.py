@@ -9,7 +9,10 @@ Memory: the torch allocator's peak while a mode's buffers are the only ones aliv
 in both modes and not in that figure).
 --rslora: every LoRA mode runs with s = alpha / sqrt(rank).  --dora: a DoRA step (fv_train_lora_begin_ex FV_LORA_DORA: the projected LoRA step with the row-norm
 pass in its commit and the magnitude gradient in its projection) joins the alternating windows, on a second engine over the same weights (a handle holds one
-adapter mode), and its projection / commit / row-norm times join kernels_ms; every other figure is measured as without it."""
+adapter mode), and its projection / commit / row-norm times join kernels_ms; every other figure is measured as without it.
+--groups: ONLY the optimiser step, single-group (fv_adamw_clip_step) against grouped (fv_adamw_clip_step_groups), in alternating windows of the same process over
+two buffers -- the full master under a full fine-tuning table (decoder x 0.1, layer decay 0.9, no decay on vectors) and the rank-r trainable buffer under a LoRA+
+table (lora_B x 16, no decay on vectors: hundreds of groups) -- written to profiles/optim_groups_bench.json unless --out names another file."""
 import argparse
 import ctypes as C
 import json
@@ -23,7 +26,58 @@ ROOT = Path(__file__).resolve().parent.parent
 for p in (str(ROOT), str(ROOT / "vla-from-fastvlm_amd")):
     if p not in sys.path:
         sys.path.insert(0, p)
-from fastvla_hip import FastVLAEngine, _lib, arch, lora, weights  # noqa: E402
+from fastvla_hip import FastVLAEngine, _lib, arch, lora, optim, weights  # noqa: E402
+
+
+def groups_bench(args, eng, dev):
+    """single-group against grouped optimiser step over the full master and over the LoRA trainable buffer; host clock around windows that end in a device
+    synchronise, the four (buffer, entry) windows alternating within a round.  GB/s counts 32 bytes per element for both entries: the norm pass reads the
+    gradient (4), the update reads p, g, m, v and writes p, m, v (28).  Every call passes step = 1 while m and v move on: the bias corrections are host-side
+    scalars, so the kernels' work does not depend on the step number."""
+    tensors, total, _ = eng.train_layout()
+    lt, ltotal = eng.train_lora_layout()
+    hp = dict(lr=1e-5, weight_decay=1e-4, max_grad_norm=1.0, grad_scale=1.0 / eng.train_loss_scale())
+    cases = {"full_master": (tensors, total, dict(lr_scales={"decoder": 0.1}, layer_decay=0.9, no_decay=("vectors",))),
+             f"lora_rank{args.rank}_trainable": (lt, ltotal, dict(lora_plus_ratio=16, no_decay=("vectors",)))}
+    bufs, res = {}, {"model": args.model, "rank": args.rank, "reps_per_window": args.kernel_reps, "bytes_per_element": 32, "buffers": {}}
+    for name, (layout, n, opts) in cases.items():
+        groups, _ = optim.build_param_groups(layout, weight_decay=hp["weight_decay"], total=n, **opts)
+        table = eng.adamw_groups(groups, n)
+        p = torch.empty(n, device=dev).normal_(0, 0.02)
+        gr = torch.empty(n, device=dev).normal_(0, 1.0)
+        bufs[name] = (p, gr, torch.zeros_like(p), torch.zeros_like(p), table, torch.zeros(len(groups), device=dev))
+        segs = sum((x["end"] - x["begin"] + _lib.FV_ADAMW_SEGMENT - 1) // _lib.FV_ADAMW_SEGMENT for x in groups)
+        res["buffers"][name] = {"numel": n, "groups": len(groups), "segments": segs, "options": optim.normalize_options(**opts), "rounds": []}
+    norm = torch.zeros(1, device=dev)
+
+    def window(fn, k):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(k):
+            fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0) / k
+
+    for _ in range(args.rounds):
+        for name, (p, gr, m, v, table, gn) in bufs.items():
+            k = args.kernel_reps if p.numel() < (1 << 26) else max(3, args.kernel_reps // 2)
+            plain = window(lambda: eng.adamw_step(p, gr, m, v, 1, grad_norm_out=norm, **hp), k)
+            grouped = window(lambda: eng.adamw_step(p, gr, m, v, 1, grad_norm_out=norm, groups=table, group_norms_out=gn, **hp), k)
+            res["buffers"][name]["rounds"].append({"single_ms": round(plain, 4), "grouped_ms": round(grouped, 4)})
+    med = lambda xs: sorted(xs)[len(xs) // 2]   # noqa: E731
+    for name, b in res["buffers"].items():
+        for key in ("single", "grouped"):
+            xs = [r[key + "_ms"] for r in b["rounds"]]
+            b[key + "_ms"] = med(xs)
+            b[key + "_spread_ms"] = round(max(xs) - min(xs), 4)
+            b[key + "_gb_s"] = round(32.0 * b["numel"] / b[key + "_ms"] / 1e6, 1)
+    print(json.dumps(res))
+    out = Path(args.out) if args.out else ROOT / "profiles" / "optim_groups_bench.json"
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(res, indent=1) + "\n")
+    for b in bufs.values():
+        b[4].close()
 
 
 def main():
@@ -39,6 +93,7 @@ def main():
     ap.add_argument("--kernel-reps", type=int, default=20)
     ap.add_argument("--dora", action="store_true", help="also measure the DoRA step (a second engine in the same process)")
     ap.add_argument("--rslora", action="store_true", help="s = alpha / sqrt(rank) in every LoRA mode")
+    ap.add_argument("--groups", action="store_true", help="only the optimiser step: single-group against grouped AdamW (profiles/optim_groups_bench.json)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -53,6 +108,10 @@ def main():
     _, total, _ = eng.train_layout()
     lt, ltotal = eng.train_lora_layout()
     front = next(t["offset"] for t in lt if ".lora_" in t["name"])
+    if args.groups:
+        groups_bench(args, eng, dev)
+        eng.close()
+        return
     g = torch.Generator().manual_seed(1)
     images = torch.rand(B, 3, 336, 336, generator=g).to(dev)
     ids = torch.randint(0, 151643, (B, T), generator=g)

@@ -290,6 +290,24 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ONE element of the fused clip + AdamW step (torch.optim.AdamW: decoupled decay, bias corrections bc1 = 1 - beta1^t, bc2_sqrt = sqrt(1 - beta2^t)).
+// adamw_kernel (head_kernels.hip) and adamw_groups_kernel (optim_kernels.hip) both evaluate THIS expression, so a grouped step whose groups all carry
+// lr_scale 1 and the same decay gives adamw_kernel's bits.  Which products fuse into an fma is WRITTEN OUT and contraction is off inside: left to the compiler
+// it depends on the code around the expression (a scalar kernel and a float4 loop fuse differently), and the two kernels would differ in the last bit.  The
+// form is the one adamw_kernel has always compiled to: 1 - lr wd and m's update fused, v's update two rounded products and a sum.
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float coef, float lr, float weight_decay, float beta1, float beta2,
+                                             float eps, float bc1, float bc2_sqrt) {
+#pragma clang fp contract(off)
+  const float gi = g * coef;
+  const float pi = p * __builtin_fmaf(-lr, weight_decay, 1.0f);
+  const float mi = __builtin_fmaf(1.0f - beta1, gi, m * beta1);
+  const float vi = v * beta2 + (gi * gi) * (1.0f - beta2);
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  p = pi - ((lr / bc1) * mi) / denom;
+  m = mi;
+  v = vi;
+}
+
 // XCD-aware bijective remap of a 1-D grid: blocks b and b+8 share an XCD (round-robin dispatch), so give each XCD a
 // contiguous run of logical ids (neighbouring tiles then share one L2).  Speed only, never correctness.
 __device__ __forceinline__ int xcd_remap(int b, int nwg) {

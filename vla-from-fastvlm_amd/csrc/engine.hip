@@ -12,7 +12,10 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <exception>
+#include <climits>
 #include <cmath>
+#include <new>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -1376,6 +1379,96 @@ int fv_adamw_clip_step(fv_handle* h, float* flat_params, const float* flat_grads
   if (!h || !hp) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step: null argument");
   return fv::launch_adamw_clip(flat_params, flat_grads, m, v, n, *hp, step, h->norm_scratch, grad_norm_out,
                                static_cast<hipStream_t>(s));
+}
+
+// ---- parameter groups of the fused step (csrc/optim_kernels.hip): the table is checked and cut into segments here, once
+struct fv_adamw_groups {
+  fv::AdamwGroupsTable t{};
+  void* dev = nullptr;   // ONE allocation: segments | groups | sums
+};
+
+int fv_adamw_groups_create(fv_handle* h, const fv_adamw_group* host_groups, int n_groups, int64_t n, fv_adamw_groups** out) {
+  HandleScope _hs(h);
+  if (!h || !host_groups || !out) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: null argument");
+  *out = nullptr;
+  if (n <= 0 || n % 4 != 0) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: n = %lld must be positive and a multiple of 4", (long long)n);
+  if (n_groups < 1 || n_groups > 65536) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: n_groups = %d outside 1 .. 65536", n_groups);
+  int64_t at = 0;
+  for (int i = 0; i < n_groups; ++i) {
+    const fv_adamw_group& g = host_groups[i];
+    if (g.reserved != 0) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d: reserved must be 0", i);
+    if (g.begin % 4 != 0 || g.end % 4 != 0)
+      return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d: [%lld, %lld) is not on multiples of 4 floats", i, (long long)g.begin, (long long)g.end);
+    if (g.end <= g.begin) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d: [%lld, %lld) is empty", i, (long long)g.begin, (long long)g.end);
+    if (g.begin != at)
+      return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d begins at %lld, %s the previous end %lld (groups must be sorted and tile [0, n) exactly)", i,
+                     (long long)g.begin, g.begin < at ? "overlapping" : "leaving a gap after", (long long)at);
+    if (g.end > n) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d ends at %lld, past n = %lld", i, (long long)g.end, (long long)n);
+    if (!(g.lr_scale >= 0.f) || !std::isfinite(g.lr_scale)) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d: lr_scale %g must be finite and >= 0", i, (double)g.lr_scale);
+    if (!(g.weight_decay >= 0.f) || !std::isfinite(g.weight_decay))
+      return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d: weight_decay %g must be finite and >= 0", i, (double)g.weight_decay);
+    at = g.end;
+  }
+  if (at != n) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: group %d ends at %lld, not at n = %lld", n_groups - 1, (long long)at, (long long)n);
+  // (a C entry point never throws: the table is counted first, refused above 2^28 segments -- 2^41 floats at the least -- and built inside a try block)
+  int64_t n_segs = 0;
+  for (int i = 0; i < n_groups; ++i) n_segs += (host_groups[i].end - host_groups[i].begin + FV_ADAMW_SEGMENT - 1) / FV_ADAMW_SEGMENT;
+  if (n_segs > ((int64_t)1 << 28)) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_create: %lld segments, more than 2^28", (long long)n_segs);
+  std::vector<fv::AdamwSeg> segs;
+  std::vector<fv::AdamwGroupDev> groups;
+  try {
+    segs.reserve((size_t)n_segs);
+    groups.resize((size_t)n_groups);
+  } catch (const std::exception&) {
+    return fv_fail(FV_ERR_STATE, "fv_adamw_groups_create: out of host memory for %lld segments", (long long)n_segs);
+  }
+  for (int i = 0; i < n_groups; ++i) {
+    const fv_adamw_group& g = host_groups[i];
+    fv::AdamwGroupDev& d = groups[(size_t)i];
+    d = fv::AdamwGroupDev{};
+    d.lr_scale = g.lr_scale; d.weight_decay = g.weight_decay; d.frozen = g.frozen != 0; d.seg_begin = (int32_t)segs.size();
+    for (int64_t b = g.begin; b < g.end; b += FV_ADAMW_SEGMENT)
+      segs.push_back(fv::AdamwSeg{b, (int32_t)std::min<int64_t>(FV_ADAMW_SEGMENT, g.end - b), i});    // (within the reserved capacity: no growth)
+    d.seg_count = (int32_t)segs.size() - d.seg_begin;
+  }
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const size_t seg_bytes = align_up(segs.size() * sizeof(fv::AdamwSeg)), grp_bytes = align_up(groups.size() * sizeof(fv::AdamwGroupDev));
+  const size_t sum_bytes = align_up((segs.size() + groups.size() + 1) * sizeof(float));
+  void* dev = nullptr;
+  FV_HIP_CHECK(hipMalloc(&dev, seg_bytes + grp_bytes + sum_bytes));
+  char* base = static_cast<char*>(dev);
+  hipError_t e = hipMemcpy(base, segs.data(), segs.size() * sizeof(fv::AdamwSeg), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(base + seg_bytes, groups.data(), groups.size() * sizeof(fv::AdamwGroupDev), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(base + seg_bytes + grp_bytes, 0, sum_bytes);   // (a frozen segment's partial is never written: it stays 0)
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(dev); return fv_hip_fail(e, "fv_adamw_groups_create: upload"); }
+  fv_adamw_groups* t = new (std::nothrow) fv_adamw_groups;
+  if (!t) { (void)hipFree(dev); return fv_fail(FV_ERR_STATE, "fv_adamw_groups_create: out of host memory"); }
+  t->dev = dev;
+  t->t.segs = reinterpret_cast<const fv::AdamwSeg*>(base);
+  t->t.groups = reinterpret_cast<const fv::AdamwGroupDev*>(base + seg_bytes);
+  t->t.sums = reinterpret_cast<float*>(base + seg_bytes + grp_bytes);
+  t->t.n = n; t->t.n_groups = n_groups; t->t.n_segs = (int)segs.size();
+  *out = t;
+  return FV_OK;
+}
+
+int fv_adamw_groups_destroy(fv_handle* h, fv_adamw_groups* groups) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "fv_adamw_groups_destroy: null handle");
+  if (!groups) return FV_OK;
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const hipError_t e = hipFree(groups->dev);    // (waits for a step still in flight on the table)
+  delete groups;
+  if (e != hipSuccess) return fv_hip_fail(e, "fv_adamw_groups_destroy: hipFree");
+  return FV_OK;
+}
+
+int fv_adamw_clip_step_groups(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, int64_t n, const fv_adamw_hparams* hp,
+                              const fv_adamw_groups* groups, int64_t step, float* grad_norm_out, float* group_norms_out, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !hp || !groups) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_groups: null argument");
+  return fv::launch_adamw_clip_groups(flat_params, flat_grads, m, v, n, *hp, groups->t, step, grad_norm_out, group_norms_out, static_cast<hipStream_t>(s));
 }
 
 

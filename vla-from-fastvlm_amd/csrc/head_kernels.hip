@@ -261,12 +261,9 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   if (hp.max_grad_norm > 0.f) coef *= fminf(hp.max_grad_norm / (norm + 1e-6f), 1.0f);
   if (i == 0 && norm_out) *norm_out = norm;
   if (i >= n) return;
-  const float gi = g[i] * coef;
-  const float pi = p[i] * (1.0f - hp.lr * hp.weight_decay);
-  const float mi = m[i] * hp.beta1 + gi * (1.0f - hp.beta1);
-  const float vi = v[i] * hp.beta2 + gi * gi * (1.0f - hp.beta2);
-  const float denom = sqrtf(vi) / bc2_sqrt + hp.eps;
-  p[i] = pi - (hp.lr / bc1) * mi / denom;
+  float pi = p[i], mi = m[i], vi = v[i];
+  adamw_update(pi, g[i], mi, vi, coef, hp.lr, hp.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);   // (shared with adamw_groups_kernel: common.h)
+  p[i] = pi;
   m[i] = mi;
   v[i] = vi;
 }

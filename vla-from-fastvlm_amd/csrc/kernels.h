@@ -306,4 +306,16 @@ int launch_axpy(float* y, const float* x, int64_t n, const float* scale_dev, hip
 int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,
                       int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s);
 
+// parameter groups of the fused step (optim_kernels.hip).  The host cuts every group into segments of at most FV_ADAMW_SEGMENT floats: a segment never
+// straddles a group, every boundary is a multiple of 4 floats, the segments of a group are consecutive.  One block per segment in every kernel.
+struct AdamwSeg { int64_t begin; int32_t len, group; };                                                   // 16 bytes
+struct AdamwGroupDev { float lr_scale, weight_decay; int32_t frozen, seg_begin, seg_count, pad[3]; };     // 32 bytes
+struct AdamwGroupsTable {
+  const AdamwSeg* segs; const AdamwGroupDev* groups;   // device
+  float* sums;                                         // device: [n_segs] segment partials | [n_groups] group sums | [1] total over the non-frozen groups
+  int64_t n; int n_groups, n_segs;
+};
+int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
+                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s);
+
 }  // namespace fv

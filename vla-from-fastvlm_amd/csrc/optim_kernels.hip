@@ -1,0 +1,111 @@
+// optim_kernels.hip -- the fused clip + AdamW step over PARAMETER GROUPS (fv_adamw_clip_step_groups): per group a learning-rate factor, a weight decay
+// and a frozen flag; one global clip norm over the non-frozen elements, and a gradient norm per group.
+//   torch.optim.AdamW's param_groups + clip_grad_norm_ over the parameters with requires_grad (the reference's step body, training/trainer.py:60-66,178-180,
+//   knows one group only: it trains a 3 M-parameter head).
+// The table (kernels.h AdamwGroupsTable) is built once on the host: every group cut into segments of <= FV_ADAMW_SEGMENT floats, all boundaries multiples of
+// 4 floats -- so every access below is a 16-byte one, a block reads its group's settings once (no per-element search) and a frozen segment's block leaves
+// before it has touched p, g, m or v.  Both kernels over the data move what adamw_kernel / sumsq_kernel move: 4 + 28 bytes per element.
+// Summation order is fixed (per-thread strided sums, wave butterfly, four wave sums added pairwise): no float atomics, two runs give the same bits.
+#include "kernels.h"
+
+namespace fv {
+namespace {
+
+__device__ __forceinline__ float block_sum_256(float s, float* red) {   // every thread returns the block's sum
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// partial[segment] <- sum of squares of the segment's gradient (frozen segments: not read, partial stays 0 as the table's creation left it)
+__global__ __launch_bounds__(256) void sumsq_segments_kernel(const float* __restrict__ g, const AdamwSeg* __restrict__ segs, const AdamwGroupDev* __restrict__ groups,
+                                                              float* __restrict__ partial) {
+  __shared__ float red[4];
+  const AdamwSeg sg = segs[blockIdx.x];
+  if (groups[sg.group].frozen) return;    // (uniform over the block)
+  const float4* g4 = reinterpret_cast<const float4*>(g + sg.begin);
+  const int n4 = sg.len >> 2;
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    const float4 x = g4[i];
+    s0 += x.x * x.x; s1 += x.y * x.y; s2 += x.z * x.z; s3 += x.w * x.w;
+  }
+  const float s = block_sum_256((s0 + s1) + (s2 + s3), red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// phase 0 (one block per group): group_sum[g] <- its segments' partials, thread t taking segments t, t + 256, ... in rising order; 0 for a frozen group.
+// phase 1 (one block):           group_sum[n_groups] <- the non-frozen groups' sums, thread t taking groups t, t + 256, ... in rising order.
+__global__ __launch_bounds__(256) void sumsq_groups_fold_kernel(const AdamwGroupDev* __restrict__ groups, int n_groups, const float* __restrict__ partial,
+                                                                 float* __restrict__ group_sum, int phase) {
+  __shared__ float red[4];
+  float s = 0.f;
+  if (phase == 0) {
+    const AdamwGroupDev gr = groups[blockIdx.x];
+    if (!gr.frozen)
+      for (int i = threadIdx.x; i < gr.seg_count; i += 256) s += partial[gr.seg_begin + i];
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) group_sum[blockIdx.x] = gr.frozen ? 0.f : s;
+  } else {
+    for (int i = threadIdx.x; i < n_groups; i += 256)
+      if (!groups[i].frozen) s += group_sum[i];
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0) group_sum[n_groups] = s;
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                            fv_adamw_hparams hp, float bc1, float bc2_sqrt, const AdamwSeg* __restrict__ segs,
+                                                            const AdamwGroupDev* __restrict__ groups, const float* __restrict__ group_sum, int n_groups,
+                                                            float* __restrict__ norm_out, float* __restrict__ group_norms_out) {
+  const AdamwSeg sg = segs[blockIdx.x];
+  const AdamwGroupDev gr = groups[sg.group];
+  // torch clip_grad_norm_ over the non-frozen elements: coef = clamp(max_norm / (norm + 1e-6), max = 1), as adamw_kernel
+  const float norm = sqrtf(group_sum[n_groups]) * hp.grad_scale;
+  float coef = hp.grad_scale;
+  if (hp.max_grad_norm > 0.f) coef *= fminf(hp.max_grad_norm / (norm + 1e-6f), 1.0f);
+  if (threadIdx.x == 0) {
+    if (blockIdx.x == 0 && norm_out) *norm_out = norm;
+    if (group_norms_out && (int)blockIdx.x == gr.seg_begin) group_norms_out[sg.group] = gr.frozen ? 0.f : sqrtf(group_sum[sg.group]) * hp.grad_scale;
+  }
+  if (gr.frozen) return;     // p, m, v keep their bits
+  const float lr = hp.lr * gr.lr_scale;
+  float4* p4 = reinterpret_cast<float4*>(p + sg.begin);
+  float4* m4 = reinterpret_cast<float4*>(m + sg.begin);
+  float4* v4 = reinterpret_cast<float4*>(v + sg.begin);
+  const float4* g4 = reinterpret_cast<const float4*>(g + sg.begin);
+  const int n4 = sg.len >> 2;
+  for (int i = threadIdx.x; i < n4; i += 256) {
+    float4 pi = p4[i], mi = m4[i], vi = v4[i];
+    const float4 gi = g4[i];
+    adamw_update(pi.x, gi.x, mi.x, vi.x, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
+    adamw_update(pi.y, gi.y, mi.y, vi.y, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
+    adamw_update(pi.z, gi.z, mi.z, vi.z, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
+    adamw_update(pi.w, gi.w, mi.w, vi.w, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
+    p4[i] = pi; m4[i] = mi; v4[i] = vi;
+  }
+}
+
+}  // namespace
+
+int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
+                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s) {
+  if (!p || !g || !m || !v || !t.segs || !t.groups || !t.sums) return fv_fail(FV_ERR_ARG, "adamw groups: null pointer");
+  if (step < 1) return fv_fail(FV_ERR_ARG, "adamw groups: step must be positive");
+  if (n != t.n) return fv_fail(FV_ERR_ARG, "adamw groups: n = %lld, the table was built for %lld", (long long)n, (long long)t.n);
+  if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return fv_fail(FV_ERR_ARG, "adamw groups: buffers must be 16-byte aligned");
+  if (t.n_segs <= 0 || t.n_groups <= 0) return fv_fail(FV_ERR_ARG, "adamw groups: empty table");
+  float* group_sum = t.sums + t.n_segs;
+  hipLaunchKernelGGL(sumsq_segments_kernel, dim3(t.n_segs), dim3(256), 0, s, g, t.segs, t.groups, t.sums);
+  hipLaunchKernelGGL(sumsq_groups_fold_kernel, dim3(t.n_groups), dim3(256), 0, s, t.groups, t.n_groups, (const float*)t.sums, group_sum, 0);
+  hipLaunchKernelGGL(sumsq_groups_fold_kernel, dim3(1), dim3(256), 0, s, t.groups, t.n_groups, (const float*)t.sums, group_sum, 1);
+  const float bc1 = (float)(1.0 - pow((double)hp.beta1, (double)step));
+  const float bc2 = (float)sqrt(1.0 - pow((double)hp.beta2, (double)step));
+  hipLaunchKernelGGL(adamw_groups_kernel, dim3(t.n_segs), dim3(256), 0, s, p, g, m, v, hp, bc1, bc2, t.segs, t.groups, (const float*)group_sum, t.n_groups,
+                     grad_norm_out, group_norms_out);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+}  // namespace fv

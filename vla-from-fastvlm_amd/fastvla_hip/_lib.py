@@ -55,6 +55,13 @@ class AdamWHParams(C.Structure):
                 ("weight_decay", C.c_float), ("max_grad_norm", C.c_float), ("grad_scale", C.c_float)]
 
 
+class AdamWGroup(C.Structure):      # fv_adamw_group: 32 bytes
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr_scale", C.c_float), ("weight_decay", C.c_float), ("frozen", C.c_int32), ("reserved", C.c_int32)]
+
+
+FV_ADAMW_SEGMENT = 8192
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
@@ -137,6 +144,9 @@ SIGNATURES = {
     "fv_profile": (_i, [_vp, _i]),
     "fv_profile_read": (_i, [_vp, C.POINTER(ProfileEntry), C.POINTER(GemmProfile), _i, C.POINTER(_i)]),
     "fv_adamw_clip_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(AdamWHParams), _i64, _vp, _vp]),
+    "fv_adamw_groups_create": (_i, [_vp, C.POINTER(AdamWGroup), _i, _i64, C.POINTER(_vp)]),
+    "fv_adamw_groups_destroy": (_i, [_vp, _vp]),
+    "fv_adamw_clip_step_groups": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(AdamWHParams), _vp, _i64, _vp, _vp, _vp]),
 }
 
 # TEST-ONLY op-level entry points (include/fastvla_hip_testops.h, tests/_native/libfastvla_hip_testops.so): not part of the product library

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -27,6 +28,38 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+class AdamWGroups:
+    """Owner of one fv_adamw_groups table (FastVLAEngine.adamw_groups).  ONE step may be in flight per table: it holds the step's partial sums."""
+
+    def __init__(self, engine: "FastVLAEngine", groups, n: int):
+        arr = (_lib.AdamWGroup * max(1, len(groups)))()
+        for i, g in enumerate(groups):
+            if isinstance(g, dict):
+                g = (g["begin"], g["end"], g.get("lr_scale", 1.0), g.get("weight_decay", 0.0), g.get("frozen", False))
+            arr[i] = _lib.AdamWGroup(int(g[0]), int(g[1]), float(g[2]), float(g[3]), int(bool(g[4])), 0)
+        self._engine, self.n, self.n_groups = engine, int(n), len(groups)
+        out = C.c_void_p()
+        with torch.cuda.device(engine.device):
+            _lib.check(engine.lib.fv_adamw_groups_create(engine.h, arr, len(groups), int(n), C.byref(out)), "fv_adamw_groups_create", engine.h)
+        self._h = out.value
+
+    def handle(self) -> int:
+        if not self._h:
+            raise _lib.FastVLAHipError("this parameter-group table has been closed")
+        return self._h
+
+    def close(self) -> None:
+        h, self._h = getattr(self, "_h", None), None
+        if h and getattr(self._engine, "h", None):      # (after the engine's fv_destroy only the host record is left: dropped with this object)
+            _lib.check(self._engine.lib.fv_adamw_groups_destroy(self._engine.h, h), "fv_adamw_groups_destroy", self._engine.h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class FastVLAEngine:
@@ -81,6 +114,8 @@ class FastVLAEngine:
 
     def close(self):
         if getattr(self, "h", None):
+            for t in list(getattr(self, "_group_tables", ())):      # parameter-group tables go before the handle
+                t.close()
             self.lib.fv_destroy(self.h)
             self.h = None
 
@@ -801,11 +836,32 @@ class FastVLAEngine:
                   for i in range(n.value)]
         return fams, shapes
 
+    def adamw_groups(self, groups, n: int) -> "AdamWGroups":
+        """The device table of a parameter-group list (fv_adamw_groups_create): groups = dicts (or tuples) of begin, end, lr_scale, weight_decay, frozen that
+        tile [0, n) on multiples of 4 floats -- fastvla_hip.optim.build_param_groups makes them from a layout.  The returned object destroys its table
+        (close(), or when it is collected); pass it as adamw_step(..., groups=)."""
+        t = AdamWGroups(self, groups, n)
+        self.__dict__.setdefault("_group_tables", weakref.WeakSet()).add(t)
+        return t
+
     def adamw_step(self, flat_params, flat_grads, m, v, step: int, *, lr: float, betas=(0.9, 0.95), eps: float = 1e-8,
                    weight_decay: float = 1e-4, max_grad_norm: float = 1.0, grad_scale: float = 1.0,
-                   grad_norm_out: Optional[torch.Tensor] = None) -> None:
+                   grad_norm_out: Optional[torch.Tensor] = None, groups: Optional["AdamWGroups"] = None,
+                   group_norms_out: Optional[torch.Tensor] = None) -> None:
+        """fused clip + AdamW on the flat buffers.  groups=None: fv_adamw_clip_step, one learning rate and one decay for the whole buffer.  With a table from
+        adamw_groups(): fv_adamw_clip_step_groups -- lr and decay per group (`weight_decay` here is then ignored: the table carries the decays), frozen groups
+        untouched, group_norms_out (n_groups f32, device) <- every group's gradient norm."""
         hp = _lib.AdamWHParams(lr, betas[0], betas[1], eps, weight_decay, max_grad_norm if max_grad_norm else 0.0,
                                grad_scale)
+        if groups is not None:
+            if group_norms_out is not None and (group_norms_out.dtype != torch.float32 or group_norms_out.numel() < groups.n_groups):
+                raise ValueError(f"group_norms_out must hold {groups.n_groups} float32 values")
+            _lib.check(self.lib.fv_adamw_clip_step_groups(self.h, flat_params.data_ptr(), flat_grads.data_ptr(), m.data_ptr(), v.data_ptr(), flat_params.numel(),
+                                                          C.byref(hp), groups.handle(), step, _ptr(grad_norm_out), _ptr(group_norms_out), _stream()),
+                       "fv_adamw_clip_step_groups", self.h)
+            return
+        if group_norms_out is not None:
+            raise ValueError("group_norms_out needs groups=")
         _lib.check(self.lib.fv_adamw_clip_step(self.h, flat_params.data_ptr(), flat_grads.data_ptr(), m.data_ptr(),
                                                v.data_ptr(), flat_params.numel(), C.byref(hp), step,
                                                _ptr(grad_norm_out), _stream()), "fv_adamw_clip_step")

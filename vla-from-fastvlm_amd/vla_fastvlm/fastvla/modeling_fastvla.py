@@ -29,7 +29,8 @@ class FastVLAPolicy(nn.Module):
 
     def enable_backbone_training(self, bucket_min_numel: int = 1 << 22, tower: Optional[bool] = None, lora_rank: Optional[int] = None,
                                  lora_alpha: Optional[float] = None, lora_targets=None, lora_seed: int = 0, lora_direct: Optional[bool] = None,
-                                 lora_dora: Optional[bool] = None, lora_rslora: Optional[bool] = None):
+                                 lora_dora: Optional[bool] = None, lora_rslora: Optional[bool] = None, lr_scales: Optional[Dict] = None, no_decay=None,
+                                 layer_decay: Optional[float] = None, lora_plus_ratio: Optional[float] = None, freeze=None):
         """Extension of this build: fine-tune the Qwen2 decoder + mm_projector together with the action expert
         (image tokens spliced); tower=True (or FASTVLA_TRAIN_TOWER=1) trains the FastViT-HD tower too, in its inference form, otherwise it stays
         frozen.  Explicit on purpose: the reference's `freeze_backbone=False` trains nothing but the head either (model/fastvlm_adapter.py:501),
@@ -47,7 +48,15 @@ class FastVLAPolicy(nn.Module):
         lora_rslora=True (or FASTVLA_LORA_RSLORA=1): rank-stabilised scaling, W0 + (lora_alpha / sqrt(r)) B A.  lora_dora=True (or FASTVLA_LORA_DORA=1):
         weight-decomposed LoRA (PEFT's use_dora) -- a trained magnitude per output row over the direction W0 + s B A, initialised to the row norms so the
         adapted model starts as the base model.  Both ARE properties of the adapters: they are recorded with {rank, alpha, targets} wherever those travel.
-        DoRA runs on the projected backward only: lora_dora=True with lora_direct=True raises ValueError."""
+        DoRA runs on the projected backward only: lora_dora=True with lora_direct=True raises ValueError.
+
+        Parameter groups of the optimiser step (fastvla_hip/optim.py; fv_adamw_clip_step_groups), each with an environment twin an explicit argument beats:
+        lr_scales={"decoder": 0.1, "tower": 0.1} (FASTVLA_LR_SCALES="decoder=0.1,tower=0.1") -- learning-rate factors per section (head, projector, embedding,
+        decoder, tower, adapters); no_decay=("vectors",) (FASTVLA_NO_DECAY) -- sections, or the class "vectors" (norm weights, biases, layer scales, DoRA
+        magnitudes), without weight decay; layer_decay=d (FASTVLA_LAYER_DECAY) -- decoder layer l of L, and its adapters, x d^(L-1-l), the embedding x d^L;
+        lora_plus_ratio=r (FASTVLA_LORA_PLUS_RATIO; needs LoRA, ValueError otherwise) -- lora_B at r times lora_A's rate; freeze=("embedding",)
+        (FASTVLA_FREEZE) -- sections or "vectors" left untouched and out of the clip norm.  Factors multiply.  With none of them the step is the single-group
+        one, bit for bit.  The step then also returns "group_grad_norms" (a device tensor, one norm per group) and "group_names" (their labels)."""
         from fastvla_hip import lora as _lora
         if tower is None:
             tower = os.environ.get("FASTVLA_TRAIN_TOWER", "0") == "1"
@@ -79,10 +88,23 @@ class FastVLAPolicy(nn.Module):
             raise RuntimeError(f"backbone training is already running with lora={self._unfrozen.lora}: ask for LoRA on the first call")
         if self._unfrozen is not None and lcfg is not None and lora_direct is not None and bool(lora_direct) != self._unfrozen.lora_direct:
             raise RuntimeError(f"backbone training is already running with lora_direct={self._unfrozen.lora_direct}: ask for the backward mode on the first call")
-        if self._unfrozen is None:
+        from fastvla_hip import optim as _optim
+        given = {k: v for k, v in (("lr_scales", lr_scales), ("no_decay", no_decay), ("layer_decay", layer_decay), ("lora_plus_ratio", lora_plus_ratio),
+                                   ("freeze", freeze)) if v is not None}
+        if self._unfrozen is not None:
+            if given and _optim.normalize_options(**given) != self._unfrozen.optim:
+                raise RuntimeError(f"backbone training is already running with the optimiser options {self._unfrozen.optim}: ask for parameter groups on the first call")
+        else:
+            opts = {**_optim.options_from_env(), **_optim.normalize_options(**given)}      # (an explicit argument beats its environment twin)
+            for k, v in given.items():       # ... also when it switches the twin OFF (an empty tuple / dict)
+                if k not in _optim.normalize_options(**{k: v}):
+                    opts.pop(k, None)
+            if "lora_plus_ratio" in opts and lcfg is None:
+                raise ValueError("lora_plus_ratio / FASTVLA_LORA_PLUS_RATIO need LoRA adapters (lora_rank or FASTVLA_LORA_RANK)")
             from ..training.unfrozen import UnfrozenState
             direct = lcfg is not None and (_lora.direct_from_env() if lora_direct is None else bool(lora_direct))
-            self._unfrozen = UnfrozenState(self, bucket_min_numel=bucket_min_numel, train_tower=bool(tower), lora=lcfg, lora_seed=lora_seed, lora_direct=direct)
+            self._unfrozen = UnfrozenState(self, bucket_min_numel=bucket_min_numel, train_tower=bool(tower), lora=lcfg, lora_seed=lora_seed, lora_direct=direct,
+                                           optim=opts)
         return self._unfrozen
 
     def merge_lora(self) -> None:
@@ -159,21 +181,28 @@ class FastVLAPolicy(nn.Module):
         return st
 
     def load_optimizer_state(self, m: torch.Tensor, v: torch.Tensor, step: int, flat: Optional[torch.Tensor] = None,
-                             train_tower: Optional[bool] = None, lora: Optional[Dict] = None) -> None:
+                             train_tower: Optional[bool] = None, lora: Optional[Dict] = None, optim: Optional[Dict] = None) -> None:
         """Restore AdamW moments and the bias-correction step (Trainer._load_checkpoint; reference trainer.py:257-262
         restores them through accelerator.load_state).  train_tower: what optimizer.pt recorded about the run being resumed (None: a round-5 file, which
-        did not record it -- FASTVLA_TRAIN_TOWER decides then, as before)."""
+        did not record it -- FASTVLA_TRAIN_TOWER decides then, as before).  optim: the parameter-group options optimizer.pt recorded ({} = none): a run
+        that steps with other options raises ValueError naming both."""
         head_numel = sum(p.numel() for p in self.model.head_parameters())
         if self._unfrozen is None and (train_tower is not None or lora is not None or m.numel() > 2 * head_numel):
             # moments of a whole-backbone run (training/unfrozen.py writes one flat m / v over every trainable tensor): the run resumes unfrozen,
             # training what the checkpointed run trained (lora: optimizer.pt's record of a LoRA run -- its m / v / flat cover the trainable buffer)
+            # (optim: the run's parameter-group options as optimizer.pt recorded them -- they come back with the run unless this one asks for others, which raises below)
+            from fastvla_hip import optim as _optim
+            okw = _optim.explicit_kwargs(optim) if optim and not _optim.options_from_env() else {}
             if lora is not None:
                 self.enable_backbone_training(lora_rank=lora["rank"], lora_alpha=lora["alpha"], lora_targets=lora["targets"],
-                                              lora_dora=bool(lora.get("dora")), lora_rslora=bool(lora.get("rslora")))
+                                              lora_dora=bool(lora.get("dora")), lora_rslora=bool(lora.get("rslora")), **okw)
             else:
-                self.enable_backbone_training(tower=train_tower)
+                self.enable_backbone_training(tower=train_tower, **okw)
         if self._unfrozen is not None:
             u = self._unfrozen
+            if optim is not None:      # (None: a caller that does not know what the checkpointed run used)
+                from ..utils.checkpoint import check_resume_optim
+                check_resume_optim(optim, u.optim)
             if m.numel() != u.m.numel():
                 raise ValueError(f"optimizer state has {m.numel()} elements, the trainable tensors of this run {u.m.numel()} (tower trained in one run and frozen in the other?)")
             u.m.copy_(m.to(u.m.device))

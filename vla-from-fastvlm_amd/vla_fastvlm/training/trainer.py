@@ -129,7 +129,8 @@ class Trainer:
         flat = core.materialize(self.device)
         if self._resume_opt is not None and hasattr(self.model, "load_optimizer_state"):
             self.model.load_optimizer_state(self._resume_opt["m"], self._resume_opt["v"], int(self._resume_opt["step"]), flat=self._resume_opt.get("flat"),
-                                            train_tower=self._resume_opt.get("train_tower"), **({"lora": self._resume_opt["lora"]} if self._resume_opt.get("lora") else {}))
+                                            train_tower=self._resume_opt.get("train_tower"), **({"lora": self._resume_opt["lora"]} if self._resume_opt.get("lora") else {}),
+                                            optim=self._resume_opt.get("optim") or {})
             self._resume_opt = None
         un = getattr(self.model, "_unfrozen", None)
         if un is not None:
@@ -222,15 +223,8 @@ class Trainer:
                                    include_backbone=self.save_backbone_weights or self._backbone_must_travel())
         st = getattr(self.model, "_opt_state", None)
         if st is not None:
-            rec = {"m": st["m"].cpu(), "v": st["v"].cpu(), "step": st["step"], "global_step": self.global_step, "update_step": self.update_step}
-            un = getattr(self.model, "_unfrozen", None)
-            if un is not None:
-                # the fp32 MASTER of an unfrozen run: the VLM tensors of policy_state_dict.pt come back through the engine's bf16 operand copies, and a master
-                # rebuilt from those has lost the low bits every later update (~1e-3 of a bf16 ulp) lives in
-                rec["flat"] = un.trainable.cpu()     # (a LoRA run: head + projector + adapters; its frozen master is the base checkpoint)
-                rec["train_backbone"], rec["train_tower"] = True, bool(un.train_tower)   # what the run trains comes back from the checkpoint, not from the environment
-                if un.lora is not None:
-                    rec["lora"] = dict(un.lora)
+            from ..utils.checkpoint import optimizer_record
+            rec = optimizer_record(st, getattr(self.model, "_unfrozen", None), self.global_step, self.update_step)
             torch.save(rec, d / "optimizer.pt")
 
     def _load_checkpoint(self, path: str) -> None:
@@ -238,6 +232,7 @@ class Trainer:
         if not p.exists():
             raise FileNotFoundError(f"Checkpoint path {path} does not exist.")
         state = torch.load(p / "policy_state_dict.pt", map_location="cpu")
+        resume_opt = torch.load(p / "optimizer.pt", map_location="cpu") if (p / "optimizer.pt").is_file() else None
         from ..utils.checkpoint import BACKBONE_PREFIX, EXTRA_STATE_MARKS
         vlm = {k[len(BACKBONE_PREFIX):]: v for k, v in state.items() if k.startswith(BACKBONE_PREFIX)}
         if vlm:
@@ -250,7 +245,7 @@ class Trainer:
                 self.model.enable_backbone_training(tower=un.train_tower, **({"lora_rank": un.lora["rank"], "lora_alpha": un.lora["alpha"], "lora_targets": un.lora["targets"],
                                                                                 "lora_direct": un.lora_direct, "lora_dora": bool(un.lora.get("dora")),
                                                                                 "lora_rslora": bool(un.lora.get("rslora"))}
-                                                                               if un.lora is not None else {}))
+                                                                               if un.lora is not None else {}), **un.optim_kwargs())
         own = self.model.state_dict()
         # `.io_norm.` / splice-mode keys exist in state_dict() only while they are on, so a freshly built model does not list them -- let them
         # through (FastVLMBackbone._load_from_state_dict re-applies them)
@@ -261,8 +256,8 @@ class Trainer:
             self.model.model.backbone.splice_image_tokens = bool(ex["splice_image_tokens"])
         if ex.get("lora"):
             from ..utils.checkpoint import load_lora_adapters
-            load_lora_adapters(self.model, p, ex["lora"])
-        if (p / "optimizer.pt").is_file():
-            self._resume_opt = torch.load(p / "optimizer.pt", map_location="cpu")  # applied by _sync_replicas()
+            load_lora_adapters(self.model, p, ex["lora"], optim=resume_opt.get("optim") if resume_opt else None)
+        if resume_opt is not None:
+            self._resume_opt = resume_opt  # applied by _sync_replicas()
             self.global_step = int(self._resume_opt.get("global_step", 0))
             self.update_step = int(self._resume_opt.get("update_step", self._resume_opt.get("step", 0)))

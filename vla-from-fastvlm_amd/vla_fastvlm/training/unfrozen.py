@@ -25,6 +25,10 @@ formed, the full-size gradient buffer is never allocated (`self.g is None`) and 
 Variants (keys of `lora`, present only when true): "rslora" -- s = alpha / sqrt(rank); "dora" -- every target also trains a magnitude per output row,
 W' = diag(m / ||V||_row) V over V = W0 + s B A (the norm a constant in the backward, as in PEFT).  m starts as the row norms (fv_train_lora_init_magnitude), so
 the adapted model starts as the base model bit for bit; the step is the projected one (the commit refreshes the norms the projection reads); not with lora_direct.
+
+Parameter groups (`optim={"lr_scales", "no_decay", "layer_decay", "lora_plus_ratio", "freeze"}`, fastvla_hip/optim.py): with one of them set the optimiser step is
+fv_adamw_clip_step_groups over a table built from the trainable buffer's layout -- a learning-rate factor, a weight decay and a frozen flag per group, ONE clip
+norm over the non-frozen elements -- and the step also returns every group's gradient norm.  With none set the step is fv_adamw_clip_step, as before.
 """
 from __future__ import annotations
 
@@ -39,7 +43,14 @@ from .dp import BucketedGradExchange, GradExchange
 
 class UnfrozenState:
     def __init__(self, policy, bucket_min_numel: int = 1 << 22, train_tower: bool = False, lora: Optional[Dict] = None, lora_seed: int = 0,
-                 lora_direct: bool = False):
+                 lora_direct: bool = False, optim: Optional[Dict] = None):
+        from fastvla_hip import optim as _optim
+        self.optim = _optim.normalize_options(**(optim or {}))     # {} = the single-group step; what optimizer.pt records and a resume compares
+        if "lora_plus_ratio" in self.optim and lora is None:
+            raise ValueError("lora_plus_ratio needs LoRA adapters (lora_rank)")
+        self._group_table: Optional[tuple] = None                  # (weight decay, device table): built on the first step that uses it
+        self.group_names: Optional[List[str]] = None
+        self.group_norms: Optional[torch.Tensor] = None
         m = policy.model
         bb = m.backbone
         self.policy = policy
@@ -113,6 +124,32 @@ class UnfrozenState:
             self.v.copy_(r["v"].to(dev))
             self.step_count = int(r["step"])
             policy._opt_state["step"] = self.step_count
+
+    # ------------------------------------------------------------------ parameter groups
+    def optim_kwargs(self) -> Dict:
+        """the options as enable_backbone_training's keywords, every one explicit (an unset one as its empty value, so no environment twin fills it in)"""
+        from fastvla_hip import optim as _optim
+        return _optim.explicit_kwargs(self.optim)
+
+    def param_groups(self, weight_decay: float):
+        """-> (groups, names) of the trainable buffer under this run's options (fastvla_hip.optim.build_param_groups over its layout)"""
+        from fastvla_hip import optim as _optim
+        tensors = self.lora_tensors if self.lora is not None else self.tensors
+        return _optim.build_param_groups(tensors, weight_decay=weight_decay, total=self.trainable.numel(), **self.optim)
+
+    def _groups_for(self, weight_decay: float):
+        """the device table for this weight decay.  The table carries the groups' decays as absolute values, so it is built on the first step and REBUILT when a
+        later step passes another decay -- a configuration call each time (fv_adamw_groups_destroy / _create: they allocate and synchronise the device).  With a
+        constant decay, which is what Trainer passes, the step allocates nothing and reads nothing back; a loop that schedules the decay pays a synchronisation
+        per change."""
+        key = float(weight_decay)
+        if self._group_table is None or self._group_table[0] != key:
+            if self._group_table is not None:
+                self._group_table[1].close()
+            groups, names = self.param_groups(key)
+            self._group_table = (key, self.eng.adamw_groups(groups, self.trainable.numel()))
+            self.group_names, self.group_norms = names, torch.zeros(len(groups), device=self.eng.device)
+        return self._group_table[1]
 
     # ------------------------------------------------------------------ views / export
     def named_backbone_tensors(self) -> Dict[str, torch.Tensor]:
@@ -289,8 +326,13 @@ class UnfrozenState:
             self.step_count += 1
             self.micro = 0
             scale /= eng.train_loss_scale()      # every gradient of fv_train_forward_backward carries the loss scale (2^12 by default)
-            eng.adamw_step(self.trainable, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                           max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm)
+            if self.optim:       # parameter groups: lr / decay per group, frozen groups untouched, every group's norm (no host read: a device tensor)
+                table = self._groups_for(weight_decay)
+                eng.adamw_step(self.trainable, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                               max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm, groups=table, group_norms_out=self.group_norms)
+            else:
+                eng.adamw_step(self.trainable, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                               max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm)
             self.lora_adapters_zero = False
             # bf16 operand copies (and their transposes) follow the master (LoRA: W0 + s B A); per-image decoder prefixes / per-prompt features computed with
             # the OLD weights must not serve an eval between steps
@@ -306,4 +348,6 @@ class UnfrozenState:
                     eng.train_set_options(loss_scale_log2=self.loss_scale_log2, keep=True)
                     warnings.warn(f"{n} fp16 gradient-operand groups saturated in the last {self.saturation_check_every} steps: loss scale lowered to 2^{self.loss_scale_log2}")
         out["grad_norm"] = self.norm[0]
+        if self.optim and self.group_norms is not None:
+            out["group_grad_norms"], out["group_names"] = self.group_norms, self.group_names     # one norm per group (a device tensor) and the groups' labels
         return out

@@ -42,6 +42,31 @@ def read_extras(checkpoint_dir) -> dict:
 EXTRA_STATE_MARKS = (".io_norm.", ".splice_image_tokens")
 
 
+def optimizer_record(st: dict, un, global_step: int, update_step: int) -> dict:
+    """What Trainer writes to optimizer.pt: AdamW's moments and step, the loop's counters, and for an unfrozen run (`un`, training/unfrozen.py UnfrozenState) its
+    trainable fp32 buffer and what it trains.  "optim" -- the parameter-group options of the run (fastvla_hip/optim.py) -- is there ONLY when one is set: a
+    plain run's file is byte for byte what it was."""
+    rec = {"m": st["m"].cpu(), "v": st["v"].cpu(), "step": st["step"], "global_step": global_step, "update_step": update_step}
+    if un is not None:
+        # the fp32 MASTER of an unfrozen run: the VLM tensors of policy_state_dict.pt come back through the engine's bf16 operand copies, and a master
+        # rebuilt from those has lost the low bits every later update (~1e-3 of a bf16 ulp) lives in
+        rec["flat"] = un.trainable.cpu()     # (a LoRA run: head + projector + adapters; its frozen master is the base checkpoint)
+        rec["train_backbone"], rec["train_tower"] = True, bool(un.train_tower)   # what the run trains comes back from the checkpoint, not from the environment
+        if un.lora is not None:
+            rec["lora"] = dict(un.lora)
+        if getattr(un, "optim", None):
+            rec["optim"] = dict(un.optim)
+    return rec
+
+
+def check_resume_optim(recorded, current) -> None:
+    """A resumed run must step the way the checkpointed one did: other parameter-group options (a missing record = none) raise, naming both."""
+    recorded, current = dict(recorded or {}), dict(current or {})
+    if recorded != current:
+        raise ValueError(f"optimizer.pt was written by a run with the optimiser options {recorded or 'none'}, this run uses {current or 'none'}: "
+                         "resume with the checkpoint's options (lr_scales / no_decay / layer_decay / lora_plus_ratio / freeze or their FASTVLA_* twins)")
+
+
 def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None = None) -> FastVLAPolicy:
     root = Path(checkpoint_dir)
     cfg_path, sd_path = root / "policy_config.json", root / "policy_state_dict.pt"
@@ -70,14 +95,19 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
     return policy
 
 
-def load_lora_adapters(policy: FastVLAPolicy, checkpoint_dir, lora_extras: dict) -> None:
+def load_lora_adapters(policy: FastVLAPolicy, checkpoint_dir, lora_extras: dict, optim: dict | None = None) -> None:
     """Put the policy into LoRA mode as hip_extras.json records it and load the adapter file it names.  Raises when the file (or a tensor in it) is missing:
-    running the base model in place of the fine-tuned one silently is the one thing this must not do."""
+    running the base model in place of the fine-tuned one silently is the one thing this must not do.  optim: the parameter-group options of the run being
+    resumed (optimizer.pt's record; Trainer passes it): used when THIS call is what switches LoRA mode on and no FASTVLA_* twin asks for others."""
     f = Path(checkpoint_dir) / lora_extras.get("file", LORA_FILE)
     if not f.is_file():
         raise FileNotFoundError(f"{Path(checkpoint_dir) / EXTRAS_FILE} records LoRA adapters (rank {lora_extras.get('rank')}) in '{f.name}', which is not there")
     # (a policy that is already in LoRA mode keeps the backward mode it was started in and just receives the adapters)
     mode = {} if getattr(policy, "_unfrozen", None) is not None else {"lora_direct": bool(lora_extras.get("direct", False))}
+    if optim and getattr(policy, "_unfrozen", None) is None:
+        from fastvla_hip import optim as _optim
+        if not _optim.options_from_env():
+            mode.update(_optim.explicit_kwargs(optim))
     un = policy.enable_backbone_training(lora_rank=int(lora_extras["rank"]), lora_alpha=float(lora_extras["alpha"]), lora_targets=list(lora_extras["targets"]),
                                          lora_dora=bool(lora_extras.get("dora")), lora_rslora=bool(lora_extras.get("rslora")), **mode)
     un.load_lora_state(torch.load(f, map_location="cpu"))
