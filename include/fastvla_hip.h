@@ -131,6 +131,39 @@ int fv_preprocess(fv_handle* h, const void* img, int dtype, int B, int C, int Hi
  * (:466-470).  mean / std: 3 floats each in HOST memory. */
 int fv_preprocess_normalized(fv_handle* h, const void* img, int dtype, int B, int C, int Hin, int Win, float pad_value, int resize_with_padding,
                              const float* mean3, const float* std3, int range_heuristic, void* pix_out, fv_stream s);
+/* ---- on-device image augmentation (an extension of this build; the reference has none) ---------------------------
+ * One row per image.  Geometry: the crop window (x0, y0, cw, ch), in continuous SOURCE pixel coordinates, is a view into the real image; the
+ * letterbox geometry (resized size, padding) is still that of the full Hin x Win, so the padding never moves.  Output pixel dx of the image region
+ * samples sx = max((dx + 0.5) * (cw / rw) - 0.5 + x0, 0), i0 = clamp((int)sx, 0, Win - 1), i1 = min(i0 + 1, Win - 1), w = sx - i0 (rows alike):
+ * crop + resize + letterbox is ONE bilinear sample.  Taps outside the window but inside the image read real neighbours, taps outside the image
+ * replicate the edge; a non-finite coordinate samples index 0; no row content reads out of range.  Colour (image-region pixels only, on the
+ * interpolated fp32 RGB; a gray source's repeated value): v' = clamp(M v + o, 0, value_max), one bf16 rounding at the end; colour == 0 skips the
+ * stage, the clamp included.  The identity row (0, 0, Win, Hin, colour 0) gives fv_preprocess's output bit for bit. */
+typedef struct fv_augment_sample {
+  float x0, y0, cw, ch;
+  float m[9], o[3];   /* row-major M, offset */
+  int32_t colour;
+  int32_t pad[3];     /* 80 bytes */
+} fv_augment_sample;
+/* ranges (lo, hi) the table is drawn from; HOST memory, 40 bytes.  crop_area: fraction of the image's area; crop_ratio: the window's aspect RELATIVE to
+ * the image's own (1, 1 keeps it), drawn log-uniformly; brightness / contrast / saturation: factors, 1 = unchanged */
+typedef struct fv_augment_config {
+  float crop_area[2], crop_ratio[2], brightness[2], contrast[2], saturation[2];
+} fv_augment_config;
+/* Draw table_dev[0 .. B) on the device.  Sample b uses two Philox4x32-10 blocks: counter (ctr lo, ctr hi, offset lo, offset hi) with
+ * ctr = 2 (sample_base + b) + {0, 1}, key = seed, u_k = (r_k >> 8) 2^-24 (the head's dropout convention): the stream belongs to the GLOBAL sample
+ * index, not to the position in the launch.  a = lerp(area, u0), rho = exp(lerp(ln ratio_lo, ln ratio_hi, u1)), cw = clamp(Win sqrt(a rho), 1, Win),
+ * ch = clamp(Hin sqrt(a / rho), 1, Hin), x0 = u2 (Win - cw), y0 = u3 (Hin - ch); b, c, s = lerp of the three colour ranges at u4, u5, u6 (u7 reserved);
+ * M = b c (s I + (1 - s) 1 w^T), o = (1 - c) b mu 1 with w = (0.299, 0.587, 0.114) and mu the gray mean of the whole source image: brightness ->
+ * contrast -> saturation in this fixed order with ONE clamp at the end (torchvision's ColorJitter permutes the order and clamps in between).
+ * colour = 0 when all three ranges are (1, 1).  The means: one block per sample, u8 in exact integer sums, f32 in a fixed-order tree, no atomics --
+ * the same bits for a given shape every time; skipped (img may be NULL) when contrast is (1, 1).  FV_ERR_ARG before anything is enqueued for null
+ * pointers, lo > hi, non-positive area or ratio, negative factors.  No allocation, no host read. */
+int fv_augment_draw(fv_handle* h, const fv_augment_config* cfg, const void* img, int dtype, int B, int C, int Hin, int Win,
+                    uint64_t seed, uint64_t offset, uint64_t sample_base, fv_augment_sample* table_dev, fv_stream s);
+/* fv_preprocess sampling through table_dev (B rows, device memory).  value_max: 255 for u8 sources, 1 for f32 sources in 0..1; <= 0 is FV_ERR_ARG. */
+int fv_preprocess_augmented(fv_handle* h, const void* img, int dtype, int B, int C, int Hin, int Win, float pad_value, int resize_with_padding,
+                            const fv_augment_sample* table_dev, float value_max, void* pix_out, fv_stream s);
 /* replaces the vision tower + mm_projector inside LlavaQwen2ForCausalLM.forward (call site fastvlm_adapter.py:533):
  * pix (B,S,S,4) bf16 -> img_tokens (B, (S/64)^2, llm_hidden) f32.  tower_out (B,(S/64)^2,tower_out_dim) bf16 may be
  * NULL.

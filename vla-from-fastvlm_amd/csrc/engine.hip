@@ -1068,6 +1068,26 @@ int fv_preprocess_normalized(fv_handle* h, const void* img, int dtype, int B, in
   return rc;
 }
 
+int fv_augment_draw(fv_handle* h, const fv_augment_config* cfg, const void* img, int dtype, int B, int C, int Hin, int Win,
+                    uint64_t seed, uint64_t offset, uint64_t sample_base, fv_augment_sample* table_dev, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  return fv::launch_augment_draw(cfg, img, dtype, B, C, Hin, Win, seed, offset, sample_base, table_dev, static_cast<hipStream_t>(s));
+}
+
+int fv_preprocess_augmented(fv_handle* h, const void* img, int dtype, int B, int C, int Hin, int Win, float pad_value, int resize_with_padding,
+                            const fv_augment_sample* table_dev, float value_max, void* pix_out, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  const double S = h->d.image_size;
+  prof_begin(h, FV_FAM_ELT, 48.0 * B * S * S, (double)B * C * Hin * Win * (dtype == FV_U8 ? 1 : 4) + B * S * S * 8.0, st);
+  const int rc = fv::launch_letterbox_augmented(img, dtype, B, C, Hin, Win, h->d.image_size, pad_value, resize_with_padding, table_dev, value_max,
+                                                static_cast<bf16_t*>(pix_out), st);
+  prof_end(h, st);
+  return rc;
+}
+
 int fv_vision_forward(fv_handle* h, const void* pix, int B, void* img_tokens, void* tower_out, fv_stream s) {
   HandleScope _hs(h);
   FV_TRY(check_ready(h, true));

@@ -65,6 +65,11 @@ int launch_letterbox(const void* img, int dtype, int B, int C, int Hin, int Win,
                      bf16_t* pix, hipStream_t s);
 int launch_letterbox_norm(const void* img, int dtype, int B, int C, int Hin, int Win, int S, float pad_value, int letterbox, const float* mean3,
                           const float* std3, int range_heuristic, unsigned* vmax_scratch, bf16_t* pix, hipStream_t s);
+// on-device image augmentation (augment_kernels.hip): the per-sample table drawn with Philox4x32-10, and the letterbox sampling through it
+int launch_augment_draw(const fv_augment_config* cfg, const void* img, int dtype, int B, int C, int Hin, int Win, uint64_t seed, uint64_t offset,
+                        uint64_t sample_base, fv_augment_sample* table, hipStream_t s);
+int launch_letterbox_augmented(const void* img, int dtype, int B, int C, int Hin, int Win, int S, float pad_value, int letterbox,
+                               const fv_augment_sample* table, float value_max, bf16_t* pix, hipStream_t s);
 int launch_stem_conv(const bf16_t* pix, const float* w, const float* bias, bf16_t* y, int B, int S, int Cout,
                      hipStream_t s);
 // implicit-GEMM stem on MFMA; wp = stem_mfma_pack image ([Cout][64] bf16), Cout % 16 == 0

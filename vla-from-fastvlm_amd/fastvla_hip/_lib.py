@@ -94,6 +94,8 @@ SIGNATURES = {
     "fv_bind_workspace": (_i, [_vp, _vp, C.c_size_t]),
     "fv_preprocess": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp]),
     "fv_preprocess_normalized": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _i, _vp, _vp]),
+    "fv_augment_draw": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _u64, _u64, _u64, _vp, _vp]),
+    "fv_preprocess_augmented": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _f, _vp, _vp]),
     "fv_vision_forward": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "fv_vision_forward_images": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "fv_vision_forward_taps": (_i, [_vp, _vp, _i, _vp, _vp, C.POINTER(_vp), _i, _vp]),

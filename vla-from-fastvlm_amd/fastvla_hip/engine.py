@@ -237,6 +237,53 @@ class FastVLAEngine:
                                           int(resize_with_padding), pix.data_ptr(), _stream()), "fv_preprocess")
         return pix
 
+    # ---------------------------------------------------------------- image augmentation (fastvla_hip/augment.py)
+    def _augment_source(self, images: torch.Tensor):
+        if images.ndim != 4:
+            raise ValueError(f"(B,C,H,W) expected, but got shape {tuple(images.shape)}")
+        if images.dtype == torch.uint8:
+            dt = _lib.FV_U8
+        else:
+            images = images.to(torch.float32)
+            dt = _lib.FV_F32
+        return images.to(self.device).contiguous(), dt
+
+    def augment_draw(self, options: Dict, images: Optional[torch.Tensor] = None, *, shape: Optional[Tuple[int, int, int, int]] = None, seed: int = 0,
+                     offset: int = 0, sample_base: int = 0) -> torch.Tensor:
+        """Draw one fv_augment_sample per image on the device (fv_augment_draw; no host synchronisation) -> the table, a (B, 20) fp32 tensor whose column
+        16 holds the int32 `colour` flag.  options: fastvla_hip.augment.normalize_options' dict.  images (B,C,H,W) f32 | u8, or -- when contrast is (1, 1),
+        the only option that reads pixels -- shape=(B, C, H, W) alone.  Row b is a function of (seed, offset, sample_base + b) and the options."""
+        from . import augment as _aug
+        cfg = _aug.config_struct(options)
+        ptr, dt = None, _lib.FV_F32
+        if images is not None:
+            images, dt = self._augment_source(images)
+            shape, ptr = tuple(images.shape), images.data_ptr()
+        if shape is None:
+            raise ValueError("augment_draw needs the images or their shape")
+        B, Cc, H, W = (int(v) for v in shape)
+        table = torch.empty(max(B, 0), _aug.SAMPLE_FLOATS, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.fv_augment_draw(self.h, C.byref(cfg), ptr, dt, B, Cc, H, W, int(seed), int(offset), int(sample_base), table.data_ptr(), _stream()),
+                   "fv_augment_draw", self.h)
+        return table
+
+    def preprocess_augmented(self, images: torch.Tensor, table: torch.Tensor, pad_value: float = 0.0, resize_with_padding: bool = True,
+                             value_max: Optional[float] = None) -> torch.Tensor:
+        """preprocess() sampling through `table` (augment_draw's, or B hand-made 80-byte rows): crop window + colour map per image
+        (fv_preprocess_augmented).  value_max: the clamp's upper end; default 255 for uint8 images, 1 otherwise."""
+        from . import augment as _aug
+        images, dt = self._augment_source(images)
+        B, Cc, H, W = images.shape
+        if table.device != self.device or table.dtype != torch.float32 or not table.is_contiguous() or tuple(table.shape) != (B, _aug.SAMPLE_FLOATS):
+            raise ValueError(f"the table must be a contiguous ({B}, {_aug.SAMPLE_FLOATS}) fp32 tensor on {self.device}, got {tuple(table.shape)} {table.dtype} on {table.device}")
+        if value_max is None:
+            value_max = 255.0 if dt == _lib.FV_U8 else 1.0
+        S = self.model.tower.image_size
+        pix = torch.empty(B, S, S, 4, dtype=torch.bfloat16, device=self.device)
+        _lib.check(self.lib.fv_preprocess_augmented(self.h, images.data_ptr(), dt, B, Cc, H, W, float(pad_value), int(resize_with_padding), table.data_ptr(),
+                                                    float(value_max), pix.data_ptr(), _stream()), "fv_preprocess_augmented", self.h)
+        return pix
+
     def vision_forward(self, pix: torch.Tensor, return_tower_out: bool = False):
         B = pix.shape[0]
         t, l = self.model.tower, self.model.llm

@@ -107,6 +107,19 @@ class FastVLAPolicy(nn.Module):
                                            optim=opts)
         return self._unfrozen
 
+    def enable_image_augmentation(self, crop_area=None, crop_ratio=None, brightness=None, contrast=None, saturation=None, seed: Optional[int] = None,
+                                  value_max: Optional[float] = None) -> Dict:
+        """Extension of this build: random crop + brightness / contrast / saturation jitter of TRAINING batches, drawn and applied on the device inside the
+        letterbox call (FastVLMBackbone.enable_image_augmentation has the details; fastvla_hip/augment.py the semantics).  Ranges are (lo, hi) or a number;
+        with none given FASTVLA_IMAGE_AUG decides, else the preset `default` (crop_area 0.9, colour factors 0.8 .. 1.2); seed: FASTVLA_IMAGE_AUG_SEED, else 0.
+        Only prepare_batch / the unfrozen prepare of a policy in train() mode augment: select_action, compute_loss, Trainer.evaluate and already
+        prepared pixels never do.  The image tokens reach the action in splice mode only (backbone training forces it)."""
+        return self.model.backbone.enable_image_augmentation(crop_area=crop_area, crop_ratio=crop_ratio, brightness=brightness, contrast=contrast,
+                                                             saturation=saturation, seed=seed, value_max=value_max)
+
+    def disable_image_augmentation(self) -> None:
+        self.model.backbone.disable_image_augmentation()
+
     def merge_lora(self) -> None:
         """LoRA mode: fold the adapters into the fp32 master (W0 += s B A, lora_B = 0).  The model computes what it computed before; the backbone export
         (save_policy_checkpoint(include_backbone=True), FASTVLA_SAVE_BACKBONE) then writes a plain checkpoint under the reference's keys."""
@@ -154,7 +167,7 @@ class FastVLAPolicy(nn.Module):
         the current stream; a pipelined loop calls it for batch k+1 while batch k's gradient all-reduce is in flight."""
         m = self.model
         dev = m.backbone.engine().device
-        images = self.processor.prepare_images(batch["images"], dev)
+        images = self.processor.prepare_images(batch["images"], dev, augment=self.training)     # (image augmentation, when on: training batches only)
         states = self.processor.prepare_states(batch["states"], dev).float()
         tasks = self.processor.prepare_tasks(batch["tasks"], batch_size=images.shape[0])
         targets = batch["actions"].to(dev, torch.float32)
@@ -244,6 +257,8 @@ class FastVLAPolicy(nn.Module):
         if self._unfrozen is not None:
             out = self._unfrozen.step(batch, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
                                       process_group=process_group, prepared=prepared, grad_accum_steps=grad_accum_steps, force_sync=force_sync)
+            if self.training:
+                self.model.backbone.note_train_step()     # (the augmentation's batch counter: what a checkpoint records)
             if next_batch is not None:
                 # Trainer's one batch of look-ahead (training/trainer.py _train_one_epoch): an unfrozen forward depends on the update, so only the
                 # parameter-INDEPENDENT half of the next batch is prepared here, AFTER the commit (image prep, tokenisation, the tower while it is frozen)
@@ -251,6 +266,8 @@ class FastVLAPolicy(nn.Module):
             return out
         m = self.model
         prep = prepared if prepared is not None else self.prepare_batch(batch)
+        if self.training:
+            m.backbone.note_train_step()     # (the augmentation's batch counter: what a checkpoint records)
         dev = prep["pooled"].device
         eng, flat = m._engine(), m.materialize(dev)
         st = self._optimizer_state(flat)

@@ -25,10 +25,10 @@ class FastVLAProcessor:
 
     prepare_tasks = normalize_tasks
 
-    def prepare_images(self, images: torch.Tensor, device: torch.device) -> torch.Tensor:
+    def prepare_images(self, images: torch.Tensor, device: torch.device, augment: bool = False) -> torch.Tensor:
         if images.ndim == 5:  # (B,T,C,H,W): keep the most recent frame
             images = images[:, -1]
-        return self.backbone._prepare_images_tensor(images, device)
+        return self.backbone._prepare_images_tensor(images, device, augment=augment)
 
     def prepare_states(self, states: torch.Tensor, device: torch.device) -> torch.Tensor:
         if states.ndim == 3:  # (B,T,D)

@@ -57,6 +57,13 @@ class FastVLAPolicy(PreTrainedPolicy):
     def reset(self):
         self._action_queue: deque[Tensor] = deque([], maxlen=self.config.n_action_steps)
 
+    def enable_image_augmentation(self, **kwargs):
+        """image augmentation of training batches: the backbone's state, as vla_fastvlm.fastvla.FastVLAPolicy.enable_image_augmentation sets it"""
+        return self.model.backbone.enable_image_augmentation(**kwargs)
+
+    def disable_image_augmentation(self) -> None:
+        self.model.backbone.disable_image_augmentation()
+
     def fold_dataset_stats(self, dataset_stats) -> None:
         """Take over the STATE / ACTION MEAN_STD normalisation LeRobot's processors would apply around the policy
         (reference lerobot_fastvla/processor_fastvla.py:34-48 with the map of configuration_fastvla.py:21-27): raw states go

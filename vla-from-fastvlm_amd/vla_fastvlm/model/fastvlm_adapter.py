@@ -59,6 +59,11 @@ class PreparedPixels(torch.Tensor):
     a no-op here."""
 
 
+class AugmentedPixels(PreparedPixels):
+    """PreparedPixels that went through the image augmentation (a training batch): never keyed into, nor served from, the prompt-feature or
+    image-prefix caches."""
+
+
 def infer_size_from_tower_name(tower_name: Any) -> Optional[int]:
     """'mobileclip_l_1024' -> 1024, '...patch14-384' -> 384, 'fastvithd' -> None (reference :300-335)."""
     if not isinstance(tower_name, str):
@@ -169,6 +174,12 @@ class FastVLMBackbone(nn.Module):
         # even a new frame runs its text positions against the prefix instead of one joint 320-token prefill
         self.cache_image_prefix = os.environ.get("FASTVLA_PREFIX_CACHE", "0") == "1"
         self.prefix_cache_size = 64
+        # image augmentation of TRAINING batches (fastvla_hip/augment.py; an attribute for the reason above): None = off, else {"options", "seed", "drawn",
+        # "stepped", "value_max"} -- set by enable_image_augmentation(); FASTVLA_IMAGE_AUG switches it on from the environment
+        self._augment: Optional[dict] = None
+        from fastvla_hip import augment as _aug
+        if _aug.options_from_env() is not None:
+            self.enable_image_augmentation()
         self._engine: Optional[FastVLAEngine] = None
         self._weights_override: Optional[Dict[str, Tensor]] = None   # load_backbone_state(): a checkpoint's own VLM tensors
         self._io_norm: Optional[dict] = None   # dataset statistics folded into the head kernels (set_io_normalization)
@@ -387,8 +398,66 @@ class FastVLMBackbone(nn.Module):
             self.set_io_normalization(**{k: found[k].float().cpu() for k in self._IO_KEYS[:4]}, eps=float(found["eps"].reshape(-1)[0]))
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
+    # ------------------------------------------------------------------ image augmentation
+    def enable_image_augmentation(self, crop_area=None, crop_ratio=None, brightness=None, contrast=None, saturation=None, seed: Optional[int] = None,
+                                  value_max: Optional[float] = None) -> dict:
+        """Extension of this build: TRAINING batches (FastVLAPolicy.prepare_batch, UnfrozenState.prepare -- nothing else) are letterboxed through a random crop
+        window and a brightness / contrast / saturation map drawn per image on the device (fv_augment_draw + fv_preprocess_augmented; fastvla_hip/augment.py
+        has the semantics).  Each range is (lo, hi) or a number; with no range given, FASTVLA_IMAGE_AUG decides, and without it the preset `default`
+        (OpenVLA's recipe without hue: crop_area 0.9, colour factors 0.8 .. 1.2).  seed: default FASTVLA_IMAGE_AUG_SEED, else 0; rank r draws with seed + r,
+        batch k of the run with offset k, so a run is reproducible from (options, seed) and a resumed run continues the stream.  value_max: the colour
+        clamp's upper end (default 255 for uint8 batches, 1 for float ones).  Not together with normalize_imagenet (ValueError)."""
+        from fastvla_hip import augment as _aug
+        opts, sd = _aug.resolve(crop_area, crop_ratio, brightness, contrast, saturation, seed)
+        if value_max is not None and not float(value_max) > 0.0:
+            raise ValueError(f"value_max must be positive, got {value_max!r}")
+        if self.config.normalize_imagenet:
+            raise ValueError("image augmentation together with normalize_imagenet=True is not built: switch one of them off")
+        self._augment = {"options": opts, "seed": int(sd), "drawn": 0, "stepped": 0, "value_max": None if value_max is None else float(value_max)}
+        return self._augment
+
+    def disable_image_augmentation(self) -> None:
+        self._augment = None
+
+    def augmentation_record(self) -> Optional[dict]:
+        """what a checkpoint keeps of a run with augmentation on (None when off): the options, the seed and the number of training batches STEPPED -- a
+        look-ahead batch prepared before the save is drawn again, with the same offset, after the resume"""
+        a = self._augment
+        if a is None:
+            return None
+        from fastvla_hip import augment as _aug
+        return {"options": _aug.record(a["options"]), "seed": int(a["seed"]), "batches": int(a["stepped"])}
+
+    def load_augmentation_record(self, rec: Optional[dict]) -> None:
+        """Resume: take the checkpointed run's options, seed and batch counter.  A run that asked for other options (or for augmentation when the
+        checkpointed run had none) raises ValueError naming both."""
+        from fastvla_hip import augment as _aug
+        cur = self._augment
+        if rec is None:
+            if cur is not None:
+                raise ValueError(f"the checkpoint was written by a run without image augmentation, this run uses {_aug.record(cur['options'])} (seed {cur['seed']}): "
+                                 "resume without it")
+            return
+        opts, seed = _aug.from_record(rec["options"]), int(rec.get("seed", 0))
+        if cur is not None and (cur["options"] != opts or cur["seed"] != seed):
+            raise ValueError(f"the checkpoint was written by a run with the image augmentation {_aug.record(opts)} (seed {seed}), this run uses "
+                             f"{_aug.record(cur['options'])} (seed {cur['seed']}): resume with the checkpoint's options")
+        if cur is None:
+            cur = self.enable_image_augmentation(**opts, seed=seed)
+        cur["drawn"] = cur["stepped"] = int(rec.get("batches", 0))
+
+    def note_train_step(self) -> None:
+        """one prepared training batch has been consumed by an optimiser (micro-)step"""
+        if self._augment is not None:
+            self._augment["stepped"] += 1
+
+    @staticmethod
+    def _rank() -> int:
+        import torch.distributed as dist
+        return dist.get_rank() if dist.is_available() and dist.is_initialized() else int(os.environ.get("RANK", "0"))
+
     # ------------------------------------------------------------------ preprocessing
-    def _prepare_images_tensor(self, images, device: torch.device) -> Tensor:
+    def _prepare_images_tensor(self, images, device: torch.device, augment: bool = False) -> Tensor:
         if isinstance(images, PreparedPixels):
             return images
         x = canonical_bchw(images)
@@ -399,6 +468,16 @@ class FastVLMBackbone(nn.Module):
         eng = self.engine(device if torch.device(device).type == "cuda" else None)
         # normalize_imagenet (reference _maybe_normalize_imagenet :463-477, after the letterbox :486-487): folded into the letterbox kernel, with the
         # value-range test of the reference's torchvision branch (what an installed reference runs) decided on the device
+        aug = self._augment if augment else None
+        if aug is not None:
+            if self.config.normalize_imagenet:
+                raise ValueError("image augmentation together with normalize_imagenet=True is not built: switch one of them off")
+            # the table is drawn on the device from (seed + rank, number of training batches drawn so far): no host synchronisation
+            x = x.to(eng.device)
+            table = eng.augment_draw(aug["options"], x, seed=aug["seed"] + self._rank(), offset=aug["drawn"])
+            aug["drawn"] += 1
+            pix = eng.preprocess_augmented(x, table, self.config.pad_value, self.config.resize_with_padding, value_max=aug["value_max"])
+            return pix.as_subclass(AugmentedPixels)
         pix = eng.preprocess(x.to(eng.device), self.config.pad_value, self.config.resize_with_padding,
                              normalize_imagenet=bool(self.config.normalize_imagenet))
         return pix.as_subclass(PreparedPixels)
@@ -454,22 +533,23 @@ class FastVLMBackbone(nn.Module):
         lens = attention_mask.to(torch.int32).sum(dim=1).to(torch.int32)
         mode = 0 if self.config.image_feature_pool == "last_token" else 1
         literal = not self.splice_image_tokens
+        augmented = isinstance(images, AugmentedPixels)    # a training batch's own frames: the caches below neither keep nor serve them
         eng.tokens_consumed(not literal)   # spliced tokens feed the decoder: the tower then keeps one set of kernel forms at every batch size (an observation's
                                            # action must not depend on how many observations were evaluated with it); literal mode drops them and stays fast
-        if (not literal and self.cache_image_prefix and mode == 0 and eng.llm_precision >= 1 and eng.model.llm.head_dim >= 64
+        if (not literal and self.cache_image_prefix and not augmented and mode == 0 and eng.llm_precision >= 1 and eng.model.llm.head_dim >= 64
                 and torch.is_tensor(images) and images.ndim == 4):
             return self._pooled_through_prefix_cache(eng, images, input_ids, lens)
         pix = self._prepare_images_tensor(images, eng.device)
         if pix.shape[0] != input_ids.shape[0]:
             raise ValueError(f"batch mismatch: {pix.shape[0]} images vs {input_ids.shape[0]} prompts")
-        if literal and not self.skip_unused_tower and not self.cache_prompt_features:
+        if literal and not self.skip_unused_tower and (augmented or not self.cache_prompt_features):
             # the reference-literal step: tower + projector run (their output is dropped) BESIDE the decoder on
             # a second HIP stream -- the same schedule bench.py times at the engine level
             return eng.backbone(None, input_ids, lens, pool_mode=mode, pix=pix)
         tok = None
         if not (literal and self.skip_unused_tower):
             tok = eng.vision_forward(pix)  # computed even when not spliced: the literal reference runs the tower too
-        if literal and self.cache_prompt_features:
+        if literal and self.cache_prompt_features and not augmented:
             return self._pooled_through_cache(eng, input_ids, lens, mode)
         return eng.llm_pooled(input_ids, lens, tok if self.splice_image_tokens else None, pool_mode=mode)
 

@@ -224,7 +224,9 @@ class Trainer:
         st = getattr(self.model, "_opt_state", None)
         if st is not None:
             from ..utils.checkpoint import optimizer_record
-            rec = optimizer_record(st, getattr(self.model, "_unfrozen", None), self.global_step, self.update_step)
+            core = getattr(self.model, "model", None)
+            aug = core.backbone.augmentation_record() if hasattr(getattr(core, "backbone", None), "augmentation_record") else None
+            rec = optimizer_record(st, getattr(self.model, "_unfrozen", None), self.global_step, self.update_step, augment=aug)
             torch.save(rec, d / "optimizer.pt")
 
     def _load_checkpoint(self, path: str) -> None:
@@ -258,6 +260,10 @@ class Trainer:
             from ..utils.checkpoint import load_lora_adapters
             load_lora_adapters(self.model, p, ex["lora"], optim=resume_opt.get("optim") if resume_opt else None)
         if resume_opt is not None:
+            # the image augmentation of the run being resumed (its options, seed and batch counter) comes back with it; a run that asks for other options raises
+            bb = getattr(getattr(self.model, "model", None), "backbone", None)
+            if hasattr(bb, "load_augmentation_record"):
+                bb.load_augmentation_record(resume_opt.get("augment"))
             self._resume_opt = resume_opt  # applied by _sync_replicas()
             self.global_step = int(self._resume_opt.get("global_step", 0))
             self.update_step = int(self._resume_opt.get("update_step", self._resume_opt.get("step", 0)))

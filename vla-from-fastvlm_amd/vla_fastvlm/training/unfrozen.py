@@ -243,13 +243,13 @@ class UnfrozenState:
         """everything that does not depend on the trainable parameters: image prep + the FROZEN tower, tokenisation"""
         pol, bb, eng = self.policy, self.policy.model.backbone, self.eng
         dev = eng.device
-        images = pol.processor.prepare_images(batch["images"], dev)
+        images = pol.processor.prepare_images(batch["images"], dev, augment=pol.training)     # (image augmentation, when on: training batches only)
         states = pol.processor.prepare_states(batch["states"], dev).float()
         tasks = pol.processor.prepare_tasks(batch["tasks"], batch_size=images.shape[0])
         targets = batch["actions"].to(dev, torch.float32)
         if targets.ndim == 3:
             targets = targets[:, 0]
-        pix = bb._prepare_images_tensor(images, dev)
+        pix = bb._prepare_images_tensor(images, dev, augment=pol.training)
         tower_out = None
         if not self.train_tower:           # a trainable tower's forward depends on the parameters: it belongs to step()
             with torch.no_grad():

@@ -24,7 +24,8 @@ from ..fastvla import FastVLAConfig, FastVLAPolicy
 BACKBONE_PREFIX = "model.backbone.model."
 # run properties of THIS build that are not tensors of the reference's module tree: written beside the two reference files, never into them, so that the
 # reference's strict `load_state_dict` / `FastVLAConfig(**payload)` accept a checkpoint of an unfrozen run as it is.  Keys: "splice_image_tokens"
-# (the decoder was trained on [image tokens | text]: inference must run the same graph), "train_backbone", "train_tower".
+# (the decoder was trained on [image tokens | text]: inference must run the same graph), "train_backbone", "train_tower", and -- only for a run with image
+# augmentation on -- "augment" = {"options", "seed"} (what the training batches went through; inference never augments).
 EXTRAS_FILE = "hip_extras.json"
 # a LoRA run (enable_backbone_training(lora_rank=...)): the adapters, the mm_projector that trains beside them and {rank, alpha, targets} in a file of their
 # own; EXTRAS_FILE names it under "lora" = {"rank", "alpha", "targets", "file", "direct"}, and a directory whose extras name adapters that are not there does not
@@ -42,11 +43,14 @@ def read_extras(checkpoint_dir) -> dict:
 EXTRA_STATE_MARKS = (".io_norm.", ".splice_image_tokens")
 
 
-def optimizer_record(st: dict, un, global_step: int, update_step: int) -> dict:
+def optimizer_record(st: dict, un, global_step: int, update_step: int, augment: dict | None = None) -> dict:
     """What Trainer writes to optimizer.pt: AdamW's moments and step, the loop's counters, and for an unfrozen run (`un`, training/unfrozen.py UnfrozenState) its
     trainable fp32 buffer and what it trains.  "optim" -- the parameter-group options of the run (fastvla_hip/optim.py) -- is there ONLY when one is set: a
-    plain run's file is byte for byte what it was."""
+    plain run's file is byte for byte what it was.  "augment" -- {options, seed, batches} of a run with image augmentation on
+    (FastVLMBackbone.augmentation_record; batches = training batches STEPPED) -- likewise only when it is on."""
     rec = {"m": st["m"].cpu(), "v": st["v"].cpu(), "step": st["step"], "global_step": global_step, "update_step": update_step}
+    if augment is not None:
+        rec["augment"] = dict(augment)
     if un is not None:
         # the fp32 MASTER of an unfrozen run: the VLM tensors of policy_state_dict.pt come back through the engine's bf16 operand copies, and a master
         # rebuilt from those has lost the low bits every later update (~1e-3 of a bf16 ulp) lives in
@@ -136,6 +140,9 @@ def save_policy_checkpoint(policy: FastVLAPolicy, checkpoint_dir: str, include_b
                 extras["lora"]["direct"] = True
         elif (d / LORA_FILE).is_file():
             (d / LORA_FILE).unlink()
+    aug = policy.model.backbone.augmentation_record()
+    if aug is not None:      # (written only when on) the run's image augmentation: its options and seed; the batch counter travels in optimizer.pt
+        extras["augment"] = {"options": aug["options"], "seed": aug["seed"]}
     if any(extras.values()):
         (d / EXTRAS_FILE).write_text(json.dumps(extras, indent=2))
     if include_backbone:
