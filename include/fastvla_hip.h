@@ -253,6 +253,33 @@ int fv_head_set_io_norm(fv_handle* h, const float* state_mean, const float* stat
  * flat_grads (overwritten, not accumulated). */
 int fv_head_mse_backward(fv_handle* h, const float* flat_params, const float* actions, const float* targets, int B,
                          float dropout_p, const void* saved, float* loss, float* flat_grads, fv_stream s);
+/* ---- action chunks and the loss of the fused backward.  The head's output width stays fv_model_desc.action_dim = K * A: a chunk of K future steps of A
+ * action dimensions each, row-major (B, K, A).  The loss below is what fv_head_mse_backward and every fv_train_*_forward_backward evaluate (one place:
+ * the head backward), so all of them take the spec and the mask from the handle.  With d = actions - targets, n = B * K * A and w = 0 where pad[b][k] else 1:
+ *     loss = sum w rho(d) / n          dL/dactions = loss_scale * w * rho'(d) / n       (rho as torch: mse d^2; l1 |d|, sign(0) = 0;
+ *     smooth_l1 0.5 d^2 / beta for |d| < beta, else |d| - 0.5 beta)
+ * The denominator is ALL n elements, padded ones included (LeRobot's `(loss * ~pad).mean()`): micro-batches and data-parallel ranks with different pad
+ * counts then still average exactly.  A padded element gives exactly 0 to the loss, the metrics and the gradient whatever its target holds (NaN, inf).
+ * kind MSE with no mask launches the single-block MSE kernel it always did, for any K; everything else a many-block kernel with fixed-order partials
+ * and a single-block fold (no float atomics: two runs agree bit for bit). */
+#define FV_LOSS_MSE 0
+#define FV_LOSS_L1 1
+#define FV_LOSS_SMOOTH_L1 2
+typedef struct fv_head_loss_spec {
+  int32_t kind;    /* FV_LOSS_* */
+  float beta;      /* smooth-L1 threshold, > 0 (read for FV_LOSS_SMOOTH_L1 only) */
+  int32_t chunk;   /* K >= 1, action_dim % K == 0 */
+} fv_head_loss_spec;
+/* NULL = {FV_LOSS_MSE, -, 1}.  FV_ERR_ARG for an unknown kind, a smooth-L1 beta that is not a positive finite number, K < 1 or K not dividing
+ * action_dim; nothing is enqueued.  A configuration call without device work.  A hipGraph captured over a loss evaluation keeps the spec AND the
+ * mask pointer of its capture: re-capture after either setter (new mask VALUES written to the same address are picked up by replays). */
+int fv_head_set_loss(fv_handle* h, const fv_head_loss_spec* spec);
+/* pad_dev: DEVICE (B, K) bytes, 1 = padded step; NULL = none.  Read by every later loss evaluation on the handle until replaced; the caller keeps it
+ * alive (and sized for the B of those calls). */
+int fv_head_set_loss_mask(fv_handle* h, const uint8_t* pad_dev);
+/* *dev = 2 handle-owned device floats written by the chunked loss kernel (not by the plain MSE path): { sum over valid elements of d^2 / n,
+ * valid steps / (B * K) }.  They head a 16-byte aligned slot of 4 floats of their own (the other two stay 0): a 4-float copy is in bounds. */
+int fv_head_loss_metrics(fv_handle* h, const float** dev);
 /* generic backward of the head from dL/dactions (B,A) f32 (what autograd hands a custom Function when the loss is
  * computed outside, e.g. lerobot_fastvla/modeling_fastvla.py:132 + loss.backward()); overwrites flat_grads. */
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,

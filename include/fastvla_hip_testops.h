@@ -157,6 +157,13 @@ int fv_op_lora_direct_scratch_floats(int R, int rank, int max_cols, size_t* out_
 int fv_op_lora_direct(int kind, int part_mask, int rank, int Np, int K, int qd, int kd, const int64_t* a_off, const int64_t* b_off, const void* dY, const void* X,
                       int xkind, int ldx, int lo_off, int R, const float* lora, float* lora_grads, float scale, float* scratch, size_t scratch_floats, fv_stream s);
 
+
+/* the chunked action loss alone (csrc/head_kernels.hip chunk_loss_kernel + its fold; fv_head_set_loss in fastvla_hip.h has the definitions): a, t (n) f32 =
+ * (B, K, A) row-major with A the step width, pad (n / A) bytes or NULL -> g (n) = loss_scale * w * rho'(a - t) / n, loss (1), metrics (2) = { masked MSE, valid
+ * fraction }.  partial: scratch of partial_floats >= 768 floats.  kind FV_LOSS_*. */
+int fv_op_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, size_t partial_floats, float* loss, float* metrics,
+                     int64_t n, int A, int kind, float beta, float loss_scale, fv_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -183,12 +183,16 @@ struct fv_handle {
   bool no_fused_ffn = false;  // FASTVLA_NO_FUSED_FFN=1: A/B switch back to the two-GEMM ConvFFN
   bool no_mfma_dw = false;    // FASTVLA_NO_MFMA_DW=1: A/B switch back to the VALU depthwise kernels
   bool no_ffn32 = false;      // FASTVLA_NO_FFN32=1: A/B switch back to the 16x16x32 fused ConvFFN
+  fv::HeadLoss loss{FV_LOSS_MSE, 1.0f, 1, nullptr, nullptr};   // fv_head_set_loss / fv_head_set_loss_mask; metrics: two words of the f16_flags block
   TrainState train;               // unfrozen-backbone training (train_path.inc): library-owned transposed bf16 weight copies
   int batch_invariant = 0;        // fv_set_batch_invariant: the inference tower never takes the range forms either
   int train_depth = 0;            // > 0 while a training entry point runs (TrainScope): gemm_p then keeps the few-row GEMM forms off
   float* ffn_part = nullptr;      // device: the fused ConvFFN's partial sums when a launch has few row tiles (B <= 4: launch_convffn32's hidden ranges), FFN_PART_BYTES
-  unsigned* f16_flags = nullptr;  // device: [0] = activation groups clamped to the fp16 range (fv_llm_fp16_saturations),
-                                  // [1] = max |scaled weight| bits seen by the loader's in-place fp16 conversion
+  unsigned* f16_flags = nullptr;  // device: ONE zero-initialised block of 64 words (256 bytes) that holds every small handle-owned device value:
+                                  // [0] = activation groups clamped to the fp16 range (fv_llm_fp16_saturations),
+                                  // [1] = max |scaled weight| bits seen by the loader's in-place fp16 conversion,
+                                  // [32] = lb_vmax, [48 .. 51] = the chunked loss's 16-byte slot (loss.metrics: two floats written by
+                                  // chunk_loss_fold_kernel, two reserved zeros so that a float4 copy of the slot reads nothing else); the rest is unused
 };
 
 namespace {
@@ -828,6 +832,7 @@ int fv_create(const fv_model_desc* desc, int device, fv_handle** out) {
     rc = dev_alloc(h, 256, &p);
     h->f16_flags = static_cast<unsigned*>(p);
     if (rc == FV_OK && hipMemset(p, 0, 256) != hipSuccess) rc = fv_fail(FV_ERR_HIP, "fp16 flag words: memset failed");
+    h->loss.metrics = reinterpret_cast<float*>(h->f16_flags + 48);   // words 48 .. 51 are the metrics' own 16-byte slot (zeroed with the block)
     h->lb_vmax = h->f16_flags + 32;   // a word of the same block (nothing is allocated inside fv_preprocess_normalized: the call stays capturable)
   }
   if (rc == FV_OK) { rc = dev_alloc(h, FFN_PART_BYTES, &p); h->ffn_part = static_cast<float*>(p); }
@@ -1341,9 +1346,36 @@ int fv_head_mse_backward(fv_handle* h, const float* flat_params, const float* ac
   hipStream_t st = static_cast<hipStream_t>(s);
   prof_begin(h, FV_FAM_HEAD, 4.0 * B * fv::head_offsets(h->hd).o[12], 8.0 * fv::head_offsets(h->hd).o[12], st);
   const int rc = fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p,
-                                          static_cast<const float*>(saved), loss, flat_grads, scr, st);
+                                          static_cast<const float*>(saved), loss, flat_grads, scr, st, nullptr, 1.0f, &h->loss);
   prof_end(h, st);
   return rc;
+}
+
+int fv_head_set_loss(fv_handle* h, const fv_head_loss_spec* spec) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (!spec) { h->loss.kind = FV_LOSS_MSE; h->loss.beta = 1.0f; h->loss.chunk = 1; return FV_OK; }
+  if (spec->kind != FV_LOSS_MSE && spec->kind != FV_LOSS_L1 && spec->kind != FV_LOSS_SMOOTH_L1) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: unknown loss kind %d", spec->kind);
+  if (spec->kind == FV_LOSS_SMOOTH_L1 && !(spec->beta > 0.f && std::isfinite(spec->beta))) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: smooth-L1 beta must be positive and finite");
+  if (spec->chunk < 1 || h->hd.da % spec->chunk) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: chunk=%d must be >= 1 and divide action_dim=%d", spec->chunk, h->hd.da);
+  h->loss.kind = spec->kind;
+  h->loss.beta = spec->kind == FV_LOSS_SMOOTH_L1 ? spec->beta : 1.0f;
+  h->loss.chunk = spec->chunk;
+  return FV_OK;
+}
+
+int fv_head_set_loss_mask(fv_handle* h, const uint8_t* pad_dev) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  h->loss.pad = pad_dev;
+  return FV_OK;
+}
+
+int fv_head_loss_metrics(fv_handle* h, const float** dev) {
+  HandleScope _hs(h);
+  if (!h || !dev) return fv_fail(FV_ERR_ARG, "fv_head_loss_metrics: null argument");
+  *dev = h->loss.metrics;
+  return FV_OK;
 }
 
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,

@@ -183,6 +183,85 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ a, c
   if (threadIdx.x == 0) *loss = (red[0] + red[1] + red[2] + red[3]) / (float)n;
 }
 
+// ---- chunked action loss (fv_head_set_loss / fv_head_set_loss_mask) ----
+// a, t: (B, K, A) row-major, n = B K A elements; pad (may be null): (B, K) bytes, 1 = the step lies past the episode end.  With w = !pad and d = a - t:
+//   loss = sum w rho(d) / n      g = loss_scale w rho'(d) / n      metrics = { sum w d^2 / n, sum w / n }   (the denominator is ALL n elements: LeRobot's
+//   `(loss * ~pad).mean()`, which keeps gradient accumulation and the data-parallel mean exact when micro-batches hold different pad counts)
+// A padded element is SELECTED away, never multiplied: whatever its target holds (NaN, +-inf) it gives 0 to the loss, the metrics and g.
+// Many blocks; every block writes three partials in a fixed order and chunk_loss_fold_kernel sums them in a fixed order (no float atomics: two runs
+// and two replicas agree bit for bit).  vec: a, t, g are 16-byte aligned -> float4 body, the n % 4 tail goes through the scalar form in block 0.
+constexpr int CHUNK_LOSS_BLOCKS = 256;
+struct LossTerm { float rho, grad; };
+__device__ __forceinline__ LossTerm loss_term(float d, int kind, float beta, float c, float loss_scale, float nf) {
+  const float ad = fabsf(d), sg = d > 0.f ? c : (d < 0.f ? -c : 0.f);   // c = loss_scale / n
+  if (kind == FV_LOSS_L1) return {ad, sg};
+  if (kind == FV_LOSS_SMOOTH_L1) return ad < beta ? LossTerm{0.5f * d * d / beta, loss_scale * (d / beta) / nf} : LossTerm{ad - 0.5f * beta, sg};
+  return {d * d, loss_scale * 2.0f * d / nf};   // mse_kernel's expression
+}
+__global__ __launch_bounds__(256) void chunk_loss_kernel(const float* __restrict__ a, const float* __restrict__ t, const uint8_t* __restrict__ pad,
+                                                          float* __restrict__ g, float* __restrict__ partial, long n, int A, int kind, float beta,
+                                                          float loss_scale, int vec) {
+  __shared__ float red[3][4];
+  const float nf = (float)n, c = loss_scale / nf;
+  float sl = 0.f, sq = 0.f;
+  unsigned cnt = 0;
+  auto one = [&](long i) {
+    const bool w = !pad || pad[i / A] == 0;
+    LossTerm r{0.f, 0.f};
+    if (w) {
+      const float d = a[i] - t[i];
+      r = loss_term(d, kind, beta, c, loss_scale, nf);
+      sl += r.rho; sq += d * d; ++cnt;
+    }
+    g[i] = r.grad;
+  };
+  if (vec) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+      const float4 av = reinterpret_cast<const float4*>(a)[i], tv = reinterpret_cast<const float4*>(t)[i];
+      const float ae[4] = {av.x, av.y, av.z, av.w}, te[4] = {tv.x, tv.y, tv.z, tv.w};
+      float ge[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool w = !pad || pad[(i * 4 + j) / A] == 0;
+        LossTerm r{0.f, 0.f};
+        if (w) {
+          const float d = ae[j] - te[j];
+          r = loss_term(d, kind, beta, c, loss_scale, nf);
+          sl += r.rho; sq += d * d; ++cnt;
+        }
+        ge[j] = r.grad;
+      }
+      reinterpret_cast<float4*>(g)[i] = make_float4(ge[0], ge[1], ge[2], ge[3]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) one((n4 << 2) + threadIdx.x);
+  } else {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) one(i);
+  }
+  sl = wave_sum(sl); sq = wave_sum(sq);
+  const float sc = wave_sum((float)cnt);   // a thread sees at most n / 256 + 4 elements: exact in fp32 for every n below 2^24
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sl; red[1][threadIdx.x >> 6] = sq; red[2][threadIdx.x >> 6] = sc; }
+  __syncthreads();
+  if (threadIdx.x < 3) partial[3 * blockIdx.x + threadIdx.x] = (red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+// single block: loss = sum of the blocks' loss partials / n, metrics = { sum w d^2 / n, sum w / n }
+__global__ __launch_bounds__(256) void chunk_loss_fold_kernel(const float* __restrict__ partial, int nb, float* __restrict__ loss,
+                                                               float* __restrict__ metrics, long n) {
+  __shared__ float red[3][4];
+  float s[3] = {0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < nb; i += 256) { s[0] += partial[3 * i]; s[1] += partial[3 * i + 1]; s[2] += partial[3 * i + 2]; }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    s[j] = wave_sum(s[j]);
+    if ((threadIdx.x & 63) == 0) red[j][threadIdx.x >> 6] = s[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const float v = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + (red[threadIdx.x][2] + red[threadIdx.x][3])) / (float)n;
+    if (threadIdx.x == 0) *loss = v; else metrics[threadIdx.x - 1] = v;
+  }
+}
+
 // LN backward: wave per row -> dx (may be null); column sums dw, db done by ln_bwd_cols_kernel
 __global__ __launch_bounds__(256) void ln_bwd_rows_kernel(const float* __restrict__ dy, const float* __restrict__ w,
                                                            const float* __restrict__ xhat, const float* __restrict__ rstd,
@@ -325,7 +404,8 @@ size_t head_saved_bytes(const HeadDims& d, int B) { return carve(d, B, nullptr).
 
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B) {
   const size_t wmax = (size_t)(d.feat + d.hid > d.fus ? d.feat + d.hid : d.fus);
-  return ((size_t)B * d.da + 2 * (size_t)B * wmax + 64) * sizeof(float);
+  // dL/dactions | two activation-gradient rows of the widest layer | alignment slack | the chunked loss's per-block partials (loss, sum w d^2, sum w)
+  return ((size_t)B * d.da + 2 * (size_t)B * wmax + 64 + 3 * (size_t)CHUNK_LOSS_BLOCKS) * sizeof(float);
 }
 
 int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, const float* states, int B,
@@ -357,10 +437,29 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
   return FV_OK;
 }
 
+size_t chunk_loss_partial_floats() { return 3 * (size_t)CHUNK_LOSS_BLOCKS; }
+
+int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, float* loss, float* metrics, long n, int A, int kind,
+                      float beta, float loss_scale, hipStream_t s) {
+  if (!a || !t || !g || !partial || !loss || !metrics) return fv_fail(FV_ERR_ARG, "chunk_loss: null pointer");
+  if (n <= 0 || A <= 0 || n % A) return fv_fail(FV_ERR_ARG, "chunk_loss: n must be a positive multiple of the step width");
+  if (kind != FV_LOSS_MSE && kind != FV_LOSS_L1 && kind != FV_LOSS_SMOOTH_L1) return fv_fail(FV_ERR_ARG, "chunk_loss: unknown loss kind %d", kind);
+  if (kind == FV_LOSS_SMOOTH_L1 && !(beta > 0.f)) return fv_fail(FV_ERR_ARG, "chunk_loss: smooth-L1 beta must be positive");
+  const int vec = (((uintptr_t)a | (uintptr_t)t | (uintptr_t)g) & 15) == 0;
+  const unsigned want = cdiv(vec ? (n >> 2) : n, 256);
+  const unsigned nb = want < 1 ? 1 : (want < (unsigned)CHUNK_LOSS_BLOCKS ? want : (unsigned)CHUNK_LOSS_BLOCKS);
+  hipLaunchKernelGGL(chunk_loss_kernel, dim3(nb), dim3(256), 0, s, a, t, pad, g, partial, n, A, kind, beta, loss_scale, vec);
+  hipLaunchKernelGGL(chunk_loss_fold_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, loss, metrics, n);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
 int launch_head_backward(const HeadDims& d, const float* P, const float* grad_actions, const float* actions,
                          const float* targets, int B, float drop_p, const float* saved, float* loss, float* G,
-                         float* scratch, hipStream_t s, float* d_pooled, float loss_scale) {
+                         float* scratch, hipStream_t s, float* d_pooled, float loss_scale, const HeadLoss* hl) {
   if (!P || !saved || !G || !scratch) return fv_fail(FV_ERR_ARG, "head_backward: null pointer");
+  const bool chunked = hl && !grad_actions && (hl->kind != FV_LOSS_MSE || hl->pad);   // MSE without a mask: mse_kernel, for any chunk length
+  if (chunked && (!hl->metrics || hl->chunk < 1 || d.da % hl->chunk)) return fv_fail(FV_ERR_ARG, "head_backward: chunked loss needs metrics and a chunk length that divides action_dim");
   if (!grad_actions && (!actions || !targets || !loss)) return fv_fail(FV_ERR_ARG, "head_backward: need grad_actions or (actions, targets, loss)");
   if (B <= 0) return fv_fail(FV_ERR_ARG, "head_backward: B must be positive");
   (void)drop_p;  // the multiplier keep/(1-p) is stored in saved.mask
@@ -374,7 +473,12 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   const dim3 blk(256);
   const unsigned b8 = cdiv(B, 8);
   const float* ga = grad_actions;
-  if (!ga) {
+  if (!ga && chunked) {
+    float* part = g2 + (size_t)B * wmax + 16;   // behind everything the layers below use; the 64 floats of slack cover the rounding of B * da and this gap (head_bwd_scratch_bytes)
+    const int rc = launch_chunk_loss(actions, targets, hl->pad, ga_own, part, loss, hl->metrics, (long)B * d.da, d.da / hl->chunk, hl->kind, hl->beta, loss_scale, s);
+    if (rc != FV_OK) return rc;
+    ga = ga_own;
+  } else if (!ga) {
     hipLaunchKernelGGL(mse_kernel, dim3(1), blk, 0, s, actions, targets, loss, ga_own, B * d.da, loss_scale);
     ga = ga_own;
   }

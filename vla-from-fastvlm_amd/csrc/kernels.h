@@ -300,12 +300,21 @@ struct HeadIoNorm { const float *state_mean, *state_istd, *action_mean, *action_
 int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, const float* states, int B,
                         int training, float drop_p, uint64_t seed, uint64_t offset, float* actions, float* saved,
                         hipStream_t s, const HeadIoNorm* io = nullptr);
+// the fused loss of launch_head_backward (fv_head_set_loss / fv_head_set_loss_mask): kind FV_LOSS_*, beta of smooth-L1, chunk = K steps of da / K action
+// dimensions each, pad = device (B, K) bytes or null, metrics = 2 device floats { masked MSE, valid fraction }.  null, or MSE without a mask: mse_kernel as ever
+struct HeadLoss { int kind; float beta; int chunk; const uint8_t* pad; float* metrics; };
 // grad_actions != null: generic backward from dL/dactions (loss untouched); else fused MSE(actions, targets) + backward
 // d_pooled (optional, [B][feat]): dL/d(pooled feature) -- the gradient an UNFROZEN backbone continues from
 int launch_head_backward(const HeadDims& d, const float* P, const float* grad_actions, const float* actions,
                          const float* targets, int B, float drop_p, const float* saved, float* loss, float* G,
-                         float* scratch, hipStream_t s, float* d_pooled = nullptr, float loss_scale = 1.0f);   // loss_scale: the fused MSE's dL/dactions times a power of two
+                         float* scratch, hipStream_t s, float* d_pooled = nullptr, float loss_scale = 1.0f,    // loss_scale: the fused loss's dL/dactions times a power of two
+                         const struct HeadLoss* hl = nullptr);
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
+// the chunked loss alone (what launch_head_backward runs when HeadLoss asks for it): a, t, g (n) f32, pad (n / A) bytes or null, partial
+// chunk_loss_partial_floats() floats of scratch, loss 1 float, metrics 2 floats
+size_t chunk_loss_partial_floats();
+int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, float* loss, float* metrics, long n, int A, int kind,
+                      float beta, float loss_scale, hipStream_t s);
 size_t adamw_scratch_bytes();  // norm_scratch of launch_adamw_clip: [0] = sum of squares, [1..] per-block partials
 int launch_axpy(float* y, const float* x, int64_t n, const float* scale_dev, hipStream_t s);  // y += x, or y *= *scale_dev when x is null
 int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,

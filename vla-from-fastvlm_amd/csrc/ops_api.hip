@@ -231,4 +231,10 @@ int fv_op_lora_direct(int kind, int part_mask, int rank, int Np, int K, int qd, 
                                 scratch_floats, static_cast<hipStream_t>(s));
 }
 
+int fv_op_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, size_t partial_floats, float* loss, float* metrics,
+                     int64_t n, int A, int kind, float beta, float loss_scale, fv_stream s) {
+  if (partial_floats < fv::chunk_loss_partial_floats()) return fv_fail(FV_ERR_ARG, "fv_op_chunk_loss: partial needs %zu floats", fv::chunk_loss_partial_floats());
+  return fv::launch_chunk_loss(a, t, pad, g, partial, loss, metrics, (long)n, A, kind, beta, loss_scale, static_cast<hipStream_t>(s));
+}
+
 }  // extern "C"

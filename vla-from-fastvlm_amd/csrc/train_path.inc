@@ -659,7 +659,7 @@ static int train_forward_backward_impl(fv_handle* h, const float* flat_params, c
   // ------------------------------------------------------------------------------------------------ backward
   float *dpooled = c.at<float>(tp.dpooled), *xg = c.at<float>(tp.xg), *dxg = c.at<float>(tp.dxg);
   FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p, head_saved, loss, gbuf, c.at<float>(tp.head_scr), s, dpooled,
-                                                      std::ldexp(1.0f, h->train.loss_scale_log2)));
+                                                      std::ldexp(1.0f, h->train.loss_scale_log2), &h->loss));
   c.bucket_done(TB_HEAD);
   // final norm on the pooled rows; the residual-gradient stream starts as zero everywhere else
   FV_TRY(fv::launch_pool_rows(c.X_in(L), xg, lens, B, Tt, Ni, H, 0, s));

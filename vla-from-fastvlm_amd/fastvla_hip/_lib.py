@@ -62,6 +62,13 @@ class AdamWGroup(C.Structure):      # fv_adamw_group: 32 bytes
 FV_ADAMW_SEGMENT = 8192
 
 
+class HeadLossSpec(C.Structure):    # fv_head_loss_spec: 12 bytes
+    _fields_ = [("kind", C.c_int32), ("beta", C.c_float), ("chunk", C.c_int32)]
+
+
+LOSS_KINDS = {"mse": 0, "l1": 1, "smooth_l1": 2}      # FV_LOSS_*
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
@@ -113,6 +120,9 @@ SIGNATURES = {
     "fv_head_set_io_norm": (_i, [_vp, _vp, _vp, _vp, _vp, _f]),
     "fv_head_mse_backward": (_i, [_vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     "fv_head_backward": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "fv_head_set_loss": (_i, [_vp, C.POINTER(HeadLossSpec)]),
+    "fv_head_set_loss_mask": (_i, [_vp, _vp]),
+    "fv_head_loss_metrics": (_i, [_vp, C.POINTER(_vp)]),
     "fv_grad_accumulate": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "fv_grad_scale": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "fv_comm_unique_id": (_i, [_vp, C.POINTER(RcclId)]),
@@ -182,6 +192,7 @@ OPS_SIGNATURES = {
     "fv_op_lora_direct": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, C.c_size_t, _vp]),
     "fv_op_attention_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "fv_op_rmsnorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "fv_op_chunk_loss": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _f, _f, _vp]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 

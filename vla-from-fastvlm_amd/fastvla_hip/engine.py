@@ -62,6 +62,22 @@ class AdamWGroups:
             pass
 
 
+def check_head_loss(kind, beta, chunk, action_dim: Optional[int] = None):
+    """-> (kind, beta, chunk) validated; ValueError for an unknown loss name, a beta that is not a positive finite number, chunk < 1 or a chunk that does
+    not divide the head's output width."""
+    import math
+    if kind not in _lib.LOSS_KINDS:
+        raise ValueError(f"unknown action loss '{kind}': one of {sorted(_lib.LOSS_KINDS)}")
+    beta = float(beta)
+    if not (beta > 0.0 and math.isfinite(beta)):
+        raise ValueError(f"action loss beta must be a positive finite number, got {beta}")
+    if int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError(f"chunk size must be an integer >= 1, got {chunk}")
+    if action_dim is not None and action_dim % int(chunk):
+        raise ValueError(f"chunk size {chunk} does not divide the head's output width {action_dim}")
+    return str(kind), beta, int(chunk)
+
+
 class FastVLAEngine:
     def __init__(self, model: ModelConfig, *, state_dim: int = 14, action_dim: int = 14, hidden_dim: int = 1024,
                  fusion_dim: int = 1024, device: Optional[torch.device] = None, max_batch: int = 64,
@@ -110,6 +126,8 @@ class FastVLAEngine:
         offs = (C.c_int64 * 13)()
         _lib.check(self.lib.fv_head_layout(self.h, C.byref(offs)), "fv_head_layout")
         self.head_offsets = list(offs)
+        self.head_loss = dict(kind="mse", beta=1.0, chunk=1)      # set_head_loss
+        self._pad_keep: Optional[torch.Tensor] = None
         self.loaded = False
 
     def close(self):
@@ -539,17 +557,72 @@ class FastVLAEngine:
         with torch.cuda.device(self.device):
             _lib.check(self.lib.fv_head_set_io_norm(self.h, *[t.data_ptr() for t in keep], float(eps)), "fv_head_set_io_norm", self.h)
 
+    # ---------------------------------------------------------------- action chunks: the loss of the fused backward
+    def set_head_loss(self, kind: str = "mse", beta: float = 1.0, chunk: int = 1) -> None:
+        """The loss every later head_backward / train_*forward_backward evaluates (fv_head_set_loss): kind "mse" | "l1" | "smooth_l1" over chunks of `chunk`
+        steps (the head's action_dim = chunk * A).  The defaults are the library's own: the plain MSE kernel."""
+        kind, beta, chunk = check_head_loss(kind, beta, chunk, self.head_dims["da"])
+        if (kind, beta, chunk) == ("mse", 1.0, 1):
+            _lib.check(self.lib.fv_head_set_loss(self.h, None), "fv_head_set_loss", self.h)
+        else:
+            spec = _lib.HeadLossSpec(_lib.LOSS_KINDS[kind], beta, chunk)
+            _lib.check(self.lib.fv_head_set_loss(self.h, C.byref(spec)), "fv_head_set_loss", self.h)
+        self.head_loss = dict(kind=kind, beta=beta, chunk=chunk)
+
+    def loss_is_chunked(self, pad) -> bool:
+        """whether a loss evaluation with this mask runs the chunked kernel (and writes head_loss_metrics) or the plain MSE kernel"""
+        return pad is not None or self.head_loss["kind"] != "mse"
+
+    def _pad_arg(self, pad, B: int) -> Optional[torch.Tensor]:
+        if pad is None:
+            return None
+        K = self.head_loss["chunk"]
+        pad = torch.as_tensor(pad)
+        if tuple(pad.shape) != (B, K):
+            raise ValueError(f"action_is_pad must be (B, chunk) = ({B}, {K}), got {tuple(pad.shape)}")
+        return (pad != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+
+    class _Mask:
+        """the padding mask on the handle for exactly one loss call: set immediately before, cleared after (a look-ahead prepare never touches it)"""
+
+        def __init__(self, eng: "FastVLAEngine", pad: Optional[torch.Tensor]):
+            self.eng, self.pad = eng, pad
+
+        def __enter__(self):
+            if self.pad is not None:
+                self.eng._pad_keep = self.pad
+                _lib.check(self.eng.lib.fv_head_set_loss_mask(self.eng.h, self.pad.data_ptr()), "fv_head_set_loss_mask", self.eng.h)
+
+        def __exit__(self, *exc):
+            if self.pad is not None:
+                _lib.check(self.eng.lib.fv_head_set_loss_mask(self.eng.h, None), "fv_head_set_loss_mask", self.eng.h)
+            return False
+
+    def head_loss_metrics(self) -> torch.Tensor:
+        """-> (2,) f32 copy of what the last chunked loss evaluation on the current stream wrote: [masked MSE, valid steps / (B * chunk)]."""
+        ptr = C.c_void_p()
+        _lib.check(self.lib.fv_head_loss_metrics(self.h, C.byref(ptr)), "fv_head_loss_metrics", self.h)
+        # a stream-ordered device copy with the library's own y += x over the metrics' 16-byte slot (0 + m == m exactly; include/fastvla_hip.h: 4 floats, two reserved zeros)
+        out = torch.zeros(4, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.fv_grad_accumulate(self.h, out.data_ptr(), ptr.value, 4, _stream()), "fv_grad_accumulate", self.h)
+        return out[:2]
+
     def head_backward(self, flat_params: torch.Tensor, actions: torch.Tensor, targets: torch.Tensor, saved: torch.Tensor,
-                      dropout_p: float = 0.0, flat_grads: Optional[torch.Tensor] = None):
+                      dropout_p: float = 0.0, flat_grads: Optional[torch.Tensor] = None, pad=None):
+        """pad: optional (B, chunk) bool, True = the step lies past the episode end and must not train."""
         B = actions.shape[0]
         self.ensure_workspace(B, 1, False)
         targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
+        if targets.numel() != actions.numel():
+            raise ValueError(f"targets must hold {tuple(actions.shape)} elements, got {tuple(targets.shape)}")
+        pad = self._pad_arg(pad, B)
         if flat_grads is None:
             flat_grads = torch.zeros(self.head_numel(), dtype=torch.float32, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.fv_head_mse_backward(self.h, flat_params.data_ptr(), actions.data_ptr(), targets.data_ptr(), B,
-                                                 float(dropout_p), saved.data_ptr(), loss.data_ptr(),
-                                                 flat_grads.data_ptr(), _stream()), "fv_head_mse_backward")
+        with self._Mask(self, pad):
+            _lib.check(self.lib.fv_head_mse_backward(self.h, flat_params.data_ptr(), actions.data_ptr(), targets.data_ptr(), B,
+                                                     float(dropout_p), saved.data_ptr(), loss.data_ptr(),
+                                                     flat_grads.data_ptr(), _stream()), "fv_head_mse_backward")
         return loss, flat_grads
 
     def head_backward_from_grad(self, flat_params: torch.Tensor, grad_actions: torch.Tensor, saved: torch.Tensor,
@@ -671,6 +744,8 @@ class FastVLAEngine:
         lens = lens.to(device=self.device, dtype=torch.int32).contiguous()
         states = states.to(device=self.device, dtype=torch.float32).contiguous()
         targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
+        if targets.numel() != B * self.head_dims["da"]:
+            raise ValueError(f"targets must hold (B, {self.head_dims['da']}) elements, got {tuple(targets.shape)}")
         tower_out = tower_out.contiguous()
         if tower_out.dtype != torch.bfloat16 or tower_out.shape != (B, self.model.tower.num_tokens, self.model.tower.out_dim):
             raise ValueError(f"tower_out must be (B, {self.model.tower.num_tokens}, {self.model.tower.out_dim}) bf16, got {tuple(tower_out.shape)} {tower_out.dtype}")
@@ -681,7 +756,7 @@ class FastVLAEngine:
 
     def train_forward_backward(self, flat_params: torch.Tensor, tower_out: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor, states: torch.Tensor,
                                targets: torch.Tensor, ws: torch.Tensor, *, training: bool = True, dropout_p: float = 0.0, seed: int = 0, offset: int = 0,
-                               flat_grads: Optional[torch.Tensor] = None, bucket_cb=None):
+                               flat_grads: Optional[torch.Tensor] = None, bucket_cb=None, pad=None):
         """One step's forward + MSE + backward over every trainable tensor (fv_train_forward_backward).  tower_out: (B, Ni, tower_out_dim)
         bf16 from vision_forward(..., return_tower_out=True).  bucket_cb(bucket, offset, numel) is called when a bucket's gradient has
         been enqueued completely.  -> (actions (B, A) in normalised space, loss (1,), flat_grads TIMES train_loss_scale())."""
@@ -698,9 +773,10 @@ class FastVLAEngine:
                     err.setdefault("exc", exc)
 
         fn = _lib.BUCKET_CB(_cb)
-        rc = self.lib.fv_train_forward_backward(self.h, flat_params.data_ptr(), tower_out.data_ptr(), ids.data_ptr(), lens.data_ptr(), states.data_ptr(),
-                                                targets.data_ptr(), B, T, int(training), float(dropout_p), seed, offset, ws_ptr, ws_bytes,
-                                                actions.data_ptr(), loss.data_ptr(), flat_grads.data_ptr(), fn, None, _stream())
+        with self._Mask(self, self._pad_arg(pad, B)):
+            rc = self.lib.fv_train_forward_backward(self.h, flat_params.data_ptr(), tower_out.data_ptr(), ids.data_ptr(), lens.data_ptr(), states.data_ptr(),
+                                                    targets.data_ptr(), B, T, int(training), float(dropout_p), seed, offset, ws_ptr, ws_bytes,
+                                                    actions.data_ptr(), loss.data_ptr(), flat_grads.data_ptr(), fn, None, _stream())
         if "exc" in err:
             raise err["exc"]
         _lib.check(rc, "fv_train_forward_backward", self.h)
@@ -742,14 +818,14 @@ class FastVLAEngine:
 
     def train_lora_forward_backward(self, flat_params: torch.Tensor, lora_params: torch.Tensor, tower_out: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor,
                                     states: torch.Tensor, targets: torch.Tensor, ws: torch.Tensor, *, training: bool = True, dropout_p: float = 0.0, seed: int = 0,
-                                    offset: int = 0, lora_grads: Optional[torch.Tensor] = None):
+                                    offset: int = 0, lora_grads: Optional[torch.Tensor] = None, pad=None):
         """The DIRECT LoRA step (fv_train_lora_forward_backward): train_forward_backward's forward and input-gradient chain, dA / dB of every adapter straight from
         the gradient rows and the kept activations -- no full-size gradient buffer, no train_lora_project.  flat_params: the master; lora_params: the trainable
         buffer.  -> (actions, loss (1,), lora_grads in the trainable layout TIMES train_loss_scale()).  Needs train_lora_begin() and the default backward options."""
         B, T, tower_out, ids, lens, states, targets, actions, loss, ws_ptr, ws_bytes = self._train_step_inputs(tower_out, ids, lens, states, targets, ws)
         if lora_grads is None:
             lora_grads = torch.empty_like(lora_params)
-        with torch.cuda.device(self.device):     # (the first call allocates the kernels' scratch)
+        with torch.cuda.device(self.device), self._Mask(self, self._pad_arg(pad, B)):     # (the first call allocates the kernels' scratch)
             rc = self.lib.fv_train_lora_forward_backward(self.h, flat_params.data_ptr(), lora_params.data_ptr(), tower_out.data_ptr(), ids.data_ptr(), lens.data_ptr(),
                                                          states.data_ptr(), targets.data_ptr(), B, T, int(training), float(dropout_p), seed, offset, ws_ptr,
                                                          ws_bytes, actions.data_ptr(), loss.data_ptr(), lora_grads.data_ptr(), _stream())

@@ -50,13 +50,15 @@ class _HeadLossFunction(torch.autograd.Function):
     backward() only scales the flat gradient by the incoming dL/dloss (fv_grad_scale) and hands out views of it."""
 
     @staticmethod
-    def forward(ctx, owner, pooled, states, targets, training, *params):
+    def forward(ctx, owner, pooled, states, targets, pad, training, *params):
         eng, flat = owner._engine(), owner._flat
         p = float(owner.config.dropout) if training else 0.0
         owner._drop_calls += 1
         actions, saved = eng.head_forward(flat, pooled, states, training=bool(training and p > 0.0), dropout_p=p,
                                           seed=owner._drop_seed, offset=owner._drop_calls, normalized_actions=True)  # a loss: normalised space
-        loss, grads = eng.head_backward(flat, actions, targets, saved, dropout_p=p)
+        loss, grads = eng.head_backward(flat, actions, targets, saved, dropout_p=p, pad=pad)
+        # the chunked loss kernel also reports the masked MSE and the valid fraction; the plain MSE path has nothing beside its loss
+        owner.last_loss_metrics = eng.head_loss_metrics() if eng.loss_is_chunked(pad) else None
         ctx.owner, ctx.grads = owner, grads
         ctx.mark_non_differentiable(actions)
         return loss[0], actions
@@ -66,22 +68,29 @@ class _HeadLossFunction(torch.autograd.Function):
         eng = ctx.owner._engine()
         eng.grad_scale(ctx.grads, grad_loss.reshape(1).to(ctx.grads.device, torch.float32).contiguous())
         views = eng.head_views(ctx.grads)
-        return (None, None, None, None, None) + tuple(views[k] for k in HEAD_KEYS)
+        return (None, None, None, None, None, None) + tuple(views[k] for k in HEAD_KEYS)
 
 
 class FastVLMWithExpert(nn.Module):
-    def __init__(self, config: FastVLAConfig) -> None:
+    def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0) -> None:
+        """chunk_size = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
+        `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library."""
         super().__init__()
+        from fastvla_hip.engine import check_head_loss
         self.config = config
+        self.action_loss, self.action_loss_beta, self.chunk_size = check_head_loss(action_loss, action_loss_beta, chunk_size)
+        self.head_width = self.chunk_size * config.action_dim
+        self.last_loss_metrics: Optional[torch.Tensor] = None    # (2,) [masked MSE, valid fraction] of the last loss the chunked kernel evaluated, else None
         self.backbone = FastVLMBackbone(config.to_backbone_config())
-        self.backbone.configure_head(state_dim=config.state_dim, action_dim=config.action_dim,
+        self.backbone.configure_head(state_dim=config.state_dim, action_dim=self.head_width,
                                      hidden_dim=config.hidden_dim, fusion_dim=config.fusion_dim)
+        self.backbone.configure_head_loss(self.action_loss, self.action_loss_beta, self.chunk_size)
         # same module tree / init as the reference so checkpoints and seeds line up
         self.state_projection = nn.Sequential(nn.LayerNorm(config.state_dim), nn.Linear(config.state_dim, config.hidden_dim), nn.SiLU())
         self.fusion = nn.Sequential(
             nn.Linear(self.backbone.output_dim + config.hidden_dim, config.fusion_dim), nn.LayerNorm(config.fusion_dim),
             nn.SiLU(), nn.Dropout(config.dropout), nn.Linear(config.fusion_dim, config.fusion_dim), nn.SiLU())
-        self.action_head = nn.Linear(config.fusion_dim, config.action_dim)
+        self.action_head = nn.Linear(config.fusion_dim, self.head_width)
         self._flat: Optional[torch.Tensor] = None
         self._drop_seed = int(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
         self._drop_calls = 0
@@ -120,6 +129,44 @@ class FastVLMWithExpert(nn.Module):
             return None
         return base
 
+    # ------------------------------------------------------------------ action chunks
+    def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
+        """the loss of every later loss evaluation / train step: "mse" | "l1" | "smooth_l1" (beta)"""
+        self.backbone.configure_head_loss(kind, beta, self.chunk_size)
+        self.action_loss, self.action_loss_beta = self.backbone._head_loss["kind"], self.backbone._head_loss["beta"]
+
+    def chunk_record(self, n_action_steps: int = 1) -> Optional[dict]:
+        """what a checkpoint records beside the tensors (hip_extras.json "action_chunk"); None with the defaults"""
+        rec = {"chunk_size": self.chunk_size, "n_action_steps": int(n_action_steps), "loss": self.action_loss, "beta": self.action_loss_beta}
+        return None if rec == {"chunk_size": 1, "n_action_steps": 1, "loss": "mse", "beta": 1.0} else rec
+
+    def chunk_targets(self, targets: torch.Tensor, pad=None):
+        """-> (targets flattened to (B, K * A), pad (B, K) bool or None).  Targets are (B, K, A); (B, A) only when K == 1 (where a longer (B, T, A) gives its
+        step 0, as ever).  pad = LeRobot's action_is_pad: True where a chunk step lies past the episode end.  Idempotent: what it returned passes through."""
+        K, A = self.chunk_size, self.config.action_dim
+        steps = None
+        if targets.ndim == 3:
+            steps = targets.shape[1]
+            if K == 1:
+                targets = targets[:, 0]
+            elif tuple(targets.shape[1:]) != (K, A):
+                raise ValueError(f"targets must be (B, {K}, {A}), got {tuple(targets.shape)}")
+            else:
+                targets = targets.reshape(targets.shape[0], K * A)
+        elif K > 1 and not (targets.ndim == 2 and targets.shape[1] == K * A):      # ((B, K * A): this function's own output)
+            raise ValueError(f"targets must be (B, {K}, {A}) with chunk_size={K}, got {tuple(targets.shape)}")
+        if pad is not None:
+            pad = torch.as_tensor(pad)
+            if K == 1 and pad.ndim == 2 and steps is not None and pad.shape[1] == steps:
+                pad = pad[:, :1]
+            if tuple(pad.shape) != (targets.shape[0], K):
+                raise ValueError(f"action_is_pad must be (B, {K}), got {tuple(pad.shape)}")
+            pad = pad != 0
+        return targets, pad
+
+    def _shape_actions(self, actions: torch.Tensor) -> torch.Tensor:
+        return actions.view(actions.shape[0], self.chunk_size, self.config.action_dim) if self.chunk_size > 1 else actions
+
     # ------------------------------------------------------------------ forward
     def features(self, images, tasks: List[str], device=None) -> torch.Tensor:
         return self.backbone(images, tasks, device=device)
@@ -137,30 +184,33 @@ class FastVLMWithExpert(nn.Module):
             # eval mode with autograd on: the library kept the actions in normalised space (its backward differentiates the head, not
             # the folded statistics); finish `* action_std + action_mean` here, in torch, so that predict() returns the SAME space with
             # and without torch.no_grad() -- and the result stays differentiable
-            std = torch.as_tensor(io["action_std"], dtype=torch.float32, device=actions.device).reshape(1, -1)
-            mean = torch.as_tensor(io["action_mean"], dtype=torch.float32, device=actions.device).reshape(1, -1)
+            std = torch.as_tensor(io["action_std"], dtype=torch.float32, device=actions.device).reshape(1, -1).repeat(1, self.chunk_size)
+            mean = torch.as_tensor(io["action_mean"], dtype=torch.float32, device=actions.device).reshape(1, -1).repeat(1, self.chunk_size)
             actions = actions * std + mean
-        return actions
+        return self._shape_actions(actions)
 
-    def head_loss(self, pooled: torch.Tensor, states: torch.Tensor, targets: torch.Tensor):
-        """-> (loss 0-dim, actions): MSE of the head's prediction against `targets`, differentiable w.r.t. the 12 head
-        tensors, with no torch operator between the pooled feature and the loss."""
+    def head_loss(self, pooled: torch.Tensor, states: torch.Tensor, targets: torch.Tensor, pad=None):
+        """-> (loss 0-dim, actions): the loss (MSE unless set_action_loss chose another) of the head's prediction against `targets`, differentiable w.r.t.
+        the 12 head tensors, with no torch operator between the pooled feature and the loss.  pad: optional (B, K) bool, True = the step does not train."""
         self.materialize(pooled.device)
         states = states.to(pooled.device, torch.float32)
         targets = targets.to(pooled.device, torch.float32).contiguous()
         if states.ndim != 2 or states.shape[1] != self.config.state_dim:
             raise ValueError(f"states must be (B,{self.config.state_dim}), got {tuple(states.shape)}")
-        if targets.shape != (pooled.shape[0], self.config.action_dim):
+        targets, pad = self.chunk_targets(targets, pad)
+        if targets.shape != (pooled.shape[0], self.head_width):
             raise ValueError(f"targets must be (B,{self.config.action_dim}), got {tuple(targets.shape)}")
-        return _HeadLossFunction.apply(self, pooled, states, targets, self.training, *self.head_parameters())
+        loss, actions = _HeadLossFunction.apply(self, pooled, states, targets.contiguous(), pad, self.training, *self.head_parameters())
+        return loss, self._shape_actions(actions)
 
     def forward(self, images: torch.Tensor, states: torch.Tensor, tasks: List[str], device: torch.device | None = None) -> torch.Tensor:
         if device is None:
             device = images.device
         return self.head(self.features(images, tasks, device=device), states)
 
-    def forward_loss(self, images, states, tasks: List[str], targets: torch.Tensor, device: torch.device | None = None):
+    def forward_loss(self, images, states, tasks: List[str], targets: torch.Tensor, device: torch.device | None = None, pad=None):
         """-> (loss, actions) for `compute_loss` / the LeRobot `forward(batch)`."""
         if device is None:
             device = images.device
-        return self.head_loss(self.features(images, tasks, device=device), states, targets)
+        targets, pad = self.chunk_targets(targets, pad)     # (shape errors before the backbone runs)
+        return self.head_loss(self.features(images, tasks, device=device), states, targets, pad)

@@ -5,6 +5,7 @@ vla_fastvlm.training.Trainer and bench.py drive."""
 from __future__ import annotations
 
 import os
+from collections import deque
 from typing import Dict, List, Optional
 
 import torch
@@ -15,14 +16,42 @@ from .fastvlm_with_expert import FastVLMWithExpert
 from .processor_fastvla import FastVLAProcessor
 
 
+def resolve_chunk_options(chunk_size=None, n_action_steps=None, action_loss=None, action_loss_beta=None) -> Dict:
+    """-> {"chunk_size", "n_action_steps", "loss", "beta"}: explicit arguments, else the FASTVLA_* twins, else the defaults (1, 1, "mse", 1.0).  ValueError for
+    n_action_steps outside 1 .. chunk_size, an unknown loss name or a non-positive beta."""
+    from fastvla_hip.engine import check_head_loss
+
+    def pick(arg, env, cast, default):
+        if arg is not None:
+            return arg
+        raw = (os.environ.get(env) or "").strip()
+        return cast(raw) if raw else default
+
+    K = pick(chunk_size, "FASTVLA_CHUNK_SIZE", int, 1)
+    loss, beta, K = check_head_loss(pick(action_loss, "FASTVLA_ACTION_LOSS", str, "mse"), pick(action_loss_beta, "FASTVLA_ACTION_LOSS_BETA", float, 1.0), K)
+    n = pick(n_action_steps, "FASTVLA_N_ACTION_STEPS", int, 1)
+    if int(n) != n or n < 1 or n > K:
+        raise ValueError(f"n_action_steps must be an integer in 1 .. chunk_size. Got n_action_steps={n}, chunk_size={K}.")
+    return {"chunk_size": K, "n_action_steps": int(n), "loss": loss, "beta": beta}
+
+
 class FastVLAPolicy(nn.Module):
     config_class = FastVLAConfig
     name = "fastvla"
 
-    def __init__(self, config: FastVLAConfig | None = None) -> None:
+    def __init__(self, config: FastVLAConfig | None = None, chunk_size: Optional[int] = None, n_action_steps: Optional[int] = None,
+                 action_loss: Optional[str] = None, action_loss_beta: Optional[float] = None) -> None:
+        """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
+        head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
+        (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
+        "smooth_l1" (action_loss_beta), evaluated in the library as sum over non-padded elements / ALL B K A elements (LeRobot's convention).
+        Environment twins an explicit argument beats: FASTVLA_CHUNK_SIZE, FASTVLA_N_ACTION_STEPS, FASTVLA_ACTION_LOSS, FASTVLA_ACTION_LOSS_BETA."""
         super().__init__()
         self.config = config or FastVLAConfig()
-        self.model = FastVLMWithExpert(self.config)
+        opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta)
+        self.n_action_steps = opts["n_action_steps"]
+        self._action_queue: deque = deque()
+        self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"])
         self.processor = FastVLAProcessor(self.config, self.model.backbone)
         self._opt_state = None
         self._unfrozen = None   # training/unfrozen.py UnfrozenState once enable_backbone_training() ran
@@ -144,21 +173,36 @@ class FastVLAPolicy(nn.Module):
         images = self.processor.prepare_images(images, device)
         states = self.processor.prepare_states(states, device)
         tasks = self.processor.prepare_tasks(tasks, batch_size=images.shape[0])
-        targets = batch["actions"]
-        if targets.ndim == 3:
-            targets = targets[:, 0]
-        mse, _pred = self.model.forward_loss(images, states, tasks, targets, device=device)
-        return {"loss": mse, "mse": mse.detach()}
+        loss, _pred = self.model.forward_loss(images, states, tasks, batch["actions"], device=device, pad=batch.get("action_is_pad"))
+        met = self.model.last_loss_metrics      # None on the plain MSE path: "mse" is then the loss itself, as ever
+        return {"loss": loss, "mse": loss.detach() if met is None else met[0]}
+
+    def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
+        """the loss of every later compute_loss / train step: "mse" | "l1" | "smooth_l1" (beta)"""
+        self.model.set_action_loss(kind, beta)
+
+    @property
+    def chunk_size(self) -> int:
+        return self.model.chunk_size
 
     @torch.inference_mode()
-    def select_action(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device) -> torch.Tensor:
+    def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device) -> torch.Tensor:
+        """-> (K, A): the whole chunk the head predicts for one observation (K = chunk_size; (1, A) without chunks)."""
         self.eval()
         tasks = self.processor.prepare_tasks(task, batch_size=1)
         action = self.forward(image.unsqueeze(0).to(device), state.unsqueeze(0).to(device), tasks, device=device)
-        return action.squeeze(0)
+        return action.reshape(self.model.chunk_size, self.config.action_dim)
+
+    @torch.inference_mode()
+    def select_action(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device) -> torch.Tensor:
+        """One action (A,) per environment step.  With n_action_steps = n > 1 the backbone runs on every n-th call: the first n rows of the predicted chunk
+        are queued and served in order; reset() empties the queue."""
+        if not self._action_queue:       # (n_action_steps = 1: a prediction on every call, row 0 served)
+            self._action_queue.extend(self.select_action_chunk(image, state, task, device)[: self.n_action_steps].unbind(0))
+        return self._action_queue.popleft()
 
     def reset(self) -> None:
-        return
+        self._action_queue.clear()
 
     # ------------------------------------------------------------------ native train step
     def prepare_batch(self, batch: Dict[str, torch.Tensor | List[str]]) -> Dict[str, torch.Tensor]:
@@ -170,12 +214,13 @@ class FastVLAPolicy(nn.Module):
         images = self.processor.prepare_images(batch["images"], dev, augment=self.training)     # (image augmentation, when on: training batches only)
         states = self.processor.prepare_states(batch["states"], dev).float()
         tasks = self.processor.prepare_tasks(batch["tasks"], batch_size=images.shape[0])
-        targets = batch["actions"].to(dev, torch.float32)
-        if targets.ndim == 3:
-            targets = targets[:, 0]
+        targets, pad = m.chunk_targets(batch["actions"].to(dev, torch.float32), batch.get("action_is_pad"))
         with torch.no_grad():
             pooled = m.features(images, tasks, device=dev)
-        return {"pooled": pooled, "states": states, "targets": targets.contiguous()}
+        prep = {"pooled": pooled, "states": states, "targets": targets.contiguous()}
+        if pad is not None:      # (B, K) bool: it travels with the prepared batch and reaches the handle only around this batch's own loss call
+            prep["pad"] = pad.to(dev)
+        return prep
 
     def _optimizer_state(self, flat: torch.Tensor) -> Dict:
         st = self._opt_state
@@ -282,11 +327,13 @@ class FastVLAPolicy(nn.Module):
             st["acc"] = torch.zeros_like(flat)
         first = st["micro"] == 1  # first micro-batch of an accumulation window: the backward writes the window's buffer
         target_buf = st["g"] if k == 1 else (st["acc"] if first else st["g"])
-        loss, grads = eng.head_backward(flat, actions, prep["targets"], saved, dropout_p=p, flat_grads=target_buf)
+        pad = prep.get("pad")
+        loss, grads = eng.head_backward(flat, actions, prep["targets"], saved, dropout_p=p, flat_grads=target_buf, pad=pad)
         if k > 1 and not first:
             eng.grad_accumulate(st["acc"], grads)
         total = st["g"] if k == 1 else st["acc"]
-        out = {"loss": loss[0], "mse": loss[0].detach(), "actions": actions, "synced": sync, "next": None}
+        out = {"loss": loss[0], "mse": eng.head_loss_metrics()[0] if eng.loss_is_chunked(pad) else loss[0].detach(), "actions": m._shape_actions(actions),
+               "synced": sync, "next": None}
         scale = 1.0
         if sync:
             st["exchange"].group = process_group

@@ -1,6 +1,10 @@
 """LeRobot policy wrapper around FastVLMWithExpert (reference:
 src/vla_fastvlm/lerobot_fastvla/modeling_fastvla.py:19-133): first VISUAL key, last timestep, task -> list[str] (+"\\n"),
-forward(batch) -> (loss, {"loss","mse"}), predict_action_chunk -> [B,1,A], select_action with the action deque."""
+forward(batch) -> (loss, {"loss","mse"}), predict_action_chunk -> [B,chunk_size,A], select_action with the action deque.
+
+config.chunk_size = K > 1 (an extension of this build: the reference accepts the field and predicts one step) widens the head to K * A: the dataset's
+(B, K, A) targets and its `action_is_pad` (B, K) train all K steps, padded ones excluded, and n_action_steps <= K of them are served per backbone run.
+The loss kind ("mse" | "l1" | "smooth_l1") comes from set_action_loss() or FASTVLA_ACTION_LOSS / FASTVLA_ACTION_LOSS_BETA."""
 from __future__ import annotations
 
 from collections import deque
@@ -29,8 +33,15 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}))
+        from ..fastvla.modeling_fastvla import resolve_chunk_options
+        opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps)      # (the loss kind: its environment twins)
+        self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
+                                       action_loss=opts["loss"], action_loss_beta=opts["beta"])
         self.reset()
+
+    def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
+        """the loss forward(batch) evaluates from now on: "mse" | "l1" | "smooth_l1" (beta)"""
+        self.model.set_action_loss(kind, beta)
 
     def _resolve_input_keys(self) -> tuple[str, list[str]]:
         feats = self.config.input_features
@@ -103,7 +114,8 @@ class FastVLAPolicy(PreTrainedPolicy):
     @torch.no_grad()
     def predict_action_chunk(self, batch: dict[str, Tensor]) -> Tensor:
         self.eval()
-        return self._predict_actions(batch).unsqueeze(1)  # [B, chunk=1, A]
+        actions = self._predict_actions(batch)
+        return actions if actions.ndim == 3 else actions.unsqueeze(1)  # [B, chunk_size, A]
 
     @torch.no_grad()
     def select_action(self, batch: dict[str, Tensor]) -> Tensor:
@@ -115,10 +127,11 @@ class FastVLAPolicy(PreTrainedPolicy):
 
     def forward(self, batch: dict[str, Tensor]) -> tuple[Tensor, dict]:
         images, states, tasks = self._prepare_inputs(batch)
-        gt = batch[ACTION]
-        if gt.ndim == 3:
-            gt = gt[:, 0]
-        # head forward + MSE (+ the head gradients autograd will ask for) in one pass through the library
-        loss, _pred = self.model.forward_loss(images, states, tasks, gt, device=images.device)
+        # head forward + loss (+ the head gradients autograd will ask for) in one pass through the library
+        # chunk_size = 1: the one target is delta index 0, the observation's own frame, which never lies past the episode end -- the (B, 1) action_is_pad
+        # every LeRobot dataset delivers is all False there and is not passed on, so default training stays on the plain MSE kernel and keeps its bits
+        pad = batch.get("action_is_pad") if self.model.chunk_size > 1 else None
+        loss, _pred = self.model.forward_loss(images, states, tasks, batch[ACTION], device=images.device, pad=pad)
         val = loss.item()
-        return loss, {"loss": val, "mse": val}
+        met = self.model.last_loss_metrics      # the chunked loss kernel's masked MSE; None on the plain MSE path, where the loss IS the MSE
+        return loss, {"loss": val, "mse": val if met is None else met[0].item()}

@@ -184,6 +184,7 @@ class FastVLMBackbone(nn.Module):
         self._weights_override: Optional[Dict[str, Tensor]] = None   # load_backbone_state(): a checkpoint's own VLM tensors
         self._io_norm: Optional[dict] = None   # dataset statistics folded into the head kernels (set_io_normalization)
         self._head_dims = dict(state_dim=14, action_dim=14, hidden_dim=1024, fusion_dim=1024)
+        self._head_loss = dict(kind="mse", beta=1.0, chunk=1)   # configure_head_loss: the fused loss of the head backward and the chunk length K
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
 
@@ -255,6 +256,26 @@ class FastVLMBackbone(nn.Module):
         self._head_dims = dict(state_dim=state_dim, action_dim=action_dim, hidden_dim=hidden_dim, fusion_dim=fusion_dim)
         self._engine = None
 
+    def configure_head_loss(self, kind: str = "mse", beta: float = 1.0, chunk: int = 1) -> None:
+        """Action chunks: the head's action_dim (configure_head) is chunk * A, and `kind` ("mse" | "l1" | "smooth_l1", beta for the last) is the loss the
+        fused head backward evaluates (FastVLAEngine.set_head_loss).  The defaults leave the library as it is."""
+        from fastvla_hip.engine import check_head_loss
+        kind, beta, chunk = check_head_loss(kind, beta, chunk, self._head_dims["action_dim"])
+        rechunk = chunk != self._head_loss["chunk"]
+        self._head_loss = dict(kind=kind, beta=beta, chunk=chunk)
+        if self._engine is not None:
+            self._engine.set_head_loss(**self._head_loss)
+            if rechunk and self._io_norm is not None:
+                self._engine.set_io_norm(**self._io_norm_for_engine())
+
+    def _io_norm_for_engine(self) -> dict:
+        """the folded statistics as the head kernels index them: the action vectors are A long in the state dict and tiled over the K steps of a chunk here"""
+        io, K = dict(self._io_norm or {}), self._head_loss["chunk"]
+        if io and K > 1:
+            for k in ("action_mean", "action_std"):
+                io[k] = torch.as_tensor(io[k], dtype=torch.float32).detach().cpu().reshape(-1).repeat(K)
+        return io
+
     def engine(self, device: torch.device | None = None) -> FastVLAEngine:
         """Create (once) the HIP engine on `device` and pack the frozen weights into it."""
         if self._engine is None:
@@ -313,8 +334,10 @@ class FastVLMBackbone(nn.Module):
                 warnings.warn(f"llm_precision={prec} refused for '{self.config.model_id}' ({exc}); falling back to llm_precision=1 "
                               "(split-bf16 operands: no range limit, 2x the decoder's MFMA work)")
                 eng = build(1)
+            if self._head_loss != dict(kind="mse", beta=1.0, chunk=1):
+                eng.set_head_loss(**self._head_loss)
             if self._io_norm is not None:
-                eng.set_io_norm(**self._io_norm)
+                eng.set_io_norm(**self._io_norm_for_engine())
             self._engine = eng
         return self._engine
 
@@ -373,7 +396,7 @@ class FastVLMBackbone(nn.Module):
         self._io_norm = None if off else dict(state_mean=state_mean, state_std=state_std, action_mean=action_mean,
                                               action_std=action_std, eps=eps)
         if self._engine is not None:
-            self._engine.set_io_norm(**(self._io_norm or {}))
+            self._engine.set_io_norm(**self._io_norm_for_engine())
 
     # The folded statistics are STATE of the policy: they travel with state_dict() (only while the folding is on, so a policy
     # that never folds keeps exactly the reference's keys) and come back through load_state_dict(), which re-applies them.

@@ -248,6 +248,17 @@ class Trainer:
                                                                                 "lora_direct": un.lora_direct, "lora_dora": bool(un.lora.get("dora")),
                                                                                 "lora_rslora": bool(un.lora.get("rslora"))}
                                                                                if un.lora is not None else {}), **un.optim_kwargs())
+        from ..utils.checkpoint import check_head_width, read_extras
+        core = getattr(self.model, "model", None)
+        if hasattr(core, "chunk_size"):      # a chunked head resumes into a model built with the same chunk length: say so by name, not as a shape error
+            have = read_extras(p).get("action_chunk") or {}
+            if int(have.get("chunk_size", 1)) != core.chunk_size:
+                raise ValueError(f"{p}: the checkpoint records chunk_size={have.get('chunk_size', 1)}, this run's policy was built with chunk_size={core.chunk_size}")
+            check_head_width(state, core.config.action_dim, have, p)
+            was, now = (have.get("loss", "mse"), float(have.get("beta", 1.0))), (core.action_loss, float(core.action_loss_beta))
+            if was != now:      # legitimate (the loss is the caller's choice), but never silent
+                import warnings
+                warnings.warn(f"{p}: the checkpointed run trained with action loss {was[0]} (beta {was[1]}), this run uses {now[0]} (beta {now[1]})")
         own = self.model.state_dict()
         # `.io_norm.` / splice-mode keys exist in state_dict() only while they are on, so a freshly built model does not list them -- let them
         # through (FastVLMBackbone._load_from_state_dict re-applies them)

@@ -246,9 +246,7 @@ class UnfrozenState:
         images = pol.processor.prepare_images(batch["images"], dev, augment=pol.training)     # (image augmentation, when on: training batches only)
         states = pol.processor.prepare_states(batch["states"], dev).float()
         tasks = pol.processor.prepare_tasks(batch["tasks"], batch_size=images.shape[0])
-        targets = batch["actions"].to(dev, torch.float32)
-        if targets.ndim == 3:
-            targets = targets[:, 0]
+        targets, pad = pol.model.chunk_targets(batch["actions"].to(dev, torch.float32), batch.get("action_is_pad"))
         pix = bb._prepare_images_tensor(images, dev, augment=pol.training)
         tower_out = None
         if not self.train_tower:           # a trainable tower's forward depends on the parameters: it belongs to step()
@@ -261,8 +259,11 @@ class UnfrozenState:
         if Tp != T:
             ids = torch.nn.functional.pad(ids, (0, Tp - T))
             mask = torch.nn.functional.pad(mask, (0, Tp - T))
-        return {"tower_out": tower_out, "pix": pix if self.train_tower else None, "ids": ids, "lens": mask.to(torch.int32).sum(1).to(torch.int32), "states": states,
+        prep = {"tower_out": tower_out, "pix": pix if self.train_tower else None, "ids": ids, "lens": mask.to(torch.int32).sum(1).to(torch.int32), "states": states,
                 "targets": targets.contiguous()}
+        if pad is not None:      # (B, K) bool: set on the handle only around this batch's own step (a look-ahead prepare leaves the step in flight alone)
+            prep["pad"] = pad.to(dev)
+        return prep
 
     def step(self, batch: Optional[Dict] = None, *, lr: float, betas=(0.9, 0.95), eps: float = 1e-8, weight_decay: float = 1e-4,
              max_grad_norm: Optional[float] = 1.0, process_group=None, prepared: Optional[Dict] = None, grad_accum_steps: int = 1,
@@ -295,11 +296,11 @@ class UnfrozenState:
             tower_out = eng.train_tower_forward(prep["pix"], tws)
         if self.lora_direct:
             actions, loss, _ = eng.train_lora_forward_backward(self.flat, self.lflat, tower_out, prep["ids"], prep["lens"], prep["states"], prep["targets"], ws,
-                                                               training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, lora_grads=self.lg)
+                                                               training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, lora_grads=self.lg, pad=prep.get("pad"))
         else:
             actions, loss, _ = eng.train_forward_backward(self.flat, tower_out, prep["ids"], prep["lens"], prep["states"], prep["targets"], ws,
                                                           training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, flat_grads=self.g,
-                                                          bucket_cb=self.bucketed.bucket_ready if overlap else None)
+                                                          bucket_cb=self.bucketed.bucket_ready if overlap else None, pad=prep.get("pad"))
         if self.train_tower:
             eng.train_tower_backward(prep["pix"], dto, tws, self.g, bucket_cb=self.bucketed.bucket_ready if overlap else None)
         total = self.g
@@ -315,7 +316,8 @@ class UnfrozenState:
             else:
                 eng.grad_accumulate(self.acc, total)
             total = self.acc
-        out = {"loss": loss[0], "mse": loss[0].detach(), "actions": actions, "synced": sync, "next": None}
+        out = {"loss": loss[0], "mse": eng.head_loss_metrics()[0] if eng.loss_is_chunked(prep.get("pad")) else loss[0].detach(),
+               "actions": m._shape_actions(actions), "synced": sync, "next": None}
         if sync:
             if overlap:
                 scale = self.bucketed.finish(eng.device)

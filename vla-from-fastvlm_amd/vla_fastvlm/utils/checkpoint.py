@@ -31,6 +31,8 @@ EXTRAS_FILE = "hip_extras.json"
 # own; EXTRAS_FILE names it under "lora" = {"rank", "alpha", "targets", "file", "direct"}, and a directory whose extras name adapters that are not there does not
 # load.  "dora" / "rslora" (the adapters' variants) are there only when true: a plain run's record is what it always was, and a record without them is plain LoRA.
 # "direct" records the run's backward mode (the direct LoRA backward; absent = projected): the default when loading has to switch LoRA mode on itself
+# "action_chunk" = {"chunk_size", "n_action_steps", "loss", "beta"} -- only when something differs from (1, 1, "mse", 1.0): the head of a chunked policy is
+# K * A wide, which the reference's config cannot say; a plain policy's extras file is byte for byte what it was
 LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
@@ -71,6 +73,15 @@ def check_resume_optim(recorded, current) -> None:
                          "resume with the checkpoint's options (lr_scales / no_decay / layer_decay / lora_plus_ratio / freeze or their FASTVLA_* twins)")
 
 
+def check_head_width(state: dict, action_dim: int, chunk: dict, where="") -> None:
+    """the action head of the file against what policy_config.json and the extras record say: a wide head without a record does not load"""
+    w = state.get("model.action_head.weight")
+    want = int((chunk or {}).get("chunk_size", 1)) * int(action_dim)
+    if w is not None and w.shape[0] != want:
+        raise ValueError(f"{where}: model.action_head.weight is {tuple(w.shape)}, but action_dim={action_dim} with "
+                         f"{'chunk_size=' + str(chunk['chunk_size']) if chunk else 'no action_chunk record in ' + EXTRAS_FILE} asks for ({want}, {w.shape[1]})")
+
+
 def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None = None) -> FastVLAPolicy:
     root = Path(checkpoint_dir)
     cfg_path, sd_path = root / "policy_config.json", root / "policy_state_dict.pt"
@@ -79,8 +90,13 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
     payload = json.loads(cfg_path.read_text())
     if "vlm_model_name" not in payload:
         raise ValueError("legacy FastVLMPolicy checkpoints (nested backbone config) are not supported by the HIP path")
-    policy = FastVLAPolicy(FastVLAConfig(**payload))
+    config = FastVLAConfig(**payload)
     state = torch.load(sd_path, map_location="cpu")
+    chunk = read_extras(root).get("action_chunk") or {}
+    check_head_width(state, config.action_dim, chunk, root)
+    # the file decides: no record means the record's defaults (1, 1, "mse", 1.0), whatever the environment twins say -- a plain checkpoint loads as a plain policy
+    policy = FastVLAPolicy(config, chunk_size=int(chunk.get("chunk_size", 1)), n_action_steps=int(chunk.get("n_action_steps", 1)),
+                           action_loss=chunk.get("loss", "mse"), action_loss_beta=float(chunk.get("beta", 1.0)))
     vlm = {k[len(BACKBONE_PREFIX):]: v for k, v in state.items() if k.startswith(BACKBONE_PREFIX)}
     if vlm:
         policy.model.backbone.load_backbone_state(vlm)
@@ -143,6 +159,9 @@ def save_policy_checkpoint(policy: FastVLAPolicy, checkpoint_dir: str, include_b
     aug = policy.model.backbone.augmentation_record()
     if aug is not None:      # (written only when on) the run's image augmentation: its options and seed; the batch counter travels in optimizer.pt
         extras["augment"] = {"options": aug["options"], "seed": aug["seed"]}
+    rec = policy.model.chunk_record(getattr(policy, "n_action_steps", 1)) if hasattr(policy.model, "chunk_record") else None
+    if rec is not None:      # (written only when something differs from the defaults)
+        extras["action_chunk"] = rec
     if any(extras.values()):
         (d / EXTRAS_FILE).write_text(json.dumps(extras, indent=2))
     if include_backbone:
