@@ -315,6 +315,13 @@ int fv_adamw_groups_destroy(fv_handle* h, fv_adamw_groups* groups);
  * Asynchronous on s, allocates nothing.  The table owns the partial sums, so ONE step may be in flight per table. */
 int fv_adamw_clip_step_groups(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, int64_t n, const fv_adamw_hparams* hp,
                               const fv_adamw_groups* groups, int64_t step, float* grad_norm_out, float* group_norms_out, fv_stream s);
+/* fused clip + AdamW + EMA: as fv_adamw_clip_step (groups == NULL) or fv_adamw_clip_step_groups, and ema <- ema + ema_weight (p_new - ema)
+ * in the same pass.  ema: n floats, same alignment rule as flat_params on the path taken.  ema_weight in [0, 1] (1 - decay; 1 copies, 0 leaves ema alone).
+ * One more read and one more write of 4 bytes per element beside the step's own traffic; p, m, v, the norm and the group norms are those of the step without
+ * ema, bit for bit, and both paths give the same ema bits for the same p_new.  A frozen group's ema keeps its bits.  FV_ERR_ARG, launching nothing, for: a
+ * null ema; ema overlapping flat_params, flat_grads, m or v; ema_weight outside [0, 1] or NaN; with a table, an ema that is not 16-byte aligned. */
+int fv_adamw_clip_step_ema(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, float* ema, float ema_weight, int64_t n,
+                           const fv_adamw_hparams* hp, const fv_adamw_groups* groups, int64_t step, float* grad_norm_out, float* group_norms_out, fv_stream s);
 
 /* gradient accumulation (training/trainer.py:96,171: accelerate sums micro-batch gradients before the optimiser step):
  * acc += grads over n floats; both 16-byte aligned flat head buffers. */

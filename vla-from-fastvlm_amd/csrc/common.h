@@ -308,6 +308,15 @@ __device__ __forceinline__ void adamw_update(float& p, float g, float& m, float&
   v = vi;
 }
 
+// ONE element of the exponential moving average the EMA instances of the two kernels keep beside p: e <- e + w (p_new - e), w = 1 - decay.  Written once, with
+// the fma spelled out as above, so the scalar kernel and the float4 loop give the same bits.  One rounding of the difference and one of the fma; e == p_new is a
+// fixed point for every w (the difference is an exact 0).  w == 1 returns p_new itself: fma(1, p_new - e, e) would round the difference first.  w == 0 never
+// gets here: the launchers then run the plain instance, which knows no e.
+__device__ __forceinline__ float ema_update(float e, float p_new, float w) {
+#pragma clang fp contract(off)
+  return w == 1.0f ? p_new : __builtin_fmaf(w, p_new - e, e);
+}
+
 // XCD-aware bijective remap of a 1-D grid: blocks b and b+8 share an XCD (round-robin dispatch), so give each XCD a
 // contiguous run of logical ids (neighbouring tiles then share one L2).  Speed only, never correctness.
 __device__ __forceinline__ int xcd_remap(int b, int nwg) {

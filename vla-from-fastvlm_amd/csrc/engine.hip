@@ -1523,6 +1523,17 @@ int fv_adamw_clip_step_groups(fv_handle* h, float* flat_params, const float* fla
   return fv::launch_adamw_clip_groups(flat_params, flat_grads, m, v, n, *hp, groups->t, step, grad_norm_out, group_norms_out, static_cast<hipStream_t>(s));
 }
 
+int fv_adamw_clip_step_ema(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, float* ema, float ema_weight, int64_t n,
+                           const fv_adamw_hparams* hp, const fv_adamw_groups* groups, int64_t step, float* grad_norm_out, float* group_norms_out, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !hp) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_ema: null argument");
+  if (!ema) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_ema: ema is null");
+  if (groups)
+    return fv::launch_adamw_clip_groups(flat_params, flat_grads, m, v, n, *hp, groups->t, step, grad_norm_out, group_norms_out, static_cast<hipStream_t>(s), ema,
+                                        ema_weight);
+  if (group_norms_out) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_ema: group_norms_out needs a groups table");
+  return fv::launch_adamw_clip(flat_params, flat_grads, m, v, n, *hp, step, h->norm_scratch, grad_norm_out, static_cast<hipStream_t>(s), ema, ema_weight);
+}
 
 // ---- gradient accumulation helpers (training/trainer.py:96,171: accelerate's accumulate() sums micro-batch gradients)
 int fv_grad_accumulate(fv_handle* h, float* acc, const float* grads, int64_t n, fv_stream s) {

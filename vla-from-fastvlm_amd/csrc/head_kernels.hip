@@ -329,10 +329,14 @@ __global__ __launch_bounds__(256) void sumsq_fold_kernel(float* __restrict__ par
   if (threadIdx.x == 0) partial[0] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// EMA instance (fv_adamw_clip_step_ema): also e <- ema_update(e, p_new, ema_w) while p_new is in its register, 8 more bytes per element.  The plain instance
+// never looks at e / ema_w: it is the kernel as it was.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ v, long n,
                                                      fv_adamw_hparams hp, float bc1, float bc2_sqrt,
-                                                     const float* __restrict__ sumsq, float* __restrict__ norm_out) {
+                                                     const float* __restrict__ sumsq, float* __restrict__ norm_out,
+                                                     float* __restrict__ e, float ema_w) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   // torch clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max = 1)
   const float norm = sqrtf(*sumsq) * hp.grad_scale;
@@ -345,6 +349,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   p[i] = pi;
   m[i] = mi;
   v[i] = vi;
+  if constexpr (EMA) e[i] = ema_update(e[i], pi, ema_w);
 }
 
 // y += x (x != null) or y *= *scale (x == null): gradient accumulation over micro-batches / an upstream loss gradient
@@ -397,6 +402,16 @@ Saved carve(const HeadDims& d, int B, float* base) {
   return s;
 }
 }  // namespace
+
+// the EMA operand of both fused steps: a buffer of its own (the kernels hold p, g, m, v, e as __restrict__) and a weight in [0, 1]
+int check_adamw_ema(const char* who, const float* p, const float* g, const float* m, const float* v, const float* ema, float ema_weight, int64_t n) {
+  if (!(ema_weight >= 0.f && ema_weight <= 1.f)) return fv_fail(FV_ERR_ARG, "%s: ema_weight %g outside [0, 1]", who, (double)ema_weight);
+  const uintptr_t e0 = (uintptr_t)ema, bytes = (uintptr_t)n * sizeof(float);
+  const struct { const float* q; const char* name; } others[4] = {{p, "flat_params"}, {g, "flat_grads"}, {m, "m"}, {v, "v"}};
+  for (const auto& o : others)
+    if (e0 < (uintptr_t)o.q + bytes && (uintptr_t)o.q < e0 + bytes) return fv_fail(FV_ERR_ARG, "%s: ema aliases %s", who, o.name);
+  return FV_OK;
+}
 
 size_t adamw_scratch_bytes() { return (size_t)(SUMSQ_BLOCKS + 4) * sizeof(float); }
 
@@ -521,9 +536,10 @@ int launch_axpy(float* y, const float* x, int64_t n, const float* scale_dev, hip
 }
 
 int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,
-                      int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s) {
+                      int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s, float* ema, float ema_weight) {
   if (!p || !g || !m || !v || !norm_scratch) return fv_fail(FV_ERR_ARG, "adamw: null pointer");
   if (n <= 0 || step < 1) return fv_fail(FV_ERR_ARG, "adamw: n and step must be positive");
+  if (ema) { const int rc = check_adamw_ema("adamw", p, g, m, v, ema, ema_weight, n); if (rc != FV_OK) return rc; }
   const unsigned nb = (unsigned)((n + 255) / 256);
   const unsigned nb4 = (unsigned)((n / 4 + 255) / 256 > 0 ? (n / 4 + 255) / 256 : 1);
   const unsigned nsb = nb4 < (unsigned)SUMSQ_BLOCKS ? nb4 : (unsigned)SUMSQ_BLOCKS;
@@ -531,7 +547,10 @@ int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, c
   hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(256), 0, s, norm_scratch, (int)nsb);
   const float bc1 = (float)(1.0 - pow((double)hp.beta1, (double)step));
   const float bc2 = (float)sqrt(1.0 - pow((double)hp.beta2, (double)step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, norm_scratch, grad_norm_out);
+  if (ema && ema_weight != 0.f)   // (weight 0 leaves the average alone: the plain instance, which never reads it)
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, ema, ema_weight);
+  else
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, (float*)nullptr, 0.f);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }

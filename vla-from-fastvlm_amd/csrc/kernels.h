@@ -317,8 +317,11 @@ int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float*
                       float beta, float loss_scale, hipStream_t s);
 size_t adamw_scratch_bytes();  // norm_scratch of launch_adamw_clip: [0] = sum of squares, [1..] per-block partials
 int launch_axpy(float* y, const float* x, int64_t n, const float* scale_dev, hipStream_t s);  // y += x, or y *= *scale_dev when x is null
+// ema != null (both launchers): the EMA instance of the step kernel, ema <- ema + ema_weight (p_new - ema) in the same pass (common.h ema_update);
+// FV_ERR_ARG when ema overlaps another operand or ema_weight is outside [0, 1].  ema_weight == 0 runs the plain instance: ema is not touched.
+int check_adamw_ema(const char* who, const float* p, const float* g, const float* m, const float* v, const float* ema, float ema_weight, int64_t n);
 int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,
-                      int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s);
+                      int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s, float* ema = nullptr, float ema_weight = 0.f);
 
 // parameter groups of the fused step (optim_kernels.hip).  The host cuts every group into segments of at most FV_ADAMW_SEGMENT floats: a segment never
 // straddles a group, every boundary is a multiple of 4 floats, the segments of a group are consecutive.  One block per segment in every kernel.
@@ -330,6 +333,6 @@ struct AdamwGroupsTable {
   int64_t n; int n_groups, n_segs;
 };
 int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
-                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s);
+                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema = nullptr, float ema_weight = 0.f);
 
 }  // namespace fv

@@ -4,7 +4,8 @@
 //   knows one group only: it trains a 3 M-parameter head).
 // The table (kernels.h AdamwGroupsTable) is built once on the host: every group cut into segments of <= FV_ADAMW_SEGMENT floats, all boundaries multiples of
 // 4 floats -- so every access below is a 16-byte one, a block reads its group's settings once (no per-element search) and a frozen segment's block leaves
-// before it has touched p, g, m or v.  Both kernels over the data move what adamw_kernel / sumsq_kernel move: 4 + 28 bytes per element.
+// before it has touched p, g, m or v.  Both kernels over the data move what adamw_kernel / sumsq_kernel move: 4 + 28 bytes per element (4 + 36 in the EMA
+// instance of the step, fv_adamw_clip_step_ema, which keeps the average e of p in the same pass).
 // Summation order is fixed (per-thread strided sums, wave butterfly, four wave sums added pairwise): no float atomics, two runs give the same bits.
 #include "kernels.h"
 
@@ -55,10 +56,13 @@ __global__ __launch_bounds__(256) void sumsq_groups_fold_kernel(const AdamwGroup
   }
 }
 
+// EMA instance (fv_adamw_clip_step_ema): e, read and written with the same 16-byte accesses, <- ema_update(e, p_new, ema_w) per lane: 4 + 36 bytes per element
+// with the norm pass.  A frozen segment's block has left before it touches e.  The plain instance never looks at e / ema_w: it is the kernel as it was.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                                             fv_adamw_hparams hp, float bc1, float bc2_sqrt, const AdamwSeg* __restrict__ segs,
                                                             const AdamwGroupDev* __restrict__ groups, const float* __restrict__ group_sum, int n_groups,
-                                                            float* __restrict__ norm_out, float* __restrict__ group_norms_out) {
+                                                            float* __restrict__ norm_out, float* __restrict__ group_norms_out, float* __restrict__ e, float ema_w) {
   const AdamwSeg sg = segs[blockIdx.x];
   const AdamwGroupDev gr = groups[sg.group];
   // torch clip_grad_norm_ over the non-frozen elements: coef = clamp(max_norm / (norm + 1e-6), max = 1), as adamw_kernel
@@ -69,41 +73,56 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     if (blockIdx.x == 0 && norm_out) *norm_out = norm;
     if (group_norms_out && (int)blockIdx.x == gr.seg_begin) group_norms_out[sg.group] = gr.frozen ? 0.f : sqrtf(group_sum[sg.group]) * hp.grad_scale;
   }
-  if (gr.frozen) return;     // p, m, v keep their bits
+  if (gr.frozen) return;     // p, m, v (and e) keep their bits
   const float lr = hp.lr * gr.lr_scale;
   float4* p4 = reinterpret_cast<float4*>(p + sg.begin);
   float4* m4 = reinterpret_cast<float4*>(m + sg.begin);
   float4* v4 = reinterpret_cast<float4*>(v + sg.begin);
   const float4* g4 = reinterpret_cast<const float4*>(g + sg.begin);
+  float4* e4 = EMA ? reinterpret_cast<float4*>(e + sg.begin) : nullptr;
   const int n4 = sg.len >> 2;
   for (int i = threadIdx.x; i < n4; i += 256) {
-    float4 pi = p4[i], mi = m4[i], vi = v4[i];
+    float4 pi = p4[i], mi = m4[i], vi = v4[i], ei;
+    if constexpr (EMA) ei = e4[i];
     const float4 gi = g4[i];
     adamw_update(pi.x, gi.x, mi.x, vi.x, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
     adamw_update(pi.y, gi.y, mi.y, vi.y, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
     adamw_update(pi.z, gi.z, mi.z, vi.z, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
     adamw_update(pi.w, gi.w, mi.w, vi.w, coef, lr, gr.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);
     p4[i] = pi; m4[i] = mi; v4[i] = vi;
+    if constexpr (EMA) {
+      ei.x = ema_update(ei.x, pi.x, ema_w); ei.y = ema_update(ei.y, pi.y, ema_w); ei.z = ema_update(ei.z, pi.z, ema_w); ei.w = ema_update(ei.w, pi.w, ema_w);
+      e4[i] = ei;
+    }
   }
 }
 
 }  // namespace
 
 int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
-                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s) {
+                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema, float ema_weight) {
   if (!p || !g || !m || !v || !t.segs || !t.groups || !t.sums) return fv_fail(FV_ERR_ARG, "adamw groups: null pointer");
   if (step < 1) return fv_fail(FV_ERR_ARG, "adamw groups: step must be positive");
   if (n != t.n) return fv_fail(FV_ERR_ARG, "adamw groups: n = %lld, the table was built for %lld", (long long)n, (long long)t.n);
   if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) != 0) return fv_fail(FV_ERR_ARG, "adamw groups: buffers must be 16-byte aligned");
   if (t.n_segs <= 0 || t.n_groups <= 0) return fv_fail(FV_ERR_ARG, "adamw groups: empty table");
+  if (ema) {
+    if (((uintptr_t)ema & 15) != 0) return fv_fail(FV_ERR_ARG, "adamw groups: ema must be 16-byte aligned");
+    const int rc = check_adamw_ema("adamw groups", p, g, m, v, ema, ema_weight, n);
+    if (rc != FV_OK) return rc;
+  }
   float* group_sum = t.sums + t.n_segs;
   hipLaunchKernelGGL(sumsq_segments_kernel, dim3(t.n_segs), dim3(256), 0, s, g, t.segs, t.groups, t.sums);
   hipLaunchKernelGGL(sumsq_groups_fold_kernel, dim3(t.n_groups), dim3(256), 0, s, t.groups, t.n_groups, (const float*)t.sums, group_sum, 0);
   hipLaunchKernelGGL(sumsq_groups_fold_kernel, dim3(1), dim3(256), 0, s, t.groups, t.n_groups, (const float*)t.sums, group_sum, 1);
   const float bc1 = (float)(1.0 - pow((double)hp.beta1, (double)step));
   const float bc2 = (float)sqrt(1.0 - pow((double)hp.beta2, (double)step));
-  hipLaunchKernelGGL(adamw_groups_kernel, dim3(t.n_segs), dim3(256), 0, s, p, g, m, v, hp, bc1, bc2, t.segs, t.groups, (const float*)group_sum, t.n_groups,
-                     grad_norm_out, group_norms_out);
+  if (ema && ema_weight != 0.f)   // (weight 0 leaves the average alone: the plain instance, which never reads it)
+    hipLaunchKernelGGL(adamw_groups_kernel<true>, dim3(t.n_segs), dim3(256), 0, s, p, g, m, v, hp, bc1, bc2, t.segs, t.groups, (const float*)group_sum, t.n_groups,
+                       grad_norm_out, group_norms_out, ema, ema_weight);
+  else
+    hipLaunchKernelGGL(adamw_groups_kernel<false>, dim3(t.n_segs), dim3(256), 0, s, p, g, m, v, hp, bc1, bc2, t.segs, t.groups, (const float*)group_sum, t.n_groups,
+                       grad_norm_out, group_norms_out, (float*)nullptr, 0.f);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }

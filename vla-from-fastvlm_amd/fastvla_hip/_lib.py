@@ -159,6 +159,7 @@ SIGNATURES = {
     "fv_adamw_groups_create": (_i, [_vp, C.POINTER(AdamWGroup), _i, _i64, C.POINTER(_vp)]),
     "fv_adamw_groups_destroy": (_i, [_vp, _vp]),
     "fv_adamw_clip_step_groups": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(AdamWHParams), _vp, _i64, _vp, _vp, _vp]),
+    "fv_adamw_clip_step_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i64, C.POINTER(AdamWHParams), _vp, _i64, _vp, _vp, _vp]),
 }
 
 # TEST-ONLY op-level entry points (include/fastvla_hip_testops.h, tests/_native/libfastvla_hip_testops.so): not part of the product library

@@ -970,12 +970,29 @@ class FastVLAEngine:
     def adamw_step(self, flat_params, flat_grads, m, v, step: int, *, lr: float, betas=(0.9, 0.95), eps: float = 1e-8,
                    weight_decay: float = 1e-4, max_grad_norm: float = 1.0, grad_scale: float = 1.0,
                    grad_norm_out: Optional[torch.Tensor] = None, groups: Optional["AdamWGroups"] = None,
-                   group_norms_out: Optional[torch.Tensor] = None) -> None:
+                   group_norms_out: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None, ema_weight: Optional[float] = None) -> None:
         """fused clip + AdamW on the flat buffers.  groups=None: fv_adamw_clip_step, one learning rate and one decay for the whole buffer.  With a table from
         adamw_groups(): fv_adamw_clip_step_groups -- lr and decay per group (`weight_decay` here is then ignored: the table carries the decays), frozen groups
-        untouched, group_norms_out (n_groups f32, device) <- every group's gradient norm."""
+        untouched, group_norms_out (n_groups f32, device) <- every group's gradient norm.  With ema= (a float32 buffer shaped like flat_params) and
+        ema_weight = 1 - decay (fastvla_hip.ema.ema_weight): fv_adamw_clip_step_ema, the same step on either path and ema <- ema + ema_weight (p_new - ema) in
+        the same pass."""
         hp = _lib.AdamWHParams(lr, betas[0], betas[1], eps, weight_decay, max_grad_norm if max_grad_norm else 0.0,
                                grad_scale)
+        if ema is not None:
+            if ema_weight is None:
+                raise ValueError("ema= needs ema_weight=")
+            if ema.dtype != torch.float32 or ema.numel() != flat_params.numel() or ema.device != flat_params.device or not ema.is_contiguous():
+                raise ValueError("ema must be a contiguous float32 buffer of flat_params' size on its device")
+            if groups is None and group_norms_out is not None:
+                raise ValueError("group_norms_out needs groups=")
+            if groups is not None and group_norms_out is not None and (group_norms_out.dtype != torch.float32 or group_norms_out.numel() < groups.n_groups):
+                raise ValueError(f"group_norms_out must hold {groups.n_groups} float32 values")
+            _lib.check(self.lib.fv_adamw_clip_step_ema(self.h, flat_params.data_ptr(), flat_grads.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(),
+                                                       float(ema_weight), flat_params.numel(), C.byref(hp), groups.handle() if groups is not None else None,
+                                                       step, _ptr(grad_norm_out), _ptr(group_norms_out), _stream()), "fv_adamw_clip_step_ema", self.h)
+            return
+        if ema_weight is not None:
+            raise ValueError("ema_weight= needs ema=")
         if groups is not None:
             if group_norms_out is not None and (group_norms_out.dtype != torch.float32 or group_norms_out.numel() < groups.n_groups):
                 raise ValueError(f"group_norms_out must hold {groups.n_groups} float32 values")

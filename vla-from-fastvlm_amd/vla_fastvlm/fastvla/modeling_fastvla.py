@@ -12,6 +12,7 @@ import torch
 from torch import nn
 
 from .configuration_fastvla import FastVLAConfig
+from .ema_state import EmaMixin
 from .fastvlm_with_expert import FastVLMWithExpert
 from .processor_fastvla import FastVLAProcessor
 
@@ -35,7 +36,7 @@ def resolve_chunk_options(chunk_size=None, n_action_steps=None, action_loss=None
     return {"chunk_size": K, "n_action_steps": int(n), "loss": loss, "beta": beta}
 
 
-class FastVLAPolicy(nn.Module):
+class FastVLAPolicy(nn.Module, EmaMixin):
     config_class = FastVLAConfig
     name = "fastvla"
 
@@ -87,6 +88,7 @@ class FastVLAPolicy(nn.Module):
         (FASTVLA_FREEZE) -- sections or "vectors" left untouched and out of the clip norm.  Factors multiply.  With none of them the step is the single-group
         one, bit for bit.  The step then also returns "group_grad_norms" (a device tensor, one norm per group) and "group_names" (their labels)."""
         from fastvla_hip import lora as _lora
+        self._ema_refuse_in_scope("enable_backbone_training()")
         if tower is None:
             tower = os.environ.get("FASTVLA_TRAIN_TOWER", "0") == "1"
         if lora_rank is None and lora_alpha is None and lora_targets is None:
@@ -134,6 +136,7 @@ class FastVLAPolicy(nn.Module):
             direct = lcfg is not None and (_lora.direct_from_env() if lora_direct is None else bool(lora_direct))
             self._unfrozen = UnfrozenState(self, bucket_min_numel=bucket_min_numel, train_tower=bool(tower), lora=lcfg, lora_seed=lora_seed, lora_direct=direct,
                                            optim=opts)
+            self._ema_attach()      # (EMA switched on before this call: the average restarts as a copy of the new trainable buffer)
         return self._unfrozen
 
     def enable_image_augmentation(self, crop_area=None, crop_ratio=None, brightness=None, contrast=None, saturation=None, seed: Optional[int] = None,
@@ -154,6 +157,7 @@ class FastVLAPolicy(nn.Module):
         (save_policy_checkpoint(include_backbone=True), FASTVLA_SAVE_BACKBONE) then writes a plain checkpoint under the reference's keys."""
         if self._unfrozen is None or self._unfrozen.lora is None:
             raise RuntimeError("merge_lora(): this policy has no LoRA adapters (enable_backbone_training(lora_rank=...))")
+        self._ema_refuse_in_scope("merge_lora()")
         self._unfrozen.merge_lora()
 
     def forward(self, images: torch.Tensor, states: torch.Tensor, tasks: List[str] | str,
@@ -296,7 +300,11 @@ class FastVLAPolicy(nn.Module):
           (1/world folded into grad_scale as well).  When `next_batch` is given, ITS frozen backbone forward is enqueued
           between the start of the all-reduce and the optimiser kernel, so the collective runs underneath it; the
           prepared batch comes back under "next" and is passed as `prepared=` to the following call.
+        * with EMA on (enable_ema() or FASTVLA_EMA_DECAY; fastvla/ema_state.py) the optimiser call of a synced micro-batch also moves the average of the
+          trainable buffer (fv_adamw_clip_step_ema) and the result gains "ema_weight", the weight 1 - d_t of the last update.
         """
+        self._ema_from_env()
+        self._ema_refuse_in_scope("a training step")
         if self._unfrozen is None and not self.config.freeze_backbone and os.environ.get("FASTVLA_TRAIN_BACKBONE", "0") == "1":
             self.enable_backbone_training()
         if self._unfrozen is not None:
@@ -304,6 +312,8 @@ class FastVLAPolicy(nn.Module):
                                       process_group=process_group, prepared=prepared, grad_accum_steps=grad_accum_steps, force_sync=force_sync)
             if self.training:
                 self.model.backbone.note_train_step()     # (the augmentation's batch counter: what a checkpoint records)
+            if self._ema is not None:
+                out["ema_weight"] = self._ema["weight"]
             if next_batch is not None:
                 # Trainer's one batch of look-ahead (training/trainer.py _train_one_epoch): an unfrozen forward depends on the update, so only the
                 # parameter-INDEPENDENT half of the next batch is prepared here, AFTER the commit (image prep, tokenisation, the tower while it is frozen)
@@ -345,6 +355,8 @@ class FastVLAPolicy(nn.Module):
             st["step"] += 1
             st["micro"] = 0
             eng.adamw_step(flat, total, st["m"], st["v"], st["step"], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                           max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=st["norm"])
+                           max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=st["norm"], **self._ema_step_args(st["step"]))
         out["grad_norm"] = st["norm"][0]
+        if self._ema is not None:
+            out["ema_weight"] = self._ema["weight"]
         return out

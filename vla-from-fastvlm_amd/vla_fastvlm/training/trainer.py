@@ -89,6 +89,8 @@ class Trainer:
         self.epoch = 0
         self.last_lr = 0.0
         self._resume_opt = None
+        if hasattr(model, "_ema_from_env"):
+            model._ema_from_env()      # FASTVLA_EMA_DECAY alone switches the EMA of the weights on (before a resume looks for its record)
 
     @property
     def is_main_process(self) -> bool:
@@ -131,6 +133,8 @@ class Trainer:
             self.model.load_optimizer_state(self._resume_opt["m"], self._resume_opt["v"], int(self._resume_opt["step"]), flat=self._resume_opt.get("flat"),
                                             train_tower=self._resume_opt.get("train_tower"), **({"lora": self._resume_opt["lora"]} if self._resume_opt.get("lora") else {}),
                                             optim=self._resume_opt.get("optim") or {})
+            if hasattr(self.model, "load_ema_record"):     # after the live weights: the average continues, or starts from them
+                self.model.load_ema_record(self._resume_opt.get("ema"))
             self._resume_opt = None
         un = getattr(self.model, "_unfrozen", None)
         if un is not None:
@@ -143,6 +147,11 @@ class Trainer:
             if st and "m" in st:
                 broadcast_flat(st["m"])
                 broadcast_flat(st["v"])
+            shadow = self.model._ema_attach() if hasattr(self.model, "_ema_attach") else None
+            if shadow is not None:
+                # the average travels with the parameters ONCE: every rank then applies the same update (same p, same weight) to the same average, so the
+                # replicas stay identical without any per-step exchange
+                broadcast_flat(shadow)
 
     def _train_one_epoch(self) -> None:
         cfg = self.config
@@ -171,6 +180,8 @@ class Trainer:
                 rec = {"train/loss": float(out["loss"]), "train/mse": float(out["mse"]), "train/lr": self.last_lr, "train/epoch": self.epoch}
                 if getattr(self, "_last_grad_norm", None) is not None:   # the LAST closed update's norm, also on logging steps that fall between two updates
                     rec["train/grad_norm"] = float(self._last_grad_norm)
+                if out.get("ema_weight") is not None:      # EMA on: the weight 1 - d_t of the last update
+                    rec["train/ema_weight"] = float(out["ema_weight"])
                 self._log(rec)
             if self.global_step % cfg.eval_steps == 0 and self.eval_dataloader is not None:
                 metrics = self.evaluate()
@@ -187,19 +198,38 @@ class Trainer:
         with open(Path(self.config.output_dir) / "logs" / "metrics.jsonl", "a", encoding="utf-8") as f:
             f.write(json.dumps(rec) + "\n")
 
-    @torch.no_grad()
-    def evaluate(self) -> Dict[str, float]:
-        if self.eval_dataloader is None:
-            return {}
-        self.model.eval()
+    # Extensions of this build (attributes, like save_backbone_weights below).  With an EMA of the weights on (policy.enable_ema() / FASTVLA_EMA_DECAY):
+    # evaluate() reports "eval/mse" from the AVERAGED weights, evaluate_live = True adds "eval/mse_live" from a second pass over the live ones;
+    # save_ema_checkpoint (FASTVLA_EMA_SAVE=0 switches it off) writes `checkpoints/<suffix>-ema/` beside every checkpoint.
+    evaluate_live: bool = False
+    save_ema_checkpoint: bool = os.environ.get("FASTVLA_EMA_SAVE", "1") != "0"
+
+    def _ema_on(self) -> bool:
+        return bool(getattr(self.model, "ema_enabled", False)) and self.model._ema_attach() is not None
+
+    def _eval_pass(self) -> float:
         total, count = 0.0, 0
         for batch in self.eval_dataloader:
             batch = move_batch_to_device(batch, self.device)
             n = batch["actions"].shape[0]
             total += float(self.model.compute_loss(batch)["mse"]) * n
             count += n
+        return total / max(count, 1)
+
+    @torch.no_grad()
+    def evaluate(self) -> Dict[str, float]:
+        if self.eval_dataloader is None:
+            return {}
+        self.model.eval()
+        if self._ema_on():
+            with self.model.ema_weights():
+                metrics = {"eval/mse": self._eval_pass()}
+            if self.evaluate_live:
+                metrics["eval/mse_live"] = self._eval_pass()
+        else:
+            metrics = {"eval/mse": self._eval_pass()}
         self.model.train()
-        return {"eval/mse": total / max(count, 1)}
+        return metrics
 
     # Extension of this build (an attribute, not a TrainingConfig field: the dataclass is the reference's contract): True writes the frozen
     # VLM tensors into policy_state_dict.pt under `model.backbone.model.*` the way the reference's state_dict() does (trainer.py:255), so
@@ -226,8 +256,15 @@ class Trainer:
             from ..utils.checkpoint import optimizer_record
             core = getattr(self.model, "model", None)
             aug = core.backbone.augmentation_record() if hasattr(getattr(core, "backbone", None), "augmentation_record") else None
-            rec = optimizer_record(st, getattr(self.model, "_unfrozen", None), self.global_step, self.update_step, augment=aug)
+            ema = self.model.ema_record() if hasattr(self.model, "ema_record") else None
+            rec = optimizer_record(st, getattr(self.model, "_unfrozen", None), self.global_step, self.update_step, augment=aug, ema=ema)
             torch.save(rec, d / "optimizer.pt")
+        if self.save_ema_checkpoint and self._ema_on():
+            # the averaged weights as a plain deployable policy: the weight files only, written while the average stands in for the live buffer
+            from ..utils.checkpoint import EMA_SUFFIX
+            with self.model.ema_weights():
+                save_policy_checkpoint(self.model, Path(self.config.output_dir) / "checkpoints" / (suffix + EMA_SUFFIX),
+                                       include_backbone=self.save_backbone_weights or self._backbone_must_travel())
 
     def _load_checkpoint(self, path: str) -> None:
         p = Path(path)

@@ -29,6 +29,9 @@ the adapted model starts as the base model bit for bit; the step is the projecte
 Parameter groups (`optim={"lr_scales", "no_decay", "layer_decay", "lora_plus_ratio", "freeze"}`, fastvla_hip/optim.py): with one of them set the optimiser step is
 fv_adamw_clip_step_groups over a table built from the trainable buffer's layout -- a learning-rate factor, a weight decay and a frozen flag per group, ONE clip
 norm over the non-frozen elements -- and the step also returns every group's gradient norm.  With none set the step is fv_adamw_clip_step, as before.
+
+EMA (policy.enable_ema(); fastvla/ema_state.py): the optimiser call of either kind becomes fv_adamw_clip_step_ema, which also moves an average of `trainable`
+in the same pass; with it off the calls are the ones above.
 """
 from __future__ import annotations
 
@@ -219,6 +222,7 @@ class UnfrozenState:
         diag(m / n) (W0 + s B A), and the magnitudes are re-initialised from it (m = its row norms, m / n == 1 exactly), so the adapted commit of the merged
         master is the plain one."""
         assert self.lora is not None
+        self.policy._ema_refuse_in_scope("merge_lora()")
         self.eng.train_lora_merge(self.flat, self.lflat)
         dora = bool(self.lora.get("dora"))
         for t in self.lora_tensors:
@@ -269,6 +273,7 @@ class UnfrozenState:
              max_grad_norm: Optional[float] = 1.0, process_group=None, prepared: Optional[Dict] = None, grad_accum_steps: int = 1,
              force_sync: bool = False) -> Dict[str, torch.Tensor]:
         pol, eng = self.policy, self.eng
+        pol._ema_refuse_in_scope("a training step")
         prep = prepared if prepared is not None else self.prepare(batch)
         B, T = prep["ids"].shape
         ws = self._workspace(B, T)
@@ -328,13 +333,15 @@ class UnfrozenState:
             self.step_count += 1
             self.micro = 0
             scale /= eng.train_loss_scale()      # every gradient of fv_train_forward_backward carries the loss scale (2^12 by default)
+            ema = pol._ema_step_args(self.step_count)      # {} with EMA off: the calls below are then the ones they were (fastvla/ema_state.py)
             if self.optim:       # parameter groups: lr / decay per group, frozen groups untouched, every group's norm (no host read: a device tensor)
                 table = self._groups_for(weight_decay)
                 eng.adamw_step(self.trainable, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                               max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm, groups=table, group_norms_out=self.group_norms)
+                               max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm, groups=table, group_norms_out=self.group_norms,
+                               **ema)
             else:
                 eng.adamw_step(self.trainable, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                               max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm)
+                               max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=self.norm, **ema)
             self.lora_adapters_zero = False
             # bf16 operand copies (and their transposes) follow the master (LoRA: W0 + s B A); per-image decoder prefixes / per-prompt features computed with
             # the OLD weights must not serve an eval between steps
