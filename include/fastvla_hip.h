@@ -503,7 +503,7 @@ int fv_profile(fv_handle* h, int enable);
 int fv_profile_read(fv_handle* h, fv_profile_entry* fam_out, fv_gemm_profile* gemm_out, int max_gemm, int* n_gemm);
 
 /* The op-level entry points of the parity tests (fv_op_*: one kernel each) are NOT part of this library: they are declared in
- * include/fastvla_hip_testops.h and built into tests/_native/libfastvla_hip_testops.so by `make` (csrc/ops_api.hip). */
+ * include/fastvla_hip_testops.h and built into vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so by `make` (csrc/ops_api.hip). */
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 /* fastvla_hip_testops.h -- TEST-ONLY op-level entry points (one kernel each) over the internals of libfastvla_hip.so.
  *
- * Built by `make -C vla-from-fastvlm_amd/csrc` into tests/_native/libfastvla_hip_testops.so (csrc/ops_api.hip); its undefined `fv::launch_*`
+ * Built by `make -C vla-from-fastvlm_amd/csrc` into vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so (csrc/ops_api.hip); its undefined `fv::launch_*`
  * references resolve against an already loaded libfastvla_hip.so (fastvla_hip._lib.load_testops() loads the product library RTLD_GLOBAL first).
  * Nothing of the product (fastvla_hip/, vla_fastvlm/, bench.py's timed region, __graft_entry__) binds these symbols: they exist so that
  * tests/test_gpu_ops.py and tools/ can check and time each kernel on its own against the oracle's op.  The product ABI a maintainer binds is
@@ -90,6 +90,26 @@ int fv_op_rope(void* qkv, int ld, int rows, int T, int heads, int kv_heads, int 
  * (gradients w.r.t. the un-rotated projections).  Runs the forward first (its output and row statistics are scratch).  D in {64, 128}. */
 int fv_op_attention_bwd(const float* qkv, int ld, const float* dO, float* dqkv, void* out_bf16_scratch, float* stat_scratch, int B, int T,
                         int heads, int kv_heads, int D, const int32_t* lens, float theta, fv_stream s);
+/* the parity-mode decoder's fp32 forward attention as the engine launches it (fv::launch_attention_f32): causal GQA over qkv fp32 rows [q | k | v] (row stride ld),
+ * scale = 1 / sqrt(D), key j visible to query i iff j <= i and j < clamp(lens[b] + len_add, 1, T) (lens NULL: T).  out: bf16 rows of stride ldo >= 2 * heads * D, the hi
+ * halves at column 0 and the remainders at column heads * D -- bf16, or with lo8 != 0 one fp8 e4m3 byte each (x 2^8) from the lo half's byte offset on.
+ * rope_table: device [T][D/2] (cos, sin) pairs the caller supplies, or NULL (qkv is then taken as already rotated).  lse: optional [B][heads][T] max + log(sum).
+ * Routes: use_split != 0 allocates the split-bf16 kernels' scratch for the call (freed after a stream sync), and launch_attention_f32 then takes them when lse is
+ * wanted or T >= 128 (head_dim 64 / 128, no pre, no lo8); otherwise head_dim 64 / 128 run the fp32-MFMA kernel and head_dim 32 the VALU kernel.
+ * pre != NULL (head_dim 64 / 128): rows (b * Np + pos) of [k | v] fp32, un-rotated, row stride ldp, for the positions < Np; qkv and out then hold ONLY the T - Np
+ * new rows of each batch entry (row b * (T - Np) + t - Np), while T, lens + len_add and the table's positions count the whole sequence.
+ * The head_dim-32 route ROTATES qkv IN PLACE (its q and k parts) when a table is given; head_dim 64 / 128 leave qkv untouched. */
+int fv_op_attention_f32(void* qkv, int ld, void* out, int ldo, int B, int T, int heads, int kv_heads, int D, const int32_t* lens, int len_add,
+                        const void* rope_table, const void* pre, int ldp, int Np, float* lse, int lo8, int use_split, fv_stream s);
+/* every output form of the decoder's RMSNorm (fv::launch_rmsnorm): y bf16 rows of stride ldy; y_lo (optional) the bf16 remainders at the same stride, or with
+ * lo8 != 0 one fp8 e4m3 byte each (x 2^8) from y_lo's row starts on; f16 != 0: y receives fp16 bits, saturating at +-65504 (y_lo must be NULL), and *sat (device,
+ * optional) grows by one per 8-element group that holds a clamped value */
+int fv_op_rmsnorm_forms(const float* x, const float* w, void* y, void* y_lo, int ldy, int rows, int H, float eps, int f16, unsigned* sat, int lo8, fv_stream s);
+/* x f32 [B][Ni + T][H]: rows t < Ni = img_tokens f32 [B][Ni][H], the others = table bf16 [vocab][H] at ids int32 [B][T] clamped to [0, vocab - 1] */
+int fv_op_embed_gather(const int32_t* ids, const void* table, const float* img_tokens, float* x, int B, int T, int Ni, int H, int vocab, fv_stream s);
+/* pooled f32 [B][H] from x f32 [B][Ttot][H]: mode 0 = RMSNorm of row Ni + max(len - 1, 0), mode 1 = mean of the RMSNorms of rows 0 .. Ni + len - 1;
+ * len = clamp(lens[b], 0, Ttot - Ni) (lens NULL: Ttot - Ni) */
+int fv_op_pool_norm(const float* x, const int32_t* lens, const float* w, float* pooled, int B, int Ttot, int Ni, int H, float eps, int mode, fv_stream s);
 /* backward of fv_op_rmsnorm: y = w x rsqrt(mean(x^2) + eps); dx (rows,H) f32 = dres (or 0) + dL/dx, dw (H) f32; scratch floats:
  * ((rows + 15) / 16 + 3) / 4 * 4 * H + 64 * H */
 int fv_op_rmsnorm_bwd(const float* x, const float* w, const float* dy, const float* dres, float* dx, float* dw, float* scratch, int rows,

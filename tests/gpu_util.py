@@ -10,7 +10,7 @@ DEV = "cuda:0"
 
 
 def lib():
-    """product entry points + the TEST-ONLY fv_op_* ones (tests/_native/libfastvla_hip_testops.so, include/fastvla_hip_testops.h)"""
+    """product entry points + the TEST-ONLY fv_op_* ones (vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so, include/fastvla_hip_testops.h)"""
     return fastvla_hip._lib.load_testops()
 
 

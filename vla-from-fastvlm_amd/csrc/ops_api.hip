@@ -1,4 +1,4 @@
-// ops_api.hip -- op-level C entry points (include/fastvla_hip_testops.h: TEST-ONLY, built into tests/_native/libfastvla_hip_testops.so, not into the product library): one kernel each, so the
+// ops_api.hip -- op-level C entry points (include/fastvla_hip_testops.h: TEST-ONLY, built into vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so, not into the product library): one kernel each, so the
 // parity tests can check every kernel of the path against the oracle on its own.  No engine state is involved.
 #include <cmath>
 #include <vector>
@@ -142,6 +142,42 @@ int fv_op_attention_bwd(const float* qkv, int ld, const float* dO, float* dqkv, 
   (void)hipFree(tab);
   if (scr) (void)hipFree(scr);
   return rc;
+}
+
+int fv_op_attention_f32(void* qkv, int ld, void* out, int ldo, int B, int T, int heads, int kv_heads, int D, const int32_t* lens, int len_add,
+                        const void* rope_table, const void* pre, int ldp, int Np, float* lse, int lo8, int use_split, fv_stream st) {
+  if (!qkv || !out) return fv_fail(FV_ERR_ARG, "attention_f32: null pointer");
+  if (B <= 0 || T <= 0 || heads <= 0 || kv_heads <= 0 || (D != 32 && D != 64 && D != 128) || ldo < 2 * heads * D)
+    return fv_fail(FV_ERR_ARG, "attention_f32: bad shape (ldo must hold the hi and lo halves)");
+  hipStream_t s = static_cast<hipStream_t>(st);
+  const int qd = heads * D;
+  bf16_t* o = static_cast<bf16_t*>(out);
+  const float scale = 1.0f / sqrtf((float)D);
+  void* scr = nullptr;   // the split-bf16 kernels' K / V records, for this call only
+  if (use_split) {
+    if (D < 64) return fv_fail(FV_ERR_UNSUPPORTED, "attention_f32: the split-bf16 kernels need head_dim 64 / 128");
+    hipError_t e = hipMalloc(&scr, fv::attention_split_scratch_bytes(B, T, kv_heads, D));
+    if (e != hipSuccess) return fv_hip_fail(e, "hipMalloc(attention scratch)");
+  }
+  const int rc = fv::launch_attention_f32(static_cast<float*>(qkv), ld, o, o + qd, ldo, B, T, heads, kv_heads, D, lens, len_add, scale, s,
+                                          static_cast<const float2*>(rope_table), static_cast<const float*>(pre), ldp, Np, lse, lo8, scr);
+  if (scr) {
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(scr);
+  }
+  return rc;
+}
+
+int fv_op_rmsnorm_forms(const float* x, const float* w, void* y, void* y_lo, int ldy, int rows, int H, float eps, int f16, unsigned* sat, int lo8, fv_stream s) {
+  return fv::launch_rmsnorm(x, w, static_cast<bf16_t*>(y), static_cast<bf16_t*>(y_lo), ldy, rows, H, eps, static_cast<hipStream_t>(s), f16, sat, lo8);
+}
+
+int fv_op_embed_gather(const int32_t* ids, const void* table, const float* img_tokens, float* x, int B, int T, int Ni, int H, int vocab, fv_stream s) {
+  return fv::launch_embed_gather(ids, static_cast<const bf16_t*>(table), img_tokens, x, B, T, Ni, H, vocab, static_cast<hipStream_t>(s));
+}
+
+int fv_op_pool_norm(const float* x, const int32_t* lens, const float* w, float* pooled, int B, int Ttot, int Ni, int H, float eps, int mode, fv_stream s) {
+  return fv::launch_pool_norm(x, lens, w, pooled, B, Ttot, Ni, H, eps, mode, static_cast<hipStream_t>(s));
 }
 
 int fv_op_rmsnorm_bwd(const float* x, const float* w, const float* dy, const float* dres, float* dx, float* dw, float* scratch, int rows,

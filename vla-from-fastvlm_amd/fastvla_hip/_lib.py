@@ -162,7 +162,7 @@ SIGNATURES = {
     "fv_adamw_clip_step_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i64, C.POINTER(AdamWHParams), _vp, _i64, _vp, _vp, _vp]),
 }
 
-# TEST-ONLY op-level entry points (include/fastvla_hip_testops.h, tests/_native/libfastvla_hip_testops.so): not part of the product library
+# TEST-ONLY op-level entry points (include/fastvla_hip_testops.h, vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so): not part of the product library
 OPS_SIGNATURES = {
     "fv_op_gemm": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "fv_op_gemm_f16": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp, C.c_size_t, _vp]),
@@ -193,6 +193,10 @@ OPS_SIGNATURES = {
     "fv_op_lora_direct": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, C.c_size_t, _vp]),
     "fv_op_attention_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp]),
     "fv_op_rmsnorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
+    "fv_op_attention_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
+    "fv_op_rmsnorm_forms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _i, _vp]),
+    "fv_op_embed_gather": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "fv_op_pool_norm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "fv_op_chunk_loss": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _f, _f, _vp]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
@@ -229,14 +233,15 @@ def load():
 
 def testops_path() -> Path:
     """The test-only op library that goes with library_path(): FASTVLA_HIP_TESTOPS_LIB, or `<name>_testops.so` beside a FASTVLA_HIP_LIB override (the tools'
-    A/B build), or tests/_native/libfastvla_hip_testops.so of this checkout."""
+    A/B build), or vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so of this checkout (beside the package, outside tests/: the
+    library belongs to the BUILD, so any version of the test files run on this build finds the entry points this build's header declares)."""
     env = os.environ.get("FASTVLA_HIP_TESTOPS_LIB")
     if env:
         return Path(env)
     if os.environ.get("FASTVLA_HIP_LIB"):
         lp = library_path()
         return lp.with_name(lp.stem + "_testops.so")
-    return Path(__file__).resolve().parents[2] / "tests" / "_native" / "libfastvla_hip_testops.so"
+    return Path(__file__).resolve().parents[1] / "testops" / "libfastvla_hip_testops.so"
 
 
 class _WithTestOps:
