@@ -90,6 +90,15 @@ int fv_op_rope(void* qkv, int ld, int rows, int T, int heads, int kv_heads, int 
  * (gradients w.r.t. the un-rotated projections).  Runs the forward first (its output and row statistics are scratch).  D in {64, 128}. */
 int fv_op_attention_bwd(const float* qkv, int ld, const float* dO, float* dqkv, void* out_bf16_scratch, float* stat_scratch, int B, int T,
                         int heads, int kv_heads, int D, const int32_t* lens, float theta, fv_stream s);
+/* fv_op_attention_bwd with every argument of fv::launch_attention_bwd the engine uses, so that each of its routes runs on its own: dO rows of stride lddo >= heads * D;
+ * out_bf16: the forward's output, bf16 rows of stride ldo >= 2 * heads * D (hi halves at column 0, remainders at column heads * D); stat: lse | delta, 2 * B * heads * T
+ * floats; key j visible to query i iff j <= i and j < clamp(lens[b] + len_add, 1, T).  part: NULL (dK / dV looped over the group's q heads in one block), or
+ * >= (heads / kv_heads) * B * T * 2 * kv_heads * D floats: with more than one q head per kv head every q head's share of dK | dV goes to part[hh][B * T][2 * kv_heads * D]
+ * and the k | v columns of dqkv are their fp32 sum in the order hh = 0, 1, ... (attn_dkv_reduce_kernel); ignored when heads == kv_heads.  use_split != 0 allocates the
+ * split-bf16 kernels' scratch for the call (forward and backward then take them); 0 runs the fp32-MFMA forward and attn_bwd_dq_kernel / attn_bwd_dkv_kernel.
+ * Arguments are checked before anything is enqueued (null pointers, D in {64, 128}, heads % kv_heads, ld % 4, lddo % 4, ldo % 8, the minimum widths). */
+int fv_op_attention_bwd_routes(const float* qkv, int ld, const float* dO, int lddo, float* dqkv, void* out_bf16, int ldo, float* stat, float* part, int B, int T,
+                               int heads, int kv_heads, int D, const int32_t* lens, int len_add, float theta, int use_split, fv_stream s);
 /* the parity-mode decoder's fp32 forward attention as the engine launches it (fv::launch_attention_f32): causal GQA over qkv fp32 rows [q | k | v] (row stride ld),
  * scale = 1 / sqrt(D), key j visible to query i iff j <= i and j < clamp(lens[b] + len_add, 1, T) (lens NULL: T).  out: bf16 rows of stride ldo >= 2 * heads * D, the hi
  * halves at column 0 and the remainders at column heads * D -- bf16, or with lo8 != 0 one fp8 e4m3 byte each (x 2^8) from the lo half's byte offset on.

@@ -118,10 +118,17 @@ int fv_op_rope(void* qkv, int ld, int rows, int T, int heads, int kv_heads, int 
   return rc;
 }
 
-int fv_op_attention_bwd(const float* qkv, int ld, const float* dO, float* dqkv, void* out_bf16_scratch, float* stat_scratch, int B, int T,
-                        int heads, int kv_heads, int D, const int32_t* lens, float theta, fv_stream st) {
-  if (!qkv || !dO || !dqkv || !out_bf16_scratch || !stat_scratch) return fv_fail(FV_ERR_ARG, "attention_bwd: null pointer");
-  if (T <= 0 || (D != 64 && D != 128)) return fv_fail(FV_ERR_UNSUPPORTED, "attention_bwd: head_dim must be 64 or 128");
+int fv_op_attention_bwd_routes(const float* qkv, int ld, const float* dO, int lddo, float* dqkv, void* out_bf16, int ldo, float* stat, float* part, int B, int T,
+                               int heads, int kv_heads, int D, const int32_t* lens, int len_add, float theta, int use_split, fv_stream st) {
+  // everything is checked before the first allocation or launch: a refused call writes nothing
+  if (!qkv || !dO || !dqkv || !out_bf16 || !stat) return fv_fail(FV_ERR_ARG, "attention_bwd: null pointer");
+  if (D != 64 && D != 128) return fv_fail(FV_ERR_UNSUPPORTED, "attention_bwd: head_dim must be 64 or 128 (got %d)", D);
+  if (B <= 0 || T <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads)
+    return fv_fail(FV_ERR_ARG, "attention_bwd: bad shape B=%d T=%d heads=%d kv_heads=%d (heads must be a multiple of kv_heads)", B, T, heads, kv_heads);
+  const int qd = heads * D;
+  if (ld % 4 || ld < (heads + 2 * kv_heads) * D) return fv_fail(FV_ERR_ARG, "attention_bwd: ld = %d must be a multiple of 4 and >= (heads + 2 kv_heads) D = %d", ld, (heads + 2 * kv_heads) * D);
+  if (lddo % 4 || lddo < qd) return fv_fail(FV_ERR_ARG, "attention_bwd: lddo = %d must be a multiple of 4 and >= heads D = %d", lddo, qd);
+  if (ldo % 8 || ldo < 2 * qd) return fv_fail(FV_ERR_ARG, "attention_bwd: ldo = %d must be a multiple of 8 and >= 2 heads D = %d (hi | lo halves)", ldo, 2 * qd);
   hipStream_t s = static_cast<hipStream_t>(st);
   std::vector<float> cs((size_t)T * D);
   fv::rope_table_host(cs.data(), T, D, theta);
@@ -129,19 +136,23 @@ int fv_op_attention_bwd(const float* qkv, int ld, const float* dO, float* dqkv, 
   FV_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&tab), cs.size() * 4));
   hipError_t e = hipMemcpy(tab, cs.data(), cs.size() * 4, hipMemcpyHostToDevice);
   int rc = e == hipSuccess ? FV_OK : fv_hip_fail(e, "hipMemcpy(rope table)");
-  const int qd = heads * D;
-  bf16_t* o = static_cast<bf16_t*>(out_bf16_scratch);
-  float* lse = stat_scratch;
-  float* delta = stat_scratch + (size_t)B * heads * T;
+  bf16_t* o = static_cast<bf16_t*>(out_bf16);
+  float* lse = stat;
+  float* delta = stat + (size_t)B * heads * T;
   const float scale = 1.0f / sqrtf((float)D);
-  void* scr = nullptr;   // the split-bf16 kernels' K / V records (the training path keeps this in its workspace)
-  if (rc == FV_OK) { e = hipMalloc(&scr, fv::attention_split_scratch_bytes(B, T, kv_heads, D)); if (e != hipSuccess) rc = fv_hip_fail(e, "hipMalloc(attention scratch)"); }
-  if (rc == FV_OK) rc = fv::launch_attention_f32(const_cast<float*>(qkv), ld, o, o + qd, 2 * qd, B, T, heads, kv_heads, D, lens, 0, scale, s, tab, nullptr, 0, 0, lse, 0, scr);
-  if (rc == FV_OK) rc = fv::launch_attention_bwd(qkv, ld, o, o + qd, 2 * qd, dO, qd, lse, delta, dqkv, B, T, heads, kv_heads, D, lens, 0, scale, tab, s, nullptr, scr);
+  void* scr = nullptr;   // the split-bf16 kernels' K / V records (the training path keeps this in its workspace); without it both launches take the fp32-MFMA kernels
+  if (rc == FV_OK && use_split) { e = hipMalloc(&scr, fv::attention_split_scratch_bytes(B, T, kv_heads, D)); if (e != hipSuccess) rc = fv_hip_fail(e, "hipMalloc(attention scratch)"); }
+  if (rc == FV_OK) rc = fv::launch_attention_f32(const_cast<float*>(qkv), ld, o, o + qd, ldo, B, T, heads, kv_heads, D, lens, len_add, scale, s, tab, nullptr, 0, 0, lse, 0, scr);
+  if (rc == FV_OK) rc = fv::launch_attention_bwd(qkv, ld, o, o + qd, ldo, dO, lddo, lse, delta, dqkv, B, T, heads, kv_heads, D, lens, len_add, scale, tab, s, part, scr);
   (void)hipStreamSynchronize(s);
   (void)hipFree(tab);
   if (scr) (void)hipFree(scr);
   return rc;
+}
+
+int fv_op_attention_bwd(const float* qkv, int ld, const float* dO, float* dqkv, void* out_bf16_scratch, float* stat_scratch, int B, int T,
+                        int heads, int kv_heads, int D, const int32_t* lens, float theta, fv_stream st) {
+  return fv_op_attention_bwd_routes(qkv, ld, dO, heads * D, dqkv, out_bf16_scratch, 2 * heads * D, stat_scratch, nullptr, B, T, heads, kv_heads, D, lens, 0, theta, 1, st);
 }
 
 int fv_op_attention_f32(void* qkv, int ld, void* out, int ldo, int B, int T, int heads, int kv_heads, int D, const int32_t* lens, int len_add,

@@ -192,6 +192,7 @@ OPS_SIGNATURES = {
     "fv_op_lora_direct_scratch_floats": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
     "fv_op_lora_direct": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, C.c_size_t, _vp]),
     "fv_op_attention_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _f, _vp]),
+    "fv_op_attention_bwd_routes": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _f, _i, _vp]),
     "fv_op_rmsnorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _vp]),
     "fv_op_attention_f32": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "fv_op_rmsnorm_forms": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _i, _vp]),
