@@ -260,7 +260,7 @@ int fv_head_mse_backward(fv_handle* h, const float* flat_params, const float* ac
  *     smooth_l1 0.5 d^2 / beta for |d| < beta, else |d| - 0.5 beta)
  * The denominator is ALL n elements, padded ones included (LeRobot's `(loss * ~pad).mean()`): micro-batches and data-parallel ranks with different pad
  * counts then still average exactly.  A padded element gives exactly 0 to the loss, the metrics and the gradient whatever its target holds (NaN, inf).
- * kind MSE with no mask launches the single-block MSE kernel it always did, for any K; everything else a many-block kernel with fixed-order partials
+ * kind MSE with no mask (and no weights: fv_head_set_loss_weights) launches the single-block MSE kernel it always did, for any K; everything else a many-block kernel with fixed-order partials
  * and a single-block fold (no float atomics: two runs agree bit for bit). */
 #define FV_LOSS_MSE 0
 #define FV_LOSS_L1 1
@@ -280,6 +280,21 @@ int fv_head_set_loss_mask(fv_handle* h, const uint8_t* pad_dev);
 /* *dev = 2 handle-owned device floats written by the chunked loss kernel (not by the plain MSE path): { sum over valid elements of d^2 / n,
  * valid steps / (B * K) }.  They head a 16-byte aligned slot of 4 floats of their own (the other two stay 0): a 4-float copy is in bounds. */
 int fv_head_loss_metrics(fv_handle* h, const float** dev);
+/* Per-dimension and per-step weights of the loss above (gripper against arm, near against far steps).  dim_w: HOST, A = action_dim / chunk floats; step_w:
+ * HOST, K = chunk floats; either may be NULL, meaning ones; both NULL switches weighting off.  With om = dim_w[a] * step_w[k]:
+ *     loss = sum_valid om rho(d) / n          dL/dactions = loss_scale * om * rho'(d) / n          (n stays ALL B K A elements)
+ * An element with om == 0 is SELECTED away exactly like a padded one: 0 to the loss, the gradient and the masked MSE whatever its target holds (NaN, inf).
+ * The two metrics stay UNWEIGHTED (masked MSE; valid steps / (B K), which looks at pads only), so runs with different weights remain comparable.
+ * With weights on EVERY kind, plain MSE without a mask included, runs the many-block kernel's weighted instance (and writes the metrics); with weights off
+ * every loss evaluation launches what it launched before.  Weights that are all exactly 1 give the bits of the unweighted many-block kernel.
+ * Values must be finite and >= 0: FV_ERR_ARG otherwise, with no state changed.  A configuration call: it synchronises the device before it overwrites
+ * the handle's ONE weight vector.  A later fv_head_set_loss that CHANGES chunk drops the weights (their sizes no longer fit): set them again after it.
+ * A hipGraph captured over a loss evaluation keeps the on/off state of its capture. */
+int fv_head_set_loss_weights(fv_handle* h, const float* dim_w, const float* step_w);
+/* out_dev[a] (A = action_dim / chunk DEVICE floats) = mean |actions - targets| over the non-padded steps of action dimension a, in the (normalised) space
+ * the loss lives in; 0 for a dimension without a valid step.  actions, targets: (B, K, A) device f32.  Uses the handle's current chunk and mask, never the
+ * weights.  One block per dimension, fixed-order sums (no float atomics).  On demand: no train step calls it. */
+int fv_head_loss_per_dim(fv_handle* h, const float* actions, const float* targets, int B, float* out_dev, fv_stream s);
 /* generic backward of the head from dL/dactions (B,A) f32 (what autograd hands a custom Function when the loss is
  * computed outside, e.g. lerobot_fastvla/modeling_fastvla.py:132 + loss.backward()); overwrites flat_grads. */
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,
@@ -322,6 +337,29 @@ int fv_adamw_clip_step_groups(fv_handle* h, float* flat_params, const float* fla
  * null ema; ema overlapping flat_params, flat_grads, m or v; ema_weight outside [0, 1] or NaN; with a table, an ema that is not 16-byte aligned. */
 int fv_adamw_clip_step_ema(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, float* ema, float ema_weight, int64_t n,
                            const fv_adamw_hparams* hp, const fv_adamw_groups* groups, int64_t step, float* grad_norm_out, float* group_norms_out, fv_stream s);
+
+/* ---- temporal ensembling of action chunks (ACT's exponential weighting; LeRobot's ACTTemporalEnsembler, per environment).  Every control step the policy
+ * predicts a chunk of K future steps; the action served for time t is the weighted mean of what the chunks predicted at t-K+1 .. t (those that exist since
+ * the last reset) say about t:  sum_i w_i c_i[t] / sum_i w_i  with  w_i = exp(-coeff i), i = 0 the OLDEST prediction.  coeff: any finite float; 0 is
+ * uniform, a negative one favours new predictions.  Kept in the online form  ens <- (ens cumsum_w[n-1] + c w[n]) / cumsum_w[n]  with a count n per slot.
+ * Device state: ens (n_env, K, A) f32 and count (n_env, K) int32, a ring -- slot (t + k) mod K holds the running mean for time t + k; w and cumsum_w
+ * (K floats each) are computed on the host in double, rounded once and uploaded at create.
+ * THE RING POSITION t IS HOST STATE of the ensembler and travels as a kernel argument: a hipGraph captured over fv_ensemble_step bakes the position of
+ * its capture in and replays it wrongly -- call fv_ensemble_step outside captured graphs. */
+typedef struct fv_ensembler fv_ensembler;
+/* A configuration call: allocates, uploads and synchronises.  FV_ERR_ARG for n_env, chunk or step_dim < 1, a non-finite coeff, a coeff whose weights
+ * leave the fp32 range over `chunk` steps, or a null pointer.  Destroy the ensembler before the handle. */
+int fv_ensemble_create(fv_handle* h, int n_env, int chunk, int step_dim, float coeff, fv_ensembler** out);
+int fv_ensemble_destroy(fv_handle* h, fv_ensembler* e);
+/* forget the history of environment env (-1 = all): its next step serves row 0 of the new chunk as it is.  Stream-ordered, no host synchronisation:
+ * vector environments that end episodes at different times are reset one by one.  FV_ERR_ARG, nothing enqueued, for env outside -1 .. n_env-1. */
+int fv_ensemble_reset(fv_handle* h, fv_ensembler* e, int env, fv_stream s);
+/* chunks: DEVICE (n_env, K, A) f32, the chunks predicted now; actions: DEVICE (n_env, A) f32, the ensembled action of this time step (must not overlap
+ * chunks).  ONE launch; every (env, slot) belongs to one thread: no atomics, no reduction, two runs agree bit for bit, and one environment's values
+ * (NaN included) never reach another's.  A slot without history (K = 1, or the first step after a reset) returns the chunk's row bit for bit.
+ * Asynchronous on s, allocates nothing; steps of one ensembler must be enqueued in order on one stream (or otherwise ordered).  FV_ERR_ARG, with nothing
+ * enqueued and the state untouched, for a null pointer. */
+int fv_ensemble_step(fv_handle* h, fv_ensembler* e, const float* chunks, float* actions, fv_stream s);
 
 /* gradient accumulation (training/trainer.py:96,171: accelerate sums micro-batch gradients before the optimiser step):
  * acc += grads over n floats; both 16-byte aligned flat head buffers. */

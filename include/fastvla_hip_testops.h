@@ -193,6 +193,11 @@ int fv_op_lora_direct(int kind, int part_mask, int rank, int Np, int K, int qd, 
 int fv_op_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, size_t partial_floats, float* loss, float* metrics,
                      int64_t n, int A, int kind, float beta, float loss_scale, fv_stream s);
 
+/* the same with the weights of fv_head_set_loss_weights: dim_w (A) and step_w (K) DEVICE floats, both required; (n / A) % K == 0.  om = dim_w[a] * step_w[k]
+ * scales rho and g, an element with om == 0 is selected away like a padded one; the metrics stay unweighted. */
+int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad, const float* dim_w, const float* step_w, float* g, float* partial,
+                              size_t partial_floats, float* loss, float* metrics, int64_t n, int A, int K, int kind, float beta, float loss_scale, fv_stream s);
+
 #ifdef __cplusplus
 }
 #endif

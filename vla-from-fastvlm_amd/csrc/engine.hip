@@ -184,6 +184,7 @@ struct fv_handle {
   bool no_mfma_dw = false;    // FASTVLA_NO_MFMA_DW=1: A/B switch back to the VALU depthwise kernels
   bool no_ffn32 = false;      // FASTVLA_NO_FFN32=1: A/B switch back to the 16x16x32 fused ConvFFN
   fv::HeadLoss loss{FV_LOSS_MSE, 1.0f, 1, nullptr, nullptr};   // fv_head_set_loss / fv_head_set_loss_mask; metrics: two words of the f16_flags block
+  float* loss_w = nullptr;        // fv_head_set_loss_weights: ONE device vector of 2 da floats per handle ([0, A) dim_w, [da, da + K) step_w), allocated on first use
   TrainState train;               // unfrozen-backbone training (train_path.inc): library-owned transposed bf16 weight copies
   int batch_invariant = 0;        // fv_set_batch_invariant: the inference tower never takes the range forms either
   int train_depth = 0;            // > 0 while a training entry point runs (TrainScope): gemm_p then keeps the few-row GEMM forms off
@@ -1354,10 +1355,16 @@ int fv_head_mse_backward(fv_handle* h, const float* flat_params, const float* ac
 int fv_head_set_loss(fv_handle* h, const fv_head_loss_spec* spec) {
   HandleScope _hs(h);
   if (!h) return fv_fail(FV_ERR_ARG, "null handle");
-  if (!spec) { h->loss.kind = FV_LOSS_MSE; h->loss.beta = 1.0f; h->loss.chunk = 1; return FV_OK; }
+  // another chunk length: the weight vectors' sizes no longer fit, so weighting is off until fv_head_set_loss_weights runs again
+  if (!spec) {
+    if (h->loss.chunk != 1) h->loss.dim_w = h->loss.step_w = nullptr;
+    h->loss.kind = FV_LOSS_MSE; h->loss.beta = 1.0f; h->loss.chunk = 1;
+    return FV_OK;
+  }
   if (spec->kind != FV_LOSS_MSE && spec->kind != FV_LOSS_L1 && spec->kind != FV_LOSS_SMOOTH_L1) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: unknown loss kind %d", spec->kind);
   if (spec->kind == FV_LOSS_SMOOTH_L1 && !(spec->beta > 0.f && std::isfinite(spec->beta))) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: smooth-L1 beta must be positive and finite");
   if (spec->chunk < 1 || h->hd.da % spec->chunk) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: chunk=%d must be >= 1 and divide action_dim=%d", spec->chunk, h->hd.da);
+  if (spec->chunk != h->loss.chunk) h->loss.dim_w = h->loss.step_w = nullptr;
   h->loss.kind = spec->kind;
   h->loss.beta = spec->kind == FV_LOSS_SMOOTH_L1 ? spec->beta : 1.0f;
   h->loss.chunk = spec->chunk;
@@ -1369,6 +1376,39 @@ int fv_head_set_loss_mask(fv_handle* h, const uint8_t* pad_dev) {
   if (!h) return fv_fail(FV_ERR_ARG, "null handle");
   h->loss.pad = pad_dev;
   return FV_OK;
+}
+
+int fv_head_set_loss_weights(fv_handle* h, const float* dim_w, const float* step_w) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (!dim_w && !step_w) { h->loss.dim_w = h->loss.step_w = nullptr; return FV_OK; }   // both NULL: weighting off
+  const int da = h->hd.da, K = h->loss.chunk, A = da / K;
+  for (int i = 0; dim_w && i < A; ++i)
+    if (!(dim_w[i] >= 0.f) || !std::isfinite(dim_w[i])) return fv_fail(FV_ERR_ARG, "fv_head_set_loss_weights: dim_w[%d] = %g must be finite and >= 0", i, (double)dim_w[i]);
+  for (int k = 0; step_w && k < K; ++k)
+    if (!(step_w[k] >= 0.f) || !std::isfinite(step_w[k])) return fv_fail(FV_ERR_ARG, "fv_head_set_loss_weights: step_w[%d] = %g must be finite and >= 0", k, (double)step_w[k]);
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  std::vector<float> v((size_t)2 * da, 1.0f);   // a NULL vector: ones
+  for (int i = 0; dim_w && i < A; ++i) v[i] = dim_w[i];
+  for (int k = 0; step_w && k < K; ++k) v[da + k] = step_w[k];
+  if (!h->loss_w) {   // allocated once, sized for every chunk length that divides action_dim
+    void* p = nullptr;
+    FV_TRY(dev_alloc(h, v.size() * 4, &p));
+    h->loss_w = static_cast<float*>(p);
+  }
+  // a loss kernel still in flight on any stream may be reading the previous weights: a configuration call, so it simply waits
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  FV_HIP_CHECK(hipMemcpy(h->loss_w, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+  h->loss.dim_w = h->loss_w;
+  h->loss.step_w = h->loss_w + da;
+  return FV_OK;
+}
+
+int fv_head_loss_per_dim(fv_handle* h, const float* actions, const float* targets, int B, float* out_dev, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !actions || !targets || !out_dev) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_dim: null argument");
+  if (B < 1) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_dim: B must be positive");
+  return fv::launch_loss_per_dim(actions, targets, h->loss.pad, out_dev, (long)B * h->loss.chunk, h->hd.da / h->loss.chunk, static_cast<hipStream_t>(s));
 }
 
 int fv_head_loss_metrics(fv_handle* h, const float** dev) {
@@ -1389,6 +1429,91 @@ int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_a
   float* scr = reinterpret_cast<float*>(static_cast<char*>(h->ws) + wp.head_scr);
   return fv::launch_head_backward(h->hd, flat_params, grad_actions, nullptr, nullptr, B, dropout_p,
                                   static_cast<const float*>(saved), nullptr, flat_grads, scr, static_cast<hipStream_t>(s));
+}
+
+// ---- temporal ensembling of action chunks (csrc/head_kernels.hip ensemble_step_kernel)
+struct fv_ensembler {
+  int n_env = 0, K = 0, A = 0;
+  int head = 0;              // ring position: the slot of the time step served next (host state, a kernel argument)
+  void* dev = nullptr;       // ONE allocation: ens | count | w | cw
+  float* ens = nullptr;
+  int32_t* count = nullptr;
+  const float *w = nullptr, *cw = nullptr;
+};
+
+int fv_ensemble_create(fv_handle* h, int n_env, int chunk, int step_dim, float coeff, fv_ensembler** out) {
+  HandleScope _hs(h);
+  if (!h || !out) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: null argument");
+  *out = nullptr;
+  if (n_env < 1 || chunk < 1 || step_dim < 1) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: n_env = %d, chunk = %d, step_dim = %d must all be >= 1", n_env, chunk, step_dim);
+  if (!std::isfinite(coeff)) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: coeff must be finite");
+  const size_t slots = (size_t)n_env * chunk;
+  if (slots * step_dim > ((size_t)1 << 40)) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: n_env * chunk * step_dim is more than 2^40");
+  // the tables in double, rounded once: w[i] = exp(-coeff i), cw[i] = w[0] + .. + w[i]
+  std::vector<float> tab;
+  try {
+    tab.resize((size_t)2 * chunk);
+  } catch (const std::exception&) {
+    return fv_fail(FV_ERR_STATE, "fv_ensemble_create: out of host memory");
+  }
+  double run = 0.0;
+  for (int i = 0; i < chunk; ++i) {
+    const double wi = std::exp(-(double)coeff * i);
+    run += wi;
+    tab[i] = (float)wi;
+    tab[chunk + i] = (float)run;
+    if (!std::isfinite(tab[chunk + i]) || !(tab[chunk + i] > 0.f))
+      return fv_fail(FV_ERR_ARG, "fv_ensemble_create: coeff = %g over %d steps leaves the fp32 range", (double)coeff, chunk);
+  }
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const size_t ens_bytes = align_up(slots * step_dim * sizeof(float)), cnt_bytes = align_up(slots * sizeof(int32_t)), tab_bytes = align_up(tab.size() * sizeof(float));
+  void* dev = nullptr;
+  FV_HIP_CHECK(hipMalloc(&dev, ens_bytes + cnt_bytes + tab_bytes));
+  char* base = static_cast<char*>(dev);
+  hipError_t e = hipMemset(base, 0, ens_bytes + cnt_bytes);
+  if (e == hipSuccess) e = hipMemcpy(base + ens_bytes + cnt_bytes, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(dev); return fv_hip_fail(e, "fv_ensemble_create: upload"); }
+  fv_ensembler* en = new (std::nothrow) fv_ensembler;
+  if (!en) { (void)hipFree(dev); return fv_fail(FV_ERR_STATE, "fv_ensemble_create: out of host memory"); }
+  en->n_env = n_env; en->K = chunk; en->A = step_dim; en->dev = dev;
+  en->ens = reinterpret_cast<float*>(base);
+  en->count = reinterpret_cast<int32_t*>(base + ens_bytes);
+  en->w = reinterpret_cast<const float*>(base + ens_bytes + cnt_bytes);
+  en->cw = en->w + chunk;
+  *out = en;
+  return FV_OK;
+}
+
+int fv_ensemble_destroy(fv_handle* h, fv_ensembler* e) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "fv_ensemble_destroy: null handle");
+  if (!e) return FV_OK;
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const hipError_t err = hipFree(e->dev);    // (waits for a step still in flight on the ring)
+  delete e;
+  if (err != hipSuccess) return fv_hip_fail(err, "fv_ensemble_destroy: hipFree");
+  return FV_OK;
+}
+
+int fv_ensemble_reset(fv_handle* h, fv_ensembler* e, int env, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !e) return fv_fail(FV_ERR_ARG, "fv_ensemble_reset: null argument");
+  if (env < -1 || env >= e->n_env) return fv_fail(FV_ERR_ARG, "fv_ensemble_reset: env = %d outside -1 .. %d", env, e->n_env - 1);
+  // the counts alone carry the history: a slot with count 0 takes the next chunk's row as it is.  Stream-ordered, no host synchronisation
+  int32_t* at = env < 0 ? e->count : e->count + (size_t)env * e->K;
+  const size_t n = (env < 0 ? (size_t)e->n_env : 1) * e->K;
+  FV_HIP_CHECK(hipMemsetAsync(at, 0, n * sizeof(int32_t), static_cast<hipStream_t>(s)));
+  return FV_OK;
+}
+
+int fv_ensemble_step(fv_handle* h, fv_ensembler* e, const float* chunks, float* actions, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !e || !chunks || !actions) return fv_fail(FV_ERR_ARG, "fv_ensemble_step: null argument");
+  const int rc = fv::launch_ensemble_step(chunks, e->ens, e->count, actions, e->w, e->cw, e->n_env, e->K, e->A, e->head, static_cast<hipStream_t>(s));
+  if (rc != FV_OK) return rc;
+  e->head = (e->head + 1) % e->K;
+  return FV_OK;
 }
 
 int fv_profile(fv_handle* h, int enable) {

@@ -302,7 +302,9 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
                         hipStream_t s, const HeadIoNorm* io = nullptr);
 // the fused loss of launch_head_backward (fv_head_set_loss / fv_head_set_loss_mask): kind FV_LOSS_*, beta of smooth-L1, chunk = K steps of da / K action
 // dimensions each, pad = device (B, K) bytes or null, metrics = 2 device floats { masked MSE, valid fraction }.  null, or MSE without a mask: mse_kernel as ever
-struct HeadLoss { int kind; float beta; int chunk; const uint8_t* pad; float* metrics; };
+// dim_w (da / chunk floats) and step_w (chunk floats): device vectors of fv_head_set_loss_weights, both set or both null.  Set: EVERY kind, plain MSE without a
+// mask included, takes the chunked kernel's weighted instance
+struct HeadLoss { int kind; float beta; int chunk; const uint8_t* pad; float* metrics; const float* dim_w = nullptr; const float* step_w = nullptr; };
 // grad_actions != null: generic backward from dL/dactions (loss untouched); else fused MSE(actions, targets) + backward
 // d_pooled (optional, [B][feat]): dL/d(pooled feature) -- the gradient an UNFROZEN backbone continues from
 int launch_head_backward(const HeadDims& d, const float* P, const float* grad_actions, const float* actions,
@@ -314,7 +316,14 @@ size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
 // chunk_loss_partial_floats() floats of scratch, loss 1 float, metrics 2 floats
 size_t chunk_loss_partial_floats();
 int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, float* loss, float* metrics, long n, int A, int kind,
-                      float beta, float loss_scale, hipStream_t s);
+                      float beta, float loss_scale, hipStream_t s, const float* dim_w = nullptr, const float* step_w = nullptr, int K = 1);
+// mean |a - t| per action dimension over the non-padded steps: a, t (rows, A) f32 with rows = B K, pad (rows) bytes or null -> out (A), 0 for a dimension
+// without a valid step.  One block per dimension, fixed-order sums
+int launch_loss_per_dim(const float* a, const float* t, const uint8_t* pad, float* out, long rows, int A, hipStream_t s);
+// temporal ensembling of action chunks (fv_ensemble_step): chunks (n_env, K, A) -> actions (n_env, A); ens (n_env, K, A) and count (n_env, K) are the ring,
+// head its position, w / cw the K weights exp(-coeff i) and their running sums
+int launch_ensemble_step(const float* chunks, float* ens, int32_t* count, float* actions, const float* w, const float* cw, int n_env, int K, int A, int head,
+                         hipStream_t s);
 size_t adamw_scratch_bytes();  // norm_scratch of launch_adamw_clip: [0] = sum of squares, [1..] per-block partials
 int launch_axpy(float* y, const float* x, int64_t n, const float* scale_dev, hipStream_t s);  // y += x, or y *= *scale_dev when x is null
 // ema != null (both launchers): the EMA instance of the step kernel, ema <- ema + ema_weight (p_new - ema) in the same pass (common.h ema_update);

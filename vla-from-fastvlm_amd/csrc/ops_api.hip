@@ -284,4 +284,11 @@ int fv_op_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* 
   return fv::launch_chunk_loss(a, t, pad, g, partial, loss, metrics, (long)n, A, kind, beta, loss_scale, static_cast<hipStream_t>(s));
 }
 
+int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad, const float* dim_w, const float* step_w, float* g, float* partial,
+                              size_t partial_floats, float* loss, float* metrics, int64_t n, int A, int K, int kind, float beta, float loss_scale, fv_stream s) {
+  if (partial_floats < fv::chunk_loss_partial_floats()) return fv_fail(FV_ERR_ARG, "fv_op_chunk_loss_weighted: partial needs %zu floats", fv::chunk_loss_partial_floats());
+  if (!dim_w || !step_w) return fv_fail(FV_ERR_ARG, "fv_op_chunk_loss_weighted: null weight vector");
+  return fv::launch_chunk_loss(a, t, pad, g, partial, loss, metrics, (long)n, A, kind, beta, loss_scale, static_cast<hipStream_t>(s), dim_w, step_w, K);
+}
+
 }  // extern "C"

@@ -4,4 +4,5 @@ raises FastVLAHipError when the library or the device is missing (there is no CP
 from ._lib import FastVLAHipError, library_path, load  # noqa: F401
 from .arch import LLMConfig, ModelConfig, TowerConfig, PRESETS, preset  # noqa: F401
 from .engine import HEAD_KEYS, FastVLAEngine  # noqa: F401
+from .ensemble import TemporalEnsembler  # noqa: F401
 from . import weights  # noqa: F401

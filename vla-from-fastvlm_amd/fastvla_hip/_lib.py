@@ -122,6 +122,12 @@ SIGNATURES = {
     "fv_head_backward": (_i, [_vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
     "fv_head_set_loss": (_i, [_vp, C.POINTER(HeadLossSpec)]),
     "fv_head_set_loss_mask": (_i, [_vp, _vp]),
+    "fv_head_set_loss_weights": (_i, [_vp, _vp, _vp]),
+    "fv_head_loss_per_dim": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "fv_ensemble_create": (_i, [_vp, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "fv_ensemble_destroy": (_i, [_vp, _vp]),
+    "fv_ensemble_reset": (_i, [_vp, _vp, _i, _vp]),
+    "fv_ensemble_step": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "fv_head_loss_metrics": (_i, [_vp, C.POINTER(_vp)]),
     "fv_grad_accumulate": (_i, [_vp, _vp, _vp, _i64, _vp]),
     "fv_grad_scale": (_i, [_vp, _vp, _i64, _vp, _vp]),
@@ -199,6 +205,7 @@ OPS_SIGNATURES = {
     "fv_op_embed_gather": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "fv_op_pool_norm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "fv_op_chunk_loss": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _f, _f, _vp]),
+    "fv_op_chunk_loss_weighted": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _i, _f, _f, _vp]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 

@@ -78,6 +78,25 @@ def check_head_loss(kind, beta, chunk, action_dim: Optional[int] = None):
     return str(kind), beta, int(chunk)
 
 
+def check_loss_weights(dim_w, step_w, A: int, K: int) -> Optional[dict]:
+    """-> {"dim": [A floats] or None, "step": [K floats] or None}, or None when both are None; ValueError for a wrong length or a negative / non-finite value"""
+    import math
+
+    def vec(v, n, name):
+        if v is None:
+            return None
+        v = [float(x) for x in (v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else list(v))]
+        if len(v) != n:
+            raise ValueError(f"{name} must have {n} values, got {len(v)}")
+        bad = [x for x in v if not (math.isfinite(x) and x >= 0.0)]
+        if bad:
+            raise ValueError(f"{name} must be finite and >= 0, got {bad[0]}")
+        return v
+
+    w = {"dim": vec(dim_w, A, "action_dim_weights"), "step": vec(step_w, K, "action_step_weights")}
+    return None if w["dim"] is None and w["step"] is None else w
+
+
 class FastVLAEngine:
     def __init__(self, model: ModelConfig, *, state_dim: int = 14, action_dim: int = 14, hidden_dim: int = 1024,
                  fusion_dim: int = 1024, device: Optional[torch.device] = None, max_batch: int = 64,
@@ -127,12 +146,13 @@ class FastVLAEngine:
         _lib.check(self.lib.fv_head_layout(self.h, C.byref(offs)), "fv_head_layout")
         self.head_offsets = list(offs)
         self.head_loss = dict(kind="mse", beta=1.0, chunk=1)      # set_head_loss
+        self.head_loss_weights: Optional[dict] = None             # set_head_loss_weights: {"dim": A floats or None, "step": K floats or None}, None = off
         self._pad_keep: Optional[torch.Tensor] = None
         self.loaded = False
 
     def close(self):
         if getattr(self, "h", None):
-            for t in list(getattr(self, "_group_tables", ())):      # parameter-group tables go before the handle
+            for t in list(getattr(self, "_group_tables", ())):      # parameter-group tables (and temporal ensemblers) go before the handle
                 t.close()
             self.lib.fv_destroy(self.h)
             self.h = None
@@ -567,11 +587,42 @@ class FastVLAEngine:
         else:
             spec = _lib.HeadLossSpec(_lib.LOSS_KINDS[kind], beta, chunk)
             _lib.check(self.lib.fv_head_set_loss(self.h, C.byref(spec)), "fv_head_set_loss", self.h)
+        if chunk != self.head_loss["chunk"]:
+            self.head_loss_weights = None      # (the library drops them: their sizes no longer fit)
         self.head_loss = dict(kind=kind, beta=beta, chunk=chunk)
 
     def loss_is_chunked(self, pad) -> bool:
         """whether a loss evaluation with this mask runs the chunked kernel (and writes head_loss_metrics) or the plain MSE kernel"""
-        return pad is not None or self.head_loss["kind"] != "mse"
+        return pad is not None or self.head_loss["kind"] != "mse" or self.head_loss_weights is not None
+
+    def set_head_loss_weights(self, dim_w=None, step_w=None) -> None:
+        """Per-dimension (A = action_dim / chunk) and per-step (K = chunk) weights of the loss (fv_head_set_loss_weights): either may be None = ones, both
+        None switches weighting off.  With weights on every loss kind runs the chunked kernel's weighted instance; an element whose weight is 0 is selected
+        away like a padded one.  ValueError for a wrong length or a negative / non-finite value, before any library call.  set_head_loss with another chunk
+        drops them."""
+        K = self.head_loss["chunk"]
+        w = check_loss_weights(dim_w, step_w, self.head_dims["da"] // K, K)
+        if w is None:
+            _lib.check(self.lib.fv_head_set_loss_weights(self.h, None, None), "fv_head_set_loss_weights", self.h)
+        else:
+            arrs = [None if v is None else (C.c_float * len(v))(*v) for v in (w["dim"], w["step"])]
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.fv_head_set_loss_weights(self.h, *[None if a is None else C.cast(a, C.c_void_p) for a in arrs]), "fv_head_set_loss_weights", self.h)
+        self.head_loss_weights = w
+
+    def head_loss_per_dim(self, actions: torch.Tensor, targets: torch.Tensor, pad=None) -> torch.Tensor:
+        """-> (A,) f32: mean |actions - targets| over the non-padded steps of each action dimension (fv_head_loss_per_dim), in the space the loss lives in;
+        0 for a dimension without a valid step.  actions, targets: (B, K, A) or (B, K * A); pad: optional (B, chunk) bool.  Never weighted."""
+        B, K = actions.shape[0], self.head_loss["chunk"]
+        actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
+        if actions.numel() != B * self.head_dims["da"] or targets.numel() != actions.numel():
+            raise ValueError(f"actions and targets must hold (B, {self.head_dims['da']}) elements, got {tuple(actions.shape)} and {tuple(targets.shape)}")
+        pad = self._pad_arg(pad, B)
+        out = torch.empty(self.head_dims["da"] // K, dtype=torch.float32, device=self.device)
+        with self._Mask(self, pad):
+            _lib.check(self.lib.fv_head_loss_per_dim(self.h, actions.data_ptr(), targets.data_ptr(), B, out.data_ptr(), _stream()), "fv_head_loss_per_dim", self.h)
+        return out
 
     def _pad_arg(self, pad, B: int) -> Optional[torch.Tensor]:
         if pad is None:

@@ -135,10 +135,40 @@ class FastVLMWithExpert(nn.Module):
         self.backbone.configure_head_loss(kind, beta, self.chunk_size)
         self.action_loss, self.action_loss_beta = self.backbone._head_loss["kind"], self.backbone._head_loss["beta"]
 
-    def chunk_record(self, n_action_steps: int = 1) -> Optional[dict]:
-        """what a checkpoint records beside the tensors (hip_extras.json "action_chunk"); None with the defaults"""
+    def set_action_loss_weights(self, dim_weights=None, step_weights=None) -> None:
+        """Weights of the loss of every later loss evaluation / train step: dim_weights (A values, e.g. gripper against arm) and step_weights (K values, e.g.
+        a discount over the chunk); either may be None = ones, both None switches weighting off.  A weight of 0 takes the element out of the loss like a
+        padded step.  ValueError for a wrong length or a negative / non-finite value."""
+        self.backbone.configure_head_loss_weights(dim_weights, step_weights)
+
+    @property
+    def action_loss_weights(self) -> Optional[dict]:
+        """{"dim": [A floats] or None, "step": [K floats] or None}, or None while weighting is off"""
+        return self.backbone._head_loss_weights
+
+    def chunk_record(self, n_action_steps: int = 1, temporal_ensemble_coeff: Optional[float] = None) -> Optional[dict]:
+        """what a checkpoint records beside the tensors (hip_extras.json "action_chunk"); None with the defaults.  "temporal_ensemble_coeff", "dim_weights" and
+        "step_weights" are there only when set: every other policy's record is what it was."""
         rec = {"chunk_size": self.chunk_size, "n_action_steps": int(n_action_steps), "loss": self.action_loss, "beta": self.action_loss_beta}
+        if temporal_ensemble_coeff is not None:
+            rec["temporal_ensemble_coeff"] = float(temporal_ensemble_coeff)
+        w = self.action_loss_weights or {}
+        for key, name in (("dim", "dim_weights"), ("step", "step_weights")):
+            if w.get(key) is not None:
+                rec[name] = [float(x) for x in w[key]]
         return None if rec == {"chunk_size": 1, "n_action_steps": 1, "loss": "mse", "beta": 1.0} else rec
+
+    def action_error_per_dim(self, pooled: torch.Tensor, states: torch.Tensor, targets: torch.Tensor, pad=None) -> torch.Tensor:
+        """-> (A,): mean |prediction - target| over the non-padded steps of each action dimension, in the normalised space the loss lives in (what the
+        per-dimension weights are tuned against); never weighted, no gradient."""
+        self.materialize(pooled.device)
+        targets, pad = self.chunk_targets(targets.to(pooled.device, torch.float32), pad)
+        if targets.shape != (pooled.shape[0], self.head_width):
+            raise ValueError(f"targets must be (B,{self.config.action_dim}), got {tuple(targets.shape)}")
+        eng = self._engine()
+        with torch.no_grad():
+            actions, _saved = eng.head_forward(self._flat, pooled, states.to(pooled.device, torch.float32), normalized_actions=True)
+            return eng.head_loss_per_dim(actions, targets.contiguous(), pad=pad)
 
     def chunk_targets(self, targets: torch.Tensor, pad=None):
         """-> (targets flattened to (B, K * A), pad (B, K) bool or None).  Targets are (B, K, A); (B, A) only when K == 1 (where a longer (B, T, A) gives its

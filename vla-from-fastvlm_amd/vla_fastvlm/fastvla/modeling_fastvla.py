@@ -17,10 +17,26 @@ from .fastvlm_with_expert import FastVLMWithExpert
 from .processor_fastvla import FastVLAProcessor
 
 
-def resolve_chunk_options(chunk_size=None, n_action_steps=None, action_loss=None, action_loss_beta=None) -> Dict:
-    """-> {"chunk_size", "n_action_steps", "loss", "beta"}: explicit arguments, else the FASTVLA_* twins, else the defaults (1, 1, "mse", 1.0).  ValueError for
-    n_action_steps outside 1 .. chunk_size, an unknown loss name or a non-positive beta."""
-    from fastvla_hip.engine import check_head_loss
+def parse_weight_list(raw: str, name: str, chunk: Optional[int] = None) -> List[float]:
+    """"1,1,4" -> [1.0, 1.0, 4.0]; with `chunk` given also "discount:0.98" -> [0.98 ** k for k in range(chunk)].  ValueError for anything else."""
+    raw = raw.strip()
+    try:
+        if chunk is not None and raw.lower().startswith("discount:"):
+            gamma = float(raw.split(":", 1)[1])
+            return [gamma ** k for k in range(int(chunk))]
+        return [float(x) for x in raw.split(",") if x.strip()]
+    except ValueError:
+        raise ValueError(f"{name}: cannot read '{raw}' (a comma-separated list of numbers{', or discount:<gamma>' if chunk is not None else ''})") from None
+
+
+def resolve_chunk_options(chunk_size=None, n_action_steps=None, action_loss=None, action_loss_beta=None, temporal_ensemble_coeff=None,
+                          action_dim_weights=None, action_step_weights=None) -> Dict:
+    """-> {"chunk_size", "n_action_steps", "loss", "beta", "temporal_ensemble_coeff", "dim_weights", "step_weights"}: explicit arguments, else the FASTVLA_*
+    twins, else the defaults (1, 1, "mse", 1.0, None, None, None).  The last three also take False: off, whatever the twin says (what a checkpoint without
+    a record of them asks for).  ValueError for n_action_steps outside 1 .. chunk_size, an unknown loss name, a non-positive beta, a non-finite coefficient,
+    a coefficient together with n_action_steps != 1, or negative / non-finite weights (their lengths are checked against the head, in set_action_loss_weights)."""
+    from fastvla_hip.engine import check_head_loss, check_loss_weights
+    from fastvla_hip.ensemble import check_coeff
 
     def pick(arg, env, cast, default):
         if arg is not None:
@@ -33,7 +49,19 @@ def resolve_chunk_options(chunk_size=None, n_action_steps=None, action_loss=None
     n = pick(n_action_steps, "FASTVLA_N_ACTION_STEPS", int, 1)
     if int(n) != n or n < 1 or n > K:
         raise ValueError(f"n_action_steps must be an integer in 1 .. chunk_size. Got n_action_steps={n}, chunk_size={K}.")
-    return {"chunk_size": K, "n_action_steps": int(n), "loss": loss, "beta": beta}
+    coeff = pick(temporal_ensemble_coeff, "FASTVLA_TEMPORAL_ENSEMBLE_COEFF", str, None)
+    coeff = None if coeff is None or coeff is False else check_coeff(coeff)
+    if coeff is not None and int(n) != 1:
+        raise ValueError("n_action_steps must be 1 when using temporal ensembling: with it the policy is queried at every step. "
+                         f"Got temporal_ensemble_coeff={coeff}, n_action_steps={n}.")
+    dim_w = pick(action_dim_weights, "FASTVLA_ACTION_DIM_WEIGHTS", lambda r: parse_weight_list(r, "FASTVLA_ACTION_DIM_WEIGHTS"), None)
+    step_w = pick(action_step_weights, "FASTVLA_ACTION_STEP_WEIGHTS", lambda r: parse_weight_list(r, "FASTVLA_ACTION_STEP_WEIGHTS", K), None)
+    if isinstance(step_w, str):
+        step_w = parse_weight_list(step_w, "action_step_weights", K)
+    dim_w, step_w = (None if v is None or v is False else v for v in (dim_w, step_w))
+    w = check_loss_weights(dim_w, step_w, len(dim_w) if dim_w is not None else 0, len(step_w) if step_w is not None else 0) or {"dim": None, "step": None}
+    return {"chunk_size": K, "n_action_steps": int(n), "loss": loss, "beta": beta, "temporal_ensemble_coeff": coeff, "dim_weights": w["dim"],
+            "step_weights": w["step"]}
 
 
 class FastVLAPolicy(nn.Module, EmaMixin):
@@ -41,18 +69,28 @@ class FastVLAPolicy(nn.Module, EmaMixin):
     name = "fastvla"
 
     def __init__(self, config: FastVLAConfig | None = None, chunk_size: Optional[int] = None, n_action_steps: Optional[int] = None,
-                 action_loss: Optional[str] = None, action_loss_beta: Optional[float] = None) -> None:
+                 action_loss: Optional[str] = None, action_loss_beta: Optional[float] = None, temporal_ensemble_coeff: Optional[float] = None,
+                 action_dim_weights=None, action_step_weights=None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
         "smooth_l1" (action_loss_beta), evaluated in the library as sum over non-padded elements / ALL B K A elements (LeRobot's convention).
-        Environment twins an explicit argument beats: FASTVLA_CHUNK_SIZE, FASTVLA_N_ACTION_STEPS, FASTVLA_ACTION_LOSS, FASTVLA_ACTION_LOSS_BETA."""
+        temporal_ensemble_coeff = c (ACT's temporal ensembling; needs n_action_steps == 1): select_action runs the backbone on EVERY call and returns the
+        exponentially weighted mean (weights exp(-c i), i = 0 the oldest) of what the last K chunks predicted for this time step, kept on the device
+        (fastvla_hip/ensemble.py).  action_dim_weights (A values) / action_step_weights (K values, or "discount:g" for g^k): weights of the loss per action
+        dimension and per chunk step (set_action_loss_weights); a weight of 0 takes the element out like a padded step.
+        Environment twins an explicit argument beats: FASTVLA_CHUNK_SIZE, FASTVLA_N_ACTION_STEPS, FASTVLA_ACTION_LOSS, FASTVLA_ACTION_LOSS_BETA,
+        FASTVLA_TEMPORAL_ENSEMBLE_COEFF, FASTVLA_ACTION_DIM_WEIGHTS ("1,1,1,1,1,1,4"), FASTVLA_ACTION_STEP_WEIGHTS (a list, or "discount:0.98")."""
         super().__init__()
         self.config = config or FastVLAConfig()
-        opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta)
+        opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
         self.n_action_steps = opts["n_action_steps"]
+        self.temporal_ensemble_coeff: Optional[float] = opts["temporal_ensemble_coeff"]
+        self._ensembler = None      # fastvla_hip.TemporalEnsembler, created on the first select_action after reset()
         self._action_queue: deque = deque()
         self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"])
+        if opts["dim_weights"] is not None or opts["step_weights"] is not None:
+            self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.processor = FastVLAProcessor(self.config, self.model.backbone)
         self._opt_state = None
         self._unfrozen = None   # training/unfrozen.py UnfrozenState once enable_backbone_training() ran
@@ -185,6 +223,24 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         """the loss of every later compute_loss / train step: "mse" | "l1" | "smooth_l1" (beta)"""
         self.model.set_action_loss(kind, beta)
 
+    def set_action_loss_weights(self, dim_weights=None, step_weights=None) -> None:
+        """weights of the loss of every later compute_loss / train step, on every training route: dim_weights (A values), step_weights (K values); both None
+        switches weighting off"""
+        self.model.set_action_loss_weights(dim_weights, step_weights)
+
+    @torch.no_grad()
+    def action_error_per_dim(self, batch: Dict[str, torch.Tensor | List[str]]) -> torch.Tensor:
+        """-> (A,): mean |prediction - target| per action dimension over the batch's non-padded steps (normalised space, unweighted): what the per-dimension
+        weights are tuned against.  Runs on demand, outside the train step."""
+        images, states, tasks = batch["images"], batch["states"], batch["tasks"]
+        device = images.device
+        images = self.processor.prepare_images(images, device)
+        states = self.processor.prepare_states(states, device)
+        tasks = self.processor.prepare_tasks(tasks, batch_size=images.shape[0])
+        targets, pad = self.model.chunk_targets(batch["actions"], batch.get("action_is_pad"))
+        pooled = self.model.features(images, tasks, device=device)
+        return self.model.action_error_per_dim(pooled, states, targets, pad)
+
     @property
     def chunk_size(self) -> int:
         return self.model.chunk_size
@@ -200,13 +256,27 @@ class FastVLAPolicy(nn.Module, EmaMixin):
     @torch.inference_mode()
     def select_action(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device) -> torch.Tensor:
         """One action (A,) per environment step.  With n_action_steps = n > 1 the backbone runs on every n-th call: the first n rows of the predicted chunk
-        are queued and served in order; reset() empties the queue."""
+        are queued and served in order; reset() empties the queue.  With temporal_ensemble_coeff set the backbone runs on every call and the action is the
+        ensembler's weighted mean over the chunks predicted since reset() (no host synchronisation: the mean lives on the device)."""
+        if self.temporal_ensemble_coeff is not None:
+            chunk = self.select_action_chunk(image, state, task, device)
+            return self._temporal_ensembler(1).step(chunk.reshape(1, self.model.chunk_size, self.config.action_dim))[0]
         if not self._action_queue:       # (n_action_steps = 1: a prediction on every call, row 0 served)
             self._action_queue.extend(self.select_action_chunk(image, state, task, device)[: self.n_action_steps].unbind(0))
         return self._action_queue.popleft()
 
+    def _temporal_ensembler(self, n_env: int):
+        from fastvla_hip.ensemble import TemporalEnsembler
+        eng, ens = self.model._engine(), self._ensembler
+        if ens is None or ens._engine is not eng or not ens._h:      # (the first call after reset(), or the engine was rebuilt underneath)
+            ens = self._ensembler = TemporalEnsembler(eng, n_env, self.model.chunk_size, self.config.action_dim, self.temporal_ensemble_coeff)
+        return ens
+
     def reset(self) -> None:
         self._action_queue.clear()
+        if self._ensembler is not None:
+            self._ensembler.close()
+            self._ensembler = None
 
     # ------------------------------------------------------------------ native train step
     def prepare_batch(self, batch: Dict[str, torch.Tensor | List[str]]) -> Dict[str, torch.Tensor]:

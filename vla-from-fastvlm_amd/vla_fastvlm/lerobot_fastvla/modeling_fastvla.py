@@ -4,7 +4,11 @@ forward(batch) -> (loss, {"loss","mse"}), predict_action_chunk -> [B,chunk_size,
 
 config.chunk_size = K > 1 (an extension of this build: the reference accepts the field and predicts one step) widens the head to K * A: the dataset's
 (B, K, A) targets and its `action_is_pad` (B, K) train all K steps, padded ones excluded, and n_action_steps <= K of them are served per backbone run.
-The loss kind ("mse" | "l1" | "smooth_l1") comes from set_action_loss() or FASTVLA_ACTION_LOSS / FASTVLA_ACTION_LOSS_BETA."""
+The loss kind ("mse" | "l1" | "smooth_l1") comes from set_action_loss() or FASTVLA_ACTION_LOSS / FASTVLA_ACTION_LOSS_BETA.
+
+Temporal ensembling and loss weights (the registered config schema is pinned and gets no field): FastVLAPolicy(config, temporal_ensemble_coeff=c,
+action_dim_weights=..., action_step_weights=...) or their FASTVLA_* twins.  With a coefficient select_action(batch) runs the backbone on every call and
+ensembles all B environments of the batch on the device in one launch."""
 from __future__ import annotations
 
 from collections import deque
@@ -34,14 +38,33 @@ class FastVLAPolicy(PreTrainedPolicy):
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
         from ..fastvla.modeling_fastvla import resolve_chunk_options
-        opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps)      # (the loss kind: its environment twins)
+        opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
+                                     temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
+                                     action_step_weights=kwargs.get("action_step_weights"))
+        self.temporal_ensemble_coeff = opts["temporal_ensemble_coeff"]
+        self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
         self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
                                        action_loss=opts["loss"], action_loss_beta=opts["beta"])
+        if opts["dim_weights"] is not None or opts["step_weights"] is not None:
+            self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.reset()
 
     def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
         """the loss forward(batch) evaluates from now on: "mse" | "l1" | "smooth_l1" (beta)"""
         self.model.set_action_loss(kind, beta)
+
+    def set_action_loss_weights(self, dim_weights=None, step_weights=None) -> None:
+        """weights of the loss forward(batch) evaluates from now on: dim_weights (A values), step_weights (K values); both None switches weighting off"""
+        self.model.set_action_loss_weights(dim_weights, step_weights)
+
+    @torch.no_grad()
+    def action_error_per_dim(self, batch: dict[str, Tensor]) -> Tensor:
+        """-> (A,): mean |prediction - target| per action dimension over the batch's non-padded steps (normalised space, unweighted)"""
+        images, states, tasks = self._prepare_inputs(batch)
+        pad = batch.get("action_is_pad") if self.model.chunk_size > 1 else None
+        targets, pad = self.model.chunk_targets(batch[ACTION], pad)
+        pooled = self.model.features(images, tasks, device=images.device)
+        return self.model.action_error_per_dim(pooled, states, targets, pad)
 
     def _resolve_input_keys(self) -> tuple[str, list[str]]:
         feats = self.config.input_features
@@ -67,6 +90,9 @@ class FastVLAPolicy(PreTrainedPolicy):
 
     def reset(self):
         self._action_queue: deque[Tensor] = deque([], maxlen=self.config.n_action_steps)
+        if getattr(self, "_ensembler", None) is not None:
+            self._ensembler.close()
+            self._ensembler = None
 
     def enable_image_augmentation(self, **kwargs):
         """image augmentation of training batches: the backbone's state, as vla_fastvlm.fastvla.FastVLAPolicy.enable_image_augmentation sets it"""
@@ -120,6 +146,15 @@ class FastVLAPolicy(PreTrainedPolicy):
     @torch.no_grad()
     def select_action(self, batch: dict[str, Tensor]) -> Tensor:
         self.eval()
+        if self.temporal_ensemble_coeff is not None:      # the backbone on every call; all B environments ensembled in one launch
+            chunk = self.predict_action_chunk(batch)
+            B, eng, ens = chunk.shape[0], self.model._engine(), self._ensembler
+            if ens is not None and ens._engine is eng and ens._h and ens.n_env != B:
+                raise ValueError(f"select_action: the batch holds {B} environments, the temporal ensembler was started with {ens.n_env}: call reset() first")
+            if ens is None or ens._engine is not eng or not ens._h:
+                from fastvla_hip.ensemble import TemporalEnsembler
+                ens = self._ensembler = TemporalEnsembler(eng, B, self.model.chunk_size, self.config.action_dim, self.temporal_ensemble_coeff)
+            return ens.step(chunk)
         if not self._action_queue:
             chunk = self.predict_action_chunk(batch)[:, : self.config.n_action_steps]
             self._action_queue.extend(chunk.transpose(0, 1))

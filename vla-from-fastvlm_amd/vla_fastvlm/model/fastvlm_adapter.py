@@ -185,6 +185,7 @@ class FastVLMBackbone(nn.Module):
         self._io_norm: Optional[dict] = None   # dataset statistics folded into the head kernels (set_io_normalization)
         self._head_dims = dict(state_dim=14, action_dim=14, hidden_dim=1024, fusion_dim=1024)
         self._head_loss = dict(kind="mse", beta=1.0, chunk=1)   # configure_head_loss: the fused loss of the head backward and the chunk length K
+        self._head_loss_weights: Optional[dict] = None          # configure_head_loss_weights: {"dim", "step"} of the weighted chunk loss, None = off
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
 
@@ -263,10 +264,22 @@ class FastVLMBackbone(nn.Module):
         kind, beta, chunk = check_head_loss(kind, beta, chunk, self._head_dims["action_dim"])
         rechunk = chunk != self._head_loss["chunk"]
         self._head_loss = dict(kind=kind, beta=beta, chunk=chunk)
+        if rechunk:
+            self._head_loss_weights = None      # (sized for the previous chunk length)
         if self._engine is not None:
             self._engine.set_head_loss(**self._head_loss)
             if rechunk and self._io_norm is not None:
                 self._engine.set_io_norm(**self._io_norm_for_engine())
+
+    def configure_head_loss_weights(self, dim_w=None, step_w=None) -> None:
+        """Per-dimension (A) and per-step (K) weights of the fused loss (FastVLAEngine.set_head_loss_weights); both None switches weighting off.  Checked here,
+        on the host, before any library call: ValueError for a wrong length or a negative / non-finite value."""
+        from fastvla_hip.engine import check_loss_weights
+        K = self._head_loss["chunk"]
+        self._head_loss_weights = check_loss_weights(dim_w, step_w, self._head_dims["action_dim"] // K, K)
+        if self._engine is not None:
+            w = self._head_loss_weights or {"dim": None, "step": None}
+            self._engine.set_head_loss_weights(w["dim"], w["step"])
 
     def _io_norm_for_engine(self) -> dict:
         """the folded statistics as the head kernels index them: the action vectors are A long in the state dict and tiled over the K steps of a chunk here"""
@@ -336,6 +349,8 @@ class FastVLMBackbone(nn.Module):
                 eng = build(1)
             if self._head_loss != dict(kind="mse", beta=1.0, chunk=1):
                 eng.set_head_loss(**self._head_loss)
+            if self._head_loss_weights is not None:
+                eng.set_head_loss_weights(self._head_loss_weights["dim"], self._head_loss_weights["step"])
             if self._io_norm is not None:
                 eng.set_io_norm(**self._io_norm_for_engine())
             self._engine = eng

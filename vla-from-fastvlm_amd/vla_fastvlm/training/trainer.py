@@ -296,6 +296,11 @@ class Trainer:
             if was != now:      # legitimate (the loss is the caller's choice), but never silent
                 import warnings
                 warnings.warn(f"{p}: the checkpointed run trained with action loss {was[0]} (beta {was[1]}), this run uses {now[0]} (beta {now[1]})")
+            w = getattr(core, "action_loss_weights", None) or {}
+            was, now = (have.get("dim_weights"), have.get("step_weights")), (w.get("dim"), w.get("step"))
+            if was != now:      # the same rule for the loss weights
+                import warnings
+                warnings.warn(f"{p}: the checkpointed run trained with action loss weights dim={was[0]} step={was[1]}, this run uses dim={now[0]} step={now[1]}")
         own = self.model.state_dict()
         # `.io_norm.` / splice-mode keys exist in state_dict() only while they are on, so a freshly built model does not list them -- let them
         # through (FastVLMBackbone._load_from_state_dict re-applies them)

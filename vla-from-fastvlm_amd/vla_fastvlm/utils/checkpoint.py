@@ -33,6 +33,7 @@ EXTRAS_FILE = "hip_extras.json"
 # "direct" records the run's backward mode (the direct LoRA backward; absent = projected): the default when loading has to switch LoRA mode on itself
 # "action_chunk" = {"chunk_size", "n_action_steps", "loss", "beta"} -- only when something differs from (1, 1, "mse", 1.0): the head of a chunked policy is
 # K * A wide, which the reference's config cannot say; a plain policy's extras file is byte for byte what it was
+# (+ "temporal_ensemble_coeff", "dim_weights", "step_weights" -- each only when set: select_action's temporal ensembling and the weights of the chunk loss)
 LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
@@ -109,7 +110,9 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
     check_head_width(state, config.action_dim, chunk, root)
     # the file decides: no record means the record's defaults (1, 1, "mse", 1.0), whatever the environment twins say -- a plain checkpoint loads as a plain policy
     policy = FastVLAPolicy(config, chunk_size=int(chunk.get("chunk_size", 1)), n_action_steps=int(chunk.get("n_action_steps", 1)),
-                           action_loss=chunk.get("loss", "mse"), action_loss_beta=float(chunk.get("beta", 1.0)))
+                           action_loss=chunk.get("loss", "mse"), action_loss_beta=float(chunk.get("beta", 1.0)),
+                           temporal_ensemble_coeff=chunk.get("temporal_ensemble_coeff", False), action_dim_weights=chunk.get("dim_weights", False),
+                           action_step_weights=chunk.get("step_weights", False))      # (False: off, whatever the twin says)
     vlm = {k[len(BACKBONE_PREFIX):]: v for k, v in state.items() if k.startswith(BACKBONE_PREFIX)}
     if vlm:
         policy.model.backbone.load_backbone_state(vlm)
@@ -172,7 +175,7 @@ def save_policy_checkpoint(policy: FastVLAPolicy, checkpoint_dir: str, include_b
     aug = policy.model.backbone.augmentation_record()
     if aug is not None:      # (written only when on) the run's image augmentation: its options and seed; the batch counter travels in optimizer.pt
         extras["augment"] = {"options": aug["options"], "seed": aug["seed"]}
-    rec = policy.model.chunk_record(getattr(policy, "n_action_steps", 1)) if hasattr(policy.model, "chunk_record") else None
+    rec = policy.model.chunk_record(getattr(policy, "n_action_steps", 1), getattr(policy, "temporal_ensemble_coeff", None)) if hasattr(policy.model, "chunk_record") else None
     if rec is not None:      # (written only when something differs from the defaults)
         extras["action_chunk"] = rec
     if any(extras.values()):
