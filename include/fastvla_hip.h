@@ -295,6 +295,45 @@ int fv_head_set_loss_weights(fv_handle* h, const float* dim_w, const float* step
  * the loss lives in; 0 for a dimension without a valid step.  actions, targets: (B, K, A) device f32.  Uses the handle's current chunk and mask, never the
  * weights.  One block per dimension, fixed-order sums (no float atomics).  On demand: no train step calls it. */
 int fv_head_loss_per_dim(fv_handle* h, const float* actions, const float* targets, int B, float* out_dev, fv_stream s);
+/* ---- flow-matching action head (pi0 / SmolVLA convention, everything in normalised action space).  With eps ~ N(0, I), a the target chunk and t in [0, 1]:
+ *     x_t = t eps + (1 - t) a        u = eps - a        sampling: x_1 = eps, x <- x + dt v for N steps of dt = -1 / N down to t = 0
+ * The velocity network v(x_t, t | observation) is the SAME expert with two more input blocks on fusion.0:
+ *     cat = [ pooled (llm_hidden) | state branch (hidden_dim) | x_t (action_dim) | phi(t) (time_dim) ]
+ *     phi(t) = [ sin(2 pi t / p_j) | cos(2 pi t / p_j) ], j < time_dim / 2, p_j geometric from min_period to max_period
+ * so the 12 tensors, their names and order and fv_head_layout's 13 offsets stay; only fusion.0.weight's column count (and with it the offsets behind it,
+ * fv_head_saved_bytes, the workspace and the training layouts) grows.  The action width is the handle's action_dim (= K * A).
+ * time_dist: 0 draws t ~ U[0, 1), 1 logit-normal t = sigmoid(dist_a + dist_b n), n ~ N(0, 1). */
+typedef struct fv_head_flow_spec {
+  int32_t time_dim;                 /* E: even, >= 2 */
+  float min_period, max_period;     /* finite, 0 < min_period < max_period (pi0: 4e-3, 4.0) */
+  int32_t time_dist;                /* 0 uniform, 1 logit-normal */
+  float dist_a, dist_b;             /* finite (read for time_dist 1 only) */
+} fv_head_flow_spec;
+/* NULL switches flow mode off: the handle is then the regression head it was, bit for bit.  Allowed only BEFORE fv_bind_workspace and before any
+ * fv_train_*_begin (FV_ERR_STATE afterwards: sizes depend on the mode).  FV_ERR_ARG, changing nothing, for an odd or non-positive time_dim, non-positive,
+ * unordered or non-finite periods, an unknown time_dist, a non-finite dist_a / dist_b.  A configuration call: it uploads time_dim / 2 frequencies. */
+int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec);
+/* Training's noising step, ONE launch: per row b a time t and per element a normal eps (Box-Muller on Philox4x32-10; the key differs from the dropout
+ * stream's, so the same (seed, offset) may serve both; the counter is a function of (row, element, offset) only: row b draws the same values whatever B is).
+ * Writes x_t and phi(t) straight into their columns of `saved` (fv_head_saved_bytes(B) bytes, the buffer the following fv_head_forward is given) and
+ * u = eps - targets into u_out (B, action_dim).  targets: (B, action_dim) device f32, normalised.  noise (B, action_dim) / t (B): device f32 that REPLACE the
+ * draws, either may be NULL.  In flow mode fv_head_forward leaves those columns alone and reads them: fv_head_flow_prepare ON THE SAME `saved` MUST COME FIRST;
+ * its output is the predicted velocity, and fv_head_mse_backward(actions = v, targets = u) evaluates the configured loss (kind, mask, weights) on velocities.
+ * The fv_train_*_forward_backward routes do the same internally from their own (seed, offset) and targets.
+ * (seed, offset) TRAVEL AS KERNEL ARGUMENTS: a hipGraph captured over this call bakes them in and replays the same draws -- inside a captured step hand
+ * in noise and t buffers and refresh those.  Asynchronous on s, allocates nothing.  FV_ERR_STATE when flow mode is off, FV_ERR_ARG for a null targets /
+ * saved / u_out or B < 1; nothing is enqueued then. */
+int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t, void* saved,
+                         float* u_out, fv_stream s);
+/* Inference: n_steps Euler steps from x_1 = noise (B, action_dim; NULL: the normals fv_head_flow_prepare would draw for (seed, offset)) to actions
+ * (B, action_dim), un-normalised on the last step when fv_head_set_io_norm is on.  The state branch and the part of fusion.0 that does not depend on t,
+ * c = W[:, :llm_hidden + hidden_dim] . [pooled | s] + b, are computed ONCE per call; every step then runs three launches that touch only fusion.0's last
+ * action_dim + time_dim columns, fusion.4 and action_head.  No dropout, no atomics, no host synchronisation, no allocation: the rows live in the bound
+ * workspace (fv_workspace_bytes grows with the mode), every reduction has a fixed order, two calls give the same bits.  n_steps travels as host state of the
+ * call: a captured graph keeps the step count and, with noise == NULL, the (seed, offset) of its capture.
+ * FV_ERR_STATE when flow mode is off or no workspace is bound, FV_ERR_ARG for n_steps < 1, B outside 1 .. max_batch or a null pointer; nothing is enqueued. */
+int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                        uint64_t seed, uint64_t offset, float* actions, fv_stream s);
 /* generic backward of the head from dL/dactions (B,A) f32 (what autograd hands a custom Function when the loss is
  * computed outside, e.g. lerobot_fastvla/modeling_fastvla.py:132 + loss.backward()); overwrites flat_grads. */
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,

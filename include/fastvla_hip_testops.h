@@ -198,6 +198,15 @@ int fv_op_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* 
 int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad, const float* dim_w, const float* step_w, float* g, float* partial,
                               size_t partial_floats, float* loss, float* metrics, int64_t n, int A, int K, int kind, float beta, float loss_scale, fv_stream s);
 
+/* the head's fused loss + backward (csrc/head_kernels.hip launch_head_backward) on explicit head dimensions, WITH d_pooled (B, feat): dL/d(pooled feature),
+ * the gradient an unfrozen backbone continues from, which no product entry point hands out at the head level.  time_dim = E > 0: the flow head, whose cat row
+ * is feat + hid + da + E wide (d_pooled is still its first feat columns).  P / G: the flat parameter / gradient buffers of that layout; actions, targets
+ * (B, da); pad (B, chunk) bytes or NULL; kind FV_LOSS_*; saved: what fv_head_forward left; metrics: 4 floats; scratch: scratch_floats floats, at least
+ * B * da + 2 * B * max(cat width, fus) + 64 + 768. */
+int fv_op_head_loss_backward(int feat, int ds, int da, int hid, int fus, int time_dim, const float* P, const float* actions, const float* targets,
+                             const uint8_t* pad, int kind, float beta, int chunk, int B, const void* saved, float* loss, float* metrics, float* G,
+                             float* scratch, size_t scratch_floats, float* d_pooled, fv_stream s);
+
 #ifdef __cplusplus
 }
 #endif

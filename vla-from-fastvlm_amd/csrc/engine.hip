@@ -184,6 +184,9 @@ struct fv_handle {
   bool no_mfma_dw = false;    // FASTVLA_NO_MFMA_DW=1: A/B switch back to the VALU depthwise kernels
   bool no_ffn32 = false;      // FASTVLA_NO_FFN32=1: A/B switch back to the 16x16x32 fused ConvFFN
   fv::HeadLoss loss{FV_LOSS_MSE, 1.0f, 1, nullptr, nullptr};   // fv_head_set_loss / fv_head_set_loss_mask; metrics: two words of the f16_flags block
+  fv::HeadFlow flow{nullptr, 0, 0.f, 0.f};   // fv_head_set_flow (hd.te > 0: on); freq: device te / 2 floats, allocated per call of the setter that needs more
+  int flow_freq_cap = 0;
+  float* flow_freq_buf = nullptr;
   float* loss_w = nullptr;        // fv_head_set_loss_weights: ONE device vector of 2 da floats per handle ([0, A) dim_w, [da, da + K) step_w), allocated on first use
   TrainState train;               // unfrozen-backbone training (train_path.inc): library-owned transposed bf16 weight copies
   int batch_invariant = 0;        // fv_set_batch_invariant: the inference tower never takes the range forms either
@@ -443,7 +446,7 @@ WsPlan plan_ws(const fv_handle* h, int B, int T, int splice) {
   p.splitk_bytes = rows <= 256 || (rows % 256 != 0 && rows <= 1024) ? (size_t)(rows <= 256 ? 40 : 24) * rows * ((std::max((size_t)d.llm_hidden, qkvw) + 255) / 256 * 256) * 4
                                : rows % 256 == 0 ? (size_t)(rows <= 2048 ? 8 : 4) * rows * ((std::max((size_t)d.llm_hidden, qkvw) + 255) / 256 * 256) * 4 : 0;
   p.splitk = take(p.splitk_bytes);
-  p.head_scr = take(fv::head_bwd_scratch_bytes(h->hd, B));
+  p.head_scr = take(std::max(fv::head_bwd_scratch_bytes(h->hd, B), fv::flow_sample_scratch_bytes(h->hd, B)));   // (flow mode: the sampler's rows live here too)
   // long sequences (the spliced prefill: 256 image + T text positions) run the split-bf16 attention kernel: its per-layer K / V records
   const int Tseq = T + (splice ? (int)P : 0);
   p.attn_scr_bytes = (d.llm_precision != 0 && Tseq >= fv::FV_ATTN_SPLIT_MIN_T && (d.llm_head_dim == 64 || d.llm_head_dim == 128))
@@ -1348,6 +1351,68 @@ int fv_head_mse_backward(fv_handle* h, const float* flat_params, const float* ac
   prof_begin(h, FV_FAM_HEAD, 4.0 * B * fv::head_offsets(h->hd).o[12], 8.0 * fv::head_offsets(h->hd).o[12], st);
   const int rc = fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p,
                                           static_cast<const float*>(saved), loss, flat_grads, scr, st, nullptr, 1.0f, &h->loss);
+  prof_end(h, st);
+  return rc;
+}
+
+int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (spec) {
+    if (spec->time_dim < 2 || spec->time_dim % 2) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: time_dim = %d must be positive and even", spec->time_dim);
+    if (!std::isfinite(spec->min_period) || !std::isfinite(spec->max_period) || !(spec->min_period > 0.f) || !(spec->max_period > spec->min_period))
+      return fv_fail(FV_ERR_ARG, "fv_head_set_flow: periods must be finite with 0 < min_period < max_period (got %g, %g)", (double)spec->min_period, (double)spec->max_period);
+    if (spec->time_dist != 0 && spec->time_dist != 1) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: unknown time_dist %d (0 uniform, 1 logit-normal)", spec->time_dist);
+    if (!std::isfinite(spec->dist_a) || !std::isfinite(spec->dist_b)) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: dist_a / dist_b must be finite");
+  }
+  // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
+  if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
+  if (!spec) { h->hd.te = 0; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; return FV_OK; }
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const int half = spec->time_dim / 2;
+  std::vector<float> fr(half);   // 2 pi / p_j, p_j geometric from min_period to max_period; in double, rounded once
+  for (int j = 0; j < half; ++j) {
+    const double frac = half > 1 ? (double)j / (half - 1) : 0.0;
+    fr[j] = (float)(2.0 * 3.14159265358979323846 / ((double)spec->min_period * std::pow((double)spec->max_period / (double)spec->min_period, frac)));
+  }
+  float* dev = h->flow_freq_cap >= half ? h->flow_freq_buf : nullptr;   // kept across off / on: toggling the mode, or asking for the same or a smaller time_dim, does not grow the handle (a LARGER one allocates anew; the old buffer stays until fv_destroy)
+  if (!dev) {
+    void* p = nullptr;
+    FV_TRY(dev_alloc(h, (size_t)half * 4, &p));
+    dev = static_cast<float*>(p);
+    h->flow_freq_cap = half;
+    h->flow_freq_buf = dev;
+  }
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  FV_HIP_CHECK(hipMemcpy(dev, fr.data(), (size_t)half * 4, hipMemcpyHostToDevice));
+  h->hd.te = spec->time_dim;
+  h->flow = fv::HeadFlow{dev, spec->time_dist, spec->dist_a, spec->dist_b};
+  return FV_OK;
+}
+
+int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t, void* saved,
+                         float* u_out, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_prepare: the head is not in flow mode (fv_head_set_flow)");
+  return fv::launch_flow_prepare(h->hd, h->flow, targets, B, seed, offset, noise, t, static_cast<float*>(saved), u_out, static_cast<hipStream_t>(s));
+}
+
+int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                        uint64_t seed, uint64_t offset, float* actions, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample: the head is not in flow mode (fv_head_set_flow)");
+  if (!flat_params || !pooled || !states || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: null pointer");
+  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: n_steps = %d must be >= 1", n_steps);
+  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
+  if (!h->ws) return fv_fail(FV_ERR_STATE, "workspace not bound: call fv_bind_workspace first");
+  const WsPlan wp = plan_ws(h, B, 1, 0);
+  if (wp.total > h->ws_bytes) return fv_fail(FV_ERR_STATE, "workspace too small for the flow sampler");
+  float* scr = reinterpret_cast<float*>(static_cast<char*>(h->ws) + wp.head_scr);
+  hipStream_t st = static_cast<hipStream_t>(s);
+  prof_begin(h, FV_FAM_HEAD, 2.0 * B * n_steps * fv::head_offsets(h->hd).o[12], 4.0 * n_steps * fv::head_offsets(h->hd).o[12], st);
+  const int rc = fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr);
   prof_end(h, st);
   return rc;
 }

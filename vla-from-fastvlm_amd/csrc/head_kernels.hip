@@ -450,13 +450,185 @@ __global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ y, const 
   }
 }
 
+// ---- flow-matching head (fv_head_set_flow): x_t = t eps + (1 - t) a, u = eps - a; sampling runs x <- x + dt v from t = 1 to t = 0 ----
+// The draws are Philox4x32-10 under a key of their own (the dropout stream of the same (seed, offset) is another stream); the counter is
+// (group, row, offset): group 0 is the row's t, group 1 + i / 4 the normals of elements 4 (i / 4) .. + 3 -- a function of (row, element) only, so row b draws
+// the same values whatever B and the launch geometry are.
+constexpr uint32_t FLOW_KEY_LO = 0x464C4F57u, FLOW_KEY_HI = 0x4D415443u;
+constexpr float FLOW_TWO_PI = 6.28318530717958647692f, FLOW_U24 = 1.0f / 16777216.0f;
+__device__ __forceinline__ uint4 flow_philox(uint32_t group, uint32_t row, uint64_t seed, uint64_t offset) {
+  return philox(make_uint4(group, row, (uint32_t)offset, (uint32_t)(offset >> 32)), make_uint2((uint32_t)seed ^ FLOW_KEY_LO, (uint32_t)(seed >> 32) ^ FLOW_KEY_HI));
+}
+// Box-Muller on two 24-bit uniforms, u1 in (0, 1] and u2 in [0, 1): (r cos, r sin) with r = sqrt(-2 log u1).  sinf / cosf / logf, not the fast intrinsics
+__device__ __forceinline__ float2 flow_box_muller(uint32_t a, uint32_t b) {
+  const float u1 = (float)((a >> 8) + 1u) * FLOW_U24, u2 = (float)(b >> 8) * FLOW_U24;
+  const float r = sqrtf(-2.0f * logf(u1)), th = FLOW_TWO_PI * u2;
+  return make_float2(r * cosf(th), r * sinf(th));
+}
+__device__ __forceinline__ void flow_normals4(uint32_t group, uint32_t row, uint64_t seed, uint64_t offset, float (&n)[4]) {
+  const uint4 r = flow_philox(group, row, seed, offset);
+  const float2 p = flow_box_muller(r.x, r.y), q = flow_box_muller(r.z, r.w);
+  n[0] = p.x; n[1] = p.y; n[2] = q.x; n[3] = q.y;
+}
+// phi(t) = [ sin(freq_j t) | cos(freq_j t) ], j < te / 2; the argument is ONE fp32 product (it reaches ~1600 rad: sinf / cosf reduce it properly)
+__device__ __forceinline__ void flow_phi(float* __restrict__ dst, const float* __restrict__ freq, int half, float t, int i) {
+  const float arg = freq[i] * t;
+  dst[i] = sinf(arg);
+  dst[half + i] = cosf(arg);
+}
+
+// block = one row.  cat: the row-major (B, cw) matrix inside `saved`; columns [xo, xo + da) <- x_t, [xo + da, xo + da + te) <- phi(t); u_out (B, da) <- eps - a.
+// x_t is formed in double and rounded once: t eps and (1 - t) a cancel for some rows, and the fp32 form then loses bits the loss target does not
+__global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restrict__ targets, const float* __restrict__ noise, const float* __restrict__ tin,
+                                                            float* __restrict__ cat, int cw, int xo, float* __restrict__ u_out, int da, int te,
+                                                            const float* __restrict__ freq, int time_dist, float dist_a, float dist_b, uint64_t seed,
+                                                            uint64_t offset) {
+  const int row = blockIdx.x;
+  float t;
+  if (tin) {
+    t = tin[row];
+  } else {
+    const uint4 r = flow_philox(0u, (uint32_t)row, seed, offset);
+    if (time_dist == 0) t = (float)(r.x >> 8) * FLOW_U24;
+    else t = 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x)));
+  }
+  float* xr = cat + (size_t)row * cw + xo;
+  const double td = (double)t, omt = 1.0 - td;
+  for (int g = threadIdx.x; g * 4 < da; g += 256) {
+    float n[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)row, seed, offset, n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = g * 4 + j;
+      if (i >= da) break;
+      const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)row * da + i];
+      xr[i] = (float)(td * (double)e + omt * (double)a);
+      u_out[(size_t)row * da + i] = e - a;
+    }
+  }
+  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t, i);
+}
+
+// the sampler's start: xphi (B, da + te) <- [ noise or the draws of (seed, offset) | phi(t0) ]
+__global__ __launch_bounds__(256) void flow_init_kernel(const float* __restrict__ noise, float* __restrict__ xphi, int da, int te, const float* __restrict__ freq,
+                                                         float t0, uint64_t seed, uint64_t offset) {
+  const int row = blockIdx.x;
+  float* xr = xphi + (size_t)row * (da + te);
+  for (int g = threadIdx.x; g * 4 < da; g += 256) {
+    float n[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)row, seed, offset, n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = g * 4 + j;
+      if (i >= da) break;
+      xr[i] = noise ? noise[(size_t)row * da + i] : n[j];
+    }
+  }
+  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t0, i);
+}
+
+// The sampler's products keep linear_fwd_kernel's layout: one wave per output column n, 8 batch rows per pass, coalesced weight reads, a wave_sum per row
+// (a fixed order: two runs give the same bits).  wr: row n of the weight, or a column range of it.
+__device__ __forceinline__ void flow_dot8(const float* __restrict__ x, int ldx, const float* __restrict__ wr, int K, int b0, int B, int lane, float (&acc)[8]) {
+  for (int k = lane; k < K; k += 64) {
+    const float wv = wr[k];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += x[(size_t)min(b0 + j, B - 1) * ldx + k] * wv;
+  }
+}
+// once per call: c[b][n] = b4[n] + W4[n][0 : feat] . pooled[b] + W4[n][feat : feat + hid] . s[b]  (the part of fusion.0 that does not depend on t)
+__global__ __launch_bounds__(256) void flow_cond_kernel(const float* __restrict__ pooled, int feat, const float* __restrict__ sb, int hid, const float* __restrict__ W,
+                                                         int ldw, const float* __restrict__ bias, float* __restrict__ c, int B, int N) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(pooled, feat, W + (size_t)n * ldw, feat, b0, B, lane, acc);
+  flow_dot8(sb, hid, W + (size_t)n * ldw + feat, hid, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) c[(size_t)(b0 + j) * N + n] = acc[j] + bias[n];
+}
+// step kernel A: z2[b][n] = c[b][n] + W4[n][xo : xo + xw] . [x | phi(t_i)][b]
+__global__ __launch_bounds__(256) void flow_step_a_kernel(const float* __restrict__ xphi, int xw, const float* __restrict__ W, int ldw, int xo,
+                                                           const float* __restrict__ c, float* __restrict__ z2, int B, int N) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(xphi, xw, W + (size_t)n * ldw + xo, xw, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) z2[(size_t)(b0 + j) * N + n] = c[(size_t)(b0 + j) * N + n] + acc[j];
+}
+// step kernel B: a3[b][n] = silu(b8[n] + W8[n] . silu(LN(z2[b]))).  Every block recomputes the statistics of its 8 rows (wave w: rows 2w, 2w + 1; ln_fwd_kernel's
+// two passes and order) and applies LayerNorm and SiLU while it loads: no normalised copy travels through memory and no block waits for another
+__global__ __launch_bounds__(256) void flow_step_b_kernel(const float* __restrict__ z2, const float* __restrict__ lw, const float* __restrict__ lb,
+                                                           const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ a3, int B, int N) {
+  __shared__ float st[2][8];   // mean, rstd
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, n = blockIdx.x * 4 + wv, b0 = blockIdx.y * 8;
+  for (int r = 2 * wv; r < 2 * wv + 2; ++r) {
+    const float* zr = z2 + (size_t)min(b0 + r, B - 1) * N;
+    float s = 0.f;
+    for (int i = lane; i < N; i += 64) s += zr[i];
+    const float mean = wave_sum(s) / (float)N;
+    float q = 0.f;
+    for (int i = lane; i < N; i += 64) { const float d = zr[i] - mean; q += d * d; }
+    const float rs = rsqrtf(wave_sum(q) / (float)N + LN_EPS);
+    if (lane == 0) { st[0][r] = mean; st[1][r] = rs; }
+  }
+  __syncthreads();
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const float* wr = W + (size_t)n * N;
+  for (int k = lane; k < N; k += 64) {
+    const float wk = wr[k], g = lw[k], be = lb[k];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float h = (z2[(size_t)min(b0 + j, B - 1) * N + k] - st[0][j]) * st[1][j];
+      acc[j] += silu_f(h * g + be) * wk;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) a3[(size_t)(b0 + j) * N + n] = silu_f(acc[j] + bias[n]);
+}
+// step kernel C: v = ba[n] + Wa[n] . a3[b]; x <- x + dt v in the epilogue (the lane that owns (b, n) reads and writes x[b][n], nobody else touches it).
+// Not the last step: the blocks of column group 0 also write phi(t_next) for their 8 rows.  The last step writes `actions`, with the folded action statistics
+__global__ __launch_bounds__(256) void flow_step_c_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
+                                                           float* __restrict__ xphi, int xw, int te, float dt, float t_next, const float* __restrict__ freq,
+                                                           float* __restrict__ actions, const float* __restrict__ post_scale, const float* __restrict__ post_shift,
+                                                           int B, int N) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (!actions && blockIdx.x == 0) {
+    const int half = te / 2;
+    for (int idx = threadIdx.x; idx < 8 * half; idx += 256) {
+      const int j = idx / half, i = idx - j * half;
+      if (b0 + j < B) flow_phi(xphi + (size_t)(b0 + j) * xw + N, freq, half, t_next, i);
+    }
+  }
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) {
+      const size_t b = (size_t)(b0 + j);
+      const float xn = xphi[b * xw + n] + dt * (acc[j] + bias[n]);
+      if (!actions) xphi[b * xw + n] = xn;
+      else actions[b * N + n] = post_scale ? xn * post_scale[n] + post_shift[n] : xn;
+    }
+}
+
 inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
 
 }  // namespace
 
 HeadOffsets head_offsets(const HeadDims& d) {
   HeadOffsets r;
-  const int64_t sz[12] = {d.ds, d.ds, (int64_t)d.hid * d.ds, d.hid, (int64_t)d.fus * (d.feat + d.hid), d.fus,
+  const int64_t sz[12] = {d.ds, d.ds, (int64_t)d.hid * d.ds, d.hid, (int64_t)d.fus * head_cat_width(d), d.fus,
                           d.fus, d.fus, (int64_t)d.fus * d.fus, d.fus, (int64_t)d.da * d.fus, d.da};
   int64_t o = 0;
   for (int i = 0; i < 12; ++i) {
@@ -477,7 +649,7 @@ Saved carve(const HeadDims& d, int B, float* base) {
   size_t o = 0;
   auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
   s.n0 = take((size_t)B * d.ds); s.xh0 = take((size_t)B * d.ds); s.rstd0 = take(B);
-  s.z1 = take((size_t)B * d.hid); s.cat = take((size_t)B * (d.feat + d.hid)); s.z2 = take((size_t)B * d.fus);
+  s.z1 = take((size_t)B * d.hid); s.cat = take((size_t)B * head_cat_width(d)); s.z2 = take((size_t)B * d.fus);
   s.xh2 = take((size_t)B * d.fus); s.rstd2 = take(B); s.n2 = take((size_t)B * d.fus); s.d2 = take((size_t)B * d.fus);
   s.mask = take((size_t)B * d.fus); s.z3 = take((size_t)B * d.fus); s.a3 = take((size_t)B * d.fus);
   s.total = o;
@@ -500,7 +672,7 @@ size_t adamw_scratch_bytes() { return (size_t)(SUMSQ_BLOCKS + 4) * sizeof(float)
 size_t head_saved_bytes(const HeadDims& d, int B) { return carve(d, B, nullptr).total * sizeof(float); }
 
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B) {
-  const size_t wmax = (size_t)(d.feat + d.hid > d.fus ? d.feat + d.hid : d.fus);
+  const size_t wmax = (size_t)(head_cat_width(d) > d.fus ? head_cat_width(d) : d.fus);
   // dL/dactions | two activation-gradient rows of the widest layer | alignment slack | the chunked loss's per-block partials (loss, sum w d^2, sum w)
   return ((size_t)B * d.da + 2 * (size_t)B * wmax + 64 + 3 * (size_t)CHUNK_LOSS_BLOCKS) * sizeof(float);
 }
@@ -513,7 +685,7 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
   if (drop_p < 0.f || drop_p >= 1.f) return fv_fail(FV_ERR_ARG, "head_forward: dropout p out of range");
   const HeadOffsets ho = head_offsets(d);
   const Saved sv = carve(d, B, saved);
-  const int cw = d.feat + d.hid;
+  const int cw = head_cat_width(d);   // flow mode: the x_t and phi(t) columns behind the conditioning part (launch_flow_prepare writes them)
   const dim3 blk(256);
   const float* sm = io ? io->state_mean : nullptr;
   const float* si = io ? io->state_istd : nullptr;
@@ -587,7 +759,7 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   (void)drop_p;  // the multiplier keep/(1-p) is stored in saved.mask
   const HeadOffsets ho = head_offsets(d);
   const Saved sv = carve(d, B, const_cast<float*>(saved));
-  const int cw = d.feat + d.hid;
+  const int cw = head_cat_width(d);   // flow mode: the x_t and phi(t) columns behind the conditioning part (launch_flow_prepare writes them)
   const size_t wmax = (size_t)(cw > d.fus ? cw : d.fus);
   float* ga_own = scratch;
   float* g1 = ga_own + ((size_t)B * d.da + 3) / 4 * 4;
@@ -630,6 +802,65 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(d.hid, 256)), blk, 0, s, g1, G + ho.o[3], B, d.hid);
   hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3(cdiv(d.ds, 32), b8), blk, 0, s, g1, P + ho.o[2], g2, d.ds, B, d.hid, d.ds);
   hipLaunchKernelGGL(ln_bwd_cols_kernel, dim3(cdiv(d.ds, 256)), blk, 0, s, g2, sv.xh0, G + ho.o[0], G + ho.o[1], B, d.ds);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
+                        float* saved, float* u_out, hipStream_t s) {
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_prepare: the head is not in flow mode (fv_head_set_flow)");
+  if (!targets || !saved || !u_out) return fv_fail(FV_ERR_ARG, "flow_prepare: null pointer");
+  if (B <= 0) return fv_fail(FV_ERR_ARG, "flow_prepare: B must be positive");
+  const Saved sv = carve(d, B, saved);
+  hipLaunchKernelGGL(flow_prepare_kernel, dim3(B), dim3(256), 0, s, targets, noise, t, sv.cat, head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
+                     f.time_dist, f.dist_a, f.dist_b, seed, offset);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+namespace {
+struct FlowScratch { float *n0, *xh0, *rstd0, *z1, *sb, *c, *xphi, *z2, *a3; size_t total; };
+FlowScratch flow_carve(const HeadDims& d, int B, float* base) {
+  FlowScratch r;
+  size_t o = 0;
+  auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
+  r.n0 = take((size_t)B * d.ds); r.xh0 = take((size_t)B * d.ds); r.rstd0 = take(B); r.z1 = take((size_t)B * d.hid); r.sb = take((size_t)B * d.hid);
+  r.c = take((size_t)B * d.fus); r.xphi = take((size_t)B * (d.da + d.te)); r.z2 = take((size_t)B * d.fus); r.a3 = take((size_t)B * d.fus);
+  r.total = o;
+  return r;
+}
+}  // namespace
+
+size_t flow_sample_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? flow_carve(d, B, nullptr).total * sizeof(float) : 0; }
+
+// 4 launches of conditioning (state LayerNorm, state projection, the t-independent part of fusion.0, the start), then 3 per Euler step.  No dropout, no
+// atomics, no host synchronisation; t_i = 1 - i / N and dt = -1 / N are rounded once on the host and travel as kernel arguments
+int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io) {
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample: the head is not in flow mode (fv_head_set_flow)");
+  if (!P || !pooled || !states || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample: null pointer");
+  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample: B and n_steps must be positive");
+  const HeadOffsets ho = head_offsets(d);
+  const FlowScratch fs = flow_carve(d, B, scratch);
+  const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
+  const dim3 blk(256);
+  const unsigned b8 = cdiv(B, 8);
+  hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(B, 4)), blk, 0, s, states, d.ds, P + ho.o[0], P + ho.o[1], fs.n0, fs.xh0, fs.rstd0, B, d.ds,
+                     io ? io->state_mean : nullptr, io ? io->state_istd : nullptr);
+  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.hid, 4), b8), blk, 0, s, fs.n0, d.ds, P + ho.o[2], P + ho.o[3], fs.sb, d.hid, fs.z1, B, d.hid, d.ds, 1,
+                     (const float*)nullptr, (const float*)nullptr);
+  hipLaunchKernelGGL(flow_cond_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[4], cw, P + ho.o[5], fs.c, B, d.fus);
+  hipLaunchKernelGGL(flow_init_kernel, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, 1.0f, seed, offset);
+  const float dt = (float)(-1.0 / (double)n_steps);
+  for (int i = 0; i < n_steps; ++i) {
+    const bool last = i + 1 == n_steps;
+    const float t_next = (float)(1.0 - (double)(i + 1) / (double)n_steps);
+    hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[4], cw, xo, fs.c, fs.z2, B, d.fus);
+    hipLaunchKernelGGL(flow_step_b_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[6], P + ho.o[7], P + ho.o[8], P + ho.o[9], fs.a3, B, d.fus);
+    hipLaunchKernelGGL(flow_step_c_kernel, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[10], P + ho.o[11], fs.xphi, xw, d.te, dt, t_next, f.freq,
+                       last ? actions : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr, last && io ? io->action_mean : (const float*)nullptr,
+                       B, d.da);
+  }
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }

@@ -290,7 +290,9 @@ int launch_attention_split_bwd(const float* qkv, int ld, const bf16_t* o_hi, con
                                const float2* rope, hipStream_t s, float* part, long pstride, void* scratch);
 
 // action expert (all fp32)
-struct HeadDims { int feat, ds, da, hid, fus; };
+// flow mode (fv_head_set_flow): fusion.0 reads te + da more columns, cat = [ pooled | state branch | x_t (da) | phi(t) (te) ]; te == 0: the regression head
+struct HeadDims { int feat, ds, da, hid, fus; int te = 0; };
+inline int head_cat_width(const HeadDims& d) { return d.feat + d.hid + (d.te > 0 ? d.da + d.te : 0); }
 struct HeadOffsets { int64_t o[13]; };
 HeadOffsets head_offsets(const HeadDims& d);
 size_t head_saved_bytes(const HeadDims& d, int B);
@@ -312,6 +314,15 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
                          float* scratch, hipStream_t s, float* d_pooled = nullptr, float loss_scale = 1.0f,    // loss_scale: the fused loss's dL/dactions times a power of two
                          const struct HeadLoss* hl = nullptr);
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
+// ---- flow-matching head (d.te > 0).  freq: te / 2 device floats, 2 pi / period_j.  time_dist 0: t ~ U[0, 1); 1: t = sigmoid(dist_a + dist_b n)
+struct HeadFlow { const float* freq; int time_dist; float dist_a, dist_b; };
+// one launch: draws (or reads) t per row and noise per element, writes x_t and phi(t) into their columns of saved's cat and u = noise - targets into u_out
+int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
+                        float* saved, float* u_out, hipStream_t s);
+// the Euler sampler: conditioning once, then three launches per step.  scratch: flow_sample_scratch_bytes(d, B)
+size_t flow_sample_scratch_bytes(const HeadDims& d, int B);
+int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io);
 // the chunked loss alone (what launch_head_backward runs when HeadLoss asks for it): a, t, g (n) f32, pad (n / A) bytes or null, partial
 // chunk_loss_partial_floats() floats of scratch, loss 1 float, metrics 2 floats
 size_t chunk_loss_partial_floats();

@@ -74,7 +74,7 @@ std::vector<TrainTensor> train_tensors(fv_handle* h, int64_t* total) {
   const fv::HeadOffsets ho = fv::head_offsets(h->hd);
   const fv::HeadDims& hd = h->hd;
   const int hrows[12] = {1, 1, hd.hid, 1, hd.fus, 1, 1, 1, hd.fus, 1, hd.da, 1};
-  const int hcols[12] = {hd.ds, hd.ds, hd.ds, hd.hid, hd.feat + hd.hid, hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, hd.da};
+  const int hcols[12] = {hd.ds, hd.ds, hd.ds, hd.hid, fv::head_cat_width(hd), hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, hd.da};
   for (int i = 0; i < 12; ++i) {
     TrainTensor t;
     t.name = head_names[i]; t.off = ho.o[i]; t.rows = hrows[i]; t.cols = hcols[i]; t.numel = (int64_t)t.rows * t.cols; t.bucket = TB_HEAD;
@@ -119,7 +119,7 @@ struct TrainPlan {
   size_t x_in, x_mid, xn1, qkvf, att, lse, xn2, gu, act;    // per-layer stashes: offset of layer 0, strides below
   size_t s_x, s_xn, s_qkvf, s_att, s_lse, s_gu, s_act, apart;
   size_t pre0, hsplit, tok;                                   // projector stash
-  size_t act_s, dx, dtmp, dsplit, AT, XT, dqkv, attn_scr, delta, scr, pooled, dpooled, xg, dxg, head_saved, head_scr, splitk;
+  size_t act_s, dx, dtmp, dsplit, AT, XT, dqkv, attn_scr, delta, scr, pooled, dpooled, xg, dxg, head_saved, head_scr, flow_u, splitk;
   size_t splitk_bytes, total;
   size_t wmax;   // the widest gradient operand (columns): the dsplit scratch holds rows x 3 wmax 16-bit values
 };
@@ -157,6 +157,7 @@ TrainPlan plan_train(const fv_handle* h, int B, int T) {
   p.pooled = take((size_t)B * H * 4); p.dpooled = take((size_t)B * H * 4); p.xg = take((size_t)B * H * 4); p.dxg = take((size_t)B * H * 4);
   p.head_saved = take(fv::head_saved_bytes(h->hd, B));
   p.head_scr = take(fv::head_bwd_scratch_bytes(h->hd, B));
+  p.flow_u = take(h->hd.te > 0 ? (size_t)B * h->hd.da * 4 : 0);   // flow mode: the velocity target u = eps - a of the step (nothing otherwise: the plan keeps its offsets)
   // split-K partial sums: up to 4 K ranges of the widest fp32 output cut that way (rows x pad(max(H, qkvw)) forward / dgrad, a weight
   // gradient [<= 2I][<= pad(I)] backward); launch_gemm takes as many ranges as fit
   p.splitk_bytes = (size_t)4 * std::max(rows * ((std::max(H, qkvw) + 255) / 256 * 256), std::max(H, qkvw) * ((I + 255) / 256 * 256)) * 4;
@@ -652,13 +653,21 @@ static int train_forward_backward_impl(fv_handle* h, const float* flat_params, c
   }
   FV_P(FV_FAM_ELT, 4.0 * B * H, 8.0 * B * H, fv::launch_pool_norm(c.X_in(L), lens, h->dec.norm, pooled, B, Tt, Ni, H, d.rms_eps, 0, s));
   const fv::HeadIoNorm* io = h->has_io ? &h->io : nullptr;
+  // flow mode: the one place where the backbone routes noise their targets -- x_t and phi(t) go into head_saved's cat columns from the step's (seed, offset), as
+  // fv_head_flow_prepare does for the head-only route, and the loss below compares the predicted velocity with u
+  const float* head_targets = targets;
+  if (h->hd.te > 0) {
+    float* u = c.at<float>(tp.flow_u);
+    FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_flow_prepare(h->hd, h->flow, targets, B, seed, offset, nullptr, nullptr, head_saved, u, s));
+    head_targets = u;
+  }
   // training != 0: the loss lives in normalised action space (fv_head_forward's convention)
   FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_forward(h->hd, flat_params, pooled, states, B, training ? (dropout_p > 0.f ? 1 : 2) : 2, dropout_p, seed, offset, actions,
                                                      head_saved, s, io));
 
   // ------------------------------------------------------------------------------------------------ backward
   float *dpooled = c.at<float>(tp.dpooled), *xg = c.at<float>(tp.xg), *dxg = c.at<float>(tp.dxg);
-  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p, head_saved, loss, gbuf, c.at<float>(tp.head_scr), s, dpooled,
+  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, head_targets, B, dropout_p, head_saved, loss, gbuf, c.at<float>(tp.head_scr), s, dpooled,
                                                       std::ldexp(1.0f, h->train.loss_scale_log2), &h->loss));
   c.bucket_done(TB_HEAD);
   // final norm on the pooled rows; the residual-gradient stream starts as zero everywhere else

@@ -69,6 +69,14 @@ class HeadLossSpec(C.Structure):    # fv_head_loss_spec: 12 bytes
 LOSS_KINDS = {"mse": 0, "l1": 1, "smooth_l1": 2}      # FV_LOSS_*
 
 
+class HeadFlowSpec(C.Structure):    # fv_head_flow_spec: 24 bytes
+    _fields_ = [("time_dim", C.c_int32), ("min_period", C.c_float), ("max_period", C.c_float), ("time_dist", C.c_int32), ("dist_a", C.c_float),
+                ("dist_b", C.c_float)]
+
+
+FLOW_TIME_DISTS = {"uniform": 0, "logit_normal": 1}
+
+
 class ProfileEntry(C.Structure):
     _fields_ = [("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double), ("launches", C.c_int64)]
 
@@ -124,6 +132,9 @@ SIGNATURES = {
     "fv_head_set_loss_mask": (_i, [_vp, _vp]),
     "fv_head_set_loss_weights": (_i, [_vp, _vp, _vp]),
     "fv_head_loss_per_dim": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "fv_head_set_flow": (_i, [_vp, C.POINTER(HeadFlowSpec)]),
+    "fv_head_flow_prepare": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "fv_head_flow_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _vp]),
     "fv_ensemble_create": (_i, [_vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "fv_ensemble_destroy": (_i, [_vp, _vp]),
     "fv_ensemble_reset": (_i, [_vp, _vp, _i, _vp]),
@@ -206,6 +217,7 @@ OPS_SIGNATURES = {
     "fv_op_pool_norm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "fv_op_chunk_loss": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _f, _f, _vp]),
     "fv_op_chunk_loss_weighted": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _i, _f, _f, _vp]),
+    "fv_op_head_loss_backward": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 

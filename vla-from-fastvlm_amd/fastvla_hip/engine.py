@@ -148,6 +148,7 @@ class FastVLAEngine:
         self.head_loss = dict(kind="mse", beta=1.0, chunk=1)      # set_head_loss
         self.head_loss_weights: Optional[dict] = None             # set_head_loss_weights: {"dim": A floats or None, "step": K floats or None}, None = off
         self._pad_keep: Optional[torch.Tensor] = None
+        self.head_flow: Optional[dict] = None                     # set_head_flow: None = the regression head
         self.loaded = False
 
     def close(self):
@@ -526,7 +527,7 @@ class FastVLAEngine:
     def head_views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         """name -> view into the flat buffer (state-dict order, each tensor 16-byte aligned)."""
         hd = self.head_dims
-        shapes = [(hd["ds"],), (hd["ds"],), (hd["hid"], hd["ds"]), (hd["hid"],), (hd["fus"], hd["feat"] + hd["hid"]),
+        shapes = [(hd["ds"],), (hd["ds"],), (hd["hid"], hd["ds"]), (hd["hid"],), (hd["fus"], self.head_cat_width()),
                   (hd["fus"],), (hd["fus"],), (hd["fus"],), (hd["fus"], hd["fus"]), (hd["fus"],), (hd["da"], hd["fus"]),
                   (hd["da"],)]
         out = {}
@@ -536,6 +537,71 @@ class FastVLAEngine:
                 n *= s
             out[k] = flat[off:off + n].view(*shp)
         return out
+
+    def head_cat_width(self) -> int:
+        """columns of fusion.0.weight: feat + hid, and in flow mode da + time_dim more (x_t and phi(t) come last)"""
+        hd = self.head_dims
+        return hd["feat"] + hd["hid"] + (hd["da"] + self.head_flow["time_dim"] if self.head_flow else 0)
+
+    # ---------------------------------------------------------------- flow-matching head
+    def set_head_flow(self, time_dim: Optional[int] = 64, min_period: float = 4e-3, max_period: float = 4.0, time_dist: str = "uniform",
+                      dist_a: float = 0.0, dist_b: float = 1.0) -> None:
+        """Flow mode of the action expert (fv_head_set_flow): fusion.0 reads [pooled | state | x_t | phi(t)], head_numel / head_views / head_saved follow.
+        time_dim None switches it off.  Only before the first workspace is bound and before any train_*begin (the library answers FV_ERR_STATE afterwards)."""
+        if time_dim is None:
+            _lib.check(self.lib.fv_head_set_flow(self.h, None), "fv_head_set_flow", self.h)
+            self.head_flow = None
+        else:
+            if time_dist not in _lib.FLOW_TIME_DISTS:
+                raise ValueError(f"flow time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {time_dist!r}")
+            spec = _lib.HeadFlowSpec(int(time_dim), float(min_period), float(max_period), _lib.FLOW_TIME_DISTS[time_dist], float(dist_a), float(dist_b))
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.fv_head_set_flow(self.h, C.byref(spec)), "fv_head_set_flow", self.h)
+            self.head_flow = dict(time_dim=int(time_dim), min_period=float(min_period), max_period=float(max_period), time_dist=time_dist,
+                                  dist_a=float(dist_a), dist_b=float(dist_b))
+        offs = (C.c_int64 * 13)()
+        _lib.check(self.lib.fv_head_layout(self.h, C.byref(offs)), "fv_head_layout")
+        self.head_offsets = list(offs)
+
+    def head_flow_prepare(self, targets: torch.Tensor, saved: torch.Tensor, *, seed: int = 0, offset: int = 0, noise: Optional[torch.Tensor] = None,
+                          t: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> u = eps - targets (B, da); x_t and phi(t) land in `saved` (head_saved(B)), which the following head_forward(saved=saved) reads
+        (fv_head_flow_prepare).  noise (B, da) / t (B) replace the draws of (seed, offset)."""
+        B, da = targets.shape[0], self.head_dims["da"]
+        targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
+        if targets.numel() != B * da:
+            raise ValueError(f"targets must hold (B, {da}) elements, got {tuple(targets.shape)}")
+        if noise is not None:
+            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
+            if noise.numel() != B * da:
+                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
+        if t is not None:
+            t = t.to(device=self.device, dtype=torch.float32).contiguous()
+            if t.numel() != B:
+                raise ValueError(f"t must hold B = {B} elements, got {tuple(t.shape)}")
+        u = torch.empty(B, da, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.fv_head_flow_prepare(self.h, targets.data_ptr(), B, seed, offset, _ptr(noise), _ptr(t), saved.data_ptr(), u.data_ptr(), _stream()),
+                   "fv_head_flow_prepare", self.h)
+        return u
+
+    def head_flow_sample(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, *, steps: int = 10,
+                         noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0) -> torch.Tensor:
+        """-> actions (B, da): `steps` Euler steps of the velocity field from x_1 = noise (None: drawn from (seed, offset)) to t = 0 (fv_head_flow_sample),
+        un-normalised when set_io_norm is on.  Not differentiated."""
+        B, da = pooled.shape[0], self.head_dims["da"]
+        states = states.to(device=self.device, dtype=torch.float32).contiguous()
+        pooled = pooled.contiguous()
+        if states.shape != (B, self.head_dims["ds"]):
+            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        if noise is not None:
+            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
+            if noise.numel() != B * da:
+                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
+        self.ensure_workspace(B, 1, False)
+        actions = torch.empty(B, da, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.fv_head_flow_sample(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed, offset,
+                                                actions.data_ptr(), _stream()), "fv_head_flow_sample", self.h)
+        return actions
 
     def head_saved(self, B: int) -> torch.Tensor:
         n = C.c_size_t()

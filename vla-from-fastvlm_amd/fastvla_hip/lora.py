@@ -159,14 +159,14 @@ def logical_shapes(model: ModelConfig) -> Dict[str, Tuple[int, int]]:
 
 
 def lora_layout(model: ModelConfig, rank: int, targets=None, *, state_dim: int = 14, action_dim: int = 14, hidden_dim: int = 1024, fusion_dim: int = 1024,
-                dora: bool = False):
+                dora: bool = False, flow_time_dim: int = 0):
     """The trainable flat buffer of LoRA mode, as fv_train_lora_layout reports it: -> (tensors, total_numel), tensors = dicts with name, offset, numel, rows,
     cols, bucket, packing (always 0).  [ head | projector | layer 0 adapters .. ]: every tensor starts on a multiple of 4 floats.  dora: each target's
-    lora_magnitude_vector (1 x out) behind its lora_B."""
+    lora_magnitude_vector (1 x out) behind its lora_B.  flow_time_dim = E > 0: the flow head, whose fusion.0 reads action_dim + E more columns."""
     names = parse_targets(targets)
     H, CO = model.llm.hidden, model.tower.out_dim
     ds, da, hid, fus = state_dim, action_dim, hidden_dim, fusion_dim
-    shapes = [(1, ds), (1, ds), (hid, ds), (1, hid), (fus, H + hid), (1, fus), (1, fus), (1, fus), (fus, fus), (1, fus), (da, fus), (1, da)]
+    shapes = [(1, ds), (1, ds), (hid, ds), (1, hid), (fus, H + hid + (da + flow_time_dim if flow_time_dim else 0)), (1, fus), (1, fus), (1, fus), (fus, fus), (1, fus), (da, fus), (1, da)]
     out: List[Dict] = []
     off = 0
 

@@ -71,10 +71,43 @@ class _HeadLossFunction(torch.autograd.Function):
         return (None, None, None, None, None, None) + tuple(views[k] for k in HEAD_KEYS)
 
 
+class _FlowLossFunction(torch.autograd.Function):
+    """_HeadLossFunction for the flow head: fv_head_flow_prepare noises the targets (x_t and phi(t) go straight into the saved activations, u = eps - a comes
+    back), the head predicts the velocity and the configured loss compares it with u -- prepare, forward, loss and backward all inside the library.  The
+    second output is the predicted VELOCITY, in normalised space."""
+
+    @staticmethod
+    def forward(ctx, owner, pooled, states, targets, pad, training, *params):
+        eng, flat = owner._engine(), owner._flat
+        p = float(owner.config.dropout) if training else 0.0
+        owner._drop_calls += 1
+        saved = eng.head_saved(pooled.shape[0])
+        seed, offset = owner.flow_loss_draw() if training else owner.flow_eval_draw()
+        u = eng.head_flow_prepare(targets, saved, seed=seed, offset=offset)
+        v, saved = eng.head_forward(flat, pooled, states, training=bool(training and p > 0.0), dropout_p=p, seed=owner._drop_seed, offset=owner._drop_calls,
+                                    saved=saved, normalized_actions=True)
+        loss, grads = eng.head_backward(flat, v, u, saved, dropout_p=p, pad=pad)
+        owner.last_loss_metrics = eng.head_loss_metrics() if eng.loss_is_chunked(pad) else None
+        ctx.owner, ctx.grads = owner, grads
+        ctx.mark_non_differentiable(v)
+        return loss[0], v
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_actions):
+        eng = ctx.owner._engine()
+        eng.grad_scale(ctx.grads, grad_loss.reshape(1).to(ctx.grads.device, torch.float32).contiguous())
+        views = eng.head_views(ctx.grads)
+        return (None, None, None, None, None, None) + tuple(views[k] for k in HEAD_KEYS)
+
+
 class FastVLMWithExpert(nn.Module):
-    def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0) -> None:
+    def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0, flow: Optional[dict] = None,
+                 flow_steps: int = 10, flow_seed: Optional[int] = None) -> None:
         """chunk_size = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
-        `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library."""
+        `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library.
+        flow = FastVLAEngine.set_head_flow's keyword arguments: the flow-matching head -- fusion.0 reads K * A + time_dim more columns (x_t and phi(t)),
+        head() samples with flow_steps Euler steps, head_loss() noises its targets and returns the predicted velocity.  flow_seed: the noise streams' seed
+        (default: torch's initial seed, as the dropout stream's)."""
         super().__init__()
         from fastvla_hip.engine import check_head_loss
         self.config = config
@@ -85,15 +118,56 @@ class FastVLMWithExpert(nn.Module):
         self.backbone.configure_head(state_dim=config.state_dim, action_dim=self.head_width,
                                      hidden_dim=config.hidden_dim, fusion_dim=config.fusion_dim)
         self.backbone.configure_head_loss(self.action_loss, self.action_loss_beta, self.chunk_size)
+        self.flow: Optional[dict] = None if flow is None else dict(flow)
+        self.flow_steps = int(flow_steps)
+        self.backbone.configure_head_flow(self.flow)
+        extra = self.head_width + int(self.flow["time_dim"]) if self.flow else 0
         # same module tree / init as the reference so checkpoints and seeds line up
         self.state_projection = nn.Sequential(nn.LayerNorm(config.state_dim), nn.Linear(config.state_dim, config.hidden_dim), nn.SiLU())
         self.fusion = nn.Sequential(
-            nn.Linear(self.backbone.output_dim + config.hidden_dim, config.fusion_dim), nn.LayerNorm(config.fusion_dim),
+            nn.Linear(self.backbone.output_dim + config.hidden_dim + extra, config.fusion_dim), nn.LayerNorm(config.fusion_dim),
             nn.SiLU(), nn.Dropout(config.dropout), nn.Linear(config.fusion_dim, config.fusion_dim), nn.SiLU())
         self.action_head = nn.Linear(config.fusion_dim, self.head_width)
         self._flat: Optional[torch.Tensor] = None
         self._drop_seed = int(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
         self._drop_calls = 0
+        self._flow_seed = int(self._drop_seed if flow_seed is None else flow_seed) & 0x7FFFFFFFFFFFFFFF
+        self._flow_loss_calls = self._flow_eval_index = self._flow_sample_calls = 0
+
+    # ------------------------------------------------------------------ flow head: the noise streams.  ONE seed, four disjoint offset ranges
+    def flow_train_draw(self, step: int, micro: int):
+        """(seed, offset) of a train step's noising: a function of the optimiser step, the micro-batch inside it and the data-parallel rank -- a resumed run
+        continues the stream, and replicas that share one seed still draw different t and eps for their local row b (the noise batch is B * world, not B)"""
+        import torch.distributed as dist
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        return self._flow_seed, (int(rank) << 44) + (int(step) << 16) + (int(micro) & 0xFFFF)
+
+    def flow_loss_draw(self):
+        """compute_loss / forward(batch) in train() mode, outside the native train step: a running counter"""
+        self._flow_loss_calls += 1
+        return self._flow_seed, (1 << 60) + self._flow_loss_calls
+
+    def flow_eval_draw(self):
+        """eval() mode: a function of the evaluation batch index, which restarts whenever the module's mode is set (Trainer.evaluate calls eval() first) --
+        two evaluations of the same weights see the same noise and give the same loss"""
+        self._flow_eval_index += 1
+        return self._flow_seed, (1 << 61) + self._flow_eval_index
+
+    def flow_sample_draw(self):
+        """predict / select_action: advances per call"""
+        self._flow_sample_calls += 1
+        return self._flow_seed, (1 << 62) + self._flow_sample_calls
+
+    def train(self, mode: bool = True):
+        self._flow_eval_index = 0
+        return super().train(mode)
+
+    def flow_record(self) -> Optional[dict]:
+        """hip_extras.json "action_head": there only in flow mode"""
+        if self.flow is None:
+            return None
+        return {"type": "flow", "steps": int(self.flow_steps), **{k: self.flow[k] for k in ("time_dim", "min_period", "max_period", "time_dist", "dist_a", "dist_b")},
+                "seed": int(self._flow_seed)}
 
     # ------------------------------------------------------------------ flat parameter storage
     def head_parameters(self):
@@ -166,6 +240,8 @@ class FastVLMWithExpert(nn.Module):
         if targets.shape != (pooled.shape[0], self.head_width):
             raise ValueError(f"targets must be (B,{self.config.action_dim}), got {tuple(targets.shape)}")
         eng = self._engine()
+        if self.flow is not None:
+            raise RuntimeError("action_error_per_dim: the flow head predicts velocities of noised targets, not actions; sample with predict() and compare outside")
         with torch.no_grad():
             actions, _saved = eng.head_forward(self._flat, pooled, states.to(pooled.device, torch.float32), normalized_actions=True)
             return eng.head_loss_per_dim(actions, targets.contiguous(), pad=pad)
@@ -208,6 +284,12 @@ class FastVLMWithExpert(nn.Module):
             raise ValueError(f"states must be (B,{self.config.state_dim}), got {tuple(states.shape)}")
         params = self.head_parameters()
         differentiable = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        if self.flow is not None:
+            if differentiable:
+                raise RuntimeError("the flow head samples its actions (Euler steps of the velocity field) and sampling is not differentiated: call predict / "
+                                   "forward under torch.no_grad(), and train through compute_loss / forward(batch) / the train step")
+            seed, offset = self.flow_sample_draw()
+            return self._shape_actions(self._engine().head_flow_sample(self._flat, pooled, states, steps=self.flow_steps, seed=seed, offset=offset))
         actions = _HeadFunction.apply(self, pooled, states, self.training, differentiable, *params)
         io = self.backbone._io_norm
         if differentiable and not self.training and io is not None:
@@ -230,7 +312,8 @@ class FastVLMWithExpert(nn.Module):
         targets, pad = self.chunk_targets(targets, pad)
         if targets.shape != (pooled.shape[0], self.head_width):
             raise ValueError(f"targets must be (B,{self.config.action_dim}), got {tuple(targets.shape)}")
-        loss, actions = _HeadLossFunction.apply(self, pooled, states, targets.contiguous(), pad, self.training, *self.head_parameters())
+        fn = _HeadLossFunction if self.flow is None else _FlowLossFunction      # (flow: `actions` is the predicted velocity, in normalised space)
+        loss, actions = fn.apply(self, pooled, states, targets.contiguous(), pad, self.training, *self.head_parameters())
         return loss, self._shape_actions(actions)
 
     def forward(self, images: torch.Tensor, states: torch.Tensor, tasks: List[str], device: torch.device | None = None) -> torch.Tensor:

@@ -64,13 +64,48 @@ def resolve_chunk_options(chunk_size=None, n_action_steps=None, action_loss=None
             "step_weights": w["step"]}
 
 
+FLOW_MIN_PERIOD, FLOW_MAX_PERIOD = 4e-3, 4.0      # pi0's periods of the time embedding
+FLOW_DIST_A, FLOW_DIST_B = 0.0, 1.0                # logit-normal time: t = sigmoid(a + b n)
+
+
+def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, flow_time_dist=None) -> Dict:
+    """-> {"action_head": "regression" | "flow", "steps", "flow": FastVLAEngine.set_head_flow's keyword arguments or None}: explicit arguments, else the
+    FASTVLA_ACTION_HEAD / FASTVLA_FLOW_STEPS / FASTVLA_FLOW_TIME_DIM / FASTVLA_FLOW_TIME_DIST twins, else ("regression", 10, 64, "uniform").  A regression head
+    neither reads nor checks the flow arguments and twins.  ValueError for an
+    unknown head or time distribution, steps < 1, a time_dim that is not a positive even integer."""
+    from fastvla_hip import _lib
+
+    def pick(arg, env, cast, default):
+        if arg is not None:
+            return arg
+        raw = (os.environ.get(env) or "").strip()
+        return cast(raw) if raw else default
+
+    head = str(pick(action_head, "FASTVLA_ACTION_HEAD", str, "regression")).lower()
+    if head not in ("regression", "flow"):
+        raise ValueError(f"action_head must be 'regression' or 'flow', got {head!r}")
+    if head != "flow":      # the FASTVLA_FLOW_* twins are read and checked for a flow head only: a stray value cannot make a regression policy (or its load) raise
+        return {"action_head": head, "steps": 10, "flow": None}
+    steps, dim = pick(flow_steps, "FASTVLA_FLOW_STEPS", int, 10), pick(flow_time_dim, "FASTVLA_FLOW_TIME_DIM", int, 64)
+    dist = str(pick(flow_time_dist, "FASTVLA_FLOW_TIME_DIST", str, "uniform")).lower()
+    if int(steps) != steps or steps < 1:
+        raise ValueError(f"flow_steps must be an integer >= 1, got {steps}")
+    if int(dim) != dim or dim < 2 or dim % 2:
+        raise ValueError(f"flow_time_dim must be a positive even integer, got {dim}")
+    if dist not in _lib.FLOW_TIME_DISTS:
+        raise ValueError(f"flow_time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {dist!r}")
+    flow = dict(time_dim=int(dim), min_period=FLOW_MIN_PERIOD, max_period=FLOW_MAX_PERIOD, time_dist=dist, dist_a=FLOW_DIST_A, dist_b=FLOW_DIST_B)
+    return {"action_head": head, "steps": int(steps), "flow": flow}
+
+
 class FastVLAPolicy(nn.Module, EmaMixin):
     config_class = FastVLAConfig
     name = "fastvla"
 
     def __init__(self, config: FastVLAConfig | None = None, chunk_size: Optional[int] = None, n_action_steps: Optional[int] = None,
                  action_loss: Optional[str] = None, action_loss_beta: Optional[float] = None, temporal_ensemble_coeff: Optional[float] = None,
-                 action_dim_weights=None, action_step_weights=None) -> None:
+                 action_dim_weights=None, action_step_weights=None, action_head: Optional[str] = None, flow_steps: Optional[int] = None,
+                 flow_time_dim: Optional[int] = None, flow_time_dist: Optional[str] = None, flow_seed: Optional[int] = None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
@@ -80,7 +115,17 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         (fastvla_hip/ensemble.py).  action_dim_weights (A values) / action_step_weights (K values, or "discount:g" for g^k): weights of the loss per action
         dimension and per chunk step (set_action_loss_weights); a weight of 0 takes the element out like a padded step.
         Environment twins an explicit argument beats: FASTVLA_CHUNK_SIZE, FASTVLA_N_ACTION_STEPS, FASTVLA_ACTION_LOSS, FASTVLA_ACTION_LOSS_BETA,
-        FASTVLA_TEMPORAL_ENSEMBLE_COEFF, FASTVLA_ACTION_DIM_WEIGHTS ("1,1,1,1,1,1,4"), FASTVLA_ACTION_STEP_WEIGHTS (a list, or "discount:0.98")."""
+        FASTVLA_TEMPORAL_ENSEMBLE_COEFF, FASTVLA_ACTION_DIM_WEIGHTS ("1,1,1,1,1,1,4"), FASTVLA_ACTION_STEP_WEIGHTS (a list, or "discount:0.98").
+
+        action_head="flow" (default "regression"; FASTVLA_ACTION_HEAD): the flow-matching head (pi0 / SmolVLA convention, normalised action space).  The same
+        12 tensors, fusion.0 reading K * A + flow_time_dim more columns; training noises the targets (x_t = t eps + (1 - t) a, t ~ flow_time_dist "uniform" |
+        "logit_normal") and the configured loss, mask and weights compare the predicted velocity with u = eps - a; predict / select_action_chunk /
+        select_action SAMPLE: flow_steps Euler steps from fresh noise (policy.flow_steps may be changed at any time), the queue and the temporal ensembling
+        work on the sampled chunk as ever.  compute_loss / forward(batch) / the train step return the PREDICTED VELOCITY (normalised space) where the
+        regression head returns actions.  In eval() mode the noise of a loss evaluation depends on the evaluation batch index only: two evaluations of the
+        same weights give the same loss.  predict with autograd enabled on the head raises RuntimeError: sampling is not differentiated.  flow_seed: the noise
+        streams' seed (default: torch's initial seed).  Twins: FASTVLA_FLOW_STEPS, FASTVLA_FLOW_TIME_DIM, FASTVLA_FLOW_TIME_DIST.  A policy that does not
+        ask for flow calls nothing new."""
         super().__init__()
         self.config = config or FastVLAConfig()
         opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
@@ -88,7 +133,10 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         self.temporal_ensemble_coeff: Optional[float] = opts["temporal_ensemble_coeff"]
         self._ensembler = None      # fastvla_hip.TemporalEnsembler, created on the first select_action after reset()
         self._action_queue: deque = deque()
-        self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"])
+        fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist)
+        self.action_head = fopts["action_head"]
+        self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"],
+                                       flow_steps=fopts["steps"], flow_seed=flow_seed)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.processor = FastVLAProcessor(self.config, self.model.backbone)
@@ -244,6 +292,17 @@ class FastVLAPolicy(nn.Module, EmaMixin):
     @property
     def chunk_size(self) -> int:
         return self.model.chunk_size
+
+    @property
+    def flow_steps(self) -> int:
+        """Euler steps of a flow head's sampler (ignored by the regression head); may be changed at any time"""
+        return self.model.flow_steps
+
+    @flow_steps.setter
+    def flow_steps(self, n: int) -> None:
+        if int(n) != n or n < 1:
+            raise ValueError(f"flow_steps must be an integer >= 1, got {n}")
+        self.model.flow_steps = int(n)
 
     @torch.inference_mode()
     def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device) -> torch.Tensor:
@@ -401,14 +460,19 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         sync = force_sync or st["micro"] % k == 0
         p = float(self.config.dropout) if self.training else 0.0
         m._drop_calls += 1
+        targets, saved = prep["targets"], None
+        if m.flow is not None:      # flow head: noise the targets first (x_t, phi(t) into `saved`); the loss below then compares velocities
+            saved = eng.head_saved(prep["pooled"].shape[0])
+            seed, offset = m.flow_train_draw(st["step"], st["micro"]) if self.training else m.flow_eval_draw()
+            targets = eng.head_flow_prepare(targets, saved, seed=seed, offset=offset)
         actions, saved = eng.head_forward(flat, prep["pooled"], prep["states"], training=p > 0.0, dropout_p=p,
-                                          seed=m._drop_seed, offset=m._drop_calls, normalized_actions=True)
+                                          seed=m._drop_seed, offset=m._drop_calls, normalized_actions=True, saved=saved)
         if k > 1 and st["acc"] is None:
             st["acc"] = torch.zeros_like(flat)
         first = st["micro"] == 1  # first micro-batch of an accumulation window: the backward writes the window's buffer
         target_buf = st["g"] if k == 1 else (st["acc"] if first else st["g"])
         pad = prep.get("pad")
-        loss, grads = eng.head_backward(flat, actions, prep["targets"], saved, dropout_p=p, flat_grads=target_buf, pad=pad)
+        loss, grads = eng.head_backward(flat, actions, targets, saved, dropout_p=p, flat_grads=target_buf, pad=pad)
         if k > 1 and not first:
             eng.grad_accumulate(st["acc"], grads)
         total = st["g"] if k == 1 else st["acc"]

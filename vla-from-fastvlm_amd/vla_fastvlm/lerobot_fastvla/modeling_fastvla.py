@@ -37,17 +37,34 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        from ..fastvla.modeling_fastvla import resolve_chunk_options
+        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_options
         opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
                                      temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
                                      action_step_weights=kwargs.get("action_step_weights"))
         self.temporal_ensemble_coeff = opts["temporal_ensemble_coeff"]
+        # the flow-matching head (FastVLAPolicy(config, action_head="flow", flow_steps=, flow_time_dim=, flow_time_dist=, flow_seed=) or the FASTVLA_ACTION_HEAD /
+        # FASTVLA_FLOW_* twins; the registered config gains no field): the core policy's docstring has the semantics -- predict_action_chunk / select_action
+        # sample, forward(batch) trains the velocity
+        fopts = resolve_flow_options(kwargs.get("action_head"), kwargs.get("flow_steps"), kwargs.get("flow_time_dim"), kwargs.get("flow_time_dist"))
+        self.action_head = fopts["action_head"]
         self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
         self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
-                                       action_loss=opts["loss"], action_loss_beta=opts["beta"])
+                                       action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"], flow_steps=fopts["steps"],
+                                       flow_seed=kwargs.get("flow_seed"))
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.reset()
+
+    @property
+    def flow_steps(self) -> int:
+        """Euler steps of a flow head's sampler (ignored by the regression head); may be changed at any time"""
+        return self.model.flow_steps
+
+    @flow_steps.setter
+    def flow_steps(self, n: int) -> None:
+        if int(n) != n or n < 1:
+            raise ValueError(f"flow_steps must be an integer >= 1, got {n}")
+        self.model.flow_steps = int(n)
 
     def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
         """the loss forward(batch) evaluates from now on: "mse" | "l1" | "smooth_l1" (beta)"""

@@ -186,6 +186,7 @@ class FastVLMBackbone(nn.Module):
         self._head_dims = dict(state_dim=14, action_dim=14, hidden_dim=1024, fusion_dim=1024)
         self._head_loss = dict(kind="mse", beta=1.0, chunk=1)   # configure_head_loss: the fused loss of the head backward and the chunk length K
         self._head_loss_weights: Optional[dict] = None          # configure_head_loss_weights: {"dim", "step"} of the weighted chunk loss, None = off
+        self._head_flow: Optional[dict] = None                  # configure_head_flow: FastVLAEngine.set_head_flow's arguments, None = the regression head
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
 
@@ -256,6 +257,13 @@ class FastVLMBackbone(nn.Module):
     def configure_head(self, *, state_dim: int, action_dim: int, hidden_dim: int, fusion_dim: int) -> None:
         self._head_dims = dict(state_dim=state_dim, action_dim=action_dim, hidden_dim=hidden_dim, fusion_dim=fusion_dim)
         self._engine = None
+
+    def configure_head_flow(self, flow: Optional[dict]) -> None:
+        """Flow mode of the action expert (FastVLAEngine.set_head_flow's keyword arguments; None = off).  The head's layout depends on it, so it is fixed
+        before the engine exists."""
+        if self._engine is not None and flow != self._head_flow:
+            raise RuntimeError("configure_head_flow: the engine is already built (the head's layout and the workspace depend on the mode)")
+        self._head_flow = None if flow is None else dict(flow)
 
     def configure_head_loss(self, kind: str = "mse", beta: float = 1.0, chunk: int = 1) -> None:
         """Action chunks: the head's action_dim (configure_head) is chunk * A, and `kind` ("mse" | "l1" | "smooth_l1", beta for the last) is the loss the
@@ -347,6 +355,8 @@ class FastVLMBackbone(nn.Module):
                 warnings.warn(f"llm_precision={prec} refused for '{self.config.model_id}' ({exc}); falling back to llm_precision=1 "
                               "(split-bf16 operands: no range limit, 2x the decoder's MFMA work)")
                 eng = build(1)
+            if self._head_flow is not None:      # (first: before any workspace is bound)
+                eng.set_head_flow(**self._head_flow)
             if self._head_loss != dict(kind="mse", beta=1.0, chunk=1):
                 eng.set_head_loss(**self._head_loss)
             if self._head_loss_weights is not None:

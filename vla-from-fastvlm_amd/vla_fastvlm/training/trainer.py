@@ -301,6 +301,12 @@ class Trainer:
             if was != now:      # the same rule for the loss weights
                 import warnings
                 warnings.warn(f"{p}: the checkpointed run trained with action loss weights dim={was[0]} step={was[1]}, this run uses dim={now[0]} step={now[1]}")
+        if hasattr(core, "flow_record"):     # flow against regression head: named, not a shape error; a flow run continues the checkpointed run's noise stream
+            from ..utils.checkpoint import check_fusion_width
+            check_fusion_width(state, self.model, p)
+            frec = read_extras(p).get("action_head") or {}
+            if core.flow is not None and frec.get("seed") is not None:
+                core._flow_seed = int(frec["seed"])      # (the offsets are functions of the optimiser step, which optimizer.pt restores)
         own = self.model.state_dict()
         # `.io_norm.` / splice-mode keys exist in state_dict() only while they are on, so a freshly built model does not list them -- let them
         # through (FastVLMBackbone._load_from_state_dict re-applies them)

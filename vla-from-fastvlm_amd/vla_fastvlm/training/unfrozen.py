@@ -283,6 +283,10 @@ class UnfrozenState:
         p = float(pol.config.dropout) if pol.training else 0.0
         m = pol.model
         m._drop_calls += 1
+        # flow head: the library noises the targets from the step's (seed, offset) -- the policy's flow stream, a function of the optimiser step (a resumed
+        # run continues it), which then serves the dropout mask too (another Philox key); otherwise the dropout stream as ever
+        seed, offset = m.flow_train_draw(self.step_count, self.micro) if m.flow is not None and pol.training else \
+            (m.flow_eval_draw() if m.flow is not None else (m._drop_seed, m._drop_calls))
         # per-bucket all-reduce under the backward pass; with accumulation the sum is exchanged once -- and in LoRA mode what is exchanged does not exist
         # before the projection has run: one all-reduce of the (small) trainable buffer
         overlap = k == 1 and sync and self.lora is None
@@ -301,10 +305,10 @@ class UnfrozenState:
             tower_out = eng.train_tower_forward(prep["pix"], tws)
         if self.lora_direct:
             actions, loss, _ = eng.train_lora_forward_backward(self.flat, self.lflat, tower_out, prep["ids"], prep["lens"], prep["states"], prep["targets"], ws,
-                                                               training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, lora_grads=self.lg, pad=prep.get("pad"))
+                                                               training=pol.training, dropout_p=p, seed=seed, offset=offset, lora_grads=self.lg, pad=prep.get("pad"))
         else:
             actions, loss, _ = eng.train_forward_backward(self.flat, tower_out, prep["ids"], prep["lens"], prep["states"], prep["targets"], ws,
-                                                          training=pol.training, dropout_p=p, seed=m._drop_seed, offset=m._drop_calls, flat_grads=self.g,
+                                                          training=pol.training, dropout_p=p, seed=seed, offset=offset, flat_grads=self.g,
                                                           bucket_cb=self.bucketed.bucket_ready if overlap else None, pad=prep.get("pad"))
         if self.train_tower:
             eng.train_tower_backward(prep["pix"], dto, tws, self.g, bucket_cb=self.bucketed.bucket_ready if overlap else None)

@@ -34,6 +34,8 @@ EXTRAS_FILE = "hip_extras.json"
 # "action_chunk" = {"chunk_size", "n_action_steps", "loss", "beta"} -- only when something differs from (1, 1, "mse", 1.0): the head of a chunked policy is
 # K * A wide, which the reference's config cannot say; a plain policy's extras file is byte for byte what it was
 # (+ "temporal_ensemble_coeff", "dim_weights", "step_weights" -- each only when set: select_action's temporal ensembling and the weights of the chunk loss)
+# "action_head" = {"type": "flow", "steps", "time_dim", "min_period", "max_period", "time_dist", "dist_a", "dist_b", "seed"} -- only for a flow-matching head
+# (FastVLAPolicy(action_head="flow")), whose fusion.0.weight is chunk_size * action_dim + time_dim columns wider than the regression head's
 LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
@@ -96,6 +98,15 @@ def check_head_width(state: dict, action_dim: int, chunk: dict, where="") -> Non
                          f"{'chunk_size=' + str(chunk['chunk_size']) if chunk else 'no action_chunk record in ' + EXTRAS_FILE} asks for ({want}, {w.shape[1]})")
 
 
+def check_fusion_width(state: dict, policy, where="") -> None:
+    """fusion.0.weight of the file against the policy's head: a flow checkpoint does not load into a regression policy, nor the reverse"""
+    w, own = state.get("model.fusion.0.weight"), policy.model.fusion[0].weight
+    if w is not None and tuple(w.shape) != tuple(own.shape):
+        raise ValueError(f"{where}: model.fusion.0.weight is {tuple(w.shape)} in the checkpoint and {tuple(own.shape)} in this policy, which was built with "
+                         f"action_head='{getattr(policy, 'action_head', 'regression')}': a flow head's fusion.0 reads chunk_size * action_dim + flow_time_dim more "
+                         f"columns than a regression head's -- build the policy with the action_head setting (and flow_time_dim) the checkpoint was trained with")
+
+
 def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None = None) -> FastVLAPolicy:
     root = Path(checkpoint_dir)
     cfg_path, sd_path = root / "policy_config.json", root / "policy_state_dict.pt"
@@ -112,7 +123,9 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
     policy = FastVLAPolicy(config, chunk_size=int(chunk.get("chunk_size", 1)), n_action_steps=int(chunk.get("n_action_steps", 1)),
                            action_loss=chunk.get("loss", "mse"), action_loss_beta=float(chunk.get("beta", 1.0)),
                            temporal_ensemble_coeff=chunk.get("temporal_ensemble_coeff", False), action_dim_weights=chunk.get("dim_weights", False),
-                           action_step_weights=chunk.get("step_weights", False))      # (False: off, whatever the twin says)
+                           action_step_weights=chunk.get("step_weights", False),      # (False: off, whatever the twin says)
+                           **flow_kwargs(read_extras(root).get("action_head")))
+    check_fusion_width(state, policy, root)
     vlm = {k[len(BACKBONE_PREFIX):]: v for k, v in state.items() if k.startswith(BACKBONE_PREFIX)}
     if vlm:
         policy.model.backbone.load_backbone_state(vlm)
@@ -129,6 +142,21 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
         load_lora_adapters(policy, root, ex["lora"])
     policy.eval()
     return policy
+
+
+def flow_kwargs(rec) -> dict:
+    """FastVLAPolicy's action-head arguments from a checkpoint's "action_head" record; no record: the regression head, whatever the twins say"""
+    if not rec or rec.get("type") != "flow":
+        return {"action_head": "regression"}
+    # the embedding's periods and the time distribution's parameters are constants of this build: a record written with others would load into another network
+    from ..fastvla.modeling_fastvla import FLOW_DIST_A, FLOW_DIST_B, FLOW_MAX_PERIOD, FLOW_MIN_PERIOD
+    ours = {"min_period": FLOW_MIN_PERIOD, "max_period": FLOW_MAX_PERIOD, "dist_a": FLOW_DIST_A, "dist_b": FLOW_DIST_B}
+    theirs = {k: float(rec.get(k, v)) for k, v in ours.items()}
+    if theirs != ours:
+        raise ValueError(f"the checkpoint's action_head record was written with {theirs}, this build's flow head uses {ours}: the time embedding / time "
+                         "distribution would differ from the one the weights were trained with")
+    return {"action_head": "flow", "flow_steps": int(rec.get("steps", 10)), "flow_time_dim": int(rec["time_dim"]), "flow_time_dist": rec.get("time_dist", "uniform"),
+            "flow_seed": rec.get("seed")}
 
 
 def load_lora_adapters(policy: FastVLAPolicy, checkpoint_dir, lora_extras: dict, optim: dict | None = None) -> None:
@@ -178,6 +206,9 @@ def save_policy_checkpoint(policy: FastVLAPolicy, checkpoint_dir: str, include_b
     rec = policy.model.chunk_record(getattr(policy, "n_action_steps", 1), getattr(policy, "temporal_ensemble_coeff", None)) if hasattr(policy.model, "chunk_record") else None
     if rec is not None:      # (written only when something differs from the defaults)
         extras["action_chunk"] = rec
+    frec = policy.model.flow_record() if hasattr(policy.model, "flow_record") else None
+    if frec is not None:     # (written only in flow mode)
+        extras["action_head"] = frec
     if any(extras.values()):
         (d / EXTRAS_FILE).write_text(json.dumps(extras, indent=2))
     if include_backbone:
