@@ -82,6 +82,18 @@ int fv_op_layernorm_rows(const void* x, const float* w, const float* b, void* y,
  * causal != 0: key j visible to query i iff j <= i; lens (B) int32 or NULL masks keys >= len. */
 int fv_op_attention(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, void* out, int ldo, int B,
                     int T, int heads, int kv_heads, int D, int causal, const int32_t* lens, float scale, fv_stream s);
+/* fv::launch_attention with every argument it has (fv_op_attention passes len_add = 0): key j visible to query i iff (causal == 0 or j <= i) and
+ * j < clamp(lens[b] + len_add, 1, T) (lens NULL: T) -- the decoder's call has lens = text lengths and len_add = the image tokens.  q, k, v: bf16, 16-byte aligned,
+ * row strides multiples of 8 and >= heads D / kv_heads D; out: bf16, 8-byte aligned, ldo % 4 == 0 and >= heads D; D in {32, 64, 128}; heads % kv_heads == 0.
+ * D = 32 without masks and T % 64 == 0 runs attention32_kernel, everything else attention_kernel<D, masked>.  Rows >= the key length of q, k, v must hold FINITE
+ * values (masked keys enter the P.V product with P = 0).  A refused call enqueues nothing. */
+int fv_op_attention_bf16(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, void* out, int ldo, int B, int T, int heads, int kv_heads, int D,
+                         int causal, const int32_t* lens, int len_add, float scale, fv_stream s);
+/* the tower's attention backward alone (fv::launch_tower_attn_bwd: tattn_dq_kernel, tattn_dkv_kernel; non-causal, head_dim 32, any T): qkv bf16 rows [q | k | v], each
+ * C = heads * 32 wide (row stride ld >= 3 C), dO fp16 bits (row stride lddo >= C) -> dqkv fp16 bits in qkv's column order (row stride ldd >= 3 C); stats: 2 * B * heads * T
+ * floats, lse2 [B][heads][T] (log2 of the row sums of 2^(scale log2e s)) then delta [B][heads][T] (sum_j P_ij dP_ij).  Strides multiples of 8, pointers 16-byte aligned.
+ * A refused call enqueues nothing. */
+int fv_op_tower_attention_bwd(const void* qkv, int ld, const void* dO, int lddo, void* dqkv, int ldd, float* stats, int B, int T, int heads, float scale, fv_stream s);
 int fv_op_rmsnorm(const float* x, const float* w, void* y_bf16, int rows, int H, float eps, fv_stream s);
 /* in-place rotate-half RoPE on the q and k parts of a packed qkv (rows = B*T, position = row % T) */
 int fv_op_rope(void* qkv, int ld, int rows, int T, int heads, int kv_heads, int D, float theta, fv_stream s);

@@ -180,10 +180,15 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 __device__ __forceinline__ float xor_max_32_16(float m) {
   // max over the four 16-lane rows (lane ^ 16, lane ^ 32) without LDS: swap halves / odd-even rows of two copies
+  // The swap's two results go through scalar copies: __builtin_bit_cast(float, a[1]) on the vector ELEMENT is compiled as a load from the vector's first bytes, i.e.
+  // a[0] again -- the fmaxf then folds away and every lane is left with the maximum of lanes 0 .. 15's keys alone (p > 1 elsewhere, inf once a row's best key
+  // leads those by 128 in the log2 domain; found by the one-hot selection test)
   const auto a = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
-  m = fmaxf(__builtin_bit_cast(float, a[0]), __builtin_bit_cast(float, a[1]));
+  const unsigned a0 = a[0], a1 = a[1];
+  m = fmaxf(__builtin_bit_cast(float, a0), __builtin_bit_cast(float, a1));
   const auto b = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, m), __builtin_bit_cast(unsigned, m), false, false);
-  return fmaxf(__builtin_bit_cast(float, b[0]), __builtin_bit_cast(float, b[1]));
+  const unsigned b0 = b[0], b1 = b[1];
+  return fmaxf(__builtin_bit_cast(float, b0), __builtin_bit_cast(float, b1));
 }
 
 __global__ __launch_bounds__(256, 2) void attention32_kernel(AttnParams p) {   // (, 2): <= 256 VGPRs, so the MFMAs take VGPR accumulators (no v_accvgpr copies)

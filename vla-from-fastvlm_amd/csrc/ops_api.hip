@@ -100,6 +100,17 @@ int fv_op_attention(const void* q, const void* k, const void* v, int ldq, int ld
                               ldv, static_cast<bf16_t*>(out), ldo, B, T, heads, kv_heads, D, causal, lens, 0, scale, static_cast<hipStream_t>(s));
 }
 
+int fv_op_attention_bf16(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, void* out, int ldo, int B, int T, int heads, int kv_heads, int D,
+                         int causal, const int32_t* lens, int len_add, float scale, fv_stream s) {
+  return fv::launch_attention(static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k), static_cast<const bf16_t*>(v), ldq, ldk, ldv, static_cast<bf16_t*>(out), ldo,
+                              B, T, heads, kv_heads, D, causal, lens, len_add, scale, static_cast<hipStream_t>(s));
+}
+
+int fv_op_tower_attention_bwd(const void* qkv, int ld, const void* dO, int lddo, void* dqkv, int ldd, float* stats, int B, int T, int heads, float scale, fv_stream s) {
+  return fv::launch_tower_attn_bwd(static_cast<const bf16_t*>(qkv), ld, static_cast<const bf16_t*>(dO), lddo, static_cast<bf16_t*>(dqkv), ldd, stats, B, T, heads, scale,
+                                   static_cast<hipStream_t>(s));
+}
+
 int fv_op_rmsnorm(const float* x, const float* w, void* y_bf16, int rows, int H, float eps, fv_stream s) {
   return fv::launch_rmsnorm(x, w, static_cast<bf16_t*>(y_bf16), nullptr, H, rows, H, eps, static_cast<hipStream_t>(s));
 }
