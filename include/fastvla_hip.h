@@ -334,6 +334,32 @@ int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t see
  * FV_ERR_STATE when flow mode is off or no workspace is bound, FV_ERR_ARG for n_steps < 1, B outside 1 .. max_batch or a null pointer; nothing is enqueued. */
 int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                         uint64_t seed, uint64_t offset, float* actions, fv_stream s);
+/* ---- real-time chunking (Black, Galliker, Levine 2025): the new chunk is sampled GUIDED by the not-yet-executed rest of the previous one.  Per Euler step,
+ * with a^ = x - t v(x, t) the denoised estimate, Y the target rows and w[k] >= 0 the weight of step k (broadcast over its action_dim / chunk dimensions):
+ *     omega = w (Y - a^)      g = omega - t J^T omega, J = dv / dx      k_i = beta at t = 1, else min(beta, ((1 - t)^2 + t^2) / ((1 - t) t))
+ *     v' = v - k_i g          x <- x + dt v'
+ * (the paper's tau is 1 - t and its velocity has the other sign).  An element with w == 0 is SELECTED to omega = 0 whatever Y holds.
+ * Configuration call: uploads `chunk` HOST floats (finite, >= 0; fastvla_hip.rtc.prefix_weights builds the paper's schedule) and keeps beta =
+ * max_guidance_weight (finite, > 0).  step_weights_host == NULL switches guidance off.  FV_ERR_STATE when flow mode is off.  FV_ERR_ARG, changing nothing, for
+ * chunk < 1, action_dim % chunk != 0, a negative or non-finite weight, a non-finite or non-positive max_guidance_weight.  The guided sampler's rows join the
+ * workspace plan with the FIRST call (fv_workspace_bytes grows from then on and stays): that call must come before fv_bind_workspace (FV_ERR_STATE afterwards);
+ * later calls with the same chunk may change weights and beta at any time (they synchronise the device).  A handle that never calls it reports the
+ * fv_workspace_bytes it always did and launches what it always launched. */
+int fv_head_set_flow_guidance(fv_handle* h, int chunk, const float* step_weights_host, float max_guidance_weight);
+/* fv_head_flow_sample with guidance.  prev: (B, action_dim) device f32, the previous chunk in NORMALISED space; Y[b][k] = prev[b][k + shift] for
+ * k + shift < chunk (the shift happens inside the kernel), steps with k + shift >= chunk count as weight 0.  row_mask: (B) device int32 or NULL (all rows);
+ * a row with 0 is unguided.  chunk_out: (B, action_dim) device f32 or NULL, the final normalised x_0 (before the folded un-normalisation): the next call's
+ * `prev`.  Everything else as fv_head_flow_sample.  A row whose row_mask is 0 or whose weights are all 0 comes out as fv_head_flow_sample's row BIT FOR BIT.
+ * Conditioning once, then 8 launches per step: the unguided forward (keeping the fusion.4 pre-activation and v), omega, three transposed products that read
+ * the row-major weights as stored (action_head over the steps up to the last non-zero weight only, fusion.4, the x columns of fusion.0) with a LayerNorm
+ * backward between the last two, and the update.  No atomics, no host synchronisation, no allocation; every reduction has a fixed order: two calls give the
+ * same bits.  shift, n_steps, the step times t_i and the guidance weights k_i are HOST STATE of the call that travels as kernel arguments: a captured graph
+ * bakes them in (and, with noise == NULL, the (seed, offset) of its capture).
+ * Refused before anything is enqueued: FV_ERR_STATE when flow mode is off, guidance is not configured or no workspace is bound; FV_ERR_ARG for a null
+ * flat_params / pooled / states / prev / actions, shift outside 0 .. chunk, n_steps < 1, B outside 1 .. max_batch. */
+int fv_head_flow_sample_guided(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                               uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions, float* chunk_out,
+                               fv_stream s);
 /* generic backward of the head from dL/dactions (B,A) f32 (what autograd hands a custom Function when the loss is
  * computed outside, e.g. lerobot_fastvla/modeling_fastvla.py:132 + loss.backward()); overwrites flat_grads. */
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,

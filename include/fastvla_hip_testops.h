@@ -219,6 +219,13 @@ int fv_op_head_loss_backward(int feat, int ds, int da, int hid, int fus, int tim
                              const uint8_t* pad, int kind, float beta, int chunk, int B, const void* saved, float* loss, float* metrics, float* G,
                              float* scratch, size_t scratch_floats, float* d_pooled, fv_stream s);
 
+/* one guided sampler step's chain alone (csrc/head_kernels.hip launch_flow_vjp; fv_head_flow_sample_guided in fastvla_hip.h has the definitions): the
+ * conditioning, the velocity v(x, t) through the step's forward kernels and J^T omega, J = dv / dx, through its three transposed products and the LayerNorm
+ * backward.  Explicit head dimensions (time_dim = E > 0), freq: E / 2 DEVICE floats 2 pi / p_j; P: the flat parameters of that layout; x, omega (B, da);
+ * v_out, jt_out (B, da).  scratch: scratch_floats floats; FV_ERR_ARG names the count when it is too small. */
+int fv_op_flow_vjp(int feat, int ds, int da, int hid, int fus, int time_dim, const float* freq, const float* P, const float* pooled, const float* states, int B,
+                   const float* x, float t, const float* omega, float* v_out, float* jt_out, float* scratch, size_t scratch_floats, fv_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ struct fv_handle {
   fv::HeadFlow flow{nullptr, 0, 0.f, 0.f};   // fv_head_set_flow (hd.te > 0: on); freq: device te / 2 floats, allocated per call of the setter that needs more
   int flow_freq_cap = 0;
   float* flow_freq_buf = nullptr;
+  fv::HeadGuide guide{nullptr, 0, 0.f, 0};   // fv_head_set_flow_guidance (step_w != null: on)
+  float* guide_buf = nullptr;     // its device weights (guide_chunk floats), allocated by the first call for a chunk length and kept
+  int guide_chunk = 0;            // > 0: the workspace plan holds the guided sampler's rows (stays when guidance is switched off)
   float* loss_w = nullptr;        // fv_head_set_loss_weights: ONE device vector of 2 da floats per handle ([0, A) dim_w, [da, da + K) step_w), allocated on first use
   TrainState train;               // unfrozen-backbone training (train_path.inc): library-owned transposed bf16 weight copies
   int batch_invariant = 0;        // fv_set_batch_invariant: the inference tower never takes the range forms either
@@ -446,7 +449,8 @@ WsPlan plan_ws(const fv_handle* h, int B, int T, int splice) {
   p.splitk_bytes = rows <= 256 || (rows % 256 != 0 && rows <= 1024) ? (size_t)(rows <= 256 ? 40 : 24) * rows * ((std::max((size_t)d.llm_hidden, qkvw) + 255) / 256 * 256) * 4
                                : rows % 256 == 0 ? (size_t)(rows <= 2048 ? 8 : 4) * rows * ((std::max((size_t)d.llm_hidden, qkvw) + 255) / 256 * 256) * 4 : 0;
   p.splitk = take(p.splitk_bytes);
-  p.head_scr = take(std::max(fv::head_bwd_scratch_bytes(h->hd, B), fv::flow_sample_scratch_bytes(h->hd, B)));   // (flow mode: the sampler's rows live here too)
+  p.head_scr = take(std::max(std::max(fv::head_bwd_scratch_bytes(h->hd, B), fv::flow_sample_scratch_bytes(h->hd, B)),   // (flow mode: the sampler's rows live here too,
+                             h->guide_chunk > 0 ? fv::flow_guided_scratch_bytes(h->hd, B) : (size_t)0));                  //  and the guided sampler's once it is configured)
   // long sequences (the spliced prefill: 256 image + T text positions) run the split-bf16 attention kernel: its per-layer K / V records
   const int Tseq = T + (splice ? (int)P : 0);
   p.attn_scr_bytes = (d.llm_precision != 0 && Tseq >= fv::FV_ATTN_SPLIT_MIN_T && (d.llm_head_dim == 64 || d.llm_head_dim == 128))
@@ -1367,7 +1371,7 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   }
   // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
   if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
-  if (!spec) { h->hd.te = 0; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; return FV_OK; }
+  if (!spec) { h->hd.te = 0; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
   FV_HIP_CHECK(hipSetDevice(h->device));
   const int half = spec->time_dim / 2;
   std::vector<float> fr(half);   // 2 pi / p_j, p_j geometric from min_period to max_period; in double, rounded once
@@ -1413,6 +1417,61 @@ int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* poo
   hipStream_t st = static_cast<hipStream_t>(s);
   prof_begin(h, FV_FAM_HEAD, 2.0 * B * n_steps * fv::head_offsets(h->hd).o[12], 4.0 * n_steps * fv::head_offsets(h->hd).o[12], st);
   const int rc = fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr);
+  prof_end(h, st);
+  return rc;
+}
+
+int fv_head_set_flow_guidance(fv_handle* h, int chunk, const float* step_weights_host, float max_guidance_weight) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_guidance: the head is not in flow mode (fv_head_set_flow)");
+  if (!step_weights_host) { h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
+  if (chunk < 1 || h->hd.da % chunk) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_guidance: chunk=%d must be >= 1 and divide action_dim=%d", chunk, h->hd.da);
+  int live = 0;
+  for (int k = 0; k < chunk; ++k) {
+    if (!std::isfinite(step_weights_host[k]) || step_weights_host[k] < 0.f)
+      return fv_fail(FV_ERR_ARG, "fv_head_set_flow_guidance: step weight %d = %g must be finite and >= 0", k, (double)step_weights_host[k]);
+    if (step_weights_host[k] != 0.f) live = k + 1;
+  }
+  if (!std::isfinite(max_guidance_weight) || !(max_guidance_weight > 0.f))
+    return fv_fail(FV_ERR_ARG, "fv_head_set_flow_guidance: max_guidance_weight = %g must be finite and > 0", (double)max_guidance_weight);
+  if (h->guide_chunk != chunk) {
+    // the guided sampler's rows (the unguided sampler's and the backward chain's partial sums on top) are larger than the head part of the plan without
+    // them, and they join the plan with the first configuration: a workspace bound before that does not hold them
+    if (h->ws && h->guide_chunk == 0)
+      return fv_fail(FV_ERR_STATE, "fv_head_set_flow_guidance: the first call must come before fv_bind_workspace (the workspace grows by the guided sampler's rows)");
+    FV_HIP_CHECK(hipSetDevice(h->device));
+    void* p = nullptr;
+    FV_TRY(dev_alloc(h, (size_t)chunk * 4, &p));   // (another chunk length allocates anew; the old vector stays until fv_destroy)
+    h->guide_buf = static_cast<float*>(p);
+    h->guide_chunk = chunk;
+  }
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  FV_HIP_CHECK(hipMemcpy(h->guide_buf, step_weights_host, (size_t)chunk * 4, hipMemcpyHostToDevice));
+  h->guide = fv::HeadGuide{h->guide_buf, chunk, max_guidance_weight, live};
+  return FV_OK;
+}
+
+int fv_head_flow_sample_guided(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                               uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions, float* chunk_out,
+                               fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_guided: the head is not in flow mode (fv_head_set_flow)");
+  if (!h->guide.step_w) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_guided: guidance is not configured (fv_head_set_flow_guidance)");
+  if (!flat_params || !pooled || !states || !prev || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: null pointer");
+  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: n_steps = %d must be >= 1", n_steps);
+  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
+  if (shift < 0 || shift > h->guide.chunk) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: shift = %d outside 0 .. chunk = %d", shift, h->guide.chunk);
+  if (!h->ws) return fv_fail(FV_ERR_STATE, "workspace not bound: call fv_bind_workspace first");
+  const WsPlan wp = plan_ws(h, B, 1, 0);
+  if (wp.total > h->ws_bytes) return fv_fail(FV_ERR_STATE, "workspace too small for the guided flow sampler");
+  float* scr = reinterpret_cast<float*>(static_cast<char*>(h->ws) + wp.head_scr);
+  hipStream_t st = static_cast<hipStream_t>(s);
+  prof_begin(h, FV_FAM_HEAD, 4.0 * B * n_steps * fv::head_offsets(h->hd).o[12], 8.0 * n_steps * fv::head_offsets(h->hd).o[12], st);
+  const int rc = fv::launch_flow_sample_guided(h->hd, h->flow, h->guide, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, row_mask, actions,
+                                               chunk_out, scr, st, h->has_io ? &h->io : nullptr);
   prof_end(h, st);
   return rc;
 }

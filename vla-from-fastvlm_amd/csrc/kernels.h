@@ -323,6 +323,17 @@ int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targe
 size_t flow_sample_scratch_bytes(const HeadDims& d, int B);
 int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                        uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io);
+// guided sampling (fv_head_set_flow_guidance): step_w = chunk device floats >= 0, beta the largest guidance weight, live_steps = 1 + the last step whose
+// weight is not 0 (0: none).  prev (B, da): the previous chunk, normalised; Y[b][k] = prev[b][k + shift]; row_mask (B) int32 or null; chunk_out (B, da) or null:
+// the final normalised x_0.  A row with all-zero omega comes out as launch_flow_sample's row, bit for bit.  scratch: flow_guided_scratch_bytes(d, B)
+struct HeadGuide { const float* step_w; int chunk; float beta; int live_steps; };
+size_t flow_guided_scratch_bytes(const HeadDims& d, int B);
+int launch_flow_sample_guided(const HeadDims& d, const HeadFlow& f, const HeadGuide& gd, const float* P, const float* pooled, const float* states, int B, int n_steps,
+                              const float* noise, uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions,
+                              float* chunk_out, float* scratch, hipStream_t s, const HeadIoNorm* io);
+// one guided step's forward and backward chain for given x (B, da), t and omega (B, da): v_out = v(x, t), jt_out = (dv / dx)^T omega.  Same scratch
+int launch_flow_vjp(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, const float* x, float t,
+                    const float* omega, float* v_out, float* jt_out, float* scratch, hipStream_t s);
 // the chunked loss alone (what launch_head_backward runs when HeadLoss asks for it): a, t, g (n) f32, pad (n / A) bytes or null, partial
 // chunk_loss_partial_floats() floats of scratch, loss 1 float, metrics 2 floats
 size_t chunk_loss_partial_floats();

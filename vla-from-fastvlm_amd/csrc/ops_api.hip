@@ -316,4 +316,14 @@ int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad
   return fv::launch_chunk_loss(a, t, pad, g, partial, loss, metrics, (long)n, A, kind, beta, loss_scale, static_cast<hipStream_t>(s), dim_w, step_w, K);
 }
 
+int fv_op_flow_vjp(int feat, int ds, int da, int hid, int fus, int time_dim, const float* freq, const float* P, const float* pooled, const float* states, int B,
+                   const float* x, float t, const float* omega, float* v_out, float* jt_out, float* scratch, size_t scratch_floats, fv_stream s) {
+  if (feat < 1 || ds < 1 || da < 1 || hid < 1 || fus < 1 || time_dim < 2 || time_dim % 2 || B < 1) return fv_fail(FV_ERR_ARG, "fv_op_flow_vjp: bad dimensions");
+  fv::HeadDims d{feat, ds, da, hid, fus};
+  d.te = time_dim;
+  if (scratch_floats * sizeof(float) < fv::flow_guided_scratch_bytes(d, B))
+    return fv_fail(FV_ERR_ARG, "fv_op_flow_vjp: scratch needs %zu floats", fv::flow_guided_scratch_bytes(d, B) / sizeof(float));
+  return fv::launch_flow_vjp(d, fv::HeadFlow{freq, 0, 0.f, 0.f}, P, pooled, states, B, x, t, omega, v_out, jt_out, scratch, static_cast<hipStream_t>(s));
+}
+
 }  // extern "C"

@@ -149,6 +149,7 @@ class FastVLAEngine:
         self.head_loss_weights: Optional[dict] = None             # set_head_loss_weights: {"dim": A floats or None, "step": K floats or None}, None = off
         self._pad_keep: Optional[torch.Tensor] = None
         self.head_flow: Optional[dict] = None                     # set_head_flow: None = the regression head
+        self.head_flow_guidance: Optional[dict] = None            # set_head_flow_guidance: None = the unguided sampler only
         self.loaded = False
 
     def close(self):
@@ -602,6 +603,53 @@ class FastVLAEngine:
         _lib.check(self.lib.fv_head_flow_sample(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed, offset,
                                                 actions.data_ptr(), _stream()), "fv_head_flow_sample", self.h)
         return actions
+
+    def set_head_flow_guidance(self, step_weights=None, max_guidance_weight: float = 5.0) -> None:
+        """Guidance of the flow sampler (fv_head_set_flow_guidance; real-time chunking): step_weights = K host floats >= 0 (fastvla_hip.rtc.prefix_weights),
+        K a divisor of action_dim; None switches it off.  The first call must come before the first workspace is bound (the library answers FV_ERR_STATE
+        afterwards); later calls with the same K may change the weights and the largest guidance weight at any time."""
+        if step_weights is None:
+            _lib.check(self.lib.fv_head_set_flow_guidance(self.h, 0, None, 0.0), "fv_head_set_flow_guidance", self.h)
+            self.head_flow_guidance = None
+            return
+        w = [float(x) for x in step_weights]
+        arr = (C.c_float * len(w))(*w)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fv_head_set_flow_guidance(self.h, len(w), arr, float(max_guidance_weight)), "fv_head_set_flow_guidance", self.h)
+        self.head_flow_guidance = dict(chunk=len(w), weights=w, max_guidance_weight=float(max_guidance_weight))
+
+    def head_flow_sample_guided(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, prev: torch.Tensor, *, shift: int = 0,
+                                row_mask: Optional[torch.Tensor] = None, steps: int = 10, noise: Optional[torch.Tensor] = None, seed: int = 0,
+                                offset: int = 0, chunk_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (actions (B, da), chunk (B, da)): head_flow_sample guided by `prev` (B, da), the previous chunk in normalised space, read `shift` steps ahead
+        (fv_head_flow_sample_guided).  row_mask (B) int32: rows with 0 are sampled unguided.  chunk: the final normalised x_0, the next call's `prev`
+        (written into chunk_out when one is handed in)."""
+        B, da = pooled.shape[0], self.head_dims["da"]
+        states = states.to(device=self.device, dtype=torch.float32).contiguous()
+        pooled = pooled.contiguous()
+        if states.shape != (B, self.head_dims["ds"]):
+            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        prev = prev.to(device=self.device, dtype=torch.float32).contiguous()
+        if prev.numel() != B * da:
+            raise ValueError(f"prev must hold (B, {da}) elements, got {tuple(prev.shape)}")
+        if noise is not None:
+            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
+            if noise.numel() != B * da:
+                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
+        if row_mask is not None:
+            row_mask = row_mask.to(device=self.device, dtype=torch.int32).contiguous()
+            if row_mask.numel() != B:
+                raise ValueError(f"row_mask must hold B = {B} elements, got {tuple(row_mask.shape)}")
+        if chunk_out is None:
+            chunk_out = torch.empty(B, da, dtype=torch.float32, device=self.device)
+        elif chunk_out.dtype != torch.float32 or not chunk_out.is_contiguous() or chunk_out.numel() != B * da or chunk_out.device != prev.device:
+            raise ValueError(f"chunk_out must be a contiguous float32 (B, {da}) tensor on {self.device}")
+        self.ensure_workspace(B, 1, False)
+        actions = torch.empty(B, da, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.fv_head_flow_sample_guided(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed,
+                                                       offset, prev.data_ptr(), int(shift), _ptr(row_mask), actions.data_ptr(), chunk_out.data_ptr(), _stream()),
+                   "fv_head_flow_sample_guided", self.h)
+        return actions, chunk_out
 
     def head_saved(self, B: int) -> torch.Tensor:
         n = C.c_size_t()

@@ -121,6 +121,8 @@ class FastVLMWithExpert(nn.Module):
         self.flow: Optional[dict] = None if flow is None else dict(flow)
         self.flow_steps = int(flow_steps)
         self.backbone.configure_head_flow(self.flow)
+        self.rtc: Optional[dict] = None      # configure_rtc: real-time chunking of the flow sampler, a property of the run
+        self._chunker = self._rtc_key = None
         extra = self.head_width + int(self.flow["time_dim"]) if self.flow else 0
         # same module tree / init as the reference so checkpoints and seeds line up
         self.state_projection = nn.Sequential(nn.LayerNorm(config.state_dim), nn.Linear(config.state_dim, config.hidden_dim), nn.SiLU())
@@ -300,6 +302,69 @@ class FastVLMWithExpert(nn.Module):
             mean = torch.as_tensor(io["action_mean"], dtype=torch.float32, device=actions.device).reshape(1, -1).repeat(1, self.chunk_size)
             actions = actions * std + mean
         return self._shape_actions(actions)
+
+    # ------------------------------------------------------------------ real-time chunking (flow head): the guided sampler
+    def configure_rtc(self, rtc: Optional[dict]) -> None:
+        """rtc = {"schedule", "max_guidance_weight", "execution_horizon"} (modeling_fastvla.resolve_rtc_options) or None.  A property of the run: no checkpoint
+        records it.  The weights of (inference_delay 0, execution_horizon) are handed to the backbone so that the engine is configured BEFORE its first
+        workspace exists; another delay or horizon re-uploads them at the call that asks for it."""
+        from fastvla_hip.rtc import prefix_weights
+        self.rtc = None if rtc is None else dict(rtc)
+        self._chunker = None
+        self._rtc_key = None if rtc is None else (0, int(rtc["execution_horizon"]))
+        self.backbone.configure_head_flow_guidance(
+            None if rtc is None else dict(step_weights=prefix_weights(self.chunk_size, 0, rtc["execution_horizon"], rtc["schedule"]),
+                                          max_guidance_weight=rtc["max_guidance_weight"]))
+
+    def _rtc_chunker(self, n_env: int):
+        from fastvla_hip.rtc import RealTimeChunker
+        eng, ck = self._engine(), getattr(self, "_chunker", None)
+        if ck is not None and ck._engine is eng and ck.n_env != n_env:
+            raise ValueError(f"real-time chunking: the batch holds {n_env} environments, the previous chunks were kept for {ck.n_env}: call reset() first")
+        if ck is None or ck._engine is not eng:      # (the first call after construction, or the engine was rebuilt underneath)
+            fresh = ck is not None      # (a rebuilt engine holds the weights the backbone configured it with: delay 0, the policy's horizon)
+            ck = self._chunker = RealTimeChunker(eng, n_env)
+            if fresh:
+                self._rtc_key = (0, int(self.rtc["execution_horizon"]))
+        return ck
+
+    def rtc_reset(self, env: Optional[int] = None) -> None:
+        """forget the previous chunk of one environment or of all: their next plan is unguided (a stream-ordered memset of the row mask)"""
+        if getattr(self, "_chunker", None) is not None:
+            self._chunker.reset(env)
+
+    @property
+    def last_chunk_normalised(self) -> Optional[torch.Tensor]:
+        """(B, K, A) copy of the chunks the last guided call produced, in normalised space (what a later call takes as prev_chunk); None before the first"""
+        ck = getattr(self, "_chunker", None)
+        return None if ck is None else ck.prev.view(ck.n_env, self.chunk_size, self.config.action_dim).clone()
+
+    def rtc_sample(self, pooled: torch.Tensor, states: torch.Tensor, *, shift: int = 0, inference_delay: int = 0, execution_horizon: Optional[int] = None,
+                   prev: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> (B, K, A): the flow sampler guided by the previous chunk read `shift` steps ahead -- the chunker's own (rows without one are sampled unguided),
+        or `prev` (B, K, A) / (B, K * A), normalised, for every row."""
+        from fastvla_hip.rtc import check_rtc, prefix_weights
+        if getattr(self, "rtc", None) is None:
+            raise RuntimeError("real-time chunking is off: construct the policy with rtc=True")
+        self.materialize(pooled.device)
+        states = states.to(pooled.device, torch.float32)
+        if states.ndim != 2 or states.shape[1] != self.config.state_dim:
+            raise ValueError(f"states must be (B,{self.config.state_dim}), got {tuple(states.shape)}")
+        K = self.chunk_size
+        s = self.rtc["execution_horizon"] if execution_horizon is None else execution_horizon
+        _, d, s = check_rtc(K, inference_delay, s, self.rtc["schedule"])
+        if isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= K:
+            raise ValueError(f"shift must be an integer in 0 .. chunk_size = {K}, got {shift!r}")
+        ck = self._rtc_chunker(pooled.shape[0])
+        if (d, s) != self._rtc_key:      # (a configuration call: it synchronises the device)
+            self._engine().set_head_flow_guidance(prefix_weights(K, d, s, self.rtc["schedule"]), self.rtc["max_guidance_weight"])
+            self._rtc_key = (d, s)
+        if prev is not None:
+            prev = prev.to(pooled.device, torch.float32).reshape(pooled.shape[0], -1)
+            if prev.shape[1] != self.head_width:
+                raise ValueError(f"prev_chunk must hold (B, {K}, {self.config.action_dim}) elements, got {tuple(prev.shape)}")
+        seed, offset = self.flow_sample_draw()
+        return self._shape_actions(ck.sample(self._flat, pooled, states, shift=int(shift), steps=self.flow_steps, seed=seed, offset=offset, prev=prev))
 
     def head_loss(self, pooled: torch.Tensor, states: torch.Tensor, targets: torch.Tensor, pad=None):
         """-> (loss 0-dim, actions): the loss (MSE unless set_action_loss chose another) of the head's prediction against `targets`, differentiable w.r.t.

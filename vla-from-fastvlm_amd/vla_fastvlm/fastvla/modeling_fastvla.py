@@ -98,6 +98,47 @@ def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, 
     return {"action_head": head, "steps": int(steps), "flow": flow}
 
 
+def resolve_rtc_options(rtc=None, rtc_schedule=None, rtc_max_guidance_weight=None, rtc_execution_horizon=None, *, action_head: str, chunk_size: int,
+                        n_action_steps: int, temporal_ensemble_coeff=None) -> Optional[Dict]:
+    """-> {"schedule", "max_guidance_weight", "execution_horizon"} or None (off): explicit arguments, else the FASTVLA_RTC / FASTVLA_RTC_SCHEDULE /
+    FASTVLA_RTC_MAX_GUIDANCE_WEIGHT / FASTVLA_RTC_EXECUTION_HORIZON twins, else (off, "exp", 5.0, n_action_steps).  The other twins are read and checked
+    only when real-time chunking is on.  ValueError, naming both settings, for rtc with a regression head, with chunk_size == 1, with
+    temporal_ensemble_coeff, or with an execution horizon that does not fit the chunk; for an unknown schedule or a non-positive / non-finite weight."""
+    import math
+    from fastvla_hip.rtc import check_rtc
+
+    def pick(arg, env, cast, default):
+        if arg is not None:
+            return arg
+        raw = (os.environ.get(env) or "").strip()
+        return cast(raw) if raw else default
+
+    on = pick(rtc, "FASTVLA_RTC", lambda r: r.lower() not in ("0", "false", "no", "off"), False)
+    if not on:
+        return None
+    if action_head != "flow":
+        raise ValueError(f"rtc=True needs action_head='flow' (guidance is defined for the flow sampler only). Got rtc={on}, action_head={action_head!r}.")
+    if chunk_size == 1:
+        raise ValueError(f"rtc=True needs chunk_size > 1: there is no overlap between chunks of one step. Got rtc={on}, chunk_size={chunk_size}.")
+    if temporal_ensemble_coeff is not None:
+        raise ValueError("rtc and temporal_ensemble_coeff cannot be combined: one joins chunks by guidance, the other by averaging them. "
+                         f"Got rtc={on}, temporal_ensemble_coeff={temporal_ensemble_coeff}.")
+    schedule = str(pick(rtc_schedule, "FASTVLA_RTC_SCHEDULE", str, "exp")).lower()
+    beta = pick(rtc_max_guidance_weight, "FASTVLA_RTC_MAX_GUIDANCE_WEIGHT", float, 5.0)
+    s = pick(rtc_execution_horizon, "FASTVLA_RTC_EXECUTION_HORIZON", int, n_action_steps)
+    try:
+        beta = float(beta)
+    except (TypeError, ValueError):
+        raise ValueError(f"rtc_max_guidance_weight must be a finite number > 0, got {beta!r}") from None
+    if not math.isfinite(beta) or beta <= 0.0:
+        raise ValueError(f"rtc_max_guidance_weight must be a finite number > 0, got {beta!r}")
+    if isinstance(s, int) and not isinstance(s, bool) and s > chunk_size:
+        raise ValueError(f"rtc_execution_horizon must not exceed chunk_size (inference_delay + execution_horizon <= chunk_size). "
+                         f"Got rtc_execution_horizon={s}, chunk_size={chunk_size}.")
+    check_rtc(chunk_size, 0, s, schedule)
+    return {"schedule": schedule, "max_guidance_weight": beta, "execution_horizon": int(s)}
+
+
 class FastVLAPolicy(nn.Module, EmaMixin):
     config_class = FastVLAConfig
     name = "fastvla"
@@ -105,7 +146,8 @@ class FastVLAPolicy(nn.Module, EmaMixin):
     def __init__(self, config: FastVLAConfig | None = None, chunk_size: Optional[int] = None, n_action_steps: Optional[int] = None,
                  action_loss: Optional[str] = None, action_loss_beta: Optional[float] = None, temporal_ensemble_coeff: Optional[float] = None,
                  action_dim_weights=None, action_step_weights=None, action_head: Optional[str] = None, flow_steps: Optional[int] = None,
-                 flow_time_dim: Optional[int] = None, flow_time_dist: Optional[str] = None, flow_seed: Optional[int] = None) -> None:
+                 flow_time_dim: Optional[int] = None, flow_time_dist: Optional[str] = None, flow_seed: Optional[int] = None, rtc: Optional[bool] = None,
+                 rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
@@ -125,7 +167,16 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         regression head returns actions.  In eval() mode the noise of a loss evaluation depends on the evaluation batch index only: two evaluations of the
         same weights give the same loss.  predict with autograd enabled on the head raises RuntimeError: sampling is not differentiated.  flow_seed: the noise
         streams' seed (default: torch's initial seed).  Twins: FASTVLA_FLOW_STEPS, FASTVLA_FLOW_TIME_DIM, FASTVLA_FLOW_TIME_DIST.  A policy that does not
-        ask for flow calls nothing new."""
+        ask for flow calls nothing new.
+
+        rtc=True (flow head, chunk_size > 1; FASTVLA_RTC): real-time chunking -- a re-plan is sampled GUIDED by the not-yet-executed rest of the previous chunk
+        (fastvla_hip/rtc.py; fv_head_flow_sample_guided), so consecutive chunks stay in one mode of the distribution instead of jumping at the seam.
+        select_action keeps its queue; when it runs dry the new chunk is guided by the last one read `shift` = the number of actions served since steps
+        ahead, with inference delay 0; the first plan after reset() is unguided.  rtc_schedule "exp" | "linear" | "ones" | "zeros" (the prefix weights),
+        rtc_max_guidance_weight (beta, default 5), rtc_execution_horizon (the last steps of the chunk left free, default n_action_steps); twins
+        FASTVLA_RTC_SCHEDULE, FASTVLA_RTC_MAX_GUIDANCE_WEIGHT, FASTVLA_RTC_EXECUTION_HORIZON.  select_action_chunk(..., prev_chunk=, inference_delay=) is
+        the explicit form for asynchronous callers.  A property of the run, not of the weights: no checkpoint records it, and a policy that does not
+        ask for it calls nothing new.  Not with a regression head, chunk_size == 1 or temporal_ensemble_coeff (ValueError)."""
         super().__init__()
         self.config = config or FastVLAConfig()
         opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
@@ -135,10 +186,16 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         self._action_queue: deque = deque()
         fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist)
         self.action_head = fopts["action_head"]
+        ropts = resolve_rtc_options(rtc, rtc_schedule, rtc_max_guidance_weight, rtc_execution_horizon, action_head=self.action_head,      # (before any engine exists)
+                                    chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
         self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"],
                                        flow_steps=fopts["steps"], flow_seed=flow_seed)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
+        self.rtc = ropts
+        self._rtc_served = 0      # actions served since the last chunk was planned: the shift of the next guided plan
+        if ropts is not None:
+            self.model.configure_rtc(ropts)
         self.processor = FastVLAProcessor(self.config, self.model.backbone)
         self._opt_state = None
         self._unfrozen = None   # training/unfrozen.py UnfrozenState once enable_backbone_training() ran
@@ -305,12 +362,45 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         self.model.flow_steps = int(n)
 
     @torch.inference_mode()
-    def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device) -> torch.Tensor:
-        """-> (K, A): the whole chunk the head predicts for one observation (K = chunk_size; (1, A) without chunks)."""
+    def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device, prev_chunk: Optional[torch.Tensor] = None,
+                            inference_delay: int = 0) -> torch.Tensor:
+        """-> (K, A): the whole chunk the head predicts for one observation (K = chunk_size; (1, A) without chunks).
+        rtc=True: prev_chunk (K', A), K' <= K, in NORMALISED space -- the not-yet-executed rows of the previous chunk, policy.last_chunk_normalised[executed:] --
+        guides the sample (row k of the new chunk towards row k of prev_chunk), with the first inference_delay steps as a hard prefix: the explicit form for
+        callers that plan while the previous chunk is still being executed.  Without prev_chunk the sample is guided by the chunk the policy planned last
+        (none after reset(): unguided), read from its start."""
         self.eval()
+        if self.rtc is None:
+            if prev_chunk is not None or inference_delay != 0:
+                raise ValueError(f"prev_chunk / inference_delay need rtc=True. Got inference_delay={inference_delay}, rtc={self.rtc is not None}.")
+            tasks = self.processor.prepare_tasks(task, batch_size=1)
+            action = self.forward(image.unsqueeze(0).to(device), state.unsqueeze(0).to(device), tasks, device=device)
+            return action.reshape(self.model.chunk_size, self.config.action_dim)
+        K, A = self.model.chunk_size, self.config.action_dim
+        prev, shift = None, 0
+        if prev_chunk is not None:
+            rows = torch.as_tensor(prev_chunk, dtype=torch.float32).reshape(-1, A)
+            if not 1 <= rows.shape[0] <= K:
+                raise ValueError(f"prev_chunk must hold 1 .. chunk_size = {K} rows of {A} values, got {tuple(rows.shape)}")
+            shift = K - rows.shape[0]      # the rows sit at the END of a full chunk, which the sampler reads `shift` steps ahead
+            prev = torch.zeros(1, K, A, dtype=torch.float32, device=device)
+            prev[0, shift:] = rows.to(device)
+        return self._rtc_plan(image, state, task, device, shift=shift, inference_delay=inference_delay, prev=prev)
+
+    def _rtc_plan(self, image, state, task, device, *, shift: int, inference_delay: int = 0, prev=None) -> torch.Tensor:
+        images = self.processor.prepare_images(image.unsqueeze(0).to(device), device)
+        states = self.processor.prepare_states(state.unsqueeze(0).to(device), device)
         tasks = self.processor.prepare_tasks(task, batch_size=1)
-        action = self.forward(image.unsqueeze(0).to(device), state.unsqueeze(0).to(device), tasks, device=device)
-        return action.reshape(self.model.chunk_size, self.config.action_dim)
+        pooled = self.model.features(images, tasks, device=device)
+        chunk = self.model.rtc_sample(pooled, states, shift=shift, inference_delay=inference_delay, prev=prev)
+        self._rtc_served = 0
+        return chunk.reshape(self.model.chunk_size, self.config.action_dim)
+
+    @property
+    def last_chunk_normalised(self) -> Optional[torch.Tensor]:
+        """rtc=True: (K, A) copy of the last planned chunk in normalised space (before the folded dataset statistics), None before the first plan"""
+        last = self.model.last_chunk_normalised
+        return None if last is None else last[0]
 
     @torch.inference_mode()
     def select_action(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device) -> torch.Tensor:
@@ -320,6 +410,12 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         if self.temporal_ensemble_coeff is not None:
             chunk = self.select_action_chunk(image, state, task, device)
             return self._temporal_ensembler(1).step(chunk.reshape(1, self.model.chunk_size, self.config.action_dim))[0]
+        if self.rtc is not None:
+            if not self._action_queue:   # the re-plan is guided by the last chunk, read from the first step that has not been served yet
+                self.eval()
+                self._action_queue.extend(self._rtc_plan(image, state, task, device, shift=self._rtc_served)[: self.n_action_steps].unbind(0))
+            self._rtc_served += 1
+            return self._action_queue.popleft()
         if not self._action_queue:       # (n_action_steps = 1: a prediction on every call, row 0 served)
             self._action_queue.extend(self.select_action_chunk(image, state, task, device)[: self.n_action_steps].unbind(0))
         return self._action_queue.popleft()
@@ -333,6 +429,8 @@ class FastVLAPolicy(nn.Module, EmaMixin):
 
     def reset(self) -> None:
         self._action_queue.clear()
+        self._rtc_served = 0
+        self.model.rtc_reset()      # (rtc: the next plan is unguided)
         if self._ensembler is not None:
             self._ensembler.close()
             self._ensembler = None

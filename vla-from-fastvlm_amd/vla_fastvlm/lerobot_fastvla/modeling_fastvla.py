@@ -8,7 +8,11 @@ The loss kind ("mse" | "l1" | "smooth_l1") comes from set_action_loss() or FASTV
 
 Temporal ensembling and loss weights (the registered config schema is pinned and gets no field): FastVLAPolicy(config, temporal_ensemble_coeff=c,
 action_dim_weights=..., action_step_weights=...) or their FASTVLA_* twins.  With a coefficient select_action(batch) runs the backbone on every call and
-ensembles all B environments of the batch on the device in one launch."""
+ensembles all B environments of the batch on the device in one launch.
+
+Real-time chunking of a flow head (no config field either): FastVLAPolicy(config, action_head="flow", rtc=True, rtc_schedule=, rtc_max_guidance_weight=,
+rtc_execution_horizon=) or the FASTVLA_RTC* twins.  select_action(batch) then samples every re-plan guided by the rest of the previous chunk, for all B
+environments in one call; predict_action_chunk(batch, inference_delay=, prev_chunk_left_over=, execution_horizon=) is LeRobot's keyword set."""
 from __future__ import annotations
 
 from collections import deque
@@ -37,7 +41,7 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_options
+        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_options, resolve_rtc_options
         opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
                                      temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
                                      action_step_weights=kwargs.get("action_step_weights"))
@@ -47,12 +51,20 @@ class FastVLAPolicy(PreTrainedPolicy):
         # sample, forward(batch) trains the velocity
         fopts = resolve_flow_options(kwargs.get("action_head"), kwargs.get("flow_steps"), kwargs.get("flow_time_dim"), kwargs.get("flow_time_dist"))
         self.action_head = fopts["action_head"]
+        # real-time chunking (FastVLAPolicy(config, rtc=True, rtc_schedule=, rtc_max_guidance_weight=, rtc_execution_horizon=) or the FASTVLA_RTC* twins; no
+        # config field): re-plans of a flow head are sampled guided by the rest of the previous chunk, for all B environments of the batch in one call
+        ropts = resolve_rtc_options(kwargs.get("rtc"), kwargs.get("rtc_schedule"), kwargs.get("rtc_max_guidance_weight"), kwargs.get("rtc_execution_horizon"),
+                                    action_head=self.action_head, chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"],
+                                    temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
         self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
         self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
                                        action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"], flow_steps=fopts["steps"],
                                        flow_seed=kwargs.get("flow_seed"))
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
+        self.rtc = ropts
+        if ropts is not None:
+            self.model.configure_rtc(ropts)
         self.reset()
 
     @property
@@ -107,6 +119,9 @@ class FastVLAPolicy(PreTrainedPolicy):
 
     def reset(self):
         self._action_queue: deque[Tensor] = deque([], maxlen=self.config.n_action_steps)
+        self._rtc_served = 0      # actions served since the last plan: the shift of the next guided one
+        if getattr(self, "model", None) is not None:
+            self.model.rtc_reset()      # (rtc: the next plan of every environment is unguided)
         if getattr(self, "_ensembler", None) is not None:
             self._ensembler.close()
             self._ensembler = None
@@ -154,11 +169,40 @@ class FastVLAPolicy(PreTrainedPolicy):
         images, states, tasks = self._prepare_inputs(batch)
         return self.model(images, states, tasks, device=images.device)
 
+    @property
+    def last_chunk_normalised(self):
+        """rtc: (B, K, A) copy of the chunks planned last, in normalised space; None before the first plan"""
+        return self.model.last_chunk_normalised
+
     @torch.no_grad()
-    def predict_action_chunk(self, batch: dict[str, Tensor]) -> Tensor:
+    def predict_action_chunk(self, batch: dict[str, Tensor], inference_delay=None, prev_chunk_left_over=None, execution_horizon=None, **kwargs) -> Tensor:
+        """rtc (LeRobot's keyword set, for all B environments in one call): prev_chunk_left_over (B, K', A), K' <= K, the not-yet-executed rows of the
+        previous chunk in normalised space (last_chunk_normalised[:, executed:]); inference_delay d: its first d steps are a hard prefix; execution_horizon:
+        the last steps left free (default: the policy's).  Without prev_chunk_left_over the plan is guided by the chunk planned last, from its start
+        (none after reset(): unguided)."""
         self.eval()
-        actions = self._predict_actions(batch)
-        return actions if actions.ndim == 3 else actions.unsqueeze(1)  # [B, chunk_size, A]
+        if self.rtc is None:
+            if inference_delay or prev_chunk_left_over is not None or execution_horizon is not None:
+                raise ValueError(f"inference_delay / prev_chunk_left_over / execution_horizon need rtc=True. Got inference_delay={inference_delay}, rtc=False.")
+            actions = self._predict_actions(batch)
+            return actions if actions.ndim == 3 else actions.unsqueeze(1)  # [B, chunk_size, A]
+        K, A = self.model.chunk_size, self.config.action_dim
+        prev, shift = None, 0
+        if prev_chunk_left_over is not None:
+            rows = torch.as_tensor(prev_chunk_left_over, dtype=torch.float32)
+            if rows.ndim != 3 or rows.shape[2] != A or not 1 <= rows.shape[1] <= K:
+                raise ValueError(f"prev_chunk_left_over must be (B, 1 .. {K}, {A}), got {tuple(rows.shape)}")
+            shift = K - rows.shape[1]
+            prev = torch.zeros(rows.shape[0], K, A, dtype=torch.float32, device=rows.device)
+            prev[:, shift:] = rows
+        return self._rtc_plan(batch, shift=shift, inference_delay=int(inference_delay or 0), execution_horizon=execution_horizon, prev=prev)
+
+    def _rtc_plan(self, batch, *, shift: int, inference_delay: int = 0, execution_horizon=None, prev=None) -> Tensor:
+        images, states, tasks = self._prepare_inputs(batch)
+        pooled = self.model.features(images, tasks, device=images.device)
+        chunk = self.model.rtc_sample(pooled, states, shift=shift, inference_delay=inference_delay, execution_horizon=execution_horizon, prev=prev)
+        self._rtc_served = 0
+        return chunk
 
     @torch.no_grad()
     def select_action(self, batch: dict[str, Tensor]) -> Tensor:
@@ -172,6 +216,11 @@ class FastVLAPolicy(PreTrainedPolicy):
                 from fastvla_hip.ensemble import TemporalEnsembler
                 ens = self._ensembler = TemporalEnsembler(eng, B, self.model.chunk_size, self.config.action_dim, self.temporal_ensemble_coeff)
             return ens.step(chunk)
+        if self.rtc is not None:
+            if not self._action_queue:      # guided by the chunks planned last, read from the first step that has not been served yet
+                self._action_queue.extend(self._rtc_plan(batch, shift=self._rtc_served)[:, : self.config.n_action_steps].transpose(0, 1))
+            self._rtc_served += 1
+            return self._action_queue.popleft()
         if not self._action_queue:
             chunk = self.predict_action_chunk(batch)[:, : self.config.n_action_steps]
             self._action_queue.extend(chunk.transpose(0, 1))

@@ -187,6 +187,7 @@ class FastVLMBackbone(nn.Module):
         self._head_loss = dict(kind="mse", beta=1.0, chunk=1)   # configure_head_loss: the fused loss of the head backward and the chunk length K
         self._head_loss_weights: Optional[dict] = None          # configure_head_loss_weights: {"dim", "step"} of the weighted chunk loss, None = off
         self._head_flow: Optional[dict] = None                  # configure_head_flow: FastVLAEngine.set_head_flow's arguments, None = the regression head
+        self._head_flow_guidance: Optional[dict] = None         # configure_head_flow_guidance: FastVLAEngine.set_head_flow_guidance's arguments, None = off
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
 
@@ -264,6 +265,13 @@ class FastVLMBackbone(nn.Module):
         if self._engine is not None and flow != self._head_flow:
             raise RuntimeError("configure_head_flow: the engine is already built (the head's layout and the workspace depend on the mode)")
         self._head_flow = None if flow is None else dict(flow)
+
+    def configure_head_flow_guidance(self, guidance: Optional[dict]) -> None:
+        """Guidance of the flow sampler (FastVLAEngine.set_head_flow_guidance's keyword arguments; None = off).  Kept for the engine's construction, where it
+        is applied before any workspace is bound; an engine that already exists is told at once (the library refuses a FIRST configuration then)."""
+        self._head_flow_guidance = None if guidance is None else dict(guidance)
+        if self._engine is not None and (guidance is not None or self._engine.head_flow_guidance is not None):
+            self._engine.set_head_flow_guidance(**(self._head_flow_guidance or {"step_weights": None}))
 
     def configure_head_loss(self, kind: str = "mse", beta: float = 1.0, chunk: int = 1) -> None:
         """Action chunks: the head's action_dim (configure_head) is chunk * A, and `kind` ("mse" | "l1" | "smooth_l1", beta for the last) is the loss the
@@ -357,6 +365,8 @@ class FastVLMBackbone(nn.Module):
                 eng = build(1)
             if self._head_flow is not None:      # (first: before any workspace is bound)
                 eng.set_head_flow(**self._head_flow)
+                if getattr(self, "_head_flow_guidance", None) is not None:
+                    eng.set_head_flow_guidance(**self._head_flow_guidance)
             if self._head_loss != dict(kind="mse", beta=1.0, chunk=1):
                 eng.set_head_loss(**self._head_loss)
             if self._head_loss_weights is not None:
