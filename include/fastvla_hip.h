@@ -325,6 +325,21 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec);
  * saved / u_out or B < 1; nothing is enqueued then. */
 int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t, void* saved,
                          float* u_out, fv_stream s);
+/* Several noise draws per observation in ONE training step: draws = S, 1 .. FV_FLOW_DRAWS_MAX (1, the default, is the handle as it was, bit for bit;
+ * fv_head_set_flow(NULL) returns it to 1).  The step then computes the mean loss and the mean gradient of S single-draw steps for one backbone pass.
+ * DRAW OFFSET: draw s of row b is exactly what a single-draw call draws for row b at offset + (s << 56) -- the key, the counter (group, row, offset) and
+ * the Box-Muller are unchanged -- so draw 0 is the single draw and row b's draws depend neither on B nor on S.  Bits 56 .. 59 of `offset` therefore belong
+ * to the draw index: with S > 1 an offset that has one of them set is refused (FV_ERR_ARG, nothing enqueued) by fv_head_flow_prepare and the train routes.
+ * HEAD ROWS are draw-major, r = s B + b.  In every training-side head call B counts OBSERVATIONS (B <= max_batch as ever): targets, pad mask (B, K), pooled
+ * and states keep B rows and apply to every draw of their observation; noise, t, u_out, the predicted velocity (`actions` of fv_head_forward with
+ * training != 0, of fv_head_mse_backward and fv_head_loss_per_dim) and grad_actions have S B rows; rows 0 .. B - 1 are the single-draw call's rows.
+ * fv_head_saved_bytes, the workspace and the training workspace are sized for S B head rows.  The loss divides by all S B K A elements; the 12 head
+ * gradients are sums over all S B rows; d_pooled and the state branch's gradient are summed over the draws in ascending s (fixed order, no atomics).
+ * The state branch runs once per observation.  The train routes keep every draw's prediction in their workspace and write draw 0's rows to the caller's
+ * (B, action_dim) `actions`.  Inference (fv_head_forward with training == 0) and the samplers ignore the setting.
+ * Allowed only in flow mode, BEFORE fv_bind_workspace and before any fv_train_*_begin (FV_ERR_STATE otherwise); FV_ERR_ARG, changing nothing, outside 1 .. 16. */
+#define FV_FLOW_DRAWS_MAX 16
+int fv_head_set_flow_draws(fv_handle* h, int draws);
 /* Inference: n_steps Euler steps from x_1 = noise (B, action_dim; NULL: the normals fv_head_flow_prepare would draw for (seed, offset)) to actions
  * (B, action_dim), un-normalised on the last step when fv_head_set_io_norm is on.  The state branch and the part of fusion.0 that does not depend on t,
  * c = W[:, :llm_hidden + hidden_dim] . [pooled | s] + b, are computed ONCE per call; every step then runs three launches that touch only fusion.0's last

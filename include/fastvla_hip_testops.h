@@ -218,6 +218,13 @@ int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad
 int fv_op_head_loss_backward(int feat, int ds, int da, int hid, int fus, int time_dim, const float* P, const float* actions, const float* targets,
                              const uint8_t* pad, int kind, float beta, int chunk, int B, const void* saved, float* loss, float* metrics, float* G,
                              float* scratch, size_t scratch_floats, float* d_pooled, fv_stream s);
+/* the same with `draws` = S noise draws per observation (fv_head_set_flow_draws; flow head only, 1 <= S <= 16): actions, targets (S B, da), draw-major; pad
+ * (B, chunk) and d_pooled (B, feat) stay per observation, d_pooled summed over the draws in ascending s; saved: what fv_head_forward left on a handle with the
+ * same setting.  dim_w (da / chunk) / step_w (chunk): the loss weights as device floats, both or both NULL.  scratch: with R = S B, at least
+ * R * da + 2 * R * max(cat width, fus) + 64 + 768 floats, and (R * da + 3) / 4 more when S > 1. */
+int fv_op_head_loss_backward_draws(int feat, int ds, int da, int hid, int fus, int time_dim, int draws, const float* P, const float* actions, const float* targets,
+                                   const uint8_t* pad, const float* dim_w, const float* step_w, int kind, float beta, int chunk, int B, const void* saved, float* loss,
+                                   float* metrics, float* G, float* scratch, size_t scratch_floats, float* d_pooled, fv_stream s);
 
 /* one guided sampler step's chain alone (csrc/head_kernels.hip launch_flow_vjp; fv_head_flow_sample_guided in fastvla_hip.h has the definitions): the
  * conditioning, the velocity v(x, t) through the step's forward kernels and J^T omega, J = dv / dx, through its three transposed products and the LayerNorm

@@ -1371,7 +1371,7 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   }
   // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
   if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
-  if (!spec) { h->hd.te = 0; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
+  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
   FV_HIP_CHECK(hipSetDevice(h->device));
   const int half = spec->time_dim / 2;
   std::vector<float> fr(half);   // 2 pi / p_j, p_j geometric from min_period to max_period; in double, rounded once
@@ -1391,6 +1391,17 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   FV_HIP_CHECK(hipMemcpy(dev, fr.data(), (size_t)half * 4, hipMemcpyHostToDevice));
   h->hd.te = spec->time_dim;
   h->flow = fv::HeadFlow{dev, spec->time_dist, spec->dist_a, spec->dist_b};
+  return FV_OK;
+}
+
+int fv_head_set_flow_draws(fv_handle* h, int draws) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_draws: the head is not in flow mode (fv_head_set_flow)");
+  // the saved activations, the backward's scratch, the workspace plan and the training plan all depend on it
+  if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_draws: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on it)");
+  if (draws < 1 || draws > FV_FLOW_DRAWS_MAX) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_draws: draws = %d outside 1 .. %d", draws, FV_FLOW_DRAWS_MAX);
+  h->hd.draws = draws;
   return FV_OK;
 }
 
@@ -1532,7 +1543,9 @@ int fv_head_loss_per_dim(fv_handle* h, const float* actions, const float* target
   HandleScope _hs(h);
   if (!h || !actions || !targets || !out_dev) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_dim: null argument");
   if (B < 1) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_dim: B must be positive");
-  return fv::launch_loss_per_dim(actions, targets, h->loss.pad, out_dev, (long)B * h->loss.chunk, h->hd.da / h->loss.chunk, static_cast<hipStream_t>(s));
+  // (draws: actions and targets have S B rows, the mask keeps B)
+  return fv::launch_loss_per_dim(actions, targets, h->loss.pad, out_dev, (long)fv::head_rows(h->hd, B) * h->loss.chunk, h->hd.da / h->loss.chunk, static_cast<hipStream_t>(s),
+                                 (long)B * h->loss.chunk);
 }
 
 int fv_head_loss_metrics(fv_handle* h, const float** dev) {

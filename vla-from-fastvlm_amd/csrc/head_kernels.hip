@@ -296,13 +296,13 @@ __global__ __launch_bounds__(256) void chunk_loss_fold_kernel(const float* __res
 // block = one action dimension: out[j] = mean |a - t| over the non-padded rows (steps) of column j, 0 when there is none.  Every thread sums its rows in
 // order, then a fixed-order fold (no float atomics); a thread counts at most rows / 256 + 1 steps, exact in fp32 below 2^24 rows per thread
 __global__ __launch_bounds__(256) void loss_per_dim_kernel(const float* __restrict__ a, const float* __restrict__ t, const uint8_t* __restrict__ pad,
-                                                            float* __restrict__ out, long rows, int A) {
+                                                            float* __restrict__ out, long rows, int A, long pad_rows) {
   __shared__ float red[2][4];
   const int j = blockIdx.x;
   float sa = 0.f;
   unsigned cnt = 0;
   for (long r = threadIdx.x; r < rows; r += 256) {
-    if (pad && pad[r] != 0) continue;
+    if (pad && pad[r % pad_rows] != 0) continue;   // pad_rows < rows: the flow head's draws (fv_head_set_flow_draws) share their observation's mask
     sa += fabsf(a[r * A + j] - t[r * A + j]);
     ++cnt;
   }
@@ -477,18 +477,22 @@ __device__ __forceinline__ void flow_phi(float* __restrict__ dst, const float* _
   dst[half + i] = cosf(arg);
 }
 
-// block = one row.  cat: the row-major (B, cw) matrix inside `saved`; columns [xo, xo + da) <- x_t, [xo + da, xo + da + te) <- phi(t); u_out (B, da) <- eps - a.
+// block = one head row, grid (B, S): head row r = s B + b is draw s of observation b (fv_head_set_flow_draws; S == 1: the rows as ever).  It reads targets[b]
+// and draws what row b draws at offset + (s << 56) -- the key, the counter (group, b, offset) and the Box-Muller as they are, so row b's draws depend
+// neither on B nor on S, and draw 0 is the single draw.  Explicit noise (S B, da) / tin (S B) are read at r.
+// cat: the row-major (S B, cw) matrix inside `saved`; columns [xo, xo + da) <- x_t, [xo + da, xo + da + te) <- phi(t); u_out (S B, da) <- eps - a.
 // x_t is formed in double and rounded once: t eps and (1 - t) a cancel for some rows, and the fp32 form then loses bits the loss target does not
 __global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restrict__ targets, const float* __restrict__ noise, const float* __restrict__ tin,
                                                             float* __restrict__ cat, int cw, int xo, float* __restrict__ u_out, int da, int te,
                                                             const float* __restrict__ freq, int time_dist, float dist_a, float dist_b, uint64_t seed,
                                                             uint64_t offset) {
-  const int row = blockIdx.x;
+  const int obs = blockIdx.x, row = blockIdx.y * gridDim.x + obs;
+  offset += (uint64_t)blockIdx.y << 56;
   float t;
   if (tin) {
     t = tin[row];
   } else {
-    const uint4 r = flow_philox(0u, (uint32_t)row, seed, offset);
+    const uint4 r = flow_philox(0u, (uint32_t)obs, seed, offset);
     if (time_dist == 0) t = (float)(r.x >> 8) * FLOW_U24;
     else t = 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x)));
   }
@@ -496,17 +500,44 @@ __global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restri
   const double td = (double)t, omt = 1.0 - td;
   for (int g = threadIdx.x; g * 4 < da; g += 256) {
     float n[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)row, seed, offset, n);
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)obs, seed, offset, n);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int i = g * 4 + j;
       if (i >= da) break;
-      const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)row * da + i];
+      const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)obs * da + i];
       xr[i] = (float)(td * (double)e + omt * (double)a);
       u_out[(size_t)row * da + i] = e - a;
     }
   }
   for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t, i);
+}
+
+// ---- several noise draws per observation (fv_head_set_flow_draws): head rows are draw-major, r = s B + b.  The conditioning columns [0, n) of cat (pooled |
+// state branch) are computed once on rows 0 .. B - 1 and copied to the rows of draws 1 .. S - 1; their gradient is summed back over the draws.
+// grid.y = S - 1: m[(1 + y) B + b][c] <- m[b][c] for c < n
+__global__ __launch_bounds__(256) void draws_broadcast_kernel(float* __restrict__ m, int ld, int B, int n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * n) return;
+  const int b = (int)(i / n), c = (int)(i % n);
+  m[((size_t)(1 + blockIdx.y) * B + b) * ld + c] = m[(size_t)b * ld + c];
+}
+// m[b][c] <- m[b][c] + m[B + b][c] + .. + m[(S - 1) B + b][c] for c < n, in ascending s.  One thread owns one (b, c): it alone reads that column of the S rows
+// and writes row b -- no atomics, a fixed order, two runs give the same bits
+__global__ __launch_bounds__(256) void draws_fold_kernel(float* __restrict__ m, int ld, int B, int S, int n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * n) return;
+  const int b = (int)(i / n), c = (int)(i % n);
+  float acc = m[(size_t)b * ld + c];
+  for (int s = 1; s < S; ++s) acc += m[((size_t)s * B + b) * ld + c];
+  m[(size_t)b * ld + c] = acc;
+}
+// the (B, K) pad bytes once per draw: dst[s B K + i] <- src[i]
+__global__ __launch_bounds__(256) void draws_pad_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long n, int S) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t v = src[i];
+  for (int s = 0; s < S; ++s) dst[(size_t)s * n + i] = v;
 }
 
 // the sampler's start: xphi (B, da + te) <- [ noise or the draws of (seed, offset) | phi(t0) ]
@@ -804,14 +835,16 @@ struct Saved {
   float *n0, *xh0, *rstd0, *z1, *cat, *z2, *xh2, *rstd2, *n2, *d2, *mask, *z3, *a3;
   size_t total;
 };
+// B observations; the state branch keeps B rows, cat .. a3 have R = head_rows(d, B) of them (more than B only with fv_head_set_flow_draws)
 Saved carve(const HeadDims& d, int B, float* base) {
   Saved s;
   size_t o = 0;
+  const size_t R = (size_t)head_rows(d, B);
   auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
   s.n0 = take((size_t)B * d.ds); s.xh0 = take((size_t)B * d.ds); s.rstd0 = take(B);
-  s.z1 = take((size_t)B * d.hid); s.cat = take((size_t)B * head_cat_width(d)); s.z2 = take((size_t)B * d.fus);
-  s.xh2 = take((size_t)B * d.fus); s.rstd2 = take(B); s.n2 = take((size_t)B * d.fus); s.d2 = take((size_t)B * d.fus);
-  s.mask = take((size_t)B * d.fus); s.z3 = take((size_t)B * d.fus); s.a3 = take((size_t)B * d.fus);
+  s.z1 = take((size_t)B * d.hid); s.cat = take(R * head_cat_width(d)); s.z2 = take(R * d.fus);
+  s.xh2 = take(R * d.fus); s.rstd2 = take(R); s.n2 = take(R * d.fus); s.d2 = take(R * d.fus);
+  s.mask = take(R * d.fus); s.z3 = take(R * d.fus); s.a3 = take(R * d.fus);
   s.total = o;
   return s;
 }
@@ -834,7 +867,9 @@ size_t head_saved_bytes(const HeadDims& d, int B) { return carve(d, B, nullptr).
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B) {
   const size_t wmax = (size_t)(head_cat_width(d) > d.fus ? head_cat_width(d) : d.fus);
   // dL/dactions | two activation-gradient rows of the widest layer | alignment slack | the chunked loss's per-block partials (loss, sum w d^2, sum w)
-  return ((size_t)B * d.da + 2 * (size_t)B * wmax + 64 + 3 * (size_t)CHUNK_LOSS_BLOCKS) * sizeof(float);
+  // (draws: every row count is R = S B, and the pad mask's R K <= R da bytes, once per draw, come last)
+  const size_t R = (size_t)head_rows(d, B);
+  return (R * d.da + 2 * R * wmax + 64 + 3 * (size_t)CHUNK_LOSS_BLOCKS + (R > (size_t)B ? (R * d.da + 3) / 4 : 0)) * sizeof(float);
 }
 
 int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, const float* states, int B,
@@ -852,16 +887,20 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
   // the action un-normalisation belongs to inference only: training computes its loss against NORMALISED targets
   const float* as = io && !training ? io->action_std : nullptr;
   const float* am = io && !training ? io->action_mean : nullptr;
+  // draws (fv_head_set_flow_draws, training forms only): the state branch and the pooled copy run once per observation, their columns are copied to the rows of
+  // draws 1 .. S - 1 and everything from fusion.0 on runs on R = S B head rows (every row its own dropout mask: the element index).  R == B: the launches as ever
+  const int R = training ? head_rows(d, B) : B;
   training &= 1;   // bit 0: dropout active; any non-zero value: actions stay in normalised space
   hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(B, 4)), blk, 0, s, states, d.ds, P + ho.o[0], P + ho.o[1], sv.n0, sv.xh0, sv.rstd0, B, d.ds, sm, si);
   hipLaunchKernelGGL(copy_cols_kernel, dim3(cdiv((long)B * d.feat, 256)), blk, 0, s, pooled, d.feat, sv.cat, cw, B, d.feat);
   hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.hid, 4), cdiv(B, 8)), blk, 0, s, sv.n0, d.ds, P + ho.o[2], P + ho.o[3], sv.cat + d.feat, cw, sv.z1, B, d.hid, d.ds, 1, (const float*)nullptr, (const float*)nullptr);
-  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.fus, 4), cdiv(B, 8)), blk, 0, s, sv.cat, cw, P + ho.o[4], P + ho.o[5], sv.z2, d.fus, (float*)nullptr, B, d.fus, cw, 0, (const float*)nullptr, (const float*)nullptr);
-  hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(B, 4)), blk, 0, s, sv.z2, d.fus, P + ho.o[6], P + ho.o[7], sv.n2, sv.xh2, sv.rstd2, B, d.fus,
+  if (R > B) hipLaunchKernelGGL(draws_broadcast_kernel, dim3(cdiv((long)B * (d.feat + d.hid), 256), R / B - 1), blk, 0, s, sv.cat, cw, B, d.feat + d.hid);
+  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.fus, 4), cdiv(R, 8)), blk, 0, s, sv.cat, cw, P + ho.o[4], P + ho.o[5], sv.z2, d.fus, (float*)nullptr, R, d.fus, cw, 0, (const float*)nullptr, (const float*)nullptr);
+  hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(R, 4)), blk, 0, s, sv.z2, d.fus, P + ho.o[6], P + ho.o[7], sv.n2, sv.xh2, sv.rstd2, R, d.fus,
                      (const float*)nullptr, (const float*)nullptr);
-  hipLaunchKernelGGL(silu_dropout_kernel, dim3(cdiv((long)B * d.fus, 256)), blk, 0, s, sv.n2, sv.d2, sv.mask, (long)B * d.fus, training, drop_p, seed, offset);
-  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.fus, 4), cdiv(B, 8)), blk, 0, s, sv.d2, d.fus, P + ho.o[8], P + ho.o[9], sv.a3, d.fus, sv.z3, B, d.fus, d.fus, 1, (const float*)nullptr, (const float*)nullptr);
-  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.da, 4), cdiv(B, 8)), blk, 0, s, sv.a3, d.fus, P + ho.o[10], P + ho.o[11], actions, d.da, (float*)nullptr, B, d.da, d.fus, 0, as, am);
+  hipLaunchKernelGGL(silu_dropout_kernel, dim3(cdiv((long)R * d.fus, 256)), blk, 0, s, sv.n2, sv.d2, sv.mask, (long)R * d.fus, training, drop_p, seed, offset);
+  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.fus, 4), cdiv(R, 8)), blk, 0, s, sv.d2, d.fus, P + ho.o[8], P + ho.o[9], sv.a3, d.fus, sv.z3, R, d.fus, d.fus, 1, (const float*)nullptr, (const float*)nullptr);
+  hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.da, 4), cdiv(R, 8)), blk, 0, s, sv.a3, d.fus, P + ho.o[10], P + ho.o[11], actions, d.da, (float*)nullptr, R, d.da, d.fus, 0, as, am);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -889,10 +928,12 @@ int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float*
   return FV_OK;
 }
 
-int launch_loss_per_dim(const float* a, const float* t, const uint8_t* pad, float* out, long rows, int A, hipStream_t s) {
+int launch_loss_per_dim(const float* a, const float* t, const uint8_t* pad, float* out, long rows, int A, hipStream_t s, long pad_rows) {
   if (!a || !t || !out) return fv_fail(FV_ERR_ARG, "loss_per_dim: null pointer");
   if (rows <= 0 || A <= 0) return fv_fail(FV_ERR_ARG, "loss_per_dim: rows and the step width must be positive");
-  hipLaunchKernelGGL(loss_per_dim_kernel, dim3(A), dim3(256), 0, s, a, t, pad, out, rows, A);
+  if (pad_rows <= 0) pad_rows = rows;
+  if (rows % pad_rows) return fv_fail(FV_ERR_ARG, "loss_per_dim: the mask's rows must divide the rows");
+  hipLaunchKernelGGL(loss_per_dim_kernel, dim3(A), dim3(256), 0, s, a, t, pad, out, rows, A, pad_rows);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -921,6 +962,10 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   const Saved sv = carve(d, B, const_cast<float*>(saved));
   const int cw = head_cat_width(d);   // flow mode: the x_t and phi(t) columns behind the conditioning part (launch_flow_prepare writes them)
   const size_t wmax = (size_t)(cw > d.fus ? cw : d.fus);
+  // draws (fv_head_set_flow_draws): B counts observations, the layers down to dcat run on R = S B head rows (actions, targets = u and grad_actions have R rows,
+  // the loss divides by all R da elements), then the conditioning columns of dcat are summed over the draws and the state branch runs on B rows.  R == B: as ever
+  const int obs = B, S = head_rows(d, B) / B;
+  B *= S;
   float* ga_own = scratch;
   float* g1 = ga_own + ((size_t)B * d.da + 3) / 4 * 4;
   float* g2 = g1 + (size_t)B * wmax;
@@ -929,7 +974,14 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   const float* ga = grad_actions;
   if (!ga && chunked) {
     float* part = g2 + (size_t)B * wmax + 16;   // behind everything the layers below use; the 64 floats of slack cover the rounding of B * da and this gap (head_bwd_scratch_bytes)
-    const int rc = launch_chunk_loss(actions, targets, hl->pad, ga_own, part, loss, hl->metrics, (long)B * d.da, d.da / hl->chunk, hl->kind, hl->beta, loss_scale, s,
+    const uint8_t* pad = hl->pad;
+    if (S > 1 && pad) {   // the mask is (obs, K): every draw of an observation reads its row, from a copy per draw behind the partials
+      uint8_t* rep = reinterpret_cast<uint8_t*>(part + 3 * (size_t)CHUNK_LOSS_BLOCKS);
+      const long nk = (long)obs * hl->chunk;
+      hipLaunchKernelGGL(draws_pad_kernel, dim3(cdiv(nk, 256)), blk, 0, s, pad, rep, nk, S);
+      pad = rep;
+    }
+    const int rc = launch_chunk_loss(actions, targets, pad, ga_own, part, loss, hl->metrics, (long)B * d.da, d.da / hl->chunk, hl->kind, hl->beta, loss_scale, s,
                                      weighted ? hl->dim_w : nullptr, weighted ? hl->step_w : nullptr, hl->chunk);
     if (rc != FV_OK) return rc;
     ga = ga_own;
@@ -954,13 +1006,18 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(cdiv(cw, 256), d.fus), blk, 0, s, g1, sv.cat, cw, G + ho.o[4], B, d.fus, cw);
   hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(d.fus, 256)), blk, 0, s, g1, G + ho.o[5], B, d.fus);
   hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3(cdiv(cw, 32), b8), blk, 0, s, g1, P + ho.o[4], g2, cw, B, d.fus, cw);
+  if (S > 1) {   // sum the conditioning columns of dcat over the draws into rows 0 .. obs - 1; from here on B counts observations again
+    hipLaunchKernelGGL(draws_fold_kernel, dim3(cdiv((long)obs * (d.feat + d.hid), 256)), blk, 0, s, g2, cw, obs, S, d.feat + d.hid);
+    B = obs;
+  }
+  const unsigned o8 = cdiv(B, 8);
   // dcat = [d pooled | d state branch]: the first `feat` columns are what an unfrozen backbone's backward starts from
   if (d_pooled) hipLaunchKernelGGL(copy_cols_kernel, dim3(cdiv((long)B * d.feat, 256)), blk, 0, s, g2, cw, d_pooled, d.feat, B, d.feat);
   // state branch: ds = dcat[:, feat:], SiLU, Linear, LayerNorm
   hipLaunchKernelGGL(silu_bwd_kernel, dim3(cdiv((long)B * d.hid, 256)), blk, 0, s, g2 + d.feat, cw, sv.z1, (const float*)nullptr, g1, B, d.hid);
   hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(cdiv(d.ds, 256), d.hid), blk, 0, s, g1, sv.n0, d.ds, G + ho.o[2], B, d.hid, d.ds);
   hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(d.hid, 256)), blk, 0, s, g1, G + ho.o[3], B, d.hid);
-  hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3(cdiv(d.ds, 32), b8), blk, 0, s, g1, P + ho.o[2], g2, d.ds, B, d.hid, d.ds);
+  hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3(cdiv(d.ds, 32), o8), blk, 0, s, g1, P + ho.o[2], g2, d.ds, B, d.hid, d.ds);
   hipLaunchKernelGGL(ln_bwd_cols_kernel, dim3(cdiv(d.ds, 256)), blk, 0, s, g2, sv.xh0, G + ho.o[0], G + ho.o[1], B, d.ds);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
@@ -971,8 +1028,10 @@ int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targe
   if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_prepare: the head is not in flow mode (fv_head_set_flow)");
   if (!targets || !saved || !u_out) return fv_fail(FV_ERR_ARG, "flow_prepare: null pointer");
   if (B <= 0) return fv_fail(FV_ERR_ARG, "flow_prepare: B must be positive");
+  const int S = head_rows(d, B) / B;
+  if (S > 1 && (offset >> 56 & 15)) return fv_fail(FV_ERR_ARG, "flow_prepare: bits 56 .. 59 of the offset number the draws and must be 0 with more than one draw");
   const Saved sv = carve(d, B, saved);
-  hipLaunchKernelGGL(flow_prepare_kernel, dim3(B), dim3(256), 0, s, targets, noise, t, sv.cat, head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
+  hipLaunchKernelGGL(flow_prepare_kernel, dim3(B, S), dim3(256), 0, s, targets, noise, t, sv.cat, head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
                      f.time_dist, f.dist_a, f.dist_b, seed, offset);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;

@@ -291,8 +291,11 @@ int launch_attention_split_bwd(const float* qkv, int ld, const bf16_t* o_hi, con
 
 // action expert (all fp32)
 // flow mode (fv_head_set_flow): fusion.0 reads te + da more columns, cat = [ pooled | state branch | x_t (da) | phi(t) (te) ]; te == 0: the regression head
-struct HeadDims { int feat, ds, da, hid, fus; int te = 0; };
+// draws (fv_head_set_flow_draws, flow mode only): S noise draws per observation in the training forms.  Head rows are draw-major, r = s B + b: the state branch
+// keeps B rows, everything from cat on has S B.  1: the head as ever
+struct HeadDims { int feat, ds, da, hid, fus; int te = 0; int draws = 1; };
 inline int head_cat_width(const HeadDims& d) { return d.feat + d.hid + (d.te > 0 ? d.da + d.te : 0); }
+inline int head_rows(const HeadDims& d, int B) { return d.te > 0 && d.draws > 1 ? d.draws * B : B; }
 struct HeadOffsets { int64_t o[13]; };
 HeadOffsets head_offsets(const HeadDims& d);
 size_t head_saved_bytes(const HeadDims& d, int B);
@@ -316,7 +319,9 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
 // ---- flow-matching head (d.te > 0).  freq: te / 2 device floats, 2 pi / period_j.  time_dist 0: t ~ U[0, 1); 1: t = sigmoid(dist_a + dist_b n)
 struct HeadFlow { const float* freq; int time_dist; float dist_a, dist_b; };
-// one launch: draws (or reads) t per row and noise per element, writes x_t and phi(t) into their columns of saved's cat and u = noise - targets into u_out
+// one launch: draws (or reads) t per row and noise per element, writes x_t and phi(t) into their columns of saved's cat and u = noise - targets into u_out.
+// d.draws = S > 1: targets (B, da) stay per observation; head row s B + b draws what row b draws at offset + (s << 56); noise, t and u_out have S B rows.
+// FV_ERR_ARG, nothing enqueued, when S > 1 and any of bits 56 .. 59 of the offset is set
 int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
                         float* saved, float* u_out, hipStream_t s);
 // the Euler sampler: conditioning once, then three launches per step.  scratch: flow_sample_scratch_bytes(d, B)
@@ -341,7 +346,8 @@ int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float*
                       float beta, float loss_scale, hipStream_t s, const float* dim_w = nullptr, const float* step_w = nullptr, int K = 1);
 // mean |a - t| per action dimension over the non-padded steps: a, t (rows, A) f32 with rows = B K, pad (rows) bytes or null -> out (A), 0 for a dimension
 // without a valid step.  One block per dimension, fixed-order sums
-int launch_loss_per_dim(const float* a, const float* t, const uint8_t* pad, float* out, long rows, int A, hipStream_t s);
+// pad_rows (0: rows): the mask has fewer rows than a, t and row r reads pad[r % pad_rows] -- the draws of a flow head share their observation's mask
+int launch_loss_per_dim(const float* a, const float* t, const uint8_t* pad, float* out, long rows, int A, hipStream_t s, long pad_rows = 0);
 // temporal ensembling of action chunks (fv_ensemble_step): chunks (n_env, K, A) -> actions (n_env, A); ens (n_env, K, A) and count (n_env, K) are the ring,
 // head its position, w / cw the K weights exp(-coeff i) and their running sums
 int launch_ensemble_step(const float* chunks, float* ens, int32_t* count, float* actions, const float* w, const float* cw, int n_env, int K, int A, int head,

@@ -309,6 +309,24 @@ int fv_op_head_loss_backward(int feat, int ds, int da, int hid, int fus, int tim
                                   1.0f, &hl);
 }
 
+// fv_op_head_loss_backward with `draws` noise draws per observation (fv_head_set_flow_draws): actions, targets have draws * B rows, pad (B, chunk) and d_pooled
+// (B, feat) stay per observation -- d_pooled comes out summed over the draws.  dim_w (da / chunk) and step_w (chunk): device weights, both or neither
+int fv_op_head_loss_backward_draws(int feat, int ds, int da, int hid, int fus, int time_dim, int draws, const float* P, const float* actions, const float* targets,
+                                   const uint8_t* pad, const float* dim_w, const float* step_w, int kind, float beta, int chunk, int B, const void* saved, float* loss,
+                                   float* metrics, float* G, float* scratch, size_t scratch_floats, float* d_pooled, fv_stream s) {
+  if (feat < 1 || ds < 1 || da < 1 || hid < 1 || fus < 1 || time_dim < 2 || draws < 1 || draws > 16 || B < 1) return fv_fail(FV_ERR_ARG, "fv_op_head_loss_backward_draws: bad dimensions");
+  if (!metrics || !d_pooled) return fv_fail(FV_ERR_ARG, "fv_op_head_loss_backward_draws: null pointer");
+  fv::HeadDims d{feat, ds, da, hid, fus};
+  d.te = time_dim;
+  d.draws = draws;
+  if (scratch_floats * sizeof(float) < fv::head_bwd_scratch_bytes(d, B))
+    return fv_fail(FV_ERR_ARG, "fv_op_head_loss_backward_draws: scratch needs %zu floats", fv::head_bwd_scratch_bytes(d, B) / sizeof(float));
+  if (!dim_w != !step_w) return fv_fail(FV_ERR_ARG, "fv_op_head_loss_backward_draws: give both weight vectors or neither");
+  const fv::HeadLoss hl{kind, beta, chunk, pad, metrics, dim_w, step_w};
+  return fv::launch_head_backward(d, P, nullptr, actions, targets, B, 0.f, static_cast<const float*>(saved), loss, G, scratch, static_cast<hipStream_t>(s), d_pooled,
+                                  1.0f, &hl);
+}
+
 int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad, const float* dim_w, const float* step_w, float* g, float* partial,
                               size_t partial_floats, float* loss, float* metrics, int64_t n, int A, int K, int kind, float beta, float loss_scale, fv_stream s) {
   if (partial_floats < fv::chunk_loss_partial_floats()) return fv_fail(FV_ERR_ARG, "fv_op_chunk_loss_weighted: partial needs %zu floats", fv::chunk_loss_partial_floats());

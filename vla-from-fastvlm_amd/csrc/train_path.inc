@@ -119,7 +119,7 @@ struct TrainPlan {
   size_t x_in, x_mid, xn1, qkvf, att, lse, xn2, gu, act;    // per-layer stashes: offset of layer 0, strides below
   size_t s_x, s_xn, s_qkvf, s_att, s_lse, s_gu, s_act, apart;
   size_t pre0, hsplit, tok;                                   // projector stash
-  size_t act_s, dx, dtmp, dsplit, AT, XT, dqkv, attn_scr, delta, scr, pooled, dpooled, xg, dxg, head_saved, head_scr, flow_u, splitk;
+  size_t act_s, dx, dtmp, dsplit, AT, XT, dqkv, attn_scr, delta, scr, pooled, dpooled, xg, dxg, head_saved, head_scr, flow_u, flow_act, splitk;
   size_t splitk_bytes, total;
   size_t wmax;   // the widest gradient operand (columns): the dsplit scratch holds rows x 3 wmax 16-bit values
 };
@@ -157,7 +157,9 @@ TrainPlan plan_train(const fv_handle* h, int B, int T) {
   p.pooled = take((size_t)B * H * 4); p.dpooled = take((size_t)B * H * 4); p.xg = take((size_t)B * H * 4); p.dxg = take((size_t)B * H * 4);
   p.head_saved = take(fv::head_saved_bytes(h->hd, B));
   p.head_scr = take(fv::head_bwd_scratch_bytes(h->hd, B));
-  p.flow_u = take(h->hd.te > 0 ? (size_t)B * h->hd.da * 4 : 0);   // flow mode: the velocity target u = eps - a of the step (nothing otherwise: the plan keeps its offsets)
+  p.flow_u = take(h->hd.te > 0 ? (size_t)fv::head_rows(h->hd, B) * h->hd.da * 4 : 0);   // flow mode: the velocity target u = eps - a of the step (nothing otherwise: the plan keeps its offsets)
+  // draws (fv_head_set_flow_draws): the predicted velocity of all S B head rows; the caller's (B, da) `actions` gets draw 0's rows (nothing otherwise)
+  p.flow_act = take(fv::head_rows(h->hd, B) > B ? (size_t)fv::head_rows(h->hd, B) * h->hd.da * 4 : 0);
   // split-K partial sums: up to 4 K ranges of the widest fp32 output cut that way (rows x pad(max(H, qkvw)) forward / dgrad, a weight
   // gradient [<= 2I][<= pad(I)] backward); launch_gemm takes as many ranges as fit
   p.splitk_bytes = (size_t)4 * std::max(rows * ((std::max(H, qkvw) + 255) / 256 * 256), std::max(H, qkvw) * ((I + 255) / 256 * 256)) * 4;
@@ -599,6 +601,8 @@ static int train_forward_backward_impl(fv_handle* h, const float* flat_params, c
     return fv_fail(FV_ERR_ARG, "%s: null pointer", who);
   const fv_model_desc& d = h->d;
   if (B <= 0 || B > d.max_batch || T <= 0 || T % 8 || T > d.max_text_tokens) return fv_fail(FV_ERR_ARG, "%s: bad B / T (T must be a multiple of 8)", who);
+  if (fv::head_rows(h->hd, B) > B && (offset >> 56 & 15))   // (launch_flow_prepare's check, before the backbone's forward is enqueued)
+    return fv_fail(FV_ERR_ARG, "%s: bits 56 .. 59 of the offset number the flow head's draws and must be 0 with more than one draw", who);
   // refused HERE, before anything is enqueued or any bucket's all-reduce is launched (launch_embed_bwd runs at the very end of the backward).  The direct LoRA
   // backward computes no embedding gradient, but fv_train_workspace_bytes sizes the workspace for both entry points and admits no larger step: same limit, its own words
   if ((long)B * T > 16384)
@@ -655,19 +659,24 @@ static int train_forward_backward_impl(fv_handle* h, const float* flat_params, c
   const fv::HeadIoNorm* io = h->has_io ? &h->io : nullptr;
   // flow mode: the one place where the backbone routes noise their targets -- x_t and phi(t) go into head_saved's cat columns from the step's (seed, offset), as
   // fv_head_flow_prepare does for the head-only route, and the loss below compares the predicted velocity with u
+  // draws (fv_head_set_flow_draws): the S draws are prepared HERE, once, for every route; the head runs on S B rows into the plan's own predictions (the
+  // caller's `actions` gets draw 0's rows), the loss is the S-draw loss, and launch_head_backward hands back d_pooled summed over the draws -- B rows, which
+  // the backbone's backward below continues from as it is
   const float* head_targets = targets;
+  float* head_actions = fv::head_rows(h->hd, B) > B ? c.at<float>(tp.flow_act) : actions;
   if (h->hd.te > 0) {
     float* u = c.at<float>(tp.flow_u);
     FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_flow_prepare(h->hd, h->flow, targets, B, seed, offset, nullptr, nullptr, head_saved, u, s));
     head_targets = u;
   }
   // training != 0: the loss lives in normalised action space (fv_head_forward's convention)
-  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_forward(h->hd, flat_params, pooled, states, B, training ? (dropout_p > 0.f ? 1 : 2) : 2, dropout_p, seed, offset, actions,
+  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_forward(h->hd, flat_params, pooled, states, B, training ? (dropout_p > 0.f ? 1 : 2) : 2, dropout_p, seed, offset, head_actions,
                                                      head_saved, s, io));
+  if (head_actions != actions) FV_HIP_CHECK(hipMemcpyAsync(actions, head_actions, (size_t)B * h->hd.da * 4, hipMemcpyDeviceToDevice, s));
 
   // ------------------------------------------------------------------------------------------------ backward
   float *dpooled = c.at<float>(tp.dpooled), *xg = c.at<float>(tp.xg), *dxg = c.at<float>(tp.dxg);
-  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, actions, head_targets, B, dropout_p, head_saved, loss, gbuf, c.at<float>(tp.head_scr), s, dpooled,
+  FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, head_actions, head_targets, B, dropout_p, head_saved, loss, gbuf, c.at<float>(tp.head_scr), s, dpooled,
                                                       std::ldexp(1.0f, h->train.loss_scale_log2), &h->loss));
   c.bucket_done(TB_HEAD);
   // final norm on the pooled rows; the residual-gradient stream starts as zero everywhere else

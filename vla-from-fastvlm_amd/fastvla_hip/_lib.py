@@ -133,6 +133,7 @@ SIGNATURES = {
     "fv_head_set_loss_weights": (_i, [_vp, _vp, _vp]),
     "fv_head_loss_per_dim": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "fv_head_set_flow": (_i, [_vp, C.POINTER(HeadFlowSpec)]),
+    "fv_head_set_flow_draws": (_i, [_vp, _i]),
     "fv_head_flow_prepare": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "fv_head_flow_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _vp]),
     "fv_head_set_flow_guidance": (_i, [_vp, _i, C.POINTER(_f), _f]),
@@ -222,6 +223,7 @@ OPS_SIGNATURES = {
     "fv_op_chunk_loss": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _f, _f, _vp]),
     "fv_op_chunk_loss_weighted": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _i, _f, _f, _vp]),
     "fv_op_head_loss_backward": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "fv_op_head_loss_backward_draws": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "fv_op_flow_vjp": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }

@@ -97,6 +97,29 @@ def check_loss_weights(dim_w, step_w, A: int, K: int) -> Optional[dict]:
     return None if w["dim"] is None and w["step"] is None else w
 
 
+FLOW_DRAWS_MAX = 16          # include/fastvla_hip.h FV_FLOW_DRAWS_MAX
+FLOW_DRAW_SHIFT = 56         # draw s of a step at offset o draws at o + (s << 56): bits 56 .. 59 of a flow offset number the draws
+
+
+def check_flow_draws(draws) -> int:
+    """-> the number of noise draws per observation, validated: an integer 1 .. 16 (ValueError otherwise)"""
+    if isinstance(draws, bool) or not isinstance(draws, int) and not (isinstance(draws, float) and draws == int(draws)):
+        raise ValueError(f"flow_noise_draws must be an integer 1 .. {FLOW_DRAWS_MAX}, got {draws!r}")
+    if not 1 <= int(draws) <= FLOW_DRAWS_MAX:
+        raise ValueError(f"flow_noise_draws must be an integer 1 .. {FLOW_DRAWS_MAX}, got {draws!r}")
+    return int(draws)
+
+
+def flow_draw_offset(offset: int, s: int) -> int:
+    """the Philox offset draw s of a step at `offset` draws at: a single-draw call at this offset gives draw s's rows.  ValueError when the step's offset
+    already uses the draw bits or s is outside 0 .. 15."""
+    if not 0 <= int(s) < FLOW_DRAWS_MAX:
+        raise ValueError(f"draw index must be 0 .. {FLOW_DRAWS_MAX - 1}, got {s}")
+    if (int(offset) >> FLOW_DRAW_SHIFT) & (FLOW_DRAWS_MAX - 1):
+        raise ValueError(f"offset {int(offset):#x} has bits {FLOW_DRAW_SHIFT} .. {FLOW_DRAW_SHIFT + 3} set: they number the draws")
+    return int(offset) + (int(s) << FLOW_DRAW_SHIFT)
+
+
 class FastVLAEngine:
     def __init__(self, model: ModelConfig, *, state_dim: int = 14, action_dim: int = 14, hidden_dim: int = 1024,
                  fusion_dim: int = 1024, device: Optional[torch.device] = None, max_batch: int = 64,
@@ -150,6 +173,7 @@ class FastVLAEngine:
         self._pad_keep: Optional[torch.Tensor] = None
         self.head_flow: Optional[dict] = None                     # set_head_flow: None = the regression head
         self.head_flow_guidance: Optional[dict] = None            # set_head_flow_guidance: None = the unguided sampler only
+        self.head_flow_draws = 1                                  # set_head_flow_draws: noise draws per observation in the training forms
         self.loaded = False
 
     def close(self):
@@ -552,6 +576,7 @@ class FastVLAEngine:
         if time_dim is None:
             _lib.check(self.lib.fv_head_set_flow(self.h, None), "fv_head_set_flow", self.h)
             self.head_flow = None
+            self.head_flow_draws = 1
         else:
             if time_dist not in _lib.FLOW_TIME_DISTS:
                 raise ValueError(f"flow time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {time_dist!r}")
@@ -564,23 +589,34 @@ class FastVLAEngine:
         _lib.check(self.lib.fv_head_layout(self.h, C.byref(offs)), "fv_head_layout")
         self.head_offsets = list(offs)
 
+    def set_head_flow_draws(self, draws: int = 1) -> None:
+        """S = draws noise draws per observation in one training step (fv_head_set_flow_draws; 1 .. 16, 1 = off): the mean loss and gradient of S single-draw
+        steps at offsets o + (s << 56) for one backbone pass.  Head rows are draw-major (row s B + b): head_flow_prepare returns u (S B, da), head_forward in
+        a training form the predicted velocity (S B, da); targets, pad, pooled and states keep B rows.  Flow mode only, before the first workspace is bound
+        and before any train_*begin (the library answers FV_ERR_STATE otherwise)."""
+        draws = check_flow_draws(draws)
+        _lib.check(self.lib.fv_head_set_flow_draws(self.h, draws), "fv_head_set_flow_draws", self.h)
+        self.head_flow_draws = draws
+
     def head_flow_prepare(self, targets: torch.Tensor, saved: torch.Tensor, *, seed: int = 0, offset: int = 0, noise: Optional[torch.Tensor] = None,
                           t: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> u = eps - targets (B, da); x_t and phi(t) land in `saved` (head_saved(B)), which the following head_forward(saved=saved) reads
-        (fv_head_flow_prepare).  noise (B, da) / t (B) replace the draws of (seed, offset)."""
+        (fv_head_flow_prepare).  noise (B, da) / t (B) replace the draws of (seed, offset).  With set_head_flow_draws(S): targets stay (B, da); noise, t and
+        the returned u have S B rows, draw-major."""
         B, da = targets.shape[0], self.head_dims["da"]
+        R = B * self.head_flow_draws
         targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
         if targets.numel() != B * da:
             raise ValueError(f"targets must hold (B, {da}) elements, got {tuple(targets.shape)}")
         if noise is not None:
             noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
-            if noise.numel() != B * da:
-                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
+            if noise.numel() != R * da:
+                raise ValueError(f"noise must hold (draws * B, {da}) = ({R}, {da}) elements, got {tuple(noise.shape)}")
         if t is not None:
             t = t.to(device=self.device, dtype=torch.float32).contiguous()
-            if t.numel() != B:
-                raise ValueError(f"t must hold B = {B} elements, got {tuple(t.shape)}")
-        u = torch.empty(B, da, dtype=torch.float32, device=self.device)
+            if t.numel() != R:
+                raise ValueError(f"t must hold draws * B = {R} elements, got {tuple(t.shape)}")
+        u = torch.empty(R, da, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.fv_head_flow_prepare(self.h, targets.data_ptr(), B, seed, offset, _ptr(noise), _ptr(t), saved.data_ptr(), u.data_ptr(), _stream()),
                    "fv_head_flow_prepare", self.h)
         return u
@@ -667,9 +703,10 @@ class FastVLAEngine:
         if states.shape != (B, self.head_dims["ds"]):
             raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
         saved = saved if saved is not None else self.head_saved(B)
-        actions = torch.empty(B, self.head_dims["da"], dtype=torch.float32, device=self.device)
         # 1 = dropout active, 2 = training-mode arithmetic without dropout (folded action statistics are NOT applied), 0 = inference
         mode = 0 if not (training or normalized_actions) else (1 if training and dropout_p > 0.0 else 2)
+        # (set_head_flow_draws: the training forms predict every draw's velocity, draws * B rows; inference ignores the setting)
+        actions = torch.empty(B * (self.head_flow_draws if mode else 1), self.head_dims["da"], dtype=torch.float32, device=self.device)
         _lib.check(self.lib.fv_head_forward(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B,
                                             mode, float(dropout_p), seed, offset, actions.data_ptr(),
                                             saved.data_ptr(), _stream()), "fv_head_forward")
@@ -726,17 +763,26 @@ class FastVLAEngine:
 
     def head_loss_per_dim(self, actions: torch.Tensor, targets: torch.Tensor, pad=None) -> torch.Tensor:
         """-> (A,) f32: mean |actions - targets| over the non-padded steps of each action dimension (fv_head_loss_per_dim), in the space the loss lives in;
-        0 for a dimension without a valid step.  actions, targets: (B, K, A) or (B, K * A); pad: optional (B, chunk) bool.  Never weighted."""
-        B, K = actions.shape[0], self.head_loss["chunk"]
+        0 for a dimension without a valid step.  actions, targets: (B, K, A) or (B, K * A); pad: optional (B, chunk) bool.  Never weighted.
+        (set_head_flow_draws(S): actions and targets have S B rows, pad keeps B.)"""
+        S, K = self.head_flow_draws, self.head_loss["chunk"]
+        B = self._draw_rows(actions.shape[0])
         actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
-        if actions.numel() != B * self.head_dims["da"] or targets.numel() != actions.numel():
+        if actions.numel() != S * B * self.head_dims["da"] or targets.numel() != actions.numel():
             raise ValueError(f"actions and targets must hold (B, {self.head_dims['da']}) elements, got {tuple(actions.shape)} and {tuple(targets.shape)}")
         pad = self._pad_arg(pad, B)
         out = torch.empty(self.head_dims["da"] // K, dtype=torch.float32, device=self.device)
         with self._Mask(self, pad):
             _lib.check(self.lib.fv_head_loss_per_dim(self.h, actions.data_ptr(), targets.data_ptr(), B, out.data_ptr(), _stream()), "fv_head_loss_per_dim", self.h)
         return out
+
+    def _draw_rows(self, rows: int) -> int:
+        """head rows -> observations: rows / draws (set_head_flow_draws; the head's rows are draw-major)"""
+        S = self.head_flow_draws
+        if rows % S:
+            raise ValueError(f"{rows} head rows are not a multiple of the {S} noise draws per observation (set_head_flow_draws)")
+        return rows // S
 
     def _pad_arg(self, pad, B: int) -> Optional[torch.Tensor]:
         if pad is None:
@@ -774,8 +820,9 @@ class FastVLAEngine:
 
     def head_backward(self, flat_params: torch.Tensor, actions: torch.Tensor, targets: torch.Tensor, saved: torch.Tensor,
                       dropout_p: float = 0.0, flat_grads: Optional[torch.Tensor] = None, pad=None):
-        """pad: optional (B, chunk) bool, True = the step lies past the episode end and must not train."""
-        B = actions.shape[0]
+        """pad: optional (B, chunk) bool, True = the step lies past the episode end and must not train.  (set_head_flow_draws(S): actions and targets have
+        S B rows, pad keeps B rows and applies to every draw of its observation.)"""
+        B = self._draw_rows(actions.shape[0])
         self.ensure_workspace(B, 1, False)
         targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
         if targets.numel() != actions.numel():
@@ -793,7 +840,7 @@ class FastVLAEngine:
     def head_backward_from_grad(self, flat_params: torch.Tensor, grad_actions: torch.Tensor, saved: torch.Tensor,
                                 dropout_p: float = 0.0, flat_grads: Optional[torch.Tensor] = None) -> torch.Tensor:
         """generic backward: dL/dactions (B,A) -> all 12 head grads in one flat buffer (overwritten)."""
-        B = grad_actions.shape[0]
+        B = self._draw_rows(grad_actions.shape[0])
         self.ensure_workspace(B, 1, False)
         grad_actions = grad_actions.to(device=self.device, dtype=torch.float32).contiguous()
         if flat_grads is None:

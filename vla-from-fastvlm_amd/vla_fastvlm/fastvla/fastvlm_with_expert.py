@@ -89,6 +89,7 @@ class _FlowLossFunction(torch.autograd.Function):
         loss, grads = eng.head_backward(flat, v, u, saved, dropout_p=p, pad=pad)
         owner.last_loss_metrics = eng.head_loss_metrics() if eng.loss_is_chunked(pad) else None
         ctx.owner, ctx.grads = owner, grads
+        v = v[:pooled.shape[0]]      # flow_noise_draws > 1: u and v hold every draw's rows (draw-major); the loss is the S-draw loss, the velocity handed out draw 0's
         ctx.mark_non_differentiable(v)
         return loss[0], v
 
@@ -102,14 +103,18 @@ class _FlowLossFunction(torch.autograd.Function):
 
 class FastVLMWithExpert(nn.Module):
     def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0, flow: Optional[dict] = None,
-                 flow_steps: int = 10, flow_seed: Optional[int] = None) -> None:
+                 flow_steps: int = 10, flow_seed: Optional[int] = None, flow_noise_draws: int = 1) -> None:
         """chunk_size = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
         `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library.
         flow = FastVLAEngine.set_head_flow's keyword arguments: the flow-matching head -- fusion.0 reads K * A + time_dim more columns (x_t and phi(t)),
         head() samples with flow_steps Euler steps, head_loss() noises its targets and returns the predicted velocity.  flow_seed: the noise streams' seed
-        (default: torch's initial seed, as the dropout stream's)."""
+        (default: torch's initial seed, as the dropout stream's).  flow_noise_draws = S (1 .. 16): S noise draws (t, eps) per observation wherever targets are
+        noised -- draw s of a call at offset o is the single draw of offset o + (s << 56); the velocity handed out is draw 0's."""
         super().__init__()
-        from fastvla_hip.engine import check_head_loss
+        from fastvla_hip.engine import check_flow_draws, check_head_loss
+        self.flow_noise_draws = check_flow_draws(flow_noise_draws)
+        if self.flow_noise_draws > 1 and flow is None:
+            raise ValueError(f"flow_noise_draws={self.flow_noise_draws} needs action_head='flow' (the regression head has no noise to draw)")
         self.config = config
         self.action_loss, self.action_loss_beta, self.chunk_size = check_head_loss(action_loss, action_loss_beta, chunk_size)
         self.head_width = self.chunk_size * config.action_dim
@@ -121,6 +126,7 @@ class FastVLMWithExpert(nn.Module):
         self.flow: Optional[dict] = None if flow is None else dict(flow)
         self.flow_steps = int(flow_steps)
         self.backbone.configure_head_flow(self.flow)
+        self.backbone.configure_head_flow_draws(self.flow_noise_draws)
         self.rtc: Optional[dict] = None      # configure_rtc: real-time chunking of the flow sampler, a property of the run
         self._chunker = self._rtc_key = None
         extra = self.head_width + int(self.flow["time_dim"]) if self.flow else 0
@@ -142,7 +148,16 @@ class FastVLMWithExpert(nn.Module):
         continues the stream, and replicas that share one seed still draw different t and eps for their local row b (the noise batch is B * world, not B)"""
         import torch.distributed as dist
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-        return self._flow_seed, (int(rank) << 44) + (int(step) << 16) + (int(micro) & 0xFFFF)
+        return self._flow_seed, self.flow_train_offset(rank, step, micro)
+
+    @staticmethod
+    def flow_train_offset(rank: int, step: int, micro: int) -> int:
+        """the offset layout of a train step: micro-batch bits 0 .. 15, optimiser step 16 .. 43, rank 44 .. 55.  Bits 56 .. 59 number the noise draws
+        (flow_noise_draws: draw s draws at offset + (s << 56)) and bits 60 .. 62 mark the compute_loss / eval / sampling ranges, so a rank >= 4096 would
+        run into them: ValueError"""
+        if not 0 <= int(rank) < 4096:
+            raise ValueError(f"flow_train_draw: rank {rank} outside 0 .. 4095 (the rank takes bits 44 .. 55 of the noise offset; 56 .. 59 number the draws)")
+        return (int(rank) << 44) + (int(step) << 16) + (int(micro) & 0xFFFF)
 
     def flow_loss_draw(self):
         """compute_loss / forward(batch) in train() mode, outside the native train step: a running counter"""

@@ -98,6 +98,31 @@ def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, 
     return {"action_head": head, "steps": int(steps), "flow": flow}
 
 
+def resolve_flow_noise_draws(flow_noise_draws=None, *, action_head: str) -> int:
+    """-> S, the noise draws per observation of a flow head's training and loss evaluations: the explicit argument, else FASTVLA_FLOW_NOISE_DRAWS, else 1.  The
+    twin is read and checked for a flow head only, like the other FASTVLA_FLOW_* twins.  ValueError, naming both settings and before any engine exists, for
+    an explicit S > 1 with the regression head, a non-integer, or a value outside 1 .. 16."""
+    from fastvla_hip.engine import check_flow_draws
+    if flow_noise_draws is not None:      # an explicit argument is checked whatever the head is
+        try:
+            draws = check_flow_draws(flow_noise_draws)
+        except ValueError:
+            raise ValueError(f"flow_noise_draws must be an integer 1 .. 16. Got flow_noise_draws={flow_noise_draws!r}, action_head={action_head!r}.") from None
+        if draws > 1 and action_head != "flow":
+            raise ValueError("flow_noise_draws > 1 needs action_head='flow' (the regression head draws no noise). "
+                             f"Got flow_noise_draws={draws}, action_head={action_head!r}.")
+        return draws
+    if action_head != "flow":
+        return 1
+    raw = (os.environ.get("FASTVLA_FLOW_NOISE_DRAWS") or "").strip()
+    if not raw:
+        return 1
+    try:
+        return check_flow_draws(int(raw))
+    except ValueError:
+        raise ValueError(f"FASTVLA_FLOW_NOISE_DRAWS must be an integer 1 .. 16. Got FASTVLA_FLOW_NOISE_DRAWS={raw!r}, action_head={action_head!r}.") from None
+
+
 def resolve_rtc_options(rtc=None, rtc_schedule=None, rtc_max_guidance_weight=None, rtc_execution_horizon=None, *, action_head: str, chunk_size: int,
                         n_action_steps: int, temporal_ensemble_coeff=None) -> Optional[Dict]:
     """-> {"schedule", "max_guidance_weight", "execution_horizon"} or None (off): explicit arguments, else the FASTVLA_RTC / FASTVLA_RTC_SCHEDULE /
@@ -147,7 +172,8 @@ class FastVLAPolicy(nn.Module, EmaMixin):
                  action_loss: Optional[str] = None, action_loss_beta: Optional[float] = None, temporal_ensemble_coeff: Optional[float] = None,
                  action_dim_weights=None, action_step_weights=None, action_head: Optional[str] = None, flow_steps: Optional[int] = None,
                  flow_time_dim: Optional[int] = None, flow_time_dist: Optional[str] = None, flow_seed: Optional[int] = None, rtc: Optional[bool] = None,
-                 rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None) -> None:
+                 rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None,
+                 flow_noise_draws: Optional[int] = None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
@@ -169,6 +195,12 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         streams' seed (default: torch's initial seed).  Twins: FASTVLA_FLOW_STEPS, FASTVLA_FLOW_TIME_DIM, FASTVLA_FLOW_TIME_DIST.  A policy that does not
         ask for flow calls nothing new.
 
+        flow_noise_draws=S (flow head, 1 .. 16, default 1; FASTVLA_FLOW_NOISE_DRAWS): S noise draws (t, eps) per observation wherever targets are noised --
+        the train step on every route, compute_loss / forward(batch) in train() and in eval() mode (a smoother evaluation loss).  One step then computes the
+        mean loss and the mean gradient of S single-draw steps (draw s draws what a single-draw step draws at offset + (s << 56)) for ONE backbone forward
+        and backward: the head runs on S B rows, the backbone on B.  The returned velocity stays (B, K, A): draw 0.  A property of the run, like rtc: no
+        checkpoint records it -- pass it again on resume, and the run continues bit for bit.  ValueError for S > 1 with a regression head.
+
         rtc=True (flow head, chunk_size > 1; FASTVLA_RTC): real-time chunking -- a re-plan is sampled GUIDED by the not-yet-executed rest of the previous chunk
         (fastvla_hip/rtc.py; fv_head_flow_sample_guided), so consecutive chunks stay in one mode of the distribution instead of jumping at the seam.
         select_action keeps its queue; when it runs dry the new chunk is guided by the last one read `shift` = the number of actions served since steps
@@ -186,10 +218,11 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         self._action_queue: deque = deque()
         fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist)
         self.action_head = fopts["action_head"]
+        self.flow_noise_draws: int = resolve_flow_noise_draws(flow_noise_draws, action_head=self.action_head)      # (before any engine exists)
         ropts = resolve_rtc_options(rtc, rtc_schedule, rtc_max_guidance_weight, rtc_execution_horizon, action_head=self.action_head,      # (before any engine exists)
                                     chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
         self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"],
-                                       flow_steps=fopts["steps"], flow_seed=flow_seed)
+                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts
@@ -574,6 +607,7 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         if k > 1 and not first:
             eng.grad_accumulate(st["acc"], grads)
         total = st["g"] if k == 1 else st["acc"]
+        actions = actions[:prep["pooled"].shape[0]]      # (flow_noise_draws > 1: every draw's rows, draw-major; the step hands out draw 0's velocity)
         out = {"loss": loss[0], "mse": eng.head_loss_metrics()[0] if eng.loss_is_chunked(pad) else loss[0].detach(), "actions": m._shape_actions(actions),
                "synced": sync, "next": None}
         scale = 1.0

@@ -41,16 +41,18 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_options, resolve_rtc_options
+        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_rtc_options
         opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
                                      temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
                                      action_step_weights=kwargs.get("action_step_weights"))
         self.temporal_ensemble_coeff = opts["temporal_ensemble_coeff"]
         # the flow-matching head (FastVLAPolicy(config, action_head="flow", flow_steps=, flow_time_dim=, flow_time_dist=, flow_seed=) or the FASTVLA_ACTION_HEAD /
         # FASTVLA_FLOW_* twins; the registered config gains no field): the core policy's docstring has the semantics -- predict_action_chunk / select_action
-        # sample, forward(batch) trains the velocity
+        # sample, forward(batch) trains the velocity.  flow_noise_draws=S (FASTVLA_FLOW_NOISE_DRAWS; no config field): S noise draws per observation in one
+        # forward(batch), the mean loss and gradient of S single-draw calls for one backbone pass
         fopts = resolve_flow_options(kwargs.get("action_head"), kwargs.get("flow_steps"), kwargs.get("flow_time_dim"), kwargs.get("flow_time_dist"))
         self.action_head = fopts["action_head"]
+        self.flow_noise_draws: int = resolve_flow_noise_draws(kwargs.get("flow_noise_draws"), action_head=self.action_head)
         # real-time chunking (FastVLAPolicy(config, rtc=True, rtc_schedule=, rtc_max_guidance_weight=, rtc_execution_horizon=) or the FASTVLA_RTC* twins; no
         # config field): re-plans of a flow head are sampled guided by the rest of the previous chunk, for all B environments of the batch in one call
         ropts = resolve_rtc_options(kwargs.get("rtc"), kwargs.get("rtc_schedule"), kwargs.get("rtc_max_guidance_weight"), kwargs.get("rtc_execution_horizon"),
@@ -59,7 +61,7 @@ class FastVLAPolicy(PreTrainedPolicy):
         self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
         self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
                                        action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"], flow_steps=fopts["steps"],
-                                       flow_seed=kwargs.get("flow_seed"))
+                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts

@@ -187,6 +187,7 @@ class FastVLMBackbone(nn.Module):
         self._head_loss = dict(kind="mse", beta=1.0, chunk=1)   # configure_head_loss: the fused loss of the head backward and the chunk length K
         self._head_loss_weights: Optional[dict] = None          # configure_head_loss_weights: {"dim", "step"} of the weighted chunk loss, None = off
         self._head_flow: Optional[dict] = None                  # configure_head_flow: FastVLAEngine.set_head_flow's arguments, None = the regression head
+        self._head_flow_draws = 1                               # configure_head_flow_draws: FastVLAEngine.set_head_flow_draws' argument, 1 = one draw per observation
         self._head_flow_guidance: Optional[dict] = None         # configure_head_flow_guidance: FastVLAEngine.set_head_flow_guidance's arguments, None = off
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
@@ -265,6 +266,17 @@ class FastVLMBackbone(nn.Module):
         if self._engine is not None and flow != self._head_flow:
             raise RuntimeError("configure_head_flow: the engine is already built (the head's layout and the workspace depend on the mode)")
         self._head_flow = None if flow is None else dict(flow)
+
+    def configure_head_flow_draws(self, draws: int = 1) -> None:
+        """Noise draws per observation of a flow head's training forms (FastVLAEngine.set_head_flow_draws; 1 = off).  The saved activations and the
+        workspaces depend on it, so it is fixed before the engine exists."""
+        from fastvla_hip.engine import check_flow_draws
+        draws = check_flow_draws(draws)
+        if draws > 1 and self._head_flow is None:
+            raise ValueError(f"flow_noise_draws={draws} needs action_head='flow' (the regression head has no noise to draw)")
+        if self._engine is not None and draws != self._head_flow_draws:
+            raise RuntimeError("configure_head_flow_draws: the engine is already built (the saved activations and the workspaces depend on the number of draws)")
+        self._head_flow_draws = draws
 
     def configure_head_flow_guidance(self, guidance: Optional[dict]) -> None:
         """Guidance of the flow sampler (FastVLAEngine.set_head_flow_guidance's keyword arguments; None = off).  Kept for the engine's construction, where it
@@ -365,6 +377,8 @@ class FastVLMBackbone(nn.Module):
                 eng = build(1)
             if self._head_flow is not None:      # (first: before any workspace is bound)
                 eng.set_head_flow(**self._head_flow)
+                if getattr(self, "_head_flow_draws", 1) > 1:
+                    eng.set_head_flow_draws(self._head_flow_draws)
                 if getattr(self, "_head_flow_guidance", None) is not None:
                     eng.set_head_flow_guidance(**self._head_flow_guidance)
             if self._head_loss != dict(kind="mse", beta=1.0, chunk=1):
