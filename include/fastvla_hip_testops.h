@@ -199,7 +199,7 @@ int fv_op_lora_direct(int kind, int part_mask, int rank, int Np, int K, int qd, 
                       int xkind, int ldx, int lo_off, int R, const float* lora, float* lora_grads, float scale, float* scratch, size_t scratch_floats, fv_stream s);
 
 
-/* the chunked action loss alone (csrc/head_kernels.hip chunk_loss_kernel + its fold; fv_head_set_loss in fastvla_hip.h has the definitions): a, t (n) f32 =
+/* the chunked action loss alone (csrc/chunk_kernels.hip chunk_loss_kernel + its fold; fv_head_set_loss in fastvla_hip.h has the definitions): a, t (n) f32 =
  * (B, K, A) row-major with A the step width, pad (n / A) bytes or NULL -> g (n) = loss_scale * w * rho'(a - t) / n, loss (1), metrics (2) = { masked MSE, valid
  * fraction }.  partial: scratch of partial_floats >= 768 floats.  kind FV_LOSS_*. */
 int fv_op_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, size_t partial_floats, float* loss, float* metrics,
@@ -226,7 +226,7 @@ int fv_op_head_loss_backward_draws(int feat, int ds, int da, int hid, int fus, i
                                    const uint8_t* pad, const float* dim_w, const float* step_w, int kind, float beta, int chunk, int B, const void* saved, float* loss,
                                    float* metrics, float* G, float* scratch, size_t scratch_floats, float* d_pooled, fv_stream s);
 
-/* one guided sampler step's chain alone (csrc/head_kernels.hip launch_flow_vjp; fv_head_flow_sample_guided in fastvla_hip.h has the definitions): the
+/* one guided sampler step's chain alone (csrc/flow_kernels.hip launch_flow_vjp; fv_head_flow_sample_guided in fastvla_hip.h has the definitions): the
  * conditioning, the velocity v(x, t) through the step's forward kernels and J^T omega, J = dv / dx, through its three transposed products and the LayerNorm
  * backward.  Explicit head dimensions (time_dim = E > 0), freq: E / 2 DEVICE floats 2 pi / p_j; P: the flat parameters of that layout; x, omega (B, da);
  * v_out, jt_out (B, da).  scratch: scratch_floats floats; FV_ERR_ARG names the count when it is too small. */

@@ -648,7 +648,7 @@ def test_c3_rank_shape_train_step_with_dropout(fullp):
     eng.adamw_step(fp, grads, mm, vv, 1, lr=1e-4, weight_decay=1e-4, max_grad_norm=1.0, grad_norm_out=norm)
     torch.cuda.synchronize()
     hid = fus = 1024
-    sizes = [B * 14, B * 14, B, B * hid, B * (lc.hidden + hid), B * fus, B * fus, B, B * fus, B * fus]   # layout of `saved` (csrc/head_kernels.hip)
+    sizes = [B * 14, B * 14, B, B * hid, B * (lc.hidden + hid), B * fus, B * fus, B, B * fus, B * fus]   # layout of `saved` (csrc/head_kernels.hip carve)
     off = sum((s + 3) // 4 * 4 for s in sizes)
     mult = saved[off: off + B * fus].view(B, fus).cpu()
     keep = (mult > 0).float()

@@ -290,8 +290,23 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- Philox4x32-10 (counter-based, Random123 constants; (seed, offset) explicit so a step is reproducible): the head's dropout (head_kernels.hip), the flow
+// head's noise and times (flow_kernels.hip) and the augmentation's draws (augment_kernels.hip), each under a key or counter layout of its own ----
+__device__ __forceinline__ uint4 philox(uint4 c, uint2 k) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
+    k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
+  }
+  return c;
+}
+
+constexpr float LN_EPS = 1e-5f;   // the action expert's LayerNorms (torch's default), forward and the samplers' recomputed statistics
+
 // ONE element of the fused clip + AdamW step (torch.optim.AdamW: decoupled decay, bias corrections bc1 = 1 - beta1^t, bc2_sqrt = sqrt(1 - beta2^t)).
-// adamw_kernel (head_kernels.hip) and adamw_groups_kernel (optim_kernels.hip) both evaluate THIS expression, so a grouped step whose groups all carry
+// adamw_kernel and adamw_groups_kernel (both optim_kernels.hip) evaluate THIS expression, so a grouped step whose groups all carry
 // lr_scale 1 and the same decay gives adamw_kernel's bits.  Which products fuse into an fma is WRITTEN OUT and contraction is off inside: left to the compiler
 // it depends on the code around the expression (a scalar kernel and a float4 loop fuse differently), and the two kernels would differ in the last bit.  The
 // form is the one adamw_kernel has always compiled to: 1 - lr wd and m's update fused, v's update two rounded products and a sum.

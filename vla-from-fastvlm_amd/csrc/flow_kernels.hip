@@ -1,0 +1,519 @@
+// flow_kernels.hip -- the flow-matching form of the action expert (fv_head_set_flow), all fp32, every sum in a fixed order:
+//   flow_prepare_kernel                    training: x_t and phi(t) into their columns of the head's cat, u = eps - a as the loss target; the head itself
+//                                          (head_kernels.hip) then runs forward and backward as it does for regression
+//   flow_cond / _init / _step_a / _b / _c  the Euler sampler (fv_head_flow_sample): conditioning once, three launches per step
+//   flow_guide_* / flow_vjp_t_kernel       guided sampling (fv_head_set_flow_guidance; real-time chunking): the step's forward with z3 and v kept, J^T omega
+//                                          through three transposed products and a LayerNorm backward, and the update
+// The state branch of both samplers is head_kernels.hip's (launch_head_state_branch); the draws come from common.h philox under this file's key.
+#include "kernels.h"
+
+#include <algorithm>
+
+namespace fv {
+namespace {
+
+// ---- flow-matching head (fv_head_set_flow): x_t = t eps + (1 - t) a, u = eps - a; sampling runs x <- x + dt v from t = 1 to t = 0 ----
+// The draws are Philox4x32-10 under a key of their own (the dropout stream of the same (seed, offset) is another stream); the counter is
+// (group, row, offset): group 0 is the row's t, group 1 + i / 4 the normals of elements 4 (i / 4) .. + 3 -- a function of (row, element) only, so row b draws
+// the same values whatever B and the launch geometry are.
+constexpr uint32_t FLOW_KEY_LO = 0x464C4F57u, FLOW_KEY_HI = 0x4D415443u;
+constexpr float FLOW_TWO_PI = 6.28318530717958647692f, FLOW_U24 = 1.0f / 16777216.0f;
+__device__ __forceinline__ uint4 flow_philox(uint32_t group, uint32_t row, uint64_t seed, uint64_t offset) {
+  return philox(make_uint4(group, row, (uint32_t)offset, (uint32_t)(offset >> 32)), make_uint2((uint32_t)seed ^ FLOW_KEY_LO, (uint32_t)(seed >> 32) ^ FLOW_KEY_HI));
+}
+// Box-Muller on two 24-bit uniforms, u1 in (0, 1] and u2 in [0, 1): (r cos, r sin) with r = sqrt(-2 log u1).  sinf / cosf / logf, not the fast intrinsics
+__device__ __forceinline__ float2 flow_box_muller(uint32_t a, uint32_t b) {
+  const float u1 = (float)((a >> 8) + 1u) * FLOW_U24, u2 = (float)(b >> 8) * FLOW_U24;
+  const float r = sqrtf(-2.0f * logf(u1)), th = FLOW_TWO_PI * u2;
+  return make_float2(r * cosf(th), r * sinf(th));
+}
+__device__ __forceinline__ void flow_normals4(uint32_t group, uint32_t row, uint64_t seed, uint64_t offset, float (&n)[4]) {
+  const uint4 r = flow_philox(group, row, seed, offset);
+  const float2 p = flow_box_muller(r.x, r.y), q = flow_box_muller(r.z, r.w);
+  n[0] = p.x; n[1] = p.y; n[2] = q.x; n[3] = q.y;
+}
+// phi(t) = [ sin(freq_j t) | cos(freq_j t) ], j < te / 2; the argument is ONE fp32 product (it reaches ~1600 rad: sinf / cosf reduce it properly)
+__device__ __forceinline__ void flow_phi(float* __restrict__ dst, const float* __restrict__ freq, int half, float t, int i) {
+  const float arg = freq[i] * t;
+  dst[i] = sinf(arg);
+  dst[half + i] = cosf(arg);
+}
+
+// block = one head row, grid (B, S): head row r = s B + b is draw s of observation b (fv_head_set_flow_draws; S == 1: the rows as ever).  It reads targets[b]
+// and draws what row b draws at offset + (s << 56) -- the key, the counter (group, b, offset) and the Box-Muller as they are, so row b's draws depend
+// neither on B nor on S, and draw 0 is the single draw.  Explicit noise (S B, da) / tin (S B) are read at r.
+// cat: the row-major (S B, cw) matrix inside `saved`; columns [xo, xo + da) <- x_t, [xo + da, xo + da + te) <- phi(t); u_out (S B, da) <- eps - a.
+// x_t is formed in double and rounded once: t eps and (1 - t) a cancel for some rows, and the fp32 form then loses bits the loss target does not
+__global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restrict__ targets, const float* __restrict__ noise, const float* __restrict__ tin,
+                                                            float* __restrict__ cat, int cw, int xo, float* __restrict__ u_out, int da, int te,
+                                                            const float* __restrict__ freq, int time_dist, float dist_a, float dist_b, uint64_t seed,
+                                                            uint64_t offset) {
+  const int obs = blockIdx.x, row = blockIdx.y * gridDim.x + obs;
+  offset += (uint64_t)blockIdx.y << 56;
+  float t;
+  if (tin) {
+    t = tin[row];
+  } else {
+    const uint4 r = flow_philox(0u, (uint32_t)obs, seed, offset);
+    if (time_dist == 0) t = (float)(r.x >> 8) * FLOW_U24;
+    else t = 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x)));
+  }
+  float* xr = cat + (size_t)row * cw + xo;
+  const double td = (double)t, omt = 1.0 - td;
+  for (int g = threadIdx.x; g * 4 < da; g += 256) {
+    float n[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)obs, seed, offset, n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = g * 4 + j;
+      if (i >= da) break;
+      const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)obs * da + i];
+      xr[i] = (float)(td * (double)e + omt * (double)a);
+      u_out[(size_t)row * da + i] = e - a;
+    }
+  }
+  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t, i);
+}
+
+// the sampler's start: xphi (B, da + te) <- [ noise or the draws of (seed, offset) | phi(t0) ]
+__global__ __launch_bounds__(256) void flow_init_kernel(const float* __restrict__ noise, float* __restrict__ xphi, int da, int te, const float* __restrict__ freq,
+                                                         float t0, uint64_t seed, uint64_t offset) {
+  const int row = blockIdx.x;
+  float* xr = xphi + (size_t)row * (da + te);
+  for (int g = threadIdx.x; g * 4 < da; g += 256) {
+    float n[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)row, seed, offset, n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = g * 4 + j;
+      if (i >= da) break;
+      xr[i] = noise ? noise[(size_t)row * da + i] : n[j];
+    }
+  }
+  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t0, i);
+}
+
+// The sampler's products keep linear_fwd_kernel's layout: one wave per output column n, 8 batch rows per pass, coalesced weight reads, a wave_sum per row
+// (a fixed order: two runs give the same bits).  wr: row n of the weight, or a column range of it.
+__device__ __forceinline__ void flow_dot8(const float* __restrict__ x, int ldx, const float* __restrict__ wr, int K, int b0, int B, int lane, float (&acc)[8]) {
+  for (int k = lane; k < K; k += 64) {
+    const float wv = wr[k];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += x[(size_t)min(b0 + j, B - 1) * ldx + k] * wv;
+  }
+}
+// once per call: c[b][n] = b4[n] + W4[n][0 : feat] . pooled[b] + W4[n][feat : feat + hid] . s[b]  (the part of fusion.0 that does not depend on t)
+__global__ __launch_bounds__(256) void flow_cond_kernel(const float* __restrict__ pooled, int feat, const float* __restrict__ sb, int hid, const float* __restrict__ W,
+                                                         int ldw, const float* __restrict__ bias, float* __restrict__ c, int B, int N) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(pooled, feat, W + (size_t)n * ldw, feat, b0, B, lane, acc);
+  flow_dot8(sb, hid, W + (size_t)n * ldw + feat, hid, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) c[(size_t)(b0 + j) * N + n] = acc[j] + bias[n];
+}
+// step kernel A: z2[b][n] = c[b][n] + W4[n][xo : xo + xw] . [x | phi(t_i)][b]
+__global__ __launch_bounds__(256) void flow_step_a_kernel(const float* __restrict__ xphi, int xw, const float* __restrict__ W, int ldw, int xo,
+                                                           const float* __restrict__ c, float* __restrict__ z2, int B, int N) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(xphi, xw, W + (size_t)n * ldw + xo, xw, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) z2[(size_t)(b0 + j) * N + n] = c[(size_t)(b0 + j) * N + n] + acc[j];
+}
+// step kernel B: a3[b][n] = silu(b8[n] + W8[n] . silu(LN(z2[b]))).  Every block recomputes the statistics of its 8 rows (wave w: rows 2w, 2w + 1; ln_fwd_kernel's
+// two passes and order) and applies LayerNorm and SiLU while it loads: no normalised copy travels through memory and no block waits for another
+// STASH (the guided step): the pre-activation z3 = b8 + W8 . silu(LN(z2)) is kept as well, for silu' in the backward chain; nothing else differs
+template <bool STASH>
+__global__ __launch_bounds__(256) void flow_step_b_kernel(const float* __restrict__ z2, const float* __restrict__ lw, const float* __restrict__ lb,
+                                                           const float* __restrict__ W, const float* __restrict__ bias, float* __restrict__ a3,
+                                                           float* __restrict__ z3, int B, int N) {
+  __shared__ float st[2][8];   // mean, rstd
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, n = blockIdx.x * 4 + wv, b0 = blockIdx.y * 8;
+  for (int r = 2 * wv; r < 2 * wv + 2; ++r) {
+    const float* zr = z2 + (size_t)min(b0 + r, B - 1) * N;
+    float s = 0.f;
+    for (int i = lane; i < N; i += 64) s += zr[i];
+    const float mean = wave_sum(s) / (float)N;
+    float q = 0.f;
+    for (int i = lane; i < N; i += 64) { const float d = zr[i] - mean; q += d * d; }
+    const float rs = rsqrtf(wave_sum(q) / (float)N + LN_EPS);
+    if (lane == 0) { st[0][r] = mean; st[1][r] = rs; }
+  }
+  __syncthreads();
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const float* wr = W + (size_t)n * N;
+  for (int k = lane; k < N; k += 64) {
+    const float wk = wr[k], g = lw[k], be = lb[k];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float h = (z2[(size_t)min(b0 + j, B - 1) * N + k] - st[0][j]) * st[1][j];
+      acc[j] += silu_f(h * g + be) * wk;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) {
+      const float z = acc[j] + bias[n];
+      if constexpr (STASH) z3[(size_t)(b0 + j) * N + n] = z;
+      a3[(size_t)(b0 + j) * N + n] = silu_f(z);
+    }
+}
+// step kernel C: v = ba[n] + Wa[n] . a3[b]; x <- x + dt v in the epilogue (the lane that owns (b, n) reads and writes x[b][n], nobody else touches it).
+// Not the last step: the blocks of column group 0 also write phi(t_next) for their 8 rows.  The last step writes `actions`, with the folded action statistics
+__global__ __launch_bounds__(256) void flow_step_c_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
+                                                           float* __restrict__ xphi, int xw, int te, float dt, float t_next, const float* __restrict__ freq,
+                                                           float* __restrict__ actions, const float* __restrict__ post_scale, const float* __restrict__ post_shift,
+                                                           int B, int N) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (!actions && blockIdx.x == 0) {
+    const int half = te / 2;
+    for (int idx = threadIdx.x; idx < 8 * half; idx += 256) {
+      const int j = idx / half, i = idx - j * half;
+      if (b0 + j < B) flow_phi(xphi + (size_t)(b0 + j) * xw + N, freq, half, t_next, i);
+    }
+  }
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) {
+      const size_t b = (size_t)(b0 + j);
+      const float xn = xphi[b * xw + n] + dt * (acc[j] + bias[n]);
+      if (!actions) xphi[b * xw + n] = xn;
+      else actions[b * N + n] = post_scale ? xn * post_scale[n] + post_shift[n] : xn;
+    }
+}
+
+// ---- guided sampling (fv_head_set_flow_guidance; real-time chunking).  Per step, with a^ = x - t v the denoised estimate, Y the shifted previous chunk and
+// w >= 0 the per-step weights:   omega = w (Y - a^)    g = omega - t J^T omega  (J = dv / dx)    v' = v - k g    x <- x + dt v'
+// The forward keeps the unguided kernels (A as it is, B with z3 kept, C' below in step C's order); J^T omega runs backwards through action_head, SiLU,
+// fusion.4, SiLU, LayerNorm and the x columns of fusion.0.  Rows never meet: a row with omega == 0 gets g == 0 and v' == v exactly.
+constexpr int FLOW_VJP_ROWS_MAX = 128;   // the largest reduction range of one block of flow_vjp_t_kernel
+__device__ __forceinline__ float silu_grad_f(float z) {
+  const float sg = sigmoid_f(z);
+  return sg * (1.0f + z * (1.0f - sg));   // silu_bwd_kernel's expression
+}
+// step kernel C': v = ba[n] + Wa[n] . a3[b] in flow_step_c_kernel's order, kept in v_out; x stays.  step_w != null: omega as well.  Element (b, n) of step
+// k = n / A: target prev[b][n + shift A] when k + shift < chunk.  A weight of 0, a step beyond the shift and a row with row_mask[b] == 0 are SELECTED to
+// omega = 0: whatever prev holds there (NaN, +-inf) is never read into the arithmetic
+__global__ __launch_bounds__(256) void flow_guide_c_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
+                                                            const float* __restrict__ xphi, int xw, float t, const float* __restrict__ prev,
+                                                            const float* __restrict__ step_w, const int32_t* __restrict__ row_mask, int chunk, int A, int shift,
+                                                            float* __restrict__ v_out, float* __restrict__ omega, int B, int N) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0) {
+    const int k = n / A;
+    const float wk = step_w && k + shift < chunk ? step_w[k] : 0.f;
+    for (int j = 0; j < 8 && b0 + j < B; ++j) {
+      const size_t b = (size_t)(b0 + j);
+      const float v = acc[j] + bias[n];
+      v_out[b * N + n] = v;
+      if (step_w) {
+        float om = 0.f;
+        if (wk != 0.f && (!row_mask || row_mask[b] != 0)) om = wk * (prev[b * N + n + (size_t)shift * A] - (xphi[b * xw + n] - t * v));
+        omega[b * N + n] = om;
+      }
+    }
+  }
+}
+// A transposed product on the row-major weight as it is stored: part[z][b][m] = sum over the block's range of n of g[b][n] W[n][col0 + m].  Lanes run along m
+// (64 consecutive floats of a weight row per wave load), the block's `rps` reduction rows are dealt to its four waves (wave w: rows w, w + 4, ...), the four
+// sums are folded through LDS in wave order, and blockIdx.z ranges of rps rows each write a partial of their own, which the NEXT kernel folds in z order:
+// every sum has a fixed order, and at B = 1 the weight stream is spread over cdiv(M, 64) x cdiv(N, rps) blocks.
+// The block first stages g for its 8 batch rows x rps reduction rows (rows beyond B: 0):
+//   FOLD == 0: g = gin (B, ldg)           FOLD == 1: g = silu'(z[b][n]) * sum_q gin[q][b][n]  (gin: S_in partials of the previous product, (S_in, B, ldg))
+template <int FOLD>
+__global__ __launch_bounds__(256) void flow_vjp_t_kernel(const float* __restrict__ gin, int ldg, int S_in, const float* __restrict__ z,
+                                                          const float* __restrict__ W, int ldw, int col0, float* __restrict__ part, int B, int N, int M, int rps) {
+  __shared__ float gs[8][FLOW_VJP_ROWS_MAX];
+  __shared__ float red[3][8][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, m = blockIdx.x * 64 + lane, b0 = blockIdx.y * 8, n0 = blockIdx.z * rps;
+  const int nn = min(rps, N - n0);
+  for (int idx = threadIdx.x; idx < 8 * rps; idx += 256) {
+    const int j = idx / rps, r = idx - j * rps, b = b0 + j, n = n0 + r;
+    float val = 0.f;
+    if (r < nn && b < B) {
+      if constexpr (FOLD == 0) {
+        val = gin[(size_t)b * ldg + n];
+      } else {
+        float sum = 0.f;
+#pragma unroll 8
+        for (int q = 0; q < S_in; ++q) sum += gin[((size_t)q * B + b) * ldg + n];
+        val = sum * silu_grad_f(z[(size_t)b * ldg + n]);
+      }
+    }
+    gs[j][r] = val;
+  }
+  __syncthreads();
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (m < M) {
+    const float* wc = W + (size_t)n0 * ldw + col0 + m;
+    for (int r = wv; r < nn; r += 4) {
+      const float wk = wc[(size_t)r * ldw];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += gs[j][r] * wk;
+    }
+  }
+  if (wv > 0) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[wv - 1][j][lane] = acc[j];
+  }
+  __syncthreads();
+  if (wv == 0 && m < M)
+    for (int j = 0; j < 8 && b0 + j < B; ++j)
+      part[((size_t)blockIdx.z * B + (b0 + j)) * M + m] = ((acc[j] + red[0][j][lane]) + red[1][j][lane]) + red[2][j][lane];
+}
+// LayerNorm backward of one row per block: dn2 = silu'(n2) * sum_q part[q][b][n] (the fusion.4 product's partials, folded in q order), dh = dn2 * gain,
+// dz2 = rstd (dh - mean(dh) - h mean(dh h)).  The row's statistics are recomputed from z2 (ln_fwd_kernel's two passes); block sums go wave by wave
+__device__ __forceinline__ float flow_block_sum(float v, float (&red)[16]) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float s = red[0];
+  for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s += red[w];
+  return s;
+}
+// (256 or 1024 threads: at B = 1 this is ONE block, and what it waits for is the latency of the fold's loads -- a wide row gets a thread per element)
+__global__ __launch_bounds__(1024) void flow_guide_ln_kernel(const float* __restrict__ z2, const float* __restrict__ lw, const float* __restrict__ lb,
+                                                             const float* __restrict__ part, int S_in, float* __restrict__ dz2, int B, int N) {
+  __shared__ float red[16];
+  const int b = blockIdx.x, nt = blockDim.x;
+  const float* zr = z2 + (size_t)b * N;
+  float* dr = dz2 + (size_t)b * N;
+  float s = 0.f;
+  for (int i = threadIdx.x; i < N; i += nt) s += zr[i];
+  const float mean = flow_block_sum(s, red) / (float)N;
+  float q = 0.f;
+  for (int i = threadIdx.x; i < N; i += nt) { const float d = zr[i] - mean; q += d * d; }
+  const float rs = rsqrtf(flow_block_sum(q, red) / (float)N + LN_EPS);
+  float s1 = 0.f, s2 = 0.f;
+  for (int i = threadIdx.x; i < N; i += nt) {
+    const float h = (zr[i] - mean) * rs;
+    float sum = 0.f;
+#pragma unroll 8
+    for (int p = 0; p < S_in; ++p) sum += part[((size_t)p * B + b) * N + i];
+    const float dh = sum * silu_grad_f(h * lw[i] + lb[i]) * lw[i];
+    dr[i] = dh;   // (read back by the same thread below)
+    s1 += dh;
+    s2 += dh * h;
+  }
+  const float m1 = flow_block_sum(s1, red) / (float)N, m2 = flow_block_sum(s2, red) / (float)N;
+  for (int i = threadIdx.x; i < N; i += nt) {
+    const float h = (zr[i] - mean) * rs;
+    dr[i] = rs * (dr[i] - m1 - h * m2);
+  }
+}
+// x + dt v as ONE fused multiply-add, the contraction flow_step_c_kernel's `x + dt * v` compiles to: with v' == v the guided update repeats its bits.
+// (the same for the folded action statistics x scale + shift)
+__device__ __forceinline__ float flow_fma_pinned(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// The last kernel of a guided step, one thread per (b, n): J^T omega = sum_q part[q][b][n] (the fusion.0 product's partials), g = omega - t J^T omega,
+// v' = v - k g, x <- x + dt v'; phi(t_next), or on the last step `actions` (with the folded statistics) and chunk_out (without), as flow_step_c_kernel.
+// jt_out != null (the op-level entry): J^T omega alone
+__global__ __launch_bounds__(256) void flow_guide_update_kernel(const float* __restrict__ part, int S_in, const float* __restrict__ omega, const float* __restrict__ v,
+                                                                 float* __restrict__ xphi, int xw, int te, float t, float kw, float dt, float t_next,
+                                                                 const float* __restrict__ freq, float* __restrict__ actions, float* __restrict__ chunk_out,
+                                                                 const float* __restrict__ post_scale, const float* __restrict__ post_shift,
+                                                                 float* __restrict__ jt_out, int B, int N) {
+  const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
+  if (!jt_out && !actions && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xphi + (size_t)b * xw + N, freq, te / 2, t_next, i);
+  if (n >= N) return;
+  const size_t e = (size_t)b * N + n;
+  float jt = 0.f;
+#pragma unroll 8
+  for (int q = 0; q < S_in; ++q) jt += part[((size_t)q * B + b) * N + n];
+  if (jt_out) { jt_out[e] = jt; return; }
+  const float g = omega[e] - t * jt;
+  const float vp = v[e] - kw * g;
+  const float xn = flow_fma_pinned(dt, vp, xphi[(size_t)b * xw + n]);
+  if (!actions) { xphi[(size_t)b * xw + n] = xn; return; }
+  if (chunk_out) chunk_out[e] = xn;
+  actions[e] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
+}
+
+}  // namespace
+
+int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
+                        float* saved, float* u_out, hipStream_t s) {
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_prepare: the head is not in flow mode (fv_head_set_flow)");
+  if (!targets || !saved || !u_out) return fv_fail(FV_ERR_ARG, "flow_prepare: null pointer");
+  if (B <= 0) return fv_fail(FV_ERR_ARG, "flow_prepare: B must be positive");
+  const int S = head_rows(d, B) / B;
+  if (S > 1 && (offset >> 56 & 15)) return fv_fail(FV_ERR_ARG, "flow_prepare: bits 56 .. 59 of the offset number the draws and must be 0 with more than one draw");
+  hipLaunchKernelGGL(flow_prepare_kernel, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved), head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
+                     f.time_dist, f.dist_a, f.dist_b, seed, offset);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+namespace {
+struct FlowScratch { float *n0, *xh0, *rstd0, *z1, *sb, *c, *xphi, *z2, *a3; size_t total; };
+FlowScratch flow_carve(const HeadDims& d, int B, float* base) {
+  FlowScratch r;
+  size_t o = 0;
+  auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
+  r.n0 = take((size_t)B * d.ds); r.xh0 = take((size_t)B * d.ds); r.rstd0 = take(B); r.z1 = take((size_t)B * d.hid); r.sb = take((size_t)B * d.hid);
+  r.c = take((size_t)B * d.fus); r.xphi = take((size_t)B * (d.da + d.te)); r.z2 = take((size_t)B * d.fus); r.a3 = take((size_t)B * d.fus);
+  r.total = o;
+  return r;
+}
+// the conditioning of a sampler call (4 launches): state LayerNorm, state projection, the t-independent part of fusion.0, the start [x | phi(t0)]
+void flow_condition(const HeadDims& d, const HeadFlow& f, const HeadOffsets& ho, const FlowScratch& fs, const float* P, const float* pooled, const float* states,
+                    int B, const float* noise, float t0, uint64_t seed, uint64_t offset, hipStream_t s, const HeadIoNorm* io) {
+  const dim3 blk(256);
+  launch_head_state_branch(d, P, states, B, fs.n0, fs.xh0, fs.rstd0, fs.z1, fs.sb, d.hid, s, io);
+  hipLaunchKernelGGL(flow_cond_kernel, dim3(cdiv(d.fus, 4), cdiv(B, 8)), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[HP_FUS0_W], head_cat_width(d), P + ho.o[HP_FUS0_B], fs.c, B, d.fus);
+  hipLaunchKernelGGL(flow_init_kernel, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, t0, seed, offset);
+}
+}  // namespace
+
+size_t flow_sample_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? flow_carve(d, B, nullptr).total * sizeof(float) : 0; }
+
+// 4 launches of conditioning (state LayerNorm, state projection, the t-independent part of fusion.0, the start), then 3 per Euler step.  No dropout, no
+// atomics, no host synchronisation; t_i = 1 - i / N and dt = -1 / N are rounded once on the host and travel as kernel arguments
+int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io) {
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample: the head is not in flow mode (fv_head_set_flow)");
+  if (!P || !pooled || !states || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample: null pointer");
+  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample: B and n_steps must be positive");
+  const HeadOffsets ho = head_offsets(d);
+  const FlowScratch fs = flow_carve(d, B, scratch);
+  const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
+  const dim3 blk(256);
+  const unsigned b8 = cdiv(B, 8);
+  flow_condition(d, f, ho, fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io);
+  const float dt = (float)(-1.0 / (double)n_steps);
+  for (int i = 0; i < n_steps; ++i) {
+    const bool last = i + 1 == n_steps;
+    const float t_next = (float)(1.0 - (double)(i + 1) / (double)n_steps);
+    hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
+    hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], fs.a3,
+                       (float*)nullptr, B, d.fus);
+    hipLaunchKernelGGL(flow_step_c_kernel, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, dt, t_next, f.freq,
+                       last ? actions : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr, last && io ? io->action_mean : (const float*)nullptr,
+                       B, d.da);
+  }
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+namespace {
+// the guided sampler's rows: the unguided sampler's, then z3, v, omega, dz2 and two partial-sum buffers the transposed products alternate between
+struct GuideScratch { FlowScratch fs; float *z3, *v, *omega, *dz2, *pa, *pb; size_t total; };
+inline int guide_rps(int B) { return B <= 16 ? 64 : FLOW_VJP_ROWS_MAX; }   // reduction rows per block: more, smaller ranges while few batch groups fill the chip
+size_t guide_part_floats(const HeadDims& d, int B) {
+  auto per_row = [&](int rps) {
+    const size_t sa = cdiv(d.da, rps), sf = cdiv(d.fus, rps);
+    return std::max(std::max(sa, sf) * (size_t)d.fus, sf * (size_t)d.da);
+  };
+  // (never smaller for a larger B: a call with B rows fits the workspace sized for max_batch)
+  return B <= 16 ? (size_t)B * per_row(64) : std::max((size_t)16 * per_row(64), (size_t)B * per_row(FLOW_VJP_ROWS_MAX));
+}
+GuideScratch guide_carve(const HeadDims& d, int B, float* base) {
+  GuideScratch r;
+  r.fs = flow_carve(d, B, base);
+  size_t o = r.fs.total;
+  auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
+  r.z3 = take((size_t)B * d.fus); r.v = take((size_t)B * d.da); r.omega = take((size_t)B * d.da); r.dz2 = take((size_t)B * d.fus);
+  r.pa = take(guide_part_floats(d, B)); r.pb = take(guide_part_floats(d, B));
+  r.total = o;
+  return r;
+}
+// forward of a guided step: A, B with z3 kept, C' (v, and omega when step_w is given)
+void guide_forward(const HeadDims& d, const HeadOffsets& ho, const GuideScratch& g, const float* P, int B, float t, const float* prev, const float* step_w,
+                   const int32_t* row_mask, int chunk, int shift, float* v_out, hipStream_t s) {
+  const dim3 blk(256);
+  const unsigned b8 = cdiv(B, 8);
+  const int xw = d.da + d.te;
+  hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, g.fs.xphi, xw, P + ho.o[HP_FUS0_W], head_cat_width(d), d.feat + d.hid, g.fs.c, g.fs.z2, B, d.fus);
+  hipLaunchKernelGGL(flow_step_b_kernel<true>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, g.fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], g.fs.a3, g.z3, B,
+                     d.fus);
+  hipLaunchKernelGGL(flow_guide_c_kernel, dim3(cdiv(d.da, 4), b8), blk, 0, s, g.fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], g.fs.xphi, xw, t, prev, step_w, row_mask,
+                     chunk, d.da / chunk, shift, v_out, g.omega, B, d.da);
+}
+// J^T omega as partial sums: action_head^T over the first n_live rows (the steps behind them have omega == 0), fusion.4^T, LayerNorm, fusion.0[:, x]^T.
+// -> the number of partials (B, da) left in g.pa, which flow_guide_update_kernel folds
+int guide_backward(const HeadDims& d, const HeadOffsets& ho, const GuideScratch& g, const float* P, const float* omega, int n_live, int B, hipStream_t s) {
+  const dim3 blk(256);
+  const unsigned b8 = cdiv(B, 8);
+  const int rps = guide_rps(B), sd = (int)cdiv(n_live, rps), sf = (int)cdiv(d.fus, rps);
+  hipLaunchKernelGGL(flow_vjp_t_kernel<0>, dim3(cdiv(d.fus, 64), b8, sd), blk, 0, s, omega, d.da, 0, (const float*)nullptr, P + ho.o[HP_ACT_W], d.fus, 0, g.pa, B, n_live,
+                     d.fus, rps);
+  hipLaunchKernelGGL(flow_vjp_t_kernel<1>, dim3(cdiv(d.fus, 64), b8, sf), blk, 0, s, g.pa, d.fus, sd, g.z3, P + ho.o[HP_FUS4_W], d.fus, 0, g.pb, B, d.fus, d.fus, rps);
+  hipLaunchKernelGGL(flow_guide_ln_kernel, dim3(B), dim3(d.fus >= 1024 ? 1024 : 256), 0, s, g.fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], g.pb, sf, g.dz2, B, d.fus);
+  hipLaunchKernelGGL(flow_vjp_t_kernel<0>, dim3(cdiv(d.da, 64), b8, sf), blk, 0, s, g.dz2, d.fus, 0, (const float*)nullptr, P + ho.o[HP_FUS0_W], head_cat_width(d),
+                     d.feat + d.hid, g.pa, B, d.fus, d.da, rps);
+  return sf;
+}
+}  // namespace
+
+size_t flow_guided_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? guide_carve(d, B, nullptr).total * sizeof(float) : 0; }
+
+// Conditioning as launch_flow_sample, then 8 launches per Euler step: A, B (z3 kept), C' (v and omega), three transposed products with a LayerNorm backward
+// between the last two, and the update.  t_i, k_i, dt, shift and the live-row count are host values that travel as kernel arguments
+int launch_flow_sample_guided(const HeadDims& d, const HeadFlow& f, const HeadGuide& gd, const float* P, const float* pooled, const float* states, int B, int n_steps,
+                              const float* noise, uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions,
+                              float* chunk_out, float* scratch, hipStream_t s, const HeadIoNorm* io) {
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample_guided: the head is not in flow mode (fv_head_set_flow)");
+  if (!gd.step_w || gd.chunk < 1 || d.da % gd.chunk) return fv_fail(FV_ERR_STATE, "flow_sample_guided: guidance is not configured (fv_head_set_flow_guidance)");
+  if (!P || !pooled || !states || !prev || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample_guided: null pointer");
+  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample_guided: B and n_steps must be positive");
+  if (shift < 0 || shift > gd.chunk) return fv_fail(FV_ERR_ARG, "flow_sample_guided: shift = %d outside 0 .. chunk = %d", shift, gd.chunk);
+  const HeadOffsets ho = head_offsets(d);
+  const GuideScratch g = guide_carve(d, B, scratch);
+  const int A = d.da / gd.chunk, xw = d.da + d.te;
+  // steps from here on have omega == 0 (weight 0, or beyond the shift): the first product stops there.  (At least one step: its omega is then all 0)
+  const int n_live = std::max(1, std::min(gd.live_steps, gd.chunk - shift)) * A;
+  flow_condition(d, f, ho, g.fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io);
+  const float dt = (float)(-1.0 / (double)n_steps);
+  for (int i = 0; i < n_steps; ++i) {
+    const bool last = i + 1 == n_steps;
+    const float t = (float)(1.0 - (double)i / (double)n_steps), t_next = (float)(1.0 - (double)(i + 1) / (double)n_steps);
+    const double td = (double)t;
+    // k_i = min(beta, ((1 - t)^2 + t^2) / ((1 - t) t)), beta at t = 1: in double from the fp32-rounded t, rounded once
+    const float kw = t >= 1.0f ? gd.beta : (float)std::min((double)gd.beta, ((1.0 - td) * (1.0 - td) + td * td) / ((1.0 - td) * td));
+    guide_forward(d, ho, g, P, B, t, prev, gd.step_w, row_mask, gd.chunk, shift, g.v, s);
+    const int sp = guide_backward(d, ho, g, P, g.omega, n_live, B, s);
+    hipLaunchKernelGGL(flow_guide_update_kernel, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, g.omega, g.v, g.fs.xphi, xw, d.te, t, kw, dt, t_next, f.freq,
+                       last ? actions : (float*)nullptr, last ? chunk_out : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr,
+                       last && io ? io->action_mean : (const float*)nullptr, (float*)nullptr, B, d.da);
+  }
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+// one guided step's chain for a given x, t and omega (tests): v (B, da) and J^T omega (B, da)
+int launch_flow_vjp(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, const float* x, float t,
+                    const float* omega, float* v_out, float* jt_out, float* scratch, hipStream_t s) {
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_vjp: the head is not in flow mode");
+  if (!P || !pooled || !states || !x || !omega || !v_out || !jt_out || !scratch) return fv_fail(FV_ERR_ARG, "flow_vjp: null pointer");
+  if (B <= 0) return fv_fail(FV_ERR_ARG, "flow_vjp: B must be positive");
+  const HeadOffsets ho = head_offsets(d);
+  const GuideScratch g = guide_carve(d, B, scratch);
+  flow_condition(d, f, ho, g.fs, P, pooled, states, B, x, t, 0, 0, s, nullptr);
+  guide_forward(d, ho, g, P, B, t, nullptr, nullptr, nullptr, 1, 0, v_out, s);
+  const int sp = guide_backward(d, ho, g, P, omega, d.da, B, s);
+  hipLaunchKernelGGL(flow_guide_update_kernel, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, omega, v_out, g.fs.xphi, d.da + d.te, d.te, t, 0.f, 0.f, 0.f,
+                     f.freq, (float*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr, jt_out, B, d.da);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+}  // namespace fv

@@ -1,0 +1,358 @@
+// head_path.inc -- the action expert's entry points (fv_head_*) and the temporal-ensembling ring's (fv_ensemble_*), included by engine.hip: argument checks,
+// the handle's configuration (dataset statistics, loss, flow mode, guidance, draws) and the call into the launchers of head_kernels.hip, chunk_kernels.hip
+// and flow_kernels.hip.
+namespace {
+
+// the head's parameter count, for the profiler's FLOP / byte estimates
+double head_param_count(const fv_handle* h) { return (double)fv::head_offsets(h->hd).o[fv::HP_TOTAL]; }
+
+// *scr <- the head's scratch inside the bound workspace for a call with B rows; `too_small`: the caller's message for a workspace bound for a smaller plan
+int head_scratch(fv_handle* h, int B, const char* too_small, float** scr) {
+  if (!h->ws) return fv_fail(FV_ERR_STATE, "workspace not bound: call fv_bind_workspace first");
+  if (B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "B=%d exceeds max_batch=%d", B, h->d.max_batch);
+  const WsPlan wp = plan_ws(h, B, 1, 0);
+  if (wp.total > h->ws_bytes) return fv_fail(FV_ERR_STATE, "%s", too_small);
+  *scr = reinterpret_cast<float*>(static_cast<char*>(h->ws) + wp.head_scr);
+  return FV_OK;
+}
+
+// n host floats -> the handle's device vector *buf, allocated first when `fresh` (every setter has its own rule for that; an old vector stays until fv_destroy).
+// A head kernel still in flight on any stream may be reading the previous values: a configuration call, so it simply waits
+int head_upload(fv_handle* h, float** buf, bool fresh, const float* host, size_t n) {
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  if (fresh) {
+    void* p = nullptr;
+    FV_TRY(dev_alloc(h, n * 4, &p));
+    *buf = static_cast<float*>(p);
+  }
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  FV_HIP_CHECK(hipMemcpy(*buf, host, n * 4, hipMemcpyHostToDevice));
+  return FV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fv_head_layout(fv_handle* h, int64_t offsets[13]) {
+  HandleScope _hs(h);
+  if (!h || !offsets) return fv_fail(FV_ERR_ARG, "fv_head_layout: null argument");
+  const fv::HeadOffsets ho = fv::head_offsets(h->hd);
+  for (int i = 0; i <= fv::HP_TOTAL; ++i) offsets[i] = ho.o[i];
+  return FV_OK;
+}
+
+int fv_head_saved_bytes(fv_handle* h, int B, size_t* out_bytes) {
+  HandleScope _hs(h);
+  if (!h || !out_bytes || B <= 0) return fv_fail(FV_ERR_ARG, "fv_head_saved_bytes: bad argument");
+  *out_bytes = fv::head_saved_bytes(h->hd, B);
+  return FV_OK;
+}
+
+int fv_head_forward(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B,
+                    int training, float dropout_p, uint64_t seed, uint64_t offset, float* actions, void* saved,
+                    fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  hipStream_t st = static_cast<hipStream_t>(s);
+  prof_begin(h, FV_FAM_HEAD, 2.0 * B * head_param_count(h), 4.0 * head_param_count(h), st);
+  const int rc = fv::launch_head_forward(h->hd, flat_params, pooled, states, B, training, dropout_p, seed, offset, actions,
+                                         static_cast<float*>(saved), st, h->has_io ? &h->io : nullptr);
+  prof_end(h, st);
+  return rc;
+}
+
+int fv_head_set_io_norm(fv_handle* h, const float* state_mean, const float* state_std, const float* action_mean,
+                        const float* action_std, float eps) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (!state_mean && !state_std && !action_mean && !action_std) { h->has_io = false; return FV_OK; }   // all NULL: folding off
+  if (!state_mean || !state_std || !action_mean || !action_std) return fv_fail(FV_ERR_ARG, "fv_head_set_io_norm: give all four vectors or none");
+  const int ds = h->hd.ds, da = h->hd.da;
+  std::vector<float> v((size_t)2 * ds + 2 * da);
+  for (int i = 0; i < ds; ++i) { v[i] = state_mean[i]; v[ds + i] = 1.0f / (state_std[i] + eps); }
+  for (int i = 0; i < da; ++i) { v[2 * ds + i] = action_mean[i]; v[2 * ds + da + i] = action_std[i]; }
+  FV_TRY(head_upload(h, &h->io_buf, !h->io_buf, v.data(), v.size()));   // allocated once: toggling the folding on / off / on does not grow the handle
+  float* f = h->io_buf;
+  h->io = fv::HeadIoNorm{f, f + ds, f + 2 * ds, f + 2 * ds + da};
+  h->has_io = true;
+  return FV_OK;
+}
+
+int fv_head_mse_backward(fv_handle* h, const float* flat_params, const float* actions, const float* targets, int B,
+                         float dropout_p, const void* saved, float* loss, float* flat_grads, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  float* scr = nullptr;
+  FV_TRY(head_scratch(h, B, "workspace too small for head backward", &scr));
+  hipStream_t st = static_cast<hipStream_t>(s);
+  prof_begin(h, FV_FAM_HEAD, 4.0 * B * head_param_count(h), 8.0 * head_param_count(h), st);
+  const int rc = fv::launch_head_backward(h->hd, flat_params, nullptr, actions, targets, B, dropout_p,
+                                          static_cast<const float*>(saved), loss, flat_grads, scr, st, nullptr, 1.0f, &h->loss);
+  prof_end(h, st);
+  return rc;
+}
+
+int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (spec) {
+    if (spec->time_dim < 2 || spec->time_dim % 2) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: time_dim = %d must be positive and even", spec->time_dim);
+    if (!std::isfinite(spec->min_period) || !std::isfinite(spec->max_period) || !(spec->min_period > 0.f) || !(spec->max_period > spec->min_period))
+      return fv_fail(FV_ERR_ARG, "fv_head_set_flow: periods must be finite with 0 < min_period < max_period (got %g, %g)", (double)spec->min_period, (double)spec->max_period);
+    if (spec->time_dist != 0 && spec->time_dist != 1) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: unknown time_dist %d (0 uniform, 1 logit-normal)", spec->time_dist);
+    if (!std::isfinite(spec->dist_a) || !std::isfinite(spec->dist_b)) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: dist_a / dist_b must be finite");
+  }
+  // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
+  if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
+  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
+  const int half = spec->time_dim / 2;
+  std::vector<float> fr(half);   // 2 pi / p_j, p_j geometric from min_period to max_period; in double, rounded once
+  for (int j = 0; j < half; ++j) {
+    const double frac = half > 1 ? (double)j / (half - 1) : 0.0;
+    fr[j] = (float)(2.0 * 3.14159265358979323846 / ((double)spec->min_period * std::pow((double)spec->max_period / (double)spec->min_period, frac)));
+  }
+  const bool grow = h->flow_freq_cap < half;   // kept across off / on: toggling the mode, or asking for the same or a smaller time_dim, does not grow the handle (a LARGER one allocates anew)
+  FV_TRY(head_upload(h, &h->flow_freq_buf, grow, fr.data(), (size_t)half));
+  if (grow) h->flow_freq_cap = half;
+  h->hd.te = spec->time_dim;
+  h->flow = fv::HeadFlow{h->flow_freq_buf, spec->time_dist, spec->dist_a, spec->dist_b};
+  return FV_OK;
+}
+
+int fv_head_set_flow_draws(fv_handle* h, int draws) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_draws: the head is not in flow mode (fv_head_set_flow)");
+  // the saved activations, the backward's scratch, the workspace plan and the training plan all depend on it
+  if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_draws: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on it)");
+  if (draws < 1 || draws > FV_FLOW_DRAWS_MAX) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_draws: draws = %d outside 1 .. %d", draws, FV_FLOW_DRAWS_MAX);
+  h->hd.draws = draws;
+  return FV_OK;
+}
+
+int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t, void* saved,
+                         float* u_out, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_prepare: the head is not in flow mode (fv_head_set_flow)");
+  return fv::launch_flow_prepare(h->hd, h->flow, targets, B, seed, offset, noise, t, static_cast<float*>(saved), u_out, static_cast<hipStream_t>(s));
+}
+
+int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                        uint64_t seed, uint64_t offset, float* actions, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample: the head is not in flow mode (fv_head_set_flow)");
+  if (!flat_params || !pooled || !states || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: null pointer");
+  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: n_steps = %d must be >= 1", n_steps);
+  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
+  float* scr = nullptr;
+  FV_TRY(head_scratch(h, B, "workspace too small for the flow sampler", &scr));
+  hipStream_t st = static_cast<hipStream_t>(s);
+  prof_begin(h, FV_FAM_HEAD, 2.0 * B * n_steps * head_param_count(h), 4.0 * n_steps * head_param_count(h), st);
+  const int rc = fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr);
+  prof_end(h, st);
+  return rc;
+}
+
+int fv_head_set_flow_guidance(fv_handle* h, int chunk, const float* step_weights_host, float max_guidance_weight) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_guidance: the head is not in flow mode (fv_head_set_flow)");
+  if (!step_weights_host) { h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
+  if (chunk < 1 || h->hd.da % chunk) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_guidance: chunk=%d must be >= 1 and divide action_dim=%d", chunk, h->hd.da);
+  int live = 0;
+  for (int k = 0; k < chunk; ++k) {
+    if (!std::isfinite(step_weights_host[k]) || step_weights_host[k] < 0.f)
+      return fv_fail(FV_ERR_ARG, "fv_head_set_flow_guidance: step weight %d = %g must be finite and >= 0", k, (double)step_weights_host[k]);
+    if (step_weights_host[k] != 0.f) live = k + 1;
+  }
+  if (!std::isfinite(max_guidance_weight) || !(max_guidance_weight > 0.f))
+    return fv_fail(FV_ERR_ARG, "fv_head_set_flow_guidance: max_guidance_weight = %g must be finite and > 0", (double)max_guidance_weight);
+  // the guided sampler's rows (the unguided sampler's and the backward chain's partial sums on top) are larger than the head part of the plan without
+  // them, and they join the plan with the first configuration: a workspace bound before that does not hold them
+  if (h->ws && h->guide_chunk == 0)
+    return fv_fail(FV_ERR_STATE, "fv_head_set_flow_guidance: the first call must come before fv_bind_workspace (the workspace grows by the guided sampler's rows)");
+  FV_TRY(head_upload(h, &h->guide_buf, h->guide_chunk != chunk, step_weights_host, (size_t)chunk));   // (another chunk length allocates anew)
+  h->guide_chunk = chunk;
+  h->guide = fv::HeadGuide{h->guide_buf, chunk, max_guidance_weight, live};
+  return FV_OK;
+}
+
+int fv_head_flow_sample_guided(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                               uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions, float* chunk_out,
+                               fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_guided: the head is not in flow mode (fv_head_set_flow)");
+  if (!h->guide.step_w) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_guided: guidance is not configured (fv_head_set_flow_guidance)");
+  if (!flat_params || !pooled || !states || !prev || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: null pointer");
+  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: n_steps = %d must be >= 1", n_steps);
+  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
+  if (shift < 0 || shift > h->guide.chunk) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: shift = %d outside 0 .. chunk = %d", shift, h->guide.chunk);
+  float* scr = nullptr;
+  FV_TRY(head_scratch(h, B, "workspace too small for the guided flow sampler", &scr));
+  hipStream_t st = static_cast<hipStream_t>(s);
+  prof_begin(h, FV_FAM_HEAD, 4.0 * B * n_steps * head_param_count(h), 8.0 * n_steps * head_param_count(h), st);
+  const int rc = fv::launch_flow_sample_guided(h->hd, h->flow, h->guide, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, row_mask, actions,
+                                               chunk_out, scr, st, h->has_io ? &h->io : nullptr);
+  prof_end(h, st);
+  return rc;
+}
+
+int fv_head_set_loss(fv_handle* h, const fv_head_loss_spec* spec) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  // another chunk length: the weight vectors' sizes no longer fit, so weighting is off until fv_head_set_loss_weights runs again
+  if (!spec) {
+    if (h->loss.chunk != 1) h->loss.dim_w = h->loss.step_w = nullptr;
+    h->loss.kind = FV_LOSS_MSE; h->loss.beta = 1.0f; h->loss.chunk = 1;
+    return FV_OK;
+  }
+  if (spec->kind != FV_LOSS_MSE && spec->kind != FV_LOSS_L1 && spec->kind != FV_LOSS_SMOOTH_L1) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: unknown loss kind %d", spec->kind);
+  if (spec->kind == FV_LOSS_SMOOTH_L1 && !(spec->beta > 0.f && std::isfinite(spec->beta))) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: smooth-L1 beta must be positive and finite");
+  if (spec->chunk < 1 || h->hd.da % spec->chunk) return fv_fail(FV_ERR_ARG, "fv_head_set_loss: chunk=%d must be >= 1 and divide action_dim=%d", spec->chunk, h->hd.da);
+  if (spec->chunk != h->loss.chunk) h->loss.dim_w = h->loss.step_w = nullptr;
+  h->loss.kind = spec->kind;
+  h->loss.beta = spec->kind == FV_LOSS_SMOOTH_L1 ? spec->beta : 1.0f;
+  h->loss.chunk = spec->chunk;
+  return FV_OK;
+}
+
+int fv_head_set_loss_mask(fv_handle* h, const uint8_t* pad_dev) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  h->loss.pad = pad_dev;
+  return FV_OK;
+}
+
+int fv_head_set_loss_weights(fv_handle* h, const float* dim_w, const float* step_w) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (!dim_w && !step_w) { h->loss.dim_w = h->loss.step_w = nullptr; return FV_OK; }   // both NULL: weighting off
+  const int da = h->hd.da, K = h->loss.chunk, A = da / K;
+  for (int i = 0; dim_w && i < A; ++i)
+    if (!(dim_w[i] >= 0.f) || !std::isfinite(dim_w[i])) return fv_fail(FV_ERR_ARG, "fv_head_set_loss_weights: dim_w[%d] = %g must be finite and >= 0", i, (double)dim_w[i]);
+  for (int k = 0; step_w && k < K; ++k)
+    if (!(step_w[k] >= 0.f) || !std::isfinite(step_w[k])) return fv_fail(FV_ERR_ARG, "fv_head_set_loss_weights: step_w[%d] = %g must be finite and >= 0", k, (double)step_w[k]);
+  std::vector<float> v((size_t)2 * da, 1.0f);   // a NULL vector: ones
+  for (int i = 0; dim_w && i < A; ++i) v[i] = dim_w[i];
+  for (int k = 0; step_w && k < K; ++k) v[da + k] = step_w[k];
+  FV_TRY(head_upload(h, &h->loss_w, !h->loss_w, v.data(), v.size()));   // allocated once, sized for every chunk length that divides action_dim
+  h->loss.dim_w = h->loss_w;
+  h->loss.step_w = h->loss_w + da;
+  return FV_OK;
+}
+
+int fv_head_loss_per_dim(fv_handle* h, const float* actions, const float* targets, int B, float* out_dev, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !actions || !targets || !out_dev) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_dim: null argument");
+  if (B < 1) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_dim: B must be positive");
+  // (draws: actions and targets have S B rows, the mask keeps B)
+  return fv::launch_loss_per_dim(actions, targets, h->loss.pad, out_dev, (long)fv::head_rows(h->hd, B) * h->loss.chunk, h->hd.da / h->loss.chunk, static_cast<hipStream_t>(s),
+                                 (long)B * h->loss.chunk);
+}
+
+int fv_head_loss_metrics(fv_handle* h, const float** dev) {
+  HandleScope _hs(h);
+  if (!h || !dev) return fv_fail(FV_ERR_ARG, "fv_head_loss_metrics: null argument");
+  *dev = h->loss.metrics;
+  return FV_OK;
+}
+
+int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,
+                     const void* saved, float* flat_grads, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !grad_actions) return fv_fail(FV_ERR_ARG, "fv_head_backward: null argument");
+  float* scr = nullptr;
+  FV_TRY(head_scratch(h, B, "workspace too small for head backward", &scr));
+  return fv::launch_head_backward(h->hd, flat_params, grad_actions, nullptr, nullptr, B, dropout_p,
+                                  static_cast<const float*>(saved), nullptr, flat_grads, scr, static_cast<hipStream_t>(s));
+}
+
+// ---- temporal ensembling of action chunks (csrc/chunk_kernels.hip ensemble_step_kernel)
+struct fv_ensembler {
+  int n_env = 0, K = 0, A = 0;
+  int head = 0;              // ring position: the slot of the time step served next (host state, a kernel argument)
+  void* dev = nullptr;       // ONE allocation: ens | count | w | cw
+  float* ens = nullptr;
+  int32_t* count = nullptr;
+  const float *w = nullptr, *cw = nullptr;
+};
+
+int fv_ensemble_create(fv_handle* h, int n_env, int chunk, int step_dim, float coeff, fv_ensembler** out) {
+  HandleScope _hs(h);
+  if (!h || !out) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: null argument");
+  *out = nullptr;
+  if (n_env < 1 || chunk < 1 || step_dim < 1) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: n_env = %d, chunk = %d, step_dim = %d must all be >= 1", n_env, chunk, step_dim);
+  if (!std::isfinite(coeff)) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: coeff must be finite");
+  const size_t slots = (size_t)n_env * chunk;
+  if (slots * step_dim > ((size_t)1 << 40)) return fv_fail(FV_ERR_ARG, "fv_ensemble_create: n_env * chunk * step_dim is more than 2^40");
+  // the tables in double, rounded once: w[i] = exp(-coeff i), cw[i] = w[0] + .. + w[i]
+  std::vector<float> tab;
+  try {
+    tab.resize((size_t)2 * chunk);
+  } catch (const std::exception&) {
+    return fv_fail(FV_ERR_STATE, "fv_ensemble_create: out of host memory");
+  }
+  double run = 0.0;
+  for (int i = 0; i < chunk; ++i) {
+    const double wi = std::exp(-(double)coeff * i);
+    run += wi;
+    tab[i] = (float)wi;
+    tab[chunk + i] = (float)run;
+    if (!std::isfinite(tab[chunk + i]) || !(tab[chunk + i] > 0.f))
+      return fv_fail(FV_ERR_ARG, "fv_ensemble_create: coeff = %g over %d steps leaves the fp32 range", (double)coeff, chunk);
+  }
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const size_t ens_bytes = align_up(slots * step_dim * sizeof(float)), cnt_bytes = align_up(slots * sizeof(int32_t)), tab_bytes = align_up(tab.size() * sizeof(float));
+  void* dev = nullptr;
+  FV_HIP_CHECK(hipMalloc(&dev, ens_bytes + cnt_bytes + tab_bytes));
+  char* base = static_cast<char*>(dev);
+  hipError_t e = hipMemset(base, 0, ens_bytes + cnt_bytes);
+  if (e == hipSuccess) e = hipMemcpy(base + ens_bytes + cnt_bytes, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(dev); return fv_hip_fail(e, "fv_ensemble_create: upload"); }
+  fv_ensembler* en = new (std::nothrow) fv_ensembler;
+  if (!en) { (void)hipFree(dev); return fv_fail(FV_ERR_STATE, "fv_ensemble_create: out of host memory"); }
+  en->n_env = n_env; en->K = chunk; en->A = step_dim; en->dev = dev;
+  en->ens = reinterpret_cast<float*>(base);
+  en->count = reinterpret_cast<int32_t*>(base + ens_bytes);
+  en->w = reinterpret_cast<const float*>(base + ens_bytes + cnt_bytes);
+  en->cw = en->w + chunk;
+  *out = en;
+  return FV_OK;
+}
+
+int fv_ensemble_destroy(fv_handle* h, fv_ensembler* e) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "fv_ensemble_destroy: null handle");
+  if (!e) return FV_OK;
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const hipError_t err = hipFree(e->dev);    // (waits for a step still in flight on the ring)
+  delete e;
+  if (err != hipSuccess) return fv_hip_fail(err, "fv_ensemble_destroy: hipFree");
+  return FV_OK;
+}
+
+int fv_ensemble_reset(fv_handle* h, fv_ensembler* e, int env, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !e) return fv_fail(FV_ERR_ARG, "fv_ensemble_reset: null argument");
+  if (env < -1 || env >= e->n_env) return fv_fail(FV_ERR_ARG, "fv_ensemble_reset: env = %d outside -1 .. %d", env, e->n_env - 1);
+  // the counts alone carry the history: a slot with count 0 takes the next chunk's row as it is.  Stream-ordered, no host synchronisation
+  int32_t* at = env < 0 ? e->count : e->count + (size_t)env * e->K;
+  const size_t n = (env < 0 ? (size_t)e->n_env : 1) * e->K;
+  FV_HIP_CHECK(hipMemsetAsync(at, 0, n * sizeof(int32_t), static_cast<hipStream_t>(s)));
+  return FV_OK;
+}
+
+int fv_ensemble_step(fv_handle* h, fv_ensembler* e, const float* chunks, float* actions, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !e || !chunks || !actions) return fv_fail(FV_ERR_ARG, "fv_ensemble_step: null argument");
+  const int rc = fv::launch_ensemble_step(chunks, e->ens, e->count, actions, e->w, e->cw, e->n_env, e->K, e->A, e->head, static_cast<hipStream_t>(s));
+  if (rc != FV_OK) return rc;
+  e->head = (e->head + 1) % e->K;
+  return FV_OK;
+}
+}  // extern "C"

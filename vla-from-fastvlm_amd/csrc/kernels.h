@@ -296,15 +296,32 @@ int launch_attention_split_bwd(const float* qkv, int ld, const bf16_t* o_hi, con
 struct HeadDims { int feat, ds, da, hid, fus; int te = 0; int draws = 1; };
 inline int head_cat_width(const HeadDims& d) { return d.feat + d.hid + (d.te > 0 ? d.da + d.te : 0); }
 inline int head_rows(const HeadDims& d, int B) { return d.te > 0 && d.draws > 1 ? d.draws * B : B; }
-struct HeadOffsets { int64_t o[13]; };
+// the 12 parameter tensors in the flat buffer's order (head_offsets; fv_head_layout's offsets[13] and Python's head_views are the same order), then the total
+enum HeadParam {
+  HP_STATE_LN_W, HP_STATE_LN_B,   // state_projection.0 (LayerNorm)
+  HP_STATE_W, HP_STATE_B,         // state_projection.1 (Linear, then SiLU)
+  HP_FUS0_W, HP_FUS0_B,           // fusion.0 (Linear over cat)
+  HP_FUS_LN_W, HP_FUS_LN_B,       // fusion.1 (LayerNorm, then SiLU and dropout)
+  HP_FUS4_W, HP_FUS4_B,           // fusion.4 (Linear, then SiLU)
+  HP_ACT_W, HP_ACT_B,             // action_head
+  HP_TOTAL                        // o[HP_TOTAL]: the flat buffer's length in floats; also the number of tensors
+};
+struct HeadOffsets { int64_t o[HP_TOTAL + 1]; };
 HeadOffsets head_offsets(const HeadDims& d);
 size_t head_saved_bytes(const HeadDims& d, int B);
+// (the two launchers that only the head's own translation units call stay out of the library's dynamic symbol table)
+__attribute__((visibility("hidden"))) float* head_saved_cat(const HeadDims& d, int B, float* saved);   // the (head_rows(d, B), head_cat_width(d)) matrix `cat` inside `saved` (launch_flow_prepare writes its x_t and phi(t) columns)
+inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }   // grid sizes of the head, chunk, flow and optimiser launchers
 // dataset normalisation folded into the head (device vectors; LeRobot MEAN_STD): states <- (states - state_mean) * state_istd
 // ahead of the first LayerNorm; actions <- actions * action_std + action_mean behind the last Linear when not training
 struct HeadIoNorm { const float *state_mean, *state_istd, *action_mean, *action_std; };
 int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, const float* states, int B,
                         int training, float drop_p, uint64_t seed, uint64_t offset, float* actions, float* saved,
                         hipStream_t s, const HeadIoNorm* io = nullptr);
+// the state branch alone (two launches; no checks, no error query: its callers do both): n0 = LN((states - state_mean) * state_istd) with xh0 / rstd0 kept,
+// z1 = state_projection.1(n0), dst[b][0 : hid] = silu(z1[b]) with row stride ldd.  launch_head_forward writes cat[:, feat:], the samplers a buffer of their own
+__attribute__((visibility("hidden"))) void launch_head_state_branch(const HeadDims& d, const float* P, const float* states, int B, float* n0, float* xh0, float* rstd0, float* z1, float* dst,
+                                                                   int ldd, hipStream_t s, const HeadIoNorm* io);
 // the fused loss of launch_head_backward (fv_head_set_loss / fv_head_set_loss_mask): kind FV_LOSS_*, beta of smooth-L1, chunk = K steps of da / K action
 // dimensions each, pad = device (B, K) bytes or null, metrics = 2 device floats { masked MSE, valid fraction }.  null, or MSE without a mask: mse_kernel as ever
 // dim_w (da / chunk floats) and step_w (chunk floats): device vectors of fv_head_set_loss_weights, both set or both null.  Set: EVERY kind, plain MSE without a

@@ -1,5 +1,9 @@
-// optim_kernels.hip -- the fused clip + AdamW step over PARAMETER GROUPS (fv_adamw_clip_step_groups): per group a learning-rate factor, a weight decay
-// and a frozen flag; one global clip norm over the non-frozen elements, and a gradient norm per group.
+// optim_kernels.hip -- the fused global-norm clip + AdamW step on one flat buffer, in its two forms, and axpy.  Both forms evaluate common.h's adamw_update /
+// ema_update per element, so a grouped step whose groups all carry lr_scale 1 and one decay gives the single-group step's bits.
+//   single group (fv_adamw_clip_step[_ema]): sumsq_kernel + its fold, adamw_kernel<EMA>   trainer.py:60-66,178-180; lerobot configuration_fastvla.py:51-55
+//   axpy_kernel: gradient accumulation over micro-batches / an upstream loss gradient
+//   PARAMETER GROUPS (fv_adamw_clip_step_groups): per group a learning-rate factor, a weight decay and a frozen flag; one global clip norm over the non-frozen
+//   elements, and a gradient norm per group.
 //   torch.optim.AdamW's param_groups + clip_grad_norm_ over the parameters with requires_grad (the reference's step body, training/trainer.py:60-66,178-180,
 //   knows one group only: it trains a 3 M-parameter head).
 // The table (kernels.h AdamwGroupsTable) is built once on the host: every group cut into segments of <= FV_ADAMW_SEGMENT floats, all boundaries multiples of
@@ -12,6 +16,77 @@
 namespace fv {
 namespace {
 
+// ---- the single-group step ----
+// Global gradient norm in a FIXED summation order (per-block partials, then one block folds them): float atomics would make
+// the norm -- and through the clip coefficient every parameter -- depend on arrival order, so two data-parallel replicas
+// (or two runs) would drift apart by an ulp per step.
+constexpr int SUMSQ_BLOCKS = 1024;
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long n, float* __restrict__ partial) {
+  __shared__ float red[4];
+  // 16-byte loads, four independent sums per thread (the unfrozen path's 2 GB gradient: 0.84 -> ~0.45 ms); a fixed order either way
+  float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+  const long n4 = n >> 2;
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float4 v = g4[i];
+    s0 += v.x * v.x; s1 += v.y * v.y; s2 += v.z * v.z; s3 += v.w * v.w;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (int)(n & 3)) { const float v = g[(n4 << 2) + threadIdx.x]; s0 += v * v; }
+  float s = wave_sum((s0 + s1) + (s2 + s3));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[1 + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ __launch_bounds__(256) void sumsq_fold_kernel(float* __restrict__ partial, int nb) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) s += partial[1 + i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[0] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// EMA instance (fv_adamw_clip_step_ema): also e <- ema_update(e, p_new, ema_w) while p_new is in its register, 8 more bytes per element.  The plain instance
+// never looks at e / ema_w: it is the kernel as it was.
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                     float* __restrict__ m, float* __restrict__ v, long n,
+                                                     fv_adamw_hparams hp, float bc1, float bc2_sqrt,
+                                                     const float* __restrict__ sumsq, float* __restrict__ norm_out,
+                                                     float* __restrict__ e, float ema_w) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  // torch clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max = 1)
+  const float norm = sqrtf(*sumsq) * hp.grad_scale;
+  float coef = hp.grad_scale;
+  if (hp.max_grad_norm > 0.f) coef *= fminf(hp.max_grad_norm / (norm + 1e-6f), 1.0f);
+  if (i == 0 && norm_out) *norm_out = norm;
+  if (i >= n) return;
+  float pi = p[i], mi = m[i], vi = v[i];
+  adamw_update(pi, g[i], mi, vi, coef, hp.lr, hp.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);   // (shared with adamw_groups_kernel: common.h)
+  p[i] = pi;
+  m[i] = mi;
+  v[i] = vi;
+  if constexpr (EMA) e[i] = ema_update(e[i], pi, ema_w);
+}
+
+// y += x (x != null) or y *= *scale (x == null): gradient accumulation over micro-batches / an upstream loss gradient
+__global__ __launch_bounds__(256) void axpy_kernel(float* __restrict__ y, const float* __restrict__ x, long n4,
+                                                    const float* __restrict__ scale) {
+  const float sc = scale ? *scale : 1.0f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    float4 a = reinterpret_cast<float4*>(y)[i];
+    if (x) {
+      const float4 b = reinterpret_cast<const float4*>(x)[i];
+      a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    } else {
+      a.x *= sc; a.y *= sc; a.z *= sc; a.w *= sc;
+    }
+    reinterpret_cast<float4*>(y)[i] = a;
+  }
+}
+
+// ---- the step over parameter groups ----
 __device__ __forceinline__ float block_sum_256(float s, float* red) {   // every thread returns the block's sum
   s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -98,6 +173,47 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
 }
 
 }  // namespace
+
+// the EMA operand of both fused steps: a buffer of its own (the kernels hold p, g, m, v, e as __restrict__) and a weight in [0, 1]
+int check_adamw_ema(const char* who, const float* p, const float* g, const float* m, const float* v, const float* ema, float ema_weight, int64_t n) {
+  if (!(ema_weight >= 0.f && ema_weight <= 1.f)) return fv_fail(FV_ERR_ARG, "%s: ema_weight %g outside [0, 1]", who, (double)ema_weight);
+  const uintptr_t e0 = (uintptr_t)ema, bytes = (uintptr_t)n * sizeof(float);
+  const struct { const float* q; const char* name; } others[4] = {{p, "flat_params"}, {g, "flat_grads"}, {m, "m"}, {v, "v"}};
+  for (const auto& o : others)
+    if (e0 < (uintptr_t)o.q + bytes && (uintptr_t)o.q < e0 + bytes) return fv_fail(FV_ERR_ARG, "%s: ema aliases %s", who, o.name);
+  return FV_OK;
+}
+
+size_t adamw_scratch_bytes() { return (size_t)(SUMSQ_BLOCKS + 4) * sizeof(float); }
+
+int launch_axpy(float* y, const float* x, int64_t n, const float* scale_dev, hipStream_t s) {
+  // the flat head buffers keep every tensor 16-byte aligned and their total a multiple of 4 elements (head_offsets)
+  if (n % 4 || ((uintptr_t)y & 15) || ((uintptr_t)x & 15)) return fv_fail(FV_ERR_ARG, "axpy: buffers must be 16-byte aligned, n %% 4 == 0");
+  const unsigned nb = cdiv(n / 4, 256);
+  hipLaunchKernelGGL(axpy_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), 0, s, y, x, (long)(n / 4), scale_dev);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,
+                      int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s, float* ema, float ema_weight) {
+  if (!p || !g || !m || !v || !norm_scratch) return fv_fail(FV_ERR_ARG, "adamw: null pointer");
+  if (n <= 0 || step < 1) return fv_fail(FV_ERR_ARG, "adamw: n and step must be positive");
+  if (ema) { const int rc = check_adamw_ema("adamw", p, g, m, v, ema, ema_weight, n); if (rc != FV_OK) return rc; }
+  const unsigned nb = (unsigned)((n + 255) / 256);
+  const unsigned nb4 = (unsigned)((n / 4 + 255) / 256 > 0 ? (n / 4 + 255) / 256 : 1);
+  const unsigned nsb = nb4 < (unsigned)SUMSQ_BLOCKS ? nb4 : (unsigned)SUMSQ_BLOCKS;
+  hipLaunchKernelGGL(sumsq_kernel, dim3(nsb), dim3(256), 0, s, g, (long)n, norm_scratch);
+  hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(256), 0, s, norm_scratch, (int)nsb);
+  const float bc1 = (float)(1.0 - pow((double)hp.beta1, (double)step));
+  const float bc2 = (float)sqrt(1.0 - pow((double)hp.beta2, (double)step));
+  if (ema && ema_weight != 0.f)   // (weight 0 leaves the average alone: the plain instance, which never reads it)
+    hipLaunchKernelGGL(adamw_kernel<true>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, ema, ema_weight);
+  else
+    hipLaunchKernelGGL(adamw_kernel<false>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, (float*)nullptr, 0.f);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
 
 int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
                              int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema, float ema_weight) {

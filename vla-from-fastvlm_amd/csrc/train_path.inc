@@ -80,7 +80,7 @@ std::vector<TrainTensor> train_tensors(fv_handle* h, int64_t* total) {
     t.name = head_names[i]; t.off = ho.o[i]; t.rows = hrows[i]; t.cols = hcols[i]; t.numel = (int64_t)t.rows * t.cols; t.bucket = TB_HEAD;
     out.push_back(t);
   }
-  off = (ho.o[12] + 3) / 4 * 4;
+  off = (ho.o[fv::HP_TOTAL] + 3) / 4 * 4;
   const int H = d.llm_hidden, CO = d.tower_out_dim, I = d.llm_inter, D = d.llm_head_dim;
   const int qd = d.llm_heads * D, kd = d.llm_kv_heads * D, qkvw = qd + 2 * kd;
   Tower& tw = h->tw;
@@ -214,7 +214,7 @@ DecCtx dec_ctx(fv_handle* h, const TrainPlan& tp, void* ws, hipStream_t s, float
     DecCtx::Span& sp = c.span[t.bucket];
     sp.lo = std::min(sp.lo, t.off); sp.hi = std::max(sp.hi, t.off + (t.numel + 3) / 4 * 4);
   }
-  c.span[TB_HEAD] = {0, (fv::head_offsets(h->hd).o[12] + 3) / 4 * 4};   // the head's own layout (and its padding)
+  c.span[TB_HEAD] = {0, (fv::head_offsets(h->hd).o[fv::HP_TOTAL] + 3) / 4 * 4};   // the head's own layout (and its padding)
   return c;
 }
 
