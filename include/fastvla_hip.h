@@ -375,6 +375,40 @@ int fv_head_set_flow_guidance(fv_handle* h, int chunk, const float* step_weights
 int fv_head_flow_sample_guided(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                                uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions, float* chunk_out,
                                fv_stream s);
+/* ---- action-prefix conditioning (Black, Ren, Equi, Levine 2025, "Training-time action conditioning for efficient real-time chunking"): the conditioning
+ * that guidance approximates at inference time moves into training.  A delay d <= D is drawn per head row; the first d steps of the chunk reach the network
+ * CLEAN, only the rest is noised and only the rest trains.  This head has one phi(t) for the whole flattened chunk, so the prefix travels as one more block:
+ *     cat = [ pooled | state branch | x_t (action_dim) | phi(t) (time_dim) | m (chunk) ]      m[k] = 1 for k < d, else 0
+ *     x_t[k, :] = a[k, :] exactly (a copy) for k < d, as ever for k >= d
+ * Only fusion.0.weight grows, by `chunk` columns behind phi; the 12 tensors, their order and fv_head_layout's 13 offsets stay.  A conditioned step is treated
+ * by the loss exactly like a padded one (0 to the loss and to every gradient; the divisor stays all S B K A elements); u is written everywhere as ever.
+ * fv_head_loss_metrics keeps reporting the pad-only valid fraction; its masked MSE is over the trained elements.
+ * chunk = K >= 2 divides action_dim and must be the loss's chunk length (fv_head_set_loss) whenever the fused loss runs (FV_ERR_STATE from the backward
+ * otherwise); max_delay = D, 1 <= D <= K - 1; thresholds_host: D + 1 non-decreasing HOST uint32, the cumulative delay distribution in units of 2^-24, the
+ * last one 2^24 (fastvla_hip.prefix.delay_thresholds builds it).  NULL thresholds switch the mode off, as fv_head_set_flow(NULL) does: every size and every
+ * launch is then the flow head's.  Allowed only in flow mode, BEFORE fv_bind_workspace and before any fv_train_*_begin (FV_ERR_STATE otherwise); FV_ERR_ARG,
+ * changing nothing, for invalid input.  fv_head_saved_bytes, the workspace and the training layouts grow by the K mask columns and a (head rows, K) byte mask
+ * inside `saved`.
+ * THE DELAY of a head row comes from the group-0 Philox block that yields t: t uses words x and y, d is the smallest j with (z >> 8) < thresholds[j] -- an
+ * integer compare, no new stream, no new counter: t and eps are the bits a plain flow head draws for the same (seed, offset, row), and draw s of an S-draw
+ * step is still the single draw at offset + (s << 56), delay included.  fv_head_flow_prepare keeps its signature and draws the delays in prefix mode;
+ * fv_head_flow_prepare_prefix takes them explicitly (device int32, one per head row, clamped to 0 .. D inside the kernel), as noise and t do: the form for
+ * tests and captured graphs.  One launch writes x_t, phi(t), m, u and the byte mask.
+ * fv_head_flow_sample, fv_head_flow_sample_guided and fv_head_forward with training == 0 work on a prefix-width head with m = 0. */
+int fv_head_set_flow_prefix(fv_handle* h, int chunk, int max_delay, const uint32_t* thresholds_host);
+int fv_head_flow_prepare_prefix(fv_handle* h, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
+                                const int32_t* delays, void* saved, float* u_out, fv_stream s);
+/* fv_head_flow_sample with the first steps of the chunk pinned.  prev: (B, action_dim) device f32, the previous chunk in NORMALISED space; delays: (B) device
+ * int32.  Row b pins its first min(delays[b], D, K - shift) steps to prev[b][k + shift] (the clamp runs inside the kernels: no host synchronisation); they
+ * leave in chunk_out ((B, action_dim) or NULL, normalised) as the bits they came in with and in `actions` as fmaf(prev, action_std, action_mean) when
+ * fv_head_set_io_norm is on.  A delay of 0 pins nothing.  Whatever prev holds outside the pinned range (NaN, +-inf) is never read.
+ * Conditioning once (the mask block's sum of fusion.0 columns joins it), then three launches per step, as fv_head_flow_sample: no guidance, no Jacobian,
+ * no atomics, no allocation, every sum in a fixed order: two calls give the same bits.  shift, n_steps and the step times are host state of the call.
+ * Refused before anything is enqueued: FV_ERR_STATE when flow mode or prefix mode is off or no workspace is bound; FV_ERR_ARG for a null flat_params /
+ * pooled / states / prev / delays / actions, shift outside 0 .. K, n_steps < 1, B outside 1 .. max_batch. */
+int fv_head_flow_sample_prefix(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                               uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out,
+                               fv_stream s);
 /* generic backward of the head from dL/dactions (B,A) f32 (what autograd hands a custom Function when the loss is
  * computed outside, e.g. lerobot_fastvla/modeling_fastvla.py:132 + loss.backward()); overwrites flat_grads. */
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,

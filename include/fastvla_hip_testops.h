@@ -232,6 +232,15 @@ int fv_op_head_loss_backward_draws(int feat, int ds, int da, int hid, int fus, i
  * v_out, jt_out (B, da).  scratch: scratch_floats floats; FV_ERR_ARG names the count when it is too small. */
 int fv_op_flow_vjp(int feat, int ds, int da, int hid, int fus, int time_dim, const float* freq, const float* P, const float* pooled, const float* states, int B,
                    const float* x, float t, const float* omega, float* v_out, float* jt_out, float* scratch, size_t scratch_floats, fv_stream s);
+/* the same on a prefix-width head (fv_head_set_flow_prefix): fusion.0.weight has prefix_chunk more columns behind phi(t), P is the flat buffer of THAT layout;
+ * the chain runs with m = 0 and never reads the mask columns.  prefix_chunk >= 2 divides da. */
+int fv_op_flow_vjp_prefix(int feat, int ds, int da, int hid, int fus, int time_dim, int prefix_chunk, const float* freq, const float* P, const float* pooled,
+                          const float* states, int B, const float* x, float t, const float* omega, float* v_out, float* jt_out, float* scratch, size_t scratch_floats,
+                          fv_stream s);
+/* where fusion.0's input `cat` = [ pooled | state branch | x_t | phi(t) | m ] lies inside the saved activations (fv_head_saved_bytes) of a head with these
+ * dimensions: *out_floats = its offset in floats; its shape is (draws * B, cat width).  time_dim 0: the regression head; draws 1 and prefix_chunk 0: off.
+ * The layout is the library's own (csrc/head_kernels.hip carve): tests ask for it here instead of repeating it. */
+int fv_op_head_saved_cat_offset(int feat, int ds, int da, int hid, int fus, int time_dim, int draws, int prefix_chunk, int B, size_t* out_floats);
 
 #ifdef __cplusplus
 }

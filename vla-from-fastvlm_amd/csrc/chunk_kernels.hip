@@ -33,7 +33,15 @@ __device__ __forceinline__ float add_square_rounded(float s, float d) {
 // WEIGHTED (fv_head_set_loss_weights): om = dim_w[i % A] * step_w[(i / A) % K] scales rho and g; an element with om == 0 is selected away like a padded
 // one (0 to the loss, to g and to the masked MSE, whatever its target holds).  The two metrics stay unweighted and the valid count looks at pads only.
 // om == 1 changes no bit: x * 1.0f is exact, and a contracted fma(rho, 1, s) is s + rho.
-template <bool WEIGHTED>
+// PREFIX (fv_head_set_flow_prefix): the mask byte is 0 live, 1 padded, 2 masked by the action prefix alone.  Both are selected away; a byte of 2 still counts
+// as a valid step, so the valid fraction stays the pad-only one.  The instances without it keep their own expressions: they are the code they were
+__device__ __forceinline__ bool chunk_step_live(const uint8_t* __restrict__ pad, long st, unsigned& cnt) {
+  if (!pad) return true;
+  const uint8_t pb = pad[st];
+  cnt += pb == 2;
+  return pb == 0;
+}
+template <bool WEIGHTED, bool PREFIX>
 __global__ __launch_bounds__(256) void chunk_loss_kernel(const float* __restrict__ a, const float* __restrict__ t, const uint8_t* __restrict__ pad,
                                                           float* __restrict__ g, float* __restrict__ partial, long n, int A, int kind, float beta,
                                                           float loss_scale, int vec, const float* __restrict__ dim_w, const float* __restrict__ step_w, int K) {
@@ -43,7 +51,11 @@ __global__ __launch_bounds__(256) void chunk_loss_kernel(const float* __restrict
   unsigned cnt = 0;
   auto weighted = [&](long i, float ai, float ti) -> float {   // element i of the weighted instance -> g
     const long st = i / A;
-    if (pad && pad[st] != 0) return 0.f;
+    if constexpr (PREFIX) {
+      if (!chunk_step_live(pad, st, cnt)) return 0.f;
+    } else {
+      if (pad && pad[st] != 0) return 0.f;
+    }
     ++cnt;
     const float om = dim_w[i - st * A] * step_w[st % K];
     if (om == 0.f) return 0.f;
@@ -57,7 +69,9 @@ __global__ __launch_bounds__(256) void chunk_loss_kernel(const float* __restrict
     if constexpr (WEIGHTED) {
       g[i] = weighted(i, a[i], t[i]);
     } else {
-      const bool w = !pad || pad[i / A] == 0;
+      bool w;
+      if constexpr (PREFIX) w = chunk_step_live(pad, i / A, cnt);
+      else w = !pad || pad[i / A] == 0;
       LossTerm r{0.f, 0.f};
       if (w) {
         const float d = a[i] - t[i];
@@ -78,7 +92,9 @@ __global__ __launch_bounds__(256) void chunk_loss_kernel(const float* __restrict
         if constexpr (WEIGHTED) {
           ge[j] = weighted(i * 4 + j, ae[j], te[j]);
         } else {
-          const bool w = !pad || pad[(i * 4 + j) / A] == 0;
+          bool w;
+          if constexpr (PREFIX) w = chunk_step_live(pad, (i * 4 + j) / A, cnt);
+          else w = !pad || pad[(i * 4 + j) / A] == 0;
           LossTerm r{0.f, 0.f};
           if (w) {
             const float d = ae[j] - te[j];
@@ -174,7 +190,7 @@ __global__ __launch_bounds__(256) void ensemble_step_kernel(const float* __restr
 size_t chunk_loss_partial_floats() { return 3 * (size_t)CHUNK_LOSS_BLOCKS; }
 
 int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, float* loss, float* metrics, long n, int A, int kind,
-                      float beta, float loss_scale, hipStream_t s, const float* dim_w, const float* step_w, int K) {
+                      float beta, float loss_scale, hipStream_t s, const float* dim_w, const float* step_w, int K, int prefix) {
   if (!a || !t || !g || !partial || !loss || !metrics) return fv_fail(FV_ERR_ARG, "chunk_loss: null pointer");
   if (n <= 0 || A <= 0 || n % A) return fv_fail(FV_ERR_ARG, "chunk_loss: n must be a positive multiple of the step width");
   if (kind != FV_LOSS_MSE && kind != FV_LOSS_L1 && kind != FV_LOSS_SMOOTH_L1) return fv_fail(FV_ERR_ARG, "chunk_loss: unknown loss kind %d", kind);
@@ -184,9 +200,13 @@ int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float*
   const unsigned nb = want < 1 ? 1 : (want < (unsigned)CHUNK_LOSS_BLOCKS ? want : (unsigned)CHUNK_LOSS_BLOCKS);
   if (dim_w || step_w) {
     if (!dim_w || !step_w || K < 1 || (n / A) % K) return fv_fail(FV_ERR_ARG, "chunk_loss: weights need both vectors and a chunk length that divides the step count");
-    hipLaunchKernelGGL(chunk_loss_kernel<true>, dim3(nb), dim3(256), 0, s, a, t, pad, g, partial, n, A, kind, beta, loss_scale, vec, dim_w, step_w, K);
+    if (prefix) hipLaunchKernelGGL((chunk_loss_kernel<true, true>), dim3(nb), dim3(256), 0, s, a, t, pad, g, partial, n, A, kind, beta, loss_scale, vec, dim_w, step_w, K);
+    else hipLaunchKernelGGL((chunk_loss_kernel<true, false>), dim3(nb), dim3(256), 0, s, a, t, pad, g, partial, n, A, kind, beta, loss_scale, vec, dim_w, step_w, K);
+  } else if (prefix) {
+    hipLaunchKernelGGL((chunk_loss_kernel<false, true>), dim3(nb), dim3(256), 0, s, a, t, pad, g, partial, n, A, kind, beta, loss_scale, vec, (const float*)nullptr,
+                       (const float*)nullptr, 1);
   } else {
-    hipLaunchKernelGGL(chunk_loss_kernel<false>, dim3(nb), dim3(256), 0, s, a, t, pad, g, partial, n, A, kind, beta, loss_scale, vec, (const float*)nullptr,
+    hipLaunchKernelGGL((chunk_loss_kernel<false, false>), dim3(nb), dim3(256), 0, s, a, t, pad, g, partial, n, A, kind, beta, loss_scale, vec, (const float*)nullptr,
                        (const float*)nullptr, 1);
   }
   hipLaunchKernelGGL(chunk_loss_fold_kernel, dim3(1), dim3(256), 0, s, partial, (int)nb, loss, metrics, n);

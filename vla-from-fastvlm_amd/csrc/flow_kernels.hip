@@ -2,6 +2,8 @@
 //   flow_prepare_kernel                    training: x_t and phi(t) into their columns of the head's cat, u = eps - a as the loss target; the head itself
 //                                          (head_kernels.hip) then runs forward and backward as it does for regression
 //   flow_cond / _init / _step_a / _b / _c  the Euler sampler (fv_head_flow_sample): conditioning once, three launches per step
+//   flow_*_prefix_kernel                   action-prefix conditioning (fv_head_set_flow_prefix): the noising step's, the conditioning's, the start's and step C's
+//                                          PREFIX instances; the kernels without the suffix are the code they were
 //   flow_guide_* / flow_vjp_t_kernel       guided sampling (fv_head_set_flow_guidance; real-time chunking): the step's forward with z3 and v kept, J^T omega
 //                                          through three transposed products and a LayerNorm backward, and the update
 // The state branch of both samplers is head_kernels.hip's (launch_head_state_branch); the draws come from common.h philox under this file's key.
@@ -69,6 +71,50 @@ __global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restri
       if (i >= da) break;
       const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)obs * da + i];
       xr[i] = (float)(td * (double)e + omt * (double)a);
+      u_out[(size_t)row * da + i] = e - a;
+    }
+  }
+  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t, i);
+}
+// The PREFIX instance (fv_head_set_flow_prefix), a sibling so that the kernel above stays the code it was.  The row's delay d: delays[row] clamped to 0 .. pd,
+// or the smallest j with (z >> 8) < thr[j], z the third word of the group-0 block whose x and y yield t (an integer compare; no new stream, no new counter:
+// t and eps are the plain head's bits).  The first d steps of x_t are COPIES of targets, m = [k < d] goes behind phi(t) as exact 0.0 / 1.0 and as bytes into
+// pmask; u is written everywhere as ever
+struct FlowPrefixArgs { const int32_t* delays; const uint32_t* thr; uint8_t* pmask; int pk, pd; };
+__global__ __launch_bounds__(256) void flow_prepare_prefix_kernel(const float* __restrict__ targets, const float* __restrict__ noise, const float* __restrict__ tin,
+                                                                   float* __restrict__ cat, int cw, int xo, float* __restrict__ u_out, int da, int te,
+                                                                   const float* __restrict__ freq, int time_dist, float dist_a, float dist_b, uint64_t seed,
+                                                                   uint64_t offset, FlowPrefixArgs px) {
+  const int obs = blockIdx.x, row = blockIdx.y * gridDim.x + obs;
+  offset += (uint64_t)blockIdx.y << 56;
+  const uint4 r = flow_philox(0u, (uint32_t)obs, seed, offset);
+  float t;
+  if (tin) t = tin[row];
+  else if (time_dist == 0) t = (float)(r.x >> 8) * FLOW_U24;
+  else t = 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x)));
+  int dl = 0;
+  if (px.delays) {
+    dl = min(max(px.delays[row], 0), px.pd);
+  } else {
+    const uint32_t z24 = r.z >> 8;
+    while (dl < px.pd && z24 >= px.thr[dl]) ++dl;
+  }
+  const int pin = dl * (da / px.pk);   // elements [0, pin) of the row are the conditioned steps
+  float* xr = cat + (size_t)row * cw + xo;
+  for (int k = threadIdx.x; k < px.pk; k += 256) {
+    xr[da + te + k] = k < dl ? 1.0f : 0.0f;
+    px.pmask[(size_t)row * px.pk + k] = k < dl ? 1 : 0;
+  }
+  const double td = (double)t, omt = 1.0 - td;
+  for (int g = threadIdx.x; g * 4 < da; g += 256) {
+    float n[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)obs, seed, offset, n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = g * 4 + j;
+      if (i >= da) break;
+      const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)obs * da + i];
+      xr[i] = i < pin ? a : (float)(td * (double)e + omt * (double)a);
       u_out[(size_t)row * da + i] = e - a;
     }
   }
@@ -348,17 +394,119 @@ __global__ __launch_bounds__(256) void flow_guide_update_kernel(const float* __r
   actions[e] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
 }
 
+// ---- the prefix sampler (fv_head_flow_sample_prefix; training-time action conditioning).  Row b's first p_b = min(delays[b], pd, chunk - shift) steps are PINNED
+// to prev[b][k + shift]: written once by the start kernel, left alone by every step, so they leave as the bits they came in with.  The clamp runs inside the
+// kernels (no host synchronisation); a pinned element is SELECTED, whatever prev holds elsewhere (NaN, +-inf) is never read
+__device__ __forceinline__ int flow_pinned_steps(const int32_t* __restrict__ delays, int b, int pd, int chunk, int shift) {
+  return min(min(max(delays[b], 0), pd), chunk - shift);
+}
+// the start: xphi (B, da + te) <- [ prev on the pinned elements, noise or the draws of (seed, offset) elsewhere | phi(t0) ]
+__global__ __launch_bounds__(256) void flow_init_prefix_kernel(const float* __restrict__ noise, float* __restrict__ xphi, int da, int te, const float* __restrict__ freq,
+                                                                float t0, uint64_t seed, uint64_t offset, const float* __restrict__ prev,
+                                                                const int32_t* __restrict__ delays, int pd, int chunk, int shift) {
+  const int row = blockIdx.x, A = da / chunk, pin = flow_pinned_steps(delays, row, pd, chunk, shift) * A;
+  float* xr = xphi + (size_t)row * (da + te);
+  for (int g = threadIdx.x; g * 4 < da; g += 256) {
+    float n[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)row, seed, offset, n);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int i = g * 4 + j;
+      if (i >= da) break;
+      if (i < pin) xr[i] = prev[(size_t)row * da + i + (size_t)shift * A];   // (i + shift A < (p_b + shift) A <= da)
+      else xr[i] = noise ? noise[(size_t)row * da + i] : n[j];
+    }
+  }
+  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t0, i);
+}
+// flow_cond_kernel with the mask block: c[b][n] += sum_{k < p_b} W4[n][mo + k], which does not change over the steps.  The mask's columns join the wave's
+// partial sums behind the state branch's (lane k % 64 owns column k), one wave_sum per row as ever: a fixed order
+__global__ __launch_bounds__(256) void flow_cond_prefix_kernel(const float* __restrict__ pooled, int feat, const float* __restrict__ sb, int hid,
+                                                                const float* __restrict__ W, int ldw, const float* __restrict__ bias, float* __restrict__ c, int B,
+                                                                int N, int mo, const int32_t* __restrict__ delays, int pd, int chunk, int shift) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (n >= N) return;
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(pooled, feat, W + (size_t)n * ldw, feat, b0, B, lane, acc);
+  flow_dot8(sb, hid, W + (size_t)n * ldw + feat, hid, b0, B, lane, acc);
+  int pin[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pin[j] = flow_pinned_steps(delays, min(b0 + j, B - 1), pd, chunk, shift);
+  for (int k = lane; k < pd; k += 64) {   // (p_b <= pd: the columns behind it are never read)
+    const float wv = W[(size_t)n * ldw + mo + k];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += k < pin[j] ? wv : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0)
+    for (int j = 0; j < 8 && b0 + j < B; ++j) c[(size_t)(b0 + j) * N + n] = acc[j] + bias[n];
+}
+// flow_step_c_kernel whose owning lane leaves a pinned element alone.  The last step writes `actions` (with the folded statistics) and chunk_out (without,
+// may be null) for every element, pinned ones from x as it stands; x + dt v and x scale + shift are the explicit fused multiply-adds
+__global__ __launch_bounds__(256) void flow_step_c_prefix_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
+                                                                  float* __restrict__ xphi, int xw, int te, float dt, float t_next, const float* __restrict__ freq,
+                                                                  float* __restrict__ actions, float* __restrict__ chunk_out, const float* __restrict__ post_scale,
+                                                                  const float* __restrict__ post_shift, int B, int N, const int32_t* __restrict__ delays, int pd,
+                                                                  int chunk, int shift) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (!actions && blockIdx.x == 0) {
+    const int half = te / 2;
+    for (int idx = threadIdx.x; idx < 8 * half; idx += 256) {
+      const int j = idx / half, i = idx - j * half;
+      if (b0 + j < B) flow_phi(xphi + (size_t)(b0 + j) * xw + N, freq, half, t_next, i);
+    }
+  }
+  if (n >= N) return;
+  // the rows' pinned step counts and this column's x are asked for ahead of the product: their latency hides behind it instead of trailing the wave sums
+  int pin[8];
+  float xv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int b = min(b0 + j, B - 1);
+    pin[j] = flow_pinned_steps(delays, b, pd, chunk, shift);
+    xv[j] = xphi[(size_t)b * xw + n];
+  }
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0) {
+    const int k = n / (N / chunk);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (b0 + j >= B) break;
+      const size_t b = (size_t)(b0 + j);
+      const bool pinned = k < pin[j];
+      const float x = xv[j];
+      const float xn = pinned ? x : flow_fma_pinned(dt, acc[j] + bias[n], x);
+      if (!actions) {
+        if (!pinned) xphi[b * xw + n] = xn;
+        continue;
+      }
+      if (chunk_out) chunk_out[b * N + n] = xn;
+      actions[b * N + n] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
+    }
+  }
+}
+
 }  // namespace
 
 int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
-                        float* saved, float* u_out, hipStream_t s) {
+                        float* saved, float* u_out, hipStream_t s, const int32_t* delays) {
   if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_prepare: the head is not in flow mode (fv_head_set_flow)");
+  if (delays && d.pk <= 0) return fv_fail(FV_ERR_STATE, "flow_prepare: delays need prefix mode (fv_head_set_flow_prefix)");
+  if (d.pk > 0 && !delays && !f.thr) return fv_fail(FV_ERR_STATE, "flow_prepare: prefix mode without a delay table");
   if (!targets || !saved || !u_out) return fv_fail(FV_ERR_ARG, "flow_prepare: null pointer");
   if (B <= 0) return fv_fail(FV_ERR_ARG, "flow_prepare: B must be positive");
   const int S = head_rows(d, B) / B;
   if (S > 1 && (offset >> 56 & 15)) return fv_fail(FV_ERR_ARG, "flow_prepare: bits 56 .. 59 of the offset number the draws and must be 0 with more than one draw");
-  hipLaunchKernelGGL(flow_prepare_kernel, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved), head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
-                     f.time_dist, f.dist_a, f.dist_b, seed, offset);
+  if (d.pk > 0)
+    hipLaunchKernelGGL(flow_prepare_prefix_kernel, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved), head_cat_width(d), d.feat + d.hid, u_out, d.da,
+                       d.te, f.freq, f.time_dist, f.dist_a, f.dist_b, seed, offset, FlowPrefixArgs{delays, f.thr, head_saved_prefix_mask(d, B, saved), d.pk, d.pd});
+  else
+    hipLaunchKernelGGL(flow_prepare_kernel, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved), head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
+                       f.time_dist, f.dist_a, f.dist_b, seed, offset);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -409,6 +557,39 @@ int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, con
     hipLaunchKernelGGL(flow_step_c_kernel, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, dt, t_next, f.freq,
                        last ? actions : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr, last && io ? io->action_mean : (const float*)nullptr,
                        B, d.da);
+  }
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+// launch_flow_sample with the conditioning's and the start's PREFIX kernels and step C's PREFIX instance: 4 launches, then 3 per Euler step
+int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                              uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out, float* scratch,
+                              hipStream_t s, const HeadIoNorm* io) {
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample_prefix: the head is not in flow mode (fv_head_set_flow)");
+  if (d.pk < 2 || d.da % d.pk || d.pd < 1 || d.pd >= d.pk) return fv_fail(FV_ERR_STATE, "flow_sample_prefix: prefix mode is off (fv_head_set_flow_prefix)");
+  if (!P || !pooled || !states || !prev || !delays || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: null pointer");
+  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: B and n_steps must be positive");
+  if (shift < 0 || shift > d.pk) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: shift = %d outside 0 .. chunk = %d", shift, d.pk);
+  const HeadOffsets ho = head_offsets(d);
+  const FlowScratch fs = flow_carve(d, B, scratch);
+  const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
+  const dim3 blk(256);
+  const unsigned b8 = cdiv(B, 8);
+  launch_head_state_branch(d, P, states, B, fs.n0, fs.xh0, fs.rstd0, fs.z1, fs.sb, d.hid, s, io);
+  hipLaunchKernelGGL(flow_cond_prefix_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[HP_FUS0_W], cw, P + ho.o[HP_FUS0_B], fs.c, B, d.fus,
+                     xo + xw, delays, d.pd, d.pk, shift);
+  hipLaunchKernelGGL(flow_init_prefix_kernel, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, 1.0f, seed, offset, prev, delays, d.pd, d.pk, shift);
+  const float dt = (float)(-1.0 / (double)n_steps);
+  for (int i = 0; i < n_steps; ++i) {
+    const bool last = i + 1 == n_steps;
+    const float t_next = (float)(1.0 - (double)(i + 1) / (double)n_steps);
+    hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
+    hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], fs.a3,
+                       (float*)nullptr, B, d.fus);
+    hipLaunchKernelGGL(flow_step_c_prefix_kernel, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, dt, t_next, f.freq,
+                       last ? actions : (float*)nullptr, last ? chunk_out : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr,
+                       last && io ? io->action_mean : (const float*)nullptr, B, d.da, delays, d.pd, d.pk, shift);
   }
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;

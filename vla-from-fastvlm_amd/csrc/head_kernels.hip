@@ -234,6 +234,20 @@ __global__ __launch_bounds__(256) void draws_pad_kernel(const uint8_t* __restric
   const uint8_t v = src[i];
   for (int s = 0; s < S; ++s) dst[(size_t)s * n + i] = v;
 }
+// prefix mode (fv_head_set_flow_prefix): the mask the chunked loss reads, dst[r K + k] = 1 where pad[(r % B) K + k] is set (pad may be null), else 2 where the
+// row's prefix mask m[r K + k] is set (conditioned on, not trained, still a valid step), else 0.  n = R K bytes, nobs = B K
+__global__ __launch_bounds__(256) void prefix_loss_mask_kernel(const uint8_t* __restrict__ pad, const uint8_t* __restrict__ m, uint8_t* __restrict__ dst, long n,
+                                                                long nobs) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  dst[i] = pad && pad[i % nobs] != 0 ? 1 : (m[i] != 0 ? 2 : 0);
+}
+// inference on a prefix-width head: the mask columns of cat are 0 (no step is conditioned on)
+__global__ __launch_bounds__(256) void zero_cols_kernel(float* __restrict__ dst, int ldd, int B, int N) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * N) return;
+  dst[(size_t)(i / N) * ldd + (i % N)] = 0.f;
+}
 
 }  // namespace
 
@@ -253,7 +267,8 @@ HeadOffsets head_offsets(const HeadDims& d) {
 namespace {
 struct Saved {
   float *n0, *xh0, *rstd0, *z1, *cat, *z2, *xh2, *rstd2, *n2, *d2, *mask, *z3, *a3;
-  size_t total;
+  uint8_t* pmask;   // prefix mode: (R, pk) bytes behind everything else (pk == 0: nothing, every offset and the total as ever)
+  size_t cat_off, total;   // cat's offset from the base and the whole block, in floats
 };
 // B observations; the state branch keeps B rows, cat .. a3 have R = head_rows(d, B) of them (more than B only with fv_head_set_flow_draws)
 Saved carve(const HeadDims& d, int B, float* base) {
@@ -262,9 +277,10 @@ Saved carve(const HeadDims& d, int B, float* base) {
   const size_t R = (size_t)head_rows(d, B);
   auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
   s.n0 = take((size_t)B * d.ds); s.xh0 = take((size_t)B * d.ds); s.rstd0 = take(B);
-  s.z1 = take((size_t)B * d.hid); s.cat = take(R * head_cat_width(d)); s.z2 = take(R * d.fus);
+  s.z1 = take((size_t)B * d.hid); s.cat_off = o; s.cat = take(R * head_cat_width(d)); s.z2 = take(R * d.fus);
   s.xh2 = take(R * d.fus); s.rstd2 = take(R); s.n2 = take(R * d.fus); s.d2 = take(R * d.fus);
   s.mask = take(R * d.fus); s.z3 = take(R * d.fus); s.a3 = take(R * d.fus);
+  s.pmask = reinterpret_cast<uint8_t*>(take(d.te > 0 ? (R * d.pk + 3) / 4 : 0));
   s.total = o;
   return s;
 }
@@ -272,13 +288,15 @@ Saved carve(const HeadDims& d, int B, float* base) {
 
 size_t head_saved_bytes(const HeadDims& d, int B) { return carve(d, B, nullptr).total * sizeof(float); }
 float* head_saved_cat(const HeadDims& d, int B, float* saved) { return carve(d, B, saved).cat; }
+size_t head_saved_cat_offset(const HeadDims& d, int B) { return carve(d, B, nullptr).cat_off; }
+uint8_t* head_saved_prefix_mask(const HeadDims& d, int B, float* saved) { return carve(d, B, saved).pmask; }
 
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B) {
   const size_t wmax = (size_t)(head_cat_width(d) > d.fus ? head_cat_width(d) : d.fus);
   // dL/dactions | two activation-gradient rows of the widest layer | alignment slack | the chunked loss's per-block partials (loss, sum w d^2, sum w)
-  // (draws: every row count is R = S B, and the pad mask's R K <= R da bytes, once per draw, come last)
+  // (draws: every row count is R = S B, and the pad mask's R K <= R da bytes, once per draw, come last; prefix mode builds its loss mask in the same place)
   const size_t R = (size_t)head_rows(d, B);
-  return (R * d.da + 2 * R * wmax + 64 + chunk_loss_partial_floats() + (R > (size_t)B ? (R * d.da + 3) / 4 : 0)) * sizeof(float);
+  return (R * d.da + 2 * R * wmax + 64 + chunk_loss_partial_floats() + (R > (size_t)B || (d.te > 0 && d.pk > 0) ? (R * d.da + 3) / 4 : 0)) * sizeof(float);
 }
 
 void launch_head_state_branch(const HeadDims& d, const float* P, const float* states, int B, float* n0, float* xh0, float* rstd0, float* z1, float* dst, int ldd,
@@ -307,10 +325,12 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
   // draws (fv_head_set_flow_draws, training forms only): the state branch and the pooled copy run once per observation, their columns are copied to the rows of
   // draws 1 .. S - 1 and everything from fusion.0 on runs on R = S B head rows (every row its own dropout mask: the element index).  R == B: the launches as ever
   const int R = training ? head_rows(d, B) : B;
+  const bool zero_mask = !training && d.te > 0 && d.pk > 0;   // prefix-width head at inference: the mask columns are 0 (a training form reads launch_flow_prepare's)
   training &= 1;   // bit 0: dropout active; any non-zero value: actions stay in normalised space
   // cat = [ pooled | state branch ]: two writers of disjoint columns
   hipLaunchKernelGGL(copy_cols_kernel, dim3(cdiv((long)B * d.feat, 256)), blk, 0, s, pooled, d.feat, sv.cat, cw, B, d.feat);
   launch_head_state_branch(d, P, states, B, sv.n0, sv.xh0, sv.rstd0, sv.z1, sv.cat + d.feat, cw, s, io);
+  if (zero_mask) hipLaunchKernelGGL(zero_cols_kernel, dim3(cdiv((long)B * d.pk, 256)), blk, 0, s, sv.cat + (cw - d.pk), cw, B, d.pk);
   if (R > B) hipLaunchKernelGGL(draws_broadcast_kernel, dim3(cdiv((long)B * (d.feat + d.hid), 256), R / B - 1), blk, 0, s, sv.cat, cw, B, d.feat + d.hid);
   hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.fus, 4), cdiv(R, 8)), blk, 0, s, sv.cat, cw, P + ho.o[HP_FUS0_W], P + ho.o[HP_FUS0_B], sv.z2, d.fus, (float*)nullptr, R, d.fus, cw, 0, (const float*)nullptr, (const float*)nullptr);
   hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(R, 4)), blk, 0, s, sv.z2, d.fus, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], sv.n2, sv.xh2, sv.rstd2, R, d.fus,
@@ -327,7 +347,10 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
                          float* scratch, hipStream_t s, float* d_pooled, float loss_scale, const HeadLoss* hl) {
   if (!P || !saved || !G || !scratch) return fv_fail(FV_ERR_ARG, "head_backward: null pointer");
   const bool weighted = hl && hl->dim_w && hl->step_w;   // fv_head_set_loss_weights: every kind takes the chunked kernel's weighted instance
-  const bool chunked = hl && !grad_actions && (hl->kind != FV_LOSS_MSE || hl->pad || weighted);   // MSE without a mask or weights: mse_kernel, for any chunk length
+  const bool prefix = d.te > 0 && d.pk > 0;   // fv_head_set_flow_prefix: the conditioned steps are masked out of the loss, so the fused loss is always the chunked kernel
+  if (prefix && !grad_actions && (!hl || hl->chunk != d.pk))
+    return fv_fail(FV_ERR_STATE, "head_backward: prefix mode needs the loss's chunk length (fv_head_set_loss) to be the prefix's, %d", d.pk);
+  const bool chunked = hl && !grad_actions && (hl->kind != FV_LOSS_MSE || hl->pad || weighted || prefix);   // MSE without a mask or weights: mse_kernel, for any chunk length
   if (chunked && (!hl->metrics || hl->chunk < 1 || d.da % hl->chunk)) return fv_fail(FV_ERR_ARG, "head_backward: chunked loss needs metrics and a chunk length that divides action_dim");
   if (!grad_actions && (!actions || !targets || !loss)) return fv_fail(FV_ERR_ARG, "head_backward: need grad_actions or (actions, targets, loss)");
   if (B <= 0) return fv_fail(FV_ERR_ARG, "head_backward: B must be positive");
@@ -349,14 +372,19 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   if (!ga && chunked) {
     float* part = g2 + (size_t)B * wmax + 16;   // behind everything the layers below use; the 64 floats of slack cover the rounding of B * da and this gap (head_bwd_scratch_bytes)
     const uint8_t* pad = hl->pad;
-    if (S > 1 && pad) {   // the mask is (obs, K): every draw of an observation reads its row, from a copy per draw behind the partials
+    if (prefix) {   // pad[r % obs] | m[r], built where the draws' copy of the mask goes
+      uint8_t* rep = reinterpret_cast<uint8_t*>(part + chunk_loss_partial_floats());
+      const long nk = (long)obs * hl->chunk;
+      hipLaunchKernelGGL(prefix_loss_mask_kernel, dim3(cdiv(nk * S, 256)), blk, 0, s, pad, sv.pmask, rep, nk * S, nk);
+      pad = rep;
+    } else if (S > 1 && pad) {   // the mask is (obs, K): every draw of an observation reads its row, from a copy per draw behind the partials
       uint8_t* rep = reinterpret_cast<uint8_t*>(part + chunk_loss_partial_floats());
       const long nk = (long)obs * hl->chunk;
       hipLaunchKernelGGL(draws_pad_kernel, dim3(cdiv(nk, 256)), blk, 0, s, pad, rep, nk, S);
       pad = rep;
     }
     const int rc = launch_chunk_loss(actions, targets, pad, ga_own, part, loss, hl->metrics, (long)B * d.da, d.da / hl->chunk, hl->kind, hl->beta, loss_scale, s,
-                                     weighted ? hl->dim_w : nullptr, weighted ? hl->step_w : nullptr, hl->chunk);
+                                     weighted ? hl->dim_w : nullptr, weighted ? hl->step_w : nullptr, hl->chunk, prefix);
     if (rc != FV_OK) return rc;
     ga = ga_own;
   } else if (!ga) {

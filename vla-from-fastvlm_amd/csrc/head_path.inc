@@ -105,7 +105,7 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   }
   // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
   if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
-  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
+  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->hd.pk = h->hd.pd = 0; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
   const int half = spec->time_dim / 2;
   std::vector<float> fr(half);   // 2 pi / p_j, p_j geometric from min_period to max_period; in double, rounded once
   for (int j = 0; j < half; ++j) {
@@ -116,7 +116,31 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   FV_TRY(head_upload(h, &h->flow_freq_buf, grow, fr.data(), (size_t)half));
   if (grow) h->flow_freq_cap = half;
   h->hd.te = spec->time_dim;
-  h->flow = fv::HeadFlow{h->flow_freq_buf, spec->time_dist, spec->dist_a, spec->dist_b};
+  h->flow = fv::HeadFlow{h->flow_freq_buf, spec->time_dist, spec->dist_a, spec->dist_b, h->hd.pk > 0 ? h->prefix_thr_buf : nullptr};
+  return FV_OK;
+}
+
+int fv_head_set_flow_prefix(fv_handle* h, int chunk, int max_delay, const uint32_t* thresholds_host) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_prefix: the head is not in flow mode (fv_head_set_flow)");
+  // fusion.0's width, the saved activations, the workspace plan and the training layouts all depend on the mode
+  if (h->ws || h->train.ready || h->train.tower)
+    return fv_fail(FV_ERR_STATE, "fv_head_set_flow_prefix: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
+  if (!thresholds_host) { h->hd.pk = h->hd.pd = 0; h->flow.thr = nullptr; return FV_OK; }
+  if (chunk < 2 || h->hd.da % chunk) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_prefix: chunk=%d must be >= 2 and divide action_dim=%d", chunk, h->hd.da);
+  if (max_delay < 1 || max_delay > chunk - 1) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_prefix: max_delay=%d outside 1 .. chunk - 1 = %d", max_delay, chunk - 1);
+  for (int j = 0; j <= max_delay; ++j)
+    if (thresholds_host[j] > (1u << 24) || (j > 0 && thresholds_host[j] < thresholds_host[j - 1]))
+      return fv_fail(FV_ERR_ARG, "fv_head_set_flow_prefix: thresholds must be non-decreasing and at most 2^24 (entry %d = %u)", j, thresholds_host[j]);
+  if (thresholds_host[max_delay] != (1u << 24)) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_prefix: the last threshold must be 2^24, got %u", thresholds_host[max_delay]);
+  const bool grow = h->prefix_thr_cap < max_delay + 1;   // (a longer table allocates anew; toggling the mode does not grow the handle)
+  static_assert(sizeof(uint32_t) == sizeof(float), "head_upload copies 4-byte words");
+  FV_TRY(head_upload(h, reinterpret_cast<float**>(&h->prefix_thr_buf), grow, reinterpret_cast<const float*>(thresholds_host), (size_t)max_delay + 1));
+  if (grow) h->prefix_thr_cap = max_delay + 1;
+  h->hd.pk = chunk;
+  h->hd.pd = max_delay;
+  h->flow.thr = h->prefix_thr_buf;
   return FV_OK;
 }
 
@@ -139,6 +163,16 @@ int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t see
   return fv::launch_flow_prepare(h->hd, h->flow, targets, B, seed, offset, noise, t, static_cast<float*>(saved), u_out, static_cast<hipStream_t>(s));
 }
 
+int fv_head_flow_prepare_prefix(fv_handle* h, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t, const int32_t* delays,
+                                void* saved, float* u_out, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_prepare_prefix: the head is not in flow mode (fv_head_set_flow)");
+  if (h->hd.pk <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_prepare_prefix: prefix mode is off (fv_head_set_flow_prefix)");
+  if (!delays) return fv_fail(FV_ERR_ARG, "fv_head_flow_prepare_prefix: null delays (fv_head_flow_prepare draws them)");
+  return fv::launch_flow_prepare(h->hd, h->flow, targets, B, seed, offset, noise, t, static_cast<float*>(saved), u_out, static_cast<hipStream_t>(s), delays);
+}
+
 int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                         uint64_t seed, uint64_t offset, float* actions, fv_stream s) {
   HandleScope _hs(h);
@@ -152,6 +186,27 @@ int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* poo
   hipStream_t st = static_cast<hipStream_t>(s);
   prof_begin(h, FV_FAM_HEAD, 2.0 * B * n_steps * head_param_count(h), 4.0 * n_steps * head_param_count(h), st);
   const int rc = fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr);
+  prof_end(h, st);
+  return rc;
+}
+
+int fv_head_flow_sample_prefix(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                               uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out,
+                               fv_stream s) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_prefix: the head is not in flow mode (fv_head_set_flow)");
+  if (h->hd.pk <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_prefix: prefix mode is off (fv_head_set_flow_prefix)");
+  if (!flat_params || !pooled || !states || !prev || !delays || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: null pointer");
+  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: n_steps = %d must be >= 1", n_steps);
+  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
+  if (shift < 0 || shift > h->hd.pk) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: shift = %d outside 0 .. chunk = %d", shift, h->hd.pk);
+  float* scr = nullptr;
+  FV_TRY(head_scratch(h, B, "workspace too small for the flow sampler", &scr));
+  hipStream_t st = static_cast<hipStream_t>(s);
+  prof_begin(h, FV_FAM_HEAD, 2.0 * B * n_steps * head_param_count(h), 4.0 * n_steps * head_param_count(h), st);
+  const int rc = fv::launch_flow_sample_prefix(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, delays, actions, chunk_out, scr, st,
+                                               h->has_io ? &h->io : nullptr);
   prof_end(h, st);
   return rc;
 }

@@ -293,8 +293,10 @@ int launch_attention_split_bwd(const float* qkv, int ld, const bf16_t* o_hi, con
 // flow mode (fv_head_set_flow): fusion.0 reads te + da more columns, cat = [ pooled | state branch | x_t (da) | phi(t) (te) ]; te == 0: the regression head
 // draws (fv_head_set_flow_draws, flow mode only): S noise draws per observation in the training forms.  Head rows are draw-major, r = s B + b: the state branch
 // keeps B rows, everything from cat on has S B.  1: the head as ever
-struct HeadDims { int feat, ds, da, hid, fus; int te = 0; int draws = 1; };
-inline int head_cat_width(const HeadDims& d) { return d.feat + d.hid + (d.te > 0 ? d.da + d.te : 0); }
+// prefix mode (fv_head_set_flow_prefix, flow mode only): pk = K > 0 mask columns m behind phi(t), m[k] = 1 for the k < d steps of the chunk that are given to
+// the network clean (d <= pd = D, the largest delay); `saved` also keeps the (head rows, K) byte mask the loss reads.  pk == 0: the flow head as ever
+struct HeadDims { int feat, ds, da, hid, fus; int te = 0; int draws = 1; int pk = 0; int pd = 0; };
+inline int head_cat_width(const HeadDims& d) { return d.feat + d.hid + (d.te > 0 ? d.da + d.te + d.pk : 0); }
 inline int head_rows(const HeadDims& d, int B) { return d.te > 0 && d.draws > 1 ? d.draws * B : B; }
 // the 12 parameter tensors in the flat buffer's order (head_offsets; fv_head_layout's offsets[13] and Python's head_views are the same order), then the total
 enum HeadParam {
@@ -309,7 +311,9 @@ enum HeadParam {
 struct HeadOffsets { int64_t o[HP_TOTAL + 1]; };
 HeadOffsets head_offsets(const HeadDims& d);
 size_t head_saved_bytes(const HeadDims& d, int B);
+size_t head_saved_cat_offset(const HeadDims& d, int B);   // floats from the start of `saved` to its (head_rows(d, B), head_cat_width(d)) matrix `cat` (the test-only ops hand it out)
 // (the two launchers that only the head's own translation units call stay out of the library's dynamic symbol table)
+__attribute__((visibility("hidden"))) uint8_t* head_saved_prefix_mask(const HeadDims& d, int B, float* saved);   // prefix mode: the (head_rows(d, B), pk) byte mask inside `saved`, 1 = the step is conditioned on and does not train
 __attribute__((visibility("hidden"))) float* head_saved_cat(const HeadDims& d, int B, float* saved);   // the (head_rows(d, B), head_cat_width(d)) matrix `cat` inside `saved` (launch_flow_prepare writes its x_t and phi(t) columns)
 inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }   // grid sizes of the head, chunk, flow and optimiser launchers
 // dataset normalisation folded into the head (device vectors; LeRobot MEAN_STD): states <- (states - state_mean) * state_istd
@@ -335,16 +339,24 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
                          const struct HeadLoss* hl = nullptr);
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
 // ---- flow-matching head (d.te > 0).  freq: te / 2 device floats, 2 pi / period_j.  time_dist 0: t ~ U[0, 1); 1: t = sigmoid(dist_a + dist_b n)
-struct HeadFlow { const float* freq; int time_dist; float dist_a, dist_b; };
+// thr (prefix mode): pd + 1 device uint32, the cumulative delay distribution in units of 2^-24 (the last one is 2^24)
+struct HeadFlow { const float* freq; int time_dist; float dist_a, dist_b; const uint32_t* thr = nullptr; };
 // one launch: draws (or reads) t per row and noise per element, writes x_t and phi(t) into their columns of saved's cat and u = noise - targets into u_out.
 // d.draws = S > 1: targets (B, da) stay per observation; head row s B + b draws what row b draws at offset + (s << 56); noise, t and u_out have S B rows.
 // FV_ERR_ARG, nothing enqueued, when S > 1 and any of bits 56 .. 59 of the offset is set
+// prefix mode (d.pk > 0): the PREFIX instance -- row r's delay is delays[r] clamped to 0 .. pd (device int32, S B of them) or, with delays == null, drawn from
+// word z of the group-0 Philox block that yields t; the first d steps of x_t are COPIES of targets, m and the row's byte mask in `saved` are written too
 int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
-                        float* saved, float* u_out, hipStream_t s);
+                        float* saved, float* u_out, hipStream_t s, const int32_t* delays = nullptr);
 // the Euler sampler: conditioning once, then three launches per step.  scratch: flow_sample_scratch_bytes(d, B)
 size_t flow_sample_scratch_bytes(const HeadDims& d, int B);
 int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                        uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io);
+// the prefix sampler (d.pk > 0): row b's first min(delays[b], pd, pk - shift) steps are pinned to prev[b][k + shift] (normalised) from the start to the end; the
+// mask block of fusion.0 joins c once per call; three launches per step as launch_flow_sample, step C in its PREFIX instance.  Same scratch
+int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                              uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out, float* scratch,
+                              hipStream_t s, const HeadIoNorm* io);
 // guided sampling (fv_head_set_flow_guidance): step_w = chunk device floats >= 0, beta the largest guidance weight, live_steps = 1 + the last step whose
 // weight is not 0 (0: none).  prev (B, da): the previous chunk, normalised; Y[b][k] = prev[b][k + shift]; row_mask (B) int32 or null; chunk_out (B, da) or null:
 // the final normalised x_0.  A row with all-zero omega comes out as launch_flow_sample's row, bit for bit.  scratch: flow_guided_scratch_bytes(d, B)
@@ -360,7 +372,8 @@ int launch_flow_vjp(const HeadDims& d, const HeadFlow& f, const float* P, const 
 // chunk_loss_partial_floats() floats of scratch, loss 1 float, metrics 2 floats
 size_t chunk_loss_partial_floats();
 int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* g, float* partial, float* loss, float* metrics, long n, int A, int kind,
-                      float beta, float loss_scale, hipStream_t s, const float* dim_w = nullptr, const float* step_w = nullptr, int K = 1);
+                      float beta, float loss_scale, hipStream_t s, const float* dim_w = nullptr, const float* step_w = nullptr, int K = 1,
+                      int prefix = 0);   // prefix != 0: a pad byte of 2 marks a step masked by the action prefix alone -- masked like a padded one, but counted as valid
 // mean |a - t| per action dimension over the non-padded steps: a, t (rows, A) f32 with rows = B K, pad (rows) bytes or null -> out (A), 0 for a dimension
 // without a valid step.  One block per dimension, fixed-order sums
 // pad_rows (0: rows): the mask has fewer rows than a, t and row r reads pad[r % pad_rows] -- the draws of a flow head share their observation's mask

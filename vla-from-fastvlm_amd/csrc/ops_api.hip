@@ -344,4 +344,32 @@ int fv_op_flow_vjp(int feat, int ds, int da, int hid, int fus, int time_dim, con
   return fv::launch_flow_vjp(d, fv::HeadFlow{freq, 0, 0.f, 0.f}, P, pooled, states, B, x, t, omega, v_out, jt_out, scratch, static_cast<hipStream_t>(s));
 }
 
+// fv_op_flow_vjp on a prefix-width head (fv_head_set_flow_prefix): fusion.0 has prefix_chunk more columns behind phi(t), which the chain never reads (m = 0)
+int fv_op_flow_vjp_prefix(int feat, int ds, int da, int hid, int fus, int time_dim, int prefix_chunk, const float* freq, const float* P, const float* pooled,
+                          const float* states, int B, const float* x, float t, const float* omega, float* v_out, float* jt_out, float* scratch, size_t scratch_floats,
+                          fv_stream s) {
+  if (feat < 1 || ds < 1 || da < 1 || hid < 1 || fus < 1 || time_dim < 2 || time_dim % 2 || B < 1) return fv_fail(FV_ERR_ARG, "fv_op_flow_vjp_prefix: bad dimensions");
+  if (prefix_chunk < 2 || da % prefix_chunk) return fv_fail(FV_ERR_ARG, "fv_op_flow_vjp_prefix: prefix_chunk=%d must be >= 2 and divide da=%d", prefix_chunk, da);
+  fv::HeadDims d{feat, ds, da, hid, fus};
+  d.te = time_dim;
+  d.pk = prefix_chunk;
+  d.pd = 1;
+  if (scratch_floats * sizeof(float) < fv::flow_guided_scratch_bytes(d, B))
+    return fv_fail(FV_ERR_ARG, "fv_op_flow_vjp_prefix: scratch needs %zu floats", fv::flow_guided_scratch_bytes(d, B) / sizeof(float));
+  return fv::launch_flow_vjp(d, fv::HeadFlow{freq, 0, 0.f, 0.f}, P, pooled, states, B, x, t, omega, v_out, jt_out, scratch, static_cast<hipStream_t>(s));
+}
+
+// where fusion.0's input `cat` lies inside the saved activations of a head with these dimensions (time_dim 0: the regression head; draws, prefix_chunk as
+// fv_head_set_flow_draws / fv_head_set_flow_prefix set them, 1 / 0 = off): *out_floats = its offset in floats; its shape is (draws * B, cat width)
+int fv_op_head_saved_cat_offset(int feat, int ds, int da, int hid, int fus, int time_dim, int draws, int prefix_chunk, int B, size_t* out_floats) {
+  if (!out_floats || feat < 1 || ds < 1 || da < 1 || hid < 1 || fus < 1 || time_dim < 0 || draws < 1 || draws > 16 || prefix_chunk < 0 || B < 1)
+    return fv_fail(FV_ERR_ARG, "fv_op_head_saved_cat_offset: bad arguments");
+  fv::HeadDims d{feat, ds, da, hid, fus};
+  d.te = time_dim;
+  d.draws = draws;
+  d.pk = time_dim > 0 ? prefix_chunk : 0;
+  *out_floats = fv::head_saved_cat_offset(d, B);
+  return FV_OK;
+}
+
 }  // extern "C"

@@ -138,6 +138,9 @@ SIGNATURES = {
     "fv_head_flow_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _vp]),
     "fv_head_set_flow_guidance": (_i, [_vp, _i, C.POINTER(_f), _f]),
     "fv_head_flow_sample_guided": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fv_head_set_flow_prefix": (_i, [_vp, _i, _i, C.POINTER(C.c_uint32)]),
+    "fv_head_flow_prepare_prefix": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "fv_head_flow_sample_prefix": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _i, _vp, _vp, _vp, _vp]),
     "fv_ensemble_create": (_i, [_vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "fv_ensemble_destroy": (_i, [_vp, _vp]),
     "fv_ensemble_reset": (_i, [_vp, _vp, _i, _vp]),
@@ -225,6 +228,8 @@ OPS_SIGNATURES = {
     "fv_op_head_loss_backward": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "fv_op_head_loss_backward_draws": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "fv_op_flow_vjp": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fv_op_flow_vjp_prefix": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fv_op_head_saved_cat_offset": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 

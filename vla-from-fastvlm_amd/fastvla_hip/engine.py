@@ -174,6 +174,7 @@ class FastVLAEngine:
         self.head_flow: Optional[dict] = None                     # set_head_flow: None = the regression head
         self.head_flow_guidance: Optional[dict] = None            # set_head_flow_guidance: None = the unguided sampler only
         self.head_flow_draws = 1                                  # set_head_flow_draws: noise draws per observation in the training forms
+        self.head_flow_prefix: Optional[dict] = None              # set_head_flow_prefix: None = no action-prefix conditioning
         self.loaded = False
 
     def close(self):
@@ -564,9 +565,10 @@ class FastVLAEngine:
         return out
 
     def head_cat_width(self) -> int:
-        """columns of fusion.0.weight: feat + hid, and in flow mode da + time_dim more (x_t and phi(t) come last)"""
+        """columns of fusion.0.weight: feat + hid, in flow mode da + time_dim more (x_t and phi(t)), in prefix mode `chunk` mask columns behind them"""
         hd = self.head_dims
-        return hd["feat"] + hd["hid"] + (hd["da"] + self.head_flow["time_dim"] if self.head_flow else 0)
+        pk = self.head_flow_prefix["chunk"] if self.head_flow_prefix else 0
+        return hd["feat"] + hd["hid"] + (hd["da"] + self.head_flow["time_dim"] + pk if self.head_flow else 0)
 
     # ---------------------------------------------------------------- flow-matching head
     def set_head_flow(self, time_dim: Optional[int] = 64, min_period: float = 4e-3, max_period: float = 4.0, time_dist: str = "uniform",
@@ -577,6 +579,7 @@ class FastVLAEngine:
             _lib.check(self.lib.fv_head_set_flow(self.h, None), "fv_head_set_flow", self.h)
             self.head_flow = None
             self.head_flow_draws = 1
+            self.head_flow_prefix = None
         else:
             if time_dist not in _lib.FLOW_TIME_DISTS:
                 raise ValueError(f"flow time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {time_dist!r}")
@@ -585,9 +588,35 @@ class FastVLAEngine:
                 _lib.check(self.lib.fv_head_set_flow(self.h, C.byref(spec)), "fv_head_set_flow", self.h)
             self.head_flow = dict(time_dim=int(time_dim), min_period=float(min_period), max_period=float(max_period), time_dist=time_dist,
                                   dist_a=float(dist_a), dist_b=float(dist_b))
+        self._refresh_head_layout()
+
+    def _refresh_head_layout(self) -> None:
         offs = (C.c_int64 * 13)()
         _lib.check(self.lib.fv_head_layout(self.h, C.byref(offs)), "fv_head_layout")
         self.head_offsets = list(offs)
+
+    def set_head_flow_prefix(self, chunk: Optional[int] = None, max_delay: int = 0, thresholds=None, dist: str = "uniform", rate: float = 0.0) -> None:
+        """Action-prefix conditioning of the flow head (fv_head_set_flow_prefix): fusion.0 reads `chunk` mask columns behind phi(t); training gives the first
+        d <= max_delay steps of a chunk to the network clean and keeps them out of the loss, head_flow_sample_prefix pins them at inference.  thresholds:
+        max_delay + 1 integers (fastvla_hip.prefix.delay_thresholds; None builds them from dist / rate).  chunk None switches the mode off.  Flow mode only,
+        before the first workspace is bound and before any train_*begin (the library answers FV_ERR_STATE otherwise)."""
+        if chunk is None:
+            _lib.check(self.lib.fv_head_set_flow_prefix(self.h, 0, 0, None), "fv_head_set_flow_prefix", self.h)
+            self.head_flow_prefix = None
+        else:
+            from . import prefix as _prefix
+            if thresholds is None:
+                thresholds = _prefix.delay_thresholds(int(max_delay), dist, rate)
+            thr = [int(x) for x in thresholds]
+            if len(thr) != int(max_delay) + 1:
+                raise ValueError(f"flow prefix thresholds must hold max_delay + 1 = {int(max_delay) + 1} integers, got {len(thr)}")
+            if any(x < 0 or x > 1 << 24 for x in thr):
+                raise ValueError("flow prefix thresholds must lie in 0 .. 2^24")
+            arr = (C.c_uint32 * len(thr))(*thr)
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.fv_head_set_flow_prefix(self.h, int(chunk), int(max_delay), arr), "fv_head_set_flow_prefix", self.h)
+            self.head_flow_prefix = dict(chunk=int(chunk), max_delay=int(max_delay), thresholds=thr, dist=dist, rate=float(rate))
+        self._refresh_head_layout()
 
     def set_head_flow_draws(self, draws: int = 1) -> None:
         """S = draws noise draws per observation in one training step (fv_head_set_flow_draws; 1 .. 16, 1 = off): the mean loss and gradient of S single-draw
@@ -599,10 +628,11 @@ class FastVLAEngine:
         self.head_flow_draws = draws
 
     def head_flow_prepare(self, targets: torch.Tensor, saved: torch.Tensor, *, seed: int = 0, offset: int = 0, noise: Optional[torch.Tensor] = None,
-                          t: Optional[torch.Tensor] = None) -> torch.Tensor:
+                          t: Optional[torch.Tensor] = None, delays: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> u = eps - targets (B, da); x_t and phi(t) land in `saved` (head_saved(B)), which the following head_forward(saved=saved) reads
         (fv_head_flow_prepare).  noise (B, da) / t (B) replace the draws of (seed, offset).  With set_head_flow_draws(S): targets stay (B, da); noise, t and
-        the returned u have S B rows, draw-major."""
+        the returned u have S B rows, draw-major.  Prefix mode (set_head_flow_prefix): delays (draws * B) int32 replace the drawn delays
+        (fv_head_flow_prepare_prefix; the kernel clamps them to 0 .. max_delay)."""
         B, da = targets.shape[0], self.head_dims["da"]
         R = B * self.head_flow_draws
         targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
@@ -617,6 +647,13 @@ class FastVLAEngine:
             if t.numel() != R:
                 raise ValueError(f"t must hold draws * B = {R} elements, got {tuple(t.shape)}")
         u = torch.empty(R, da, dtype=torch.float32, device=self.device)
+        if delays is not None:
+            delays = torch.as_tensor(delays).to(device=self.device, dtype=torch.int32).contiguous()
+            if delays.numel() != R:
+                raise ValueError(f"delays must hold draws * B = {R} elements, got {tuple(delays.shape)}")
+            _lib.check(self.lib.fv_head_flow_prepare_prefix(self.h, targets.data_ptr(), B, seed, offset, _ptr(noise), _ptr(t), delays.data_ptr(), saved.data_ptr(),
+                                                            u.data_ptr(), _stream()), "fv_head_flow_prepare_prefix", self.h)
+            return u
         _lib.check(self.lib.fv_head_flow_prepare(self.h, targets.data_ptr(), B, seed, offset, _ptr(noise), _ptr(t), saved.data_ptr(), u.data_ptr(), _stream()),
                    "fv_head_flow_prepare", self.h)
         return u
@@ -687,6 +724,38 @@ class FastVLAEngine:
                    "fv_head_flow_sample_guided", self.h)
         return actions, chunk_out
 
+    def head_flow_sample_prefix(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, prev: torch.Tensor, delays: torch.Tensor, *,
+                                shift: int = 0, steps: int = 10, noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
+                                chunk_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (actions (B, da), chunk (B, da)): head_flow_sample with row b's first min(delays[b], max_delay, chunk - shift) steps pinned to `prev` (B, da), the
+        previous chunk in normalised space, read `shift` steps ahead (fv_head_flow_sample_prefix).  delays (B) int32, 0 pins nothing.  chunk: the final
+        normalised x_0, the next call's `prev` (written into chunk_out when one is handed in)."""
+        B, da = pooled.shape[0], self.head_dims["da"]
+        states = states.to(device=self.device, dtype=torch.float32).contiguous()
+        pooled = pooled.contiguous()
+        if states.shape != (B, self.head_dims["ds"]):
+            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        prev = prev.to(device=self.device, dtype=torch.float32).contiguous()
+        if prev.numel() != B * da:
+            raise ValueError(f"prev must hold (B, {da}) elements, got {tuple(prev.shape)}")
+        delays = torch.as_tensor(delays).to(device=self.device, dtype=torch.int32).contiguous()
+        if delays.numel() != B:
+            raise ValueError(f"delays must hold B = {B} elements, got {tuple(delays.shape)}")
+        if noise is not None:
+            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
+            if noise.numel() != B * da:
+                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
+        if chunk_out is None:
+            chunk_out = torch.empty(B, da, dtype=torch.float32, device=self.device)
+        elif chunk_out.dtype != torch.float32 or not chunk_out.is_contiguous() or chunk_out.numel() != B * da or chunk_out.device != prev.device:
+            raise ValueError(f"chunk_out must be a contiguous float32 (B, {da}) tensor on {self.device}")
+        self.ensure_workspace(B, 1, False)
+        actions = torch.empty(B, da, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.fv_head_flow_sample_prefix(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed,
+                                                       offset, prev.data_ptr(), int(shift), delays.data_ptr(), actions.data_ptr(), chunk_out.data_ptr(), _stream()),
+                   "fv_head_flow_sample_prefix", self.h)
+        return actions, chunk_out
+
     def head_saved(self, B: int) -> torch.Tensor:
         n = C.c_size_t()
         _lib.check(self.lib.fv_head_saved_bytes(self.h, B, C.byref(n)), "fv_head_saved_bytes")
@@ -744,7 +813,7 @@ class FastVLAEngine:
 
     def loss_is_chunked(self, pad) -> bool:
         """whether a loss evaluation with this mask runs the chunked kernel (and writes head_loss_metrics) or the plain MSE kernel"""
-        return pad is not None or self.head_loss["kind"] != "mse" or self.head_loss_weights is not None
+        return pad is not None or self.head_loss["kind"] != "mse" or self.head_loss_weights is not None or self.head_flow_prefix is not None
 
     def set_head_loss_weights(self, dim_w=None, step_w=None) -> None:
         """Per-dimension (A = action_dim / chunk) and per-step (K = chunk) weights of the loss (fv_head_set_loss_weights): either may be None = ones, both

@@ -93,3 +93,18 @@ class RealTimeChunker:
         self.prev, self._next = self._next, self.prev
         self.has_prev.fill_(1)
         return actions
+
+    def sample_prefix(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, *, shift: int, delay: int, steps: int,
+                      noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0, prev: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> actions (n_env, da): the prefix sampler (fv_head_flow_sample_prefix; a head trained with set_head_flow_prefix) in place of the guided one.  Every
+        row pins its first min(delay, max_delay, K - shift) steps to the kept chunk read `shift` steps ahead; the row mask becomes per-row delays, so a
+        row without a previous chunk has delay 0 and pins nothing.  prev: an explicit previous chunk for every row, as in sample()"""
+        if pooled.shape[0] != self.n_env:
+            raise ValueError(f"this chunker holds {self.n_env} environments, the batch has {pooled.shape[0]}")
+        explicit = prev is not None
+        delays = torch.full_like(self.has_prev, int(delay)) if explicit else self.has_prev * int(delay)      # (device arithmetic: no host synchronisation)
+        actions, _ = self._engine.head_flow_sample_prefix(flat_params, pooled, states, prev if explicit else self.prev, delays, shift=shift, steps=steps,
+                                                          noise=noise, seed=seed, offset=offset, chunk_out=self._next)
+        self.prev, self._next = self._next, self.prev
+        self.has_prev.fill_(1)
+        return actions

@@ -103,13 +103,15 @@ class _FlowLossFunction(torch.autograd.Function):
 
 class FastVLMWithExpert(nn.Module):
     def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0, flow: Optional[dict] = None,
-                 flow_steps: int = 10, flow_seed: Optional[int] = None, flow_noise_draws: int = 1) -> None:
+                 flow_steps: int = 10, flow_seed: Optional[int] = None, flow_noise_draws: int = 1, flow_prefix: Optional[dict] = None) -> None:
         """chunk_size = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
         `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library.
         flow = FastVLAEngine.set_head_flow's keyword arguments: the flow-matching head -- fusion.0 reads K * A + time_dim more columns (x_t and phi(t)),
         head() samples with flow_steps Euler steps, head_loss() noises its targets and returns the predicted velocity.  flow_seed: the noise streams' seed
         (default: torch's initial seed, as the dropout stream's).  flow_noise_draws = S (1 .. 16): S noise draws (t, eps) per observation wherever targets are
-        noised -- draw s of a call at offset o is the single draw of offset o + (s << 56); the velocity handed out is draw 0's."""
+        noised -- draw s of a call at offset o is the single draw of offset o + (s << 56); the velocity handed out is draw 0's.
+        flow_prefix = fastvla_hip.prefix.check_prefix_config's result (flow head, K > 1): action-prefix conditioning -- fusion.0 reads K mask columns behind
+        phi(t), training gives the first d <= max_delay steps of a chunk to the network clean and keeps them out of the loss, rtc_sample pins them."""
         super().__init__()
         from fastvla_hip.engine import check_flow_draws, check_head_loss
         self.flow_noise_draws = check_flow_draws(flow_noise_draws)
@@ -126,10 +128,14 @@ class FastVLMWithExpert(nn.Module):
         self.flow: Optional[dict] = None if flow is None else dict(flow)
         self.flow_steps = int(flow_steps)
         self.backbone.configure_head_flow(self.flow)
+        if flow_prefix is not None and (flow is None or int(flow_prefix["chunk"]) != self.chunk_size):
+            raise ValueError(f"flow_prefix_max_delay={flow_prefix.get('max_delay')} needs action_head='flow' and the head's chunk_size={self.chunk_size}")
+        self.flow_prefix: Optional[dict] = None if flow_prefix is None else dict(flow_prefix)
+        self.backbone.configure_head_flow_prefix(self.flow_prefix)
         self.backbone.configure_head_flow_draws(self.flow_noise_draws)
         self.rtc: Optional[dict] = None      # configure_rtc: real-time chunking of the flow sampler, a property of the run
         self._chunker = self._rtc_key = None
-        extra = self.head_width + int(self.flow["time_dim"]) if self.flow else 0
+        extra = self.head_width + int(self.flow["time_dim"]) + (self.chunk_size if self.flow_prefix else 0) if self.flow else 0
         # same module tree / init as the reference so checkpoints and seeds line up
         self.state_projection = nn.Sequential(nn.LayerNorm(config.state_dim), nn.Linear(config.state_dim, config.hidden_dim), nn.SiLU())
         self.fusion = nn.Sequential(
@@ -183,8 +189,9 @@ class FastVLMWithExpert(nn.Module):
         """hip_extras.json "action_head": there only in flow mode"""
         if self.flow is None:
             return None
+        from fastvla_hip import prefix as _prefix
         return {"type": "flow", "steps": int(self.flow_steps), **{k: self.flow[k] for k in ("time_dim", "min_period", "max_period", "time_dist", "dist_a", "dist_b")},
-                "seed": int(self._flow_seed)}
+                "seed": int(self._flow_seed), **_prefix.extras_record(self.flow_prefix)}
 
     # ------------------------------------------------------------------ flat parameter storage
     def head_parameters(self):
@@ -326,6 +333,12 @@ class FastVLMWithExpert(nn.Module):
         from fastvla_hip.rtc import prefix_weights
         self.rtc = None if rtc is None else dict(rtc)
         self._chunker = None
+        if rtc is not None and rtc.get("method") == "prefix":      # the prefix sampler: no guidance, no weights, nothing to configure on the engine
+            if self.flow_prefix is None:
+                raise ValueError("rtc_method='prefix' needs a head trained with flow_prefix_max_delay")
+            self._rtc_key = None
+            self.backbone.configure_head_flow_guidance(None)
+            return
         self._rtc_key = None if rtc is None else (0, int(rtc["execution_horizon"]))
         self.backbone.configure_head_flow_guidance(
             None if rtc is None else dict(step_weights=prefix_weights(self.chunk_size, 0, rtc["execution_horizon"], rtc["schedule"]),
@@ -339,7 +352,7 @@ class FastVLMWithExpert(nn.Module):
         if ck is None or ck._engine is not eng:      # (the first call after construction, or the engine was rebuilt underneath)
             fresh = ck is not None      # (a rebuilt engine holds the weights the backbone configured it with: delay 0, the policy's horizon)
             ck = self._chunker = RealTimeChunker(eng, n_env)
-            if fresh:
+            if fresh and self.rtc.get("method") != "prefix":
                 self._rtc_key = (0, int(self.rtc["execution_horizon"]))
         return ck
 
@@ -354,10 +367,11 @@ class FastVLMWithExpert(nn.Module):
         ck = getattr(self, "_chunker", None)
         return None if ck is None else ck.prev.view(ck.n_env, self.chunk_size, self.config.action_dim).clone()
 
-    def rtc_sample(self, pooled: torch.Tensor, states: torch.Tensor, *, shift: int = 0, inference_delay: int = 0, execution_horizon: Optional[int] = None,
-                   prev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def rtc_sample(self, pooled: torch.Tensor, states: torch.Tensor, *, shift: int = 0, inference_delay: Optional[int] = None,
+                   execution_horizon: Optional[int] = None, prev: Optional[torch.Tensor] = None) -> torch.Tensor:
         """-> (B, K, A): the flow sampler guided by the previous chunk read `shift` steps ahead -- the chunker's own (rows without one are sampled unguided),
-        or `prev` (B, K, A) / (B, K * A), normalised, for every row."""
+        or `prev` (B, K, A) / (B, K * A), normalised, for every row.  rtc_method="prefix": the prefix sampler instead -- the first
+        min(inference_delay, max_delay, K - shift) steps are PINNED to the previous chunk (inference_delay None: the policy's rtc_prefix_steps)."""
         from fastvla_hip.rtc import check_rtc, prefix_weights
         if getattr(self, "rtc", None) is None:
             raise RuntimeError("real-time chunking is off: construct the policy with rtc=True")
@@ -366,10 +380,23 @@ class FastVLMWithExpert(nn.Module):
         if states.ndim != 2 or states.shape[1] != self.config.state_dim:
             raise ValueError(f"states must be (B,{self.config.state_dim}), got {tuple(states.shape)}")
         K = self.chunk_size
-        s = self.rtc["execution_horizon"] if execution_horizon is None else execution_horizon
-        _, d, s = check_rtc(K, inference_delay, s, self.rtc["schedule"])
         if isinstance(shift, bool) or int(shift) != shift or not 0 <= int(shift) <= K:
             raise ValueError(f"shift must be an integer in 0 .. chunk_size = {K}, got {shift!r}")
+        if self.rtc.get("method") == "prefix":
+            from fastvla_hip.prefix import check_inference_delay
+            if execution_horizon is not None:
+                raise ValueError(f"execution_horizon belongs to rtc_method='guidance'. Got execution_horizon={execution_horizon}, rtc_method='prefix'.")
+            d = self.rtc["prefix_steps"] if inference_delay is None else check_inference_delay(inference_delay, self.flow_prefix["max_delay"])
+            ck = self._rtc_chunker(pooled.shape[0])
+            if prev is not None:
+                prev = prev.to(pooled.device, torch.float32).reshape(pooled.shape[0], -1)
+                if prev.shape[1] != self.head_width:
+                    raise ValueError(f"prev_chunk must hold (B, {K}, {self.config.action_dim}) elements, got {tuple(prev.shape)}")
+            seed, offset = self.flow_sample_draw()
+            return self._shape_actions(ck.sample_prefix(self._flat, pooled, states, shift=int(shift), delay=d, steps=self.flow_steps, seed=seed, offset=offset,
+                                                        prev=prev))
+        s = self.rtc["execution_horizon"] if execution_horizon is None else execution_horizon
+        _, d, s = check_rtc(K, 0 if inference_delay is None else inference_delay, s, self.rtc["schedule"])
         ck = self._rtc_chunker(pooled.shape[0])
         if (d, s) != self._rtc_key:      # (a configuration call: it synchronises the device)
             self._engine().set_head_flow_guidance(prefix_weights(K, d, s, self.rtc["schedule"]), self.rtc["max_guidance_weight"])

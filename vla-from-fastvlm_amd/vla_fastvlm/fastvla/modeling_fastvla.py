@@ -123,8 +123,41 @@ def resolve_flow_noise_draws(flow_noise_draws=None, *, action_head: str) -> int:
         raise ValueError(f"FASTVLA_FLOW_NOISE_DRAWS must be an integer 1 .. 16. Got FASTVLA_FLOW_NOISE_DRAWS={raw!r}, action_head={action_head!r}.") from None
 
 
+def resolve_prefix_options(flow_prefix_max_delay=None, flow_prefix_delay_dist=None, flow_prefix_delay_rate=None, *, action_head: str, chunk_size: int,
+                           temporal_ensemble_coeff=None) -> Optional[Dict]:
+    """-> fastvla_hip.prefix.check_prefix_config's record {"chunk", "max_delay", "dist", "rate", "thresholds"} or None (off): explicit arguments, else the
+    FASTVLA_FLOW_PREFIX_MAX_DELAY / _DELAY_DIST / _DELAY_RATE twins (read for a flow head only, like the other FASTVLA_FLOW_* twins), else off.
+    flow_prefix_max_delay=False: off whatever the twin says.  ValueError, naming both settings and before any engine exists, for a regression head,
+    chunk_size == 1, a delay that does not fit the chunk, or temporal_ensemble_coeff."""
+    from fastvla_hip import prefix as _prefix
+
+    def pick(arg, env, cast, default):
+        if arg is not None:
+            return arg
+        raw = (os.environ.get(env) or "").strip()
+        if not raw:
+            return default
+        try:
+            return cast(raw)
+        except ValueError:
+            raise ValueError(f"{env} must be {cast.__name__}, got {raw!r}") from None
+
+    D = flow_prefix_max_delay
+    if D is False:
+        return None
+    if D is None:
+        if action_head != "flow":
+            return None
+        D = pick(None, "FASTVLA_FLOW_PREFIX_MAX_DELAY", int, None)
+        if D is None or D == 0:
+            return None
+    dist = str(pick(flow_prefix_delay_dist, "FASTVLA_FLOW_PREFIX_DELAY_DIST", str, "uniform")).lower()
+    rate = pick(flow_prefix_delay_rate, "FASTVLA_FLOW_PREFIX_DELAY_RATE", float, 0.5)
+    return _prefix.check_prefix_config(D, action_head=action_head, chunk_size=chunk_size, temporal_ensemble_coeff=temporal_ensemble_coeff, dist=dist, rate=rate)
+
+
 def resolve_rtc_options(rtc=None, rtc_schedule=None, rtc_max_guidance_weight=None, rtc_execution_horizon=None, *, action_head: str, chunk_size: int,
-                        n_action_steps: int, temporal_ensemble_coeff=None) -> Optional[Dict]:
+                        n_action_steps: int, temporal_ensemble_coeff=None, rtc_method=None, rtc_prefix_steps=None, prefix: Optional[Dict] = None) -> Optional[Dict]:
     """-> {"schedule", "max_guidance_weight", "execution_horizon"} or None (off): explicit arguments, else the FASTVLA_RTC / FASTVLA_RTC_SCHEDULE /
     FASTVLA_RTC_MAX_GUIDANCE_WEIGHT / FASTVLA_RTC_EXECUTION_HORIZON twins, else (off, "exp", 5.0, n_action_steps).  The other twins are read and checked
     only when real-time chunking is on.  ValueError, naming both settings, for rtc with a regression head, with chunk_size == 1, with
@@ -148,6 +181,24 @@ def resolve_rtc_options(rtc=None, rtc_schedule=None, rtc_max_guidance_weight=Non
     if temporal_ensemble_coeff is not None:
         raise ValueError("rtc and temporal_ensemble_coeff cannot be combined: one joins chunks by guidance, the other by averaging them. "
                          f"Got rtc={on}, temporal_ensemble_coeff={temporal_ensemble_coeff}.")
+    # rtc_method (FASTVLA_RTC_METHOD): "guidance" (the default: everything below, on either head width) or "prefix" -- the prefix sampler of a head trained
+    # with flow_prefix_max_delay = D: a re-plan PINS its first min(rtc_prefix_steps, D, K - shift) steps to the previous chunk; no guidance, no schedule, no beta
+    method = str(pick(rtc_method, "FASTVLA_RTC_METHOD", str, "guidance")).lower()
+    if method not in ("guidance", "prefix"):
+        raise ValueError(f"rtc_method must be 'guidance' or 'prefix', got {method!r}")
+    if method == "prefix":
+        if prefix is None:
+            raise ValueError("rtc_method='prefix' needs a head trained with action-prefix conditioning. Got rtc_method='prefix', flow_prefix_max_delay=None.")
+        for name, val in (("rtc_schedule", rtc_schedule), ("rtc_max_guidance_weight", rtc_max_guidance_weight), ("rtc_execution_horizon", rtc_execution_horizon)):
+            if val is not None:
+                raise ValueError(f"{name} belongs to rtc_method='guidance': the prefix sampler has no guidance to shape. Got {name}={val!r}, rtc_method='prefix'.")
+        D = int(prefix["max_delay"])
+        steps = pick(rtc_prefix_steps, "FASTVLA_RTC_PREFIX_STEPS", int, D)
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= D:
+            raise ValueError(f"rtc_prefix_steps must be an integer in 0 .. flow_prefix_max_delay. Got rtc_prefix_steps={steps!r}, flow_prefix_max_delay={D}.")
+        return {"method": "prefix", "prefix_steps": int(steps), "max_delay": D}
+    if rtc_prefix_steps is not None:
+        raise ValueError(f"rtc_prefix_steps needs rtc_method='prefix'. Got rtc_prefix_steps={rtc_prefix_steps!r}, rtc_method={method!r}.")
     schedule = str(pick(rtc_schedule, "FASTVLA_RTC_SCHEDULE", str, "exp")).lower()
     beta = pick(rtc_max_guidance_weight, "FASTVLA_RTC_MAX_GUIDANCE_WEIGHT", float, 5.0)
     s = pick(rtc_execution_horizon, "FASTVLA_RTC_EXECUTION_HORIZON", int, n_action_steps)
@@ -173,7 +224,8 @@ class FastVLAPolicy(nn.Module, EmaMixin):
                  action_dim_weights=None, action_step_weights=None, action_head: Optional[str] = None, flow_steps: Optional[int] = None,
                  flow_time_dim: Optional[int] = None, flow_time_dist: Optional[str] = None, flow_seed: Optional[int] = None, rtc: Optional[bool] = None,
                  rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None,
-                 flow_noise_draws: Optional[int] = None) -> None:
+                 flow_noise_draws: Optional[int] = None, flow_prefix_max_delay: Optional[int] = None, flow_prefix_delay_dist: Optional[str] = None,
+                 flow_prefix_delay_rate: Optional[float] = None, rtc_method: Optional[str] = None, rtc_prefix_steps: Optional[int] = None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
@@ -208,7 +260,19 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         rtc_max_guidance_weight (beta, default 5), rtc_execution_horizon (the last steps of the chunk left free, default n_action_steps); twins
         FASTVLA_RTC_SCHEDULE, FASTVLA_RTC_MAX_GUIDANCE_WEIGHT, FASTVLA_RTC_EXECUTION_HORIZON.  select_action_chunk(..., prev_chunk=, inference_delay=) is
         the explicit form for asynchronous callers.  A property of the run, not of the weights: no checkpoint records it, and a policy that does not
-        ask for it calls nothing new.  Not with a regression head, chunk_size == 1 or temporal_ensemble_coeff (ValueError)."""
+        ask for it calls nothing new.  Not with a regression head, chunk_size == 1 or temporal_ensemble_coeff (ValueError).
+
+        flow_prefix_max_delay=D (flow head, 1 <= D < chunk_size; FASTVLA_FLOW_PREFIX_MAX_DELAY): action-prefix conditioning (Black, Ren, Equi, Levine 2025;
+        fastvla_hip/prefix.py; fv_head_set_flow_prefix).  Training draws a delay d <= D per head row -- flow_prefix_delay_dist "uniform" | "exp" with
+        flow_prefix_delay_rate (twins FASTVLA_FLOW_PREFIX_DELAY_DIST / _RATE) -- gives the first d steps of the chunk to the network clean and keeps them out
+        of the loss, on every training route, in compute_loss / forward(batch) and with flow_noise_draws.  An ARCHITECTURE property, unlike rtc and
+        flow_noise_draws: fusion.0.weight has chunk_size more columns, checkpoints record it, and a plain flow checkpoint does not load
+        (fastvla_hip.prefix.widen_flow_state_dict turns one into a prefix head to fine-tune).  Not with a regression head, chunk_size == 1, D >= chunk_size
+        or temporal_ensemble_coeff (ValueError).  rtc=True, rtc_method="prefix" (FASTVLA_RTC_METHOD; default "guidance"): a re-plan PINS its first
+        min(rtc_prefix_steps, D, K - shift) steps to the last chunk read `shift` = the actions served since steps ahead and samples the rest with the plain
+        three-launch sampler -- no guidance, no Jacobian, no beta; rtc_prefix_steps defaults to D (FASTVLA_RTC_PREFIX_STEPS).  The first plan after reset()
+        pins nothing.  select_action_chunk(..., prev_chunk=, inference_delay=d) pins d <= D steps (ValueError above D).  rtc_schedule,
+        rtc_max_guidance_weight and rtc_execution_horizon given together with "prefix" are refused."""
         super().__init__()
         self.config = config or FastVLAConfig()
         opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
@@ -219,10 +283,14 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist)
         self.action_head = fopts["action_head"]
         self.flow_noise_draws: int = resolve_flow_noise_draws(flow_noise_draws, action_head=self.action_head)      # (before any engine exists)
+        popts = resolve_prefix_options(flow_prefix_max_delay, flow_prefix_delay_dist, flow_prefix_delay_rate, action_head=self.action_head,      # (likewise)
+                                       chunk_size=opts["chunk_size"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
+        self.flow_prefix: Optional[Dict] = popts
         ropts = resolve_rtc_options(rtc, rtc_schedule, rtc_max_guidance_weight, rtc_execution_horizon, action_head=self.action_head,      # (before any engine exists)
-                                    chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
+                                    chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"],
+                                    rtc_method=rtc_method, rtc_prefix_steps=rtc_prefix_steps, prefix=popts)
         self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"],
-                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws)
+                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws, flow_prefix=popts)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts
@@ -396,15 +464,16 @@ class FastVLAPolicy(nn.Module, EmaMixin):
 
     @torch.inference_mode()
     def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device, prev_chunk: Optional[torch.Tensor] = None,
-                            inference_delay: int = 0) -> torch.Tensor:
+                            inference_delay: Optional[int] = None) -> torch.Tensor:
         """-> (K, A): the whole chunk the head predicts for one observation (K = chunk_size; (1, A) without chunks).
         rtc=True: prev_chunk (K', A), K' <= K, in NORMALISED space -- the not-yet-executed rows of the previous chunk, policy.last_chunk_normalised[executed:] --
         guides the sample (row k of the new chunk towards row k of prev_chunk), with the first inference_delay steps as a hard prefix: the explicit form for
         callers that plan while the previous chunk is still being executed.  Without prev_chunk the sample is guided by the chunk the policy planned last
-        (none after reset(): unguided), read from its start."""
+        (none after reset(): unguided), read from its start.  inference_delay None: 0 under rtc_method="guidance"; under rtc_method="prefix" the policy's
+        rtc_prefix_steps, as in select_action (rows without a previous chunk pin nothing whatever the delay)."""
         self.eval()
         if self.rtc is None:
-            if prev_chunk is not None or inference_delay != 0:
+            if prev_chunk is not None or inference_delay not in (None, 0):
                 raise ValueError(f"prev_chunk / inference_delay need rtc=True. Got inference_delay={inference_delay}, rtc={self.rtc is not None}.")
             tasks = self.processor.prepare_tasks(task, batch_size=1)
             action = self.forward(image.unsqueeze(0).to(device), state.unsqueeze(0).to(device), tasks, device=device)
@@ -420,7 +489,7 @@ class FastVLAPolicy(nn.Module, EmaMixin):
             prev[0, shift:] = rows.to(device)
         return self._rtc_plan(image, state, task, device, shift=shift, inference_delay=inference_delay, prev=prev)
 
-    def _rtc_plan(self, image, state, task, device, *, shift: int, inference_delay: int = 0, prev=None) -> torch.Tensor:
+    def _rtc_plan(self, image, state, task, device, *, shift: int, inference_delay: Optional[int] = None, prev=None) -> torch.Tensor:
         images = self.processor.prepare_images(image.unsqueeze(0).to(device), device)
         states = self.processor.prepare_states(state.unsqueeze(0).to(device), device)
         tasks = self.processor.prepare_tasks(task, batch_size=1)

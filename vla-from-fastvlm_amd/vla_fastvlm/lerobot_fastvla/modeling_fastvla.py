@@ -12,7 +12,11 @@ ensembles all B environments of the batch on the device in one launch.
 
 Real-time chunking of a flow head (no config field either): FastVLAPolicy(config, action_head="flow", rtc=True, rtc_schedule=, rtc_max_guidance_weight=,
 rtc_execution_horizon=) or the FASTVLA_RTC* twins.  select_action(batch) then samples every re-plan guided by the rest of the previous chunk, for all B
-environments in one call; predict_action_chunk(batch, inference_delay=, prev_chunk_left_over=, execution_horizon=) is LeRobot's keyword set."""
+environments in one call; predict_action_chunk(batch, inference_delay=, prev_chunk_left_over=, execution_horizon=) is LeRobot's keyword set.
+
+Action-prefix conditioning (no config field): FastVLAPolicy(config, action_head="flow", flow_prefix_max_delay=D, flow_prefix_delay_dist=,
+flow_prefix_delay_rate=) or the FASTVLA_FLOW_PREFIX_* twins train the head with a clean prefix of d <= D steps; rtc=True, rtc_method="prefix"
+(FASTVLA_RTC_METHOD) then pins the first steps of every re-plan to the previous chunk with the plain sampler's three launches per step."""
 from __future__ import annotations
 
 from collections import deque
@@ -41,7 +45,7 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_rtc_options
+        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_prefix_options, resolve_rtc_options
         opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
                                      temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
                                      action_step_weights=kwargs.get("action_step_weights"))
@@ -55,13 +59,17 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.flow_noise_draws: int = resolve_flow_noise_draws(kwargs.get("flow_noise_draws"), action_head=self.action_head)
         # real-time chunking (FastVLAPolicy(config, rtc=True, rtc_schedule=, rtc_max_guidance_weight=, rtc_execution_horizon=) or the FASTVLA_RTC* twins; no
         # config field): re-plans of a flow head are sampled guided by the rest of the previous chunk, for all B environments of the batch in one call
+        popts = resolve_prefix_options(kwargs.get("flow_prefix_max_delay"), kwargs.get("flow_prefix_delay_dist"), kwargs.get("flow_prefix_delay_rate"),
+                                       action_head=self.action_head, chunk_size=opts["chunk_size"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
+        self.flow_prefix = popts
         ropts = resolve_rtc_options(kwargs.get("rtc"), kwargs.get("rtc_schedule"), kwargs.get("rtc_max_guidance_weight"), kwargs.get("rtc_execution_horizon"),
                                     action_head=self.action_head, chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"],
-                                    temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
+                                    temporal_ensemble_coeff=opts["temporal_ensemble_coeff"], rtc_method=kwargs.get("rtc_method"),
+                                    rtc_prefix_steps=kwargs.get("rtc_prefix_steps"), prefix=popts)
         self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
         self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
                                        action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"], flow_steps=fopts["steps"],
-                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws)
+                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws, flow_prefix=popts)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts
@@ -197,9 +205,11 @@ class FastVLAPolicy(PreTrainedPolicy):
             shift = K - rows.shape[1]
             prev = torch.zeros(rows.shape[0], K, A, dtype=torch.float32, device=rows.device)
             prev[:, shift:] = rows
-        return self._rtc_plan(batch, shift=shift, inference_delay=int(inference_delay or 0), execution_horizon=execution_horizon, prev=prev)
+        # (inference_delay None: 0 under rtc_method="guidance", the policy's rtc_prefix_steps under "prefix" -- FastVLMWithExpert.rtc_sample's default)
+        return self._rtc_plan(batch, shift=shift, inference_delay=None if inference_delay is None else int(inference_delay), execution_horizon=execution_horizon,
+                              prev=prev)
 
-    def _rtc_plan(self, batch, *, shift: int, inference_delay: int = 0, execution_horizon=None, prev=None) -> Tensor:
+    def _rtc_plan(self, batch, *, shift: int, inference_delay=None, execution_horizon=None, prev=None) -> Tensor:
         images, states, tasks = self._prepare_inputs(batch)
         pooled = self.model.features(images, tasks, device=images.device)
         chunk = self.model.rtc_sample(pooled, states, shift=shift, inference_delay=inference_delay, execution_horizon=execution_horizon, prev=prev)

@@ -189,6 +189,7 @@ class FastVLMBackbone(nn.Module):
         self._head_flow: Optional[dict] = None                  # configure_head_flow: FastVLAEngine.set_head_flow's arguments, None = the regression head
         self._head_flow_draws = 1                               # configure_head_flow_draws: FastVLAEngine.set_head_flow_draws' argument, 1 = one draw per observation
         self._head_flow_guidance: Optional[dict] = None         # configure_head_flow_guidance: FastVLAEngine.set_head_flow_guidance's arguments, None = off
+        self._head_flow_prefix: Optional[dict] = None           # configure_head_flow_prefix: {"chunk", "max_delay", "thresholds", "dist", "rate"}, None = off
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
 
@@ -266,6 +267,15 @@ class FastVLMBackbone(nn.Module):
         if self._engine is not None and flow != self._head_flow:
             raise RuntimeError("configure_head_flow: the engine is already built (the head's layout and the workspace depend on the mode)")
         self._head_flow = None if flow is None else dict(flow)
+
+    def configure_head_flow_prefix(self, prefix: Optional[dict]) -> None:
+        """Action-prefix conditioning of a flow head (fastvla_hip.prefix.check_prefix_config's result; None = off).  fusion.0's width, the saved activations
+        and the workspaces depend on it, so it is fixed before the engine is built."""
+        if prefix is not None and self._head_flow is None:
+            raise ValueError(f"flow_prefix_max_delay={prefix.get('max_delay')} needs action_head='flow'")
+        if self._engine is not None and prefix != self._head_flow_prefix:
+            raise RuntimeError("configure_head_flow_prefix: the engine is already built (the head's layout and the workspace depend on the mode)")
+        self._head_flow_prefix = None if prefix is None else dict(prefix)
 
     def configure_head_flow_draws(self, draws: int = 1) -> None:
         """Noise draws per observation of a flow head's training forms (FastVLAEngine.set_head_flow_draws; 1 = off).  The saved activations and the
@@ -377,6 +387,9 @@ class FastVLMBackbone(nn.Module):
                 eng = build(1)
             if self._head_flow is not None:      # (first: before any workspace is bound)
                 eng.set_head_flow(**self._head_flow)
+                if getattr(self, "_head_flow_prefix", None) is not None:
+                    px = self._head_flow_prefix
+                    eng.set_head_flow_prefix(px["chunk"], px["max_delay"], thresholds=px["thresholds"], dist=px["dist"], rate=px["rate"])
                 if getattr(self, "_head_flow_draws", 1) > 1:
                     eng.set_head_flow_draws(self._head_flow_draws)
                 if getattr(self, "_head_flow_guidance", None) is not None:

@@ -36,6 +36,8 @@ EXTRAS_FILE = "hip_extras.json"
 # (+ "temporal_ensemble_coeff", "dim_weights", "step_weights" -- each only when set: select_action's temporal ensembling and the weights of the chunk loss)
 # "action_head" = {"type": "flow", "steps", "time_dim", "min_period", "max_period", "time_dist", "dist_a", "dist_b", "seed"} -- only for a flow-matching head
 # (FastVLAPolicy(action_head="flow")), whose fusion.0.weight is chunk_size * action_dim + time_dim columns wider than the regression head's
+# (+ "prefix_max_delay", and "prefix_delay_dist" / "prefix_delay_rate" for information -- only for a head with action-prefix conditioning
+# (flow_prefix_max_delay), whose fusion.0.weight has chunk_size more columns still)
 LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
@@ -104,7 +106,9 @@ def check_fusion_width(state: dict, policy, where="") -> None:
     if w is not None and tuple(w.shape) != tuple(own.shape):
         raise ValueError(f"{where}: model.fusion.0.weight is {tuple(w.shape)} in the checkpoint and {tuple(own.shape)} in this policy, which was built with "
                          f"action_head='{getattr(policy, 'action_head', 'regression')}': a flow head's fusion.0 reads chunk_size * action_dim + flow_time_dim more "
-                         f"columns than a regression head's -- build the policy with the action_head setting (and flow_time_dim) the checkpoint was trained with")
+                         f"columns than a regression head's, and a head with flow_prefix_max_delay chunk_size more than a plain flow head's (fastvla_hip.prefix."
+                         f"widen_flow_state_dict widens a plain flow checkpoint) -- build the policy with the action_head setting (flow_time_dim, flow_prefix_max_delay) "
+                         f"the checkpoint was trained with")
 
 
 def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None = None) -> FastVLAPolicy:
@@ -124,7 +128,7 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
                            action_loss=chunk.get("loss", "mse"), action_loss_beta=float(chunk.get("beta", 1.0)),
                            temporal_ensemble_coeff=chunk.get("temporal_ensemble_coeff", False), action_dim_weights=chunk.get("dim_weights", False),
                            action_step_weights=chunk.get("step_weights", False),      # (False: off, whatever the twin says)
-                           **flow_kwargs(read_extras(root).get("action_head")))
+                           **flow_kwargs(read_extras(root).get("action_head")), **prefix_kwargs(read_extras(root).get("action_head")))
     check_fusion_width(state, policy, root)
     vlm = {k[len(BACKBONE_PREFIX):]: v for k, v in state.items() if k.startswith(BACKBONE_PREFIX)}
     if vlm:
@@ -157,6 +161,15 @@ def flow_kwargs(rec) -> dict:
                          "distribution would differ from the one the weights were trained with")
     return {"action_head": "flow", "flow_steps": int(rec.get("steps", 10)), "flow_time_dim": int(rec["time_dim"]), "flow_time_dist": rec.get("time_dist", "uniform"),
             "flow_seed": rec.get("seed")}
+
+
+def prefix_kwargs(rec) -> dict:
+    """FastVLAPolicy's action-prefix arguments from a checkpoint's "action_head" record.  The file decides: no "prefix_max_delay" means a head without the
+    mask columns, whatever the FASTVLA_FLOW_PREFIX_MAX_DELAY twin says"""
+    if not rec or rec.get("type") != "flow" or not rec.get("prefix_max_delay"):
+        return {"flow_prefix_max_delay": False}
+    return {"flow_prefix_max_delay": int(rec["prefix_max_delay"]), "flow_prefix_delay_dist": rec.get("prefix_delay_dist", "uniform"),
+            "flow_prefix_delay_rate": float(rec.get("prefix_delay_rate", 0.5))}
 
 
 def load_lora_adapters(policy: FastVLAPolicy, checkpoint_dir, lora_extras: dict, optim: dict | None = None) -> None:
