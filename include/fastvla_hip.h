@@ -409,6 +409,26 @@ int fv_head_flow_prepare_prefix(fv_handle* h, const float* targets, int B, uint6
 int fv_head_flow_sample_prefix(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                                uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out,
                                fv_stream s);
+/* ---- higher-order integrators for all three samplers (fv_head_flow_sample, _prefix, _guided).  Explicit Runge-Kutta schemes whose stage j + 1 depends on
+ * stage j only; within a step from t_i to t_i + h, h = -1 / n_steps, with k_j = v(x_j, t_i + c_j h):
+ *     x_1 = x0      x_{j+1} = x0 + (a_{j+1} h) k_j      x <- x0 + h sum_j b_j k_j
+ *     midpoint  c = 0, 1/2          a = 1/2          b = 0, 1
+ *     Heun      c = 0, 1            a = 1            b = 1/2, 1/2
+ *     RK4       c = 0, 1/2, 1/2, 1  a = 1/2, 1/2, 1  b = 1/6, 1/3, 1/3, 1/6
+ * n_steps keeps meaning STEPS: a call makes n_steps x stages network evaluations, each the Euler step's launches with the x update replaced by a stage
+ * update over two more (B, action_dim) rows, the step's start and the running sum.  The stage times 1 - (i + c_j) / n_steps, the products a_j h, the b_j and
+ * h are formed on the host in double and rounded once.  The guided sampler evaluates the corrected velocity v' with the STAGE's t and guidance weight; the
+ * prefix sampler leaves a pinned element alone at every stage.  Everything the three entry points promise stays: no atomics, no host synchronisation, no
+ * allocation, rows never meet, two calls give the same bits, a guided row with omega == 0 is the plain sampler's row of the same solver bit for bit.
+ * Configuration call, for all three entry points; their signatures do not change.  FV_ERR_STATE when flow mode is off; FV_ERR_ARG, changing nothing, for an
+ * unknown solver.  The two rows join the workspace plan with the FIRST call that names a solver other than Euler (fv_workspace_bytes grows from then on and
+ * stays): that call must come before fv_bind_workspace (FV_ERR_STATE afterwards); later calls switch freely among all four.  A handle that never names one
+ * reports the fv_workspace_bytes it always did; FV_FLOW_SOLVER_EULER launches the Euler kernels as they are.  fv_head_set_flow(NULL) returns it to Euler. */
+#define FV_FLOW_SOLVER_EULER 0
+#define FV_FLOW_SOLVER_MIDPOINT 1
+#define FV_FLOW_SOLVER_HEUN 2
+#define FV_FLOW_SOLVER_RK4 3
+int fv_head_set_flow_solver(fv_handle* h, int solver);
 /* generic backward of the head from dL/dactions (B,A) f32 (what autograd hands a custom Function when the loss is
  * computed outside, e.g. lerobot_fastvla/modeling_fastvla.py:132 + loss.backward()); overwrites flat_grads. */
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,

@@ -192,6 +192,8 @@ struct fv_handle {
   fv::HeadGuide guide{nullptr, 0, 0.f, 0};   // fv_head_set_flow_guidance (step_w != null: on)
   float* guide_buf = nullptr;     // its device weights (guide_chunk floats), allocated by the first call for a chunk length and kept
   int guide_chunk = 0;            // > 0: the workspace plan holds the guided sampler's rows (stays when guidance is switched off)
+  int flow_solver = FV_FLOW_SOLVER_EULER;   // fv_head_set_flow_solver: the integrator of all three samplers
+  bool flow_rk_rows = false;      // true: the workspace plan holds the higher-order solvers' two rows (from the first call that names one; stays)
   float* loss_w = nullptr;        // fv_head_set_loss_weights: ONE device vector of 2 da floats per handle ([0, A) dim_w, [da, da + K) step_w), allocated on first use
   TrainState train;               // unfrozen-backbone training (train_path.inc): library-owned transposed bf16 weight copies
   int batch_invariant = 0;        // fv_set_batch_invariant: the inference tower never takes the range forms either
@@ -401,6 +403,11 @@ int load_ffn(Loader& L, const std::string& pre, int C, int hidden, float bn_eps,
   return L.rc;
 }
 
+// the rows of the flow samplers inside the plan's head scratch (the guided sampler's once it is configured); the higher-order solvers' rows start behind them
+size_t head_sampler_bytes(const fv_handle* h, int B) {
+  return std::max(fv::flow_sample_scratch_bytes(h->hd, B), h->guide_chunk > 0 ? fv::flow_guided_scratch_bytes(h->hd, B) : (size_t)0);
+}
+
 WsPlan plan_ws(const fv_handle* h, int B, int T, int splice) {
   const fv_model_desc& d = h->d;
   WsPlan p{};
@@ -451,8 +458,8 @@ WsPlan plan_ws(const fv_handle* h, int B, int T, int splice) {
   p.splitk_bytes = rows <= 256 || (rows % 256 != 0 && rows <= 1024) ? (size_t)(rows <= 256 ? 40 : 24) * rows * ((std::max((size_t)d.llm_hidden, qkvw) + 255) / 256 * 256) * 4
                                : rows % 256 == 0 ? (size_t)(rows <= 2048 ? 8 : 4) * rows * ((std::max((size_t)d.llm_hidden, qkvw) + 255) / 256 * 256) * 4 : 0;
   p.splitk = take(p.splitk_bytes);
-  p.head_scr = take(std::max(std::max(fv::head_bwd_scratch_bytes(h->hd, B), fv::flow_sample_scratch_bytes(h->hd, B)),   // (flow mode: the sampler's rows live here too,
-                             h->guide_chunk > 0 ? fv::flow_guided_scratch_bytes(h->hd, B) : (size_t)0));                  //  and the guided sampler's once it is configured)
+  // (flow mode: the sampler's rows live here too, the guided sampler's once it is configured, and BEHIND them the higher-order solvers' two rows once one is named)
+  p.head_scr = take(std::max(fv::head_bwd_scratch_bytes(h->hd, B), head_sampler_bytes(h, B) +(h->flow_rk_rows ? fv::flow_rk_scratch_bytes(h->hd, B) : (size_t)0)));
   // long sequences (the spliced prefill: 256 image + T text positions) run the split-bf16 attention kernel: its per-layer K / V records
   const int Tseq = T + (splice ? (int)P : 0);
   p.attn_scr_bytes = (d.llm_precision != 0 && Tseq >= fv::FV_ATTN_SPLIT_MIN_T && (d.llm_head_dim == 64 || d.llm_head_dim == 128))

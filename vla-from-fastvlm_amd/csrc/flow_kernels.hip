@@ -6,6 +6,8 @@
 //                                          PREFIX instances; the kernels without the suffix are the code they were
 //   flow_guide_* / flow_vjp_t_kernel       guided sampling (fv_head_set_flow_guidance; real-time chunking): the step's forward with z3 and v kept, J^T omega
 //                                          through three transposed products and a LayerNorm backward, and the update
+//   flow_rk_stage / flow_*_rk_kernel       higher-order integrators (fv_head_set_flow_solver; midpoint, Heun, RK4): the three kernels that own the x update as
+//                                          Runge-Kutta stages over two more rows per batch row; the Euler kernels and loops are the code they were
 // The state branch of both samplers is head_kernels.hip's (launch_head_state_branch); the draws come from common.h philox under this file's key.
 #include "kernels.h"
 
@@ -490,7 +492,121 @@ __global__ __launch_bounds__(256) void flow_step_c_prefix_kernel(const float* __
   }
 }
 
+// ---- higher-order integrators (fv_head_set_flow_solver): explicit Runge-Kutta schemes whose stage j + 1 depends on stage j only.  A stage is the Euler step's
+// launches with another epilogue; a step keeps two more rows per batch row, x0 (the step's start) and S (the running sum of b_j k_j).  Within a step of size
+// h = dt, with k the stage's velocity (the corrected v' in the guided sampler) and xphi holding the stage's x:
+//     first stage:      x0 <- x (xphi holds the step's start), S <- b k                 later stages:  S <- fmaf(b, k, S)
+//     not the last:     x <- fmaf(a h, k, x0)                                           the last:      x <- fmaf(h, S, x0)
+// ah = a_{j+1} h, b = b_j and h are rounded once on the host.  The lane or thread that owns (b, n) is the only one that touches x0, S and x of that element
+struct FlowRkArgs { float* x0; float* S; float ah, b, h; int first, last; };
+// e = b N + n; xb = xphi[b][n] as it stands; -> the value xphi[b][n] takes.  ONE helper for all three samplers: equal k give equal bits
+__device__ __forceinline__ float flow_rk_stage(const FlowRkArgs& rk, size_t e, float xb, float k) {
+  const float x0v = rk.first ? xb : rk.x0[e];
+  const float sv = rk.first ? rk.b * k : flow_fma_pinned(rk.b, k, rk.S[e]);
+  if (rk.last) return flow_fma_pinned(rk.h, sv, x0v);
+  if (rk.first) rk.x0[e] = x0v;
+  rk.S[e] = sv;
+  return flow_fma_pinned(rk.ah, k, x0v);
+}
+// flow_step_c_kernel (PREFIX: flow_step_c_prefix_kernel) as a Runge-Kutta stage.  t_next is the time of the NEXT evaluation (the next stage's, or the next
+// step's first); `actions` is given on the last stage of the last step only.  PREFIX: a pinned element is left alone in xphi at every stage and never enters
+// x0 or S; the last stage writes it out from x as it stands
+template <bool PREFIX>
+__global__ __launch_bounds__(256) void flow_step_c_rk_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
+                                                              float* __restrict__ xphi, int xw, int te, FlowRkArgs rk, float t_next, const float* __restrict__ freq,
+                                                              float* __restrict__ actions, float* __restrict__ chunk_out, const float* __restrict__ post_scale,
+                                                              const float* __restrict__ post_shift, int B, int N, const int32_t* __restrict__ delays, int pd,
+                                                              int chunk, int shift) {
+  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
+  if (!actions && blockIdx.x == 0) {
+    const int half = te / 2;
+    for (int idx = threadIdx.x; idx < 8 * half; idx += 256) {
+      const int j = idx / half, i = idx - j * half;
+      if (b0 + j < B) flow_phi(xphi + (size_t)(b0 + j) * xw + N, freq, half, t_next, i);
+    }
+  }
+  if (n >= N) return;
+  int pin[8];
+  float xv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int b = min(b0 + j, B - 1);
+    pin[j] = PREFIX ? flow_pinned_steps(delays, b, pd, chunk, shift) : 0;
+    xv[j] = xphi[(size_t)b * xw + n];
+  }
+  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
+  if (lane == 0) {
+    const int k = PREFIX ? n / (N / chunk) : 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (b0 + j >= B) break;
+      const size_t b = (size_t)(b0 + j);
+      const bool pinned = PREFIX && k < pin[j];
+      const float xn = pinned ? xv[j] : flow_rk_stage(rk, b * N + n, xv[j], acc[j] + bias[n]);
+      if (!actions) {
+        if (!pinned) xphi[b * xw + n] = xn;
+        continue;
+      }
+      if (chunk_out) chunk_out[b * N + n] = xn;
+      actions[b * N + n] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
+    }
+  }
+}
+// flow_guide_update_kernel as a Runge-Kutta stage: k is the corrected velocity v' = v - kw g, with t and kw the STAGE's; t_next as above
+__global__ __launch_bounds__(256) void flow_guide_update_rk_kernel(const float* __restrict__ part, int S_in, const float* __restrict__ omega, const float* __restrict__ v,
+                                                                    float* __restrict__ xphi, int xw, int te, float t, float kw, FlowRkArgs rk, float t_next,
+                                                                    const float* __restrict__ freq, float* __restrict__ actions, float* __restrict__ chunk_out,
+                                                                    const float* __restrict__ post_scale, const float* __restrict__ post_shift, int B, int N) {
+  const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
+  if (!actions && blockIdx.x == 0)
+    for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xphi + (size_t)b * xw + N, freq, te / 2, t_next, i);
+  if (n >= N) return;
+  const size_t e = (size_t)b * N + n;
+  float jt = 0.f;
+#pragma unroll 8
+  for (int q = 0; q < S_in; ++q) jt += part[((size_t)q * B + b) * N + n];
+  const float g = omega[e] - t * jt;
+  const float vp = v[e] - kw * g;
+  const float xn = flow_rk_stage(rk, e, xphi[(size_t)b * xw + n], vp);
+  if (!actions) { xphi[(size_t)b * xw + n] = xn; return; }
+  if (chunk_out) chunk_out[e] = xn;
+  actions[e] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
+}
+
+// the tableaux (FV_FLOW_SOLVER_*; Euler has no entry: it takes the Euler loops): stage times c, a[j] the coefficient that forms stage j + 1's x from k_j, b
+struct FlowTableau { int stages; double c[4], a[3], b[4]; };
+constexpr FlowTableau FLOW_TABLEAUX[3] = {
+    {2, {0.0, 0.5}, {0.5}, {0.0, 1.0}},                                                     // midpoint
+    {2, {0.0, 1.0}, {1.0}, {0.5, 0.5}},                                                     // Heun
+    {4, {0.0, 0.5, 0.5, 1.0}, {0.5, 0.5, 1.0}, {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0}},   // RK4
+};
+// what stage j of step i of n_steps needs: its time t, the next evaluation's time, and the epilogue's scalars -- all formed in double and rounded once, so a
+// stage with c = 1 sees the bits of t_{i + 1}
+struct FlowStage { float t, t_next; FlowRkArgs rk; bool final; };
+FlowStage flow_stage(const FlowTableau& tb, int i, int j, int n_steps, float* rows, size_t row_floats) {
+  auto time = [&](int step, double c) { return (float)(1.0 - ((double)step + c) / (double)n_steps); };
+  const bool last = j + 1 == tb.stages;
+  const double h = -1.0 / (double)n_steps;
+  FlowStage st;
+  st.t = time(i, tb.c[j]);
+  st.t_next = last ? time(i + 1, 0.0) : time(i, tb.c[j + 1]);
+  st.rk = FlowRkArgs{rows, rows + row_floats, last ? 0.f : (float)(tb.a[j] * h), (float)tb.b[j], (float)h, j == 0, last};
+  st.final = last && i + 1 == n_steps;
+  return st;
+}
+inline size_t flow_rk_row_floats(const HeadDims& d, int B) { return ((size_t)B * d.da + 3) / 4 * 4; }
+int flow_solver_check(const char* who, int solver, const float* rk_rows) {
+  if (solver < FV_FLOW_SOLVER_EULER || solver > FV_FLOW_SOLVER_RK4) return fv_fail(FV_ERR_ARG, "%s: unknown solver %d", who, solver);
+  if (solver != FV_FLOW_SOLVER_EULER && !rk_rows) return fv_fail(FV_ERR_STATE, "%s: a higher-order solver needs its rows (fv_head_set_flow_solver before fv_bind_workspace)", who);
+  return FV_OK;
+}
+
 }  // namespace
+
+size_t flow_rk_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? 2 * flow_rk_row_floats(d, B) * sizeof(float) : 0; }
 
 int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
                         float* saved, float* u_out, hipStream_t s, const int32_t* delays) {
@@ -537,16 +653,32 @@ size_t flow_sample_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? f
 // 4 launches of conditioning (state LayerNorm, state projection, the t-independent part of fusion.0, the start), then 3 per Euler step.  No dropout, no
 // atomics, no host synchronisation; t_i = 1 - i / N and dt = -1 / N are rounded once on the host and travel as kernel arguments
 int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
-                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io) {
+                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows) {
   if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample: the head is not in flow mode (fv_head_set_flow)");
   if (!P || !pooled || !states || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample: null pointer");
   if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample: B and n_steps must be positive");
+  if (const int rc = flow_solver_check("flow_sample", solver, rk_rows)) return rc;
   const HeadOffsets ho = head_offsets(d);
   const FlowScratch fs = flow_carve(d, B, scratch);
   const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
   const dim3 blk(256);
   const unsigned b8 = cdiv(B, 8);
   flow_condition(d, f, ho, fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io);
+  if (solver != FV_FLOW_SOLVER_EULER) {   // n_steps x stages evaluations: A and B as they are, step C as a Runge-Kutta stage
+    const FlowTableau& tb = FLOW_TABLEAUX[solver - 1];
+    for (int i = 0; i < n_steps; ++i)
+      for (int j = 0; j < tb.stages; ++j) {
+        const FlowStage st = flow_stage(tb, i, j, n_steps, rk_rows, flow_rk_row_floats(d, B));
+        hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
+        hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B],
+                           fs.a3, (float*)nullptr, B, d.fus);
+        hipLaunchKernelGGL(flow_step_c_rk_kernel<false>, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, st.rk, st.t_next,
+                           f.freq, st.final ? actions : (float*)nullptr, (float*)nullptr, st.final && io ? io->action_std : (const float*)nullptr,
+                           st.final && io ? io->action_mean : (const float*)nullptr, B, d.da, (const int32_t*)nullptr, 0, 1, 0);
+      }
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+  }
   const float dt = (float)(-1.0 / (double)n_steps);
   for (int i = 0; i < n_steps; ++i) {
     const bool last = i + 1 == n_steps;
@@ -565,12 +697,13 @@ int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, con
 // launch_flow_sample with the conditioning's and the start's PREFIX kernels and step C's PREFIX instance: 4 launches, then 3 per Euler step
 int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                               uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out, float* scratch,
-                              hipStream_t s, const HeadIoNorm* io) {
+                              hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows) {
   if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample_prefix: the head is not in flow mode (fv_head_set_flow)");
   if (d.pk < 2 || d.da % d.pk || d.pd < 1 || d.pd >= d.pk) return fv_fail(FV_ERR_STATE, "flow_sample_prefix: prefix mode is off (fv_head_set_flow_prefix)");
   if (!P || !pooled || !states || !prev || !delays || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: null pointer");
   if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: B and n_steps must be positive");
   if (shift < 0 || shift > d.pk) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: shift = %d outside 0 .. chunk = %d", shift, d.pk);
+  if (const int rc = flow_solver_check("flow_sample_prefix", solver, rk_rows)) return rc;
   const HeadOffsets ho = head_offsets(d);
   const FlowScratch fs = flow_carve(d, B, scratch);
   const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
@@ -580,6 +713,21 @@ int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float*
   hipLaunchKernelGGL(flow_cond_prefix_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[HP_FUS0_W], cw, P + ho.o[HP_FUS0_B], fs.c, B, d.fus,
                      xo + xw, delays, d.pd, d.pk, shift);
   hipLaunchKernelGGL(flow_init_prefix_kernel, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, 1.0f, seed, offset, prev, delays, d.pd, d.pk, shift);
+  if (solver != FV_FLOW_SOLVER_EULER) {   // as launch_flow_sample's, step C in its PREFIX Runge-Kutta instance
+    const FlowTableau& tb = FLOW_TABLEAUX[solver - 1];
+    for (int i = 0; i < n_steps; ++i)
+      for (int j = 0; j < tb.stages; ++j) {
+        const FlowStage st = flow_stage(tb, i, j, n_steps, rk_rows, flow_rk_row_floats(d, B));
+        hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
+        hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B],
+                           fs.a3, (float*)nullptr, B, d.fus);
+        hipLaunchKernelGGL(flow_step_c_rk_kernel<true>, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, st.rk, st.t_next,
+                           f.freq, st.final ? actions : (float*)nullptr, st.final ? chunk_out : (float*)nullptr, st.final && io ? io->action_std : (const float*)nullptr,
+                           st.final && io ? io->action_mean : (const float*)nullptr, B, d.da, delays, d.pd, d.pk, shift);
+      }
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+  }
   const float dt = (float)(-1.0 / (double)n_steps);
   for (int i = 0; i < n_steps; ++i) {
     const bool last = i + 1 == n_steps;
@@ -598,6 +746,11 @@ int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float*
 namespace {
 // the guided sampler's rows: the unguided sampler's, then z3, v, omega, dz2 and two partial-sum buffers the transposed products alternate between
 struct GuideScratch { FlowScratch fs; float *z3, *v, *omega, *dz2, *pa, *pb; size_t total; };
+// the Euler loop's k_i for a stage time (in double from the fp32-rounded t, rounded once; beta at t = 1 and, the ratio being unbounded there, at t = 0)
+inline float guide_weight(float t, float beta) {
+  const double td = (double)t;
+  return t >= 1.0f || t <= 0.0f ? beta : (float)std::min((double)beta, ((1.0 - td) * (1.0 - td) + td * td) / ((1.0 - td) * td));
+}
 inline int guide_rps(int B) { return B <= 16 ? 64 : FLOW_VJP_ROWS_MAX; }   // reduction rows per block: more, smaller ranges while few batch groups fill the chip
 size_t guide_part_floats(const HeadDims& d, int B) {
   auto per_row = [&](int rps) {
@@ -651,18 +804,34 @@ size_t flow_guided_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? g
 // between the last two, and the update.  t_i, k_i, dt, shift and the live-row count are host values that travel as kernel arguments
 int launch_flow_sample_guided(const HeadDims& d, const HeadFlow& f, const HeadGuide& gd, const float* P, const float* pooled, const float* states, int B, int n_steps,
                               const float* noise, uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions,
-                              float* chunk_out, float* scratch, hipStream_t s, const HeadIoNorm* io) {
+                              float* chunk_out, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows) {
   if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample_guided: the head is not in flow mode (fv_head_set_flow)");
   if (!gd.step_w || gd.chunk < 1 || d.da % gd.chunk) return fv_fail(FV_ERR_STATE, "flow_sample_guided: guidance is not configured (fv_head_set_flow_guidance)");
   if (!P || !pooled || !states || !prev || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample_guided: null pointer");
   if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample_guided: B and n_steps must be positive");
   if (shift < 0 || shift > gd.chunk) return fv_fail(FV_ERR_ARG, "flow_sample_guided: shift = %d outside 0 .. chunk = %d", shift, gd.chunk);
+  if (const int rc = flow_solver_check("flow_sample_guided", solver, rk_rows)) return rc;
   const HeadOffsets ho = head_offsets(d);
   const GuideScratch g = guide_carve(d, B, scratch);
   const int A = d.da / gd.chunk, xw = d.da + d.te;
   // steps from here on have omega == 0 (weight 0, or beyond the shift): the first product stops there.  (At least one step: its omega is then all 0)
   const int n_live = std::max(1, std::min(gd.live_steps, gd.chunk - shift)) * A;
   flow_condition(d, f, ho, g.fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io);
+  if (solver != FV_FLOW_SOLVER_EULER) {   // every stage is a guided evaluation at the STAGE's time: forward, omega, J^T omega, then the update as a Runge-Kutta stage
+    const FlowTableau& tb = FLOW_TABLEAUX[solver - 1];
+    for (int i = 0; i < n_steps; ++i)
+      for (int j = 0; j < tb.stages; ++j) {
+        const FlowStage st = flow_stage(tb, i, j, n_steps, rk_rows, flow_rk_row_floats(d, B));
+        const float kw = guide_weight(st.t, gd.beta);
+        guide_forward(d, ho, g, P, B, st.t, prev, gd.step_w, row_mask, gd.chunk, shift, g.v, s);
+        const int sp = guide_backward(d, ho, g, P, g.omega, n_live, B, s);
+        hipLaunchKernelGGL(flow_guide_update_rk_kernel, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, g.omega, g.v, g.fs.xphi, xw, d.te, st.t, kw, st.rk, st.t_next, f.freq,
+                           st.final ? actions : (float*)nullptr, st.final ? chunk_out : (float*)nullptr, st.final && io ? io->action_std : (const float*)nullptr,
+                           st.final && io ? io->action_mean : (const float*)nullptr, B, d.da);
+      }
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+  }
   const float dt = (float)(-1.0 / (double)n_steps);
   for (int i = 0; i < n_steps; ++i) {
     const bool last = i + 1 == n_steps;

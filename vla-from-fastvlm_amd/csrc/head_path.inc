@@ -16,6 +16,17 @@ int head_scratch(fv_handle* h, int B, const char* too_small, float** scr) {
   return FV_OK;
 }
 
+// the higher-order solvers' rows for a call whose scratch is `scr` (null under Euler, which takes none)
+float* head_rk_rows(fv_handle* h, int B, float* scr) {
+  return h->flow_solver != FV_FLOW_SOLVER_EULER ? scr + head_sampler_bytes(h, B) / sizeof(float) : nullptr;
+}
+
+// network evaluations of a sampler call, for the profiler's estimates: n_steps x the solver's stages
+double flow_evals(const fv_handle* h, int n_steps) {
+  static const int stages[4] = {1, 2, 2, 4};
+  return (double)n_steps * stages[h->flow_solver];
+}
+
 // n host floats -> the handle's device vector *buf, allocated first when `fresh` (every setter has its own rule for that; an old vector stays until fv_destroy).
 // A head kernel still in flight on any stream may be reading the previous values: a configuration call, so it simply waits
 int head_upload(fv_handle* h, float** buf, bool fresh, const float* host, size_t n) {
@@ -105,7 +116,7 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   }
   // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
   if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
-  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->hd.pk = h->hd.pd = 0; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
+  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->hd.pk = h->hd.pd = 0; h->flow_solver = FV_FLOW_SOLVER_EULER; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
   const int half = spec->time_dim / 2;
   std::vector<float> fr(half);   // 2 pi / p_j, p_j geometric from min_period to max_period; in double, rounded once
   for (int j = 0; j < half; ++j) {
@@ -184,8 +195,9 @@ int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* poo
   float* scr = nullptr;
   FV_TRY(head_scratch(h, B, "workspace too small for the flow sampler", &scr));
   hipStream_t st = static_cast<hipStream_t>(s);
-  prof_begin(h, FV_FAM_HEAD, 2.0 * B * n_steps * head_param_count(h), 4.0 * n_steps * head_param_count(h), st);
-  const int rc = fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr);
+  prof_begin(h, FV_FAM_HEAD, 2.0 * B * flow_evals(h, n_steps) * head_param_count(h), 4.0 * flow_evals(h, n_steps) * head_param_count(h), st);
+  const int rc = fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr,
+                                        h->flow_solver, head_rk_rows(h, B, scr));
   prof_end(h, st);
   return rc;
 }
@@ -204,11 +216,27 @@ int fv_head_flow_sample_prefix(fv_handle* h, const float* flat_params, const flo
   float* scr = nullptr;
   FV_TRY(head_scratch(h, B, "workspace too small for the flow sampler", &scr));
   hipStream_t st = static_cast<hipStream_t>(s);
-  prof_begin(h, FV_FAM_HEAD, 2.0 * B * n_steps * head_param_count(h), 4.0 * n_steps * head_param_count(h), st);
+  prof_begin(h, FV_FAM_HEAD, 2.0 * B * flow_evals(h, n_steps) * head_param_count(h), 4.0 * flow_evals(h, n_steps) * head_param_count(h), st);
   const int rc = fv::launch_flow_sample_prefix(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, delays, actions, chunk_out, scr, st,
-                                               h->has_io ? &h->io : nullptr);
+                                               h->has_io ? &h->io : nullptr, h->flow_solver, head_rk_rows(h, B, scr));
   prof_end(h, st);
   return rc;
+}
+
+int fv_head_set_flow_solver(fv_handle* h, int solver) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_solver: the head is not in flow mode (fv_head_set_flow)");
+  if (solver < FV_FLOW_SOLVER_EULER || solver > FV_FLOW_SOLVER_RK4)
+    return fv_fail(FV_ERR_ARG, "fv_head_set_flow_solver: unknown solver %d (0 Euler, 1 midpoint, 2 Heun, 3 RK4)", solver);
+  // the step's start and the running stage sum, two (B, action_dim) rows, join the plan with the first call that names a higher-order solver: a workspace
+  // bound before that does not hold them
+  if (solver != FV_FLOW_SOLVER_EULER && !h->flow_rk_rows) {
+    if (h->ws) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_solver: the first call for a higher-order solver must come before fv_bind_workspace (the workspace grows by two rows)");
+    h->flow_rk_rows = true;
+  }
+  h->flow_solver = solver;
+  return FV_OK;
 }
 
 int fv_head_set_flow_guidance(fv_handle* h, int chunk, const float* step_weights_host, float max_guidance_weight) {
@@ -249,9 +277,9 @@ int fv_head_flow_sample_guided(fv_handle* h, const float* flat_params, const flo
   float* scr = nullptr;
   FV_TRY(head_scratch(h, B, "workspace too small for the guided flow sampler", &scr));
   hipStream_t st = static_cast<hipStream_t>(s);
-  prof_begin(h, FV_FAM_HEAD, 4.0 * B * n_steps * head_param_count(h), 8.0 * n_steps * head_param_count(h), st);
+  prof_begin(h, FV_FAM_HEAD, 4.0 * B * flow_evals(h, n_steps) * head_param_count(h), 8.0 * flow_evals(h, n_steps) * head_param_count(h), st);
   const int rc = fv::launch_flow_sample_guided(h->hd, h->flow, h->guide, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, row_mask, actions,
-                                               chunk_out, scr, st, h->has_io ? &h->io : nullptr);
+                                               chunk_out, scr, st, h->has_io ? &h->io : nullptr, h->flow_solver, head_rk_rows(h, B, scr));
   prof_end(h, st);
   return rc;
 }

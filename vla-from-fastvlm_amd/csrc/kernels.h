@@ -351,12 +351,16 @@ int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targe
 // the Euler sampler: conditioning once, then three launches per step.  scratch: flow_sample_scratch_bytes(d, B)
 size_t flow_sample_scratch_bytes(const HeadDims& d, int B);
 int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
-                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io);
+                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver = 0, float* rk_rows = nullptr);
+// higher-order integrators (fv_head_set_flow_solver), for all three samplers: solver = FV_FLOW_SOLVER_*; 0 takes the Euler loop and the Euler kernels as they
+// are.  Another one runs n_steps x stages evaluations, each the Euler step's launches with the x update as a Runge-Kutta stage, over rk_rows: two more
+// (B, da) rows, the step's start x0 and the running sum S, flow_rk_scratch_bytes(d, B) in all.  FV_ERR_ARG for an unknown solver, FV_ERR_STATE without the rows
+size_t flow_rk_scratch_bytes(const HeadDims& d, int B);
 // the prefix sampler (d.pk > 0): row b's first min(delays[b], pd, pk - shift) steps are pinned to prev[b][k + shift] (normalised) from the start to the end; the
 // mask block of fusion.0 joins c once per call; three launches per step as launch_flow_sample, step C in its PREFIX instance.  Same scratch
 int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                               uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out, float* scratch,
-                              hipStream_t s, const HeadIoNorm* io);
+                              hipStream_t s, const HeadIoNorm* io, int solver = 0, float* rk_rows = nullptr);
 // guided sampling (fv_head_set_flow_guidance): step_w = chunk device floats >= 0, beta the largest guidance weight, live_steps = 1 + the last step whose
 // weight is not 0 (0: none).  prev (B, da): the previous chunk, normalised; Y[b][k] = prev[b][k + shift]; row_mask (B) int32 or null; chunk_out (B, da) or null:
 // the final normalised x_0.  A row with all-zero omega comes out as launch_flow_sample's row, bit for bit.  scratch: flow_guided_scratch_bytes(d, B)
@@ -364,7 +368,7 @@ struct HeadGuide { const float* step_w; int chunk; float beta; int live_steps; }
 size_t flow_guided_scratch_bytes(const HeadDims& d, int B);
 int launch_flow_sample_guided(const HeadDims& d, const HeadFlow& f, const HeadGuide& gd, const float* P, const float* pooled, const float* states, int B, int n_steps,
                               const float* noise, uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions,
-                              float* chunk_out, float* scratch, hipStream_t s, const HeadIoNorm* io);
+                              float* chunk_out, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver = 0, float* rk_rows = nullptr);
 // one guided step's forward and backward chain for given x (B, da), t and omega (B, da): v_out = v(x, t), jt_out = (dv / dx)^T omega.  Same scratch
 int launch_flow_vjp(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, const float* x, float t,
                     const float* omega, float* v_out, float* jt_out, float* scratch, hipStream_t s);

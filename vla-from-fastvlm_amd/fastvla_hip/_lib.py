@@ -75,6 +75,8 @@ class HeadFlowSpec(C.Structure):    # fv_head_flow_spec: 24 bytes
 
 
 FLOW_TIME_DISTS = {"uniform": 0, "logit_normal": 1}
+FLOW_SOLVERS = {"euler": 0, "midpoint": 1, "heun": 2, "rk4": 3}      # FV_FLOW_SOLVER_*
+FLOW_SOLVER_STAGES = {"euler": 1, "midpoint": 2, "heun": 2, "rk4": 4}      # network evaluations per step
 
 
 class ProfileEntry(C.Structure):
@@ -139,6 +141,7 @@ SIGNATURES = {
     "fv_head_set_flow_guidance": (_i, [_vp, _i, C.POINTER(_f), _f]),
     "fv_head_flow_sample_guided": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _i, _vp, _vp, _vp, _vp]),
     "fv_head_set_flow_prefix": (_i, [_vp, _i, _i, C.POINTER(C.c_uint32)]),
+    "fv_head_set_flow_solver": (_i, [_vp, _i]),
     "fv_head_flow_prepare_prefix": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fv_head_flow_sample_prefix": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _i, _vp, _vp, _vp, _vp]),
     "fv_ensemble_create": (_i, [_vp, _i, _i, _i, _f, C.POINTER(_vp)]),

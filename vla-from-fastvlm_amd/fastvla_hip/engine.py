@@ -110,6 +110,14 @@ def check_flow_draws(draws) -> int:
     return int(draws)
 
 
+def check_flow_solver(name) -> str:
+    """-> the solver's name in lower case; ValueError for anything but the keys of _lib.FLOW_SOLVERS"""
+    key = name.strip().lower() if isinstance(name, str) else name
+    if key not in _lib.FLOW_SOLVERS:
+        raise ValueError(f"flow_solver must be one of {list(_lib.FLOW_SOLVERS)}, got {name!r}")
+    return key
+
+
 def flow_draw_offset(offset: int, s: int) -> int:
     """the Philox offset draw s of a step at `offset` draws at: a single-draw call at this offset gives draw s's rows.  ValueError when the step's offset
     already uses the draw bits or s is outside 0 .. 15."""
@@ -175,6 +183,8 @@ class FastVLAEngine:
         self.head_flow_guidance: Optional[dict] = None            # set_head_flow_guidance: None = the unguided sampler only
         self.head_flow_draws = 1                                  # set_head_flow_draws: noise draws per observation in the training forms
         self.head_flow_prefix: Optional[dict] = None              # set_head_flow_prefix: None = no action-prefix conditioning
+        self.head_flow_solver = "euler"                           # set_head_flow_solver: the integrator of all three samplers
+        self.head_flow_solver_rows = False                        # True once a higher-order solver was named: the workspace plan holds its two rows
         self.loaded = False
 
     def close(self):
@@ -580,6 +590,7 @@ class FastVLAEngine:
             self.head_flow = None
             self.head_flow_draws = 1
             self.head_flow_prefix = None
+            self.head_flow_solver = "euler"
         else:
             if time_dist not in _lib.FLOW_TIME_DISTS:
                 raise ValueError(f"flow time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {time_dist!r}")
@@ -660,7 +671,7 @@ class FastVLAEngine:
 
     def head_flow_sample(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, *, steps: int = 10,
                          noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0) -> torch.Tensor:
-        """-> actions (B, da): `steps` Euler steps of the velocity field from x_1 = noise (None: drawn from (seed, offset)) to t = 0 (fv_head_flow_sample),
+        """-> actions (B, da): `steps` steps of the chosen solver (set_head_flow_solver; Euler by default) along the velocity field from x_1 = noise (None: drawn from (seed, offset)) to t = 0 (fv_head_flow_sample),
         un-normalised when set_io_norm is on.  Not differentiated."""
         B, da = pooled.shape[0], self.head_dims["da"]
         states = states.to(device=self.device, dtype=torch.float32).contiguous()
@@ -676,6 +687,16 @@ class FastVLAEngine:
         _lib.check(self.lib.fv_head_flow_sample(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed, offset,
                                                 actions.data_ptr(), _stream()), "fv_head_flow_sample", self.h)
         return actions
+
+    def set_head_flow_solver(self, name: str = "euler") -> None:
+        """The integrator of head_flow_sample, head_flow_sample_prefix and head_flow_sample_guided (fv_head_set_flow_solver): "euler" | "midpoint" | "heun" |
+        "rk4".  `steps` keeps meaning steps: a call makes steps x stages (1, 2, 2, 4) network evaluations.  The first call that names a higher-order solver
+        must come before the first workspace is bound (the library answers FV_ERR_STATE afterwards: the plan grows by two rows); later calls switch freely
+        among all four.  ValueError for an unknown name, before any library call."""
+        name = check_flow_solver(name)
+        _lib.check(self.lib.fv_head_set_flow_solver(self.h, _lib.FLOW_SOLVERS[name]), "fv_head_set_flow_solver", self.h)
+        self.head_flow_solver = name
+        self.head_flow_solver_rows = self.head_flow_solver_rows or name != "euler"
 
     def set_head_flow_guidance(self, step_weights=None, max_guidance_weight: float = 5.0) -> None:
         """Guidance of the flow sampler (fv_head_set_flow_guidance; real-time chunking): step_weights = K host floats >= 0 (fastvla_hip.rtc.prefix_weights),

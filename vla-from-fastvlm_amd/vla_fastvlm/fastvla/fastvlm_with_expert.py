@@ -103,15 +103,17 @@ class _FlowLossFunction(torch.autograd.Function):
 
 class FastVLMWithExpert(nn.Module):
     def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0, flow: Optional[dict] = None,
-                 flow_steps: int = 10, flow_seed: Optional[int] = None, flow_noise_draws: int = 1, flow_prefix: Optional[dict] = None) -> None:
+                 flow_steps: int = 10, flow_seed: Optional[int] = None, flow_noise_draws: int = 1, flow_prefix: Optional[dict] = None,
+                 flow_solver: str = "euler") -> None:
         """chunk_size = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
         `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library.
         flow = FastVLAEngine.set_head_flow's keyword arguments: the flow-matching head -- fusion.0 reads K * A + time_dim more columns (x_t and phi(t)),
-        head() samples with flow_steps Euler steps, head_loss() noises its targets and returns the predicted velocity.  flow_seed: the noise streams' seed
+        head() samples with flow_steps steps of flow_solver, head_loss() noises its targets and returns the predicted velocity.  flow_seed: the noise streams' seed
         (default: torch's initial seed, as the dropout stream's).  flow_noise_draws = S (1 .. 16): S noise draws (t, eps) per observation wherever targets are
         noised -- draw s of a call at offset o is the single draw of offset o + (s << 56); the velocity handed out is draw 0's.
         flow_prefix = fastvla_hip.prefix.check_prefix_config's result (flow head, K > 1): action-prefix conditioning -- fusion.0 reads K mask columns behind
-        phi(t), training gives the first d <= max_delay steps of a chunk to the network clean and keeps them out of the loss, rtc_sample pins them."""
+        phi(t), training gives the first d <= max_delay steps of a chunk to the network clean and keeps them out of the loss, rtc_sample pins them.
+        flow_solver: "euler" | "midpoint" | "heun" | "rk4", the integrator of every sampling route (flow_steps are steps of it); a property of the run."""
         super().__init__()
         from fastvla_hip.engine import check_flow_draws, check_head_loss
         self.flow_noise_draws = check_flow_draws(flow_noise_draws)
@@ -133,6 +135,12 @@ class FastVLMWithExpert(nn.Module):
         self.flow_prefix: Optional[dict] = None if flow_prefix is None else dict(flow_prefix)
         self.backbone.configure_head_flow_prefix(self.flow_prefix)
         self.backbone.configure_head_flow_draws(self.flow_noise_draws)
+        from fastvla_hip.engine import check_flow_solver
+        self._flow_solver = check_flow_solver(flow_solver)
+        if self._flow_solver != "euler" and flow is None:
+            raise ValueError(f"flow_solver={self._flow_solver!r} needs action_head='flow' (the regression head integrates nothing)")
+        self._flow_solver_rows = self._flow_solver != "euler"      # a policy built with a higher-order solver reserved their rows and may switch among all four
+        self.backbone.configure_head_flow_solver(self._flow_solver)
         self.rtc: Optional[dict] = None      # configure_rtc: real-time chunking of the flow sampler, a property of the run
         self._chunker = self._rtc_key = None
         extra = self.head_width + int(self.flow["time_dim"]) + (self.chunk_size if self.flow_prefix else 0) if self.flow else 0
@@ -185,13 +193,38 @@ class FastVLMWithExpert(nn.Module):
         self._flow_eval_index = 0
         return super().train(mode)
 
+    def flow_error_draw(self):
+        """action_error_per_dim: ONE fixed offset in a range of its own (bit 63) -- two calls sample from the same noise, and no counter advances"""
+        return self._flow_seed, 1 << 63
+
+    @property
+    def flow_solver(self) -> str:
+        """"euler" | "midpoint" | "heun" | "rk4": the integrator of every sampling route"""
+        return self._flow_solver
+
+    @flow_solver.setter
+    def flow_solver(self, name: str) -> None:
+        from fastvla_hip.engine import check_flow_solver
+        name = check_flow_solver(name)
+        if self.flow is None:
+            raise ValueError(f"flow_solver={name!r} needs action_head='flow' (the regression head integrates nothing)")
+        if name != "euler" and not self._flow_solver_rows:
+            raise ValueError(f"flow_solver={name!r}: this policy was built with flow_solver='euler', so the two rows a higher-order solver works over were "
+                             "not reserved in the workspace -- build the policy with flow_solver='midpoint' | 'heun' | 'rk4' (or FASTVLA_FLOW_SOLVER); it may "
+                             "then switch among all four at any time")
+        self.backbone.configure_head_flow_solver(name)
+        self._flow_solver = name
+
     def flow_record(self) -> Optional[dict]:
-        """hip_extras.json "action_head": there only in flow mode"""
+        """hip_extras.json "action_head": there only in flow mode ("solver" only when it is not Euler: an Euler run writes the record it wrote)"""
         if self.flow is None:
             return None
         from fastvla_hip import prefix as _prefix
-        return {"type": "flow", "steps": int(self.flow_steps), **{k: self.flow[k] for k in ("time_dim", "min_period", "max_period", "time_dist", "dist_a", "dist_b")},
-                "seed": int(self._flow_seed), **_prefix.extras_record(self.flow_prefix)}
+        rec = {"type": "flow", "steps": int(self.flow_steps), **{k: self.flow[k] for k in ("time_dim", "min_period", "max_period", "time_dist", "dist_a", "dist_b")},
+               "seed": int(self._flow_seed), **_prefix.extras_record(self.flow_prefix)}
+        if self._flow_solver != "euler":
+            rec["solver"] = self._flow_solver
+        return rec
 
     # ------------------------------------------------------------------ flat parameter storage
     def head_parameters(self):
@@ -258,14 +291,33 @@ class FastVLMWithExpert(nn.Module):
 
     def action_error_per_dim(self, pooled: torch.Tensor, states: torch.Tensor, targets: torch.Tensor, pad=None) -> torch.Tensor:
         """-> (A,): mean |prediction - target| over the non-padded steps of each action dimension, in the normalised space the loss lives in (what the
-        per-dimension weights are tuned against); never weighted, no gradient."""
+        per-dimension weights are tuned against); never weighted, no gradient.  A flow head SAMPLES one chunk per row with the policy's solver and step
+        count, from the flow seed's noise at a fixed offset (flow_error_draw): two calls on the same weights agree bit for bit and the sampling counter
+        does not advance -- the action-space metric a solver and a step count are chosen with.  (A prefix-width head samples with m = 0.)"""
         self.materialize(pooled.device)
         targets, pad = self.chunk_targets(targets.to(pooled.device, torch.float32), pad)
         if targets.shape != (pooled.shape[0], self.head_width):
             raise ValueError(f"targets must be (B,{self.config.action_dim}), got {tuple(targets.shape)}")
         eng = self._engine()
         if self.flow is not None:
-            raise RuntimeError("action_error_per_dim: the flow head predicts velocities of noised targets, not actions; sample with predict() and compare outside")
+            with torch.no_grad():
+                seed, offset = self.flow_error_draw()
+                # the prefix sampler with a delay of 0 everywhere: nothing pinned, m = 0, and chunk_out is the sample BEFORE the folded un-normalisation
+                # (fv_head_flow_sample_prefix's pinned-step clamp selects; with p_b = 0 the previous chunk is never read)
+                zeros = torch.zeros(pooled.shape[0], self.head_width, dtype=torch.float32, device=pooled.device)
+                if self.flow_prefix is not None:
+                    _, chunk = eng.head_flow_sample_prefix(self._flat, pooled, states.to(pooled.device, torch.float32), zeros,
+                                                           torch.zeros(pooled.shape[0], dtype=torch.int32, device=pooled.device), steps=self.flow_steps, seed=seed,
+                                                           offset=offset)
+                else:
+                    chunk = eng.head_flow_sample(self._flat, pooled, states.to(pooled.device, torch.float32), steps=self.flow_steps, seed=seed, offset=offset)
+                    io = self.backbone._io_norm
+                    if io is not None:      # the plain sampler hands out un-normalised actions only: undo the folded x std + mean (one rounding each way)
+                        std = torch.as_tensor(io["action_std"], dtype=torch.float32, device=chunk.device).reshape(1, -1).repeat(1, self.chunk_size)
+                        mean = torch.as_tensor(io["action_mean"], dtype=torch.float32, device=chunk.device).reshape(1, -1).repeat(1, self.chunk_size)
+                        chunk = torch.where(std > 0, (chunk - mean) / std, torch.zeros_like(chunk))
+                S = self.flow_noise_draws      # (the metric kernel counts head rows in draws: every draw sees the one sampled chunk)
+                return eng.head_loss_per_dim(chunk.repeat(S, 1) if S > 1 else chunk, targets.repeat(S, 1) if S > 1 else targets.contiguous(), pad=pad)
         with torch.no_grad():
             actions, _saved = eng.head_forward(self._flat, pooled, states.to(pooled.device, torch.float32), normalized_actions=True)
             return eng.head_loss_per_dim(actions, targets.contiguous(), pad=pad)

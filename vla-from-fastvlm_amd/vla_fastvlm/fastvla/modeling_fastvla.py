@@ -98,6 +98,30 @@ def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, 
     return {"action_head": head, "steps": int(steps), "flow": flow}
 
 
+def resolve_flow_solver(flow_solver=None, *, action_head: str) -> str:
+    """-> "euler" | "midpoint" | "heun" | "rk4", the integrator of a flow head's samplers: the explicit argument, else FASTVLA_FLOW_SOLVER, else "euler".  The
+    twin is read and checked for a flow head only, like the other FASTVLA_FLOW_* twins.  ValueError, naming both settings and before any engine exists, for
+    an unknown name or an explicit flow_solver with the regression head."""
+    from fastvla_hip.engine import check_flow_solver
+    if flow_solver is not None:      # an explicit argument is checked whatever the head is
+        try:
+            name = check_flow_solver(flow_solver)
+        except ValueError:
+            raise ValueError(f"flow_solver must be 'euler', 'midpoint', 'heun' or 'rk4'. Got flow_solver={flow_solver!r}, action_head={action_head!r}.") from None
+        if action_head != "flow":
+            raise ValueError(f"flow_solver needs action_head='flow' (the regression head integrates nothing). Got flow_solver={name!r}, action_head={action_head!r}.")
+        return name
+    if action_head != "flow":
+        return "euler"
+    raw = (os.environ.get("FASTVLA_FLOW_SOLVER") or "").strip()
+    if not raw:
+        return "euler"
+    try:
+        return check_flow_solver(raw)
+    except ValueError:
+        raise ValueError(f"FASTVLA_FLOW_SOLVER must be 'euler', 'midpoint', 'heun' or 'rk4'. Got FASTVLA_FLOW_SOLVER={raw!r}, action_head={action_head!r}.") from None
+
+
 def resolve_flow_noise_draws(flow_noise_draws=None, *, action_head: str) -> int:
     """-> S, the noise draws per observation of a flow head's training and loss evaluations: the explicit argument, else FASTVLA_FLOW_NOISE_DRAWS, else 1.  The
     twin is read and checked for a flow head only, like the other FASTVLA_FLOW_* twins.  ValueError, naming both settings and before any engine exists, for
@@ -225,7 +249,8 @@ class FastVLAPolicy(nn.Module, EmaMixin):
                  flow_time_dim: Optional[int] = None, flow_time_dist: Optional[str] = None, flow_seed: Optional[int] = None, rtc: Optional[bool] = None,
                  rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None,
                  flow_noise_draws: Optional[int] = None, flow_prefix_max_delay: Optional[int] = None, flow_prefix_delay_dist: Optional[str] = None,
-                 flow_prefix_delay_rate: Optional[float] = None, rtc_method: Optional[str] = None, rtc_prefix_steps: Optional[int] = None) -> None:
+                 flow_prefix_delay_rate: Optional[float] = None, rtc_method: Optional[str] = None, rtc_prefix_steps: Optional[int] = None,
+                 flow_solver: Optional[str] = None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
@@ -240,7 +265,7 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         action_head="flow" (default "regression"; FASTVLA_ACTION_HEAD): the flow-matching head (pi0 / SmolVLA convention, normalised action space).  The same
         12 tensors, fusion.0 reading K * A + flow_time_dim more columns; training noises the targets (x_t = t eps + (1 - t) a, t ~ flow_time_dist "uniform" |
         "logit_normal") and the configured loss, mask and weights compare the predicted velocity with u = eps - a; predict / select_action_chunk /
-        select_action SAMPLE: flow_steps Euler steps from fresh noise (policy.flow_steps may be changed at any time), the queue and the temporal ensembling
+        select_action SAMPLE: flow_steps steps of the chosen solver from fresh noise (policy.flow_steps may be changed at any time), the queue and the temporal ensembling
         work on the sampled chunk as ever.  compute_loss / forward(batch) / the train step return the PREDICTED VELOCITY (normalised space) where the
         regression head returns actions.  In eval() mode the noise of a loss evaluation depends on the evaluation batch index only: two evaluations of the
         same weights give the same loss.  predict with autograd enabled on the head raises RuntimeError: sampling is not differentiated.  flow_seed: the noise
@@ -272,7 +297,14 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         min(rtc_prefix_steps, D, K - shift) steps to the last chunk read `shift` = the actions served since steps ahead and samples the rest with the plain
         three-launch sampler -- no guidance, no Jacobian, no beta; rtc_prefix_steps defaults to D (FASTVLA_RTC_PREFIX_STEPS).  The first plan after reset()
         pins nothing.  select_action_chunk(..., prev_chunk=, inference_delay=d) pins d <= D steps (ValueError above D).  rtc_schedule,
-        rtc_max_guidance_weight and rtc_execution_horizon given together with "prefix" are refused."""
+        rtc_max_guidance_weight and rtc_execution_horizon given together with "prefix" are refused.
+
+        flow_solver="euler" | "midpoint" | "heun" | "rk4" (flow head; default "euler"; FASTVLA_FLOW_SOLVER): the integrator of EVERY sampling route -- predict /
+        select_action / select_action_chunk, rtc with either method -- (fv_head_set_flow_solver).  flow_steps keeps meaning steps: a sample costs flow_steps x
+        (1, 2, 2, 4) network evaluations, and at an equal number of evaluations a higher-order solver ends one to two orders closer to the exact flow
+        (DESIGN.md section 7); action_error_per_dim(batch) is the action-space metric to choose a solver and a step count with.  policy.flow_solver may be
+        changed at any time on a policy BUILT with a higher-order solver (the workspace holds their two rows); a policy built with "euler" raises ValueError.
+        A property of the run: hip_extras.json records it only when it is not Euler.  ValueError with a regression head."""
         super().__init__()
         self.config = config or FastVLAConfig()
         opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
@@ -283,6 +315,7 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist)
         self.action_head = fopts["action_head"]
         self.flow_noise_draws: int = resolve_flow_noise_draws(flow_noise_draws, action_head=self.action_head)      # (before any engine exists)
+        solver = resolve_flow_solver(flow_solver, action_head=self.action_head)      # (likewise)
         popts = resolve_prefix_options(flow_prefix_max_delay, flow_prefix_delay_dist, flow_prefix_delay_rate, action_head=self.action_head,      # (likewise)
                                        chunk_size=opts["chunk_size"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
         self.flow_prefix: Optional[Dict] = popts
@@ -290,7 +323,7 @@ class FastVLAPolicy(nn.Module, EmaMixin):
                                     chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"],
                                     rtc_method=rtc_method, rtc_prefix_steps=rtc_prefix_steps, prefix=popts)
         self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"],
-                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws, flow_prefix=popts)
+                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts
@@ -437,7 +470,8 @@ class FastVLAPolicy(nn.Module, EmaMixin):
     @torch.no_grad()
     def action_error_per_dim(self, batch: Dict[str, torch.Tensor | List[str]]) -> torch.Tensor:
         """-> (A,): mean |prediction - target| per action dimension over the batch's non-padded steps (normalised space, unweighted): what the per-dimension
-        weights are tuned against.  Runs on demand, outside the train step."""
+        weights are tuned against.  Runs on demand, outside the train step.  A flow head samples one chunk per row with policy.flow_solver and
+        policy.flow_steps from noise at a fixed offset of the flow seed: repeatable, and the sampling counter does not advance."""
         images, states, tasks = batch["images"], batch["states"], batch["tasks"]
         device = images.device
         images = self.processor.prepare_images(images, device)
@@ -453,7 +487,7 @@ class FastVLAPolicy(nn.Module, EmaMixin):
 
     @property
     def flow_steps(self) -> int:
-        """Euler steps of a flow head's sampler (ignored by the regression head); may be changed at any time"""
+        """steps of the chosen solver (flow_solver) in a flow head's samplers (ignored by the regression head); may be changed at any time"""
         return self.model.flow_steps
 
     @flow_steps.setter
@@ -461,6 +495,16 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         if int(n) != n or n < 1:
             raise ValueError(f"flow_steps must be an integer >= 1, got {n}")
         self.model.flow_steps = int(n)
+
+    @property
+    def flow_solver(self) -> str:
+        """"euler" | "midpoint" | "heun" | "rk4": the integrator of every sampling route of a flow head.  A policy built with a higher-order solver may switch
+        among all four at any time; one built with "euler" raises ValueError (the rows a higher-order solver works over were not reserved)"""
+        return self.model.flow_solver
+
+    @flow_solver.setter
+    def flow_solver(self, name: str) -> None:
+        self.model.flow_solver = name
 
     @torch.inference_mode()
     def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device, prev_chunk: Optional[torch.Tensor] = None,

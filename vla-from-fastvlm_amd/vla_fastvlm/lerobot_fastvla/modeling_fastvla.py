@@ -16,7 +16,11 @@ environments in one call; predict_action_chunk(batch, inference_delay=, prev_chu
 
 Action-prefix conditioning (no config field): FastVLAPolicy(config, action_head="flow", flow_prefix_max_delay=D, flow_prefix_delay_dist=,
 flow_prefix_delay_rate=) or the FASTVLA_FLOW_PREFIX_* twins train the head with a clean prefix of d <= D steps; rtc=True, rtc_method="prefix"
-(FASTVLA_RTC_METHOD) then pins the first steps of every re-plan to the previous chunk with the plain sampler's three launches per step."""
+(FASTVLA_RTC_METHOD) then pins the first steps of every re-plan to the previous chunk with the plain sampler's three launches per step.
+
+Higher-order integrators (no config field): FastVLAPolicy(config, action_head="flow", flow_solver="midpoint" | "heun" | "rk4") or FASTVLA_FLOW_SOLVER: every
+sampling route -- predict_action_chunk, select_action, rtc with either method -- integrates with it, flow_steps being steps of the chosen solver;
+policy.flow_solver switches among all four on a policy built with a higher-order one."""
 from __future__ import annotations
 
 from collections import deque
@@ -45,7 +49,8 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        from ..fastvla.modeling_fastvla import resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_prefix_options, resolve_rtc_options
+        from ..fastvla.modeling_fastvla import (resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_flow_solver, resolve_prefix_options,
+                                                resolve_rtc_options)
         opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
                                      temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
                                      action_step_weights=kwargs.get("action_step_weights"))
@@ -57,6 +62,8 @@ class FastVLAPolicy(PreTrainedPolicy):
         fopts = resolve_flow_options(kwargs.get("action_head"), kwargs.get("flow_steps"), kwargs.get("flow_time_dim"), kwargs.get("flow_time_dist"))
         self.action_head = fopts["action_head"]
         self.flow_noise_draws: int = resolve_flow_noise_draws(kwargs.get("flow_noise_draws"), action_head=self.action_head)
+        # flow_solver= (FASTVLA_FLOW_SOLVER; no config field): the integrator of every sampling route, a property of the run
+        solver = resolve_flow_solver(kwargs.get("flow_solver"), action_head=self.action_head)
         # real-time chunking (FastVLAPolicy(config, rtc=True, rtc_schedule=, rtc_max_guidance_weight=, rtc_execution_horizon=) or the FASTVLA_RTC* twins; no
         # config field): re-plans of a flow head are sampled guided by the rest of the previous chunk, for all B environments of the batch in one call
         popts = resolve_prefix_options(kwargs.get("flow_prefix_max_delay"), kwargs.get("flow_prefix_delay_dist"), kwargs.get("flow_prefix_delay_rate"),
@@ -69,7 +76,7 @@ class FastVLAPolicy(PreTrainedPolicy):
         self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
         self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
                                        action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"], flow_steps=fopts["steps"],
-                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws, flow_prefix=popts)
+                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver)
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts
@@ -79,7 +86,7 @@ class FastVLAPolicy(PreTrainedPolicy):
 
     @property
     def flow_steps(self) -> int:
-        """Euler steps of a flow head's sampler (ignored by the regression head); may be changed at any time"""
+        """steps of the chosen solver (flow_solver) in a flow head's samplers (ignored by the regression head); may be changed at any time"""
         return self.model.flow_steps
 
     @flow_steps.setter
@@ -87,6 +94,16 @@ class FastVLAPolicy(PreTrainedPolicy):
         if int(n) != n or n < 1:
             raise ValueError(f"flow_steps must be an integer >= 1, got {n}")
         self.model.flow_steps = int(n)
+
+    @property
+    def flow_solver(self) -> str:
+        """"euler" | "midpoint" | "heun" | "rk4": the integrator of every sampling route of a flow head.  A policy built with a higher-order solver may switch
+        among all four at any time; one built with "euler" raises ValueError (the rows a higher-order solver works over were not reserved)"""
+        return self.model.flow_solver
+
+    @flow_solver.setter
+    def flow_solver(self, name: str) -> None:
+        self.model.flow_solver = name
 
     def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
         """the loss forward(batch) evaluates from now on: "mse" | "l1" | "smooth_l1" (beta)"""
@@ -98,7 +115,8 @@ class FastVLAPolicy(PreTrainedPolicy):
 
     @torch.no_grad()
     def action_error_per_dim(self, batch: dict[str, Tensor]) -> Tensor:
-        """-> (A,): mean |prediction - target| per action dimension over the batch's non-padded steps (normalised space, unweighted)"""
+        """-> (A,): mean |prediction - target| per action dimension over the batch's non-padded steps (normalised space, unweighted).  A flow head samples
+        one chunk per row with flow_solver and flow_steps from noise at a fixed offset of the flow seed: repeatable, the sampling counter does not advance"""
         images, states, tasks = self._prepare_inputs(batch)
         pad = batch.get("action_is_pad") if self.model.chunk_size > 1 else None
         targets, pad = self.model.chunk_targets(batch[ACTION], pad)

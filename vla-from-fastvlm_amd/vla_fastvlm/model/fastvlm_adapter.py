@@ -190,6 +190,8 @@ class FastVLMBackbone(nn.Module):
         self._head_flow_draws = 1                               # configure_head_flow_draws: FastVLAEngine.set_head_flow_draws' argument, 1 = one draw per observation
         self._head_flow_guidance: Optional[dict] = None         # configure_head_flow_guidance: FastVLAEngine.set_head_flow_guidance's arguments, None = off
         self._head_flow_prefix: Optional[dict] = None           # configure_head_flow_prefix: {"chunk", "max_delay", "thresholds", "dist", "rate"}, None = off
+        self._head_flow_solver = "euler"                        # configure_head_flow_solver: FastVLAEngine.set_head_flow_solver's argument
+        self._head_flow_solver_rows = False                     # True once a higher-order solver was configured: an engine is built with its two rows reserved
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
 
@@ -287,6 +289,18 @@ class FastVLMBackbone(nn.Module):
         if self._engine is not None and draws != self._head_flow_draws:
             raise RuntimeError("configure_head_flow_draws: the engine is already built (the saved activations and the workspaces depend on the number of draws)")
         self._head_flow_draws = draws
+
+    def configure_head_flow_solver(self, name: str = "euler") -> None:
+        """The integrator of the flow samplers (FastVLAEngine.set_head_flow_solver).  Kept for the engine's construction, where a higher-order solver reserves
+        its two rows before any workspace is bound; an engine that already exists is told at once (the library refuses a FIRST higher-order solver then)."""
+        from fastvla_hip.engine import check_flow_solver
+        name = check_flow_solver(name)
+        if name != "euler" and self._head_flow is None:
+            raise ValueError(f"flow_solver={name!r} needs action_head='flow' (the regression head integrates nothing)")
+        if self._engine is not None and (name != "euler" or self._engine.head_flow_solver != "euler"):
+            self._engine.set_head_flow_solver(name)
+        self._head_flow_solver = name
+        self._head_flow_solver_rows = self._head_flow_solver_rows or name != "euler"
 
     def configure_head_flow_guidance(self, guidance: Optional[dict]) -> None:
         """Guidance of the flow sampler (FastVLAEngine.set_head_flow_guidance's keyword arguments; None = off).  Kept for the engine's construction, where it
@@ -394,6 +408,9 @@ class FastVLMBackbone(nn.Module):
                     eng.set_head_flow_draws(self._head_flow_draws)
                 if getattr(self, "_head_flow_guidance", None) is not None:
                     eng.set_head_flow_guidance(**self._head_flow_guidance)
+                if getattr(self, "_head_flow_solver_rows", False):      # (a policy switched back to Euler keeps its rows: it may switch again)
+                    eng.set_head_flow_solver(self._head_flow_solver if self._head_flow_solver != "euler" else "midpoint")
+                    eng.set_head_flow_solver(self._head_flow_solver)
             if self._head_loss != dict(kind="mse", beta=1.0, chunk=1):
                 eng.set_head_loss(**self._head_loss)
             if self._head_loss_weights is not None:

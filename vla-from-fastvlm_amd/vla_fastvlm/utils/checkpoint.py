@@ -159,8 +159,11 @@ def flow_kwargs(rec) -> dict:
     if theirs != ours:
         raise ValueError(f"the checkpoint's action_head record was written with {theirs}, this build's flow head uses {ours}: the time embedding / time "
                          "distribution would differ from the one the weights were trained with")
-    return {"action_head": "flow", "flow_steps": int(rec.get("steps", 10)), "flow_time_dim": int(rec["time_dim"]), "flow_time_dist": rec.get("time_dist", "uniform"),
-            "flow_seed": rec.get("seed")}
+    kw = {"action_head": "flow", "flow_steps": int(rec.get("steps", 10)), "flow_time_dim": int(rec["time_dim"]), "flow_time_dist": rec.get("time_dist", "uniform"),
+          "flow_seed": rec.get("seed")}
+    if rec.get("solver"):      # (written only when it is not Euler: an Euler run's record, and what it maps to, is what it was)
+        kw["flow_solver"] = str(rec["solver"])
+    return kw
 
 
 def prefix_kwargs(rec) -> dict:
