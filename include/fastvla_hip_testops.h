@@ -3,7 +3,8 @@
  * Built by `make -C vla-from-fastvlm_amd/csrc` into vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so (csrc/ops_api.hip); its undefined `fv::launch_*`
  * references resolve against an already loaded libfastvla_hip.so (fastvla_hip._lib.load_testops() loads the product library RTLD_GLOBAL first).
  * Nothing of the product (fastvla_hip/, vla_fastvlm/, bench.py's timed region, __graft_entry__) binds these symbols: they exist so that
- * tests/test_gpu_ops.py and tools/ can check and time each kernel on its own against the oracle's op.  The product ABI a maintainer binds is
+ * tests/test_gpu_ops.py, its sibling op-level files (tests/test_gpu_dw_backward.py: every kernel instance and route of the depthwise backward, input gradient
+ * included) and tools/ can check and time each kernel on its own against the oracle's op.  The product ABI a maintainer binds is
  * include/fastvla_hip.h alone.  (The epilogue enum lives here because only these entry points take it as an argument; the library's own
  * sources include this header for it.) */
 #ifndef FASTVLA_HIP_TESTOPS_H
@@ -187,6 +188,18 @@ int fv_op_gemm_f16_gelup(const void* A, int lda, const void* W, int M, int N, in
  * dw f32 tap-major [k*k][C*mult], db f32 [C*mult]; scratch_floats >= (B * ceil(W / 32) or 512) * (k*k + 1) * C*mult (the call checks).  Stride-1 maps with C % 32 == 0,
  * W >= 32, H >= 16 and k = 7 run on the matrix cores (dw_wgrad_mfma_kernel, round 6), everything else on the VALU forms. */
 int fv_op_dw_wgrad(const void* x, const void* dy, float* dw, float* db, float* scratch, size_t scratch_floats, int B, int H, int W, int C, int k, int stride, int mult, fv_stream s);
+/* the INPUT gradient of the same convs, one entry point per route of the tower's backward (tests/test_gpu_dw_backward.py drives every kernel instance of the
+ * depthwise backward through these two and fv_op_dw_wgrad): dy fp16 bits (B,Ho,Wo,Ci*mult), res (may be NULL) and dx fp16 bits (B,Hi,Wi,Ci), dx = res + conv^T(dy),
+ * saturating; *sat (may be NULL) goes up by one for every (pixel, 8-channel group) cell that holds a clamped value.  Arguments are checked before anything is
+ * enqueued.
+ *   fv_op_dw_dgrad: dw_dgrad_kernel<k, stride, mult>, (k, stride, mult) one of (3,1,1) (7,1,1) (3,2,1) (7,2,2) (3,1,2); w fp32 tap-major [k*k][Ci*mult]; round_w = 1
+ *     rounds the taps to bf16 first (the forward ran on a bf16 Toeplitz table).  A cell counts when res + conv^T(dy), summed in fp32, leaves +-65504.
+ *   fv_op_dw_dgrad_mfma: dwconv_march_kernel<k, GRAD> (stride 1, mult 1, k = 3 / 7, C % 32 == 0, W >= 16, H >= 16: anything else is refused); ttab16 = the fp16
+ *     Toeplitz table of the FLIPPED taps (tap t takes tap k*k-1-t).  conv^T(dy) crosses LDS in fp16 cells (two per value under a residual, so the sum is rounded
+ *     once); a cell counts when conv^T(dy) itself or the final sum leaves +-65504, and a conv^T(dy) that does is written as +-65504 whatever res holds. */
+int fv_op_dw_dgrad(const void* dy, const float* w, const void* res, void* dx, int B, int Hi, int Wi, int Ci, int k, int stride, int mult, int round_w, unsigned* sat,
+                   fv_stream s);
+int fv_op_dw_dgrad_mfma(const void* dy, const void* ttab16, const void* res, void* dx, int B, int H, int W, int C, int k, unsigned* sat, fv_stream s);
 int fv_op_convffn32_split(const void* x, const void* wq, const float* b1, const float* b2, const float* ls, const void* res, void* out,
                           int M, int C, float* part, size_t part_bytes, fv_stream s);
 

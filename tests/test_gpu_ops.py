@@ -14,6 +14,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from gpu_util import DEV, bf, call, check_close, dev_bf16, dev_f32, lib, stream  # noqa: E402
+from dw_bwd_util import toeplitz as _toeplitz  # noqa: E402  (the Toeplitz table of the MFMA depthwise kernels: shared with tests/test_gpu_dw_backward.py)
 from fastvla_hip import _lib  # noqa: E402
 from oracle import fastvit_hd, preprocess, qwen2  # noqa: E402
 
@@ -505,21 +506,6 @@ def test_dw_wgrad_matches_autograd(k, C, H, W, B):
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])      # fixed-order partial sums: bit-repeatable
     check_close(outs[0][0], ref_w, rel=2e-5, amax=1e-4, what=f"dw{k}x{k} tap gradients C={C} {H}x{W}")
     check_close(outs[0][1], ref_b, rel=2e-5, amax=1e-4, what=f"dw{k}x{k} bias gradient C={C} {H}x{W}")
-
-
-def _toeplitz(w, k):
-    """depthwise weights (C,1,k,k) -> bf16 table [C/16][k][NM][16][4 i][4 kk] = w[ky][4m + kk - i] (fastvla_hip.h)."""
-    Cc = w.shape[0]
-    nm = (k + 6) // 4
-    t = torch.zeros(Cc // 16, k, nm, 16, 4, 4)
-    wv = w.view(Cc // 16, 16, k, k)
-    for m in range(nm):
-        for i in range(4):
-            for kk in range(4):
-                kx = 4 * m + kk - i
-                if 0 <= kx < k:
-                    t[:, :, m, :, i, kk] = wv[:, :, :, kx].permute(0, 2, 1)
-    return t
 
 
 @pytest.mark.parametrize("k,C,H,W,gelu", [(7, 32, 8, 32, 0), (7, 96, 40, 64, 0), (3, 64, 33, 47, 0), (7, 64, 19, 33, 1),

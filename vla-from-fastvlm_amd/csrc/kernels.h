@@ -241,7 +241,8 @@ int launch_dw_dgrad(const bf16_t* dy, const float* w, const bf16_t* res, bf16_t*
                     hipStream_t s, int round_w = 0);   // round_w: taps rounded to bf16 first (the forward ran on a bf16 Toeplitz table)
 // the same input gradient on the marching MFMA depthwise kernel (stride 1, W >= 16, H >= 16, C % 32 == 0): ttab16 = fp16 Toeplitz table of the flipped taps
 bool dw_dgrad_mfma_supported(int H, int W, int C, int k);
-int launch_dw_dgrad_mfma(const bf16_t* dy, const bf16_t* ttab16, const bf16_t* res, bf16_t* dx, int B, int H, int W, int C, int k, hipStream_t s);
+int launch_dw_dgrad_mfma(const bf16_t* dy, const bf16_t* ttab16, const bf16_t* res, bf16_t* dx, int B, int H, int W, int C, int k, unsigned* sat,
+                         hipStream_t s);   // sat: counts the (pixel, 8-channel group) cells that clamp, as launch_dw_dgrad's does (may be null)
 int launch_dw_wgrad(const bf16_t* x, const bf16_t* dy, float* dw, float* db, float* scratch, int B, int Hi, int Wi, int Ci, int k, int stride, int mult,
                     hipStream_t s);
 constexpr int TOWER_COLSUM_CHUNKS = 512;   // row ranges of the tower backward's column sums (10^5 .. 10^6 rows of 96 .. 1536 columns: the grid must fill the chip)

@@ -260,6 +260,32 @@ int fv_op_dw_wgrad(const void* x, const void* dy, float* dw, float* db, float* s
   return fv::launch_dw_wgrad(static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(dy), dw, db, scratch, B, H, W, C, k, stride, mult, static_cast<hipStream_t>(s));
 }
 
+// input gradient of a depthwise / channel-multiplier conv, both routes of the tower's backward.  Every argument is checked here, before the launcher is entered:
+// a refused call enqueues nothing
+static bool dw_op_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+int fv_op_dw_dgrad(const void* dy, const float* w, const void* res, void* dx, int B, int Hi, int Wi, int Ci, int k, int stride, int mult, int round_w, unsigned* sat,
+                   fv_stream s) {
+  if (!dy || !w || !dx) return fv_fail(FV_ERR_ARG, "fv_op_dw_dgrad: null pointer");
+  if (!dw_op_aligned16(dy) || !dw_op_aligned16(w) || !dw_op_aligned16(res) || !dw_op_aligned16(dx) || (reinterpret_cast<uintptr_t>(sat) & 3))
+    return fv_fail(FV_ERR_ARG, "fv_op_dw_dgrad: dy, w, res, dx must be 16-byte aligned");
+  if (B <= 0 || Hi <= 0 || Wi <= 0 || Ci <= 0 || Ci % 8) return fv_fail(FV_ERR_ARG, "fv_op_dw_dgrad: bad shape B=%d %dx%d C=%d", B, Hi, Wi, Ci);
+  const bool inst = (k == 3 && stride == 1 && mult == 1) || (k == 7 && stride == 1 && mult == 1) || (k == 3 && stride == 2 && mult == 1) ||
+                    (k == 7 && stride == 2 && mult == 2) || (k == 3 && stride == 1 && mult == 2);
+  if (!inst) return fv_fail(FV_ERR_UNSUPPORTED, "fv_op_dw_dgrad: unsupported k=%d stride=%d mult=%d", k, stride, mult);
+  if (round_w != 0 && round_w != 1) return fv_fail(FV_ERR_ARG, "fv_op_dw_dgrad: round_w is 0 or 1");
+  return fv::launch_dw_dgrad(static_cast<const bf16_t*>(dy), w, static_cast<const bf16_t*>(res), static_cast<bf16_t*>(dx), B, Hi, Wi, Ci, k, stride, mult, sat,
+                             static_cast<hipStream_t>(s), round_w);
+}
+int fv_op_dw_dgrad_mfma(const void* dy, const void* ttab16, const void* res, void* dx, int B, int H, int W, int C, int k, unsigned* sat, fv_stream s) {
+  if (!dy || !ttab16 || !dx) return fv_fail(FV_ERR_ARG, "fv_op_dw_dgrad_mfma: null pointer");
+  if (!dw_op_aligned16(dy) || !dw_op_aligned16(ttab16) || !dw_op_aligned16(res) || !dw_op_aligned16(dx) || (reinterpret_cast<uintptr_t>(sat) & 3))
+    return fv_fail(FV_ERR_ARG, "fv_op_dw_dgrad_mfma: dy, ttab16, res, dx must be 16-byte aligned");
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return fv_fail(FV_ERR_ARG, "fv_op_dw_dgrad_mfma: bad shape B=%d %dx%d C=%d", B, H, W, C);
+  if (!fv::dw_dgrad_mfma_supported(H, W, C, k)) return fv_fail(FV_ERR_UNSUPPORTED, "fv_op_dw_dgrad_mfma: unsupported shape H=%d W=%d C=%d k=%d", H, W, C, k);
+  return fv::launch_dw_dgrad_mfma(static_cast<const bf16_t*>(dy), static_cast<const bf16_t*>(ttab16), static_cast<const bf16_t*>(res), static_cast<bf16_t*>(dx), B, H,
+                                  W, C, k, sat, static_cast<hipStream_t>(s));
+}
+
 int fv_op_convffn32_split(const void* x, const void* wq, const float* b1, const float* b2, const float* ls, const void* res, void* out,
                           int M, int C, float* part, size_t part_bytes, fv_stream s) {
   return fv::launch_convffn32(static_cast<const bf16_t*>(x), static_cast<const bf16_t*>(wq), b1, b2, ls, static_cast<const bf16_t*>(res),

@@ -1288,13 +1288,30 @@ static int dw_wgrad_row_blocks(int nrows, int NPS, int nslabs) {
   if (nrb > cap) nrb = cap;
   return nrb < 1 ? 1 : nrb;
 }
+// blocks of dw_wgrad_lds_kernel: a group = NPS consecutive output rows of one image, gpb groups per block.  Two blocks are resident per CU (190 registers, 80 KB
+// of LDS each): 512 blocks are ONE round of a 256-CU chip, and every block more is another partial-sum row for the reduce pass to read
+struct DwWgLdsBlocks { int gpi, ngroups, gpb, nb; };
+static DwWgLdsBlocks dw_wgrad_lds_blocks(int B, int Ho, int NPS, int nslabs) {
+  DwWgLdsBlocks g;
+  g.gpi = (Ho + NPS - 1) / NPS;
+  g.ngroups = B * g.gpi;
+  int nb = 512 / nslabs;
+  if (nb < 1) nb = 1;
+  if (nb > g.ngroups) nb = g.ngroups;
+  g.gpb = (g.ngroups + nb - 1) / nb;
+  g.nb = (g.ngroups + g.gpb - 1) / g.gpb;
+  return g;
+}
 size_t dw_bwd_scratch_floats(int B, int Ho, int Wo, int Co, int k) {
   const long npix = (long)B * Ho * Wo;
   long npb = (npix + 255) / 256;
   if (npb > 512) npb = 512;
   const int CS = pick_slab(Co, 128);
   const long nrb = dw_wgrad_row_blocks(B * Ho, 256 / (CS / 2), Co / CS) + 1;
-  return (size_t)std::max(npb, nrb) * (k * k + 1) * Co;
+  // the LDS-staged form writes one row per block of row GROUPS, and groups do not cross images: B * ceil(Ho / NPS) of them can exceed B * Ho / NPS + 1
+  // (B = 2, Ho = 9, NPS = 8: 4 against 3)
+  const long nlds = dw_wgrad_lds_blocks(B, Ho, 256 / (CS / 2), Co / CS).nb;
+  return (size_t)std::max(std::max(npb, nrb), nlds) * (k * k + 1) * Co;
 }
 
 // input gradient of a depthwise / channel-multiplier conv: dy fp16 (B,Ho,Wo,Ci*mult) -> dx fp16 (B,Hi,Wi,Ci) (+ res fp16); w fp32 tap-major [k*k][Ci*mult]
@@ -1359,14 +1376,8 @@ int launch_dw_wgrad(const bf16_t* x, const bf16_t* dy, float* dw, float* db, flo
   }
   if ((k == 3 || k == 7) && Wo >= 8 && CS >= 32 * mult) {   // the LDS-staged form (dw_wgrad_lds_kernel)
     const int NPSl = 256 / (CS / 2);
-    const int gpi = (Ho + NPSl - 1) / NPSl, ngroups = B * gpi;
-    // two blocks are resident per CU (190 registers, 80 KB of LDS each): 512 blocks are ONE round of a 256-CU chip, and every block more is another partial-sum
-    // row for the reduce pass to read
-    int nb = 512 / nslabs;
-    if (nb < 1) nb = 1;
-    if (nb > ngroups) nb = ngroups;
-    const int gpb = (ngroups + nb - 1) / nb;
-    nb = (ngroups + gpb - 1) / gpb;
+    const DwWgLdsBlocks lb = dw_wgrad_lds_blocks(B, Ho, NPSl, nslabs);   // the same count dw_bwd_scratch_floats sized the scratch for
+    const int gpi = lb.gpi, ngroups = lb.ngroups, gpb = lb.gpb, nb = lb.nb;
     const int NR = (NPSl - 1) * stride + k, NCc = 7 * stride + k;
     const size_t xb = (size_t)B * Hi * Wi * Ci * 2;
     if ((long)NR * NCc * (CS / mult / 8) <= 256L * 10 && xb < 0xfffffff0ull) {

@@ -919,10 +919,19 @@ __global__ __launch_bounds__(256, 2) void dwconv_s2_mfma_kernel(const bf16_t* __
 // GRAD (round 5, the tower's backward): the same march as the INPUT-GRADIENT of a stride-1 depthwise conv -- x = dL/dy as fp16, ttab = the Toeplitz table of the
 // FLIPPED taps as fp16 (correlation = convolution with the mirrored kernel under "same" padding), products on v_mfma_f32_4x4x4_16b_f16, no bias / GELU, the
 // result (+ the fp16 residual `res`: dL/dx' = G + dw7^T(dL/dt)) written as fp16.  Everything between the loads and the stores moves 16-bit cells and does not care.
+// With a residual the fp32 sum crosses the output tile as TWO fp16 cells (the value and what its rounding dropped), so the cancellation of res against the conv
+// result costs nothing: one rounding, of the final sum (a single cell left 2^-11 |conv| in a result that can be much smaller than the conv term).
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4_t;
+// fp32 -> fp16 for a value that is rounded AGAIN before it is stored: what pack_h2 would clamp (|v| > 65504) becomes an infinity instead, so the clamp stays
+// visible to the second rounding (a plain cast overflows only from 65520 on)
+__device__ __forceinline__ _Float16 f2h_ovf(float v) { return (_Float16)(fabsf(v) > FV_F16_MAX ? copysignf(__builtin_inff(), v) : v); }
+// the forward instances keep the argument list (and so the code) they had before GRAD counted its clamps: the counter travels in the slot GRAD has no bias for
+template <bool GRAD> struct MarchAux { typedef const float* type; };
+template <> struct MarchAux<true> { typedef unsigned* type; };
+template <bool GRAD> using march_aux_t = typename MarchAux<GRAD>::type;
 template <int K, bool GRAD = false>
 __global__ __launch_bounds__(256, DW_MARCH_OCC) void dwconv_march_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ ttab,
-                                                               const float* __restrict__ bias, bf16_t* __restrict__ y,
+                                                               march_aux_t<GRAD> __restrict__ aux, bf16_t* __restrict__ y,   // aux: the bias, or GRAD's saturation counter (may be null)
                                                                int H, int W, int C, int gelu, int tiles_x, int nslices, const bf16_t* __restrict__ res = nullptr) {
   constexpr int TW = 32, PAD = K / 2, IW = TW + K - 1;
   constexpr int NQ = (IW + 3) / 4, NM = (K + 3 + 3) / 4;
@@ -933,6 +942,9 @@ __global__ __launch_bounds__(256, DW_MARCH_OCC) void dwconv_march_kernel(const b
 #else
   __shared__ __attribute__((aligned(16))) char smem[16 * RS + 8 * RSO];
 #endif
+  // GRAD with a residual: a second output tile (8 * RSO bytes of DYNAMIC LDS, launch_dw_dgrad_mfma asks for it) carries what the fp16 cells of the first drop
+  extern __shared__ __attribute__((aligned(16))) char smem_lo[];
+  static_assert(!GRAD || DW_MARCH_OCC < 3, "the GRAD instances keep an output tile of their own");
   char* sX = smem;
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -953,7 +965,8 @@ __global__ __launch_bounds__(256, DW_MARCH_OCC) void dwconv_march_kernel(const b
 #pragma unroll
       for (int m = 0; m < NM; ++m) afr[ky][m] = __builtin_bit_cast(s16x4, *reinterpret_cast<const uint2*>(tsrc + (ky * NM + m) * 512));
   }
-  const float bv = GRAD ? 0.f : bias[c0 + gg * 16 + bch];
+  float bv = 0.f;
+  if constexpr (!GRAD) bv = aux[c0 + gg * 16 + bch];
 
   // one unit = 8 rows x NQ quads x 4 channel groups of (4 pixels x 8 channels) tasks
   constexpr int NTASK = 8 * NQ * 4, TPT = (NTASK + 255) / 256;
@@ -1048,7 +1061,18 @@ __global__ __launch_bounds__(256, DW_MARCH_OCC) void dwconv_march_kernel(const b
           if (gelu) v[i] = gelu_f(v[i]);
         }
         uint2 u;
-        if constexpr (GRAD) { u.x = pack_h2(v[0], v[1]); u.y = pack_h2(v[2], v[3]); }
+        if constexpr (GRAD) {   // a sum beyond +-65504 crosses the tile as an fp16 infinity: the store below counts the cell and clamps it, residual or not
+          const f16x2 h01 = {f2h_ovf(v[0]), f2h_ovf(v[1])}, h23 = {f2h_ovf(v[2]), f2h_ovf(v[3])};
+          u.x = __builtin_bit_cast(uint32_t, h01); u.y = __builtin_bit_cast(uint32_t, h23);
+          if (res) {   // what the cell dropped (|.| <= 2^-11 |v|; 0 beside an infinity), as a cell of the second tile: res + conv is then rounded ONCE, from fp32
+            float l[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) l[i] = fabsf(v[i]) > FV_F16_MAX ? 0.f : v[i] - (float)(i < 2 ? h01[i] : h23[i - 2]);
+            uint2 ul;
+            ul.x = pack_h2(l[0], l[1]); ul.y = pack_h2(l[2], l[3]);
+            *reinterpret_cast<uint2*>(smem_lo + (rg * 4 + jr) * RSO + sw[q & 3] + q * 256) = ul;
+          }
+        }
         else { u.x = pack_bf2(v[0], v[1]); u.y = pack_bf2(v[2], v[3]); }
         *reinterpret_cast<uint2*>(orow + sw[q & 3] + q * 256) = u;
       }
@@ -1060,6 +1084,13 @@ __global__ __launch_bounds__(256, DW_MARCH_OCC) void dwconv_march_kernel(const b
       uint2 r[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) r[e] = *reinterpret_cast<const uint2*>(sO + (src ^ (uint32_t)(e * 8)));
+      uint2 rl[8];
+      if constexpr (GRAD) {
+        if (res) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) rl[e] = *reinterpret_cast<const uint2*>(smem_lo + (src ^ (uint32_t)(e * 8)));
+        }
+      }
       const int oy = g * 8 + row, ox0 = tx * TW + quad * 4;
       if (oy < H) {
         bf16_t* yp = y + (((size_t)b * H + oy) * W + ox0) * C + c0 + cg * 8;
@@ -1072,14 +1103,23 @@ __global__ __launch_bounds__(256, DW_MARCH_OCC) void dwconv_march_kernel(const b
             o.x = FV_PX(0, 1); o.y = FV_PX(2, 3); o.z = FV_PX(4, 5); o.w = FV_PX(6, 7);
 #undef FV_PX
             if constexpr (GRAD) {
-              if (res) {   // + the residual branch's gradient (a second fp16 rounding of the sum: 2^-12)
-                float a8[8], r8[8];
-                unpack8_h(o, a8);
+              float a8[8];
+              unpack8_h(o, a8);
+              if (res) {   // + the residual branch's gradient, in fp32 on (cell + dropped part) = the MFMA sum to 2^-22: ONE fp16 rounding, of the sum
+                float l8[8], r8[8];
+                uint4 ol;
+#define FV_PXL(A, B) __builtin_amdgcn_perm((j & 2) ? rl[B].y : rl[B].x, (j & 2) ? rl[A].y : rl[A].x, sel)
+                ol.x = FV_PXL(0, 1); ol.y = FV_PXL(2, 3); ol.z = FV_PXL(4, 5); ol.w = FV_PXL(6, 7);
+#undef FV_PXL
+                unpack8_h(ol, l8);
                 unpack8_h(*reinterpret_cast<const uint4*>(res + (((size_t)b * H + oy) * W + ox0 + j) * C + c0 + cg * 8), r8);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) a8[e] += r8[e];
-                o = pack8_h(a8);
+                for (int e = 0; e < 8; ++e) a8[e] = (a8[e] + l8[e]) + r8[e];
               }
+              // one count per (pixel, 8-channel group) that clamps, as dw_dgrad_kernel counts.  A conv sum that overflowed arrives here as an infinity and stays one
+              // under any (finite) residual: the cell is counted once and written as +-65504, never as the clamp's value plus the residual
+              count_f16_sat8(a8, aux);
+              o = pack8_h(a8);
             }
             *reinterpret_cast<uint4*>(yp + (size_t)j * C) = o;
           }
@@ -1808,14 +1848,24 @@ int launch_dwconv_mfma(const bf16_t* x, const bf16_t* ttab, const float* bias, b
 // input gradient of a stride-1 depthwise k x k conv on the marching MFMA kernel: dy fp16 (B,H,W,C), ttab16 = fp16 Toeplitz table of the FLIPPED taps
 // (dwconv_toeplitz_pack of w[k-1-ky][k-1-kx]), res = optional fp16 residual added to the result; dx fp16
 bool dw_dgrad_mfma_supported(int H, int W, int C, int k) { return dwconv_mfma_supported(W, C, k, 1, 1) && H >= 16; }
-int launch_dw_dgrad_mfma(const bf16_t* dy, const bf16_t* ttab16, const bf16_t* res, bf16_t* dx, int B, int H, int W, int C, int k, hipStream_t s) {
+int launch_dw_dgrad_mfma(const bf16_t* dy, const bf16_t* ttab16, const bf16_t* res, bf16_t* dx, int B, int H, int W, int C, int k, unsigned* sat, hipStream_t s) {
   if (!dy || !ttab16 || !dx) return fv_fail(FV_ERR_ARG, "dw_dgrad_mfma: null pointer");
   if (B <= 0 || !dw_dgrad_mfma_supported(H, W, C, k)) return fv_fail(FV_ERR_UNSUPPORTED, "dw_dgrad_mfma: unsupported shape H=%d W=%d C=%d k=%d", H, W, C, k);
   const int tiles_x = (W + 31) / 32, nsl = C / 32;
   const long nstrips = (long)B * tiles_x * nsl;
   if (nstrips > 0x7fffffffL) return fv_fail(FV_ERR_ARG, "dw_dgrad_mfma: grid too large");
-  if (k == 7) hipLaunchKernelGGL((dwconv_march_kernel<7, true>), dim3((unsigned)nstrips), dim3(256), 0, s, dy, ttab16, static_cast<const float*>(nullptr), dx, H, W, C, 0, tiles_x, nsl, res);
-  else hipLaunchKernelGGL((dwconv_march_kernel<3, true>), dim3((unsigned)nstrips), dim3(256), 0, s, dy, ttab16, static_cast<const float*>(nullptr), dx, H, W, C, 0, tiles_x, nsl, res);
+  // with a residual the kernel keeps a second output tile (8 rows of RSO = 8 * 256 + 64 bytes) in dynamic LDS, on top of its static ring + tile: over 64 KB together
+  constexpr int LO_TILE = 8 * (8 * 256 + 64);
+  const size_t dyn = res ? LO_TILE : 0;
+  if (k == 7) {
+    static bool attr7 = false;
+    if (!attr7) { FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv_march_kernel<7, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LO_TILE)); attr7 = true; }
+    hipLaunchKernelGGL((dwconv_march_kernel<7, true>), dim3((unsigned)nstrips), dim3(256), dyn, s, dy, ttab16, sat, dx, H, W, C, 0, tiles_x, nsl, res);
+  } else {
+    static bool attr3 = false;
+    if (!attr3) { FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv_march_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, LO_TILE)); attr3 = true; }
+    hipLaunchKernelGGL((dwconv_march_kernel<3, true>), dim3((unsigned)nstrips), dim3(256), dyn, s, dy, ttab16, sat, dx, H, W, C, 0, tiles_x, nsl, res);
+  }
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }

@@ -495,7 +495,7 @@ int dw_backward(const TowerCtx& c, const bf16_t* x, const bf16_t* dy, const floa
   const int B = c.B;
   const int Ho = (Hi + 2 * (k / 2) - k) / stride + 1;
   if (dx) FV_P(FV_FAM_DWCONV, 2.0 * B * Ho * Ho * Ci * mult * k * k, 2.0 * B * Hi * Hi * Ci * (res ? 2 : 1) + 2.0 * B * Ho * Ho * Ci * mult,
-               flipped16 ? fv::launch_dw_dgrad_mfma(dy, flipped16, res, dx, B, Hi, Hi, Ci, k, s)
+               flipped16 ? fv::launch_dw_dgrad_mfma(dy, flipped16, res, dx, B, Hi, Hi, Ci, k, h->f16_flags, s)
                          : fv::launch_dw_dgrad(dy, w, res, dx, B, Hi, Hi, Ci, k, stride, mult, h->f16_flags, s, mfma_table ? 1 : 0));
   FV_P(FV_FAM_DWCONV, 2.0 * B * Ho * Ho * Ci * mult * k * k, 2.0 * B * Hi * Hi * Ci + 2.0 * B * Ho * Ho * Ci * mult,
        fv::launch_dw_wgrad(x, dy, gw, gb, c.at<float>(c.tp->scr), B, Hi, Hi, Ci, k, stride, mult, s));

@@ -216,6 +216,8 @@ OPS_SIGNATURES = {
     "fv_op_convffn32_stash": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "fv_op_gemm_f16_gelup": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "fv_op_dw_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "fv_op_dw_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "fv_op_dw_dgrad_mfma": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "fv_op_convffn32_split": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, C.c_size_t, _vp]),
     "fv_op_lora_direct_scratch_floats": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
     "fv_op_lora_direct": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, C.c_size_t, _vp]),
