@@ -423,7 +423,7 @@ int fv_head_flow_sample_prefix(fv_handle* h, const float* flat_params, const flo
  * Configuration call, for all three entry points; their signatures do not change.  FV_ERR_STATE when flow mode is off; FV_ERR_ARG, changing nothing, for an
  * unknown solver.  The two rows join the workspace plan with the FIRST call that names a solver other than Euler (fv_workspace_bytes grows from then on and
  * stays): that call must come before fv_bind_workspace (FV_ERR_STATE afterwards); later calls switch freely among all four.  A handle that never names one
- * reports the fv_workspace_bytes it always did; FV_FLOW_SOLVER_EULER launches the Euler kernels as they are.  fv_head_set_flow(NULL) returns it to Euler. */
+ * reports the fv_workspace_bytes it always did; FV_FLOW_SOLVER_EULER is the scheme with one stage and needs neither row.  fv_head_set_flow(NULL) returns it to Euler. */
 #define FV_FLOW_SOLVER_EULER 0
 #define FV_FLOW_SOLVER_MIDPOINT 1
 #define FV_FLOW_SOLVER_HEUN 2

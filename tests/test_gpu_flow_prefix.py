@@ -382,6 +382,16 @@ def test_prefix_sampler_bit_rules(name, B):
             others = [r for r in range(B) if r != b]
             assert bool(torch.isnan(nc[b]).any())
             assert torch.equal(na[others], act[others]) and torch.equal(nc[others], chunk[others])
+    # no delays pin nothing and add no mask column: the plain sampler's bits on the same handle, whatever the shift (one step: the first stage is the final one)
+    none = torch.zeros_like(delays)
+    for io in (False, True):
+        _set_io(eng, st, io)
+        for steps in (1, 4):
+            plain = eng.head_flow_sample(flat, pooled, states, steps=steps, noise=c["noise"]).clone()
+            for shift in (0, 2, K):
+                a_, c_ = eng.head_flow_sample_prefix(flat, pooled, states, prev, none, shift=shift, steps=steps, noise=c["noise"])
+                torch.cuda.synchronize()
+                assert torch.equal(a_, plain) and (io or torch.equal(c_, plain)), (io, steps, shift)
     eng.close()
 
 

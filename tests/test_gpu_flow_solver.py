@@ -214,6 +214,19 @@ def test_bit_rules(name, B, solver):
                 keep = torch.arange(B) != 1
                 assert bool(torch.isnan(hp[1]).any()) and torch.equal(hp[keep], plain[keep]) and torch.equal(hg[keep], guided[keep])
     eng.close()
+    # a prefix-mode handle: no delays pin nothing and add no mask column -- the plain sampler's bits for the same solver, whatever the shift
+    pc = su.prefix_case(name, B)
+    eng = _engine(name, B, solver, D=pc["D"])
+    flat = _flat(eng, pc["p"])
+    none = torch.zeros(B, dtype=torch.int32, device=DEV)
+    for io in (False, True):
+        _set_io(eng, pc["stats"], io)
+        for N in (1, 4):
+            plain = eng.head_flow_sample(flat, pooled, states, steps=N, noise=noise).clone()
+            for sh in (0, 2, K):
+                a_none, c_none = eng.head_flow_sample_prefix(flat, pooled, states, prev, none, shift=sh, steps=N, noise=noise)
+                assert torch.equal(a_none, plain) and (io or torch.equal(c_none, plain)), (io, N, sh)
+    eng.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5. refusals

@@ -1,14 +1,14 @@
 // flow_kernels.hip -- the flow-matching form of the action expert (fv_head_set_flow), all fp32, every sum in a fixed order:
 //   flow_prepare_kernel                    training: x_t and phi(t) into their columns of the head's cat, u = eps - a as the loss target; the head itself
 //                                          (head_kernels.hip) then runs forward and backward as it does for regression
-//   flow_cond / _init / _step_a / _b / _c  the Euler sampler (fv_head_flow_sample): conditioning once, three launches per step
-//   flow_*_prefix_kernel                   action-prefix conditioning (fv_head_set_flow_prefix): the noising step's, the conditioning's, the start's and step C's
-//                                          PREFIX instances; the kernels without the suffix are the code they were
+//   flow_cond / _init / _step_a / _b / _c  the sampler (fv_head_flow_sample): conditioning once, three launches per network evaluation
+//   <PREFIX> instances                     action-prefix conditioning (fv_head_set_flow_prefix): what the noising step, the conditioning, the start and step C
+//                                          add for it sits under `if constexpr (PREFIX)` in the one body each of them has
 //   flow_guide_* / flow_vjp_t_kernel       guided sampling (fv_head_set_flow_guidance; real-time chunking): the step's forward with z3 and v kept, J^T omega
 //                                          through three transposed products and a LayerNorm backward, and the update
-//   flow_rk_stage / flow_*_rk_kernel       higher-order integrators (fv_head_set_flow_solver; midpoint, Heun, RK4): the three kernels that own the x update as
-//                                          Runge-Kutta stages over two more rows per batch row; the Euler kernels and loops are the code they were
-// The state branch of both samplers is head_kernels.hip's (launch_head_state_branch); the draws come from common.h philox under this file's key.
+//   flow_rk_stage                          the x update of every solver (fv_head_set_flow_solver), in step C and in the guided update: an explicit
+//                                          Runge-Kutta stage, Euler being the scheme with one (FLOW_TABLEAUX); flow_integrate is the one loop over them
+// The state branch of every sampler is head_kernels.hip's (launch_head_state_branch); the draws come from common.h philox under this file's key.
 #include "kernels.h"
 
 #include <algorithm>
@@ -47,65 +47,39 @@ __device__ __forceinline__ void flow_phi(float* __restrict__ dst, const float* _
 // and draws what row b draws at offset + (s << 56) -- the key, the counter (group, b, offset) and the Box-Muller as they are, so row b's draws depend
 // neither on B nor on S, and draw 0 is the single draw.  Explicit noise (S B, da) / tin (S B) are read at r.
 // cat: the row-major (S B, cw) matrix inside `saved`; columns [xo, xo + da) <- x_t, [xo + da, xo + da + te) <- phi(t); u_out (S B, da) <- eps - a.
-// x_t is formed in double and rounded once: t eps and (1 - t) a cancel for some rows, and the fp32 form then loses bits the loss target does not
+// x_t is formed in double and rounded once: t eps and (1 - t) a cancel for some rows, and the fp32 form then loses bits the loss target does not.
+// PREFIX (fv_head_set_flow_prefix): the row's delay d is delays[row] clamped to 0 .. pd, or the smallest j with (z >> 8) < thr[j], z the third word of the
+// group-0 block whose x and y yield t (an integer compare; no new stream, no new counter: t and eps are the plain head's bits).  The first d steps of x_t are
+// COPIES of targets, m = [k < d] goes behind phi(t) as exact 0.0 / 1.0 and as bytes into pmask; u is written everywhere as ever
+struct FlowPrefixArgs { const int32_t* delays; const uint32_t* thr; uint8_t* pmask; int pk, pd; };
+template <bool PREFIX>
 __global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restrict__ targets, const float* __restrict__ noise, const float* __restrict__ tin,
                                                             float* __restrict__ cat, int cw, int xo, float* __restrict__ u_out, int da, int te,
                                                             const float* __restrict__ freq, int time_dist, float dist_a, float dist_b, uint64_t seed,
-                                                            uint64_t offset) {
+                                                            uint64_t offset, FlowPrefixArgs px) {
   const int obs = blockIdx.x, row = blockIdx.y * gridDim.x + obs;
   offset += (uint64_t)blockIdx.y << 56;
-  float t;
-  if (tin) {
-    t = tin[row];
-  } else {
-    const uint4 r = flow_philox(0u, (uint32_t)obs, seed, offset);
-    if (time_dist == 0) t = (float)(r.x >> 8) * FLOW_U24;
-    else t = 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x)));
-  }
-  float* xr = cat + (size_t)row * cw + xo;
-  const double td = (double)t, omt = 1.0 - td;
-  for (int g = threadIdx.x; g * 4 < da; g += 256) {
-    float n[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)obs, seed, offset, n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = g * 4 + j;
-      if (i >= da) break;
-      const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)obs * da + i];
-      xr[i] = (float)(td * (double)e + omt * (double)a);
-      u_out[(size_t)row * da + i] = e - a;
-    }
-  }
-  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t, i);
-}
-// The PREFIX instance (fv_head_set_flow_prefix), a sibling so that the kernel above stays the code it was.  The row's delay d: delays[row] clamped to 0 .. pd,
-// or the smallest j with (z >> 8) < thr[j], z the third word of the group-0 block whose x and y yield t (an integer compare; no new stream, no new counter:
-// t and eps are the plain head's bits).  The first d steps of x_t are COPIES of targets, m = [k < d] goes behind phi(t) as exact 0.0 / 1.0 and as bytes into
-// pmask; u is written everywhere as ever
-struct FlowPrefixArgs { const int32_t* delays; const uint32_t* thr; uint8_t* pmask; int pk, pd; };
-__global__ __launch_bounds__(256) void flow_prepare_prefix_kernel(const float* __restrict__ targets, const float* __restrict__ noise, const float* __restrict__ tin,
-                                                                   float* __restrict__ cat, int cw, int xo, float* __restrict__ u_out, int da, int te,
-                                                                   const float* __restrict__ freq, int time_dist, float dist_a, float dist_b, uint64_t seed,
-                                                                   uint64_t offset, FlowPrefixArgs px) {
-  const int obs = blockIdx.x, row = blockIdx.y * gridDim.x + obs;
-  offset += (uint64_t)blockIdx.y << 56;
-  const uint4 r = flow_philox(0u, (uint32_t)obs, seed, offset);
+  uint4 r = make_uint4(0u, 0u, 0u, 0u);
+  if (PREFIX || !tin) r = flow_philox(0u, (uint32_t)obs, seed, offset);   // (PREFIX: a drawn delay needs the block with t given, too)
   float t;
   if (tin) t = tin[row];
   else if (time_dist == 0) t = (float)(r.x >> 8) * FLOW_U24;
   else t = 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x)));
-  int dl = 0;
-  if (px.delays) {
-    dl = min(max(px.delays[row], 0), px.pd);
-  } else {
-    const uint32_t z24 = r.z >> 8;
-    while (dl < px.pd && z24 >= px.thr[dl]) ++dl;
-  }
-  const int pin = dl * (da / px.pk);   // elements [0, pin) of the row are the conditioned steps
   float* xr = cat + (size_t)row * cw + xo;
-  for (int k = threadIdx.x; k < px.pk; k += 256) {
-    xr[da + te + k] = k < dl ? 1.0f : 0.0f;
-    px.pmask[(size_t)row * px.pk + k] = k < dl ? 1 : 0;
+  int pin = 0;   // elements [0, pin) of the row are the conditioned steps
+  if constexpr (PREFIX) {
+    int dl = 0;
+    if (px.delays) {
+      dl = min(max(px.delays[row], 0), px.pd);
+    } else {
+      const uint32_t z24 = r.z >> 8;
+      while (dl < px.pd && z24 >= px.thr[dl]) ++dl;
+    }
+    pin = dl * (da / px.pk);
+    for (int k = threadIdx.x; k < px.pk; k += 256) {
+      xr[da + te + k] = k < dl ? 1.0f : 0.0f;
+      px.pmask[(size_t)row * px.pk + k] = k < dl ? 1 : 0;
+    }
   }
   const double td = (double)t, omt = 1.0 - td;
   for (int g = threadIdx.x; g * 4 < da; g += 256) {
@@ -116,17 +90,30 @@ __global__ __launch_bounds__(256) void flow_prepare_prefix_kernel(const float* _
       const int i = g * 4 + j;
       if (i >= da) break;
       const float e = noise ? noise[(size_t)row * da + i] : n[j], a = targets[(size_t)obs * da + i];
-      xr[i] = i < pin ? a : (float)(td * (double)e + omt * (double)a);
+      xr[i] = PREFIX && i < pin ? a : (float)(td * (double)e + omt * (double)a);
       u_out[(size_t)row * da + i] = e - a;
     }
   }
   for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t, i);
 }
 
-// the sampler's start: xphi (B, da + te) <- [ noise or the draws of (seed, offset) | phi(t0) ]
+// ---- the prefix sampler (fv_head_flow_sample_prefix; training-time action conditioning): the PREFIX instances of the start, the conditioning and step C.
+// Row b's first p_b = min(delays[b], pd, chunk - shift) steps are PINNED to prev[b][k + shift]: written once by the start kernel, left alone by every step, so
+// they leave as the bits they came in with.  The clamp runs inside the kernels (no host synchronisation); a pinned element is SELECTED, whatever prev holds
+// elsewhere (NaN, +-inf) is never read.  The plain instances get an empty FlowPinned and read none of it
+struct FlowPinned { const float* prev; const int32_t* delays; int pd, chunk, shift; };
+__device__ __forceinline__ int flow_pinned_steps(const FlowPinned& p, int b) { return min(min(max(p.delays[b], 0), p.pd), p.chunk - p.shift); }
+
+// the sampler's start: xphi (B, da + te) <- [ noise or the draws of (seed, offset); PREFIX: prev on the pinned elements | phi(t0) ]
+template <bool PREFIX>
 __global__ __launch_bounds__(256) void flow_init_kernel(const float* __restrict__ noise, float* __restrict__ xphi, int da, int te, const float* __restrict__ freq,
-                                                         float t0, uint64_t seed, uint64_t offset) {
+                                                         float t0, uint64_t seed, uint64_t offset, FlowPinned p) {
   const int row = blockIdx.x;
+  int A = 0, pin = 0;
+  if constexpr (PREFIX) {
+    A = da / p.chunk;
+    pin = flow_pinned_steps(p, row) * A;
+  }
   float* xr = xphi + (size_t)row * (da + te);
   for (int g = threadIdx.x; g * 4 < da; g += 256) {
     float n[4] = {0.f, 0.f, 0.f, 0.f};
@@ -135,7 +122,8 @@ __global__ __launch_bounds__(256) void flow_init_kernel(const float* __restrict_
     for (int j = 0; j < 4; ++j) {
       const int i = g * 4 + j;
       if (i >= da) break;
-      xr[i] = noise ? noise[(size_t)row * da + i] : n[j];
+      if (PREFIX && i < pin) xr[i] = p.prev[(size_t)row * da + i + (size_t)p.shift * A];   // (i + shift A < (p_b + shift) A <= da)
+      else xr[i] = noise ? noise[(size_t)row * da + i] : n[j];
     }
   }
   for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t0, i);
@@ -151,13 +139,26 @@ __device__ __forceinline__ void flow_dot8(const float* __restrict__ x, int ldx, 
   }
 }
 // once per call: c[b][n] = b4[n] + W4[n][0 : feat] . pooled[b] + W4[n][feat : feat + hid] . s[b]  (the part of fusion.0 that does not depend on t)
+// PREFIX: the mask block as well, c[b][n] += sum_{k < p_b} W4[n][mo + k], which does not change over the steps.  The mask's columns join the wave's partial
+// sums behind the state branch's (lane k % 64 owns column k), one wave_sum per row as ever: a fixed order
+template <bool PREFIX>
 __global__ __launch_bounds__(256) void flow_cond_kernel(const float* __restrict__ pooled, int feat, const float* __restrict__ sb, int hid, const float* __restrict__ W,
-                                                         int ldw, const float* __restrict__ bias, float* __restrict__ c, int B, int N) {
+                                                         int ldw, const float* __restrict__ bias, float* __restrict__ c, int B, int N, int mo, FlowPinned p) {
   const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
   if (n >= N) return;
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   flow_dot8(pooled, feat, W + (size_t)n * ldw, feat, b0, B, lane, acc);
   flow_dot8(sb, hid, W + (size_t)n * ldw + feat, hid, b0, B, lane, acc);
+  if constexpr (PREFIX) {
+    int pin[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pin[j] = flow_pinned_steps(p, min(b0 + j, B - 1));
+    for (int k = lane; k < p.pd; k += 64) {   // (p_b <= pd: the columns behind it are never read)
+      const float wv = W[(size_t)n * ldw + mo + k];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] += k < pin[j] ? wv : 0.f;
+    }
+  }
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
   if (lane == 0)
@@ -215,12 +216,39 @@ __global__ __launch_bounds__(256) void flow_step_b_kernel(const float* __restric
       a3[(size_t)(b0 + j) * N + n] = silu_f(z);
     }
 }
-// step kernel C: v = ba[n] + Wa[n] . a3[b]; x <- x + dt v in the epilogue (the lane that owns (b, n) reads and writes x[b][n], nobody else touches it).
-// Not the last step: the blocks of column group 0 also write phi(t_next) for their 8 rows.  The last step writes `actions`, with the folded action statistics
+// ---- the x update (fv_head_set_flow_solver): explicit Runge-Kutta schemes whose stage j + 1 depends on stage j only; Euler is the one with a single stage.
+// A higher-order step keeps two more rows per batch row, x0 (the step's start) and S (the running sum of b_j k_j).  Within a step of size h = dt, with k the
+// stage's velocity (the corrected v' in the guided sampler) and xphi holding the stage's x:
+//     first stage:      x0 <- x (xphi holds the step's start), S <- b k                 later stages:  S <- fmaf(b, k, S)
+//     not the last:     x <- fmaf(a h, k, x0)                                           the last:      x <- fmaf(h, S, x0)
+// ah = a_{j+1} h, b = b_j and h are rounded once on the host.  The lane or thread that owns (b, n) is the only one that touches x0, S and x of that element.
+// A stage that is first AND last (Euler: b = 1) is x <- fmaf(h, k, x) and touches neither row: x0 and S may be null
+struct FlowRkArgs { float* x0; float* S; float ah, b, h; int first, last; };
+// every x + h k and x scale + shift of the samplers is ONE explicit fused multiply-add: equal operands give equal bits in all three
+__device__ __forceinline__ float flow_fma_pinned(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// e = b N + n; xb = xphi[b][n] as it stands; -> the value xphi[b][n] takes.  ONE helper for all three samplers: equal k give equal bits.
+// SINGLE: the caller's compile-time promise that the stage is first and last (the one-stage scheme), in both kernels that call this.  The same expressions,
+// minus the branches on the two flags: in step C's serial epilogue they cost the prefix sampler 0.8 % at B = 64 (profiles/flow_refactor_ab.json)
+template <bool SINGLE>
+__device__ __forceinline__ float flow_rk_stage(const FlowRkArgs& rk, size_t e, float xb, float k) {
+  const bool first = SINGLE || rk.first, last = SINGLE || rk.last;
+  const float x0v = first ? xb : rk.x0[e];
+  const float sv = first ? rk.b * k : flow_fma_pinned(rk.b, k, rk.S[e]);
+  if (last) return flow_fma_pinned(rk.h, sv, x0v);
+  if (first) rk.x0[e] = x0v;
+  rk.S[e] = sv;
+  return flow_fma_pinned(rk.ah, k, x0v);
+}
+// step kernel C: k = ba[n] + Wa[n] . a3[b]; x <- flow_rk_stage(x, k) in the epilogue (the lane that owns (b, n) reads and writes x[b][n], nobody else touches
+// it).  t_next is the time of the NEXT evaluation (the next stage's, or the next step's first): unless this is the final one, the blocks of column group 0
+// also write phi(t_next) for their 8 rows.  `actions` is given on the last stage of the last step only, which writes it (with the folded action statistics) and
+// chunk_out (without, may be null).  PREFIX: a pinned element is left alone in xphi at every stage and never enters x0 or S; the final stage writes it out
+// from x as it stands.  SINGLE: the instance for the one-stage scheme (flow_rk_stage)
+template <bool PREFIX, bool SINGLE>
 __global__ __launch_bounds__(256) void flow_step_c_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
-                                                           float* __restrict__ xphi, int xw, int te, float dt, float t_next, const float* __restrict__ freq,
-                                                           float* __restrict__ actions, const float* __restrict__ post_scale, const float* __restrict__ post_shift,
-                                                           int B, int N) {
+                                                           float* __restrict__ xphi, int xw, int te, FlowRkArgs rk, float t_next, const float* __restrict__ freq,
+                                                           float* __restrict__ actions, float* __restrict__ chunk_out, const float* __restrict__ post_scale,
+                                                           const float* __restrict__ post_shift, int B, int N, FlowPinned p) {
   const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
   if (!actions && blockIdx.x == 0) {
     const int half = te / 2;
@@ -230,17 +258,37 @@ __global__ __launch_bounds__(256) void flow_step_c_kernel(const float* __restric
     }
   }
   if (n >= N) return;
+  // this column's x (and the rows' pinned step counts) are asked for ahead of the product: their latency hides behind it instead of trailing the wave sums
+  int pin[8];
+  float xv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int b = min(b0 + j, B - 1);
+    if constexpr (PREFIX) pin[j] = flow_pinned_steps(p, b);
+    xv[j] = xphi[(size_t)b * xw + n];
+  }
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
-  if (lane == 0)
-    for (int j = 0; j < 8 && b0 + j < B; ++j) {
+  if (lane == 0) {
+    int k = 0;
+    if constexpr (PREFIX) k = n / (N / p.chunk);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if (b0 + j >= B) break;
       const size_t b = (size_t)(b0 + j);
-      const float xn = xphi[b * xw + n] + dt * (acc[j] + bias[n]);
-      if (!actions) xphi[b * xw + n] = xn;
-      else actions[b * N + n] = post_scale ? xn * post_scale[n] + post_shift[n] : xn;
+      bool pinned = false;
+      if constexpr (PREFIX) pinned = k < pin[j];
+      const float xn = pinned ? xv[j] : flow_rk_stage<SINGLE>(rk, b * N + n, xv[j], acc[j] + bias[n]);
+      if (!actions) {
+        if (!pinned) xphi[b * xw + n] = xn;
+        continue;
+      }
+      if (chunk_out) chunk_out[b * N + n] = xn;
+      actions[b * N + n] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
     }
+  }
 }
 
 // ---- guided sampling (fv_head_set_flow_guidance; real-time chunking).  Per step, with a^ = x - t v the denoised estimate, Y the shifted previous chunk and
@@ -368,14 +416,12 @@ __global__ __launch_bounds__(1024) void flow_guide_ln_kernel(const float* __rest
     dr[i] = rs * (dr[i] - m1 - h * m2);
   }
 }
-// x + dt v as ONE fused multiply-add, the contraction flow_step_c_kernel's `x + dt * v` compiles to: with v' == v the guided update repeats its bits.
-// (the same for the folded action statistics x scale + shift)
-__device__ __forceinline__ float flow_fma_pinned(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-// The last kernel of a guided step, one thread per (b, n): J^T omega = sum_q part[q][b][n] (the fusion.0 product's partials), g = omega - t J^T omega,
-// v' = v - k g, x <- x + dt v'; phi(t_next), or on the last step `actions` (with the folded statistics) and chunk_out (without), as flow_step_c_kernel.
-// jt_out != null (the op-level entry): J^T omega alone
+// The last kernel of a guided evaluation, one thread per (b, n): J^T omega = sum_q part[q][b][n] (the fusion.0 product's partials), g = omega - t J^T omega,
+// v' = v - kw g with t and kw the STAGE's, x <- flow_rk_stage(x, v'); phi(t_next), or on the final stage `actions` (with the folded statistics) and chunk_out
+// (without), as flow_step_c_kernel: with v' == v it repeats step C's bits.  jt_out != null (the op-level entry): J^T omega alone.  SINGLE: as in step C
+template <bool SINGLE>
 __global__ __launch_bounds__(256) void flow_guide_update_kernel(const float* __restrict__ part, int S_in, const float* __restrict__ omega, const float* __restrict__ v,
-                                                                 float* __restrict__ xphi, int xw, int te, float t, float kw, float dt, float t_next,
+                                                                 float* __restrict__ xphi, int xw, int te, float t, float kw, FlowRkArgs rk, float t_next,
                                                                  const float* __restrict__ freq, float* __restrict__ actions, float* __restrict__ chunk_out,
                                                                  const float* __restrict__ post_scale, const float* __restrict__ post_shift,
                                                                  float* __restrict__ jt_out, int B, int N) {
@@ -390,201 +436,23 @@ __global__ __launch_bounds__(256) void flow_guide_update_kernel(const float* __r
   if (jt_out) { jt_out[e] = jt; return; }
   const float g = omega[e] - t * jt;
   const float vp = v[e] - kw * g;
-  const float xn = flow_fma_pinned(dt, vp, xphi[(size_t)b * xw + n]);
+  const float xn = flow_rk_stage<SINGLE>(rk, e, xphi[(size_t)b * xw + n], vp);
   if (!actions) { xphi[(size_t)b * xw + n] = xn; return; }
   if (chunk_out) chunk_out[e] = xn;
   actions[e] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
 }
 
-// ---- the prefix sampler (fv_head_flow_sample_prefix; training-time action conditioning).  Row b's first p_b = min(delays[b], pd, chunk - shift) steps are PINNED
-// to prev[b][k + shift]: written once by the start kernel, left alone by every step, so they leave as the bits they came in with.  The clamp runs inside the
-// kernels (no host synchronisation); a pinned element is SELECTED, whatever prev holds elsewhere (NaN, +-inf) is never read
-__device__ __forceinline__ int flow_pinned_steps(const int32_t* __restrict__ delays, int b, int pd, int chunk, int shift) {
-  return min(min(max(delays[b], 0), pd), chunk - shift);
-}
-// the start: xphi (B, da + te) <- [ prev on the pinned elements, noise or the draws of (seed, offset) elsewhere | phi(t0) ]
-__global__ __launch_bounds__(256) void flow_init_prefix_kernel(const float* __restrict__ noise, float* __restrict__ xphi, int da, int te, const float* __restrict__ freq,
-                                                                float t0, uint64_t seed, uint64_t offset, const float* __restrict__ prev,
-                                                                const int32_t* __restrict__ delays, int pd, int chunk, int shift) {
-  const int row = blockIdx.x, A = da / chunk, pin = flow_pinned_steps(delays, row, pd, chunk, shift) * A;
-  float* xr = xphi + (size_t)row * (da + te);
-  for (int g = threadIdx.x; g * 4 < da; g += 256) {
-    float n[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)row, seed, offset, n);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int i = g * 4 + j;
-      if (i >= da) break;
-      if (i < pin) xr[i] = prev[(size_t)row * da + i + (size_t)shift * A];   // (i + shift A < (p_b + shift) A <= da)
-      else xr[i] = noise ? noise[(size_t)row * da + i] : n[j];
-    }
-  }
-  for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t0, i);
-}
-// flow_cond_kernel with the mask block: c[b][n] += sum_{k < p_b} W4[n][mo + k], which does not change over the steps.  The mask's columns join the wave's
-// partial sums behind the state branch's (lane k % 64 owns column k), one wave_sum per row as ever: a fixed order
-__global__ __launch_bounds__(256) void flow_cond_prefix_kernel(const float* __restrict__ pooled, int feat, const float* __restrict__ sb, int hid,
-                                                                const float* __restrict__ W, int ldw, const float* __restrict__ bias, float* __restrict__ c, int B,
-                                                                int N, int mo, const int32_t* __restrict__ delays, int pd, int chunk, int shift) {
-  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
-  if (n >= N) return;
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  flow_dot8(pooled, feat, W + (size_t)n * ldw, feat, b0, B, lane, acc);
-  flow_dot8(sb, hid, W + (size_t)n * ldw + feat, hid, b0, B, lane, acc);
-  int pin[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) pin[j] = flow_pinned_steps(delays, min(b0 + j, B - 1), pd, chunk, shift);
-  for (int k = lane; k < pd; k += 64) {   // (p_b <= pd: the columns behind it are never read)
-    const float wv = W[(size_t)n * ldw + mo + k];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += k < pin[j] ? wv : 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
-  if (lane == 0)
-    for (int j = 0; j < 8 && b0 + j < B; ++j) c[(size_t)(b0 + j) * N + n] = acc[j] + bias[n];
-}
-// flow_step_c_kernel whose owning lane leaves a pinned element alone.  The last step writes `actions` (with the folded statistics) and chunk_out (without,
-// may be null) for every element, pinned ones from x as it stands; x + dt v and x scale + shift are the explicit fused multiply-adds
-__global__ __launch_bounds__(256) void flow_step_c_prefix_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
-                                                                  float* __restrict__ xphi, int xw, int te, float dt, float t_next, const float* __restrict__ freq,
-                                                                  float* __restrict__ actions, float* __restrict__ chunk_out, const float* __restrict__ post_scale,
-                                                                  const float* __restrict__ post_shift, int B, int N, const int32_t* __restrict__ delays, int pd,
-                                                                  int chunk, int shift) {
-  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
-  if (!actions && blockIdx.x == 0) {
-    const int half = te / 2;
-    for (int idx = threadIdx.x; idx < 8 * half; idx += 256) {
-      const int j = idx / half, i = idx - j * half;
-      if (b0 + j < B) flow_phi(xphi + (size_t)(b0 + j) * xw + N, freq, half, t_next, i);
-    }
-  }
-  if (n >= N) return;
-  // the rows' pinned step counts and this column's x are asked for ahead of the product: their latency hides behind it instead of trailing the wave sums
-  int pin[8];
-  float xv[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int b = min(b0 + j, B - 1);
-    pin[j] = flow_pinned_steps(delays, b, pd, chunk, shift);
-    xv[j] = xphi[(size_t)b * xw + n];
-  }
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
-  if (lane == 0) {
-    const int k = n / (N / chunk);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (b0 + j >= B) break;
-      const size_t b = (size_t)(b0 + j);
-      const bool pinned = k < pin[j];
-      const float x = xv[j];
-      const float xn = pinned ? x : flow_fma_pinned(dt, acc[j] + bias[n], x);
-      if (!actions) {
-        if (!pinned) xphi[b * xw + n] = xn;
-        continue;
-      }
-      if (chunk_out) chunk_out[b * N + n] = xn;
-      actions[b * N + n] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
-    }
-  }
-}
-
-// ---- higher-order integrators (fv_head_set_flow_solver): explicit Runge-Kutta schemes whose stage j + 1 depends on stage j only.  A stage is the Euler step's
-// launches with another epilogue; a step keeps two more rows per batch row, x0 (the step's start) and S (the running sum of b_j k_j).  Within a step of size
-// h = dt, with k the stage's velocity (the corrected v' in the guided sampler) and xphi holding the stage's x:
-//     first stage:      x0 <- x (xphi holds the step's start), S <- b k                 later stages:  S <- fmaf(b, k, S)
-//     not the last:     x <- fmaf(a h, k, x0)                                           the last:      x <- fmaf(h, S, x0)
-// ah = a_{j+1} h, b = b_j and h are rounded once on the host.  The lane or thread that owns (b, n) is the only one that touches x0, S and x of that element
-struct FlowRkArgs { float* x0; float* S; float ah, b, h; int first, last; };
-// e = b N + n; xb = xphi[b][n] as it stands; -> the value xphi[b][n] takes.  ONE helper for all three samplers: equal k give equal bits
-__device__ __forceinline__ float flow_rk_stage(const FlowRkArgs& rk, size_t e, float xb, float k) {
-  const float x0v = rk.first ? xb : rk.x0[e];
-  const float sv = rk.first ? rk.b * k : flow_fma_pinned(rk.b, k, rk.S[e]);
-  if (rk.last) return flow_fma_pinned(rk.h, sv, x0v);
-  if (rk.first) rk.x0[e] = x0v;
-  rk.S[e] = sv;
-  return flow_fma_pinned(rk.ah, k, x0v);
-}
-// flow_step_c_kernel (PREFIX: flow_step_c_prefix_kernel) as a Runge-Kutta stage.  t_next is the time of the NEXT evaluation (the next stage's, or the next
-// step's first); `actions` is given on the last stage of the last step only.  PREFIX: a pinned element is left alone in xphi at every stage and never enters
-// x0 or S; the last stage writes it out from x as it stands
-template <bool PREFIX>
-__global__ __launch_bounds__(256) void flow_step_c_rk_kernel(const float* __restrict__ a3, int K, const float* __restrict__ W, const float* __restrict__ bias,
-                                                              float* __restrict__ xphi, int xw, int te, FlowRkArgs rk, float t_next, const float* __restrict__ freq,
-                                                              float* __restrict__ actions, float* __restrict__ chunk_out, const float* __restrict__ post_scale,
-                                                              const float* __restrict__ post_shift, int B, int N, const int32_t* __restrict__ delays, int pd,
-                                                              int chunk, int shift) {
-  const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6), b0 = blockIdx.y * 8;
-  if (!actions && blockIdx.x == 0) {
-    const int half = te / 2;
-    for (int idx = threadIdx.x; idx < 8 * half; idx += 256) {
-      const int j = idx / half, i = idx - j * half;
-      if (b0 + j < B) flow_phi(xphi + (size_t)(b0 + j) * xw + N, freq, half, t_next, i);
-    }
-  }
-  if (n >= N) return;
-  int pin[8];
-  float xv[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int b = min(b0 + j, B - 1);
-    pin[j] = PREFIX ? flow_pinned_steps(delays, b, pd, chunk, shift) : 0;
-    xv[j] = xphi[(size_t)b * xw + n];
-  }
-  float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  flow_dot8(a3, K, W + (size_t)n * K, K, b0, B, lane, acc);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = wave_sum(acc[j]);
-  if (lane == 0) {
-    const int k = PREFIX ? n / (N / chunk) : 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (b0 + j >= B) break;
-      const size_t b = (size_t)(b0 + j);
-      const bool pinned = PREFIX && k < pin[j];
-      const float xn = pinned ? xv[j] : flow_rk_stage(rk, b * N + n, xv[j], acc[j] + bias[n]);
-      if (!actions) {
-        if (!pinned) xphi[b * xw + n] = xn;
-        continue;
-      }
-      if (chunk_out) chunk_out[b * N + n] = xn;
-      actions[b * N + n] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
-    }
-  }
-}
-// flow_guide_update_kernel as a Runge-Kutta stage: k is the corrected velocity v' = v - kw g, with t and kw the STAGE's; t_next as above
-__global__ __launch_bounds__(256) void flow_guide_update_rk_kernel(const float* __restrict__ part, int S_in, const float* __restrict__ omega, const float* __restrict__ v,
-                                                                    float* __restrict__ xphi, int xw, int te, float t, float kw, FlowRkArgs rk, float t_next,
-                                                                    const float* __restrict__ freq, float* __restrict__ actions, float* __restrict__ chunk_out,
-                                                                    const float* __restrict__ post_scale, const float* __restrict__ post_shift, int B, int N) {
-  const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
-  if (!actions && blockIdx.x == 0)
-    for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xphi + (size_t)b * xw + N, freq, te / 2, t_next, i);
-  if (n >= N) return;
-  const size_t e = (size_t)b * N + n;
-  float jt = 0.f;
-#pragma unroll 8
-  for (int q = 0; q < S_in; ++q) jt += part[((size_t)q * B + b) * N + n];
-  const float g = omega[e] - t * jt;
-  const float vp = v[e] - kw * g;
-  const float xn = flow_rk_stage(rk, e, xphi[(size_t)b * xw + n], vp);
-  if (!actions) { xphi[(size_t)b * xw + n] = xn; return; }
-  if (chunk_out) chunk_out[e] = xn;
-  actions[e] = post_scale ? flow_fma_pinned(xn, post_scale[n], post_shift[n]) : xn;
-}
-
-// the tableaux (FV_FLOW_SOLVER_*; Euler has no entry: it takes the Euler loops): stage times c, a[j] the coefficient that forms stage j + 1's x from k_j, b
+// the tableaux, indexed by FV_FLOW_SOLVER_*: stage times c, a[j] the coefficient that forms stage j + 1's x from k_j, b
 struct FlowTableau { int stages; double c[4], a[3], b[4]; };
-constexpr FlowTableau FLOW_TABLEAUX[3] = {
+constexpr FlowTableau FLOW_TABLEAUX[4] = {
+    {1, {0.0}, {}, {1.0}},                                                                  // Euler
     {2, {0.0, 0.5}, {0.5}, {0.0, 1.0}},                                                     // midpoint
     {2, {0.0, 1.0}, {1.0}, {0.5, 0.5}},                                                     // Heun
     {4, {0.0, 0.5, 0.5, 1.0}, {0.5, 0.5, 1.0}, {1.0 / 6.0, 1.0 / 3.0, 1.0 / 3.0, 1.0 / 6.0}},   // RK4
 };
+static_assert(FV_FLOW_SOLVER_EULER == 0 && FV_FLOW_SOLVER_MIDPOINT == 1 && FV_FLOW_SOLVER_HEUN == 2 && FV_FLOW_SOLVER_RK4 == 3, "FLOW_TABLEAUX is indexed by the solver");
 // what stage j of step i of n_steps needs: its time t, the next evaluation's time, and the epilogue's scalars -- all formed in double and rounded once, so a
-// stage with c = 1 sees the bits of t_{i + 1}
+// stage with c = 1 sees the bits of t_{i + 1}; Euler's are t_i = 1 - i / N, t_{i + 1} and h = dt = -1 / N.  rows: null for Euler, which never reads them
 struct FlowStage { float t, t_next; FlowRkArgs rk; bool final; };
 FlowStage flow_stage(const FlowTableau& tb, int i, int j, int n_steps, float* rows, size_t row_floats) {
   auto time = [&](int step, double c) { return (float)(1.0 - ((double)step + c) / (double)n_steps); };
@@ -593,7 +461,7 @@ FlowStage flow_stage(const FlowTableau& tb, int i, int j, int n_steps, float* ro
   FlowStage st;
   st.t = time(i, tb.c[j]);
   st.t_next = last ? time(i + 1, 0.0) : time(i, tb.c[j + 1]);
-  st.rk = FlowRkArgs{rows, rows + row_floats, last ? 0.f : (float)(tb.a[j] * h), (float)tb.b[j], (float)h, j == 0, last};
+  st.rk = FlowRkArgs{rows, rows ? rows + row_floats : nullptr, last ? 0.f : (float)(tb.a[j] * h), (float)tb.b[j], (float)h, j == 0, last};
   st.final = last && i + 1 == n_steps;
   return st;
 }
@@ -602,6 +470,18 @@ int flow_solver_check(const char* who, int solver, const float* rk_rows) {
   if (solver < FV_FLOW_SOLVER_EULER || solver > FV_FLOW_SOLVER_RK4) return fv_fail(FV_ERR_ARG, "%s: unknown solver %d", who, solver);
   if (solver != FV_FLOW_SOLVER_EULER && !rk_rows) return fv_fail(FV_ERR_STATE, "%s: a higher-order solver needs its rows (fv_head_set_flow_solver before fv_bind_workspace)", who);
   return FV_OK;
+}
+// The one loop of every sampler, n_steps x stages network evaluations: eval(stage, out) issues the sampler's launches for one of them.  `out` is where the
+// final stage writes the result -- all null before it, so its kernel writes phi(t_next) instead
+struct FlowOut { float *actions, *chunk_out; const float *post_scale, *post_shift; };
+template <class Eval>
+void flow_integrate(const HeadDims& d, int B, int n_steps, int solver, float* rk_rows, float* actions, float* chunk_out, const HeadIoNorm* io, Eval&& eval) {
+  const FlowTableau& tb = FLOW_TABLEAUX[solver];
+  for (int i = 0; i < n_steps; ++i)
+    for (int j = 0; j < tb.stages; ++j) {
+      const FlowStage st = flow_stage(tb, i, j, n_steps, rk_rows, flow_rk_row_floats(d, B));
+      eval(st, st.final ? FlowOut{actions, chunk_out, io ? io->action_std : nullptr, io ? io->action_mean : nullptr} : FlowOut{});
+    }
 }
 
 }  // namespace
@@ -617,12 +497,9 @@ int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targe
   if (B <= 0) return fv_fail(FV_ERR_ARG, "flow_prepare: B must be positive");
   const int S = head_rows(d, B) / B;
   if (S > 1 && (offset >> 56 & 15)) return fv_fail(FV_ERR_ARG, "flow_prepare: bits 56 .. 59 of the offset number the draws and must be 0 with more than one draw");
-  if (d.pk > 0)
-    hipLaunchKernelGGL(flow_prepare_prefix_kernel, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved), head_cat_width(d), d.feat + d.hid, u_out, d.da,
-                       d.te, f.freq, f.time_dist, f.dist_a, f.dist_b, seed, offset, FlowPrefixArgs{delays, f.thr, head_saved_prefix_mask(d, B, saved), d.pk, d.pd});
-  else
-    hipLaunchKernelGGL(flow_prepare_kernel, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved), head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
-                       f.time_dist, f.dist_a, f.dist_b, seed, offset);
+  const FlowPrefixArgs px = d.pk > 0 ? FlowPrefixArgs{delays, f.thr, head_saved_prefix_mask(d, B, saved), d.pk, d.pd} : FlowPrefixArgs{};
+  hipLaunchKernelGGL(d.pk > 0 ? flow_prepare_kernel<true> : flow_prepare_kernel<false>, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved),
+                     head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq, f.time_dist, f.dist_a, f.dist_b, seed, offset, px);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -638,107 +515,49 @@ FlowScratch flow_carve(const HeadDims& d, int B, float* base) {
   r.total = o;
   return r;
 }
-// the conditioning of a sampler call (4 launches): state LayerNorm, state projection, the t-independent part of fusion.0, the start [x | phi(t0)]
+// the conditioning of a sampler call (4 launches): state LayerNorm, state projection, the t-independent part of fusion.0, the start [x | phi(t0)].
+// pin != null: the PREFIX instances of the last two
 void flow_condition(const HeadDims& d, const HeadFlow& f, const HeadOffsets& ho, const FlowScratch& fs, const float* P, const float* pooled, const float* states,
-                    int B, const float* noise, float t0, uint64_t seed, uint64_t offset, hipStream_t s, const HeadIoNorm* io) {
+                    int B, const float* noise, float t0, uint64_t seed, uint64_t offset, hipStream_t s, const HeadIoNorm* io, const FlowPinned* pin = nullptr) {
   const dim3 blk(256);
+  const FlowPinned p = pin ? *pin : FlowPinned{};
   launch_head_state_branch(d, P, states, B, fs.n0, fs.xh0, fs.rstd0, fs.z1, fs.sb, d.hid, s, io);
-  hipLaunchKernelGGL(flow_cond_kernel, dim3(cdiv(d.fus, 4), cdiv(B, 8)), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[HP_FUS0_W], head_cat_width(d), P + ho.o[HP_FUS0_B], fs.c, B, d.fus);
-  hipLaunchKernelGGL(flow_init_kernel, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, t0, seed, offset);
+  hipLaunchKernelGGL(pin ? flow_cond_kernel<true> : flow_cond_kernel<false>, dim3(cdiv(d.fus, 4), cdiv(B, 8)), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[HP_FUS0_W],
+                     head_cat_width(d), P + ho.o[HP_FUS0_B], fs.c, B, d.fus, d.feat + d.hid + d.da + d.te, p);
+  hipLaunchKernelGGL(pin ? flow_init_kernel<true> : flow_init_kernel<false>, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, t0, seed, offset, p);
 }
 }  // namespace
 
 size_t flow_sample_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? flow_carve(d, B, nullptr).total * sizeof(float) : 0; }
 
-// 4 launches of conditioning (state LayerNorm, state projection, the t-independent part of fusion.0, the start), then 3 per Euler step.  No dropout, no
-// atomics, no host synchronisation; t_i = 1 - i / N and dt = -1 / N are rounded once on the host and travel as kernel arguments
+// 4 launches of conditioning, then 3 per network evaluation.  No dropout, no atomics, no host synchronisation; every time and step size is rounded once on
+// the host and travels as a kernel argument.  pin != null: the prefix sampler (the conditioning's, the start's and step C's PREFIX instances)
 int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
-                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows) {
-  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample: the head is not in flow mode (fv_head_set_flow)");
-  if (!P || !pooled || !states || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample: null pointer");
-  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample: B and n_steps must be positive");
-  if (const int rc = flow_solver_check("flow_sample", solver, rk_rows)) return rc;
+                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows,
+                       const FlowPin* pin) {
+  const char* who = pin ? "flow_sample_prefix" : "flow_sample";
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "%s: the head is not in flow mode (fv_head_set_flow)", who);
+  if (pin && (d.pk < 2 || d.da % d.pk || d.pd < 1 || d.pd >= d.pk)) return fv_fail(FV_ERR_STATE, "%s: prefix mode is off (fv_head_set_flow_prefix)", who);
+  if (!P || !pooled || !states || (pin && (!pin->prev || !pin->delays)) || !actions || !scratch) return fv_fail(FV_ERR_ARG, "%s: null pointer", who);
+  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "%s: B and n_steps must be positive", who);
+  if (pin && (pin->shift < 0 || pin->shift > d.pk)) return fv_fail(FV_ERR_ARG, "%s: shift = %d outside 0 .. chunk = %d", who, pin->shift, d.pk);
+  if (const int rc = flow_solver_check(who, solver, rk_rows)) return rc;
   const HeadOffsets ho = head_offsets(d);
   const FlowScratch fs = flow_carve(d, B, scratch);
   const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
   const dim3 blk(256);
   const unsigned b8 = cdiv(B, 8);
-  flow_condition(d, f, ho, fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io);
-  if (solver != FV_FLOW_SOLVER_EULER) {   // n_steps x stages evaluations: A and B as they are, step C as a Runge-Kutta stage
-    const FlowTableau& tb = FLOW_TABLEAUX[solver - 1];
-    for (int i = 0; i < n_steps; ++i)
-      for (int j = 0; j < tb.stages; ++j) {
-        const FlowStage st = flow_stage(tb, i, j, n_steps, rk_rows, flow_rk_row_floats(d, B));
-        hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
-        hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B],
-                           fs.a3, (float*)nullptr, B, d.fus);
-        hipLaunchKernelGGL(flow_step_c_rk_kernel<false>, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, st.rk, st.t_next,
-                           f.freq, st.final ? actions : (float*)nullptr, (float*)nullptr, st.final && io ? io->action_std : (const float*)nullptr,
-                           st.final && io ? io->action_mean : (const float*)nullptr, B, d.da, (const int32_t*)nullptr, 0, 1, 0);
-      }
-    FV_HIP_CHECK(hipGetLastError());
-    return FV_OK;
-  }
-  const float dt = (float)(-1.0 / (double)n_steps);
-  for (int i = 0; i < n_steps; ++i) {
-    const bool last = i + 1 == n_steps;
-    const float t_next = (float)(1.0 - (double)(i + 1) / (double)n_steps);
+  const FlowPinned p = pin ? FlowPinned{pin->prev, pin->delays, d.pd, d.pk, pin->shift} : FlowPinned{};
+  const bool single = FLOW_TABLEAUX[solver].stages == 1;
+  const auto step_c = pin ? (single ? flow_step_c_kernel<true, true> : flow_step_c_kernel<true, false>) : (single ? flow_step_c_kernel<false, true> : flow_step_c_kernel<false, false>);
+  flow_condition(d, f, ho, fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io, pin ? &p : nullptr);
+  flow_integrate(d, B, n_steps, solver, rk_rows, actions, pin ? pin->chunk_out : nullptr, io, [&](const FlowStage& st, const FlowOut& out) {
     hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
     hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], fs.a3,
                        (float*)nullptr, B, d.fus);
-    hipLaunchKernelGGL(flow_step_c_kernel, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, dt, t_next, f.freq,
-                       last ? actions : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr, last && io ? io->action_mean : (const float*)nullptr,
-                       B, d.da);
-  }
-  FV_HIP_CHECK(hipGetLastError());
-  return FV_OK;
-}
-
-// launch_flow_sample with the conditioning's and the start's PREFIX kernels and step C's PREFIX instance: 4 launches, then 3 per Euler step
-int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
-                              uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out, float* scratch,
-                              hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows) {
-  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "flow_sample_prefix: the head is not in flow mode (fv_head_set_flow)");
-  if (d.pk < 2 || d.da % d.pk || d.pd < 1 || d.pd >= d.pk) return fv_fail(FV_ERR_STATE, "flow_sample_prefix: prefix mode is off (fv_head_set_flow_prefix)");
-  if (!P || !pooled || !states || !prev || !delays || !actions || !scratch) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: null pointer");
-  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: B and n_steps must be positive");
-  if (shift < 0 || shift > d.pk) return fv_fail(FV_ERR_ARG, "flow_sample_prefix: shift = %d outside 0 .. chunk = %d", shift, d.pk);
-  if (const int rc = flow_solver_check("flow_sample_prefix", solver, rk_rows)) return rc;
-  const HeadOffsets ho = head_offsets(d);
-  const FlowScratch fs = flow_carve(d, B, scratch);
-  const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
-  const dim3 blk(256);
-  const unsigned b8 = cdiv(B, 8);
-  launch_head_state_branch(d, P, states, B, fs.n0, fs.xh0, fs.rstd0, fs.z1, fs.sb, d.hid, s, io);
-  hipLaunchKernelGGL(flow_cond_prefix_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[HP_FUS0_W], cw, P + ho.o[HP_FUS0_B], fs.c, B, d.fus,
-                     xo + xw, delays, d.pd, d.pk, shift);
-  hipLaunchKernelGGL(flow_init_prefix_kernel, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, 1.0f, seed, offset, prev, delays, d.pd, d.pk, shift);
-  if (solver != FV_FLOW_SOLVER_EULER) {   // as launch_flow_sample's, step C in its PREFIX Runge-Kutta instance
-    const FlowTableau& tb = FLOW_TABLEAUX[solver - 1];
-    for (int i = 0; i < n_steps; ++i)
-      for (int j = 0; j < tb.stages; ++j) {
-        const FlowStage st = flow_stage(tb, i, j, n_steps, rk_rows, flow_rk_row_floats(d, B));
-        hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
-        hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B],
-                           fs.a3, (float*)nullptr, B, d.fus);
-        hipLaunchKernelGGL(flow_step_c_rk_kernel<true>, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, st.rk, st.t_next,
-                           f.freq, st.final ? actions : (float*)nullptr, st.final ? chunk_out : (float*)nullptr, st.final && io ? io->action_std : (const float*)nullptr,
-                           st.final && io ? io->action_mean : (const float*)nullptr, B, d.da, delays, d.pd, d.pk, shift);
-      }
-    FV_HIP_CHECK(hipGetLastError());
-    return FV_OK;
-  }
-  const float dt = (float)(-1.0 / (double)n_steps);
-  for (int i = 0; i < n_steps; ++i) {
-    const bool last = i + 1 == n_steps;
-    const float t_next = (float)(1.0 - (double)(i + 1) / (double)n_steps);
-    hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
-    hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], fs.a3,
-                       (float*)nullptr, B, d.fus);
-    hipLaunchKernelGGL(flow_step_c_prefix_kernel, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw, d.te, dt, t_next, f.freq,
-                       last ? actions : (float*)nullptr, last ? chunk_out : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr,
-                       last && io ? io->action_mean : (const float*)nullptr, B, d.da, delays, d.pd, d.pk, shift);
-  }
+    hipLaunchKernelGGL(step_c, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw,
+                       d.te, st.rk, st.t_next, f.freq, out.actions, out.chunk_out, out.post_scale, out.post_shift, B, d.da, p);
+  });
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -746,7 +565,8 @@ int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float*
 namespace {
 // the guided sampler's rows: the unguided sampler's, then z3, v, omega, dz2 and two partial-sum buffers the transposed products alternate between
 struct GuideScratch { FlowScratch fs; float *z3, *v, *omega, *dz2, *pa, *pb; size_t total; };
-// the Euler loop's k_i for a stage time (in double from the fp32-rounded t, rounded once; beta at t = 1 and, the ratio being unbounded there, at t = 0)
+// k = min(beta, ((1 - t)^2 + t^2) / ((1 - t) t)) for a stage time: in double from the fp32-rounded t, rounded once; beta at t = 1 and, the ratio being unbounded
+// there, at t = 0
 inline float guide_weight(float t, float beta) {
   const double td = (double)t;
   return t >= 1.0f || t <= 0.0f ? beta : (float)std::min((double)beta, ((1.0 - td) * (1.0 - td) + td * td) / ((1.0 - td) * td));
@@ -800,8 +620,9 @@ int guide_backward(const HeadDims& d, const HeadOffsets& ho, const GuideScratch&
 
 size_t flow_guided_scratch_bytes(const HeadDims& d, int B) { return d.te > 0 ? guide_carve(d, B, nullptr).total * sizeof(float) : 0; }
 
-// Conditioning as launch_flow_sample, then 8 launches per Euler step: A, B (z3 kept), C' (v and omega), three transposed products with a LayerNorm backward
-// between the last two, and the update.  t_i, k_i, dt, shift and the live-row count are host values that travel as kernel arguments
+// Conditioning as launch_flow_sample, then 8 launches per network evaluation, each guided at the STAGE's time: A, B (z3 kept), C' (v and omega), three
+// transposed products with a LayerNorm backward between the last two, and the update.  The stage's times and weight, the step size, shift and the live-row
+// count are host values that travel as kernel arguments
 int launch_flow_sample_guided(const HeadDims& d, const HeadFlow& f, const HeadGuide& gd, const float* P, const float* pooled, const float* states, int B, int n_steps,
                               const float* noise, uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions,
                               float* chunk_out, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows) {
@@ -817,34 +638,13 @@ int launch_flow_sample_guided(const HeadDims& d, const HeadFlow& f, const HeadGu
   // steps from here on have omega == 0 (weight 0, or beyond the shift): the first product stops there.  (At least one step: its omega is then all 0)
   const int n_live = std::max(1, std::min(gd.live_steps, gd.chunk - shift)) * A;
   flow_condition(d, f, ho, g.fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io);
-  if (solver != FV_FLOW_SOLVER_EULER) {   // every stage is a guided evaluation at the STAGE's time: forward, omega, J^T omega, then the update as a Runge-Kutta stage
-    const FlowTableau& tb = FLOW_TABLEAUX[solver - 1];
-    for (int i = 0; i < n_steps; ++i)
-      for (int j = 0; j < tb.stages; ++j) {
-        const FlowStage st = flow_stage(tb, i, j, n_steps, rk_rows, flow_rk_row_floats(d, B));
-        const float kw = guide_weight(st.t, gd.beta);
-        guide_forward(d, ho, g, P, B, st.t, prev, gd.step_w, row_mask, gd.chunk, shift, g.v, s);
-        const int sp = guide_backward(d, ho, g, P, g.omega, n_live, B, s);
-        hipLaunchKernelGGL(flow_guide_update_rk_kernel, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, g.omega, g.v, g.fs.xphi, xw, d.te, st.t, kw, st.rk, st.t_next, f.freq,
-                           st.final ? actions : (float*)nullptr, st.final ? chunk_out : (float*)nullptr, st.final && io ? io->action_std : (const float*)nullptr,
-                           st.final && io ? io->action_mean : (const float*)nullptr, B, d.da);
-      }
-    FV_HIP_CHECK(hipGetLastError());
-    return FV_OK;
-  }
-  const float dt = (float)(-1.0 / (double)n_steps);
-  for (int i = 0; i < n_steps; ++i) {
-    const bool last = i + 1 == n_steps;
-    const float t = (float)(1.0 - (double)i / (double)n_steps), t_next = (float)(1.0 - (double)(i + 1) / (double)n_steps);
-    const double td = (double)t;
-    // k_i = min(beta, ((1 - t)^2 + t^2) / ((1 - t) t)), beta at t = 1: in double from the fp32-rounded t, rounded once
-    const float kw = t >= 1.0f ? gd.beta : (float)std::min((double)gd.beta, ((1.0 - td) * (1.0 - td) + td * td) / ((1.0 - td) * td));
-    guide_forward(d, ho, g, P, B, t, prev, gd.step_w, row_mask, gd.chunk, shift, g.v, s);
+  const auto update = FLOW_TABLEAUX[solver].stages == 1 ? flow_guide_update_kernel<true> : flow_guide_update_kernel<false>;
+  flow_integrate(d, B, n_steps, solver, rk_rows, actions, chunk_out, io, [&](const FlowStage& st, const FlowOut& out) {
+    guide_forward(d, ho, g, P, B, st.t, prev, gd.step_w, row_mask, gd.chunk, shift, g.v, s);
     const int sp = guide_backward(d, ho, g, P, g.omega, n_live, B, s);
-    hipLaunchKernelGGL(flow_guide_update_kernel, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, g.omega, g.v, g.fs.xphi, xw, d.te, t, kw, dt, t_next, f.freq,
-                       last ? actions : (float*)nullptr, last ? chunk_out : (float*)nullptr, last && io ? io->action_std : (const float*)nullptr,
-                       last && io ? io->action_mean : (const float*)nullptr, (float*)nullptr, B, d.da);
-  }
+    hipLaunchKernelGGL(update, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, g.omega, g.v, g.fs.xphi, xw, d.te, st.t, guide_weight(st.t, gd.beta), st.rk,
+                       st.t_next, f.freq, out.actions, out.chunk_out, out.post_scale, out.post_shift, (float*)nullptr, B, d.da);
+  });
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -860,7 +660,7 @@ int launch_flow_vjp(const HeadDims& d, const HeadFlow& f, const float* P, const 
   flow_condition(d, f, ho, g.fs, P, pooled, states, B, x, t, 0, 0, s, nullptr);
   guide_forward(d, ho, g, P, B, t, nullptr, nullptr, nullptr, 1, 0, v_out, s);
   const int sp = guide_backward(d, ho, g, P, omega, d.da, B, s);
-  hipLaunchKernelGGL(flow_guide_update_kernel, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, omega, v_out, g.fs.xphi, d.da + d.te, d.te, t, 0.f, 0.f, 0.f,
+  hipLaunchKernelGGL(flow_guide_update_kernel<true>, dim3(cdiv(d.da, 256), B), dim3(256), 0, s, g.pa, sp, omega, v_out, g.fs.xphi, d.da + d.te, d.te, t, 0.f, FlowRkArgs{}, 0.f,
                      f.freq, (float*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr, jt_out, B, d.da);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;

@@ -27,6 +27,29 @@ double flow_evals(const fv_handle* h, int n_steps) {
   return (double)n_steps * stages[h->flow_solver];
 }
 
+// What the three sampler entry points (`who`) share, in the order of their checks: the handle, flow mode, own() -- the entry point's refusals for its mode
+// and its pointers --, n_steps, B, own_late() -- its refusal of the shift --, the scratch (`too_small`: its message for a workspace bound for a smaller
+// plan) and, inside the profiler's bracket, run(scratch, the solver's rows, stream) -- the entry point's one launcher call.  flops / bytes: the profiler's
+// factors on evaluations x parameters (x B for the FLOPs)
+template <class Own, class OwnLate, class Run>
+int head_flow_sample_call(fv_handle* h, const char* who, int B, int n_steps, const char* too_small, double flops, double bytes, fv_stream s, Own&& own, OwnLate&& own_late,
+                          Run&& run) {
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "%s: the head is not in flow mode (fv_head_set_flow)", who);
+  FV_TRY(own());
+  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "%s: n_steps = %d must be >= 1", who, n_steps);
+  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "%s: B=%d outside 1 .. max_batch=%d", who, B, h->d.max_batch);
+  FV_TRY(own_late());
+  float* scr = nullptr;
+  FV_TRY(head_scratch(h, B, too_small, &scr));
+  hipStream_t st = static_cast<hipStream_t>(s);
+  const double work = flow_evals(h, n_steps) * head_param_count(h);
+  prof_begin(h, FV_FAM_HEAD, flops * B * work, bytes * work, st);
+  const int rc = run(scr, head_rk_rows(h, B, scr), st);
+  prof_end(h, st);
+  return rc;
+}
+
 // n host floats -> the handle's device vector *buf, allocated first when `fresh` (every setter has its own rule for that; an old vector stays until fv_destroy).
 // A head kernel still in flight on any stream may be reading the previous values: a configuration call, so it simply waits
 int head_upload(fv_handle* h, float** buf, bool fresh, const float* host, size_t n) {
@@ -187,40 +210,31 @@ int fv_head_flow_prepare_prefix(fv_handle* h, const float* targets, int B, uint6
 int fv_head_flow_sample(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                         uint64_t seed, uint64_t offset, float* actions, fv_stream s) {
   HandleScope _hs(h);
-  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
-  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample: the head is not in flow mode (fv_head_set_flow)");
-  if (!flat_params || !pooled || !states || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: null pointer");
-  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: n_steps = %d must be >= 1", n_steps);
-  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
-  float* scr = nullptr;
-  FV_TRY(head_scratch(h, B, "workspace too small for the flow sampler", &scr));
-  hipStream_t st = static_cast<hipStream_t>(s);
-  prof_begin(h, FV_FAM_HEAD, 2.0 * B * flow_evals(h, n_steps) * head_param_count(h), 4.0 * flow_evals(h, n_steps) * head_param_count(h), st);
-  const int rc = fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr,
-                                        h->flow_solver, head_rk_rows(h, B, scr));
-  prof_end(h, st);
-  return rc;
+  return head_flow_sample_call(
+      h, "fv_head_flow_sample", B, n_steps, "workspace too small for the flow sampler", 2.0, 4.0, s,
+      [&] { return !flat_params || !pooled || !states || !actions ? fv_fail(FV_ERR_ARG, "fv_head_flow_sample: null pointer") : FV_OK; }, [] { return (int)FV_OK; },
+      [&](float* scr, float* rk_rows, hipStream_t st) {
+        return fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr, h->flow_solver,
+                                      rk_rows);
+      });
 }
 
 int fv_head_flow_sample_prefix(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                                uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out,
                                fv_stream s) {
   HandleScope _hs(h);
-  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
-  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_prefix: the head is not in flow mode (fv_head_set_flow)");
-  if (h->hd.pk <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_prefix: prefix mode is off (fv_head_set_flow_prefix)");
-  if (!flat_params || !pooled || !states || !prev || !delays || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: null pointer");
-  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: n_steps = %d must be >= 1", n_steps);
-  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
-  if (shift < 0 || shift > h->hd.pk) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: shift = %d outside 0 .. chunk = %d", shift, h->hd.pk);
-  float* scr = nullptr;
-  FV_TRY(head_scratch(h, B, "workspace too small for the flow sampler", &scr));
-  hipStream_t st = static_cast<hipStream_t>(s);
-  prof_begin(h, FV_FAM_HEAD, 2.0 * B * flow_evals(h, n_steps) * head_param_count(h), 4.0 * flow_evals(h, n_steps) * head_param_count(h), st);
-  const int rc = fv::launch_flow_sample_prefix(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, delays, actions, chunk_out, scr, st,
-                                               h->has_io ? &h->io : nullptr, h->flow_solver, head_rk_rows(h, B, scr));
-  prof_end(h, st);
-  return rc;
+  return head_flow_sample_call(
+      h, "fv_head_flow_sample_prefix", B, n_steps, "workspace too small for the flow sampler", 2.0, 4.0, s,
+      [&] {
+        if (h->hd.pk <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_prefix: prefix mode is off (fv_head_set_flow_prefix)");
+        return !flat_params || !pooled || !states || !prev || !delays || !actions ? fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: null pointer") : FV_OK;
+      },
+      [&] { return shift < 0 || shift > h->hd.pk ? fv_fail(FV_ERR_ARG, "fv_head_flow_sample_prefix: shift = %d outside 0 .. chunk = %d", shift, h->hd.pk) : FV_OK; },
+      [&](float* scr, float* rk_rows, hipStream_t st) {
+        const fv::FlowPin pin{prev, delays, shift, chunk_out};
+        return fv::launch_flow_sample(h->hd, h->flow, flat_params, pooled, states, B, n_steps, noise, seed, offset, actions, scr, st, h->has_io ? &h->io : nullptr, h->flow_solver,
+                                      rk_rows, &pin);
+      });
 }
 
 int fv_head_set_flow_solver(fv_handle* h, int solver) {
@@ -267,21 +281,17 @@ int fv_head_flow_sample_guided(fv_handle* h, const float* flat_params, const flo
                                uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* row_mask, float* actions, float* chunk_out,
                                fv_stream s) {
   HandleScope _hs(h);
-  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
-  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_guided: the head is not in flow mode (fv_head_set_flow)");
-  if (!h->guide.step_w) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_guided: guidance is not configured (fv_head_set_flow_guidance)");
-  if (!flat_params || !pooled || !states || !prev || !actions) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: null pointer");
-  if (n_steps < 1) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: n_steps = %d must be >= 1", n_steps);
-  if (B < 1 || B > h->d.max_batch) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: B=%d outside 1 .. max_batch=%d", B, h->d.max_batch);
-  if (shift < 0 || shift > h->guide.chunk) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: shift = %d outside 0 .. chunk = %d", shift, h->guide.chunk);
-  float* scr = nullptr;
-  FV_TRY(head_scratch(h, B, "workspace too small for the guided flow sampler", &scr));
-  hipStream_t st = static_cast<hipStream_t>(s);
-  prof_begin(h, FV_FAM_HEAD, 4.0 * B * flow_evals(h, n_steps) * head_param_count(h), 8.0 * flow_evals(h, n_steps) * head_param_count(h), st);
-  const int rc = fv::launch_flow_sample_guided(h->hd, h->flow, h->guide, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, row_mask, actions,
-                                               chunk_out, scr, st, h->has_io ? &h->io : nullptr, h->flow_solver, head_rk_rows(h, B, scr));
-  prof_end(h, st);
-  return rc;
+  return head_flow_sample_call(
+      h, "fv_head_flow_sample_guided", B, n_steps, "workspace too small for the guided flow sampler", 4.0, 8.0, s,
+      [&] {
+        if (!h->guide.step_w) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_guided: guidance is not configured (fv_head_set_flow_guidance)");
+        return !flat_params || !pooled || !states || !prev || !actions ? fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: null pointer") : FV_OK;
+      },
+      [&] { return shift < 0 || shift > h->guide.chunk ? fv_fail(FV_ERR_ARG, "fv_head_flow_sample_guided: shift = %d outside 0 .. chunk = %d", shift, h->guide.chunk) : FV_OK; },
+      [&](float* scr, float* rk_rows, hipStream_t st) {
+        return fv::launch_flow_sample_guided(h->hd, h->flow, h->guide, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, row_mask, actions, chunk_out, scr,
+                                             st, h->has_io ? &h->io : nullptr, h->flow_solver, rk_rows);
+      });
 }
 
 int fv_head_set_loss(fv_handle* h, const fv_head_loss_spec* spec) {

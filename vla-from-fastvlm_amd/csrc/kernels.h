@@ -345,23 +345,23 @@ struct HeadFlow { const float* freq; int time_dist; float dist_a, dist_b; const 
 // one launch: draws (or reads) t per row and noise per element, writes x_t and phi(t) into their columns of saved's cat and u = noise - targets into u_out.
 // d.draws = S > 1: targets (B, da) stay per observation; head row s B + b draws what row b draws at offset + (s << 56); noise, t and u_out have S B rows.
 // FV_ERR_ARG, nothing enqueued, when S > 1 and any of bits 56 .. 59 of the offset is set
-// prefix mode (d.pk > 0): the PREFIX instance -- row r's delay is delays[r] clamped to 0 .. pd (device int32, S B of them) or, with delays == null, drawn from
+// prefix mode (d.pk > 0): the kernel's PREFIX instance -- row r's delay is delays[r] clamped to 0 .. pd (device int32, S B of them) or, with delays == null, drawn from
 // word z of the group-0 Philox block that yields t; the first d steps of x_t are COPIES of targets, m and the row's byte mask in `saved` are written too
 int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t,
                         float* saved, float* u_out, hipStream_t s, const int32_t* delays = nullptr);
-// the Euler sampler: conditioning once, then three launches per step.  scratch: flow_sample_scratch_bytes(d, B)
+// the sampler: conditioning once, then three launches per network evaluation.  scratch: flow_sample_scratch_bytes(d, B)
+// pin != null: the prefix sampler (d.pk > 0).  Row b's first min(delays[b], pd, pk - shift) steps are pinned to prev[b][k + shift] (normalised) from the start
+// to the end, and the mask block of fusion.0 joins c once per call: the same launches and scratch, the PREFIX instances of three kernels.  chunk_out (B, da)
+// or null: the final normalised x_0
+struct FlowPin { const float* prev; const int32_t* delays; int shift; float* chunk_out; };
 size_t flow_sample_scratch_bytes(const HeadDims& d, int B);
 int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
-                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver = 0, float* rk_rows = nullptr);
-// higher-order integrators (fv_head_set_flow_solver), for all three samplers: solver = FV_FLOW_SOLVER_*; 0 takes the Euler loop and the Euler kernels as they
-// are.  Another one runs n_steps x stages evaluations, each the Euler step's launches with the x update as a Runge-Kutta stage, over rk_rows: two more
-// (B, da) rows, the step's start x0 and the running sum S, flow_rk_scratch_bytes(d, B) in all.  FV_ERR_ARG for an unknown solver, FV_ERR_STATE without the rows
+                       uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver = 0, float* rk_rows = nullptr,
+                       const FlowPin* pin = nullptr);
+// the integrators (fv_head_set_flow_solver), for all three samplers: solver = FV_FLOW_SOLVER_*, n_steps x stages evaluations whose x update is a Runge-Kutta
+// stage.  Euler has one stage and needs nothing more; the others work over rk_rows: two more (B, da) rows, the step's start x0 and the running sum S,
+// flow_rk_scratch_bytes(d, B) in all.  FV_ERR_ARG for an unknown solver, FV_ERR_STATE without the rows
 size_t flow_rk_scratch_bytes(const HeadDims& d, int B);
-// the prefix sampler (d.pk > 0): row b's first min(delays[b], pd, pk - shift) steps are pinned to prev[b][k + shift] (normalised) from the start to the end; the
-// mask block of fusion.0 joins c once per call; three launches per step as launch_flow_sample, step C in its PREFIX instance.  Same scratch
-int launch_flow_sample_prefix(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
-                              uint64_t seed, uint64_t offset, const float* prev, int shift, const int32_t* delays, float* actions, float* chunk_out, float* scratch,
-                              hipStream_t s, const HeadIoNorm* io, int solver = 0, float* rk_rows = nullptr);
 // guided sampling (fv_head_set_flow_guidance): step_w = chunk device floats >= 0, beta the largest guidance weight, live_steps = 1 + the last step whose
 // weight is not 0 (0: none).  prev (B, da): the previous chunk, normalised; Y[b][k] = prev[b][k + shift]; row_mask (B) int32 or null; chunk_out (B, da) or null:
 // the final normalised x_0.  A row with all-zero omega comes out as launch_flow_sample's row, bit for bit.  scratch: flow_guided_scratch_bytes(d, B)
