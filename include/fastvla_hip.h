@@ -429,6 +429,44 @@ int fv_head_flow_sample_prefix(fv_handle* h, const float* flat_params, const flo
 #define FV_FLOW_SOLVER_HEUN 2
 #define FV_FLOW_SOLVER_RK4 3
 int fv_head_set_flow_solver(fv_handle* h, int solver);
+/* ---- several samples per observation, one chosen on the device.  A call draws S candidates per observation and returns ONE of them: the one the others
+ * agree with (MEDOID: the smallest sum of squared distances to the rest), the one that continues the previous chunk (COHERENT: the backward-coherence
+ * criterion of Bidirectional Decoding, Liu et al. 2024), or simply candidate 0 (FIRST).  The mean of the candidates is deliberately not offered: between
+ * two modes it is a chunk the policy never learned.
+ * Head rows are sample-major, r = s B + b, and candidate s of a call at offset o is EXACTLY the single-sample call at o + (s << 56), as the draws of
+ * fv_head_set_flow_draws are: candidate 0 is fv_head_flow_sample's (fv_head_flow_sample_prefix's) output bit for bit.  Bits 56 .. 59 of the offset number the
+ * candidates: with S > 1 an offset that has one of them set is refused (FV_ERR_ARG, nothing enqueued).
+ * fv_head_set_flow_samples: max_samples 1 .. FV_FLOW_SAMPLES_MAX; 1 (the default; fv_head_set_flow(NULL) returns to it) switches it off, every size and
+ * every launch is then what it was.  The sampler's rows in the workspace grow to max_samples x max_batch head rows (the higher-order solvers' two rows too),
+ * so the FIRST call that names more than 1 must come before fv_bind_workspace (FV_ERR_STATE afterwards).  step_weights_host: `chunk` HOST floats, finite and
+ * >= 0, the per-step weights w[k] of the coherence score (fastvla_hip.select.coherence_weights); NULL: COHERENT is refused.  chunk >= 1 divides action_dim.
+ * Later calls with the same two integers may change the weights at any time (they synchronise the device).  Flow mode only (FV_ERR_STATE); FV_ERR_ARG,
+ * changing nothing, outside the ranges. */
+#define FV_FLOW_SAMPLES_MAX 16
+#define FV_FLOW_SELECT_FIRST 0
+#define FV_FLOW_SELECT_MEDOID 1
+#define FV_FLOW_SELECT_COHERENT 2
+int fv_head_set_flow_samples(fv_handle* h, int max_samples, int chunk, const float* step_weights_host);
+/* fv_head_flow_sample (delays == NULL) or fv_head_flow_sample_prefix (delays != NULL: prefix mode, prev and shift pin as there, every candidate of a row pins
+ * the same steps) for S candidates, 1 <= S <= max_samples, then the choice.  noise: (S B, action_dim) sample-major, or NULL.
+ *     MEDOID    score[s] = sum over s' ascending of sum_e (x_s[e] - x_s'[e])^2
+ *     COHERENT  score[s] = sum_{k < chunk - shift} w[k] sum_a (x_s[k][a] - prev[b][k + shift][a])^2; a row whose row_mask ((B) int32 or NULL) is 0 takes the
+ *               MEDOID score.  A weight of 0 selects its step away; prev beyond the overlap is never read
+ *     FIRST     candidate 0 (scores_out reports the MEDOID scores)
+ * The smallest score wins, a non-finite score counts as +inf, ties go to the lowest index: shift == chunk, all-zero weights or no finite score choose
+ * candidate 0.  A candidate with a NaN or +-inf element scores +inf in every mode and the MEDOID sums of the others leave it out: it wins only as
+ * candidate 0 of a row without a finite score. chunk_out (B, action_dim) is a COPY of the chosen normalised candidate; actions (B, action_dim) applies the one fused multiply-add of the
+ * folded action statistics to it, so FIRST is the single-sample call bit for bit.  Optional (NULL: not written): candidates_out (S B, action_dim) normalised,
+ * sample-major; choice_out (B) int32; scores_out (B, S); spread_out (B, action_dim), the population standard deviation over the candidates per element.
+ * S = 1 with every optional output NULL is the single-sample call's launches (the final stage writes actions and chunk_out itself); otherwise one launch
+ * more than the single-sample call for S = 1, two more for S > 1 (the conditioning is computed on B rows and copied): no atomics, no host
+ * synchronisation, no allocation, every sum in a fixed order, two calls give the same bits.  Guided sampling with candidates is not offered.
+ * Refused before anything is enqueued, in fv_head_flow_sample's order: FV_ERR_STATE when flow mode is off, delays are given without prefix mode, COHERENT
+ * is asked for without weights, or no workspace is bound; FV_ERR_ARG for a null flat_params / pooled / states / actions / chunk_out, prev missing where
+ * delays or COHERENT need it, S outside 1 .. max_samples, an unknown select, n_steps < 1, B outside 1 .. max_batch, shift outside 0 .. chunk. */
+int fv_head_flow_sample_multi(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                              uint64_t seed, uint64_t offset, int S, int select, const float* prev, int shift, const int32_t* row_mask, const int32_t* delays,
+                              float* actions, float* chunk_out, float* candidates_out, int32_t* choice_out, float* scores_out, float* spread_out, fv_stream s);
 /* generic backward of the head from dL/dactions (B,A) f32 (what autograd hands a custom Function when the loss is
  * computed outside, e.g. lerobot_fastvla/modeling_fastvla.py:132 + loss.backward()); overwrites flat_grads. */
 int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_actions, int B, float dropout_p,

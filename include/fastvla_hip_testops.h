@@ -254,6 +254,13 @@ int fv_op_flow_vjp_prefix(int feat, int ds, int da, int hid, int fus, int time_d
  * dimensions: *out_floats = its offset in floats; its shape is (draws * B, cat width).  time_dim 0: the regression head; draws 1 and prefix_chunk 0: off.
  * The layout is the library's own (csrc/head_kernels.hip carve): tests ask for it here instead of repeating it. */
 int fv_op_head_saved_cat_offset(int feat, int ds, int da, int hid, int fus, int time_dim, int draws, int prefix_chunk, int B, size_t* out_floats);
+/* the selection kernel of fv_head_flow_sample_multi alone, on candidates the test supplies: cand (S B, da) device f32, sample-major (row s B + b); select
+ * FV_FLOW_SELECT_*; prev (B, da), shift, row_mask (B) int32 or NULL and step_w (chunk DEVICE floats) feed the coherence score; post_scale / post_shift (da)
+ * device floats or both NULL: the action statistics `actions` folds in.  Outputs as fv_head_flow_sample_multi's: actions, chunk_out (B, da); optional
+ * candidates_out (S B, da), choice_out (B) int32, scores_out (B, S), spread_out (B, da). */
+int fv_op_flow_select(const float* cand, int B, int S, int da, int select, const float* prev, int shift, const int32_t* row_mask, const float* step_w, int chunk,
+                      const float* post_scale, const float* post_shift, float* actions, float* chunk_out, float* candidates_out, int32_t* choice_out,
+                      float* scores_out, float* spread_out, fv_stream s);
 
 #ifdef __cplusplus
 }

@@ -194,6 +194,10 @@ struct fv_handle {
   int guide_chunk = 0;            // > 0: the workspace plan holds the guided sampler's rows (stays when guidance is switched off)
   int flow_solver = FV_FLOW_SOLVER_EULER;   // fv_head_set_flow_solver: the integrator of all three samplers
   bool flow_rk_rows = false;      // true: the workspace plan holds the higher-order solvers' two rows (from the first call that names one; stays)
+  int flow_samples = 1;           // fv_head_set_flow_samples: the most candidates per observation of fv_head_flow_sample_multi; > 1: the plan's sampler rows (and the solvers' two) hold flow_samples x B head rows
+  float* select_w_buf = nullptr;  // its device step weights (select_chunk floats), allocated by the first call for a chunk length and kept
+  const float* select_w = nullptr;   // null: coherent selection is refused
+  int select_chunk = 0;
   float* loss_w = nullptr;        // fv_head_set_loss_weights: ONE device vector of 2 da floats per handle ([0, A) dim_w, [da, da + K) step_w), allocated on first use
   TrainState train;               // unfrozen-backbone training (train_path.inc): library-owned transposed bf16 weight copies
   int batch_invariant = 0;        // fv_set_batch_invariant: the inference tower never takes the range forms either
@@ -404,8 +408,10 @@ int load_ffn(Loader& L, const std::string& pre, int C, int hidden, float bn_eps,
 }
 
 // the rows of the flow samplers inside the plan's head scratch (the guided sampler's once it is configured); the higher-order solvers' rows start behind them
+// (fv_head_set_flow_samples: the multi-sample call's rows for flow_samples x B head rows join the maximum)
 size_t head_sampler_bytes(const fv_handle* h, int B) {
-  return std::max(fv::flow_sample_scratch_bytes(h->hd, B), h->guide_chunk > 0 ? fv::flow_guided_scratch_bytes(h->hd, B) : (size_t)0);
+  const size_t one = std::max(fv::flow_sample_scratch_bytes(h->hd, B), h->guide_chunk > 0 ? fv::flow_guided_scratch_bytes(h->hd, B) : (size_t)0);
+  return h->flow_samples > 1 ? std::max(one, fv::flow_multi_scratch_bytes(h->hd, h->flow_samples * B)) : one;
 }
 
 WsPlan plan_ws(const fv_handle* h, int B, int T, int splice) {
@@ -459,7 +465,7 @@ WsPlan plan_ws(const fv_handle* h, int B, int T, int splice) {
                                : rows % 256 == 0 ? (size_t)(rows <= 2048 ? 8 : 4) * rows * ((std::max((size_t)d.llm_hidden, qkvw) + 255) / 256 * 256) * 4 : 0;
   p.splitk = take(p.splitk_bytes);
   // (flow mode: the sampler's rows live here too, the guided sampler's once it is configured, and BEHIND them the higher-order solvers' two rows once one is named)
-  p.head_scr = take(std::max(fv::head_bwd_scratch_bytes(h->hd, B), head_sampler_bytes(h, B) +(h->flow_rk_rows ? fv::flow_rk_scratch_bytes(h->hd, B) : (size_t)0)));
+  p.head_scr = take(std::max(fv::head_bwd_scratch_bytes(h->hd, B), head_sampler_bytes(h, B) +(h->flow_rk_rows ? fv::flow_rk_scratch_bytes(h->hd, h->flow_samples * B) : (size_t)0)));
   // long sequences (the spliced prefill: 256 image + T text positions) run the split-bf16 attention kernel: its per-layer K / V records
   const int Tseq = T + (splice ? (int)P : 0);
   p.attn_scr_bytes = (d.llm_precision != 0 && Tseq >= fv::FV_ATTN_SPLIT_MIN_T && (d.llm_head_dim == 64 || d.llm_head_dim == 128))

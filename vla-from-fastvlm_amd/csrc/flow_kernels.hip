@@ -6,6 +6,8 @@
 //                                          add for it sits under `if constexpr (PREFIX)` in the one body each of them has
 //   flow_guide_* / flow_vjp_t_kernel       guided sampling (fv_head_set_flow_guidance; real-time chunking): the step's forward with z3 and v kept, J^T omega
 //                                          through three transposed products and a LayerNorm backward, and the update
+//   flow_cond_broadcast_kernel             several samples per observation (fv_head_flow_sample_multi): the start runs on a (B, S) grid, the conditioning on B
+//                                          rows and is copied, the steps run unchanged on S B rows; the choice among them is flow_select_kernels.hip's
 //   flow_rk_stage                          the x update of every solver (fv_head_set_flow_solver), in step C and in the guided update: an explicit
 //                                          Runge-Kutta stage, Euler being the scheme with one (FLOW_TABLEAUX); flow_integrate is the one loop over them
 // The state branch of every sampler is head_kernels.hip's (launch_head_state_branch); the draws come from common.h philox under this file's key.
@@ -104,29 +106,41 @@ __global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restri
 struct FlowPinned { const float* prev; const int32_t* delays; int pd, chunk, shift; };
 __device__ __forceinline__ int flow_pinned_steps(const FlowPinned& p, int b) { return min(min(max(p.delays[b], 0), p.pd), p.chunk - p.shift); }
 
-// the sampler's start: xphi (B, da + te) <- [ noise or the draws of (seed, offset); PREFIX: prev on the pinned elements | phi(t0) ]
+// the sampler's start: xphi (S B, da + te) <- [ noise or the draws of (seed, offset); PREFIX: prev on the pinned elements | phi(t0) ]
+// grid (B, S): block (b, s) writes head row r = s B + b, candidate s of observation b (fv_head_set_flow_samples; S == 1: blockIdx.y == 0, the rows and the
+// arithmetic as ever).  It draws what row b draws at offset + (s << 56) -- the counter is (group, b, offset) --, so candidate s is the single-sample call at
+// that offset and candidate 0 is today's sample.  Explicit noise (S B, da) is read at r.  PREFIX: prev / delays are observation b's; delays_rows (S B) or null
+// takes a copy of the row's delay, which step C then reads per head row
 template <bool PREFIX>
 __global__ __launch_bounds__(256) void flow_init_kernel(const float* __restrict__ noise, float* __restrict__ xphi, int da, int te, const float* __restrict__ freq,
-                                                         float t0, uint64_t seed, uint64_t offset, FlowPinned p) {
-  const int row = blockIdx.x;
+                                                         float t0, uint64_t seed, uint64_t offset, FlowPinned p, int32_t* __restrict__ delays_rows) {
+  const int obs = blockIdx.x, row = blockIdx.y * gridDim.x + obs;
+  offset += (uint64_t)blockIdx.y << 56;
   int A = 0, pin = 0;
   if constexpr (PREFIX) {
     A = da / p.chunk;
-    pin = flow_pinned_steps(p, row) * A;
+    pin = flow_pinned_steps(p, obs) * A;
+    if (delays_rows && threadIdx.x == 0) delays_rows[row] = p.delays[obs];
   }
   float* xr = xphi + (size_t)row * (da + te);
   for (int g = threadIdx.x; g * 4 < da; g += 256) {
     float n[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)row, seed, offset, n);
+    if (!noise) flow_normals4(1u + (uint32_t)g, (uint32_t)obs, seed, offset, n);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int i = g * 4 + j;
       if (i >= da) break;
-      if (PREFIX && i < pin) xr[i] = p.prev[(size_t)row * da + i + (size_t)p.shift * A];   // (i + shift A < (p_b + shift) A <= da)
+      if (PREFIX && i < pin) xr[i] = p.prev[(size_t)obs * da + i + (size_t)p.shift * A];   // (i + shift A < (p_b + shift) A <= da)
       else xr[i] = noise ? noise[(size_t)row * da + i] : n[j];
     }
   }
   for (int i = threadIdx.x; i < te / 2; i += 256) flow_phi(xr + da, freq, te / 2, t0, i);
+}
+// c (B, n) -> the rows of candidates 1 .. S - 1 (grid.y = S - 1): the conditioning depends on the observation only, so it is computed on B rows and copied
+__global__ __launch_bounds__(256) void flow_cond_broadcast_kernel(float* __restrict__ c, int B, int n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)B * n) return;
+  c[(size_t)(1 + blockIdx.y) * B * n + i] = c[i];
 }
 
 // The sampler's products keep linear_fwd_kernel's layout: one wave per output column n, 8 batch rows per pass, coalesced weight reads, a wave_sum per row
@@ -516,15 +530,42 @@ FlowScratch flow_carve(const HeadDims& d, int B, float* base) {
   return r;
 }
 // the conditioning of a sampler call (4 launches): state LayerNorm, state projection, the t-independent part of fusion.0, the start [x | phi(t0)].
-// pin != null: the PREFIX instances of the last two
+// pin != null: the PREFIX instances of the last two.  S > 1 (fv_head_flow_sample_multi; fs carved for S B rows): the state branch and c run on the B
+// observations, one more launch copies c into the rows of candidates 1 .. S - 1, and the start writes all S B rows (delays_rows: its copy of the delays)
 void flow_condition(const HeadDims& d, const HeadFlow& f, const HeadOffsets& ho, const FlowScratch& fs, const float* P, const float* pooled, const float* states,
-                    int B, const float* noise, float t0, uint64_t seed, uint64_t offset, hipStream_t s, const HeadIoNorm* io, const FlowPinned* pin = nullptr) {
+                    int B, const float* noise, float t0, uint64_t seed, uint64_t offset, hipStream_t s, const HeadIoNorm* io, const FlowPinned* pin = nullptr,
+                    int S = 1, int32_t* delays_rows = nullptr) {
   const dim3 blk(256);
   const FlowPinned p = pin ? *pin : FlowPinned{};
   launch_head_state_branch(d, P, states, B, fs.n0, fs.xh0, fs.rstd0, fs.z1, fs.sb, d.hid, s, io);
   hipLaunchKernelGGL(pin ? flow_cond_kernel<true> : flow_cond_kernel<false>, dim3(cdiv(d.fus, 4), cdiv(B, 8)), blk, 0, s, pooled, d.feat, fs.sb, d.hid, P + ho.o[HP_FUS0_W],
                      head_cat_width(d), P + ho.o[HP_FUS0_B], fs.c, B, d.fus, d.feat + d.hid + d.da + d.te, p);
-  hipLaunchKernelGGL(pin ? flow_init_kernel<true> : flow_init_kernel<false>, dim3(B), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, t0, seed, offset, p);
+  if (S > 1) hipLaunchKernelGGL(flow_cond_broadcast_kernel, dim3(cdiv((long)B * d.fus, 256), S - 1), blk, 0, s, fs.c, B, d.fus);
+  hipLaunchKernelGGL(pin ? flow_init_kernel<true> : flow_init_kernel<false>, dim3(B, S), blk, 0, s, noise, fs.xphi, d.da, d.te, f.freq, t0, seed, offset, p, delays_rows);
+}
+// The launches of the plain and the prefix sampler, checks done: the conditioning on B observations, then three launches per network evaluation on R = S B
+// head rows (S == 1: launch_flow_sample's, as ever).  io: the state statistics; io_out: the action statistics the final stage folds (null: normalised output).
+// delays_rows (S > 1 with pin): R ints the start fills, which step C reads per head row in place of pin->delays
+void flow_sample_rows(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int S, int n_steps, const float* noise,
+                      uint64_t seed, uint64_t offset, float* actions, float* chunk_out, const FlowScratch& fs, hipStream_t s, const HeadIoNorm* io,
+                      const HeadIoNorm* io_out, int solver, float* rk_rows, const FlowPin* pin, int32_t* delays_rows) {
+  const HeadOffsets ho = head_offsets(d);
+  const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te, R = S * B;
+  const dim3 blk(256);
+  const unsigned b8 = cdiv(R, 8);
+  const FlowPinned p = pin ? FlowPinned{pin->prev, pin->delays, d.pd, d.pk, pin->shift} : FlowPinned{};
+  FlowPinned pr = p;   // step C's: a delay per head row
+  if (pin && S > 1) pr.delays = delays_rows;
+  const bool single = FLOW_TABLEAUX[solver].stages == 1;
+  const auto step_c = pin ? (single ? flow_step_c_kernel<true, true> : flow_step_c_kernel<true, false>) : (single ? flow_step_c_kernel<false, true> : flow_step_c_kernel<false, false>);
+  flow_condition(d, f, ho, fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io, pin ? &p : nullptr, S, pin && S > 1 ? delays_rows : nullptr);
+  flow_integrate(d, R, n_steps, solver, rk_rows, actions, chunk_out, io_out, [&](const FlowStage& st, const FlowOut& out) {
+    hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, R, d.fus);
+    hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], fs.a3,
+                       (float*)nullptr, R, d.fus);
+    hipLaunchKernelGGL(step_c, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw,
+                       d.te, st.rk, st.t_next, f.freq, out.actions, out.chunk_out, out.post_scale, out.post_shift, R, d.da, pr);
+  });
 }
 }  // namespace
 
@@ -542,24 +583,58 @@ int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, con
   if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "%s: B and n_steps must be positive", who);
   if (pin && (pin->shift < 0 || pin->shift > d.pk)) return fv_fail(FV_ERR_ARG, "%s: shift = %d outside 0 .. chunk = %d", who, pin->shift, d.pk);
   if (const int rc = flow_solver_check(who, solver, rk_rows)) return rc;
-  const HeadOffsets ho = head_offsets(d);
-  const FlowScratch fs = flow_carve(d, B, scratch);
-  const int cw = head_cat_width(d), xo = d.feat + d.hid, xw = d.da + d.te;
-  const dim3 blk(256);
-  const unsigned b8 = cdiv(B, 8);
-  const FlowPinned p = pin ? FlowPinned{pin->prev, pin->delays, d.pd, d.pk, pin->shift} : FlowPinned{};
-  const bool single = FLOW_TABLEAUX[solver].stages == 1;
-  const auto step_c = pin ? (single ? flow_step_c_kernel<true, true> : flow_step_c_kernel<true, false>) : (single ? flow_step_c_kernel<false, true> : flow_step_c_kernel<false, false>);
-  flow_condition(d, f, ho, fs, P, pooled, states, B, noise, 1.0f, seed, offset, s, io, pin ? &p : nullptr);
-  flow_integrate(d, B, n_steps, solver, rk_rows, actions, pin ? pin->chunk_out : nullptr, io, [&](const FlowStage& st, const FlowOut& out) {
-    hipLaunchKernelGGL(flow_step_a_kernel, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.xphi, xw, P + ho.o[HP_FUS0_W], cw, xo, fs.c, fs.z2, B, d.fus);
-    hipLaunchKernelGGL(flow_step_b_kernel<false>, dim3(cdiv(d.fus, 4), b8), blk, 0, s, fs.z2, P + ho.o[HP_FUS_LN_W], P + ho.o[HP_FUS_LN_B], P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], fs.a3,
-                       (float*)nullptr, B, d.fus);
-    hipLaunchKernelGGL(step_c, dim3(cdiv(d.da, 4), b8), blk, 0, s, fs.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], fs.xphi, xw,
-                       d.te, st.rk, st.t_next, f.freq, out.actions, out.chunk_out, out.post_scale, out.post_shift, B, d.da, p);
-  });
+  flow_sample_rows(d, f, P, pooled, states, B, 1, n_steps, noise, seed, offset, actions, pin ? pin->chunk_out : nullptr, flow_carve(d, B, scratch), s, io, io, solver, rk_rows,
+                   pin, nullptr);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
+}
+
+namespace {
+// the rows of a multi-sample call: the sampler's for S B head rows, then the S B normalised candidates and, for the prefix sampler, a delay per head row
+struct MultiScratch { FlowScratch fs; float* cand; int32_t* delays; size_t total; };
+MultiScratch multi_carve(const HeadDims& d, int R, float* base) {
+  MultiScratch r;
+  r.fs = flow_carve(d, R, base);
+  size_t o = r.fs.total;
+  auto take = [&](size_t n) { float* p = base ? base + o : nullptr; o += (n + 3) / 4 * 4; return p; };
+  r.cand = take((size_t)R * d.da);
+  r.delays = reinterpret_cast<int32_t*>(take(R));
+  r.total = o;
+  return r;
+}
+}  // namespace
+
+size_t flow_multi_scratch_bytes(const HeadDims& d, int R) { return d.te > 0 ? multi_carve(d, R, nullptr).total * sizeof(float) : 0; }
+
+// S candidates per observation in one call, then the choice among them (flow_select_kernels.hip).  The conditioning runs on B rows and is copied, the steps
+// run unchanged on S B rows -- at B = 1 up to eight candidates share the one pass flow_dot8 makes anyway --, the final stage writes the normalised
+// candidates into scratch without the folded statistics, and the selection kernel writes every output.  pin != null: the candidates of the prefix sampler
+int launch_flow_sample_multi(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int S, int n_steps,
+                             const float* noise, uint64_t seed, uint64_t offset, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows,
+                             const FlowPin* pin, const FlowSelect& sel) {
+  const char* who = "flow_sample_multi";
+  if (d.te <= 0 || !f.freq) return fv_fail(FV_ERR_STATE, "%s: the head is not in flow mode (fv_head_set_flow)", who);
+  if (pin && (d.pk < 2 || d.da % d.pk || d.pd < 1 || d.pd >= d.pk)) return fv_fail(FV_ERR_STATE, "%s: prefix mode is off (fv_head_set_flow_prefix)", who);
+  if (!P || !pooled || !states || (pin && (!pin->prev || !pin->delays)) || !scratch) return fv_fail(FV_ERR_ARG, "%s: null pointer", who);
+  if (B <= 0 || n_steps < 1) return fv_fail(FV_ERR_ARG, "%s: B and n_steps must be positive", who);
+  if (S < 1 || S > FV_FLOW_SAMPLES_MAX) return fv_fail(FV_ERR_ARG, "%s: S = %d outside 1 .. %d", who, S, FV_FLOW_SAMPLES_MAX);
+  if (S > 1 && (offset >> 56 & 15)) return fv_fail(FV_ERR_ARG, "%s: bits 56 .. 59 of the offset number the candidates and must be 0 with more than one", who);
+  if (pin && (pin->shift < 0 || pin->shift > d.pk)) return fv_fail(FV_ERR_ARG, "%s: shift = %d outside 0 .. chunk = %d", who, pin->shift, d.pk);
+  if (const int rc = flow_solver_check(who, solver, rk_rows)) return rc;
+  if (const int rc = flow_select_check(sel, S, d.da)) return rc;
+  const MultiScratch ms = multi_carve(d, S * B, scratch);
+  // one candidate and none of the optional outputs: there is nothing to choose and nothing to report, so the final stage writes actions and chunk_out
+  // itself, as the prefix sampler always did -- the single-sample call's launches, no more
+  if (S == 1 && !sel.candidates_out && !sel.choice_out && !sel.scores_out && !sel.spread_out) {
+    flow_sample_rows(d, f, P, pooled, states, B, 1, n_steps, noise, seed, offset, sel.actions, sel.chunk_out, ms.fs, s, io, io, solver, rk_rows, pin, nullptr);
+    FV_HIP_CHECK(hipGetLastError());
+    return FV_OK;
+  }
+  // (S == 1 needs no row beyond the plain sampler's, so a handle that never grew its plan can make the call: the one candidate lands in chunk_out, where the
+  // selection kernel reads it and writes it back, element by element in the thread that owns it)
+  float* cand = S > 1 ? ms.cand : sel.chunk_out;
+  flow_sample_rows(d, f, P, pooled, states, B, S, n_steps, noise, seed, offset, cand, nullptr, ms.fs, s, io, nullptr, solver, rk_rows, pin, ms.delays);
+  return launch_flow_select(cand, B, S, d.da, sel, io ? io->action_std : nullptr, io ? io->action_mean : nullptr, s);
 }
 
 namespace {

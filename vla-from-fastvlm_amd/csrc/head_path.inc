@@ -139,7 +139,7 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   }
   // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
   if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
-  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->hd.pk = h->hd.pd = 0; h->flow_solver = FV_FLOW_SOLVER_EULER; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
+  if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->hd.pk = h->hd.pd = 0; h->flow_solver = FV_FLOW_SOLVER_EULER; h->flow_samples = 1; h->select_w = nullptr; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
   const int half = spec->time_dim / 2;
   std::vector<float> fr(half);   // 2 pi / p_j, p_j geometric from min_period to max_period; in double, rounded once
   for (int j = 0; j < half; ++j) {
@@ -291,6 +291,60 @@ int fv_head_flow_sample_guided(fv_handle* h, const float* flat_params, const flo
       [&](float* scr, float* rk_rows, hipStream_t st) {
         return fv::launch_flow_sample_guided(h->hd, h->flow, h->guide, flat_params, pooled, states, B, n_steps, noise, seed, offset, prev, shift, row_mask, actions, chunk_out, scr,
                                              st, h->has_io ? &h->io : nullptr, h->flow_solver, rk_rows);
+      });
+}
+
+int fv_head_set_flow_samples(fv_handle* h, int max_samples, int chunk, const float* step_weights_host) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_samples: the head is not in flow mode (fv_head_set_flow)");
+  if (max_samples < 1 || max_samples > FV_FLOW_SAMPLES_MAX) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_samples: max_samples = %d outside 1 .. %d", max_samples, FV_FLOW_SAMPLES_MAX);
+  if (step_weights_host) {
+    if (chunk < 1 || h->hd.da % chunk) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_samples: chunk=%d must be >= 1 and divide action_dim=%d", chunk, h->hd.da);
+    for (int k = 0; k < chunk; ++k)
+      if (!std::isfinite(step_weights_host[k]) || step_weights_host[k] < 0.f)
+        return fv_fail(FV_ERR_ARG, "fv_head_set_flow_samples: step weight %d = %g must be finite and >= 0", k, (double)step_weights_host[k]);
+  }
+  // the sampler's rows (and the higher-order solvers' two) are sized for max_samples x B head rows: a workspace bound for another count does not fit
+  if (max_samples != h->flow_samples && h->ws)
+    return fv_fail(FV_ERR_STATE, "fv_head_set_flow_samples: the call that changes max_samples must come before fv_bind_workspace (the sampler's rows grow with it)");
+  if (step_weights_host) {
+    FV_TRY(head_upload(h, &h->select_w_buf, h->select_chunk != chunk, step_weights_host, (size_t)chunk));   // (another chunk length allocates anew)
+    h->select_chunk = chunk;
+  }
+  h->select_w = step_weights_host ? h->select_w_buf : nullptr;
+  h->flow_samples = max_samples;
+  return FV_OK;
+}
+
+int fv_head_flow_sample_multi(fv_handle* h, const float* flat_params, const float* pooled, const float* states, int B, int n_steps, const float* noise,
+                              uint64_t seed, uint64_t offset, int S, int select, const float* prev, int shift, const int32_t* row_mask, const int32_t* delays,
+                              float* actions, float* chunk_out, float* candidates_out, int32_t* choice_out, float* scores_out, float* spread_out, fv_stream s) {
+  HandleScope _hs(h);
+  const bool coherent = select == FV_FLOW_SELECT_COHERENT;
+  return head_flow_sample_call(
+      h, "fv_head_flow_sample_multi", B, n_steps, "workspace too small for the flow sampler's candidates", 2.0 * S, 4.0, s,
+      [&] {
+        if (delays && h->hd.pk <= 0) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_multi: delays need prefix mode (fv_head_set_flow_prefix)");
+        if (coherent && !h->select_w) return fv_fail(FV_ERR_STATE, "fv_head_flow_sample_multi: coherent selection has no step weights (fv_head_set_flow_samples)");
+        if (!flat_params || !pooled || !states || !actions || !chunk_out || ((delays || coherent) && !prev)) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_multi: null pointer");
+        if (S < 1 || S > h->flow_samples) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_multi: S = %d outside 1 .. max_samples = %d (fv_head_set_flow_samples)", S, h->flow_samples);
+        if (select != FV_FLOW_SELECT_FIRST && select != FV_FLOW_SELECT_MEDOID && !coherent)
+          return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_multi: unknown select %d (0 first, 1 medoid, 2 coherent)", select);
+        if (S > 1 && (offset >> 56 & 15))
+          return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_multi: bits 56 .. 59 of the offset number the candidates and must be 0 with more than one");
+        return (int)FV_OK;
+      },
+      [&] {
+        if (delays && (shift < 0 || shift > h->hd.pk)) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_multi: shift = %d outside 0 .. chunk = %d", shift, h->hd.pk);
+        if (coherent && (shift < 0 || shift > h->select_chunk)) return fv_fail(FV_ERR_ARG, "fv_head_flow_sample_multi: shift = %d outside 0 .. chunk = %d", shift, h->select_chunk);
+        return (int)FV_OK;
+      },
+      [&](float* scr, float* rk_rows, hipStream_t st) {
+        const fv::FlowPin pin{prev, delays, shift, nullptr};
+        const fv::FlowSelect sel{select, prev, shift, row_mask, h->select_w, h->select_chunk, actions, chunk_out, candidates_out, choice_out, scores_out, spread_out};
+        return fv::launch_flow_sample_multi(h->hd, h->flow, flat_params, pooled, states, B, S, n_steps, noise, seed, offset, scr, st, h->has_io ? &h->io : nullptr, h->flow_solver,
+                                            rk_rows, delays ? &pin : nullptr, sel);
       });
 }
 

@@ -358,6 +358,23 @@ size_t flow_sample_scratch_bytes(const HeadDims& d, int B);
 int launch_flow_sample(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int n_steps, const float* noise,
                        uint64_t seed, uint64_t offset, float* actions, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver = 0, float* rk_rows = nullptr,
                        const FlowPin* pin = nullptr);
+// several samples per observation (fv_head_set_flow_samples / fv_head_flow_sample_multi): S candidates, head rows sample-major (r = s B + b), candidate s the
+// single-sample call at offset + (s << 56); then ONE of them is chosen per observation on the device (flow_select_kernels.hip).  mode FV_FLOW_SELECT_*;
+// prev (B, da) normalised, shift, row_mask (B) int32 or null, step_w (chunk device floats >= 0): the coherence score's, all unused by the other modes;
+// actions, chunk_out (B, da); optional candidates_out (S B, da), choice_out (B), scores_out (B, S), spread_out (B, da).
+// scratch: flow_multi_scratch_bytes(d, S B); rk_rows: flow_rk_scratch_bytes(d, S B)
+struct FlowSelect {
+  int mode; const float* prev; int shift; const int32_t* row_mask; const float* step_w; int chunk;
+  float *actions, *chunk_out, *candidates_out; int32_t* choice_out; float *scores_out, *spread_out;
+};
+size_t flow_multi_scratch_bytes(const HeadDims& d, int R);
+int launch_flow_sample_multi(const HeadDims& d, const HeadFlow& f, const float* P, const float* pooled, const float* states, int B, int S, int n_steps,
+                             const float* noise, uint64_t seed, uint64_t offset, float* scratch, hipStream_t s, const HeadIoNorm* io, int solver, float* rk_rows,
+                             const FlowPin* pin, const FlowSelect& sel);
+// the selection alone, on candidates (S B, da) the caller supplies: flow_select_check refuses (nothing enqueued), launch_flow_select checks and launches.
+// post_scale / post_shift (da) or null: the action statistics `actions` folds in
+__attribute__((visibility("hidden"))) int flow_select_check(const FlowSelect& sel, int S, int da);
+int launch_flow_select(const float* cand, int B, int S, int da, const FlowSelect& sel, const float* post_scale, const float* post_shift, hipStream_t s);
 // the integrators (fv_head_set_flow_solver), for all three samplers: solver = FV_FLOW_SOLVER_*, n_steps x stages evaluations whose x update is a Runge-Kutta
 // stage.  Euler has one stage and needs nothing more; the others work over rk_rows: two more (B, da) rows, the step's start x0 and the running sum S,
 // flow_rk_scratch_bytes(d, B) in all.  FV_ERR_ARG for an unknown solver, FV_ERR_STATE without the rows

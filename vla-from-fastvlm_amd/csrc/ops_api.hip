@@ -398,4 +398,11 @@ int fv_op_head_saved_cat_offset(int feat, int ds, int da, int hid, int fus, int 
   return FV_OK;
 }
 
+int fv_op_flow_select(const float* cand, int B, int S, int da, int select, const float* prev, int shift, const int32_t* row_mask, const float* step_w, int chunk,
+                      const float* post_scale, const float* post_shift, float* actions, float* chunk_out, float* candidates_out, int32_t* choice_out,
+                      float* scores_out, float* spread_out, fv_stream s) {
+  const fv::FlowSelect sel{select, prev, shift, row_mask, step_w, chunk, actions, chunk_out, candidates_out, choice_out, scores_out, spread_out};
+  return fv::launch_flow_select(cand, B, S, da, sel, post_scale, post_shift, static_cast<hipStream_t>(s));
+}
+
 }  // extern "C"

@@ -76,6 +76,8 @@ class HeadFlowSpec(C.Structure):    # fv_head_flow_spec: 24 bytes
 
 FLOW_TIME_DISTS = {"uniform": 0, "logit_normal": 1}
 FLOW_SOLVERS = {"euler": 0, "midpoint": 1, "heun": 2, "rk4": 3}      # FV_FLOW_SOLVER_*
+FLOW_SELECTS = {"first": 0, "medoid": 1, "coherent": 2}              # FV_FLOW_SELECT_*
+FLOW_SAMPLES_MAX = 16                                                 # FV_FLOW_SAMPLES_MAX
 FLOW_SOLVER_STAGES = {"euler": 1, "midpoint": 2, "heun": 2, "rk4": 4}      # network evaluations per step
 
 
@@ -144,6 +146,8 @@ SIGNATURES = {
     "fv_head_set_flow_solver": (_i, [_vp, _i]),
     "fv_head_flow_prepare_prefix": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fv_head_flow_sample_prefix": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _i, _vp, _vp, _vp, _vp]),
+    "fv_head_set_flow_samples": (_i, [_vp, _i, _i, C.POINTER(_f)]),
+    "fv_head_flow_sample_multi": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fv_ensemble_create": (_i, [_vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "fv_ensemble_destroy": (_i, [_vp, _vp]),
     "fv_ensemble_reset": (_i, [_vp, _vp, _i, _vp]),
@@ -234,6 +238,7 @@ OPS_SIGNATURES = {
     "fv_op_head_loss_backward_draws": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "fv_op_flow_vjp": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "fv_op_flow_vjp_prefix": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "fv_op_flow_select": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fv_op_head_saved_cat_offset": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }

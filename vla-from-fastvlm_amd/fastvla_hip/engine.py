@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from .arch import ModelConfig
+from .select import check_flow_samples
 
 HEAD_KEYS = (
     "state_projection.0.weight", "state_projection.0.bias", "state_projection.1.weight", "state_projection.1.bias",
@@ -184,6 +185,7 @@ class FastVLAEngine:
         self.head_flow_draws = 1                                  # set_head_flow_draws: noise draws per observation in the training forms
         self.head_flow_prefix: Optional[dict] = None              # set_head_flow_prefix: None = no action-prefix conditioning
         self.head_flow_solver = "euler"                           # set_head_flow_solver: the integrator of all three samplers
+        self.head_flow_samples: Optional[dict] = None             # set_head_flow_samples: None = one sample per observation
         self.head_flow_solver_rows = False                        # True once a higher-order solver was named: the workspace plan holds its two rows
         self.loaded = False
 
@@ -591,6 +593,7 @@ class FastVLAEngine:
             self.head_flow_draws = 1
             self.head_flow_prefix = None
             self.head_flow_solver = "euler"
+            self.head_flow_samples = None
         else:
             if time_dist not in _lib.FLOW_TIME_DISTS:
                 raise ValueError(f"flow time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {time_dist!r}")
@@ -776,6 +779,66 @@ class FastVLAEngine:
                                                        offset, prev.data_ptr(), int(shift), delays.data_ptr(), actions.data_ptr(), chunk_out.data_ptr(), _stream()),
                    "fv_head_flow_sample_prefix", self.h)
         return actions, chunk_out
+
+    def set_head_flow_samples(self, max_samples: int = 1, step_weights=None) -> None:
+        """Several samples per observation (fv_head_set_flow_samples): head_flow_sample_multi may then draw up to max_samples (1 .. 16; 1 = off) candidates
+        in one call.  step_weights: K host floats >= 0, K a divisor of action_dim, the per-step weights of the coherence score
+        (fastvla_hip.select.coherence_weights); None: "coherent" is refused.  The first call that names more than one sample must come before the first
+        workspace is bound (the library answers FV_ERR_STATE afterwards: the sampler's rows grow); later calls with the same count may change the weights."""
+        max_samples = check_flow_samples(max_samples)
+        w = None if step_weights is None else [float(x) for x in step_weights]
+        arr = None if w is None else (C.c_float * len(w))(*w)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.fv_head_set_flow_samples(self.h, max_samples, len(w) if w else 0, arr), "fv_head_set_flow_samples", self.h)
+        self.head_flow_samples = dict(max_samples=max_samples, weights=w)
+
+    def head_flow_sample_multi(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, *, samples: int = 1, select: str = "first",
+                               prev: Optional[torch.Tensor] = None, shift: int = 0, row_mask: Optional[torch.Tensor] = None,
+                               delays: Optional[torch.Tensor] = None, steps: int = 10, noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0,
+                               chunk_out: Optional[torch.Tensor] = None, extras: bool = True) -> Dict[str, torch.Tensor]:
+        """`samples` candidates per observation in one call, one of them chosen on the device (fv_head_flow_sample_multi).  Candidate s is head_flow_sample
+        (with delays: head_flow_sample_prefix) at offset + (s << 56); noise is (samples * B, da), sample-major.  select: "first" | "medoid" | "coherent"
+        (prev (B, da) normalised, read `shift` steps ahead; row_mask (B) int32, rows with 0 take the medoid).
+        -> dict: actions (B, da), chunk (B, da) normalised (written into chunk_out when one is handed in) and, with extras, candidates (samples * B, da)
+        normalised and sample-major, choice (B) int32, scores (B, samples), spread (B, da).  Everything stays on the device."""
+        if select not in _lib.FLOW_SELECTS:
+            raise ValueError(f"select must be one of {list(_lib.FLOW_SELECTS)}, got {select!r}")
+        S = check_flow_samples(samples)
+        B, da = pooled.shape[0], self.head_dims["da"]
+        states = states.to(device=self.device, dtype=torch.float32).contiguous()
+        pooled = pooled.contiguous()
+        if states.shape != (B, self.head_dims["ds"]):
+            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        if prev is not None:
+            prev = prev.to(device=self.device, dtype=torch.float32).contiguous()
+            if prev.numel() != B * da:
+                raise ValueError(f"prev must hold (B, {da}) elements, got {tuple(prev.shape)}")
+        if delays is not None:
+            delays = torch.as_tensor(delays).to(device=self.device, dtype=torch.int32).contiguous()
+            if delays.numel() != B:
+                raise ValueError(f"delays must hold B = {B} elements, got {tuple(delays.shape)}")
+        if row_mask is not None:
+            row_mask = row_mask.to(device=self.device, dtype=torch.int32).contiguous()
+            if row_mask.numel() != B:
+                raise ValueError(f"row_mask must hold B = {B} elements, got {tuple(row_mask.shape)}")
+        if noise is not None:
+            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
+            if noise.numel() != S * B * da:
+                raise ValueError(f"noise must hold (samples * B, {da}) = ({S * B}, {da}) elements, got {tuple(noise.shape)}")
+        if chunk_out is None:
+            chunk_out = torch.empty(B, da, dtype=torch.float32, device=self.device)
+        elif chunk_out.dtype != torch.float32 or not chunk_out.is_contiguous() or chunk_out.numel() != B * da or chunk_out.device != pooled.device:
+            raise ValueError(f"chunk_out must be a contiguous float32 (B, {da}) tensor on {self.device}")
+        self.ensure_workspace(B, 1, False)
+        out = dict(actions=torch.empty(B, da, dtype=torch.float32, device=self.device), chunk=chunk_out)
+        if extras:
+            out.update(candidates=torch.empty(S * B, da, dtype=torch.float32, device=self.device), choice=torch.empty(B, dtype=torch.int32, device=self.device),
+                       scores=torch.empty(B, S, dtype=torch.float32, device=self.device), spread=torch.empty(B, da, dtype=torch.float32, device=self.device))
+        _lib.check(self.lib.fv_head_flow_sample_multi(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed, offset, S,
+                                                      _lib.FLOW_SELECTS[select], _ptr(prev), int(shift), _ptr(row_mask), _ptr(delays), out["actions"].data_ptr(),
+                                                      chunk_out.data_ptr(), _ptr(out.get("candidates")), _ptr(out.get("choice")), _ptr(out.get("scores")),
+                                                      _ptr(out.get("spread")), _stream()), "fv_head_flow_sample_multi", self.h)
+        return out
 
     def head_saved(self, B: int) -> torch.Tensor:
         n = C.c_size_t()

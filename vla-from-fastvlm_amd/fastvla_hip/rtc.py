@@ -108,3 +108,19 @@ class RealTimeChunker:
         self.prev, self._next = self._next, self.prev
         self.has_prev.fill_(1)
         return actions
+
+    def sample_multi(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, *, samples: int, select: str, shift: int, steps: int,
+                     delay: Optional[int] = None, noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0, prev: Optional[torch.Tensor] = None) -> dict:
+        """-> head_flow_sample_multi's dict: `samples` candidates per row in one call, one of them chosen (fv_head_flow_sample_multi), and the CHOSEN chunk
+        kept as the next call's previous one.  select "coherent" scores every candidate against the kept chunk read `shift` steps ahead; a row without one
+        (has_prev 0) takes the medoid.  delay (None: the plain sampler): the candidates come from the prefix sampler, as in sample_prefix()"""
+        if pooled.shape[0] != self.n_env:
+            raise ValueError(f"this chunker holds {self.n_env} environments, the batch has {pooled.shape[0]}")
+        explicit = prev is not None
+        delays = None if delay is None else (torch.full_like(self.has_prev, int(delay)) if explicit else self.has_prev * int(delay))
+        out = self._engine.head_flow_sample_multi(flat_params, pooled, states, samples=samples, select=select, prev=prev if explicit else self.prev, shift=shift,
+                                                  row_mask=None if explicit else self.has_prev, delays=delays, steps=steps, noise=noise, seed=seed, offset=offset,
+                                                  chunk_out=self._next)
+        self.prev, self._next = self._next, self.prev
+        self.has_prev.fill_(1)
+        return out

@@ -104,7 +104,7 @@ class _FlowLossFunction(torch.autograd.Function):
 class FastVLMWithExpert(nn.Module):
     def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0, flow: Optional[dict] = None,
                  flow_steps: int = 10, flow_seed: Optional[int] = None, flow_noise_draws: int = 1, flow_prefix: Optional[dict] = None,
-                 flow_solver: str = "euler") -> None:
+                 flow_solver: str = "euler", flow_samples: int = 1, flow_select: Optional[str] = None, flow_coherence_decay: float = 0.5) -> None:
         """chunk_size = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
         `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library.
         flow = FastVLAEngine.set_head_flow's keyword arguments: the flow-matching head -- fusion.0 reads K * A + time_dim more columns (x_t and phi(t)),
@@ -113,8 +113,17 @@ class FastVLMWithExpert(nn.Module):
         noised -- draw s of a call at offset o is the single draw of offset o + (s << 56); the velocity handed out is draw 0's.
         flow_prefix = fastvla_hip.prefix.check_prefix_config's result (flow head, K > 1): action-prefix conditioning -- fusion.0 reads K mask columns behind
         phi(t), training gives the first d <= max_delay steps of a chunk to the network clean and keeps them out of the loss, rtc_sample pins them.
-        flow_solver: "euler" | "midpoint" | "heun" | "rk4", the integrator of every sampling route (flow_steps are steps of it); a property of the run."""
+        flow_solver: "euler" | "midpoint" | "heun" | "rk4", the integrator of every sampling route (flow_steps are steps of it); a property of the run.
+        flow_samples = S (1 .. 16) with flow_select "first" | "medoid" | "coherent" (fastvla_hip/select.py): every sampling route draws S candidates per
+        observation in one call and returns the chosen one; "coherent" weights step k of the overlap with the previous chunk flow_coherence_decay**k.
+        A property of the run; S = 1 calls nothing new."""
         super().__init__()
+        from fastvla_hip.select import check_flow_select, coherence_weights
+        self.flow_samples, self.flow_select = check_flow_select(flow_samples, flow_select, action_head="flow" if flow is not None else "regression",
+                                                                chunk_size=chunk_size)
+        self.flow_samples_now = self.flow_samples      # select_action_chunk(num_samples=) lowers it for one call
+        self.last_candidates = self.last_choice = self.last_sample_spread = None      # device tensors of the last multi-sample call
+        self._coherence_weights = coherence_weights(int(chunk_size), flow_coherence_decay) if self.flow_select == "coherent" else None
         from fastvla_hip.engine import check_flow_draws, check_head_loss
         self.flow_noise_draws = check_flow_draws(flow_noise_draws)
         if self.flow_noise_draws > 1 and flow is None:
@@ -141,6 +150,7 @@ class FastVLMWithExpert(nn.Module):
             raise ValueError(f"flow_solver={self._flow_solver!r} needs action_head='flow' (the regression head integrates nothing)")
         self._flow_solver_rows = self._flow_solver != "euler"      # a policy built with a higher-order solver reserved their rows and may switch among all four
         self.backbone.configure_head_flow_solver(self._flow_solver)
+        self.backbone.configure_head_flow_samples(dict(max_samples=self.flow_samples, step_weights=self._coherence_weights) if self.flow_samples > 1 else None)
         self.rtc: Optional[dict] = None      # configure_rtc: real-time chunking of the flow sampler, a property of the run
         self._chunker = self._rtc_key = None
         extra = self.head_width + int(self.flow["time_dim"]) + (self.chunk_size if self.flow_prefix else 0) if self.flow else 0
@@ -364,6 +374,8 @@ class FastVLMWithExpert(nn.Module):
             if differentiable:
                 raise RuntimeError("the flow head samples its actions (Euler steps of the velocity field) and sampling is not differentiated: call predict / "
                                    "forward under torch.no_grad(), and train through compute_loss / forward(batch) / the train step")
+            if self.flow_samples > 1:      # (a call without a previous chunk to continue: "coherent" rows take the medoid)
+                return self.sample_multi(pooled, states)
             seed, offset = self.flow_sample_draw()
             return self._shape_actions(self._engine().head_flow_sample(self._flat, pooled, states, steps=self.flow_steps, seed=seed, offset=offset))
         actions = _HeadFunction.apply(self, pooled, states, self.training, differentiable, *params)
@@ -377,12 +389,36 @@ class FastVLMWithExpert(nn.Module):
             actions = actions * std + mean
         return self._shape_actions(actions)
 
+    # ------------------------------------------------------------------ several samples per observation, one chosen on the device
+    def sample_multi(self, pooled: torch.Tensor, states: torch.Tensor, *, shift: Optional[int] = None, delay: Optional[int] = None,
+                     prev: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> (B, K, A): flow_samples_now candidates per row in ONE sampler call (fv_head_flow_sample_multi), the one flow_select names returned; the
+        candidates (B, S, K, A), the choice (B) and the spread (B, K, A) stay on the device in last_candidates / last_choice / last_sample_spread.
+        shift (None: a call on its own): the plan continues the chunker's kept chunk, read `shift` steps ahead -- "coherent" scores against it (rows without
+        one take the medoid) and the chosen chunk is kept; delay: the candidates come from the prefix sampler and pin their first steps to it."""
+        self.materialize(pooled.device)
+        states = states.to(pooled.device, torch.float32)
+        if states.ndim != 2 or states.shape[1] != self.config.state_dim:
+            raise ValueError(f"states must be (B,{self.config.state_dim}), got {tuple(states.shape)}")
+        B, S, K, A = pooled.shape[0], int(self.flow_samples_now), self.chunk_size, self.config.action_dim
+        seed, offset = self.flow_sample_draw()
+        kw = dict(samples=S, steps=self.flow_steps, seed=seed, offset=offset)
+        if shift is None:
+            out = self._engine().head_flow_sample_multi(self._flat, pooled, states, select="medoid" if self.flow_select == "coherent" else self.flow_select, **kw)
+        else:
+            out = self._rtc_chunker(B).sample_multi(self._flat, pooled, states, select=self.flow_select, shift=int(shift), delay=delay, prev=prev, **kw)
+        self.last_candidates = out["candidates"].view(S, B, K, A).transpose(0, 1)
+        self.last_choice, self.last_sample_spread = out["choice"], out["spread"].view(B, K, A)
+        return self._shape_actions(out["actions"])
+
     # ------------------------------------------------------------------ real-time chunking (flow head): the guided sampler
     def configure_rtc(self, rtc: Optional[dict]) -> None:
         """rtc = {"schedule", "max_guidance_weight", "execution_horizon"} (modeling_fastvla.resolve_rtc_options) or None.  A property of the run: no checkpoint
         records it.  The weights of (inference_delay 0, execution_horizon) are handed to the backbone so that the engine is configured BEFORE its first
         workspace exists; another delay or horizon re-uploads them at the call that asks for it."""
         from fastvla_hip.rtc import prefix_weights
+        if rtc is not None and rtc.get("method") != "prefix" and getattr(self, "flow_samples", 1) > 1:
+            raise ValueError(f"flow_samples={self.flow_samples} with rtc_method='guidance': guided sampling with candidates is not offered")
         self.rtc = None if rtc is None else dict(rtc)
         self._chunker = None
         if rtc is not None and rtc.get("method") == "prefix":      # the prefix sampler: no guidance, no weights, nothing to configure on the engine
@@ -404,7 +440,7 @@ class FastVLMWithExpert(nn.Module):
         if ck is None or ck._engine is not eng:      # (the first call after construction, or the engine was rebuilt underneath)
             fresh = ck is not None      # (a rebuilt engine holds the weights the backbone configured it with: delay 0, the policy's horizon)
             ck = self._chunker = RealTimeChunker(eng, n_env)
-            if fresh and self.rtc.get("method") != "prefix":
+            if fresh and self.rtc is not None and self.rtc.get("method") != "prefix":
                 self._rtc_key = (0, int(self.rtc["execution_horizon"]))
         return ck
 
@@ -444,6 +480,8 @@ class FastVLMWithExpert(nn.Module):
                 prev = prev.to(pooled.device, torch.float32).reshape(pooled.shape[0], -1)
                 if prev.shape[1] != self.head_width:
                     raise ValueError(f"prev_chunk must hold (B, {K}, {self.config.action_dim}) elements, got {tuple(prev.shape)}")
+            if self.flow_samples > 1:
+                return self.sample_multi(pooled, states, shift=int(shift), delay=d, prev=prev)
             seed, offset = self.flow_sample_draw()
             return self._shape_actions(ck.sample_prefix(self._flat, pooled, states, shift=int(shift), delay=d, steps=self.flow_steps, seed=seed, offset=offset,
                                                         prev=prev))

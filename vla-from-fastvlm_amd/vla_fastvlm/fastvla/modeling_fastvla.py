@@ -122,6 +122,36 @@ def resolve_flow_solver(flow_solver=None, *, action_head: str) -> str:
         raise ValueError(f"FASTVLA_FLOW_SOLVER must be 'euler', 'midpoint', 'heun' or 'rk4'. Got FASTVLA_FLOW_SOLVER={raw!r}, action_head={action_head!r}.") from None
 
 
+def resolve_flow_samples(flow_samples=None, flow_select=None, flow_coherence_decay=None, *, action_head: str, chunk_size: int, rtc_method: Optional[str] = None) -> Dict:
+    """-> {"samples", "select", "decay"}: several samples per observation at inference (fastvla_hip/select.py).  Explicit arguments, else the FASTVLA_FLOW_SAMPLES /
+    FASTVLA_FLOW_SELECT / FASTVLA_FLOW_COHERENCE_DECAY twins -- read for a flow head only --, else (1, None, 0.5).  ValueError naming both settings, before any
+    engine exists: a regression head, samples outside 1 .. 16, a select name with one sample, "coherent" with chunk_size = 1, rtc_method="guidance" with
+    several samples."""
+    from fastvla_hip.select import check_flow_select, coherence_weights
+    flow = action_head == "flow"
+
+    def pick(arg, env, cast, default):
+        if arg is not None:
+            return arg
+        raw = (os.environ.get(env) or "").strip() if flow else ""
+        if not raw:
+            return default
+        try:
+            return cast(raw)
+        except ValueError:
+            raise ValueError(f"{env} must be {'an integer' if cast is int else 'a number'}, got {env}={raw!r} (action_head={action_head!r})") from None
+
+    samples = pick(flow_samples, "FASTVLA_FLOW_SAMPLES", int, None)
+    select = pick(flow_select, "FASTVLA_FLOW_SELECT", lambda r: r.lower(), None)
+    decay = pick(flow_coherence_decay, "FASTVLA_FLOW_COHERENCE_DECAY", float, None)
+    if decay is not None and not flow:
+        raise ValueError(f"flow_coherence_decay={decay!r} / flow_samples={samples!r} need action_head='flow', got action_head={action_head!r}")
+    samples, select = check_flow_select(samples, select, action_head=action_head, chunk_size=chunk_size, rtc_method=rtc_method)
+    decay = 0.5 if decay is None else decay
+    coherence_weights(max(int(chunk_size), 1), decay)      # (checks the decay)
+    return {"samples": samples, "select": select, "decay": float(decay)}
+
+
 def resolve_flow_noise_draws(flow_noise_draws=None, *, action_head: str) -> int:
     """-> S, the noise draws per observation of a flow head's training and loss evaluations: the explicit argument, else FASTVLA_FLOW_NOISE_DRAWS, else 1.  The
     twin is read and checked for a flow head only, like the other FASTVLA_FLOW_* twins.  ValueError, naming both settings and before any engine exists, for
@@ -250,7 +280,8 @@ class FastVLAPolicy(nn.Module, EmaMixin):
                  rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None,
                  flow_noise_draws: Optional[int] = None, flow_prefix_max_delay: Optional[int] = None, flow_prefix_delay_dist: Optional[str] = None,
                  flow_prefix_delay_rate: Optional[float] = None, rtc_method: Optional[str] = None, rtc_prefix_steps: Optional[int] = None,
-                 flow_solver: Optional[str] = None) -> None:
+                 flow_solver: Optional[str] = None, flow_samples: Optional[int] = None, flow_select: Optional[str] = None,
+                 flow_coherence_decay: Optional[float] = None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
@@ -304,7 +335,20 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         (1, 2, 2, 4) network evaluations, and at an equal number of evaluations a higher-order solver ends one to two orders closer to the exact flow
         (DESIGN.md section 7); action_error_per_dim(batch) is the action-space metric to choose a solver and a step count with.  policy.flow_solver may be
         changed at any time on a policy BUILT with a higher-order solver (the workspace holds their two rows); a policy built with "euler" raises ValueError.
-        A property of the run: hip_extras.json records it only when it is not Euler.  ValueError with a regression head."""
+        A property of the run: hip_extras.json records it only when it is not Euler.  ValueError with a regression head.
+
+        flow_samples=S (flow head, 1 .. 16, default 1; FASTVLA_FLOW_SAMPLES) with flow_select="medoid" (the default with S > 1) | "coherent" | "first"
+        (FASTVLA_FLOW_SELECT): predict / select_action / select_action_chunk draw S candidate chunks per observation in ONE sampler call
+        (fv_head_flow_sample_multi; candidate s is the single sample at offset + (s << 56), so "first" serves the bits of a policy without samples) and
+        return one of them, chosen on the device: the medoid (the candidate the others agree with), or the one that best continues the chunk planned last
+        over the steps the two share, step k weighted flow_coherence_decay**k (default 0.5; FASTVLA_FLOW_COHERENCE_DECAY; the backward-coherence criterion of
+        Bidirectional Decoding, Liu et al. 2024).  "coherent" keeps the chosen chunk: select_action scores a re-plan against it read `shift` = the actions
+        served since steps ahead, the first plan after reset() takes the medoid, and predict -- a call on its own -- takes the medoid too; it works without
+        rtc and with rtc_method="prefix" (every candidate then pins the same steps).  The candidates never average: between two modes the mean is a chunk the
+        policy did not learn.  policy.last_candidates (B, S, K, A, normalised), last_choice (B) and last_sample_spread (B, K, A; the candidates' standard
+        deviation, an uncertainty signal) stay on the device.  The queue, n_action_steps, temporal ensembling, the solver and flow_steps work on the chosen
+        chunk; action_error_per_dim stays single-sample.  A property of the run: no checkpoint or hip_extras.json key.  ValueError, before any engine exists,
+        for a regression head, S outside 1 .. 16, a select name with S = 1, "coherent" with chunk_size = 1, rtc_method="guidance" with S > 1."""
         super().__init__()
         self.config = config or FastVLAConfig()
         opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
@@ -322,8 +366,12 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         ropts = resolve_rtc_options(rtc, rtc_schedule, rtc_max_guidance_weight, rtc_execution_horizon, action_head=self.action_head,      # (before any engine exists)
                                     chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"],
                                     rtc_method=rtc_method, rtc_prefix_steps=rtc_prefix_steps, prefix=popts)
+        sopts = resolve_flow_samples(flow_samples, flow_select, flow_coherence_decay, action_head=self.action_head, chunk_size=opts["chunk_size"],      # (likewise)
+                                     rtc_method=None if ropts is None else ropts.get("method", "guidance"))
+        self.flow_samples, self.flow_select = sopts["samples"], sopts["select"]
         self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"],
-                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver)
+                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver,
+                                       flow_samples=sopts["samples"], flow_select=sopts["select"], flow_coherence_decay=sopts["decay"])
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts
@@ -508,14 +556,29 @@ class FastVLAPolicy(nn.Module, EmaMixin):
 
     @torch.inference_mode()
     def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device, prev_chunk: Optional[torch.Tensor] = None,
-                            inference_delay: Optional[int] = None) -> torch.Tensor:
+                            inference_delay: Optional[int] = None, num_samples: Optional[int] = None) -> torch.Tensor:
         """-> (K, A): the whole chunk the head predicts for one observation (K = chunk_size; (1, A) without chunks).
         rtc=True: prev_chunk (K', A), K' <= K, in NORMALISED space -- the not-yet-executed rows of the previous chunk, policy.last_chunk_normalised[executed:] --
         guides the sample (row k of the new chunk towards row k of prev_chunk), with the first inference_delay steps as a hard prefix: the explicit form for
         callers that plan while the previous chunk is still being executed.  Without prev_chunk the sample is guided by the chunk the policy planned last
         (none after reset(): unguided), read from its start.  inference_delay None: 0 under rtc_method="guidance"; under rtc_method="prefix" the policy's
-        rtc_prefix_steps, as in select_action (rows without a previous chunk pin nothing whatever the delay)."""
+        rtc_prefix_steps, as in select_action (rows without a previous chunk pin nothing whatever the delay).
+        num_samples (flow_samples > 1; 1 .. flow_samples): the candidates of THIS call; the chosen chunk is returned.  flow_select="coherent" scores them
+        against the chunk planned last, read from its start (none after reset(): the medoid), and keeps the chosen one."""
+        if num_samples is not None:
+            from fastvla_hip.select import check_flow_samples
+            if check_flow_samples(num_samples) > self.flow_samples:
+                raise ValueError(f"num_samples={num_samples} exceeds the flow_samples={self.flow_samples} the policy was constructed with (the sampler's rows are sized for it)")
+            self.model.flow_samples_now = int(num_samples)
+            try:
+                return self.select_action_chunk(image, state, task, device, prev_chunk=prev_chunk, inference_delay=inference_delay)
+            finally:
+                self.model.flow_samples_now = self.flow_samples
         self.eval()
+        if self.rtc is None and self.flow_select == "coherent":
+            if prev_chunk is not None or inference_delay not in (None, 0):
+                raise ValueError(f"prev_chunk / inference_delay need rtc=True. Got inference_delay={inference_delay}, rtc={self.rtc is not None}.")
+            return self._coherent_plan(image, state, task, device, shift=0)
         if self.rtc is None:
             if prev_chunk is not None or inference_delay not in (None, 0):
                 raise ValueError(f"prev_chunk / inference_delay need rtc=True. Got inference_delay={inference_delay}, rtc={self.rtc is not None}.")
@@ -542,6 +605,31 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         self._rtc_served = 0
         return chunk.reshape(self.model.chunk_size, self.config.action_dim)
 
+    def _coherent_plan(self, image, state, task, device, *, shift: int) -> torch.Tensor:
+        """flow_select="coherent" without rtc: flow_samples candidates, the one that best continues the chunk planned last (read `shift` steps ahead) chosen"""
+        images = self.processor.prepare_images(image.unsqueeze(0).to(device), device)
+        states = self.processor.prepare_states(state.unsqueeze(0).to(device), device)
+        tasks = self.processor.prepare_tasks(task, batch_size=1)
+        pooled = self.model.features(images, tasks, device=device)
+        chunk = self.model.sample_multi(pooled, states, shift=shift)
+        self._rtc_served = 0
+        return chunk.reshape(self.model.chunk_size, self.config.action_dim)
+
+    @property
+    def last_candidates(self) -> Optional[torch.Tensor]:
+        """flow_samples > 1: (B, S, K, A), the candidates of the last sampling call in normalised space, on the device; None before the first"""
+        return self.model.last_candidates
+
+    @property
+    def last_choice(self) -> Optional[torch.Tensor]:
+        """flow_samples > 1: (B) int32, the index of the candidate the last sampling call chose, on the device"""
+        return self.model.last_choice
+
+    @property
+    def last_sample_spread(self) -> Optional[torch.Tensor]:
+        """flow_samples > 1: (B, K, A), the standard deviation of the last call's candidates per element (normalised space), on the device"""
+        return self.model.last_sample_spread
+
     @property
     def last_chunk_normalised(self) -> Optional[torch.Tensor]:
         """rtc=True: (K, A) copy of the last planned chunk in normalised space (before the folded dataset statistics), None before the first plan"""
@@ -560,6 +648,12 @@ class FastVLAPolicy(nn.Module, EmaMixin):
             if not self._action_queue:   # the re-plan is guided by the last chunk, read from the first step that has not been served yet
                 self.eval()
                 self._action_queue.extend(self._rtc_plan(image, state, task, device, shift=self._rtc_served)[: self.n_action_steps].unbind(0))
+            self._rtc_served += 1
+            return self._action_queue.popleft()
+        if self.flow_select == "coherent":      # (without rtc: the re-plan is the candidate that best continues the last chunk from the first step not served yet)
+            if not self._action_queue:
+                self.eval()
+                self._action_queue.extend(self._coherent_plan(image, state, task, device, shift=min(self._rtc_served, self.model.chunk_size))[: self.n_action_steps].unbind(0))
             self._rtc_served += 1
             return self._action_queue.popleft()
         if not self._action_queue:       # (n_action_steps = 1: a prediction on every call, row 0 served)

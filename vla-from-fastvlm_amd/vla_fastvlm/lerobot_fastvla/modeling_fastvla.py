@@ -20,7 +20,12 @@ flow_prefix_delay_rate=) or the FASTVLA_FLOW_PREFIX_* twins train the head with 
 
 Higher-order integrators (no config field): FastVLAPolicy(config, action_head="flow", flow_solver="midpoint" | "heun" | "rk4") or FASTVLA_FLOW_SOLVER: every
 sampling route -- predict_action_chunk, select_action, rtc with either method -- integrates with it, flow_steps being steps of the chosen solver;
-policy.flow_solver switches among all four on a policy built with a higher-order one."""
+policy.flow_solver switches among all four on a policy built with a higher-order one.
+
+Several samples per observation (no config field): FastVLAPolicy(config, action_head="flow", flow_samples=S, flow_select="medoid" | "coherent" | "first",
+flow_coherence_decay=) or the FASTVLA_FLOW_SAMPLES / FASTVLA_FLOW_SELECT / FASTVLA_FLOW_COHERENCE_DECAY twins: predict_action_chunk(batch, num_samples=) and
+select_action draw S candidates per environment in one sampler call and return the one chosen on the device; last_candidates, last_choice and
+last_sample_spread stay on the device."""
 from __future__ import annotations
 
 from collections import deque
@@ -49,8 +54,8 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        from ..fastvla.modeling_fastvla import (resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_flow_solver, resolve_prefix_options,
-                                                resolve_rtc_options)
+        from ..fastvla.modeling_fastvla import (resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_flow_samples, resolve_flow_solver,
+                                                resolve_prefix_options, resolve_rtc_options)
         opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
                                      temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
                                      action_step_weights=kwargs.get("action_step_weights"))
@@ -73,10 +78,16 @@ class FastVLAPolicy(PreTrainedPolicy):
                                     action_head=self.action_head, chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"],
                                     temporal_ensemble_coeff=opts["temporal_ensemble_coeff"], rtc_method=kwargs.get("rtc_method"),
                                     rtc_prefix_steps=kwargs.get("rtc_prefix_steps"), prefix=popts)
+        # flow_samples= / flow_select= / flow_coherence_decay= (FASTVLA_FLOW_SAMPLES / _SELECT / _COHERENCE_DECAY; no config field): S candidates per environment
+        # in one sampler call, one chosen on the device; a property of the run
+        sopts = resolve_flow_samples(kwargs.get("flow_samples"), kwargs.get("flow_select"), kwargs.get("flow_coherence_decay"), action_head=self.action_head,
+                                     chunk_size=opts["chunk_size"], rtc_method=None if ropts is None else ropts.get("method", "guidance"))
+        self.flow_samples, self.flow_select = sopts["samples"], sopts["select"]
         self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
         self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
                                        action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"], flow_steps=fopts["steps"],
-                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver)
+                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver,
+                                       flow_samples=sopts["samples"], flow_select=sopts["select"], flow_coherence_decay=sopts["decay"])
         if opts["dim_weights"] is not None or opts["step_weights"] is not None:
             self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
         self.rtc = ropts
@@ -202,13 +213,51 @@ class FastVLAPolicy(PreTrainedPolicy):
         """rtc: (B, K, A) copy of the chunks planned last, in normalised space; None before the first plan"""
         return self.model.last_chunk_normalised
 
+    @property
+    def last_candidates(self):
+        """flow_samples > 1: (B, S, K, A), the candidates of the last sampling call in normalised space, on the device; None before the first"""
+        return self.model.last_candidates
+
+    @property
+    def last_choice(self):
+        """flow_samples > 1: (B) int32, the candidate the last sampling call chose per environment, on the device"""
+        return self.model.last_choice
+
+    @property
+    def last_sample_spread(self):
+        """flow_samples > 1: (B, K, A), the standard deviation of the last call's candidates per element (normalised space), on the device"""
+        return self.model.last_sample_spread
+
+    def _coherent_plan(self, batch, *, shift: int) -> Tensor:
+        """flow_select="coherent" without rtc: the candidate that best continues the chunks planned last (read `shift` steps ahead), for all B environments"""
+        images, states, tasks = self._prepare_inputs(batch)
+        pooled = self.model.features(images, tasks, device=images.device)
+        chunk = self.model.sample_multi(pooled, states, shift=shift)
+        self._rtc_served = 0
+        return chunk if chunk.ndim == 3 else chunk.unsqueeze(1)
+
     @torch.no_grad()
-    def predict_action_chunk(self, batch: dict[str, Tensor], inference_delay=None, prev_chunk_left_over=None, execution_horizon=None, **kwargs) -> Tensor:
+    def predict_action_chunk(self, batch: dict[str, Tensor], inference_delay=None, prev_chunk_left_over=None, execution_horizon=None, num_samples=None,
+                             **kwargs) -> Tensor:
         """rtc (LeRobot's keyword set, for all B environments in one call): prev_chunk_left_over (B, K', A), K' <= K, the not-yet-executed rows of the
         previous chunk in normalised space (last_chunk_normalised[:, executed:]); inference_delay d: its first d steps are a hard prefix; execution_horizon:
         the last steps left free (default: the policy's).  Without prev_chunk_left_over the plan is guided by the chunk planned last, from its start
-        (none after reset(): unguided)."""
+        (none after reset(): unguided).
+        num_samples (flow_samples > 1; 1 .. flow_samples): the candidates of THIS call; the chosen chunk of every environment is returned."""
+        if num_samples is not None:
+            from fastvla_hip.select import check_flow_samples
+            if check_flow_samples(num_samples) > self.flow_samples:
+                raise ValueError(f"num_samples={num_samples} exceeds the flow_samples={self.flow_samples} the policy was constructed with (the sampler's rows are sized for it)")
+            self.model.flow_samples_now = int(num_samples)
+            try:
+                return self.predict_action_chunk(batch, inference_delay=inference_delay, prev_chunk_left_over=prev_chunk_left_over, execution_horizon=execution_horizon)
+            finally:
+                self.model.flow_samples_now = self.flow_samples
         self.eval()
+        if self.rtc is None and self.flow_select == "coherent":
+            if inference_delay or prev_chunk_left_over is not None or execution_horizon is not None:
+                raise ValueError(f"inference_delay / prev_chunk_left_over / execution_horizon need rtc=True. Got inference_delay={inference_delay}, rtc=False.")
+            return self._coherent_plan(batch, shift=0)
         if self.rtc is None:
             if inference_delay or prev_chunk_left_over is not None or execution_horizon is not None:
                 raise ValueError(f"inference_delay / prev_chunk_left_over / execution_horizon need rtc=True. Got inference_delay={inference_delay}, rtc=False.")
@@ -249,6 +298,11 @@ class FastVLAPolicy(PreTrainedPolicy):
         if self.rtc is not None:
             if not self._action_queue:      # guided by the chunks planned last, read from the first step that has not been served yet
                 self._action_queue.extend(self._rtc_plan(batch, shift=self._rtc_served)[:, : self.config.n_action_steps].transpose(0, 1))
+            self._rtc_served += 1
+            return self._action_queue.popleft()
+        if self.flow_select == "coherent":      # (without rtc: the re-plan best continues the chunks planned last from the first step not served yet)
+            if not self._action_queue:
+                self._action_queue.extend(self._coherent_plan(batch, shift=min(self._rtc_served, self.model.chunk_size))[:, : self.config.n_action_steps].transpose(0, 1))
             self._rtc_served += 1
             return self._action_queue.popleft()
         if not self._action_queue:

@@ -191,6 +191,7 @@ class FastVLMBackbone(nn.Module):
         self._head_flow_guidance: Optional[dict] = None         # configure_head_flow_guidance: FastVLAEngine.set_head_flow_guidance's arguments, None = off
         self._head_flow_prefix: Optional[dict] = None           # configure_head_flow_prefix: {"chunk", "max_delay", "thresholds", "dist", "rate"}, None = off
         self._head_flow_solver = "euler"                        # configure_head_flow_solver: FastVLAEngine.set_head_flow_solver's argument
+        self._head_flow_samples: Optional[dict] = None          # configure_head_flow_samples: FastVLAEngine.set_head_flow_samples' arguments, None = one sample
         self._head_flow_solver_rows = False                     # True once a higher-order solver was configured: an engine is built with its two rows reserved
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
@@ -302,6 +303,13 @@ class FastVLMBackbone(nn.Module):
         self._head_flow_solver = name
         self._head_flow_solver_rows = self._head_flow_solver_rows or name != "euler"
 
+    def configure_head_flow_samples(self, samples: Optional[dict]) -> None:
+        """Several samples per observation (FastVLAEngine.set_head_flow_samples' keyword arguments; None = one).  The sampler's rows in the workspace grow
+        with max_samples, so it is fixed before the engine is built."""
+        if self._engine is not None and samples != self._head_flow_samples:
+            raise RuntimeError("configure_head_flow_samples: the engine is already built (the sampler's rows in the workspace depend on the number of samples)")
+        self._head_flow_samples = None if samples is None else dict(samples)
+
     def configure_head_flow_guidance(self, guidance: Optional[dict]) -> None:
         """Guidance of the flow sampler (FastVLAEngine.set_head_flow_guidance's keyword arguments; None = off).  Kept for the engine's construction, where it
         is applied before any workspace is bound; an engine that already exists is told at once (the library refuses a FIRST configuration then)."""
@@ -408,6 +416,8 @@ class FastVLMBackbone(nn.Module):
                     eng.set_head_flow_draws(self._head_flow_draws)
                 if getattr(self, "_head_flow_guidance", None) is not None:
                     eng.set_head_flow_guidance(**self._head_flow_guidance)
+                if getattr(self, "_head_flow_samples", None) is not None:
+                    eng.set_head_flow_samples(**self._head_flow_samples)
                 if getattr(self, "_head_flow_solver_rows", False):      # (a policy switched back to Euler keeps its rows: it may switch again)
                     eng.set_head_flow_solver(self._head_flow_solver if self._head_flow_solver != "euler" else "midpoint")
                     eng.set_head_flow_solver(self._head_flow_solver)
