@@ -97,7 +97,7 @@ def test_state_dict_shapes_with_four_steps():
     grown = {k for k in sb if sb[k].shape != sp[k].shape}
     assert grown == {"model.action_head.weight", "model.action_head.bias"}
     assert sp["model.action_head.weight"].shape == (4 * A, fus) and sp["model.action_head.bias"].shape == (4 * A,)
-    assert pol.config == base.config and pol.model.backbone._head_dims["action_dim"] == 4 * A
+    assert pol.config == base.config and pol.model.backbone.head_spec.dims["action_dim"] == 4 * A
     # folded statistics stay A long in the state dict and are tiled over the steps only on their way to the kernels
     stats = dict(state_mean=torch.zeros(pol.config.state_dim), state_std=torch.ones(pol.config.state_dim), action_mean=torch.arange(A).float(),
                  action_std=torch.arange(A).float() + 1)

@@ -42,11 +42,11 @@ def test_policies_take_the_option_before_any_engine_exists(monkeypatch):
         monkeypatch.delenv(k, raising=False)
     cfg = FastVLAConfig(vlm_model_name="synthetic:tiny:77", hidden_dim=48, fusion_dim=64, dropout=0.0)
     flow = FastVLAPolicy(cfg, chunk_size=3, action_head="flow", flow_time_dim=6, flow_noise_draws=4)
-    assert flow.flow_noise_draws == 4 and flow.model.flow_noise_draws == 4 and flow.model.backbone._head_flow_draws == 4
+    assert flow.flow_noise_draws == 4 and flow.model.flow_noise_draws == 4 and flow.model.backbone.head_spec.draws == 4
     assert flow.model.backbone._engine is None                             # nothing was built
     assert "draws" not in flow.model.flow_record() and "noise_draws" not in flow.model.flow_record()      # a property of the run: no checkpoint key
     plain = FastVLAPolicy(cfg, chunk_size=3, action_head="flow", flow_time_dim=6)
-    assert plain.flow_noise_draws == 1 and plain.model.backbone._head_flow_draws == 1
+    assert plain.flow_noise_draws == 1 and plain.model.backbone.head_spec.draws == 1
     assert list(plain.state_dict()) == list(flow.state_dict())
     for kw in (dict(flow_noise_draws=2), dict(action_head="regression", flow_noise_draws=8)):
         with pytest.raises(ValueError, match="action_head"):
@@ -139,7 +139,7 @@ def test_lerobot_plugin_takes_the_same_argument_and_twin(monkeypatch):
 
     fields = set(vars(cfg()))
     pol = LRPolicy(cfg(), action_head="flow", flow_time_dim=6, flow_noise_draws=3)
-    assert pol.flow_noise_draws == 3 and pol.model.flow_noise_draws == 3 and pol.model.backbone._head_flow_draws == 3 and pol.model.backbone._engine is None
+    assert pol.flow_noise_draws == 3 and pol.model.flow_noise_draws == 3 and pol.model.backbone.head_spec.draws == 3 and pol.model.backbone._engine is None
     assert set(vars(pol.config)) == fields                                 # the registered config gains no field
     assert LRPolicy(cfg(), action_head="flow", flow_time_dim=6).flow_noise_draws == 1
     with pytest.raises(ValueError, match="action_head"):

@@ -141,7 +141,7 @@ def test_flow_policy_modules_record_and_mismatched_loads(monkeypatch):
     assert m.flow_eval_draw()[1] == (1 << 61) + 1
     assert m.flow_loss_draw()[1] == (1 << 60) + 1
     # the head's layout is fixed before the engine exists
-    assert flow.model.backbone._head_flow == m.flow and reg.model.backbone._head_flow is None
+    assert flow.model.backbone.head_spec.flow == m.flow and reg.model.backbone.head_spec.flow is None
     for pol, other in ((reg, flow), (flow, reg)):
         with pytest.raises(ValueError) as ei:
             check_fusion_width({"model.fusion.0.weight": other.model.fusion[0].weight.detach()}, pol, "ckpt")

@@ -164,12 +164,12 @@ def test_policy_arguments_twins_and_refusals(monkeypatch, make):
     for k in SAMPLES_ENV:
         monkeypatch.delenv(k, raising=False)
     off = make(**FLOW)
-    assert (off.flow_samples, off.flow_select) == (1, None) and off.model.backbone._head_flow_samples is None and off.last_candidates is None
+    assert (off.flow_samples, off.flow_select) == (1, None) and off.model.backbone.head_spec.samples is None and off.last_candidates is None
     med = make(**FLOW, flow_samples=4)
-    assert (med.flow_samples, med.flow_select) == (4, "medoid") and med.model.backbone._head_flow_samples == dict(max_samples=4, step_weights=None)
+    assert (med.flow_samples, med.flow_select) == (4, "medoid") and med.model.backbone.head_spec.samples == dict(max_samples=4, step_weights=None)
     coh = make(**FLOW, flow_samples=5, flow_select="coherent", flow_coherence_decay=0.25)
     K = coh.model.chunk_size
-    assert coh.model.backbone._head_flow_samples == dict(max_samples=5, step_weights=[0.25 ** k for k in range(K)])
+    assert coh.model.backbone.head_spec.samples == dict(max_samples=5, step_weights=[0.25 ** k for k in range(K)])
     assert make(**FLOW, flow_samples=2, flow_select="first").flow_select == "first"
     # a property of the run: no record anywhere
     assert med.model.flow_record() == off.model.flow_record() and coh.model.flow_record() == off.model.flow_record()
@@ -190,7 +190,7 @@ def test_policy_arguments_twins_and_refusals(monkeypatch, make):
     monkeypatch.setenv("FASTVLA_FLOW_SELECT", "Coherent")
     monkeypatch.setenv("FASTVLA_FLOW_COHERENCE_DECAY", "0.75")
     tw = make(**FLOW)
-    assert (tw.flow_samples, tw.flow_select) == (6, "coherent") and tw.model.backbone._head_flow_samples["step_weights"][1] == 0.75
+    assert (tw.flow_samples, tw.flow_select) == (6, "coherent") and tw.model.backbone.head_spec.samples["step_weights"][1] == 0.75
     assert make(**FLOW, flow_samples=2, flow_select="first").flow_samples == 2
     reg = make()
     assert (reg.flow_samples, reg.flow_select) == (1, None)

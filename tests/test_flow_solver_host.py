@@ -128,7 +128,7 @@ def test_flow_solver_on_the_policies_setter_and_record(monkeypatch):
     flow = dict(action_head="flow", flow_time_dim=6, flow_steps=4, flow_seed=9)
     euler, heun = _core(**flow), _core(**flow, flow_solver="heun")
     assert euler.flow_solver == "euler" and heun.flow_solver == "heun" and heun.flow_steps == 4
-    assert heun.model.backbone._head_flow_solver == "heun" and heun.model.backbone._head_flow_solver_rows and not euler.model.backbone._head_flow_solver_rows
+    assert heun.model.backbone.head_spec.solver == "heun" and heun.model.backbone.head_spec.solver_rows and not euler.model.backbone.head_spec.solver_rows
     # the record: "solver" only when it is not Euler; flow_kwargs maps it back; an Euler run writes the record it wrote
     base = {"type": "flow", "steps": 4, "time_dim": 6, "min_period": 4e-3, "max_period": 4.0, "time_dist": "uniform", "dist_a": 0.0, "dist_b": 1.0, "seed": 9}
     assert euler.model.flow_record() == base and heun.model.flow_record() == {**base, "solver": "heun"}
@@ -139,7 +139,7 @@ def test_flow_solver_on_the_policies_setter_and_record(monkeypatch):
     # a policy built with a higher-order solver switches among all four (Euler included) at any time; the record follows
     for name in ("rk4", "euler", "midpoint", "heun"):
         heun.flow_solver = name
-        assert heun.flow_solver == name and heun.model.backbone._head_flow_solver == name and heun.model.backbone._head_flow_solver_rows
+        assert heun.flow_solver == name and heun.model.backbone.head_spec.solver == name and heun.model.backbone.head_spec.solver_rows
         assert heun.model.flow_record().get("solver") == (None if name == "euler" else name)
     with pytest.raises(ValueError, match="flow_solver"):
         heun.flow_solver = "rk5"

@@ -27,6 +27,26 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
+def _bucket_trampoline(bucket_cb):
+    """-> (the C callback that hands a finished gradient bucket to bucket_cb(bucket, offset, numel), the dict its first exception is kept in under "exc": it
+    must not unwind through the C frames, so the caller raises it once the library call has returned)"""
+    err = {}
+
+    def _cb(_user, bucket, off, numel):
+        if bucket_cb is not None:
+            try:
+                bucket_cb(int(bucket), int(off), int(numel))
+            except Exception as exc:
+                err.setdefault("exc", exc)
+
+    return _lib.BUCKET_CB(_cb), err
+
+
+def _train_tensors(arr):
+    """fv_train_tensor records -> the dicts train_layout() and train_lora_layout() hand out"""
+    return [dict(name=t.name.decode(), offset=t.offset, numel=t.numel, rows=t.rows, cols=t.cols, bucket=t.bucket, packing=t.packing) for t in arr]
+
+
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
@@ -282,9 +302,7 @@ class FastVLAEngine:
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            base = self._ws.data_ptr()
-            off = (-base) % 256
-            _lib.check(self.lib.fv_bind_workspace(self.h, base + off, self._ws.numel() - off), "fv_bind_workspace")
+            _lib.check(self.lib.fv_bind_workspace(self.h, *self._aligned(self._ws)), "fv_bind_workspace")
 
     # ---------------------------------------------------------------- frozen backbone
     IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # reference model/fastvlm_adapter.py:468-469,475-476
@@ -293,14 +311,7 @@ class FastVLAEngine:
                    range_heuristic: bool = True) -> torch.Tensor:
         """letterbox (+ the reference's `_maybe_normalize_imagenet`, :463-477, when asked; range_heuristic = its torchvision branch, which is what an installed
         reference runs: torchvision is one of its dependencies)."""
-        if images.ndim != 4:
-            raise ValueError(f"(B,C,H,W) expected, but got shape {tuple(images.shape)}")
-        if images.dtype == torch.uint8:
-            dt = _lib.FV_U8
-        else:
-            images = images.to(torch.float32)
-            dt = _lib.FV_F32
-        images = images.to(self.device).contiguous()
+        images, dt = self._augment_source(images)
         B, Cc, H, W = images.shape
         S = self.model.tower.image_size
         pix = torch.empty(B, S, S, 4, dtype=torch.bfloat16, device=self.device)
@@ -316,6 +327,7 @@ class FastVLAEngine:
 
     # ---------------------------------------------------------------- image augmentation (fastvla_hip/augment.py)
     def _augment_source(self, images: torch.Tensor):
+        """-> (images on the device, contiguous, uint8 as it is and everything else fp32; the library's type code): what every entry point that reads source images takes"""
         if images.ndim != 4:
             raise ValueError(f"(B,C,H,W) expected, but got shape {tuple(images.shape)}")
         if images.dtype == torch.uint8:
@@ -375,14 +387,7 @@ class FastVLAEngine:
                               return_tower_out: bool = False):
         """preprocess() + vision_forward() as ONE call (fv_vision_forward_images): the stem samples the source images itself, the
         letterboxed 1024^2 frame never exists in HBM.  Same tokens, bit for bit."""
-        if images.ndim != 4:
-            raise ValueError(f"(B,C,H,W) expected, but got shape {tuple(images.shape)}")
-        if images.dtype == torch.uint8:
-            dt = _lib.FV_U8
-        else:
-            images = images.to(torch.float32)
-            dt = _lib.FV_F32
-        images = images.to(self.device).contiguous()
+        images, dt = self._augment_source(images)
         B, Cc, H, W = images.shape
         t, l = self.model.tower, self.model.llm
         self.ensure_workspace(B, 1, False)
@@ -672,19 +677,46 @@ class FastVLAEngine:
                    "fv_head_flow_prepare", self.h)
         return u
 
+    def _states(self, states: torch.Tensor, B: int) -> torch.Tensor:
+        """states as the head kernels read them: fp32 (B, ds), contiguous, on the device (every head call passes here: a tensor that is already both
+        skips .to(), which would hand it back unchanged, and that pays for the call)"""
+        if states.dtype is not torch.float32 or states.device != self.device:
+            states = states.to(device=self.device, dtype=torch.float32)
+        states = states.contiguous()
+        if states.shape != (B, self.head_dims["ds"]):
+            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        return states
+
+    def _f32(self, t: torch.Tensor, rows: int, da: int, name: str, what: str = "(B, {da})") -> torch.Tensor:
+        """a sampler's float operand: fp32, contiguous, on the device, rows * da elements"""
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if t.numel() != rows * da:
+            raise ValueError(f"{name} must hold {what.format(rows=rows, da=da)} elements, got {tuple(t.shape)}")
+        return t
+
+    def _i32(self, t: torch.Tensor, B: int, name: str) -> torch.Tensor:
+        """a sampler's per-row integer operand: int32, contiguous, on the device, B elements"""
+        t = t.to(device=self.device, dtype=torch.int32).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"{name} must hold B = {B} elements, got {tuple(t.shape)}")
+        return t
+
+    def _chunk_out(self, chunk_out: Optional[torch.Tensor], B: int, da: int, like: torch.Tensor) -> torch.Tensor:
+        """where a sampler writes its normalised chunk: the caller's tensor, checked (it lives where `like` does), or a new one"""
+        if chunk_out is None:
+            return torch.empty(B, da, dtype=torch.float32, device=self.device)
+        if chunk_out.dtype != torch.float32 or not chunk_out.is_contiguous() or chunk_out.numel() != B * da or chunk_out.device != like.device:
+            raise ValueError(f"chunk_out must be a contiguous float32 (B, {da}) tensor on {self.device}")
+        return chunk_out
+
     def head_flow_sample(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, *, steps: int = 10,
                          noise: Optional[torch.Tensor] = None, seed: int = 0, offset: int = 0) -> torch.Tensor:
         """-> actions (B, da): `steps` steps of the chosen solver (set_head_flow_solver; Euler by default) along the velocity field from x_1 = noise (None: drawn from (seed, offset)) to t = 0 (fv_head_flow_sample),
         un-normalised when set_io_norm is on.  Not differentiated."""
         B, da = pooled.shape[0], self.head_dims["da"]
-        states = states.to(device=self.device, dtype=torch.float32).contiguous()
-        pooled = pooled.contiguous()
-        if states.shape != (B, self.head_dims["ds"]):
-            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        states, pooled = self._states(states, B), pooled.contiguous()
         if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
-            if noise.numel() != B * da:
-                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
+            noise = self._f32(noise, B, da, "noise")
         self.ensure_workspace(B, 1, False)
         actions = torch.empty(B, da, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.fv_head_flow_sample(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed, offset,
@@ -722,25 +754,13 @@ class FastVLAEngine:
         (fv_head_flow_sample_guided).  row_mask (B) int32: rows with 0 are sampled unguided.  chunk: the final normalised x_0, the next call's `prev`
         (written into chunk_out when one is handed in)."""
         B, da = pooled.shape[0], self.head_dims["da"]
-        states = states.to(device=self.device, dtype=torch.float32).contiguous()
-        pooled = pooled.contiguous()
-        if states.shape != (B, self.head_dims["ds"]):
-            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
-        prev = prev.to(device=self.device, dtype=torch.float32).contiguous()
-        if prev.numel() != B * da:
-            raise ValueError(f"prev must hold (B, {da}) elements, got {tuple(prev.shape)}")
+        states, pooled = self._states(states, B), pooled.contiguous()
+        prev = self._f32(prev, B, da, "prev")
         if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
-            if noise.numel() != B * da:
-                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
+            noise = self._f32(noise, B, da, "noise")
         if row_mask is not None:
-            row_mask = row_mask.to(device=self.device, dtype=torch.int32).contiguous()
-            if row_mask.numel() != B:
-                raise ValueError(f"row_mask must hold B = {B} elements, got {tuple(row_mask.shape)}")
-        if chunk_out is None:
-            chunk_out = torch.empty(B, da, dtype=torch.float32, device=self.device)
-        elif chunk_out.dtype != torch.float32 or not chunk_out.is_contiguous() or chunk_out.numel() != B * da or chunk_out.device != prev.device:
-            raise ValueError(f"chunk_out must be a contiguous float32 (B, {da}) tensor on {self.device}")
+            row_mask = self._i32(row_mask, B, "row_mask")
+        chunk_out = self._chunk_out(chunk_out, B, da, prev)
         self.ensure_workspace(B, 1, False)
         actions = torch.empty(B, da, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.fv_head_flow_sample_guided(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed,
@@ -755,24 +775,12 @@ class FastVLAEngine:
         previous chunk in normalised space, read `shift` steps ahead (fv_head_flow_sample_prefix).  delays (B) int32, 0 pins nothing.  chunk: the final
         normalised x_0, the next call's `prev` (written into chunk_out when one is handed in)."""
         B, da = pooled.shape[0], self.head_dims["da"]
-        states = states.to(device=self.device, dtype=torch.float32).contiguous()
-        pooled = pooled.contiguous()
-        if states.shape != (B, self.head_dims["ds"]):
-            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
-        prev = prev.to(device=self.device, dtype=torch.float32).contiguous()
-        if prev.numel() != B * da:
-            raise ValueError(f"prev must hold (B, {da}) elements, got {tuple(prev.shape)}")
-        delays = torch.as_tensor(delays).to(device=self.device, dtype=torch.int32).contiguous()
-        if delays.numel() != B:
-            raise ValueError(f"delays must hold B = {B} elements, got {tuple(delays.shape)}")
+        states, pooled = self._states(states, B), pooled.contiguous()
+        prev = self._f32(prev, B, da, "prev")
+        delays = self._i32(torch.as_tensor(delays), B, "delays")
         if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
-            if noise.numel() != B * da:
-                raise ValueError(f"noise must hold (B, {da}) elements, got {tuple(noise.shape)}")
-        if chunk_out is None:
-            chunk_out = torch.empty(B, da, dtype=torch.float32, device=self.device)
-        elif chunk_out.dtype != torch.float32 or not chunk_out.is_contiguous() or chunk_out.numel() != B * da or chunk_out.device != prev.device:
-            raise ValueError(f"chunk_out must be a contiguous float32 (B, {da}) tensor on {self.device}")
+            noise = self._f32(noise, B, da, "noise")
+        chunk_out = self._chunk_out(chunk_out, B, da, prev)
         self.ensure_workspace(B, 1, False)
         actions = torch.empty(B, da, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.fv_head_flow_sample_prefix(self.h, flat_params.data_ptr(), pooled.data_ptr(), states.data_ptr(), B, int(steps), _ptr(noise), seed,
@@ -805,30 +813,16 @@ class FastVLAEngine:
             raise ValueError(f"select must be one of {list(_lib.FLOW_SELECTS)}, got {select!r}")
         S = check_flow_samples(samples)
         B, da = pooled.shape[0], self.head_dims["da"]
-        states = states.to(device=self.device, dtype=torch.float32).contiguous()
-        pooled = pooled.contiguous()
-        if states.shape != (B, self.head_dims["ds"]):
-            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        states, pooled = self._states(states, B), pooled.contiguous()
         if prev is not None:
-            prev = prev.to(device=self.device, dtype=torch.float32).contiguous()
-            if prev.numel() != B * da:
-                raise ValueError(f"prev must hold (B, {da}) elements, got {tuple(prev.shape)}")
+            prev = self._f32(prev, B, da, "prev")
         if delays is not None:
-            delays = torch.as_tensor(delays).to(device=self.device, dtype=torch.int32).contiguous()
-            if delays.numel() != B:
-                raise ValueError(f"delays must hold B = {B} elements, got {tuple(delays.shape)}")
+            delays = self._i32(torch.as_tensor(delays), B, "delays")
         if row_mask is not None:
-            row_mask = row_mask.to(device=self.device, dtype=torch.int32).contiguous()
-            if row_mask.numel() != B:
-                raise ValueError(f"row_mask must hold B = {B} elements, got {tuple(row_mask.shape)}")
+            row_mask = self._i32(row_mask, B, "row_mask")
         if noise is not None:
-            noise = noise.to(device=self.device, dtype=torch.float32).contiguous()
-            if noise.numel() != S * B * da:
-                raise ValueError(f"noise must hold (samples * B, {da}) = ({S * B}, {da}) elements, got {tuple(noise.shape)}")
-        if chunk_out is None:
-            chunk_out = torch.empty(B, da, dtype=torch.float32, device=self.device)
-        elif chunk_out.dtype != torch.float32 or not chunk_out.is_contiguous() or chunk_out.numel() != B * da or chunk_out.device != pooled.device:
-            raise ValueError(f"chunk_out must be a contiguous float32 (B, {da}) tensor on {self.device}")
+            noise = self._f32(noise, S * B, da, "noise", "(samples * B, {da}) = ({rows}, {da})")
+        chunk_out = self._chunk_out(chunk_out, B, da, pooled)
         self.ensure_workspace(B, 1, False)
         out = dict(actions=torch.empty(B, da, dtype=torch.float32, device=self.device), chunk=chunk_out)
         if extras:
@@ -851,10 +845,7 @@ class FastVLAEngine:
         """normalized_actions: keep the output in normalised action space even without dropout (loss / training paths when
         set_io_norm folded the dataset statistics in)."""
         B = pooled.shape[0]
-        states = states.to(device=self.device, dtype=torch.float32).contiguous()
-        pooled = pooled.contiguous()
-        if states.shape != (B, self.head_dims["ds"]):
-            raise ValueError(f"states must be (B,{self.head_dims['ds']}), got {tuple(states.shape)}")
+        states, pooled = self._states(states, B), pooled.contiguous()
         saved = saved if saved is not None else self.head_saved(B)
         # 1 = dropout active, 2 = training-mode arithmetic without dropout (folded action statistics are NOT applied), 0 = inference
         mode = 0 if not (training or normalized_actions) else (1 if training and dropout_p > 0.0 else 2)
@@ -1054,8 +1045,7 @@ class FastVLAEngine:
         _lib.check(self.lib.fv_train_layout(self.h, None, 0, C.byref(n), C.byref(total), C.byref(nb)), "fv_train_layout", self.h)
         arr = (_lib.TrainTensor * n.value)()
         _lib.check(self.lib.fv_train_layout(self.h, arr, n.value, C.byref(n), C.byref(total), C.byref(nb)), "fv_train_layout", self.h)
-        tensors = [dict(name=t.name.decode(), offset=t.offset, numel=t.numel, rows=t.rows, cols=t.cols, bucket=t.bucket, packing=t.packing) for t in arr]
-        return tensors, int(total.value), int(nb.value)
+        return _train_tensors(arr), int(total.value), int(nb.value)
 
     def train_export_params(self, flat: torch.Tensor) -> None:
         """backbone part of the flat master buffer <- the library's current weights (fv_train_export_params)"""
@@ -1116,8 +1106,7 @@ class FastVLAEngine:
             raise ValueError(f"tower_out must be (B, {self.model.tower.num_tokens}, {self.model.tower.out_dim}) bf16, got {tuple(tower_out.shape)} {tower_out.dtype}")
         actions = torch.empty(B, self.head_dims["da"], dtype=torch.float32, device=self.device)
         loss = torch.empty(1, dtype=torch.float32, device=self.device)
-        pad = (-ws.data_ptr()) % 256
-        return B, T, tower_out, ids, lens, states, targets, actions, loss, ws.data_ptr() + pad, ws.numel() - pad
+        return (B, T, tower_out, ids, lens, states, targets, actions, loss, *self._aligned(ws))
 
     def train_forward_backward(self, flat_params: torch.Tensor, tower_out: torch.Tensor, ids: torch.Tensor, lens: torch.Tensor, states: torch.Tensor,
                                targets: torch.Tensor, ws: torch.Tensor, *, training: bool = True, dropout_p: float = 0.0, seed: int = 0, offset: int = 0,
@@ -1128,16 +1117,7 @@ class FastVLAEngine:
         B, T, tower_out, ids, lens, states, targets, actions, loss, ws_ptr, ws_bytes = self._train_step_inputs(tower_out, ids, lens, states, targets, ws)
         if flat_grads is None:
             flat_grads = torch.empty_like(flat_params)
-        err = {}
-
-        def _cb(_user, bucket, off, numel):
-            if bucket_cb is not None:
-                try:
-                    bucket_cb(int(bucket), int(off), int(numel))
-                except Exception as exc:  # must not unwind through the C frames
-                    err.setdefault("exc", exc)
-
-        fn = _lib.BUCKET_CB(_cb)
+        fn, err = _bucket_trampoline(bucket_cb)
         with self._Mask(self, self._pad_arg(pad, B)):
             rc = self.lib.fv_train_forward_backward(self.h, flat_params.data_ptr(), tower_out.data_ptr(), ids.data_ptr(), lens.data_ptr(), states.data_ptr(),
                                                     targets.data_ptr(), B, T, int(training), float(dropout_p), seed, offset, ws_ptr, ws_bytes,
@@ -1173,8 +1153,7 @@ class FastVLAEngine:
         _lib.check(self.lib.fv_train_lora_layout(self.h, None, 0, C.byref(n), C.byref(total)), "fv_train_lora_layout", self.h)
         arr = (_lib.TrainTensor * n.value)()
         _lib.check(self.lib.fv_train_lora_layout(self.h, arr, n.value, C.byref(n), C.byref(total)), "fv_train_lora_layout", self.h)
-        tensors = [dict(name=t.name.decode(), offset=t.offset, numel=t.numel, rows=t.rows, cols=t.cols, bucket=t.bucket, packing=t.packing) for t in arr]
-        return tensors, int(total.value)
+        return _train_tensors(arr), int(total.value)
 
     def train_lora_project(self, flat_grads_full: torch.Tensor, lora_params: torch.Tensor, lora_grads: torch.Tensor) -> None:
         """lora_grads <- head / projector gradients copied, dA = s B^T dW', dB = s dW' A^T of every adapted matrix (fv_train_lora_project)"""
@@ -1221,6 +1200,7 @@ class FastVLAEngine:
 
     @staticmethod
     def _aligned(ws: torch.Tensor):
+        """-> (pointer, bytes) of a workspace from its first 256-byte boundary on (every workspace is allocated 256 bytes larger than the library asks for)"""
         base = ws.data_ptr()
         pad = (-base) % 256
         return base + pad, ws.numel() - pad
@@ -1251,16 +1231,7 @@ class FastVLAEngine:
     def train_tower_backward(self, pix: torch.Tensor, d_tower_out: torch.Tensor, tws: torch.Tensor, flat_grads: torch.Tensor, bucket_cb=None) -> None:
         """the tower's backward from dL/d(tower_out) (fp16, loss-scaled): its gradients into flat_grads at their train_layout() offsets"""
         B = pix.shape[0]
-        err = {}
-
-        def _cb(_user, bucket, off, numel):
-            if bucket_cb is not None:
-                try:
-                    bucket_cb(int(bucket), int(off), int(numel))
-                except Exception as exc:  # must not unwind through the C frames
-                    err.setdefault("exc", exc)
-
-        fn = _lib.BUCKET_CB(_cb)
+        fn, err = _bucket_trampoline(bucket_cb)
         p, n = self._aligned(tws)
         rc = self.lib.fv_train_tower_backward(self.h, pix.data_ptr(), d_tower_out.data_ptr(), B, p, n, flat_grads.data_ptr(), fn, None, _stream())
         if "exc" in err:

@@ -16,6 +16,7 @@ from fastvla_hip import HEAD_KEYS
 
 from ..model.fastvlm_adapter import FastVLMBackbone
 from .configuration_fastvla import FastVLAConfig
+from .options import PolicyOptions
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -102,55 +103,45 @@ class _FlowLossFunction(torch.autograd.Function):
 
 
 class FastVLMWithExpert(nn.Module):
-    def __init__(self, config: FastVLAConfig, chunk_size: int = 1, action_loss: str = "mse", action_loss_beta: float = 1.0, flow: Optional[dict] = None,
-                 flow_steps: int = 10, flow_seed: Optional[int] = None, flow_noise_draws: int = 1, flow_prefix: Optional[dict] = None,
-                 flow_solver: str = "euler", flow_samples: int = 1, flow_select: Optional[str] = None, flow_coherence_decay: float = 0.5) -> None:
-        """chunk_size = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
-        `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  action_loss: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library.
+    def __init__(self, config: FastVLAConfig, options: Optional[PolicyOptions] = None) -> None:
+        """options: fastvla.options.resolve_policy_options' result (None: the defaults, the reference's model).  What the head takes from it --
+        chunk["chunk_size"] = K > 1 (an extension of this build; the pinned core config has no such field): the head predicts K future steps per observation --
+        `action_head` is Linear(fusion_dim, K * A), actions are (B, K, A).  chunk["loss"]: "mse" | "l1" | "smooth_l1" (beta), evaluated inside the library.
         flow = FastVLAEngine.set_head_flow's keyword arguments: the flow-matching head -- fusion.0 reads K * A + time_dim more columns (x_t and phi(t)),
-        head() samples with flow_steps steps of flow_solver, head_loss() noises its targets and returns the predicted velocity.  flow_seed: the noise streams' seed
-        (default: torch's initial seed, as the dropout stream's).  flow_noise_draws = S (1 .. 16): S noise draws (t, eps) per observation wherever targets are
+        head() samples with flow_steps steps of the solver, head_loss() noises its targets and returns the predicted velocity.  flow_seed: the noise streams' seed
+        (default: torch's initial seed, as the dropout stream's).  noise_draws = S (1 .. 16): S noise draws (t, eps) per observation wherever targets are
         noised -- draw s of a call at offset o is the single draw of offset o + (s << 56); the velocity handed out is draw 0's.
-        flow_prefix = fastvla_hip.prefix.check_prefix_config's result (flow head, K > 1): action-prefix conditioning -- fusion.0 reads K mask columns behind
+        prefix = fastvla_hip.prefix.check_prefix_config's result (flow head, K > 1): action-prefix conditioning -- fusion.0 reads K mask columns behind
         phi(t), training gives the first d <= max_delay steps of a chunk to the network clean and keeps them out of the loss, rtc_sample pins them.
-        flow_solver: "euler" | "midpoint" | "heun" | "rk4", the integrator of every sampling route (flow_steps are steps of it); a property of the run.
-        flow_samples = S (1 .. 16) with flow_select "first" | "medoid" | "coherent" (fastvla_hip/select.py): every sampling route draws S candidates per
-        observation in one call and returns the chosen one; "coherent" weights step k of the overlap with the previous chunk flow_coherence_decay**k.
-        A property of the run; S = 1 calls nothing new."""
+        solver: "euler" | "midpoint" | "heun" | "rk4", the integrator of every sampling route (flow_steps are steps of it); a property of the run.
+        samples = S (1 .. 16) with select "first" | "medoid" | "coherent" (fastvla_hip/select.py): every sampling route draws S candidates per
+        observation in one call and returns the chosen one; "coherent" weights step k of the overlap with the previous chunk decay**k.
+        A property of the run; S = 1 calls nothing new.  The cross-field refusals are HeadSpec's (fastvla_hip/head_spec.py)."""
         super().__init__()
+        from fastvla_hip.head_spec import HeadSpec
         from fastvla_hip.select import check_flow_select, coherence_weights
-        self.flow_samples, self.flow_select = check_flow_select(flow_samples, flow_select, action_head="flow" if flow is not None else "regression",
-                                                                chunk_size=chunk_size)
+        o = PolicyOptions() if options is None else options
+        K = o.chunk["chunk_size"]
+        # (the one pair checked here and not in HeadSpec, which holds no select name: a hand-built PolicyOptions gets its "medoid" default and a refusal
+        # that names the select it asked for)
+        self.flow_samples, self.flow_select = check_flow_select(o.samples, o.select, action_head="flow" if o.flow is not None else "regression", chunk_size=K)
         self.flow_samples_now = self.flow_samples      # select_action_chunk(num_samples=) lowers it for one call
         self.last_candidates = self.last_choice = self.last_sample_spread = None      # device tensors of the last multi-sample call
-        self._coherence_weights = coherence_weights(int(chunk_size), flow_coherence_decay) if self.flow_select == "coherent" else None
-        from fastvla_hip.engine import check_flow_draws, check_head_loss
-        self.flow_noise_draws = check_flow_draws(flow_noise_draws)
-        if self.flow_noise_draws > 1 and flow is None:
-            raise ValueError(f"flow_noise_draws={self.flow_noise_draws} needs action_head='flow' (the regression head has no noise to draw)")
+        self._coherence_weights = coherence_weights(int(K), o.decay) if self.flow_select == "coherent" else None
+        spec = HeadSpec(dims=dict(state_dim=config.state_dim, action_dim=K * config.action_dim, hidden_dim=config.hidden_dim, fusion_dim=config.fusion_dim),
+                        loss=dict(kind=o.chunk["loss"], beta=o.chunk["beta"], chunk=K), flow=None if o.flow is None else dict(o.flow),
+                        prefix=None if o.prefix is None else dict(o.prefix), draws=o.noise_draws, solver=o.solver,
+                        samples=dict(max_samples=self.flow_samples, step_weights=self._coherence_weights) if self.flow_samples > 1 else None)
         self.config = config
-        self.action_loss, self.action_loss_beta, self.chunk_size = check_head_loss(action_loss, action_loss_beta, chunk_size)
+        self.flow_noise_draws = spec.draws
+        self.action_loss, self.action_loss_beta, self.chunk_size = spec.loss["kind"], spec.loss["beta"], spec.loss["chunk"]
         self.head_width = self.chunk_size * config.action_dim
         self.last_loss_metrics: Optional[torch.Tensor] = None    # (2,) [masked MSE, valid fraction] of the last loss the chunked kernel evaluated, else None
         self.backbone = FastVLMBackbone(config.to_backbone_config())
-        self.backbone.configure_head(state_dim=config.state_dim, action_dim=self.head_width,
-                                     hidden_dim=config.hidden_dim, fusion_dim=config.fusion_dim)
-        self.backbone.configure_head_loss(self.action_loss, self.action_loss_beta, self.chunk_size)
-        self.flow: Optional[dict] = None if flow is None else dict(flow)
-        self.flow_steps = int(flow_steps)
-        self.backbone.configure_head_flow(self.flow)
-        if flow_prefix is not None and (flow is None or int(flow_prefix["chunk"]) != self.chunk_size):
-            raise ValueError(f"flow_prefix_max_delay={flow_prefix.get('max_delay')} needs action_head='flow' and the head's chunk_size={self.chunk_size}")
-        self.flow_prefix: Optional[dict] = None if flow_prefix is None else dict(flow_prefix)
-        self.backbone.configure_head_flow_prefix(self.flow_prefix)
-        self.backbone.configure_head_flow_draws(self.flow_noise_draws)
-        from fastvla_hip.engine import check_flow_solver
-        self._flow_solver = check_flow_solver(flow_solver)
-        if self._flow_solver != "euler" and flow is None:
-            raise ValueError(f"flow_solver={self._flow_solver!r} needs action_head='flow' (the regression head integrates nothing)")
-        self._flow_solver_rows = self._flow_solver != "euler"      # a policy built with a higher-order solver reserved their rows and may switch among all four
-        self.backbone.configure_head_flow_solver(self._flow_solver)
-        self.backbone.configure_head_flow_samples(dict(max_samples=self.flow_samples, step_weights=self._coherence_weights) if self.flow_samples > 1 else None)
+        self.backbone.configure_head(spec)
+        self.flow, self.flow_prefix, self.flow_steps = spec.flow, spec.prefix, int(o.flow_steps)
+        self._flow_solver = spec.solver
+        self._flow_solver_rows = spec.solver_rows      # a policy built with a higher-order solver reserved their rows and may switch among all four
         self.rtc: Optional[dict] = None      # configure_rtc: real-time chunking of the flow sampler, a property of the run
         self._chunker = self._rtc_key = None
         extra = self.head_width + int(self.flow["time_dim"]) + (self.chunk_size if self.flow_prefix else 0) if self.flow else 0
@@ -163,8 +154,12 @@ class FastVLMWithExpert(nn.Module):
         self._flat: Optional[torch.Tensor] = None
         self._drop_seed = int(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
         self._drop_calls = 0
-        self._flow_seed = int(self._drop_seed if flow_seed is None else flow_seed) & 0x7FFFFFFFFFFFFFFF
+        self._flow_seed = int(self._drop_seed if o.flow_seed is None else o.flow_seed) & 0x7FFFFFFFFFFFFFFF
         self._flow_loss_calls = self._flow_eval_index = self._flow_sample_calls = 0
+        if o.chunk["dim_weights"] is not None or o.chunk["step_weights"] is not None:
+            self.set_action_loss_weights(o.chunk["dim_weights"], o.chunk["step_weights"])
+        if o.rtc is not None:
+            self.configure_rtc(o.rtc)
 
     # ------------------------------------------------------------------ flow head: the noise streams.  ONE seed, four disjoint offset ranges
     def flow_train_draw(self, step: int, micro: int):
@@ -274,7 +269,7 @@ class FastVLMWithExpert(nn.Module):
     def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
         """the loss of every later loss evaluation / train step: "mse" | "l1" | "smooth_l1" (beta)"""
         self.backbone.configure_head_loss(kind, beta, self.chunk_size)
-        self.action_loss, self.action_loss_beta = self.backbone._head_loss["kind"], self.backbone._head_loss["beta"]
+        self.action_loss, self.action_loss_beta = self.backbone.head_spec.loss["kind"], self.backbone.head_spec.loss["beta"]
 
     def set_action_loss_weights(self, dim_weights=None, step_weights=None) -> None:
         """Weights of the loss of every later loss evaluation / train step: dim_weights (A values, e.g. gripper against arm) and step_weights (K values, e.g.
@@ -285,7 +280,7 @@ class FastVLMWithExpert(nn.Module):
     @property
     def action_loss_weights(self) -> Optional[dict]:
         """{"dim": [A floats] or None, "step": [K floats] or None}, or None while weighting is off"""
-        return self.backbone._head_loss_weights
+        return self.backbone.head_spec.loss_weights
 
     def chunk_record(self, n_action_steps: int = 1, temporal_ensemble_coeff: Optional[float] = None) -> Optional[dict]:
         """what a checkpoint records beside the tensors (hip_extras.json "action_chunk"); None with the defaults.  "temporal_ensemble_coeff", "dim_weights" and
@@ -413,7 +408,7 @@ class FastVLMWithExpert(nn.Module):
 
     # ------------------------------------------------------------------ real-time chunking (flow head): the guided sampler
     def configure_rtc(self, rtc: Optional[dict]) -> None:
-        """rtc = {"schedule", "max_guidance_weight", "execution_horizon"} (modeling_fastvla.resolve_rtc_options) or None.  A property of the run: no checkpoint
+        """rtc = {"schedule", "max_guidance_weight", "execution_horizon"} (options.resolve_rtc_options) or None.  A property of the run: no checkpoint
         records it.  The weights of (inference_delay 0, execution_horizon) are handed to the backbone so that the engine is configured BEFORE its first
         workspace exists; another delay or horizon re-uploads them at the call that asks for it."""
         from fastvla_hip.rtc import prefix_weights

@@ -14,262 +14,14 @@ from torch import nn
 from .configuration_fastvla import FastVLAConfig
 from .ema_state import EmaMixin
 from .fastvlm_with_expert import FastVLMWithExpert
+from .flow_surface import FlowSurfaceMixin
+from .options import (FLOW_DIST_A, FLOW_DIST_B, FLOW_MAX_PERIOD, FLOW_MIN_PERIOD, parse_weight_list, resolve_chunk_options,  # noqa: F401  (their public home)
+                      resolve_flow_noise_draws, resolve_flow_options, resolve_flow_samples, resolve_flow_solver, resolve_policy_options,
+                      resolve_prefix_options, resolve_rtc_options)
 from .processor_fastvla import FastVLAProcessor
 
 
-def parse_weight_list(raw: str, name: str, chunk: Optional[int] = None) -> List[float]:
-    """"1,1,4" -> [1.0, 1.0, 4.0]; with `chunk` given also "discount:0.98" -> [0.98 ** k for k in range(chunk)].  ValueError for anything else."""
-    raw = raw.strip()
-    try:
-        if chunk is not None and raw.lower().startswith("discount:"):
-            gamma = float(raw.split(":", 1)[1])
-            return [gamma ** k for k in range(int(chunk))]
-        return [float(x) for x in raw.split(",") if x.strip()]
-    except ValueError:
-        raise ValueError(f"{name}: cannot read '{raw}' (a comma-separated list of numbers{', or discount:<gamma>' if chunk is not None else ''})") from None
-
-
-def resolve_chunk_options(chunk_size=None, n_action_steps=None, action_loss=None, action_loss_beta=None, temporal_ensemble_coeff=None,
-                          action_dim_weights=None, action_step_weights=None) -> Dict:
-    """-> {"chunk_size", "n_action_steps", "loss", "beta", "temporal_ensemble_coeff", "dim_weights", "step_weights"}: explicit arguments, else the FASTVLA_*
-    twins, else the defaults (1, 1, "mse", 1.0, None, None, None).  The last three also take False: off, whatever the twin says (what a checkpoint without
-    a record of them asks for).  ValueError for n_action_steps outside 1 .. chunk_size, an unknown loss name, a non-positive beta, a non-finite coefficient,
-    a coefficient together with n_action_steps != 1, or negative / non-finite weights (their lengths are checked against the head, in set_action_loss_weights)."""
-    from fastvla_hip.engine import check_head_loss, check_loss_weights
-    from fastvla_hip.ensemble import check_coeff
-
-    def pick(arg, env, cast, default):
-        if arg is not None:
-            return arg
-        raw = (os.environ.get(env) or "").strip()
-        return cast(raw) if raw else default
-
-    K = pick(chunk_size, "FASTVLA_CHUNK_SIZE", int, 1)
-    loss, beta, K = check_head_loss(pick(action_loss, "FASTVLA_ACTION_LOSS", str, "mse"), pick(action_loss_beta, "FASTVLA_ACTION_LOSS_BETA", float, 1.0), K)
-    n = pick(n_action_steps, "FASTVLA_N_ACTION_STEPS", int, 1)
-    if int(n) != n or n < 1 or n > K:
-        raise ValueError(f"n_action_steps must be an integer in 1 .. chunk_size. Got n_action_steps={n}, chunk_size={K}.")
-    coeff = pick(temporal_ensemble_coeff, "FASTVLA_TEMPORAL_ENSEMBLE_COEFF", str, None)
-    coeff = None if coeff is None or coeff is False else check_coeff(coeff)
-    if coeff is not None and int(n) != 1:
-        raise ValueError("n_action_steps must be 1 when using temporal ensembling: with it the policy is queried at every step. "
-                         f"Got temporal_ensemble_coeff={coeff}, n_action_steps={n}.")
-    dim_w = pick(action_dim_weights, "FASTVLA_ACTION_DIM_WEIGHTS", lambda r: parse_weight_list(r, "FASTVLA_ACTION_DIM_WEIGHTS"), None)
-    step_w = pick(action_step_weights, "FASTVLA_ACTION_STEP_WEIGHTS", lambda r: parse_weight_list(r, "FASTVLA_ACTION_STEP_WEIGHTS", K), None)
-    if isinstance(step_w, str):
-        step_w = parse_weight_list(step_w, "action_step_weights", K)
-    dim_w, step_w = (None if v is None or v is False else v for v in (dim_w, step_w))
-    w = check_loss_weights(dim_w, step_w, len(dim_w) if dim_w is not None else 0, len(step_w) if step_w is not None else 0) or {"dim": None, "step": None}
-    return {"chunk_size": K, "n_action_steps": int(n), "loss": loss, "beta": beta, "temporal_ensemble_coeff": coeff, "dim_weights": w["dim"],
-            "step_weights": w["step"]}
-
-
-FLOW_MIN_PERIOD, FLOW_MAX_PERIOD = 4e-3, 4.0      # pi0's periods of the time embedding
-FLOW_DIST_A, FLOW_DIST_B = 0.0, 1.0                # logit-normal time: t = sigmoid(a + b n)
-
-
-def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, flow_time_dist=None) -> Dict:
-    """-> {"action_head": "regression" | "flow", "steps", "flow": FastVLAEngine.set_head_flow's keyword arguments or None}: explicit arguments, else the
-    FASTVLA_ACTION_HEAD / FASTVLA_FLOW_STEPS / FASTVLA_FLOW_TIME_DIM / FASTVLA_FLOW_TIME_DIST twins, else ("regression", 10, 64, "uniform").  A regression head
-    neither reads nor checks the flow arguments and twins.  ValueError for an
-    unknown head or time distribution, steps < 1, a time_dim that is not a positive even integer."""
-    from fastvla_hip import _lib
-
-    def pick(arg, env, cast, default):
-        if arg is not None:
-            return arg
-        raw = (os.environ.get(env) or "").strip()
-        return cast(raw) if raw else default
-
-    head = str(pick(action_head, "FASTVLA_ACTION_HEAD", str, "regression")).lower()
-    if head not in ("regression", "flow"):
-        raise ValueError(f"action_head must be 'regression' or 'flow', got {head!r}")
-    if head != "flow":      # the FASTVLA_FLOW_* twins are read and checked for a flow head only: a stray value cannot make a regression policy (or its load) raise
-        return {"action_head": head, "steps": 10, "flow": None}
-    steps, dim = pick(flow_steps, "FASTVLA_FLOW_STEPS", int, 10), pick(flow_time_dim, "FASTVLA_FLOW_TIME_DIM", int, 64)
-    dist = str(pick(flow_time_dist, "FASTVLA_FLOW_TIME_DIST", str, "uniform")).lower()
-    if int(steps) != steps or steps < 1:
-        raise ValueError(f"flow_steps must be an integer >= 1, got {steps}")
-    if int(dim) != dim or dim < 2 or dim % 2:
-        raise ValueError(f"flow_time_dim must be a positive even integer, got {dim}")
-    if dist not in _lib.FLOW_TIME_DISTS:
-        raise ValueError(f"flow_time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {dist!r}")
-    flow = dict(time_dim=int(dim), min_period=FLOW_MIN_PERIOD, max_period=FLOW_MAX_PERIOD, time_dist=dist, dist_a=FLOW_DIST_A, dist_b=FLOW_DIST_B)
-    return {"action_head": head, "steps": int(steps), "flow": flow}
-
-
-def resolve_flow_solver(flow_solver=None, *, action_head: str) -> str:
-    """-> "euler" | "midpoint" | "heun" | "rk4", the integrator of a flow head's samplers: the explicit argument, else FASTVLA_FLOW_SOLVER, else "euler".  The
-    twin is read and checked for a flow head only, like the other FASTVLA_FLOW_* twins.  ValueError, naming both settings and before any engine exists, for
-    an unknown name or an explicit flow_solver with the regression head."""
-    from fastvla_hip.engine import check_flow_solver
-    if flow_solver is not None:      # an explicit argument is checked whatever the head is
-        try:
-            name = check_flow_solver(flow_solver)
-        except ValueError:
-            raise ValueError(f"flow_solver must be 'euler', 'midpoint', 'heun' or 'rk4'. Got flow_solver={flow_solver!r}, action_head={action_head!r}.") from None
-        if action_head != "flow":
-            raise ValueError(f"flow_solver needs action_head='flow' (the regression head integrates nothing). Got flow_solver={name!r}, action_head={action_head!r}.")
-        return name
-    if action_head != "flow":
-        return "euler"
-    raw = (os.environ.get("FASTVLA_FLOW_SOLVER") or "").strip()
-    if not raw:
-        return "euler"
-    try:
-        return check_flow_solver(raw)
-    except ValueError:
-        raise ValueError(f"FASTVLA_FLOW_SOLVER must be 'euler', 'midpoint', 'heun' or 'rk4'. Got FASTVLA_FLOW_SOLVER={raw!r}, action_head={action_head!r}.") from None
-
-
-def resolve_flow_samples(flow_samples=None, flow_select=None, flow_coherence_decay=None, *, action_head: str, chunk_size: int, rtc_method: Optional[str] = None) -> Dict:
-    """-> {"samples", "select", "decay"}: several samples per observation at inference (fastvla_hip/select.py).  Explicit arguments, else the FASTVLA_FLOW_SAMPLES /
-    FASTVLA_FLOW_SELECT / FASTVLA_FLOW_COHERENCE_DECAY twins -- read for a flow head only --, else (1, None, 0.5).  ValueError naming both settings, before any
-    engine exists: a regression head, samples outside 1 .. 16, a select name with one sample, "coherent" with chunk_size = 1, rtc_method="guidance" with
-    several samples."""
-    from fastvla_hip.select import check_flow_select, coherence_weights
-    flow = action_head == "flow"
-
-    def pick(arg, env, cast, default):
-        if arg is not None:
-            return arg
-        raw = (os.environ.get(env) or "").strip() if flow else ""
-        if not raw:
-            return default
-        try:
-            return cast(raw)
-        except ValueError:
-            raise ValueError(f"{env} must be {'an integer' if cast is int else 'a number'}, got {env}={raw!r} (action_head={action_head!r})") from None
-
-    samples = pick(flow_samples, "FASTVLA_FLOW_SAMPLES", int, None)
-    select = pick(flow_select, "FASTVLA_FLOW_SELECT", lambda r: r.lower(), None)
-    decay = pick(flow_coherence_decay, "FASTVLA_FLOW_COHERENCE_DECAY", float, None)
-    if decay is not None and not flow:
-        raise ValueError(f"flow_coherence_decay={decay!r} / flow_samples={samples!r} need action_head='flow', got action_head={action_head!r}")
-    samples, select = check_flow_select(samples, select, action_head=action_head, chunk_size=chunk_size, rtc_method=rtc_method)
-    decay = 0.5 if decay is None else decay
-    coherence_weights(max(int(chunk_size), 1), decay)      # (checks the decay)
-    return {"samples": samples, "select": select, "decay": float(decay)}
-
-
-def resolve_flow_noise_draws(flow_noise_draws=None, *, action_head: str) -> int:
-    """-> S, the noise draws per observation of a flow head's training and loss evaluations: the explicit argument, else FASTVLA_FLOW_NOISE_DRAWS, else 1.  The
-    twin is read and checked for a flow head only, like the other FASTVLA_FLOW_* twins.  ValueError, naming both settings and before any engine exists, for
-    an explicit S > 1 with the regression head, a non-integer, or a value outside 1 .. 16."""
-    from fastvla_hip.engine import check_flow_draws
-    if flow_noise_draws is not None:      # an explicit argument is checked whatever the head is
-        try:
-            draws = check_flow_draws(flow_noise_draws)
-        except ValueError:
-            raise ValueError(f"flow_noise_draws must be an integer 1 .. 16. Got flow_noise_draws={flow_noise_draws!r}, action_head={action_head!r}.") from None
-        if draws > 1 and action_head != "flow":
-            raise ValueError("flow_noise_draws > 1 needs action_head='flow' (the regression head draws no noise). "
-                             f"Got flow_noise_draws={draws}, action_head={action_head!r}.")
-        return draws
-    if action_head != "flow":
-        return 1
-    raw = (os.environ.get("FASTVLA_FLOW_NOISE_DRAWS") or "").strip()
-    if not raw:
-        return 1
-    try:
-        return check_flow_draws(int(raw))
-    except ValueError:
-        raise ValueError(f"FASTVLA_FLOW_NOISE_DRAWS must be an integer 1 .. 16. Got FASTVLA_FLOW_NOISE_DRAWS={raw!r}, action_head={action_head!r}.") from None
-
-
-def resolve_prefix_options(flow_prefix_max_delay=None, flow_prefix_delay_dist=None, flow_prefix_delay_rate=None, *, action_head: str, chunk_size: int,
-                           temporal_ensemble_coeff=None) -> Optional[Dict]:
-    """-> fastvla_hip.prefix.check_prefix_config's record {"chunk", "max_delay", "dist", "rate", "thresholds"} or None (off): explicit arguments, else the
-    FASTVLA_FLOW_PREFIX_MAX_DELAY / _DELAY_DIST / _DELAY_RATE twins (read for a flow head only, like the other FASTVLA_FLOW_* twins), else off.
-    flow_prefix_max_delay=False: off whatever the twin says.  ValueError, naming both settings and before any engine exists, for a regression head,
-    chunk_size == 1, a delay that does not fit the chunk, or temporal_ensemble_coeff."""
-    from fastvla_hip import prefix as _prefix
-
-    def pick(arg, env, cast, default):
-        if arg is not None:
-            return arg
-        raw = (os.environ.get(env) or "").strip()
-        if not raw:
-            return default
-        try:
-            return cast(raw)
-        except ValueError:
-            raise ValueError(f"{env} must be {cast.__name__}, got {raw!r}") from None
-
-    D = flow_prefix_max_delay
-    if D is False:
-        return None
-    if D is None:
-        if action_head != "flow":
-            return None
-        D = pick(None, "FASTVLA_FLOW_PREFIX_MAX_DELAY", int, None)
-        if D is None or D == 0:
-            return None
-    dist = str(pick(flow_prefix_delay_dist, "FASTVLA_FLOW_PREFIX_DELAY_DIST", str, "uniform")).lower()
-    rate = pick(flow_prefix_delay_rate, "FASTVLA_FLOW_PREFIX_DELAY_RATE", float, 0.5)
-    return _prefix.check_prefix_config(D, action_head=action_head, chunk_size=chunk_size, temporal_ensemble_coeff=temporal_ensemble_coeff, dist=dist, rate=rate)
-
-
-def resolve_rtc_options(rtc=None, rtc_schedule=None, rtc_max_guidance_weight=None, rtc_execution_horizon=None, *, action_head: str, chunk_size: int,
-                        n_action_steps: int, temporal_ensemble_coeff=None, rtc_method=None, rtc_prefix_steps=None, prefix: Optional[Dict] = None) -> Optional[Dict]:
-    """-> {"schedule", "max_guidance_weight", "execution_horizon"} or None (off): explicit arguments, else the FASTVLA_RTC / FASTVLA_RTC_SCHEDULE /
-    FASTVLA_RTC_MAX_GUIDANCE_WEIGHT / FASTVLA_RTC_EXECUTION_HORIZON twins, else (off, "exp", 5.0, n_action_steps).  The other twins are read and checked
-    only when real-time chunking is on.  ValueError, naming both settings, for rtc with a regression head, with chunk_size == 1, with
-    temporal_ensemble_coeff, or with an execution horizon that does not fit the chunk; for an unknown schedule or a non-positive / non-finite weight."""
-    import math
-    from fastvla_hip.rtc import check_rtc
-
-    def pick(arg, env, cast, default):
-        if arg is not None:
-            return arg
-        raw = (os.environ.get(env) or "").strip()
-        return cast(raw) if raw else default
-
-    on = pick(rtc, "FASTVLA_RTC", lambda r: r.lower() not in ("0", "false", "no", "off"), False)
-    if not on:
-        return None
-    if action_head != "flow":
-        raise ValueError(f"rtc=True needs action_head='flow' (guidance is defined for the flow sampler only). Got rtc={on}, action_head={action_head!r}.")
-    if chunk_size == 1:
-        raise ValueError(f"rtc=True needs chunk_size > 1: there is no overlap between chunks of one step. Got rtc={on}, chunk_size={chunk_size}.")
-    if temporal_ensemble_coeff is not None:
-        raise ValueError("rtc and temporal_ensemble_coeff cannot be combined: one joins chunks by guidance, the other by averaging them. "
-                         f"Got rtc={on}, temporal_ensemble_coeff={temporal_ensemble_coeff}.")
-    # rtc_method (FASTVLA_RTC_METHOD): "guidance" (the default: everything below, on either head width) or "prefix" -- the prefix sampler of a head trained
-    # with flow_prefix_max_delay = D: a re-plan PINS its first min(rtc_prefix_steps, D, K - shift) steps to the previous chunk; no guidance, no schedule, no beta
-    method = str(pick(rtc_method, "FASTVLA_RTC_METHOD", str, "guidance")).lower()
-    if method not in ("guidance", "prefix"):
-        raise ValueError(f"rtc_method must be 'guidance' or 'prefix', got {method!r}")
-    if method == "prefix":
-        if prefix is None:
-            raise ValueError("rtc_method='prefix' needs a head trained with action-prefix conditioning. Got rtc_method='prefix', flow_prefix_max_delay=None.")
-        for name, val in (("rtc_schedule", rtc_schedule), ("rtc_max_guidance_weight", rtc_max_guidance_weight), ("rtc_execution_horizon", rtc_execution_horizon)):
-            if val is not None:
-                raise ValueError(f"{name} belongs to rtc_method='guidance': the prefix sampler has no guidance to shape. Got {name}={val!r}, rtc_method='prefix'.")
-        D = int(prefix["max_delay"])
-        steps = pick(rtc_prefix_steps, "FASTVLA_RTC_PREFIX_STEPS", int, D)
-        if isinstance(steps, bool) or not isinstance(steps, int) or not 0 <= steps <= D:
-            raise ValueError(f"rtc_prefix_steps must be an integer in 0 .. flow_prefix_max_delay. Got rtc_prefix_steps={steps!r}, flow_prefix_max_delay={D}.")
-        return {"method": "prefix", "prefix_steps": int(steps), "max_delay": D}
-    if rtc_prefix_steps is not None:
-        raise ValueError(f"rtc_prefix_steps needs rtc_method='prefix'. Got rtc_prefix_steps={rtc_prefix_steps!r}, rtc_method={method!r}.")
-    schedule = str(pick(rtc_schedule, "FASTVLA_RTC_SCHEDULE", str, "exp")).lower()
-    beta = pick(rtc_max_guidance_weight, "FASTVLA_RTC_MAX_GUIDANCE_WEIGHT", float, 5.0)
-    s = pick(rtc_execution_horizon, "FASTVLA_RTC_EXECUTION_HORIZON", int, n_action_steps)
-    try:
-        beta = float(beta)
-    except (TypeError, ValueError):
-        raise ValueError(f"rtc_max_guidance_weight must be a finite number > 0, got {beta!r}") from None
-    if not math.isfinite(beta) or beta <= 0.0:
-        raise ValueError(f"rtc_max_guidance_weight must be a finite number > 0, got {beta!r}")
-    if isinstance(s, int) and not isinstance(s, bool) and s > chunk_size:
-        raise ValueError(f"rtc_execution_horizon must not exceed chunk_size (inference_delay + execution_horizon <= chunk_size). "
-                         f"Got rtc_execution_horizon={s}, chunk_size={chunk_size}.")
-    check_rtc(chunk_size, 0, s, schedule)
-    return {"schedule": schedule, "max_guidance_weight": beta, "execution_horizon": int(s)}
-
-
-class FastVLAPolicy(nn.Module, EmaMixin):
+class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
     config_class = FastVLAConfig
     name = "fastvla"
 
@@ -351,33 +103,23 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         for a regression head, S outside 1 .. 16, a select name with S = 1, "coherent" with chunk_size = 1, rtc_method="guidance" with S > 1."""
         super().__init__()
         self.config = config or FastVLAConfig()
-        opts = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
-        self.n_action_steps = opts["n_action_steps"]
-        self.temporal_ensemble_coeff: Optional[float] = opts["temporal_ensemble_coeff"]
+        self.options = resolve_policy_options(      # (every option is resolved and refused here, before any engine exists)
+            chunk_size=chunk_size, n_action_steps=n_action_steps, action_loss=action_loss, action_loss_beta=action_loss_beta,
+            temporal_ensemble_coeff=temporal_ensemble_coeff, action_dim_weights=action_dim_weights, action_step_weights=action_step_weights,
+            action_head=action_head, flow_steps=flow_steps, flow_time_dim=flow_time_dim, flow_time_dist=flow_time_dist, flow_seed=flow_seed, rtc=rtc,
+            rtc_schedule=rtc_schedule, rtc_max_guidance_weight=rtc_max_guidance_weight, rtc_execution_horizon=rtc_execution_horizon,
+            flow_noise_draws=flow_noise_draws, flow_prefix_max_delay=flow_prefix_max_delay, flow_prefix_delay_dist=flow_prefix_delay_dist,
+            flow_prefix_delay_rate=flow_prefix_delay_rate, rtc_method=rtc_method, rtc_prefix_steps=rtc_prefix_steps, flow_solver=flow_solver,
+            flow_samples=flow_samples, flow_select=flow_select, flow_coherence_decay=flow_coherence_decay)
+        o = self.options
+        self.n_action_steps = o.chunk["n_action_steps"]
+        self.temporal_ensemble_coeff: Optional[float] = o.chunk["temporal_ensemble_coeff"]
+        self.action_head, self.flow_noise_draws, self.flow_prefix, self.rtc = o.action_head, o.noise_draws, o.prefix, o.rtc
+        self.flow_samples, self.flow_select = o.samples, o.select
         self._ensembler = None      # fastvla_hip.TemporalEnsembler, created on the first select_action after reset()
         self._action_queue: deque = deque()
-        fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist)
-        self.action_head = fopts["action_head"]
-        self.flow_noise_draws: int = resolve_flow_noise_draws(flow_noise_draws, action_head=self.action_head)      # (before any engine exists)
-        solver = resolve_flow_solver(flow_solver, action_head=self.action_head)      # (likewise)
-        popts = resolve_prefix_options(flow_prefix_max_delay, flow_prefix_delay_dist, flow_prefix_delay_rate, action_head=self.action_head,      # (likewise)
-                                       chunk_size=opts["chunk_size"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
-        self.flow_prefix: Optional[Dict] = popts
-        ropts = resolve_rtc_options(rtc, rtc_schedule, rtc_max_guidance_weight, rtc_execution_horizon, action_head=self.action_head,      # (before any engine exists)
-                                    chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"],
-                                    rtc_method=rtc_method, rtc_prefix_steps=rtc_prefix_steps, prefix=popts)
-        sopts = resolve_flow_samples(flow_samples, flow_select, flow_coherence_decay, action_head=self.action_head, chunk_size=opts["chunk_size"],      # (likewise)
-                                     rtc_method=None if ropts is None else ropts.get("method", "guidance"))
-        self.flow_samples, self.flow_select = sopts["samples"], sopts["select"]
-        self.model = FastVLMWithExpert(self.config, chunk_size=opts["chunk_size"], action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"],
-                                       flow_steps=fopts["steps"], flow_seed=flow_seed, flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver,
-                                       flow_samples=sopts["samples"], flow_select=sopts["select"], flow_coherence_decay=sopts["decay"])
-        if opts["dim_weights"] is not None or opts["step_weights"] is not None:
-            self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
-        self.rtc = ropts
         self._rtc_served = 0      # actions served since the last chunk was planned: the shift of the next guided plan
-        if ropts is not None:
-            self.model.configure_rtc(ropts)
+        self.model = FastVLMWithExpert(self.config, o)
         self.processor = FastVLAProcessor(self.config, self.model.backbone)
         self._opt_state = None
         self._unfrozen = None   # training/unfrozen.py UnfrozenState once enable_backbone_training() ran
@@ -533,27 +275,6 @@ class FastVLAPolicy(nn.Module, EmaMixin):
     def chunk_size(self) -> int:
         return self.model.chunk_size
 
-    @property
-    def flow_steps(self) -> int:
-        """steps of the chosen solver (flow_solver) in a flow head's samplers (ignored by the regression head); may be changed at any time"""
-        return self.model.flow_steps
-
-    @flow_steps.setter
-    def flow_steps(self, n: int) -> None:
-        if int(n) != n or n < 1:
-            raise ValueError(f"flow_steps must be an integer >= 1, got {n}")
-        self.model.flow_steps = int(n)
-
-    @property
-    def flow_solver(self) -> str:
-        """"euler" | "midpoint" | "heun" | "rk4": the integrator of every sampling route of a flow head.  A policy built with a higher-order solver may switch
-        among all four at any time; one built with "euler" raises ValueError (the rows a higher-order solver works over were not reserved)"""
-        return self.model.flow_solver
-
-    @flow_solver.setter
-    def flow_solver(self, name: str) -> None:
-        self.model.flow_solver = name
-
     @torch.inference_mode()
     def select_action_chunk(self, image: torch.Tensor, state: torch.Tensor, task: str, device: torch.device, prev_chunk: Optional[torch.Tensor] = None,
                             inference_delay: Optional[int] = None, num_samples: Optional[int] = None) -> torch.Tensor:
@@ -614,21 +335,6 @@ class FastVLAPolicy(nn.Module, EmaMixin):
         chunk = self.model.sample_multi(pooled, states, shift=shift)
         self._rtc_served = 0
         return chunk.reshape(self.model.chunk_size, self.config.action_dim)
-
-    @property
-    def last_candidates(self) -> Optional[torch.Tensor]:
-        """flow_samples > 1: (B, S, K, A), the candidates of the last sampling call in normalised space, on the device; None before the first"""
-        return self.model.last_candidates
-
-    @property
-    def last_choice(self) -> Optional[torch.Tensor]:
-        """flow_samples > 1: (B) int32, the index of the candidate the last sampling call chose, on the device"""
-        return self.model.last_choice
-
-    @property
-    def last_sample_spread(self) -> Optional[torch.Tensor]:
-        """flow_samples > 1: (B, K, A), the standard deviation of the last call's candidates per element (normalised space), on the device"""
-        return self.model.last_sample_spread
 
     @property
     def last_chunk_normalised(self) -> Optional[torch.Tensor]:

@@ -36,6 +36,8 @@ from torch import Tensor
 
 from ..fastvla.configuration_fastvla import FastVLAConfig as CoreFastVLAConfig
 from ..fastvla.fastvlm_with_expert import FastVLMWithExpert
+from ..fastvla.flow_surface import FlowSurfaceMixin
+from ..fastvla.options import POLICY_KEYWORDS, resolve_policy_options
 from ._lerobot_compat import ACTION, FeatureType, PreTrainedPolicy
 from .configuration_fastvla import FastVLAConfig
 
@@ -44,7 +46,7 @@ _CORE_FIELDS = ("vlm_model_name", "bootstrap_model_name", "state_dim", "action_d
                 "resize_with_padding", "image_size", "pad_value", "add_trailing_newline")
 
 
-class FastVLAPolicy(PreTrainedPolicy):
+class FastVLAPolicy(PreTrainedPolicy, FlowSurfaceMixin):
     config_class = FastVLAConfig
     name = "fastvla"
 
@@ -54,67 +56,17 @@ class FastVLAPolicy(PreTrainedPolicy):
         self.config = config
         self._state_key, self._image_keys = self._resolve_input_keys()
         self._infer_io_dims_from_features()
-        from ..fastvla.modeling_fastvla import (resolve_chunk_options, resolve_flow_noise_draws, resolve_flow_options, resolve_flow_samples, resolve_flow_solver,
-                                                resolve_prefix_options, resolve_rtc_options)
-        opts = resolve_chunk_options(chunk_size=config.chunk_size, n_action_steps=config.n_action_steps,      # (the loss kind: its environment twins)
-                                     temporal_ensemble_coeff=kwargs.get("temporal_ensemble_coeff"), action_dim_weights=kwargs.get("action_dim_weights"),
-                                     action_step_weights=kwargs.get("action_step_weights"))
-        self.temporal_ensemble_coeff = opts["temporal_ensemble_coeff"]
-        # the flow-matching head (FastVLAPolicy(config, action_head="flow", flow_steps=, flow_time_dim=, flow_time_dist=, flow_seed=) or the FASTVLA_ACTION_HEAD /
-        # FASTVLA_FLOW_* twins; the registered config gains no field): the core policy's docstring has the semantics -- predict_action_chunk / select_action
-        # sample, forward(batch) trains the velocity.  flow_noise_draws=S (FASTVLA_FLOW_NOISE_DRAWS; no config field): S noise draws per observation in one
-        # forward(batch), the mean loss and gradient of S single-draw calls for one backbone pass
-        fopts = resolve_flow_options(kwargs.get("action_head"), kwargs.get("flow_steps"), kwargs.get("flow_time_dim"), kwargs.get("flow_time_dist"))
-        self.action_head = fopts["action_head"]
-        self.flow_noise_draws: int = resolve_flow_noise_draws(kwargs.get("flow_noise_draws"), action_head=self.action_head)
-        # flow_solver= (FASTVLA_FLOW_SOLVER; no config field): the integrator of every sampling route, a property of the run
-        solver = resolve_flow_solver(kwargs.get("flow_solver"), action_head=self.action_head)
-        # real-time chunking (FastVLAPolicy(config, rtc=True, rtc_schedule=, rtc_max_guidance_weight=, rtc_execution_horizon=) or the FASTVLA_RTC* twins; no
-        # config field): re-plans of a flow head are sampled guided by the rest of the previous chunk, for all B environments of the batch in one call
-        popts = resolve_prefix_options(kwargs.get("flow_prefix_max_delay"), kwargs.get("flow_prefix_delay_dist"), kwargs.get("flow_prefix_delay_rate"),
-                                       action_head=self.action_head, chunk_size=opts["chunk_size"], temporal_ensemble_coeff=opts["temporal_ensemble_coeff"])
-        self.flow_prefix = popts
-        ropts = resolve_rtc_options(kwargs.get("rtc"), kwargs.get("rtc_schedule"), kwargs.get("rtc_max_guidance_weight"), kwargs.get("rtc_execution_horizon"),
-                                    action_head=self.action_head, chunk_size=opts["chunk_size"], n_action_steps=opts["n_action_steps"],
-                                    temporal_ensemble_coeff=opts["temporal_ensemble_coeff"], rtc_method=kwargs.get("rtc_method"),
-                                    rtc_prefix_steps=kwargs.get("rtc_prefix_steps"), prefix=popts)
-        # flow_samples= / flow_select= / flow_coherence_decay= (FASTVLA_FLOW_SAMPLES / _SELECT / _COHERENCE_DECAY; no config field): S candidates per environment
-        # in one sampler call, one chosen on the device; a property of the run
-        sopts = resolve_flow_samples(kwargs.get("flow_samples"), kwargs.get("flow_select"), kwargs.get("flow_coherence_decay"), action_head=self.action_head,
-                                     chunk_size=opts["chunk_size"], rtc_method=None if ropts is None else ropts.get("method", "guidance"))
-        self.flow_samples, self.flow_select = sopts["samples"], sopts["select"]
+        # no option below has a field in the registered config (its schema is pinned): they come as keywords or from their FASTVLA_* twins, and the core
+        # policy's docstring has their semantics.  Unknown keywords are ignored; the loss kind comes from its twins (or set_action_loss) only
+        given = {k: v for k, v in kwargs.items() if k in POLICY_KEYWORDS}
+        self.options = o = resolve_policy_options(**{**given, "chunk_size": config.chunk_size, "n_action_steps": config.n_action_steps, "action_loss": None,
+                                                     "action_loss_beta": None})
+        self.temporal_ensemble_coeff = o.chunk["temporal_ensemble_coeff"]
+        self.action_head, self.flow_noise_draws, self.flow_prefix, self.rtc = o.action_head, o.noise_draws, o.prefix, o.rtc
+        self.flow_samples, self.flow_select = o.samples, o.select
         self._ensembler = None      # fastvla_hip.TemporalEnsembler over the B environments of select_action's batch, created on the first call after reset()
-        self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), chunk_size=opts["chunk_size"],
-                                       action_loss=opts["loss"], action_loss_beta=opts["beta"], flow=fopts["flow"], flow_steps=fopts["steps"],
-                                       flow_seed=kwargs.get("flow_seed"), flow_noise_draws=self.flow_noise_draws, flow_prefix=popts, flow_solver=solver,
-                                       flow_samples=sopts["samples"], flow_select=sopts["select"], flow_coherence_decay=sopts["decay"])
-        if opts["dim_weights"] is not None or opts["step_weights"] is not None:
-            self.model.set_action_loss_weights(opts["dim_weights"], opts["step_weights"])
-        self.rtc = ropts
-        if ropts is not None:
-            self.model.configure_rtc(ropts)
+        self.model = FastVLMWithExpert(CoreFastVLAConfig(**{k: getattr(config, k) for k in _CORE_FIELDS}), o)
         self.reset()
-
-    @property
-    def flow_steps(self) -> int:
-        """steps of the chosen solver (flow_solver) in a flow head's samplers (ignored by the regression head); may be changed at any time"""
-        return self.model.flow_steps
-
-    @flow_steps.setter
-    def flow_steps(self, n: int) -> None:
-        if int(n) != n or n < 1:
-            raise ValueError(f"flow_steps must be an integer >= 1, got {n}")
-        self.model.flow_steps = int(n)
-
-    @property
-    def flow_solver(self) -> str:
-        """"euler" | "midpoint" | "heun" | "rk4": the integrator of every sampling route of a flow head.  A policy built with a higher-order solver may switch
-        among all four at any time; one built with "euler" raises ValueError (the rows a higher-order solver works over were not reserved)"""
-        return self.model.flow_solver
-
-    @flow_solver.setter
-    def flow_solver(self, name: str) -> None:
-        self.model.flow_solver = name
 
     def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
         """the loss forward(batch) evaluates from now on: "mse" | "l1" | "smooth_l1" (beta)"""
@@ -207,26 +159,6 @@ class FastVLAPolicy(PreTrainedPolicy):
     def _predict_actions(self, batch: dict[str, Tensor]) -> Tensor:
         images, states, tasks = self._prepare_inputs(batch)
         return self.model(images, states, tasks, device=images.device)
-
-    @property
-    def last_chunk_normalised(self):
-        """rtc: (B, K, A) copy of the chunks planned last, in normalised space; None before the first plan"""
-        return self.model.last_chunk_normalised
-
-    @property
-    def last_candidates(self):
-        """flow_samples > 1: (B, S, K, A), the candidates of the last sampling call in normalised space, on the device; None before the first"""
-        return self.model.last_candidates
-
-    @property
-    def last_choice(self):
-        """flow_samples > 1: (B) int32, the candidate the last sampling call chose per environment, on the device"""
-        return self.model.last_choice
-
-    @property
-    def last_sample_spread(self):
-        """flow_samples > 1: (B, K, A), the standard deviation of the last call's candidates per element (normalised space), on the device"""
-        return self.model.last_sample_spread
 
     def _coherent_plan(self, batch, *, shift: int) -> Tensor:
         """flow_select="coherent" without rtc: the candidate that best continues the chunks planned last (read `shift` steps ahead), for all B environments"""

@@ -15,7 +15,8 @@ from __future__ import annotations
 
 import os
 import re
-from dataclasses import dataclass
+from copy import copy
+from dataclasses import dataclass, replace
 from pathlib import Path
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -23,6 +24,7 @@ import torch
 from torch import nn
 
 from fastvla_hip import FastVLAEngine, FastVLAHipError, arch as fv_arch, weights as fv_weights
+from fastvla_hip.head_spec import LAYOUT_FIELDS, HeadSpec
 
 from ..tokenization import SyntheticTokenizer
 
@@ -183,16 +185,7 @@ class FastVLMBackbone(nn.Module):
         self._engine: Optional[FastVLAEngine] = None
         self._weights_override: Optional[Dict[str, Tensor]] = None   # load_backbone_state(): a checkpoint's own VLM tensors
         self._io_norm: Optional[dict] = None   # dataset statistics folded into the head kernels (set_io_normalization)
-        self._head_dims = dict(state_dim=14, action_dim=14, hidden_dim=1024, fusion_dim=1024)
-        self._head_loss = dict(kind="mse", beta=1.0, chunk=1)   # configure_head_loss: the fused loss of the head backward and the chunk length K
-        self._head_loss_weights: Optional[dict] = None          # configure_head_loss_weights: {"dim", "step"} of the weighted chunk loss, None = off
-        self._head_flow: Optional[dict] = None                  # configure_head_flow: FastVLAEngine.set_head_flow's arguments, None = the regression head
-        self._head_flow_draws = 1                               # configure_head_flow_draws: FastVLAEngine.set_head_flow_draws' argument, 1 = one draw per observation
-        self._head_flow_guidance: Optional[dict] = None         # configure_head_flow_guidance: FastVLAEngine.set_head_flow_guidance's arguments, None = off
-        self._head_flow_prefix: Optional[dict] = None           # configure_head_flow_prefix: {"chunk", "max_delay", "thresholds", "dist", "rate"}, None = off
-        self._head_flow_solver = "euler"                        # configure_head_flow_solver: FastVLAEngine.set_head_flow_solver's argument
-        self._head_flow_samples: Optional[dict] = None          # configure_head_flow_samples: FastVLAEngine.set_head_flow_samples' arguments, None = one sample
-        self._head_flow_solver_rows = False                     # True once a higher-order solver was configured: an engine is built with its two rows reserved
+        self.head_spec = HeadSpec()   # configure_head: everything the engine's action expert is configured with (fastvla_hip/head_spec.py)
         self._max_batch = int(os.environ.get("FASTVLA_MAX_BATCH", "64"))
         print(f"[FastVLMBackbone] expected (S,S) = ({self.expected_size},{self.expected_size})")
 
@@ -260,90 +253,63 @@ class FastVLMBackbone(nn.Module):
     _infer_size_from_tower_name = staticmethod(infer_size_from_tower_name)
 
     # ------------------------------------------------------------------ engine
-    def configure_head(self, *, state_dim: int, action_dim: int, hidden_dim: int, fusion_dim: int) -> None:
-        self._head_dims = dict(state_dim=state_dim, action_dim=action_dim, hidden_dim=hidden_dim, fusion_dim=fusion_dim)
+    def configure_head(self, spec: Optional[HeadSpec] = None, **dims) -> None:
+        """The action expert of every engine built from now on: a HeadSpec, or the widths alone (state_dim=, action_dim=, hidden_dim=, fusion_dim=) for a
+        plain regression head.  The engine is rebuilt on its next use; a built engine refuses a spec whose flow mode, prefix, draws or samples differ
+        (RuntimeError: the head's layout and the workspaces were sized by them)."""
+        spec = HeadSpec(dims=dims) if spec is None else spec
+        if self._engine is not None:
+            for name, refusal in LAYOUT_FIELDS:
+                if getattr(spec, name) != getattr(self.head_spec, name):
+                    raise RuntimeError(refusal)
+        self.head_spec = spec
         self._engine = None
 
-    def configure_head_flow(self, flow: Optional[dict]) -> None:
-        """Flow mode of the action expert (FastVLAEngine.set_head_flow's keyword arguments; None = off).  The head's layout depends on it, so it is fixed
-        before the engine exists."""
-        if self._engine is not None and flow != self._head_flow:
-            raise RuntimeError("configure_head_flow: the engine is already built (the head's layout and the workspace depend on the mode)")
-        self._head_flow = None if flow is None else dict(flow)
-
-    def configure_head_flow_prefix(self, prefix: Optional[dict]) -> None:
-        """Action-prefix conditioning of a flow head (fastvla_hip.prefix.check_prefix_config's result; None = off).  fusion.0's width, the saved activations
-        and the workspaces depend on it, so it is fixed before the engine is built."""
-        if prefix is not None and self._head_flow is None:
-            raise ValueError(f"flow_prefix_max_delay={prefix.get('max_delay')} needs action_head='flow'")
-        if self._engine is not None and prefix != self._head_flow_prefix:
-            raise RuntimeError("configure_head_flow_prefix: the engine is already built (the head's layout and the workspace depend on the mode)")
-        self._head_flow_prefix = None if prefix is None else dict(prefix)
-
-    def configure_head_flow_draws(self, draws: int = 1) -> None:
-        """Noise draws per observation of a flow head's training forms (FastVLAEngine.set_head_flow_draws; 1 = off).  The saved activations and the
-        workspaces depend on it, so it is fixed before the engine exists."""
-        from fastvla_hip.engine import check_flow_draws
-        draws = check_flow_draws(draws)
-        if draws > 1 and self._head_flow is None:
-            raise ValueError(f"flow_noise_draws={draws} needs action_head='flow' (the regression head has no noise to draw)")
-        if self._engine is not None and draws != self._head_flow_draws:
-            raise RuntimeError("configure_head_flow_draws: the engine is already built (the saved activations and the workspaces depend on the number of draws)")
-        self._head_flow_draws = draws
-
+    # The four settings that may change on a built policy: each replaces its field (HeadSpec checks it) and tells an engine that already exists at once.
+    # They are for changes of the configuration and must stay off every per-call path: replace() runs ALL of HeadSpec's checks again (what changes per call,
+    # the guidance weights of another delay or horizon, goes straight to FastVLAEngine.set_head_flow_guidance).
     def configure_head_flow_solver(self, name: str = "euler") -> None:
-        """The integrator of the flow samplers (FastVLAEngine.set_head_flow_solver).  Kept for the engine's construction, where a higher-order solver reserves
-        its two rows before any workspace is bound; an engine that already exists is told at once (the library refuses a FIRST higher-order solver then)."""
-        from fastvla_hip.engine import check_flow_solver
-        name = check_flow_solver(name)
-        if name != "euler" and self._head_flow is None:
-            raise ValueError(f"flow_solver={name!r} needs action_head='flow' (the regression head integrates nothing)")
-        if self._engine is not None and (name != "euler" or self._engine.head_flow_solver != "euler"):
-            self._engine.set_head_flow_solver(name)
-        self._head_flow_solver = name
-        self._head_flow_solver_rows = self._head_flow_solver_rows or name != "euler"
-
-    def configure_head_flow_samples(self, samples: Optional[dict]) -> None:
-        """Several samples per observation (FastVLAEngine.set_head_flow_samples' keyword arguments; None = one).  The sampler's rows in the workspace grow
-        with max_samples, so it is fixed before the engine is built."""
-        if self._engine is not None and samples != self._head_flow_samples:
-            raise RuntimeError("configure_head_flow_samples: the engine is already built (the sampler's rows in the workspace depend on the number of samples)")
-        self._head_flow_samples = None if samples is None else dict(samples)
+        """The integrator of the flow samplers (FastVLAEngine.set_head_flow_solver).  The library refuses a FIRST higher-order solver on a built engine."""
+        spec = replace(self.head_spec, solver=name)
+        if self._engine is not None and (spec.solver != "euler" or self._engine.head_flow_solver != "euler"):
+            self._engine.set_head_flow_solver(spec.solver)
+        self.head_spec = spec
 
     def configure_head_flow_guidance(self, guidance: Optional[dict]) -> None:
-        """Guidance of the flow sampler (FastVLAEngine.set_head_flow_guidance's keyword arguments; None = off).  Kept for the engine's construction, where it
-        is applied before any workspace is bound; an engine that already exists is told at once (the library refuses a FIRST configuration then)."""
-        self._head_flow_guidance = None if guidance is None else dict(guidance)
+        """Guidance of the flow sampler (FastVLAEngine.set_head_flow_guidance's keyword arguments; None = off).  The library refuses a FIRST configuration on
+        a built engine."""
+        self.head_spec = replace(self.head_spec, guidance=None if guidance is None else dict(guidance))
         if self._engine is not None and (guidance is not None or self._engine.head_flow_guidance is not None):
-            self._engine.set_head_flow_guidance(**(self._head_flow_guidance or {"step_weights": None}))
+            self._engine.set_head_flow_guidance(**(self.head_spec.guidance or {"step_weights": None}))
 
     def configure_head_loss(self, kind: str = "mse", beta: float = 1.0, chunk: int = 1) -> None:
-        """Action chunks: the head's action_dim (configure_head) is chunk * A, and `kind` ("mse" | "l1" | "smooth_l1", beta for the last) is the loss the
-        fused head backward evaluates (FastVLAEngine.set_head_loss).  The defaults leave the library as it is."""
+        """Action chunks: the head's action_dim is chunk * A, and `kind` ("mse" | "l1" | "smooth_l1", beta for the last) is the loss the fused head backward
+        evaluates (FastVLAEngine.set_head_loss).  A new chunk length drops the loss weights (sized for the previous one) and re-tiles the folded statistics."""
         from fastvla_hip.engine import check_head_loss
-        kind, beta, chunk = check_head_loss(kind, beta, chunk, self._head_dims["action_dim"])
-        rechunk = chunk != self._head_loss["chunk"]
-        self._head_loss = dict(kind=kind, beta=beta, chunk=chunk)
+        kind, beta, chunk = check_head_loss(kind, beta, chunk, self.head_spec.dims["action_dim"])
+        rechunk = chunk != self.head_spec.loss["chunk"]
+        # (a copy with the field assigned, not replace(): this setter checks the loss alone -- what else hangs on the chunk length, a prefix, is the
+        # engine's to refuse; a spec the caller still holds stays as it was)
+        self.head_spec = spec = copy(self.head_spec)
+        spec.loss = dict(kind=kind, beta=beta, chunk=chunk)
         if rechunk:
-            self._head_loss_weights = None      # (sized for the previous chunk length)
+            spec.loss_weights = None      # (sized for the previous chunk length)
         if self._engine is not None:
-            self._engine.set_head_loss(**self._head_loss)
+            self._engine.set_head_loss(**self.head_spec.loss)
             if rechunk and self._io_norm is not None:
                 self._engine.set_io_norm(**self._io_norm_for_engine())
 
     def configure_head_loss_weights(self, dim_w=None, step_w=None) -> None:
-        """Per-dimension (A) and per-step (K) weights of the fused loss (FastVLAEngine.set_head_loss_weights); both None switches weighting off.  Checked here,
-        on the host, before any library call: ValueError for a wrong length or a negative / non-finite value."""
-        from fastvla_hip.engine import check_loss_weights
-        K = self._head_loss["chunk"]
-        self._head_loss_weights = check_loss_weights(dim_w, step_w, self._head_dims["action_dim"] // K, K)
+        """Per-dimension (A) and per-step (K) weights of the fused loss (FastVLAEngine.set_head_loss_weights); both None switches weighting off.  Checked on
+        the host, before any library call: ValueError for a wrong length or a negative / non-finite value."""
+        self.head_spec = replace(self.head_spec, loss_weights={"dim": dim_w, "step": step_w})
         if self._engine is not None:
-            w = self._head_loss_weights or {"dim": None, "step": None}
+            w = self.head_spec.loss_weights or {"dim": None, "step": None}
             self._engine.set_head_loss_weights(w["dim"], w["step"])
 
     def _io_norm_for_engine(self) -> dict:
         """the folded statistics as the head kernels index them: the action vectors are A long in the state dict and tiled over the K steps of a chunk here"""
-        io, K = dict(self._io_norm or {}), self._head_loss["chunk"]
+        io, K = dict(self._io_norm or {}), self.head_spec.loss["chunk"]
         if io and K > 1:
             for k in ("action_mean", "action_std"):
                 io[k] = torch.as_tensor(io[k], dtype=torch.float32).detach().cpu().reshape(-1).repeat(K)
@@ -376,7 +342,7 @@ class FastVLMBackbone(nn.Module):
 
             def build(p: int) -> FastVLAEngine:
                 e = FastVLAEngine(model, device=dev, max_batch=self._max_batch, max_text_tokens=self.config.tokenizer_max_length,
-                                  tower_microbatch=int(os.environ.get("FASTVLA_TOWER_MICROBATCH", "0")), llm_precision=p, **self._head_dims)
+                                  tower_microbatch=int(os.environ.get("FASTVLA_TOWER_MICROBATCH", "0")), llm_precision=p, **self.head_spec.dims)
                 try:
                     if kind == "state":
                         e.load_weights(self._weights_override)
@@ -407,24 +373,7 @@ class FastVLMBackbone(nn.Module):
                 warnings.warn(f"llm_precision={prec} refused for '{self.config.model_id}' ({exc}); falling back to llm_precision=1 "
                               "(split-bf16 operands: no range limit, 2x the decoder's MFMA work)")
                 eng = build(1)
-            if self._head_flow is not None:      # (first: before any workspace is bound)
-                eng.set_head_flow(**self._head_flow)
-                if getattr(self, "_head_flow_prefix", None) is not None:
-                    px = self._head_flow_prefix
-                    eng.set_head_flow_prefix(px["chunk"], px["max_delay"], thresholds=px["thresholds"], dist=px["dist"], rate=px["rate"])
-                if getattr(self, "_head_flow_draws", 1) > 1:
-                    eng.set_head_flow_draws(self._head_flow_draws)
-                if getattr(self, "_head_flow_guidance", None) is not None:
-                    eng.set_head_flow_guidance(**self._head_flow_guidance)
-                if getattr(self, "_head_flow_samples", None) is not None:
-                    eng.set_head_flow_samples(**self._head_flow_samples)
-                if getattr(self, "_head_flow_solver_rows", False):      # (a policy switched back to Euler keeps its rows: it may switch again)
-                    eng.set_head_flow_solver(self._head_flow_solver if self._head_flow_solver != "euler" else "midpoint")
-                    eng.set_head_flow_solver(self._head_flow_solver)
-            if self._head_loss != dict(kind="mse", beta=1.0, chunk=1):
-                eng.set_head_loss(**self._head_loss)
-            if self._head_loss_weights is not None:
-                eng.set_head_loss_weights(self._head_loss_weights["dim"], self._head_loss_weights["step"])
+            self.head_spec.apply(eng)
             if self._io_norm is not None:
                 eng.set_io_norm(**self._io_norm_for_engine())
             self._engine = eng
