@@ -340,6 +340,32 @@ int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t see
  * Allowed only in flow mode, BEFORE fv_bind_workspace and before any fv_train_*_begin (FV_ERR_STATE otherwise); FV_ERR_ARG, changing nothing, outside 1 .. 16. */
 #define FV_FLOW_DRAWS_MAX 16
 int fv_head_set_flow_draws(fv_handle* h, int draws);
+/* The distribution of the training time, beyond fv_head_set_flow's two: every drawn t becomes t = t_lo + (t_hi - t_lo) tau with tau = F^-1(u), u taken from the
+ * ONE 24-bit uniform the noising kernel already draws (k = x >> 8 of the group-0 Philox block; u = k 2^-24 in double).  Nothing is rejected and nothing loops on
+ * the random stream: a row's draws still depend on (seed, offset, row) alone, and eps, u_out, the prefix delay and the dropout stream do not move.
+ *     dist 0 uniform: tau = u.     dist 2 Beta(a, b): tau = I^-1_u(a, b), the inverse regularised incomplete beta function, evaluated in double.
+ *     dist 1 logit-normal: tau = sigmoid(a + b n) with fv_head_set_flow's Box-Muller n and its bits; stratified: n = Phi^-1(u), and u = 0 gives tau = 0.
+ *     stratify (with S = fv_head_set_flow_draws > 1): draw s takes the s-th of S equal-probability strata, u = (s + k 2^-24) / S.  With S = 1 it does nothing.
+ * t is formed in double and rounded to fp32 once.  pi0 / SmolVLA: {2, 1.5, 1.0, 0.001, 1.0, 0}.  Explicit t buffers still replace every draw.
+ * NULL returns the handle to what fv_head_set_flow's own time_dist / dist_a / dist_b say, bit for bit; fv_head_set_flow (NULL or a spec) resets it.  A handle
+ * that never calls this launches what it always launched.  No size depends on it: allowed at any time in flow mode (FV_ERR_STATE when flow mode is off).
+ * FV_ERR_ARG, changing nothing, for an unknown dist, a non-finite field, a Beta a or b outside [0.25, 32], a range that is not 0 <= t_lo < t_hi <= 1,
+ * stratify not 0 or 1.  A hipGraph captured over a noising launch keeps the setting of its capture. */
+typedef struct fv_head_flow_time_spec {
+  int32_t dist;       /* 0 uniform, 1 logit-normal (a + b n), 2 Beta(alpha = a, beta = b) */
+  float a, b;
+  float t_lo, t_hi;   /* t = t_lo + (t_hi - t_lo) * tau, 0 <= t_lo < t_hi <= 1 */
+  int32_t stratify;   /* 0 | 1: draw s of S takes the s-th of S equal-probability strata */
+} fv_head_flow_time_spec;
+int fv_head_set_flow_time(fv_handle* h, const fv_head_flow_time_spec* spec);
+/* The velocity error as a function of t: out_dev (n_buckets, 2) DEVICE floats, per bucket { sum over non-padded elements of (actions - targets)^2, the number
+ * of those elements }; an empty bucket reads (0, 0).  actions = v, targets = u: (R, action_dim) device f32, t: (R) device f32, R = B head rows (S B with
+ * fv_head_set_flow_draws, as fv_head_loss_per_dim).  Row r falls into bucket min(n_buckets - 1, (int)(t n_buckets)), t clamped to [0, 1].  Uses the handle's
+ * chunk and (B, K) mask, never the loss kind or the weights.  One block per bucket, rows in ascending order, fixed-order sums, no atomics: two calls give the
+ * same bits.  Asynchronous on s, allocates nothing.  FV_ERR_STATE when flow mode is off, FV_ERR_ARG for a null pointer, B < 1 or n_buckets outside 1 .. 64;
+ * nothing is enqueued then. */
+#define FV_LOSS_TIME_BUCKETS_MAX 64
+int fv_head_loss_per_time(fv_handle* h, const float* actions, const float* targets, const float* t, int B, int n_buckets, float* out_dev, fv_stream s);
 /* Inference: n_steps Euler steps from x_1 = noise (B, action_dim; NULL: the normals fv_head_flow_prepare would draw for (seed, offset)) to actions
  * (B, action_dim), un-normalised on the last step when fv_head_set_io_norm is on.  The state branch and the part of fusion.0 that does not depend on t,
  * c = W[:, :llm_hidden + hidden_dim] . [pooled | s] + b, are computed ONCE per call; every step then runs three launches that touch only fusion.0's last

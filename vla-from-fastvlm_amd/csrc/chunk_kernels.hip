@@ -2,6 +2,7 @@
 //   chunk_loss_kernel<WEIGHTED> + its fold   pad-masked L1 / smooth-L1 / MSE over (B, K, A), optionally weighted per dimension and step
 //                                            (fv_head_set_loss / _mask / _weights; launch_head_backward runs it when HeadLoss asks for it)
 //   loss_per_dim_kernel                      mean |a - t| per action dimension (fv_head_loss_per_dim)
+//   loss_per_time_kernel                     the flow head's squared velocity error and element count per time bucket (fv_head_loss_per_time)
 //   ensemble_step_kernel                     the temporal-ensembling ring (fv_ensemble_step)
 #include "kernels.h"
 
@@ -157,6 +158,36 @@ __global__ __launch_bounds__(256) void loss_per_dim_kernel(const float* __restri
   }
 }
 
+// block = one time bucket (fv_head_loss_per_time): out[j] = { sum of (a - u)^2, count } over the non-padded elements of the rows whose t falls into bucket j.
+// Every block walks the rows in ascending order (t[r] is one uniform load), a thread sums its elements of the bucket's rows in that order, then a fixed-order
+// fold (no atomics).  A thread counts its elements in an integer; the fold of the counts is exact in fp32 below 2^24 elements per bucket
+__global__ __launch_bounds__(256) void loss_per_time_kernel(const float* __restrict__ a, const float* __restrict__ u, const float* __restrict__ t,
+                                                             const uint8_t* __restrict__ pad, float* __restrict__ out, int R, int B, int da, int K, int nb) {
+  __shared__ float red[2][4];
+  const int j = blockIdx.x, A = da / K;
+  float sq = 0.f;
+  unsigned cnt = 0;
+  for (int r = 0; r < R; ++r) {
+    const float tc = fminf(fmaxf(t[r], 0.f), 1.f);
+    if (min(nb - 1, (int)(tc * (float)nb)) != j) continue;
+    const uint8_t* pr = pad ? pad + (size_t)(r % B) * K : nullptr;   // (the draws of a flow head share their observation's mask)
+    for (int i = threadIdx.x; i < da; i += 256) {
+      if (pr && pr[i / A] != 0) continue;
+      const float d = a[(size_t)r * da + i] - u[(size_t)r * da + i];
+      sq += d * d;
+      ++cnt;
+    }
+  }
+  sq = wave_sum(sq);
+  const float sc = wave_sum((float)cnt);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sq; red[1][threadIdx.x >> 6] = sc; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    out[2 * j] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    out[2 * j + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
 // ---- temporal ensembling of action chunks (fv_ensemble_step; LeRobot's ACTTemporalEnsembler, per environment) ----
 // Ring: slot (head + k) % K holds the running average for the time step k ahead of now; row k of the new chunk is one more prediction of it.  A slot with
 // count n == 0 takes the row as it is, otherwise ens <- (ens cw[n-1] + c w[n]) / cw[n] with w[i] = exp(-coeff i) (i = 0 the oldest) and cw its running sum.
@@ -220,6 +251,15 @@ int launch_loss_per_dim(const float* a, const float* t, const uint8_t* pad, floa
   if (pad_rows <= 0) pad_rows = rows;
   if (rows % pad_rows) return fv_fail(FV_ERR_ARG, "loss_per_dim: the mask's rows must divide the rows");
   hipLaunchKernelGGL(loss_per_dim_kernel, dim3(A), dim3(256), 0, s, a, t, pad, out, rows, A, pad_rows);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+
+int launch_loss_per_time(const float* a, const float* u, const float* t, const uint8_t* pad, float* out, int R, int B, int da, int K, int nb, hipStream_t s) {
+  if (!a || !u || !t || !out) return fv_fail(FV_ERR_ARG, "loss_per_time: null pointer");
+  if (B < 1 || R < B || R % B || K < 1 || da < 1 || da % K) return fv_fail(FV_ERR_ARG, "loss_per_time: bad shape");
+  if (nb < 1 || nb > FV_LOSS_TIME_BUCKETS_MAX) return fv_fail(FV_ERR_ARG, "loss_per_time: n_buckets = %d outside 1 .. %d", nb, FV_LOSS_TIME_BUCKETS_MAX);
+  hipLaunchKernelGGL(loss_per_time_kernel, dim3(nb), dim3(256), 0, s, a, u, t, pad, out, R, B, da, K, nb);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }

@@ -1,6 +1,8 @@
 // flow_kernels.hip -- the flow-matching form of the action expert (fv_head_set_flow), all fp32, every sum in a fixed order:
 //   flow_prepare_kernel                    training: x_t and phi(t) into their columns of the head's cat, u = eps - a as the loss target; the head itself
 //                                          (head_kernels.hip) then runs forward and backward as it does for regression
+//   flow_time / flow_beta_inv              the training time as an inverse CDF (fv_head_set_flow_time): Beta, range and strata from the row's one uniform, in the
+//                                          <FlowTimeArgs> instances of flow_prepare_kernel -- a handle without the setting launches the plain ones
 //   flow_cond / _init / _step_a / _b / _c  the sampler (fv_head_flow_sample): conditioning once, three launches per network evaluation
 //   <PREFIX> instances                     action-prefix conditioning (fv_head_set_flow_prefix): what the noising step, the conditioning, the start and step C
 //                                          add for it sits under `if constexpr (PREFIX)` in the one body each of them has
@@ -45,6 +47,90 @@ __device__ __forceinline__ void flow_phi(float* __restrict__ dst, const float* _
   dst[half + i] = cosf(arg);
 }
 
+// ---- the training time as an inverse CDF (fv_head_set_flow_time): tau = F^-1(u) in double from the row's one uniform.  Every thread of the block runs the
+// same arithmetic on the same u, so the control flow below is uniform over the block: no barrier, no hand-over, no atomics; every loop has a cap.
+// The continued fraction of I_x(a, b) (modified Lentz), for x <= (a + 1) / (a + b + 2) where it converges in O(sqrt(max(a, b))) terms:
+//     I_x(a, b) = x^a (1 - x)^b / (a B(a, b)) * cf
+constexpr int FLOW_BETA_CF_MAX = 300, FLOW_BETA_NEWTON_MAX = 64;
+__device__ double flow_beta_cf(double a, double b, double x) {
+  const double qab = a + b, qap = a + 1.0, qam = a - 1.0, tiny = 1e-300;
+  double c = 1.0, d = 1.0 - qab * x / qap;
+  if (fabs(d) < tiny) d = tiny;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= FLOW_BETA_CF_MAX; ++m) {
+    const double dm = (double)m, m2 = 2.0 * dm;
+    double aa = dm * (b - dm) * x / ((qam + m2) * (a + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    h *= d * c;
+    aa = -(a + dm) * (qab + dm) * x / ((a + m2) * (qap + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) < 3e-16) break;
+  }
+  return h;
+}
+// x in (0, xhi] with I_x(a, b) = p, for 0 < p <= I_xhi(a, b) and xhi <= (a + 1) / (a + b + 2).  Newton on g(y) = log I_{exp y} - log p in y = log x, where g is
+// close to a line of slope a for small x and g'(y) = a / ((1 - x) cf): the RELATIVE error of x is what converges, down to x = 1e-300.  lab = log(a B(a, b)).
+// Safeguard: the iterate stays inside the bracket the signs of g have drawn so far, by bisection where Newton would leave it.  It stops once a NEWTON step is
+// below 1e-9 (the error behind a quadratically convergent step of that size is far below 2^-40) or the bracket is narrower than 1e-14, at the cap otherwise
+__device__ double flow_beta_inv_lower(double a, double b, double lab, double p, double xhi) {
+  const double lp = log(p);
+  double ylo = -700.0, yhi = log(xhi);
+  double y = fmin(fmax((lp + lab) / a, ylo), yhi);
+  bool top = false;   // the upper end itself has been evaluated
+  for (int it = 0; it < FLOW_BETA_NEWTON_MAX; ++it) {
+    const double x = exp(y), cf = flow_beta_cf(a, b, x);
+    const double g = a * y + b * log1p(-x) - lab + log(cf) - lp;
+    if (g == 0.0) break;
+    top = top || y == yhi;
+    if (g > 0.0) yhi = y; else ylo = y;
+    double yn = y - g * (1.0 - x) * cf / a;
+    bool newton = true;
+    if (yn > yhi && !top) yn = yhi;   // (a root at the end of the range: look at the end before halving towards it)
+    else if (!(yn >= ylo && yn <= yhi)) { yn = 0.5 * (ylo + yhi); newton = false; }
+    const double dy = yn - y;
+    y = yn;
+    if ((newton && fabs(dy) < 1e-9) || yhi - ylo < 1e-14) break;   // (a halving step says nothing about the error: only the bracket's width ends those)
+  }
+  return exp(y);
+}
+// tau = I^-1_u(a, b).  The closed forms of a = 1 and b = 1 (pi0's Beta(1.5, 1) is u^(1 / 1.5)) keep the relative accuracy of exp / log / expm1 / log1p in double.
+// Otherwise the tail is chosen at xs = (a + 1) / (a + b + 2), where both continued fractions converge: the lower one solves for x, the upper one for 1 - x in
+// Beta(b, a) at 1 - u (exact in double for u >= 1 / 2), so a tau near 0 keeps its relative and a tau near 1 its absolute accuracy
+__device__ double flow_beta_inv(double a, double b, double lbeta, double u) {
+  if (u <= 0.0) return 0.0;
+  if (a == 1.0 && b == 1.0) return u;
+  if (b == 1.0) return exp(log(u) / a);
+  if (a == 1.0) return -expm1(log1p(-u) / b);
+  const double xs = (a + 1.0) / (a + b + 2.0), la = log(a) + lbeta, lb = log(b) + lbeta;
+  const double ps = exp(a * log(xs) + b * log1p(-xs) - la) * flow_beta_cf(a, b, xs);
+  if (u <= ps) return flow_beta_inv_lower(a, b, la, u, xs);
+  return 1.0 - flow_beta_inv_lower(b, a, lb, 1.0 - u, 1.0 - xs);
+}
+// the row's time from k, the 24-bit integer behind the uniform t (s of S: the stratum; S == 1: none).  t = t_lo + (t_hi - t_lo) tau in double, rounded once.
+// bm: the fp32 logit-normal tau of the unstratified form, fv_head_set_flow's expression with its bits
+struct FlowTimeArgs { int dist, strat; double a, b, lbeta, t_lo, t_span; };
+__device__ float flow_time(const FlowTimeArgs& tm, uint32_t k, uint32_t s, uint32_t S, float bm) {
+  double u = (double)k * (1.0 / 16777216.0);
+  if (tm.strat) u = ((double)s + u) / (double)S;
+  double tau;
+  if (tm.dist == 2) tau = flow_beta_inv(tm.a, tm.b, tm.lbeta, u);
+  else if (tm.dist == 0) tau = u;
+  else if (!tm.strat) tau = (double)bm;
+  else tau = u <= 0.0 ? 0.0 : 1.0 / (1.0 + exp(-(tm.a + tm.b * normcdfinv(u))));
+  return (float)(tm.t_lo + tm.t_span * tau);
+}
+
 // block = one head row, grid (B, S): head row r = s B + b is draw s of observation b (fv_head_set_flow_draws; S == 1: the rows as ever).  It reads targets[b]
 // and draws what row b draws at offset + (s << 56) -- the key, the counter (group, b, offset) and the Box-Muller as they are, so row b's draws depend
 // neither on B nor on S, and draw 0 is the single draw.  Explicit noise (S B, da) / tin (S B) are read at r.
@@ -53,18 +139,26 @@ __device__ __forceinline__ void flow_phi(float* __restrict__ dst, const float* _
 // PREFIX (fv_head_set_flow_prefix): the row's delay d is delays[row] clamped to 0 .. pd, or the smallest j with (z >> 8) < thr[j], z the third word of the
 // group-0 block whose x and y yield t (an integer compare; no new stream, no new counter: t and eps are the plain head's bits).  The first d steps of x_t are
 // COPIES of targets, m = [k < d] goes behind phi(t) as exact 0.0 / 1.0 and as bytes into pmask; u is written everywhere as ever
+// TM (fv_head_set_flow_time): empty, or one FlowTimeArgs behind the plain arguments -- the drawn t then goes through flow_time.  Instances of their own with
+// an argument of their own: a handle without the setting launches the kernels, with the arguments, it always did
 struct FlowPrefixArgs { const int32_t* delays; const uint32_t* thr; uint8_t* pmask; int pk, pd; };
-template <bool PREFIX>
+template <bool PREFIX, class... TM>
 __global__ __launch_bounds__(256) void flow_prepare_kernel(const float* __restrict__ targets, const float* __restrict__ noise, const float* __restrict__ tin,
                                                             float* __restrict__ cat, int cw, int xo, float* __restrict__ u_out, int da, int te,
                                                             const float* __restrict__ freq, int time_dist, float dist_a, float dist_b, uint64_t seed,
-                                                            uint64_t offset, FlowPrefixArgs px) {
+                                                            uint64_t offset, FlowPrefixArgs px, TM... tma) {
+  static_assert(sizeof...(TM) <= 1, "at most one FlowTimeArgs");
   const int obs = blockIdx.x, row = blockIdx.y * gridDim.x + obs;
   offset += (uint64_t)blockIdx.y << 56;
   uint4 r = make_uint4(0u, 0u, 0u, 0u);
   if (PREFIX || !tin) r = flow_philox(0u, (uint32_t)obs, seed, offset);   // (PREFIX: a drawn delay needs the block with t given, too)
   float t;
   if (tin) t = tin[row];
+  else if constexpr (sizeof...(TM) != 0) {
+    const FlowTimeArgs& tm = (tma, ...);
+    const float bm = tm.dist == 1 && !tm.strat ? 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x))) : 0.f;
+    t = flow_time(tm, r.x >> 8, blockIdx.y, gridDim.y, bm);
+  }
   else if (time_dist == 0) t = (float)(r.x >> 8) * FLOW_U24;
   else t = 1.0f / (1.0f + expf(-(dist_a + dist_b * flow_box_muller(r.x, r.y).x)));
   float* xr = cat + (size_t)row * cw + xo;
@@ -512,8 +606,22 @@ int launch_flow_prepare(const HeadDims& d, const HeadFlow& f, const float* targe
   const int S = head_rows(d, B) / B;
   if (S > 1 && (offset >> 56 & 15)) return fv_fail(FV_ERR_ARG, "flow_prepare: bits 56 .. 59 of the offset number the draws and must be 0 with more than one draw");
   const FlowPrefixArgs px = d.pk > 0 ? FlowPrefixArgs{delays, f.thr, head_saved_prefix_mask(d, B, saved), d.pk, d.pd} : FlowPrefixArgs{};
-  hipLaunchKernelGGL(d.pk > 0 ? flow_prepare_kernel<true> : flow_prepare_kernel<false>, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved),
-                     head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq, f.time_dist, f.dist_a, f.dist_b, seed, offset, px);
+  // fv_head_set_flow_time: the handle's own distribution gives way to the setting's.  The TIMED instances run only where the setting changes a drawn t: a
+  // Beta, a range other than [0, 1], or strata with more than one draw; explicit t, and a setting that amounts to uniform or logit-normal on [0, 1], launch
+  // the plain instances with the plain arguments
+  const FlowTime& tm = f.tm;
+  const int dist = tm.on ? tm.dist : f.time_dist;
+  const float da_ = tm.on ? tm.a : f.dist_a, db_ = tm.on ? tm.b : f.dist_b;
+  const int strat = tm.on && tm.stratify && S > 1;
+  const bool timed = tm.on && !t && (dist == 2 || strat || tm.t_lo != 0.f || tm.t_hi != 1.f);
+  const FlowTimeArgs ta{dist, strat, (double)tm.a, (double)tm.b, tm.lbeta, (double)tm.t_lo, (double)tm.t_hi - (double)tm.t_lo};
+  if (timed) {
+    const auto kern = d.pk > 0 ? flow_prepare_kernel<true, FlowTimeArgs> : flow_prepare_kernel<false, FlowTimeArgs>;
+    hipLaunchKernelGGL(kern, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved), head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq,
+                       dist, da_, db_, seed, offset, px, ta);
+  } else
+    hipLaunchKernelGGL(d.pk > 0 ? flow_prepare_kernel<true> : flow_prepare_kernel<false>, dim3(B, S), dim3(256), 0, s, targets, noise, t, head_saved_cat(d, B, saved),
+                       head_cat_width(d), d.feat + d.hid, u_out, d.da, d.te, f.freq, dist, da_, db_, seed, offset, px);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }

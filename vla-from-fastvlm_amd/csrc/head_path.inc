@@ -189,6 +189,26 @@ int fv_head_set_flow_draws(fv_handle* h, int draws) {
   return FV_OK;
 }
 
+int fv_head_set_flow_time(fv_handle* h, const fv_head_flow_time_spec* spec) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow_time: the head is not in flow mode (fv_head_set_flow)");
+  if (!spec) { h->flow.tm = fv::FlowTime{}; return FV_OK; }
+  if (spec->dist < 0 || spec->dist > 2) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_time: unknown dist %d (0 uniform, 1 logit-normal, 2 Beta)", spec->dist);
+  if (!std::isfinite(spec->a) || !std::isfinite(spec->b) || !std::isfinite(spec->t_lo) || !std::isfinite(spec->t_hi))
+    return fv_fail(FV_ERR_ARG, "fv_head_set_flow_time: a, b, t_lo and t_hi must be finite");
+  if (spec->dist == 2 && (spec->a < 0.25f || spec->a > 32.f || spec->b < 0.25f || spec->b > 32.f))
+    return fv_fail(FV_ERR_ARG, "fv_head_set_flow_time: Beta(%g, %g) outside [0.25, 32] (the range the inversion is held to)", (double)spec->a, (double)spec->b);
+  if (!(spec->t_lo >= 0.f && spec->t_lo < spec->t_hi && spec->t_hi <= 1.f))
+    return fv_fail(FV_ERR_ARG, "fv_head_set_flow_time: the range must be 0 <= t_lo < t_hi <= 1 (got %g, %g)", (double)spec->t_lo, (double)spec->t_hi);
+  if (spec->stratify != 0 && spec->stratify != 1) return fv_fail(FV_ERR_ARG, "fv_head_set_flow_time: stratify = %d must be 0 or 1", spec->stratify);
+  fv::FlowTime tm;
+  tm.on = 1; tm.dist = spec->dist; tm.stratify = spec->stratify; tm.a = spec->a; tm.b = spec->b; tm.t_lo = spec->t_lo; tm.t_hi = spec->t_hi;
+  if (spec->dist == 2) tm.lbeta = std::lgamma((double)spec->a) + std::lgamma((double)spec->b) - std::lgamma((double)spec->a + (double)spec->b);
+  h->flow.tm = tm;
+  return FV_OK;
+}
+
 int fv_head_flow_prepare(fv_handle* h, const float* targets, int B, uint64_t seed, uint64_t offset, const float* noise, const float* t, void* saved,
                          float* u_out, fv_stream s) {
   HandleScope _hs(h);
@@ -399,6 +419,17 @@ int fv_head_loss_per_dim(fv_handle* h, const float* actions, const float* target
   // (draws: actions and targets have S B rows, the mask keeps B)
   return fv::launch_loss_per_dim(actions, targets, h->loss.pad, out_dev, (long)fv::head_rows(h->hd, B) * h->loss.chunk, h->hd.da / h->loss.chunk, static_cast<hipStream_t>(s),
                                  (long)B * h->loss.chunk);
+}
+
+int fv_head_loss_per_time(fv_handle* h, const float* actions, const float* targets, const float* t, int B, int n_buckets, float* out_dev, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !actions || !targets || !t || !out_dev) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_time: null argument");
+  if (h->hd.te <= 0) return fv_fail(FV_ERR_STATE, "fv_head_loss_per_time: the head is not in flow mode (fv_head_set_flow)");
+  if (B < 1) return fv_fail(FV_ERR_ARG, "fv_head_loss_per_time: B must be positive");
+  if (n_buckets < 1 || n_buckets > FV_LOSS_TIME_BUCKETS_MAX)
+    return fv_fail(FV_ERR_ARG, "fv_head_loss_per_time: n_buckets = %d outside 1 .. %d", n_buckets, FV_LOSS_TIME_BUCKETS_MAX);
+  // (draws: actions, targets and t have S B rows, the mask keeps B)
+  return fv::launch_loss_per_time(actions, targets, t, h->loss.pad, out_dev, fv::head_rows(h->hd, B), B, h->hd.da, h->loss.chunk, n_buckets, static_cast<hipStream_t>(s));
 }
 
 int fv_head_loss_metrics(fv_handle* h, const float** dev) {

@@ -341,7 +341,10 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
 // ---- flow-matching head (d.te > 0).  freq: te / 2 device floats, 2 pi / period_j.  time_dist 0: t ~ U[0, 1); 1: t = sigmoid(dist_a + dist_b n)
 // thr (prefix mode): pd + 1 device uint32, the cumulative delay distribution in units of 2^-24 (the last one is 2^24)
-struct HeadFlow { const float* freq; int time_dist; float dist_a, dist_b; const uint32_t* thr = nullptr; };
+// FlowTime (fv_head_set_flow_time; on == 0: the handle draws t as fv_head_set_flow says): t = t_lo + (t_hi - t_lo) F^-1(u) from the one uniform of the row.
+// dist 0 uniform, 1 logit-normal, 2 Beta(a, b); lbeta = log B(a, b), formed once on the host in double (dist 2 only)
+struct FlowTime { int on = 0, dist = 0, stratify = 0; float a = 0.f, b = 0.f, t_lo = 0.f, t_hi = 1.f; double lbeta = 0.0; };
+struct HeadFlow { const float* freq; int time_dist; float dist_a, dist_b; const uint32_t* thr = nullptr; FlowTime tm = {}; };
 // one launch: draws (or reads) t per row and noise per element, writes x_t and phi(t) into their columns of saved's cat and u = noise - targets into u_out.
 // d.draws = S > 1: targets (B, da) stay per observation; head row s B + b draws what row b draws at offset + (s << 56); noise, t and u_out have S B rows.
 // FV_ERR_ARG, nothing enqueued, when S > 1 and any of bits 56 .. 59 of the offset is set
@@ -400,6 +403,9 @@ int launch_chunk_loss(const float* a, const float* t, const uint8_t* pad, float*
 // without a valid step.  One block per dimension, fixed-order sums
 // pad_rows (0: rows): the mask has fewer rows than a, t and row r reads pad[r % pad_rows] -- the draws of a flow head share their observation's mask
 int launch_loss_per_dim(const float* a, const float* t, const uint8_t* pad, float* out, long rows, int A, hipStream_t s, long pad_rows = 0);
+// the squared error by time bucket (fv_head_loss_per_time): a, u (R, da) f32, t (R), pad (B, K) bytes or null (row r reads the mask of observation r % B) ->
+// out (nb, 2): { sum of (a - u)^2 over the non-padded elements of the rows in the bucket, their number }.  One block per bucket, fixed-order sums
+int launch_loss_per_time(const float* a, const float* u, const float* t, const uint8_t* pad, float* out, int R, int B, int da, int K, int nb, hipStream_t s);
 // temporal ensembling of action chunks (fv_ensemble_step): chunks (n_env, K, A) -> actions (n_env, A); ens (n_env, K, A) and count (n_env, K) are the ring,
 // head its position, w / cw the K weights exp(-coeff i) and their running sums
 int launch_ensemble_step(const float* chunks, float* ens, int32_t* count, float* actions, const float* w, const float* cw, int n_env, int K, int A, int head,

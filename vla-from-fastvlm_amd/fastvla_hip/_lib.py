@@ -75,6 +75,15 @@ class HeadFlowSpec(C.Structure):    # fv_head_flow_spec: 24 bytes
 
 
 FLOW_TIME_DISTS = {"uniform": 0, "logit_normal": 1}
+
+
+class HeadFlowTimeSpec(C.Structure):    # fv_head_flow_time_spec: 24 bytes
+    _fields_ = [("dist", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("t_lo", C.c_float), ("t_hi", C.c_float), ("stratify", C.c_int32)]
+
+
+FLOW_TIME_SPEC_DISTS = {"uniform": 0, "logit_normal": 1, "beta": 2}      # fv_head_flow_time_spec.dist (fv_head_set_flow itself takes the first two)
+FLOW_BETA_RANGE = (0.25, 32.0)                                            # the Beta parameters fv_head_set_flow_time accepts
+LOSS_TIME_BUCKETS_MAX = 64                                                # FV_LOSS_TIME_BUCKETS_MAX
 FLOW_SOLVERS = {"euler": 0, "midpoint": 1, "heun": 2, "rk4": 3}      # FV_FLOW_SOLVER_*
 FLOW_SELECTS = {"first": 0, "medoid": 1, "coherent": 2}              # FV_FLOW_SELECT_*
 FLOW_SAMPLES_MAX = 16                                                 # FV_FLOW_SAMPLES_MAX
@@ -138,6 +147,8 @@ SIGNATURES = {
     "fv_head_loss_per_dim": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "fv_head_set_flow": (_i, [_vp, C.POINTER(HeadFlowSpec)]),
     "fv_head_set_flow_draws": (_i, [_vp, _i]),
+    "fv_head_set_flow_time": (_i, [_vp, C.POINTER(HeadFlowTimeSpec)]),
+    "fv_head_loss_per_time": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "fv_head_flow_prepare": (_i, [_vp, _vp, _i, _u64, _u64, _vp, _vp, _vp, _vp, _vp]),
     "fv_head_flow_sample": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _u64, _u64, _vp, _vp]),
     "fv_head_set_flow_guidance": (_i, [_vp, _i, C.POINTER(_f), _f]),

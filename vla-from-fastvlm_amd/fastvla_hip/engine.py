@@ -139,6 +139,26 @@ def check_flow_solver(name) -> str:
     return key
 
 
+def check_flow_time(dist, a, b, t_lo, t_hi, stratify) -> dict:
+    """-> set_head_flow_time's arguments, validated as fv_head_set_flow_time validates them (ValueError otherwise): dist a key of _lib.FLOW_TIME_SPEC_DISTS,
+    finite a / b (a Beta's inside _lib.FLOW_BETA_RANGE), 0 <= t_lo < t_hi <= 1, stratify a bool"""
+    import math
+    key = dist.strip().lower() if isinstance(dist, str) else dist
+    if key not in _lib.FLOW_TIME_SPEC_DISTS:
+        raise ValueError(f"flow time dist must be one of {list(_lib.FLOW_TIME_SPEC_DISTS)}, got {dist!r}")
+    a, b, t_lo, t_hi = float(a), float(b), float(t_lo), float(t_hi)
+    if not all(math.isfinite(x) for x in (a, b, t_lo, t_hi)):
+        raise ValueError(f"flow time a, b and range must be finite, got {(a, b, t_lo, t_hi)}")
+    lo, hi = _lib.FLOW_BETA_RANGE
+    if key == "beta" and not (lo <= a <= hi and lo <= b <= hi):
+        raise ValueError(f"flow time Beta({a:g}, {b:g}): both parameters must lie in [{lo:g}, {hi:g}]")
+    if not 0.0 <= t_lo < t_hi <= 1.0:
+        raise ValueError(f"flow time range must be 0 <= lo < hi <= 1, got ({t_lo:g}, {t_hi:g})")
+    if not isinstance(stratify, (bool, int)) or stratify not in (0, 1):
+        raise ValueError(f"flow time stratify must be a bool, got {stratify!r}")
+    return dict(dist=key, a=a, b=b, t_lo=t_lo, t_hi=t_hi, stratify=bool(stratify))
+
+
 def flow_draw_offset(offset: int, s: int) -> int:
     """the Philox offset draw s of a step at `offset` draws at: a single-draw call at this offset gives draw s's rows.  ValueError when the step's offset
     already uses the draw bits or s is outside 0 .. 15."""
@@ -202,6 +222,7 @@ class FastVLAEngine:
         self._pad_keep: Optional[torch.Tensor] = None
         self.head_flow: Optional[dict] = None                     # set_head_flow: None = the regression head
         self.head_flow_guidance: Optional[dict] = None            # set_head_flow_guidance: None = the unguided sampler only
+        self.head_flow_time = None                                # set_head_flow_time: the training time's distribution beyond set_head_flow's own (None: off)
         self.head_flow_draws = 1                                  # set_head_flow_draws: noise draws per observation in the training forms
         self.head_flow_prefix: Optional[dict] = None              # set_head_flow_prefix: None = no action-prefix conditioning
         self.head_flow_solver = "euler"                           # set_head_flow_solver: the integrator of all three samplers
@@ -595,6 +616,7 @@ class FastVLAEngine:
         if time_dim is None:
             _lib.check(self.lib.fv_head_set_flow(self.h, None), "fv_head_set_flow", self.h)
             self.head_flow = None
+            self.head_flow_time = None
             self.head_flow_draws = 1
             self.head_flow_prefix = None
             self.head_flow_solver = "euler"
@@ -607,6 +629,7 @@ class FastVLAEngine:
                 _lib.check(self.lib.fv_head_set_flow(self.h, C.byref(spec)), "fv_head_set_flow", self.h)
             self.head_flow = dict(time_dim=int(time_dim), min_period=float(min_period), max_period=float(max_period), time_dist=time_dist,
                                   dist_a=float(dist_a), dist_b=float(dist_b))
+            self.head_flow_time = None           # (a fresh fv_head_set_flow resets fv_head_set_flow_time)
         self._refresh_head_layout()
 
     def _refresh_head_layout(self) -> None:
@@ -645,6 +668,21 @@ class FastVLAEngine:
         draws = check_flow_draws(draws)
         _lib.check(self.lib.fv_head_set_flow_draws(self.h, draws), "fv_head_set_flow_draws", self.h)
         self.head_flow_draws = draws
+
+    def set_head_flow_time(self, dist: Optional[str] = "uniform", a: float = 0.0, b: float = 1.0, t_lo: float = 0.0, t_hi: float = 1.0,
+                           stratify: bool = False) -> None:
+        """The distribution of the drawn training time (fv_head_set_flow_time): t = t_lo + (t_hi - t_lo) F^-1(u) from the row's one uniform.  dist "uniform" |
+        "logit_normal" (a + b n) | "beta" (Beta(a, b), both in [0.25, 32]; pi0: "beta", 1.5, 1.0, 0.001, 1.0); stratify: draw s of the S of set_head_flow_draws
+        takes the s-th of S equal-probability strata (nothing with S = 1).  dist None returns the handle to set_head_flow's own time_dist.  Flow mode only, at any
+        time: no size depends on it.  Explicit t buffers still replace every draw."""
+        if dist is None:
+            _lib.check(self.lib.fv_head_set_flow_time(self.h, None), "fv_head_set_flow_time", self.h)
+            self.head_flow_time = None
+            return
+        tm = check_flow_time(dist, a, b, t_lo, t_hi, stratify)
+        spec = _lib.HeadFlowTimeSpec(_lib.FLOW_TIME_SPEC_DISTS[tm["dist"]], tm["a"], tm["b"], tm["t_lo"], tm["t_hi"], int(tm["stratify"]))
+        _lib.check(self.lib.fv_head_set_flow_time(self.h, C.byref(spec)), "fv_head_set_flow_time", self.h)
+        self.head_flow_time = tm
 
     def head_flow_prepare(self, targets: torch.Tensor, saved: torch.Tensor, *, seed: int = 0, offset: int = 0, noise: Optional[torch.Tensor] = None,
                           t: Optional[torch.Tensor] = None, delays: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -919,6 +957,26 @@ class FastVLAEngine:
         out = torch.empty(self.head_dims["da"] // K, dtype=torch.float32, device=self.device)
         with self._Mask(self, pad):
             _lib.check(self.lib.fv_head_loss_per_dim(self.h, actions.data_ptr(), targets.data_ptr(), B, out.data_ptr(), _stream()), "fv_head_loss_per_dim", self.h)
+        return out
+
+    def head_loss_per_time(self, actions: torch.Tensor, targets: torch.Tensor, t: torch.Tensor, buckets: int = 10, pad=None) -> torch.Tensor:
+        """-> (buckets, 2) f32: per time bucket the sum of (actions - targets)^2 over the non-padded elements of the rows whose t falls into it, and the number
+        of those elements (fv_head_loss_per_time); row r's bucket is min(buckets - 1, int(t buckets)).  actions = v, targets = u: (R, da), t: (R,); pad:
+        optional (B, chunk) bool.  Never weighted, whatever the loss kind.  (set_head_flow_draws(S): R = S B rows, pad keeps B.)"""
+        S, da = self.head_flow_draws, self.head_dims["da"]
+        B = self._draw_rows(actions.shape[0])
+        if isinstance(buckets, bool) or not isinstance(buckets, int) or not 1 <= buckets <= _lib.LOSS_TIME_BUCKETS_MAX:
+            raise ValueError(f"buckets must be an integer 1 .. {_lib.LOSS_TIME_BUCKETS_MAX}, got {buckets!r}")
+        actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        targets = targets.to(device=self.device, dtype=torch.float32).contiguous()
+        t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if actions.numel() != S * B * da or targets.numel() != actions.numel() or t.numel() != S * B:
+            raise ValueError(f"actions and targets must hold (R, {da}) elements and t R, got {tuple(actions.shape)}, {tuple(targets.shape)} and {tuple(t.shape)}")
+        pad = self._pad_arg(pad, B)
+        out = torch.empty(buckets, 2, dtype=torch.float32, device=self.device)
+        with self._Mask(self, pad):
+            _lib.check(self.lib.fv_head_loss_per_time(self.h, actions.data_ptr(), targets.data_ptr(), t.data_ptr(), B, buckets, out.data_ptr(), _stream()),
+                       "fv_head_loss_per_time", self.h)
         return out
 
     def _draw_rows(self, rows: int) -> int:

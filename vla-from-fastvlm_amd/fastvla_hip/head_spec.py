@@ -19,6 +19,7 @@ class HeadSpec:
     loss: dict = field(default_factory=lambda: dict(kind="mse", beta=1.0, chunk=1))      # set_head_loss' arguments: the fused loss and the chunk length K
     loss_weights: Optional[dict] = None      # {"dim", "step"} of the weighted chunk loss, None = off
     flow: Optional[dict] = None              # set_head_flow's arguments, None = the regression head
+    flow_time: Optional[dict] = None         # set_head_flow_time's arguments (+ "name", the checkpoint's string), None = set_head_flow's own distribution
     prefix: Optional[dict] = None            # fastvla_hip.prefix.check_prefix_config's record, None = off
     draws: int = 1                           # set_head_flow_draws' argument, 1 = one draw per observation
     guidance: Optional[dict] = None          # set_head_flow_guidance's arguments, None = off
@@ -27,7 +28,7 @@ class HeadSpec:
     solver_rows: bool = False                # a higher-order solver was named once: an engine is built with its two rows reserved
 
     def __post_init__(self):
-        from .engine import check_flow_draws, check_flow_solver, check_head_loss, check_loss_weights
+        from .engine import check_flow_draws, check_flow_solver, check_flow_time, check_head_loss, check_loss_weights
         from .prefix import check_prefix_config
         from .select import check_flow_select
         head = "regression" if self.flow is None else "flow"
@@ -36,6 +37,13 @@ class HeadSpec:
         self.draws = check_flow_draws(self.draws)
         if self.draws > 1 and self.flow is None:
             raise ValueError(f"flow_noise_draws={self.draws} needs action_head='flow' (the regression head has no noise to draw)")
+        if self.flow_time is not None:
+            tm = self.flow_time
+            if self.flow is None:
+                raise ValueError(f"flow_time_dist={tm.get('name', tm['dist'])!r} needs action_head='flow' (the regression head draws no time)")
+            self.flow_time = dict(check_flow_time(tm["dist"], tm["a"], tm["b"], tm["t_lo"], tm["t_hi"], tm["stratify"]), name=str(tm.get("name", tm["dist"])))
+            if self.flow_time["stratify"] and self.draws == 1:
+                raise ValueError("flow_time_stratify=True needs flow_noise_draws > 1 (the strata are dealt to the draws of one observation), got flow_noise_draws=1")
         kind, beta, K = check_head_loss(self.loss["kind"], self.loss["beta"], self.loss["chunk"], self.dims["action_dim"])
         self.loss = dict(kind=kind, beta=beta, chunk=K)
         if self.loss_weights is not None:
@@ -50,10 +58,12 @@ class HeadSpec:
         self.solver_rows = bool(self.solver_rows or self.solver != "euler")      # (a policy switched back to Euler keeps its rows: it may switch again)
 
     def apply(self, engine) -> None:
-        """Configure a NEW engine.  The order is a constraint of the library: flow mode first; prefix, draws, guidance and samples before any workspace is
-        bound; the solver twice, so that a spec switched back to Euler still reserves a higher-order solver's rows; switched-off options call nothing."""
+        """Configure a NEW engine.  The order is a constraint of the library: flow mode first, the time distribution behind it (set_head_flow resets it);
+        prefix, draws, guidance and samples before any workspace is bound; the solver twice, so that a spec switched back to Euler still reserves a higher-order solver's rows; switched-off options call nothing."""
         if self.flow is not None:
             engine.set_head_flow(**self.flow)
+            if self.flow_time is not None:
+                engine.set_head_flow_time(**{k: v for k, v in self.flow_time.items() if k != "name"})
             if self.prefix is not None:
                 px = self.prefix
                 engine.set_head_flow_prefix(px["chunk"], px["max_delay"], thresholds=px["thresholds"], dist=px["dist"], rate=px["rate"])

@@ -130,7 +130,7 @@ class FastVLMWithExpert(nn.Module):
         self._coherence_weights = coherence_weights(int(K), o.decay) if self.flow_select == "coherent" else None
         spec = HeadSpec(dims=dict(state_dim=config.state_dim, action_dim=K * config.action_dim, hidden_dim=config.hidden_dim, fusion_dim=config.fusion_dim),
                         loss=dict(kind=o.chunk["loss"], beta=o.chunk["beta"], chunk=K), flow=None if o.flow is None else dict(o.flow),
-                        prefix=None if o.prefix is None else dict(o.prefix), draws=o.noise_draws, solver=o.solver,
+                        flow_time=None if o.flow_time is None else dict(o.flow_time), prefix=None if o.prefix is None else dict(o.prefix), draws=o.noise_draws, solver=o.solver,
                         samples=dict(max_samples=self.flow_samples, step_weights=self._coherence_weights) if self.flow_samples > 1 else None)
         self.config = config
         self.flow_noise_draws = spec.draws
@@ -140,6 +140,7 @@ class FastVLMWithExpert(nn.Module):
         self.backbone = FastVLMBackbone(config.to_backbone_config())
         self.backbone.configure_head(spec)
         self.flow, self.flow_prefix, self.flow_steps = spec.flow, spec.prefix, int(o.flow_steps)
+        self.flow_time = spec.flow_time      # the training time beyond set_head_flow's own distribution (flow_time_dist "beta:..." | "pi0", range, strata); None: off
         self._flow_solver = spec.solver
         self._flow_solver_rows = spec.solver_rows      # a policy built with a higher-order solver reserved their rows and may switch among all four
         self.rtc: Optional[dict] = None      # configure_rtc: real-time chunking of the flow sampler, a property of the run
@@ -202,6 +203,11 @@ class FastVLMWithExpert(nn.Module):
         """action_error_per_dim: ONE fixed offset in a range of its own (bit 63) -- two calls sample from the same noise, and no counter advances"""
         return self._flow_seed, 1 << 63
 
+    def flow_time_loss_draw(self):
+        """flow_loss_per_time: ONE fixed offset in a range of its own (bits 62 and 63 both set; the draw bits 56 .. 59 stay free) -- two calls see the same
+        noise, and no counter advances"""
+        return self._flow_seed, (1 << 63) | (1 << 62)
+
     @property
     def flow_solver(self) -> str:
         """"euler" | "midpoint" | "heun" | "rk4": the integrator of every sampling route"""
@@ -229,6 +235,13 @@ class FastVLMWithExpert(nn.Module):
                "seed": int(self._flow_seed), **_prefix.extras_record(self.flow_prefix)}
         if self._flow_solver != "euler":
             rec["solver"] = self._flow_solver
+        if self.flow_time is not None:      # "time_dist" holds the string; "time_range" / "time_stratify" only when set; dist_a / dist_b keep their constants
+            tm = self.flow_time
+            rec["time_dist"] = tm["name"]
+            if (tm["t_lo"], tm["t_hi"]) != (0.0, 1.0):
+                rec["time_range"] = [tm["t_lo"], tm["t_hi"]]
+            if tm["stratify"]:
+                rec["time_stratify"] = True
         return rec
 
     # ------------------------------------------------------------------ flat parameter storage
@@ -326,6 +339,31 @@ class FastVLMWithExpert(nn.Module):
         with torch.no_grad():
             actions, _saved = eng.head_forward(self._flat, pooled, states.to(pooled.device, torch.float32), normalized_actions=True)
             return eng.head_loss_per_dim(actions, targets.contiguous(), pad=pad)
+
+    def flow_loss_per_time(self, pooled: torch.Tensor, states: torch.Tensor, targets: torch.Tensor, pad=None, buckets: int = 10):
+        """-> (mse, count), each (buckets,) on the device: the velocity error as a function of t -- per time bucket the mean of (v - u)^2 over the non-padded
+        elements of the head rows in it (0 where there is none) and their number; never weighted, whatever the loss kind, no gradient.  Head row r (S B of
+        them with flow_noise_draws = S) is noised at the EXPLICIT time ((r mod buckets) + 0.5) / buckets, so every bucket is covered whatever the training
+        distribution is, from the flow seed's noise at a fixed offset (flow_time_loss_draw): no dropout, no counter advances, and two calls on the same weights
+        agree bit for bit.  The metric a time distribution is judged with, as action_error_per_dim is a solver's.  (A prefix-width head is given m = 0.)"""
+        if self.flow is None:
+            raise ValueError("flow_loss_per_time needs action_head='flow' (the regression head has no time)")
+        self.materialize(pooled.device)
+        targets, pad = self.chunk_targets(targets.to(pooled.device, torch.float32), pad)
+        if targets.shape != (pooled.shape[0], self.head_width):
+            raise ValueError(f"targets must be (B,{self.config.action_dim}), got {tuple(targets.shape)}")
+        eng = self._engine()
+        with torch.no_grad():
+            B, nb = pooled.shape[0], int(buckets)
+            R = B * self.flow_noise_draws
+            t = ((torch.arange(R, device=pooled.device) % nb).to(torch.float32) + 0.5) / float(nb)
+            seed, offset = self.flow_time_loss_draw()
+            saved = eng.head_saved(B)
+            delays = torch.zeros(R, dtype=torch.int32, device=pooled.device) if self.flow_prefix is not None else None
+            u = eng.head_flow_prepare(targets.contiguous(), saved, seed=seed, offset=offset, t=t, delays=delays)
+            v, _ = eng.head_forward(self._flat, pooled, states.to(pooled.device, torch.float32), saved=saved, normalized_actions=True)
+            out = eng.head_loss_per_time(v, u, t, nb, pad=pad)
+            return torch.where(out[:, 1] > 0, out[:, 0] / out[:, 1].clamp_min(1.0), torch.zeros_like(out[:, 0])), out[:, 1]
 
     def chunk_targets(self, targets: torch.Tensor, pad=None):
         """-> (targets flattened to (B, K * A), pad (B, K) bool or None).  Targets are (B, K, A); (B, A) only when K == 1 (where a longer (B, T, A) gives its

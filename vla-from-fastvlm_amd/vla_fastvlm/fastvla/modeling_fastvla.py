@@ -29,7 +29,7 @@ class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
                  action_loss: Optional[str] = None, action_loss_beta: Optional[float] = None, temporal_ensemble_coeff: Optional[float] = None,
                  action_dim_weights=None, action_step_weights=None, action_head: Optional[str] = None, flow_steps: Optional[int] = None,
                  flow_time_dim: Optional[int] = None, flow_time_dist: Optional[str] = None, flow_seed: Optional[int] = None, rtc: Optional[bool] = None,
-                 rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None,
+                 flow_time_range=None, flow_time_stratify: Optional[bool] = None, rtc_schedule: Optional[str] = None, rtc_max_guidance_weight: Optional[float] = None, rtc_execution_horizon: Optional[int] = None,
                  flow_noise_draws: Optional[int] = None, flow_prefix_max_delay: Optional[int] = None, flow_prefix_delay_dist: Optional[str] = None,
                  flow_prefix_delay_rate: Optional[float] = None, rtc_method: Optional[str] = None, rtc_prefix_steps: Optional[int] = None,
                  flow_solver: Optional[str] = None, flow_samples: Optional[int] = None, flow_select: Optional[str] = None,
@@ -54,6 +54,17 @@ class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
         same weights give the same loss.  predict with autograd enabled on the head raises RuntimeError: sampling is not differentiated.  flow_seed: the noise
         streams' seed (default: torch's initial seed).  Twins: FASTVLA_FLOW_STEPS, FASTVLA_FLOW_TIME_DIM, FASTVLA_FLOW_TIME_DIST.  A policy that does not
         ask for flow calls nothing new.
+
+        flow_time_dist="beta:<alpha>,<beta>" | "pi0" (flow head; FASTVLA_FLOW_TIME_DIST takes the same strings): the training time as pi0 and SmolVLA draw it --
+        tau ~ Beta(alpha, beta), both in [0.25, 32]; "pi0" is "beta:1.5,1.0" on flow_time_range=(0.001, 1.0), which puts the mass on the noisy end and never
+        reaches t = 0.  flow_time_range=(lo, hi) (FASTVLA_FLOW_TIME_RANGE="lo:hi"): t = lo + (hi - lo) tau for any distribution, 0 <= lo < hi <= 1.
+        flow_time_stratify=True (FASTVLA_FLOW_TIME_STRATIFY; needs flow_noise_draws = S > 1): draw s of an observation takes the s-th of S equal-probability
+        strata of tau, the cheapest variance reduction of an S-draw step.  All three go through ONE inverse CDF on the uniform the noising kernel already draws
+        (fv_head_set_flow_time): eps, the prefix delay and the dropout stream do not move, and a policy that asks for none launches what it launched.  The bare
+        word "beta" is a ValueError: a Beta without its parameters names no distribution.  hip_extras.json records the string under "time_dist", and
+        "time_range" / "time_stratify" only when set; a resumed Trainer continues bit for bit.  flow_loss_per_time(batch, buckets) is the metric to judge a
+        time distribution with.  ValueError, naming both settings and before any engine exists, for strata with one draw and for any of the three given
+        explicitly with a regression head.
 
         flow_noise_draws=S (flow head, 1 .. 16, default 1; FASTVLA_FLOW_NOISE_DRAWS): S noise draws (t, eps) per observation wherever targets are noised --
         the train step on every route, compute_loss / forward(batch) in train() and in eval() mode (a smoother evaluation loss).  One step then computes the
@@ -106,8 +117,8 @@ class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
         self.options = resolve_policy_options(      # (every option is resolved and refused here, before any engine exists)
             chunk_size=chunk_size, n_action_steps=n_action_steps, action_loss=action_loss, action_loss_beta=action_loss_beta,
             temporal_ensemble_coeff=temporal_ensemble_coeff, action_dim_weights=action_dim_weights, action_step_weights=action_step_weights,
-            action_head=action_head, flow_steps=flow_steps, flow_time_dim=flow_time_dim, flow_time_dist=flow_time_dist, flow_seed=flow_seed, rtc=rtc,
-            rtc_schedule=rtc_schedule, rtc_max_guidance_weight=rtc_max_guidance_weight, rtc_execution_horizon=rtc_execution_horizon,
+            action_head=action_head, flow_steps=flow_steps, flow_time_dim=flow_time_dim, flow_time_dist=flow_time_dist, flow_time_range=flow_time_range,
+            flow_time_stratify=flow_time_stratify, flow_seed=flow_seed, rtc=rtc, rtc_schedule=rtc_schedule, rtc_max_guidance_weight=rtc_max_guidance_weight, rtc_execution_horizon=rtc_execution_horizon,
             flow_noise_draws=flow_noise_draws, flow_prefix_max_delay=flow_prefix_max_delay, flow_prefix_delay_dist=flow_prefix_delay_dist,
             flow_prefix_delay_rate=flow_prefix_delay_rate, rtc_method=rtc_method, rtc_prefix_steps=rtc_prefix_steps, flow_solver=flow_solver,
             flow_samples=flow_samples, flow_select=flow_select, flow_coherence_decay=flow_coherence_decay)
@@ -270,6 +281,20 @@ class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
         targets, pad = self.model.chunk_targets(batch["actions"], batch.get("action_is_pad"))
         pooled = self.model.features(images, tasks, device=device)
         return self.model.action_error_per_dim(pooled, states, targets, pad)
+
+    @torch.no_grad()
+    def flow_loss_per_time(self, batch: Dict[str, torch.Tensor | List[str]], buckets: int = 10):
+        """-> (mse, count), each (buckets,) on the device: the velocity error of the flow head by time bucket over the batch's non-padded steps (normalised
+        space, unweighted) -- the metric a time distribution (flow_time_dist, flow_time_range) is judged with.  One backbone forward; head row r is noised at
+        the explicit time ((r mod buckets) + 0.5) / buckets from noise at a fixed offset of the flow seed: repeatable, no dropout, no counter advances."""
+        images, states, tasks = batch["images"], batch["states"], batch["tasks"]
+        device = images.device
+        images = self.processor.prepare_images(images, device)
+        states = self.processor.prepare_states(states, device)
+        tasks = self.processor.prepare_tasks(tasks, batch_size=images.shape[0])
+        targets, pad = self.model.chunk_targets(batch["actions"], batch.get("action_is_pad"))
+        pooled = self.model.features(images, tasks, device=device)
+        return self.model.flow_loss_per_time(pooled, states, targets, pad, buckets)
 
     @property
     def chunk_size(self) -> int:

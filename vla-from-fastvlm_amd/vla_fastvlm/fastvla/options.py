@@ -72,28 +72,95 @@ FLOW_MIN_PERIOD, FLOW_MAX_PERIOD = 4e-3, 4.0      # pi0's periods of the time em
 FLOW_DIST_A, FLOW_DIST_B = 0.0, 1.0                # logit-normal time: t = sigmoid(a + b n)
 
 
-def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, flow_time_dist=None) -> Dict:
+FLOW_TIME_PI0 = ("beta", 1.5, 1.0, (0.001, 1.0))   # pi0 / SmolVLA: tau ~ Beta(1.5, 1), t = 0.001 + 0.999 tau
+FLOW_TIME_FORMS = "'uniform', 'logit_normal', 'beta:<alpha>,<beta>' (e.g. 'beta:1.5,1.0') or 'pi0' (= 'beta:1.5,1.0' on the range (0.001, 1.0))"
+
+
+def parse_flow_time_dist(raw) -> Dict:
+    """-> {"dist": "uniform" | "logit_normal" | "beta", "a", "b", "range": (lo, hi) or None, "name": the canonical string a checkpoint records}.  ValueError,
+    giving the accepted forms, for anything else -- the bare word "beta" included: a Beta without its parameters names no distribution."""
+    from fastvla_hip import _lib
+    text = str(raw).strip().lower()
+    if text in _lib.FLOW_TIME_DISTS:
+        return {"dist": text, "a": FLOW_DIST_A, "b": FLOW_DIST_B, "range": None, "name": text}
+    if text == "pi0":
+        dist, a, b, rng = FLOW_TIME_PI0
+        return {"dist": dist, "a": a, "b": b, "range": rng, "name": f"beta:{a!r},{b!r}"}
+    if text.startswith("beta:"):
+        try:
+            a, b = (float(x) for x in text[5:].split(","))
+        except ValueError:
+            raise ValueError(f"flow_time_dist must be {FLOW_TIME_FORMS}, got {raw!r}") from None
+        lo, hi = _lib.FLOW_BETA_RANGE
+        if not (lo <= a <= hi and lo <= b <= hi):      # (NaN fails both)
+            raise ValueError(f"flow_time_dist={raw!r}: both Beta parameters must lie in [{lo:g}, {hi:g}]")
+        return {"dist": "beta", "a": a, "b": b, "range": None, "name": f"beta:{a!r},{b!r}"}
+    raise ValueError(f"flow_time_dist must be {FLOW_TIME_FORMS}, got {raw!r}")
+
+
+def parse_flow_time_range(raw, name: str = "flow_time_range"):
+    """(lo, hi) or "lo:hi" -> (lo, hi) floats with 0 <= lo < hi <= 1; ValueError otherwise"""
+    try:
+        lo, hi = (float(x) for x in (raw.split(":") if isinstance(raw, str) else raw))
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be (lo, hi){' written lo:hi' if name.isupper() else ''} with 0 <= lo < hi <= 1, got {raw!r}") from None
+    if not 0.0 <= lo < hi <= 1.0:
+        raise ValueError(f"{name} must be (lo, hi) with 0 <= lo < hi <= 1, got {raw!r}")
+    return lo, hi
+
+
+def _flag(raw: str) -> bool:
+    return raw.lower() not in ("0", "false", "no", "off")
+
+
+def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, flow_time_dist=None, flow_time_range=None, flow_time_stratify=None, *,
+                         flow_noise_draws: Optional[int] = None) -> Dict:
     """-> {"action_head": "regression" | "flow", "steps", "flow": FastVLAEngine.set_head_flow's keyword arguments or None}: explicit arguments, else the
     FASTVLA_ACTION_HEAD / FASTVLA_FLOW_STEPS / FASTVLA_FLOW_TIME_DIM / FASTVLA_FLOW_TIME_DIST twins, else ("regression", 10, 64, "uniform").  A regression head
-    neither reads nor checks the flow arguments and twins.  ValueError for an
-    unknown head or time distribution, steps < 1, a time_dim that is not a positive even integer."""
+    neither reads nor checks the flow twins.  ValueError for an
+    unknown head or time distribution, steps < 1, a time_dim that is not a positive even integer.
+    The training time beyond set_head_flow's two distributions -- flow_time_dist "beta:<alpha>,<beta>" | "pi0", flow_time_range=(lo, hi)
+    (FASTVLA_FLOW_TIME_RANGE="lo:hi"), flow_time_stratify (FASTVLA_FLOW_TIME_STRATIFY) -- adds ONE key, and only when asked for:
+    "time": FastVLAEngine.set_head_flow_time's keyword arguments plus "name", the string a checkpoint records.  flow_time_range / flow_time_stratify = False:
+    off, whatever the twin says.  flow_noise_draws: the resolved S, when the caller has it -- ValueError, naming both settings, for strata with one draw;
+    and for any of the three given explicitly with a regression head."""
     from fastvla_hip import _lib
 
     head = str(pick(action_head, "FASTVLA_ACTION_HEAD", str, "regression")).lower()
     if head not in ("regression", "flow"):
         raise ValueError(f"action_head must be 'regression' or 'flow', got {head!r}")
     if head != "flow":      # the FASTVLA_FLOW_* twins are read and checked for a flow head only: a stray value cannot make a regression policy (or its load) raise
+        for name, val in (("flow_time_dist", flow_time_dist), ("flow_time_range", flow_time_range), ("flow_time_stratify", flow_time_stratify)):
+            if val is not None and val is not False:
+                raise ValueError(f"{name} needs action_head='flow' (the regression head draws no time). Got {name}={val!r}, action_head={head!r}.")
         return {"action_head": head, "steps": 10, "flow": None}
     steps, dim = pick(flow_steps, "FASTVLA_FLOW_STEPS", int, 10), pick(flow_time_dim, "FASTVLA_FLOW_TIME_DIM", int, 64)
-    dist = str(pick(flow_time_dist, "FASTVLA_FLOW_TIME_DIST", str, "uniform")).lower()
+    tdist = parse_flow_time_dist(pick(flow_time_dist, "FASTVLA_FLOW_TIME_DIST", str, "uniform"))
+    dist = tdist["dist"] if tdist["dist"] in _lib.FLOW_TIME_DISTS else "uniform"      # (set_head_flow's own: a Beta rides on the uniform head)
     if int(steps) != steps or steps < 1:
         raise ValueError(f"flow_steps must be an integer >= 1, got {steps}")
     if int(dim) != dim or dim < 2 or dim % 2:
         raise ValueError(f"flow_time_dim must be a positive even integer, got {dim}")
-    if dist not in _lib.FLOW_TIME_DISTS:
-        raise ValueError(f"flow_time_dist must be one of {sorted(_lib.FLOW_TIME_DISTS)}, got {dist!r}")
     flow = dict(time_dim=int(dim), min_period=FLOW_MIN_PERIOD, max_period=FLOW_MAX_PERIOD, time_dist=dist, dist_a=FLOW_DIST_A, dist_b=FLOW_DIST_B)
-    return {"action_head": head, "steps": int(steps), "flow": flow}
+    out = {"action_head": head, "steps": int(steps), "flow": flow}
+    rng = None if flow_time_range is False else pick(flow_time_range, "FASTVLA_FLOW_TIME_RANGE", lambda r: parse_flow_time_range(r, "FASTVLA_FLOW_TIME_RANGE"), None)
+    rng = tdist["range"] if rng is None else parse_flow_time_range(rng)      # (an explicit range wins over pi0's)
+    strat = False if flow_time_stratify is False else pick(flow_time_stratify, "FASTVLA_FLOW_TIME_STRATIFY", _flag, False)
+    if not isinstance(strat, (bool, int)) or strat not in (0, 1):
+        raise ValueError(f"flow_time_stratify must be a bool, got {strat!r}")
+    if tdist["dist"] == "beta" or rng is not None or strat:
+        lo, hi = rng or (0.0, 1.0)
+        out["time"] = dict(dist=tdist["dist"], a=float(tdist["a"]), b=float(tdist["b"]), t_lo=float(lo), t_hi=float(hi), stratify=bool(strat), name=tdist["name"])
+    if flow_noise_draws is not None:
+        check_flow_time_draws(out.get("time"), flow_noise_draws)
+    return out
+
+
+def check_flow_time_draws(time: Optional[Dict], draws: int) -> None:
+    """strata are dealt to the draws of one observation: ValueError, naming both settings, for flow_time_stratify with one draw"""
+    if time is not None and time["stratify"] and int(draws) == 1:
+        raise ValueError("flow_time_stratify=True needs flow_noise_draws > 1: the strata are dealt to the draws of one observation. "
+                         f"Got flow_time_stratify=True, flow_noise_draws={draws}.")
 
 
 def resolve_flow_solver(flow_solver=None, *, action_head: str) -> str:
@@ -239,6 +306,7 @@ class PolicyOptions:
                                                  "dim_weights": None, "step_weights": None})      # resolve_chunk_options' record
     action_head: str = "regression"
     flow: Optional[Dict] = None      # FastVLAEngine.set_head_flow's keyword arguments, None = the regression head
+    flow_time: Optional[Dict] = None      # resolve_flow_options' "time": set_head_flow_time's keyword arguments + "name"; None = set_head_flow's own distribution
     flow_steps: int = 10
     flow_seed: Optional[int] = None      # None: torch's initial seed
     noise_draws: int = 1
@@ -252,16 +320,17 @@ class PolicyOptions:
 
 def resolve_policy_options(*, chunk_size=None, n_action_steps=None, action_loss=None, action_loss_beta=None, temporal_ensemble_coeff=None,
                            action_dim_weights=None, action_step_weights=None, action_head=None, flow_steps=None, flow_time_dim=None, flow_time_dist=None,
-                           flow_seed=None, rtc=None, rtc_schedule=None, rtc_max_guidance_weight=None, rtc_execution_horizon=None, flow_noise_draws=None,
+                           flow_time_range=None, flow_time_stratify=None, flow_seed=None, rtc=None, rtc_schedule=None, rtc_max_guidance_weight=None, rtc_execution_horizon=None, flow_noise_draws=None,
                            flow_prefix_max_delay=None, flow_prefix_delay_dist=None, flow_prefix_delay_rate=None, rtc_method=None, rtc_prefix_steps=None,
                            flow_solver=None, flow_samples=None, flow_select=None, flow_coherence_decay=None) -> PolicyOptions:
     """Every option of a policy constructor, resolved and refused before any engine exists.  The resolvers run in this order -- chunk, flow, noise draws,
     solver, prefix, rtc, samples -- and the first ValueError wins."""
     chunk = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
     K, coeff = chunk["chunk_size"], chunk["temporal_ensemble_coeff"]
-    fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist)
+    fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist, flow_time_range, flow_time_stratify)
     head = fopts["action_head"]
     draws = resolve_flow_noise_draws(flow_noise_draws, action_head=head)
+    check_flow_time_draws(fopts.get("time"), draws)
     solver = resolve_flow_solver(flow_solver, action_head=head)
     prefix = resolve_prefix_options(flow_prefix_max_delay, flow_prefix_delay_dist, flow_prefix_delay_rate, action_head=head, chunk_size=K,
                                     temporal_ensemble_coeff=coeff)
@@ -270,7 +339,7 @@ def resolve_policy_options(*, chunk_size=None, n_action_steps=None, action_loss=
                                 prefix=prefix)
     sopts = resolve_flow_samples(flow_samples, flow_select, flow_coherence_decay, action_head=head, chunk_size=K,
                                  rtc_method=None if ropts is None else ropts.get("method", "guidance"))
-    return PolicyOptions(chunk=chunk, action_head=head, flow=fopts["flow"], flow_steps=fopts["steps"], flow_seed=flow_seed, noise_draws=draws, solver=solver,
+    return PolicyOptions(chunk=chunk, action_head=head, flow=fopts["flow"], flow_time=fopts.get("time"), flow_steps=fopts["steps"], flow_seed=flow_seed, noise_draws=draws, solver=solver,
                          prefix=prefix, rtc=ropts, samples=sopts["samples"], select=sopts["select"], decay=sopts["decay"])
 
 

@@ -86,6 +86,16 @@ class FastVLAPolicy(PreTrainedPolicy, FlowSurfaceMixin):
         pooled = self.model.features(images, tasks, device=images.device)
         return self.model.action_error_per_dim(pooled, states, targets, pad)
 
+    def flow_loss_per_time(self, batch: dict[str, Tensor], buckets: int = 10):
+        """-> (mse, count), each (buckets,) on the device: the flow head's velocity error by time bucket over the batch's non-padded steps (normalised space,
+        unweighted).  Head row r is noised at the explicit time ((r mod buckets) + 0.5) / buckets from noise at a fixed offset of the flow seed: repeatable, no
+        dropout, no counter advances"""
+        images, states, tasks = self._prepare_inputs(batch)
+        pad = batch.get("action_is_pad") if self.model.chunk_size > 1 else None
+        targets, pad = self.model.chunk_targets(batch[ACTION], pad)
+        pooled = self.model.features(images, tasks, device=images.device)
+        return self.model.flow_loss_per_time(pooled, states, targets, pad, buckets)
+
     def _resolve_input_keys(self) -> tuple[str, list[str]]:
         feats = self.config.input_features
         if not feats:

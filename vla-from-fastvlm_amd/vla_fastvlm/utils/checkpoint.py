@@ -35,6 +35,7 @@ EXTRAS_FILE = "hip_extras.json"
 # K * A wide, which the reference's config cannot say; a plain policy's extras file is byte for byte what it was
 # (+ "temporal_ensemble_coeff", "dim_weights", "step_weights" -- each only when set: select_action's temporal ensembling and the weights of the chunk loss)
 # "action_head" = {"type": "flow", "steps", "time_dim", "min_period", "max_period", "time_dist", "dist_a", "dist_b", "seed"} -- only for a flow-matching head
+# ("time_dist" is the option's string: "uniform" | "logit_normal" | "beta:1.5,1.0"; + "time_range" = [lo, hi] and "time_stratify" = true -- each only when set)
 # (FastVLAPolicy(action_head="flow")), whose fusion.0.weight is chunk_size * action_dim + time_dim columns wider than the regression head's
 # (+ "prefix_max_delay", and "prefix_delay_dist" / "prefix_delay_rate" for information -- only for a head with action-prefix conditioning
 # (flow_prefix_max_delay), whose fusion.0.weight has chunk_size more columns still)
@@ -123,12 +124,13 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
     state = torch.load(sd_path, map_location="cpu")
     chunk = read_extras(root).get("action_chunk") or {}
     check_head_width(state, config.action_dim, chunk, root)
+    head_kw = strata_need_draws(flow_kwargs(read_extras(root).get("action_head")))
     # the file decides: no record means the record's defaults (1, 1, "mse", 1.0), whatever the environment twins say -- a plain checkpoint loads as a plain policy
     policy = FastVLAPolicy(config, chunk_size=int(chunk.get("chunk_size", 1)), n_action_steps=int(chunk.get("n_action_steps", 1)),
                            action_loss=chunk.get("loss", "mse"), action_loss_beta=float(chunk.get("beta", 1.0)),
                            temporal_ensemble_coeff=chunk.get("temporal_ensemble_coeff", False), action_dim_weights=chunk.get("dim_weights", False),
                            action_step_weights=chunk.get("step_weights", False),      # (False: off, whatever the twin says)
-                           **flow_kwargs(read_extras(root).get("action_head")), **prefix_kwargs(read_extras(root).get("action_head")))
+                           **head_kw, **prefix_kwargs(read_extras(root).get("action_head")))
     check_fusion_width(state, policy, root)
     vlm = {k[len(BACKBONE_PREFIX):]: v for k, v in state.items() if k.startswith(BACKBONE_PREFIX)}
     if vlm:
@@ -161,8 +163,23 @@ def flow_kwargs(rec) -> dict:
                          "distribution would differ from the one the weights were trained with")
     kw = {"action_head": "flow", "flow_steps": int(rec.get("steps", 10)), "flow_time_dim": int(rec["time_dim"]), "flow_time_dist": rec.get("time_dist", "uniform"),
           "flow_seed": rec.get("seed")}
+    if rec.get("time_range"):      # ("time_dist" may be "beta:1.5,1.0"; these two are written only when set: a record without them maps to what it mapped to)
+        kw["flow_time_range"] = tuple(float(x) for x in rec["time_range"])
+    if rec.get("time_stratify"):
+        kw["flow_time_stratify"] = True
     if rec.get("solver"):      # (written only when it is not Euler: an Euler run's record, and what it maps to, is what it was)
         kw["flow_solver"] = str(rec["solver"])
+    return kw
+
+
+def strata_need_draws(kw: dict) -> dict:
+    """flow_kwargs' result for a LOAD: the strata are dealt to the draws of a training step, and the number of draws is a property of the run that no checkpoint
+    records -- a load without FASTVLA_FLOW_NOISE_DRAWS > 1 (inference, say) gets the recorded distribution without strata (False: off, whatever the twin says); a
+    resumed Trainer builds its policy from the run's own options"""
+    if kw.get("flow_time_stratify"):
+        from ..fastvla.options import resolve_flow_noise_draws
+        if resolve_flow_noise_draws(None, action_head="flow") == 1:
+            kw = {**kw, "flow_time_stratify": False}
     return kw
 
 
