@@ -176,6 +176,25 @@ int fv_vision_forward(fv_handle* h, const void* pix, int B, void* img_tokens, vo
  * image evaluated alone then gets the tokens it gets inside a batch, bit for bit (measured), at ~0.9 ms per step of a one-observation control loop (4.75 instead of 3.83 ms).
  * Off by default (the host side switches it with FASTVLA_BATCH_INVARIANT=1).  The row-segmented depthwise march is bit-identical and stays on. */
 int fv_set_batch_invariant(fv_handle* h, int on);
+/* Prompt reuse.  In literal mode (fv_llm_forward_pooled with Ni == 0) the decoder never sees the image: pooled (B, H) is a function of (ids, lens, B, T,
+ * pool_mode) and the decoder's weights alone, and a control loop sends the same task string for a whole episode.  The handle keeps ONE slot in device memory
+ * (sized at fv_create for max_batch x max_text_tokens): the key of the last literal call and its pooled rows.  Every literal call starts with a one-block
+ * probe that compares its key with the slot ON THE DEVICE and ends with a commit launch; on a hit every decoder kernel of the call returns at once and the
+ * commit copies the kept rows out, on a miss the decoder runs as ever and the commit stores key and rows.  No host read, no allocation, no synchronisation:
+ * the call stays capturable, and a captured graph decides anew on every replay.  A hit returns the bits a recomputation would give.
+ *   - compared: B, T, pool_mode, lens[0 .. B), and of every row its first max(min(lens[b], T), 1) ids -- ids past lens[b] cannot reach pooled (causal
+ *     attention with keys >= lens[b] masked, row-wise kernels everywhere else, pooling over rows < max(lens[b], 1)).
+ *   - invalidated (stream-ordered clear of the slot where the writer takes a stream, and a forced miss of the next call) by everything else pooled depends
+ *     on: fv_load_weights / fv_load_weights_cb, fv_train_commit (decoder and tower), fv_train_lora_commit, fv_train_lora_merge,
+ *     fv_train_lora_init_magnitude, fv_train_set_options, fv_train_set_forward_f16, fv_set_batch_invariant, fv_set_prompt_reuse.  llm_precision is fixed at
+ *     fv_create; the few-row kernel forms follow B and T, which are part of the key.
+ *   - never used by the spliced call (Ni > 0), fv_llm_forward_pooled_prefixed, any fv_train_* entry point, or a call whose B x T the slot cannot hold.
+ *   - ONE handle serves ONE stream at a time (as its workspace already demands): the slot is read and written in stream order.
+ * On by default; on == 0 switches it off (the host side does so for FASTVLA_PROMPT_REUSE=0).  While fv_profile is on, fv_profile_read leaves the flops and
+ * bytes of a hit call's skipped launches out (their time and launch count stay) and does not list them among the GEMM shapes. */
+int fv_set_prompt_reuse(fv_handle* h, int on);
+/* Literal calls that used the slot, and how many of them hit, since fv_create (device counters; synchronises the device). */
+int fv_prompt_reuse_stats(fv_handle* h, uint64_t* calls_out, uint64_t* hits_out);
 /* fv_preprocess + fv_vision_forward in one (the on-device input pipeline): the stem kernel samples the SOURCE images
  * (B,C,Hin,Win) f32 | u8 through resize_with_pad's arithmetic itself (model/fastvlm_adapter.py:36-55,479-488 then :533), so the letterboxed
  * (B,S,S,4) frame is never written or read.  Same tokens as the two-call form, bit for bit.  Needs the fused stem (first stage width 96). */

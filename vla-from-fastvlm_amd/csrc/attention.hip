@@ -18,12 +18,14 @@ namespace {
 struct AttnParams {
   const bf16_t *q, *k, *v; bf16_t* out; const int32_t* lens;
   int ldq, ldk, ldv, ldo, B, T, heads, kv_heads, causal, len_add; float scale;
+  const unsigned* skip = nullptr;   // prompt reuse (common.h FV_SKIP_EXIT): read by attention_kernel, the decoder's; the tower's attention32_kernel never sees one
 };
 
 // MASKED = false: no causal mask, no key-length mask and T % 64 == 0 (the FastViT-HD MHSA): the softmax then costs one
 // FMA (scale * log2e folded in) and one v_exp_f32 per score -- with head_dim 32 this kernel is VALU-bound, not MFMA-bound.
 template <int D, bool MASKED>
 __global__ __launch_bounds__(256) void attention_kernel(AttnParams p) {
+  FV_SKIP_EXIT(p.skip);
   constexpr int KS = D / 32;        // k-steps of the S^T product
   constexpr int DT = D / 16;        // 16-row tiles of O^T
   constexpr int KLD = D + 8;        // padded K row (elements)
@@ -300,13 +302,15 @@ __global__ __launch_bounds__(256, 2) void attention32_kernel(AttnParams p) {   /
 
 int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ldq, int ldk, int ldv, bf16_t* out,
                      int ldo, int B, int T, int heads, int kv_heads, int D, int causal, const int32_t* lens,
-                     int len_add, float scale, hipStream_t s) {
+                     int len_add, float scale, hipStream_t s, const unsigned* skip) {
   if (!q || !k || !v || !out) return fv_fail(FV_ERR_ARG, "attention: null pointer");
   if (B <= 0 || T <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads) return fv_fail(FV_ERR_ARG, "attention: bad shape B=%d T=%d heads=%d kv=%d", B, T, heads, kv_heads);
   if ((ldq | ldk | ldv) % 8 || ldo % 4) return fv_fail(FV_ERR_ARG, "attention: row strides must be multiples of 8 (out: 4)");
   if (ldq < heads * D || ldk < kv_heads * D || ldv < kv_heads * D || ldo < heads * D) return fv_fail(FV_ERR_ARG, "attention: row stride smaller than heads*D");
   if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15 || ((uintptr_t)out & 7)) return fv_fail(FV_ERR_ARG, "attention: misaligned pointer");
   AttnParams p{q, k, v, out, lens, ldq, ldk, ldv, ldo, B, T, heads, kv_heads, causal, len_add, scale};
+  if (skip && D == 32 && !(causal || lens || (T & 63))) return fv_fail(FV_ERR_ARG, "attention: the unmasked head_dim 32 kernel takes no skip word");
+  p.skip = skip;
   const long blocks = (long)B * heads * ((T + 63) / 64);
   if (blocks > 0x7fffffffL) return fv_fail(FV_ERR_ARG, "attention: grid too large");
   const dim3 grid((unsigned)blocks), blk(256);

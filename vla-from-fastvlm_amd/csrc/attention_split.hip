@@ -181,7 +181,8 @@ __device__ __forceinline__ void copy_flat(char* __restrict__ dst, const char* __
 // forward / dq block would otherwise convert for itself (14 q heads / 2 kv heads x 3 query blocks: ~15x at the training shape)
 template <int D>
 __global__ __launch_bounds__(256) void attn_prep_kv_kernel(const float* __restrict__ qkv, int ld, int T, int heads, int kv_heads, const float2* __restrict__ rope,
-                                                           char* __restrict__ rec, int nchunks) {
+                                                           char* __restrict__ rec, int nchunks, const unsigned* skip = nullptr) {
+  FV_SKIP_EXIT(skip);
   using GEO = ASGeo<D>;
   extern __shared__ __attribute__((aligned(16))) char as_smem[];
   bf16_t* a0 = reinterpret_cast<bf16_t*>(as_smem);
@@ -214,7 +215,9 @@ __global__ __launch_bounds__(256) void attn_prep_kv_kernel(const float* __restri
 template <int D, bool GQ>
 __global__ __launch_bounds__(GQ ? 512 : 256, 2) void attn_fwd_split_kernel(const float* __restrict__ qkv, int ld, bf16_t* __restrict__ out_hi, bf16_t* __restrict__ out_lo, int ldo,
                                                                  const int32_t* __restrict__ lens, int len_add, int T, int heads, int kv_heads, float scale,
-                                                                 const float2* __restrict__ rope, float* __restrict__ lse, const char* __restrict__ rec, int nchunks) {
+                                                                 const float2* __restrict__ rope, float* __restrict__ lse, const char* __restrict__ rec, int nchunks,
+                                                                 const unsigned* skip = nullptr) {
+  FV_SKIP_EXIT(skip);
   using GEO = ASGeo<D>;
   constexpr int KS = D / 32, DT = D / 16, NT = GEO::NT, RB = GEO::RB, LDN = D + 8;
   extern __shared__ __attribute__((aligned(16))) char as_smem[];
@@ -650,7 +653,7 @@ size_t attention_split_scratch_bytes(int B, int T, int kv_heads, int D) {
   return (size_t)B * kv_heads * ((T + ACH - 1) / ACH) * rec;
 }
 
-static int launch_prep_kv(const float* qkv, int ld, int B, int T, int heads, int kv_heads, int D, const float2* rope, char* rec, hipStream_t s) {
+static int launch_prep_kv(const float* qkv, int ld, int B, int T, int heads, int kv_heads, int D, const float2* rope, char* rec, hipStream_t s, const unsigned* skip = nullptr) {
   static bool attr = false;
   if (!attr) {
     FV_TRY_RC(set_lds(attn_prep_kv_kernel<64>, ASGeo<64>::REC));
@@ -658,14 +661,14 @@ static int launch_prep_kv(const float* qkv, int ld, int B, int T, int heads, int
     attr = true;
   }
   const int nch = (T + ACH - 1) / ACH;
-  if (D == 64) hipLaunchKernelGGL(attn_prep_kv_kernel<64>, dim3(B * kv_heads * nch), dim3(256), ASGeo<64>::REC, s, qkv, ld, T, heads, kv_heads, rope, rec, nch);
-  else hipLaunchKernelGGL(attn_prep_kv_kernel<128>, dim3(B * kv_heads * nch), dim3(256), ASGeo<128>::REC, s, qkv, ld, T, heads, kv_heads, rope, rec, nch);
+  if (D == 64) hipLaunchKernelGGL(attn_prep_kv_kernel<64>, dim3(B * kv_heads * nch), dim3(256), ASGeo<64>::REC, s, qkv, ld, T, heads, kv_heads, rope, rec, nch, skip);
+  else hipLaunchKernelGGL(attn_prep_kv_kernel<128>, dim3(B * kv_heads * nch), dim3(256), ASGeo<128>::REC, s, qkv, ld, T, heads, kv_heads, rope, rec, nch, skip);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
 
 int launch_attention_split_fwd(const float* qkv, int ld, bf16_t* out_hi, bf16_t* out_lo, int ldo, int B, int T, int heads, int kv_heads, int D,
-                               const int32_t* lens, int len_add, float scale, const float2* rope, float* lse, void* scratch, hipStream_t s) {
+                               const int32_t* lens, int len_add, float scale, const float2* rope, float* lse, void* scratch, hipStream_t s, const unsigned* skip) {
   if (!qkv || !out_hi || !out_lo || !scratch) return fv_fail(FV_ERR_ARG, "attention_split_fwd: null pointer");
   if (D != 64 && D != 128) return fv_fail(FV_ERR_UNSUPPORTED, "attention_split_fwd: head_dim must be 64 or 128 (got %d)", D);
   if (B <= 0 || T <= 0 || heads <= 0 || kv_heads <= 0 || heads % kv_heads || ld % 4 || ld < (heads + 2 * kv_heads) * D || ldo % 8 || ldo < heads * D)
@@ -683,24 +686,24 @@ int launch_attention_split_fwd(const float* qkv, int ld, bf16_t* out_hi, bf16_t*
 #endif
   char* rec = static_cast<char*>(scratch);
   const int nch = (T + ACH - 1) / ACH, grp = heads / kv_heads;
-  FV_TRY_RC(launch_prep_kv(qkv, ld, B, T, heads, kv_heads, D, rope, rec, s));
+  FV_TRY_RC(launch_prep_kv(qkv, ld, B, T, heads, kv_heads, D, rope, rec, s, skip));
   static const bool no_gq = fv_ab_env("FASTVLA_ATTN_NO_GQ") != nullptr;   // A/B: one block per q head
   const bool gq = !no_gq && grp >= 2 && grp <= 8;
   if (D == 64) {
     if (gq) {
       const long nb = (long)B * kv_heads * ((T + 16 * ASGeo<64>::NT - 1) / (16 * ASGeo<64>::NT));
-      hipLaunchKernelGGL((attn_fwd_split_kernel<64, true>), dim3((unsigned)nb), dim3(64 * grp), as_fwd_lds<64>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch);
+      hipLaunchKernelGGL((attn_fwd_split_kernel<64, true>), dim3((unsigned)nb), dim3(64 * grp), as_fwd_lds<64>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch, skip);
     } else {
       const long nb = (long)B * heads * ((T + ASGeo<64>::RB - 1) / ASGeo<64>::RB);
-      hipLaunchKernelGGL((attn_fwd_split_kernel<64, false>), dim3((unsigned)nb), dim3(256), as_fwd_lds<64>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch);
+      hipLaunchKernelGGL((attn_fwd_split_kernel<64, false>), dim3((unsigned)nb), dim3(256), as_fwd_lds<64>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch, skip);
     }
   } else {
     if (gq) {
       const long nb = (long)B * kv_heads * ((T + 16 * ASGeo<128>::NT - 1) / (16 * ASGeo<128>::NT));
-      hipLaunchKernelGGL((attn_fwd_split_kernel<128, true>), dim3((unsigned)nb), dim3(64 * grp), as_fwd_lds<128>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch);
+      hipLaunchKernelGGL((attn_fwd_split_kernel<128, true>), dim3((unsigned)nb), dim3(64 * grp), as_fwd_lds<128>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch, skip);
     } else {
       const long nb = (long)B * heads * ((T + ASGeo<128>::RB - 1) / ASGeo<128>::RB);
-      hipLaunchKernelGGL((attn_fwd_split_kernel<128, false>), dim3((unsigned)nb), dim3(256), as_fwd_lds<128>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch);
+      hipLaunchKernelGGL((attn_fwd_split_kernel<128, false>), dim3((unsigned)nb), dim3(256), as_fwd_lds<128>(), s, qkv, ld, out_hi, out_lo, ldo, lens, len_add, T, heads, kv_heads, scale, rope, lse, rec, nch, skip);
     }
   }
   FV_HIP_CHECK(hipGetLastError());

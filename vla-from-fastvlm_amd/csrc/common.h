@@ -9,6 +9,11 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define FV_WAVE 64
 
+// Prompt reuse (engine.hip, fv_set_prompt_reuse): every kernel of the literal decoder call takes `const unsigned* skip`, the device word the call's
+// prompt_probe_kernel wrote, and this is its FIRST statement -- ahead of any LDS or barrier use, the same answer for every lane of every block.
+// skip == nullptr (every other caller: the tower, training, LoRA, splice, the prefix path) is the kernel as it was.
+#define FV_SKIP_EXIT(skip) do { if ((skip) != nullptr && *(skip) != 0u) return; } while (0)
+
 __device__ __forceinline__ float bf2f(bf16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 // plain cast: hipcc emits v_cvt_pk_bf16_f32 (RNE, NaN-preserving) on gfx950
 __device__ __forceinline__ bf16_t f2bf(float f) {

@@ -13,7 +13,8 @@ namespace {
 __global__ __launch_bounds__(256) void embed_gather_kernel(const int32_t* __restrict__ ids,
                                                             const bf16_t* __restrict__ table,
                                                             const float* __restrict__ img, float* __restrict__ x, int T,
-                                                            int Ni, int H, int vocab, long rows) {
+                                                            int Ni, int H, int vocab, long rows, const unsigned* skip) {
+  FV_SKIP_EXIT(skip);
   // one wave per output row; rows = B * (Ni + T)
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -42,7 +43,8 @@ __global__ __launch_bounds__(256) void embed_gather_kernel(const int32_t* __rest
 template <bool F16>   // F16: y receives fp16 bits (11 significant bits: the single-pass operand of llm_precision = 2's gate/up GEMM)
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                        bf16_t* __restrict__ y, bf16_t* __restrict__ y_lo, int ldy, int rows,
-                                                       int H, float eps, unsigned* __restrict__ sat, int lo8) {
+                                                       int H, float eps, unsigned* __restrict__ sat, int lo8, const unsigned* skip) {
+  FV_SKIP_EXIT(skip);
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -78,7 +80,8 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ 
 
 // thread = (row, head, 8 consecutive d in the first half); cos/sin come from a host-built table [T][D/2] (float2)
 __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ qkv, const float2* __restrict__ cs, int ld,
-                                                    long rows, int T, int nheads_total, int D) {
+                                                    long rows, int T, int nheads_total, int D, const unsigned* skip) {
+  FV_SKIP_EXIT(skip);
   const int per_head = D / 16;  // 8-wide chunks in half a head
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const long total = rows * nheads_total * per_head;
@@ -105,7 +108,8 @@ __global__ __launch_bounds__(256) void rope_kernel(bf16_t* __restrict__ qkv, con
 
 // fp32 variant of the RoPE for the parity-mode decoder (qkv kept in fp32): thread = (row, head, 4 d of the first half)
 __global__ __launch_bounds__(256) void rope_f32_kernel(float* __restrict__ qkv, const float2* __restrict__ cs, int ld,
-                                                        long rows, int T, int nheads_total, int D) {
+                                                        long rows, int T, int nheads_total, int D, const unsigned* skip) {
+  FV_SKIP_EXIT(skip);
   const int per_head = D / 8;
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= rows * nheads_total * per_head) return;
@@ -135,7 +139,8 @@ template <int DPT, int NT>
 __global__ __launch_bounds__(256) void attention_f32_kernel(const float* __restrict__ qkv, bf16_t* __restrict__ out_hi,
                                                              bf16_t* __restrict__ out_lo, const int32_t* __restrict__ lens,
                                                              int len_add, int ld, int ldo, int T, int heads, int kv_heads,
-                                                             int QT, float scale, int lo8) {
+                                                             int QT, float scale, int lo8, const unsigned* skip) {
+  FV_SKIP_EXIT(skip);
   constexpr int D = DPT * NT;
   extern __shared__ __attribute__((aligned(16))) float skv[];  // [2][64][D]
   float* sK = skv;
@@ -247,7 +252,8 @@ __global__ __launch_bounds__(256, 2) void attention_f32_mfma_kernel(const float*
                                                                      bf16_t* __restrict__ out_lo, const int32_t* __restrict__ lens,
                                                                      int len_add, int ld, int ldo, int T, int heads, int kv_heads,
                                                                      float scale, const float2* __restrict__ rope,
-                                                                     const float* __restrict__ pre, int ldp, int Np, float* __restrict__ lse, int lo8) {
+                                                                     const float* __restrict__ pre, int ldp, int Np, float* __restrict__ lse, int lo8, const unsigned* skip) {
+  FV_SKIP_EXIT(skip);
   // lse != null (training, Np == 0): the row statistics max + log(sum) of every (batch, head, query) for attn_bwd_* (train_kernels.hip)
   // pre != null (image-prefix reuse): the sequence is Np cached prefix positions + Ts = T - Np new ones.  qkv and
   // the outputs hold ONLY the new rows (row b * Ts + t - Np); keys / values of positions < Np come from `pre`, rows
@@ -398,7 +404,8 @@ __global__ __launch_bounds__(256, 2) void attention_f32_mfma_kernel(const float*
 // one block per batch row: final RMSNorm on the pooled row(s).  mode 0 = last_token, 1 = mean over valid rows.
 __global__ __launch_bounds__(256) void pool_norm_kernel(const float* __restrict__ x, const int32_t* __restrict__ lens,
                                                          const float* __restrict__ w, float* __restrict__ pooled,
-                                                         int Ttot, int Ni, int H, float eps, int mode) {
+                                                         int Ttot, int Ni, int H, float eps, int mode, const unsigned* skip) {
+  FV_SKIP_EXIT(skip);
   __shared__ float red[4];
   const int b = blockIdx.x, tid = threadIdx.x;
   int len = lens ? lens[b] : (Ttot - Ni);
@@ -423,22 +430,22 @@ __global__ __launch_bounds__(256) void pool_norm_kernel(const float* __restrict_
 }  // namespace
 
 int launch_embed_gather(const int32_t* ids, const bf16_t* table, const float* img_tokens, float* x, int B, int T,
-                        int Ni, int H, int vocab, hipStream_t s) {
+                        int Ni, int H, int vocab, hipStream_t s, const unsigned* skip) {
   if (!ids || !table || !x) return fv_fail(FV_ERR_ARG, "embed_gather: null pointer");
   if (Ni > 0 && !img_tokens) return fv_fail(FV_ERR_ARG, "embed_gather: Ni > 0 without image tokens");
   if (B <= 0 || T <= 0 || Ni < 0 || H % 8 || vocab <= 0) return fv_fail(FV_ERR_ARG, "embed_gather: bad shape");
   const long rows = (long)B * (Ni + T);
-  hipLaunchKernelGGL(embed_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ids, table, img_tokens, x, T, Ni, H, vocab, rows);
+  hipLaunchKernelGGL(embed_gather_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ids, table, img_tokens, x, T, Ni, H, vocab, rows, skip);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
 
-int launch_rmsnorm(const float* x, const float* w, bf16_t* y, bf16_t* y_lo, int ldy, int rows, int H, float eps, hipStream_t s, int f16, unsigned* sat, int lo8) {
+int launch_rmsnorm(const float* x, const float* w, bf16_t* y, bf16_t* y_lo, int ldy, int rows, int H, float eps, hipStream_t s, int f16, unsigned* sat, int lo8, const unsigned* skip) {
   if (!x || !w || !y) return fv_fail(FV_ERR_ARG, "rmsnorm: null pointer");
   if (rows <= 0 || H <= 0 || H % 8 || ldy < H || ldy % 8) return fv_fail(FV_ERR_ARG, "rmsnorm: bad shape rows=%d H=%d ldy=%d", rows, H, ldy);
   if (f16 && y_lo) return fv_fail(FV_ERR_ARG, "rmsnorm: the fp16 form has no remainder output");
-  if (f16) hipLaunchKernelGGL(rmsnorm_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, y, y_lo, ldy, rows, H, eps, sat, 0);
-  else hipLaunchKernelGGL(rmsnorm_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, y, y_lo, ldy, rows, H, eps, nullptr, lo8);
+  if (f16) hipLaunchKernelGGL(rmsnorm_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, y, y_lo, ldy, rows, H, eps, sat, 0, skip);
+  else hipLaunchKernelGGL(rmsnorm_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, y, y_lo, ldy, rows, H, eps, nullptr, lo8, skip);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -505,18 +512,18 @@ int launch_bf16_to_f16(bf16_t* p, size_t n, float scale, hipStream_t s, unsigned
   return FV_OK;
 }
 
-int launch_rope_f32(float* qkv, const float2* table, int ld, int rows, int T, int heads, int kv_heads, int D, hipStream_t s) {
+int launch_rope_f32(float* qkv, const float2* table, int ld, int rows, int T, int heads, int kv_heads, int D, hipStream_t s, const unsigned* skip) {
   if (!qkv || !table) return fv_fail(FV_ERR_ARG, "rope_f32: null pointer");
   if (rows <= 0 || T <= 0 || D % 8 || ld % 4 || ld < (heads + kv_heads) * D) return fv_fail(FV_ERR_ARG, "rope_f32: bad shape");
   const long total = (long)rows * (heads + kv_heads) * (D / 8);
-  hipLaunchKernelGGL(rope_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, table, ld, (long)rows, T, heads + kv_heads, D);
+  hipLaunchKernelGGL(rope_f32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, table, ld, (long)rows, T, heads + kv_heads, D, skip);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
 
 int launch_attention_f32(float* qkv, int ld, bf16_t* out_hi, bf16_t* out_lo, int ldo, int B, int T, int heads,
                          int kv_heads, int D, const int32_t* lens, int len_add, float scale, hipStream_t s, const float2* rope,
-                         const float* pre, int ldp, int Np, float* lse, int lo8, void* split_scratch) {
+                         const float* pre, int ldp, int Np, float* lse, int lo8, void* split_scratch, const unsigned* skip) {
   if (!qkv || !out_hi || !out_lo) return fv_fail(FV_ERR_ARG, "attention_f32: null pointer");
   if (lse && (pre || D < 64)) return fv_fail(FV_ERR_UNSUPPORTED, "attention_f32: row statistics (training) need head_dim 64 / 128 and no cached prefix");
   if (pre && (Np <= 0 || Np >= T || ldp < 2 * kv_heads * D || ldp % 4 || D < 64))
@@ -532,17 +539,17 @@ int launch_attention_f32(float* qkv, int ld, bf16_t* out_hi, bf16_t* out_lo, int
   static const bool no_split = fv_ab_env("FASTVLA_NO_ATTN_SPLIT") != nullptr;   // A/B: the fp32-MFMA kernels of round 4's first version
   // training (lse wanted): the split-bf16 kernel -- 5x the fp32 pipe's rate at 16 significant bits per operand (attention_split.hip)
   if (D >= 64 && (lse || T >= FV_ATTN_SPLIT_MIN_T) && !pre && !lo8 && !no_split && split_scratch)
-    return launch_attention_split_fwd(qkv, ld, out_hi, out_lo, ldo, B, T, heads, kv_heads, D, lens, len_add, scale, rope, lse, split_scratch, s);
+    return launch_attention_split_fwd(qkv, ld, out_hi, out_lo, ldo, B, T, heads, kv_heads, D, lens, len_add, scale, rope, lse, split_scratch, s, skip);
   if (D >= 64 && (!no_mfma || pre || lse)) {
     const long nb = (long)B * heads * ((T - Np + 63) / 64);
     // rope given: q and k are rotated inside the kernel (no separate pass over the packed projections)
-    if (D == 64) hipLaunchKernelGGL((attention_f32_mfma_kernel<64>), dim3((unsigned)nb), dim3(256), 0, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, scale, rope, pre, ldp, Np, lse, lo8);
-    else hipLaunchKernelGGL((attention_f32_mfma_kernel<128>), dim3((unsigned)nb), dim3(256), 0, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, scale, rope, pre, ldp, Np, lse, lo8);
+    if (D == 64) hipLaunchKernelGGL((attention_f32_mfma_kernel<64>), dim3((unsigned)nb), dim3(256), 0, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, scale, rope, pre, ldp, Np, lse, lo8, skip);
+    else hipLaunchKernelGGL((attention_f32_mfma_kernel<128>), dim3((unsigned)nb), dim3(256), 0, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, scale, rope, pre, ldp, Np, lse, lo8, skip);
     FV_HIP_CHECK(hipGetLastError());
     return FV_OK;
   }
   if (G * NT > 256) return fv_fail(FV_ERR_UNSUPPORTED, "attention_f32: too many q heads per kv head (%d)", G);
-  if (rope) FV_TRY_RC(launch_rope_f32(qkv, rope, ld, B * T, T, heads, kv_heads, D, s));   // the VALU kernel reads rotated q / k
+  if (rope) FV_TRY_RC(launch_rope_f32(qkv, rope, ld, B * T, T, heads, kv_heads, D, s, skip));   // the VALU kernel reads rotated q / k
   // queries per block: as many as 256 threads hold (any count, not a power of two: G = 7 leaves 44 % of the lanes idle at
   // 16), then levelled over the tiles so the causal key ranges of the tiles are balanced
   int QT = 256 / (G * NT);
@@ -552,9 +559,9 @@ int launch_attention_f32(float* qkv, int ld, bf16_t* out_hi, bf16_t* out_lo, int
   const long blocks = (long)B * kv_heads * ((T + QT - 1) / QT);
   const size_t lds = (size_t)2 * 64 * D * sizeof(float);
   const dim3 grid((unsigned)blocks), blk(256);
-  if (D == 32) hipLaunchKernelGGL((attention_f32_kernel<32, 1>), grid, blk, lds, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, QT, scale, lo8);
-  else if (D == 64) hipLaunchKernelGGL((attention_f32_kernel<64, 1>), grid, blk, lds, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, QT, scale, lo8);
-  else hipLaunchKernelGGL((attention_f32_kernel<64, 2>), grid, blk, lds, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, QT, scale, lo8);
+  if (D == 32) hipLaunchKernelGGL((attention_f32_kernel<32, 1>), grid, blk, lds, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, QT, scale, lo8, skip);
+  else if (D == 64) hipLaunchKernelGGL((attention_f32_kernel<64, 1>), grid, blk, lds, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, QT, scale, lo8, skip);
+  else hipLaunchKernelGGL((attention_f32_kernel<64, 2>), grid, blk, lds, s, qkv, out_hi, out_lo, lens, len_add, ld, ldo, T, heads, kv_heads, QT, scale, lo8, skip);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
@@ -571,20 +578,20 @@ void rope_table_host(float* cs, int T, int D, float theta) {
 }
 
 int launch_rope(bf16_t* qkv, const float2* table, int ld, int rows, int T, int heads, int kv_heads, int D,
-                hipStream_t s) {
+                hipStream_t s, const unsigned* skip) {
   if (!qkv || !table) return fv_fail(FV_ERR_ARG, "rope: null pointer");
   if (rows <= 0 || T <= 0 || D % 16 || ld % 8 || ld < (heads + kv_heads) * D) return fv_fail(FV_ERR_ARG, "rope: bad shape");
   const long total = (long)rows * (heads + kv_heads) * (D / 16);
-  hipLaunchKernelGGL(rope_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, table, ld, (long)rows, T, heads + kv_heads, D);
+  hipLaunchKernelGGL(rope_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, qkv, table, ld, (long)rows, T, heads + kv_heads, D, skip);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
 
 int launch_pool_norm(const float* x, const int32_t* lens, const float* w, float* pooled, int B, int Ttot, int Ni,
-                     int H, float eps, int mode, hipStream_t s) {
+                     int H, float eps, int mode, hipStream_t s, const unsigned* skip) {
   if (!x || !w || !pooled) return fv_fail(FV_ERR_ARG, "pool_norm: null pointer");
   if (B <= 0 || Ttot <= Ni || H <= 0 || (mode != 0 && mode != 1)) return fv_fail(FV_ERR_ARG, "pool_norm: bad shape/mode");
-  hipLaunchKernelGGL(pool_norm_kernel, dim3(B), dim3(256), 0, s, x, lens, w, pooled, Ttot, Ni, H, eps, mode);
+  hipLaunchKernelGGL(pool_norm_kernel, dim3(B), dim3(256), 0, s, x, lens, w, pooled, Ttot, Ni, H, eps, mode, skip);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }

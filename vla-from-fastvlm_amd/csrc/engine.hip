@@ -130,7 +130,78 @@ struct WsPlan {
 };
 
 // optional per-launch HIP-event timing on the caller's stream (bench.py's roofline numbers); off by default
-struct ProfRec { int fam; double flops, bytes; int m, n, k, epi; hipEvent_t e0, e1; };
+struct ProfRec { int fam; double flops, bytes; int m, n, k, epi; hipEvent_t e0, e1; long long call = -1; };   // call >= 0: a launch of the literal decoder call with that index (PromptSlot)
+
+// ---- prompt reuse (fv_set_prompt_reuse).  In literal mode (Ni == 0) the decoder never sees the image: `pooled` is a function of (ids, lens, B, T,
+// pool_mode) and the decoder's operand images alone, and a control loop sends the same task string for a whole episode.  The handle keeps ONE slot in
+// device memory -- the key of the last literal call and its pooled rows -- and the decision is made on the device, every call (and every replay of a
+// captured graph): prompt_probe_kernel compares the call's key with the slot and writes `hit`; every kernel of the call takes that word as its `skip`
+// (common.h FV_SKIP_EXIT); prompt_commit_kernel ends the call (hit: slot rows -> the caller's pooled; miss: key and fresh rows -> slot).
+// Only the first max(min(lens[b], T), 1) ids of a row are compared: attention is causal and masks keys >= lens[b], every other decoder kernel works
+// row by row, and pool_norm_kernel reads rows < max(lens[b], 1) only, so padding ids cannot reach `pooled` (tests/test_gpu_prompt_reuse.py pins this).
+// What the result depends on besides the key invalidates the slot (prompt_invalidate).  The writers of decoder operand images and the switches of kernel forms:
+//   load_impl (fv_load_weights, fv_load_weights_cb)         every image
+//   fv_train_commit (launch_commit, launch_tower_commit)    bf16 rows, norms, embedding from the flat master
+//   fv_train_lora_commit (launch_commit, launch_lora_commit), fv_train_lora_merge, fv_train_lora_init_magnitude (the merged / re-normed master's next images)
+//   fv_train_set_forward_f16, fv_train_set_options          rebuild operand copies from the library's rows
+//   fv_set_batch_invariant, fv_set_prompt_reuse             kernel-form / policy switches
+// llm_precision is fixed at fv_create; the few-row GEMM forms follow B and T, which are part of the key; training entry points never touch the slot.
+constexpr int PROMPT_RING = 256;          // per-call hit bits kept for fv_profile_read
+enum { PW_VALID = 0, PW_HIT = 1, PW_CALLS = 2, PW_HITS = 3, PW_B = 4, PW_T = 5, PW_MODE = 6, PW_RING = 8, PW_WORDS = PW_RING + PROMPT_RING };
+struct PromptSlot {
+  unsigned* w = nullptr;      // device: PW_WORDS words (zeroed at fv_create: valid starts clear)
+  int32_t* ids = nullptr;     // device: cap_b * cap_t ids of the last literal call, row stride ITS T
+  int32_t* lens = nullptr;    // device: cap_b
+  float* pooled = nullptr;    // device: cap_b * llm_hidden
+  int cap_b = 0, cap_t = 0;
+  bool on = true;             // fv_set_prompt_reuse
+  bool dirty = true;          // a host-side invalidation is pending: the next literal call is forced to miss (and re-validates the slot)
+  long long calls = 0;        // host count of literal calls that used the slot: the profiler's call index
+};
+
+// one block: hit = valid && same (B, T, pool_mode) && same lens && same valid prefix of every row
+__global__ __launch_bounds__(256) void prompt_probe_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens, int B, int T, int pool_mode,
+                                                           int force_miss, unsigned ring_pos, unsigned* __restrict__ w, const int32_t* __restrict__ key_ids,
+                                                           const int32_t* __restrict__ key_lens) {
+  __shared__ int wdiff[4];
+  const int tid = threadIdx.x;
+  int diff = 0;
+  const bool cand = !force_miss && w[PW_VALID] != 0u && w[PW_B] == (unsigned)B && w[PW_T] == (unsigned)T && w[PW_MODE] == (unsigned)pool_mode;
+  if (cand) {   // (the key is read only behind `valid`: uninitialised slot memory is never a key)
+    for (int b = tid; b < B; b += 256) diff |= lens[b] != key_lens[b];
+    for (int i = tid; i < B * T; i += 256) {
+      const int b = i / T, t = i - b * T;
+      const int n = max(min(lens[b], T), 1);
+      if (t < n) diff |= ids[i] != key_ids[i];
+    }
+  }
+  const int any = __builtin_amdgcn_ballot_w64(diff != 0) != 0;
+  if ((tid & 63) == 0) wdiff[tid >> 6] = any;
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned hit = cand && !(wdiff[0] | wdiff[1] | wdiff[2] | wdiff[3]) ? 1u : 0u;
+    w[PW_HIT] = hit;
+    w[PW_CALLS] += 1u;
+    w[PW_HITS] += hit;
+    w[PW_RING + ring_pos] = hit;
+  }
+}
+
+// hit: slot rows -> pooled.  miss: (ids, lens, pooled) -> slot, valid <- 1.  Grid-stride over max(B * H, B * T) elements
+__global__ __launch_bounds__(256) void prompt_commit_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ lens, float* __restrict__ pooled, int B,
+                                                            int T, int H, int pool_mode, unsigned* __restrict__ w, int32_t* __restrict__ key_ids,
+                                                            int32_t* __restrict__ key_lens, float* __restrict__ key_pooled) {
+  const int i0 = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+  if (w[PW_HIT] != 0u) {
+    for (int i = i0; i < B * H; i += step) pooled[i] = key_pooled[i];
+    return;
+  }
+  for (int i = i0; i < B * H; i += step) key_pooled[i] = pooled[i];
+  for (int i = i0; i < B * T; i += step) key_ids[i] = ids[i];
+  for (int i = i0; i < B; i += step) key_lens[i] = lens[i];
+  if (i0 == 0) { w[PW_B] = (unsigned)B; w[PW_T] = (unsigned)T; w[PW_MODE] = (unsigned)pool_mode; w[PW_VALID] = 1u; }
+}
+
 struct Profiler {
   bool on = false;
   std::vector<ProfRec> recs;
@@ -167,6 +238,8 @@ struct fv_handle {
   size_t ws_bytes = 0;
   fv::HeadDims hd;
   Profiler prof;
+  PromptSlot prompt;          // fv_set_prompt_reuse: the literal call's one-entry result cache (device memory, sized at fv_create)
+  long long prof_call = -1;   // >= 0 while a literal call that uses the slot enqueues its launches: prof_begin tags its records with it
   char err[768] = "";         // last error of a call made on THIS handle (fv_last_error(h)); fv_fail's thread-local
                               // buffer is only the staging area
   void* const* taps = nullptr;  // fv_vision_forward_taps: per-stage copies of the activation map (parity tests)
@@ -492,6 +565,7 @@ void prof_begin(fv_handle* h, int fam, double flops, double bytes, hipStream_t s
   if (!h->prof.on) return;
   ProfRec r{fam, flops, bytes, m, n, k, epi, h->prof.get(), h->prof.get()};
   if (!r.e0 || !r.e1) return;
+  r.call = h->prof_call;
   (void)hipEventRecord(r.e0, s);
   h->prof.recs.push_back(r);
 }
@@ -506,6 +580,26 @@ void prof_end(fv_handle* h, hipStream_t s) {
     prof_end(h, s);                              \
     if (_rc != FV_OK) return _rc;                \
   } while (0)
+
+// Everything `pooled` depends on besides the call's key comes through here (the list stands at PromptSlot).  Host side: the next literal call is forced to
+// miss.  With a stream: `valid` is cleared in stream order too, so a graph captured earlier misses on its next replay behind the writer.
+int prompt_invalidate(fv_handle* h, hipStream_t s, bool stream_ordered) {
+  h->prompt.dirty = true;
+  if (stream_ordered && h->prompt.w) FV_HIP_CHECK(hipMemsetAsync(h->prompt.w + PW_VALID, 0, sizeof(unsigned), s));
+  return FV_OK;
+}
+
+int launch_prompt_probe(const PromptSlot& ps, const int32_t* ids, const int32_t* lens, int B, int T, int pool_mode, hipStream_t s) {
+  hipLaunchKernelGGL(prompt_probe_kernel, dim3(1), dim3(256), 0, s, ids, lens, B, T, pool_mode, ps.dirty ? 1 : 0, (unsigned)(ps.calls % PROMPT_RING), ps.w, ps.ids, ps.lens);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+int launch_prompt_commit(const PromptSlot& ps, const int32_t* ids, const int32_t* lens, float* pooled, int B, int T, int H, int pool_mode, hipStream_t s) {
+  const int n = std::max(B * H, B * T), blocks = std::min((n + 255) / 256, 64);
+  hipLaunchKernelGGL(prompt_commit_kernel, dim3(blocks), dim3(256), 0, s, ids, lens, pooled, B, T, H, pool_mode, ps.w, ps.ids, ps.lens, ps.pooled);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
 
 int gemm_p(fv_handle* h, const fv::GemmArgs& g_in, hipStream_t s) {
   fv::GemmArgs g = g_in;
@@ -706,7 +800,7 @@ int tower_pass(fv_handle* h, const bf16_t* pix, int b0, int mb, bf16_t* tower_ou
 // (the 256 image tokens come first in the causal sequence, so their K / V depend on the image alone.)
 enum DecMode { DEC_FULL = 0, DEC_PREFIX = 1, DEC_SUFFIX = 2 };
 int decoder_layers_split(fv_handle* h, const WsPlan& wp, int B, int Tq, const int32_t* lens, int len_add, float* kv, int Np, int mode,
-                         hipStream_t s) {
+                         hipStream_t s, const unsigned* skip = nullptr) {   // skip: the literal call's hit word (PromptSlot); null: every launch as ever
   const fv_model_desc& d = h->d;
   char* ws = static_cast<char*>(h->ws);
   float* x = reinterpret_cast<float*>(ws + wp.x);
@@ -733,9 +827,9 @@ int decoder_layers_split(fv_handle* h, const WsPlan& wp, int B, int Tq, const in
       // llm_precision = 5: every split operand is "hi + lo8" (bf16 + one fp8 byte of remainder per element, in the lo half's place) and
       // every projection takes ksplit = 2: the lo product on the scaled fp8 MFMA against the weights' fp8 copies -- 1.5 passes
       const int lo8 = d.llm_precision == 5, KS = lo8 ? 2 : 1;
-      if (li == 0) FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 8.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln1, xs, xs + Hd, 2 * Hd, rows, Hd, d.rms_eps, s, 0, nullptr, lo8));
+      if (li == 0) FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 8.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln1, xs, xs + Hd, 2 * Hd, rows, Hd, d.rms_eps, s, 0, nullptr, lo8, skip));
       fv::GemmArgs q1{xs, 2 * Hd, L.qkv_w, rows, qkvw, Hd, L.qkv_b, nullptr, nullptr, 0, qkvf, qkvw, FV_EPI_F32, KS};
-      q1.W8 = L.qkv_w8;
+      q1.W8 = L.qkv_w8; q1.skip = skip;
       // few output tiles and a long K (7B: 72 tiles of 256 x 256 at M = 1024): the 256-tile kernel cut along K, as the down projection
       q1.splitk_ws = wp.splitk_bytes ? reinterpret_cast<float*>(ws + wp.splitk) : nullptr;
       q1.splitk_bytes = wp.splitk_bytes;
@@ -749,9 +843,9 @@ int decoder_layers_split(fv_handle* h, const WsPlan& wp, int B, int Tq, const in
       FV_P(FV_FAM_ATTN, 2.0 * B * (double)Tq * Tt * qd + 3.0 * rows * (qd + kd), 4.0 * rows * (qkvw + qd),
            fv::launch_attention_f32(qkvf, qkvw, as, as + qd, 2 * qd, B, Tt, d.llm_heads, d.llm_kv_heads, D, lens, len_add, att_scale, s, h->rope,
                                     mode == DEC_SUFFIX ? kv + li * kv_layer : nullptr, 2 * kd, mode == DEC_SUFFIX ? Np : 0, nullptr, lo8,
-                                    wp.attn_scr_bytes && mode != DEC_SUFFIX ? ws + wp.attn_scr : nullptr));
+                                    wp.attn_scr_bytes && mode != DEC_SUFFIX ? ws + wp.attn_scr : nullptr, skip));
       fv::GemmArgs o1{as, 2 * qd, L.o_w, rows, Hd, qd, nullptr, nullptr, x, Hd, x, Hd, FV_EPI_RES_F32, KS};
-      o1.W8 = L.o_w8;
+      o1.W8 = L.o_w8; o1.skip = skip;
       o1.splitk_ws = q1.splitk_ws;
       o1.splitk_bytes = wp.splitk_bytes;
       // policies 1 / 5: post_attention_layernorm rides on the output projection (its split-K reducer where there is one, launch_gemm's own norm launch
@@ -763,34 +857,34 @@ int decoder_layers_split(fv_handle* h, const WsPlan& wp, int B, int Tq, const in
       d1.W8 = L.down_w8;
       if (d.llm_precision == 2) {
         // the MLP in ONE pass on fp16 operands (tests/precision_budget.py): post-norm rows as fp16, SwiGLU output / 16 as fp16
-        FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xn, nullptr, Hd, rows, Hd, d.rms_eps, s, 1, h->f16_flags));
+        FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xn, nullptr, Hd, rows, Hd, d.rms_eps, s, 1, h->f16_flags, 0, skip));
         fv::GemmArgs g1{xn, Hd, L.gu_w, rows, I2, Hd, nullptr, nullptr, nullptr, 0, act, I, FV_EPI_SWIGLU_F16, 0};
-        g1.f16 = 1; g1.sat = h->f16_flags;
+        g1.f16 = 1; g1.sat = h->f16_flags; g1.skip = skip;
         FV_TRY(gemm_p(h, g1, s));
         d1 = fv::GemmArgs{act, I, L.down_w, rows, Hd, I, nullptr, nullptr, x, Hd, x, Hd, FV_EPI_RES_F32, 0};
         d1.f16 = 1;
       } else if (d.llm_precision == 3) {
         // gate/up alone in one fp16 pass; its SwiGLU output leaves as hi + lo bf16 for a split-bf16 down projection
-        FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xn, nullptr, Hd, rows, Hd, d.rms_eps, s, 1, h->f16_flags));
+        FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xn, nullptr, Hd, rows, Hd, d.rms_eps, s, 1, h->f16_flags, 0, skip));
         fv::GemmArgs g1{xn, Hd, L.gu_w, rows, I2, Hd, nullptr, nullptr, nullptr, 0, cs, I2, FV_EPI_SWIGLU_SPLIT, 0};
-        g1.f16 = 1;
+        g1.f16 = 1; g1.skip = skip;
         FV_TRY(gemm_p(h, g1, s));
       } else if (d.llm_precision == 4) {
         // down alone in one fp16 pass: split-bf16 gate/up whose SwiGLU output / 16 leaves as fp16
-        FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 8.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xs, xs + Hd, 2 * Hd, rows, Hd, d.rms_eps, s));
+        FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 8.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xs, xs + Hd, 2 * Hd, rows, Hd, d.rms_eps, s, 0, nullptr, 0, skip));
         fv::GemmArgs g1{xs, 2 * Hd, L.gu_w, rows, I2, Hd, nullptr, nullptr, nullptr, 0, act, I, FV_EPI_SWIGLU_F16, 1};
-        g1.sat = h->f16_flags;
+        g1.sat = h->f16_flags; g1.skip = skip;
         FV_TRY(gemm_p(h, g1, s));
         d1 = fv::GemmArgs{act, I, L.down_w, rows, Hd, I, nullptr, nullptr, x, Hd, x, Hd, FV_EPI_RES_F32, 0};
         d1.f16 = 1;
       } else {
         fv::GemmArgs g1{xs, 2 * Hd, L.gu_w, rows, I2, Hd, nullptr, nullptr, nullptr, 0, cs, I2, FV_EPI_SWIGLU_SPLIT, KS};
-        g1.W8 = L.gu_w8;
+        g1.W8 = L.gu_w8; g1.skip = skip;
         g1.splitk_ws = q1.splitk_ws; g1.splitk_bytes = wp.splitk_bytes;   // few rows: K ranges + a SwiGLU reduce (launch_gemm's few-row rule)
         FV_TRY(gemm_p(h, g1, s));  // silu(gate)*up and its hi / lo (or lo8) split happen in the epilogue: no fp32 round trip
       }
       d1.splitk_ws = wp.splitk_bytes ? reinterpret_cast<float*>(ws + wp.splitk) : nullptr;
-      d1.splitk_bytes = wp.splitk_bytes;
+      d1.splitk_bytes = wp.splitk_bytes; d1.skip = skip;
       if (li + 1 < h->dec.layers.size()) {
         d1.norm_w = h->dec.layers[li + 1].ln1; d1.norm_y = xs; d1.norm_ylo = xs + Hd; d1.norm_ld = 2 * Hd; d1.norm_eps = d.rms_eps;
       }
@@ -859,6 +953,17 @@ int fv_create(const fv_model_desc* desc, int device, fv_handle** out) {
     h->lb_vmax = h->f16_flags + 32;   // a word of the same block (nothing is allocated inside fv_preprocess_normalized: the call stays capturable)
   }
   if (rc == FV_OK) { rc = dev_alloc(h, FFN_PART_BYTES, &p); h->ffn_part = static_cast<float*>(p); }
+  if (rc == FV_OK && d.max_batch > 0 && d.max_text_tokens > 0) {   // the prompt slot: words | ids | lens | pooled rows, each part 256-byte aligned
+    PromptSlot& ps = h->prompt;
+    ps.cap_b = d.max_batch; ps.cap_t = d.max_text_tokens;
+    const size_t ow = 0, oi = align_up(PW_WORDS * sizeof(unsigned)), ol = oi + align_up((size_t)ps.cap_b * ps.cap_t * 4), op = ol + align_up((size_t)ps.cap_b * 4);
+    const size_t total = op + align_up((size_t)ps.cap_b * d.llm_hidden * 4);
+    rc = dev_alloc(h, total, &p);
+    if (rc == FV_OK && hipMemset(p, 0, total) != hipSuccess) rc = fv_fail(FV_ERR_HIP, "prompt slot: memset failed");
+    char* base = static_cast<char*>(p);
+    ps.w = reinterpret_cast<unsigned*>(base + ow); ps.ids = reinterpret_cast<int32_t*>(base + oi);
+    ps.lens = reinterpret_cast<int32_t*>(base + ol); ps.pooled = reinterpret_cast<float*>(base + op);
+  }
   if (rc != FV_OK) { fv_destroy(h); return rc; }
   *out = h;
   return FV_OK;
@@ -897,6 +1002,7 @@ int fv_load_weights_cb(fv_handle* h, fv_tensor_provider provider, void* user) {
 }
 
 static int load_impl(fv_handle* h, Loader& L) {
+  FV_TRY(prompt_invalidate(h, nullptr, true));   // every operand image is about to be written
   FV_HIP_CHECK(hipSetDevice(h->device));
   const fv_model_desc& d = h->d;
   Tower& tw = h->tw;
@@ -1210,29 +1316,50 @@ int fv_llm_forward_pooled(fv_handle* h, const int32_t* ids, const int32_t* lens,
   bf16_t* act = reinterpret_cast<bf16_t*>(ws + wp.act);
   const int rows = B * Tt, Hd = d.llm_hidden, D = d.llm_head_dim;
   const int qd = d.llm_heads * D, kd = d.llm_kv_heads * D, qkvw = qd + 2 * kd;
-  FV_P(FV_FAM_ELT, 0.0, 6.0 * rows * Hd, fv::launch_embed_gather(ids, h->dec.embed, static_cast<const float*>(img_tokens), x, B, T, Ni, Hd, d.llm_vocab, s));
+  // literal mode with reuse on: the probe decides on the device, every launch below carries its word, the commit ends the call (PromptSlot).  A call the
+  // slot cannot hold (B * T beyond its capacity) and every training entry point run as ever (skip == nullptr)
+  PromptSlot& ps = h->prompt;
+  const bool reuse = Ni == 0 && ps.on && ps.w && h->train_depth == 0 && B <= ps.cap_b && (size_t)B * T <= (size_t)ps.cap_b * ps.cap_t;
+  const unsigned* skip = reuse ? ps.w + PW_HIT : nullptr;
+  struct ProfCall { fv_handle* h; ~ProfCall() { h->prof_call = -1; } } prof_call_scope{h};
+  if (reuse) {
+    FV_P(FV_FAM_ELT, 0.0, 8.0 * rows,   // (untagged: the probe and the commit always run)
+         launch_prompt_probe(ps, ids, lens, B, T, pool_mode, s));
+    h->prof_call = ps.calls++;
+  }
+  FV_P(FV_FAM_ELT, 0.0, 6.0 * rows * Hd, fv::launch_embed_gather(ids, h->dec.embed, static_cast<const float*>(img_tokens), x, B, T, Ni, Hd, d.llm_vocab, s, skip));
   const float att_scale = 1.0f / std::sqrt((float)D);
   if (d.llm_precision == 0) {
     for (const DecLayer& L : h->dec.layers) {
-      FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln1, xn, nullptr, Hd, rows, Hd, d.rms_eps, s));
+      FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln1, xn, nullptr, Hd, rows, Hd, d.rms_eps, s, 0, nullptr, 0, skip));
       fv::GemmArgs gq{xn, Hd, L.qkv_w, rows, qkvw, Hd, L.qkv_b, nullptr, nullptr, 0, qkv, qkvw, FV_EPI_BIAS};
+      gq.skip = skip;
       FV_TRY(gemm_p(h, gq, s));
-      FV_P(FV_FAM_ELT, 3.0 * rows * (qd + kd), 4.0 * rows * (qd + kd), fv::launch_rope(qkv, h->rope, qkvw, rows, Tt, d.llm_heads, d.llm_kv_heads, D, s));
+      FV_P(FV_FAM_ELT, 3.0 * rows * (qd + kd), 4.0 * rows * (qd + kd), fv::launch_rope(qkv, h->rope, qkvw, rows, Tt, d.llm_heads, d.llm_kv_heads, D, s, skip));
       FV_P(FV_FAM_ATTN, 2.0 * B * (double)Tt * Tt * qd, 2.0 * rows * (qkvw + qd),
            fv::launch_attention(qkv, qkv + qd, qkv + qd + kd, qkvw, qkvw, qkvw, att, qd, B, Tt, d.llm_heads, d.llm_kv_heads,
-                                D, 1, lens, Ni, att_scale, s));
+                                D, 1, lens, Ni, att_scale, s, skip));
       fv::GemmArgs go{att, qd, L.o_w, rows, Hd, qd, nullptr, nullptr, x, Hd, x, Hd, FV_EPI_RES_F32};
+      go.skip = skip;
       FV_TRY(gemm_p(h, go, s));
-      FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xn, nullptr, Hd, rows, Hd, d.rms_eps, s));
+      FV_P(FV_FAM_NORM, 4.0 * rows * Hd, 6.0 * rows * Hd, fv::launch_rmsnorm(x, L.ln2, xn, nullptr, Hd, rows, Hd, d.rms_eps, s, 0, nullptr, 0, skip));
       fv::GemmArgs gg{xn, Hd, L.gu_w, rows, 2 * d.llm_inter, Hd, nullptr, nullptr, nullptr, 0, act, d.llm_inter, FV_EPI_SWIGLU};
+      gg.skip = skip;
       FV_TRY(gemm_p(h, gg, s));
       fv::GemmArgs gd{act, d.llm_inter, L.down_w, rows, Hd, d.llm_inter, nullptr, nullptr, x, Hd, x, Hd, FV_EPI_RES_F32};
+      gd.skip = skip;
       FV_TRY(gemm_p(h, gd, s));
     }
   } else {
-    FV_TRY(decoder_layers_split(h, wp, B, Tt, lens, Ni, nullptr, 0, DEC_FULL, s));
+    FV_TRY(decoder_layers_split(h, wp, B, Tt, lens, Ni, nullptr, 0, DEC_FULL, s, skip));
   }
-  FV_P(FV_FAM_ELT, 4.0 * B * Hd, 8.0 * B * Hd, fv::launch_pool_norm(x, lens, h->dec.norm, static_cast<float*>(pooled), B, Tt, Ni, Hd, d.rms_eps, pool_mode, s));
+  FV_P(FV_FAM_ELT, 4.0 * B * Hd, 8.0 * B * Hd, fv::launch_pool_norm(x, lens, h->dec.norm, static_cast<float*>(pooled), B, Tt, Ni, Hd, d.rms_eps, pool_mode, s, skip));
+  if (reuse) {
+    h->prof_call = -1;   // the commit always runs
+    FV_P(FV_FAM_ELT, 0.0, 8.0 * B * Hd + 8.0 * rows,
+         launch_prompt_commit(ps, ids, lens, static_cast<float*>(pooled), B, T, Hd, pool_mode, s));
+    ps.dirty = false;    // the slot now describes the handle's current operand images (a miss re-validated it; a hit found it valid)
+  }
   return FV_OK;
 }
 
@@ -1245,6 +1372,26 @@ int fv_set_batch_invariant(fv_handle* h, int on) {
   HandleScope _hs(h);
   if (!h) return fv_fail(FV_ERR_ARG, "fv_set_batch_invariant: null handle");
   h->batch_invariant = on != 0;
+  return prompt_invalidate(h, nullptr, false);
+}
+
+int fv_set_prompt_reuse(fv_handle* h, int on) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "fv_set_prompt_reuse: null handle");
+  h->prompt.on = on != 0;
+  return prompt_invalidate(h, nullptr, false);   // calls made while it was off left the slot as it was: what it holds is re-proved by the next call
+}
+
+int fv_prompt_reuse_stats(fv_handle* h, uint64_t* calls_out, uint64_t* hits_out) {
+  HandleScope _hs(h);
+  if (!h || !calls_out || !hits_out) return fv_fail(FV_ERR_ARG, "fv_prompt_reuse_stats: null argument");
+  unsigned w[2] = {0u, 0u};
+  if (h->prompt.w) {
+    FV_HIP_CHECK(hipSetDevice(h->device));
+    FV_HIP_CHECK(hipDeviceSynchronize());
+    FV_HIP_CHECK(hipMemcpy(w, h->prompt.w + PW_CALLS, sizeof(w), hipMemcpyDeviceToHost));
+  }
+  *calls_out = w[0]; *hits_out = w[1];
   return FV_OK;
 }
 
@@ -1318,12 +1465,25 @@ int fv_profile_read(fv_handle* h, fv_profile_entry* fam_out, fv_gemm_profile* ge
   if (!h || !fam_out) return fv_fail(FV_ERR_ARG, "fv_profile_read: null argument");
   for (int i = 0; i < FV_FAM_COUNT; ++i) fam_out[i] = fv_profile_entry{0.0, 0.0, 0.0, 0};
   std::map<std::vector<int>, fv_gemm_profile> shapes;
+  std::vector<unsigned> ring(PROMPT_RING, 0u);
+  bool ring_ok = false;   // the per-call hit bits, fetched once behind the last tagged record's end
+  for (auto it = h->prof.recs.rbegin(); it != h->prof.recs.rend() && !ring_ok; ++it)
+    if (it->call >= 0 && h->prompt.w) {
+      FV_HIP_CHECK(hipEventSynchronize(it->e1));
+      FV_HIP_CHECK(hipMemcpy(ring.data(), h->prompt.w + PW_RING, PROMPT_RING * sizeof(unsigned), hipMemcpyDeviceToHost));
+      ring_ok = true;
+    }
   for (ProfRec& r : h->prof.recs) {
     FV_HIP_CHECK(hipEventSynchronize(r.e1));
     float ms = 0.f;
     FV_HIP_CHECK(hipEventElapsedTime(&ms, r.e0, r.e1));
+    // a launch of a literal call that hit returned at once: its time and its launch stay, the work it did not do is not counted, and it is no sample of
+    // its GEMM shape.  (Calls more than PROMPT_RING behind the newest have lost their bit: counted as executed.)
+    const bool skipped = r.call >= 0 && h->prompt.calls - r.call <= PROMPT_RING && ring_ok && ring[r.call % PROMPT_RING] != 0u;
     fv_profile_entry& e = fam_out[r.fam];
-    e.ms += ms; e.flops += r.flops; e.bytes += r.bytes; e.launches += 1;
+    e.ms += ms; e.launches += 1;
+    if (skipped) continue;
+    e.flops += r.flops; e.bytes += r.bytes;
     if (r.fam == FV_FAM_GEMM) {
       fv_gemm_profile& g = shapes[{r.m, r.n, r.k, r.epi}];
       g.m = r.m; g.n = r.n; g.k = r.k; g.epi = r.epi; g.ms += ms; g.launches += 1;

@@ -41,6 +41,7 @@ struct Params {
   unsigned* sat = nullptr;   // FV_EPI_SWIGLU_F16: device counter of 8-value groups clamped to the fp16 range (0 in a healthy model)
   void* stash = nullptr;     // FV_EPI_SWIGLU_SPLIT: raw gate/up accumulators, [M][N] fp32 or (stash_f16) fp16
   int stash_f16 = 0;
+  const unsigned* skip = nullptr;   // prompt reuse: the literal decoder call's hit word (common.h FV_SKIP_EXIT); null everywhere else
 };
 
 #ifdef FASTVLA_AB_SWITCHES
@@ -78,6 +79,7 @@ __device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const 
 // M = B*T = 4096 decoder GEMMs) -- twice the blocks, 3 co-resident per CU.
 template <int BM, bool F16 = false, bool LO8 = false>   // LO8: the hi + lo8 instance (p.ksplit == 2); the others carry none of its code
 __global__ __launch_bounds__(256, 2) void gemm_kernel(Params p) {
+  FV_SKIP_EXIT(p.skip);
   constexpr int MI = BM / 32;                             // 16-row MFMA tiles per wave along M
   constexpr int A_ELEMS = BM * BK, B_ELEMS = BN * BK;
   constexpr int STAGE_BYTES = 2 * (A_ELEMS + B_ELEMS) * 2, EPI_BYTES = BM * LDC * 4;
@@ -397,6 +399,7 @@ __device__ __forceinline__ bf16x8 g2_tr_frag(const char* region, int cols16, int
 // 16 + 4 fq + e - 4 (e >= 4) of a 32-deep step on BOTH operands (attention32_kernel's V recipe).
 template <int MI, int WN, bool ASYM = false, bool F16 = false, bool LO8 = false, bool TN = false>   // LO8: the hi + lo8 instance (p.ksplit == 2)
 __global__ __launch_bounds__(128 * WN, WN == 4 ? 1 : 2) void gemm256_kernel(Params p) {   // <8,4> 256x256, <4,2> 128x128
+  FV_SKIP_EXIT(p.skip);
   static_assert(!ASYM || WN == 4, "asymmetric staging pairs wave w with wave w + 4");
   static_assert(!TN || (!ASYM && !LO8 && MI == 8 && WN == 4), "the TN instance is the plain 256 x 256 one");
   constexpr int BMT = 32 * MI, BNT = 64 * WN, NTH = 128 * WN, BUFB = (BMT + BNT) * 128, AB = BMT * 128;
@@ -774,7 +777,8 @@ __global__ __launch_bounds__(128 * WN, WN == 4 ? 1 : 2) void gemm256_kernel(Para
 // out[m][n] = (res ? res[m][n] : 0) + (bias ? bias[n] : 0) + sum over splits of part[s][m][n], 4 columns per thread
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int splits, int M, int N, int npad,
                                                              const float* __restrict__ bias, const float* res, int ldr, float* out,
-                                                             int ldo) {
+                                                             int ldo, const unsigned* skip = nullptr) {
+  FV_SKIP_EXIT(skip);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const int n4 = N >> 2;
   if (i >= (long)M * n4) return;
@@ -794,7 +798,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 __global__ __launch_bounds__(256) void splitk_reduce_norm_kernel(const float* __restrict__ part, int splits, int M, int N, int npad,
                                                                   const float* __restrict__ bias, const float* res, int ldr, float* out,
                                                                   int ldo, const float* __restrict__ nw, bf16_t* __restrict__ y,
-                                                                  bf16_t* __restrict__ ylo, int ldy, float eps, int lo8) {
+                                                                  bf16_t* __restrict__ ylo, int ldy, float eps, int lo8, const unsigned* skip = nullptr) {
+  FV_SKIP_EXIT(skip);
   const int lane = threadIdx.x & 63;
   const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
@@ -833,7 +838,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_norm_kernel(const float* __
 __global__ __launch_bounds__(256) void splitk_reduce_norm_row_kernel(const float* __restrict__ part, int splits, int M, int N, int npad,
                                                                       const float* __restrict__ bias, const float* res, int ldr, float* out,
                                                                       int ldo, const float* __restrict__ nw, bf16_t* __restrict__ y,
-                                                                      bf16_t* __restrict__ ylo, int ldy, float eps) {
+                                                                      bf16_t* __restrict__ ylo, int ldy, float eps, const unsigned* skip = nullptr) {
+  FV_SKIP_EXIT(skip);
   __shared__ float wsum[4];
   const int m = blockIdx.x, tid = threadIdx.x;
   float4 keep[4];   // N <= 4096
@@ -886,7 +892,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_norm_row_kernel(const float
 // bf16-output epilogues behind K ranges (the tower's last stages and the projector at B <= 4: 48 .. 192 tiles of 64 x 128 walking 48 .. 96 K-tiles each):
 // out = epi(sum of ranges + bias), epi in {bias, bias + GELU, res + scale * ( . )} with the one-launch epilogue's own arithmetic; 8 columns per thread
 __global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const float* __restrict__ part, int splits, int M, int N, int npad, const float* __restrict__ bias,
-                                                                  int epi, const float* __restrict__ scale, const bf16_t* res, int ldr, bf16_t* out, int ldo) {
+                                                                  int epi, const float* __restrict__ scale, const bf16_t* res, int ldr, bf16_t* out, int ldo, const unsigned* skip = nullptr) {
+  FV_SKIP_EXIT(skip);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const int n8 = N >> 3;
   if (i >= (long)M * n8) return;
@@ -916,7 +923,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const float* __
 
 // The few-row split-K of gate/up: part[s][m][16 j .. 16 j + 15] = 8 gate | 8 up sums of range s -> silu(gate) * up as hi | lo bf16 halves ([M][N/2 | N/2]),
 // exactly the FV_EPI_SWIGLU_SPLIT epilogue on the summed accumulators
-__global__ __launch_bounds__(256) void splitk_reduce_swiglu_kernel(const float* __restrict__ part, int splits, int M, int N, int npad, bf16_t* __restrict__ out, int ldo, int lo_off) {
+__global__ __launch_bounds__(256) void splitk_reduce_swiglu_kernel(const float* __restrict__ part, int splits, int M, int N, int npad, bf16_t* __restrict__ out, int ldo, int lo_off, const unsigned* skip = nullptr) {
+  FV_SKIP_EXIT(skip);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   const int n16 = N >> 4;
   if (i >= (long)M * n16) return;
@@ -947,6 +955,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_swiglu_kernel(const float* 
 // during the products), and the bf16 results leave through a wave-private LDS stage as one contiguous 32 x 2C-byte run.
 template <int C>
 __global__ __launch_bounds__(256, C == 96 ? 3 : 1) void pwconv_kernel(Params p) {
+  FV_SKIP_EXIT(p.skip);
   constexpr int KS = C / 32, NT = C / 16, WP = C * 2 + 16, OP = C * 2 + 16, CH = C / 8;
   extern __shared__ __attribute__((aligned(16))) char pw_smem[];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1078,24 +1087,24 @@ static int launch_splitk_reduce(const GemmArgs& a, int splits, int npad, bool fe
   const float* res32 = a.epi == FV_EPI_RES_F32 ? static_cast<const float*>(a.res) : nullptr;
   if (a.epi == FV_EPI_SWIGLU_SPLIT) {
     const long n = (long)a.M * (a.N / 16);
-    hipLaunchKernelGGL(splitk_reduce_swiglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, static_cast<bf16_t*>(a.out), a.ldo, a.lo_off ? a.lo_off : a.N / 2);
+    hipLaunchKernelGGL(splitk_reduce_swiglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, static_cast<bf16_t*>(a.out), a.ldo, a.lo_off ? a.lo_off : a.N / 2, a.skip);
   } else if (a.epi == FV_EPI_BIAS || a.epi == FV_EPI_BIAS_GELU || a.epi == FV_EPI_LS_RES) {
     const long n = (long)a.M * (a.N / 8);
     hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, a.epi, a.scale,
-                       static_cast<const bf16_t*>(a.res), a.ldr, static_cast<bf16_t*>(a.out), a.ldo);
+                       static_cast<const bf16_t*>(a.res), a.ldr, static_cast<bf16_t*>(a.out), a.ldo, a.skip);
   } else if (a.norm_w && (few_rows || a.few_rows) && a.N <= 4096 && !lo8) {   // a block per row (the wave-per-row form below walks splits x N / 256 dependent
                                                                               // steps: 32 us per launch at 1024 x 3584, 4.6 % of the 7B step); inference only
     g_norm_fused = true;
     hipLaunchKernelGGL(splitk_reduce_norm_row_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, res32, a.ldr,
-                       static_cast<float*>(a.out), a.ldo, a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps);
+                       static_cast<float*>(a.out), a.ldo, a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps, a.skip);
   } else if (a.norm_w) {
     g_norm_fused = true;
     hipLaunchKernelGGL(splitk_reduce_norm_kernel, dim3((unsigned)((a.M + 3) / 4)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, res32, a.ldr,
-                       static_cast<float*>(a.out), a.ldo, a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps, lo8);
+                       static_cast<float*>(a.out), a.ldo, a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps, lo8, a.skip);
   } else {
     const long quads = (long)a.M * (a.N / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, res32, a.ldr,
-                       static_cast<float*>(a.out), a.ldo);
+                       static_cast<float*>(a.out), a.ldo, a.skip);
   }
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
@@ -1109,7 +1118,7 @@ int launch_gemm(const GemmArgs& a, hipStream_t s) {
   const int rc = launch_gemm_core(a, s);
   if (rc != FV_OK) return rc;
   if (a.norm_w && rc == FV_OK && !g_norm_fused)
-    return launch_rmsnorm(static_cast<const float*>(a.out), a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.M, a.N, a.norm_eps, s, 0, nullptr, a.ksplit == 2 ? 1 : 0);
+    return launch_rmsnorm(static_cast<const float*>(a.out), a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.M, a.N, a.norm_eps, s, 0, nullptr, a.ksplit == 2 ? 1 : 0, a.skip);
   return FV_OK;
 }
 
@@ -1132,7 +1141,7 @@ static int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
   if ((size_t)a.K * a.lda * 2 >= ((size_t)1 << 31) || (size_t)a.K * a.ldw * 2 >= ((size_t)1 << 31)) return fv_fail(FV_ERR_UNSUPPORTED, "gemm (TN): operands of 2 GiB or more");
   Params p;
   p.A = a.A; p.W = a.W; p.bias = a.bias; p.scale = nullptr; p.res = a.res; p.out = a.out;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldw = a.ldw; p.ldr = a.ldr; p.ldo = a.ldo; p.epi = a.epi; p.ksplit = 0;
+  p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldw = a.ldw; p.ldr = a.ldr; p.ldo = a.ldo; p.epi = a.epi; p.ksplit = 0; p.skip = a.skip;
   static int cus = 0;
   if (!cus) {
     int dev = 0;
@@ -1163,7 +1172,7 @@ static int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
   if (splits > 1) {
     const long quads = (long)a.M * (a.N / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, p.npad, a.bias,
-                       a.epi == FV_EPI_RES_F32 ? static_cast<const float*>(a.res) : nullptr, a.ldr, static_cast<float*>(a.out), a.ldo);
+                       a.epi == FV_EPI_RES_F32 ? static_cast<const float*>(a.res) : nullptr, a.ldr, static_cast<float*>(a.out), a.ldo, a.skip);
   }
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
@@ -1202,7 +1211,7 @@ static int launch_gemm_core(const GemmArgs& a, hipStream_t s) {
   p.A = a.A; p.W = a.W; p.bias = a.bias; p.scale = a.scale; p.res = a.res; p.out = a.out; p.lo_off = a.lo_off ? a.lo_off : a.N / 2;
   p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldr = a.ldr; p.ldo = a.ldo; p.epi = a.epi;
   p.ksplit = a.ksplit == 2 ? 2 : (a.ksplit ? 1 : 0);
-  p.sat = a.sat;
+  p.sat = a.sat; p.skip = a.skip;
   p.stash = a.stash; p.stash_f16 = a.stash_f16;
   if (a.stash && a.epi == FV_EPI_MUL_GELUP) { if ((uintptr_t)a.stash & 15) return fv_fail(FV_ERR_ARG, "gemm: MUL_GELUP's gelu(a) output must be 16-byte aligned"); }
   else if (a.stash && a.epi != FV_EPI_GELU_GRAD && ((a.epi != FV_EPI_SWIGLU_SPLIT && a.epi != FV_EPI_SWIGLU_F16) || ((uintptr_t)a.stash & 15) || (a.stash_f16 && !a.sat)))

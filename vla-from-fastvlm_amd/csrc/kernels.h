@@ -43,6 +43,7 @@ struct GemmArgs {
   // with row stride ldw >= N, out[m][n] = sum_k A[k][m] W[k][n].  K % 64 == 0 (rows past the data must be zero), M % 8 == 0, N % 8 == 0, fp32
   // epilogues, no ksplit; the 256-tile kernel only (LDS image in [k/8][n/16][8][16] blocks, fragments by ds_read_b64_tr_b16)
   int tn = 0, ldw = 0;
+  const unsigned* skip = nullptr;   // prompt reuse (fv_set_prompt_reuse): device word; non-zero = every kernel of this launch returns at once.  null: as ever
 };
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 
@@ -106,21 +107,21 @@ int launch_se_gelu(const bf16_t* x, const float* w1, const float* b1, const floa
 // lens (B) int32 or null; the visible key count of batch row b is clamp(lens[b] + len_add, 1, T)
 int launch_attention(const bf16_t* q, const bf16_t* k, const bf16_t* v, int ldq, int ldk, int ldv, bf16_t* out,
                      int ldo, int B, int T, int heads, int kv_heads, int D, int causal, const int32_t* lens,
-                     int len_add, float scale, hipStream_t s);
+                     int len_add, float scale, hipStream_t s, const unsigned* skip = nullptr);   // skip: GemmArgs::skip (the causal / masked kernel only)
 
 // decoder elementwise
 int launch_embed_gather(const int32_t* ids, const bf16_t* table, const float* img_tokens, float* x, int B, int T,
-                        int Ni, int H, int vocab, hipStream_t s);
+                        int Ni, int H, int vocab, hipStream_t s, const unsigned* skip = nullptr);   // skip: as GemmArgs::skip, here and below
 // y_lo != null: also writes the bf16 remainder (x ~= y + y_lo), the split operand of the parity-mode decoder GEMMs
 int launch_rmsnorm(const float* x, const float* w, bf16_t* y, bf16_t* y_lo, int ldy, int rows, int H, float eps, hipStream_t s,
                    int f16 = 0, unsigned* sat = nullptr,    // f16 != 0: y receives fp16 bits (y_lo must be null), clamps counted in *sat
-                   int lo8 = 0);                            // lo8 != 0: the remainder leaves as fp8 (x 2^8), one byte per element, at y_lo's row starts
+                   int lo8 = 0, const unsigned* skip = nullptr);   // lo8 != 0: the remainder leaves as fp8 (x 2^8), one byte per element, at y_lo's row starts
 // in place: n bf16 values -> the fp16 values scale * x (weights of the fp16-operand projections, once at load time); maxbits (device,
 // optional) receives max(|scale * x|) as float bits by atomicMax, so the loader can refuse weights outside the fp16 range
 int launch_bf16_to_f16(bf16_t* p, size_t n, float scale, hipStream_t s, unsigned* maxbits = nullptr);
 // W [rows][K] bf16 -> fp8 e4m3 copy of W x 2^6 at row stride 2K bytes (GemmArgs::W8); maxbits as launch_bf16_to_f16
 int launch_bf16_to_w8(const bf16_t* w, void* w8, size_t rows, int K, hipStream_t s, unsigned* maxbits = nullptr);
-int launch_rope_f32(float* qkv, const float2* table, int ld, int rows, int T, int heads, int kv_heads, int D, hipStream_t s);
+int launch_rope_f32(float* qkv, const float2* table, int ld, int rows, int T, int heads, int kv_heads, int D, hipStream_t s, const unsigned* skip = nullptr);
 // rope != null: qkv holds un-rotated projections; the rotate-half RoPE is fused into the MFMA kernel (head_dim 64 / 128) or applied
 // in place by a rope_f32 launch ahead of the VALU kernel (head_dim 32)
 int launch_attention_f32(float* qkv, int ld, bf16_t* out_hi, bf16_t* out_lo, int ldo, int B, int T, int heads,
@@ -128,15 +129,16 @@ int launch_attention_f32(float* qkv, int ld, bf16_t* out_hi, bf16_t* out_lo, int
                          const float* pre = nullptr, int ldp = 0, int Np = 0,    // pre: cached [k | v] rows of positions < Np (8f-1)
                          float* lse = nullptr,    // optional [B][heads][T] row statistics max + log(sum) for the backward pass (head_dim 64 / 128, Np = 0)
                          int lo8 = 0,             // remainders as fp8 bytes (the hi + lo8 operand form of llm_precision = 5)
-                         void* split_scratch = nullptr);   // attention_split_scratch_bytes() bytes -> the split-bf16 kernel (attention_split.hip) when lse is wanted (training)
+                         void* split_scratch = nullptr,    // attention_split_scratch_bytes() bytes -> the split-bf16 kernel (attention_split.hip) when lse is wanted (training)
                                                            // or the sequence is at least FV_ATTN_SPLIT_MIN_T long (the spliced prefill); never with a cached prefix or lo8
+                         const unsigned* skip = nullptr);
 constexpr int FV_ATTN_SPLIT_MIN_T = 128;
 // table: [>=T][D/2] (cos, sin) pairs built by rope_table_host(); position = row % T
 int launch_rope(bf16_t* qkv, const float2* table, int ld, int rows, int T, int heads, int kv_heads, int D,
-                hipStream_t s);
+                hipStream_t s, const unsigned* skip = nullptr);
 void rope_table_host(float* cos_sin_pairs, int T, int D, float theta);
 int launch_pool_norm(const float* x, const int32_t* lens, const float* w, float* pooled, int B, int Ttot, int Ni,
-                     int H, float eps, int mode, hipStream_t s);
+                     int H, float eps, int mode, hipStream_t s, const unsigned* skip = nullptr);
 
 // ---- unfrozen-backbone training glue (train_kernels.hip) ------------------------------------------------------
 constexpr int RMS_BWD_RPW = 4;      // rows per wave of rmsnorm_bwd_kernel (one dw partial row per wave)
@@ -285,7 +287,8 @@ int launch_tower_commit(const TowerCommitOp* ops_dev, int nops, int nblocks, con
 // per call by a small pre-pass and copied flat into LDS by every q head's / query block's thread block
 size_t attention_split_scratch_bytes(int B, int T, int kv_heads, int D);
 int launch_attention_split_fwd(const float* qkv, int ld, bf16_t* out_hi, bf16_t* out_lo, int ldo, int B, int T, int heads, int kv_heads, int D,
-                               const int32_t* lens, int len_add, float scale, const float2* rope, float* lse, void* scratch, hipStream_t s);
+                               const int32_t* lens, int len_add, float scale, const float2* rope, float* lse, void* scratch, hipStream_t s,
+                               const unsigned* skip = nullptr);
 int launch_attention_split_bwd(const float* qkv, int ld, const bf16_t* o_hi, const bf16_t* o_lo, int ldo, const float* dO, int lddo, const float* lse,
                                float* delta, float* dqkv, int B, int T, int heads, int kv_heads, int D, const int32_t* lens, int len_add, float scale,
                                const float2* rope, hipStream_t s, float* part, long pstride, void* scratch);

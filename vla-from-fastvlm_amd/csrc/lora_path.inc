@@ -311,6 +311,7 @@ int fv_train_lora_commit(fv_handle* h, float* flat_params_master, const float* l
   FV_TRY(check_buffers("fv_train_lora_commit", "buffer", {flat_params_master, lora_params}));
   hipStream_t s = static_cast<hipStream_t>(st);
   LoraState& ls = h->train.lora;
+  FV_TRY(prompt_invalidate(h, s, true));   // the adapted operand images change
   // the master's head | projector front mirrors the trainable buffer's (fv_train_forward_backward reads the head there); nothing else of it is written
   FV_HIP_CHECK(hipMemcpyAsync(flat_params_master, lora_params, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
   const int f16t = h->train.grad_split == 2 ? 1 : 0;
@@ -330,6 +331,7 @@ int fv_train_lora_merge(fv_handle* h, float* flat_params_master, const float* lo
   FV_TRY(check_buffers("fv_train_lora_merge", "buffer", {flat_params_master, lora_params}));
   hipStream_t s = static_cast<hipStream_t>(st);
   LoraState& ls = h->train.lora;
+  FV_TRY(prompt_invalidate(h, s, true));   // (the merged master reaches the operand images with its next commit; the slot goes now)
   FV_HIP_CHECK(hipMemcpyAsync(flat_params_master, lora_params, (size_t)ls.front * 4, hipMemcpyDeviceToDevice, s));
   const bool dora = lora_dora(h);
   if (dora) {     // the norms of the master BEFORE it is overwritten; they describe neither buffer afterwards: the next commit refreshes them
@@ -345,6 +347,7 @@ int fv_train_lora_init_magnitude(fv_handle* h, const float* flat_params_master, 
   FV_TRY(lora_check(h));
   if (!lora_dora(h)) return fv_fail(FV_ERR_STATE, "fv_train_lora_init_magnitude: LoRA mode was begun without FV_LORA_DORA");
   FV_TRY(check_buffers("fv_train_lora_init_magnitude", "buffer", {flat_params_master, lora_params}));
+  FV_TRY(prompt_invalidate(h, static_cast<hipStream_t>(st), true));
   h->train.lora.master = nullptr;     // (the norm buffer now describes these buffers, but no commit of them has run)
   return lora_refresh_norms(h, flat_params_master, lora_params, lora_params, static_cast<hipStream_t>(st));
 }

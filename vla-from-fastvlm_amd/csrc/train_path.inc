@@ -512,6 +512,7 @@ int fv_train_commit(fv_handle* h, const float* flat, fv_stream st) {
   FV_TRY(train_check(h));
   if (!flat) return fv_fail(FV_ERR_ARG, "fv_train_commit: null buffer");
   hipStream_t s = static_cast<hipStream_t>(st);
+  FV_TRY(prompt_invalidate(h, s, true));   // the decoder's (and the tower's) operand images change: the literal call's kept result is void
   // (the transposed copies of the ACTIVE dgrad form only: fp16 for grad_split = 2, bf16 otherwise -- fv_train_set_options rebuilds the other on a switch)
   FV_TRY(fv::launch_commit(h->train.commit_desc, h->train.commit_n, h->train.commit_tiles, flat, h->train.grad_split == 2 ? 1 : 0, h->f16_flags, s));
   if (h->train.tower) FV_TRY(fv::launch_tower_commit(h->train.tower_ops, h->train.tower_nops, h->train.tower_blocks, flat, h->f16_flags, s));
@@ -525,6 +526,7 @@ int fv_train_set_options(fv_handle* h, int grad_split, int wgrad_f16, int loss_s
   // gradients, 1 ms slower -- are gone from the product; the TN instance itself serves the tower's weight gradients, tower_train.inc)
   if (grad_split < 1 || grad_split > 2 || wgrad_f16 < 0 || wgrad_f16 > 1 || loss_scale_log2 < 0 || loss_scale_log2 > 24)
     return fv_fail(FV_ERR_ARG, "fv_train_set_options: grad_split in {1, 2}, wgrad_f16 in {0, 1}, loss_scale_log2 in [0, 24]");
+  FV_TRY(prompt_invalidate(h, nullptr, false));
   if (h->train.ready && ((grad_split == 2) != (h->train.grad_split == 2))) {
     // the transposed weight copies of the OTHER form may be stale (fv_train_commit refreshes the active form only): rebuild them from the library's weights
     FV_HIP_CHECK(hipSetDevice(h->device));
@@ -553,6 +555,7 @@ int fv_train_loss_scale(fv_handle* h, float* scale_out) {
 int fv_train_set_forward_f16(fv_handle* h, int on) {
   HandleScope _hs(h);
   FV_TRY(train_check(h));
+  FV_TRY(prompt_invalidate(h, nullptr, false));
   if (!on) { if (h->train.fwd_f16) { h->train.fwd_f16 = false; FV_TRY(build_commit_table(h)); } return FV_OK; }
   FV_HIP_CHECK(hipSetDevice(h->device));
   FV_HIP_CHECK(hipDeviceSynchronize());

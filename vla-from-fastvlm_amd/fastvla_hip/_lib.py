@@ -132,6 +132,8 @@ SIGNATURES = {
     "fv_llm_forward_pooled": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "fv_llm_fp16_saturations": (_i, [_vp, C.POINTER(_u64), _i]),
     "fv_set_batch_invariant": (_i, [_vp, _i]),
+    "fv_set_prompt_reuse": (_i, [_vp, _i]),
+    "fv_prompt_reuse_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "fv_llm_prefix_bytes": (_i, [_vp, _i, _i, C.POINTER(C.c_size_t)]),
     "fv_llm_prefix": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "fv_llm_forward_pooled_prefixed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),

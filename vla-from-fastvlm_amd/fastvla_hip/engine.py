@@ -214,6 +214,9 @@ class FastVLAEngine:
         self._invariant_on = False
         if self._invariant_policy:
             self.set_batch_invariant(True)
+        # FASTVLA_PROMPT_REUSE=0: the literal call recomputes the decoder every time (fv_set_prompt_reuse; on by default in the library)
+        if os.environ.get("FASTVLA_PROMPT_REUSE", "1") == "0":
+            self.set_prompt_reuse(False)
         offs = (C.c_int64 * 13)()
         _lib.check(self.lib.fv_head_layout(self.h, C.byref(offs)), "fv_head_layout")
         self.head_offsets = list(offs)
@@ -477,6 +480,16 @@ class FastVLAEngine:
         _lib.check(self.lib.fv_set_batch_invariant(self.h, int(bool(on))), "fv_set_batch_invariant", self.h)
         self._invariant_on = bool(on)
 
+    def set_prompt_reuse(self, on: bool = True) -> None:
+        """fv_set_prompt_reuse: literal-mode calls keep the pooled rows of the last prompt on the device and return them while (ids, lens) stay the same."""
+        _lib.check(self.lib.fv_set_prompt_reuse(self.h, int(bool(on))), "fv_set_prompt_reuse", self.h)
+
+    def prompt_reuse_stats(self) -> Tuple[int, int]:
+        """(literal calls that used the prompt slot, how many of them hit) since the engine was created.  Synchronises the device."""
+        calls, hits = C.c_uint64(), C.c_uint64()
+        _lib.check(self.lib.fv_prompt_reuse_stats(self.h, C.byref(calls), C.byref(hits)), "fv_prompt_reuse_stats", self.h)
+        return int(calls.value), int(hits.value)
+
     def tokens_consumed(self, consumed: bool) -> None:
         """The caller says whether the tower tokens of the calls that follow feed the decoder (splice mode) or are dropped (the literal reference): unless
         FASTVLA_BATCH_INVARIANT pins the choice, batch invariance of the tower follows that (VERDICT r5 #6)."""
@@ -582,7 +595,13 @@ class FastVLAEngine:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             actions = step()
-        return graph.replay, actions
+
+        def replay(_keep=(saved, images, ids, lens, states, flat_params)):
+            # the graph writes `saved` and reads the static inputs on every replay: they live as long as the replay handle does (handing out graph.replay
+            # alone let `saved` return to the allocator, and a later tensor of the caller's -- a clone of `actions` -- was overwritten by the next replay)
+            graph.replay()
+
+        return replay, actions
 
     # ---------------------------------------------------------------- action expert
     def head_numel(self) -> int:
