@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 from gpu_util import DEV, bf, call, check_close, dev_bf16, dev_f32, lib, stream  # noqa: E402
 from dw_bwd_util import toeplitz as _toeplitz  # noqa: E402  (the Toeplitz table of the MFMA depthwise kernels: shared with tests/test_gpu_dw_backward.py)
+from dw_fwd_util import toeplitz_s2 as _toeplitz_s2  # noqa: E402  (the stride-2 kernel's table: shared with tests/test_gpu_dw_forward.py)
 from fastvla_hip import _lib  # noqa: E402
 from oracle import fastvit_hd, preprocess, qwen2  # noqa: E402
 
@@ -527,20 +528,6 @@ def test_dwconv_mfma(k, C, H, W, gelu):
          "fv_op_dwconv_mfma")
     torch.cuda.synchronize()
     check_close(y.float().cpu().permute(0, 3, 1, 2), ref, what=f"dwconv mfma k{k} C{C} {H}x{W}")
-
-
-def _toeplitz_s2(w):
-    """[2C,1,7,7] -> the table of fv_op_dwconv_s2_mfma: [C/16][e][ky][m][16 ch][4 i][4 kk] = w[2(16g+ch)+e][ky][4m+kk-2i]."""
-    C = w.shape[0] // 2
-    wv = w.view(C // 16, 16, 2, 7, 7)                       # [g][ch][e][ky][kx]
-    t = torch.zeros(C // 16, 2, 7, 4, 16, 4, 4)
-    for m in range(4):
-        for i in range(4):
-            for kk in range(4):
-                kx = 4 * m + kk - 2 * i
-                if 0 <= kx < 7:
-                    t[:, :, :, m, :, i, kk] = wv[:, :, :, :, kx].permute(0, 2, 3, 1)
-    return t
 
 
 @pytest.mark.parametrize("C,H,W,gelu", [(32, 16, 32, 1), (96, 40, 64, 1), (64, 18, 34, 0), (192, 32, 32, 1), (32, 2, 16, 0)])
