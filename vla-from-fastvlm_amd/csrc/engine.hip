@@ -617,77 +617,147 @@ int gemm_p(fv_handle* h, const fv::GemmArgs& g_in, hipStream_t s) {
 }
 double dw_flops(int B, int Ho, int Wo, int Cout, int k) { return 2.0 * B * Ho * Wo * Cout * k * k; }
 
-// stride-1 depthwise conv: MFMA Toeplitz kernel when a table was packed for this layer, VALU kernels otherwise
+// stride-1 depthwise conv under its profiler bracket: MFMA Toeplitz kernel when a table was packed for this layer, VALU kernels otherwise
 int dw_s1(fv_handle* h, const bf16_t* x, const float* w, const bf16_t* ttab, const float* bias, bf16_t* y, int mb, int H, int C,
           int k, hipStream_t s) {
-  if (ttab && !h->no_mfma_dw) return fv::launch_dwconv_mfma(x, ttab, bias, y, mb, H, H, C, k, 0, s);
-  return fv::launch_dwconv(x, w, bias, y, mb, H, H, C, k, 1, 1, 0, s);
+  FV_P(FV_FAM_DWCONV, dw_flops(mb, H, H, C, k), 4.0 * (mb * H * H) * C,
+       (ttab && !h->no_mfma_dw) ? fv::launch_dwconv_mfma(x, ttab, bias, y, mb, H, H, C, k, 0, s) : fv::launch_dwconv(x, w, bias, y, mb, H, H, C, k, 1, 1, 0, s));
+  return FV_OK;
 }
 
-// fused ConvFFN pointwise half: the 32x32x16 kernel where it exists (C = 96 / 192 / 384), else the 16x16x32 one
-// ranges: the inference tower lets launch_convffn32 cut the hidden units into ranges when the launch has few row tiles (B <= 2).  That changes the fp32
-// summation order (<= 1 bf16 step per output), so the TRAINING forward keeps the one-launch form at every batch size: a row's gradient must not depend
-// on how many rows share its step (tests/test_gpu_train_tower.py, B = 32 against B = 2).
-// stash_y (the tower's training forward): the pre-activation / 4 written out by the one-launch 32x32x16 kernel (ffn_stash_ok says whether it can)
-bool ffn_stash_ok(const fv_handle* h, const FFN& f, int M, int C) { return f.w2q && !h->no_ffn32 && fv::convffn32_stash_supported(M, C); }
-int fused_ffn(fv_handle* h, const FFN& f, const bf16_t* t, const bf16_t* res, bf16_t* out, int M, int C, int hidden, hipStream_t s, bool ranges = true,
-              bf16_t* stash_y = nullptr) {
-  if (stash_y) return fv::launch_convffn32(t, f.w2q, f.fc1_b, f.fc2_b, f.ls, res, out, M, C, hidden, s, nullptr, 0, stash_y);
-  if (f.w2q && !h->no_ffn32 && (size_t)M * C * 2 < ((size_t)1 << 31))
-    return fv::launch_convffn32(t, f.w2q, f.fc1_b, f.fc2_b, f.ls, res, out, M, C, hidden, s, ranges && !h->batch_invariant ? h->ffn_part : nullptr,
-                                ranges && !h->batch_invariant && h->ffn_part ? FFN_PART_BYTES : 0);
-  return fv::launch_convffn(t, f.fc1_w, f.fc1_b, f.w2p, f.fc2_b, f.ls, res, out, M, C, hidden, s);
+// ---- the tower's units: ONE body each -----------------------------------------------------------------------------------------------------
+// A body picks the route, brackets every launch for the profiler (the one cost formula) and launches.  Two walks call them: tower_pass below (inference
+// and the taps, over three ping-pong buffers) and unit_forward (tower_train.inc, into the training stash).  A body does not know its caller: every buffer
+// is an argument, and what differs between the walks arrives as a pointer that is null or as pointers that alias.  (RepCPE and the ConvFFN's own 7x7 in an
+// attention block are dw_s1 itself.)
+
+// stem: dense 3x3 stride 2 (in -> h0 at half resolution; MFMA where its weight image was packed), depthwise 3x3 stride 2 (h0 -> h1); stem_pw follows.
+// At inference the fused stems of tower_pass stand in for stem_convs; training cannot use them because the backward reads h0 and h1.
+int stem_convs(fv_handle* h, const bf16_t* in, bf16_t* h0, bf16_t* h1, int mb, hipStream_t s) {
+  const Tower& tw = h->tw;
+  const int S = h->d.image_size, C0 = h->d.tower_dims[0];
+  FV_P(FV_FAM_STEM, 2.0 * mb * (S / 2) * (S / 2) * 27 * C0, (double)mb * S * S * 8 + (double)mb * (S / 2) * (S / 2) * C0 * 2,
+       tw.stem0_wp ? fv::launch_stem_mfma(in, tw.stem0_wp, tw.stem0_b, h0, mb, S, C0, s) : fv::launch_stem_conv(in, tw.stem0_w, tw.stem0_b, h0, mb, S, C0, s));
+  FV_P(FV_FAM_DWCONV, dw_flops(mb, S / 4, S / 4, C0, 3), (double)mb * (S / 2) * (S / 2) * C0 * 2 * 1.25,
+       fv::launch_dwconv(h0, tw.stem1_w, tw.stem1_b, h1, mb, S / 2, S / 2, C0, 3, 2, 1, 1, s));
+  return FV_OK;
+}
+int stem_pw(fv_handle* h, const bf16_t* h1, bf16_t* out, int mb, hipStream_t s) {   // 1x1 + GELU
+  const int H = h->d.image_size / 4, C0 = h->d.tower_dims[0];
+  fv::GemmArgs g{h1, C0, h->tw.stem2_w, mb * H * H, C0, C0, h->tw.stem2_b, nullptr, nullptr, 0, out, C0, FV_EPI_BIAS_GELU};
+  return gemm_p(h, g, s);
 }
 
-int run_ffn(fv_handle* h, const FFN& f, bf16_t* x_dw_in, bf16_t* dw_out, bf16_t* hid, bf16_t* res_out, int mb, int H, int W, int C,
-            int ratio, hipStream_t s) {
-  // dw_out = dw7x7(x_dw_in) (+BN folded); hid = gelu(fc1(dw_out)); res_out += ls * fc2(hid)
-  const int M = mb * H * W;
-  FV_P(FV_FAM_DWCONV, dw_flops(mb, H, W, C, 7), 4.0 * M * C, dw_s1(h, x_dw_in, f.dw_w, f.dw_t, f.dw_b, dw_out, mb, H, C, 7, s));
-  if (f.w2p && !h->no_fused_ffn) {
-    prof_begin(h, FV_FAM_GEMM, 4.0 * M * C * (double)(C * ratio), 6.0 * M * C, s, M, C, C * ratio, 6);
-    const int rc = fused_ffn(h, f, dw_out, res_out, res_out, M, C, C * ratio, s);
-    prof_end(h, s);
-    return rc;
+// RepMixer block, convolution half: x' = dw3x3(in), t = dw7x7(x') (the ConvFFN's own 7x7).  mixer_pair_ok is THE predicate for the marching kernel that
+// writes both in one pass.  That kernel refuses aliased buffers: a walk whose t aliases `in` gets the two launches.
+bool mixer_pair_ok(const fv_handle* h, const Block& b, int mb, int H, int C) {
+  static const bool pair_on = !fv_ab_env("FASTVLA_NO_DW_PAIR");
+  return pair_on && !h->no_mfma_dw && b.mix_t && b.ffn.dw_t && fv::dwconv_pair_supported(mb, H, H, C);
+}
+int mixer_convs(fv_handle* h, const Block& b, const bf16_t* in, bf16_t* xp, bf16_t* t, int mb, int H, int C, hipStream_t s) {
+  if (t != in && mixer_pair_ok(h, b, mb, H, C)) {
+    FV_P(FV_FAM_DWCONV, dw_flops(mb, H, H, C, 3) + dw_flops(mb, H, H, C, 7), 6.0 * (mb * H * H) * C,
+         fv::launch_dwconv_pair(in, b.mix_t, b.mix_b, b.ffn.dw_t, b.ffn.dw_b, xp, t, mb, H, H, C, s));
+    return FV_OK;
   }
-  fv::GemmArgs g1{dw_out, C, f.fc1_w, M, C * ratio, C, f.fc1_b, nullptr, nullptr, 0, hid, C * ratio, FV_EPI_BIAS_GELU};
-  FV_TRY(gemm_p(h, g1, s));
-  fv::GemmArgs g2{hid, C * ratio, f.fc2_w, M, C, C * ratio, f.fc2_b, f.ls, res_out, C, res_out, C, FV_EPI_LS_RES};
-  if (!h->batch_invariant) { g2.splitk_ws = h->ffn_part; g2.splitk_bytes = h->ffn_part ? FFN_PART_BYTES : 0; }   // few rows (B <= 2): launch_gemm cuts K = 4C into ranges (inference only)
-  FV_TRY(gemm_p(h, g2, s));
+  FV_TRY(dw_s1(h, in, b.mix_w, b.mix_t, b.mix_b, xp, mb, H, C, 3, s));
+  return dw_s1(h, xp, b.ffn.dw_w, b.ffn.dw_t, b.ffn.dw_b, t, mb, H, C, 7, s);
+}
+
+// ConvFFN, pointwise half: out = res + ls * (fc2(gelu(fc1(t) + b1)) + b2).  ffn_route is THE choice between the fused 32x32x16 kernel (C = 96 / 192 / 384),
+// the fused 16x16x32 one, and two GEMMs through hb.
+//   part / part_bytes: partial-sum scratch.  With it launch_convffn32 cuts the hidden units into ranges when the launch has few row tiles (B <= 2), and the
+//     unfused fc2 cuts K.  That changes the fp32 summation order (<= 1 bf16 step per output).  Null asks for the one-launch form: batch-invariant inference,
+//     and the TRAINING forward at every batch size, where a row's gradient must not depend on how many rows share its step
+//     (tests/test_gpu_train_tower.py, B = 32 against B = 2).
+//   stash_y (training): the 32x32x16 kernel also writes the pre-activation / 4 for the backward.  ffn_stash_ok says where the plan may reserve one.
+enum FfnRoute { FFN_GEMMS, FFN_16, FFN_32 };
+FfnRoute ffn_route(const fv_handle* h, const FFN& f, int M, int C) {
+  if (!f.w2p || h->no_fused_ffn) return FFN_GEMMS;
+  return f.w2q && !h->no_ffn32 && (size_t)M * C * 2 < ((size_t)1 << 31) ? FFN_32 : FFN_16;
+}
+bool ffn_stash_ok(const fv_handle* h, const FFN& f, int M, int C) { return ffn_route(h, f, M, C) == FFN_32 && fv::convffn32_stash_supported(M, C); }
+int ffn_pointwise(fv_handle* h, const FFN& f, const bf16_t* t, const bf16_t* res, bf16_t* out, bf16_t* hb, float* part, size_t part_bytes, bf16_t* stash_y,
+                  int M, int C, int hid, hipStream_t s) {
+  const FfnRoute r = ffn_route(h, f, M, C);
+  if (stash_y && r != FFN_32) return fv_fail(FV_ERR_STATE, "ConvFFN stash reserved where the 32x32x16 kernel does not run (M=%d C=%d)", M, C);
+  if (r == FFN_GEMMS) {
+    fv::GemmArgs g1{t, C, f.fc1_w, M, hid, C, f.fc1_b, nullptr, nullptr, 0, hb, hid, FV_EPI_BIAS_GELU};
+    FV_TRY(gemm_p(h, g1, s));
+    fv::GemmArgs g2{hb, hid, f.fc2_w, M, C, hid, f.fc2_b, f.ls, res, C, out, C, FV_EPI_LS_RES};
+    g2.splitk_ws = part; g2.splitk_bytes = part_bytes;
+    return gemm_p(h, g2, s);
+  }
+  prof_begin(h, FV_FAM_GEMM, 4.0 * M * C * (double)hid, 6.0 * M * C + (stash_y ? 2.0 * M * hid : 0.0), s, M, C, hid, 6);
+  const int rc = r == FFN_32 ? fv::launch_convffn32(t, f.w2q, f.fc1_b, f.fc2_b, f.ls, res, out, M, C, hid, s, part, part_bytes, stash_y)
+                             : fv::launch_convffn(t, f.fc1_w, f.fc1_b, f.w2p, f.fc2_b, f.ls, res, out, M, C, hid, s);
+  prof_end(h, s);
+  return rc;
+}
+
+// attention block, token-mixer half: y = LayerNorm(in), qkv = y . Wqkv^T, o = attention(qkv), x1 = in + ls1 * (proj(o) + pb)   (o may alias y, x1 may alias in)
+int attn_mixer(fv_handle* h, const Block& b, const bf16_t* in, bf16_t* y, bf16_t* qkv, bf16_t* o, bf16_t* x1, int mb, int H, int C, hipStream_t s) {
+  const fv_model_desc& d = h->d;
+  const int M = mb * H * H, nh = C / d.tower_head_dim;
+  FV_P(FV_FAM_NORM, 8.0 * M * C, 4.0 * M * C, fv::launch_layernorm_rows(in, b.ln_w, b.ln_b, y, M, C, d.ln_eps, s));
+  fv::GemmArgs gq{y, C, b.qkv_w, M, 3 * C, C, nullptr, nullptr, nullptr, 0, qkv, 3 * C, FV_EPI_BIAS};
+  FV_TRY(gemm_p(h, gq, s));
+  FV_P(FV_FAM_ATTN, 4.0 * mb * (double)(H * H) * (H * H) * C, 8.0 * M * C,
+       fv::launch_attention(qkv, qkv + C, qkv + 2 * C, 3 * C, 3 * C, 3 * C, o, C, mb, H * H, nh, nh, d.tower_head_dim, 0, nullptr, 0,
+                            1.0f / std::sqrt((float)d.tower_head_dim), s));
+  fv::GemmArgs gp{o, C, b.proj_w, M, C, C, b.proj_b, b.ls1, in, C, x1, C, FV_EPI_LS_RES};
+  return gemm_p(h, gp, s);
+}
+
+// PatchEmbed: depthwise 7x7 stride 2, C -> C2 channels (in -> h1; MFMA where its table was packed), then 1x1 + GELU (h1 -> out)
+int patch_embed(fv_handle* h, const Down& dn, const bf16_t* in, bf16_t* h1, bf16_t* out, int mb, int H, int C, int C2, hipStream_t s) {
+  const int M = mb * H * H;
+  FV_P(FV_FAM_DWCONV, dw_flops(mb, H / 2, H / 2, C2, 7), 2.0 * M * C + 2.0 * (M / 4) * C2,
+       (dn.lk_t && !h->no_mfma_dw) ? fv::launch_dwconv_s2_mfma(in, dn.lk_t, dn.lk_b, h1, mb, H, H, C, 1, s)
+                                   : fv::launch_dwconv(in, dn.lk_w, dn.lk_b, h1, mb, H, H, C, 7, 2, C2 / C, 1, s));
+  fv::GemmArgs g{h1, C2, dn.pw_w, mb * (H / 2) * (H / 2), C2, C2, dn.pw_b, nullptr, nullptr, 0, out, C2, FV_EPI_BIAS_GELU};
+  return gemm_p(h, g, s);
+}
+
+// the tower's head: conv_exp (depthwise 3x3, CL -> CO channels: in -> e), then SE + GELU (e -> out; se: its fp32 scratch)
+int tower_head(fv_handle* h, const bf16_t* in, bf16_t* e, bf16_t* out, float* se, int mb, int H, hipStream_t s) {
+  const fv_model_desc& d = h->d;
+  const Tower& tw = h->tw;
+  const int CL = d.tower_dims[d.tower_stages - 1], CO = d.tower_out_dim, P = H * H;
+  FV_P(FV_FAM_DWCONV, dw_flops(mb, H, H, CO, 3), 2.0 * mb * P * (CL + CO), fv::launch_dwconv(in, tw.exp_w, tw.exp_b, e, mb, H, H, CL, 3, 1, CO / CL, 0, s));
+  FV_P(FV_FAM_ELT, 20.0 * mb * P * CO, 6.0 * mb * P * CO, fv::launch_se_gelu(e, tw.se_w1, tw.se_b1, tw.se_w2, tw.se_b2, out, se, mb, P, CO, d.tower_se_rd, s));
   return FV_OK;
 }
 
-// parity-test hook: copy the activation map (NHWC bf16) of tap `t` for images [b0, b0 + mb) out of the ping-pong buffer
-int tap_copy(fv_handle* h, int t, const bf16_t* src, int b0, int mb, size_t per_image, hipStream_t s) {
-  if (!h->taps || t >= h->n_taps || !h->taps[t]) return FV_OK;
-  bf16_t* dst = static_cast<bf16_t*>(h->taps[t]) + (size_t)b0 * per_image;
+// parity-test hook: copy an activation map (NHWC bf16) for images [b0, b0 + mb) into entry t of a tap table.  fv_vision_forward_taps: t = 0 the stem, 1 + i
+// stage i; fv_vision_forward_unit_taps: t = the unit (fv_vision_unit_info order)
+int tap_copy(void* const* taps, int n_taps, int t, const bf16_t* src, int b0, int mb, size_t per_image, hipStream_t s) {
+  if (!taps || t >= n_taps || !taps[t]) return FV_OK;
+  bf16_t* dst = static_cast<bf16_t*>(taps[t]) + (size_t)b0 * per_image;
   FV_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)mb * per_image * 2, hipMemcpyDeviceToDevice, s));
   return FV_OK;
 }
 
-// the same per tower UNIT (fv_vision_unit_info order): unit u's output for images [b0, b0 + mb)
-int unit_tap(fv_handle* h, int u, const bf16_t* src, int b0, int mb, size_t per_image, hipStream_t s) {
-  if (!h->utaps || u >= h->n_utaps || !h->utaps[u]) return FV_OK;
-  bf16_t* dst = static_cast<bf16_t*>(h->utaps[u]) + (size_t)b0 * per_image;
-  FV_HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)mb * per_image * 2, hipMemcpyDeviceToDevice, s));
-  return FV_OK;
-}
-
-// tower units in execution order: 0 = stem (three convolutions), then per stage [RepCPE] block ... block [PatchEmbed]
-struct UnitInfo { int kind, stage, side, channels; };   // kind: 0 stem, 1 RepCPE, 2 block, 3 PatchEmbed (side / channels of its OUTPUT)
-std::vector<UnitInfo> tower_units(const fv_model_desc& d) {
+// THE enumeration of the tower's units in execution order: the stem (three convolutions), then per stage [RepCPE] block ... block [PatchEmbed]; with_head
+// appends conv_exp + SE, which fv_vision_unit_info does not count.  side / channels describe a unit's OUTPUT, in_side / in_channels its input; j = the
+// block's index in its stage.
+enum UnitKind { TK_STEM = 0, TK_CPE = 1, TK_BLOCK = 2, TK_DOWN = 3, TK_HEAD = 4 };
+struct UnitInfo { int kind, stage, side, channels, j, in_side, in_channels; };
+std::vector<UnitInfo> tower_units(const fv_model_desc& d, bool with_head = false) {
   std::vector<UnitInfo> u;
   int H = d.image_size / 4;
-  u.push_back({0, 0, H, d.tower_dims[0]});
+  u.push_back({TK_STEM, 0, H, d.tower_dims[0], 0, d.image_size, 4});
   for (int i = 0; i < d.tower_stages; ++i) {
-    if (d.tower_is_attn[i]) u.push_back({1, i, H, d.tower_dims[i]});
-    for (int j = 0; j < d.tower_layers[i]; ++j) u.push_back({2, i, H, d.tower_dims[i]});
-    if (i + 1 < d.tower_stages) { H /= 2; u.push_back({3, i, H, d.tower_dims[i + 1]}); }
+    const int C = d.tower_dims[i];
+    if (d.tower_is_attn[i]) u.push_back({TK_CPE, i, H, C, 0, H, C});
+    for (int j = 0; j < d.tower_layers[i]; ++j) u.push_back({TK_BLOCK, i, H, C, j, H, C});
+    if (i + 1 < d.tower_stages) { u.push_back({TK_DOWN, i, H / 2, d.tower_dims[i + 1], 0, H, C}); H /= 2; }
   }
+  if (with_head) u.push_back({TK_HEAD, d.tower_stages - 1, H, d.tower_out_dim, 0, H, d.tower_dims[d.tower_stages - 1]});
   return u;
 }
 
+// inference walk: the units over three ping-pong buffers (cur = the running activation), then the projector
 int tower_pass(fv_handle* h, const bf16_t* pix, int b0, int mb, bf16_t* tower_out, float* img_tokens, const WsPlan& wp,
                hipStream_t s) {
   const fv_model_desc& d = h->d;
@@ -696,8 +766,9 @@ int tower_pass(fv_handle* h, const bf16_t* pix, int b0, int mb, bf16_t* tower_ou
   bf16_t* cur = reinterpret_cast<bf16_t*>(ws + wp.bufA);
   bf16_t* oth = reinterpret_cast<bf16_t*>(ws + wp.bufB);
   bf16_t* hid = reinterpret_cast<bf16_t*>(ws + wp.bufH);
-  float* se = reinterpret_cast<float*>(ws + wp.se);
-  const int S = d.image_size, C0 = d.tower_dims[0];
+  float* part = h->batch_invariant ? nullptr : h->ffn_part;   // few rows (B <= 2): the ConvFFN and the projector cut their sums into ranges (inference only)
+  const size_t part_bytes = part ? FFN_PART_BYTES : 0;
+  const int S = d.image_size, C0 = d.tower_dims[0], hr = d.tower_mlp_ratio;
   static const bool fuse_stem = !fv_ab_env("FASTVLA_NO_FUSED_STEM");
   if (h->lbsrc) {
     // letterbox + both stem convolutions in one kernel: neither the 1024^2 frame nor the half-resolution map exists in HBM
@@ -714,77 +785,49 @@ int tower_pass(fv_handle* h, const bf16_t* pix, int b0, int mb, bf16_t* tower_ou
          (double)mb * S * S * 8 + (double)mb * (S / 4) * (S / 4) * C0 * 2,
          fv::launch_stem_fused(pix, tw.stem0_wp, tw.stem0_b, tw.stem1_w, tw.stem1_b, oth, mb, S, C0, s));
   } else {
-    FV_P(FV_FAM_STEM, 2.0 * mb * (S / 2) * (S / 2) * 27 * C0, (double)mb * S * S * 8 + (double)mb * (S / 2) * (S / 2) * C0 * 2,
-         tw.stem0_wp ? fv::launch_stem_mfma(pix, tw.stem0_wp, tw.stem0_b, cur, mb, S, C0, s)
-                     : fv::launch_stem_conv(pix, tw.stem0_w, tw.stem0_b, cur, mb, S, C0, s));
-    FV_P(FV_FAM_DWCONV, dw_flops(mb, S / 4, S / 4, C0, 3), (double)mb * (S / 2) * (S / 2) * C0 * 2 * 1.25,
-         fv::launch_dwconv(cur, tw.stem1_w, tw.stem1_b, oth, mb, S / 2, S / 2, C0, 3, 2, 1, 1, s));
+    FV_TRY(stem_convs(h, pix, cur, oth, mb, s));
   }
+  FV_TRY(stem_pw(h, oth, cur, mb, s));
   int H = S / 4;
-  {
-    fv::GemmArgs g{oth, C0, tw.stem2_w, mb * H * H, C0, C0, tw.stem2_b, nullptr, nullptr, 0, cur, C0, FV_EPI_BIAS_GELU};
-    FV_TRY(gemm_p(h, g, s));
-  }
-  FV_TRY(tap_copy(h, 0, cur, b0, mb, (size_t)H * H * C0, s));
+  FV_TRY(tap_copy(h->taps, h->n_taps, 0, cur, b0, mb, (size_t)H * H * C0, s));
   int unit = 0;
-  FV_TRY(unit_tap(h, unit++, cur, b0, mb, (size_t)H * H * C0, s));
+  FV_TRY(tap_copy(h->utaps, h->n_utaps, unit++, cur, b0, mb, (size_t)H * H * C0, s));
   for (int i = 0; i < d.tower_stages; ++i) {
     const int C = d.tower_dims[i];
     const int M = mb * H * H;
     if (d.tower_is_attn[i]) {
-      FV_P(FV_FAM_DWCONV, dw_flops(mb, H, H, C, 7), 4.0 * M * C, dw_s1(h, cur, tw.cpes[i].w, tw.cpes[i].t, tw.cpes[i].b, oth, mb, H, C, 7, s));
+      FV_TRY(dw_s1(h, cur, tw.cpes[i].w, tw.cpes[i].t, tw.cpes[i].b, oth, mb, H, C, 7, s));   // RepCPE
       std::swap(cur, oth);
-      FV_TRY(unit_tap(h, unit++, cur, b0, mb, (size_t)H * H * C, s));
+      FV_TRY(tap_copy(h->utaps, h->n_utaps, unit++, cur, b0, mb, (size_t)H * H * C, s));
     }
     for (const Block& b : tw.stages[i]) {
       if (!d.tower_is_attn[i]) {
-        static const bool pair_ok = !fv_ab_env("FASTVLA_NO_DW_PAIR");
-        if (pair_ok && !h->no_mfma_dw && !h->no_fused_ffn && b.mix_t && b.ffn.dw_t && b.ffn.w2p && fv::dwconv_pair_supported(mb, H, H, C)) {
-          // token mixer and the ConvFFN's 7x7 in one marching kernel: cur -> oth (x') and hid (t); then oth += ls * ffn(t)
-          FV_P(FV_FAM_DWCONV, dw_flops(mb, H, H, C, 3) + dw_flops(mb, H, H, C, 7), 6.0 * M * C,
-               fv::launch_dwconv_pair(cur, b.mix_t, b.mix_b, b.ffn.dw_t, b.ffn.dw_b, oth, hid, mb, H, H, C, s));
-          prof_begin(h, FV_FAM_GEMM, 4.0 * M * C * (double)(C * d.tower_mlp_ratio), 6.0 * M * C, s, M, C, C * d.tower_mlp_ratio, 6);
-          const int rc = fused_ffn(h, b.ffn, hid, oth, oth, M, C, C * d.tower_mlp_ratio, s);
-          prof_end(h, s);
-          if (rc != FV_OK) return rc;
-        } else {
-          FV_P(FV_FAM_DWCONV, dw_flops(mb, H, H, C, 3), 4.0 * M * C, dw_s1(h, cur, b.mix_w, b.mix_t, b.mix_b, oth, mb, H, C, 3, s));  // x = RepMixer(x) -> oth
-          FV_TRY(run_ffn(h, b.ffn, oth, cur, hid, oth, mb, H, H, C, d.tower_mlp_ratio, s));        // oth += ls * ffn(oth)
-        }
+        // x' -> oth.  t -> hid on the pair route, which the walk can take only where the ConvFFN leaves hid free; otherwise t -> cur, the unit's own input,
+        // dead after the 3x3, and mixer_convs sees the alias.  Then oth += ls * ffn(t).
+        bf16_t* t = mixer_pair_ok(h, b, mb, H, C) && ffn_route(h, b.ffn, M, C) != FFN_GEMMS ? hid : cur;
+        FV_TRY(mixer_convs(h, b, cur, oth, t, mb, H, C, s));
+        FV_TRY(ffn_pointwise(h, b.ffn, t, oth, oth, hid, part, part_bytes, nullptr, M, C, C * hr, s));
         std::swap(cur, oth);
       } else {
-        FV_P(FV_FAM_NORM, 8.0 * M * C, 4.0 * M * C, fv::launch_layernorm_rows(cur, b.ln_w, b.ln_b, oth, M, C, d.ln_eps, s));
-        fv::GemmArgs gq{oth, C, b.qkv_w, M, 3 * C, C, nullptr, nullptr, nullptr, 0, hid, 3 * C, FV_EPI_BIAS};
-        FV_TRY(gemm_p(h, gq, s));
-        const int nh = C / d.tower_head_dim;
-        FV_P(FV_FAM_ATTN, 4.0 * mb * (double)(H * H) * (H * H) * C, 8.0 * M * C,
-             fv::launch_attention(hid, hid + C, hid + 2 * C, 3 * C, 3 * C, 3 * C, oth, C, mb, H * H, nh, nh,
-                                  d.tower_head_dim, 0, nullptr, 0, 1.0f / std::sqrt((float)d.tower_head_dim), s));
-        fv::GemmArgs gp{oth, C, b.proj_w, M, C, C, b.proj_b, b.ls1, cur, C, cur, C, FV_EPI_LS_RES};
-        FV_TRY(gemm_p(h, gp, s));
-        FV_TRY(run_ffn(h, b.ffn, cur, oth, hid, cur, mb, H, H, C, d.tower_mlp_ratio, s));
+        FV_TRY(attn_mixer(h, b, cur, oth, hid, oth, cur, mb, H, C, s));
+        FV_TRY(dw_s1(h, cur, b.ffn.dw_w, b.ffn.dw_t, b.ffn.dw_b, oth, mb, H, C, 7, s));   // the ConvFFN's own 7x7; then cur += ls * ffn(oth)
+        FV_TRY(ffn_pointwise(h, b.ffn, oth, cur, cur, hid, part, part_bytes, nullptr, M, C, C * hr, s));
       }
-      FV_TRY(unit_tap(h, unit++, cur, b0, mb, (size_t)H * H * C, s));
+      FV_TRY(tap_copy(h->utaps, h->n_utaps, unit++, cur, b0, mb, (size_t)H * H * C, s));
     }
-    FV_TRY(tap_copy(h, 1 + i, cur, b0, mb, (size_t)H * H * C, s));
+    FV_TRY(tap_copy(h->taps, h->n_taps, 1 + i, cur, b0, mb, (size_t)H * H * C, s));
     if (i + 1 < d.tower_stages) {
       const int C2 = d.tower_dims[i + 1];
-      FV_P(FV_FAM_DWCONV, dw_flops(mb, H / 2, H / 2, C2, 7), 2.0 * M * C + 2.0 * (M / 4) * C2,
-           (tw.downs[i].lk_t && !h->no_mfma_dw)
-               ? fv::launch_dwconv_s2_mfma(cur, tw.downs[i].lk_t, tw.downs[i].lk_b, oth, mb, H, H, C, 1, s)
-               : fv::launch_dwconv(cur, tw.downs[i].lk_w, tw.downs[i].lk_b, oth, mb, H, H, C, 7, 2, C2 / C, 1, s));
+      FV_TRY(patch_embed(h, tw.downs[i], cur, oth, cur, mb, H, C, C2, s));
       H /= 2;
-      fv::GemmArgs g{oth, C2, tw.downs[i].pw_w, mb * H * H, C2, C2, tw.downs[i].pw_b, nullptr, nullptr, 0, cur, C2, FV_EPI_BIAS_GELU};
-      FV_TRY(gemm_p(h, g, s));
-      FV_TRY(unit_tap(h, unit++, cur, b0, mb, (size_t)H * H * C2, s));
+      FV_TRY(tap_copy(h->utaps, h->n_utaps, unit++, cur, b0, mb, (size_t)H * H * C2, s));
     }
   }
-  const int CL = d.tower_dims[d.tower_stages - 1], CO = d.tower_out_dim, P = H * H;
-  FV_P(FV_FAM_DWCONV, dw_flops(mb, H, H, CO, 3), 2.0 * mb * P * (CL + CO), fv::launch_dwconv(cur, tw.exp_w, tw.exp_b, oth, mb, H, H, CL, 3, 1, CO / CL, 0, s));
-  FV_P(FV_FAM_ELT, 20.0 * mb * P * CO, 6.0 * mb * P * CO, fv::launch_se_gelu(oth, tw.se_w1, tw.se_b1, tw.se_w2, tw.se_b2, tower_out, se, mb, P, CO, d.tower_se_rd, s));
+  FV_TRY(tower_head(h, cur, oth, tower_out, reinterpret_cast<float*>(ws + wp.se), mb, H, s));
   // mm_projector: Linear + GELU + Linear -> fp32 tokens ([site] fast_vlm/modeling_fast_vlm.py:51-55)
+  const int CO = d.tower_out_dim, P = H * H;
   fv::GemmArgs p0{tower_out, CO, tw.pj0_w, mb * P, d.llm_hidden, CO, tw.pj0_b, nullptr, nullptr, 0, hid, d.llm_hidden, FV_EPI_BIAS_GELU};
-  if (!h->batch_invariant) { p0.splitk_ws = h->ffn_part; p0.splitk_bytes = h->ffn_part ? FFN_PART_BYTES : 0; }
+  p0.splitk_ws = part; p0.splitk_bytes = part_bytes;
   FV_TRY(gemm_p(h, p0, s));
   fv::GemmArgs p2{hid, d.llm_hidden, tw.pj2_w, mb * P, d.llm_hidden, d.llm_hidden, tw.pj2_b, nullptr, nullptr, 0, img_tokens, d.llm_hidden, FV_EPI_F32};
   FV_TRY(gemm_p(h, p2, s));

@@ -15,15 +15,17 @@
 // (pack(ones) gives each destination element's coefficient, pack(index + 1) its source), and the transposed fp16 dgrad operands (fc2 / proj with their
 // layer scale folded in).
 //
-// Forward = the inference kernels (fused dw3x3 + dw7x7 march, fused ConvFFN, MFMA attention) writing every unit's tensors into a caller-owned stash
-// instead of ping-pong buffers.  Backward, per unit, in fp16 operands carrying the loss scale (train_path.inc): the ConvFFN's hidden is RECOMPUTED by one
-// GEMM whose epilogue leaves gelu(a) and gelu'(a) (FV_EPI_GELU_GRAD); dgrads are NT GEMMs against the transposed fp16 copies (FV_EPI_MUL_AUX /
-// FV_EPI_F16 epilogues write the next operand directly); weight gradients are TN GEMMs over the pixel rows, cut into up to 32 K ranges; layer-scale
-// gradients fall out of the UN-scaled weight gradient (ls_grads_kernel) without another pass over the pixels; everything else in tower_bwd_kernels.hip.
+// Forward = the inference kernels, through the SAME unit bodies as the inference walk (engine.hip: mixer_convs, ffn_pointwise, attn_mixer, ...), writing
+// every unit's tensors into a caller-owned stash instead of ping-pong buffers.  Backward, per unit, in fp16 operands carrying the loss scale
+// (train_path.inc).  The ConvFFN's hidden is not kept: where the forward ran the fused 32x32x16 kernel's STASH instance, its pre-activation / 4 travels
+// in the stash ([M][4C] fp16) and ONE dgrad GEMM leaves both gelu(a) and d a = (dout ls W2) gelu'(a) (FV_EPI_MUL_GELUP); only a block without that stash
+// (the attention blocks, widths the 32x32x16 kernel lacks) recomputes the hidden by a GEMM of its own (FV_EPI_GELU_GRAD).  Dgrads are NT GEMMs against
+// the transposed fp16 copies (FV_EPI_MUL_AUX / FV_EPI_F16 epilogues write the next operand directly); weight gradients are TN GEMMs over the pixel
+// rows, cut into up to 32 K ranges; layer-scale gradients fall out of the UN-scaled weight gradient (ls_grads_kernel) without another pass over the
+// pixels; everything else in tower_bwd_kernels.hip.
 
 namespace {
 
-enum { TK_STEM = 0, TK_CPE = 1, TK_BLOCK = 2, TK_DOWN = 3, TK_HEAD = 4 };
 enum {   // tensor roles inside a unit (index into TowerUnitOffs::o)
   R_W0 = 0, R_B0, R_W1, R_B1, R_W2, R_B2,                                                   // stem
   R_CW = 0, R_CB,                                                                            // RepCPE
@@ -198,62 +200,39 @@ TowerTrainPlan plan_tower_train(const fv_handle* h, int B) {
   size_t o = 0;
   auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes + 256); return r; };
   const size_t S = d.image_size;
-  const int C0 = d.tower_dims[0];
+  const int C0 = d.tower_dims[0], CO = d.tower_out_dim;
   size_t max_io = 0, max_hid = 0, max_rowsw = 0, max_t16 = 0;   // largest unit input / output (elements), largest [rows][4C] (elements), widest row, largest [rows][C + 8]
-  auto io = [&](size_t n) { max_io = std::max(max_io, n); };
-  {
-    TUnit u{TK_STEM, 0, 0, (int)S, 4, (int)S / 4, C0, 0, 0, 0, 0, 0, 0};
-    u.a = take((size_t)B * (S / 2) * (S / 2) * C0 * 2);
-    u.b = take((size_t)B * (S / 4) * (S / 4) * C0 * 2);
-    u.out = take((size_t)B * (S / 4) * (S / 4) * C0 * 2);
-    p.u.push_back(u);
-    io((size_t)B * (S / 4) * (S / 4) * C0);
-    max_hid = std::max(max_hid, (size_t)B * (S / 2) * (S / 2) * C0);   // dL/d(first conv's output) borrows the hidden-sized scratch
-  }
-  int H = (int)S / 4;
-  for (int i = 0; i < d.tower_stages; ++i) {
-    const int C = d.tower_dims[i];
-    const size_t M = (size_t)B * H * H;
-    io(M * C);
-    max_t16 = std::max(max_t16, M * (C + 8));
-    max_rowsw = std::max(max_rowsw, (size_t)C * d.tower_mlp_ratio);
-    if (d.tower_is_attn[i]) {
-      TUnit u{TK_CPE, i, 0, H, C, H, C, 0, 0, 0, 0, 0, 0};
-      u.out = take(M * C * 2);
-      p.u.push_back(u);
+  for (const UnitInfo& q : tower_units(d, true)) {
+    TUnit u{q.kind, q.stage, q.j, q.in_side, q.in_channels, q.side, q.channels, 0, 0, 0, 0, 0, 0};
+    const int C = u.C;
+    const size_t M = (size_t)B * u.H * u.H, out = (size_t)B * u.Ho * u.Ho * u.Co * 2;   // input rows (the stem: pixels), output bytes
+    if (u.kind != TK_STEM) {
+      max_io = std::max(max_io, M * C);
+      max_t16 = std::max(max_t16, M * (C + 8));
+      max_rowsw = std::max(max_rowsw, (size_t)C * d.tower_mlp_ratio);
     }
-    for (int j = 0; j < d.tower_layers[i]; ++j) {
-      TUnit u{TK_BLOCK, i, j, H, C, H, C, 0, 0, 0, 0, 0, 0};
-      if (d.tower_is_attn[i]) {
+    if (u.kind == TK_STEM) {
+      const size_t half = (size_t)B * (S / 2) * (S / 2) * C0;   // the first conv's output h0
+      u.a = take(half * 2);
+      u.b = take(out);
+      max_hid = std::max(max_hid, half);   // dL/dh0 borrows the hidden-sized scratch
+    } else if (u.kind == TK_BLOCK) {
+      if (d.tower_is_attn[u.stage]) {
         u.a = take(M * C * 2); u.b = take(M * 3 * C * 2); u.c = take(M * C * 2); u.d = take(M * C * 2); u.e = take(M * C * 2);
       } else {
         u.a = take(M * C * 2); u.b = take(M * C * 2);
-        // round 6: the fused ConvFFN's pre-activation travels from the forward to the backward (a / 4 as fp16 [M][4C]: convffn32.hip STASH) instead of being
-        // recomputed by a GEMM of its own -- 0.7 GB per image at 1024^2.  (c == 0: the block keeps the recompute.)
-        const Block& blk = h->tw.stages[i][j];
-        if (ffn_stash_ok(h, blk.ffn, (int)M, C) && !fv_ab_env("FASTVLA_NO_FFN_STASH")) u.c = take(M * C * d.tower_mlp_ratio * 2);
+        // the fused ConvFFN's pre-activation travels from the forward to the backward (a / 4 as fp16 [M][4C]: convffn32.hip STASH) -- 0.7 GB per image at
+        // 1024^2 -- exactly where ffn_pointwise will run the STASH instance.  (c == 0: the backward recomputes it by a GEMM of its own.)
+        if (ffn_stash_ok(h, h->tw.stages[u.stage][u.j].ffn, (int)M, C) && !fv_ab_env("FASTVLA_NO_FFN_STASH")) u.c = take(M * C * d.tower_mlp_ratio * 2);
       }
-      u.out = take(M * C * 2);
-      p.u.push_back(u);
       max_hid = std::max(max_hid, M * C * d.tower_mlp_ratio);
+    } else if (u.kind == TK_DOWN || u.kind == TK_HEAD) {
+      u.a = take(out);   // PatchEmbed's h1; the head's conv_exp output
     }
-    if (i + 1 < d.tower_stages) {
-      const int C2 = d.tower_dims[i + 1];
-      TUnit u{TK_DOWN, i, 0, H, C, H / 2, C2, 0, 0, 0, 0, 0, 0};
-      u.a = take(M / 4 * C2 * 2);
-      u.out = take(M / 4 * C2 * 2);
-      p.u.push_back(u);
-      H /= 2;
-      io(M / 4 * C2);
-    }
-  }
-  const int CL = d.tower_dims[d.tower_stages - 1], CO = d.tower_out_dim, P = H * H;
-  {
-    TUnit u{TK_HEAD, d.tower_stages - 1, 0, H, CL, H, CO, 0, 0, 0, 0, 0, 0};
-    u.a = take((size_t)B * P * CO * 2);
+    if (u.kind == TK_HEAD) max_rowsw = std::max(max_rowsw, (size_t)CO);
+    else u.out = take(out);   // (the head writes the caller's tower_out)
+    max_io = std::max(max_io, out / 2);
     p.u.push_back(u);
-    io((size_t)B * P * CO);
-    max_rowsw = std::max(max_rowsw, (size_t)CO);
   }
   p.se = take((size_t)B * (2 * CO + d.tower_se_rd) * 4);
   // scratch: row buffers carry 64 rows of the widest row as slack (the TN weight gradients contract over rows padded to 64 with zeros)
@@ -274,7 +253,7 @@ TowerTrainPlan plan_tower_train(const fv_handle* h, int B) {
   p.f32b = take(cmax * 4);
   // per-image attention statistics
   size_t stats = 0, scr = (size_t)fv::TOWER_COLSUM_CHUNKS * cmax;
-  H = (int)S / 4;
+  int H = (int)S / 4;
   scr = std::max(scr, fv::stem0_wgrad_scratch_floats(B, (int)S, C0));
   scr = std::max(scr, fv::dw_bwd_scratch_floats(B, (int)S / 4, (int)S / 4, C0, 3));
   for (int i = 0; i < d.tower_stages; ++i) {
@@ -325,94 +304,34 @@ int tower_check(fv_handle* h) {
   return FV_OK;
 }
 
-// ---- forward of one unit into its stash ----------------------------------------------------------------------------------------------------
-int ffn_forward(const TowerCtx& c, const FFN& f, const bf16_t* t, const bf16_t* res, bf16_t* out, int M, int C, int hid, bf16_t* stash_y = nullptr) {
-  fv_handle* h = c.h; hipStream_t s = c.s;
-  if (f.w2p) {
-    prof_begin(h, FV_FAM_GEMM, 4.0 * M * C * (double)hid, 6.0 * M * C + (stash_y ? 2.0 * M * hid : 0.0), s, M, C, hid, 6);
-    const int rc = fused_ffn(h, f, t, res, out, M, C, hid, s, false, stash_y);
-    prof_end(h, s);
-    return rc;
-  }
-  bf16_t* hb = c.at<bf16_t>(c.tp->hh);
-  fv::GemmArgs g1{t, C, f.fc1_w, M, hid, C, f.fc1_b, nullptr, nullptr, 0, hb, hid, FV_EPI_BIAS_GELU};
-  FV_TRY(gemm_p(h, g1, s));
-  fv::GemmArgs g2{hb, hid, f.fc2_w, M, C, hid, f.fc2_b, f.ls, res, C, out, C, FV_EPI_LS_RES};
-  FV_TRY(gemm_p(h, g2, s));
-  return FV_OK;
-}
-
+// ---- forward of one unit into its stash: the unit bodies of engine.hip over the plan's buffers -----------------------------------------------------
 int unit_forward(const TowerCtx& c, int ui, const bf16_t* in, bf16_t* out_override) {
   fv_handle* h = c.h; hipStream_t s = c.s;
-  const fv_model_desc& d = h->d;
   const Tower& tw = h->tw;
   const TUnit& u = c.tp->u[ui];
-  const int B = c.B;
+  const int B = c.B, H = u.H, C = u.C;
   bf16_t* out = out_override ? out_override : c.at<bf16_t>(u.out);
+  bf16_t *a = c.at<bf16_t>(u.a), *b = c.at<bf16_t>(u.b);
   if (u.kind == TK_STEM) {
-    const int S = d.image_size, C0 = d.tower_dims[0], H = S / 4;
-    bf16_t* h0 = c.at<bf16_t>(u.a);
-    bf16_t* h1 = c.at<bf16_t>(u.b);
-    FV_P(FV_FAM_STEM, 2.0 * B * (S / 2) * (S / 2) * 27 * C0, (double)B * S * S * 8 + (double)B * (S / 2) * (S / 2) * C0 * 2,
-         tw.stem0_wp ? fv::launch_stem_mfma(in, tw.stem0_wp, tw.stem0_b, h0, B, S, C0, s) : fv::launch_stem_conv(in, tw.stem0_w, tw.stem0_b, h0, B, S, C0, s));
-    FV_P(FV_FAM_DWCONV, dw_flops(B, H, H, C0, 3), (double)B * (S / 2) * (S / 2) * C0 * 2 * 1.25, fv::launch_dwconv(h0, tw.stem1_w, tw.stem1_b, h1, B, S / 2, S / 2, C0, 3, 2, 1, 1, s));
-    fv::GemmArgs g{h1, C0, tw.stem2_w, B * H * H, C0, C0, tw.stem2_b, nullptr, nullptr, 0, out, C0, FV_EPI_BIAS_GELU};
-    FV_TRY(gemm_p(h, g, s));
-    return FV_OK;
+    FV_TRY(stem_convs(h, in, a, b, B, s));
+    return stem_pw(h, b, out, B, s);
   }
-  const int H = u.H, C = u.C, M = B * H * H;
-  if (u.kind == TK_CPE) {
-    const Cpe& cp = tw.cpes[u.stage];
-    FV_P(FV_FAM_DWCONV, dw_flops(B, H, H, C, 7), 4.0 * M * C, dw_s1(h, in, cp.w, cp.t, cp.b, out, B, H, C, 7, s));
-    return FV_OK;
-  }
+  if (u.kind == TK_CPE) return dw_s1(h, in, tw.cpes[u.stage].w, tw.cpes[u.stage].t, tw.cpes[u.stage].b, out, B, H, C, 7, s);
   if (u.kind == TK_BLOCK) {
-    const Block& b = tw.stages[u.stage][u.j];
-    const int hid = C * d.tower_mlp_ratio;
-    if (!d.tower_is_attn[u.stage]) {
-      bf16_t* xp = c.at<bf16_t>(u.a);
-      bf16_t* t = c.at<bf16_t>(u.b);
-      if (b.mix_t && b.ffn.dw_t && fv::dwconv_pair_supported(B, H, H, C)) {
-        FV_P(FV_FAM_DWCONV, dw_flops(B, H, H, C, 3) + dw_flops(B, H, H, C, 7), 6.0 * M * C,
-             fv::launch_dwconv_pair(in, b.mix_t, b.mix_b, b.ffn.dw_t, b.ffn.dw_b, xp, t, B, H, H, C, s));
-      } else {
-        FV_P(FV_FAM_DWCONV, dw_flops(B, H, H, C, 3), 4.0 * M * C, dw_s1(h, in, b.mix_w, b.mix_t, b.mix_b, xp, B, H, C, 3, s));
-        FV_P(FV_FAM_DWCONV, dw_flops(B, H, H, C, 7), 4.0 * M * C, dw_s1(h, xp, b.ffn.dw_w, b.ffn.dw_t, b.ffn.dw_b, t, B, H, C, 7, s));
-      }
-      return ffn_forward(c, b.ffn, t, xp, out, M, C, hid, u.c ? c.at<bf16_t>(u.c) : nullptr);
+    const Block& blk = tw.stages[u.stage][u.j];
+    bf16_t* hb = c.at<bf16_t>(c.tp->hh);
+    const int M = B * H * H, hid = C * h->d.tower_mlp_ratio;
+    if (!h->d.tower_is_attn[u.stage]) {   // a = x', b = t, c = the ConvFFN's stash where the plan reserved one
+      FV_TRY(mixer_convs(h, blk, in, a, b, B, H, C, s));
+      return ffn_pointwise(h, blk.ffn, b, a, out, hb, nullptr, 0, u.c ? c.at<bf16_t>(u.c) : nullptr, M, C, hid, s);
     }
-    bf16_t* y = c.at<bf16_t>(u.a);
-    bf16_t* qkv = c.at<bf16_t>(u.b);
-    bf16_t* o = c.at<bf16_t>(u.c);
-    bf16_t* x1 = c.at<bf16_t>(u.d);
-    bf16_t* t = c.at<bf16_t>(u.e);
-    FV_P(FV_FAM_NORM, 8.0 * M * C, 4.0 * M * C, fv::launch_layernorm_rows(in, b.ln_w, b.ln_b, y, M, C, d.ln_eps, s));
-    fv::GemmArgs gq{y, C, b.qkv_w, M, 3 * C, C, nullptr, nullptr, nullptr, 0, qkv, 3 * C, FV_EPI_BIAS};
-    FV_TRY(gemm_p(h, gq, s));
-    const int nh = C / d.tower_head_dim;
-    FV_P(FV_FAM_ATTN, 4.0 * B * (double)(H * H) * (H * H) * C, 8.0 * M * C,
-         fv::launch_attention(qkv, qkv + C, qkv + 2 * C, 3 * C, 3 * C, 3 * C, o, C, B, H * H, nh, nh, d.tower_head_dim, 0, nullptr, 0, 1.0f / std::sqrt((float)d.tower_head_dim), s));
-    fv::GemmArgs gp{o, C, b.proj_w, M, C, C, b.proj_b, b.ls1, in, C, x1, C, FV_EPI_LS_RES};
-    FV_TRY(gemm_p(h, gp, s));
-    FV_P(FV_FAM_DWCONV, dw_flops(B, H, H, C, 7), 4.0 * M * C, dw_s1(h, x1, b.ffn.dw_w, b.ffn.dw_t, b.ffn.dw_b, t, B, H, C, 7, s));
-    return ffn_forward(c, b.ffn, t, x1, out, M, C, hid);
+    bf16_t *x1 = c.at<bf16_t>(u.d), *t = c.at<bf16_t>(u.e);   // a = y, b = qkv, c = o
+    FV_TRY(attn_mixer(h, blk, in, a, b, c.at<bf16_t>(u.c), x1, B, H, C, s));
+    FV_TRY(dw_s1(h, x1, blk.ffn.dw_w, blk.ffn.dw_t, blk.ffn.dw_b, t, B, H, C, 7, s));
+    return ffn_pointwise(h, blk.ffn, t, x1, out, hb, nullptr, 0, nullptr, M, C, hid, s);
   }
-  if (u.kind == TK_DOWN) {
-    const Down& dn = tw.downs[u.stage];
-    const int C2 = u.Co;
-    bf16_t* h1 = c.at<bf16_t>(u.a);
-    FV_P(FV_FAM_DWCONV, dw_flops(B, H / 2, H / 2, C2, 7), 2.0 * M * C + 2.0 * (M / 4) * C2,
-         dn.lk_t ? fv::launch_dwconv_s2_mfma(in, dn.lk_t, dn.lk_b, h1, B, H, H, C, 1, s) : fv::launch_dwconv(in, dn.lk_w, dn.lk_b, h1, B, H, H, C, 7, 2, C2 / C, 1, s));
-    fv::GemmArgs g{h1, C2, dn.pw_w, B * (H / 2) * (H / 2), C2, C2, dn.pw_b, nullptr, nullptr, 0, out, C2, FV_EPI_BIAS_GELU};
-    FV_TRY(gemm_p(h, g, s));
-    return FV_OK;
-  }
-  // conv_exp + SE + GELU -> tower_out (out_override is mandatory: the caller's buffer)
-  const int CO = u.Co, P = H * H;
-  bf16_t* e = c.at<bf16_t>(u.a);
-  FV_P(FV_FAM_DWCONV, dw_flops(B, H, H, CO, 3), 2.0 * B * P * (C + CO), fv::launch_dwconv(in, tw.exp_w, tw.exp_b, e, B, H, H, C, 3, 1, CO / C, 0, s));
-  FV_P(FV_FAM_ELT, 20.0 * B * P * CO, 6.0 * B * P * CO, fv::launch_se_gelu(e, tw.se_w1, tw.se_b1, tw.se_w2, tw.se_b2, out, c.at<float>(c.tp->se), B, P, CO, d.tower_se_rd, s));
-  return FV_OK;
+  if (u.kind == TK_DOWN) return patch_embed(h, tw.downs[u.stage], in, a, out, B, H, C, u.Co, s);
+  return tower_head(h, in, a, out, c.at<float>(c.tp->se), B, H, s);   // out_override is mandatory here: the caller's tower_out
 }
 
 // ---- backward helpers ----------------------------------------------------------------------------------------------------------------------
@@ -694,15 +613,13 @@ int fv_train_tower_begin(fv_handle* h) {
     op(5, t.off, 0, *dst, (int64_t)g.n, 0, 0, &g);
     return FV_OK;
   };
-  std::vector<UnitInfo> ui = tower_units(d);
+  const std::vector<UnitInfo> ui = tower_units(d, true);
   for (const TowerTensor& t : tl) {
     const int64_t n = (int64_t)t.rows * t.cols;
     TowerTrainUnit& tu = h->train.tunits[t.unit];
     if (t.lib_f32) op(0, t.off, 0, t.lib_f32, n, t.rows, t.cols, nullptr);
     if (t.lib_bf16) op(1, t.off, 0, t.lib_bf16, n, t.rows, t.cols, nullptr);
-    const bool head = t.unit == nu - 1;
-    const int kind = head ? TK_HEAD : (ui[t.unit].kind == 0 ? TK_STEM : ui[t.unit].kind == 1 ? TK_CPE : ui[t.unit].kind == 2 ? TK_BLOCK : TK_DOWN);
-    const int stage = head ? d.tower_stages - 1 : ui[t.unit].stage;
+    const int kind = ui[t.unit].kind, stage = ui[t.unit].stage;
     const bool attn = kind == TK_BLOCK && d.tower_is_attn[stage];
     GTab g;
     if (kind == TK_STEM) {
@@ -736,10 +653,7 @@ int fv_train_tower_begin(fv_handle* h) {
       }
       if (t.role == R_PWW) { tu.pwT16 = t16((size_t)n); op(3, t.off, 0, tu.pwT16, n, t.rows, t.cols, nullptr); }
     } else if (kind == TK_BLOCK) {
-      // which block is this?  (units of a stage are consecutive: j = unit - first block unit of the stage)
-      int first = 0;
-      for (int q = 0; q < t.unit; ++q) if (!(ui[q].kind == 2 && ui[q].stage == stage)) first = q + 1;
-      Block& b = tw.stages[stage][t.unit - first];
+      Block& b = tw.stages[stage][ui[t.unit].j];
       FFN& f = b.ffn;
       const int C = d.tower_dims[stage], hid = C * d.tower_mlp_ratio;
       if (!attn && t.role == R_MW && b.mix_t) { FV_TRY(toeplitz(C, 3, &g)); op(2, t.off, 0, b.mix_t, (int64_t)g.n, 0, 0, &g); }
