@@ -59,6 +59,13 @@ int fv_op_gemm_tn(const void* A, int lda, const void* W, int ldw, int M, int N, 
                   size_t ws_bytes, fv_stream s);
 int fv_op_gemm_splitk(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const void* res, int ldr,
                       void* out, int ldo, int epilogue, int ksplit, void* ws, size_t ws_bytes, fv_stream s);
+/* fv_op_gemm_splitk with the decoder's remaining launch settings: scale[N] (FV_EPI_LS_RES, also behind K ranges), few_rows (0 = never the few-row K-range
+ * forms: the training path) and an RMSNorm of the fp32 output rows (norm_w[N] non-NULL; fp32 epilogues, ldo == N): norm_y (+ norm_ylo, may be NULL) = bf16
+ * hi (+ lo) of norm_w * out * rsqrt(mean(out^2) + norm_eps), row stride norm_ld -- fused into the split-K reducer where K ranges are taken, a separate
+ * launch otherwise */
+int fv_op_gemm_norm(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const float* scale, const void* res, int ldr, void* out,
+                    int ldo, int epilogue, int ksplit, void* ws, size_t ws_bytes, int few_rows, const float* norm_w, void* norm_y, void* norm_ylo, int norm_ld,
+                    float norm_eps, fv_stream s);
 /* depthwise / channel-multiplier grouped conv, NHWC bf16: x (B,H,W,C) -> y (B,Ho,Wo,C*mult); w f32 [k*k][C*mult] */
 int fv_op_dwconv(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int k,
                  int stride, int mult, int gelu, fv_stream s);

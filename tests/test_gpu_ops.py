@@ -941,13 +941,18 @@ def test_gemm_few_rows_k_ranges(M):
 
 @pytest.mark.parametrize("M,N,K,ksplit,ws", [(8200, 896, 256, 0, False), (10240, 1152, 192, 1, False), (9728, 904, 128, 1, False),
                                               (896, 4864, 2048, 1, True), (900, 904, 4096, 0, True), (1152, 896, 2048, 1, True),
-                                              # 11 x 12 tiles, ragged on both edges: the grouped tile walk (groups of 4 tile rows) with a last group of 3
+                                              # 11 x 12 tiles, ragged on both edges.  pick_group_m wants a group height that divides the row-tile count and returns 0 for
+                                              # 11: both shapes are walked row-major (a grouped walk with ragged edges: tests/test_gpu_gemm.py, ragged-group4)
                                               (2660, 2920, 128, 0, False), (2660, 2920, 1024, 1, True)])
 def test_gemm_256_tile_ragged_edges_fp32_epilogues(M, N, K, ksplit, ws):
     """Round 4: fp32-epilogue problems whose M or N is not a multiple of 256 (the decoder's N = 896 / 1152 projections at a training
     batch, every dgrad / wgrad of the unfrozen path: M = 896, N = 4864 ...) on the 256-tile LDS-DMA kernel with ragged edge tiles --
     plain (>= 128 tiles) and cut along K (few tiles, long K, scratch given) -- F32 with bias and RES_F32 in place, against fp64.
-    Rows / columns past the edge must not be written (the outputs are embedded in NaN-guarded buffers)."""
+    Rows / columns past the edge must not be written (the outputs are embedded in NaN-guarded buffers).
+    What the scratch cases run on 256 CUs (tests/gemm_util.py gemm_route; tests/test_gemm_reference_host.py test_walks_and_asym pins it): (1152, 896, 2048) is the
+    ragged 256-tile split-K, 4 ranges; (900, 904, 4096) meets M % 256 != 0 && M <= 1024 first and runs as 5 K ranges of gemm_kernel<64>; (896, 4864, 2048) and
+    (2660, 2920, 1024) get no ranges at all -- two ranges of their partial sums do not fit the 32 MiB of scratch -- and run in one pass, on gemm_kernel<64> and on
+    the 256-tile kernel.  tests/test_gpu_gemm.py holds a case per route, each asserting the route it ran."""
     torch.manual_seed(M + N + K)
     Kt = (2 if ksplit else 1) * K
     A = bf(torch.randn(M, Kt) * (0.5 if not ksplit else 1.0))

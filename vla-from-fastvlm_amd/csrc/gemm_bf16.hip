@@ -922,7 +922,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_bf16_kernel(const float* __
 }
 
 // The few-row split-K of gate/up: part[s][m][16 j .. 16 j + 15] = 8 gate | 8 up sums of range s -> silu(gate) * up as hi | lo bf16 halves ([M][N/2 | N/2]),
-// exactly the FV_EPI_SWIGLU_SPLIT epilogue on the summed accumulators
+// the FV_EPI_SWIGLU_SPLIT epilogue on the summed accumulators (the same hi bit for bit; lo can differ from the in-kernel epilogue's in its last bits:
+// docs/kernels.md, "Dense GEMM", the open point; tests/test_gpu_gemm.py test_the_tail_against_the_one_pass_call_in_every_column)
 __global__ __launch_bounds__(256) void splitk_reduce_swiglu_kernel(const float* __restrict__ part, int splits, int M, int N, int npad, bf16_t* __restrict__ out, int ldo, int lo_off, const unsigned* skip = nullptr) {
   FV_SKIP_EXIT(skip);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;

@@ -26,6 +26,19 @@ int fv_op_gemm_splitk(const void* A, int lda, const void* W, int M, int N, int K
   g.splitk_bytes = ws_bytes;
   return fv::launch_gemm(g, static_cast<hipStream_t>(s));
 }
+// fv_op_gemm_splitk plus what the decoder sets on its launches: the layer scale (FV_EPI_LS_RES behind K ranges), GemmArgs::few_rows (0: the training path's
+// setting) and the RMSNorm that follows the fp32 output (fused into the split-K reducer where K ranges are taken, a separate launch otherwise)
+int fv_op_gemm_norm(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const float* scale, const void* res, int ldr, void* out,
+                    int ldo, int epilogue, int ksplit, void* ws, size_t ws_bytes, int few_rows, const float* norm_w, void* norm_y, void* norm_ylo, int norm_ld,
+                    float norm_eps, fv_stream s) {
+  fv::GemmArgs g{static_cast<const bf16_t*>(A), lda, static_cast<const bf16_t*>(W), M, N, K, bias, scale, res, ldr, out, ldo, epilogue};
+  g.ksplit = ksplit != 0;
+  g.splitk_ws = static_cast<float*>(ws);
+  g.splitk_bytes = ws_bytes;
+  g.few_rows = few_rows;
+  g.norm_w = norm_w; g.norm_y = static_cast<bf16_t*>(norm_y); g.norm_ylo = static_cast<bf16_t*>(norm_ylo); g.norm_ld = norm_ld; g.norm_eps = norm_eps;
+  return fv::launch_gemm(g, static_cast<hipStream_t>(s));
+}
 
 int fv_op_gemm_tn(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int f16, const float* bias, void* out, int ldo, void* ws,
                   size_t ws_bytes, fv_stream s) {
