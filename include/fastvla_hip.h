@@ -555,6 +555,75 @@ int fv_adamw_clip_step_groups(fv_handle* h, float* flat_params, const float* fla
 int fv_adamw_clip_step_ema(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, float* ema, float ema_weight, int64_t n,
                            const fv_adamw_hparams* hp, const fv_adamw_groups* groups, int64_t step, float* grad_norm_out, float* group_norms_out, fv_stream s);
 
+/* ---- the step guard: skip a step whose gradient is non-finite or was computed from saturated fp16 operands, and keep a dynamic loss scale, all on the
+ * device (what torch.cuda.amp.GradScaler does around an optimiser: skip, back off, grow again after a run of good steps).  The guard's state is one
+ * 64-byte device block:
+ *   delta_log2   the dynamic factor delta = 2^delta_log2 ON TOP of the static loss scale 2^k of fv_train_set_options.  A bound guard
+ *                (fv_train_set_step_guard) makes the training backward multiply dL/dactions by delta, so every gradient carries 2^k delta; the guarded step
+ *                divides delta out again on the device and the caller's grad_scale = 2^-k / world / accum stays what it is.
+ *   good_steps   applied steps since delta last changed
+ *   the counters applied, skipped_nonfinite, skipped_saturated, saturated_applied
+ *   the last decision (apply 0 / 1 and the 1 / delta that step used), the sticky saturation flag, the last value seen of the saturation counter.
+ * One guarded step: the sums of squares by the kernels of the plain steps, ONE decision launch of one block, then the GUARD instance of the step kernel:
+ *   bad_nonfinite = the sum of squares is not finite (a NaN / inf gradient element, or squares that overflow); a frozen group's gradient is never read
+ *   bad_sat       = skip_on_saturation && flag > 0 && delta_log2 > min_delta_log2
+ *   bad:  the step is SKIPPED -- p, m, v and ema keep their bits --, delta_log2 <- max(min, delta_log2 - backoff_log2), good_steps <- 0;
+ *         skipped_nonfinite (which wins when both hold) or skipped_saturated counts it
+ *   good: the step is applied with coef and the reported norms times 1 / delta (an exact power of two: the bits of the plain step over gradients that
+ *         never carried delta; delta = 1 gives fv_adamw_clip_step[_groups | _ema]'s bits); applied counts it, saturated_applied too when the flag was set
+ *         (a saturation at the floor, where halving cannot help, is applied as an unguarded run applies it); good_steps += 1, and at growth_interval
+ *         delta_log2 <- min(max, delta_log2 + growth_log2), good_steps <- 0
+ *   either way the flag is cleared, and grad_norm_out / group_norms_out are written (non-finite if that is what they are: the log shows why).
+ * `step`, which feeds the bias correction, stays the CALLER'S count and advances on a skipped step too, as a learning-rate schedule does: a rare skip
+ * shifts the bias correction by one step, and a run without skips needs no second code path.
+ * No float atomics, no host read, no allocation after create; two runs give the same bits; every call below that takes a stream is capturable. */
+typedef struct fv_step_guard fv_step_guard;
+typedef struct fv_step_guard_config {
+  int32_t init_delta_log2, min_delta_log2, max_delta_log2;
+  int32_t growth_interval;             /* >= 1; GradScaler's default is 2000 */
+  int32_t backoff_log2, growth_log2;   /* >= 0; 1 and 1 halve and double */
+  int32_t skip_on_saturation;          /* 0: a flagged step is applied (and counted in saturated_applied) */
+  int32_t reserved;                    /* must be 0 */
+} fv_step_guard_config;                /* 32 bytes */
+typedef struct fv_step_guard_state {
+  int32_t delta_log2, good_steps;
+  int32_t last_apply; float last_inv_delta;
+  float flag; uint32_t last_saturations;
+  int64_t applied, skipped_nonfinite, skipped_saturated, saturated_applied;
+} fv_step_guard_state;                 /* 56 bytes */
+/* A configuration call: allocates, uploads and synchronises.  FV_ERR_ARG for: min > max, init outside [min, max], growth_interval < 1, a negative
+ * backoff_log2 / growth_log2, reserved != 0, or a range that, added to the handle's current loss_scale_log2, leaves [0, 24] (fv_train_set_options' bounds).
+ * Head-only training is fp32 and has no loss scale: its guard is created with min = init = max = 0 and guards against non-finite gradients only.
+ * Destroy the guard before the handle (a guard still bound to the backward is unbound by its destruction). */
+int fv_step_guard_create(fv_handle* h, const fv_step_guard_config* cfg, fv_step_guard** out);
+int fv_step_guard_destroy(fv_handle* h, fv_step_guard* g);
+/* the state for a checkpoint / from one: status calls, both synchronise.  import: FV_ERR_ARG for a delta_log2 outside the guard's range or negative counts. */
+int fv_step_guard_export(fv_handle* h, fv_step_guard* g, fv_step_guard_state* out);
+int fv_step_guard_import(fv_handle* h, fv_step_guard* g, const fv_step_guard_state* in);
+/* ONE one-block launch, to be enqueued after a backward: if the handle's fp16 saturation counter (the one behind fv_llm_fp16_saturations) differs from the
+ * value seen last, the flag is set; the new value is remembered.  The flag is sticky across the micro-batches of a gradient-accumulation window until a
+ * guarded step consumes it. */
+int fv_step_guard_observe(fv_handle* h, fv_step_guard* g, fv_stream s);
+/* *flag_dev <- the device address of the flag, one float holding 0 or 1: data-parallel callers SUM it across ranks before the guarded step (any value > 0
+ * counts as set), so that every rank takes the same decision.  The non-finite check needs no exchange: a NaN or inf survives the gradient sum on every rank. */
+int fv_step_guard_flag(fv_handle* h, fv_step_guard* g, float** flag_dev);
+/* ONE one-block launch: out2_dev (2 floats, device) <- { 1 if the last guarded step was skipped, else 0; the delta the next backward runs with }: what a
+ * training loop logs per step without reading anything back. */
+int fv_step_guard_report(fv_handle* h, fv_step_guard* g, float* out2_dev, fv_stream s);
+/* the guarded form of all four steps: ema == NULL -> no average is kept (ema_weight ignored), groups == NULL -> the single-group step, otherwise the operands
+ * and their rules are fv_adamw_clip_step_ema's.  FV_ERR_ARG, launching nothing and leaving the guard's state untouched, for a null guard and for everything
+ * the unguarded entry points refuse. */
+int fv_adamw_clip_step_guarded(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, float* ema, float ema_weight, int64_t n,
+                               const fv_adamw_hparams* hp, const fv_adamw_groups* groups, int64_t step, fv_step_guard* guard, float* grad_norm_out,
+                               float* group_norms_out, fv_stream s);
+/* bind the guard to fv_train_forward_backward / fv_train_lora_forward_backward (NULL unbinds; a configuration call like fv_train_set_tower_grad): while bound,
+ * dL/dactions is multiplied by the guard's delta (one launch over its floats, read from the device) right after the loss launch, which still writes the
+ * static 2^k; everything downstream is linear in that buffer.  The tower's stream picks its own power-of-two scale per step towards a target of twice the loss
+ * scale; with a guard bound that target is 2^(k+1) delta, read on the device, so the stream follows the whole scale as it follows a static one, and it takes
+ * only its own scale out again: the tower's gradients carry 2^k delta like every other, with the bits of a run whose static scale is 2^k delta.  Without a bound guard nothing new is launched.  FV_ERR_ARG when the guard's range
+ * added to the current loss_scale_log2 leaves [0, 24]; fv_train_set_options refuses such a loss_scale_log2 while the guard is bound. */
+int fv_train_set_step_guard(fv_handle* h, fv_step_guard* guard);
+
 /* ---- temporal ensembling of action chunks (ACT's exponential weighting; LeRobot's ACTTemporalEnsembler, per environment).  Every control step the policy
  * predicts a chunk of K future steps; the action served for time t is the weighted mean of what the chunks predicted at t-K+1 .. t (those that exist since
  * the last reset) say about t:  sum_i w_i c_i[t] / sum_i w_i  with  w_i = exp(-coeff i), i = 0 the OLDEST prediction.  coeff: any finite float; 0 is

@@ -269,6 +269,10 @@ int fv_op_flow_select(const float* cand, int B, int S, int da, int select, const
                       const float* post_scale, const float* post_shift, float* actions, float* chunk_out, float* candidates_out, int32_t* choice_out,
                       float* scores_out, float* spread_out, fv_stream s);
 
+/* *flag_dev <- value (>= 0), stream-ordered: the step guard's sticky saturation flag (its address: fv_step_guard_flag in fastvla_hip.h) as saturating casts
+ * followed by fv_step_guard_observe would leave it, without having to provoke a saturation. */
+int fv_op_step_guard_set_flag(float* flag_dev, float value, fv_stream s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,6 +118,7 @@ struct TrainState {
   int grad_split = 2;   // dgrad's gradient operand: 2 ONE fp16 pass against fp16 transposed weights, 1 split bf16 (hi + lo, two passes) (fv_train_set_options)
   int wgrad_f16 = 1;    // 1: the weight gradients in ONE fp16 pass (both operands 11 significant bits, the gradient carrying the loss scale); 0: split-bf16 gradient x bf16 activation
   int loss_scale_log2 = 12;   // every gradient the backward produces is multiplied by 2^this (the optimiser's grad_scale takes it out again): fp16's range for the wgrad operands
+  fv_step_guard* guard = nullptr;   // fv_train_set_step_guard: the backward multiplies dL/dactions by the guard's device delta (null: nothing is launched)
 };
 struct DecLayer {
   float* ln1 = nullptr; bf16_t* qkv_w = nullptr; float* qkv_b = nullptr; bf16_t* o_w = nullptr; float* ln2 = nullptr; bf16_t *gu_w = nullptr, *down_w = nullptr;
@@ -1649,6 +1650,131 @@ int fv_adamw_clip_step_ema(fv_handle* h, float* flat_params, const float* flat_g
                                         ema_weight);
   if (group_norms_out) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_ema: group_norms_out needs a groups table");
   return fv::launch_adamw_clip(flat_params, flat_grads, m, v, n, *hp, step, h->norm_scratch, grad_norm_out, static_cast<hipStream_t>(s), ema, ema_weight);
+}
+
+// ---- the step guard (csrc/optim_kernels.hip): the object is its configuration on the host and ONE 64-byte block on the device
+struct fv_step_guard {
+  fv::GuardCfg cfg{};
+  fv::GuardWords* w = nullptr;   // device
+};
+static_assert(sizeof(fv::GuardWords) == 64, "the guard's device block");
+
+// the guard's range on top of a static loss scale 2^k must stay inside fv_train_set_options' own bounds
+static int guard_range_check(const char* who, const fv::GuardCfg& c, int k) {
+  if (c.min_log2 + k < 0 || c.max_log2 + k > 24)
+    return fv_fail(FV_ERR_ARG, "%s: delta_log2 in [%d, %d] on top of loss_scale_log2 = %d leaves [0, 24]", who, c.min_log2, c.max_log2, k);
+  return FV_OK;
+}
+
+int fv_step_guard_create(fv_handle* h, const fv_step_guard_config* cfg, fv_step_guard** out) {
+  HandleScope _hs(h);
+  if (!h || !cfg || !out) return fv_fail(FV_ERR_ARG, "fv_step_guard_create: null argument");
+  *out = nullptr;
+  if (cfg->reserved != 0) return fv_fail(FV_ERR_ARG, "fv_step_guard_create: reserved must be 0");
+  if (cfg->min_delta_log2 > cfg->max_delta_log2)
+    return fv_fail(FV_ERR_ARG, "fv_step_guard_create: min_delta_log2 = %d above max_delta_log2 = %d", cfg->min_delta_log2, cfg->max_delta_log2);
+  if (cfg->init_delta_log2 < cfg->min_delta_log2 || cfg->init_delta_log2 > cfg->max_delta_log2)
+    return fv_fail(FV_ERR_ARG, "fv_step_guard_create: init_delta_log2 = %d outside [%d, %d]", cfg->init_delta_log2, cfg->min_delta_log2, cfg->max_delta_log2);
+  if (cfg->growth_interval < 1) return fv_fail(FV_ERR_ARG, "fv_step_guard_create: growth_interval = %d must be >= 1", cfg->growth_interval);
+  if (cfg->backoff_log2 < 0 || cfg->growth_log2 < 0 || cfg->backoff_log2 > 48 || cfg->growth_log2 > 48)
+    return fv_fail(FV_ERR_ARG, "fv_step_guard_create: backoff_log2 = %d and growth_log2 = %d must be in [0, 48]", cfg->backoff_log2, cfg->growth_log2);
+  const fv::GuardCfg c{cfg->min_delta_log2, cfg->max_delta_log2, cfg->growth_interval, cfg->backoff_log2, cfg->growth_log2, cfg->skip_on_saturation != 0};
+  FV_TRY(guard_range_check("fv_step_guard_create", c, h->train.loss_scale_log2));
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  fv::GuardWords w{};
+  w.delta_log2 = cfg->init_delta_log2;
+  w.apply = 1;
+  w.inv_delta = std::ldexp(1.0f, -cfg->init_delta_log2);
+  w.delta = std::ldexp(1.0f, cfg->init_delta_log2);
+  FV_HIP_CHECK(hipMemcpy(&w.last_sat, h->f16_flags, 4, hipMemcpyDeviceToHost));   // what the counter holds now is not news
+  void* dev = nullptr;
+  FV_HIP_CHECK(hipMalloc(&dev, sizeof(fv::GuardWords)));
+  hipError_t e = hipMemcpy(dev, &w, sizeof(w), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(dev); return fv_hip_fail(e, "fv_step_guard_create: upload"); }
+  fv_step_guard* g = new (std::nothrow) fv_step_guard;
+  if (!g) { (void)hipFree(dev); return fv_fail(FV_ERR_STATE, "fv_step_guard_create: out of host memory"); }
+  g->cfg = c;
+  g->w = static_cast<fv::GuardWords*>(dev);
+  *out = g;
+  return FV_OK;
+}
+
+int fv_step_guard_destroy(fv_handle* h, fv_step_guard* g) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "fv_step_guard_destroy: null handle");
+  if (!g) return FV_OK;
+  if (h->train.guard == g) h->train.guard = nullptr;
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  const hipError_t e = hipFree(g->w);    // (waits for a step still in flight on the guard)
+  delete g;
+  if (e != hipSuccess) return fv_hip_fail(e, "fv_step_guard_destroy: hipFree");
+  return FV_OK;
+}
+
+int fv_step_guard_export(fv_handle* h, fv_step_guard* g, fv_step_guard_state* out) {
+  HandleScope _hs(h);
+  if (!h || !g || !out) return fv_fail(FV_ERR_ARG, "fv_step_guard_export: null argument");
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  fv::GuardWords w{};
+  FV_HIP_CHECK(hipMemcpy(&w, g->w, sizeof(w), hipMemcpyDeviceToHost));
+  *out = fv_step_guard_state{w.delta_log2, w.good_steps, w.apply, w.inv_delta, w.flag, w.last_sat, (int64_t)w.applied, (int64_t)w.skipped_nonfinite,
+                             (int64_t)w.skipped_saturated, (int64_t)w.saturated_applied};
+  return FV_OK;
+}
+
+int fv_step_guard_import(fv_handle* h, fv_step_guard* g, const fv_step_guard_state* in) {
+  HandleScope _hs(h);
+  if (!h || !g || !in) return fv_fail(FV_ERR_ARG, "fv_step_guard_import: null argument");
+  if (in->delta_log2 < g->cfg.min_log2 || in->delta_log2 > g->cfg.max_log2)
+    return fv_fail(FV_ERR_ARG, "fv_step_guard_import: delta_log2 = %d outside the guard's [%d, %d]", in->delta_log2, g->cfg.min_log2, g->cfg.max_log2);
+  if (in->good_steps < 0 || in->applied < 0 || in->skipped_nonfinite < 0 || in->skipped_saturated < 0 || in->saturated_applied < 0)
+    return fv_fail(FV_ERR_ARG, "fv_step_guard_import: negative count");
+  fv::GuardWords w{};
+  w.delta_log2 = in->delta_log2; w.good_steps = in->good_steps; w.apply = in->last_apply != 0; w.inv_delta = in->last_inv_delta;
+  w.flag = in->flag > 0.f ? in->flag : 0.f; w.last_sat = in->last_saturations; w.delta = std::ldexp(1.0f, in->delta_log2);
+  w.applied = (unsigned long long)in->applied; w.skipped_nonfinite = (unsigned long long)in->skipped_nonfinite;
+  w.skipped_saturated = (unsigned long long)in->skipped_saturated; w.saturated_applied = (unsigned long long)in->saturated_applied;
+  FV_HIP_CHECK(hipSetDevice(h->device));
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  FV_HIP_CHECK(hipMemcpy(g->w, &w, sizeof(w), hipMemcpyHostToDevice));
+  FV_HIP_CHECK(hipDeviceSynchronize());
+  return FV_OK;
+}
+
+int fv_step_guard_observe(fv_handle* h, fv_step_guard* g, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !g) return fv_fail(FV_ERR_ARG, "fv_step_guard_observe: null argument");
+  return fv::launch_guard_observe(g->w, h->f16_flags, static_cast<hipStream_t>(s));
+}
+
+int fv_step_guard_report(fv_handle* h, fv_step_guard* g, float* out2_dev, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !g || !out2_dev) return fv_fail(FV_ERR_ARG, "fv_step_guard_report: null argument");
+  return fv::launch_guard_report(g->w, out2_dev, static_cast<hipStream_t>(s));
+}
+
+int fv_step_guard_flag(fv_handle* h, fv_step_guard* g, float** flag_dev) {
+  HandleScope _hs(h);
+  if (!h || !g || !flag_dev) return fv_fail(FV_ERR_ARG, "fv_step_guard_flag: null argument");
+  *flag_dev = &g->w->flag;   // (an address only: nothing is read)
+  return FV_OK;
+}
+
+int fv_adamw_clip_step_guarded(fv_handle* h, float* flat_params, const float* flat_grads, float* m, float* v, float* ema, float ema_weight, int64_t n,
+                               const fv_adamw_hparams* hp, const fv_adamw_groups* groups, int64_t step, fv_step_guard* guard, float* grad_norm_out,
+                               float* group_norms_out, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !hp) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_guarded: null argument");
+  if (!guard) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_guarded: guard is null");
+  if (groups)
+    return fv::launch_adamw_clip_groups_guarded(flat_params, flat_grads, m, v, n, *hp, groups->t, step, grad_norm_out, group_norms_out, static_cast<hipStream_t>(s), ema,
+                                                ema_weight, guard->w, guard->cfg);
+  if (group_norms_out) return fv_fail(FV_ERR_ARG, "fv_adamw_clip_step_guarded: group_norms_out needs a groups table");
+  return fv::launch_adamw_clip_guarded(flat_params, flat_grads, m, v, n, *hp, step, h->norm_scratch, grad_norm_out, static_cast<hipStream_t>(s), ema, ema_weight,
+                                       guard->w, guard->cfg);
 }
 
 // ---- gradient accumulation helpers (training/trainer.py:96,171: accelerate's accumulate() sums micro-batch gradients)

@@ -344,7 +344,7 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
 
 int launch_head_backward(const HeadDims& d, const float* P, const float* grad_actions, const float* actions,
                          const float* targets, int B, float drop_p, const float* saved, float* loss, float* G,
-                         float* scratch, hipStream_t s, float* d_pooled, float loss_scale, const HeadLoss* hl) {
+                         float* scratch, hipStream_t s, float* d_pooled, float loss_scale, const HeadLoss* hl, const float* ga_scale_dev) {
   if (!P || !saved || !G || !scratch) return fv_fail(FV_ERR_ARG, "head_backward: null pointer");
   const bool weighted = hl && hl->dim_w && hl->step_w;   // fv_head_set_loss_weights: every kind takes the chunked kernel's weighted instance
   const bool prefix = d.te > 0 && d.pk > 0;   // fv_head_set_flow_prefix: the conditioned steps are masked out of the loss, so the fused loss is always the chunked kernel
@@ -390,6 +390,11 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   } else if (!ga) {
     hipLaunchKernelGGL(mse_kernel, dim3(1), blk, 0, s, actions, targets, loss, ga_own, B * d.da, loss_scale);
     ga = ga_own;
+  }
+  // the step guard's dynamic factor on top of loss_scale: dL/dactions *= *ga_scale_dev, a power of two read on the device (the gap up to g1 is scratch)
+  if (ga_scale_dev && ga == ga_own) {
+    const int rc = launch_axpy(ga_own, nullptr, (int64_t)(g1 - ga_own), ga_scale_dev, s);
+    if (rc != FV_OK) return rc;
   }
   // action_head
   hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(cdiv(d.fus, 256), d.da), blk, 0, s, ga, sv.a3, d.fus, G + ho.o[HP_ACT_W], B, d.da, d.fus);

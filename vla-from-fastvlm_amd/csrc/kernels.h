@@ -253,7 +253,8 @@ int launch_mul16(const bf16_t* a, const bf16_t* b, bf16_t* out, size_t n, unsign
 int launch_gelu_grad_mul(const bf16_t* dh, const bf16_t* pre, bf16_t* out, size_t n, unsigned* sat, hipStream_t s);   // out f16 = dh f16 * gelu'(pre bf16)
 int launch_f16_to_f32(const bf16_t* in, float* out, size_t n, float scale, hipStream_t s);
 int launch_scale_to_f16(const float* in, bf16_t* out, size_t n, float scale, unsigned* sat, hipStream_t s);   // out f16 = in * scale (saturating)
-int launch_rescale_to_f16(const float* in, bf16_t* out, size_t n, float target, unsigned* bits, float* sc, unsigned* sat, hipStream_t s);   // the tower's own gradient scale (device-chosen power of two)
+int launch_rescale_to_f16(const float* in, bf16_t* out, size_t n, float target, unsigned* bits, float* sc, unsigned* sat, hipStream_t s,
+                          const float* target_mul_dev = nullptr);   // the tower's own gradient scale (device-chosen power of two)
 int launch_unscale_dev(float* p, size_t n, const float* sc, hipStream_t s);
 int launch_ones_col(bf16_t* out, int ld, int C, long R, hipStream_t s);   // fp16 rows [R][ld]: columns [C, C + 8) <- {1, 0, ..., 0}
 int launch_ls_grads(const float* dWraw, const float* dbraw, const bf16_t* W, const float* bias, const float* ls, float* dW, float* db, float* dls, int C, int Kd,
@@ -340,7 +341,8 @@ struct HeadLoss { int kind; float beta; int chunk; const uint8_t* pad; float* me
 int launch_head_backward(const HeadDims& d, const float* P, const float* grad_actions, const float* actions,
                          const float* targets, int B, float drop_p, const float* saved, float* loss, float* G,
                          float* scratch, hipStream_t s, float* d_pooled = nullptr, float loss_scale = 1.0f,    // loss_scale: the fused loss's dL/dactions times a power of two
-                         const struct HeadLoss* hl = nullptr);
+                         const struct HeadLoss* hl = nullptr,
+                         const float* ga_scale_dev = nullptr);   // the step guard's dynamic factor (fv_train_set_step_guard): the fused loss's dL/dactions times *ga_scale_dev, one axpy launch
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
 // ---- flow-matching head (d.te > 0).  freq: te / 2 device floats, 2 pi / period_j.  time_dist 0: t ~ U[0, 1); 1: t = sigmoid(dist_a + dist_b n)
 // thr (prefix mode): pd + 1 device uint32, the cumulative delay distribution in units of 2^-24 (the last one is 2^24)
@@ -432,5 +434,21 @@ struct AdamwGroupsTable {
 };
 int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
                              int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema = nullptr, float ema_weight = 0.f);
+
+// the step guard (fv_step_guard, optim_kernels.hip): its whole state is this one device block.  delta = 2^delta_log2 is what the training backward multiplies
+// dL/dactions by (launch_head_backward's ga_scale_dev points at it); apply / inv_delta are the last decision, read by every block of the GUARD step kernels
+struct GuardWords {
+  int32_t delta_log2, good_steps, apply; float inv_delta;   // inv_delta: 2^-delta_log2 of the step the decision was made for
+  float flag; uint32_t last_sat; float delta; int32_t pad;  // flag: sticky, > 0 when the saturation counter moved since the last guarded step
+  unsigned long long applied, skipped_nonfinite, skipped_saturated, saturated_applied;
+};                                                          // 64 bytes
+struct GuardCfg { int32_t min_log2, max_log2, growth_interval, backoff_log2, growth_log2, skip_on_saturation; };
+int launch_guard_observe(GuardWords* w, const unsigned* sat_counter, hipStream_t s);
+int launch_guard_report(const GuardWords* w, float* out2, hipStream_t s);   // out2 <- { 1 - apply of the last decision, delta of the next backward }
+// guard != null versions of the two steps: sums of squares by the same kernels, ONE decision launch (one block), then the GUARD instance of the step kernel
+int launch_adamw_clip_guarded(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, int64_t step, float* norm_scratch,
+                              float* grad_norm_out, hipStream_t s, float* ema, float ema_weight, GuardWords* guard, const GuardCfg& cfg);
+int launch_adamw_clip_groups_guarded(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t, int64_t step,
+                                     float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema, float ema_weight, GuardWords* guard, const GuardCfg& cfg);
 
 }  // namespace fv

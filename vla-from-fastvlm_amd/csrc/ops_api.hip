@@ -419,3 +419,14 @@ int fv_op_flow_select(const float* cand, int B, int S, int da, int select, const
 }
 
 }  // extern "C"
+
+// the step guard's saturation flag, set as a run of saturating casts would leave it (fv_step_guard_flag hands out the address): one float, stream-ordered
+namespace {
+__global__ void set_float_kernel(float* dst, float value) { *dst = value; }
+}  // namespace
+extern "C" int fv_op_step_guard_set_flag(float* flag_dev, float value, fv_stream s) {
+  if (!flag_dev || !(value >= 0.f)) return fv_fail(FV_ERR_ARG, "fv_op_step_guard_set_flag: a flag address and a value >= 0");
+  hipLaunchKernelGGL(set_float_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(s), flag_dev, value);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}

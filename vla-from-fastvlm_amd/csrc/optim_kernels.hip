@@ -10,6 +10,9 @@
 // 4 floats -- so every access below is a 16-byte one, a block reads its group's settings once (no per-element search) and a frozen segment's block leaves
 // before it has touched p, g, m or v.  Both kernels over the data move what adamw_kernel / sumsq_kernel move: 4 + 28 bytes per element (4 + 36 in the EMA
 // instance of the step, fv_adamw_clip_step_ema, which keeps the average e of p in the same pass).
+//   STEP GUARD (fv_step_guard, fv_adamw_clip_step_guarded): between the norm and the step ONE one-block decision launch -- non-finite norm, or a saturation flag
+//   above the floor of the dynamic loss scale: skip, back the scale off; otherwise apply, grow it after growth_interval good steps -- and the GUARD instances of
+//   both step kernels, which read that decision once per block: an early return on a skip, coef and the reported norms times 1 / delta (a power of two) otherwise.
 // Summation order is fixed (per-thread strided sums, wave butterfly, four wave sums added pairwise): no float atomics, two runs give the same bits.
 #include "kernels.h"
 
@@ -49,18 +52,24 @@ __global__ __launch_bounds__(256) void sumsq_fold_kernel(float* __restrict__ par
 
 // EMA instance (fv_adamw_clip_step_ema): also e <- ema_update(e, p_new, ema_w) while p_new is in its register, 8 more bytes per element.  The plain instance
 // never looks at e / ema_w: it is the kernel as it was.
-template <bool EMA>
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                     float* __restrict__ m, float* __restrict__ v, long n,
-                                                     fv_adamw_hparams hp, float bc1, float bc2_sqrt,
-                                                     const float* __restrict__ sumsq, float* __restrict__ norm_out,
-                                                     float* __restrict__ e, float ema_w) {
+// GUARD instances (fv_adamw_clip_step_guarded): every block reads the decision step_guard_decide_kernel left in the guard's block -- one scalar load, nothing per
+// element.  Skip: the norm is still reported, then the block leaves before it touches p, m, v or e.  Apply: coef and the reported norms times the decision's
+// 1 / delta, an exact power of two, so the step has the bits of the plain step over gradients that never carried delta.  The plain instances never look at `gd`.
+template <bool EMA, bool GUARD>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g,
+                                           float* __restrict__ m, float* __restrict__ v, long n,
+                                           const fv_adamw_hparams& hp, float bc1, float bc2_sqrt,
+                                           const float* __restrict__ sumsq, float* __restrict__ norm_out,
+                                           float* __restrict__ e, float ema_w, const GuardWords* __restrict__ gd) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   // torch clip_grad_norm_: coef = clamp(max_norm / (norm + 1e-6), max = 1)
-  const float norm = sqrtf(*sumsq) * hp.grad_scale;
+  float norm = sqrtf(*sumsq) * hp.grad_scale;
+  if constexpr (GUARD) norm *= gd->inv_delta;
   float coef = hp.grad_scale;
   if (hp.max_grad_norm > 0.f) coef *= fminf(hp.max_grad_norm / (norm + 1e-6f), 1.0f);
+  if constexpr (GUARD) coef *= gd->inv_delta;
   if (i == 0 && norm_out) *norm_out = norm;
+  if constexpr (GUARD) { if (!gd->apply) return; }    // (uniform over the grid)
   if (i >= n) return;
   float pi = p[i], mi = m[i], vi = v[i];
   adamw_update(pi, g[i], mi, vi, coef, hp.lr, hp.weight_decay, hp.beta1, hp.beta2, hp.eps, bc1, bc2_sqrt);   // (shared with adamw_groups_kernel: common.h)
@@ -68,6 +77,22 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
   m[i] = mi;
   v[i] = vi;
   if constexpr (EMA) e[i] = ema_update(e[i], pi, ema_w);
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                     float* __restrict__ m, float* __restrict__ v, long n,
+                                                     fv_adamw_hparams hp, float bc1, float bc2_sqrt,
+                                                     const float* __restrict__ sumsq, float* __restrict__ norm_out,
+                                                     float* __restrict__ e, float ema_w) {
+  adamw_body<EMA, false>(p, g, m, v, n, hp, bc1, bc2_sqrt, sumsq, norm_out, e, ema_w, nullptr);
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_guard_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v, long n,
+                                                           fv_adamw_hparams hp, float bc1, float bc2_sqrt,
+                                                           const float* __restrict__ sumsq, float* __restrict__ norm_out,
+                                                           float* __restrict__ e, float ema_w, const GuardWords* __restrict__ gd) {
+  adamw_body<EMA, true>(p, g, m, v, n, hp, bc1, bc2_sqrt, sumsq, norm_out, e, ema_w, gd);
 }
 
 // y += x (x != null) or y *= *scale (x == null): gradient accumulation over micro-batches / an upstream loss gradient
@@ -133,21 +158,29 @@ __global__ __launch_bounds__(256) void sumsq_groups_fold_kernel(const AdamwGroup
 
 // EMA instance (fv_adamw_clip_step_ema): e, read and written with the same 16-byte accesses, <- ema_update(e, p_new, ema_w) per lane: 4 + 36 bytes per element
 // with the norm pass.  A frozen segment's block has left before it touches e.  The plain instance never looks at e / ema_w: it is the kernel as it was.
-template <bool EMA>
-__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                            fv_adamw_hparams hp, float bc1, float bc2_sqrt, const AdamwSeg* __restrict__ segs,
-                                                            const AdamwGroupDev* __restrict__ groups, const float* __restrict__ group_sum, int n_groups,
-                                                            float* __restrict__ norm_out, float* __restrict__ group_norms_out, float* __restrict__ e, float ema_w) {
+template <bool EMA, bool GUARD>
+__device__ __forceinline__ void adamw_groups_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                  const fv_adamw_hparams& hp, float bc1, float bc2_sqrt, const AdamwSeg* __restrict__ segs,
+                                                  const AdamwGroupDev* __restrict__ groups, const float* __restrict__ group_sum, int n_groups,
+                                                  float* __restrict__ norm_out, float* __restrict__ group_norms_out, float* __restrict__ e, float ema_w,
+                                                  const GuardWords* __restrict__ gd) {
   const AdamwSeg sg = segs[blockIdx.x];
   const AdamwGroupDev gr = groups[sg.group];
   // torch clip_grad_norm_ over the non-frozen elements: coef = clamp(max_norm / (norm + 1e-6), max = 1), as adamw_kernel
-  const float norm = sqrtf(group_sum[n_groups]) * hp.grad_scale;
+  float norm = sqrtf(group_sum[n_groups]) * hp.grad_scale;
+  if constexpr (GUARD) norm *= gd->inv_delta;
   float coef = hp.grad_scale;
   if (hp.max_grad_norm > 0.f) coef *= fminf(hp.max_grad_norm / (norm + 1e-6f), 1.0f);
+  if constexpr (GUARD) coef *= gd->inv_delta;
   if (threadIdx.x == 0) {
     if (blockIdx.x == 0 && norm_out) *norm_out = norm;
-    if (group_norms_out && (int)blockIdx.x == gr.seg_begin) group_norms_out[sg.group] = gr.frozen ? 0.f : sqrtf(group_sum[sg.group]) * hp.grad_scale;
+    if (group_norms_out && (int)blockIdx.x == gr.seg_begin) {
+      float gn = gr.frozen ? 0.f : sqrtf(group_sum[sg.group]) * hp.grad_scale;
+      if constexpr (GUARD) gn *= gd->inv_delta;
+      group_norms_out[sg.group] = gn;
+    }
   }
+  if constexpr (GUARD) { if (!gd->apply) return; }    // (uniform over the grid)
   if (gr.frozen) return;     // p, m, v (and e) keep their bits
   const float lr = hp.lr * gr.lr_scale;
   float4* p4 = reinterpret_cast<float4*>(p + sg.begin);
@@ -170,6 +203,60 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
       e4[i] = ei;
     }
   }
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                            fv_adamw_hparams hp, float bc1, float bc2_sqrt, const AdamwSeg* __restrict__ segs,
+                                                            const AdamwGroupDev* __restrict__ groups, const float* __restrict__ group_sum, int n_groups,
+                                                            float* __restrict__ norm_out, float* __restrict__ group_norms_out, float* __restrict__ e, float ema_w) {
+  adamw_groups_body<EMA, false>(p, g, m, v, hp, bc1, bc2_sqrt, segs, groups, group_sum, n_groups, norm_out, group_norms_out, e, ema_w, nullptr);
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_groups_guard_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                                  fv_adamw_hparams hp, float bc1, float bc2_sqrt, const AdamwSeg* __restrict__ segs,
+                                                                  const AdamwGroupDev* __restrict__ groups, const float* __restrict__ group_sum, int n_groups,
+                                                                  float* __restrict__ norm_out, float* __restrict__ group_norms_out, float* __restrict__ e, float ema_w,
+                                                                  const GuardWords* __restrict__ gd) {
+  adamw_groups_body<EMA, true>(p, g, m, v, hp, bc1, bc2_sqrt, segs, groups, group_sum, n_groups, norm_out, group_norms_out, e, ema_w, gd);
+}
+
+// ---- the step guard (fv_step_guard): two one-block kernels over the guard's own 64-byte block
+// observe: the handle's fp16 saturation counter against the value seen last; a change sets the sticky flag (the guarded step clears it)
+__global__ void step_guard_observe_kernel(GuardWords* __restrict__ w, const unsigned* __restrict__ sat) {
+  if (threadIdx.x != 0) return;
+  const unsigned c = *sat;
+  if (c != w->last_sat) {
+    w->last_sat = c;
+    if (!(w->flag > 0.f)) w->flag = 1.0f;
+  }
+}
+__global__ void step_guard_report_kernel(const GuardWords* __restrict__ w, float* __restrict__ out) {
+  if (threadIdx.x == 0) { out[0] = w->apply ? 0.f : 1.f; out[1] = w->delta; }
+}
+// decide: the decision of THIS step (apply, 1 / delta) from the sum of squares and the flag, then the state the next forward runs with.  Integers only beyond
+// isfinite; tests/step_guard_util.py is the same machine on the host
+__global__ void step_guard_decide_kernel(GuardWords* __restrict__ w, const float* __restrict__ sumsq, GuardCfg cfg) {
+  if (threadIdx.x != 0) return;
+  int dl = w->delta_log2, good = w->good_steps;
+  const bool flagged = w->flag > 0.f;
+  const bool bad_nonfinite = !isfinite(*sumsq);
+  const bool bad_sat = cfg.skip_on_saturation && flagged && dl > cfg.min_log2;
+  w->apply = (bad_nonfinite || bad_sat) ? 0 : 1;
+  w->inv_delta = ldexpf(1.0f, -dl);
+  if (bad_nonfinite || bad_sat) {
+    if (bad_nonfinite) w->skipped_nonfinite += 1; else w->skipped_saturated += 1;
+    dl = max(cfg.min_log2, dl - cfg.backoff_log2);
+    good = 0;
+  } else {
+    w->applied += 1;
+    if (flagged) w->saturated_applied += 1;
+    good += 1;
+    if (good >= cfg.growth_interval) { dl = min(cfg.max_log2, dl + cfg.growth_log2); good = 0; }
+  }
+  w->flag = 0.f;
+  w->delta_log2 = dl;
+  w->good_steps = good;
+  w->delta = ldexpf(1.0f, dl);
 }
 
 }  // namespace
@@ -195,8 +282,8 @@ int launch_axpy(float* y, const float* x, int64_t n, const float* scale_dev, hip
   return FV_OK;
 }
 
-int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,
-                      int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s, float* ema, float ema_weight) {
+static int adamw_clip_impl(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,
+                           int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s, float* ema, float ema_weight, GuardWords* guard, const GuardCfg* cfg) {
   if (!p || !g || !m || !v || !norm_scratch) return fv_fail(FV_ERR_ARG, "adamw: null pointer");
   if (n <= 0 || step < 1) return fv_fail(FV_ERR_ARG, "adamw: n and step must be positive");
   if (ema) { const int rc = check_adamw_ema("adamw", p, g, m, v, ema, ema_weight, n); if (rc != FV_OK) return rc; }
@@ -207,16 +294,46 @@ int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, c
   hipLaunchKernelGGL(sumsq_fold_kernel, dim3(1), dim3(256), 0, s, norm_scratch, (int)nsb);
   const float bc1 = (float)(1.0 - pow((double)hp.beta1, (double)step));
   const float bc2 = (float)sqrt(1.0 - pow((double)hp.beta2, (double)step));
-  if (ema && ema_weight != 0.f)   // (weight 0 leaves the average alone: the plain instance, which never reads it)
+  if (guard) {
+    hipLaunchKernelGGL(step_guard_decide_kernel, dim3(1), dim3(64), 0, s, guard, (const float*)norm_scratch, *cfg);
+    if (ema && ema_weight != 0.f)
+      hipLaunchKernelGGL(adamw_guard_kernel<true>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, ema, ema_weight,
+                         (const GuardWords*)guard);
+    else
+      hipLaunchKernelGGL(adamw_guard_kernel<false>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, (float*)nullptr, 0.f,
+                         (const GuardWords*)guard);
+  } else if (ema && ema_weight != 0.f)   // (weight 0 leaves the average alone: the plain instance, which never reads it)
     hipLaunchKernelGGL(adamw_kernel<true>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, ema, ema_weight);
   else
     hipLaunchKernelGGL(adamw_kernel<false>, dim3(nb), dim3(256), 0, s, p, g, m, v, (long)n, hp, bc1, bc2, (const float*)norm_scratch, grad_norm_out, (float*)nullptr, 0.f);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
 }
+int launch_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp,
+                      int64_t step, float* norm_scratch, float* grad_norm_out, hipStream_t s, float* ema, float ema_weight) {
+  return adamw_clip_impl(p, g, m, v, n, hp, step, norm_scratch, grad_norm_out, s, ema, ema_weight, nullptr, nullptr);
+}
+int launch_adamw_clip_guarded(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, int64_t step, float* norm_scratch,
+                              float* grad_norm_out, hipStream_t s, float* ema, float ema_weight, GuardWords* guard, const GuardCfg& cfg) {
+  if (!guard) return fv_fail(FV_ERR_ARG, "adamw: null guard");
+  return adamw_clip_impl(p, g, m, v, n, hp, step, norm_scratch, grad_norm_out, s, ema, ema_weight, guard, &cfg);
+}
+int launch_guard_report(const GuardWords* w, float* out2, hipStream_t s) {
+  if (!w || !out2) return fv_fail(FV_ERR_ARG, "step guard report: null pointer");
+  hipLaunchKernelGGL(step_guard_report_kernel, dim3(1), dim3(64), 0, s, w, out2);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
+int launch_guard_observe(GuardWords* w, const unsigned* sat_counter, hipStream_t s) {
+  if (!w || !sat_counter) return fv_fail(FV_ERR_ARG, "step guard observe: null pointer");
+  hipLaunchKernelGGL(step_guard_observe_kernel, dim3(1), dim3(64), 0, s, w, sat_counter);
+  FV_HIP_CHECK(hipGetLastError());
+  return FV_OK;
+}
 
-int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
-                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema, float ema_weight) {
+static int adamw_clip_groups_impl(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
+                                  int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema, float ema_weight, GuardWords* guard,
+                                  const GuardCfg* cfg) {
   if (!p || !g || !m || !v || !t.segs || !t.groups || !t.sums) return fv_fail(FV_ERR_ARG, "adamw groups: null pointer");
   if (step < 1) return fv_fail(FV_ERR_ARG, "adamw groups: step must be positive");
   if (n != t.n) return fv_fail(FV_ERR_ARG, "adamw groups: n = %lld, the table was built for %lld", (long long)n, (long long)t.n);
@@ -233,7 +350,15 @@ int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64
   hipLaunchKernelGGL(sumsq_groups_fold_kernel, dim3(1), dim3(256), 0, s, t.groups, t.n_groups, (const float*)t.sums, group_sum, 1);
   const float bc1 = (float)(1.0 - pow((double)hp.beta1, (double)step));
   const float bc2 = (float)sqrt(1.0 - pow((double)hp.beta2, (double)step));
-  if (ema && ema_weight != 0.f)   // (weight 0 leaves the average alone: the plain instance, which never reads it)
+  if (guard) {
+    hipLaunchKernelGGL(step_guard_decide_kernel, dim3(1), dim3(64), 0, s, guard, (const float*)(group_sum + t.n_groups), *cfg);
+    if (ema && ema_weight != 0.f)
+      hipLaunchKernelGGL(adamw_groups_guard_kernel<true>, dim3(t.n_segs), dim3(256), 0, s, p, g, m, v, hp, bc1, bc2, t.segs, t.groups, (const float*)group_sum, t.n_groups,
+                         grad_norm_out, group_norms_out, ema, ema_weight, (const GuardWords*)guard);
+    else
+      hipLaunchKernelGGL(adamw_groups_guard_kernel<false>, dim3(t.n_segs), dim3(256), 0, s, p, g, m, v, hp, bc1, bc2, t.segs, t.groups, (const float*)group_sum, t.n_groups,
+                         grad_norm_out, group_norms_out, (float*)nullptr, 0.f, (const GuardWords*)guard);
+  } else if (ema && ema_weight != 0.f)   // (weight 0 leaves the average alone: the plain instance, which never reads it)
     hipLaunchKernelGGL(adamw_groups_kernel<true>, dim3(t.n_segs), dim3(256), 0, s, p, g, m, v, hp, bc1, bc2, t.segs, t.groups, (const float*)group_sum, t.n_groups,
                        grad_norm_out, group_norms_out, ema, ema_weight);
   else
@@ -241,6 +366,15 @@ int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64
                        grad_norm_out, group_norms_out, (float*)nullptr, 0.f);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
+}
+int launch_adamw_clip_groups(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t,
+                             int64_t step, float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema, float ema_weight) {
+  return adamw_clip_groups_impl(p, g, m, v, n, hp, t, step, grad_norm_out, group_norms_out, s, ema, ema_weight, nullptr, nullptr);
+}
+int launch_adamw_clip_groups_guarded(float* p, const float* g, float* m, float* v, int64_t n, const fv_adamw_hparams& hp, const AdamwGroupsTable& t, int64_t step,
+                                     float* grad_norm_out, float* group_norms_out, hipStream_t s, float* ema, float ema_weight, GuardWords* guard, const GuardCfg& cfg) {
+  if (!guard) return fv_fail(FV_ERR_ARG, "adamw groups: null guard");
+  return adamw_clip_groups_impl(p, g, m, v, n, hp, t, step, grad_norm_out, group_norms_out, s, ema, ema_weight, guard, &cfg);
 }
 
 }  // namespace fv

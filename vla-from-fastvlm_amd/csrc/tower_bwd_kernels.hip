@@ -676,7 +676,10 @@ __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ in,
   if ((threadIdx.x & 63) == 0 && m > 0.f && m <= 3.0e38f) atomicMax(bits, __float_as_uint(m));
 }
 // sc[0] = 2^k, sc[1] = 2^-k with k = clamp(floor(log2(target / amax)), 0, 24); bits is cleared for the next step
-__global__ void pick_scale_kernel(unsigned* __restrict__ bits, float* __restrict__ sc, float target) {
+// target_mul (device, may be null): a power of two the target is multiplied by -- the step guard's delta, so that the stream follows the WHOLE loss scale
+// 2^k delta as it follows fv_train_set_options' static one
+__global__ void pick_scale_kernel(unsigned* __restrict__ bits, float* __restrict__ sc, float target, const float* __restrict__ target_mul) {
+  if (target_mul) target *= *target_mul;
   const float amax = __uint_as_float(*bits);
   int k = 0;
   if (amax > 0.f) {
@@ -1477,11 +1480,11 @@ int launch_scale_to_f16(const float* in, bf16_t* out, size_t n, float scale, uns
   return FV_OK;
 }
 // out f16 = in * 2^k with 2^k picked on the device so that max |in| 2^k ~ target (sc[0] = 2^k, sc[1] = 2^-k; bits: a zeroed device word of scratch)
-int launch_rescale_to_f16(const float* in, bf16_t* out, size_t n, float target, unsigned* bits, float* sc, unsigned* sat, hipStream_t s) {
+int launch_rescale_to_f16(const float* in, bf16_t* out, size_t n, float target, unsigned* bits, float* sc, unsigned* sat, hipStream_t s, const float* target_mul_dev) {
   if (!in || !out || !bits || !sc || n % 8) return fv_fail(FV_ERR_ARG, "rescale_to_f16: bad argument");
   const long n4 = (long)(n / 4);
   hipLaunchKernelGGL(amax_kernel, dim3((unsigned)(n4 / 256 + 1 < 2048 ? n4 / 256 + 1 : 2048)), dim3(256), 0, s, in, n4, bits);
-  hipLaunchKernelGGL(pick_scale_kernel, dim3(1), dim3(1), 0, s, bits, sc, target);
+  hipLaunchKernelGGL(pick_scale_kernel, dim3(1), dim3(1), 0, s, bits, sc, target, target_mul_dev);
   hipLaunchKernelGGL(scale_to_f16_dev_kernel, dim3(grid1((long)(n / 8))), dim3(256), 0, s, in, out, (long)(n / 8), sc, sat);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;

@@ -526,6 +526,7 @@ int fv_train_set_options(fv_handle* h, int grad_split, int wgrad_f16, int loss_s
   // gradients, 1 ms slower -- are gone from the product; the TN instance itself serves the tower's weight gradients, tower_train.inc)
   if (grad_split < 1 || grad_split > 2 || wgrad_f16 < 0 || wgrad_f16 > 1 || loss_scale_log2 < 0 || loss_scale_log2 > 24)
     return fv_fail(FV_ERR_ARG, "fv_train_set_options: grad_split in {1, 2}, wgrad_f16 in {0, 1}, loss_scale_log2 in [0, 24]");
+  if (h->train.guard) FV_TRY(guard_range_check("fv_train_set_options", h->train.guard->cfg, loss_scale_log2));   // (a bound step guard moves the scale inside its range)
   FV_TRY(prompt_invalidate(h, nullptr, false));
   if (h->train.ready && ((grad_split == 2) != (h->train.grad_split == 2))) {
     // the transposed weight copies of the OTHER form may be stale (fv_train_commit refreshes the active form only): rebuild them from the library's weights
@@ -541,6 +542,13 @@ int fv_train_set_options(fv_handle* h, int grad_split, int wgrad_f16, int loss_s
   h->train.grad_split = grad_split;
   h->train.wgrad_f16 = wgrad_f16 != 0;
   h->train.loss_scale_log2 = loss_scale_log2;
+  return FV_OK;
+}
+int fv_train_set_step_guard(fv_handle* h, fv_step_guard* guard) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  if (guard) FV_TRY(guard_range_check("fv_train_set_step_guard", guard->cfg, h->train.loss_scale_log2));
+  h->train.guard = guard;
   return FV_OK;
 }
 int fv_train_loss_scale(fv_handle* h, float* scale_out) {
@@ -680,7 +688,7 @@ static int train_forward_backward_impl(fv_handle* h, const float* flat_params, c
   // ------------------------------------------------------------------------------------------------ backward
   float *dpooled = c.at<float>(tp.dpooled), *xg = c.at<float>(tp.xg), *dxg = c.at<float>(tp.dxg);
   FV_P(FV_FAM_HEAD, 0.0, 0.0, fv::launch_head_backward(h->hd, flat_params, nullptr, head_actions, head_targets, B, dropout_p, head_saved, loss, gbuf, c.at<float>(tp.head_scr), s, dpooled,
-                                                      std::ldexp(1.0f, h->train.loss_scale_log2), &h->loss));
+                                                      std::ldexp(1.0f, h->train.loss_scale_log2), &h->loss, h->train.guard ? &h->train.guard->w->delta : nullptr));
   c.bucket_done(TB_HEAD);
   // final norm on the pooled rows; the residual-gradient stream starts as zero everywhere else
   FV_TRY(fv::launch_pool_rows(c.X_in(L), xg, lens, B, Tt, Ni, H, 0, s));
@@ -733,7 +741,8 @@ static int train_forward_backward_impl(fv_handle* h, const float* flat_params, c
       g.f16 = 1;
       FV_TRY(gemm_p(h, g, s));
       FV_P(FV_FAM_ELT, 0.0, (double)RI * CO * 10, fv::launch_rescale_to_f16(dtmp, static_cast<bf16_t*>(h->train.d_tower_out), (size_t)RI * CO, std::ldexp(2.0f, h->train.loss_scale_log2),
-                                                                              reinterpret_cast<unsigned*>(h->train.tscale + 2), h->train.tscale, h->f16_flags, s));
+                                                                              reinterpret_cast<unsigned*>(h->train.tscale + 2), h->train.tscale, h->f16_flags, s,
+                                                                              h->train.guard ? &h->train.guard->w->delta : nullptr));   // (a bound step guard: the target follows 2^k delta)
     }
   }
   return FV_OK;

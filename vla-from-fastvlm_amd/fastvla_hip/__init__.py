@@ -5,5 +5,6 @@ from ._lib import FastVLAHipError, library_path, load  # noqa: F401
 from .arch import LLMConfig, ModelConfig, TowerConfig, PRESETS, preset  # noqa: F401
 from .engine import HEAD_KEYS, FastVLAEngine  # noqa: F401
 from .ensemble import TemporalEnsembler  # noqa: F401
+from .guard import StepGuard  # noqa: F401
 from .rtc import RealTimeChunker, prefix_weights  # noqa: F401
 from . import weights  # noqa: F401

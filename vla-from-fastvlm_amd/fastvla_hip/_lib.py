@@ -62,6 +62,17 @@ class AdamWGroup(C.Structure):      # fv_adamw_group: 32 bytes
 FV_ADAMW_SEGMENT = 8192
 
 
+class StepGuardConfig(C.Structure):     # fv_step_guard_config: 32 bytes
+    _fields_ = [("init_delta_log2", C.c_int32), ("min_delta_log2", C.c_int32), ("max_delta_log2", C.c_int32), ("growth_interval", C.c_int32),
+                ("backoff_log2", C.c_int32), ("growth_log2", C.c_int32), ("skip_on_saturation", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StepGuardState(C.Structure):      # fv_step_guard_state: 56 bytes
+    _fields_ = [("delta_log2", C.c_int32), ("good_steps", C.c_int32), ("last_apply", C.c_int32), ("last_inv_delta", C.c_float), ("flag", C.c_float),
+                ("last_saturations", C.c_uint32), ("applied", C.c_int64), ("skipped_nonfinite", C.c_int64), ("skipped_saturated", C.c_int64),
+                ("saturated_applied", C.c_int64)]
+
+
 class HeadLossSpec(C.Structure):    # fv_head_loss_spec: 12 bytes
     _fields_ = [("kind", C.c_int32), ("beta", C.c_float), ("chunk", C.c_int32)]
 
@@ -203,6 +214,15 @@ SIGNATURES = {
     "fv_adamw_groups_destroy": (_i, [_vp, _vp]),
     "fv_adamw_clip_step_groups": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(AdamWHParams), _vp, _i64, _vp, _vp, _vp]),
     "fv_adamw_clip_step_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i64, C.POINTER(AdamWHParams), _vp, _i64, _vp, _vp, _vp]),
+    "fv_step_guard_create": (_i, [_vp, C.POINTER(StepGuardConfig), C.POINTER(_vp)]),
+    "fv_step_guard_destroy": (_i, [_vp, _vp]),
+    "fv_step_guard_export": (_i, [_vp, _vp, C.POINTER(StepGuardState)]),
+    "fv_step_guard_import": (_i, [_vp, _vp, C.POINTER(StepGuardState)]),
+    "fv_step_guard_observe": (_i, [_vp, _vp, _vp]),
+    "fv_step_guard_flag": (_i, [_vp, _vp, C.POINTER(_vp)]),
+    "fv_step_guard_report": (_i, [_vp, _vp, _vp, _vp]),
+    "fv_adamw_clip_step_guarded": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i64, C.POINTER(AdamWHParams), _vp, _i64, _vp, _vp, _vp, _vp]),
+    "fv_train_set_step_guard": (_i, [_vp, _vp]),
 }
 
 # TEST-ONLY op-level entry points (include/fastvla_hip_testops.h, vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so): not part of the product library
@@ -255,6 +275,7 @@ OPS_SIGNATURES = {
     "fv_op_flow_select": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "fv_op_head_saved_cat_offset": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_size_t)]),
     "fv_op_se_gelu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "fv_op_step_guard_set_flag": (_i, [_vp, _f, _vp]),
 }
 
 _LIB = None

@@ -1305,6 +1305,11 @@ class FastVLAEngine:
         """bind (or, with None, unbind) the fp16 (B, tokens, tower_out_dim) buffer train_forward_backward leaves dL/d(tower_out) in"""
         _lib.check(self.lib.fv_train_set_tower_grad(self.h, _ptr(buf)), "fv_train_set_tower_grad", self.h)
 
+    def train_set_step_guard(self, guard) -> None:
+        """bind (or, with None, unbind) a fastvla_hip.guard.StepGuard to train_forward_backward / train_lora_forward_backward: dL/dactions is multiplied by the
+        guard's device delta, so every gradient carries train_loss_scale() * delta; the guarded adamw_step divides delta out again"""
+        _lib.check(self.lib.fv_train_set_step_guard(self.h, guard.handle() if guard is not None else None), "fv_train_set_step_guard", self.h)
+
     def train_tower_backward(self, pix: torch.Tensor, d_tower_out: torch.Tensor, tws: torch.Tensor, flat_grads: torch.Tensor, bucket_cb=None) -> None:
         """the tower's backward from dL/d(tower_out) (fp16, loss-scaled): its gradients into flat_grads at their train_layout() offsets"""
         B = pix.shape[0]
@@ -1383,23 +1388,35 @@ class FastVLAEngine:
     def adamw_step(self, flat_params, flat_grads, m, v, step: int, *, lr: float, betas=(0.9, 0.95), eps: float = 1e-8,
                    weight_decay: float = 1e-4, max_grad_norm: float = 1.0, grad_scale: float = 1.0,
                    grad_norm_out: Optional[torch.Tensor] = None, groups: Optional["AdamWGroups"] = None,
-                   group_norms_out: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None, ema_weight: Optional[float] = None) -> None:
+                   group_norms_out: Optional[torch.Tensor] = None, ema: Optional[torch.Tensor] = None, ema_weight: Optional[float] = None,
+                   guard=None) -> None:
         """fused clip + AdamW on the flat buffers.  groups=None: fv_adamw_clip_step, one learning rate and one decay for the whole buffer.  With a table from
         adamw_groups(): fv_adamw_clip_step_groups -- lr and decay per group (`weight_decay` here is then ignored: the table carries the decays), frozen groups
         untouched, group_norms_out (n_groups f32, device) <- every group's gradient norm.  With ema= (a float32 buffer shaped like flat_params) and
         ema_weight = 1 - decay (fastvla_hip.ema.ema_weight): fv_adamw_clip_step_ema, the same step on either path and ema <- ema + ema_weight (p_new - ema) in
-        the same pass."""
+        the same pass.  With guard= (a fastvla_hip.guard.StepGuard): fv_adamw_clip_step_guarded on whichever of the four paths the other arguments name -- the
+        step is skipped on the device when the gradient is non-finite or the guard's saturation flag is set, and the guard's delta is divided out of an
+        applied one.  `step` stays the caller's count and advances on a skipped step too."""
         hp = _lib.AdamWHParams(lr, betas[0], betas[1], eps, weight_decay, max_grad_norm if max_grad_norm else 0.0,
                                grad_scale)
-        if ema is not None:
-            if ema_weight is None:
+        if ema is not None or guard is not None:
+            if ema is not None and ema_weight is None:
                 raise ValueError("ema= needs ema_weight=")
-            if ema.dtype != torch.float32 or ema.numel() != flat_params.numel() or ema.device != flat_params.device or not ema.is_contiguous():
+            if ema is None and ema_weight is not None:
+                raise ValueError("ema_weight= needs ema=")
+            if ema is not None and (ema.dtype != torch.float32 or ema.numel() != flat_params.numel() or ema.device != flat_params.device or not ema.is_contiguous()):
                 raise ValueError("ema must be a contiguous float32 buffer of flat_params' size on its device")
             if groups is None and group_norms_out is not None:
                 raise ValueError("group_norms_out needs groups=")
             if groups is not None and group_norms_out is not None and (group_norms_out.dtype != torch.float32 or group_norms_out.numel() < groups.n_groups):
                 raise ValueError(f"group_norms_out must hold {groups.n_groups} float32 values")
+        if guard is not None:
+            _lib.check(self.lib.fv_adamw_clip_step_guarded(self.h, flat_params.data_ptr(), flat_grads.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(ema),
+                                                           float(ema_weight) if ema is not None else 0.0, flat_params.numel(), C.byref(hp),
+                                                           groups.handle() if groups is not None else None, step, guard.handle(), _ptr(grad_norm_out),
+                                                           _ptr(group_norms_out), _stream()), "fv_adamw_clip_step_guarded", self.h)
+            return
+        if ema is not None:
             _lib.check(self.lib.fv_adamw_clip_step_ema(self.h, flat_params.data_ptr(), flat_grads.data_ptr(), m.data_ptr(), v.data_ptr(), ema.data_ptr(),
                                                        float(ema_weight), flat_params.numel(), C.byref(hp), groups.handle() if groups is not None else None,
                                                        step, _ptr(grad_norm_out), _ptr(group_norms_out), _stream()), "fv_adamw_clip_step_ema", self.h)

@@ -15,13 +15,14 @@ from .configuration_fastvla import FastVLAConfig
 from .ema_state import EmaMixin
 from .fastvlm_with_expert import FastVLMWithExpert
 from .flow_surface import FlowSurfaceMixin
+from .guard_state import StepGuardMixin
 from .options import (FLOW_DIST_A, FLOW_DIST_B, FLOW_MAX_PERIOD, FLOW_MIN_PERIOD, parse_weight_list, resolve_chunk_options,  # noqa: F401  (their public home)
                       resolve_flow_noise_draws, resolve_flow_options, resolve_flow_samples, resolve_flow_solver, resolve_policy_options,
                       resolve_prefix_options, resolve_rtc_options)
 from .processor_fastvla import FastVLAProcessor
 
 
-class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
+class FastVLAPolicy(nn.Module, EmaMixin, StepGuardMixin, FlowSurfaceMixin):
     config_class = FastVLAConfig
     name = "fastvla"
 
@@ -500,8 +501,13 @@ class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
           prepared batch comes back under "next" and is passed as `prepared=` to the following call.
         * with EMA on (enable_ema() or FASTVLA_EMA_DECAY; fastvla/ema_state.py) the optimiser call of a synced micro-batch also moves the average of the
           trainable buffer (fv_adamw_clip_step_ema) and the result gains "ema_weight", the weight 1 - d_t of the last update.
+        * with the step guard on (enable_step_guard() or FASTVLA_STEP_GUARD=1; fastvla/guard_state.py) the optimiser call is fv_adamw_clip_step_guarded: a
+          step whose gradient is non-finite (backbone training: or whose fp16 operands saturated) is skipped on the device, and the result gains
+          "step_skipped" (0 / 1: the last guarded step's decision) and "loss_scale" (the scale the next backward runs with), both device tensors.  `step`,
+          Adam's bias-correction index, advances on a skipped step too.
         """
         self._ema_from_env()
+        self._step_guard_from_env()
         self._ema_refuse_in_scope("a training step")
         if self._unfrozen is None and not self.config.freeze_backbone and os.environ.get("FASTVLA_TRAIN_BACKBONE", "0") == "1":
             self.enable_backbone_training()
@@ -542,6 +548,9 @@ class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
         target_buf = st["g"] if k == 1 else (st["acc"] if first else st["g"])
         pad = prep.get("pad")
         loss, grads = eng.head_backward(flat, actions, targets, saved, dropout_p=p, flat_grads=target_buf, pad=pad)
+        guard = self._step_guard_attach(eng, None)      # None with the guard off: every call below is then the one it was (head-only: fp32, delta stays 1)
+        if guard is not None:
+            guard.observe()
         if k > 1 and not first:
             eng.grad_accumulate(st["acc"], grads)
         total = st["g"] if k == 1 else st["acc"]
@@ -558,8 +567,16 @@ class FastVLAPolicy(nn.Module, EmaMixin, FlowSurfaceMixin):
             st["exchange"].finish(dev)
             st["step"] += 1
             st["micro"] = 0
+            gkw = {}
+            if guard is not None:
+                from fastvla_hip.guard import all_reduce_flag
+                all_reduce_flag(guard.flag(), process_group)      # one rank's flag skips the step on every rank (a NaN / inf survives the gradient sum by itself)
+                gkw["guard"] = guard
             eng.adamw_step(flat, total, st["m"], st["v"], st["step"], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                           max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=st["norm"], **self._ema_step_args(st["step"]))
+                           max_grad_norm=max_grad_norm or 0.0, grad_scale=scale, grad_norm_out=st["norm"], **self._ema_step_args(st["step"]), **gkw)
+        if guard is not None:
+            rep = guard.report()
+            out["step_skipped"], out["loss_scale"] = rep[0], rep[1]
         out["grad_norm"] = st["norm"][0]
         if self._ema is not None:
             out["ema_weight"] = self._ema["weight"]

@@ -91,6 +91,8 @@ class Trainer:
         self._resume_opt = None
         if hasattr(model, "_ema_from_env"):
             model._ema_from_env()      # FASTVLA_EMA_DECAY alone switches the EMA of the weights on (before a resume looks for its record)
+        if hasattr(model, "_step_guard_from_env"):
+            model._step_guard_from_env()      # FASTVLA_STEP_GUARD=1 likewise
 
     @property
     def is_main_process(self) -> bool:
@@ -135,6 +137,8 @@ class Trainer:
                                             optim=self._resume_opt.get("optim") or {})
             if hasattr(self.model, "load_ema_record"):     # after the live weights: the average continues, or starts from them
                 self.model.load_ema_record(self._resume_opt.get("ema"))
+            if hasattr(self.model, "load_step_guard_record"):     # the guard's counters and loss scale continue
+                self.model.load_step_guard_record(self._resume_opt.get("step_guard"))
             self._resume_opt = None
         un = getattr(self.model, "_unfrozen", None)
         if un is not None:
@@ -180,6 +184,8 @@ class Trainer:
                 rec = {"train/loss": float(out["loss"]), "train/mse": float(out["mse"]), "train/lr": self.last_lr, "train/epoch": self.epoch}
                 if getattr(self, "_last_grad_norm", None) is not None:   # the LAST closed update's norm, also on logging steps that fall between two updates
                     rec["train/grad_norm"] = float(self._last_grad_norm)
+                if out.get("step_skipped") is not None:      # step guard on: the last update's decision and the loss scale in force
+                    rec["train/step_skipped"], rec["train/loss_scale"] = float(out["step_skipped"]), float(out["loss_scale"])
                 if out.get("ema_weight") is not None:      # EMA on: the weight 1 - d_t of the last update
                     rec["train/ema_weight"] = float(out["ema_weight"])
                 self._log(rec)
@@ -257,7 +263,9 @@ class Trainer:
             core = getattr(self.model, "model", None)
             aug = core.backbone.augmentation_record() if hasattr(getattr(core, "backbone", None), "augmentation_record") else None
             ema = self.model.ema_record() if hasattr(self.model, "ema_record") else None
-            rec = optimizer_record(st, getattr(self.model, "_unfrozen", None), self.global_step, self.update_step, augment=aug, ema=ema)
+            sg = self.model.step_guard_record() if hasattr(self.model, "step_guard_record") else None
+            rec = optimizer_record(st, getattr(self.model, "_unfrozen", None), self.global_step, self.update_step, augment=aug, ema=ema,
+                                   **({"step_guard": sg} if sg is not None else {}))
             torch.save(rec, d / "optimizer.pt")
         if self.save_ema_checkpoint and self._ema_on():
             # the averaged weights as a plain deployable policy: the weight files only, written while the average stands in for the live buffer

@@ -30,6 +30,10 @@ Parameter groups (`optim={"lr_scales", "no_decay", "layer_decay", "lora_plus_rat
 fv_adamw_clip_step_groups over a table built from the trainable buffer's layout -- a learning-rate factor, a weight decay and a frozen flag per group, ONE clip
 norm over the non-frozen elements -- and the step also returns every group's gradient norm.  With none set the step is fv_adamw_clip_step, as before.
 
+Step guard (policy.enable_step_guard(); fastvla/guard_state.py): the optimiser call of any kind becomes fv_adamw_clip_step_guarded -- a step whose gradient is
+non-finite or whose backward clamped an fp16 operand is skipped on the device, the loss scale backs off and grows again there -- and the 50-step host poll of
+the saturation counter below is not run.  The commit after a skipped step still runs: it rebuilds the same operand images.
+
 EMA (policy.enable_ema(); fastvla/ema_state.py): the optimiser call of either kind becomes fv_adamw_clip_step_ema, which also moves an average of `trainable`
 in the same pass; with it off the calls are the ones above.
 """
@@ -293,6 +297,9 @@ class UnfrozenState:
         if overlap:
             self.bucketed.group = process_group
             self.bucketed.begin(self.g)
+        # the step guard (policy.enable_step_guard(); fastvla/guard_state.py): None with it off -- every call below is then the one it was.  On: bound to the
+        # backward (every gradient carries the loss scale times the guard's delta), observed after every micro-batch, consumed by the guarded step
+        guard = pol._step_guard_attach(eng, self.loss_scale_log2)
         tower_out, tws, dto = prep["tower_out"], None, None
         if self.train_tower:
             if B not in self._tws:
@@ -312,6 +319,8 @@ class UnfrozenState:
                                                           bucket_cb=self.bucketed.bucket_ready if overlap else None, pad=prep.get("pad"))
         if self.train_tower:
             eng.train_tower_backward(prep["pix"], dto, tws, self.g, bucket_cb=self.bucketed.bucket_ready if overlap else None)
+        if guard is not None:
+            guard.observe()      # did this micro-batch's backward clamp an fp16 operand?  (sticky over the accumulation window)
         total = self.g
         if self.lora is not None:
             if not self.lora_direct:
@@ -338,6 +347,10 @@ class UnfrozenState:
             self.micro = 0
             scale /= eng.train_loss_scale()      # every gradient of fv_train_forward_backward carries the loss scale (2^12 by default)
             ema = pol._ema_step_args(self.step_count)      # {} with EMA off: the calls below are then the ones they were (fastvla/ema_state.py)
+            if guard is not None:
+                from fastvla_hip.guard import all_reduce_flag
+                all_reduce_flag(guard.flag(), process_group)      # one rank's flag skips the step on every rank (a NaN / inf survives the gradient sum by itself)
+                ema = {**ema, "guard": guard}
             if self.optim:       # parameter groups: lr / decay per group, frozen groups untouched, every group's norm (no host read: a device tensor)
                 table = self._groups_for(weight_decay)
                 eng.adamw_step(self.trainable, total, self.m, self.v, self.step_count, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
@@ -351,7 +364,7 @@ class UnfrozenState:
             # the OLD weights must not serve an eval between steps
             self.commit()
             pol._opt_state["step"] = self.step_count
-            if self.step_count % self.saturation_check_every == 0:
+            if guard is None and self.step_count % self.saturation_check_every == 0:
                 # the backward's fp16 operands carry the gradient x 2^loss_scale: a clamp means the scale is too large for this model / loss
                 # -- say so and halve it (every 50 optimiser steps: the read synchronises)
                 n = eng.fp16_saturations(reset=True)
@@ -360,6 +373,9 @@ class UnfrozenState:
                     self.loss_scale_log2 -= 1
                     eng.train_set_options(loss_scale_log2=self.loss_scale_log2, keep=True)
                     warnings.warn(f"{n} fp16 gradient-operand groups saturated in the last {self.saturation_check_every} steps: loss scale lowered to 2^{self.loss_scale_log2}")
+        if guard is not None:      # the last guarded step's decision and the scale the next backward runs with: device tensors, nothing is read back
+            rep = guard.report()
+            out["step_skipped"], out["loss_scale"] = rep[0], rep[1] * eng.train_loss_scale()
         out["grad_norm"] = self.norm[0]
         if self.optim and self.group_norms is not None:
             out["group_grad_norms"], out["group_names"] = self.group_norms, self.group_names     # one norm per group (a device tensor) and the groups' labels

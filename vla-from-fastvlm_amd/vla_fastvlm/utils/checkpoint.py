@@ -51,17 +51,21 @@ def read_extras(checkpoint_dir) -> dict:
 EXTRA_STATE_MARKS = (".io_norm.", ".splice_image_tokens")
 
 
-def optimizer_record(st: dict, un, global_step: int, update_step: int, augment: dict | None = None, ema: dict | None = None) -> dict:
+def optimizer_record(st: dict, un, global_step: int, update_step: int, augment: dict | None = None, ema: dict | None = None,
+                     step_guard: dict | None = None) -> dict:
     """What Trainer writes to optimizer.pt: AdamW's moments and step, the loop's counters, and for an unfrozen run (`un`, training/unfrozen.py UnfrozenState) its
     trainable fp32 buffer and what it trains.  "optim" -- the parameter-group options of the run (fastvla_hip/optim.py) -- is there ONLY when one is set: a
     plain run's file is byte for byte what it was.  "augment" -- {options, seed, batches} of a run with image augmentation on
     (FastVLMBackbone.augmentation_record; batches = training batches STEPPED) -- likewise only when it is on.  "ema" -- {options, shadow, updates} of a run that
-    keeps an EMA of its weights (policy.ema_record()) -- likewise.  "flat" and the weight files beside this one are always the LIVE weights."""
+    keeps an EMA of its weights (policy.ema_record()) -- likewise.  "step_guard" -- {options, state} of a run with the step guard on
+    (policy.step_guard_record()) -- likewise.  "flat" and the weight files beside this one are always the LIVE weights."""
     rec = {"m": st["m"].cpu(), "v": st["v"].cpu(), "step": st["step"], "global_step": global_step, "update_step": update_step}
     if augment is not None:
         rec["augment"] = dict(augment)
     if ema is not None:
         rec["ema"] = dict(ema)
+    if step_guard is not None:
+        rec["step_guard"] = dict(step_guard)
     if un is not None:
         # the fp32 MASTER of an unfrozen run: the VLM tensors of policy_state_dict.pt come back through the engine's bf16 operand copies, and a master
         # rebuilt from those has lost the low bits every later update (~1e-3 of a bf16 ulp) lives in
