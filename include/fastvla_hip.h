@@ -297,7 +297,8 @@ int fv_head_set_loss(fv_handle* h, const fv_head_loss_spec* spec);
  * alive (and sized for the B of those calls). */
 int fv_head_set_loss_mask(fv_handle* h, const uint8_t* pad_dev);
 /* *dev = 2 handle-owned device floats written by the chunked loss kernel (not by the plain MSE path): { sum over valid elements of d^2 / n,
- * valid steps / (B * K) }.  They head a 16-byte aligned slot of 4 floats of their own (the other two stay 0): a 4-float copy is in bounds. */
+ * valid steps / (B * K) }.  They head a 16-byte aligned slot of 4 floats of their own (the other two stay 0): a 4-float copy is in bounds.
+ * (A binned head -- fv_head_set_bins, below -- writes the slot with every loss evaluation and uses the third float for its accuracy.) */
 int fv_head_loss_metrics(fv_handle* h, const float** dev);
 /* Per-dimension and per-step weights of the loss above (gripper against arm, near against far steps).  dim_w: HOST, A = action_dim / chunk floats; step_w:
  * HOST, K = chunk floats; either may be NULL, meaning ones; both NULL switches weighting off.  With om = dim_w[a] * step_w[k]:
@@ -314,6 +315,47 @@ int fv_head_set_loss_weights(fv_handle* h, const float* dim_w, const float* step
  * the loss lives in; 0 for a dimension without a valid step.  actions, targets: (B, K, A) device f32.  Uses the handle's current chunk and mask, never the
  * weights.  One block per dimension, fixed-order sums (no float atomics).  On demand: no train step calls it. */
 int fv_head_loss_per_dim(fv_handle* h, const float* actions, const float* targets, int B, float* out_dev, fv_stream s);
+/* ---- binned action head ("discretised actions", OpenVLA / RT-2; normalised action space).  action_head becomes Linear(fusion_dim, action_dim * bins): the
+ * logits are (B, K, A, bins) row-major and the `bins` logits of one action element are a GROUP.  The 12 tensors, their names and order stay; action_dim stays
+ * the ACTION width K * A everywhere a caller sees it; fv_head_layout, fv_head_saved_bytes, the workspace and the training layouts follow the taller tensor.
+ * Element e of a row has the range [lo, hi] = entry e % n_range of the two host vectors.  w = (hi - lo) / bins (formed in double, rounded to fp32 once); bin j
+ * covers [lo + j w, lo + (j + 1) w) and has the centre c_j = lo + (j + 1/2) w; a target a is clamped to [lo, hi] and falls into bin min(bins - 1, floor((a - lo) / w)).
+ * Target distribution q of a group: sigma == 0 one-hot at the target's bin; sigma > 0 (HL-Gauss, sigma in units of w, S = sigma w) the Gaussian around the
+ * clamped target integrated over the bins and renormalised to the range,
+ *     q_j = [Phi((e_{j+1} - a) / S) - Phi((e_j - a) / S)] / [Phi((hi - a) / S) - Phi((lo - a) / S)],  e_j = lo + j w (the last edge is hi itself),
+ * evaluated in double inside the kernel and rounded to fp32 once.  With p = softmax(z), n = B K A (ALL elements) and om as fv_head_set_loss_weights:
+ *     loss = sum_valid om (-sum_j q_j log p_j) / n          dL/dz_j = loss_scale om (p_j - q_j) / n
+ * A padded step (fv_head_set_loss_mask) or an element with om == 0 is SELECTED away: exactly 0 to the loss, the metrics and all `bins` gradient elements,
+ * its target never read.  Decode: FV_BINS_DECODE_ARGMAX the centre of the most likely bin (ties to the lowest index), FV_BINS_DECODE_MEAN sum_j p_j c_j.
+ * In bins mode
+ *   fv_head_forward writes the logits into `saved` (fv_head_bins_logits) and the DECODED (B, action_dim) chunk to `actions`: normalised when training != 0,
+ *     with the folded action statistics of fv_head_set_io_norm applied behind the decode otherwise;
+ *   fv_head_mse_backward and every fv_train_*_forward_backward evaluate the loss above from the saved logits and `targets` (continuous, normalised; `actions`
+ *     is not read) -- FV_ERR_STATE unless the configured loss kind is the default FV_LOSS_MSE (the kind has no meaning here; chunk, mask and weights apply);
+ *   fv_head_backward (a caller's grad_actions) is refused with FV_ERR_STATE: the decode is not differentiated, the head trains through its own loss;
+ *   fv_head_loss_metrics' 4-float slot is written by every loss evaluation: { sum_valid (decoded - target)^2 / n, valid steps / (B K), the fraction of the
+ *     valid elements whose most likely bin is the target's, 0 } -- unweighted, valid looks at pads only, an om == 0 element adds no error and is no hit.
+ * One wave per group, the logits read once, fixed-order sums (no float atomics: two runs agree bit for bit). */
+#define FV_BINS_DECODE_ARGMAX 0
+#define FV_BINS_DECODE_MEAN 1
+#define FV_HEAD_BINS_MAX 1024
+#define FV_HEAD_BINS_MAX_WIDTH 32768   /* action_dim * bins: the head's linear kernels put one output per block row, a wide-output GEMM is not built */
+typedef struct fv_head_bins_spec {
+  int32_t bins;      /* 2 .. FV_HEAD_BINS_MAX */
+  int32_t decode;    /* FV_BINS_DECODE_* */
+  float sigma;       /* >= 0, finite; 0 = one-hot targets */
+  int32_t n_range;   /* entries of lo_host / hi_host: >= 1 and a divisor of action_dim (1: one range for all; A: one per action dimension) */
+} fv_head_bins_spec;
+/* NULL spec switches the mode off: the handle is the regression head again, bit for bit.  Allowed only BEFORE fv_bind_workspace and before any
+ * fv_train_*_begin (FV_ERR_STATE afterwards: sizes depend on the mode), and not while flow mode is on (FV_ERR_STATE; fv_head_set_flow answers the same while
+ * bins are on).  FV_ERR_ARG, changing nothing, for bins outside 2 .. 1024, an unknown decode, a negative or non-finite sigma, n_range < 1 or not dividing
+ * action_dim, a null, non-finite or unordered (lo >= hi) range, action_dim * bins > FV_HEAD_BINS_MAX_WIDTH.  A configuration call: it uploads the ranges. */
+int fv_head_set_bins(fv_handle* h, const fv_head_bins_spec* spec, const float* lo_host, const float* hi_host);
+/* *logits_dev = the (B, action_dim, bins) logits a bins-mode fv_head_forward(B) wrote into `saved`.  FV_ERR_STATE when bins mode is off. */
+int fv_head_bins_logits(fv_handle* h, const void* saved, int B, const float** logits_dev);
+/* probs_dev (B, action_dim, bins) DEVICE f32 <- softmax of every group of those logits (the decode kernel's own max-subtracted softmax), one launch on s.
+ * FV_ERR_STATE when bins mode is off. */
+int fv_head_bins_probs(fv_handle* h, const void* saved, int B, float* probs_dev, fv_stream s);
 /* ---- flow-matching action head (pi0 / SmolVLA convention, everything in normalised action space).  With eps ~ N(0, I), a the target chunk and t in [0, 1]:
  *     x_t = t eps + (1 - t) a        u = eps - a        sampling: x_1 = eps, x <- x + dt v for N steps of dt = -1 / N down to t = 0
  * The velocity network v(x_t, t | observation) is the SAME expert with two more input blocks on fusion.0:

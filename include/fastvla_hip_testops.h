@@ -230,6 +230,18 @@ int fv_op_chunk_loss(const float* a, const float* t, const uint8_t* pad, float* 
 int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad, const float* dim_w, const float* step_w, float* g, float* partial,
                               size_t partial_floats, float* loss, float* metrics, int64_t n, int A, int K, int kind, float beta, float loss_scale, fv_stream s);
 
+/* the binned head's loss alone (csrc/bins_kernels.hip bins_loss_kernel + fold; fastvla_hip.h "binned action head" has the formulas): logits, g (n, bins)
+ * DEVICE f32 with n = rows * da groups, targets (n), pad (n / (da / K)) bytes or NULL, dim_w (da / K) and step_w (K) DEVICE floats, both or neither;
+ * range: DEVICE [lo | hi | w], n_range floats each (w = the fp32 (hi - lo) / bins), element e of a row reads entry e % n_range.  partial: 4 * ceil(n / 4) floats
+ * of scratch; loss 1 float; metrics 4 floats. */
+int fv_op_bins_loss(const float* logits, const float* targets, const uint8_t* pad, const float* dim_w, const float* step_w, const float* range, int n_range,
+                    float sigma, int decode, float* g, float* partial, size_t partial_floats, float* loss, float* metrics, int64_t n, int bins, int da, int K,
+                    float loss_scale, fv_stream s);
+/* the decode alone (bins_decode_kernel): logits (n, bins) -> actions (n), then actions * post_scale[e] + post_shift[e] (da DEVICE floats each, both or NULL);
+ * probs (n, bins) or NULL: softmax(logits) as well. */
+int fv_op_bins_decode(const float* logits, const float* range, int n_range, int decode, float* actions, float* probs, int64_t n, int bins, int da,
+                      const float* post_scale, const float* post_shift, fv_stream s);
+
 /* the head's fused loss + backward (csrc/head_kernels.hip launch_head_backward) on explicit head dimensions, WITH d_pooled (B, feat): dL/d(pooled feature),
  * the gradient an unfrozen backbone continues from, which no product entry point hands out at the head level.  time_dim = E > 0: the flow head, whose cat row
  * is feat + hid + da + E wide (d_pooled is still its first feat columns).  P / G: the flat parameter / gradient buffers of that layout; actions, targets

@@ -261,6 +261,9 @@ struct fv_handle {
   fv::HeadFlow flow{nullptr, 0, 0.f, 0.f};   // fv_head_set_flow (hd.te > 0: on); freq: device te / 2 floats, allocated per call of the setter that needs more
   int flow_freq_cap = 0;
   float* flow_freq_buf = nullptr;
+  fv::HeadBins bins{nullptr, 0, 0.f, 0};   // fv_head_set_bins (hd.nb > 0: on, and hd.bn points here); range: device [lo | hi | w], kept across off / on
+  int bins_range_cap = 0;                  // entries per vector bins_range_buf holds (a LARGER n_range allocates anew)
+  float* bins_range_buf = nullptr;
   uint32_t* prefix_thr_buf = nullptr;   // fv_head_set_flow_prefix (hd.pk > 0: on): the delay table's device copy, prefix_thr_cap words, kept across off / on
   int prefix_thr_cap = 0;
   fv::HeadGuide guide{nullptr, 0, 0.f, 0};   // fv_head_set_flow_guidance (step_w != null: on)

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void zero_cols_kernel(float* __restrict__ dst,
 HeadOffsets head_offsets(const HeadDims& d) {
   HeadOffsets r;
   const int64_t sz[HP_TOTAL] = {d.ds, d.ds, (int64_t)d.hid * d.ds, d.hid, (int64_t)d.fus * head_cat_width(d), d.fus,
-                          d.fus, d.fus, (int64_t)d.fus * d.fus, d.fus, (int64_t)d.da * d.fus, d.da};
+                          d.fus, d.fus, (int64_t)d.fus * d.fus, d.fus, (int64_t)head_out_width(d) * d.fus, head_out_width(d)};
   int64_t o = 0;
   for (int i = 0; i < HP_TOTAL; ++i) {
     r.o[i] = o;
@@ -268,6 +268,7 @@ namespace {
 struct Saved {
   float *n0, *xh0, *rstd0, *z1, *cat, *z2, *xh2, *rstd2, *n2, *d2, *mask, *z3, *a3;
   uint8_t* pmask;   // prefix mode: (R, pk) bytes behind everything else (pk == 0: nothing, every offset and the total as ever)
+  float* logits;    // bins mode: (R, da, nb) behind that (nb == 0: nothing)
   size_t cat_off, total;   // cat's offset from the base and the whole block, in floats
 };
 // B observations; the state branch keeps B rows, cat .. a3 have R = head_rows(d, B) of them (more than B only with fv_head_set_flow_draws)
@@ -281,6 +282,7 @@ Saved carve(const HeadDims& d, int B, float* base) {
   s.xh2 = take(R * d.fus); s.rstd2 = take(R); s.n2 = take(R * d.fus); s.d2 = take(R * d.fus);
   s.mask = take(R * d.fus); s.z3 = take(R * d.fus); s.a3 = take(R * d.fus);
   s.pmask = reinterpret_cast<uint8_t*>(take(d.te > 0 ? (R * d.pk + 3) / 4 : 0));
+  s.logits = take(d.nb > 0 ? R * d.da * d.nb : 0);
   s.total = o;
   return s;
 }
@@ -290,13 +292,15 @@ size_t head_saved_bytes(const HeadDims& d, int B) { return carve(d, B, nullptr).
 float* head_saved_cat(const HeadDims& d, int B, float* saved) { return carve(d, B, saved).cat; }
 size_t head_saved_cat_offset(const HeadDims& d, int B) { return carve(d, B, nullptr).cat_off; }
 uint8_t* head_saved_prefix_mask(const HeadDims& d, int B, float* saved) { return carve(d, B, saved).pmask; }
+float* head_saved_logits(const HeadDims& d, int B, float* saved) { return carve(d, B, saved).logits; }
 
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B) {
   const size_t wmax = (size_t)(head_cat_width(d) > d.fus ? head_cat_width(d) : d.fus);
   // dL/dactions | two activation-gradient rows of the widest layer | alignment slack | the chunked loss's per-block partials (loss, sum w d^2, sum w)
   // (draws: every row count is R = S B, and the pad mask's R K <= R da bytes, once per draw, come last; prefix mode builds its loss mask in the same place)
+  // (bins mode: dL/dlogits is nb times wider, and the bins loss's per-block partials follow the chunked loss's)
   const size_t R = (size_t)head_rows(d, B);
-  return (R * d.da + 2 * R * wmax + 64 + chunk_loss_partial_floats() + (R > (size_t)B || (d.te > 0 && d.pk > 0) ? (R * d.da + 3) / 4 : 0)) * sizeof(float);
+  return (R * head_out_width(d) + 2 * R * wmax + 64 + chunk_loss_partial_floats() + (d.nb > 0 ? bins_loss_partial_floats((long)(R * d.da)) : 0) + (R > (size_t)B || (d.te > 0 && d.pk > 0) ? (R * d.da + 3) / 4 : 0)) * sizeof(float);
 }
 
 void launch_head_state_branch(const HeadDims& d, const float* P, const float* states, int B, float* n0, float* xh0, float* rstd0, float* z1, float* dst, int ldd,
@@ -313,6 +317,7 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
                         int training, float drop_p, uint64_t seed, uint64_t offset, float* actions, float* saved,
                         hipStream_t s, const HeadIoNorm* io) {
   if (!P || !pooled || !states || !actions || !saved) return fv_fail(FV_ERR_ARG, "head_forward: null pointer");
+  if (d.nb > 0 && (!d.bn || d.te > 0)) return fv_fail(FV_ERR_STATE, "head_forward: bins mode needs its configuration and excludes flow mode");
   if (B <= 0) return fv_fail(FV_ERR_ARG, "head_forward: B must be positive");
   if (drop_p < 0.f || drop_p >= 1.f) return fv_fail(FV_ERR_ARG, "head_forward: dropout p out of range");
   const HeadOffsets ho = head_offsets(d);
@@ -337,6 +342,13 @@ int launch_head_forward(const HeadDims& d, const float* P, const float* pooled, 
                      (const float*)nullptr, (const float*)nullptr);
   hipLaunchKernelGGL(silu_dropout_kernel, dim3(cdiv((long)R * d.fus, 256)), blk, 0, s, sv.n2, sv.d2, sv.mask, (long)R * d.fus, training, drop_p, seed, offset);
   hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.fus, 4), cdiv(R, 8)), blk, 0, s, sv.d2, d.fus, P + ho.o[HP_FUS4_W], P + ho.o[HP_FUS4_B], sv.a3, d.fus, sv.z3, R, d.fus, d.fus, 1, (const float*)nullptr, (const float*)nullptr);
+  if (d.nb > 0) {   // bins mode: the logits stay in `saved`, `actions` receives the decoded chunk (the action statistics behind the decode)
+    const int ow = head_out_width(d);
+    hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(ow, 4), cdiv(R, 8)), blk, 0, s, sv.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], sv.logits, ow, (float*)nullptr, R, ow, d.fus, 0,
+                       (const float*)nullptr, (const float*)nullptr);
+    FV_HIP_CHECK(hipGetLastError());
+    return launch_bins_decode(*d.bn, sv.logits, actions, nullptr, (long)R * d.da, d.nb, d.da, as, am, s);
+  }
   hipLaunchKernelGGL(linear_fwd_kernel, dim3(cdiv(d.da, 4), cdiv(R, 8)), blk, 0, s, sv.a3, d.fus, P + ho.o[HP_ACT_W], P + ho.o[HP_ACT_B], actions, d.da, (float*)nullptr, R, d.da, d.fus, 0, as, am);
   FV_HIP_CHECK(hipGetLastError());
   return FV_OK;
@@ -352,7 +364,14 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
     return fv_fail(FV_ERR_STATE, "head_backward: prefix mode needs the loss's chunk length (fv_head_set_loss) to be the prefix's, %d", d.pk);
   const bool chunked = hl && !grad_actions && (hl->kind != FV_LOSS_MSE || hl->pad || weighted || prefix);   // MSE without a mask or weights: mse_kernel, for any chunk length
   if (chunked && (!hl->metrics || hl->chunk < 1 || d.da % hl->chunk)) return fv_fail(FV_ERR_ARG, "head_backward: chunked loss needs metrics and a chunk length that divides action_dim");
-  if (!grad_actions && (!actions || !targets || !loss)) return fv_fail(FV_ERR_ARG, "head_backward: need grad_actions or (actions, targets, loss)");
+  const bool bins = d.nb > 0;
+  if (bins) {   // the head's own loss from the saved logits; `actions` is not read
+    if (!d.bn || d.te > 0) return fv_fail(FV_ERR_STATE, "head_backward: bins mode needs its configuration and excludes flow mode");
+    if (grad_actions) return fv_fail(FV_ERR_STATE, "head_backward: a bins head trains through its own loss (the decode is not differentiated): no grad_actions");
+    if (!targets || !loss || !hl || !hl->metrics) return fv_fail(FV_ERR_ARG, "head_backward: the bins loss needs targets, loss and the metrics slot");
+    if (hl->kind != FV_LOSS_MSE) return fv_fail(FV_ERR_STATE, "head_backward: the loss kind %d has no meaning for a bins head (cross-entropy): leave it at FV_LOSS_MSE", hl->kind);
+    if (hl->chunk < 1 || d.da % hl->chunk) return fv_fail(FV_ERR_ARG, "head_backward: the chunk length must divide action_dim");
+  } else if (!grad_actions && (!actions || !targets || !loss)) return fv_fail(FV_ERR_ARG, "head_backward: need grad_actions or (actions, targets, loss)");
   if (B <= 0) return fv_fail(FV_ERR_ARG, "head_backward: B must be positive");
   (void)drop_p;  // the multiplier keep/(1-p) is stored in saved.mask
   const HeadOffsets ho = head_offsets(d);
@@ -364,12 +383,19 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
   const int obs = B, S = head_rows(d, B) / B;
   B *= S;
   float* ga_own = scratch;
-  float* g1 = ga_own + ((size_t)B * d.da + 3) / 4 * 4;
+  const int ow = head_out_width(d);   // rows of action_head.weight: da, or da nb logits in bins mode
+  float* g1 = ga_own + ((size_t)B * ow + 3) / 4 * 4;
   float* g2 = g1 + (size_t)B * wmax;
   const dim3 blk(256);
   const unsigned b8 = cdiv(B, 8);
   const float* ga = grad_actions;
-  if (!ga && chunked) {
+  if (bins) {
+    float* part = g2 + (size_t)B * wmax + 16;   // (where the chunked loss's partials go; head_bwd_scratch_bytes holds the bins loss's behind them)
+    const int rc = launch_bins_loss(*d.bn, sv.logits, targets, hl->pad, ga_own, part, loss, hl->metrics, (long)B * d.da, d.nb, d.da, hl->chunk, loss_scale, s,
+                                    weighted ? hl->dim_w : nullptr, weighted ? hl->step_w : nullptr);
+    if (rc != FV_OK) return rc;
+    ga = ga_own;
+  } else if (!ga && chunked) {
     float* part = g2 + (size_t)B * wmax + 16;   // behind everything the layers below use; the 64 floats of slack cover the rounding of B * da and this gap (head_bwd_scratch_bytes)
     const uint8_t* pad = hl->pad;
     if (prefix) {   // pad[r % obs] | m[r], built where the draws' copy of the mask goes
@@ -397,9 +423,9 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
     if (rc != FV_OK) return rc;
   }
   // action_head
-  hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(cdiv(d.fus, 256), d.da), blk, 0, s, ga, sv.a3, d.fus, G + ho.o[HP_ACT_W], B, d.da, d.fus);
-  hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(d.da, 256)), blk, 0, s, ga, G + ho.o[HP_ACT_B], B, d.da);
-  hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3(cdiv(d.fus, 32), b8), blk, 0, s, ga, P + ho.o[HP_ACT_W], g1, d.fus, B, d.da, d.fus);
+  hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(cdiv(d.fus, 256), ow), blk, 0, s, ga, sv.a3, d.fus, G + ho.o[HP_ACT_W], B, ow, d.fus);
+  hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(ow, 256)), blk, 0, s, ga, G + ho.o[HP_ACT_B], B, ow);
+  hipLaunchKernelGGL(linear_bwd_dx_kernel, dim3(cdiv(d.fus, 32), b8), blk, 0, s, ga, P + ho.o[HP_ACT_W], g1, d.fus, B, ow, d.fus);
   hipLaunchKernelGGL(silu_bwd_kernel, dim3(cdiv((long)B * d.fus, 256)), blk, 0, s, g1, d.fus, sv.z3, (const float*)nullptr, g1, B, d.fus);
   // fusion.4
   hipLaunchKernelGGL(linear_bwd_dw_kernel, dim3(cdiv(d.fus, 256), d.fus), blk, 0, s, g1, sv.d2, d.fus, G + ho.o[HP_FUS4_W], B, d.fus, d.fus);

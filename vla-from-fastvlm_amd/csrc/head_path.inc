@@ -137,6 +137,7 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
     if (spec->time_dist != 0 && spec->time_dist != 1) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: unknown time_dist %d (0 uniform, 1 logit-normal)", spec->time_dist);
     if (!std::isfinite(spec->dist_a) || !std::isfinite(spec->dist_b)) return fv_fail(FV_ERR_ARG, "fv_head_set_flow: dist_a / dist_b must be finite");
   }
+  if (spec && h->hd.nb > 0) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: the head is in bins mode (fv_head_set_bins); switch that off first");
   // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
   if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_flow: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
   if (!spec) { h->hd.te = 0; h->hd.draws = 1; h->hd.pk = h->hd.pd = 0; h->flow_solver = FV_FLOW_SOLVER_EULER; h->flow_samples = 1; h->select_w = nullptr; h->flow = fv::HeadFlow{nullptr, 0, 0.f, 0.f}; h->guide = fv::HeadGuide{nullptr, 0, 0.f, 0}; return FV_OK; }
@@ -152,6 +153,57 @@ int fv_head_set_flow(fv_handle* h, const fv_head_flow_spec* spec) {
   h->hd.te = spec->time_dim;
   h->flow = fv::HeadFlow{h->flow_freq_buf, spec->time_dist, spec->dist_a, spec->dist_b, h->hd.pk > 0 ? h->prefix_thr_buf : nullptr};
   return FV_OK;
+}
+
+int fv_head_set_bins(fv_handle* h, const fv_head_bins_spec* spec, const float* lo_host, const float* hi_host) {
+  HandleScope _hs(h);
+  if (!h) return fv_fail(FV_ERR_ARG, "null handle");
+  const int da = h->hd.da;
+  std::vector<float> tab;
+  if (spec) {
+    if (spec->bins < 2 || spec->bins > FV_HEAD_BINS_MAX) return fv_fail(FV_ERR_ARG, "fv_head_set_bins: bins = %d outside 2 .. %d", spec->bins, FV_HEAD_BINS_MAX);
+    if (spec->decode != FV_BINS_DECODE_ARGMAX && spec->decode != FV_BINS_DECODE_MEAN) return fv_fail(FV_ERR_ARG, "fv_head_set_bins: unknown decode %d (0 argmax, 1 mean)", spec->decode);
+    if (!std::isfinite(spec->sigma) || spec->sigma < 0.f) return fv_fail(FV_ERR_ARG, "fv_head_set_bins: sigma = %g must be finite and >= 0", (double)spec->sigma);
+    if (spec->n_range < 1 || da % spec->n_range) return fv_fail(FV_ERR_ARG, "fv_head_set_bins: n_range = %d must be >= 1 and divide action_dim = %d", spec->n_range, da);
+    if (!lo_host || !hi_host) return fv_fail(FV_ERR_ARG, "fv_head_set_bins: null range");
+    if ((int64_t)da * spec->bins > FV_HEAD_BINS_MAX_WIDTH)
+      return fv_fail(FV_ERR_ARG, "fv_head_set_bins: action_dim * bins = %d * %d exceeds %d (the head's linear kernels take one output per block row)", da, spec->bins, FV_HEAD_BINS_MAX_WIDTH);
+    tab.resize((size_t)3 * spec->n_range);   // [lo | hi | w]; w in double, rounded once
+    for (int i = 0; i < spec->n_range; ++i) {
+      const float lo = lo_host[i], hi = hi_host[i];
+      const float w = (float)(((double)hi - (double)lo) / spec->bins);
+      if (!std::isfinite(lo) || !std::isfinite(hi) || !(lo < hi) || !std::isfinite(w) || !(w > 0.f))
+        return fv_fail(FV_ERR_ARG, "fv_head_set_bins: range %d = [%g, %g] must be finite with lo < hi", i, (double)lo, (double)hi);
+      tab[i] = lo; tab[spec->n_range + i] = hi; tab[2 * spec->n_range + i] = w;
+    }
+  }
+  // the head's layout, the saved activations, the workspace plan and the training layouts all depend on the mode
+  if (h->ws || h->train.ready || h->train.tower) return fv_fail(FV_ERR_STATE, "fv_head_set_bins: call it before fv_bind_workspace and before any fv_train_*_begin (sizes depend on the mode)");
+  if (!spec) { h->hd.nb = 0; h->hd.bn = nullptr; h->bins = fv::HeadBins{nullptr, 0, 0.f, 0}; return FV_OK; }
+  if (h->hd.te > 0) return fv_fail(FV_ERR_STATE, "fv_head_set_bins: the head is in flow mode (fv_head_set_flow); switch that off first");
+  const bool grow = h->bins_range_cap < spec->n_range;   // (kept across off / on: toggling the mode does not grow the handle)
+  FV_TRY(head_upload(h, &h->bins_range_buf, grow, tab.data(), tab.size()));
+  if (grow) h->bins_range_cap = spec->n_range;
+  h->bins = fv::HeadBins{h->bins_range_buf, spec->n_range, spec->sigma, spec->decode};
+  h->hd.nb = spec->bins;
+  h->hd.bn = &h->bins;
+  return FV_OK;
+}
+
+int fv_head_bins_logits(fv_handle* h, const void* saved, int B, const float** logits_dev) {
+  HandleScope _hs(h);
+  if (!h || !saved || !logits_dev || B < 1) return fv_fail(FV_ERR_ARG, "fv_head_bins_logits: bad argument");
+  if (h->hd.nb <= 0) return fv_fail(FV_ERR_STATE, "fv_head_bins_logits: the head is not in bins mode (fv_head_set_bins)");
+  *logits_dev = fv::head_saved_logits(h->hd, B, static_cast<float*>(const_cast<void*>(saved)));
+  return FV_OK;
+}
+
+int fv_head_bins_probs(fv_handle* h, const void* saved, int B, float* probs_dev, fv_stream s) {
+  HandleScope _hs(h);
+  if (!h || !saved || !probs_dev || B < 1) return fv_fail(FV_ERR_ARG, "fv_head_bins_probs: bad argument");
+  if (h->hd.nb <= 0) return fv_fail(FV_ERR_STATE, "fv_head_bins_probs: the head is not in bins mode (fv_head_set_bins)");
+  const float* logits = fv::head_saved_logits(h->hd, B, static_cast<float*>(const_cast<void*>(saved)));
+  return fv::launch_bins_decode(h->bins, logits, nullptr, probs_dev, (long)B * h->hd.da, h->hd.nb, h->hd.da, nullptr, nullptr, static_cast<hipStream_t>(s));
 }
 
 int fv_head_set_flow_prefix(fv_handle* h, int chunk, int max_delay, const uint32_t* thresholds_host) {
@@ -443,6 +495,7 @@ int fv_head_backward(fv_handle* h, const float* flat_params, const float* grad_a
                      const void* saved, float* flat_grads, fv_stream s) {
   HandleScope _hs(h);
   if (!h || !grad_actions) return fv_fail(FV_ERR_ARG, "fv_head_backward: null argument");
+  if (h->hd.nb > 0) return fv_fail(FV_ERR_STATE, "fv_head_backward: a bins head trains through its own loss (fv_head_mse_backward); the decode is not differentiated");
   float* scr = nullptr;
   FV_TRY(head_scratch(h, B, "workspace too small for head backward", &scr));
   return fv::launch_head_backward(h->hd, flat_params, grad_actions, nullptr, nullptr, B, dropout_p,

@@ -300,7 +300,11 @@ int launch_attention_split_bwd(const float* qkv, int ld, const bf16_t* o_hi, con
 // keeps B rows, everything from cat on has S B.  1: the head as ever
 // prefix mode (fv_head_set_flow_prefix, flow mode only): pk = K > 0 mask columns m behind phi(t), m[k] = 1 for the k < d steps of the chunk that are given to
 // the network clean (d <= pd = D, the largest delay); `saved` also keeps the (head rows, K) byte mask the loss reads.  pk == 0: the flow head as ever
-struct HeadDims { int feat, ds, da, hid, fus; int te = 0; int draws = 1; int pk = 0; int pd = 0; };
+// bins mode (fv_head_set_bins, never together with flow mode): nb > 0 logits per action element -- action_head is (da nb, fus), the logits (head rows, da, nb)
+// are kept in `saved`, what the callers see as actions stays (head rows, da): the decoded chunk.  bn: the mode's configuration, non-null exactly when nb > 0
+struct HeadBins { const float* range; int n_range; float sigma; int decode; };   // range: device [lo | hi | w], n_range floats each; element e reads entry e % n_range
+struct HeadDims { int feat, ds, da, hid, fus; int te = 0; int draws = 1; int pk = 0; int pd = 0; int nb = 0; const HeadBins* bn = nullptr; };
+inline int head_out_width(const HeadDims& d) { return d.nb > 0 ? d.da * d.nb : d.da; }   // rows of action_head.weight
 inline int head_cat_width(const HeadDims& d) { return d.feat + d.hid + (d.te > 0 ? d.da + d.te + d.pk : 0); }
 inline int head_rows(const HeadDims& d, int B) { return d.te > 0 && d.draws > 1 ? d.draws * B : B; }
 // the 12 parameter tensors in the flat buffer's order (head_offsets; fv_head_layout's offsets[13] and Python's head_views are the same order), then the total
@@ -344,6 +348,15 @@ int launch_head_backward(const HeadDims& d, const float* P, const float* grad_ac
                          const struct HeadLoss* hl = nullptr,
                          const float* ga_scale_dev = nullptr);   // the step guard's dynamic factor (fv_train_set_step_guard): the fused loss's dL/dactions times *ga_scale_dev, one axpy launch
 size_t head_bwd_scratch_bytes(const HeadDims& d, int B);
+// ---- binned action head (bins_kernels.hip).  logits, g (n, nb) f32 with n = rows * da groups; targets (n) continuous; pad (n / (da / K)) bytes or null;
+// partial: bins_loss_partial_floats(n) floats of scratch; loss 1 float; metrics 4 floats { decoded squared error / n, valid / n, hits / valid, 0 }
+size_t bins_loss_partial_floats(long n);
+int launch_bins_loss(const HeadBins& hb, const float* logits, const float* targets, const uint8_t* pad, float* g, float* partial, float* loss, float* metrics, long n,
+                     int nb, int da, int K, float loss_scale, hipStream_t s, const float* dim_w = nullptr, const float* step_w = nullptr);
+// logits -> actions (n; null: none, probs is required then) by hb.decode, then actions * post_scale[e] + post_shift[e] (da floats each, both or neither); probs (n, nb) or null: softmax(logits) too
+int launch_bins_decode(const HeadBins& hb, const float* logits, float* actions, float* probs, long n, int nb, int da, const float* post_scale, const float* post_shift,
+                       hipStream_t s);
+__attribute__((visibility("hidden"))) float* head_saved_logits(const HeadDims& d, int B, float* saved);   // bins mode: the (head_rows(d, B), da, nb) logits inside `saved`
 // ---- flow-matching head (d.te > 0).  freq: te / 2 device floats, 2 pi / period_j.  time_dist 0: t ~ U[0, 1); 1: t = sigmoid(dist_a + dist_b n)
 // thr (prefix mode): pd + 1 device uint32, the cumulative delay distribution in units of 2^-24 (the last one is 2^24)
 // FlowTime (fv_head_set_flow_time; on == 0: the handle draws t as fv_head_set_flow says): t = t_lo + (t_hi - t_lo) F^-1(u) from the one uniform of the row.

@@ -373,6 +373,20 @@ int fv_op_chunk_loss_weighted(const float* a, const float* t, const uint8_t* pad
   return fv::launch_chunk_loss(a, t, pad, g, partial, loss, metrics, (long)n, A, kind, beta, loss_scale, static_cast<hipStream_t>(s), dim_w, step_w, K);
 }
 
+int fv_op_bins_loss(const float* logits, const float* targets, const uint8_t* pad, const float* dim_w, const float* step_w, const float* range, int n_range,
+                    float sigma, int decode, float* g, float* partial, size_t partial_floats, float* loss, float* metrics, int64_t n, int bins, int da, int K,
+                    float loss_scale, fv_stream s) {
+  if (n < 1 || partial_floats < fv::bins_loss_partial_floats((long)n)) return fv_fail(FV_ERR_ARG, "fv_op_bins_loss: partial needs 4 * ceil(n / 4) floats");
+  const fv::HeadBins hb{range, n_range, sigma, decode};
+  return fv::launch_bins_loss(hb, logits, targets, pad, g, partial, loss, metrics, (long)n, bins, da, K, loss_scale, static_cast<hipStream_t>(s), dim_w, step_w);
+}
+
+int fv_op_bins_decode(const float* logits, const float* range, int n_range, int decode, float* actions, float* probs, int64_t n, int bins, int da,
+                      const float* post_scale, const float* post_shift, fv_stream s) {
+  const fv::HeadBins hb{range, n_range, 0.f, decode};
+  return fv::launch_bins_decode(hb, logits, actions, probs, (long)n, bins, da, post_scale, post_shift, static_cast<hipStream_t>(s));
+}
+
 int fv_op_flow_vjp(int feat, int ds, int da, int hid, int fus, int time_dim, const float* freq, const float* P, const float* pooled, const float* states, int B,
                    const float* x, float t, const float* omega, float* v_out, float* jt_out, float* scratch, size_t scratch_floats, fv_stream s) {
   if (feat < 1 || ds < 1 || da < 1 || hid < 1 || fus < 1 || time_dim < 2 || time_dim % 2 || B < 1) return fv_fail(FV_ERR_ARG, "fv_op_flow_vjp: bad dimensions");

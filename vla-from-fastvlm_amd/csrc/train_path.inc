@@ -73,8 +73,8 @@ std::vector<TrainTensor> train_tensors(fv_handle* h, int64_t* total) {
                                        "action_head.weight", "action_head.bias"};
   const fv::HeadOffsets ho = fv::head_offsets(h->hd);
   const fv::HeadDims& hd = h->hd;
-  const int hrows[12] = {1, 1, hd.hid, 1, hd.fus, 1, 1, 1, hd.fus, 1, hd.da, 1};
-  const int hcols[12] = {hd.ds, hd.ds, hd.ds, hd.hid, fv::head_cat_width(hd), hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, hd.da};
+  const int hrows[12] = {1, 1, hd.hid, 1, hd.fus, 1, 1, 1, hd.fus, 1, fv::head_out_width(hd), 1};
+  const int hcols[12] = {hd.ds, hd.ds, hd.ds, hd.hid, fv::head_cat_width(hd), hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, hd.fus, fv::head_out_width(hd)};
   for (int i = 0; i < 12; ++i) {
     TrainTensor t;
     t.name = head_names[i]; t.off = ho.o[i]; t.rows = hrows[i]; t.cols = hcols[i]; t.numel = (int64_t)t.rows * t.cols; t.bucket = TB_HEAD;

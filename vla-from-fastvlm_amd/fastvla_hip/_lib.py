@@ -88,6 +88,14 @@ class HeadFlowSpec(C.Structure):    # fv_head_flow_spec: 24 bytes
 FLOW_TIME_DISTS = {"uniform": 0, "logit_normal": 1}
 
 
+class HeadBinsSpec(C.Structure):    # fv_head_bins_spec: 16 bytes
+    _fields_ = [("bins", C.c_int32), ("decode", C.c_int32), ("sigma", C.c_float), ("n_range", C.c_int32)]
+
+
+BINS_DECODES = {"argmax": 0, "mean": 1}      # FV_BINS_DECODE_*
+HEAD_BINS_MAX, HEAD_BINS_MAX_WIDTH = 1024, 32768      # FV_HEAD_BINS_MAX, FV_HEAD_BINS_MAX_WIDTH
+
+
 class HeadFlowTimeSpec(C.Structure):    # fv_head_flow_time_spec: 24 bytes
     _fields_ = [("dist", C.c_int32), ("a", C.c_float), ("b", C.c_float), ("t_lo", C.c_float), ("t_hi", C.c_float), ("stratify", C.c_int32)]
 
@@ -159,6 +167,9 @@ SIGNATURES = {
     "fv_head_set_loss_weights": (_i, [_vp, _vp, _vp]),
     "fv_head_loss_per_dim": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "fv_head_set_flow": (_i, [_vp, C.POINTER(HeadFlowSpec)]),
+    "fv_head_set_bins": (_i, [_vp, C.POINTER(HeadBinsSpec), C.POINTER(_f), C.POINTER(_f)]),
+    "fv_head_bins_logits": (_i, [_vp, _vp, _i, C.POINTER(_vp)]),
+    "fv_head_bins_probs": (_i, [_vp, _vp, _i, _vp, _vp]),
     "fv_head_set_flow_draws": (_i, [_vp, _i]),
     "fv_head_set_flow_time": (_i, [_vp, C.POINTER(HeadFlowTimeSpec)]),
     "fv_head_loss_per_time": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
@@ -268,6 +279,8 @@ OPS_SIGNATURES = {
     "fv_op_pool_norm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "fv_op_chunk_loss": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _f, _f, _vp]),
     "fv_op_chunk_loss_weighted": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _i, _f, _f, _vp]),
+    "fv_op_bins_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, C.c_size_t, _vp, _vp, _i64, _i, _i, _i, _f, _vp]),
+    "fv_op_bins_decode": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
     "fv_op_head_loss_backward": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "fv_op_head_loss_backward_draws": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "fv_op_flow_vjp": (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -118,6 +118,62 @@ def check_loss_weights(dim_w, step_w, A: int, K: int) -> Optional[dict]:
     return None if w["dim"] is None and w["step"] is None else w
 
 
+def check_head_bins(bins, range, sigma=0.0, decode="argmax", action_dim: Optional[int] = None, chunk: int = 1) -> dict:
+    """-> {"bins", "range": [[lo, hi], ...] (one pair, or one per action dimension), "sigma", "decode"} validated as fv_head_set_bins validates them; ValueError
+    for bins outside 2 .. 1024, a range that is not (lo, hi) or a list of such pairs with finite lo < hi, a negative or non-finite sigma, an unknown decode
+    name and -- with action_dim = A and chunk = K given -- a list whose length is neither 1 nor A, or K * A * bins above the head's widest output."""
+    import math
+    if isinstance(bins, bool) or not isinstance(bins, int) and not (isinstance(bins, float) and bins == int(bins)) or not 2 <= int(bins) <= _lib.HEAD_BINS_MAX:
+        raise ValueError(f"action_bins must be an integer 2 .. {_lib.HEAD_BINS_MAX}, got action_bins={bins!r} (action_head='bins')")
+    bins = int(bins)
+    try:
+        pairs = [list(range)] if len(range) == 2 and not hasattr(range[0], "__len__") else [list(p) for p in range]
+        pairs = [[float(lo), float(hi)] for lo, hi in pairs]
+    except (TypeError, ValueError):
+        raise ValueError(f"action_bins_range must be (lo, hi) or one such pair per action dimension, got action_bins_range={range!r}") from None
+    for lo, hi in pairs:
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+            raise ValueError(f"action_bins_range needs finite lo < hi in every pair, got lo={lo!r}, hi={hi!r} (action_bins_range={range!r})")
+    try:
+        sigma = float(sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"action_bins_sigma must be a finite number >= 0, got action_bins_sigma={sigma!r}") from None
+    if not (math.isfinite(sigma) and sigma >= 0.0):
+        raise ValueError(f"action_bins_sigma must be a finite number >= 0 (in units of the bin width), got action_bins_sigma={sigma!r} with action_bins={bins}")
+    key = decode.strip().lower() if isinstance(decode, str) else decode
+    if key not in _lib.BINS_DECODES:
+        raise ValueError(f"action_bins_decode must be one of {list(_lib.BINS_DECODES)}, got action_bins_decode={decode!r} (action_head='bins')")
+    if action_dim is not None:
+        A, K = int(action_dim), int(chunk)
+        if len(pairs) not in (1, A):
+            raise ValueError(f"action_bins_range must hold one (lo, hi) pair or one per action dimension: got {len(pairs)} pairs with action_dim={A}")
+        if K * A * bins > _lib.HEAD_BINS_MAX_WIDTH:
+            raise ValueError(f"chunk_size * action_dim * action_bins must not exceed {_lib.HEAD_BINS_MAX_WIDTH} (the head's linear kernels take one output per "
+                             f"block row). Got chunk_size={K}, action_dim={A}, action_bins={bins}.")
+    return dict(bins=bins, range=pairs, sigma=sigma, decode=key)
+
+
+def bins_ranges_from_stats(stats: dict, *, mode: str = "min_max", margin: float = 0.05, num_std: float = 3.0):
+    """Dataset statistics of the action (LeRobot's {"min", "max", "mean", "std"}, A values each, un-normalised) -> A (lo, hi) pairs in the NORMALISED space the
+    head works in ((a - mean) / std).  mode "min_max": the observed extremes, widened by `margin` of their span on either side; "std": +- num_std everywhere.
+    A dimension that never moves (std or span 0) gets (-1, 1)."""
+    if mode not in ("min_max", "std"):
+        raise ValueError(f"mode must be 'min_max' or 'std', got {mode!r}")
+    vec = lambda k: [float(x) for x in torch.as_tensor(stats[k], dtype=torch.float64).reshape(-1).tolist()]      # noqa: E731
+    mean, std = vec("mean"), vec("std")
+    if mode == "std":
+        return [(-float(num_std), float(num_std)) for _ in mean]
+    out = []
+    for lo, hi, m, sd in zip(vec("min"), vec("max"), mean, std):
+        if not sd > 0.0 or not hi > lo:
+            out.append((-1.0, 1.0))
+            continue
+        nlo, nhi = (lo - m) / sd, (hi - m) / sd
+        pad = float(margin) * (nhi - nlo)
+        out.append((nlo - pad, nhi + pad))
+    return out
+
+
 FLOW_DRAWS_MAX = 16          # include/fastvla_hip.h FV_FLOW_DRAWS_MAX
 FLOW_DRAW_SHIFT = 56         # draw s of a step at offset o draws at o + (s << 56): bits 56 .. 59 of a flow offset number the draws
 
@@ -224,6 +280,7 @@ class FastVLAEngine:
         self.head_loss_weights: Optional[dict] = None             # set_head_loss_weights: {"dim": A floats or None, "step": K floats or None}, None = off
         self._pad_keep: Optional[torch.Tensor] = None
         self.head_flow: Optional[dict] = None                     # set_head_flow: None = the regression head
+        self.head_bins: Optional[dict] = None                     # set_head_bins: None = no binned head
         self.head_flow_guidance: Optional[dict] = None            # set_head_flow_guidance: None = the unguided sampler only
         self.head_flow_time = None                                # set_head_flow_time: the training time's distribution beyond set_head_flow's own (None: off)
         self.head_flow_draws = 1                                  # set_head_flow_draws: noise draws per observation in the training forms
@@ -611,8 +668,8 @@ class FastVLAEngine:
         """name -> view into the flat buffer (state-dict order, each tensor 16-byte aligned)."""
         hd = self.head_dims
         shapes = [(hd["ds"],), (hd["ds"],), (hd["hid"], hd["ds"]), (hd["hid"],), (hd["fus"], self.head_cat_width()),
-                  (hd["fus"],), (hd["fus"],), (hd["fus"],), (hd["fus"], hd["fus"]), (hd["fus"],), (hd["da"], hd["fus"]),
-                  (hd["da"],)]
+                  (hd["fus"],), (hd["fus"],), (hd["fus"],), (hd["fus"], hd["fus"]), (hd["fus"],), (self.head_out_width(), hd["fus"]),
+                  (self.head_out_width(),)]
         out = {}
         for k, shp, off in zip(HEAD_KEYS, shapes, self.head_offsets):
             n = 1
@@ -626,6 +683,53 @@ class FastVLAEngine:
         hd = self.head_dims
         pk = self.head_flow_prefix["chunk"] if self.head_flow_prefix else 0
         return hd["feat"] + hd["hid"] + (hd["da"] + self.head_flow["time_dim"] + pk if self.head_flow else 0)
+
+    def head_out_width(self) -> int:
+        """rows of action_head.weight: da, in bins mode da * bins logits"""
+        return self.head_dims["da"] * (self.head_bins["bins"] if self.head_bins else 1)
+
+    # ---------------------------------------------------------------- binned action head
+    def set_head_bins(self, bins: Optional[int] = 256, range=(-3.0, 3.0), sigma: float = 0.0, decode: str = "argmax") -> None:
+        """Bins mode of the action expert (fv_head_set_bins): action_head is Linear(fusion_dim, da * bins), head_forward hands out the DECODED (B, da) chunk
+        ("argmax": the centre of the most likely bin, "mean": the mean of the centres under the softmax) and keeps the logits in `saved`; head_backward
+        evaluates the cross-entropy of the logits against the binned targets (sigma == 0: one-hot, sigma > 0: HL-Gauss with sigma bin widths).  range: one
+        (lo, hi) for every element, or n pairs with n dividing da (element e reads pair e % n), in normalised action space.  bins None switches the mode off.
+        Only before the first workspace is bound and before any train_*begin, and never together with flow mode (the library answers FV_ERR_STATE)."""
+        if bins is None:
+            _lib.check(self.lib.fv_head_set_bins(self.h, None, None, None), "fv_head_set_bins", self.h)
+            self.head_bins = None
+        else:
+            rec = check_head_bins(bins, range, sigma, decode)
+            n = len(rec["range"])
+            if self.head_dims["da"] % n:
+                raise ValueError(f"action_bins_range holds {n} pairs, which does not divide the head's action width {self.head_dims['da']}")
+            spec = _lib.HeadBinsSpec(rec["bins"], _lib.BINS_DECODES[rec["decode"]], rec["sigma"], n)
+            lo, hi = (C.c_float * n)(*[p[0] for p in rec["range"]]), (C.c_float * n)(*[p[1] for p in rec["range"]])
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.fv_head_set_bins(self.h, C.byref(spec), lo, hi), "fv_head_set_bins", self.h)
+            self.head_bins = rec
+        self._refresh_head_layout()
+
+    def _bins_saved(self, saved: torch.Tensor, B: int) -> None:
+        if self.head_bins is None:
+            raise ValueError("the head is not in bins mode (set_head_bins)")
+        if saved.numel() != self.head_saved_numel(B):
+            raise ValueError(f"saved holds {saved.numel()} floats, a head_forward of {B} rows writes {self.head_saved_numel(B)}")
+
+    def head_bins_logits(self, saved: torch.Tensor, B: int) -> torch.Tensor:
+        """-> (B, da, bins) view of the logits a bins-mode head_forward of B rows wrote into `saved` (fv_head_bins_logits)"""
+        self._bins_saved(saved, B)
+        ptr = C.c_void_p()
+        _lib.check(self.lib.fv_head_bins_logits(self.h, saved.data_ptr(), B, C.byref(ptr)), "fv_head_bins_logits", self.h)
+        off = (ptr.value - saved.data_ptr()) // 4
+        return saved[off:off + B * self.head_out_width()].view(B, self.head_dims["da"], self.head_bins["bins"])
+
+    def head_bins_probs(self, saved: torch.Tensor, B: int) -> torch.Tensor:
+        """-> (B, da, bins) f32: the softmax of every group of those logits, by the decode kernel (fv_head_bins_probs)"""
+        self._bins_saved(saved, B)
+        out = torch.empty(B, self.head_dims["da"], self.head_bins["bins"], dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.fv_head_bins_probs(self.h, saved.data_ptr(), B, out.data_ptr(), _stream()), "fv_head_bins_probs", self.h)
+        return out
 
     # ---------------------------------------------------------------- flow-matching head
     def set_head_flow(self, time_dim: Optional[int] = 64, min_period: float = 4e-3, max_period: float = 4.0, time_dist: str = "uniform",
@@ -891,10 +995,13 @@ class FastVLAEngine:
                                                       _ptr(out.get("spread")), _stream()), "fv_head_flow_sample_multi", self.h)
         return out
 
-    def head_saved(self, B: int) -> torch.Tensor:
+    def head_saved_numel(self, B: int) -> int:
         n = C.c_size_t()
         _lib.check(self.lib.fv_head_saved_bytes(self.h, B, C.byref(n)), "fv_head_saved_bytes")
-        return torch.empty(n.value // 4, dtype=torch.float32, device=self.device)
+        return n.value // 4
+
+    def head_saved(self, B: int) -> torch.Tensor:
+        return torch.empty(self.head_saved_numel(B), dtype=torch.float32, device=self.device)
 
     def head_forward(self, flat_params: torch.Tensor, pooled: torch.Tensor, states: torch.Tensor, *, training: bool = False,
                      dropout_p: float = 0.0, seed: int = 0, offset: int = 0, saved: Optional[torch.Tensor] = None,
@@ -945,7 +1052,7 @@ class FastVLAEngine:
 
     def loss_is_chunked(self, pad) -> bool:
         """whether a loss evaluation with this mask runs the chunked kernel (and writes head_loss_metrics) or the plain MSE kernel"""
-        return pad is not None or self.head_loss["kind"] != "mse" or self.head_loss_weights is not None or self.head_flow_prefix is not None
+        return pad is not None or self.head_loss["kind"] != "mse" or self.head_loss_weights is not None or self.head_flow_prefix is not None or self.head_bins is not None
 
     def set_head_loss_weights(self, dim_w=None, step_w=None) -> None:
         """Per-dimension (A = action_dim / chunk) and per-step (K = chunk) weights of the loss (fv_head_set_loss_weights): either may be None = ones, both
@@ -1031,13 +1138,14 @@ class FastVLAEngine:
             return False
 
     def head_loss_metrics(self) -> torch.Tensor:
-        """-> (2,) f32 copy of what the last chunked loss evaluation on the current stream wrote: [masked MSE, valid steps / (B * chunk)]."""
+        """-> (2,) f32 copy of what the last chunked loss evaluation on the current stream wrote: [masked MSE, valid steps / (B * chunk)].  In bins mode (3,):
+        [masked squared error of the decoded chunk, valid steps / (B * chunk), the fraction of valid elements whose most likely bin is the target's]."""
         ptr = C.c_void_p()
         _lib.check(self.lib.fv_head_loss_metrics(self.h, C.byref(ptr)), "fv_head_loss_metrics", self.h)
         # a stream-ordered device copy with the library's own y += x over the metrics' 16-byte slot (0 + m == m exactly; include/fastvla_hip.h: 4 floats, two reserved zeros)
         out = torch.zeros(4, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.fv_grad_accumulate(self.h, out.data_ptr(), ptr.value, 4, _stream()), "fv_grad_accumulate", self.h)
-        return out[:2]
+        return out[:3] if self.head_bins is not None else out[:2]
 
     def head_backward(self, flat_params: torch.Tensor, actions: torch.Tensor, targets: torch.Tensor, saved: torch.Tensor,
                       dropout_p: float = 0.0, flat_grads: Optional[torch.Tensor] = None, pad=None):

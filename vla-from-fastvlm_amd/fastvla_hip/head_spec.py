@@ -7,7 +7,8 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 # the fields an engine's head layout and workspaces are sized by, and the refusal a built engine answers a change of each with
-LAYOUT_FIELDS = (("flow", "configure_head_flow: the engine is already built (the head's layout and the workspace depend on the mode)"),
+LAYOUT_FIELDS = (("bins", "configure_head_bins: the engine is already built (the head's layout and the workspace depend on the mode)"),
+                 ("flow", "configure_head_flow: the engine is already built (the head's layout and the workspace depend on the mode)"),
                  ("prefix", "configure_head_flow_prefix: the engine is already built (the head's layout and the workspace depend on the mode)"),
                  ("draws", "configure_head_flow_draws: the engine is already built (the saved activations and the workspaces depend on the number of draws)"),
                  ("samples", "configure_head_flow_samples: the engine is already built (the sampler's rows in the workspace depend on the number of samples)"))
@@ -19,6 +20,7 @@ class HeadSpec:
     loss: dict = field(default_factory=lambda: dict(kind="mse", beta=1.0, chunk=1))      # set_head_loss' arguments: the fused loss and the chunk length K
     loss_weights: Optional[dict] = None      # {"dim", "step"} of the weighted chunk loss, None = off
     flow: Optional[dict] = None              # set_head_flow's arguments, None = the regression head
+    bins: Optional[dict] = None              # set_head_bins' arguments {"bins", "range", "sigma", "decode"}, None = no binned head
     flow_time: Optional[dict] = None         # set_head_flow_time's arguments (+ "name", the checkpoint's string), None = set_head_flow's own distribution
     prefix: Optional[dict] = None            # fastvla_hip.prefix.check_prefix_config's record, None = off
     draws: int = 1                           # set_head_flow_draws' argument, 1 = one draw per observation
@@ -28,10 +30,17 @@ class HeadSpec:
     solver_rows: bool = False                # a higher-order solver was named once: an engine is built with its two rows reserved
 
     def __post_init__(self):
-        from .engine import check_flow_draws, check_flow_solver, check_flow_time, check_head_loss, check_loss_weights
+        from .engine import check_flow_draws, check_flow_solver, check_flow_time, check_head_bins, check_head_loss, check_loss_weights
         from .prefix import check_prefix_config
         from .select import check_flow_select
         head = "regression" if self.flow is None else "flow"
+        if self.bins is not None:
+            if self.flow is not None:
+                raise ValueError("action_head='bins' and the flow head exclude each other: got both action_bins and flow settings")
+            if self.loss["kind"] != "mse":
+                raise ValueError(f"action_head='bins' trains with its own cross-entropy: action_loss must stay 'mse', got action_loss={self.loss['kind']!r}")
+            K = int(self.loss["chunk"])
+            self.bins = check_head_bins(self.bins["bins"], self.bins["range"], self.bins["sigma"], self.bins["decode"], self.dims["action_dim"] // max(K, 1), K)
         # (the spec holds the samples' count and weights, not the select name: FastVLMWithExpert checks the pair, with the name, before it builds the spec)
         check_flow_select(None if self.samples is None else self.samples["max_samples"], None, action_head=head)
         self.draws = check_flow_draws(self.draws)
@@ -60,6 +69,8 @@ class HeadSpec:
     def apply(self, engine) -> None:
         """Configure a NEW engine.  The order is a constraint of the library: flow mode first, the time distribution behind it (set_head_flow resets it);
         prefix, draws, guidance and samples before any workspace is bound; the solver twice, so that a spec switched back to Euler still reserves a higher-order solver's rows; switched-off options call nothing."""
+        if self.bins is not None:
+            engine.set_head_bins(**self.bins)
         if self.flow is not None:
             engine.set_head_flow(**self.flow)
             if self.flow_time is not None:

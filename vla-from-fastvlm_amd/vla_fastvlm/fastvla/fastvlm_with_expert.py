@@ -116,7 +116,10 @@ class FastVLMWithExpert(nn.Module):
         solver: "euler" | "midpoint" | "heun" | "rk4", the integrator of every sampling route (flow_steps are steps of it); a property of the run.
         samples = S (1 .. 16) with select "first" | "medoid" | "coherent" (fastvla_hip/select.py): every sampling route draws S candidates per
         observation in one call and returns the chosen one; "coherent" weights step k of the overlap with the previous chunk decay**k.
-        A property of the run; S = 1 calls nothing new.  The cross-field refusals are HeadSpec's (fastvla_hip/head_spec.py)."""
+        A property of the run; S = 1 calls nothing new.
+        bins = FastVLAEngine.set_head_bins' keyword arguments: the binned head -- `action_head` is Linear(fusion_dim, K * A * bins), head() returns the DECODED
+        chunk, head_loss() the cross-entropy of the logits against the binned targets beside it, action_bin_probs() the per-element distributions.
+        The cross-field refusals are HeadSpec's (fastvla_hip/head_spec.py)."""
         super().__init__()
         from fastvla_hip.head_spec import HeadSpec
         from fastvla_hip.select import check_flow_select, coherence_weights
@@ -131,15 +134,18 @@ class FastVLMWithExpert(nn.Module):
         spec = HeadSpec(dims=dict(state_dim=config.state_dim, action_dim=K * config.action_dim, hidden_dim=config.hidden_dim, fusion_dim=config.fusion_dim),
                         loss=dict(kind=o.chunk["loss"], beta=o.chunk["beta"], chunk=K), flow=None if o.flow is None else dict(o.flow),
                         flow_time=None if o.flow_time is None else dict(o.flow_time), prefix=None if o.prefix is None else dict(o.prefix), draws=o.noise_draws, solver=o.solver,
-                        samples=dict(max_samples=self.flow_samples, step_weights=self._coherence_weights) if self.flow_samples > 1 else None)
+                        samples=dict(max_samples=self.flow_samples, step_weights=self._coherence_weights) if self.flow_samples > 1 else None,
+                        bins=None if o.bins is None else dict(o.bins))
         self.config = config
         self.flow_noise_draws = spec.draws
         self.action_loss, self.action_loss_beta, self.chunk_size = spec.loss["kind"], spec.loss["beta"], spec.loss["chunk"]
         self.head_width = self.chunk_size * config.action_dim
         self.last_loss_metrics: Optional[torch.Tensor] = None    # (2,) [masked MSE, valid fraction] of the last loss the chunked kernel evaluated, else None
+                                                                 # (a binned head: (3,), + the fraction of valid elements whose most likely bin is the target's)
         self.backbone = FastVLMBackbone(config.to_backbone_config())
         self.backbone.configure_head(spec)
         self.flow, self.flow_prefix, self.flow_steps = spec.flow, spec.prefix, int(o.flow_steps)
+        self.bins = spec.bins      # the binned head's {"bins", "range", "sigma", "decode"}; None: another head
         self.flow_time = spec.flow_time      # the training time beyond set_head_flow's own distribution (flow_time_dist "beta:..." | "pi0", range, strata); None: off
         self._flow_solver = spec.solver
         self._flow_solver_rows = spec.solver_rows      # a policy built with a higher-order solver reserved their rows and may switch among all four
@@ -151,7 +157,7 @@ class FastVLMWithExpert(nn.Module):
         self.fusion = nn.Sequential(
             nn.Linear(self.backbone.output_dim + config.hidden_dim + extra, config.fusion_dim), nn.LayerNorm(config.fusion_dim),
             nn.SiLU(), nn.Dropout(config.dropout), nn.Linear(config.fusion_dim, config.fusion_dim), nn.SiLU())
-        self.action_head = nn.Linear(config.fusion_dim, self.head_width)
+        self.action_head = nn.Linear(config.fusion_dim, self.head_width * (self.bins["bins"] if self.bins else 1))
         self._flat: Optional[torch.Tensor] = None
         self._drop_seed = int(torch.initial_seed() & 0x7FFFFFFFFFFFFFFF)
         self._drop_calls = 0
@@ -227,7 +233,11 @@ class FastVLMWithExpert(nn.Module):
         self._flow_solver = name
 
     def flow_record(self) -> Optional[dict]:
-        """hip_extras.json "action_head": there only in flow mode ("solver" only when it is not Euler: an Euler run writes the record it wrote)"""
+        """hip_extras.json "action_head": there only in flow mode ("solver" only when it is not Euler: an Euler run writes the record it wrote) and for a
+        binned head ({"type": "bins", "bins", "range", "sigma", "decode"})"""
+        if self.bins is not None:
+            return {"type": "bins", "bins": int(self.bins["bins"]), "range": [[float(lo), float(hi)] for lo, hi in self.bins["range"]], "sigma": float(self.bins["sigma"]),
+                    "decode": self.bins["decode"]}
         if self.flow is None:
             return None
         from fastvla_hip import prefix as _prefix
@@ -411,6 +421,13 @@ class FastVLMWithExpert(nn.Module):
                 return self.sample_multi(pooled, states)
             seed, offset = self.flow_sample_draw()
             return self._shape_actions(self._engine().head_flow_sample(self._flat, pooled, states, steps=self.flow_steps, seed=seed, offset=offset))
+        if self.bins is not None:
+            if differentiable:
+                raise ValueError("action_head='bins' decodes its actions from the bins (argmax / mean of the centres) and the decode is not differentiated: call predict "
+                                 "/ forward under torch.no_grad(), and train through compute_loss / forward(batch) / the train step. Got action_head='bins' with "
+                                 "autograd enabled.")
+            actions, _saved = self._engine().head_forward(self._flat, pooled, states)      # (inference form: the folded action statistics behind the decode)
+            return self._shape_actions(actions)
         actions = _HeadFunction.apply(self, pooled, states, self.training, differentiable, *params)
         io = self.backbone._io_norm
         if differentiable and not self.training and io is not None:
@@ -421,6 +438,20 @@ class FastVLMWithExpert(nn.Module):
             mean = torch.as_tensor(io["action_mean"], dtype=torch.float32, device=actions.device).reshape(1, -1).repeat(1, self.chunk_size)
             actions = actions * std + mean
         return self._shape_actions(actions)
+
+    def action_bin_probs(self, pooled: torch.Tensor, states: torch.Tensor) -> torch.Tensor:
+        """-> (B, K, A, bins) on the device: the binned head's distribution over the bins of every action element (softmax of the logits, no dropout); its entropy
+        is an uncertainty signal.  No gradient."""
+        if self.bins is None:
+            raise ValueError("action_bin_probs needs action_head='bins'")
+        self.materialize(pooled.device)
+        states = states.to(pooled.device, torch.float32)
+        if states.ndim != 2 or states.shape[1] != self.config.state_dim:
+            raise ValueError(f"states must be (B,{self.config.state_dim}), got {tuple(states.shape)}")
+        with torch.no_grad():
+            eng, B = self._engine(), pooled.shape[0]
+            _actions, saved = eng.head_forward(self._flat, pooled, states)
+            return eng.head_bins_probs(saved, B).view(B, self.chunk_size, self.config.action_dim, self.bins["bins"])
 
     # ------------------------------------------------------------------ several samples per observation, one chosen on the device
     def sample_multi(self, pooled: torch.Tensor, states: torch.Tensor, *, shift: Optional[int] = None, delay: Optional[int] = None,

@@ -34,7 +34,8 @@ class FastVLAPolicy(nn.Module, EmaMixin, StepGuardMixin, FlowSurfaceMixin):
                  flow_noise_draws: Optional[int] = None, flow_prefix_max_delay: Optional[int] = None, flow_prefix_delay_dist: Optional[str] = None,
                  flow_prefix_delay_rate: Optional[float] = None, rtc_method: Optional[str] = None, rtc_prefix_steps: Optional[int] = None,
                  flow_solver: Optional[str] = None, flow_samples: Optional[int] = None, flow_select: Optional[str] = None,
-                 flow_coherence_decay: Optional[float] = None) -> None:
+                 flow_coherence_decay: Optional[float] = None, action_bins: Optional[int] = None, action_bins_range=None, action_bins_sigma: Optional[float] = None,
+                 action_bins_decode: Optional[str] = None) -> None:
         """Action chunks (an extension of this build, off by default; the core config is the reference's and has no field for them): chunk_size = K makes the
         head predict K future steps per observation -- forward / predict return (B, K, A), targets are (B, K, A) with an optional batch["action_is_pad"]
         (B, K) -- and select_action serves n_action_steps <= K of them from a queue before it runs the backbone again.  action_loss: "mse" | "l1" |
@@ -112,7 +113,22 @@ class FastVLAPolicy(nn.Module, EmaMixin, StepGuardMixin, FlowSurfaceMixin):
         policy did not learn.  policy.last_candidates (B, S, K, A, normalised), last_choice (B) and last_sample_spread (B, K, A; the candidates' standard
         deviation, an uncertainty signal) stay on the device.  The queue, n_action_steps, temporal ensembling, the solver and flow_steps work on the chosen
         chunk; action_error_per_dim stays single-sample.  A property of the run: no checkpoint or hip_extras.json key.  ValueError, before any engine exists,
-        for a regression head, S outside 1 .. 16, a select name with S = 1, "coherent" with chunk_size = 1, rtc_method="guidance" with S > 1."""
+        for a regression head, S outside 1 .. 16, a select name with S = 1, "coherent" with chunk_size = 1, rtc_method="guidance" with S > 1.
+
+        action_head="bins" (OpenVLA / RT-2 "discretised actions"; normalised action space): every action element is a classification over action_bins = Nb
+        (2 .. 1024, default 256; FASTVLA_ACTION_BINS) uniform bins of action_bins_range = (lo, hi), or one pair per action dimension (default (-3, 3);
+        FASTVLA_ACTION_BINS_RANGE="lo:hi"; fastvla_hip.engine.bins_ranges_from_stats turns dataset min / max / mean / std into per-dimension pairs).  The same
+        12 tensors, action_head.weight Nb times taller: an ARCHITECTURE property, recorded in hip_extras.json, and a checkpoint of another head type does not
+        load.  Training is the cross-entropy of the logits against the target's bin (targets clamped to the range), with the chunk mask, the loss weights and
+        the all-elements denominator of every other loss; action_bins_sigma = s > 0 (FASTVLA_ACTION_BINS_SIGMA; HL-Gauss, Farebrother et al. 2024, 0.75 is their
+        recommendation) smooths the one-hot target into a Gaussian of s bin widths integrated over the bins.  action_bins_decode "argmax" (default) | "mean"
+        (FASTVLA_ACTION_BINS_DECODE): predict / select_action / select_action_chunk return the centre of the most likely bin, or the mean of the centres under
+        the softmax; the queue, n_action_steps and temporal ensembling work on the decoded chunk.  compute_loss / forward(batch) / the train step return the
+        decoded chunk (normalised) beside the loss, and last_loss_metrics / the step's "accuracy" the fraction of valid elements whose most likely bin is the
+        target's.  action_bin_probs(batch) -> (B, K, A, Nb) on the device.  The twins are read for a bins head only.  ValueError, naming both settings and
+        before any engine exists: bins with any flow_* / rtc* option or an action_loss other than "mse", an action_bins_* option with another head, Nb outside
+        2 .. 1024, chunk_size * action_dim * Nb > 32768, lo >= hi, a range list that is neither one pair nor action_dim pairs, a negative sigma, an unknown
+        decode; predict with autograd enabled on the head raises ValueError too (the decode is not differentiated)."""
         super().__init__()
         self.config = config or FastVLAConfig()
         self.options = resolve_policy_options(      # (every option is resolved and refused here, before any engine exists)
@@ -122,7 +138,8 @@ class FastVLAPolicy(nn.Module, EmaMixin, StepGuardMixin, FlowSurfaceMixin):
             flow_time_stratify=flow_time_stratify, flow_seed=flow_seed, rtc=rtc, rtc_schedule=rtc_schedule, rtc_max_guidance_weight=rtc_max_guidance_weight, rtc_execution_horizon=rtc_execution_horizon,
             flow_noise_draws=flow_noise_draws, flow_prefix_max_delay=flow_prefix_max_delay, flow_prefix_delay_dist=flow_prefix_delay_dist,
             flow_prefix_delay_rate=flow_prefix_delay_rate, rtc_method=rtc_method, rtc_prefix_steps=rtc_prefix_steps, flow_solver=flow_solver,
-            flow_samples=flow_samples, flow_select=flow_select, flow_coherence_decay=flow_coherence_decay)
+            flow_samples=flow_samples, flow_select=flow_select, flow_coherence_decay=flow_coherence_decay, action_bins=action_bins,
+            action_bins_range=action_bins_range, action_bins_sigma=action_bins_sigma, action_bins_decode=action_bins_decode, action_dim=self.config.action_dim)
         o = self.options
         self.n_action_steps = o.chunk["n_action_steps"]
         self.temporal_ensemble_coeff: Optional[float] = o.chunk["temporal_ensemble_coeff"]
@@ -258,7 +275,10 @@ class FastVLAPolicy(nn.Module, EmaMixin, StepGuardMixin, FlowSurfaceMixin):
         tasks = self.processor.prepare_tasks(tasks, batch_size=images.shape[0])
         loss, _pred = self.model.forward_loss(images, states, tasks, batch["actions"], device=device, pad=batch.get("action_is_pad"))
         met = self.model.last_loss_metrics      # None on the plain MSE path: "mse" is then the loss itself, as ever
-        return {"loss": loss, "mse": loss.detach() if met is None else met[0]}
+        out = {"loss": loss, "mse": loss.detach() if met is None else met[0]}
+        if self.model.bins is not None:      # a binned head: the loss is a cross-entropy, "mse" the decoded chunk's masked squared error
+            out["accuracy"] = met[2]
+        return out
 
     def set_action_loss(self, kind: str, beta: float = 1.0) -> None:
         """the loss of every later compute_loss / train step: "mse" | "l1" | "smooth_l1" (beta)"""
@@ -282,6 +302,22 @@ class FastVLAPolicy(nn.Module, EmaMixin, StepGuardMixin, FlowSurfaceMixin):
         targets, pad = self.model.chunk_targets(batch["actions"], batch.get("action_is_pad"))
         pooled = self.model.features(images, tasks, device=device)
         return self.model.action_error_per_dim(pooled, states, targets, pad)
+
+    @property
+    def last_loss_metrics(self) -> Optional[torch.Tensor]:
+        """what the last compute_loss / forward(batch) left beside its loss: (2,) [masked MSE, valid fraction] from the chunked kernel, (3,) with the bin
+        accuracy behind them for a binned head, None on the plain MSE path"""
+        return self.model.last_loss_metrics
+
+    @torch.no_grad()
+    def action_bin_probs(self, batch: Dict[str, torch.Tensor | List[str]]) -> torch.Tensor:
+        """-> (B, K, A, action_bins) on the device: a binned head's distribution over the bins of every action element (its entropy is an uncertainty signal)"""
+        images, states, tasks = batch["images"], batch["states"], batch["tasks"]
+        device = images.device
+        images = self.processor.prepare_images(images, device)
+        states = self.processor.prepare_states(states, device)
+        tasks = self.processor.prepare_tasks(tasks, batch_size=images.shape[0])
+        return self.model.action_bin_probs(self.model.features(images, tasks, device=device), states)
 
     @torch.no_grad()
     def flow_loss_per_time(self, batch: Dict[str, torch.Tensor | List[str]], buckets: int = 10):
@@ -555,8 +591,10 @@ class FastVLAPolicy(nn.Module, EmaMixin, StepGuardMixin, FlowSurfaceMixin):
             eng.grad_accumulate(st["acc"], grads)
         total = st["g"] if k == 1 else st["acc"]
         actions = actions[:prep["pooled"].shape[0]]      # (flow_noise_draws > 1: every draw's rows, draw-major; the step hands out draw 0's velocity)
-        out = {"loss": loss[0], "mse": eng.head_loss_metrics()[0] if eng.loss_is_chunked(pad) else loss[0].detach(), "actions": m._shape_actions(actions),
-               "synced": sync, "next": None}
+        met = eng.head_loss_metrics() if eng.loss_is_chunked(pad) else None
+        out = {"loss": loss[0], "mse": met[0] if met is not None else loss[0].detach(), "actions": m._shape_actions(actions), "synced": sync, "next": None}
+        if m.bins is not None:
+            out["accuracy"] = met[2]
         scale = 1.0
         if sync:
             st["exchange"].group = process_group

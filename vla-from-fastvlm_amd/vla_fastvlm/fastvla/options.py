@@ -113,6 +113,47 @@ def _flag(raw: str) -> bool:
     return raw.lower() not in ("0", "false", "no", "off")
 
 
+BINS_DEFAULTS = {"bins": 256, "range": (-3.0, 3.0), "sigma": 0.0, "decode": "argmax"}
+
+
+def parse_bins_range(raw, name: str = "FASTVLA_ACTION_BINS_RANGE"):
+    """"lo:hi" -> (lo, hi) floats; ValueError for anything else (the order is check_head_bins' to refuse)"""
+    try:
+        lo, hi = (float(x) for x in str(raw).split(":"))
+    except ValueError:
+        raise ValueError(f"{name} must be written lo:hi, got {raw!r}") from None
+    return lo, hi
+
+
+def resolve_bins_options(action_bins=None, action_bins_range=None, action_bins_sigma=None, action_bins_decode=None, *, action_head: str, chunk_size: int = 1,
+                         action_loss: str = "mse", action_dim: Optional[int] = None) -> Optional[Dict]:
+    """-> FastVLAEngine.set_head_bins' keyword arguments {"bins", "range", "sigma", "decode"} for action_head == "bins", else None: explicit arguments, else the
+    FASTVLA_ACTION_BINS / FASTVLA_ACTION_BINS_RANGE ("lo:hi") / FASTVLA_ACTION_BINS_SIGMA / FASTVLA_ACTION_BINS_DECODE twins -- read for a bins head only, like
+    the FASTVLA_FLOW_* twins for flow --, else (256, (-3, 3), 0.0, "argmax").  ValueError, naming both settings and before any engine exists: an explicit
+    action_bins_* with another head, an action_loss other than "mse", and check_head_bins' refusals (action_dim, when the caller has it, for the list length
+    and the width limit)."""
+    from fastvla_hip.engine import check_head_bins
+    given = (("action_bins", action_bins), ("action_bins_range", action_bins_range), ("action_bins_sigma", action_bins_sigma), ("action_bins_decode", action_bins_decode))
+    if action_head != "bins":
+        for name, val in given:
+            if val is not None:
+                raise ValueError(f"{name} needs action_head='bins'. Got {name}={val!r}, action_head={action_head!r}.")
+        return None
+    if action_loss != "mse":
+        raise ValueError(f"action_head='bins' trains with its own cross-entropy over the bins: action_loss must stay 'mse'. Got action_loss={action_loss!r}, action_head='bins'.")
+
+    def twin(arg, env, cast, default):
+        return pick(arg, env, cast, default, error=lambda env, raw, cast: f"{env} cannot be read: got {env}={raw!r} (action_head='bins')")
+
+    bins = twin(action_bins, "FASTVLA_ACTION_BINS", int, BINS_DEFAULTS["bins"])
+    rng = twin(action_bins_range, "FASTVLA_ACTION_BINS_RANGE", parse_bins_range, BINS_DEFAULTS["range"])
+    if isinstance(rng, str):
+        rng = parse_bins_range(rng, "action_bins_range")
+    sigma = twin(action_bins_sigma, "FASTVLA_ACTION_BINS_SIGMA", float, BINS_DEFAULTS["sigma"])
+    decode = twin(action_bins_decode, "FASTVLA_ACTION_BINS_DECODE", lambda r: r.lower(), BINS_DEFAULTS["decode"])
+    return check_head_bins(bins, rng, sigma, decode, action_dim, chunk_size)
+
+
 def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, flow_time_dist=None, flow_time_range=None, flow_time_stratify=None, *,
                          flow_noise_draws: Optional[int] = None) -> Dict:
     """-> {"action_head": "regression" | "flow", "steps", "flow": FastVLAEngine.set_head_flow's keyword arguments or None}: explicit arguments, else the
@@ -127,12 +168,15 @@ def resolve_flow_options(action_head=None, flow_steps=None, flow_time_dim=None, 
     from fastvla_hip import _lib
 
     head = str(pick(action_head, "FASTVLA_ACTION_HEAD", str, "regression")).lower()
-    if head not in ("regression", "flow"):
-        raise ValueError(f"action_head must be 'regression' or 'flow', got {head!r}")
+    if head not in ("regression", "flow", "bins"):
+        raise ValueError(f"action_head must be 'regression', 'flow' or 'bins', got {head!r}")
     if head != "flow":      # the FASTVLA_FLOW_* twins are read and checked for a flow head only: a stray value cannot make a regression policy (or its load) raise
         for name, val in (("flow_time_dist", flow_time_dist), ("flow_time_range", flow_time_range), ("flow_time_stratify", flow_time_stratify)):
             if val is not None and val is not False:
-                raise ValueError(f"{name} needs action_head='flow' (the regression head draws no time). Got {name}={val!r}, action_head={head!r}.")
+                raise ValueError(f"{name} needs action_head='flow' (the {head} head draws no time). Got {name}={val!r}, action_head={head!r}.")
+        if head == "bins" and (flow_steps is not None or flow_time_dim is not None):
+            name, val = ("flow_steps", flow_steps) if flow_steps is not None else ("flow_time_dim", flow_time_dim)
+            raise ValueError(f"{name} needs action_head='flow' (the bins head integrates nothing). Got {name}={val!r}, action_head={head!r}.")
         return {"action_head": head, "steps": 10, "flow": None}
     steps, dim = pick(flow_steps, "FASTVLA_FLOW_STEPS", int, 10), pick(flow_time_dim, "FASTVLA_FLOW_TIME_DIM", int, 64)
     tdist = parse_flow_time_dist(pick(flow_time_dist, "FASTVLA_FLOW_TIME_DIST", str, "uniform"))
@@ -316,15 +360,19 @@ class PolicyOptions:
     samples: int = 1
     select: Optional[str] = None
     decay: float = 0.5
+    bins: Optional[Dict] = None      # resolve_bins_options' record (set_head_bins' keyword arguments), None = no binned head
 
 
 def resolve_policy_options(*, chunk_size=None, n_action_steps=None, action_loss=None, action_loss_beta=None, temporal_ensemble_coeff=None,
                            action_dim_weights=None, action_step_weights=None, action_head=None, flow_steps=None, flow_time_dim=None, flow_time_dist=None,
                            flow_time_range=None, flow_time_stratify=None, flow_seed=None, rtc=None, rtc_schedule=None, rtc_max_guidance_weight=None, rtc_execution_horizon=None, flow_noise_draws=None,
                            flow_prefix_max_delay=None, flow_prefix_delay_dist=None, flow_prefix_delay_rate=None, rtc_method=None, rtc_prefix_steps=None,
-                           flow_solver=None, flow_samples=None, flow_select=None, flow_coherence_decay=None) -> PolicyOptions:
+                           flow_solver=None, flow_samples=None, flow_select=None, flow_coherence_decay=None, action_bins=None, action_bins_range=None,
+                           action_bins_sigma=None, action_bins_decode=None, action_dim: Optional[int] = None) -> PolicyOptions:
     """Every option of a policy constructor, resolved and refused before any engine exists.  The resolvers run in this order -- chunk, flow, noise draws,
-    solver, prefix, rtc, samples -- and the first ValueError wins."""
+    solver, prefix, rtc, samples, bins -- and the first ValueError wins.  action_dim: the config's A, when the caller has it (the bins head's width limit and
+    per-dimension ranges are checked against it here; HeadSpec checks them again).  A bins head refuses every flow_* / rtc* option by the resolvers' own
+    "needs action_head='flow'" refusals."""
     chunk = resolve_chunk_options(chunk_size, n_action_steps, action_loss, action_loss_beta, temporal_ensemble_coeff, action_dim_weights, action_step_weights)
     K, coeff = chunk["chunk_size"], chunk["temporal_ensemble_coeff"]
     fopts = resolve_flow_options(action_head, flow_steps, flow_time_dim, flow_time_dist, flow_time_range, flow_time_stratify)
@@ -339,7 +387,16 @@ def resolve_policy_options(*, chunk_size=None, n_action_steps=None, action_loss=
                                 prefix=prefix)
     sopts = resolve_flow_samples(flow_samples, flow_select, flow_coherence_decay, action_head=head, chunk_size=K,
                                  rtc_method=None if ropts is None else ropts.get("method", "guidance"))
-    return PolicyOptions(chunk=chunk, action_head=head, flow=fopts["flow"], flow_time=fopts.get("time"), flow_steps=fopts["steps"], flow_seed=flow_seed, noise_draws=draws, solver=solver,
+    if head == "bins":      # the options whose resolvers let an explicit value pass for a head that is not flow
+        for name, val in (("flow_seed", flow_seed), ("flow_noise_draws", flow_noise_draws), ("flow_prefix_max_delay", flow_prefix_max_delay), ("flow_select", flow_select),
+                          ("flow_samples", flow_samples), ("rtc_method", rtc_method), ("rtc_schedule", rtc_schedule), ("rtc_max_guidance_weight", rtc_max_guidance_weight),
+                          ("rtc_execution_horizon", rtc_execution_horizon), ("rtc_prefix_steps", rtc_prefix_steps), ("flow_prefix_delay_dist", flow_prefix_delay_dist),
+                          ("flow_prefix_delay_rate", flow_prefix_delay_rate), ("rtc", rtc)):
+            if val is not None and val is not False:
+                raise ValueError(f"{name} needs action_head='flow' (the bins head samples nothing). Got {name}={val!r}, action_head='bins'.")
+    bins = resolve_bins_options(action_bins, action_bins_range, action_bins_sigma, action_bins_decode, action_head=head, chunk_size=K, action_loss=chunk["loss"],
+                                action_dim=action_dim)
+    return PolicyOptions(bins=bins, chunk=chunk, action_head=head, flow=fopts["flow"], flow_time=fopts.get("time"), flow_steps=fopts["steps"], flow_seed=flow_seed, noise_draws=draws, solver=solver,
                          prefix=prefix, rtc=ropts, samples=sopts["samples"], select=sopts["select"], decay=sopts["decay"])
 
 

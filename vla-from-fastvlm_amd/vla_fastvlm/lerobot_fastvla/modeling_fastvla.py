@@ -25,7 +25,12 @@ policy.flow_solver switches among all four on a policy built with a higher-order
 Several samples per observation (no config field): FastVLAPolicy(config, action_head="flow", flow_samples=S, flow_select="medoid" | "coherent" | "first",
 flow_coherence_decay=) or the FASTVLA_FLOW_SAMPLES / FASTVLA_FLOW_SELECT / FASTVLA_FLOW_COHERENCE_DECAY twins: predict_action_chunk(batch, num_samples=) and
 select_action draw S candidates per environment in one sampler call and return the one chosen on the device; last_candidates, last_choice and
-last_sample_spread stay on the device."""
+last_sample_spread stay on the device.
+
+Binned actions (no config field): FastVLAPolicy(config, action_head="bins", action_bins=, action_bins_range=, action_bins_sigma=, action_bins_decode=) or the
+FASTVLA_ACTION_BINS* twins: forward(batch) trains the cross-entropy over the bins and reports {"loss", "mse", "accuracy"}, predict_action_chunk and
+select_action return decoded chunks, action_bin_probs(batch) the (B, K, A, bins) distributions.  A torch optimiser sees the taller action_head through
+forward(batch)'s gradients like any other head tensor."""
 from __future__ import annotations
 
 from collections import deque
@@ -60,7 +65,7 @@ class FastVLAPolicy(PreTrainedPolicy, FlowSurfaceMixin):
         # policy's docstring has their semantics.  Unknown keywords are ignored; the loss kind comes from its twins (or set_action_loss) only
         given = {k: v for k, v in kwargs.items() if k in POLICY_KEYWORDS}
         self.options = o = resolve_policy_options(**{**given, "chunk_size": config.chunk_size, "n_action_steps": config.n_action_steps, "action_loss": None,
-                                                     "action_loss_beta": None})
+                                                     "action_loss_beta": None, "action_dim": config.action_dim})
         self.temporal_ensemble_coeff = o.chunk["temporal_ensemble_coeff"]
         self.action_head, self.flow_noise_draws, self.flow_prefix, self.rtc = o.action_head, o.noise_draws, o.prefix, o.rtc
         self.flow_samples, self.flow_select = o.samples, o.select
@@ -85,6 +90,12 @@ class FastVLAPolicy(PreTrainedPolicy, FlowSurfaceMixin):
         targets, pad = self.model.chunk_targets(batch[ACTION], pad)
         pooled = self.model.features(images, tasks, device=images.device)
         return self.model.action_error_per_dim(pooled, states, targets, pad)
+
+    @torch.no_grad()
+    def action_bin_probs(self, batch: dict[str, Tensor]) -> Tensor:
+        """-> (B, K, A, action_bins) on the device: a binned head's distribution over the bins of every action element"""
+        images, states, tasks = self._prepare_inputs(batch)
+        return self.model.action_bin_probs(self.model.features(images, tasks, device=images.device), states)
 
     def flow_loss_per_time(self, batch: dict[str, Tensor], buckets: int = 10):
         """-> (mse, count), each (buckets,) on the device: the flow head's velocity error by time bucket over the batch's non-padded steps (normalised space,
@@ -261,4 +272,7 @@ class FastVLAPolicy(PreTrainedPolicy, FlowSurfaceMixin):
         loss, _pred = self.model.forward_loss(images, states, tasks, batch[ACTION], device=images.device, pad=pad)
         val = loss.item()
         met = self.model.last_loss_metrics      # the chunked loss kernel's masked MSE; None on the plain MSE path, where the loss IS the MSE
-        return loss, {"loss": val, "mse": val if met is None else met[0].item()}
+        info = {"loss": val, "mse": val if met is None else met[0].item()}
+        if self.model.bins is not None:      # a binned head: the loss is a cross-entropy, "mse" the decoded chunk's, and the bin accuracy joins them
+            info["accuracy"] = met[2].item()
+        return loss, info

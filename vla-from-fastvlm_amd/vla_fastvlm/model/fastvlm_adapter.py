@@ -287,6 +287,8 @@ class FastVLMBackbone(nn.Module):
         evaluates (FastVLAEngine.set_head_loss).  A new chunk length drops the loss weights (sized for the previous one) and re-tiles the folded statistics."""
         from fastvla_hip.engine import check_head_loss
         kind, beta, chunk = check_head_loss(kind, beta, chunk, self.head_spec.dims["action_dim"])
+        if self.head_spec.bins is not None and kind != "mse":
+            raise ValueError(f"action_head='bins' trains with its own cross-entropy over the bins: action_loss must stay 'mse', got action_loss={kind!r}")
         rechunk = chunk != self.head_spec.loss["chunk"]
         # (a copy with the field assigned, not replace(): this setter checks the loss alone -- what else hangs on the chunk length, a prefix, is the
         # engine's to refuse; a spec the caller still holds stays as it was)

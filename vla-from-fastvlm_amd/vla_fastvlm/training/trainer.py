@@ -299,7 +299,7 @@ class Trainer:
             have = read_extras(p).get("action_chunk") or {}
             if int(have.get("chunk_size", 1)) != core.chunk_size:
                 raise ValueError(f"{p}: the checkpoint records chunk_size={have.get('chunk_size', 1)}, this run's policy was built with chunk_size={core.chunk_size}")
-            check_head_width(state, core.config.action_dim, have, p)
+            check_head_width(state, core.config.action_dim, have, p, read_extras(p).get("action_head"))
             was, now = (have.get("loss", "mse"), float(have.get("beta", 1.0))), (core.action_loss, float(core.action_loss_beta))
             if was != now:      # legitimate (the loss is the caller's choice), but never silent
                 import warnings
@@ -310,8 +310,9 @@ class Trainer:
                 import warnings
                 warnings.warn(f"{p}: the checkpointed run trained with action loss weights dim={was[0]} step={was[1]}, this run uses dim={now[0]} step={now[1]}")
         if hasattr(core, "flow_record"):     # flow against regression head: named, not a shape error; a flow run continues the checkpointed run's noise stream
-            from ..utils.checkpoint import check_fusion_width
+            from ..utils.checkpoint import check_action_head_shape, check_fusion_width
             check_fusion_width(state, self.model, p)
+            check_action_head_shape(state, self.model, p)
             frec = read_extras(p).get("action_head") or {}
             if core.flow is not None and frec.get("seed") is not None:
                 core._flow_seed = int(frec["seed"])      # (the offsets are functions of the optimiser step, which optimizer.pt restores)

@@ -334,8 +334,10 @@ class UnfrozenState:
             else:
                 eng.grad_accumulate(self.acc, total)
             total = self.acc
-        out = {"loss": loss[0], "mse": eng.head_loss_metrics()[0] if eng.loss_is_chunked(prep.get("pad")) else loss[0].detach(),
-               "actions": m._shape_actions(actions), "synced": sync, "next": None}
+        met = eng.head_loss_metrics() if eng.loss_is_chunked(prep.get("pad")) else None
+        out = {"loss": loss[0], "mse": met[0] if met is not None else loss[0].detach(), "actions": m._shape_actions(actions), "synced": sync, "next": None}
+        if getattr(m, "bins", None) is not None:      # a binned head: the fraction of valid elements whose most likely bin is the target's
+            out["accuracy"] = met[2]
         if sync:
             if overlap:
                 scale = self.bucketed.finish(eng.device)

@@ -39,6 +39,8 @@ EXTRAS_FILE = "hip_extras.json"
 # (FastVLAPolicy(action_head="flow")), whose fusion.0.weight is chunk_size * action_dim + time_dim columns wider than the regression head's
 # (+ "prefix_max_delay", and "prefix_delay_dist" / "prefix_delay_rate" for information -- only for a head with action-prefix conditioning
 # (flow_prefix_max_delay), whose fusion.0.weight has chunk_size more columns still)
+# "action_head" = {"type": "bins", "bins", "range" (a list of [lo, hi] pairs: one, or one per action dimension), "sigma", "decode"} -- only for a binned head
+# (FastVLAPolicy(action_head="bins")), whose action_head.weight has `bins` times the rows of the regression head's
 LORA_FILE = "lora_adapters.pt"
 SPLICE_KEY_MARK = ".splice_image_tokens"
 
@@ -96,13 +98,25 @@ def check_resume_ema(recorded, current) -> None:
 EMA_SUFFIX = "-ema"
 
 
-def check_head_width(state: dict, action_dim: int, chunk: dict, where="") -> None:
-    """the action head of the file against what policy_config.json and the extras record say: a wide head without a record does not load"""
+def check_head_width(state: dict, action_dim: int, chunk: dict, where="", head: dict | None = None) -> None:
+    """the action head of the file against what policy_config.json and the extras records say: a wide head without a record does not load.  head: the file's
+    "action_head" record (a binned head is `bins` times taller)"""
     w = state.get("model.action_head.weight")
-    want = int((chunk or {}).get("chunk_size", 1)) * int(action_dim)
+    bins = int(head["bins"]) if head and head.get("type") == "bins" else 1
+    want = int((chunk or {}).get("chunk_size", 1)) * int(action_dim) * bins
     if w is not None and w.shape[0] != want:
         raise ValueError(f"{where}: model.action_head.weight is {tuple(w.shape)}, but action_dim={action_dim} with "
-                         f"{'chunk_size=' + str(chunk['chunk_size']) if chunk else 'no action_chunk record in ' + EXTRAS_FILE} asks for ({want}, {w.shape[1]})")
+                         f"{'chunk_size=' + str(chunk['chunk_size']) if chunk else 'no action_chunk record in ' + EXTRAS_FILE}"
+                         f"{' and bins=' + str(bins) if bins > 1 else ''} asks for ({want}, {w.shape[1]})")
+
+
+def check_action_head_shape(state: dict, policy, where="") -> None:
+    """action_head.weight of the file against the policy's head: a binned checkpoint does not load into a regression or flow policy, nor the reverse"""
+    w, own = state.get("model.action_head.weight"), policy.model.action_head.weight
+    if w is not None and tuple(w.shape) != tuple(own.shape):
+        raise ValueError(f"{where}: model.action_head.weight is {tuple(w.shape)} in the checkpoint and {tuple(own.shape)} in this policy, which was built with "
+                         f"action_head='{getattr(policy, 'action_head', 'regression')}': a binned head's action_head has action_bins rows per action element -- "
+                         f"build the policy with the action_head setting (action_bins, chunk_size) the checkpoint was trained with")
 
 
 def check_fusion_width(state: dict, policy, where="") -> None:
@@ -127,7 +141,7 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
     config = FastVLAConfig(**payload)
     state = torch.load(sd_path, map_location="cpu")
     chunk = read_extras(root).get("action_chunk") or {}
-    check_head_width(state, config.action_dim, chunk, root)
+    check_head_width(state, config.action_dim, chunk, root, read_extras(root).get("action_head"))
     head_kw = strata_need_draws(flow_kwargs(read_extras(root).get("action_head")))
     # the file decides: no record means the record's defaults (1, 1, "mse", 1.0), whatever the environment twins say -- a plain checkpoint loads as a plain policy
     policy = FastVLAPolicy(config, chunk_size=int(chunk.get("chunk_size", 1)), n_action_steps=int(chunk.get("n_action_steps", 1)),
@@ -136,6 +150,7 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
                            action_step_weights=chunk.get("step_weights", False),      # (False: off, whatever the twin says)
                            **head_kw, **prefix_kwargs(read_extras(root).get("action_head")))
     check_fusion_width(state, policy, root)
+    check_action_head_shape(state, policy, root)
     vlm = {k[len(BACKBONE_PREFIX):]: v for k, v in state.items() if k.startswith(BACKBONE_PREFIX)}
     if vlm:
         policy.model.backbone.load_backbone_state(vlm)
@@ -156,6 +171,9 @@ def load_policy_from_checkpoint(checkpoint_dir: str, device: torch.device | None
 
 def flow_kwargs(rec) -> dict:
     """FastVLAPolicy's action-head arguments from a checkpoint's "action_head" record; no record: the regression head, whatever the twins say"""
+    if rec and rec.get("type") == "bins":      # (the file decides here too: every action_bins_* argument is explicit, so no twin is read)
+        return {"action_head": "bins", "action_bins": int(rec["bins"]), "action_bins_range": [tuple(float(x) for x in p) for p in rec["range"]],
+                "action_bins_sigma": float(rec.get("sigma", 0.0)), "action_bins_decode": str(rec.get("decode", "argmax"))}
     if not rec or rec.get("type") != "flow":
         return {"action_head": "regression"}
     # the embedding's periods and the time distribution's parameters are constants of this build: a record written with others would load into another network
