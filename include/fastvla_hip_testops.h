@@ -66,6 +66,18 @@ int fv_op_gemm_splitk(const void* A, int lda, const void* W, int M, int N, int K
 int fv_op_gemm_norm(const void* A, int lda, const void* W, int M, int N, int K, const float* bias, const float* scale, const void* res, int ldr, void* out,
                     int ldo, int epilogue, int ksplit, void* ws, size_t ws_bytes, int few_rows, const float* norm_w, void* norm_y, void* norm_ylo, int norm_ld,
                     float norm_eps, fv_stream s);
+/* What launch_gemm would do with a problem on a device of `cus` compute units, without launching anything (the library's plan_gemm: it reads no memory, so the
+ * operands are given as presence flags; ws_bytes = the split-K scratch, 0: none; ksplit 0 / 1 / 2 = one operand, [hi | lo], hi + lo8).  Writes one launch to
+ * out[0], or two where the tail is cut off (columns [c0, c1) each), and returns their number -- or the refusal's code (negative), with out untouched.  The names
+ * are those of tests/gemm_util.py: "gemm256_kernel<8,4,ASYM>", "splitk_reduce_kernel" ("" = one pass). */
+typedef struct fv_gemm_plan_launch {
+  char kernel[40], reducer[40];
+  int tile, tiles_m, group_m, splits, npad, grid;
+  int norm;    /* the RMSNorm that follows: 0 not asked, 1 fused into the reducer, 2 a launch of its own */
+  int c0, c1;
+} fv_gemm_plan_launch;
+int fv_op_gemm_plan(int M, int N, int K, int lda, int ldw, int ldo, int ldr, int epilogue, int ksplit, int f16, int tn, int few_rows, int cus, size_t ws_bytes,
+                    int has_bias, int has_scale, int has_res, int has_stash, int has_norm, int has_w8, fv_gemm_plan_launch* out);
 /* depthwise / channel-multiplier grouped conv, NHWC bf16: x (B,H,W,C) -> y (B,Ho,Wo,C*mult); w f32 [k*k][C*mult] */
 int fv_op_dwconv(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int k,
                  int stride, int mult, int gelu, fv_stream s);

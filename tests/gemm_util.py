@@ -1,6 +1,7 @@
 """CPU-only helpers of the dense-GEMM suites (tests/test_gemm_reference_host.py, tests/test_gpu_gemm.py): a mirror of launch_gemm's dispatch for the product
-build (csrc/gemm_bf16.hip: launch_gemm, launch_gemm_core, launch_gemm_tn, gemm_glds_tile, pick_group_m, launch_splitk_reduce -- every fv_ab_env switch is
-absent there), the case list both files share, the three input classes (exact, selection, Gaussian), their checks, and float32 / bf16 emulations of a small
+build (csrc/gemm_bf16.hip: plan_gemm, i.e. check_gemm, tail_cut, route_gemm and their helpers gemm_glds_tile, set_walk, k_ranges, few_row_ranges, set_ranges --
+every FASTVLA_* switch of its Tuning is at its default there), library_route, which asks the library's own plan_gemm through fv_op_gemm_plan so that the two can
+be compared field for field, the case list both files share, the three input classes (exact, selection, Gaussian), their checks, and float32 / bf16 emulations of a small
 GEMM with defects to plant."""
 import math
 
@@ -18,6 +19,7 @@ CUS = 256                      # the MI355X; the GPU file asks the device
 
 # ------------------------------------------------------------------------------------------------ the route mirror
 def pick_group_m(tiles_m_total, want):
+    """set_walk's group height"""
     if want >= 4 and tiles_m_total % 4 == 0:
         return 4
     if want >= 2 and tiles_m_total % 2 == 0:
@@ -68,7 +70,7 @@ def _staged_name(bm, f16=False, lo8=False):
 
 
 def _reducer(epi, norm, few_rows_form, few_rows, N, lo8):
-    """launch_splitk_reduce: (kernel, the RMSNorm went with it)"""
+    """set_ranges: (kernel, the RMSNorm went with it)"""
     if epi == SWIGLU_SPLIT:
         return "splitk_reduce_swiglu_kernel", False
     if epi in (BIAS, GELU, LS_RES):
@@ -104,24 +106,47 @@ def refused(r):
     return isinstance(r, dict) and "refused" in r
 
 
+def _strides(M, N, K, lda, ldo, ldr, ldw, epi, ksplit, tn):
+    """the row strides a call leaves out: tight ones"""
+    ncols = N // 2 if epi in (SWIGLU, SWIGLU_F16) else N
+    return (lda if lda is not None else (M if tn else (2 * K if ksplit else K)), ldo if ldo is not None else ncols, ldr if ldr is not None else N,
+            ldw if ldw is not None else (N if tn else 0))
+
+
+def library_route(L, M, N, K, lda=None, ldo=None, epi=BIAS, ksplit=0, f16=False, tn=False, bias=False, scratch=0, few_rows=1, norm=False, cus=CUS, ldw=None,
+                  ldr=None, res=True, scale=True, stash=False):
+    """gemm_route's arguments, answered by the library itself: fv_op_gemm_plan (plan_gemm, what launch_gemm runs) in gemm_route's form.  L: the loaded test-ops
+    library.  The weights' fp8 copy is present whenever ksplit == 2."""
+    from fastvla_hip._lib import GemmPlanLaunch
+    lda, ldo, ldr, ldw = _strides(M, N, K, lda, ldo, ldr, ldw, epi, ksplit, tn)
+    out = (GemmPlanLaunch * 2)()
+    n = L.fv_op_gemm_plan(M, N, K, lda, ldw, ldo, ldr, epi, ksplit, int(f16), int(tn), few_rows, cus, scratch, int(bool(bias)), int(bool(scale)), int(bool(res)),
+                          int(bool(stash)), int(bool(norm)), int(ksplit == 2), out)
+    if n <= 0:
+        return {"refused": (L.fv_last_error(None) or b"?").decode()}
+    routes = []
+    for x in out[:n]:
+        kernel = x.kernel.decode()
+        walk = None if not kernel.startswith("gemm256") else "column-major" if x.tiles_m else f"group_m {x.group_m}" if x.group_m else "row-major"
+        routes.append(_route(kernel, x.tile, M, N, x.splits, x.npad, x.grid, x.reducer.decode() or None, walk, x.tiles_m, x.group_m,
+                             {0: None, 1: "fused", 2: "separate"}[x.norm], (x.c0, x.c1) if n == 2 else None))
+    return routes if n == 2 else routes[0]
+
+
 def gemm_route(M, N, K, lda=None, ldo=None, epi=BIAS, ksplit=0, f16=False, tn=False, bias=False, scratch=0, few_rows=1, norm=False, cus=CUS, ldw=None,
                ldr=None, res=True, scale=True, stash=False, no_tail=False, _cols=None):
     """What launch_gemm does with the problem in the product build: a route (dict), a LIST of two routes where the tail is cut off as a K-range problem of its
     own, or {"refused": why}.  scratch = the scratch buffer's bytes (0: none).  res / scale / stash: whether the caller hands the pointer in.  Pointer
     alignment is the one refusal this mirror cannot see."""
-    Kt = K * (2 if ksplit == 1 else 1)
-    lda = lda if lda is not None else (M if tn else (2 * K if ksplit else K))
     f32out = epi in F32_EPIS
     swiglu = epi in (SWIGLU, SWIGLU_SPLIT, SWIGLU_F16)
     ncols = N // 2 if epi in (SWIGLU, SWIGLU_F16) else N
-    ldo = ldo if ldo is not None else ncols
-    ldr = ldr if ldr is not None else N
+    lda, ldo, ldr, ldw = _strides(M, N, K, lda, ldo, ldr, ldw, epi, ksplit, tn)
     if norm and (not f32out or ldo != N or N % 8):
         return {"refused": "fused norm needs an fp32 epilogue, ldo == N and N % 8 == 0"}
     if M <= 0 or N <= 0 or K <= 0:
         return {"refused": "empty shape"}
     if tn:
-        ldw = ldw if ldw is not None else N
         if not f32out or ksplit or norm or stash:
             return {"refused": "TN: fp32 epilogues only, no ksplit / fused norm / stash"}
         if K % 64 or M % 8 or N % 8 or lda % 8 or ldw % 8 or lda < M or ldw < N:
@@ -264,7 +289,7 @@ REACHABLE = ["gemm_kernel<64>", "gemm_kernel<64,F16>", "gemm_kernel<64,LO8>", "g
              "gemm256_kernel<4,2>", "gemm256_kernel<4,2,LO8>", "gemm256_kernel<8,4,TN>", "gemm256_kernel<8,4,F16,TN>", "pwconv_kernel<96>", "pwconv_kernel<192>"]
 REDUCERS = ["splitk_reduce_kernel", "splitk_reduce_norm_kernel", "splitk_reduce_norm_row_kernel", "splitk_reduce_bf16_kernel", "splitk_reduce_swiglu_kernel"]
 WALKS = ["column-major", "row-major", "group_m 4", "group_m 2"]
-# compiled (launch_gemm_core names them) but not reachable in the product build, and why
+# compiled (gemm_bf16.hip's instance table names them) but not reachable in the product build, and why
 UNREACHABLE = {
     "gemm256_kernel<4,2,F16>": "gemm_glds_tile returns 0 for fp16 operands before its 128-tile rule; FASTVLA_F16_TILE128, which returns 128 earlier, is a tools-build "
                                "switch (fv_ab_env is a constant nullptr in the product build)",
@@ -304,10 +329,18 @@ class Case:
     def ldr(self):
         return self.N + self.pad
 
+    def route_args(self, epi, cus=CUS, scratch=None, bias=True):
+        """the launch as gemm_route's (and library_route's) keyword arguments"""
+        return dict(M=self.M, N=self.N, K=self.K, lda=self.lda, ldo=self.ldo(epi), epi=epi, ksplit=self.ksplit, f16=self.f16, tn=self.tn,
+                    bias=bias and epi not in (SWIGLU, SWIGLU_SPLIT, SWIGLU_F16), scratch=self.scratch if scratch is None else scratch,
+                    few_rows=self.few_rows, norm=self.norm, cus=cus, ldw=self.ldw, ldr=self.ldr())
+
     def route(self, epi, cus=CUS, scratch=None, bias=True):
-        return gemm_route(self.M, self.N, self.K, lda=self.lda, ldo=self.ldo(epi), epi=epi, ksplit=self.ksplit, f16=self.f16, tn=self.tn,
-                          bias=bias and epi not in (SWIGLU, SWIGLU_SPLIT, SWIGLU_F16), scratch=self.scratch if scratch is None else scratch,
-                          few_rows=self.few_rows, norm=self.norm, cus=cus, ldw=self.ldw, ldr=self.ldr())
+        return gemm_route(**self.route_args(epi, cus, scratch, bias))
+
+    def launch_args(self, epi, cus=CUS, scratch=None, bias=True):
+        """route_args with the residual and the scale present where the GPU file's launch hands them in (_epilogue_inputs, selection_problem)"""
+        return dict(self.route_args(epi, cus, scratch, bias), res=epi in (LS_RES, RES_F32, MUL_AUX) and not self.tn, scale=epi == LS_RES)
 
     def __repr__(self):
         return self.name
@@ -414,7 +447,7 @@ def covered_reducer_epilogues(cus=CUS):
 
 # What every instance's own epilogue code admits AND an op-level entry point can express: the CPU file asserts that the case list runs exactly these.
 _BF16_OPS = {BIAS, GELU, LS_RES, RES_F32, F32, SWIGLU_SPLIT, SWIGLU_F16, F16, MUL_AUX}
-_F16_OPS = {BIAS, RES_F32, F32, SWIGLU_SPLIT, SWIGLU_F16, F16, MUL_AUX}                    # launch_gemm_core refuses GELU, LS_RES, SWIGLU with fp16 operands
+_F16_OPS = {BIAS, RES_F32, F32, SWIGLU_SPLIT, SWIGLU_F16, F16, MUL_AUX}                    # check_gemm refuses GELU, LS_RES, SWIGLU with fp16 operands
 _LO8_OPS = {BIAS, GELU, RES_F32, F32}
 EPILOGUES = {
     "gemm_kernel<64>": _BF16_OPS | {SWIGLU}, "gemm_kernel<128>": _BF16_OPS | {SWIGLU},     # plain SWIGLU: the register-staged kernel only (gemm_glds_tile returns 0)
@@ -457,7 +490,7 @@ def covered(cus=CUS):
 
 
 # launches that must be refused: (what, keyword arguments of gemm_route); the GPU file sends the same launch and expects a non-zero code and an untouched output.
-# (A misaligned pointer is the one refusal the mirror cannot see: the GPU file adds it by hand.  "TN with a non-fp32 epilogue" is refused by launch_gemm_tn, but
+# (A misaligned pointer is the one refusal the mirror cannot see: the GPU file adds it by hand.  "TN with a non-fp32 epilogue" is refused by check_gemm, but
 # fv_op_gemm_tn always passes FV_EPI_F32: no entry point can send it.)
 REFUSED = [
     ("K % 8", dict(M=64, N=64, K=68, lda=72, epi=BIAS)),

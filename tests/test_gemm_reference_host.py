@@ -1,5 +1,6 @@
 """CPU: the dense-GEMM suite's own machinery (tests/gemm_util.py) -- the route mirror on both sides of every threshold of launch_gemm, the case list's
-coverage of every reachable kernel instance and reducer, the exact class's budget, and proof that the new checks fail on broken arithmetic that the old
+coverage of every reachable kernel instance and reducer, the mirror against the library's own planner (fv_op_gemm_plan: the case list at three CU counts, the
+threshold shapes, the refusals, a seeded sweep), the exact class's budget, and proof that the new checks fail on broken arithmetic that the old
 rel-L2 / max-abs bar lets through.  tests/test_gpu_gemm.py runs the same cases and checks on the device."""
 import torch
 
@@ -125,6 +126,99 @@ def test_the_fused_norm_placement():
     assert n(M=4096, N=896, K=2432)["norm"] == "separate" and n(M=4096, N=896, K=2432, scratch=BIG)["norm"] == "fused"
 
 
+# ------------------------------------------------------------------------------------------------ the mirror against the library's planner
+# fv_op_gemm_plan answers with plan_gemm, the function launch_gemm runs: it makes no HIP call and reads no operand, so the comparison needs no device.
+def _agree(what, **kw):
+    """the mirror's route, after the library's planner has given the same one field for field (or both have refused)"""
+    from fastvla_hip import _lib
+    want, got = G.gemm_route(**kw), G.library_route(_lib.load_testops(), **kw)
+    if G.refused(want) or G.refused(got):
+        assert G.refused(want) and G.refused(got), f"{what} {kw}: plan_gemm says {describe(got)}, the mirror {describe(want)}"
+    else:
+        assert got == want, f"{what} {kw}: plan_gemm says {describe(got)} {got}, the mirror {describe(want)} {want}"
+    return want
+
+
+OTHER_CUS = (64, 304)         # with the present cases both move a threshold: asserted below
+
+
+def test_the_library_plans_every_case_as_the_mirror():
+    moved = {cus: 0 for cus in OTHER_CUS}
+    for c in CASES:
+        for epi in sorted(set(c.epis) | set(c.gauss)):
+            for scratch in (c.scratch or 64 << 20, 0):
+                at256 = _agree(c.name, **c.route_args(epi, G.CUS, scratch))
+                for cus in OTHER_CUS:
+                    moved[cus] += route_key(_agree(c.name, **c.route_args(epi, cus, scratch))) != route_key(at256)
+            assert not G.refused(c.route(epi))
+    assert all(moved.values()), moved
+
+
+def test_the_library_refuses_what_the_mirror_refuses():
+    for what, kw in G.REFUSED:
+        assert G.refused(_agree(what, **kw)), what
+
+
+def test_the_library_agrees_on_both_sides_of_every_threshold(monkeypatch):
+    """The threshold tests above, run again with every problem they put to the mirror also put to plan_gemm (a glds_tile question as the launch without scratch)."""
+    import sys
+    asked, mirror_tile, busy = [], G.glds_tile, []
+
+    def route(**kw):
+        asked.append(kw)
+        busy.append(1)
+        try:
+            return _agree("threshold", **kw)
+        finally:
+            busy.pop()
+
+    def tile(M, N, K, lda, epi, f16=False, bias=False):
+        if not busy:                                      # (gemm_route asks glds_tile itself)
+            route(M=M, N=N, K=K, lda=lda, epi=epi, f16=f16, bias=bias)
+        return mirror_tile(M, N, K, lda, epi, f16, bias)
+
+    monkeypatch.setattr(sys.modules[__name__], "gemm_route", route)      # what the threshold tests call; _agree asks G.gemm_route
+    monkeypatch.setattr(G, "glds_tile", tile)
+    for test in (test_glds_tile_thresholds, test_register_staged_rows_and_pointwise, test_walks_and_asym, test_k_range_rules, test_the_tail_cut,
+                 test_the_fused_norm_placement):
+        test()
+    assert len(asked) >= 100, len(asked)                  # (113 when this was written: the patches took hold)
+
+
+SWEEP_M = (8, 64, 77, 136, 256, 320, 384, 512, 1024, 2048, 4096, 4104, 8192, 10240, 16384, 65536)
+SWEEP_N = (96, 136, 144, 192, 256, 512, 896, 1024, 1152, 1536, 2048, 4864, 9728, 17920, 37888)
+SWEEP_K = (72, 96, 128, 192, 360, 512, 896, 1024, 1536, 2048, 3584, 4864)
+
+
+def sweep_problems(n=6000, seed=1):
+    import random
+    rnd = random.Random(seed)
+    for _ in range(n):
+        yield dict(M=rnd.choice(SWEEP_M), N=rnd.choice(SWEEP_N), K=rnd.choice(SWEEP_K), epi=rnd.choice(sorted(G.EPI_NAME)),
+                   ksplit=rnd.choice((0, 1, 2)) if rnd.random() < 0.5 else 0, f16=rnd.random() < 0.15, tn=rnd.random() < 0.10,
+                   scratch=rnd.choice((0, 64 << 20, 512 << 20)), few_rows=rnd.choice((0, 1)), norm=rnd.random() < 0.15, cus=rnd.choice((G.CUS,) + OTHER_CUS),
+                   bias=rnd.random() < 0.5)
+
+
+def test_the_library_agrees_with_the_mirror_on_a_sweep():
+    """6000 seeded problems (tight strides), refusals included.  With this seed the mirror admits 3440 of them (57 %), cuts the tail off twice and reaches every
+    reachable instance (the two pointwise ones twice each) and every reducer; the three conditions below keep the sweep from passing by refusing."""
+    kernels, reducers, admitted, tails = {}, {}, 0, 0
+    for kw in sweep_problems():
+        r = _agree("sweep", **kw)
+        if G.refused(r):
+            continue
+        admitted += 1
+        tails += isinstance(r, list)
+        for x in (r if isinstance(r, list) else [r]):
+            kernels[x["kernel"]] = kernels.get(x["kernel"], 0) + 1
+            reducers[x["reducer"]] = reducers.get(x["reducer"], 0) + 1
+    print(f"[gemm plan sweep] admitted {admitted} of 6000, tail cuts {tails}, launches by kernel {kernels}, by reducer {reducers}")
+    assert admitted >= 3000
+    assert set(kernels) >= set(G.REACHABLE) - {"pwconv_kernel<96>", "pwconv_kernel<192>"} and not set(kernels) & set(G.UNREACHABLE)
+    assert set(reducers) >= set(G.REDUCERS)
+
+
 # ------------------------------------------------------------------------------------------------ the case list
 def test_every_case_reaches_its_route_on_256_cus():
     for c in CASES:
@@ -181,7 +275,7 @@ def test_every_instance_runs_every_epilogue_it_admits():
 
 
 def test_unreachable_instances_are_unreachable():
-    """gemm256_kernel<4,2,F16>: launch_gemm_core names it (gt == 128 with fp16 operands), but gemm_glds_tile never returns 128 for fp16 operands in the product
+    """gemm256_kernel<4,2,F16>: glds_instance names it (a 128-tile with fp16 operands), but gemm_glds_tile never returns 128 for fp16 operands in the product
     build.  Sweep the shapes the 128-tile rule admits."""
     for M in (1024, 1152, 4096):
         for N in (1920, 2048, 896 * 4):

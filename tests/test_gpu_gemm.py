@@ -1,5 +1,6 @@
 """-m gpu: launch_gemm (csrc/gemm_bf16.hip) at op level -- every kernel instance, tile walk, K-range form and reducer the product build can reach, each case
-asserting the route the mirror (tests/gemm_util.py gemm_route) gives for THIS device's CU count.
+asserting the route the mirror (tests/gemm_util.py gemm_route) gives for THIS device's CU count, and that the library's own planner (fv_op_gemm_plan: plan_gemm,
+which launch_gemm runs) gives the same route for the launch's arguments.
 
 Three input classes (tests/gemm_util.py):
   exact      integer operands (split operands: hi integers, lo = j 2^-8) whose every partial sum fp32 holds exactly: fp32 outputs equal the float64 product bit
@@ -34,14 +35,18 @@ def _cus():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
-def _assert_route(c, epi, scratch=None, expect=None):
-    """the case's route on THIS device; a difference fails and names both"""
+def _assert_route(c, epi, scratch=None, expect=None, bias=True):
+    """the case's route on THIS device, by the mirror and by the library's own planner (fv_op_gemm_plan: plan_gemm, which launch_gemm runs) for the arguments the
+    launch is about to get; a difference fails and names both"""
     cus = _cus()
-    r = c.route(epi, cus, scratch=scratch)
+    r = c.route(epi, cus, scratch=scratch, bias=bias)
     want = c.expect if expect is None else expect
     if route_key(r) != want:
         pytest.fail(f"{c.name} {G.EPI_NAME[epi]}: the case is there for {want} ({describe(c.route(epi, G.CUS, scratch=scratch))} at {G.CUS} CUs); "
                     f"this device has {cus} CUs and launch_gemm takes {describe(r)}")
+    planned = G.library_route(lib(), **c.launch_args(epi, cus, scratch, bias))
+    if planned != r:
+        pytest.fail(f"{c.name} {G.EPI_NAME[epi]} at {cus} CUs: the library plans {describe(planned)} {planned}, the mirror says {describe(r)} {r}")
     return r
 
 
@@ -207,7 +212,7 @@ def test_selection(c):
     the lo8 half: the weights' fp8 copy), +0 on the empty rows: every k-slot pairing of every fragment read -- the XOR swizzle, the TN transposing reads, the fp8
     32-byte operand, the zero-filled last K-tile at K % 64 != 0, the hi | lo seam."""
     epi = _selection_epi(c)
-    _assert_route(c, epi)
+    _assert_route(c, epi, bias=False)
     for i in range(G.selection_launches(c)):
         what = f"{c.name} {G.EPI_NAME[epi]} selection launch {i}"
         p, pi = G.selection_problem(c, epi, i)

@@ -12,6 +12,10 @@
 // The epilogue goes through an fp32 LDS image of the 128x128 tile so that bias / GELU / layer-scale+residual /
 // SwiGLU / fp32-residual all run on 8 contiguous columns per lane with 16-byte global accesses.
 // Bounded by the MFMA roof for K >= ~512, by HBM for the K = 96..384 tower shapes (kernel table).
+//
+// Host side (below the kernels): launch_gemm = plan_gemm + run_launch.  plan_gemm (check_gemm, tail_cut, route_gemm) makes every argument check and the whole
+// routing decision among the instances of the table `instances` without a HIP call; run_launch fills Params, launches the planned instance, its reducer and
+// the RMSNorm where one is left over.  tests/gemm_util.py mirrors plan_gemm and the CPU suite compares the two through fv_op_gemm_plan.
 #include <cstdlib>
 #include <type_traits>
 
@@ -1033,17 +1037,108 @@ __global__ __launch_bounds__(256, C == 96 ? 3 : 1) void pwconv_kernel(Params p) 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------
+// Host side, top-down: the A/B switches, the instance table, plan_gemm (the argument checks, then the route) and launch_gemm, which runs a plan.
+
+// Every FASTVLA_* switch of this file, read once (tools build, `make AB=1`; fv_ab_env is a constant nullptr in the product build: all defaults there).
+struct Tuning {
+  bool gemm256, f16_tile128, ragged, colmajor, asym, tail, skinny, splitk, splitk_old, pwconv, krot;
+  int min_kt, group_m, grid;   // K-tiles per range of the 256-tile split-K; the grouped walk's height (0 = row-major); blocks of the one-pass 256-tile launch (0 = the CUs)
+};
+const Tuning& tuning() {
+  static const Tuning t = [] {
+    const auto on = [](const char* name) { return fv_ab_env(name) != nullptr; };
+    const auto num = [](const char* name, int dflt) { const char* e = fv_ab_env(name); return e ? atoi(e) : dflt; };
+    return Tuning{!on("FASTVLA_NO_GEMM256"), on("FASTVLA_F16_TILE128"), !on("FASTVLA_NO_GEMM_RAGGED"), !on("FASTVLA_NO_GEMM_COLMAJOR"), !on("FASTVLA_NO_GEMM_ASYM"),
+                  !on("FASTVLA_NO_GEMM_TAIL"), !on("FASTVLA_NO_SKINNY_SPLITK"), !on("FASTVLA_NO_SPLITK"), on("FASTVLA_SPLITK_OLD"), !on("FASTVLA_NO_PWCONV"),
+                  on("FASTVLA_GEMM_KROT"), num("FASTVLA_GEMM_MIN_KT", 16), num("FASTVLA_GEMM_GROUP_M", 4), num("FASTVLA_GEMM_GRID", 0)};
+  }();
+  return t;
+}
+
+// Every kernel instance of this file: the name as tests/gemm_util.py spells it, the kernel, its block size and dynamic LDS bytes.  A plan names a row.
+struct Instance { const char* name; void (*fn)(Params); int block, lds; };
+constexpr int LDS256 = 2 * 512 * 128, LDS128 = 2 * 256 * 128;
+constexpr int pw_lds(int C) { return C * (C * 2 + 16) + 4 * 32 * (C * 2 + 16); }
+// (Rows in the order this file has always first named its instances: hipcc emits them in that order, and the code object keeps its layout.)
+enum { T256_TN, T256_F16_TN, T256, T128, T256_ASYM, T256_F16, T256_ASYM_F16, T256_LO8, T128_LO8, T128_F16, G64, PW96, PW192, G128_LO8, G128_F16, G128, G64_LO8, G64_F16, INSTANCES };
+const Instance instances[INSTANCES] = {
+    {"gemm256_kernel<8,4,TN>", gemm256_kernel<8, 4, false, false, false, true>, 512, LDS256}, {"gemm256_kernel<8,4,F16,TN>", gemm256_kernel<8, 4, false, true, false, true>, 512, LDS256},
+    {"gemm256_kernel<8,4>", gemm256_kernel<8, 4>, 512, LDS256}, {"gemm256_kernel<4,2>", gemm256_kernel<4, 2>, 256, LDS128},
+    {"gemm256_kernel<8,4,ASYM>", gemm256_kernel<8, 4, true>, 512, LDS256}, {"gemm256_kernel<8,4,F16>", gemm256_kernel<8, 4, false, true>, 512, LDS256},
+    {"gemm256_kernel<8,4,ASYM,F16>", gemm256_kernel<8, 4, true, true>, 512, LDS256},
+    {"gemm256_kernel<8,4,LO8>", gemm256_kernel<8, 4, false, false, true>, 512, LDS256},   // (no asymmetric-staging instance of the hi + lo8 kernel: it spills)
+    {"gemm256_kernel<4,2,LO8>", gemm256_kernel<4, 2, false, false, true>, 256, LDS128}, {"gemm256_kernel<4,2,F16>", gemm256_kernel<4, 2, false, true>, 256, LDS128},
+    {"gemm_kernel<64>", gemm_kernel<64>, 256, 0}, {"pwconv_kernel<96>", pwconv_kernel<96>, 256, pw_lds(96)}, {"pwconv_kernel<192>", pwconv_kernel<192>, 256, pw_lds(192)},
+    {"gemm_kernel<128,LO8>", gemm_kernel<128, false, true>, 256, 0}, {"gemm_kernel<128,F16>", gemm_kernel<128, true>, 256, 0}, {"gemm_kernel<128>", gemm_kernel<128>, 256, 0},
+    {"gemm_kernel<64,LO8>", gemm_kernel<64, false, true>, 256, 0}, {"gemm_kernel<64,F16>", gemm_kernel<64, true>, 256, 0},
+};
+int staged_instance(int bm, bool f16, bool lo8) { return bm == 128 ? (lo8 ? G128_LO8 : f16 ? G128_F16 : G128) : (lo8 ? G64_LO8 : f16 ? G64_F16 : G64); }
+int glds_instance(int tile, bool asym, bool f16, bool lo8) {
+  if (tile == 128) return lo8 ? T128_LO8 : f16 ? T128_F16 : T128;
+  return lo8 ? T256_LO8 : f16 ? (asym ? T256_ASYM_F16 : T256_F16) : (asym ? T256_ASYM : T256);
+}
+const char* const reducer_names[] = {"", "splitk_reduce_kernel", "splitk_reduce_norm_kernel", "splitk_reduce_norm_row_kernel", "splitk_reduce_bf16_kernel", "splitk_reduce_swiglu_kernel"};
+
+bool f32_epi(int e) { return e == FV_EPI_RES_F32 || e == FV_EPI_F32; }
+bool f16_epi(int e) { return e == FV_EPI_GELU_GRAD || e == FV_EPI_MUL_AUX || e == FV_EPI_MUL_GELUP || e == FV_EPI_F16; }   // the tower backward's (2-byte fp16 outputs: the bf16 epilogues' store loop)
+bool bf16_epi(int e) { return e == FV_EPI_BIAS || e == FV_EPI_BIAS_GELU || e == FV_EPI_LS_RES; }
+
+// ---- plan_gemm, part one: every argument check, in the order they have always been made (a problem with two faults reports the first)
+int check_gemm(const GemmArgs& a) {
+  const bool f32out = f32_epi(a.epi);
+  // a following RMSNorm of the fp32 output rows: fused into the split-K reducer when that path is taken
+  if (a.norm_w && (!f32out || !a.norm_y || a.ldo != a.N || a.norm_ld < a.N || a.N % 8)) return fv_fail(FV_ERR_ARG, "gemm: fused norm needs an fp32 epilogue, ldo == N and N %% 8 == 0");
+  if (!a.A || !a.W || (!a.out && a.epi != FV_EPI_GELU_GRAD)) return fv_fail(FV_ERR_ARG, "gemm: null operand");
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return fv_fail(FV_ERR_ARG, "gemm: empty shape M=%d N=%d K=%d", a.M, a.N, a.K);
+  if (a.tn) {
+    if (!f32out || a.ksplit || a.norm_w || a.stash) return fv_fail(FV_ERR_UNSUPPORTED, "gemm (TN): fp32 epilogues only, no ksplit / fused norm / stash");
+    if (a.K % 64 || a.M % 8 || a.N % 8 || a.lda % 8 || a.ldw % 8 || a.lda < a.M || a.ldw < a.N)
+      return fv_fail(FV_ERR_ARG, "gemm (TN): K %% 64, M %% 8, N %% 8, lda >= M, ldw >= N (M=%d N=%d K=%d lda=%d ldw=%d)", a.M, a.N, a.K, a.lda, a.ldw);
+    if (a.ldo < a.N || a.ldo % 4 || (a.epi == FV_EPI_RES_F32 && (!a.res || a.ldr % 4 || a.ldr < a.N))) return fv_fail(FV_ERR_ARG, "gemm (TN): bad ldo / residual");
+    if (((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.out | (uintptr_t)a.res | (uintptr_t)a.bias) & 15) return fv_fail(FV_ERR_ARG, "gemm (TN): pointers must be 16-byte aligned");
+    if ((size_t)a.K * a.lda * 2 >= ((size_t)1 << 31) || (size_t)a.K * a.ldw * 2 >= ((size_t)1 << 31)) return fv_fail(FV_ERR_UNSUPPORTED, "gemm (TN): operands of 2 GiB or more");
+    return FV_OK;
+  }
+  if (a.K % 8 || a.lda % 8 || a.N % 8) return fv_fail(FV_ERR_ARG, "gemm: K, lda, N must be multiples of 8 (K=%d lda=%d N=%d)", a.K, a.lda, a.N);
+  if (a.lda < a.K) return fv_fail(FV_ERR_ARG, "gemm: lda < K");
+  if (a.epi < FV_EPI_BIAS || a.epi > FV_EPI_MUL_GELUP || a.epi == 6) return fv_fail(FV_ERR_ARG, "gemm: bad epilogue %d", a.epi);
+  if (f16_epi(a.epi) && a.ksplit) return fv_fail(FV_ERR_ARG, "gemm: the fp16-output epilogues take no ksplit");
+  if (a.epi == FV_EPI_GELU_GRAD && (!a.stash || ((uintptr_t)a.stash & 15))) return fv_fail(FV_ERR_ARG, "gemm: GELU_GRAD needs a 16-byte aligned stash (gelu' output)");
+  if ((a.epi == FV_EPI_MUL_AUX || a.epi == FV_EPI_MUL_GELUP) && (!a.res || a.ldr % 8 || a.ldr < a.N)) return fv_fail(FV_ERR_ARG, "gemm: MUL_AUX / MUL_GELUP need the fp16 factor in res");
+  if (a.f16 && a.ksplit) return fv_fail(FV_ERR_ARG, "gemm: fp16 operands are a single pass (no ksplit)");
+  if (a.f16 && (a.epi == FV_EPI_BIAS_GELU || a.epi == FV_EPI_LS_RES || a.epi == FV_EPI_SWIGLU))
+    return fv_fail(FV_ERR_UNSUPPORTED, "gemm: fp16 operands go with the BIAS / F32 / RES_F32 / SWIGLU_SPLIT / SWIGLU_F16 epilogues");
+  const bool swiglu = a.epi == FV_EPI_SWIGLU || a.epi == FV_EPI_SWIGLU_SPLIT || a.epi == FV_EPI_SWIGLU_F16;
+  const int ncols = (a.epi == FV_EPI_SWIGLU || a.epi == FV_EPI_SWIGLU_F16) ? a.N / 2 : a.N;  // SPLIT: hi and lo halves side by side -> N columns
+  if (swiglu && a.N % 16) return fv_fail(FV_ERR_ARG, "gemm: SwiGLU needs N %% 16 == 0");
+  if (a.ldo < ncols || a.ldo % (f32out ? 4 : 8)) return fv_fail(FV_ERR_ARG, "gemm: bad ldo %d", a.ldo);
+  if (a.epi == FV_EPI_LS_RES && (!a.res || !a.scale || a.ldr % 8 || a.ldr < a.N)) return fv_fail(FV_ERR_ARG, "gemm: LS_RES needs res/scale");
+  if (a.epi == FV_EPI_RES_F32 && (!a.res || a.ldr % 4 || a.ldr < a.N)) return fv_fail(FV_ERR_ARG, "gemm: RES_F32 needs res");
+  if (((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.out | (uintptr_t)a.res | (uintptr_t)a.bias | (uintptr_t)a.scale) & 15)
+    return fv_fail(FV_ERR_ARG, "gemm: pointers must be 16-byte aligned");
+  if (a.stash && a.epi == FV_EPI_MUL_GELUP) { if ((uintptr_t)a.stash & 15) return fv_fail(FV_ERR_ARG, "gemm: MUL_GELUP's gelu(a) output must be 16-byte aligned"); }
+  else if (a.stash && a.epi != FV_EPI_GELU_GRAD && ((a.epi != FV_EPI_SWIGLU_SPLIT && a.epi != FV_EPI_SWIGLU_F16) || ((uintptr_t)a.stash & 15) || (a.stash_f16 && !a.sat)))
+    return fv_fail(FV_ERR_ARG, "gemm: stash goes with FV_EPI_SWIGLU_SPLIT / FV_EPI_SWIGLU_F16 (16-byte aligned; the fp16 form with a saturation counter)");
+  if (a.ksplit == 2) {
+    if (!a.W8 || a.K % 128 || a.lda * 2 < 3 * a.K || ((uintptr_t)a.W8 & 15)) return fv_fail(FV_ERR_ARG, "gemm: the hi + lo8 form needs W8, K %% 128 == 0 and lda >= 1.5 K");
+    if (a.f16) return fv_fail(FV_ERR_ARG, "gemm: hi + lo8 goes with bf16 hi operands");
+  } else if (a.ksplit && a.lda < 2 * a.K) return fv_fail(FV_ERR_ARG, "gemm: ksplit needs lda >= 2K");
+  // (ksplit with a K that is no multiple of 64 -- a decoder whose inter is 32 mod 64 -- goes to the register-staged kernel: every form on whole 64-element
+  // K tiles below asks for K % 64 == 0 itself, gemm_kernel walks ceil(K / 64) tiles per half and zero-fills the last one's columns past K on both operands)
+  return FV_OK;
+}
+
+// ---- plan_gemm, part two: the route
 // which glds kernel (0 = none, 256 or 128) takes the problem.  256-tiles when there are enough of them to keep one block per
 // CU busy; otherwise 128-tiles (two blocks per CU) if the shape allows.
-int gemm_glds_tile(const GemmArgs& a) {
-  static const bool off = fv_ab_env("FASTVLA_NO_GEMM256") != nullptr;
-  if (off || a.K % 64 || a.K < 128) return 0;
+int gemm_glds_tile(const GemmArgs& a, const Tuning& t) {
+  if (!t.gemm256 || a.K % 64 || a.K < 128) return 0;
   // gemm256_kernel keeps per-lane source byte offsets in 32 bits ((row * lda) * 2 for A, (row * K) * 2 for W): operands of
   // 4 GiB or more go to the register-staged kernel, which addresses with size_t
   if ((size_t)a.M * a.lda * 2 >= ((size_t)1 << 32) || (size_t)a.N * a.K * 2 >= ((size_t)1 << 32)) return 0;
-  const bool f32 = a.epi == FV_EPI_RES_F32 || a.epi == FV_EPI_F32;
-  const bool f16_epi = a.epi == FV_EPI_GELU_GRAD || a.epi == FV_EPI_MUL_AUX || a.epi == FV_EPI_MUL_GELUP || a.epi == FV_EPI_F16;   // the tower backward's (2-byte fp16 outputs: the bf16 epilogues' store loop)
-  if (a.epi != FV_EPI_BIAS && a.epi != FV_EPI_BIAS_GELU && a.epi != FV_EPI_LS_RES && a.epi != FV_EPI_SWIGLU_SPLIT && a.epi != FV_EPI_SWIGLU_F16 && !f32 && !f16_epi) return 0;
+  const bool f32 = f32_epi(a.epi), f16e = f16_epi(a.epi);
+  if (!bf16_epi(a.epi) && a.epi != FV_EPI_SWIGLU_SPLIT && a.epi != FV_EPI_SWIGLU_F16 && !f32 && !f16e) return 0;
   if ((a.epi == FV_EPI_SWIGLU_SPLIT || a.epi == FV_EPI_SWIGLU_F16) && a.bias) return 0;
   // (a 128 x 256 variant for shapes whose last round of 256-tiles is mostly idle -- the decoder's gate/up, 608 tiles = 2.4
   // rounds -- was measured slower, 184 vs 150 us: 64 x 64 per wave reads a third more LDS per MFMA)
@@ -1052,18 +1147,15 @@ int gemm_glds_tile(const GemmArgs& a) {
   // round 6 experiment (tools build only, FASTVLA_F16_TILE128=1): the tower backward's short-K fp16 GEMMs (K = C <= 512: six K-tiles, then an epilogue that is
   // ~45 % of a 256 x 256 tile's time with ONE block per CU to hide its LDS turn and dependent aux loads) on 128 x 128 tiles at TWO blocks per CU, so that one
   // block's epilogue runs under the other's K loop
-  static const bool f16_tile128 = fv_ab_env("FASTVLA_F16_TILE128") != nullptr;
-  if (f16_tile128 && a.f16 && f16_epi && !a.tn && a.K <= 512 && a.M % 128 == 0 && a.N % 128 == 0 && (long)(a.M / 128) * (a.N / 128) >= 512) return 128;
+  if (t.f16_tile128 && a.f16 && f16e && !a.tn && a.K <= 512 && a.M % 128 == 0 && a.N % 128 == 0 && (long)(a.M / 128) * (a.N / 128) >= 512) return 128;
   constexpr int min_tiles_small_m = 128;
   if (a.M % 256 == 0 && a.N % 256 == 0 && (long)(a.M / 256) * (a.N / 256) >= (a.M <= 2048 ? min_tiles_small_m : 320)) return 256;
   // fp32 epilogues (the decoder's projections and every dgrad / wgrad of the unfrozen training path: N = 896, 1152, 4864, M = 896 ...)
   // take RAGGED edge tiles on the 256-tile kernel -- staging clamps rows past M / N, the epilogue drops them -- when the edge waste is
   // small: the register-staged kernel they fell to runs at ~0.45 PF against ~0.9 here
-  static const bool no_ragged = fv_ab_env("FASTVLA_NO_GEMM_RAGGED") != nullptr;   // A/B
   // (late round 4: the bf16 epilogues too -- bias / bias + GELU / layer-scale + residual share the guarded store loop: the PatchEmbed 1x1 at
   // 262144 x 384 x 384 and the projector's first Linear, N = 896, were the last two launches on the register-staged kernel)
-  const bool bf16_epi = a.epi == FV_EPI_BIAS || a.epi == FV_EPI_BIAS_GELU || a.epi == FV_EPI_LS_RES || f16_epi;
-  if (!no_ragged && (((f32 || bf16_epi) && a.N % 8 == 0) || (a.epi == FV_EPI_SWIGLU_SPLIT && a.N % 256 == 0))) {   // (SwiGLU: ragged rows only)
+  if (t.ragged && (((f32 || bf16_epi(a.epi) || f16e) && a.N % 8 == 0) || (a.epi == FV_EPI_SWIGLU_SPLIT && a.N % 256 == 0))) {   // (SwiGLU: ragged rows only)
     const long tm = (a.M + 255) / 256, tn = (a.N + 255) / 256;
     const double fill = (double)a.M * a.N / ((double)tm * tn * 65536.0);
     if (tm * tn >= 128 && fill >= 0.75) return 256;
@@ -1076,330 +1168,240 @@ int gemm_glds_tile(const GemmArgs& a) {
   return 0;
 }
 
-thread_local bool g_norm_fused = false;   // set by launch_gemm_core when the split-K reducer took the RMSNorm with it
+// the 256-tile kernels' tile walk: column-major for up to 8 row tiles (16 measured at the headline shape in round 3: gate/up -3.5 %, split-K down +9 %, step
+// unchanged), else in groups of 4 or 2 tile rows, whichever divides the row-tile count (the kernel then needs one division and no short last group: a general
+// group height cost gemm256_kernel 20 bytes of scratch per lane), else row-major
+void set_walk(GemmLaunch& l, int tiles_mt, bool colmajor, int want) {
+  l.tiles_mt = tiles_mt;
+  l.tiles_m = colmajor && tiles_mt <= 8 ? tiles_mt : 0;
+  l.group_m = (l.tiles_m || l.tiles_n <= 8) ? 0 : (want >= 4 && tiles_mt % 4 == 0) ? 4 : (want >= 2 && tiles_mt % 2 == 0) ? 2 : 0;
+}
+
+// K ranges per 256-tile: the count that minimises (rounds of `cus` units, each 1 / s of a tile's K loop) + the partial sums' trip through memory
+// (s x M x npad floats written and read back: ~0.5 of a 2048-deep K loop per range at 10 240 x 1024) -- 160 tiles (the unfrozen path's
+// 10 240 x 896 projections) take 3 ranges = 480 units = 1.9 rounds instead of 0.6 of one
+int k_ranges(int tiles, int nkt, int M, int tn, size_t scratch, int cus, int max_ranges, int min_kt) {
+  const double tile_us = (double)nkt * 64.0 * 131072.0 / 1.0e6 / 4.0;                 // ~a 256 x 256 x (64 nkt) tile on one CU at ~4 GF/us/CU
+  const double part_us = 2.0 * (double)M * (tn * 256) * 4.0 / 4.0e6;                  // one range's partials written + read at ~4 TB/s
+  double best = 1e30;
+  int splits = 1;
+  for (int sN = 1; sN <= max_ranges; ++sN) {
+    if (sN > 1 && (nkt / sN < min_kt || (size_t)sN * M * (tn * 256) * sizeof(float) > scratch)) break;
+    const long units = (long)tiles * sN, rounds = (units + cus - 1) / cus;
+    const double t = (double)rounds * tile_us / sN + (sN > 1 ? sN * part_us : 0.0);
+    if (t < best * 0.97) { best = t; splits = sN; }
+  }
+  return splits;
+}
+
+// few rows: K ranges of 64-row tiles of the register-staged kernel until the chip is covered twice.  fp32 / SwiGLU-split epilogues (the control loop: M = 64 B
+// rows of the decoder at B <= 4): fewer tiles than CUs (gate/up at M = 256 is 304 tiles: it keeps the one-launch form), >= 4 K-tiles per range.  bf16 epilogues
+// (scratch supplied by the inference tower only): tiles on <= 3/8 of the CUs, one or two observations (B = 4 -- configs[0], the shape the oracle checks -- keeps
+// the kernels of the large batches, so that its rows stay within one rounding of theirs: tests/test_gpu_fullsize.py, batch-row properties), >= 8 per range
+int few_row_ranges(const GemmArgs& a, int cus, bool bf16) {
+  const int npad = (a.N + BN - 1) / BN * BN, tiles = ((a.M + 63) / 64) * (npad / BN), nkt = (a.ksplit ? 2 : 1) * ((a.K + BK - 1) / BK);
+  int splits = (bf16 ? tiles * 8 <= cus * 3 : tiles < cus) ? (2 * cus + tiles - 1) / tiles : 1;
+  if (splits > nkt / (bf16 ? 8 : 4)) splits = nkt / (bf16 ? 8 : 4);
+  while (splits > 1 && (size_t)splits * a.M * npad * sizeof(float) > a.splitk_bytes) --splits;
+  return splits;
+}
+
+// the second pass of a K-range launch (the rules of the reducers' comments above) and, with it, where the RMSNorm runs
+void set_ranges(GemmLaunch& l, const GemmArgs& a, int splits, int npad, bool few_row_form) {
+  l.splits = splits; l.npad = npad; l.nwg *= splits;
+  if (a.epi == FV_EPI_SWIGLU_SPLIT) l.reducer = GEMM_RED_SWIGLU;
+  else if (bf16_epi(a.epi)) l.reducer = GEMM_RED_BF16;
+  // a block per row (the wave-per-row form walks splits x N / 256 dependent steps: 32 us per launch at 1024 x 3584, 4.6 % of the 7B step); inference only
+  else if (a.norm_w && (few_row_form || a.few_rows) && a.N <= 4096 && a.ksplit != 2) l.reducer = GEMM_RED_NORM_ROW;
+  else l.reducer = a.norm_w ? GEMM_RED_NORM : GEMM_RED_F32;
+  if (l.reducer == GEMM_RED_NORM_ROW || l.reducer == GEMM_RED_NORM) l.norm = GEMM_NORM_FUSED;
+}
+
+// The tail.  A problem of r >= 1 full rounds of 256-tiles plus a short last round (7B gate/up at M = 1024: 592 tiles = 2.31 rounds on 256 CUs, i.e. three
+// rounds of time) is cut at a column: the full rounds' column panels run as they are, the remaining panels as a K-range problem of their own (one more
+// short round + a reduce pass over those columns).  Whole column panels only; inference only (the cut depends on the row count).  Returns the column, 0: no cut.
+int tail_cut(const GemmArgs& a, int cus, const Tuning& t) {
+  if (!t.tail || a.tn || a.no_tail || !a.few_rows || !a.splitk_ws || a.norm_w || a.stash || a.f16 || a.ksplit == 2 || a.M % 256 || a.N % 256 || a.K % 64 ||
+      !(f32_epi(a.epi) || (a.epi == FV_EPI_SWIGLU_SPLIT && a.N % 512 == 0)) || gemm_glds_tile(a, t) != 256) return 0;
+  const int tmr = a.M / 256, tn = a.N / 256, tiles = tmr * tn, rem = tiles % cus, nkt = (a.ksplit ? 2 : 1) * (a.K / 64);
+  return (tiles > cus && rem > 0 && 2 * rem <= cus && rem % tmr == 0 && nkt >= 32) ? (tn - rem / tmr) * 256 : 0;
+}
+// columns [c0, c1) of a problem as a problem of its own (SWIGLU_SPLIT keeps the whole problem's lo half column)
+GemmArgs column_range(const GemmArgs& a, int c0, int c1) {
+  GemmArgs r = a;
+  r.N = c1 - c0; r.no_tail = 1; r.lo_off = a.lo_off ? a.lo_off : a.N / 2;
+  r.W = a.W + (size_t)c0 * a.K;
+  if (a.bias) r.bias = a.bias + c0;
+  if (f32_epi(a.epi)) {
+    r.out = static_cast<float*>(a.out) + c0;
+    if (a.res) r.res = static_cast<const float*>(a.res) + c0;
+  } else {
+    r.out = static_cast<bf16_t*>(a.out) + c0 / 2;
+  }
+  return r;
+}
+
+// one launch for a problem that passed check_gemm
+void route_gemm(const GemmArgs& a, int cus, const Tuning& t, GemmLaunch& l) {
+  l = GemmLaunch{};
+  l.splits = 1; l.norm = a.norm_w ? GEMM_NORM_SEPARATE : GEMM_NORM_NONE; l.c1 = a.N;
+  const bool f32out = f32_epi(a.epi), lo8 = a.ksplit == 2;
+  if (a.tn) {   // always the 256-tile kernel, ragged edges allowed, K ranges from the NT path's cost model: up to 256 of them (the tower's weight gradients are
+                // 1 .. 12 tiles over a contraction of 10^5 .. 10^7 pixels; the stem's is ONE tile over 8.4 M rows)
+    const int tmr = (a.M + 255) / 256, tn = (a.N + 255) / 256;
+    l.kernel = a.f16 ? T256_F16_TN : T256_TN; l.tile = 256; l.tiles_n = tn; l.nwg = tmr * tn; l.npad = tn * 256;
+    set_walk(l, tmr, true, 4);
+    const int splits = a.splitk_ws ? k_ranges(l.nwg, a.K / 64, a.M, tn, a.splitk_bytes, cus, 256, 16) : 1;
+    if (splits > 1) set_ranges(l, a, splits, l.npad, false);
+    l.grid = l.nwg < cus / 8 * 8 ? l.nwg : cus / 8 * 8;
+    return;
+  }
+  // (the SwiGLU reducer writes its lo half as bf16: the hi + lo8 form, whose consumer reads fp8 bytes there, and the fp16 form keep the one-launch
+  // epilogue -- policy 5's gate/up at 256 x 17920 x 1536 would otherwise pick 2 ranges here)
+  const bool swiglu_sk = a.epi == FV_EPI_SWIGLU_SPLIT && !a.stash && a.N % 16 == 0 && !lo8 && !a.f16;
+  // few rows -- fp32: M <= 256, or a row count the 256-tile split-K below does not take whole (the spliced control loop's 320 B rows); bf16: a long K
+  const bool few_f32 = (f32out || swiglu_sk) && (a.M <= 256 || (a.M % 256 != 0 && a.M <= 1024)) && !lo8;
+  const bool few_bf16 = bf16_epi(a.epi) && !a.ksplit && a.K % BK == 0 && a.K >= 24 * BK;
+  if (t.skinny && a.few_rows && a.splitk_ws && !a.f16 && a.N % 8 == 0 && (few_f32 || few_bf16)) {
+    const int splits = few_row_ranges(a, cus, few_bf16);
+    if (splits > 1) {
+      l.kernel = G64; l.tile = 64; l.tiles_n = (a.N + BN - 1) / BN; l.nwg = ((a.M + 63) / 64) * l.tiles_n;
+      set_ranges(l, a, splits, l.tiles_n * BN, true);
+      l.grid = l.nwg;
+      return;
+    }
+  }
+  const bool asym = t.asym && a.M <= 8192 && a.M % 256 == 0;   // the asymmetric staging addresses row + 32 from a (clamped) base row: whole row tiles only
+  // split-K: fp32 output, few 256-tiles, long K, scratch supplied -> one (tile, K-range) unit per CU, then a reduce pass
+  if (t.splitk && a.splitk_ws && (f32out || (swiglu_sk && a.M % 256 == 0 && a.N % 256 == 0)) && t.gemm256 && (a.M % 256 == 0 || (t.ragged && a.N % 8 == 0)) && a.K % 64 == 0 && a.N % 4 == 0 &&
+      (size_t)a.M * a.lda * 2 < ((size_t)1 << 32) && (size_t)a.N * a.K * 2 < ((size_t)1 << 32)) {
+    const int tmr = (a.M + 255) / 256;            // a ragged last row tile: staging clamps its rows, the partial-sum stores skip them
+    const int tn = (a.N + 255) / 256, tiles = tmr * tn, nkt = lo8 ? a.K / 64 + a.K / 128 : (a.ksplit ? 2 : 1) * (a.K / 64);
+    int splits = k_ranges(tiles, nkt, a.M, tn, a.splitk_bytes, cus, 8, t.min_kt);
+    if (t.splitk_old) {   // A/B: round 3's rule (cus / tiles ranges, only below one round)
+      splits = tiles < cus ? (cus / tiles > 8 ? 8 : cus / tiles) : 1;
+      while (splits > 1 && (nkt / splits < 16 || (size_t)splits * a.M * (tn * 256) * sizeof(float) > a.splitk_bytes)) --splits;
+    }
+    if (splits > 1) {
+      l.kernel = glds_instance(256, asym, a.f16, lo8); l.tile = 256; l.tiles_n = tn; l.nwg = tiles;
+      set_walk(l, tmr, t.colmajor, t.group_m);
+      set_ranges(l, a, splits, tn * 256, false);
+      l.grid = l.nwg < cus ? l.nwg : cus / 8 * 8;
+      return;
+    }
+  }
+  if (t.pwconv && !a.ksplit && !a.f16 && a.N == a.K && (a.K == 96 || a.K == 192) && a.lda == a.K && a.ldo == a.N && a.M % 128 == 0 &&
+      (a.epi == FV_EPI_BIAS || a.epi == FV_EPI_BIAS_GELU)) {
+    l.kernel = a.K == 96 ? PW96 : PW192; l.tile = 128; l.tiles_n = 1; l.nwg = a.M / 128;
+    const int slots = a.K == 96 ? 3 * cus : cus;   // (__launch_bounds__: three blocks per CU at C = 96)
+    l.grid = l.nwg < slots ? l.nwg : slots;
+    return;
+  }
+  if (const int gt = gemm_glds_tile(a, t)) {
+    const int tmr = (a.M + gt - 1) / gt;        // ragged edge tiles only come back from gemm_glds_tile for the epilogues with a guarded store loop
+    l.kernel = glds_instance(gt, asym, a.f16, lo8); l.tile = gt; l.tiles_n = (a.N + gt - 1) / gt; l.nwg = tmr * l.tiles_n;
+    set_walk(l, tmr, t.colmajor, t.group_m);   // (the 128-tile instance shares the kernel: two blocks per CU, 64 tiles per XCD at a time)
+    int slots = (gt == 128 ? 2 * cus : cus) / 8 * 8;   // persistent; a multiple of 8 keeps the XCD remap exact
+    if (t.grid >= 8 && gt == 256) slots = t.grid / 8 * 8;   // tools only
+    l.grid = l.nwg < slots ? l.nwg : slots;
+    return;
+  }
+  // the register-staged kernel: 64-row tiles when 128-row tiles would give fewer than two blocks per CU
+  l.tiles_n = (a.N + BN - 1) / BN;
+  const long blocks128 = (long)((a.M + 127) / 128) * l.tiles_n;
+  l.tile = blocks128 >= 512 ? 128 : 64;
+  l.kernel = staged_instance(l.tile, a.f16, lo8);
+  l.grid = l.nwg = l.tile == 128 ? (int)blocks128 : ((a.M + 63) / 64) * l.tiles_n;
+}
+
+int plan_with(const GemmArgs& a, int cus, const Tuning& t, GemmPlan& plan) {
+  if (const int rc = check_gemm(a)) return rc;
+  plan.n = 1;
+  if (const int n0 = tail_cut(a, cus, t)) {   // two launches, each planned as a problem of its own with no_tail set
+    for (int i = 0; i < 2; ++i) {
+      GemmPlan half;
+      const int c0 = i ? n0 : 0, c1 = i ? a.N : n0;
+      if (const int rc = plan_with(column_range(a, c0, c1), cus, t, half)) return rc;
+      plan.launch[i] = half.launch[0]; plan.launch[i].c0 = c0; plan.launch[i].c1 = c1;
+    }
+    plan.n = 2;
+  } else {
+    route_gemm(a, cus, t, plan.launch[0]);
+  }
+  return FV_OK;
+}
+
+// ---- launch_gemm: run a plan
+int run_launch(const GemmArgs& whole, const GemmLaunch& l, hipStream_t s) {
+  const GemmArgs a = column_range(whole, l.c0, l.c1);   // (the whole problem unless the tail was cut off)
+  const bool lo8 = a.ksplit == 2;
+  Params p;
+  p.A = a.A; p.W = a.W; p.bias = a.bias; p.scale = a.scale; p.res = a.res; p.out = a.out; p.lo_off = a.lo_off;
+  p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldw = a.ldw; p.ldr = a.ldr; p.ldo = a.ldo; p.epi = a.epi;
+  p.ksplit = lo8 ? 2 : (a.ksplit ? 1 : 0);
+  p.sat = a.sat; p.skip = a.skip; p.stash = a.stash; p.stash_f16 = a.stash_f16; p.W8 = static_cast<const uint8_t*>(a.W8);
+  p.tiles_n = l.tiles_n; p.tiles_m = l.tiles_m; p.tiles_mt = l.tiles_mt; p.group_m = l.group_m; p.nwg = l.nwg;
+  p.splits = l.splits; p.npad = l.npad; p.part = l.splits > 1 ? a.splitk_ws : nullptr;
+  const Instance& k = instances[l.kernel];
+  void* kargs[] = {&p};
+  (void)hipLaunchKernel(reinterpret_cast<const void*>(k.fn), dim3(l.grid), dim3(k.block), kargs, k.lds, s);
+  // the second pass of every K-range form: sums the ranges' fp32 partials in range order and applies the launch's epilogue (bias / fp32 residual, + the
+  // NEXT RMSNorm where one is attached, SwiGLU + hi | lo split, or a bf16 epilogue).  lo8: the normalised operand's remainder leaves as fp8 (policy 5).
+  const float* res32 = a.epi == FV_EPI_RES_F32 ? static_cast<const float*>(a.res) : nullptr;
+  float* out32 = static_cast<float*>(a.out);
+  const auto blocks = [](long n) { return dim3((unsigned)((n + 255) / 256)); };
+  switch (l.reducer) {
+    case GEMM_RED_SWIGLU:
+      hipLaunchKernelGGL(splitk_reduce_swiglu_kernel, blocks((long)a.M * (a.N / 16)), dim3(256), 0, s, a.splitk_ws, l.splits, a.M, a.N, l.npad, static_cast<bf16_t*>(a.out), a.ldo, a.lo_off, a.skip);
+      break;
+    case GEMM_RED_BF16:
+      hipLaunchKernelGGL(splitk_reduce_bf16_kernel, blocks((long)a.M * (a.N / 8)), dim3(256), 0, s, a.splitk_ws, l.splits, a.M, a.N, l.npad, a.bias, a.epi, a.scale,
+                         static_cast<const bf16_t*>(a.res), a.ldr, static_cast<bf16_t*>(a.out), a.ldo, a.skip);
+      break;
+    case GEMM_RED_NORM_ROW:
+      hipLaunchKernelGGL(splitk_reduce_norm_row_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a.splitk_ws, l.splits, a.M, a.N, l.npad, a.bias, res32, a.ldr, out32, a.ldo,
+                         a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps, a.skip);
+      break;
+    case GEMM_RED_NORM:
+      hipLaunchKernelGGL(splitk_reduce_norm_kernel, dim3((unsigned)((a.M + 3) / 4)), dim3(256), 0, s, a.splitk_ws, l.splits, a.M, a.N, l.npad, a.bias, res32, a.ldr, out32, a.ldo,
+                         a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps, lo8 ? 1 : 0, a.skip);
+      break;
+    case GEMM_RED_F32:
+      hipLaunchKernelGGL(splitk_reduce_kernel, blocks((long)a.M * (a.N / 4)), dim3(256), 0, s, a.splitk_ws, l.splits, a.M, a.N, l.npad, a.bias, res32, a.ldr, out32, a.ldo, a.skip);
+      break;
+  }
+  FV_HIP_CHECK(hipGetLastError());
+  if (l.norm == GEMM_NORM_SEPARATE) return launch_rmsnorm(out32, a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.M, a.N, a.norm_eps, s, 0, nullptr, lo8 ? 1 : 0, a.skip);
+  return FV_OK;
+}
 
 }  // namespace
 
-static int launch_gemm_core(const GemmArgs& a, hipStream_t s);
-
-// the second pass of every K-range form: sums the ranges' fp32 partials in range order and applies the launch's epilogue (bias / fp32 residual, + the
-// NEXT RMSNorm where one is attached, SwiGLU + hi | lo split, or a bf16 epilogue).  lo8: the normalised operand's remainder leaves as fp8 (policy 5).
-static int launch_splitk_reduce(const GemmArgs& a, int splits, int npad, bool few_rows, int lo8, hipStream_t s) {
-  const float* res32 = a.epi == FV_EPI_RES_F32 ? static_cast<const float*>(a.res) : nullptr;
-  if (a.epi == FV_EPI_SWIGLU_SPLIT) {
-    const long n = (long)a.M * (a.N / 16);
-    hipLaunchKernelGGL(splitk_reduce_swiglu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, static_cast<bf16_t*>(a.out), a.ldo, a.lo_off ? a.lo_off : a.N / 2, a.skip);
-  } else if (a.epi == FV_EPI_BIAS || a.epi == FV_EPI_BIAS_GELU || a.epi == FV_EPI_LS_RES) {
-    const long n = (long)a.M * (a.N / 8);
-    hipLaunchKernelGGL(splitk_reduce_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, a.epi, a.scale,
-                       static_cast<const bf16_t*>(a.res), a.ldr, static_cast<bf16_t*>(a.out), a.ldo, a.skip);
-  } else if (a.norm_w && (few_rows || a.few_rows) && a.N <= 4096 && !lo8) {   // a block per row (the wave-per-row form below walks splits x N / 256 dependent
-                                                                              // steps: 32 us per launch at 1024 x 3584, 4.6 % of the 7B step); inference only
-    g_norm_fused = true;
-    hipLaunchKernelGGL(splitk_reduce_norm_row_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, res32, a.ldr,
-                       static_cast<float*>(a.out), a.ldo, a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps, a.skip);
-  } else if (a.norm_w) {
-    g_norm_fused = true;
-    hipLaunchKernelGGL(splitk_reduce_norm_kernel, dim3((unsigned)((a.M + 3) / 4)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, res32, a.ldr,
-                       static_cast<float*>(a.out), a.ldo, a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.norm_eps, lo8, a.skip);
-  } else {
-    const long quads = (long)a.M * (a.N / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, npad, a.bias, res32, a.ldr,
-                       static_cast<float*>(a.out), a.ldo, a.skip);
-  }
-  FV_HIP_CHECK(hipGetLastError());
-  return FV_OK;
-}
+int plan_gemm(const GemmArgs& a, int cus, GemmPlan& plan) { return plan_with(a, cus, tuning(), plan); }
+const char* gemm_kernel_name(int kernel) { return kernel >= 0 && kernel < INSTANCES ? instances[kernel].name : ""; }
+const char* gemm_reducer_name(int reducer) { return reducer >= 0 && reducer <= GEMM_RED_SWIGLU ? reducer_names[reducer] : ""; }
 
 int launch_gemm(const GemmArgs& a, hipStream_t s) {
-  if (a.norm_w) {   // a following RMSNorm of the fp32 output rows: fused into the split-K reducer when that path is taken
-    const bool f32 = a.epi == FV_EPI_RES_F32 || a.epi == FV_EPI_F32;
-    if (!f32 || !a.norm_y || a.ldo != a.N || a.norm_ld < a.N || a.N % 8) return fv_fail(FV_ERR_ARG, "gemm: fused norm needs an fp32 epilogue, ldo == N and N %% 8 == 0");
-  }
-  const int rc = launch_gemm_core(a, s);
-  if (rc != FV_OK) return rc;
-  if (a.norm_w && rc == FV_OK && !g_norm_fused)
-    return launch_rmsnorm(static_cast<const float*>(a.out), a.norm_w, a.norm_y, a.norm_ylo, a.norm_ld, a.M, a.N, a.norm_eps, s, 0, nullptr, a.ksplit == 2 ? 1 : 0, a.skip);
-  return FV_OK;
-}
-
-// the grouped tile walk's group height: 4 or 2 tile rows, whichever divides the row-tile count (the kernel then needs one division and no
-// short last group: a general group height cost gemm256_kernel 20 bytes of scratch per lane); 0 = row-major
-static int pick_group_m(int tiles_m_total, int want) {
-  if (want >= 4 && tiles_m_total % 4 == 0) return 4;
-  if (want >= 2 && tiles_m_total % 2 == 0) return 2;
-  return 0;
-}
-
-// TN problems (GemmArgs::tn): always the 256-tile kernel, ragged edges allowed, K ranges per tile from the same cost model as the NT path
-static int launch_gemm_tn(const GemmArgs& a, hipStream_t s) {
-  const bool f32out = a.epi == FV_EPI_RES_F32 || a.epi == FV_EPI_F32;
-  if (!f32out || a.ksplit || a.norm_w || a.stash) return fv_fail(FV_ERR_UNSUPPORTED, "gemm (TN): fp32 epilogues only, no ksplit / fused norm / stash");
-  if (a.K % 64 || a.M % 8 || a.N % 8 || a.lda % 8 || a.ldw % 8 || a.lda < a.M || a.ldw < a.N)
-    return fv_fail(FV_ERR_ARG, "gemm (TN): K %% 64, M %% 8, N %% 8, lda >= M, ldw >= N (M=%d N=%d K=%d lda=%d ldw=%d)", a.M, a.N, a.K, a.lda, a.ldw);
-  if (a.ldo < a.N || a.ldo % 4 || (a.epi == FV_EPI_RES_F32 && (!a.res || a.ldr % 4 || a.ldr < a.N))) return fv_fail(FV_ERR_ARG, "gemm (TN): bad ldo / residual");
-  if (((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.out | (uintptr_t)a.res | (uintptr_t)a.bias) & 15) return fv_fail(FV_ERR_ARG, "gemm (TN): pointers must be 16-byte aligned");
-  if ((size_t)a.K * a.lda * 2 >= ((size_t)1 << 31) || (size_t)a.K * a.ldw * 2 >= ((size_t)1 << 31)) return fv_fail(FV_ERR_UNSUPPORTED, "gemm (TN): operands of 2 GiB or more");
-  Params p;
-  p.A = a.A; p.W = a.W; p.bias = a.bias; p.scale = nullptr; p.res = a.res; p.out = a.out;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldw = a.ldw; p.ldr = a.ldr; p.ldo = a.ldo; p.epi = a.epi; p.ksplit = 0; p.skip = a.skip;
   static int cus = 0;
   if (!cus) {
     int dev = 0;
     hipDeviceProp_t prop;
     cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<8, 4, false, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<8, 4, false, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
   }
-  const int tmr = (a.M + 255) / 256, tn = (a.N + 255) / 256, tiles = tmr * tn, nkt = a.K / 64;
-  int splits = 1;
-  if (a.splitk_ws) {
-    const double tile_us = (double)nkt * 64.0 * 131072.0 / 1.0e6 / 4.0, part_us = 2.0 * (double)a.M * (tn * 256) * 4.0 / 4.0e6;
-    double best = 1e30;
-    for (int sN = 1; sN <= 256; ++sN) {   // (up to 256 ranges: the tower's weight gradients are 1 .. 12 tiles over a contraction of 10^5 .. 10^7 pixels; the stem's is ONE tile over 8.4 M rows)
-      if (sN > 1 && (nkt / sN < 16 || (size_t)sN * a.M * (tn * 256) * sizeof(float) > a.splitk_bytes)) break;
-      const long units = (long)tiles * sN, rounds = (units + cus - 1) / cus;
-      const double t = (double)rounds * tile_us / sN + (sN > 1 ? sN * part_us : 0.0);
-      if (t < best * 0.97) { best = t; splits = sN; }
-    }
-  }
-  p.tiles_n = tn; p.tiles_m = tmr <= 8 ? tmr : 0; p.tiles_mt = tmr; p.group_m = (!p.tiles_m && tn > 8) ? pick_group_m(tmr, 4) : 0;
-  p.splits = splits; p.npad = tn * 256; p.part = splits > 1 ? a.splitk_ws : nullptr;
-  p.nwg = tiles * splits;
-  const int slots = cus / 8 * 8;
-  const dim3 g(p.nwg < slots ? p.nwg : slots);
-  if (a.f16) hipLaunchKernelGGL((gemm256_kernel<8, 4, false, true, false, true>), g, dim3(512), 2 * 512 * 128, s, p);
-  else hipLaunchKernelGGL((gemm256_kernel<8, 4, false, false, false, true>), g, dim3(512), 2 * 512 * 128, s, p);
-  if (splits > 1) {
-    const long quads = (long)a.M * (a.N / 4);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, s, a.splitk_ws, splits, a.M, a.N, p.npad, a.bias,
-                       a.epi == FV_EPI_RES_F32 ? static_cast<const float*>(a.res) : nullptr, a.ldr, static_cast<float*>(a.out), a.ldo, a.skip);
-  }
-  FV_HIP_CHECK(hipGetLastError());
-  return FV_OK;
-}
-
-static int launch_gemm_core(const GemmArgs& a, hipStream_t s) {
-  g_norm_fused = false;
+  GemmPlan plan;
+  if (const int rc = plan_gemm(a, cus, plan)) return rc;
+  static bool set_up = false;   // the first launch: the instances' dynamic LDS sizes
+  if (!set_up) {
+    set_up = true;
+    for (const Instance& k : instances)
+      if (k.lds) FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, k.lds));
 #ifdef FASTVLA_AB_SWITCHES
-  {
-    static bool done = false;
-    if (!done) { done = true; const int v = fv_ab_env("FASTVLA_GEMM_KROT") ? 1 : 0; (void)hipMemcpyToSymbol(HIP_SYMBOL(g_g2_krot), &v, sizeof(int)); }
-  }
+    const int v = tuning().krot ? 1 : 0;
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_g2_krot), &v, sizeof(int));
 #endif
-  if (!a.A || !a.W || (!a.out && a.epi != FV_EPI_GELU_GRAD)) return fv_fail(FV_ERR_ARG, "gemm: null operand");
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return fv_fail(FV_ERR_ARG, "gemm: empty shape M=%d N=%d K=%d", a.M, a.N, a.K);
-  if (a.tn) return launch_gemm_tn(a, s);
-  if (a.K % 8 || a.lda % 8 || a.N % 8) return fv_fail(FV_ERR_ARG, "gemm: K, lda, N must be multiples of 8 (K=%d lda=%d N=%d)", a.K, a.lda, a.N);
-  if (a.lda < a.K) return fv_fail(FV_ERR_ARG, "gemm: lda < K");
-  if (a.epi < FV_EPI_BIAS || a.epi > FV_EPI_MUL_GELUP || a.epi == 6) return fv_fail(FV_ERR_ARG, "gemm: bad epilogue %d", a.epi);
-  if ((a.epi == FV_EPI_GELU_GRAD || a.epi == FV_EPI_MUL_AUX || a.epi == FV_EPI_MUL_GELUP || a.epi == FV_EPI_F16) && a.ksplit) return fv_fail(FV_ERR_ARG, "gemm: the fp16-output epilogues take no ksplit");
-  if (a.epi == FV_EPI_GELU_GRAD && (!a.stash || ((uintptr_t)a.stash & 15))) return fv_fail(FV_ERR_ARG, "gemm: GELU_GRAD needs a 16-byte aligned stash (gelu' output)");
-  if ((a.epi == FV_EPI_MUL_AUX || a.epi == FV_EPI_MUL_GELUP) && (!a.res || a.ldr % 8 || a.ldr < a.N)) return fv_fail(FV_ERR_ARG, "gemm: MUL_AUX / MUL_GELUP need the fp16 factor in res");
-  if (a.f16 && a.ksplit) return fv_fail(FV_ERR_ARG, "gemm: fp16 operands are a single pass (no ksplit)");
-  if (a.f16 && (a.epi == FV_EPI_BIAS_GELU || a.epi == FV_EPI_LS_RES || a.epi == FV_EPI_SWIGLU))
-    return fv_fail(FV_ERR_UNSUPPORTED, "gemm: fp16 operands go with the BIAS / F32 / RES_F32 / SWIGLU_SPLIT / SWIGLU_F16 epilogues");
-  const bool f32out = a.epi == FV_EPI_RES_F32 || a.epi == FV_EPI_F32;
-  const bool swiglu = a.epi == FV_EPI_SWIGLU || a.epi == FV_EPI_SWIGLU_SPLIT || a.epi == FV_EPI_SWIGLU_F16;
-  const int ncols = (a.epi == FV_EPI_SWIGLU || a.epi == FV_EPI_SWIGLU_F16) ? a.N / 2 : a.N;  // SPLIT: hi and lo halves side by side -> N columns
-  if (swiglu && a.N % 16) return fv_fail(FV_ERR_ARG, "gemm: SwiGLU needs N %% 16 == 0");
-  if (a.ldo < ncols || a.ldo % (f32out ? 4 : 8)) return fv_fail(FV_ERR_ARG, "gemm: bad ldo %d", a.ldo);
-  if (a.epi == FV_EPI_LS_RES && (!a.res || !a.scale || a.ldr % 8 || a.ldr < a.N)) return fv_fail(FV_ERR_ARG, "gemm: LS_RES needs res/scale");
-  if (a.epi == FV_EPI_RES_F32 && (!a.res || a.ldr % 4 || a.ldr < a.N)) return fv_fail(FV_ERR_ARG, "gemm: RES_F32 needs res");
-  if (((uintptr_t)a.A | (uintptr_t)a.W | (uintptr_t)a.out | (uintptr_t)a.res | (uintptr_t)a.bias | (uintptr_t)a.scale) & 15)
-    return fv_fail(FV_ERR_ARG, "gemm: pointers must be 16-byte aligned");
-  Params p;
-  p.A = a.A; p.W = a.W; p.bias = a.bias; p.scale = a.scale; p.res = a.res; p.out = a.out; p.lo_off = a.lo_off ? a.lo_off : a.N / 2;
-  p.M = a.M; p.N = a.N; p.K = a.K; p.lda = a.lda; p.ldr = a.ldr; p.ldo = a.ldo; p.epi = a.epi;
-  p.ksplit = a.ksplit == 2 ? 2 : (a.ksplit ? 1 : 0);
-  p.sat = a.sat; p.skip = a.skip;
-  p.stash = a.stash; p.stash_f16 = a.stash_f16;
-  if (a.stash && a.epi == FV_EPI_MUL_GELUP) { if ((uintptr_t)a.stash & 15) return fv_fail(FV_ERR_ARG, "gemm: MUL_GELUP's gelu(a) output must be 16-byte aligned"); }
-  else if (a.stash && a.epi != FV_EPI_GELU_GRAD && ((a.epi != FV_EPI_SWIGLU_SPLIT && a.epi != FV_EPI_SWIGLU_F16) || ((uintptr_t)a.stash & 15) || (a.stash_f16 && !a.sat)))
-    return fv_fail(FV_ERR_ARG, "gemm: stash goes with FV_EPI_SWIGLU_SPLIT / FV_EPI_SWIGLU_F16 (16-byte aligned; the fp16 form with a saturation counter)");
-  p.W8 = static_cast<const uint8_t*>(a.W8);
-  if (a.ksplit == 2) {
-    if (!a.W8 || a.K % 128 || a.lda * 2 < 3 * a.K || ((uintptr_t)a.W8 & 15)) return fv_fail(FV_ERR_ARG, "gemm: the hi + lo8 form needs W8, K %% 128 == 0 and lda >= 1.5 K");
-    if (a.f16) return fv_fail(FV_ERR_ARG, "gemm: hi + lo8 goes with bf16 hi operands");
-  } else if (a.ksplit && a.lda < 2 * a.K) return fv_fail(FV_ERR_ARG, "gemm: ksplit needs lda >= 2K");
-  // (ksplit with a K that is no multiple of 64 -- a decoder whose inter is 32 mod 64 -- goes to the register-staged kernel: every form on whole 64-element
-  // K tiles below asks for K % 64 == 0 itself, gemm_kernel walks ceil(K / 64) tiles per half and zero-fills the last one's columns past K on both operands)
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<8, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<8, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<8, 4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<8, 4, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 512 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<4, 2, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * 128));
-    FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<4, 2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 256 * 128));
   }
-  static const bool colmajor_ok = fv_ab_env("FASTVLA_NO_GEMM_COLMAJOR") == nullptr;   // A/B
-  constexpr int cm_max = 8;   // (16 measured at the headline shape in round 3: gate/up -3.5 %, split-K down +9 %, step unchanged)
-  static const bool no_asym = fv_ab_env("FASTVLA_NO_GEMM_ASYM") != nullptr;   // A/B
-  static const int min_kt_per_range = fv_ab_env("FASTVLA_GEMM_MIN_KT") ? atoi(fv_ab_env("FASTVLA_GEMM_MIN_KT")) : 16;   // A/B
-  static const int group_m_default = fv_ab_env("FASTVLA_GEMM_GROUP_M") ? atoi(fv_ab_env("FASTVLA_GEMM_GROUP_M")) : 4;   // A/B (0 = row-major walk)
-  const bool asym = !no_asym && a.M <= 8192 && a.M % 256 == 0;   // the asymmetric staging addresses row + 32 from a (clamped) base row: whole row tiles only
-  // The tail.  A problem of r >= 1 full rounds of 256-tiles plus a short last round (7B gate/up at M = 1024: 592 tiles = 2.31 rounds on 256 CUs, i.e. three
-  // rounds of time) is cut at a column: the full rounds' column panels run as they are, the remaining panels as a K-range problem of their own (one more
-  // short round + a reduce pass over those columns).  Whole column panels only; inference only (the cut depends on the row count).
-  static const bool no_tail_env = fv_ab_env("FASTVLA_NO_GEMM_TAIL") != nullptr;   // A/B
-  if (!no_tail_env && !a.no_tail && a.few_rows && a.splitk_ws && !a.norm_w && !a.stash && !a.f16 && a.ksplit != 2 && a.M % 256 == 0 && a.N % 256 == 0 &&
-      a.K % 64 == 0 && (f32out || (a.epi == FV_EPI_SWIGLU_SPLIT && a.N % 512 == 0)) && gemm_glds_tile(a) == 256) {
-    const int tmr = a.M / 256, tn = a.N / 256, tiles = tmr * tn, rem = tiles % cus, nkt = (a.ksplit ? 2 : 1) * (a.K / 64);
-    if (tiles > cus && rem > 0 && 2 * rem <= cus && rem % tmr == 0 && nkt >= 32) {
-      const int n0 = (tn - rem / tmr) * 256;   // columns [0, n0): the full rounds; [n0, N): the tail
-      const int lo = a.lo_off ? a.lo_off : a.N / 2;
-      GemmArgs a1 = a, a2 = a;
-      a1.N = n0; a1.no_tail = 1; a1.lo_off = lo;
-      a2.N = a.N - n0; a2.no_tail = 1; a2.lo_off = lo;
-      a2.W = a.W + (size_t)n0 * a.K;
-      if (a.bias) a2.bias = a.bias + n0;
-      if (f32out) {
-        a2.out = static_cast<float*>(a.out) + n0;
-        if (a.res) a2.res = static_cast<const float*>(a.res) + n0;
-      } else {
-        a2.out = static_cast<bf16_t*>(a.out) + n0 / 2;
-      }
-      const int rc = launch_gemm(a1, s);
-      return rc != FV_OK ? rc : launch_gemm(a2, s);
-    }
-  }
-  // few rows (the control loop: M = 64 B rows of the decoder at B <= 4): 64-row tiles of the register-staged kernel cut along K until the chip is covered
-  // twice, >= 4 K-tiles per range; fp32 epilogues through the same reduce kernels as the 256-tile split-K below
-  static const bool no_skinny_env = fv_ab_env("FASTVLA_NO_SKINNY_SPLITK") != nullptr;   // A/B
-  const bool no_skinny = no_skinny_env || !a.few_rows;
-  // (the SwiGLU reducer writes its lo half as bf16: the hi + lo8 form, whose consumer reads fp8 bytes there, and the fp16 form keep the one-launch
-  // epilogue -- policy 5's gate/up at 256 x 17920 x 1536 would otherwise pick 2 ranges here)
-  const bool swiglu_sk = a.epi == FV_EPI_SWIGLU_SPLIT && !a.stash && a.N % 16 == 0 && a.ksplit != 2 && !a.f16;
-  // (M <= 256, or a row count the 256-tile split-K below does not take whole: the spliced control loop's 320 B rows)
-  if (!no_skinny && a.splitk_ws && (f32out || swiglu_sk) && (a.M <= 256 || (a.M % 256 != 0 && a.M <= 1024)) && a.N % 8 == 0 && a.ksplit != 2 && !a.f16) {
-    const int tn = (a.N + BN - 1) / BN, tiles = ((a.M + 63) / 64) * tn, nkt = (a.ksplit ? 2 : 1) * ((a.K + BK - 1) / BK);
-    const int npad = tn * BN;
-    int splits = tiles < cus ? (2 * cus + tiles - 1) / tiles : 1;   // (gate/up at M = 256 is 304 tiles: it keeps the one-launch form)
-    if (splits > nkt / 4) splits = nkt / 4;
-    while (splits > 1 && (size_t)splits * a.M * npad * sizeof(float) > a.splitk_bytes) --splits;
-    if (splits > 1) {
-      p.tiles_n = tn; p.splits = splits; p.npad = npad; p.part = a.splitk_ws; p.nwg = tiles * splits;
-      hipLaunchKernelGGL(gemm_kernel<64>, dim3(p.nwg), dim3(256), 0, s, p);
-      return launch_splitk_reduce(a, splits, npad, true, 0, s);
-    }
-  }
-  // bf16 epilogues with few 64-row tiles and a long K (scratch supplied by the inference tower only): K ranges of >= 8 K-tiles until the chip is covered twice
-  if (!no_skinny && a.splitk_ws && (a.epi == FV_EPI_BIAS || a.epi == FV_EPI_BIAS_GELU || a.epi == FV_EPI_LS_RES) && !a.ksplit && !a.f16 && a.N % 8 == 0 &&
-      a.K % BK == 0 && a.K >= 24 * BK) {
-    const int tn = (a.N + BN - 1) / BN, tiles = ((a.M + 63) / 64) * tn, nkt = a.K / BK, npad = tn * BN;
-    // (<= 3/8 of the CUs: one or two observations.  B = 4 -- configs[0], the shape the oracle checks -- keeps the kernels of the large batches, so that
-    // its rows stay within one rounding of theirs: tests/test_gpu_fullsize.py, batch-row properties)
-    int splits = tiles * 8 <= cus * 3 ? (2 * cus + tiles - 1) / tiles : 1;
-    if (splits > nkt / 8) splits = nkt / 8;
-    while (splits > 1 && (size_t)splits * a.M * npad * sizeof(float) > a.splitk_bytes) --splits;
-    if (splits > 1) {
-      p.tiles_n = tn; p.splits = splits; p.npad = npad; p.part = a.splitk_ws; p.nwg = tiles * splits;
-      hipLaunchKernelGGL(gemm_kernel<64>, dim3(p.nwg), dim3(256), 0, s, p);
-      return launch_splitk_reduce(a, splits, npad, true, 0, s);
-    }
-  }
-  // split-K: fp32 output, few 256-tiles, long K, scratch supplied -> one (tile, K-range) unit per CU, then a reduce pass
-  static const bool no_splitk = fv_ab_env("FASTVLA_NO_SPLITK") != nullptr, no_g256 = fv_ab_env("FASTVLA_NO_GEMM256") != nullptr;
-  static const bool no_ragged_sk = fv_ab_env("FASTVLA_NO_GEMM_RAGGED") != nullptr;   // A/B
-  if (!no_splitk && a.splitk_ws && (f32out || (swiglu_sk && a.M % 256 == 0 && a.N % 256 == 0)) && !no_g256 && (a.M % 256 == 0 || (!no_ragged_sk && a.N % 8 == 0)) && a.K % 64 == 0 && a.N % 4 == 0 &&
-      (size_t)a.M * a.lda * 2 < ((size_t)1 << 32) && (size_t)a.N * a.K * 2 < ((size_t)1 << 32)) {
-    const int tmr = (a.M + 255) / 256;            // a ragged last row tile: staging clamps its rows, the partial-sum stores skip them
-    const int tn = (a.N + 255) / 256, tiles = tmr * tn, nkt = a.ksplit == 2 ? a.K / 64 + a.K / 128 : (a.ksplit ? 2 : 1) * (a.K / 64);
-    // K ranges per tile: the count that minimises (rounds of `cus` units, each 1 / s of a tile's K loop) + the partial sums' trip through memory
-    // (s x M x npad floats written and read back: ~0.5 of a 2048-deep K loop per range at 10 240 x 1024) -- 160 tiles (the unfrozen path's
-    // 10 240 x 896 projections) take 3 ranges = 480 units = 1.9 rounds instead of 0.6 of one
-    int splits = 1;
-    static const bool old_rule = fv_ab_env("FASTVLA_SPLITK_OLD") != nullptr;   // A/B: round 3's rule (cus / tiles ranges, only below one round)
-    if (old_rule) {
-      splits = tiles < cus ? cus / tiles : 1;
-      if (splits > 8) splits = 8;
-      while (splits > 1 && nkt / splits < 16) --splits;
-      while (splits > 1 && (size_t)splits * a.M * (tn * 256) * sizeof(float) > a.splitk_bytes) --splits;
-    } else {
-      const double tile_us = (double)nkt * 64.0 * 131072.0 / 1.0e6 / 4.0;                 // ~a 256 x 256 x (64 nkt) tile on one CU at ~4 GF/us/CU
-      const double part_us = 2.0 * (double)a.M * (tn * 256) * 4.0 / 4.0e6;               // one range's partials written + read at ~4 TB/s
-      double best = 1e30;
-      for (int sN = 1; sN <= 8; ++sN) {
-        if (sN > 1 && (nkt / sN < min_kt_per_range || (size_t)sN * a.M * (tn * 256) * sizeof(float) > a.splitk_bytes)) break;
-        const long units = (long)tiles * sN, rounds = (units + cus - 1) / cus;
-        const double t = (double)rounds * tile_us / sN + (sN > 1 ? sN * part_us : 0.0);
-        if (t < best * 0.97) { best = t; splits = sN; }
-      }
-    }
-    if (splits > 1) {
-      p.tiles_n = tn;
-      p.tiles_m = colmajor_ok && tmr <= cm_max ? tmr : 0;
-      p.tiles_mt = tmr; p.group_m = (!p.tiles_m && tn > 8) ? pick_group_m(tmr, group_m_default) : 0;
-      p.splits = splits; p.npad = tn * 256; p.part = a.splitk_ws;
-      p.nwg = tiles * splits;
-      const dim3 g2(p.nwg < cus ? p.nwg : cus / 8 * 8);
-      /* (no asymmetric-staging instance of the hi + lo8 kernel: it spills) */ if (a.ksplit == 2) hipLaunchKernelGGL((gemm256_kernel<8, 4, false, false, true>), g2, dim3(512), 2 * 512 * 128, s, p);
-      else if (a.f16 && asym) hipLaunchKernelGGL((gemm256_kernel<8, 4, true, true>), g2, dim3(512), 2 * 512 * 128, s, p);
-      else if (a.f16) hipLaunchKernelGGL((gemm256_kernel<8, 4, false, true>), g2, dim3(512), 2 * 512 * 128, s, p);
-      else if (asym) hipLaunchKernelGGL((gemm256_kernel<8, 4, true>), g2, dim3(512), 2 * 512 * 128, s, p);
-      else hipLaunchKernelGGL((gemm256_kernel<8, 4>), g2, dim3(512), 2 * 512 * 128, s, p);
-      return launch_splitk_reduce(a, splits, p.npad, false, a.ksplit == 2 ? 1 : 0, s);
-    }
-  }
-  static const bool no_pw = fv_ab_env("FASTVLA_NO_PWCONV") != nullptr;
-  if (!no_pw && !a.ksplit && !a.f16 && a.N == a.K && (a.K == 96 || a.K == 192) && a.lda == a.K && a.ldo == a.N && a.M % 128 == 0 &&
-      (a.epi == FV_EPI_BIAS || a.epi == FV_EPI_BIAS_GELU)) {
-    const int tiles = a.M / 128;
-    if (a.K == 96) {
-      constexpr int LDS = 96 * (96 * 2 + 16) + 4 * 32 * (96 * 2 + 16);
-      static bool set96 = false;
-      if (!set96) { FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pwconv_kernel<96>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); set96 = true; }
-      hipLaunchKernelGGL(pwconv_kernel<96>, dim3(tiles < 3 * cus ? tiles : 3 * cus), dim3(256), LDS, s, p);
-    } else {
-      constexpr int LDS = 192 * (192 * 2 + 16) + 4 * 32 * (192 * 2 + 16);
-      static bool set192 = false;
-      if (!set192) { FV_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pwconv_kernel<192>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS)); set192 = true; }
-      hipLaunchKernelGGL(pwconv_kernel<192>, dim3(tiles < cus ? tiles : cus), dim3(256), LDS, s, p);
-    }
-    FV_HIP_CHECK(hipGetLastError());
-    return FV_OK;
-  }
-  if (const int gt = gemm_glds_tile(a)) {
-    const int tmr = (a.M + gt - 1) / gt;        // ragged edge tiles only come back from gemm_glds_tile for fp32 epilogues
-    p.tiles_n = (a.N + gt - 1) / gt;
-    p.nwg = tmr * p.tiles_n;
-    p.tiles_m = colmajor_ok && tmr <= cm_max ? tmr : 0;
-    p.tiles_mt = tmr; p.group_m = (!p.tiles_m && p.tiles_n > 8) ? pick_group_m(tmr, group_m_default) : 0;   // (the 128-tile instance shares the kernel: two blocks per CU, 64 tiles per XCD at a time)
-    int slots = (gt == 128 ? 2 * cus : cus) / 8 * 8;   // persistent; a multiple of 8 keeps the XCD remap exact
-    if (const char* e = fv_ab_env("FASTVLA_GEMM_GRID")) { const int v = atoi(e); if (v >= 8 && gt == 256) slots = v / 8 * 8; }   // tools only
-    const int grid = p.nwg < slots ? p.nwg : slots;
-    if (gt == 256 && a.ksplit == 2) hipLaunchKernelGGL((gemm256_kernel<8, 4, false, false, true>), dim3(grid), dim3(512), 2 * 512 * 128, s, p);
-    else if (a.ksplit == 2) hipLaunchKernelGGL((gemm256_kernel<4, 2, false, false, true>), dim3(grid), dim3(256), 2 * 256 * 128, s, p);
-    else if (gt == 256 && a.f16 && asym) hipLaunchKernelGGL((gemm256_kernel<8, 4, true, true>), dim3(grid), dim3(512), 2 * 512 * 128, s, p);
-    else if (gt == 256 && a.f16) hipLaunchKernelGGL((gemm256_kernel<8, 4, false, true>), dim3(grid), dim3(512), 2 * 512 * 128, s, p);
-    else if (gt == 256 && asym) hipLaunchKernelGGL((gemm256_kernel<8, 4, true>), dim3(grid), dim3(512), 2 * 512 * 128, s, p);
-    else if (gt == 256) hipLaunchKernelGGL((gemm256_kernel<8, 4>), dim3(grid), dim3(512), 2 * 512 * 128, s, p);
-    else if (a.f16) hipLaunchKernelGGL((gemm256_kernel<4, 2, false, true>), dim3(grid), dim3(256), 2 * 256 * 128, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<4, 2>), dim3(grid), dim3(256), 2 * 256 * 128, s, p);
-    FV_HIP_CHECK(hipGetLastError());
-    return FV_OK;
-  }
-  p.tiles_n = (a.N + BN - 1) / BN;
-  // pick the row-tile height: 64-row tiles when 128-row tiles would give fewer than two blocks per CU
-  const long blocks128 = (long)((a.M + 127) / 128) * p.tiles_n;
-  if (blocks128 >= 512) {
-    p.nwg = (int)blocks128;
-    if (a.ksplit == 2) hipLaunchKernelGGL((gemm_kernel<128, false, true>), dim3(p.nwg), dim3(256), 0, s, p);
-    else if (a.f16) hipLaunchKernelGGL((gemm_kernel<128, true>), dim3(p.nwg), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gemm_kernel<128>, dim3(p.nwg), dim3(256), 0, s, p);
-  } else {
-    p.nwg = ((a.M + 63) / 64) * p.tiles_n;
-    if (a.ksplit == 2) hipLaunchKernelGGL((gemm_kernel<64, false, true>), dim3(p.nwg), dim3(256), 0, s, p);
-    else if (a.f16) hipLaunchKernelGGL((gemm_kernel<64, true>), dim3(p.nwg), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gemm_kernel<64>, dim3(p.nwg), dim3(256), 0, s, p);
-  }
-  FV_HIP_CHECK(hipGetLastError());
+  for (int i = 0; i < plan.n; ++i)
+    if (const int rc = run_launch(a, plan.launch[i], s)) return rc;
   return FV_OK;
 }
 

@@ -47,6 +47,24 @@ struct GemmArgs {
 };
 int launch_gemm(const GemmArgs& a, hipStream_t s);
 
+// What launch_gemm does with a problem.  plan_gemm makes every argument check and the whole routing decision for a device of `cus` CUs: no HIP call, no
+// allocation, no state, and pointers are tested for null and alignment only; launch_gemm asks the device for `cus` and runs the plan.  One launch, or two where
+// the tail is cut off (columns [c0, c1) each).  tests/gemm_util.py gemm_route mirrors it field for field (fv_op_gemm_plan is the tests' way in).
+enum GemmReducer { GEMM_RED_NONE = 0, GEMM_RED_F32, GEMM_RED_NORM, GEMM_RED_NORM_ROW, GEMM_RED_BF16, GEMM_RED_SWIGLU };
+enum GemmNorm { GEMM_NORM_NONE = 0, GEMM_NORM_FUSED, GEMM_NORM_SEPARATE };   // the RMSNorm of GemmArgs::norm_w: not asked, in the reducer, a launch of its own
+struct GemmLaunch {
+  int kernel;                                // row of gemm_bf16.hip's instance table (gemm_kernel_name)
+  int tile;                                  // rows of a tile: 64 / 128 (the register-staged kernel; the pointwise kernel: 128), 128 / 256 (square)
+  int tiles_n, tiles_m, tiles_mt, group_m;   // the tile walk, as the kernels' Params
+  int splits, npad, nwg, grid;               // K ranges per tile (1: one pass), the partial sums' row stride, work units, blocks
+  int reducer, norm;                         // GemmReducer (NONE: one pass), GemmNorm
+  int c0, c1;                                // the launch's columns of the problem
+};
+struct GemmPlan { int n; GemmLaunch launch[2]; };
+int plan_gemm(const GemmArgs& a, int cus, GemmPlan& plan);
+const char* gemm_kernel_name(int kernel);     // "gemm256_kernel<8,4,ASYM,F16>": the spelling of tests/gemm_util.py
+const char* gemm_reducer_name(int reducer);   // "" for GEMM_RED_NONE
+
 // fused ConvFFN pointwise half: out = res + ls * (fc2(gelu(fc1(x) + b1)) + b2); w1 [4C][C] bf16, w2p = convffn_pack_w2 layout
 bool convffn_supported(int C, int ratio);
 void convffn_pack_w2(const float* w2, float* out, int C, int hidden);

@@ -1,6 +1,7 @@
 // ops_api.hip -- op-level C entry points (include/fastvla_hip_testops.h: TEST-ONLY, built into vla-from-fastvlm_amd/testops/libfastvla_hip_testops.so, not into the product library): one kernel each, so the
 // parity tests can check every kernel of the path against the oracle on its own.  No engine state is involved.
 #include <cmath>
+#include <cstdio>
 #include <vector>
 
 #include "kernels.h"
@@ -38,6 +39,29 @@ int fv_op_gemm_norm(const void* A, int lda, const void* W, int M, int N, int K, 
   g.few_rows = few_rows;
   g.norm_w = norm_w; g.norm_y = static_cast<bf16_t*>(norm_y); g.norm_ylo = static_cast<bf16_t*>(norm_ylo); g.norm_ld = norm_ld; g.norm_eps = norm_eps;
   return fv::launch_gemm(g, static_cast<hipStream_t>(s));
+}
+// what launch_gemm would do with the problem on a device of `cus` CUs: plan_gemm's answer, no launch.  The planner reads no memory, so the operands that are
+// marked present are one aligned dummy.  Returns the number of launches written to `out` (1, or 2 with the tail cut off) or the refusal's code (negative).
+int fv_op_gemm_plan(int M, int N, int K, int lda, int ldw, int ldo, int ldr, int epilogue, int ksplit, int f16, int tn, int few_rows, int cus, size_t ws_bytes,
+                    int has_bias, int has_scale, int has_res, int has_stash, int has_norm, int has_w8, fv_gemm_plan_launch* out) {
+  alignas(16) static float mem[4];
+  const auto at = [](int present) { return present ? mem : nullptr; };
+  fv::GemmArgs g{reinterpret_cast<const bf16_t*>(mem), lda, reinterpret_cast<const bf16_t*>(mem), M, N, K, at(has_bias), at(has_scale), at(has_res), ldr, mem, ldo, epilogue, ksplit};
+  g.f16 = f16; g.tn = tn; g.ldw = ldw; g.few_rows = few_rows;
+  g.splitk_ws = at(ws_bytes != 0); g.splitk_bytes = ws_bytes;
+  g.stash = at(has_stash); g.W8 = at(has_w8);
+  g.norm_w = at(has_norm); g.norm_y = reinterpret_cast<bf16_t*>(at(has_norm)); g.norm_ld = N;
+  fv::GemmPlan plan;
+  const int rc = fv::plan_gemm(g, cus, plan);
+  if (rc != FV_OK) return rc;
+  for (int i = 0; i < plan.n; ++i) {
+    const fv::GemmLaunch& l = plan.launch[i];
+    fv_gemm_plan_launch& o = out[i];
+    snprintf(o.kernel, sizeof(o.kernel), "%s", fv::gemm_kernel_name(l.kernel));
+    snprintf(o.reducer, sizeof(o.reducer), "%s", fv::gemm_reducer_name(l.reducer));
+    o.tile = l.tile; o.tiles_m = l.tiles_m; o.group_m = l.group_m; o.splits = l.splits; o.npad = l.npad; o.grid = l.grid; o.norm = l.norm; o.c0 = l.c0; o.c1 = l.c1;
+  }
+  return plan.n;
 }
 
 int fv_op_gemm_tn(const void* A, int lda, const void* W, int ldw, int M, int N, int K, int f16, const float* bias, void* out, int ldo, void* ws,

@@ -118,6 +118,11 @@ class GemmProfile(C.Structure):
                 ("launches", C.c_int64)]
 
 
+class GemmPlanLaunch(C.Structure):
+    """fv_gemm_plan_launch (include/fastvla_hip_testops.h): one launch of what fv_op_gemm_plan answers.  Test-only."""
+    _fields_ = [("kernel", C.c_char * 40), ("reducer", C.c_char * 40)] + [(n, C.c_int) for n in ("tile", "tiles_m", "group_m", "splits", "npad", "grid", "norm", "c0", "c1")]
+
+
 class TrainTensor(C.Structure):
     _fields_ = [("name", C.c_char * 104), ("offset", C.c_int64), ("numel", C.c_int64), ("rows", C.c_int32), ("cols", C.c_int32),
                 ("bucket", C.c_int32), ("packing", C.c_int32)]
@@ -246,6 +251,7 @@ OPS_SIGNATURES = {
     "fv_op_gemm_tn": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, C.c_size_t, _vp]),
     "fv_op_gemm_splitk": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _vp, C.c_size_t, _vp]),
     "fv_op_gemm_norm": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, C.c_size_t, _i, _vp, _vp, _vp, _i, _f, _vp]),
+    "fv_op_gemm_plan": (_i, [_i] * 13 + [C.c_size_t] + [_i] * 6 + [C.POINTER(GemmPlanLaunch)]),
     "fv_op_dwconv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "fv_op_stem_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "fv_op_stem_mfma": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
